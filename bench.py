@@ -19,6 +19,9 @@ Other BASELINE configs through flags (same JSON line, `config.workload` names wh
     cfg4  --scaling strong --total 1000000 --dim 960     (GIST-shaped; `splitarray` shards: 125 000 vectors per GPU at N = 8)
     cfg5  --vectors 12500000                              (weak scaling, 12.5 M vectors per GPU generated on the device, 13 resident chunks)
 
+--dump-outputs DIR writes what the last timed step returned (codes, objective sums, ILS counters) as DIR/*.npy; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output (dump_outputs).
+
 Prints ONE JSON line on rank 0 with the driver's contract fields plus
   `roofline`         dominant kernel (the ICM node update): algorithmic HBM bytes / HIP-event launch time vs 8 TB/s, the LDS-side
                      gather rate vs the guide's 150 TB/s, the M1 compulsory-bytes fraction, PMC traffic when the committed
@@ -101,11 +104,44 @@ def parse():
                    help="after the timed region keep running identical UNTIMED steps until the GPU legs have lasted this long "
                         "(lets a 5 s utilisation sampler see the device busy; reported as steady_state)")
     p.add_argument("--multi-leg", action="store_true", help="also time the single-process multi-GPU entry point (lsq_multi_*) on all visible devices")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned (codes, objective sums, ILS counters) as DIR/<name>.npy "
+                        "in float32 / float64, at most 64 MB in all (see dump_outputs)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def lib_hash(path):
     return hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]
+
+
+DUMP_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(out_dir, dBs, sums, stats, n, m, goff, rank, world):
+    """--dump-outputs: what the timed path (encode_icm_dev) returned to its caller in the last timed step, as DIR/<name>.npy:
+      codes.npy      (1, rows, m) float32   the 0-based codes of dBs
+      obj_sums.npy   (1,) float64           the sum of the vectors' costs
+      ils_stats.npy  (I, 2) float64         the per-ILS-iteration counters
+    When all n rows do not fit this rank's share of 64 MB (at 4 B per code), `codes` holds a fixed seeded sample of rows, ascending, and
+    code_rows.npy (rows,) float64 their global indices.  Several ranks: every name gets the suffix _rank<r>.  -> {name: shape}"""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    budget = DUMP_BYTES // world - 4096
+    arrays = {"obj_sums": np.asarray(sums, dtype=np.float64), "ils_stats": np.asarray(stats, dtype=np.float64)}
+    if n * m * 4 <= budget:
+        arrays["codes"] = dBs.cpu().numpy().astype(np.float32)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=budget // (4 * m + 8), replace=False))
+        arrays["codes"] = dBs[:, torch.from_numpy(rows).to(dBs.device)].cpu().numpy().astype(np.float32)
+        arrays["code_rows"] = (rows + goff).astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    return {name + suffix: list(a.shape) for name, a in arrays.items()}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -517,6 +553,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     tm = eng.timings()
+    dumped = dump_outputs(args.dump_outputs, dBs, sums, stats, n, m, goff, rank, world) if args.dump_outputs else None
 
     # ---- per-rank roofline numbers (every rank computes its own; rank 0 reports all of them) -------------------------
     cs = 8 if m <= 8 else 16
@@ -627,6 +664,8 @@ def main():
         }
         if args.tuning and args.ablation:
             out["INVALID"] = "ablation %d: timing-only variant, results are garbage" % args.ablation
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
 
     # ---- extra legs: rank 0 of a single-GPU run only -----------------------------------------------------------------------
     if rank == 0 and world == 1 and not args.no_sample_parity:      # copies two 256-row slices only: also on the 12.5 M-vector cfg5 share

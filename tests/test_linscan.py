@@ -1,11 +1,22 @@
 """Row 8(f)-1: ADC linear scan.  This half of the path IS pinned by the real reference: oracle/_ref holds
 src/linscan/cpp/linscan_aqd_pairwise_byte.cpp compiled from the reference's own source with its own flags
 (oracle/Makefile `ref`).  lsq_linscan_aqd_query_extra_byte must reproduce it bit for bit -- distances AND ids,
-including ties -- on the same inputs.  Host code: runs without a GPU."""
+including ties -- on the same inputs.  Host code: runs without a GPU.
+
+The reference build's outputs on these seeded inputs are stored in tests/golden/linscan/reference_outputs.npz
+(tests/golden/make_linscan_golden.py), so the comparison does not depend on the reference sources being present;
+where oracle/_ref was built, the live build is held to the stored outputs as well."""
+import hashlib
+import os
+
 import numpy as np
 import pytest
 
 H = 256
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "linscan", "reference_outputs.npz")
+REF_CASES = [(5000, 37, 32, 7, 100, False), (3000, 16, 128, 8, 1000, False), (2000, 20, 16, 4, 50, True), (64, 5, 8, 2, 64, True),
+             (1000, 3, 24, 16, 10, False)]
+RECALL_CASE = (3000, 40, 32, 8, 100, False)             # test_reference_shaped_linscan_and_recall, rng seed 9
 
 
 def _case(rng, n, nq, d, m, ties=False):
@@ -21,6 +32,29 @@ def _case(rng, n, nq, d, m, ties=False):
     return codes, Q, K, dbnorms
 
 
+def case_key(n, nq, d, m, knn, ties):
+    return "n%d_nq%d_d%d_m%d_k%d%s" % (n, nq, d, m, knn, "_ties" if ties else "")
+
+
+def inputs_digest(codes, Q, K, dbnorms):
+    h = hashlib.sha256()
+    for a in (codes, Q, K, dbnorms):
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def reference_outputs(oracle, key, codes, Q, K, dbnorms, m, knn):
+    """What the reference's own build returns on these inputs -> dists (nq, knn) f32, ids (nq, knn) int32 1-based: the stored outputs,
+    checked against oracle/_ref where it was built."""
+    z = np.load(GOLDEN)
+    assert str(z[key + "_inputs"]) == inputs_digest(codes, Q, K, dbnorms), "the seeded inputs of %s are not those the fixture was made from" % key
+    dref, iref = z[key + "_dists"], z[key + "_idx"]
+    if oracle.ref_linscan_path() is not None:
+        dlive, ilive = oracle.ref_linscan(codes, Q, K, dbnorms, m, H, knn)
+        assert np.array_equal(dlive, dref) and np.array_equal(ilive, iref), "oracle/_ref differs from tests/golden/linscan/reference_outputs.npz (%s)" % key
+    return dref, iref
+
+
 def _ours(lsq, codes, Q, K, dbnorms, m, knn, nthreads=0):
     L = lsq._lib.load()
     nq, d = Q.shape
@@ -31,14 +65,11 @@ def _ours(lsq, codes, Q, K, dbnorms, m, knn, nthreads=0):
     return dists, idx
 
 
-@pytest.mark.parametrize("n,nq,d,m,knn,ties", [(5000, 37, 32, 7, 100, False), (3000, 16, 128, 8, 1000, False),
-                                              (2000, 20, 16, 4, 50, True), (64, 5, 8, 2, 64, True), (1000, 3, 24, 16, 10, False)])
+@pytest.mark.parametrize("n,nq,d,m,knn,ties", REF_CASES)
 def test_matches_reference_build(lsq, oracle, n, nq, d, m, knn, ties):
-    if oracle.ref_linscan_path() is None:
-        pytest.skip("oracle/_ref not built (reference sources absent and no prebuilt .so)")
     rng = np.random.default_rng(n + d)
     codes, Q, K, dbnorms = _case(rng, n, nq, d, m, ties)
-    dref, iref = oracle.ref_linscan(codes, Q, K, dbnorms, m, H, knn)
+    dref, iref = reference_outputs(oracle, case_key(n, nq, d, m, knn, ties), codes, Q, K, dbnorms, m, knn)
     for nt in (1, 3):
         dists, idx = _ours(lsq, codes, Q, K, dbnorms, m, knn, nthreads=nt)
         assert np.array_equal(dists, dref), "max |diff| %g" % np.abs(dists - dref).max()
@@ -63,15 +94,14 @@ def test_against_float64_brute_force(lsq):
 
 def test_reference_shaped_linscan_and_recall(lsq, oracle):
     rng = np.random.default_rng(9)
-    n, nq, d, m, knn = 3000, 40, 32, 8, 100
+    n, nq, d, m, knn, _ = RECALL_CASE
     codes, Q, K, dbnorms = _case(rng, n, nq, d, m)
     C = [np.ascontiguousarray(K[j * H:(j + 1) * H].T) for j in range(m)]
     R = np.eye(d, dtype=np.float32)
     dists, res = lsq.linscan_lsq(codes.T, Q.T, C, dbnorms, R, knn)             # Julia shapes: B (m,n), X (d,nq)
     assert dists.shape == (knn, nq) and res.shape == (knn, nq) and res.dtype == np.int32
-    if oracle.ref_linscan_path() is not None:
-        dref, iref = oracle.ref_linscan(codes, Q, K, dbnorms, m, H, knn)
-        assert np.array_equal(res.T, iref) and np.array_equal(dists.T, dref)
+    dref, iref = reference_outputs(oracle, case_key(*RECALL_CASE), codes, Q, K, dbnorms, m, knn)
+    assert np.array_equal(res.T, iref) and np.array_equal(dists.T, dref)
     # eval_recall: ground truth = our own first neighbour -> recall@1 = 1; a shifted truth -> recall@1 = 0
     rec = lsq.eval_recall(res[0], res, knn)
     assert rec.shape == (knn,) and rec[0] == 1.0 and np.all(np.diff(rec) >= 0)
