@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 600
+#define LSQ_VERSION 700
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -264,7 +264,30 @@ LSQ_API int lsq_linscan_dev(lsq_ctx *ctx, float *d_dists, int *d_idx, const uint
  * lists by (distance, id)): the result of ONE scan of the whole database, ties across shards included. */
 LSQ_API int lsq_multi_linscan(lsq_multi *mg, float *dists, int *idx, const unsigned char *codes, const float *queries, const float *codebooks,
                               const float *dbnorms, int nqueries, int ncodes, int m, int h, int d, int nn);
-/* What the device scan did since the last lsq_reset_timings (times only with option "profile" = 1). */
+/* ---- (3c) the reference's other scan: PQ / OPQ codes (since v700) -------------------------------------------------------------------------
+ * linscan_aqd_query(dists, res, codes, centers, queries, N, NQ, B, K, dim1codes, dim1queries, subdim)
+ *   src/linscan/cpp/linscan_aqd.cpp:37-114, bound by linscan_pq / linscan_opq at src/linscan/Linscan.jl:5-43 (linscan_opq = linscan_pq of R'X).
+ * The reference's argument list and types, host code (std::thread workers).  m = B/8 sub-spaces of h = 256 centres each.
+ *   codes    [N][dim1codes] uint8 0-based (Julia B, m x n: dim1codes = m); only the first m bytes of a row are read.
+ *   centers  [m][256][subdim] = cat(3, C...) (C[k] subdim x 256)  -> c_{k,r}[s] at centers[(k*256 + r)*subdim + s].
+ *   queries  [NQ][dim1queries] (Julia X, d x nq: dim1queries = d); sub-space k reads q[k*subdim .. k*subdim + subdim).
+ *   table[k*256 + r] = ((0 + e_0*e_0) + e_1*e_1) + ..., e_s = c_{k,r}[s] - q[k*subdim + s]        (f32, s ascending, no FMA)
+ *   dist(i)          = ((0 + table[0*256 + b_i0]) + table[1*256 + b_i1]) + ...                    (k ascending, no norm term)
+ * Outputs (caller-allocated): dists [NQ][K] f32 ascending; res [NQ][K] uint32, 0-BASED ids (linscan_pq adds 1 on the Julia side).  The K smallest
+ * (dist, id) pairs in lexicographic order (ties: smaller id first), bit-identical to the reference build; NaN distances sort last.
+ * Requires B % 8 == 0, 1 <= B/8 <= dim1codes, subdim >= 1, (B/8)*subdim <= dim1queries, 1 <= K <= N, non-null pointers (NQ > 0). */
+LSQ_API int lsq_linscan_aqd_query(float *dists, uint32_t *res, const uint8_t *codes, const float *centers, const float *queries, int N,
+                                  uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim);
+/* The same scan ON THE DEVICE (csrc/lsq_adc.hip: the LSQ scan's kernels with the sub-space squared-distance tables and no norm term).  Same
+ * argument list behind a context, same results bit for bit as lsq_linscan_aqd_query, 0-based uint32 ids included.  Device limits of lsq_linscan:
+ * B/8 <= 16 (LSQ_EINVAL beyond), NQ <= 2^31 - 1.  Options "linscan_exhaustive" / "linscan_rank" and lsq_get_linscan_stats cover it.
+ *   lsq_linscan_pq      host buffers (uploaded, searched, downloaded);
+ *   lsq_linscan_pq_dev  device buffers, the layouts above. */
+LSQ_API int lsq_linscan_pq(lsq_ctx *ctx, float *dists, uint32_t *res, const uint8_t *codes, const float *centers, const float *queries, int N,
+                           uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim);
+LSQ_API int lsq_linscan_pq_dev(lsq_ctx *ctx, float *d_dists, uint32_t *d_res, const uint8_t *d_codes, const float *d_centers, const float *d_queries,
+                               int N, uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim);
+/* What the device scans (LSQ and PQ) did since the last lsq_reset_timings (times only with option "profile" = 1). */
 typedef struct lsq_linscan_stats {
     int64_t queries, codes;          /* queries searched (accumulated); database size of the last call */
     int64_t candidates;              /* (dist, id) pairs written to memory: the lists the selection sorted */

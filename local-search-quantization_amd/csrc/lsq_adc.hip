@@ -23,6 +23,10 @@
 //           databases, massive ties) is redone by the exhaustive road -- every distance written, sorted -- and small databases take that
 //           road directly.  rocPRIM's segmented radix sort (hipcub) does the sorting.
 // NaN distances (the reference's partial_sort has no defined order for them) sort after everything else here.
+//
+// The reference's other scan, linscan_aqd_query for PQ / OPQ codes (src/linscan/cpp/linscan_aqd.cpp:37-114; lsq_adc_search_pq), runs on the same
+// machinery: adc_pq_lut_kernel builds the sub-space squared-distance tables in the same layout, adc_scan_kernel drops the norm term (NORM = false)
+// and reads code rows dim1codes bytes apart, and the gather hands out 0-based ids.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -98,6 +102,55 @@ __global__ __launch_bounds__(256) void adc_lut_kernel(const float *__restrict__ 
     }
 }
 
+// PQ / OPQ (linscan_aqd.cpp:66-74): LUT[tile][k h + r][s] = ((0 + d_0 d_0) + d_1 d_1) + ..., d_t = C[k][r][t] - q[k subdim + t] of query
+// qid(tile * QT + s), t ascending.  One block per (sub-space k, query tile), one thread per centre r: the tile's sub-vectors are staged in LDS
+// as [t][QT] and read as broadcast 16-byte words, as adc_lut_kernel reads 2 q.  h d multiply-adds per query (m h d for the LSQ table).
+template <int QT>
+__global__ __launch_bounds__(LSQ_H) void adc_pq_lut_kernel(const float *__restrict__ Q, const float *__restrict__ C, const int *__restrict__ qsel,
+                                                           int q0, int nqb, int qstride, int subdim, int entries, float *__restrict__ LUT) {
+    extern __shared__ __attribute__((aligned(16))) float qs[];      // [kc][QT]: the tile's sub-vectors of sub-space k
+    const int tile = blockIdx.y, k = blockIdx.x, e = k * LSQ_H + threadIdx.x;
+    float acc[QT];
+#pragma unroll
+    for (int s = 0; s < QT; ++s) acc[s] = 0.0f;
+    const float *c = C + (int64_t)e * subdim;
+    const bool vec = (subdim & 3) == 0 && (((uintptr_t)C & 15) == 0);
+    auto step = [&](int t, float ct) {
+#pragma unroll
+        for (int s = 0; s < QT; s += 4) {
+            const f32x4 qv = *reinterpret_cast<const f32x4 *>(qs + t * QT + s);
+            const f32x4 df = (f32x4){ct, ct, ct, ct} - qv;            // c - q, rounded; then the square, rounded; then the add (no FMA)
+            const f32x4 sq = df * df;
+            acc[s] = acc[s] + sq.x;
+            acc[s + 1] = acc[s + 1] + sq.y;
+            acc[s + 2] = acc[s + 2] + sq.z;
+            acc[s + 3] = acc[s + 3] + sq.w;
+        }
+    };
+    for (int t0 = 0; t0 < subdim; t0 += ADC_KC) {
+        const int kc = subdim - t0 < ADC_KC ? subdim - t0 : ADC_KC;
+        __syncthreads();
+        for (int t = threadIdx.x; t < QT * kc; t += LSQ_H) {
+            const int s = t / kc, j = t % kc, slot = tile * QT + s;      // consecutive threads read consecutive dimensions of one query
+            float v = 0.0f;
+            if (slot < nqb) v = Q[(int64_t)(qsel ? qsel[slot] : q0 + slot) * qstride + (int64_t)k * subdim + t0 + j];
+            qs[j * QT + s] = v;
+        }
+        __syncthreads();
+        if (vec) {
+            for (int j = 0; j < kc; j += 4) {                       // subdim % 4 == 0 and ADC_KC % 4 == 0: whole quads
+                const f32x4 cv = *reinterpret_cast<const f32x4 *>(c + t0 + j);
+                step(j, cv.x); step(j + 1, cv.y); step(j + 2, cv.z); step(j + 3, cv.w);
+            }
+        } else {
+            for (int j = 0; j < kc; ++j) step(j, c[t0 + j]);
+        }
+    }
+    float *o = LUT + ((int64_t)tile * entries + e) * QT;
+#pragma unroll
+    for (int s = 0; s < QT; s += 4) *reinterpret_cast<f32x4 *>(o + s) = (f32x4){acc[s], acc[s + 1], acc[s + 2], acc[s + 3]};
+}
+
 constexpr int ADC_STAGE = 64;                // staged (dist, id) pairs per wave
 struct AdcStage {
     uint64_t rec[ADC_STAGE];
@@ -107,14 +160,14 @@ struct AdcStage {
 };
 
 // MODE 0: append (key << idbits | id) of every distance <= tau to the query's candidate list;  MODE 1: write every (key << idbits | id) of the strided
-// subset i = s * stride, s < ns, to out[slot * ns + s];  MODE 2: the same subset, keys only (u32).  MW > 0: m = 4 MW, codes read as dwords;
-// MW = 0: any m, byte reads.
+// subset i = s * stride, s < ns, to out[slot * ns + s];  MODE 2: the same subset, keys only (u32).  MW > 0: m = 4 MW = cstride, codes read as
+// dwords; MW = 0: any m, byte reads of rows cstride bytes apart.  NORM: + dbnorms[i] (LSQ); without it the distance is the table sum alone (PQ).
 // A lane owns one code and four queries per step.  The codes of the NEXT batch of U steps are requested before the current batch is walked: a
 // code's bytes come from L2 (~1 us away), its 16-byte table reads from LDS (~0.1 us), and without the prefetch the walk waits for L2 once per
 // code (measured: 7 of 28 TB/s of LDS gathers).
-template <int QT, int MODE, int MW>
+template <int QT, int MODE, int MW, bool NORM>
 __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void adc_scan_kernel(const float *__restrict__ LUT, const uint8_t *__restrict__ codes,
-                                                                    const float *__restrict__ dbnorms, int n, int m, int nqb, int stride, int ns,
+                                                                    const float *__restrict__ dbnorms, int n, int m, int cstride, int nqb, int stride, int ns,
                                                                     int per_block, const uint32_t *__restrict__ tau, unsigned *__restrict__ count,
                                                                     int cap, uint64_t *__restrict__ out, int idbits) {
     extern __shared__ __attribute__((aligned(16))) float lut[];      // [m * 256][QT], then the emission staging of MODE 0 (AdcStage)
@@ -183,7 +236,7 @@ __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_e
 #pragma unroll
                 for (int t = 0; t < CW; ++t) bt.w[u][t] = cp[t];
             }
-            bt.nrm[u] = dbnorms[i];
+            if (NORM) bt.nrm[u] = dbnorms[i];
         }
     };
     Batch cur, nxt;
@@ -215,11 +268,15 @@ __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_e
                     for (int j = 0; j < 4 * CW; ++j) acc = acc + v[g][j];
                 } else {
                     const int64_t i = (int64_t)(s < last ? s : first) * (MODE == 0 ? 1 : stride);
-                    const uint8_t *cp = codes + i * m;
+                    const uint8_t *cp = codes + i * cstride;
                     for (int j = 0; j < m; ++j) acc = acc + lut4[(j * LSQ_H + (int)cp[j]) * NQ + qq];
                 }
-                const float nrm = cur.nrm[u0 + g];
-                dist[g] = acc + (f32x4){nrm, nrm, nrm, nrm};
+                if constexpr (NORM) {
+                    const float nrm = cur.nrm[u0 + g];
+                    dist[g] = acc + (f32x4){nrm, nrm, nrm, nrm};
+                } else {
+                    dist[g] = acc;
+                }
             }
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -343,15 +400,16 @@ __global__ void adc_segments_kernel(const unsigned *__restrict__ count, int nqb,
     if (fail) fail[slot] = bad ? 1 : 0;
 }
 
+// ids leave as (record id 1 .. n) - id_base: 1-based for the LSQ scan (id_base 0), 0-based for the PQ scan (id_base 1)
 __global__ void adc_gather_kernel(const uint64_t *__restrict__ sorted, const int *__restrict__ fail, const int *__restrict__ qsel, int q0, int nqb,
-                                  int cap, int nn, float *__restrict__ dists, int *__restrict__ idx, int idbits) {
+                                  int cap, int nn, float *__restrict__ dists, int *__restrict__ idx, int idbits, int id_base) {
     const int slot = blockIdx.y;
     if (fail && fail[slot]) return;
     const int64_t q = qsel ? qsel[slot] : q0 + slot;
     for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < nn; r += gridDim.x * blockDim.x) {
         const uint64_t rec = sorted[(int64_t)slot * cap + r];
         dists[q * nn + r] = adc_unkey((uint32_t)(rec >> idbits));
-        idx[q * nn + r] = (int)(uint32_t)(rec & ((1ull << idbits) - 1ull));
+        idx[q * nn + r] = (int)((uint32_t)(rec & ((1ull << idbits) - 1ull)) - (uint32_t)id_base);
     }
 }
 
@@ -376,10 +434,22 @@ void lsq_adc_free(lsq_adc_state *st) {
 
 namespace {
 
+// What one call searches.  LSQ (dbnorms set): K = [m h][d] codebooks, tables -2<q, c>, + dbnorms[i], 1-based ids out.  PQ / OPQ (dbnorms null):
+// K = [m][h][d] sub-space centres (d = subdim), squared-distance tables, no norm term, 0-based ids out.
+struct AdcInput {
+    const uint8_t *codes; int cstride;       // [n][cstride] u8 0-based, the first m bytes of a row used
+    const float *Q; int qstride;             // query rows, qstride floats apart
+    const float *K;
+    const float *dbnorms;
+    int n, m, d;
+    bool pq() const { return dbnorms == nullptr; }
+};
+
 template <int QT, int MODE>
-int launch_scan(hipStream_t s, const float *LUT, const uint8_t *codes, const float *dbnorms, int n, int m, int nqb, int stride, int ns,
-                const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits) {
+int launch_scan(hipStream_t s, const float *LUT, const AdcInput &in, int nqb, int stride, int ns, const uint32_t *tau, unsigned *count, int cap,
+                uint64_t *out, int idbits) {
     const int tiles = (nqb + QT - 1) / QT;
+    const int n = in.n, m = in.m;
     const int total = MODE == 0 ? n : ns;
     if (tiles == 0 || total == 0) return LSQ_OK;
     // enough blocks to fill the chip a few times over, ranges long enough that the table load (m KiB per query) is amortised
@@ -392,34 +462,46 @@ int launch_scan(hipStream_t s, const float *LUT, const uint8_t *codes, const flo
     per_block = (per_block + 255) & ~255;
     ranges = (total + per_block - 1) / per_block;
     const size_t lds = sizeof(float) * (size_t)m * LSQ_H * QT + (MODE == 0 ? sizeof(AdcStage) * (ADC_SCAN_THREADS / 64) : 0);
-    const bool words = (m % 4 == 0) && (((uintptr_t)codes & 3) == 0);
+    const bool words = (m % 4 == 0) && in.cstride == m && (((uintptr_t)in.codes & 3) == 0);
     const dim3 grid((unsigned)tiles, (unsigned)ranges), block(ADC_SCAN_THREADS);
-#define ADC_LAUNCH(MWV)                                                                                                                     \
+#define ADC_LAUNCH(MWV, NORMV)                                                                                                              \
     do {                                                                                                                                    \
-        LSQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&adc_scan_kernel<QT, MODE, MWV>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)lds));                                                                                             \
-        hipLaunchKernelGGL((adc_scan_kernel<QT, MODE, MWV>), grid, block, lds, s, LUT, codes, dbnorms, n, m, nqb, stride, ns, per_block, tau,  \
-                           count, cap, out, idbits);                                                                                                \
+        LSQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&adc_scan_kernel<QT, MODE, MWV, NORMV>),                                  \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                                  \
+        hipLaunchKernelGGL((adc_scan_kernel<QT, MODE, MWV, NORMV>), grid, block, lds, s, LUT, in.codes, in.dbnorms, n, m, in.cstride, nqb,   \
+                           stride, ns, per_block, tau, count, cap, out, idbits);                                                            \
     } while (0)
-    if (words && m == 4) ADC_LAUNCH(1);
-    else if (words && m == 8) ADC_LAUNCH(2);
-    else if (words && m == 12) ADC_LAUNCH(3);
-    else if (words && m == 16) ADC_LAUNCH(4);
-    else ADC_LAUNCH(0);
+#define ADC_LAUNCH_MW(NORMV)                      \
+    do {                                          \
+        if (words && m == 4) ADC_LAUNCH(1, NORMV);       \
+        else if (words && m == 8) ADC_LAUNCH(2, NORMV);  \
+        else if (words && m == 12) ADC_LAUNCH(3, NORMV); \
+        else if (words && m == 16) ADC_LAUNCH(4, NORMV); \
+        else ADC_LAUNCH(0, NORMV);                \
+    } while (0)
+    if (in.pq()) ADC_LAUNCH_MW(false);
+    else ADC_LAUNCH_MW(true);
+#undef ADC_LAUNCH_MW
 #undef ADC_LAUNCH
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }
 
 template <int QT>
-int launch_lut(hipStream_t s, const float *Q, const float *K, const int *qsel, int q0, int nqb, int d, int m, float *LUT) {
-    const int tiles = (nqb + QT - 1) / QT, entries = m * LSQ_H;
+int launch_lut(hipStream_t s, const AdcInput &in, const int *qsel, int q0, int nqb, float *LUT) {
+    const int tiles = (nqb + QT - 1) / QT, entries = in.m * LSQ_H, d = in.d;
     if (tiles == 0) return LSQ_OK;
     const int kc = d < ADC_KC ? d : ADC_KC;
     const size_t lds = sizeof(float) * (size_t)QT * kc;
-    LSQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&adc_lut_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((adc_lut_kernel<QT>), dim3((unsigned)((entries + 255) / 256), (unsigned)tiles), dim3(256), lds, s, Q, K, qsel, q0, nqb, d,
-                       entries, LUT);
+    if (in.pq()) {
+        LSQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&adc_pq_lut_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((adc_pq_lut_kernel<QT>), dim3((unsigned)in.m, (unsigned)tiles), dim3(LSQ_H), lds, s, in.Q, in.K, qsel, q0, nqb, in.qstride,
+                           d, entries, LUT);
+    } else {
+        LSQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&adc_lut_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((adc_lut_kernel<QT>), dim3((unsigned)((entries + 255) / 256), (unsigned)tiles), dim3(256), lds, s, in.Q, in.K, qsel, q0,
+                           nqb, d, entries, LUT);
+    }
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }
@@ -455,9 +537,9 @@ Plan make_plan(int n, int nn, int force_exhaustive) {
 }
 
 template <int QT>
-int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const uint8_t *codes, const float *Q, const float *K, const float *dbnorms,
-              const int *qsel, int q0, int nqb, int n, int m, int d, int nn, const Plan &P, int *h_fail, lsq_linscan_stats *stats, bool timed) {
-    const int entries = m * LSQ_H, tiles = (nqb + QT - 1) / QT;
+int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const AdcInput &in, const int *qsel, int q0, int nqb, int nn, const Plan &P,
+              int *h_fail, lsq_linscan_stats *stats, bool timed) {
+    const int n = in.n, entries = in.m * LSQ_H, tiles = (nqb + QT - 1) / QT, id_base = in.pq() ? 1 : 0;
     int idbits = 1;                                   // ids 1 .. n: the records are (distance key << idbits | id), sorted on their 32 + idbits bits
     while (idbits < 32 && ((uint64_t)n >> idbits) != 0) ++idbits;
     LSQ_TRY(st->lut.ensure(sizeof(float) * (size_t)tiles * entries * QT));
@@ -465,7 +547,7 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ui
     LSQ_TRY(st->fail.ensure(sizeof(int) * (size_t)nqb));
     int *begin = st->seg.as<int>(), *end = begin + nqb;
     if (timed) LSQ_HIP(hipEventRecord(st->ev[0], s));
-    LSQ_TRY(launch_lut<QT>(s, Q, K, qsel, q0, nqb, d, m, st->lut.as<float>()));
+    LSQ_TRY(launch_lut<QT>(s, in, qsel, q0, nqb, st->lut.as<float>()));
     if (timed) LSQ_HIP(hipEventRecord(st->ev[1], s));
     const unsigned gblocks = (unsigned)((nqb + 255) / 256);
     int seg_len;
@@ -474,12 +556,12 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ui
         LSQ_TRY(st->keys_a.ensure(sizeof(uint64_t) * (size_t)nqb * n));
         LSQ_TRY(st->keys_b.ensure(sizeof(uint64_t) * (size_t)nqb * n));
         if (timed) { LSQ_HIP(hipEventRecord(st->ev[2], s)); }
-        LSQ_TRY((launch_scan<QT, 1>(s, st->lut.as<float>(), codes, dbnorms, n, m, nqb, 1, n, nullptr, nullptr, n, st->keys_a.as<uint64_t>(), idbits)));
+        LSQ_TRY((launch_scan<QT, 1>(s, st->lut.as<float>(), in, nqb, 1, n, nullptr, nullptr, n, st->keys_a.as<uint64_t>(), idbits)));
         if (timed) LSQ_HIP(hipEventRecord(st->ev[3], s));
         hipLaunchKernelGGL(adc_segments_kernel, dim3(gblocks), dim3(256), 0, s, (const unsigned *)nullptr, nqb, n, nn, begin, end, (int *)nullptr);
         LSQ_TRY(sort_segments(st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), (int64_t)nqb * n, nqb, begin, end, 32 + idbits));
         hipLaunchKernelGGL(adc_gather_kernel, dim3((unsigned)((nn + 255) / 256 < 64 ? (nn + 255) / 256 : 64), (unsigned)nqb), dim3(256), 0, s,
-                           st->keys_b.as<uint64_t>(), (const int *)nullptr, qsel, q0, nqb, n, nn, dists, idx, idbits);
+                           st->keys_b.as<uint64_t>(), (const int *)nullptr, qsel, q0, nqb, n, nn, dists, idx, idbits, id_base);
         if (stats) stats->candidates += (int64_t)nqb * n;
     } else {
         seg_len = P.cap;
@@ -489,18 +571,18 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ui
         LSQ_TRY(st->tau.ensure(sizeof(uint32_t) * (size_t)nqb));
         LSQ_TRY(st->count.ensure(sizeof(unsigned) * (size_t)nqb));
         // sample -> thresholds
-        LSQ_TRY((launch_scan<QT, 2>(s, st->lut.as<float>(), codes, dbnorms, n, m, nqb, P.stride, P.ns, nullptr, nullptr, P.ns, st->keys_b.as<uint64_t>(), idbits)));
+        LSQ_TRY((launch_scan<QT, 2>(s, st->lut.as<float>(), in, nqb, P.stride, P.ns, nullptr, nullptr, P.ns, st->keys_b.as<uint64_t>(), idbits)));
         hipLaunchKernelGGL(adc_rank_select_kernel, dim3((unsigned)nqb), dim3(256), 0, s, st->keys_b.as<uint32_t>(), P.r, st->tau.as<uint32_t>());
         LSQ_HIP(hipMemsetAsync(st->count.p, 0, sizeof(unsigned) * (size_t)nqb, s));
         if (timed) LSQ_HIP(hipEventRecord(st->ev[2], s));
         // the scan proper
-        LSQ_TRY((launch_scan<QT, 0>(s, st->lut.as<float>(), codes, dbnorms, n, m, nqb, 1, n, st->tau.as<uint32_t>(), st->count.as<unsigned>(), P.cap,
+        LSQ_TRY((launch_scan<QT, 0>(s, st->lut.as<float>(), in, nqb, 1, n, st->tau.as<uint32_t>(), st->count.as<unsigned>(), P.cap,
                                     st->keys_a.as<uint64_t>(), idbits)));
         if (timed) LSQ_HIP(hipEventRecord(st->ev[3], s));
         hipLaunchKernelGGL(adc_segments_kernel, dim3(gblocks), dim3(256), 0, s, st->count.as<unsigned>(), nqb, P.cap, nn, begin, end, st->fail.as<int>());
         LSQ_TRY(sort_segments(st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), (int64_t)nqb * P.cap, nqb, begin, end, 32 + idbits));
         hipLaunchKernelGGL(adc_gather_kernel, dim3((unsigned)((nn + 255) / 256 < 64 ? (nn + 255) / 256 : 64), (unsigned)nqb), dim3(256), 0, s,
-                           st->keys_b.as<uint64_t>(), st->fail.as<int>(), qsel, q0, nqb, P.cap, nn, dists, idx, idbits);
+                           st->keys_b.as<uint64_t>(), st->fail.as<int>(), qsel, q0, nqb, P.cap, nn, dists, idx, idbits, id_base);
         LSQ_HIP(hipMemcpyAsync(h_fail, st->fail.p, sizeof(int) * (size_t)nqb, hipMemcpyDeviceToHost, s));
         if (stats) {
             std::vector<unsigned> hc((size_t)nqb);
@@ -526,20 +608,18 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ui
     return LSQ_OK;
 }
 
-}  // namespace
-
 // All pointers are device pointers.  force_exhaustive: test hook (every query by the exhaustive road).
-int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const uint8_t *codes, const float *Q, const float *K,
-                   const float *dbnorms, int nq, int n, int m, int d, int nn, int force_exhaustive, int sample_override, lsq_linscan_stats *stats,
-                   int timed) {
+int adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const AdcInput &in, int nq, int nn, int force_exhaustive, int sample_override,
+               lsq_linscan_stats *stats, int timed) {
     if (!*pst) *pst = new lsq_adc_state();
     lsq_adc_state *st = *pst;
+    const int n = in.n;
     if (timed) for (hipEvent_t &e : st->ev) if (!e) LSQ_HIP(hipEventCreate(&e));
     Plan P = make_plan(n, nn, force_exhaustive);
     if (!P.exhaustive && sample_override > 0) {      // test hook: a deliberately wrong threshold rank (forces the fallback road)
         P.r = sample_override < P.ns ? sample_override : P.ns;
     }
-    const bool wide = m <= 8;                        // 16 queries per block up to m = 8 (128 KiB of tables), 8 above
+    const bool wide = in.m <= 8;                     // 16 queries per block up to m = 8 (128 KiB of tables), 8 above
     const int64_t per_query = P.exhaustive ? n : (P.cap > P.ns ? P.cap : P.ns);
     // batches of queries: two key buffers of per_query entries each, at most ~2 GiB apiece, and hipcub counts items in int
     int64_t qb = (int64_t)(1u << 28) / per_query;
@@ -551,8 +631,8 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
     for (int q0 = 0; q0 < nq; q0 += (int)qb) {
         const int nqb = (int)std::min<int64_t>(qb, nq - q0);
         h_fail.assign((size_t)nqb, 0);
-        if (wide) LSQ_TRY(run_batch<16>(st, s, dists, idx, codes, Q, K, dbnorms, nullptr, q0, nqb, n, m, d, nn, P, h_fail.data(), stats, timed != 0));
-        else LSQ_TRY(run_batch<8>(st, s, dists, idx, codes, Q, K, dbnorms, nullptr, q0, nqb, n, m, d, nn, P, h_fail.data(), stats, timed != 0));
+        if (wide) LSQ_TRY(run_batch<16>(st, s, dists, idx, in, nullptr, q0, nqb, nn, P, h_fail.data(), stats, timed != 0));
+        else LSQ_TRY(run_batch<8>(st, s, dists, idx, in, nullptr, q0, nqb, nn, P, h_fail.data(), stats, timed != 0));
         if (!P.exhaustive) {
             LSQ_HIP(hipStreamSynchronize(s));
             for (int t = 0; t < nqb; ++t) if (h_fail[(size_t)t]) failed.push_back(q0 + t);
@@ -571,8 +651,8 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
         for (size_t f0 = 0; f0 < failed.size(); f0 += (size_t)fb) {
             const int nqb = (int)std::min<size_t>((size_t)fb, failed.size() - f0);
             const int *qs = st->qsel.as<int>() + f0;
-            if (wide) LSQ_TRY(run_batch<16>(st, s, dists, idx, codes, Q, K, dbnorms, qs, 0, nqb, n, m, d, nn, E, nullptr, stats, timed != 0));
-            else LSQ_TRY(run_batch<8>(st, s, dists, idx, codes, Q, K, dbnorms, qs, 0, nqb, n, m, d, nn, E, nullptr, stats, timed != 0));
+            if (wide) LSQ_TRY(run_batch<16>(st, s, dists, idx, in, qs, 0, nqb, nn, E, nullptr, stats, timed != 0));
+            else LSQ_TRY(run_batch<8>(st, s, dists, idx, in, qs, 0, nqb, nn, E, nullptr, stats, timed != 0));
             if (stats) stats->batches += 1;
         }
         if (stats) stats->fallback_queries += (int64_t)failed.size();
@@ -580,6 +660,15 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
     if (stats) { stats->queries += nq; stats->codes = n; stats->exhaustive = P.exhaustive ? 1 : 0; stats->threshold_rank = P.r; stats->list_capacity = P.cap; }
     LSQ_HIP(hipStreamSynchronize(s));
     return LSQ_OK;
+}
+
+}  // namespace
+
+int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const uint8_t *codes, const float *Q, const float *K,
+                   const float *dbnorms, int nq, int n, int m, int d, int nn, int force_exhaustive, int sample_override, lsq_linscan_stats *stats,
+                   int timed) {
+    const AdcInput in{codes, m, Q, d, K, dbnorms, n, m, d};
+    return adc_search(s, pst, dists, idx, in, nq, nn, force_exhaustive, sample_override, stats, timed);
 }
 
 // host-buffer entry: upload, search, download
@@ -600,6 +689,37 @@ int lsq_adc_search_host(hipStream_t s, lsq_adc_state **pst, float *dists, int *i
     LSQ_HIP(hipMemcpyAsync(st->h_norms.p, dbnorms, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
     LSQ_TRY(lsq_adc_search(s, pst, st->h_dists.as<float>(), st->h_idx.as<int>(), st->h_codes.as<uint8_t>(), st->h_q.as<float>(), st->h_k.as<float>(),
                            st->h_norms.as<float>(), nq, n, m, d, nn, force_exhaustive, sample_override, stats, timed));
+    LSQ_HIP(hipMemcpyAsync(dists, st->h_dists.p, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
+    LSQ_HIP(hipMemcpyAsync(idx, st->h_idx.p, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
+    LSQ_HIP(hipStreamSynchronize(s));
+    return LSQ_OK;
+}
+
+// PQ / OPQ (linscan_aqd.cpp): codes [n][cstride], centres [m][h][subdim], query rows qstride floats apart; ids out 0-based
+int lsq_adc_search_pq(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const uint8_t *codes, int cstride, const float *centers,
+                      const float *Q, int qstride, int nq, int n, int m, int subdim, int nn, int force_exhaustive, int sample_override,
+                      lsq_linscan_stats *stats, int timed) {
+    const AdcInput in{codes, cstride, Q, qstride, centers, nullptr, n, m, subdim};
+    return adc_search(s, pst, dists, idx, in, nq, nn, force_exhaustive, sample_override, stats, timed);
+}
+
+// host-buffer entry: upload what the reference reads (rows up to their m-th byte / (m subdim)-th float), search, download
+int lsq_adc_search_pq_host(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const uint8_t *codes, int cstride, const float *centers,
+                           const float *Q, int qstride, int nq, int n, int m, int subdim, int nn, int force_exhaustive, int sample_override,
+                           lsq_linscan_stats *stats, int timed) {
+    if (!*pst) *pst = new lsq_adc_state();
+    lsq_adc_state *st = *pst;
+    const size_t code_bytes = (size_t)(n - 1) * cstride + m, q_floats = (size_t)(nq - 1) * qstride + (size_t)m * subdim;
+    LSQ_TRY(st->h_codes.ensure(code_bytes + 16));
+    LSQ_TRY(st->h_q.ensure(sizeof(float) * q_floats));
+    LSQ_TRY(st->h_k.ensure(sizeof(float) * (size_t)m * LSQ_H * subdim));
+    LSQ_TRY(st->h_dists.ensure(sizeof(float) * (size_t)nq * nn));
+    LSQ_TRY(st->h_idx.ensure(sizeof(int) * (size_t)nq * nn));
+    LSQ_HIP(hipMemcpyAsync(st->h_codes.p, codes, code_bytes, hipMemcpyHostToDevice, s));
+    LSQ_HIP(hipMemcpyAsync(st->h_q.p, Q, sizeof(float) * q_floats, hipMemcpyHostToDevice, s));
+    LSQ_HIP(hipMemcpyAsync(st->h_k.p, centers, sizeof(float) * (size_t)m * LSQ_H * subdim, hipMemcpyHostToDevice, s));
+    LSQ_TRY(lsq_adc_search_pq(s, pst, st->h_dists.as<float>(), st->h_idx.as<int>(), st->h_codes.as<uint8_t>(), cstride, st->h_k.as<float>(),
+                              st->h_q.as<float>(), qstride, nq, n, m, subdim, nn, force_exhaustive, sample_override, stats, timed));
     LSQ_HIP(hipMemcpyAsync(dists, st->h_dists.p, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
     LSQ_HIP(hipMemcpyAsync(idx, st->h_idx.p, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
     LSQ_HIP(hipStreamSynchronize(s));

@@ -390,6 +390,35 @@ extern "C" int lsq_linscan(lsq_ctx *c, float *dists, int *idx, const unsigned ch
                                c->adc_rank, &c->adc_stats, c->profile);
 }
 
+// the PQ / OPQ scan: the host drop-in's checks (lsq_linscan.hip), then the device limits of lsq_linscan
+static int linscan_pq_check(const char *fn, const void *a, const void *b, const void *c0, const void *d0, const void *e, int N, uint32_t NQ, int B,
+                            int K, int dim1codes, int dim1queries, int subdim) {
+    LSQ_TRY(lsq_linscan_pq_check(fn, a, b, c0, d0, e, N, NQ, B, K, dim1codes, dim1queries, subdim));
+    if (B / 8 > LSQ_MAX_M) { lsq_set_error("%s: the device scan needs B/8 <= 16 (got B=%d: %d sub-spaces)", fn, B, B / 8); return LSQ_EINVAL; }
+    if (NQ > (uint32_t)INT32_MAX) { lsq_set_error("%s: NQ=%u exceeds the device scan's limit of 2^31 - 1 queries", fn, NQ); return LSQ_EINVAL; }
+    return LSQ_OK;
+}
+
+extern "C" int lsq_linscan_pq_dev(lsq_ctx *c, float *d_dists, uint32_t *d_res, const uint8_t *d_codes, const float *d_centers, const float *d_queries,
+                                  int N, uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim) {
+    if (!c) { lsq_set_error("lsq_linscan_pq_dev: null context"); return LSQ_EINVAL; }
+    LSQ_TRY(linscan_pq_check("lsq_linscan_pq_dev", d_dists, d_res, d_codes, d_centers, d_queries, N, NQ, B, K, dim1codes, dim1queries, subdim));
+    if (NQ == 0) return LSQ_OK;
+    LSQ_TRY(use_device(c));
+    return lsq_adc_search_pq(c->stream, &c->adc, d_dists, reinterpret_cast<int *>(d_res), d_codes, dim1codes, d_centers, d_queries, dim1queries,
+                             (int)NQ, N, B / 8, subdim, K, c->adc_exhaustive, c->adc_rank, &c->adc_stats, c->profile);
+}
+
+extern "C" int lsq_linscan_pq(lsq_ctx *c, float *dists, uint32_t *res, const uint8_t *codes, const float *centers, const float *queries, int N,
+                              uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim) {
+    if (!c) { lsq_set_error("lsq_linscan_pq: null context"); return LSQ_EINVAL; }
+    LSQ_TRY(linscan_pq_check("lsq_linscan_pq", dists, res, codes, centers, queries, N, NQ, B, K, dim1codes, dim1queries, subdim));
+    if (NQ == 0) return LSQ_OK;
+    LSQ_TRY(use_device(c));
+    return lsq_adc_search_pq_host(c->stream, &c->adc, dists, reinterpret_cast<int *>(res), codes, dim1codes, centers, queries, dim1queries, (int)NQ,
+                                  N, B / 8, subdim, K, c->adc_exhaustive, c->adc_rank, &c->adc_stats, c->profile);
+}
+
 extern "C" int lsq_get_linscan_stats(lsq_ctx *c, lsq_linscan_stats *out) {
     if (!c || !out) { lsq_set_error("lsq_get_linscan_stats: null argument"); return LSQ_EINVAL; }
     *out = c->adc_stats;

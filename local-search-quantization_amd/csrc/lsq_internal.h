@@ -226,6 +226,17 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, co
 int lsq_adc_search_host(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const unsigned char *codes, const float *Q, const float *K,
                         const float *dbnorms, int nq, int n, int m, int d, int nn, int force_exhaustive, int rank_override, lsq_linscan_stats *stats,
                         int timed);
+// PQ / OPQ (no norm term, 0-based ids out): codes [n][cstride] u8, centers [m][256][subdim], query rows qstride floats apart
+int lsq_adc_search_pq(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const uint8_t *codes, int cstride, const float *centers,
+                      const float *Q, int qstride, int nq, int n, int m, int subdim, int nn, int force_exhaustive, int rank_override,
+                      lsq_linscan_stats *stats, int timed);
+int lsq_adc_search_pq_host(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const uint8_t *codes, int cstride, const float *centers,
+                           const float *Q, int qstride, int nq, int n, int m, int subdim, int nn, int force_exhaustive, int rank_override,
+                           lsq_linscan_stats *stats, int timed);
+
+// argument checks of the PQ / OPQ scan (lsq_linscan.hip), shared by the host drop-in and the device scan
+int lsq_linscan_pq_check(const char *fn, const void *dists, const void *res, const void *codes, const void *centers, const void *queries, int N,
+                         uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim);
 
 // ---- quantize_norms on the device (lsq_norms.hip): codes [n][stride] u8 0-based; any of the four outputs may be null ----------------------
 int lsq_launch_quantize_norms(hipStream_t s, const uint8_t *codes, int stride, const float *K, const float *cb, int ncb, int64_t n, int d, int m,

@@ -11,7 +11,10 @@
 //   table[j]   = ((0 - (2 q0) c_j0) - (2 q1) c_j1) - ...           (f32, k ascending; no FMA: -ffp-contract=off)
 //   dist(i)    = (((0 + table[0*h + b_i0]) + table[1*h + b_i1]) + ...) + dbnorms[i]
 //   result     = the nn smallest (dist, id) pairs in lexicographic order, ids 1-BASED like the reference (:75).
+//
+// Below it, the reference's other scan (PQ / OPQ codes, no norm term): lsq_linscan_aqd_query.
 #include <algorithm>
+#include <cstring>
 #include <thread>
 #include <utility>
 #include <vector>
@@ -80,6 +83,110 @@ extern "C" int lsq_linscan_aqd_query_extra_byte(float *dists, int *idx, const un
     for (int t = 0; t < nt; ++t) {
         const int q0 = (int)((int64_t)nqueries * t / nt), q1 = (int)((int64_t)nqueries * (t + 1) / nt);
         pool.emplace_back(scan_queries, dists, idx, codes, queries, codebooks, dbnorms, q0, q1, ncodes, m, h, d, nn);
+    }
+    for (auto &th : pool) th.join();
+    return LSQ_OK;
+}
+
+// ---- PQ / OPQ: linscan_aqd_query of the reference (src/linscan/cpp/linscan_aqd.cpp:37-114, bound by linscan_pq / linscan_opq at
+// src/linscan/Linscan.jl:5-43), written from scratch with the same arithmetic order:
+//
+//   table[k 256 + r] = ((0 + d_0 d_0) + d_1 d_1) + ...,   d_s = c[k][r][s] - q[k subdim + s]     (f32, s ascending; no FMA)
+//   dist(i)          = ((0 + table[0 256 + b_i0]) + table[1 256 + b_i1]) + ...                    (k ascending; no norm term)
+//   result           = the K smallest (dist, id) pairs in lexicographic order, ids 0-BASED uint32 (:93-101)
+//
+// The reference's chunks of 10^7 pairs return exactly the K lexicographically smallest pairs (what a pair left over from an earlier chunk
+// could displace was already smaller); a bounded heap per query does the same.  Pairs are held as 64-bit keys (order-preserving distance bits
+// << 32 | id): the lexicographic order for every non-NaN distance, and NaN last (the reference's partial_sort leaves NaN undefined) -- what the
+// device scan does.
+namespace {
+
+inline uint64_t pq_key(float v, uint32_t id) {
+    uint32_t b;
+    memcpy(&b, &v, 4);
+    const uint32_t k = v != v ? 0xffffffffu : b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+    return ((uint64_t)k << 32) | id;
+}
+inline float pq_unkey(uint64_t key) {
+    const uint32_t k = (uint32_t)(key >> 32);
+    const uint32_t b = k == 0xffffffffu ? 0x7fc00000u : ((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+    float v;
+    memcpy(&v, &b, 4);
+    return v;
+}
+
+void pq_scan_queries(float *dists, uint32_t *res, const uint8_t *codes, const float *centers, const float *queries, int64_t q0, int64_t q1,
+                     int N, int m, int K, int dim1codes, int dim1queries, int subdim) {
+    std::vector<float> table((size_t)m * LSQ_H);
+    std::vector<uint64_t> heap;
+    heap.reserve((size_t)K + 1);
+    for (int64_t q = q0; q < q1; ++q) {
+        const float *query = queries + q * dim1queries;
+        for (int k = 0; k < m; ++k) {
+            const float *qk = query + (size_t)k * subdim;
+            for (int r = 0; r < LSQ_H; ++r) {
+                const float *c = centers + ((size_t)k * LSQ_H + r) * subdim;
+                float t = 0.0f;
+                for (int s = 0; s < subdim; ++s) {
+                    const float e = c[s] - qk[s];
+                    t += e * e;                                          // product rounded, then the add (-ffp-contract=off)
+                }
+                table[(size_t)k * LSQ_H + r] = t;
+            }
+        }
+        heap.clear();
+        const uint8_t *code = codes;
+        for (int i = 0; i < N; ++i, code += dim1codes) {
+            float acc = 0.0f;
+            for (int k = 0; k < m; ++k) acc += table[(size_t)LSQ_H * k + code[k]];
+            const uint64_t cand = pq_key(acc, (uint32_t)i);
+            if ((int)heap.size() < K) {
+                heap.push_back(cand);
+                std::push_heap(heap.begin(), heap.end());               // max-heap on (dist, id)
+            } else if (cand < heap.front()) {
+                std::pop_heap(heap.begin(), heap.end());
+                heap.back() = cand;
+                std::push_heap(heap.begin(), heap.end());
+            }
+        }
+        std::sort_heap(heap.begin(), heap.end());                       // ascending (dist, id)
+        for (int j = 0; j < K; ++j) {
+            dists[q * K + j] = pq_unkey(heap[(size_t)j]);
+            res[q * K + j] = (uint32_t)heap[(size_t)j];
+        }
+    }
+}
+
+}  // namespace
+
+// Argument checks shared with the device scan (lsq_api.hip): 0 or LSQ_EINVAL with the message set.
+int lsq_linscan_pq_check(const char *fn, const void *dists, const void *res, const void *codes, const void *centers, const void *queries, int N,
+                         uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim) {
+    if (B < 8 || B % 8 != 0) { lsq_set_error("%s: B=%d bits must be a positive multiple of 8 (h = 256)", fn, B); return LSQ_EINVAL; }
+    const int m = B / 8;
+    if (m > dim1codes) { lsq_set_error("%s: B/8=%d exceeds dim1codes=%d", fn, m, dim1codes); return LSQ_EINVAL; }
+    if (subdim < 1) { lsq_set_error("%s: subdim=%d must be >= 1", fn, subdim); return LSQ_EINVAL; }
+    if ((int64_t)m * subdim > (int64_t)dim1queries) {
+        lsq_set_error("%s: (B/8)*subdim=%lld exceeds dim1queries=%d", fn, (long long)m * subdim, dim1queries);
+        return LSQ_EINVAL;
+    }
+    if (K < 1 || K > N) { lsq_set_error("%s: needs 1 <= K <= N (got K=%d N=%d)", fn, K, N); return LSQ_EINVAL; }
+    if (NQ > 0 && (!dists || !res || !codes || !centers || !queries)) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    return LSQ_OK;
+}
+
+extern "C" int lsq_linscan_aqd_query(float *dists, uint32_t *res, const uint8_t *codes, const float *centers, const float *queries, int N,
+                                     uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim) {
+    LSQ_TRY(lsq_linscan_pq_check("lsq_linscan_aqd_query", dists, res, codes, centers, queries, N, NQ, B, K, dim1codes, dim1queries, subdim));
+    if (NQ == 0) return LSQ_OK;
+    int64_t nt = (int64_t)std::thread::hardware_concurrency();
+    if (nt < 1) nt = 1;
+    if (nt > (int64_t)NQ) nt = (int64_t)NQ;
+    std::vector<std::thread> pool;
+    pool.reserve((size_t)nt);
+    for (int64_t t = 0; t < nt; ++t) {
+        const int64_t q0 = (int64_t)NQ * t / nt, q1 = (int64_t)NQ * (t + 1) / nt;
+        pool.emplace_back(pq_scan_queries, dists, res, codes, centers, queries, q0, q1, N, B / 8, K, dim1codes, dim1queries, subdim);
     }
     for (auto &th : pool) th.join();
     return LSQ_OK;

@@ -182,6 +182,37 @@ class Engine:
                                                 dnorms.data_ptr(), nq, n, m, h, d, int(k)))
         return dists, ids
 
+    def linscan_pq(self, codes, Q, C3, m, k, subdim):
+        """PQ / OPQ codes, no norm term.  codes (n, dim1codes) uint8 0-based (the first m bytes of a row used), Q (nq, dim1queries),
+        C3 (m, 256, subdim) centres (any shape holding m*256*subdim floats): host arrays.
+        -> dists (nq,k) float32 ascending, ids (nq,k) uint32 0-BASED   [lsq_linscan_pq]"""
+        codes, Q, C3 = _np(codes, np.uint8), _np(Q, np.float32), _np(C3, np.float32)
+        if codes.ndim != 2 or Q.ndim != 2 or C3.size != m * H * subdim:
+            raise ValueError("shape mismatch: codes %s Q %s C3 %s m=%d subdim=%d" % (codes.shape, Q.shape, C3.shape, m, subdim))
+        (n, dc), (nq, dq) = codes.shape, Q.shape
+        dists = np.zeros((nq, k), dtype=np.float32)
+        ids = np.zeros((nq, k), dtype=np.uint32)
+        self._check(self._L.lsq_linscan_pq(self._h, dists.ctypes.data, ids.ctypes.data, codes.ctypes.data, C3.ctypes.data, Q.ctypes.data,
+                                           n, nq, 8 * m, int(k), dc, dq, int(subdim)))
+        return dists, ids
+
+    def linscan_pq_dev(self, dcodes, dQ, dC3, m, k, subdim):
+        """The same on device-resident torch tensors -> (dists (nq,k) f32, ids (nq,k) 0-based) tensors; torch has no uint32 arithmetic, so the
+        ids tensor is int32 holding the uint32 bits (every id is below 2^31)   [lsq_linscan_pq_dev]"""
+        import torch
+        assert dcodes.is_cuda and dQ.is_cuda and dC3.is_cuda, "device tensors required"
+        assert dcodes.dtype == torch.uint8 and dQ.dtype == torch.float32 and dC3.dtype == torch.float32
+        assert dcodes.is_contiguous() and dQ.is_contiguous() and dC3.is_contiguous()
+        if dcodes.dim() != 2 or dQ.dim() != 2 or dC3.numel() != m * H * subdim:
+            raise ValueError("shape mismatch")
+        (n, dc), (nq, dq) = dcodes.shape, dQ.shape
+        dists = torch.empty((nq, k), dtype=torch.float32, device=dQ.device)
+        ids = torch.empty((nq, k), dtype=torch.int32, device=dQ.device)
+        with self._on_torch_stream():
+            self._check(self._L.lsq_linscan_pq_dev(self._h, dists.data_ptr(), ids.data_ptr(), dcodes.data_ptr(), dC3.data_ptr(), dQ.data_ptr(),
+                                                   n, nq, 8 * m, int(k), dc, dq, int(subdim)))
+        return dists, ids
+
     def quantize_norms(self, B, K, cbnorms, m, h=H):
         """B (n,m) int16 1-based, K (m*h,d), cbnorms (<= 256,): host arrays.
         -> idx (n,) int16 1-based index of the nearest norm centroid, dbnorms (n,) = cbnorms[idx-1], norms (n,) unquantised   [lsq_quantize_norms]"""

@@ -134,6 +134,37 @@ def linscan_lsq(B, X, C, dbnorms, R, k=10000, *, nthreads=0, engine=None):
     return dists.T, res.T
 
 
+def linscan_pq(B, X, C, b, k=10000, *, engine=None):
+    """Linear scan with PQ codes  (src/linscan/Linscan.jl:5-26 -> linscan_aqd_query, src/linscan/cpp/linscan_aqd.cpp:37-114).
+    B (m, n) uint8 0-based; X (d, nq) queries; C list of (subdim, h) centre matrices; b bits per code (8 m); d % m == 0 (Cint(d/m)).
+    -> dists (k, nq) float32 ascending, res (k, nq) uint32 1-based ids.
+    engine=None: the host scan (lsq_linscan_aqd_query, the reference's own division of labour);
+    engine=<Engine>: the device scan (lsq_linscan_pq) -- same results bit for bit."""
+    from . import _lib
+    codes = np.ascontiguousarray(np.asarray(B, dtype=np.uint8).T)              # (n, m): dim1codes = m
+    Q = _X_of(X)                                                                # (nq, d): dim1queries = d
+    n, m = codes.shape
+    nq, d = Q.shape
+    if d % m != 0:
+        raise ValueError("linscan_pq: d=%d is not a multiple of m=%d (the reference passes Cint(d/m))" % (d, m))
+    subdim = d // m
+    centers = np.ascontiguousarray(np.stack([np.asarray(Ck, dtype=np.float32).T for Ck in C]))      # cat(3, C...) -> [len(C)][h][subdim]
+    dists = np.zeros((nq, k), dtype=np.float32)
+    res = np.zeros((nq, k), dtype=np.uint32)
+    args = (dists.ctypes.data, res.ctypes.data, codes.ctypes.data, centers.ctypes.data, Q.ctypes.data, n, nq, int(b), int(k), m, d, subdim)
+    if engine is not None:
+        engine._check(engine._L.lsq_linscan_pq(engine._h, *args))
+    else:
+        _lib.check(_lib.load().lsq_linscan_aqd_query(*args))
+    return dists.T, res.T + np.uint32(1)                                        # Linscan.jl:25: res .+= 1
+
+
+def linscan_opq(B, X, C, b, R, k=10000, *, engine=None):
+    """Linear scan with OPQ codes  (src/linscan/Linscan.jl:29-43): linscan_pq(B, R'X, C, b, k)."""
+    RX = np.asarray(R, dtype=np.float32).T @ np.asarray(X, dtype=np.float32)
+    return linscan_pq(B, RX, C, b, k, engine=engine)
+
+
 def eval_recall(ids_gnd, ids_predicted, k, V=False):
     """recall@N curve (src/linscan/Linscan.jl:76-117): ids_gnd (nq,), ids_predicted (k, nq), same id base.
     -> recall_at_i (k,) with recall_at_i[i-1] = fraction of queries whose true neighbour ranks <= i."""
