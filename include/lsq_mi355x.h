@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 700
+#define LSQ_VERSION 800
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -329,6 +329,33 @@ LSQ_API int lsq_update_codebooks_lsmr(const float *X, const int16_t *B, int d, i
 LSQ_API int lsq_update_codebooks_gpu(lsq_ctx *ctx, const float *X, const int16_t *B, int d, int64_t n, int m, int h, float *K_out, int *iterations);
 LSQ_API int lsq_update_codebooks_dev(lsq_ctx *ctx, const float *d_X, const uint8_t *d_codes, int d, int64_t n, int m, int h, float *d_K_out,
                                      int *iterations);
+
+/* ---- sparse codebooks: the SPGL1 (LASSO) codebook update ON THE DEVICE (csrc/lsq_spgl1.hip; since v800) -------------------------------------
+ * update_codebooks_spgl1(X, B, h, tau, prevC) and update_codebooks_spgl1_threshold(..., S)      src/codebook_update_sparse.jl (the reference calls
+ * MATLAB's SPGL1 on the operator of matlab/sparse_lsq_fun.m): one joint problem over all d dimensions,
+ *     minimise 1/2 ||A k - b||^2  subject to  ||k||_1 <= tau,      A = I_d (x) sparsify_codes(B, h),  b = vec(X'),
+ * solved in float64 by SPGL1's single-tau spectral projected gradient (van den Berg & Friedlander 2008; spgSetParms defaults: optTol 1e-4,
+ * 3 previous objectives, steps in [1e-16, 1e5], at most 10 n d iterations), warm-started from the projection of K_init (NULL: from 0).
+ * "Solved" means rGap = |r'(r - b) + tau ||A'r||_inf| / max(1, ||r||^2 / 2) <= opt_tol, or ||r|| < opt_tol ||b||.
+ * K_out (d x (m*h) = [m*h][d], f32) receives the best accepted iterate; then, for 0 <= S < d m h, only its S entries largest in |K| are kept
+ * (ties: the lower flat index first -- Julia's sortperm(abs(K[:]), rev=true)) and the others become +0.0.  tau = 0 gives K = 0; S >= d m h keeps all.
+ * The same bits on every call.  Host form: X d x n, B m x n Int16 1-based; _dev: device pointers, codes [n][m] uint8 0-based.  h must be 256.
+ * LSQ_OK is returned whatever info->status says (the trainer goes on with the best iterate); bad tau (< 0 or NaN), S or shapes: LSQ_EINVAL. */
+typedef struct lsq_spgl1_params {
+    double opt_tol;          /* <= 0: 1e-4 */
+    int64_t max_iter;        /* <= 0: 10 n d */
+} lsq_spgl1_params;          /* NULL -> SPGL1's defaults */
+enum { LSQ_SPGL1_OPTIMAL = 0, LSQ_SPGL1_ITERATIONS = 1, LSQ_SPGL1_LINE_ERROR = 2 };
+typedef struct lsq_spgl1_info {
+    int status;                          /* LSQ_SPGL1_*: the gap test passed / the iteration cap / the line search failed 10 times */
+    int64_t iterations, line_search_trials;
+    double f, rel_gap, l1, tau;          /* of the returned iterate before thresholding: 1/2 ||r||^2, rGap, ||K_out||_1 (of the f32 values) */
+    int64_t nnz_before_threshold, nnz;
+} lsq_spgl1_info;
+LSQ_API int lsq_update_codebooks_spgl1(lsq_ctx *ctx, const float *X, const int16_t *B, int d, int64_t n, int m, int h, double tau,
+                                       const float *K_init, int64_t S, const lsq_spgl1_params *params, float *K_out, lsq_spgl1_info *info);
+LSQ_API int lsq_update_codebooks_spgl1_dev(lsq_ctx *ctx, const float *d_X, const uint8_t *d_codes, int d, int64_t n, int m, int h, double tau,
+                                           const float *d_K_init, int64_t S, const lsq_spgl1_params *params, float *d_K_out, lsq_spgl1_info *info);
 
 /* ---- the initialisers' two data-parallel steps ON THE DEVICE (csrc/lsq_init.hip; since v600) -----------------------------------
  * encoding_viterbi(X, C) -> B      src/encodings/encode_chain.jl:92-123 (worker encode_viterbi! :2-89): the exact MAP codes of a CHAIN -- unaries

@@ -44,6 +44,20 @@ class LinscanStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Spgl1Params(C.Structure):
+    _fields_ = [("opt_tol", C.c_double), ("max_iter", C.c_int64)]
+
+
+class Spgl1Info(C.Structure):
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int64), ("line_search_trials", C.c_int64), ("f", C.c_double), ("rel_gap", C.c_double),
+                ("l1", C.c_double), ("tau", C.c_double), ("nnz_before_threshold", C.c_int64), ("nnz", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+SPGL1_OPTIMAL, SPGL1_ITERATIONS, SPGL1_LINE_ERROR = 0, 1, 2
+
 _vp, _i, _i64, _u64, _u32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint32
 
 # name -> (restype, argtypes).  Pointers are passed as raw addresses (host or device).
@@ -90,6 +104,8 @@ SIGNATURES = {
     "lsq_update_codebooks_lsmr": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _vp]),
     "lsq_update_codebooks_gpu": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, C.POINTER(_i)]),
     "lsq_update_codebooks_dev": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, C.POINTER(_i)]),
+    "lsq_update_codebooks_spgl1": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, C.c_double, _vp, _i64, C.POINTER(Spgl1Params), _vp, C.POINTER(Spgl1Info)]),
+    "lsq_update_codebooks_spgl1_dev": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, C.c_double, _vp, _i64, C.POINTER(Spgl1Params), _vp, C.POINTER(Spgl1Info)]),
     "lsq_encode_viterbi": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp]),
     "lsq_encode_viterbi_dev": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp]),
     "lsq_assign_codewords": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp]),

@@ -96,6 +96,7 @@ struct lsq_ctx {
     int64_t call_I = 0, call_q16_chunks = 0;
     float *q_colshift = nullptr;                       // inside qscratch: the per-candidate shift of the unary levels (double-centred tables)
     lsq_lsqr_state *lsqr = nullptr;                    // device LSQR (lsq_lsqr.hip): work buffers, created on first use
+    lsq_spgl1_state *spgl1 = nullptr;                  // device SPGL1 (lsq_spgl1.hip): work buffers, created on first use
     lsq_adc_state *adc = nullptr;                      // device ADC scan (lsq_adc.hip): buffers, created on first use
     lsq_linscan_stats adc_stats{};
     int adc_exhaustive = 0, adc_rank = 0;              // options "linscan_exhaustive", "linscan_rank": test hooks of the scan's selection
@@ -233,6 +234,7 @@ extern "C" int lsq_destroy(lsq_ctx *c) {
     for (auto e : c->panel_ev) (void)hipEventDestroy(e);
     lsq_adc_free(c->adc);
     lsq_lsqr_free(c->lsqr);
+    lsq_spgl1_free(c->spgl1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->copy_done) (void)hipEventDestroy(c->copy_done);
@@ -1359,6 +1361,59 @@ extern "C" int lsq_update_codebooks_gpu(lsq_ctx *c, const float *X, const int16_
     LSQ_TRY(lsq_launch_codes_compact(c->stream, c->recCur.as<uint8_t>(), n, m, c->sTight.as<uint8_t>()));
     LSQ_TRY(lsq_lsqr_update_codebooks(c->stream, &c->lsqr, c->sX.as<float>(), c->sTight.as<uint8_t>(), d, n, m, c->sK.as<float>(), iterations));
     LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, sizeof(float) * (size_t)m * LSQ_H * d, hipMemcpyDeviceToHost, c->stream));
+    LSQ_HIP(hipStreamSynchronize(c->stream));
+    return LSQ_OK;
+}
+
+// ---- the SPGL1 (LASSO) codebook update (lsq_spgl1.hip) ----------------------------------------------------------------------------------------
+// arguments first (no device needed to reject them), then the context: a NULL context on a machine without a device is LSQ_ENODEV
+static int spgl1_args(const char *fn, lsq_ctx *c, int d, int64_t n, int m, int h, double tau, const lsq_spgl1_params *p, double *opt_tol,
+                      int64_t *max_iter) {
+    LSQ_TRY(check_shape(fn, d, n, m, h));
+    if (n < 1) { lsq_set_error("%s: n=%lld must be >= 1", fn, (long long)n); return LSQ_EINVAL; }
+    if (!(tau >= 0.0)) { lsq_set_error("%s: tau=%g must be a number >= 0", fn, tau); return LSQ_EINVAL; }
+    if (p && (p->opt_tol != p->opt_tol || p->opt_tol >= 1.0)) { lsq_set_error("%s: opt_tol=%g must be below 1", fn, p->opt_tol); return LSQ_EINVAL; }
+    *opt_tol = p && p->opt_tol > 0.0 ? p->opt_tol : 1e-4;
+    *max_iter = p && p->max_iter > 0 ? p->max_iter : 10 * n * (int64_t)d;        // spgSetParms: iterations = 10 length(b)
+    if (!c) {
+        int count = 0;
+        if (lsq_device_count(&count) != LSQ_OK || count <= 0) { lsq_set_error("%s: no HIP device visible (this library has no CPU fallback)", fn); return LSQ_ENODEV; }
+        lsq_set_error("%s: null lsq_ctx", fn);
+        return LSQ_EINVAL;
+    }
+    return use_device(c);
+}
+
+extern "C" int lsq_update_codebooks_spgl1_dev(lsq_ctx *c, const float *d_X, const uint8_t *d_codes, int d, int64_t n, int m, int h, double tau,
+                                              const float *d_K_init, int64_t S, const lsq_spgl1_params *params, float *d_K_out, lsq_spgl1_info *info) {
+    double opt_tol = 0.0;
+    int64_t max_iter = 0;
+    LSQ_TRY(spgl1_args("lsq_update_codebooks_spgl1_dev", c, d, n, m, h, tau, params, &opt_tol, &max_iter));
+    if (!d_X || !d_codes || !d_K_out) { lsq_set_error("lsq_update_codebooks_spgl1_dev: null pointer"); return LSQ_EINVAL; }
+    const AsyncOff sync_here(c);
+    return lsq_spgl1_update_codebooks(c->stream, &c->spgl1, d_X, d_codes, d, n, m, tau, d_K_init, S, opt_tol, max_iter, d_K_out, info);
+}
+
+extern "C" int lsq_update_codebooks_spgl1(lsq_ctx *c, const float *X, const int16_t *B, int d, int64_t n, int m, int h, double tau, const float *K_init,
+                                          int64_t S, const lsq_spgl1_params *params, float *K_out, lsq_spgl1_info *info) {
+    double opt_tol = 0.0;
+    int64_t max_iter = 0;
+    LSQ_TRY(spgl1_args("lsq_update_codebooks_spgl1", c, d, n, m, h, tau, params, &opt_tol, &max_iter));
+    if (!X || !B || !K_out) { lsq_set_error("lsq_update_codebooks_spgl1: null pointer"); return LSQ_EINVAL; }
+    const AsyncOff sync_here(c);
+    const size_t kbytes = sizeof(float) * (size_t)m * LSQ_H * d;
+    LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)n * d));
+    LSQ_TRY(c->sK.ensure(kbytes));
+    if (K_init) LSQ_TRY(c->sF32.ensure(kbytes));
+    c->tables_valid = false;
+    LSQ_HIP(hipMemcpyAsync(c->sX.p, X, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
+    if (K_init) LSQ_HIP(hipMemcpyAsync(c->sF32.p, K_init, kbytes, hipMemcpyHostToDevice, c->stream));
+    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));                          // records of stride 8 / 16 -> tight [n][m] below
+    LSQ_TRY(c->sTight.ensure((size_t)n * m));
+    LSQ_TRY(lsq_launch_codes_compact(c->stream, c->recCur.as<uint8_t>(), n, m, c->sTight.as<uint8_t>()));
+    LSQ_TRY(lsq_spgl1_update_codebooks(c->stream, &c->spgl1, c->sX.as<float>(), c->sTight.as<uint8_t>(), d, n, m, tau,
+                                       K_init ? c->sF32.as<float>() : nullptr, S, opt_tol, max_iter, c->sK.as<float>(), info));
+    LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, kbytes, hipMemcpyDeviceToHost, c->stream));
     LSQ_HIP(hipStreamSynchronize(c->stream));
     return LSQ_OK;
 }

@@ -246,3 +246,12 @@ int lsq_launch_quantize_norms(hipStream_t s, const uint8_t *codes, int stride, c
 struct lsq_lsqr_state;
 void lsq_lsqr_free(lsq_lsqr_state *st);
 int lsq_lsqr_update_codebooks(hipStream_t s, lsq_lsqr_state **st, const float *dX, const uint8_t *dcodes, int d, int64_t n, int m, float *dK, int *iters_out);
+// the rows of a code matrix sorted by (codebook j, code) once per call: keys and segment starts live in `buf` (shared by lsq_lsqr.hip and lsq_spgl1.hip)
+int lsq_sort_rows_by_code(hipStream_t s, DevBuf &buf, const uint8_t *dcodes, int64_t n, int m, const uint64_t **sorted, const int64_t **seg);
+
+// ---- SPGL1 (LASSO) codebook update on the device (lsq_spgl1.hip) ---------------------------------------------------------------------------------
+struct lsq_spgl1_state;
+void lsq_spgl1_free(lsq_spgl1_state *st);
+// dX [n][d], dcodes [n][m] u8 0-based, dK0 [m*256][d] (optional warm start), dK [m*256][d] (output); all device pointers.  S < 0: no threshold.
+int lsq_spgl1_update_codebooks(hipStream_t s, lsq_spgl1_state **st, const float *dX, const uint8_t *dcodes, int d, int64_t n, int m, double tau,
+                               const float *dK0, int64_t S, double opt_tol, int64_t max_iter, float *dK, lsq_spgl1_info *info);

@@ -273,6 +273,27 @@ __global__ void lsqr_scal_stop(int d, Scal S, float atol, float btol, float ctol
 
 }  // namespace
 
+// (column j h + b_ij) << 32 | row keys of the n m code entries, radix-sorted on their 32 + ceil(log2 cols) bits, and seg[c] = the first sorted position of
+// column c (seg[cols] = n m): a column's rows in ascending order.  Shared by the device LSQR and the SPGL1 gradient (lsq_spgl1.hip).
+int lsq_sort_rows_by_code(hipStream_t s, DevBuf &buf, const uint8_t *dcodes, int64_t n, int m, const uint64_t **sorted_out, const int64_t **seg_out) {
+    const int cols = m * LSQ_H;
+    const int64_t total = n * (int64_t)m;
+    size_t sort_bytes = 0;
+    int end_bit = 33;
+    while (end_bit < 64 && ((uint64_t)cols >> (end_bit - 32)) != 0) ++end_bit;
+    LSQ_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)total, 0, end_bit, s));
+    const size_t off_sorted = (size_t)total * 8, off_seg = off_sorted + (size_t)total * 8, off_tmp = (off_seg + ((size_t)cols + 1) * 8 + 255) & ~(size_t)255;
+    LSQ_TRY(buf.ensure(off_tmp + sort_bytes + 16));
+    uint64_t *keys = buf.as<uint64_t>(), *sorted = reinterpret_cast<uint64_t *>(buf.as<char>() + off_sorted);
+    int64_t *seg = reinterpret_cast<int64_t *>(buf.as<char>() + off_seg);
+    hipLaunchKernelGGL(lsqr_make_keys, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dcodes, n, m, keys);
+    LSQ_HIP(hipcub::DeviceRadixSort::SortKeys(buf.as<char>() + off_tmp, sort_bytes, keys, sorted, (int)total, 0, end_bit, s));
+    hipLaunchKernelGGL(lsqr_segments, dim3((unsigned)((cols + 1 + 255) / 256)), dim3(256), 0, s, sorted, total, cols, seg);
+    *sorted_out = sorted;
+    *seg_out = seg;
+    return LSQ_OK;
+}
+
 struct lsq_lsqr_state {
     DevBuf work;      // U, V, W, the per-block norm partials and the per-system scalars of one update
     DevBuf keys;      // (column, row) keys: unsorted, sorted, segment starts, the sort's temporary storage
@@ -315,18 +336,10 @@ int lsq_lsqr_update_codebooks(hipStream_t s, lsq_lsqr_state **pst, const float *
     S.active = reinterpret_cast<int *>(dbl + 3 * d);
     LSQ_HIP(hipMemsetAsync(base + off_sc, 0, wtotal - off_sc, s));      // scalars, done flags, double sums, the counter
 
-    // the rows sorted by code, once per call: (column << 32 | row) keys, radix sort on their 32 + ceil(log2 cols) bits
-    size_t sort_bytes = 0;
-    int end_bit = 33;
-    while (end_bit < 64 && ((uint64_t)cols >> (end_bit - 32)) != 0) ++end_bit;
-    LSQ_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)total, 0, end_bit, s));
-    const size_t off_sorted = (size_t)total * 8, off_seg = off_sorted + (size_t)total * 8, off_tmp = (off_seg + ((size_t)cols + 1) * 8 + 255) & ~(size_t)255;
-    LSQ_TRY(st->keys.ensure(off_tmp + sort_bytes + 16));
-    uint64_t *keys = st->keys.as<uint64_t>(), *sorted = reinterpret_cast<uint64_t *>(st->keys.as<char>() + off_sorted);
-    int64_t *seg = reinterpret_cast<int64_t *>(st->keys.as<char>() + off_seg);
-    hipLaunchKernelGGL(lsqr_make_keys, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dcodes, n, m, keys);
-    LSQ_HIP(hipcub::DeviceRadixSort::SortKeys(st->keys.as<char>() + off_tmp, sort_bytes, keys, sorted, (int)total, 0, end_bit, s));
-    hipLaunchKernelGGL(lsqr_segments, dim3((unsigned)((cols + 1 + 255) / 256)), dim3(256), 0, s, sorted, total, cols, seg);
+    // the rows sorted by code, once per call
+    const uint64_t *sorted = nullptr;
+    const int64_t *seg = nullptr;
+    LSQ_TRY(lsq_sort_rows_by_code(s, st->keys, dcodes, n, m, &sorted, &seg));
 
     const dim3 rows_grid((unsigned)nblocks, (unsigned)((d + TB - 1) / TB));
     const dim3 cols_grid((unsigned)((cols + 63) / 64), (unsigned)((d + TB - 1) / TB));

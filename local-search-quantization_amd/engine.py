@@ -267,6 +267,52 @@ class Engine:
             self._check(self._L.lsq_update_codebooks_dev(self._h, dX.data_ptr(), dcodes.data_ptr(), d, n, m, h, dK.data_ptr(), C.byref(it)))
         return dK, int(it.value)
 
+    # -- the sparse codebook update: SPGL1's LASSO mode (csrc/lsq_spgl1.hip) ---------------------------------
+    @staticmethod
+    def _spgl1_params(opt_tol, max_iter):
+        if opt_tol is None and max_iter is None:
+            return None
+        return _lib.Spgl1Params(float(opt_tol or 0.0), int(max_iter or 0))
+
+    def update_codebooks_spgl1(self, X, B, m, tau, K_init=None, S=-1, h=H, opt_tol=None, max_iter=None):
+        """X (n,d) f32, B (n,m) int16 1-based: host arrays -> (K (m*h,d) f32, info dict): min 1/2||A k - b||^2 s.t. ||k||_1 <= tau warm-started
+        from K_init, then only the S largest |K| kept (S < 0: all)   [lsq_update_codebooks_spgl1]"""
+        X, B = _np(X, np.float32), _np(B, np.int16)
+        n, d = X.shape if X.ndim == 2 else (-1, -1)
+        check_spgl1_args(X.shape, B.shape, m, h, tau, S, None if K_init is None else np.shape(K_init), opt_tol, max_iter)
+        K0 = None if K_init is None else _np(K_init, np.float32)
+        K = np.zeros((m * h, d), dtype=np.float32)
+        info = _lib.Spgl1Info()
+        p = self._spgl1_params(opt_tol, max_iter)
+        self._check(self._L.lsq_update_codebooks_spgl1(self._h, X.ctypes.data, B.ctypes.data, d, n, m, h, float(tau),
+                                                       None if K0 is None else K0.ctypes.data, int(S), None if p is None else C.byref(p),
+                                                       K.ctypes.data, C.byref(info)))
+        return K, info.as_dict()
+
+    def update_codebooks_spgl1_dev(self, dX, dcodes, m, tau, dK_init=None, S=-1, h=H, opt_tol=None, max_iter=None, out=None):
+        """device tensors: X (n,d) f32, codes (n,m) uint8 0-based, K_init (m*h,d) f32 or None -> (K (m*h,d) f32 tensor, info dict)
+        [lsq_update_codebooks_spgl1_dev]"""
+        import torch
+        check_spgl1_args(tuple(dX.shape), tuple(dcodes.shape), m, h, tau, S, None if dK_init is None else tuple(dK_init.shape), opt_tol, max_iter)
+        for name, t, dt in (("X", dX, torch.float32), ("codes", dcodes, torch.uint8), ("K_init", dK_init, torch.float32), ("out", out, torch.float32)):
+            if t is None:
+                continue
+            if not t.is_cuda or t.dtype != dt:
+                raise ValueError("%s must be a %s device tensor" % (name, dt))
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        n, d = dX.shape
+        dK = out if out is not None else torch.empty((m * h, d), dtype=torch.float32, device=dX.device)
+        if tuple(dK.shape) != (m * h, d):
+            raise ValueError("out must be (m*h, d) = (%d, %d)" % (m * h, d))
+        info = _lib.Spgl1Info()
+        p = self._spgl1_params(opt_tol, max_iter)
+        with self._on_torch_stream():
+            self._check(self._L.lsq_update_codebooks_spgl1_dev(self._h, dX.data_ptr(), dcodes.data_ptr(), d, n, m, h, float(tau),
+                                                               None if dK_init is None else dK_init.data_ptr(), int(S),
+                                                               None if p is None else C.byref(p), dK.data_ptr(), C.byref(info)))
+        return dK, info.as_dict()
+
     # -- the initialisers' data-parallel steps (csrc/lsq_init.hip) ----------------------------------
     def encode_viterbi(self, X, K, m, h=H):
         """X (n,d) f32, K (m*h,d) f32 (chain codebooks, zero outside their dimensions) -> B (n,m) int16 1-based: the exact chain optimum
@@ -415,6 +461,34 @@ class Engine:
 
 
 # -- host-only pieces of the path (no GPU needed) ---------------------------------------------
+
+def check_spgl1_args(xshape, bshape, m, h, tau, S, kshape=None, opt_tol=None, max_iter=None):
+    """The argument rules of lsq_update_codebooks_spgl1, checked before any device is touched: X (n, d), codes (n, m), K_init (m h, d)."""
+    import math
+    if len(xshape) != 2 or xshape[0] < 1 or xshape[1] < 1:
+        raise ValueError("X must be (n, d) with n, d >= 1, got %s" % (tuple(xshape),))
+    n, d = xshape
+    if not (isinstance(m, (int, np.integer)) and 1 <= m <= 16):
+        raise ValueError("m=%r must be an integer in 1..16" % (m,))
+    if h != H:
+        raise ValueError("h=%r unsupported: h must be 256" % (h,))
+    if tuple(bshape) != (n, m):
+        raise ValueError("codes must be (n, m) = (%d, %d), got %s" % (n, m, tuple(bshape)))
+    try:
+        t = float(tau)
+    except (TypeError, ValueError):
+        raise ValueError("tau=%r must be a number" % (tau,))
+    if math.isnan(t) or t < 0:
+        raise ValueError("tau=%r must be a number >= 0" % (tau,))
+    if not isinstance(S, (int, np.integer)) or isinstance(S, bool):
+        raise ValueError("S=%r must be an integer (< 0: no threshold)" % (S,))
+    if kshape is not None and tuple(kshape) != (m * h, d):
+        raise ValueError("K_init must be (m*h, d) = (%d, %d), got %s" % (m * h, d, tuple(kshape)))
+    if opt_tol is not None and not (0 < float(opt_tol) < 1):
+        raise ValueError("opt_tol=%r must lie in (0, 1)" % (opt_tol,))
+    if max_iter is not None and int(max_iter) < 1:
+        raise ValueError("max_iter=%r must be >= 1" % (max_iter,))
+
 
 def randinit(n, m, h=H, seed=0, global_offset=0):
     """initializations.jl:2-8 -> (n, m) int16 1-based (Philox-keyed, shard-invariant)."""

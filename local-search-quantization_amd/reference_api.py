@@ -283,6 +283,119 @@ def train_lsq_dev(dX, m, h, dB, niter, ilsiter, icmiter, randord, npert, *, seed
     return dK, dB, centers.reshape(-1).astype(np.float32), (assign + 1).reshape(1, n).astype(np.int16), obj      # B_norms 1 x n like train_lsq (LSQ.jl:84)
 
 
+def _spgl1_inputs(X, B, h, tau, prevC, S):
+    """Julia-layout arguments of the sparse codebook step -> (Xr (n, d), Br (n, m), K0 (m h, d) or None, m), checked before any device is touched."""
+    X = np.asarray(X, dtype=np.float32)
+    B = np.asarray(B)
+    if X.ndim != 2 or B.ndim != 2:
+        raise ValueError("X must be d x n and B m x n, got %s and %s" % (X.shape, B.shape))
+    d, n = X.shape
+    m = B.shape[0]
+    K0 = None
+    if prevC is not None:
+        if len(prevC) != m or any(np.shape(Cj) != (d, h) for Cj in prevC):
+            raise ValueError("prevC must hold m = %d matrices of d x h = %d x %d" % (m, d, h))
+        K0 = _K_of(prevC)
+    _engine.check_spgl1_args((n, d), (B.shape[1], m), m, h, tau, S, None if K0 is None else K0.shape)
+    if B.size and (B.min() < 1 or B.max() > h):
+        raise ValueError("codes must lie in 1..%d" % h)
+    return _X_of(X), _B_of(B.astype(np.int16)), K0, m
+
+
+def _spgl1(X, B, h, tau, prevC, S, engine, opt_tol, max_iter):
+    Xr, Br, K0, m = _spgl1_inputs(X, B, h, tau, prevC, S)
+    eng = engine or default_engine()
+    K, info = eng.update_codebooks_spgl1(Xr, Br, m, float(tau), K_init=K0, S=int(S), h=h, opt_tol=opt_tol, max_iter=max_iter)
+    return [np.ascontiguousarray(K[j * h:(j + 1) * h].T) for j in range(m)], info
+
+
+def update_codebooks_spgl1(X, B, h, tau, prevC, spgl1_path=None, V=False, *, engine=None, opt_tol=None, max_iter=None, return_info=False):
+    """src/codebook_update_sparse.jl:9-73: min 1/2 ||A k - vec(X')||^2 s.t. ||k||_1 <= tau over all d dimensions at once (A = I_d (x) sparsify_codes(B, h)),
+    warm-started from prevC, on the device (csrc/lsq_spgl1.hip: SPGL1's LASSO mode restated; the reference calls MATLAB's SPGL1).  X d x n, B m x n Int16
+    1-based, prevC m matrices d x h.  -> new C (m matrices d x h, f32) [, info dict].  `spgl1_path` is accepted and ignored: nothing calls MATLAB here."""
+    C, info = _spgl1(X, B, h, tau, prevC, -1, engine, opt_tol, max_iter)
+    if V:
+        print("SPGL1 codebook update: %d iterations, f = %e, relative gap %.2e" % (info["iterations"], info["f"], info["rel_gap"]))
+    return (C, info) if return_info else C
+
+
+def update_codebooks_spgl1_threshold(X, B, h, tau, prevC, S, spgl1_path=None, V=False, *, engine=None, opt_tol=None, max_iter=None, return_info=False):
+    """src/codebook_update_sparse.jl:75-106: update_codebooks_spgl1, then keep the S entries of K = hcat(C...) largest in |K| (ties: the lower linear
+    index -- sortperm(abs(K[:]), rev=true)) and set the others to 0.  -> C [, info]."""
+    C, info = _spgl1(X, B, h, tau, prevC, S, engine, opt_tol, max_iter)
+    if V:
+        print("%d non-zero elements after update" % info["nnz_before_threshold"])
+    return (C, info) if return_info else C
+
+
+def train_lsq_sparse(X, m, h, niter, ilsiter, icmiter, randord, npert, S, tau, B, Cinit, R, spgl1_path=None, V=True, *, seed=0, engine=None,
+                     infos=None, opt_tol=None, max_iter=None):
+    """src/lsq_sparse/LSQ_SPGL1.jl:6-120 (SLSQ): PQ codebooks Cinit (m matrices len(subdim) x h) padded to full dimension, then on RX = R'X alternate
+    {SPGL1 codebook update + top-S threshold, ilsiter x encoding_icm} niter times, recording qerror before every update; the norm codebook is k-means on
+    the squared norms of the reconstructions.  -> (C, B, R, obj, cbnorms, objs) like the reference: C in the rotated space (not rotated back).
+    `infos` (optional list) receives the info dict of every codebook update.  encoding_icm's ILS iteration counter runs from `seed`'s call 0."""
+    X = np.asarray(X, dtype=np.float32)
+    R = np.asarray(R, dtype=np.float32)
+    if X.ndim != 2:
+        raise ValueError("X must be d x n")
+    d, n = X.shape
+    if R.shape != (d, d):
+        raise ValueError("R must be d x d = %d x %d, got %s" % (d, d, R.shape))
+    if len(Cinit) != m:
+        raise ValueError("Cinit must hold m = %d codebooks" % m)
+    subdims = [slice(lo, hi) for lo, hi in _engine.splitarray(d, m)]
+    C = []
+    for i in range(m):
+        Ci = np.zeros((d, h), dtype=np.float32)
+        Ci[subdims[i], :] = np.asarray(Cinit[i], dtype=np.float32)
+        C.append(Ci)
+    B = np.asarray(B, dtype=np.int16)
+    _spgl1_inputs(X, B, h, tau, C, S)                                   # every argument checked before the device is touched
+    if int(niter) < 0 or int(ilsiter) < 0:
+        raise ValueError("niter and ilsiter must be >= 0")
+    eng = engine or default_engine()
+    RX = np.ascontiguousarray(R.T @ X)
+    if V:
+        print("Warm start error: %e" % qerror(RX, B, C, engine=eng))
+    it = 0
+
+    def update(C):
+        C, info = _spgl1(RX, B, h, tau, C, S, eng, opt_tol, max_iter)
+        if infos is not None:
+            infos.append(info)
+        if V:
+            print("%d non-zero elements. l1 norm is %e" % (info["nnz"], sum(float(np.abs(Cj).sum(dtype=np.float64)) for Cj in C)))
+        return C
+
+    def encode(B, it):
+        for _ in range(ilsiter):
+            B = encoding_icm(RX, B, C, icmiter, randord, npert, V, seed=seed, it=it, engine=eng)
+            it += 1
+        return B, it
+
+    C = update(C)
+    B, it = encode(B, it)
+    objs = np.zeros(niter, dtype=np.float32)
+    for iter_ in range(niter):
+        obj = qerror(RX, B, C, engine=eng)
+        if V:
+            print("%3d %e" % (iter_ + 1, obj))
+        C = update(C)
+        B, it = encode(B, it)
+        objs[iter_] = obj
+    from .initializers import kmeans
+    CB = reconstruct(B, C)
+    dbnorms = np.zeros(n, dtype=np.float32)
+    for j in range(CB.shape[0]):
+        dbnorms += CB[j] * CB[j]
+    centers, _, _ = kmeans(dbnorms.reshape(1, n), min(h, n), niter=100, seed=seed)
+    cbnorms = centers.reshape(-1).astype(np.float32)
+    obj = qerror(RX, B, C, engine=eng)
+    if V:
+        print("%3d %e" % (niter + 1, obj))
+    return C, B, R, obj, cbnorms, objs
+
+
 def reconstruct(B, C):
     """src/utils.jl:203-223: CB = sum_i C[i][:, B[i, :]] accumulated in codebook order from zero (f32). -> (d, n)"""
     B = np.asarray(B)
