@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 800
+#define LSQ_VERSION 900
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -287,7 +287,25 @@ LSQ_API int lsq_linscan_pq(lsq_ctx *ctx, float *dists, uint32_t *res, const uint
                            uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim);
 LSQ_API int lsq_linscan_pq_dev(lsq_ctx *ctx, float *d_dists, uint32_t *d_res, const uint8_t *d_codes, const float *d_centers, const float *d_queries,
                                int N, uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim);
-/* What the device scans (LSQ and PQ) did since the last lsq_reset_timings (times only with option "profile" = 1). */
+/* ---- (3d) exact k-NN: the ground truth of a recall figure (since v900) ---------------------------------------------------------------------------
+ * The reference reads ground truth from sift_groundtruth.ivecs (full SIFT1M base only); these compute it for any float base.
+ *   base     [n][ldb] f32, queries [nq][ldq] f32; only the first d floats of each row are read.
+ *   dist(q, i) = ((0 + e_0*e_0) + e_1*e_1) + ... + e_{d-1}*e_{d-1},   e_s = x_i[s] - q[s]       (f32, s ascending, every op rounded, no FMA)
+ *   -- the PQ table rule above with one sub-space of width d.
+ * Outputs (caller-allocated): dists [nq][nn] f32 ascending; ids [nq][nn] uint32, 0-BASED (the .ivecs convention).  The nn smallest (dist, id) pairs
+ * in lexicographic order (ties: smaller id first); NaN distances sort last.  All three functions return the same bits.
+ * LSQ_EINVAL: d < 1, ldb < d, ldq < d, nq < 1, nn < 1, nn > n, a null pointer or context.
+ *   lsq_knn_exact_cpu  host cores, std::thread workers (nthreads 0 = all): the checker and the engine-less road;
+ *   lsq_knn_exact      device, host buffers (uploaded, searched, downloaded);
+ *   lsq_knn_exact_dev  device, device buffers.  The device forms run the selection of the scans above: options "linscan_exhaustive" /
+ *                      "linscan_rank" and lsq_get_linscan_stats cover them (lut_ms stays 0). */
+LSQ_API int lsq_knn_exact_cpu(float *dists, uint32_t *ids, const float *base, const float *queries, int n, int nq, int d, int ldb, int ldq, int nn,
+                              int nthreads);
+LSQ_API int lsq_knn_exact(lsq_ctx *ctx, float *dists, uint32_t *ids, const float *base, const float *queries, int n, int nq, int d, int ldb, int ldq,
+                          int nn);
+LSQ_API int lsq_knn_exact_dev(lsq_ctx *ctx, float *d_dists, uint32_t *d_ids, const float *d_base, const float *d_queries, int n, int nq, int d,
+                              int ldb, int ldq, int nn);
+/* What the device scans (LSQ, PQ and exact k-NN) did since the last lsq_reset_timings (times only with option "profile" = 1). */
 typedef struct lsq_linscan_stats {
     int64_t queries, codes;          /* queries searched (accumulated); database size of the last call */
     int64_t candidates;              /* (dist, id) pairs written to memory: the lists the selection sorted */

@@ -15,7 +15,7 @@ from .reference_api import (  # noqa: F401
     encode_icm_cuda, encoding_icm, encode_icm_fully, get_unaries, get_binaries, veccost, qerror,
     randinit, splitarray, default_engine, linscan_lsq, linscan_pq, linscan_opq, eval_recall, quantize_norms, reconstruct,
     fvecs_read, ivecs_read, bvecs_read, update_codebooks, train_lsq, train_lsq_dev,
-    update_codebooks_spgl1, update_codebooks_spgl1_threshold, train_lsq_sparse,
+    update_codebooks_spgl1, update_codebooks_spgl1_threshold, train_lsq_sparse, knn_exact,
 )
 from .initializers import (  # noqa: F401
     train_pq, quantize_pq, train_opq, quantize_opq, train_chainq, encoding_viterbi, update_codebooks_chain, get_cbdims_chain,
@@ -27,5 +27,5 @@ __all__ = [
     "veccost", "qerror", "randinit", "splitarray", "node_order", "device_count", "distributed", "linscan_lsq", "linscan_pq", "linscan_opq", "eval_recall",
     "quantize_norms", "reconstruct", "update_codebooks", "train_lsq", "train_lsq_dev", "train_pq", "quantize_pq", "train_opq", "quantize_opq",
     "train_chainq", "encoding_viterbi", "update_codebooks_chain", "get_cbdims_chain", "fvecs_read", "ivecs_read", "bvecs_read",
-    "update_codebooks_spgl1", "update_codebooks_spgl1_threshold", "train_lsq_sparse",
+    "update_codebooks_spgl1", "update_codebooks_spgl1_threshold", "train_lsq_sparse", "knn_exact",
 ]

@@ -98,6 +98,9 @@ SIGNATURES = {
     "lsq_linscan_aqd_query": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _u32, _i, _i, _i, _i, _i]),
     "lsq_linscan_pq": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _u32, _i, _i, _i, _i, _i]),
     "lsq_linscan_pq_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _u32, _i, _i, _i, _i, _i]),
+    "lsq_knn_exact_cpu": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
+    "lsq_knn_exact": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    "lsq_knn_exact_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "lsq_quantize_norms": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "lsq_quantize_norms_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "lsq_update_codebooks": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _vp]),

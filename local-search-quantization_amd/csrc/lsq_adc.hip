@@ -45,16 +45,6 @@ constexpr int ADC_SMALL_N = 65536;           // databases up to this size: exhau
 constexpr int ADC_SCAN_THREADS = 1024;
 constexpr int ADC_KC = 1024;                 // LUT build: dimensions staged per pass
 
-__device__ inline uint32_t adc_key(float v) {                    // order-preserving: a < b  <=>  key(a) < key(b);  NaN last
-    if (v != v) return 0xffffffffu;
-    const uint32_t b = __float_as_uint(v);
-    return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
-}
-__device__ inline float adc_unkey(uint32_t k) {
-    if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
 // LUT[tile][e][s] = table entry e = j h + a of query qid(tile * QT + s);  qsel (optional) lists the query ids of this batch
 template <int QT>
 __global__ __launch_bounds__(256) void adc_lut_kernel(const float *__restrict__ Q, const float *__restrict__ K, const int *__restrict__ qsel, int q0,
@@ -189,7 +179,7 @@ __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_e
     float tf[4] = {0.0f, 0.0f, 0.0f, 0.0f};                          // thresholds as floats: emit unless dist > tau (a NaN on either side emits)
     if (MODE == 0) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) tf[c] = slot0 + c < nqb ? adc_unkey(tau[slot0 + c]) : -__builtin_inff();
+        for (int c = 0; c < 4; ++c) tf[c] = slot0 + c < nqb ? lsq_adc_unkey(tau[slot0 + c]) : -__builtin_inff();
     }
     const int total = MODE == 0 ? n : ns;
     const int first = blockIdx.y * per_block;
@@ -291,7 +281,7 @@ __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_e
                     if (!hit) continue;
                     const int slot = slot0 + c;
                     if (slot >= nqb) continue;
-                    const uint32_t key = adc_key(dv[c]);
+                    const uint32_t key = lsq_adc_key(dv[c]);
                     const uint64_t rec = ((uint64_t)key << idbits) | (uint64_t)(i + 1);      // ids are 1-BASED (:75)
                     if (MODE == 1) {
                         out[(int64_t)slot * ns + s] = rec;
@@ -408,7 +398,7 @@ __global__ void adc_gather_kernel(const uint64_t *__restrict__ sorted, const int
     const int64_t q = qsel ? qsel[slot] : q0 + slot;
     for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < nn; r += gridDim.x * blockDim.x) {
         const uint64_t rec = sorted[(int64_t)slot * cap + r];
-        dists[q * nn + r] = adc_unkey((uint32_t)(rec >> idbits));
+        dists[q * nn + r] = lsq_adc_unkey((uint32_t)(rec >> idbits));
         idx[q * nn + r] = (int)((uint32_t)(rec & ((1ull << idbits) - 1ull)) - (uint32_t)id_base);
     }
 }
@@ -435,13 +425,16 @@ void lsq_adc_free(lsq_adc_state *st) {
 namespace {
 
 // What one call searches.  LSQ (dbnorms set): K = [m h][d] codebooks, tables -2<q, c>, + dbnorms[i], 1-based ids out.  PQ / OPQ (dbnorms null):
-// K = [m][h][d] sub-space centres (d = subdim), squared-distance tables, no norm term, 0-based ids out.
+// K = [m][h][d] sub-space centres (d = subdim), squared-distance tables, no norm term, 0-based ids out.  Exact (base set): no codes, no tables;
+// lsq_knn.hip computes the squared distances to the float rows base[i * bstride ..] directly, 0-based ids out.
 struct AdcInput {
     const uint8_t *codes; int cstride;       // [n][cstride] u8 0-based, the first m bytes of a row used
     const float *Q; int qstride;             // query rows, qstride floats apart
     const float *K;
     const float *dbnorms;
     int n, m, d;
+    const float *base = nullptr; int bstride = 0;
+    bool exact() const { return base != nullptr; }
     bool pq() const { return dbnorms == nullptr; }
 };
 
@@ -485,6 +478,15 @@ int launch_scan(hipStream_t s, const float *LUT, const AdcInput &in, int nqb, in
 #undef ADC_LAUNCH
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
+}
+
+// the scan of either producer: the table walk of adc_scan_kernel, or the exact distances of lsq_knn.hip (which reads the queries itself)
+template <int QT, int MODE>
+int launch_producer(hipStream_t s, const float *LUT, const AdcInput &in, const int *qsel, int q0, int nqb, int stride, int ns, const uint32_t *tau,
+                    unsigned *count, int cap, uint64_t *out, int idbits) {
+    if (in.exact())
+        return lsq_knn_launch_scan(s, MODE, in.base, in.bstride, in.Q, in.qstride, qsel, q0, nqb, in.n, in.d, stride, ns, tau, count, cap, out, idbits);
+    return launch_scan<QT, MODE>(s, LUT, in, nqb, stride, ns, tau, count, cap, out, idbits);
 }
 
 template <int QT>
@@ -542,12 +544,12 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const Ad
     const int n = in.n, entries = in.m * LSQ_H, tiles = (nqb + QT - 1) / QT, id_base = in.pq() ? 1 : 0;
     int idbits = 1;                                   // ids 1 .. n: the records are (distance key << idbits | id), sorted on their 32 + idbits bits
     while (idbits < 32 && ((uint64_t)n >> idbits) != 0) ++idbits;
-    LSQ_TRY(st->lut.ensure(sizeof(float) * (size_t)tiles * entries * QT));
+    if (!in.exact()) LSQ_TRY(st->lut.ensure(sizeof(float) * (size_t)tiles * entries * QT));
     LSQ_TRY(st->seg.ensure(sizeof(int) * 2 * (size_t)nqb));
     LSQ_TRY(st->fail.ensure(sizeof(int) * (size_t)nqb));
     int *begin = st->seg.as<int>(), *end = begin + nqb;
     if (timed) LSQ_HIP(hipEventRecord(st->ev[0], s));
-    LSQ_TRY(launch_lut<QT>(s, in, qsel, q0, nqb, st->lut.as<float>()));
+    if (!in.exact()) LSQ_TRY(launch_lut<QT>(s, in, qsel, q0, nqb, st->lut.as<float>()));
     if (timed) LSQ_HIP(hipEventRecord(st->ev[1], s));
     const unsigned gblocks = (unsigned)((nqb + 255) / 256);
     int seg_len;
@@ -556,7 +558,7 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const Ad
         LSQ_TRY(st->keys_a.ensure(sizeof(uint64_t) * (size_t)nqb * n));
         LSQ_TRY(st->keys_b.ensure(sizeof(uint64_t) * (size_t)nqb * n));
         if (timed) { LSQ_HIP(hipEventRecord(st->ev[2], s)); }
-        LSQ_TRY((launch_scan<QT, 1>(s, st->lut.as<float>(), in, nqb, 1, n, nullptr, nullptr, n, st->keys_a.as<uint64_t>(), idbits)));
+        LSQ_TRY((launch_producer<QT, 1>(s, st->lut.as<float>(), in, qsel, q0, nqb, 1, n, nullptr, nullptr, n, st->keys_a.as<uint64_t>(), idbits)));
         if (timed) LSQ_HIP(hipEventRecord(st->ev[3], s));
         hipLaunchKernelGGL(adc_segments_kernel, dim3(gblocks), dim3(256), 0, s, (const unsigned *)nullptr, nqb, n, nn, begin, end, (int *)nullptr);
         LSQ_TRY(sort_segments(st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), (int64_t)nqb * n, nqb, begin, end, 32 + idbits));
@@ -571,13 +573,14 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const Ad
         LSQ_TRY(st->tau.ensure(sizeof(uint32_t) * (size_t)nqb));
         LSQ_TRY(st->count.ensure(sizeof(unsigned) * (size_t)nqb));
         // sample -> thresholds
-        LSQ_TRY((launch_scan<QT, 2>(s, st->lut.as<float>(), in, nqb, P.stride, P.ns, nullptr, nullptr, P.ns, st->keys_b.as<uint64_t>(), idbits)));
+        LSQ_TRY((launch_producer<QT, 2>(s, st->lut.as<float>(), in, qsel, q0, nqb, P.stride, P.ns, nullptr, nullptr, P.ns, st->keys_b.as<uint64_t>(),
+                                        idbits)));
         hipLaunchKernelGGL(adc_rank_select_kernel, dim3((unsigned)nqb), dim3(256), 0, s, st->keys_b.as<uint32_t>(), P.r, st->tau.as<uint32_t>());
         LSQ_HIP(hipMemsetAsync(st->count.p, 0, sizeof(unsigned) * (size_t)nqb, s));
         if (timed) LSQ_HIP(hipEventRecord(st->ev[2], s));
         // the scan proper
-        LSQ_TRY((launch_scan<QT, 0>(s, st->lut.as<float>(), in, nqb, 1, n, st->tau.as<uint32_t>(), st->count.as<unsigned>(), P.cap,
-                                    st->keys_a.as<uint64_t>(), idbits)));
+        LSQ_TRY((launch_producer<QT, 0>(s, st->lut.as<float>(), in, qsel, q0, nqb, 1, n, st->tau.as<uint32_t>(), st->count.as<unsigned>(), P.cap,
+                                        st->keys_a.as<uint64_t>(), idbits)));
         if (timed) LSQ_HIP(hipEventRecord(st->ev[3], s));
         hipLaunchKernelGGL(adc_segments_kernel, dim3(gblocks), dim3(256), 0, s, st->count.as<unsigned>(), nqb, P.cap, nn, begin, end, st->fail.as<int>());
         LSQ_TRY(sort_segments(st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), (int64_t)nqb * P.cap, nqb, begin, end, 32 + idbits));
@@ -601,6 +604,7 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const Ad
         LSQ_HIP(hipEventElapsedTime(&b, st->ev[1], st->ev[2]));
         LSQ_HIP(hipEventElapsedTime(&c, st->ev[2], st->ev[3]));
         LSQ_HIP(hipEventElapsedTime(&e, st->ev[3], st->ev[4]));
+        if (in.exact()) a = 0.0f;                     // no tables
         stats->lut_ms += a; stats->sample_ms += b; stats->scan_ms += c; stats->select_ms += e;
     } else {
         LSQ_HIP(hipStreamSynchronize(s));
@@ -720,6 +724,35 @@ int lsq_adc_search_pq_host(hipStream_t s, lsq_adc_state **pst, float *dists, int
     LSQ_HIP(hipMemcpyAsync(st->h_k.p, centers, sizeof(float) * (size_t)m * LSQ_H * subdim, hipMemcpyHostToDevice, s));
     LSQ_TRY(lsq_adc_search_pq(s, pst, st->h_dists.as<float>(), st->h_idx.as<int>(), st->h_codes.as<uint8_t>(), cstride, st->h_k.as<float>(),
                               st->h_q.as<float>(), qstride, nq, n, m, subdim, nn, force_exhaustive, sample_override, stats, timed));
+    LSQ_HIP(hipMemcpyAsync(dists, st->h_dists.p, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
+    LSQ_HIP(hipMemcpyAsync(idx, st->h_idx.p, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
+    LSQ_HIP(hipStreamSynchronize(s));
+    return LSQ_OK;
+}
+
+// exact k-NN: base rows [n][ldb], query rows [nq][ldq] (d floats of each read); ids out 0-based
+int lsq_adc_search_exact(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const float *base, int ldb, const float *Q, int ldq, int nq, int n,
+                         int d, int nn, int force_exhaustive, int sample_override, lsq_linscan_stats *stats, int timed) {
+    AdcInput in{nullptr, 0, Q, ldq, nullptr, nullptr, n, 0, d};
+    in.base = base;
+    in.bstride = ldb;
+    return adc_search(s, pst, dists, idx, in, nq, nn, force_exhaustive, sample_override, stats, timed);
+}
+
+// host-buffer entry: upload the rows up to their d-th float, search, download
+int lsq_adc_search_exact_host(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const float *base, int ldb, const float *Q, int ldq, int nq,
+                              int n, int d, int nn, int force_exhaustive, int sample_override, lsq_linscan_stats *stats, int timed) {
+    if (!*pst) *pst = new lsq_adc_state();
+    lsq_adc_state *st = *pst;
+    const size_t b_floats = (size_t)(n - 1) * ldb + d, q_floats = (size_t)(nq - 1) * ldq + d;
+    LSQ_TRY(st->h_k.ensure(sizeof(float) * b_floats));
+    LSQ_TRY(st->h_q.ensure(sizeof(float) * q_floats));
+    LSQ_TRY(st->h_dists.ensure(sizeof(float) * (size_t)nq * nn));
+    LSQ_TRY(st->h_idx.ensure(sizeof(int) * (size_t)nq * nn));
+    LSQ_HIP(hipMemcpyAsync(st->h_k.p, base, sizeof(float) * b_floats, hipMemcpyHostToDevice, s));
+    LSQ_HIP(hipMemcpyAsync(st->h_q.p, Q, sizeof(float) * q_floats, hipMemcpyHostToDevice, s));
+    LSQ_TRY(lsq_adc_search_exact(s, pst, st->h_dists.as<float>(), st->h_idx.as<int>(), st->h_k.as<float>(), ldb, st->h_q.as<float>(), ldq, nq, n, d, nn,
+                                 force_exhaustive, sample_override, stats, timed));
     LSQ_HIP(hipMemcpyAsync(dists, st->h_dists.p, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
     LSQ_HIP(hipMemcpyAsync(idx, st->h_idx.p, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
     LSQ_HIP(hipStreamSynchronize(s));

@@ -421,6 +421,25 @@ extern "C" int lsq_linscan_pq(lsq_ctx *c, float *dists, uint32_t *res, const uin
                                   N, B / 8, subdim, K, c->adc_exhaustive, c->adc_rank, &c->adc_stats, c->profile);
 }
 
+// exact k-NN: the host drop-in's checks (lsq_linscan.hip), then the device search (lsq_knn.hip under lsq_adc.hip's selection)
+extern "C" int lsq_knn_exact_dev(lsq_ctx *c, float *d_dists, uint32_t *d_ids, const float *d_base, const float *d_queries, int n, int nq, int d, int ldb,
+                                 int ldq, int nn) {
+    if (!c) { lsq_set_error("lsq_knn_exact_dev: null context"); return LSQ_EINVAL; }
+    LSQ_TRY(lsq_knn_exact_check("lsq_knn_exact_dev", d_dists, d_ids, d_base, d_queries, n, nq, d, ldb, ldq, nn));
+    LSQ_TRY(use_device(c));
+    return lsq_adc_search_exact(c->stream, &c->adc, d_dists, reinterpret_cast<int *>(d_ids), d_base, ldb, d_queries, ldq, nq, n, d, nn, c->adc_exhaustive,
+                                c->adc_rank, &c->adc_stats, c->profile);
+}
+
+extern "C" int lsq_knn_exact(lsq_ctx *c, float *dists, uint32_t *ids, const float *base, const float *queries, int n, int nq, int d, int ldb, int ldq,
+                             int nn) {
+    if (!c) { lsq_set_error("lsq_knn_exact: null context"); return LSQ_EINVAL; }
+    LSQ_TRY(lsq_knn_exact_check("lsq_knn_exact", dists, ids, base, queries, n, nq, d, ldb, ldq, nn));
+    LSQ_TRY(use_device(c));
+    return lsq_adc_search_exact_host(c->stream, &c->adc, dists, reinterpret_cast<int *>(ids), base, ldb, queries, ldq, nq, n, d, nn, c->adc_exhaustive,
+                                     c->adc_rank, &c->adc_stats, c->profile);
+}
+
 extern "C" int lsq_get_linscan_stats(lsq_ctx *c, lsq_linscan_stats *out) {
     if (!c || !out) { lsq_set_error("lsq_get_linscan_stats: null argument"); return LSQ_EINVAL; }
     *out = c->adc_stats;

@@ -218,6 +218,16 @@ int lsq_launch_viterbi(hipStream_t s, const float *U, const float *T, int64_t n,
 int lsq_launch_unary_argmin(hipStream_t s, const float *U, int64_t n, int m, uint8_t *codes, float *minval);     // PQ.jl:12-41, kmeans.jl:6-75; minval optional [n][m]
 
 // ---- device ADC scan (lsq_adc.hip) ----------------------------------------------------------------------------------------------------
+// distance keys of the scans' records: order-preserving (a < b  <=>  key(a) < key(b)), NaN last
+__device__ inline uint32_t lsq_adc_key(float v) {
+    if (v != v) return 0xffffffffu;
+    const uint32_t b = __float_as_uint(v);
+    return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+}
+__device__ inline float lsq_adc_unkey(uint32_t k) {
+    if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
+    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
 struct lsq_adc_state;      // buffers of the scan, owned by the context
 void lsq_adc_free(lsq_adc_state *st);
 // device pointers; force_exhaustive / rank_override: test hooks (options "linscan_exhaustive", "linscan_rank")
@@ -233,6 +243,19 @@ int lsq_adc_search_pq(hipStream_t s, lsq_adc_state **st, float *dists, int *idx,
 int lsq_adc_search_pq_host(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const uint8_t *codes, int cstride, const float *centers,
                            const float *Q, int qstride, int nq, int n, int m, int subdim, int nn, int force_exhaustive, int rank_override,
                            lsq_linscan_stats *stats, int timed);
+
+// exact k-NN (no tables; lsq_knn.hip produces the distances for the same selection): base rows [n][ldb], query rows [nq][ldq], d floats of each
+// read; ids out 0-based
+int lsq_adc_search_exact(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const float *base, int ldb, const float *Q, int ldq, int nq, int n,
+                         int d, int nn, int force_exhaustive, int rank_override, lsq_linscan_stats *stats, int timed);
+int lsq_adc_search_exact_host(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const float *base, int ldb, const float *Q, int ldq, int nq,
+                              int n, int d, int nn, int force_exhaustive, int rank_override, lsq_linscan_stats *stats, int timed);
+// the exact scan of one batch in adc_scan_kernel's three modes (0: against tau, 1: every record, 2: sample keys); qsel optional
+int lsq_knn_launch_scan(hipStream_t s, int mode, const float *X, int ldb, const float *Q, int ldq, const int *qsel, int q0, int nqb, int n, int d,
+                        int stride, int ns, const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits);
+// argument checks of exact k-NN (lsq_linscan.hip), shared by the host drop-in and the device search
+int lsq_knn_exact_check(const char *fn, const void *dists, const void *ids, const void *base, const void *queries, int n, int nq, int d, int ldb,
+                        int ldq, int nn);
 
 // argument checks of the PQ / OPQ scan (lsq_linscan.hip), shared by the host drop-in and the device scan
 int lsq_linscan_pq_check(const char *fn, const void *dists, const void *res, const void *codes, const void *centers, const void *queries, int N,

@@ -12,7 +12,7 @@
 //   dist(i)    = (((0 + table[0*h + b_i0]) + table[1*h + b_i1]) + ...) + dbnorms[i]
 //   result     = the nn smallest (dist, id) pairs in lexicographic order, ids 1-BASED like the reference (:75).
 //
-// Below it, the reference's other scan (PQ / OPQ codes, no norm term): lsq_linscan_aqd_query.
+// Below it, the reference's other scan (PQ / OPQ codes, no norm term): lsq_linscan_aqd_query; then exact k-NN (lsq_knn_exact_cpu).
 #include <algorithm>
 #include <cstring>
 #include <thread>
@@ -187,6 +187,85 @@ extern "C" int lsq_linscan_aqd_query(float *dists, uint32_t *res, const uint8_t 
     for (int64_t t = 0; t < nt; ++t) {
         const int64_t q0 = (int64_t)NQ * t / nt, q1 = (int64_t)NQ * (t + 1) / nt;
         pool.emplace_back(pq_scan_queries, dists, res, codes, centers, queries, q0, q1, N, B / 8, K, dim1codes, dim1queries, subdim);
+    }
+    for (auto &th : pool) th.join();
+    return LSQ_OK;
+}
+
+// ---- exact k-NN (ground truth; the device form is lsq_knn.hip):
+//
+//   dist(q, i) = ((0 + e_0 e_0) + e_1 e_1) + ...,   e_s = x_i[s] - q[s]      (f32, s ascending; no FMA)
+//   result     = the nn smallest (dist, id) pairs in lexicographic order, ids 0-BASED uint32, NaN last
+//
+// -- the PQ table rule above with one sub-space of width d.  Four queries share a pass over the base (four independent add chains per row).
+namespace {
+
+void knn_queries(float *dists, uint32_t *ids, const float *base, const float *queries, int q0, int q1, int n, int d, int ldb, int ldq, int nn) {
+    constexpr int QB = 4;
+    std::vector<uint64_t> heap[QB];
+    for (auto &h : heap) h.reserve((size_t)nn + 1);
+    for (int qa = q0; qa < q1; qa += QB) {
+        const int nb = q1 - qa < QB ? q1 - qa : QB;
+        const float *qp[QB];
+        for (int b = 0; b < QB; ++b) qp[b] = queries + (size_t)(qa + (b < nb ? b : 0)) * ldq;
+        for (auto &h : heap) h.clear();
+        const float *x = base;
+        for (int i = 0; i < n; ++i, x += ldb) {
+            float acc[QB] = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int s = 0; s < d; ++s) {
+                const float xs = x[s];
+                for (int b = 0; b < QB; ++b) {
+                    const float e = xs - qp[b][s];
+                    acc[b] += e * e;                                     // product rounded, then the add (-ffp-contract=off)
+                }
+            }
+            for (int b = 0; b < nb; ++b) {
+                const uint64_t cand = pq_key(acc[b], (uint32_t)i);
+                std::vector<uint64_t> &h = heap[b];
+                if ((int)h.size() < nn) {
+                    h.push_back(cand);
+                    std::push_heap(h.begin(), h.end());                 // max-heap on (dist, id)
+                } else if (cand < h.front()) {
+                    std::pop_heap(h.begin(), h.end());
+                    h.back() = cand;
+                    std::push_heap(h.begin(), h.end());
+                }
+            }
+        }
+        for (int b = 0; b < nb; ++b) {
+            std::sort_heap(heap[b].begin(), heap[b].end());              // ascending (dist, id)
+            const size_t q = (size_t)(qa + b);
+            for (int j = 0; j < nn; ++j) {
+                dists[q * nn + j] = pq_unkey(heap[b][(size_t)j]);
+                ids[q * nn + j] = (uint32_t)heap[b][(size_t)j];
+            }
+        }
+    }
+}
+
+}  // namespace
+
+// Argument checks shared with the device search (lsq_api.hip): 0 or LSQ_EINVAL with the message set.
+int lsq_knn_exact_check(const char *fn, const void *dists, const void *ids, const void *base, const void *queries, int n, int nq, int d, int ldb,
+                        int ldq, int nn) {
+    if (d < 1 || ldb < d || ldq < d) { lsq_set_error("%s: needs d >= 1, ldb >= d, ldq >= d (got d=%d ldb=%d ldq=%d)", fn, d, ldb, ldq); return LSQ_EINVAL; }
+    if (nq < 1) { lsq_set_error("%s: needs nq >= 1 (got %d)", fn, nq); return LSQ_EINVAL; }
+    if (nn < 1 || nn > n) { lsq_set_error("%s: needs 1 <= nn <= n (got nn=%d n=%d)", fn, nn, n); return LSQ_EINVAL; }
+    if (!dists || !ids || !base || !queries) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    return LSQ_OK;
+}
+
+extern "C" int lsq_knn_exact_cpu(float *dists, uint32_t *ids, const float *base, const float *queries, int n, int nq, int d, int ldb, int ldq, int nn,
+                                 int nthreads) {
+    LSQ_TRY(lsq_knn_exact_check("lsq_knn_exact_cpu", dists, ids, base, queries, n, nq, d, ldb, ldq, nn));
+    int nt = nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency();
+    if (nt < 1) nt = 1;
+    if (nt > nq) nt = nq;
+    std::vector<std::thread> pool;
+    pool.reserve((size_t)nt);
+    for (int t = 0; t < nt; ++t) {
+        const int q0 = (int)((int64_t)nq * t / nt), q1 = (int)((int64_t)nq * (t + 1) / nt);
+        pool.emplace_back(knn_queries, dists, ids, base, queries, q0, q1, n, d, ldb, ldq, nn);
     }
     for (auto &th : pool) th.join();
     return LSQ_OK;

@@ -213,6 +213,37 @@ class Engine:
                                                    n, nq, 8 * m, int(k), dc, dq, int(subdim)))
         return dists, ids
 
+    def knn_exact(self, Xb, Xq, k):
+        """Exact k-NN (the ground truth of a recall figure).  Xb (n, d) base rows, Xq (nq, d) queries: host arrays.
+        -> dists (nq,k) float32 ascending, ids (nq,k) uint32 0-BASED; ties by smaller id, NaN last   [lsq_knn_exact]"""
+        Xb, Xq = _np(Xb, np.float32), _np(Xq, np.float32)
+        if Xb.ndim != 2 or Xq.ndim != 2 or Xb.shape[1] != Xq.shape[1]:
+            raise ValueError("shape mismatch: base %s queries %s" % (Xb.shape, Xq.shape))
+        (n, d), nq = Xb.shape, Xq.shape[0]
+        dists = np.zeros((nq, k), dtype=np.float32)
+        ids = np.zeros((nq, k), dtype=np.uint32)
+        self._check(self._L.lsq_knn_exact(self._h, dists.ctypes.data, ids.ctypes.data, Xb.ctypes.data, Xq.ctypes.data, n, nq, d, d, d, int(k)))
+        return dists, ids
+
+    def knn_exact_dev(self, dXb, dXq, k):
+        """The same on device-resident f32 torch tensors (n, d) / (nq, d); row views with unit column stride are read in place.
+        -> (dists (nq,k) f32, ids (nq,k) 0-based) tensors; the ids tensor is int32 holding the uint32 bits   [lsq_knn_exact_dev]"""
+        import torch
+        assert dXb.is_cuda and dXq.is_cuda and dXb.dtype == torch.float32 and dXq.dtype == torch.float32, "device f32 tensors required"
+        if dXb.dim() != 2 or dXq.dim() != 2 or dXb.shape[1] != dXq.shape[1]:
+            raise ValueError("shape mismatch: base %s queries %s" % (tuple(dXb.shape), tuple(dXq.shape)))
+        (n, d), nq = dXb.shape, dXq.shape[0]
+        for t in (dXb, dXq):
+            if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < d):
+                raise ValueError("rows must be unit-stride and at least d floats apart (got strides %s)" % (t.stride(),))
+        ldb = dXb.stride(0) if n > 1 else d
+        ldq = dXq.stride(0) if nq > 1 else d
+        dists = torch.empty((nq, k), dtype=torch.float32, device=dXq.device)
+        ids = torch.empty((nq, k), dtype=torch.int32, device=dXq.device)
+        with self._on_torch_stream():
+            self._check(self._L.lsq_knn_exact_dev(self._h, dists.data_ptr(), ids.data_ptr(), dXb.data_ptr(), dXq.data_ptr(), n, nq, d, ldb, ldq, int(k)))
+        return dists, ids
+
     def quantize_norms(self, B, K, cbnorms, m, h=H):
         """B (n,m) int16 1-based, K (m*h,d), cbnorms (<= 256,): host arrays.
         -> idx (n,) int16 1-based index of the nearest norm centroid, dbnorms (n,) = cbnorms[idx-1], norms (n,) unquantised   [lsq_quantize_norms]"""
