@@ -3,7 +3,7 @@
 // Replaces (does NOT translate) the reference's CUDA kernels src/encodings/cuda/cudautils.cu:
 //   condition_icm3 (:236-339)  -> icm_walk_kernel  (LDS-staged table slices, slice-major unary stream)
 //   perturb        (:27-80)    -> perturb_kernel   (Philox counter RNG, no state buffer)
-//   veccost2       (:145-183)  -> cost_kernel / cost2_kernel (fused with the accept rule)
+//   veccost2       (:145-183)  -> cost4_kernel / cost4w_kernel (fused with the accept rule)
 //   setup_kernel / vec_add     -> gone (counter-based RNG; ||c||^2 is the GEMM epilogue)
 // Semantics follow the reference CPU path (src/encodings/encode_icm.jl), restated in
 // oracle/lsq_oracle.c: conditioning adds in ascending k (plain f32 adds), argmin = LOWEST index
@@ -25,8 +25,6 @@
 
 #include "lsq_wave.h"
 #include <atomic>
-
-#include "lsq_cost.h"
 
 namespace {
 
@@ -422,6 +420,51 @@ __global__ __launch_bounds__(256) void icm_wave_kernel(const float *__restrict__
             if (stat_s[e]) atomicAdd(active_total + e, (unsigned long long)stat_s[e]);
 }
 
+// ---- perturbation (cudautils.cu:27-80 / encode_icm.jl:55-70) ------------------------------------
+// npert distinct positions (selection sampling, ascending) of the record w get uniform codes; Philox keyed by (seed, global index, ILS iteration)
+__device__ inline bool perturb_record(uint64_t (&w)[2], int m, int npert, uint64_t seed, uint32_t it, uint64_t gi) {
+    // Same stream as orc_perturb (word p decides position p, word 16 + p is its value), drawn BLOCKWISE: the selection words of positions 4 g .. 4 g + 3
+    // are Philox block g, their value words block 4 + g -- both computed unconditionally, once per group.  (Round 4 drew every value word with its own
+    // Philox call inside the data-dependent branch: up to 2 + m blocks per wave, ~80 quarter-rate multiplies each -- a fifth of the cost pass.)
+    int need = npert < m ? npert : m;
+    bool changed = false;
+    for (int g = 0; 4 * g < m && need > 0; ++g) {
+        const lsq_u32x4 sel = lsq_rng_block(seed, gi, it, LSQ_DOM_PERTURB, (uint32_t)g);
+        const lsq_u32x4 vals = lsq_rng_block(seed, gi, it, LSQ_DOM_PERTURB, (uint32_t)(4 + g));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int pp = 4 * g + e;
+            if (pp < m && need > 0 && lsq_mulhi32(sel.v[e], (uint32_t)(m - pp)) < (uint32_t)need) {
+                const uint64_t val = lsq_mulhi32(vals.v[e], LSQ_H);
+                const int sh = 8 * (pp & 7);
+                changed |= (((w[pp >> 3] >> sh) & 0xffull) != val);
+                w[pp >> 3] = (w[pp >> 3] & ~(0xffull << sh)) | (val << sh);
+                --need;
+            }
+        }
+    }
+    return changed;
+}
+
+// The cost kernels can perturb for the NEXT ILS iteration on their way out (lsq_perturb_next::on): the lane that looked at vector i knows its
+// final record (accepted candidate or current one) and validity word, so the separate pass over the records and its launch disappear.
+template <int CS>
+__device__ inline void perturb_next_store(const lsq_perturb_next &pn, int64_t i, const uint32_t (&fin)[CS / 4], unsigned short vfin) {
+    uint64_t w[2];
+    w[0] = (uint64_t)fin[0] | ((uint64_t)fin[1] << 32);
+    w[1] = (CS == 16) ? ((uint64_t)fin[CS / 4 - 2] | ((uint64_t)fin[CS / 4 - 1] << 32)) : 0ull;
+#ifdef LSQ_TUNING
+    if (pn.abl & 16) return;
+    const bool changed = (pn.abl & 1) ? false : perturb_record(w, pn.m, pn.npert, pn.seed, pn.it, pn.goff + (uint64_t)i);
+#else
+    const bool changed = perturb_record(w, pn.m, pn.npert, pn.seed, pn.it, pn.goff + (uint64_t)i);
+#endif
+    uint64_t *q = reinterpret_cast<uint64_t *>(pn.dst + i * CS);
+    q[0] = w[0];
+    if (CS == 16) q[1] = w[1];
+    if (pn.vdst) pn.vdst[i] = changed ? (unsigned short)0 : vfin;      // a changed code invalidates every node
+}
+
 template <int CS>
 __global__ __launch_bounds__(256) void perturb_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int64_t n,
                                                       int m, int npert, uint64_t seed, uint32_t it, uint64_t goff,
@@ -443,257 +486,250 @@ __global__ __launch_bounds__(256) void perturb_kernel(const uint8_t *__restrict_
 // ---- cost (+ accept) ----------------------------------------------------------------------------
 // utils.jl:225-254 per vector, reduction order = oracle cost_one(); mode 1 applies
 // encode_icm.jl:178-186 (keep the new codes iff strictly better) and counts ==/< .
-template <int M>
-__global__ __launch_bounds__(256) void cost_kernel(const float *__restrict__ X, const float *__restrict__ K,
-                                                   const uint8_t *rec, uint8_t *cur, float *__restrict__ prev,
-                                                   unsigned long long *__restrict__ counters, int64_t n, int d, int mode,
-                                                   const unsigned short *vnew, unsigned short *vcur, const lsq_perturb_next pn) {
-    constexpr int CS = (M <= 8) ? 8 : 16;
-    constexpr int RW = CS / 4;
-    constexpr int NV = 2;                     // vectors in flight per wave (memory-level parallelism)
-    const int lane = threadIdx.x & 63;
-    const int64_t nwaves = (int64_t)gridDim.x * 4;
-    const int64_t w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    unsigned n_eq = 0, n_lt = 0;
-    // A wave takes 64 consecutive vectors, lane l looks at vector base + l: in accept mode a vector whose candidate record
-    // equals its current record has, bit for bit, the cost it already has (same codes, same arithmetic) -- it is counted as
-    // "equal" (encode_icm_cuda.jl:199-204) without touching X or the codebooks.  ~60 % of the vectors from the second ILS
-    // iteration on.  (A NaN cost is never "equal" in the reference's comparison, so those are evaluated.)
-    for (int64_t base = w * 64; base < n; base += nwaves * 64) {
-        const int64_t il = base + lane;
-        const bool live = il < n;
-        const int64_t ic = live ? il : n - 1;
-        uint32_t rn[RW], cw[RW];
-        bool same = (mode == 1);
-#pragma unroll
-        for (int q = 0; q < RW; ++q) {
-            rn[q] = reinterpret_cast<const uint32_t *>(rec + ic * CS)[q];
-            cw[q] = (mode == 1) ? reinterpret_cast<const uint32_t *>(cur + ic * CS)[q] : rn[q];
-            same = same && (rn[q] == cw[q]);
-        }
-        const float pl = (mode == 1) ? prev[ic] : 0.0f;
-        const bool skip = live && same && (pl == pl);
-        n_eq += (unsigned)__popcll(__ballot(skip)) * (lane == 0 ? 1u : 0u);
-        unsigned short vfin = (live && vcur) ? vcur[il] : (unsigned short)0;       // the vector's validity word after this kernel (for the fused perturbation)
-        const unsigned short vn = (live && vcur && mode == 1) ? vnew[il] : (unsigned short)0;
-        if (same && live && vcur) { vfin = (unsigned short)(vfin | vn); vcur[il] = vfin; }      // same tuple: what the sweeps learnt about it is kept
-        uint64_t accepted = 0;                                                       // bit l: the candidate of vector base + l replaced the current record
-        uint64_t todo = __ballot(live && !skip);
-        while (todo) {
-            CodeRec cr[NV];
-            int64_t ii[NV];
-            float pcv[NV], part[NV];
-            bool have[NV];
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {        // every independent load is issued up front
-                have[v] = todo != 0;
-                const int src = have[v] ? __builtin_ctzll(todo) : 0;
-                if (have[v]) todo &= todo - 1;
-                ii[v] = base + src;
-                cr[v].lo = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)rn[0], src) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)rn[1], src) << 32);
-                cr[v].hi = 0;
-                if (RW == 4) cr[v].hi = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)rn[RW - 2], src) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)rn[RW - 1], src) << 32);
-                pcv[v] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pl), src));
-                part[v] = 0.0f;
-            }
-            for (int t0 = 0; t0 < d; t0 += 64) {
-                const int t = t0 + lane;
-                const bool valid = t < d;
-                const int tt = valid ? t : 0;
-                float xv[NV], kv[NV][M];
-#pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    xv[v] = X[ii[v] * (int64_t)d + tt];
-#pragma unroll
-                    for (int k = 0; k < M; ++k) kv[v][k] = K[((int64_t)(k * LSQ_H) + cr[v].get(k)) * d + tt];
-                }
-#pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    float cb = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < M; ++k) cb = cb + kv[v][k];          // k ascending from 0 (utils.jl:238-244)
-                    const float r = cb - xv[v];
-                    const float sq = r * r;                                   // never fused (-ffp-contract=off)
-                    part[v] = part[v] + (valid ? sq : 0.0f);                  // lane partial: t = lane + 64 q, q ascending
-                }
-            }
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const float cost = wave_sum_tree(part[v]);
-                if (!have[v]) continue;
-                if (mode == 0) {
-                    if (lane == 0) prev[ii[v]] = cost;
-                } else {
-                    const float pc = pcv[v];
-                    if (lane == 0) n_eq += (cost == pc);
-                    if (cost < pc) {                                          // strict improvement only (encode_icm.jl:183-186)
-                        accepted |= 1ull << (int)(ii[v] - base);
-                        if (lane == 0) {
-                            ++n_lt;
-                            prev[ii[v]] = cost;
-                            uint64_t *q = reinterpret_cast<uint64_t *>(cur + ii[v] * CS);
-                            q[0] = cr[v].lo;
-                            if (CS == 16) q[1] = cr[v].hi;
-                            if (vcur) vcur[ii[v]] = vnew[ii[v]];
-                        }
-                    }
-                }
-            }
-        }
-        if (pn.on && live) {
-            const bool acc = (accepted >> lane) & 1ull;
-            uint32_t fin[RW];
-#pragma unroll
-            for (int q = 0; q < RW; ++q) fin[q] = acc ? rn[q] : cw[q];
-            perturb_next_store<CS>(pn, il, fin, acc ? vn : vfin);
-        }
+//
+// The four floats that lane lp of a row owns in the 64-float step of d starting at c, in 4 / VW loads of VW floats; load s starts at
+// c + 16 VW s + VW lp, so that the row's 16 lanes read one contiguous piece.  VW = 4: c + 4 lp .. + 3 (d % 4 == 0, p 16-byte aligned); VW = 1:
+// c + lp + {0, 16, 32, 48} (any d, any float alignment).  A load that starts at or past d reads p[off] instead: the caller masks it, and neither
+// the last x row nor the last codeword row is read past its end.
+template <int VW>
+__device__ inline int load_start(int c, int lp, int s) { return c + 16 * VW * s + VW * lp; }
+template <int VW, typename OFF>
+__device__ inline f32x4 load4(const float *p, OFF off, int c, int lp, int d) {
+    if constexpr (VW == 4) {
+        const int t = load_start<VW>(c, lp, 0);
+        return *reinterpret_cast<const f32x4 *>(p + (size_t)(off + (OFF)(t < d ? t : 0)));
     }
-    if (mode == 1 && lane == 0 && (n_eq | n_lt)) {
-        if (n_eq) atomicAdd(&counters[0], (unsigned long long)n_eq);
-        if (n_lt) atomicAdd(&counters[1], (unsigned long long)n_lt);
+    f32x4 v;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int t = load_start<VW>(c, lp, s);
+        v[s] = p[(size_t)(off + (OFF)(t < d ? t : 0))];
     }
+    return v;
 }
 
-// Even d: half a wave per vector, 8-byte loads.  Lane l' (0..31) of a half owns dimensions
-// t = 128c + {2l', 2l'+1, 2l'+64, 2l'+65}: the two residues x = 2l', 2l'+1 (mod 64) of the canonical 64 strided
-// partial sums, each accumulated in ascending t, so the reduction order is exactly oracle cost_one()'s:
-// level 1 in-lane (p[2l'] + p[2l'+1]), levels 2..32 across the 32 lanes of the half (DPP), result in the
-// half's last lane.  Half the load instructions of cost_kernel and twice the bytes per instruction.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+// levels x 2 .. x 16 of the pairwise tree across the 16 lanes of a row (f32 add commutes: both lanes of a pair get the same bits)
+__device__ inline float row_sum16(float v) {
+    v = v + dpp_self<DPP_XOR1, 0xf>(v);
+    v = v + dpp_self<DPP_XOR2, 0xf>(v);
+    v = v + dpp_self<DPP_HALF_MIRROR, 0xf>(v);
+    return v + dpp_self<DPP_MIRROR, 0xf>(v);
+}
 
-template <int M>
-__global__ __launch_bounds__(256) void cost2_kernel(const float *__restrict__ X, const float *__restrict__ K,
-                                                    const uint8_t *rec, uint8_t *cur, float *__restrict__ prev,
-                                                    unsigned long long *__restrict__ counters, int64_t n, int d, int mode,
-                                                    const unsigned short *vnew, unsigned short *vcur, const lsq_perturb_next pn) {
+// A QUARTER wave (one 16-lane DPP row) per vector.  Lane l' (0..15) of a row owns four of the canonical 64 strided partial sums (residues of t
+// mod 64, load4 above), each accumulated in ascending t; the reduction is oracle cost_one()'s pairwise tree for either load width VW.  VW = 4:
+// residues 4 l' .. 4 l' + 3, levels 1 and 2 in-lane ((p0 + p1) + (p2 + p3)), levels 4 .. 32 across the row.  VW = 1: residues l' + 16 s, levels
+// 1 .. 8 across the row for each s, levels 16 and 32 in-lane.  So both widths give the same bits.  (The layout of VW = 4 with 4-byte loads, a
+// 16-byte stride across the lanes, measured twice as slow as this one.)
+//
+// Round 5 rewrite (same arithmetic, same results).  Measured on the round-4 kernel: the pass took 212-340 us where its own memory traffic, replayed by
+// tools/ubench_cost.hip, needs 100-280 us -- the rest was structure: (i) the batch preamble (candidate record, current record, cost, two validity
+// words) compiled into FIVE dependent round trips (a load, a wait, a branch, the next load); (ii) every accepted vector stored its record / cost and
+// re-LOADED its validity word inside the round (a wait for a scattered load in front of the next round's gathers); (iii) one 64-float step of d per
+// wait.  Now: MODE / HASV are template parameters, so the preamble is one group of unconditional loads; a round only computes -- its four costs
+// travel to the lanes that own the vectors (v_readlane / select) and the batch ends with lane-parallel, coalesced stores of whatever was
+// accepted; NQ steps of d (two for d >= 128: 18 sixteen-byte loads per lane) are in flight per wait.
+template <int M, int MODE, int HASV, int NQ, int VW>
+__device__ inline void cost4_body(const float *__restrict__ X, const float *__restrict__ K,
+                                  const uint8_t *rec, uint8_t *cur, float *__restrict__ prev,
+                                  unsigned long long *__restrict__ counters, int64_t n, int64_t w, int64_t nwaves, int d,
+                                  const unsigned short *vnew, unsigned short *vcur, const lsq_perturb_next &pn) {
+    // wave w of nwaves takes the 64-vector batches 64 (w + q nwaves)
+    static_assert(VW == 4 || VW == 1, "load width: 16 or 4 bytes");
+    // element offsets into K: 32-bit for the 16-byte loads (m h d < 2^31: checked by the launcher), 64-bit for the 4-byte ones (any codebook size)
+    using koff_t = std::conditional_t<VW == 4, uint32_t, uint64_t>;
     constexpr int CS = (M <= 8) ? 8 : 16;
     constexpr int RW = CS / 4;
     const int lane = threadIdx.x & 63;
-    const int half = lane >> 5, lp = lane & 31;
-    const int64_t nwaves = (int64_t)gridDim.x * 4;
-    const int64_t w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    const int qtr = lane >> 4, lp = lane & 15;
     unsigned n_eq = 0, n_lt = 0;
-    // 64 consecutive vectors per wave batch; vectors whose candidate record equals the current one keep their cost (see
-    // cost_kernel) and are skipped; the others are taken two at a time, one per half-wave.
+    // 64 consecutive vectors per wave batch.  Accept mode: a vector whose candidate record equals its current record has, bit for bit, the cost it
+    // already has (same codes, same arithmetic) -- counted as "equal" (encode_icm_cuda.jl:199-204) without touching X or the codebooks (a NaN cost is
+    // never "equal" in the reference's comparison: those are evaluated).  The others are taken four at a time, one per row.
     for (int64_t base = w * 64; base < n; base += nwaves * 64) {
         const int64_t il = base + lane;
         const bool livel = il < n;
         const int64_t ic = livel ? il : n - 1;
         uint32_t rn[RW], cw[RW];
-        bool same = (mode == 1);
+        float pl = 0.0f;
+        unsigned short vc = 0, vn = 0;
+        {   // one group of independent loads (no control flow between them)
+            const uint32_t *rp = reinterpret_cast<const uint32_t *>(rec + ic * CS), *cp = reinterpret_cast<const uint32_t *>(cur + ic * CS);
+#pragma unroll
+            for (int q = 0; q < RW; ++q) rn[q] = rp[q];
+            if (MODE == 1) {
+#pragma unroll
+                for (int q = 0; q < RW; ++q) cw[q] = cp[q];
+                pl = prev[ic];
+            }
+            if (HASV) vc = vcur[ic];
+            if (HASV && MODE == 1) vn = vnew[ic];
+        }
+        bool same = (MODE == 1);
 #pragma unroll
         for (int q = 0; q < RW; ++q) {
-            rn[q] = reinterpret_cast<const uint32_t *>(rec + ic * CS)[q];
-            cw[q] = (mode == 1) ? reinterpret_cast<const uint32_t *>(cur + ic * CS)[q] : rn[q];
+            if (MODE == 0) cw[q] = rn[q];
             same = same && (rn[q] == cw[q]);
         }
-        const float pl = (mode == 1) ? prev[ic] : 0.0f;
         const bool skip = livel && same && (pl == pl);
-        const unsigned nskip = (unsigned)__popcll(__ballot(skip));              // all lanes vote, lane 0 keeps the wave's counters
+        const unsigned nskip = (unsigned)__popcll(__ballot(skip));
         if (lane == 0) n_eq += nskip;
-        unsigned short vfin = (livel && vcur) ? vcur[il] : (unsigned short)0;      // the vector's validity word after this kernel (for the fused perturbation)
-        const unsigned short vn = (livel && vcur && mode == 1) ? vnew[il] : (unsigned short)0;
-        if (same && livel && vcur) { vfin = (unsigned short)(vfin | vn); vcur[il] = vfin; }     // same tuple: what the sweeps learnt about it is kept
+        unsigned short vfin = vc;                                                   // the vector's validity word after this kernel (for the fused perturbation)
+        const bool merge_v = HASV && MODE == 1 && same && livel;                    // same tuple: what the sweeps learnt about it is kept
+        if (merge_v) vfin = (unsigned short)(vfin | vn);
         uint64_t accepted = 0;                                                      // bit l: the candidate of vector base + l replaced the current record
+        float newp = 0.0f;                                                          // the evaluated cost of this lane's vector
         uint64_t todo = __ballot(livel && !skip);
-        while (todo) {
-            const int sa = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const bool haveb = todo != 0;
-            const int sb = haveb ? __builtin_ctzll(todo) : sa;                // odd count: the second half repeats the first, unwritten
-            if (haveb) todo &= todo - 1;
-            const bool live = half ? haveb : true;
-            const int64_t i = base + (half ? sb : sa);
+#ifdef LSQ_TUNING
+        if (pn.abl & 8) todo = 0;
+#endif
+        // Rounds of four vectors.  The x row comes from HBM, the codeword rows from L2: waiting for both in the same round leaves the L1 idle for the
+        // length of an HBM round trip, so the x loads run ONE STEP AHEAD -- those of the next 64 NQ dimensions (or of the next round's vectors) are
+        // issued behind the current step's codeword loads and are still in flight while it is summed.
+        int nsidx[4];
+        bool nhv[4];
+        auto pick = [&]() {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {                                           // fewer than four left: the spare rows repeat the first, unwritten
+                nhv[v] = todo != 0;
+                nsidx[v] = nhv[v] ? __builtin_ctzll(todo) : (v ? nsidx[0] : 0);
+                if (nhv[v]) todo &= todo - 1;
+            }
+        };
+        auto xrow = [&]() -> const float * {
+            const int mys = qtr == 0 ? nsidx[0] : qtr == 1 ? nsidx[1] : qtr == 2 ? nsidx[2] : nsidx[3];
+            return X + (base + mys) * (int64_t)d;                                   // an empty pick points at the batch's first vector: a harmless read
+        };
+        f32x4 xn[NQ];
+        auto xload = [&](const float *x, int c0) {
+#pragma unroll
+            for (int g = 0; g < NQ; ++g) {
+                xn[g] = load4<VW>(x, 0, c0 + 64 * g, lp, d);
+            }
+        };
+        pick();
+        const float *xnext = xrow();
+        if (nhv[0]) xload(xnext, 0);
+        while (nhv[0]) {
+            int sidx[4];
+            bool hv[4];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) { sidx[v] = nsidx[v]; hv[v] = nhv[v]; }
+            const float *x = xnext;
+            pick();                                                                 // the NEXT round's vectors (none: nhv[0] = false)
+            xnext = xrow();
+            const bool live = qtr == 0 ? hv[0] : qtr == 1 ? hv[1] : qtr == 2 ? hv[2] : hv[3];
             uint32_t r[RW];
+            float pc;
+            {
+                uint32_t rv4[4][RW];
+                float pc4[4];
 #pragma unroll
-            for (int q = 0; q < RW; ++q) {
-                const uint32_t ra_ = (uint32_t)__builtin_amdgcn_readlane((int)rn[q], sa), rb_ = (uint32_t)__builtin_amdgcn_readlane((int)rn[q], sb);
-                r[q] = half ? rb_ : ra_;
-            }
-            const float pca = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pl), sa));
-            const float pcb = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pl), sb));
-            const float pc = half ? pcb : pca;
-            const float *x = X + i * (int64_t)d;
-            const float *kb[M];
+                for (int v = 0; v < 4; ++v) {
 #pragma unroll
-            for (int k = 0; k < M; ++k) kb[k] = K + ((int64_t)(k * LSQ_H) + ((r[k >> 2] >> (8 * (k & 3))) & 0xffu)) * d;
-            float p0 = 0.0f, p1 = 0.0f;
-            for (int c0 = 0; c0 < d; c0 += 128) {
-                const int ta = c0 + 2 * lp, tb = ta + 64;
-                const bool va = ta < d, vb = tb < d;
-                const int ua = va ? ta : 0, ub = vb ? tb : 0;
-                const f32x2 xa = *reinterpret_cast<const f32x2 *>(x + ua), xb = *reinterpret_cast<const f32x2 *>(x + ub);
-                f32x2 ka[M], kbv[M];
-#pragma unroll
-                for (int k = 0; k < M; ++k) {
-                    ka[k] = *reinterpret_cast<const f32x2 *>(kb[k] + ua);
-                    kbv[k] = *reinterpret_cast<const f32x2 *>(kb[k] + ub);
+                    for (int q = 0; q < RW; ++q) rv4[v][q] = (uint32_t)__builtin_amdgcn_readlane((int)rn[q], sidx[v]);
+                    pc4[v] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pl), sidx[v]));
                 }
-                f32x2 ca = (f32x2){0.f, 0.f}, cb = (f32x2){0.f, 0.f};
 #pragma unroll
-                for (int k = 0; k < M; ++k) { ca = ca + ka[k]; cb = cb + kbv[k]; }      // k ascending from 0 (utils.jl:238-244)
-                const f32x2 ra = ca - xa, rb = cb - xb;
-                const f32x2 sa2 = ra * ra, sb2 = rb * rb;                               // never fused (-ffp-contract=off)
-                p0 = p0 + (va ? sa2.x : 0.0f);                                          // residue 2l':   t ascending
-                p1 = p1 + (va ? sa2.y : 0.0f);                                          // residue 2l'+1
-                p0 = p0 + (vb ? sb2.x : 0.0f);
-                p1 = p1 + (vb ? sb2.y : 0.0f);
+                for (int q = 0; q < RW; ++q) r[q] = qtr == 0 ? rv4[0][q] : qtr == 1 ? rv4[1][q] : qtr == 2 ? rv4[2][q] : rv4[3][q];
+                pc = qtr == 0 ? pc4[0] : qtr == 1 ? pc4[1] : qtr == 2 ? pc4[2] : pc4[3];
             }
-            float v = p0 + p1;                                                          // tree level 1
-            v = v + dpp_self<DPP_XOR1, 0xf>(v);                                         // levels 2, 4, 8, 16: within the row
-            v = v + dpp_self<DPP_XOR2, 0xf>(v);
-            v = v + dpp_self<DPP_HALF_MIRROR, 0xf>(v);
-            v = v + dpp_self<DPP_MIRROR, 0xf>(v);
-            v = v + dpp_zero<DPP_BCAST15, 0xa>(v);                                      // level 32: rows 1 and 3 add rows 0 and 2
-            const float costA = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 31));
-            const float costB = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-            const float cost = half ? costB : costA;
-            if (mode == 0) {
-                if (live && lp == 0) prev[i] = cost;
-            } else {
-                const bool eq = live && (cost == pc), lt = live && (cost < pc);          // strict improvement only (encode_icm.jl:183-186)
-                const uint64_t bl = __ballot(lt && lp == 0);                              // bit 0: first half's vector (sa), bit 32: second half's (sb)
+            koff_t kb[M];                                                            // one offset per codeword row
+#pragma unroll
+            for (int k = 0; k < M; ++k) kb[k] = ((koff_t)(k * LSQ_H) + (koff_t)((r[k >> 2] >> (8 * (k & 3))) & 0xffu)) * (koff_t)d;
+            f32x4 p = (f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int c0 = 0; c0 < d; c0 += 64 * NQ) {
+                f32x4 xv[NQ], kv[NQ][M];
+                bool ok[NQ][4];
+#pragma unroll
+                for (int g = 0; g < NQ; ++g) {                                       // every codeword load of the NQ steps is issued before the first add
+                    const int c = c0 + 64 * g;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ok[g][e] = load_start<VW>(c, lp, e / VW) < d;     // element e is in iff the load that carries it is
+                    xv[g] = xn[g];
+#pragma unroll
+                    for (int k = 0; k < M; ++k) kv[g][k] = load4<VW>(K, kb[k], c, lp, d);
+                }
+                if (c0 + 64 * NQ < d) xload(x, c0 + 64 * NQ);                        // ... and behind them the x of the next step
+                else xload(xnext, 0);
+#pragma unroll
+                for (int g = 0; g < NQ; ++g) {                                       // step by step: residues 4 l' .. 4 l' + 3 accumulate in ascending t
+                    f32x4 cb = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int k = 0; k < M; ++k) cb = cb + kv[g][k];                  // k ascending from 0 (utils.jl:238-244)
+                    const f32x4 rr = cb - xv[g];
+                    const f32x4 sq = rr * rr;                                        // never fused (-ffp-contract=off)
+                    p.x = p.x + (ok[g][0] ? sq.x : 0.0f);
+                    p.y = p.y + (ok[g][1] ? sq.y : 0.0f);
+                    p.z = p.z + (ok[g][2] ? sq.z : 0.0f);
+                    p.w = p.w + (ok[g][3] ? sq.w : 0.0f);
+                }
+            }
+            float cost;                                                             // every lane of the row holds its vector's cost
+            if constexpr (VW == 4) cost = row_sum16((p.x + p.y) + (p.z + p.w));
+            else cost = (row_sum16(p.x) + row_sum16(p.y)) + (row_sum16(p.z) + row_sum16(p.w));
+            // the four costs go to the lanes that own the vectors: nothing is stored inside the round
+#pragma unroll
+            for (int v2 = 0; v2 < 4; ++v2) {
+                const float cv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cost), 16 * v2));
+                if (hv[v2] && lane == sidx[v2]) newp = cv;
+            }
+            if (MODE == 1) {
+                const bool eq = live && (cost == pc), lt = live && (cost < pc);     // strict improvement only (encode_icm.jl:183-186)
+                const uint64_t bl = __ballot(lt && lp == 0);                        // bits 0, 16, 32, 48: the four rows' vectors
                 const unsigned ne = (unsigned)__popcll(__ballot(eq && lp == 0)), nl = (unsigned)__popcll(bl);
-                accepted |= ((bl & 1ull) ? 1ull << sa : 0ull) | (((bl >> 32) & 1ull) ? 1ull << sb : 0ull);
-                if (lane == 0) { n_eq += ne; n_lt += nl; }
-                if (lt && lp == 0) {
-                    prev[i] = cost;
-                    uint32_t *qd = reinterpret_cast<uint32_t *>(cur + i * CS);
 #pragma unroll
-                    for (int q = 0; q < RW; ++q) qd[q] = r[q];
-                    if (vcur) vcur[i] = vnew[i];
-                }
+                for (int v2 = 0; v2 < 4; ++v2)
+                    if ((bl >> (16 * v2)) & 1ull) accepted |= 1ull << sidx[v2];
+                if (lane == 0) { n_eq += ne; n_lt += nl; }
             }
         }
+        // lane-parallel epilogue of the batch: coalesced stores of what changed
+        const bool acc = (accepted >> lane) & 1ull;
+        if (MODE == 0) {
+            if (livel) prev[il] = newp;
+        } else if (acc) {
+            prev[il] = newp;
+            uint32_t *qd = reinterpret_cast<uint32_t *>(cur + il * CS);
+#pragma unroll
+            for (int q = 0; q < RW; ++q) qd[q] = rn[q];
+        }
+        if (HASV && MODE == 1 && (acc || merge_v)) vcur[il] = acc ? vn : vfin;
         if (pn.on && livel) {
-            const bool acc = (accepted >> lane) & 1ull;
             uint32_t fin[RW];
 #pragma unroll
             for (int q = 0; q < RW; ++q) fin[q] = acc ? rn[q] : cw[q];
             perturb_next_store<CS>(pn, il, fin, acc ? vn : vfin);
         }
     }
-    if (mode == 1 && lane == 0 && (n_eq | n_lt)) {
-        if (n_eq) atomicAdd(&counters[0], (unsigned long long)n_eq);
-        if (n_lt) atomicAdd(&counters[1], (unsigned long long)n_lt);
+    if (MODE == 1) {                                                                 // one pair of device atomics per block
+        __shared__ unsigned cnt_s[2];
+        if (threadIdx.x == 0) { cnt_s[0] = 0u; cnt_s[1] = 0u; }
+        __syncthreads();
+        if (lane == 0 && n_eq) atomicAdd(&cnt_s[0], n_eq);
+        if (lane == 0 && n_lt) atomicAdd(&cnt_s[1], n_lt);
+        __syncthreads();
+        if (threadIdx.x == 0 && cnt_s[0]) atomicAdd(&counters[0], (unsigned long long)cnt_s[0]);
+        if (threadIdx.x == 0 && cnt_s[1]) atomicAdd(&counters[1], (unsigned long long)cnt_s[1]);
     }
 }
 
-// NQ = 1 (d <= 64): the compiler's own register budget; NQ = 2: four waves per SIMD (128 VGPRs) so that the 18 loads of a round really are in flight together
-template <int M, int MODE, int HASV, int NQ>
+// NQ = 1: the compiler's own register budget; NQ = 2 (16-byte loads, d > 64, m <= 8): four waves per SIMD (128 VGPRs) so that the 18 loads of a round
+// really are in flight together
+template <int M, int MODE, int HASV, int NQ, int VW>
 __global__ __launch_bounds__(256) void cost4_kernel(const float *__restrict__ X, const float *__restrict__ K, const uint8_t *rec, uint8_t *cur,
                                                     float *__restrict__ prev, unsigned long long *__restrict__ counters, int64_t n, int d,
                                                     const unsigned short *vnew, unsigned short *vcur, const lsq_perturb_next pn) {
-    cost4_body<M, MODE, HASV, NQ>(X, K, rec, cur, prev, counters, 0, n, __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))),
-                                  (int64_t)gridDim.x * 4, d, vnew, vcur, pn);
+    cost4_body<M, MODE, HASV, NQ, VW>(X, K, rec, cur, prev, counters, n, __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))),
+                                      (int64_t)gridDim.x * 4, d, vnew, vcur, pn);
 }
-template <int M, int MODE, int HASV, int NQ>
+template <int M, int MODE, int HASV, int NQ, int VW>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void cost4w_kernel(const float *__restrict__ X, const float *__restrict__ K,
                                                     const uint8_t *rec, uint8_t *cur, float *__restrict__ prev,
                                                     unsigned long long *__restrict__ counters, int64_t n, int d,
                                                     const unsigned short *vnew, unsigned short *vcur, const lsq_perturb_next pn) {
-    cost4_body<M, MODE, HASV, NQ>(X, K, rec, cur, prev, counters, 0, n, __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))),
-                                  (int64_t)gridDim.x * 4, d, vnew, vcur, pn);
+    cost4_body<M, MODE, HASV, NQ, VW>(X, K, rec, cur, prev, counters, n, __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))),
+                                      (int64_t)gridDim.x * 4, d, vnew, vcur, pn);
 }
 
 __global__ __launch_bounds__(256) void sum_f64_kernel(const float *__restrict__ v, int64_t n, double *__restrict__ sum) {
@@ -773,12 +809,6 @@ __global__ __launch_bounds__(256) void synth_codebooks_kernel(uint64_t seed, int
     K[q] = (float)(w >> 24) / (float)m;
 }
 
-inline unsigned wave_grid(int64_t n) {      // persistent grid: 4 waves per block, <= 8 blocks per CU on 256 CUs
-    int64_t blocks = (n + 3) / 4;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
-}
 inline unsigned thread_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -942,44 +972,49 @@ int lsq_launch_perturb(hipStream_t s, const uint8_t *src, uint8_t *dst, int64_t 
 
 const void *lsq_probe_kernel_icm() { return reinterpret_cast<const void *>(&tables_to_slices_kernel<16>); }
 
+// persistent grid: as many 256-thread blocks as are resident at once (a second, partial generation of blocks would idle the CUs it does not reach)
+template <int M, int NQ, int VW>
+static void launch_cost_t(hipStream_t s, const float *X, const float *K, const uint8_t *rec, uint8_t *cur, float *prev,
+                          unsigned long long *counters, int64_t n, int d, int mode, const unsigned short *vnew, unsigned short *vcur,
+                          const lsq_perturb_next &pn) {
+    static std::atomic<int> per_cu_known[3];      // one per kernel below (lsq_multi_* runs one host thread per device through here)
+    auto launch = [&](auto kern, int which) {
+        int per_cu = per_cu_known[which].load(std::memory_order_relaxed);
+        if (per_cu == 0) {
+            int nb = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, 0) != hipSuccess || nb < 1) nb = 4;
+            per_cu = nb > 8 ? 8 : nb;
+            per_cu_known[which].store(per_cu, std::memory_order_relaxed);
+        }
+        const int64_t want = (n + 255) / 256, cap = 256 * (int64_t)per_cu;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, s, X, K, rec, cur, prev, counters, n, d, vnew, vcur, pn);
+    };
+    if constexpr (NQ == 1) {
+        if (mode == 1) launch(cost4_kernel<M, 1, 1, 1, VW>, 0); else if (vcur) launch(cost4_kernel<M, 0, 1, 1, VW>, 1); else launch(cost4_kernel<M, 0, 0, 1, VW>, 2);
+    } else if constexpr (M <= 8) {                // NQ = 2 is chosen for m <= 8 only
+        if (mode == 1) launch(cost4w_kernel<M, 1, 1, 2, VW>, 0); else if (vcur) launch(cost4w_kernel<M, 0, 1, 2, VW>, 1); else launch(cost4w_kernel<M, 0, 0, 2, VW>, 2);
+    }
+}
+
 int lsq_launch_cost(hipStream_t s, const float *X, const float *K, const uint8_t *rec, uint8_t *cur, float *prev,
                     unsigned long long *counters, int64_t n, int d, int m, int mode, const unsigned short *vnew, unsigned short *vcur,
                     const lsq_perturb_next *next) {
     if (n <= 0) return LSQ_OK;
+    if (mode == 1 && (!vnew || !vcur)) { lsq_set_error("lsq_launch_cost: accept mode needs both validity arrays"); return LSQ_EINVAL; }
     lsq_perturb_next pn = {};
     if (next) pn = *next;
     pn.abl = LSQ_KNOB("LSQ_COST_ABL", 0);
-    const int use_v2 = LSQ_KNOB("LSQ_COST_V2", 1), use_v4 = LSQ_KNOB("LSQ_COST_V4", 1);
-    // a quarter wave per vector with 16-byte loads (any d that is a multiple of 4); else half a wave per vector with 8-byte loads (measured 13 %
-    // faster than the scalar kernel at d = 128, 7 % slower at d = 960); else one wave per vector, 4-byte loads
-    if (use_v4 && d % 4 == 0 && ((uintptr_t)X | (uintptr_t)K) % 16 == 0) {
-        // persistent grid: as many 256-thread blocks as are resident at once (a second, partial generation of blocks would idle the CUs it does not reach)
-        const int64_t want = (n + 255) / 256;
-#define LSQ_COST4(KERN_, MODE_, HASV_, NQ_)                                                                                                        \
-        LSQ_DISPATCH_M(m, {                                                                                                                 \
-            static std::atomic<int> per_cu_known{0};      /* (lsq_multi_* runs one host thread per device through here) */                  \
-            int per_cu = per_cu_known.load(std::memory_order_relaxed);                                                                      \
-            if (per_cu == 0) {                                                                                                              \
-                int nb = 0;                                                                                                                 \
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KERN_<M_, MODE_, HASV_, NQ_>, 256, 0) != hipSuccess || nb < 1) nb = 4;   \
-                per_cu = nb > 8 ? 8 : nb;                                                                                                   \
-                per_cu_known.store(per_cu, std::memory_order_relaxed);                                                                      \
-            }                                                                                                                               \
-            const int64_t cap = 256 * (int64_t)per_cu;                                                                                      \
-            hipLaunchKernelGGL((KERN_<M_, MODE_, HASV_, NQ_>), dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, s, X, K, rec, cur, prev, counters, n, d, vnew, vcur, pn); \
-        })
-        if (mode == 1 && (!vnew || !vcur)) { lsq_set_error("lsq_launch_cost: accept mode needs both validity arrays"); return LSQ_EINVAL; }
+    // 16-byte loads when d is a multiple of 4 and X and K are 16-byte aligned (every torch allocation), else 4-byte loads (measured faster than
+    // 8-byte ones where d is even and X and K 8-byte aligned)
+    if (d % 4 == 0 && ((uintptr_t)X | (uintptr_t)K) % 16 == 0) {
         if ((int64_t)m * LSQ_H * d >= (1ll << 31)) { lsq_set_error("lsq_launch_cost: codebook matrix too large"); return LSQ_EINVAL; }
         if (d > 64 && m <= 8) {             // two 64-float steps of d in flight (18 loads per lane); above m = 8 the codeword rows of ONE step already fill the registers
-            if (mode == 1) { LSQ_COST4(cost4w_kernel, 1, 1, 2); } else if (vcur) { LSQ_COST4(cost4w_kernel, 0, 1, 2); } else { LSQ_COST4(cost4w_kernel, 0, 0, 2); }
+            LSQ_DISPATCH_M(m, (launch_cost_t<M_, 2, 4>(s, X, K, rec, cur, prev, counters, n, d, mode, vnew, vcur, pn)));
         } else {
-            if (mode == 1) { LSQ_COST4(cost4_kernel, 1, 1, 1); } else if (vcur) { LSQ_COST4(cost4_kernel, 0, 1, 1); } else { LSQ_COST4(cost4_kernel, 0, 0, 1); }
+            LSQ_DISPATCH_M(m, (launch_cost_t<M_, 1, 4>(s, X, K, rec, cur, prev, counters, n, d, mode, vnew, vcur, pn)));
         }
-#undef LSQ_COST4
-    } else if (use_v2 && d % 2 == 0 && d <= 256 && ((uintptr_t)X | (uintptr_t)K) % 8 == 0) {
-        LSQ_DISPATCH_M(m, hipLaunchKernelGGL(cost2_kernel<M_>, dim3(wave_grid((n + 1) / 2)), dim3(256), 0, s, X, K, rec, cur, prev, counters, n, d, mode, vnew, vcur, pn));
     } else {
-        LSQ_DISPATCH_M(m, hipLaunchKernelGGL(cost_kernel<M_>, dim3(wave_grid((n + 1) / 2)), dim3(256), 0, s, X, K, rec, cur, prev, counters, n, d, mode, vnew, vcur, pn));
+        LSQ_DISPATCH_M(m, (launch_cost_t<M_, 1, 1>(s, X, K, rec, cur, prev, counters, n, d, mode, vnew, vcur, pn)));
     }
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;

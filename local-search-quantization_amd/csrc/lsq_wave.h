@@ -15,10 +15,6 @@ __device__ inline float dpp_self(float v) {          // disabled lanes keep thei
     const int iv = __float_as_int(v);
     return __int_as_float(__builtin_amdgcn_update_dpp(iv, iv, CTRL, ROW_MASK, 0xf, false));
 }
-template <int CTRL, int ROW_MASK>
-__device__ inline float dpp_zero(float v) {          // disabled lanes receive +0
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
 
 enum { DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HALF_MIRROR = 0x141, DPP_MIRROR = 0x140, DPP_BCAST15 = 0x142, DPP_BCAST31 = 0x143 };
 
@@ -30,19 +26,6 @@ __device__ inline float wave_min(float v) {
     v = fminf(v, dpp_self<DPP_MIRROR, 0xf>(v));
     v = fminf(v, dpp_self<DPP_BCAST15, 0xa>(v));
     v = fminf(v, dpp_self<DPP_BCAST31, 0xc>(v));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
-// sum over the 64 lanes as a balanced pairwise tree, adjacent pairs first -- the exact order
-// of oracle cost_one() ([build-defined 2]); f32 add is commutative so the mirrored DPP sources
-// give the same bits.  Result valid in lane 63, returned wave-uniform.
-__device__ inline float wave_sum_tree(float v) {
-    v = v + dpp_self<DPP_XOR1, 0xf>(v);
-    v = v + dpp_self<DPP_XOR2, 0xf>(v);
-    v = v + dpp_self<DPP_HALF_MIRROR, 0xf>(v);
-    v = v + dpp_self<DPP_MIRROR, 0xf>(v);
-    v = v + dpp_zero<DPP_BCAST15, 0xa>(v);
-    v = v + dpp_zero<DPP_BCAST31, 0xc>(v);
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 

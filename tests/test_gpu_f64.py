@@ -88,18 +88,19 @@ def test_encoder_objective_and_no_vector_gets_worse(lsq, variant, d, n, m):
 @pytest.mark.parametrize("variant", [v for v in ENCODE_VARIANTS if v.id in ("default", "s6_forced")])
 def test_encoder_on_views_with_an_offset(lsq, variant):
     """d = 32: the aligned call takes the 16-byte paths (cost4, the vec4 GEMM, sqnorms' and the 16-bit walk's vector loads), the views offset by
-    one float the 4-byte fallbacks; both must return the same codes and sums"""
+    one float (4-byte aligned) and by two (8-byte aligned) the narrower loads; all must return the same codes and sums"""
     import torch
     d, n, m = 32, 700, 4
     X, K, B0 = make_problem(d, n, m, seed=5)
     B0u = (B0 - 1).astype(np.uint8)
     with open_engine(lsq, variant) as eng:
         a, sa, _ = eng.encode_icm_dev(dev(X), dev(B0u), dev(K), m, [2], 4, 4, True, seed=3)
-        b, sb, _ = eng.encode_icm_dev(dev(X, 1), dev(B0u), dev(K, 1), m, [2], 4, 4, True, seed=3)
-        torch.cuda.synchronize()
-    assert np.array_equal(a.cpu().numpy(), b.cpu().numpy()) and np.array_equal(sa, sb)
-    c64, cb = R.veccost(X, K, b.cpu().numpy()[0].astype(np.int64), m)
-    R.check_values(sb[0] / n, c64.mean(), R.mean_bound(cb, c64), "objective on offset views")
+        for offset in (1, 2):
+            b, sb, _ = eng.encode_icm_dev(dev(X, offset), dev(B0u), dev(K, offset), m, [2], 4, 4, True, seed=3)
+            torch.cuda.synchronize()
+            assert np.array_equal(a.cpu().numpy(), b.cpu().numpy()) and np.array_equal(sa, sb), "offset %d" % offset
+            c64, cb = R.veccost(X, K, b.cpu().numpy()[0].astype(np.int64), m)
+            R.check_values(sb[0] / n, c64.mean(), R.mean_bound(cb, c64), "objective on views offset by %d" % offset)
 
 
 # ---- the LSQ ADC scan ----------------------------------------------------------------------------------------------------------------------

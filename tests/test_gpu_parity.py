@@ -37,7 +37,9 @@ def test_unaries_bit_exact(engine, oracle, d, n, m, kind):
 
 
 @pytest.mark.parametrize("d,n,m,kind", [(16, 64, 4, "gauss"), (128, 1000, 8, "sift"), (960, 33, 8, "gauss"),
-                                        (100, 77, 3, "gauss"), (128, 64, 16, "sift"), (7, 5, 2, "gauss")])
+                                        (100, 77, 3, "gauss"), (128, 64, 16, "sift"), (7, 5, 2, "gauss"),
+                                        (2, 70, 4, "gauss"), (30, 200, 8, "sift"), (130, 300, 8, "gauss"), (258, 40, 16, "gauss"),
+                                        (129, 150, 9, "sift")])
 def test_veccost_bit_exact(engine, oracle, d, n, m, kind):
     X, K, B0 = make_problem(d, n, m, seed=d, kind=kind)
     c = engine.veccost(X, B0, K, m)
@@ -71,6 +73,8 @@ CONFIGS = [
     (24, 90, 1, [2], 2, 1, True, 10, "gauss"),        # one codebook: argmin of the unary
     (32, 150, 8, [2], 9, 3, True, 11, "gauss"),       # 72 node updates per ILS iteration: more than one launch's node list (64)
     (32, 70, 16, [1], 5, 4, True, 12, "gauss"),       # 80 node updates, 16-byte code records
+    (130, 120, 8, [1, 2], 4, 4, True, 13, "gauss"),   # d % 4 == 2: the cost pass's 4-byte loads
+    (33, 90, 5, [2], 3, 2, True, 14, "sift"),         # odd d
 ]
 
 
