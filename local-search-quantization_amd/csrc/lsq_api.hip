@@ -498,10 +498,6 @@ static int check_codes_host(const char *fn, const int16_t *B, int64_t n, int m, 
 }
 
 // ---- device core ----------------------------------------------------------------------------------
-static int u_slice_width(const lsq_ctx *c, int m) {      // layout of the unary planes for the active schedule
-    return lsq_walk_slice_width(m);
-}
-
 static int prepare_tables(lsq_ctx *c, const float *dK, int d, int m) {
     Timer t(c, CAT_TABLES);
     c->tables_changed = 1;
@@ -761,7 +757,7 @@ static int encode_chunk(lsq_ctx *c, const float *dXc, const float *dK, int64_t c
                         bool unaries_ready = false) {
     const int cs = lsq_code_stride(P.m);
     c->call_I = I;
-    if (!unaries_ready) LSQ_TRY(build_unaries(c, dXc, dK, P.d, cn, P.m, u_slice_width(c, P.m), 0, cn));
+    if (!unaries_ready) LSQ_TRY(build_unaries(c, dXc, dK, P.d, cn, P.m, lsq_walk_slice_width(P.m), 0, cn));
     LSQ_TRY(c->recNew.ensure((size_t)cn * cs));
     LSQ_TRY(c->prev.ensure(sizeof(float) * (size_t)cn));
     LSQ_TRY(c->vCur.ensure(sizeof(unsigned short) * (size_t)(cn + 8)));
@@ -1030,7 +1026,7 @@ static int encode_host(lsq_ctx *c, const char *fn, const float *X, const int16_t
         auto snap = [&](int r, const uint8_t *cur) {
             return lsq_launch_codes_to_i16(c->stream, cur, cn, m, c->sOut16.as<int16_t>() + (int64_t)r * cn * m);
         };
-        if (piped) LSQ_TRY(build_unaries_from_host(c, X, dXc, dK, d, cn, m, u_slice_width(c, m)));
+        if (piped) LSQ_TRY(build_unaries_from_host(c, X, dXc, dK, d, cn, m, lsq_walk_slice_width(m)));
         LSQ_TRY(encode_chunk(c, dXc, dK, cn, global_offset + (uint64_t)off, P, I, snap, piped));
         const int64_t noff = off + c->chunk;
         if (noff < n) {      // next chunk's X: its buffer was last read by chunk c-1, which completed at the previous synchronize
@@ -1272,7 +1268,7 @@ extern "C" int lsq_encode_icm_fully(lsq_ctx *c, int16_t *B, const float *X, cons
     LSQ_TRY(prepare_tables(c, c->sK.as<float>(), d, m));
     c->call_I = 0;                                     // the worker has no accept step and no probe memory: always the configured road
     c->walk_counters = nullptr;
-    LSQ_TRY(build_unaries(c, c->sX.as<float>(), c->sK.as<float>(), d, n, m, u_slice_width(c, m), 0, n));
+    LSQ_TRY(build_unaries(c, c->sX.as<float>(), c->sK.as<float>(), d, n, m, lsq_walk_slice_width(m), 0, n));
     LSQ_TRY(c->recNew.ensure((size_t)n * lsq_code_stride(m)));
     int32_t order[LSQ_MAX_M];
     LSQ_TRY(lsq_node_order(seed, it, m, randord, order));

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(NT) void icm_walk_kernel(const float *__restrict__ 
     constexpr int CW = (M - 1 + 3) / 4;
     constexpr int RW = CS / 4;
     constexpr int TAB = (M - 1) * LSQ_H * LPV;          // f32x4 entries of one slice table
-    constexpr int PP = LSQ_WALK_PP(M, SL);               // vectors per pass (LDS budget)
+    constexpr int PP = lsq_walk_pp(M, SL);               // vectors per pass (LDS budget)
     extern __shared__ f32x4 lds_walk[];
     f32x4 *tab = lds_walk;
     // running first-argmin per (compact) vector: one packed 64-bit key = orderable(value) << 32 | candidate index,
@@ -814,19 +814,6 @@ inline unsigned thread_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
 
 
-#define LSQ_DISPATCH_M(m, EXPR)                                                              \
-    switch (m) {                                                                             \
-        case 1: { constexpr int M_ = 1; EXPR; } break;   case 2: { constexpr int M_ = 2; EXPR; } break;   \
-        case 3: { constexpr int M_ = 3; EXPR; } break;   case 4: { constexpr int M_ = 4; EXPR; } break;   \
-        case 5: { constexpr int M_ = 5; EXPR; } break;   case 6: { constexpr int M_ = 6; EXPR; } break;   \
-        case 7: { constexpr int M_ = 7; EXPR; } break;   case 8: { constexpr int M_ = 8; EXPR; } break;   \
-        case 9: { constexpr int M_ = 9; EXPR; } break;   case 10: { constexpr int M_ = 10; EXPR; } break; \
-        case 11: { constexpr int M_ = 11; EXPR; } break; case 12: { constexpr int M_ = 12; EXPR; } break; \
-        case 13: { constexpr int M_ = 13; EXPR; } break; case 14: { constexpr int M_ = 14; EXPR; } break; \
-        case 15: { constexpr int M_ = 15; EXPR; } break; case 16: { constexpr int M_ = 16; EXPR; } break; \
-        default: lsq_set_error("m = %d out of range 1..16", m); return LSQ_EINVAL;          \
-    }
-
 // geometry of a walk launch over n vectors: vectors per pass (<= the LDS budget PP), number of passes (= segments), grid
 void lsq_walk_geometry(int64_t n, int m, int *per_pass, int *npass, int *pp_cap) {
     const int PP = lsq_walk_pp(m, lsq_walk_slice_width(m));
@@ -844,7 +831,7 @@ static int launch_walk_t(hipStream_t s, const float *U, const float *Ts, const f
                          const WalkNodes &nodes, int use_skip, unsigned long long *active_total, int light,
                          const uint8_t *ref_rec, const unsigned short *ref_valid, const int *idle_if_set) {
     constexpr int TAB = (M - 1) * LSQ_H * (SL / 4);
-    constexpr int PP = LSQ_WALK_PP(M, SL);
+    constexpr int PP = lsq_walk_pp(M, SL);
     constexpr int LDS_BYTES = TAB * 16 + PP * 8 + PP * 2;                // slice table + packed running best + active list
     static_assert(LDS_BYTES + 256 <= 160 * 1024, "slice table + running best must fit the 160 KiB LDS");
     int per_pass = 1, npass = 1;
@@ -859,10 +846,6 @@ static int launch_walk_t(hipStream_t s, const float *U, const float *Ts, const f
                        skip, (T && ABL == 0) ? direct_max : 0, active_total, skip ? ref_rec : nullptr, skip ? ref_valid : nullptr, idle_if_set);
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
-}
-
-int lsq_walk_slice_width(int m) {
-    return (m <= 8 && LSQ_KNOB("LSQ_WALK_SL", 16) != 8) ? 16 : 8;
 }
 
 // `order[nnodes]`: the node updates to run back to back inside the launch (1 = one node; icmiter*m = a whole ILS iteration)
@@ -886,29 +869,21 @@ int lsq_launch_icm_walk(hipStream_t s, const float *U, const float *Ts, const fl
 #define LSQ_WALK_ARGS s, U, Ts, T, rec, valid, n, nodes, use_skip, active_total, light, ref_rec, ref_valid, idle_if_set
 #define LSQ_WALK_CASE_MID(MM) case MM: LSQ_TRY((launch_walk_t<MM, 8, 0, 2>(LSQ_WALK_ARGS))); break;
 #define LSQ_WALK_CASE_BIG(MM) case MM: LSQ_TRY((launch_walk_t<MM, 8, 0, 4, 512>(LSQ_WALK_ARGS))); break;
-#define LSQ_WALK_CASE(MM, SLL) case MM: LSQ_TRY((launch_walk_t<MM, SLL, 0, 3>(LSQ_WALK_ARGS))); break;
-#ifdef LSQ_TUNING      // timing-only variants and alternative shapes: profiling library only (results of the ablations are garbage)
+#define LSQ_WALK_CASE(MM) case MM: LSQ_TRY((launch_walk_t<MM, 16, 0, 3>(LSQ_WALK_ARGS))); break;
+#ifdef LSQ_TUNING      // timing-only variants: profiling library only (results of the ablations are garbage)
         bool handled = true;
-        if (m <= 8 && lsq_walk_slice_width(m) == 8) {
-            switch (m) {
-                LSQ_WALK_CASE(1, 8) LSQ_WALK_CASE(2, 8) LSQ_WALK_CASE(3, 8) LSQ_WALK_CASE(4, 8)
-                LSQ_WALK_CASE(5, 8) LSQ_WALK_CASE(6, 8) LSQ_WALK_CASE(7, 8) LSQ_WALK_CASE(8, 8)
-            }
-        } else if (m == 8 && ablation == 1) { LSQ_TRY((launch_walk_t<8, 16, 1>(LSQ_WALK_ARGS)));
+        if (m == 8 && ablation == 1) { LSQ_TRY((launch_walk_t<8, 16, 1>(LSQ_WALK_ARGS)));
         } else if (m == 8 && ablation == 2) { LSQ_TRY((launch_walk_t<8, 16, 2>(LSQ_WALK_ARGS)));
         } else if (m == 8 && ablation == 3) { LSQ_TRY((launch_walk_t<8, 16, 3>(LSQ_WALK_ARGS)));
         } else if (m == 8 && ablation == 4) { LSQ_TRY((launch_walk_t<8, 16, 4>(LSQ_WALK_ARGS)));
-        } else if (m >= 14 && LSQ_KNOB("LSQ_WALK_BIG_NT", 512) == 1024) {
-            switch (m) { case 14: LSQ_TRY((launch_walk_t<14, 8>(LSQ_WALK_ARGS))); break; case 15: LSQ_TRY((launch_walk_t<15, 8>(LSQ_WALK_ARGS))); break;
-                         case 16: LSQ_TRY((launch_walk_t<16, 8>(LSQ_WALK_ARGS))); break; }
         } else handled = false;
         if (handled) continue;
 #else
         (void)ablation;
 #endif
         switch (m) {
-            LSQ_WALK_CASE(1, 16) LSQ_WALK_CASE(2, 16) LSQ_WALK_CASE(3, 16) LSQ_WALK_CASE(4, 16)
-            LSQ_WALK_CASE(5, 16) LSQ_WALK_CASE(6, 16) LSQ_WALK_CASE(7, 16) LSQ_WALK_CASE(8, 16)
+            LSQ_WALK_CASE(1) LSQ_WALK_CASE(2) LSQ_WALK_CASE(3) LSQ_WALK_CASE(4)
+            LSQ_WALK_CASE(5) LSQ_WALK_CASE(6) LSQ_WALK_CASE(7) LSQ_WALK_CASE(8)
             LSQ_WALK_CASE_MID(9) LSQ_WALK_CASE_MID(10) LSQ_WALK_CASE_MID(11) LSQ_WALK_CASE_MID(12)
             LSQ_WALK_CASE_MID(13) LSQ_WALK_CASE_BIG(14) LSQ_WALK_CASE_BIG(15) LSQ_WALK_CASE_BIG(16)
         }

@@ -350,7 +350,7 @@ __global__ __launch_bounds__(256) void tables_to_q16_slices_kernel(const float *
         const float q1 = fminf(fmaxf(rintf(((src[2 * t + 1] - gs[2 * t + 1]) - lo) * inv), 0.0f), 65535.0f);
         w[t] = (uint32_t)q0 | ((uint32_t)q1 << 16);
     }
-    const int64_t dst = (((int64_t)j * NS + slice) * (m - 1) * LSQ_H + q16_row_index<SLQ>(m, kk, b)) * LPV + qq;      // (plain geometry: dst == e)
+    const int64_t dst = (((int64_t)j * NS + slice) * (m - 1) * LSQ_H + q16_row_index<SLQ>(m, kk, b)) * LPV + qq;
     reinterpret_cast<u32x4 *>(Tq)[dst] = (u32x4){w[0], w[1], w[2], w[3]};
 }
 
@@ -363,21 +363,22 @@ __global__ __launch_bounds__(256) void tables_to_q16_slices_kernel(const float *
 //     (lanes 0..7: a1, 8..15: a2; term 0 = unary, 1.. = table entries in ascending k) and summed in canonical order through shuffles;
 //   * survivors other than a1 / a2 (rare) take a second trip: q16_exact_value per survivor.
 // The lexicographic (value, index) minimum over everything evaluated is the argmin.  Kept lean: it shares the slice walk's 128 VGPRs.
-template <int M, int SLQ, int NT>
+template <int M>
 __device__ inline int q16_refine(const float *__restrict__ U, const uint16_t *__restrict__ Uq, const uint16_t *__restrict__ Tq,
                                  const float *__restrict__ T, uint8_t *__restrict__ rec, unsigned short *__restrict__ valid,
                                  const uint8_t *__restrict__ ref_rec, const unsigned short *__restrict__ ref_valid, int64_t n, int j,
-                                 int64_t lo, const unsigned short *list, const uint32_t *arec, int namb, int SLF, int abl, unsigned short *vmir, bool list_hole = false) {      // list_hole: 16 entries in every 128 (WalkqRot::LHOLE)
+                                 int64_t lo, const unsigned short *list, const uint32_t *arec, int namb, int SLF, int abl, unsigned short *vmir) {
+    using RT = WalkqRot<M>;
     constexpr int CS = (M <= 8) ? 8 : 16;
     constexpr int RW = CS / 4;
     constexpr int AREC = 2 + RW;
     if (abl & 4) return 0;
-    constexpr int NS = LSQ_H / SLQ;
-    constexpr int TAB = (M - 1) * LSQ_H * (SLQ / 8);
-    constexpr int NW = NT / 64;
+    constexpr int NS = LSQ_H / RT::SLQ;
+    constexpr int TAB = (M - 1) * LSQ_H * (RT::SLQ / 8);
+    constexpr int NW = RT::NT / 64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane >> 4, t16 = lane & 15;
-    const int sl = (16 * t16) / SLQ, off = (16 * t16) % SLQ;              // slice / offset (in candidates) of this lane's 16 candidates
+    const int sl = (16 * t16) / RT::SLQ, off = (16 * t16) % RT::SLQ;        // slice / offset (in candidates) of this lane's 16 candidates
     const uint16_t *__restrict__ Uqj = Uq + (int64_t)j * n * LSQ_H;
     const uint16_t *__restrict__ Tqj = Tq + ((int64_t)j * NS + sl) * TAB * 8 + off;
     const float *__restrict__ Tj = T + (int64_t)j * M * LSQ_H * LSQ_H;
@@ -392,9 +393,9 @@ __device__ inline int q16_refine(const float *__restrict__ U, const uint16_t *__
 #pragma unroll
         for (int w2 = 0; w2 < RW; ++w2) rw[w2] = ar[2 + w2];
         const int ci = (int)(key & 0xffffu), a1 = (int)((key >> 16) & 0xffu), a2 = (int)(key >> 24);
-        const int64_t i = lo + (list_hole ? list[((ci >> 4) << 7) + (ci & 15)] : list[ci]);
+        const int64_t i = lo + (RT::LHOLE ? list[((ci >> 4) << 7) + (ci & 15)] : list[ci]);      // LHOLE: 16 list entries in every 128
         // ---- the one round trip: unary levels, table levels, bookkeeping (lane 0), speculative exact terms (one per lane)
-        const u32x4 *up = reinterpret_cast<const u32x4 *>(Uqj + ((int64_t)sl * n + ((abl & 2) ? (int64_t)0 : i)) * SLQ + off);
+        const u32x4 *up = reinterpret_cast<const u32x4 *>(Uqj + ((int64_t)sl * n + ((abl & 2) ? (int64_t)0 : i)) * RT::SLQ + off);
         u32x4 s0 = (u32x4){0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, s1 = s0;
         if (!(abl & 8)) { s0 = up[0]; s1 = up[1]; }
         unsigned short vo = 0, rv = 0;
@@ -425,7 +426,7 @@ __device__ inline int q16_refine(const float *__restrict__ U, const uint16_t *__
             if (abl & 8) break;
             const int k = kk + (kk >= j ? 1 : 0);
             const uint32_t bk = (rw[k >> 2] >> (8 * (k & 3))) & 0xffu;
-            const u32x4 *tp = reinterpret_cast<const u32x4 *>(Tqj + (int64_t)q16_row_index<SLQ>(M, kk, (int)bk) * SLQ);
+            const u32x4 *tp = reinterpret_cast<const u32x4 *>(Tqj + (int64_t)q16_row_index<RT::SLQ>(M, kk, (int)bk) * RT::SLQ);
             const u32x4 b0 = tp[0], b1 = tp[1];
             s0.x = pk_add_u16(s0.x, b0.x); s0.y = pk_add_u16(s0.y, b0.y); s0.z = pk_add_u16(s0.z, b0.z); s0.w = pk_add_u16(s0.w, b0.w);
             s1.x = pk_add_u16(s1.x, b1.x); s1.y = pk_add_u16(s1.y, b1.y); s1.z = pk_add_u16(s1.z, b1.z); s1.w = pk_add_u16(s1.w, b1.w);
@@ -487,50 +488,39 @@ __device__ inline int q16_refine(const float *__restrict__ U, const uint16_t *__
     return nexact;
 }
 
-// dynamic LDS of icm_walkq_kernel: the arrays (table, keys, active list, validity mirror), then the block's scalars
-template <int M, int SLQ, int CPL, int NT, int BPC>
-constexpr int walkq_main_bytes() {
-    if (walkq_rot(M, SLQ, CPL, NT, BPC)) return WalkqRot<M>::lds_bytes();
-    const int pp = WalkqTab<SLQ, CPL>::pp(M, BPC);
-    return WalkqTab<SLQ, CPL>::lds_entries(M) * 16 + pp * 8 + pp * 2 + (WalkqTab<SLQ, CPL>::mirror(M, BPC) ? pp * 2 : 0);
-}
+// dynamic LDS of icm_walkq_kernel: the arrays (table, keys, active list, validity mirror: WalkqRot<M>::lds_bytes()), then the block's scalars
 constexpr int WALKQ_MISC_BYTES = (20 + LSQ_WALK_COUNTERS) * 4;
 
 // ---- the filtered walk ----------------------------------------------------------------------------------------------------------
 // Block / pass / node structure, compaction of the active vectors, light blocks and the validity bookkeeping are those of
 // icm_walk_kernel; the slice walk runs on 16-bit levels (slices of SLQ = 32 candidates for m <= 8, 16 above: the same 64 / 32-byte
-// pieces and the same LDS table footprint as the f32 walk, half as many slices).
-template <int M, int SLQ, int CPL, int DEPTH, int NT, int BPC>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BPC / 4, NT / 64 * BPC / 4))) void icm_walkq_kernel(const float *__restrict__ U, const uint16_t *__restrict__ Uq, const uint16_t *__restrict__ Tq,
+// pieces and the same LDS table footprint as the f32 walk, half as many slices).  The geometry is WalkqRot<M>'s (lsq_q16.h).
+template <int M>
+__global__ __launch_bounds__(WalkqRot<M>::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void icm_walkq_kernel(const float *__restrict__ U, const uint16_t *__restrict__ Uq, const uint16_t *__restrict__ Tq,
                                                        const float *__restrict__ T, uint8_t *__restrict__ rec, unsigned short *__restrict__ valid,
                                                        int64_t n, const WalkNodes nodes, int per_pass, int use_skip, int direct_max,
                                                        unsigned long long *__restrict__ active_total,
                                                        const uint8_t *__restrict__ ref_rec, const unsigned short *__restrict__ ref_valid,
                                                        const lsq_q16_params *__restrict__ P, int SLF, const unsigned short *__restrict__ qflag, int abl,
                                                        const unsigned *__restrict__ gate) {
+    using RT = WalkqRot<M>;                              // the rotated-rows placement of the slice table and the kernel's geometry (lsq_q16.h)
     constexpr int CS = (M <= 8) ? 8 : 16;
-    constexpr int NS = LSQ_H / SLQ;
-    using TL = WalkqTab<SLQ, CPL>;
-    constexpr int NR = TL::NR;                           // 16-byte reads per lane and table (8 levels each)
-    constexpr int LPV = TL::LPV;                         // lanes per vector: CPL levels per lane
-    constexpr int EPR = TL::EPR;                         // 16-byte entries per table row (global layout)
+    constexpr int NS = LSQ_H / RT::SLQ;
+    constexpr int LPV = RT::SLQ / 8;                     // lanes per vector: 8 levels (one 16-byte read per table) per lane
     constexpr int VPW = 64 / LPV;
     constexpr int CW = (M - 1 + 3) / 4;
     constexpr int RW = CS / 4;
-    constexpr int TAB = (M - 1) * LSQ_H * EPR;           // 16-byte entries of one slice table (global)
-    constexpr int LTAB = TL::lds_entries(M);             // ... in LDS (planes, skew)
-    using RT = WalkqRot<M>;
-    constexpr bool ROT = walkq_rot(M, SLQ, CPL, NT, BPC);   // rotated-rows placement of the slice table (lsq_q16.h): the default geometry up to m = 8
-    constexpr int PP = ROT ? RT::pp() : TL::pp(M, BPC);  // BPC = 1: the f32 walk's geometry (4096 up to m = 14); BPC = 2: two 512-thread blocks share a CU
+    constexpr int TAB = (M - 1) * LSQ_H * LPV;           // 16-byte entries of one slice table (global)
+    constexpr int PP = RT::pp();
     if (P->ok == 0) return;                              // never launched in that case (the host read the verdict after the GEMM); kept as a guard
     if (gate && *gate != 2u) return;                     // option "async": the chunk's road word (q16_road_kernel) names the f32 walk
-#ifdef LSQ_TUNING
-    unsigned long long *dbgp = nullptr;
     extern __shared__ u32x4 lds_walkq[];
     // No static __shared__ in this kernel: the dynamic segment must start at LDS address 0 -- the rotated placement builds table addresses byte-wise
-    // (v_perm_b32) and has no instruction to spare for a segment base.  The block's few scalars live behind the arrays (walkq_misc_words()).
-    constexpr int MAIN_BYTES = walkq_main_bytes<M, SLQ, CPL, NT, BPC>();
+    // (v_perm_b32) and has no instruction to spare for a segment base.  The block's few scalars live behind the arrays (WALKQ_MISC_BYTES).
+    constexpr int MAIN_BYTES = RT::lds_bytes();
     int *misc = reinterpret_cast<int *>(reinterpret_cast<char *>(lds_walkq) + MAIN_BYTES);
+#ifdef LSQ_TUNING
+    unsigned long long *dbgp = nullptr;
     if (g_walkq_dbg) {
         unsigned &dbg_slot_s = reinterpret_cast<unsigned *>(misc)[19];
         if (threadIdx.x == 0) dbg_slot_s = (blockIdx.x == 0) ? atomicAdd(&g_walkq_dbg_slot, 1u) : 0u;
@@ -542,26 +532,19 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
     if (blockIdx.x == 0 && threadIdx.x == 0) g_walkq_dbg_cur = dbgp;
     if (g_walkq_blk && threadIdx.x == 0) g_walkq_blk[2 * blockIdx.x] = wall_clock64();
 #endif
-#ifndef LSQ_TUNING
-    extern __shared__ u32x4 lds_walkq[];
-    constexpr int MAIN_BYTES = walkq_main_bytes<M, SLQ, CPL, NT, BPC>();
-    int *misc = reinterpret_cast<int *>(reinterpret_cast<char *>(lds_walkq) + MAIN_BYTES);      // (see the note in the tuning branch above: no static __shared__ here)
-#endif
-    if constexpr (walkq_rot(M, SLQ, CPL, NT, BPC)) {
-        if ((uint32_t)(uintptr_t)(lds_char *)lds_walkq != 0u) __builtin_trap();      // the rotated placement addresses LDS by number: the segment must start at 0
-    }
+    if ((uint32_t)(uintptr_t)(lds_char *)lds_walkq != 0u) __builtin_trap();      // the rotated placement addresses LDS by number: the segment must start at 0
     u32x4 *tab = lds_walkq;
-    constexpr bool HOLE = ROT && RT::HOLE;                                                       // bestA in the free slot of the table's second group (m <= 8)
-    constexpr bool LHOLE = ROT && RT::LHOLE;                                                     // the active list in the free slot of the second group (m > 8)
-    constexpr bool ROT8 = ROT && M <= 8, ROT16 = ROT && M > 8;
-    constexpr int TABE = ROT ? RT::TAB_BYTES / 16 : LTAB;
+    constexpr bool HOLE = RT::HOLE;                                                              // bestA in the free slot of the table's second group (m <= 8)
+    constexpr bool LHOLE = RT::LHOLE;                                                            // the active list in the free slot of the second group (m > 8)
+    constexpr bool ROT8 = M <= 8, ROT16 = M > 8;                                                 // four slots per line / eight
+    constexpr int TABE = RT::TAB_BYTES / 16;
     uint32_t *bestA = HOLE ? reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(lds_walkq) + RT::HOLE_BYTE0)
                            : reinterpret_cast<uint32_t *>(lds_walkq + TABE);                     // [PP] smallest key (Q << 16 | candidate); HOLE: 16 words in every 64 (keyA())
     uint32_t *bestB = HOLE ? reinterpret_cast<uint32_t *>(lds_walkq + TABE) : bestA + PP;        // [PP] second smallest key
     unsigned short *list = LHOLE ? reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(lds_walkq) + RT::HOLE_BYTE0)
                                  : reinterpret_cast<unsigned short *>(bestB + PP);             // [PP] active local indices; LHOLE: 16 entries in every 128 (listp())
     auto listp = [&](int i) -> unsigned short * { return LHOLE ? list + ((i >> 4) << 7) + (i & 15) : list + i; };
-    constexpr bool MIRROR = ROT ? RT::mirror() : TL::mirror(M, BPC);
+    constexpr bool MIRROR = RT::mirror();
     auto keyA = [&](int ci) -> uint32_t * { return HOLE ? bestA + ((ci >> 4) << 6) + (ci & 15) : bestA + ci; };
     // the f32-path list (16-bit entries) reuses bestA's storage after the decide phase has read the keys
     auto f32slot = [&](int i) -> unsigned short * { return reinterpret_cast<unsigned short *>(keyA(i >> 1)) + (i & 1); };
@@ -573,17 +556,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
     // statistics are accumulated per block in LDS and flushed ONCE per launch: per-node device atomics from 256 blocks on the same few
     // words sat in front of every node update's first barrier (5-9 us per node, profiles/r02j_walkq_phases.txt "pre")
     unsigned *stat_s = reinterpret_cast<unsigned *>(misc) + 20;      // [LSQ_WALK_COUNTERS]
-    for (int e = threadIdx.x; e < LSQ_WALK_COUNTERS; e += NT) stat_s[e] = 0u;
+    for (int e = threadIdx.x; e < LSQ_WALK_COUNTERS; e += RT::NT) stat_s[e] = 0u;
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int v = lane / LPV, q = lane % LPV;
-    constexpr int NW = NT / 64;
-    constexpr int EPT = 4096 / NT;
+    constexpr int NW = RT::NT / 64;
+    constexpr int EPT = 4096 / RT::NT;
     constexpr int step = NW * VPW;
 
-    struct Item { u32x4 u[NR]; uint32_t r[RW]; };
+    struct Item { u32x4 u; uint32_t r[RW]; };
 
     auto walk_slices = [&](const int j, const int64_t lo, const int nact, const bool dense) {
 #ifndef LSQ_TUNING
@@ -603,7 +586,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
             }
             sel[w] = sv;
         }
-        constexpr int NST = (TAB + NT - 1) / NT;
+        constexpr int NST = (TAB + RT::NT - 1) / RT::NT;
         u32x4 nxt[NST > 0 ? NST : 1];
         // rotated rows (lsq_q16.h, WalkqRot): lane constants of this node.  selC0 / selC1 gather the record's code bytes of the lane's t-th read of group 0 / 1
         // (slot (t + v) mod tables-of-the-group, table kk = 4 group + slot, code k = kk + (kk >= j)); base0 / base1 hold the matching slot | lane_q address bytes
@@ -647,14 +630,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
             }
         }
         const uint32_t v4 = (uint32_t)v * 4u;
-        constexpr uint32_t LIST_BYTE0 = (uint32_t)(ROT && !LHOLE ? RT::TAB_BYTES + PP * RT::KEY_BYTES : 0);      // byte address of list[] under the rotated placement
+        constexpr uint32_t LIST_BYTE0 = (uint32_t)(LHOLE ? 0 : RT::TAB_BYTES + PP * RT::KEY_BYTES);      // byte address of list[] outside the table
         const int limv = q == 0 ? nact - v : -0x7fffffff;      // c0 < limv  <=>  q == 0 and c0 + v < nact: one compare per item
         // staging of a slice: global rows are [group][code][slot] (q16_row_index) -- a straight copy for a group of four tables; a group of nt < 4 tables
         // leaves 4 - nt slots of every 256-byte LDS line free
-        constexpr bool GROT = (SLQ == 32 && M <= 8) || (SLQ == 16 && M > 8);          // the global layout of this geometry
         auto rot_entry = [&](auto R_) -> int {
             constexpr int r = decltype(R_)::value;
-            constexpr int g = r * NT >= RT::G0_ENTRIES ? 1 : 0, nt = g ? RT::NT1 : RT::NT0, e0 = r * NT - g * RT::G0_ENTRIES;      // (group 0 is a whole number of rounds)
+            constexpr int g = r * RT::NT >= RT::G0_ENTRIES ? 1 : 0, nt = g ? RT::NT1 : RT::NT0, e0 = r * RT::NT - g * RT::G0_ENTRIES;      // (group 0 is a whole number of rounds)
             const int eg = e0 + (int)threadIdx.x;             // entry inside the group
             if constexpr (nt == RT::SPL) return g * 4096 + eg;
             else { const int code = eg / (RT::EPS * (nt ? nt : 1)); return g * 4096 + code * 16 + (eg - code * RT::EPS * nt); }
@@ -663,34 +645,31 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
             const u32x4 *src = reinterpret_cast<const u32x4 *>(Tqj) + (int64_t)sl * TAB;
 #pragma unroll
             for (int r = 0; r < NST; ++r) {
-                const int e = (int)threadIdx.x + r * NT;
-                if constexpr (GROT && !ROT)                   // (tuning geometries on slices of 32: plain LDS placement from the rotated global rows)
-                    nxt[r] = (e < TAB) ? src[q16_row_index<SLQ>(M, e / (LSQ_H * EPR), (e / EPR) % LSQ_H) * EPR + e % EPR] : (u32x4){0u, 0u, 0u, 0u};
-                else nxt[r] = (e < TAB) ? src[e] : (u32x4){0u, 0u, 0u, 0u};
+                const int e = (int)threadIdx.x + r * RT::NT;
+                nxt[r] = (e < TAB) ? src[e] : (u32x4){0u, 0u, 0u, 0u};
             }
         };
         prefetch_tab(0);
         const int ipw = (wave * VPW < nact) ? (nact - wave * VPW + step - 1) / step : 0;
         int ls = 0, lit = 0;
         // the slice plane of the level stream the NEXT loaded item belongs to: advanced when the wave's items wrap around (uniform, scalar)
-        const char *ub = reinterpret_cast<const char *>(Uqj + lo * SLQ);
+        const char *ub = reinterpret_cast<const char *>(Uqj + lo * RT::SLQ);
         const char *const rb = reinterpret_cast<const char *>(rec + lo * CS);
-        const int64_t plane_bytes = n * (int64_t)(SLQ * 2);
+        const int64_t plane_bytes = n * (int64_t)(RT::SLQ * 2);
         auto load_next = [&](Item &it) {
             int ci = wave * VPW + lit * step + v;
             ci = ci < nact ? ci : nact - 1;
             uint32_t li = (uint32_t)ci;
             if (!dense) {
-                if constexpr (ROT && !LHOLE) li = *reinterpret_cast<lds_u16 *>(LIST_BYTE0 + 2u * (uint32_t)ci);      // (LDS by number: no segment-base add)
+                if constexpr (!LHOLE) li = *reinterpret_cast<lds_u16 *>(LIST_BYTE0 + 2u * (uint32_t)ci);      // (LDS by number: no segment-base add)
                 else li = *listp(ci);
             }
 #ifdef LSQ_TUNING
-            const uint32_t uo = ((abl & 32) ? (li & 63u) : li) * (uint32_t)(SLQ * 2) + (uint32_t)q * 16u;      // ablation: the level stream from L2 instead of HBM
+            const uint32_t uo = ((abl & 32) ? (li & 63u) : li) * (uint32_t)(RT::SLQ * 2) + (uint32_t)q * 16u;      // ablation: the level stream from L2 instead of HBM
 #else
-            const uint32_t uo = li * (uint32_t)(SLQ * 2) + (uint32_t)q * 16u;
+            const uint32_t uo = li * (uint32_t)(RT::SLQ * 2) + (uint32_t)q * 16u;
 #endif
-#pragma unroll
-            for (int r = 0; r < NR; ++r) it.u[r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ub + uo + r * (LPV * 16)));
+            it.u = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ub + uo));
 #ifdef LSQ_TUNING
             const uint32_t *rp = reinterpret_cast<const uint32_t *>(rb + ((abl & 512) ? (li & 63u) : li) * (uint32_t)CS);      // ablation: records from 64 hot lines
 #else
@@ -704,31 +683,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
             }
         };
         auto compute = [&](const Item &cur, int slice, int c0) {
-            u32x4 s[NR];
-#pragma unroll
-            for (int r = 0; r < NR; ++r) s[r] = cur.u[r];
+            u32x4 s = cur.u;
             // The two 16-bit halves of a word never carry into each other (the sum of the m levels of a candidate stays below 65536: lsq_q16_node::hiq),
             // so plain 32-bit adds are exact on the packed levels -- and v_add3_u32 takes two table rows per instruction where v_pk_add_u16 takes one.
-            uint32_t code[M > 1 ? M - 1 : 1];                // (plain placement only)
-#pragma unroll
-            for (int w = 0; w < (ROT ? 0 : CW); ++w) {
-                const uint32_t hiw = (w + 1 < RW) ? cur.r[w + 1] : 0u;
-                const uint32_t cw = __builtin_amdgcn_perm(hiw, cur.r[w], sel[w]);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int kk = 4 * w + t;
-                    if (kk < M - 1) {
-                        if (t == 0) asm("v_and_b32 %0, 0xff, %1" : "=v"(code[kk]) : "v"(cw));
-                        else code[kk] = (cw >> (8 * t)) & 0xffu;
-                    }
-                }
-            }
-#ifdef LSQ_TUNING
-            if (!ROT && (abl & 1024)) {                      // timing only: rows whose bank position depends on the vector's place in the wave, not on its codes (no conflicts)
-#pragma unroll
-                for (int kk = 0; kk < M - 1; ++kk) code[kk] = (code[kk] & ~(uint32_t)(64 / (LPV * 16) * 4 - 1)) | (uint32_t)((v + kk) & (256 / (LPV * 16) - 1));
-            }
-#endif
             if constexpr (ROT16) {
                 uint32_t dw[4] = {0u, 0u, 0u, 0u};               // the compressed code bytes kk = 0 .. m - 2
 #pragma unroll
@@ -755,16 +712,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
 #pragma unroll
                         for (int t = 0; t < 4; t += 2) {
                             if (t + 1 < cnt) {
-                                s[0].x = s[0].x + rd[t].x + rd[t + 1].x; s[0].y = s[0].y + rd[t].y + rd[t + 1].y;
-                                s[0].z = s[0].z + rd[t].z + rd[t + 1].z; s[0].w = s[0].w + rd[t].w + rd[t + 1].w;
+                                s.x = s.x + rd[t].x + rd[t + 1].x; s.y = s.y + rd[t].y + rd[t + 1].y;
+                                s.z = s.z + rd[t].z + rd[t + 1].z; s.w = s.w + rd[t].w + rd[t + 1].w;
                             } else if (t < cnt) {
-                                s[0].x += rd[t].x; s[0].y += rd[t].y; s[0].z += rd[t].z; s[0].w += rd[t].w;
+                                s.x += rd[t].x; s.y += rd[t].y; s.z += rd[t].z; s.w += rd[t].w;
                             }
                         }
                     }
-                    if (g4 < 3) asm volatile("" : "+v"(s[0].x), "+v"(s[0].y), "+v"(s[0].z), "+v"(s[0].w) : : "memory");
+                    if (g4 < 3) asm volatile("" : "+v"(s.x), "+v"(s.y), "+v"(s.z), "+v"(s.w) : : "memory");
                 }
-            } else if constexpr (ROT8) {
+            } else {
                 u32x4 rd[M > 1 ? M - 1 : 1];
                 const uint32_t c0r = __builtin_amdgcn_perm(cur.r[1], cur.r[0], selC0);
                 // LDS addresses as plain numbers (the segment starts at 0, checked at kernel entry): through the segment's symbol every read pays an add of its base
@@ -778,10 +735,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
 #pragma unroll
                     for (int kk = k0; kk < k1; kk += 2) {
                         if (kk + 1 < k1) {
-                            s[0].x = s[0].x + rd[kk].x + rd[kk + 1 < M - 1 ? kk + 1 : kk].x; s[0].y = s[0].y + rd[kk].y + rd[kk + 1 < M - 1 ? kk + 1 : kk].y;
-                            s[0].z = s[0].z + rd[kk].z + rd[kk + 1 < M - 1 ? kk + 1 : kk].z; s[0].w = s[0].w + rd[kk].w + rd[kk + 1 < M - 1 ? kk + 1 : kk].w;
+                            s.x = s.x + rd[kk].x + rd[kk + 1 < M - 1 ? kk + 1 : kk].x; s.y = s.y + rd[kk].y + rd[kk + 1 < M - 1 ? kk + 1 : kk].y;
+                            s.z = s.z + rd[kk].z + rd[kk + 1 < M - 1 ? kk + 1 : kk].z; s.w = s.w + rd[kk].w + rd[kk + 1 < M - 1 ? kk + 1 : kk].w;
                         } else {
-                            s[0].x += rd[kk].x; s[0].y += rd[kk].y; s[0].z += rd[kk].z; s[0].w += rd[kk].w;
+                            s.x += rd[kk].x; s.y += rd[kk].y; s.z += rd[kk].z; s.w += rd[kk].w;
                         }
                     }
                 };
@@ -790,56 +747,32 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
                     // loop cannot keep is spilled AROUND it -- the compaction and the decide phase then wait for scratch (measured: +20 us per node update)
                     const uint32_t c1r = __builtin_amdgcn_perm(cur.r[1], cur.r[0], selC1);
                     add_rows(0, RT::NT0);
-                    asm volatile("" : "+v"(s[0].x), "+v"(s[0].y), "+v"(s[0].z), "+v"(s[0].w) : : "memory");
+                    asm volatile("" : "+v"(s.x), "+v"(s.y), "+v"(s.z), "+v"(s.w) : : "memory");
 #pragma unroll
                     for (int t = 0; t < RT::NT1; ++t)        // ... [1] [0]: the second group
                         rd[RT::NT0 + t] = *reinterpret_cast<lds_cu32x4 *>(__builtin_amdgcn_perm(c1r, base1, 0x0c030400u + 0x0101u * (uint32_t)t));
                     add_rows(RT::NT0, M - 1);
                 } else add_rows(0, M - 1);
-            } else {
-#ifdef LSQ_TUNING
-            if (!(abl & 64))                                 // ablation: no table rows
-#endif
-#pragma unroll
-            for (int kk = 0; kk < M - 1; kk += 2) {
-#pragma unroll
-                for (int r = 0; r < NR; ++r) {
-                    const u32x4 ra = tab[kk * TL::TS_E + r * TL::PLANE_E + (int)code[kk] * LPV + q];
-                    if (kk + 1 < M - 1) {
-                        const u32x4 rb2 = tab[(kk + 1) * TL::TS_E + r * TL::PLANE_E + (int)code[kk + 1 < M - 1 ? kk + 1 : kk] * LPV + q];
-                        s[r].x = s[r].x + ra.x + rb2.x; s[r].y = s[r].y + ra.y + rb2.y;
-                        s[r].z = s[r].z + ra.z + rb2.z; s[r].w = s[r].w + ra.w + rb2.w;
-                    } else {
-                        s[r].x += ra.x; s[r].y += ra.y; s[r].z += ra.z; s[r].w += ra.w;
-                    }
-                }
-            }
             }
 #ifdef LSQ_TUNING
             if (abl & 128) {                                 // ablation: no keys / top-2 / LDS atomics
-                if ((q == 0) & (c0 + v < nact) & (s[0].x == 0x12345678u)) *keyA(c0 + v) = s[0].y ^ s[NR - 1].z;
+                if ((q == 0) & (c0 + v < nact) & (s.x == 0x12345678u)) *keyA(c0 + v) = s.y ^ s.z;
                 return;
             }
 #endif
-            // keys (Q << 16 | candidate): the two smallest of the lane's CPL, then of the vector's LPV lanes.  Inside the lane the keys carry the
-            // candidate's offset from the lane's first one (inline constants: chunk r starts LPV * 8 r further); the base is added to the two survivors
-            uint32_t l0 = 0, h0 = 0;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                constexpr uint32_t HI = 0xffff0000u;
-                const uint32_t o = (uint32_t)(r * LPV * 8);
-                const uint32_t k0 = (s[r].x << 16) | o, k1 = (s[r].x & HI) | (o + 1u);
-                const uint32_t k2 = (s[r].y << 16) | (o + 2u), k3 = (s[r].y & HI) | (o + 3u);
-                const uint32_t k4 = (s[r].z << 16) | (o + 4u), k5 = (s[r].z & HI) | (o + 5u);
-                const uint32_t k6 = (s[r].w << 16) | (o + 6u), k7 = (s[r].w & HI) | (o + 7u);
-                uint32_t la = umin3(k0, k1, k2), ha = umed3(k0, k1, k2);      // two triples + a pair: 6 + 2 x 3 instructions instead of 8 + 3 x 3
-                const uint32_t lb = umin3(k3, k4, k5), hb = umed3(k3, k4, k5);
-                const uint32_t lc = umin(k6, k7), hc = umax(k6, k7);
-                top2_merge(la, ha, lb, hb);
-                top2_merge(la, ha, lc, hc);
-                if (r == 0) { l0 = la; h0 = ha; } else top2_merge(l0, h0, la, ha);
-            }
-            const uint32_t base = (uint32_t)(SLQ * slice) + 8u * (uint32_t)q;
+            // keys (Q << 16 | candidate): the two smallest of the lane's 8, then of the vector's LPV lanes.  Inside the lane the keys carry the
+            // candidate's offset from the lane's first one (inline constants); the base is added to the two survivors
+            constexpr uint32_t HI = 0xffff0000u;
+            const uint32_t k0 = s.x << 16, k1 = (s.x & HI) | 1u;
+            const uint32_t k2 = (s.y << 16) | 2u, k3 = (s.y & HI) | 3u;
+            const uint32_t k4 = (s.z << 16) | 4u, k5 = (s.z & HI) | 5u;
+            const uint32_t k6 = (s.w << 16) | 6u, k7 = (s.w & HI) | 7u;
+            const uint32_t lc = umin(k6, k7), hc = umax(k6, k7);      // a pair + two triples: 2 x 3 + 6 instructions instead of 3 x 3 + 8
+            uint32_t l0 = umin3(k0, k1, k2), h0 = umed3(k0, k1, k2);
+            const uint32_t lb = umin3(k3, k4, k5), hb = umed3(k3, k4, k5);
+            top2_merge(l0, h0, lb, hb);
+            top2_merge(l0, h0, lc, hc);
+            const uint32_t base = (uint32_t)(RT::SLQ * slice) + 8u * (uint32_t)q;
             l0 += base; h0 += base;                                          // candidate < 256: never carries into the level
             if (LPV >= 2) top2_merge(l0, h0, dpp_u32<DPP_XOR1>(l0), dpp_u32<DPP_XOR1>(h0));
             if (LPV >= 4) top2_merge(l0, h0, dpp_u32<DPP_XOR2>(l0), dpp_u32<DPP_XOR2>(h0));
@@ -855,27 +788,19 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
                 }
             }
         };
-        Item buf[DEPTH];
+        Item buf[RT::DEPTH];
 #pragma unroll
-        for (int e = 0; e < DEPTH; ++e) load_next(buf[e]);
+        for (int e = 0; e < RT::DEPTH; ++e) load_next(buf[e]);
         int phase = 0;
         for (int slice = 0; slice < NS; ++slice) {
             __syncthreads();
 #ifdef LSQ_TUNING
             if (slice < 8) DBG_STAMP(3 + slice);
 #endif
-            if constexpr (ROT) {
-                static_for<NST>([&](auto R_) {
-                    constexpr int r = decltype(R_)::value;
-                    if ((r + 1) * NT <= TAB || r * NT + (int)threadIdx.x < TAB) tab[rot_entry(R_)] = nxt[r];      // (only the last round can be short)
-                });
-            } else {
-#pragma unroll
-                for (int r = 0; r < NST; ++r) {
-                    const int e = (int)threadIdx.x + r * NT;
-                    if (e < TAB) tab[TL::entry(e / (LSQ_H * EPR), (e / EPR) % LSQ_H, e % EPR)] = nxt[r];      // NT = 1024, EPR = 4: table r, the thread's fixed (code, chunk)
-                }
-            }
+            static_for<NST>([&](auto R_) {
+                constexpr int r = decltype(R_)::value;
+                if ((r + 1) * RT::NT <= TAB || r * RT::NT + (int)threadIdx.x < TAB) tab[rot_entry(R_)] = nxt[r];      // (only the last round can be short)
+            });
             __syncthreads();
 #ifdef LSQ_TUNING
             if (slice == 4) DBG_STAMP(20);
@@ -887,22 +812,22 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
             int c0 = wave * VPW, t = 0;
             auto run = [&](auto P_) {
                 constexpr int PH = decltype(P_)::value;
-                for (; t + DEPTH <= ipw; t += DEPTH) {
+                for (; t + RT::DEPTH <= ipw; t += RT::DEPTH) {
 #pragma unroll
-                    for (int e = 0; e < DEPTH; ++e) {
-                        compute(buf[(PH + e) % DEPTH], slice, c0); load_next(buf[(PH + e) % DEPTH]); c0 += step;
+                    for (int e = 0; e < RT::DEPTH; ++e) {
+                        compute(buf[(PH + e) % RT::DEPTH], slice, c0); load_next(buf[(PH + e) % RT::DEPTH]); c0 += step;
                     }
                 }
 #pragma unroll
-                for (int e = 0; e < DEPTH - 1; ++e)
+                for (int e = 0; e < RT::DEPTH - 1; ++e)
                     if (t < ipw) {
-                        compute(buf[(PH + e) % DEPTH], slice, c0); load_next(buf[(PH + e) % DEPTH]); c0 += step;
-                        ++t; phase = (PH + e + 1) % DEPTH;
+                        compute(buf[(PH + e) % RT::DEPTH], slice, c0); load_next(buf[(PH + e) % RT::DEPTH]); c0 += step;
+                        ++t; phase = (PH + e + 1) % RT::DEPTH;
                     }
             };
             bool ran = false;
             auto try_phase = [&](auto P_) {
-                if constexpr (decltype(P_)::value < DEPTH) {
+                if constexpr (decltype(P_)::value < RT::DEPTH) {
                     if (!ran && phase == decltype(P_)::value) { run(P_); ran = true; }
                 }
             };
@@ -943,7 +868,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
         lo_cur = lo;
         if (vmir) {
             __syncthreads();                                   // (a previous pass' readers are done)
-            for (int idx = (int)threadIdx.x; idx < cnt; idx += NT) vmir[idx] = valid[lo + idx];
+            for (int idx = (int)threadIdx.x; idx < cnt; idx += RT::NT) vmir[idx] = valid[lo + idx];
             __syncthreads();
         }
         for (int nu = 0; nu < nodes.count; ++nu) {
@@ -981,7 +906,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
 #pragma unroll
                 for (int e = 0; e < EPT; ++e)
                     if (f[e]) *listp(pos++) = (unsigned short)(base + e);
-                if (threadIdx.x == NT - 1) { nact_s = wbase + inc; redo_s = 0; f32_s = 0; }
+                if (threadIdx.x == RT::NT - 1) { nact_s = wbase + inc; redo_s = 0; f32_s = 0; }
                 DBG_STAMP(18);
                 __syncthreads();
             }
@@ -1001,7 +926,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
                 __syncthreads();
                 continue;
             }
-            for (int ci = tix; ci < nact; ci += NT) { *keyA(ci) = 0xffffffffu; bestB[ci] = 0xffffffffu; }
+            for (int ci = tix; ci < nact; ci += RT::NT) { *keyA(ci) = 0xffffffffu; bestB[ci] = 0xffffffffu; }
             DBG_STAMP(2);
             walk_slices(j, lo, nact, nact == cnt);
             DBG_STAMP(11);
@@ -1010,7 +935,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
             // argmin and all its exact ties) is evaluated exactly below.
             const lsq_q16_node &nd = P->node[j];
             const int window = nd.window;
-            constexpr int EPD = (PP + NT - 1) / NT;                // vectors per thread
+            constexpr int EPD = (PP + RT::NT - 1) / RT::NT;                // vectors per thread
             constexpr int AREC = 2 + RW;                           // words of an ambiguous-vector record: {ci | a1 << 16 | a2 << 24, limit, record words}
             constexpr int ACAP = (PP * 4) / (AREC * 4);            // records that fit bestB's storage
             {
@@ -1027,7 +952,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
                 const bool have_ref = ref_rec && ref_valid;
 #pragma unroll
                 for (int e = 0; e < EPD; ++e) {
-                    const int ci = tix + e * NT;
+                    const int ci = tix + e * RT::NT;
                     vi[e] = lo; kA[e] = 0; kB[e] = 0; vo[e] = 0; rv[e] = 0; fl[e] = 0;
 #pragma unroll
                     for (int w2 = 0; w2 < RW; ++w2) { rw[e][w2] = 0; rr[e][w2] = 0; }
@@ -1049,7 +974,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
                 }
 #pragma unroll
                 for (int e = 0; e < EPD; ++e) {
-                    const int ci = tix + e * NT;
+                    const int ci = tix + e * RT::NT;
                     von[e] = false; vamb[e] = false; vf32[e] = false; vcode[e] = 0; vkey[e] = 0; vlim[e] = 0;
                     if (ci < nact) {
                         vcode[e] = kA[e] & 0xffffu;
@@ -1115,7 +1040,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
             DBG_STAMP(12);
             // ---- exact refinement of the ambiguous vectors
             const int namb = redo_s < ACAP ? redo_s : ACAP;
-            int nexact = q16_refine<M, SLQ, NT>(U, Uq, Tq, T, rec, valid, ref_rec, ref_valid, n, j, lo, list, bestB, namb, SLF, abl, vmir, LHOLE);
+            int nexact = q16_refine<M>(U, Uq, Tq, T, rec, valid, ref_rec, ref_valid, n, j, lo, list, bestB, namb, SLF, abl, vmir);
             {   // vectors outside the sampled level range: one wave each, in full f32
                 const int nf32 = f32_s;
                 light_list(j, nf32, [&](int r) { return *listp(*f32slot(r)); });
@@ -1140,7 +1065,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 64 * BP
     if (g_walkq_blk && threadIdx.x == 0) g_walkq_blk[2 * blockIdx.x + 1] = wall_clock64();
 #endif
     if (active_total)
-        for (int e = threadIdx.x; e < LSQ_WALK_COUNTERS; e += NT)
+        for (int e = threadIdx.x; e < LSQ_WALK_COUNTERS; e += RT::NT)
             if (stat_s[e]) atomicAdd(active_total + e, (unsigned long long)stat_s[e]);
 }
 
@@ -1192,13 +1117,6 @@ int lsq_launch_q16_probe(hipStream_t s, const unsigned long long *probe, unsigne
 }
 
 const void *lsq_probe_kernel_icmq() { return reinterpret_cast<const void *>(&q16_range_init_kernel); }
-
-int lsq_q16_slice_width(int m) {
-#ifdef LSQ_TUNING
-    if (m <= 8 && LSQ_KNOB("LSQ_WALKQ_BPC", 1) == 2) return 16;
-#endif
-    return 2 * lsq_walk_slice_width(m);
-}      // candidates per 16-bit slice: the same bytes per piece as the f32 walk
 
 int lsq_launch_unary_shift_panel(hipStream_t s, const float *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
                                  unsigned short *qflag, int64_t row0, lsq_q16_params *P) {
@@ -1265,15 +1183,15 @@ int lsq_launch_q16_prepare(hipStream_t s, const float *X, int64_t n, int d, cons
     return LSQ_OK;
 }
 
-template <int M, int SLQ, int CPL, int DEPTH, int NT, int BPC>
+template <int M>
 static int launch_walkq_t(hipStream_t s, const float *U, const uint16_t *Uq, const uint16_t *Tq, const float *T, uint8_t *rec, unsigned short *valid,
                           int64_t n, const WalkNodes &nodes, int use_skip, unsigned long long *active_total, int light,
                           const uint8_t *ref_rec, const unsigned short *ref_valid, const lsq_q16_params *P, const unsigned short *qflag, const unsigned *gate) {
-    constexpr bool ROT = walkq_rot(M, SLQ, CPL, NT, BPC);
-    constexpr int PP = ROT ? WalkqRot<M>::pp() : WalkqTab<SLQ, CPL>::pp(M, BPC);
-    constexpr int LDS_BYTES = walkq_main_bytes<M, SLQ, CPL, NT, BPC>() + WALKQ_MISC_BYTES;      // slice table + two smallest keys + active list (+ validity mirror) + the block's scalars
-    static_assert(LDS_BYTES * BPC <= 160 * 1024 && WALKQ_MISC_BYTES <= 768, "slice table + keys must fit the block's share of the 160 KiB LDS");
-    constexpr int NBLK = 256 * BPC;
+    using RT = WalkqRot<M>;
+    constexpr int PP = RT::pp();
+    constexpr int LDS_BYTES = RT::lds_bytes() + WALKQ_MISC_BYTES;      // slice table + two smallest keys + active list (+ validity mirror) + the block's scalars
+    static_assert(LDS_BYTES <= 160 * 1024 && WALKQ_MISC_BYTES <= 768, "slice table + keys must fit the 160 KiB LDS");
+    constexpr int NBLK = 256;
     const int64_t rounds = (n + NBLK * (int64_t)PP - 1) / (NBLK * (int64_t)PP);      // passes per block
     int64_t per = rounds > 0 ? (n + NBLK * rounds - 1) / (NBLK * rounds) : 1;
     per = per > PP ? PP : (per < 1 ? 1 : per);
@@ -1281,20 +1199,19 @@ static int launch_walkq_t(hipStream_t s, const float *U, const uint16_t *Uq, con
     const int direct_max = light >= 0 ? light : LSQ_KNOB("LSQ_WALK_DIRECT", 160);
     const int skip = (use_skip && valid) ? 1 : 0;
     static LdsOptIn optin;
-    LSQ_TRY(optin_lds(optin, &icm_walkq_kernel<M, SLQ, CPL, DEPTH, NT, BPC>, LDS_BYTES));
-    if (ROT) {      // the rotated placement addresses LDS by number: the kernel must have been compiled without static LDS (it also traps at entry otherwise)
-        static std::atomic<int> static_lds_known{-1};      // (lsq_multi_* runs one host thread per device through here)
-        int static_lds = static_lds_known.load(std::memory_order_relaxed);
-        if (static_lds < 0) {
-            hipFuncAttributes fa;
-            LSQ_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&icm_walkq_kernel<M, SLQ, CPL, DEPTH, NT, BPC>)));
-            static_lds = (int)fa.sharedSizeBytes;
-            static_lds_known.store(static_lds, std::memory_order_relaxed);
-        }
-        if (static_lds != 0) { lsq_set_error("icm_walkq_kernel<%d>: %d bytes of static LDS in a kernel that addresses LDS from 0", M, static_lds); return LSQ_EHIP; }
+    LSQ_TRY(optin_lds(optin, &icm_walkq_kernel<M>, LDS_BYTES));
+    // the rotated placement addresses LDS by number: the kernel must have been compiled without static LDS (it also traps at entry otherwise)
+    static std::atomic<int> static_lds_known{-1};      // (lsq_multi_* runs one host thread per device through here)
+    int static_lds = static_lds_known.load(std::memory_order_relaxed);
+    if (static_lds < 0) {
+        hipFuncAttributes fa;
+        LSQ_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&icm_walkq_kernel<M>)));
+        static_lds = (int)fa.sharedSizeBytes;
+        static_lds_known.store(static_lds, std::memory_order_relaxed);
     }
+    if (static_lds != 0) { lsq_set_error("icm_walkq_kernel<%d>: %d bytes of static LDS in a kernel that addresses LDS from 0", M, static_lds); return LSQ_EHIP; }
     const unsigned grid = (unsigned)(npass < NBLK ? npass : NBLK);
-    hipLaunchKernelGGL((icm_walkq_kernel<M, SLQ, CPL, DEPTH, NT, BPC>), dim3(grid), dim3(NT), LDS_BYTES, s, U, Uq, Tq, T, rec, valid, n, nodes, per_pass, skip,
+    hipLaunchKernelGGL((icm_walkq_kernel<M>), dim3(grid), dim3(RT::NT), LDS_BYTES, s, U, Uq, Tq, T, rec, valid, n, nodes, per_pass, skip,
                        direct_max, active_total, skip ? ref_rec : nullptr, skip ? ref_valid : nullptr, P, lsq_walk_slice_width(M), qflag, LSQ_KNOB("LSQ_Q16_ABL", 0), gate);
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
@@ -1315,37 +1232,7 @@ int lsq_launch_icm_walkq(hipStream_t s, const float *U, const uint16_t *Uq, cons
             if (j < 0 || j >= m) { lsq_set_error("node %d out of range 0..%d", j, m - 1); return LSQ_EINVAL; }
             nodes.j[t] = (uint8_t)j;
         }
-#define LSQ_WQ_ARGS s, U, Uq, Tq, T, rec, valid, n, nodes, use_skip, active_total, light, ref_rec, ref_valid, P, qflag, gate
-#define LSQ_WQ_CASE(MM, SLL, CPLL, DD, NTT) case MM: LSQ_TRY((launch_walkq_t<MM, SLL, CPLL, DD, NTT, 1>(LSQ_WQ_ARGS))); break;
-#define LSQ_WQ_CASE2(MM, SLL, CPLL, DD, NTT) case MM: LSQ_TRY((launch_walkq_t<MM, SLL, CPLL, DD, NTT, 2>(LSQ_WQ_ARGS))); break;
-        // m <= 8: slices of 32 candidates, four lanes per vector (8 candidates per lane); above: slices of 16, two lanes of 8
-#ifdef LSQ_TUNING
-        if (m <= 8 && LSQ_KNOB("LSQ_WALKQ_CPL", 8) == 16) {      // two lanes per vector, 16 candidates per lane: 22 % fewer instructions per candidate, dense
-            switch (m) {                                          // node updates 7 % faster, sparse ones up to 30 % slower (coarser items): DESIGN.md 4.2
-                LSQ_WQ_CASE(1, 32, 16, 3, 1024) LSQ_WQ_CASE(2, 32, 16, 3, 1024) LSQ_WQ_CASE(3, 32, 16, 3, 1024) LSQ_WQ_CASE(4, 32, 16, 3, 1024)
-                LSQ_WQ_CASE(5, 32, 16, 3, 1024) LSQ_WQ_CASE(6, 32, 16, 3, 1024) LSQ_WQ_CASE(7, 32, 16, 3, 1024) LSQ_WQ_CASE(8, 32, 16, 3, 1024)
-            }
-            continue;
-        }
-#endif
-#ifdef LSQ_TUNING
-        if (m <= 8 && LSQ_KNOB("LSQ_WALKQ_BPC", 1) == 2) {       // two 512-thread blocks per CU, slices of 16 candidates
-            switch (m) {
-                LSQ_WQ_CASE2(1, 16, 8, 3, 512) LSQ_WQ_CASE2(2, 16, 8, 3, 512) LSQ_WQ_CASE2(3, 16, 8, 3, 512) LSQ_WQ_CASE2(4, 16, 8, 3, 512)
-                LSQ_WQ_CASE2(5, 16, 8, 3, 512) LSQ_WQ_CASE2(6, 16, 8, 3, 512) LSQ_WQ_CASE2(7, 16, 8, 3, 512) LSQ_WQ_CASE2(8, 16, 8, 3, 512)
-            }
-            continue;
-        }
-#endif
-        switch (m) {
-            LSQ_WQ_CASE(1, 32, 8, 3, 1024) LSQ_WQ_CASE(2, 32, 8, 3, 1024) LSQ_WQ_CASE(3, 32, 8, 3, 1024) LSQ_WQ_CASE(4, 32, 8, 3, 1024)
-            LSQ_WQ_CASE(5, 32, 8, 3, 1024) LSQ_WQ_CASE(6, 32, 8, 3, 1024) LSQ_WQ_CASE(7, 32, 8, 3, 1024) LSQ_WQ_CASE(8, 32, 8, 3, 1024)
-            LSQ_WQ_CASE(9, 16, 8, 2, 1024) LSQ_WQ_CASE(10, 16, 8, 2, 1024) LSQ_WQ_CASE(11, 16, 8, 2, 1024) LSQ_WQ_CASE(12, 16, 8, 2, 1024)
-            LSQ_WQ_CASE(13, 16, 8, 2, 1024) LSQ_WQ_CASE(14, 16, 8, 2, 1024) LSQ_WQ_CASE(15, 16, 8, 2, 1024) LSQ_WQ_CASE(16, 16, 8, 2, 1024)
-        }
-#undef LSQ_WQ_CASE
-#undef LSQ_WQ_CASE2
-#undef LSQ_WQ_ARGS
+        LSQ_DISPATCH_M(m, LSQ_TRY((launch_walkq_t<M_>(s, U, Uq, Tq, T, rec, valid, n, nodes, use_skip, active_total, light, ref_rec, ref_valid, P, qflag, gate))));
     }
     return LSQ_OK;
 }

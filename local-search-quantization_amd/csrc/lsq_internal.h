@@ -155,7 +155,8 @@ int lsq_launch_codes_to_i16(hipStream_t s, const uint8_t *rec, int64_t n, int m,
 int lsq_launch_perturb(hipStream_t s, const uint8_t *src, uint8_t *dst, int64_t n, int m, int npert,
                        uint64_t seed, uint32_t it, uint64_t global_offset, const unsigned short *vsrc, unsigned short *vdst);
 // LDS-walk schedule: one block walks all slices of its vector range; Ts = slice-major pair tables
-int lsq_walk_slice_width(int m);      // 16 for m <= 8 (8 if LSQ_WALK_SL=8 is set: tuning knob), 8 above
+constexpr int lsq_walk_slice_width(int m) { return m <= 8 ? 16 : 8; }      // f32 candidates per slice
+constexpr int lsq_q16_slice_width(int m) { return 2 * lsq_walk_slice_width(m); }      // candidates per 16-bit slice: the same bytes per piece as the f32 walk
 int lsq_launch_tables_to_slices(hipStream_t s, const float *T, float *Ts, int m, int sl);
 // valid (optional): validity masks, maintained by the kernel; use_skip: skip vectors whose bit j is set (exact);
 // active_total (optional): += number of vectors actually recomputed; ablation != 0: timing-only variants (m = 8), garbage results.
@@ -173,7 +174,6 @@ int lsq_launch_icm_walk(hipStream_t s, const float *U, const float *Ts, const fl
 // parameters P and the 16-bit slice tables Tq [m][256/SLQ][m-1][256][SLQ]; tables_changed = 1 on the first chunk of a call.
 // bad (1 int), trange (3 m m floats), qrange (2 * 16 + 2 u32): scratch.  lsq_launch_icm_walkq: same contract as lsq_launch_icm_walk plus
 // Uq (the GEMM's u16 planes), Tq and P; the caller launches it only after reading the chunk's verdict (P->ok, P->nflag) on the host.
-int lsq_q16_slice_width(int m);
 int lsq_launch_q16_prepare(hipStream_t s, const float *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, uint16_t *Tq,
                            int *bad, float *trange, unsigned *qrange, unsigned short *qflag, lsq_q16_params *P, int tables_changed,
                            float *rowmin, float *means, float *sigma, float *colmean, float *colshift, const float *Xsample = nullptr,

@@ -1,4 +1,4 @@
-// lsq_q16.h -- level arithmetic and LDS placements of the 16-bit FILTERED node-update kernel (lsq_icmq.hip: one block walks all slices of its
+// lsq_q16.h -- level arithmetic and LDS placement of the 16-bit FILTERED node-update kernel (lsq_icmq.hip: one block walks all slices of its
 // vectors).  gfx950 only; not a public header.  (Round 4's XCD-cooperative variant, schedule 7, lives under the tag r05-schedule7-and-fused-launch.)
 #pragma once
 
@@ -54,29 +54,7 @@ __device__ inline float q16_exact_value(const float *__restrict__ U, const float
 }
 
 
-// LDS placement of a slice table.  A lane owns CPL = 8 NR candidates of its vector's slice: NR 16-byte chunks, chunk c = r LPV + q (r-th read of
-// lane q).  The table is stored as NR planes (plane r = the chunks every lane reads r-th, LPV per row), later planes skewed by 128 bytes:
-// the layout tools/ubench_lds.hip measured best for two lanes per vector (NR = 1: plain rows).  Global Tq keeps plain rows.
-template <int SLQ, int CPL>
-struct WalkqTab {
-    static constexpr int NR = CPL / 8, LPV = SLQ / CPL, EPR = SLQ / 8;                      // reads per lane and table / lanes per vector / entries per row
-    static constexpr int PLANE_E = LSQ_H * LPV + (NR > 1 ? 8 : 0), TS_E = NR * PLANE_E;     // 16-byte entries per plane / per table
-    __device__ static constexpr int entry(int kk, int code, int c) { return kk * TS_E + (c / LPV) * PLANE_E + code * LPV + (c % LPV); }
-    static constexpr int lds_entries(int m) { return (m - 1) * TS_E; }
-    // vectors per block pass with BPC blocks per CU: the slice table + 10 B per vector within the block's share of the 160 KiB
-    static constexpr int pp_for(int m, int bpc, int bytes_per_vector) {
-        const int avail = 160 * 1024 / bpc - 768 - lds_entries(m) * 16;
-        const int v = avail / bytes_per_vector / 64 * 64;
-        return v > 4096 / bpc ? 4096 / bpc : v;
-    }
-    // Round 5: the block keeps a MIRROR of its vectors' validity words in LDS (2 more bytes per vector) so that the compaction at the head of every node
-    // update reads LDS instead of waiting for L2 -- where that costs at most 1/64 of the vectors per pass (plain placement, m = 8: 4032 instead of 4096; m = 16 would drop
-    // from 3968 to 3328 and need a second pass per 10^6-vector chunk: no mirror there)
-    static constexpr bool mirror(int m, int bpc) { return pp_for(m, bpc, 12) * 64 >= pp_for(m, bpc, 10) * 63; }
-    static constexpr int pp(int m, int bpc) { return mirror(m, bpc) ? pp_for(m, bpc, 12) : pp_for(m, bpc, 10); }
-};
-
-// Round 5 (late): "rotated rows" placement for the default geometry up to m = 8 (slices of 32 candidates, four lanes of 16 bytes per vector).
+// The LDS placement of a slice table: "rotated rows" (round 5, late).  Up to m = 8 a slice holds 32 candidates, four lanes of 16 bytes per vector.
 // The slice table is stored code-major in 256-byte lines: byte address = group * 65536 + code * 256 + slot * 64 + lane_q * 16, table kk = 4 group + slot
 // (group 0: tables 0..3, group 1: tables 4..m-2).  Two things follow.  (i) Code and bank are decoupled: the bank quarter of a read is its SLOT, so when the
 // four vectors of a 16-lane group read four different slots the read is conflict-free whatever their codes are -- vector v reads, as the t-th read of a
@@ -84,11 +62,15 @@ struct WalkqTab {
 // E[max rows per bank quarter] = 2.125 LDS cycles per 16-lane group instead of 1: profiles/r05_ubench_lds.txt).  (ii) The code sits in byte 1 of the address:
 // one v_perm_b32 builds an address from the (rotated) code bytes and a lane constant holding the four slot | lane_q bytes -- 9 VALU instructions per item for
 // the seven addresses instead of 16 (extract, shift-add).  With 5..7 tables the free slot 3 of group 1 (64 bytes in every 256) holds the smallest keys
-// (bestA: word ci at line ci / 16, 16 words per line), so the table costs no more LDS than the plain placement: 128 KiB + 8 bytes per vector.
+// (bestA: word ci at line ci / 16, 16 words per line), so the table and the keys cost 128 KiB + 8 bytes per vector.
 // Above m = 8 (slices of 16 candidates, two lanes of 16 bytes per vector: 32-byte rows) a line holds EIGHT slots: group 0 = tables 0..7, group 1 = tables 8..m-2
 // (at most seven: slot 7 of its lines is free and holds the active list, 16 entries per line); the eight vectors of a 16-lane group read eight different slots.
+// The struct also carries the geometry of icm_walkq_kernel<M>: one 1024-thread block per CU, 8 candidates per lane.
 template <int M>
 struct WalkqRot {
+    static constexpr int SLQ = lsq_q16_slice_width(M);                                       // candidates per slice
+    static constexpr int DEPTH = M <= 8 ? 3 : 2;                                             // level items in flight per wave
+    static constexpr int NT = 1024;                                                          // threads per block
     static constexpr int NTAB = M - 1;
     static constexpr int SPL = M <= 8 ? 4 : 8;                                               // slots per 256-byte line
     static constexpr int SLOT_BYTES = 256 / SPL, EPS = SLOT_BYTES / 16;                      // bytes / 16-byte entries per slot (= per table row of a slice)
@@ -106,7 +88,9 @@ struct WalkqRot {
     }
     static constexpr int KEY_BYTES = HOLE ? 4 : 8;                                           // per vector outside the table: bestB (+ bestA)
     static constexpr int LIST_BYTES = LHOLE ? 0 : 2;                                         // ... and the active list
-    // validity mirror (2 bytes per vector, see WalkqTab::mirror): kept where a block pass still holds 10^6 / 256 vectors (BASELINE configs[1] in one pass)
+    // Round 5: the block keeps a MIRROR of its vectors' validity words in LDS (2 more bytes per vector) so that the compaction at the head of every node
+    // update reads LDS instead of waiting for L2 -- kept where a block pass still holds 10^6 / 256 vectors (BASELINE configs[1] in one pass; m = 16 would
+    // drop from 3968 to 3328 vectors and need a second pass per 10^6-vector chunk)
     static constexpr bool mirror() { return M <= 8 && pp_for(KEY_BYTES + LIST_BYTES + 2) * 256 >= 1000000; }
     static constexpr int pp() { return pp_for(KEY_BYTES + LIST_BYTES + (mirror() ? 2 : 0)); }
     static constexpr int lds_bytes() { return TAB_BYTES + pp() * (KEY_BYTES + LIST_BYTES + (mirror() ? 2 : 0)); }
@@ -117,21 +101,13 @@ __device__ inline void static_for(F &&f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<N, F, I + 1>(static_cast<F &&>(f)); }
 }
 
-// Row (kk, code) of a slice table in GLOBAL memory, in rows of SLQ levels.  Slices of 32 candidates up to m = 8 are stored as the LDS image of the rotated
-// placement without its free slot -- [group][code][slot] -- so that a slice is staged by a straight, fully coalesced copy; so are slices of 16 above m = 8
-// (eight slots per line); every other geometry keeps [kk][code].
+// Row (kk, code) of a slice table in GLOBAL memory, in rows of SLQ levels: the LDS image of the rotated placement without its free slot -- [group][code][slot],
+// four slots per line for slices of 32 (m <= 8), eight for slices of 16 (m > 8) -- so that a slice is staged by a straight, fully coalesced copy.
 template <int SLQ>
 __host__ __device__ inline int q16_row_index(int m, int kk, int code) {
-    if ((SLQ == 32 && m <= 8) || (SLQ == 16 && m > 8)) {
-        const int spl = SLQ == 32 ? 4 : 8;
-        const int nt0 = m - 1 < spl ? m - 1 : spl, g = kk >= spl ? 1 : 0;
-        return g ? nt0 * LSQ_H + code * (m - 1 - nt0) + (kk - spl) : code * nt0 + kk;
-    }
-    return kk * LSQ_H + code;
+    const int spl = SLQ == 32 ? 4 : 8;
+    const int nt0 = m - 1 < spl ? m - 1 : spl, g = kk >= spl ? 1 : 0;
+    return g ? nt0 * LSQ_H + code * (m - 1 - nt0) + (kk - spl) : code * nt0 + kk;
 }
-
-// which geometry takes the rotated-rows placement
-constexpr bool walkq_rot(int m, int slq, int cpl, int nt, int bpc) { return ((m <= 8 && slq == 32) || (m > 8 && slq == 16)) && cpl == 8 && nt == 1024 && bpc == 1; }
-
 
 }  // namespace

@@ -77,7 +77,6 @@ constexpr int lsq_walk_pp(int M, int SL) {
     const int pp = avail / 10 / 64 * 64;
     return pp > 4096 ? 4096 : pp;                                             // 4096 up to m = 14 (SL = 8), 4032 at m = 16
 }
-#define LSQ_WALK_PP(M, SL) lsq_walk_pp(M, SL)
 
 // Code j of vector i changes: the whole record leaves as aligned words (a wave's stores cover whole lines: no byte-masked partial writes);
 // callers skip the store when the code is unchanged.
@@ -274,3 +273,17 @@ int optin_lds(LdsOptIn &st, Kern kernel, int bytes) {
 
 
 }  // namespace
+
+// Host dispatch on the number of codebooks: EXPR runs with the compile-time constant M_ = m (1..16); any other m is an error of the calling launcher.
+#define LSQ_DISPATCH_M(m, EXPR)                                                              \
+    switch (m) {                                                                             \
+        case 1: { constexpr int M_ = 1; EXPR; } break;   case 2: { constexpr int M_ = 2; EXPR; } break;   \
+        case 3: { constexpr int M_ = 3; EXPR; } break;   case 4: { constexpr int M_ = 4; EXPR; } break;   \
+        case 5: { constexpr int M_ = 5; EXPR; } break;   case 6: { constexpr int M_ = 6; EXPR; } break;   \
+        case 7: { constexpr int M_ = 7; EXPR; } break;   case 8: { constexpr int M_ = 8; EXPR; } break;   \
+        case 9: { constexpr int M_ = 9; EXPR; } break;   case 10: { constexpr int M_ = 10; EXPR; } break; \
+        case 11: { constexpr int M_ = 11; EXPR; } break; case 12: { constexpr int M_ = 12; EXPR; } break; \
+        case 13: { constexpr int M_ = 13; EXPR; } break; case 14: { constexpr int M_ = 14; EXPR; } break; \
+        case 15: { constexpr int M_ = 15; EXPR; } break; case 16: { constexpr int M_ = 16; EXPR; } break; \
+        default: lsq_set_error("m = %d out of range 1..16", m); return LSQ_EINVAL;          \
+    }

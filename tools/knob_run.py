@@ -1,6 +1,6 @@
 """tools/knob_run.py n d m [key=value ...] -- one timed encode configuration in a fresh process (the tuning build reads its
 environment knobs once per process): prints one JSON line with the step time and the per-class timings.
-    LSQ_WALKQ_BPC=2 python tools/knob_run.py 125000 960 8 tuning=1
+    LSQ_WALK_DIRECT=96 python tools/knob_run.py 125000 960 8 tuning=1
 """
 import importlib, json, os, sys, time
 import torch
