@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 900
+#define LSQ_VERSION 1000
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -129,7 +129,8 @@ LSQ_API int lsq_set_stream(lsq_ctx *ctx, void *hip_stream);
  *        (lsq_encoding_icm chained by a trainer) splits its launch after the first SWEEP and probes that; nothing is remembered between calls.
  *   "async" (0/1, default 0): lsq_encode_icm_dev without any host synchronisation (see there).  Which entry points block: every entry point that
  *        takes or returns HOST buffers waits for its results; lsq_encode_icm_dev waits (per chunk: verdict, probe; at the end: sums) unless "async" = 1;
- *        lsq_linscan_dev, lsq_quantize_norms_dev and lsq_update_codebooks_dev read small control words back (threshold lists, convergence counter) and wait.
+ *        lsq_linscan_dev, lsq_quantize_norms_dev, lsq_update_codebooks_dev and lsq_update_codebooks_struct_dev read small control words back (threshold
+ *        lists, convergence counter, the cover map) and wait.
  *   "ils_counter": the next iteration index used by lsq_encoding_icm / lsq_encode_icm_fully when called with it = LSQ_IT_AUTO
  *        (starts at 0, advances by one per such call).
  *   (liblsq_mi355x_tuning.so only) "ablation": timing-only kernel variants whose results are garbage. */
@@ -347,6 +348,24 @@ LSQ_API int lsq_update_codebooks_lsmr(const float *X, const int16_t *B, int d, i
 LSQ_API int lsq_update_codebooks_gpu(lsq_ctx *ctx, const float *X, const int16_t *B, int d, int64_t n, int m, int h, float *K_out, int *iterations);
 LSQ_API int lsq_update_codebooks_dev(lsq_ctx *ctx, const float *d_X, const uint8_t *d_codes, int d, int64_t n, int m, int h, float *d_K_out,
                                      int *iterations);
+
+/* ---- the structured codebook update (since v1000) -------------------------------------------------------------------------------------------
+ * update_codebooks_generic(X, B, h, odimsfunc) -> C and update_codebooks_chain(X, B, h) -> C      src/codebook_update.jl:104-158
+ * dim2C is the reference's map of dimensions to codebooks (:134-136): a d x m Bool matrix in Julia's (column-major) order, one byte per entry, 1 where
+ * codebook j covers dimension t, every entry 0 or 1 (anything else: LSQ_EINVAL).  For every dimension t, over cbs(t) = the codebooks that cover it, ascending:
+ *     K[t, columns of cbs(t)] = lsqr(S[:, columns of cbs(t)], X[t, :])        K[t, every other column] = 0 (exactly)
+ * with the restatement, tolerances and accumulation rules of lsq_update_codebooks and maxiter = max(n, |cbs(t)| h), the size of the sub-matrix.  A
+ * dimension that no codebook covers gets a zero row.  dim2C = NULL: every codebook covers every dimension -- the call IS the unstructured one below it
+ * (same path, same bits).  The chain's map is get_cbdims_chain(d, m) (:88-102; m >= 2, d >= m - 1).  Layouts, limits and `iterations` as for the
+ * unstructured functions: host code, any h;  _gpu: host buffers on the device solver, h = 256, n m < 2^31;  _dev: device buffers (d_dim2C too: its d m
+ * bytes are read back once per call), uint8 0-BASED codes [n][m], on the context's stream.  K_out may hold anything on entry.  The host solver groups
+ * the dimensions by equal cover set and returns the bits of lsq_update_codebooks called on each group's sub-problem; the device solver has returned the
+ * host solver's bits on every tested problem (required: 1e-5 on the reconstruction). */
+LSQ_API int lsq_update_codebooks_struct(const float *X, const int16_t *B, const uint8_t *dim2C, int d, int64_t n, int m, int h, int nthreads, float *K_out);
+LSQ_API int lsq_update_codebooks_struct_gpu(lsq_ctx *ctx, const float *X, const int16_t *B, const uint8_t *dim2C, int d, int64_t n, int m, int h,
+                                            float *K_out, int *iterations);
+LSQ_API int lsq_update_codebooks_struct_dev(lsq_ctx *ctx, const float *d_X, const uint8_t *d_codes, const uint8_t *d_dim2C, int d, int64_t n, int m,
+                                            int h, float *d_K_out, int *iterations);
 
 /* ---- sparse codebooks: the SPGL1 (LASSO) codebook update ON THE DEVICE (csrc/lsq_spgl1.hip; since v800) -------------------------------------
  * update_codebooks_spgl1(X, B, h, tau, prevC) and update_codebooks_spgl1_threshold(..., S)      src/codebook_update_sparse.jl (the reference calls

@@ -18,7 +18,8 @@ from .reference_api import (  # noqa: F401
     update_codebooks_spgl1, update_codebooks_spgl1_threshold, train_lsq_sparse, knn_exact,
 )
 from .initializers import (  # noqa: F401
-    train_pq, quantize_pq, train_opq, quantize_opq, train_chainq, encoding_viterbi, update_codebooks_chain, get_cbdims_chain,
+    train_pq, quantize_pq, train_opq, quantize_opq, train_chainq, train_chainq_dev, encoding_viterbi, update_codebooks_chain, update_codebooks_generic,
+    get_cbdims_chain,
 )
 from . import distributed  # noqa: F401
 
@@ -26,6 +27,6 @@ __all__ = [
     "Engine", "MultiEngine", "encode_icm_cuda", "encoding_icm", "encode_icm_fully", "get_unaries", "get_binaries",
     "veccost", "qerror", "randinit", "splitarray", "node_order", "device_count", "distributed", "linscan_lsq", "linscan_pq", "linscan_opq", "eval_recall",
     "quantize_norms", "reconstruct", "update_codebooks", "train_lsq", "train_lsq_dev", "train_pq", "quantize_pq", "train_opq", "quantize_opq",
-    "train_chainq", "encoding_viterbi", "update_codebooks_chain", "get_cbdims_chain", "fvecs_read", "ivecs_read", "bvecs_read",
+    "train_chainq", "train_chainq_dev", "encoding_viterbi", "update_codebooks_chain", "update_codebooks_generic", "get_cbdims_chain", "fvecs_read", "ivecs_read", "bvecs_read",
     "update_codebooks_spgl1", "update_codebooks_spgl1_threshold", "train_lsq_sparse", "knn_exact",
 ]

@@ -107,6 +107,9 @@ SIGNATURES = {
     "lsq_update_codebooks_lsmr": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _vp]),
     "lsq_update_codebooks_gpu": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, C.POINTER(_i)]),
     "lsq_update_codebooks_dev": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, C.POINTER(_i)]),
+    "lsq_update_codebooks_struct": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp]),
+    "lsq_update_codebooks_struct_gpu": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, C.POINTER(_i)]),
+    "lsq_update_codebooks_struct_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, C.POINTER(_i)]),
     "lsq_update_codebooks_spgl1": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, C.c_double, _vp, _i64, C.POINTER(Spgl1Params), _vp, C.POINTER(Spgl1Info)]),
     "lsq_update_codebooks_spgl1_dev": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, C.c_double, _vp, _i64, C.POINTER(Spgl1Params), _vp, C.POINTER(Spgl1Info)]),
     "lsq_encode_viterbi": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp]),

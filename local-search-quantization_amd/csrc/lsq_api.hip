@@ -1355,18 +1355,34 @@ extern "C" int lsq_quantize_norms_dev(lsq_ctx *c, const uint8_t *d_codes, const 
     return lsq_launch_quantize_norms(c->stream, d_codes, m, d_K, d_cbnorms, ncb, n, d, m, d_idx_out, nullptr, d_dbnorms, d_norms);
 }
 
-extern "C" int lsq_update_codebooks_dev(lsq_ctx *c, const float *d_X, const uint8_t *d_codes, int d, int64_t n, int m, int h, float *d_K_out,
-                                        int *iterations) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape("lsq_update_codebooks_dev", d, n, m, h));
-    if (n < 1 || !d_X || !d_codes || !d_K_out) { lsq_set_error("lsq_update_codebooks_dev: bad arguments"); return LSQ_EINVAL; }
-    return lsq_lsqr_update_codebooks(c->stream, &c->lsqr, d_X, d_codes, d, n, m, d_K_out, iterations);
+// the LSQR codebook update on the device (lsq_lsqr.hip).  cover: HOST bytes of a structured update's map (checked here), or null = the unstructured update
+static int check_cover(const char *fn, const uint8_t *dim2C, int d, int m) {      // d x m bytes in Julia's column-major order ([m][d] here), every entry 0 or 1
+    for (int64_t e = 0; dim2C && e < (int64_t)d * m; ++e)
+        if (dim2C[e] > 1) { lsq_set_error("%s: dim2C[%lld] = %d is neither 0 nor 1", fn, (long long)e, (int)dim2C[e]); return LSQ_EINVAL; }
+    return LSQ_OK;
 }
 
-extern "C" int lsq_update_codebooks_gpu(lsq_ctx *c, const float *X, const int16_t *B, int d, int64_t n, int m, int h, float *K_out, int *iterations) {
+static int update_codebooks_dev(const char *fn, lsq_ctx *c, const float *d_X, const uint8_t *d_codes, const uint8_t *d_dim2C, int d, int64_t n, int m, int h,
+                                float *d_K_out, int *iterations) {
     LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape("lsq_update_codebooks_gpu", d, n, m, h));
-    if (n < 1 || !X || !B || !K_out) { lsq_set_error("lsq_update_codebooks_gpu: bad arguments"); return LSQ_EINVAL; }
+    LSQ_TRY(check_shape(fn, d, n, m, h));
+    if (n < 1 || !d_X || !d_codes || !d_K_out) { lsq_set_error("%s: bad arguments", fn); return LSQ_EINVAL; }
+    std::vector<uint8_t> cover;                                               // the map's d m bytes: read back, checked and turned into the two lists on the host
+    if (d_dim2C) {
+        cover.resize((size_t)d * m);
+        LSQ_HIP(hipMemcpyAsync(cover.data(), d_dim2C, cover.size(), hipMemcpyDeviceToHost, c->stream));
+        LSQ_HIP(hipStreamSynchronize(c->stream));
+        LSQ_TRY(check_cover(fn, cover.data(), d, m));
+    }
+    return lsq_lsqr_update_codebooks(c->stream, &c->lsqr, d_X, d_codes, d_dim2C ? cover.data() : nullptr, d, n, m, d_K_out, iterations);
+}
+
+static int update_codebooks_gpu(const char *fn, lsq_ctx *c, const float *X, const int16_t *B, const uint8_t *dim2C, int d, int64_t n, int m, int h, float *K_out,
+                                int *iterations) {
+    LSQ_TRY(use_device(c));
+    LSQ_TRY(check_shape(fn, d, n, m, h));
+    if (n < 1 || !X || !B || !K_out) { lsq_set_error("%s: bad arguments", fn); return LSQ_EINVAL; }
+    LSQ_TRY(check_cover(fn, dim2C, d, m));
     LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)n * d));
     LSQ_TRY(c->sK.ensure(sizeof(float) * (size_t)m * LSQ_H * d));
     c->tables_valid = false;
@@ -1374,10 +1390,30 @@ extern "C" int lsq_update_codebooks_gpu(lsq_ctx *c, const float *X, const int16_
     LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));                          // records of stride 8 / 16 -> tight [n][m] below
     LSQ_TRY(c->sTight.ensure((size_t)n * m));
     LSQ_TRY(lsq_launch_codes_compact(c->stream, c->recCur.as<uint8_t>(), n, m, c->sTight.as<uint8_t>()));
-    LSQ_TRY(lsq_lsqr_update_codebooks(c->stream, &c->lsqr, c->sX.as<float>(), c->sTight.as<uint8_t>(), d, n, m, c->sK.as<float>(), iterations));
+    LSQ_TRY(lsq_lsqr_update_codebooks(c->stream, &c->lsqr, c->sX.as<float>(), c->sTight.as<uint8_t>(), dim2C, d, n, m, c->sK.as<float>(), iterations));
     LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, sizeof(float) * (size_t)m * LSQ_H * d, hipMemcpyDeviceToHost, c->stream));
     LSQ_HIP(hipStreamSynchronize(c->stream));
     return LSQ_OK;
+}
+
+extern "C" int lsq_update_codebooks_dev(lsq_ctx *c, const float *d_X, const uint8_t *d_codes, int d, int64_t n, int m, int h, float *d_K_out,
+                                        int *iterations) {
+    return update_codebooks_dev("lsq_update_codebooks_dev", c, d_X, d_codes, nullptr, d, n, m, h, d_K_out, iterations);
+}
+
+extern "C" int lsq_update_codebooks_gpu(lsq_ctx *c, const float *X, const int16_t *B, int d, int64_t n, int m, int h, float *K_out, int *iterations) {
+    return update_codebooks_gpu("lsq_update_codebooks_gpu", c, X, B, nullptr, d, n, m, h, K_out, iterations);
+}
+
+// the structured update: update_codebooks_generic / update_codebooks_chain (src/codebook_update.jl:104-158); a null map is the unstructured call
+extern "C" int lsq_update_codebooks_struct_dev(lsq_ctx *c, const float *d_X, const uint8_t *d_codes, const uint8_t *d_dim2C, int d, int64_t n, int m, int h,
+                                               float *d_K_out, int *iterations) {
+    return update_codebooks_dev(d_dim2C ? "lsq_update_codebooks_struct_dev" : "lsq_update_codebooks_dev", c, d_X, d_codes, d_dim2C, d, n, m, h, d_K_out, iterations);
+}
+
+extern "C" int lsq_update_codebooks_struct_gpu(lsq_ctx *c, const float *X, const int16_t *B, const uint8_t *dim2C, int d, int64_t n, int m, int h, float *K_out,
+                                               int *iterations) {
+    return update_codebooks_gpu(dim2C ? "lsq_update_codebooks_struct_gpu" : "lsq_update_codebooks_gpu", c, X, B, dim2C, d, n, m, h, K_out, iterations);
 }
 
 // ---- the SPGL1 (LASSO) codebook update (lsq_spgl1.hip) ----------------------------------------------------------------------------------------

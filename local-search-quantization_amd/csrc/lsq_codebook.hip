@@ -11,8 +11,15 @@
 //     (S' u)[c] += u[i] for every code c of row i (scatter)
 // Rows of K (dimensions) are independent and are spread over std::thread workers -- the reference spreads
 // them over `julia -p` workers the same way (codebook_update.jl:67-79, splitarray(1:d, nworkers())).
+//
+// The STRUCTURED update, update_codebooks_generic(X, B, h, odimsfunc) / update_codebooks_chain (src/codebook_update.jl:104-169), is the same
+// solver under a cover map dim2C (d x m Bool): dimension t is fitted over the columns of the codebooks that cover it only,
+//     K[t, cbs(t) columns] = lsqr(S[:, cbs(t) columns], X[t, :]),     K[t, other columns] = 0.
+// The dimensions are grouped by equal cover set; a group gets one compact CodeView (its codebooks renumbered 0, 1, ... in ascending order) and
+// every dimension of the group runs lsqr_one on it -- the bits of lsq_update_codebooks called on the group's sub-problem.
 #include <algorithm>
 #include <cmath>
+#include <map>
 #include <thread>
 #include <vector>
 
@@ -263,6 +270,58 @@ static int update_codebooks_host(const float *X, const int16_t *B, int d, int64_
             if (lsmr) lsmr_one(A, b, x, tol, tol, 1e8f, maxiter);
             else lsqr_one(A, b, x, tol, tol, 1e8f, maxiter);
             for (int c = 0; c < cols; ++c) K[(size_t)c * d + t] = x[(size_t)c];
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 0; t < nt; ++t) pool.emplace_back(work, (int)((int64_t)d * t / nt), (int)((int64_t)d * (t + 1) / nt));
+    for (auto &th : pool) th.join();
+    return LSQ_OK;
+}
+
+// update_codebooks_generic(X, B, h, odimsfunc) / update_codebooks_chain(X, B, h)   (src/codebook_update.jl:104-158)
+// dim2C: the reference's Bool map (:134-136), d x m in Julia's column-major order = [m][d] bytes here, 0 / 1.  NULL: every codebook covers every dimension.
+extern "C" int lsq_update_codebooks_struct(const float *X, const int16_t *B, const uint8_t *dim2C, int d, int64_t n, int m, int h, int nthreads, float *K) {
+    if (!dim2C) return update_codebooks_host(X, B, d, n, m, h, nthreads, K, false);
+    if (d < 1 || n < 1 || m < 1 || h < 1 || !X || !B || !K) { lsq_set_error("lsq_update_codebooks_struct: bad arguments"); return LSQ_EINVAL; }
+    for (int64_t e = 0; e < (int64_t)d * m; ++e)
+        if (dim2C[e] > 1) { lsq_set_error("lsq_update_codebooks_struct: dim2C[%lld] = %d is neither 0 nor 1", (long long)e, (int)dim2C[e]); return LSQ_EINVAL; }
+    for (int64_t e = 0; e < n * (int64_t)m; ++e)
+        if (B[e] < 1 || B[e] > h) { lsq_set_error("lsq_update_codebooks_struct: code %d outside 1..%d", (int)B[e], h); return LSQ_ECODE; }
+    // the dimensions grouped by equal cover set; one compact view per group
+    struct Group { std::vector<int> cbs; std::vector<int32_t> col; };
+    std::map<std::vector<int>, int> index;
+    std::vector<Group> groups;
+    std::vector<int> group_of((size_t)d);
+    for (int t = 0; t < d; ++t) {
+        std::vector<int> cbs;
+        for (int j = 0; j < m; ++j) if (dim2C[(size_t)j * d + t]) cbs.push_back(j);
+        auto it = index.find(cbs);
+        if (it == index.end()) { it = index.emplace(cbs, (int)groups.size()).first; groups.push_back(Group{cbs, {}}); }
+        group_of[(size_t)t] = it->second;
+    }
+    for (auto &g : groups) {
+        const int q = (int)g.cbs.size();
+        g.col.resize((size_t)n * q);
+        for (int64_t i = 0; i < n; ++i)
+            for (int k = 0; k < q; ++k) g.col[(size_t)(i * q + k)] = k * h + (B[i * m + g.cbs[(size_t)k]] - 1);
+    }
+    std::fill(K, K + (size_t)m * h * d, 0.0f);
+    const float tol = std::sqrt(1.1920929e-07f);             // sqrt(eps(Float32)): IterativeSolvers' default atol = btol
+    int nt = nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency();
+    if (nt < 1) nt = 1;
+    if (nt > d) nt = d;
+    auto work = [&](int t0, int t1) {
+        std::vector<float> b((size_t)n), x;
+        for (int t = t0; t < t1; ++t) {
+            const Group &g = groups[(size_t)group_of[(size_t)t]];
+            const int q = (int)g.cbs.size(), cols = q * h;
+            if (q == 0) continue;                            // no codebook covers t: the row stays zero
+            const CodeView A{g.col.data(), n, q, cols};
+            for (int64_t i = 0; i < n; ++i) b[(size_t)i] = X[i * d + t];
+            x.assign((size_t)cols, 0.0f);
+            lsqr_one(A, b, x, tol, tol, 1e8f, n > cols ? n : cols);      // maxiter = max(size(S[:, rcbs]))
+            for (int k = 0; k < q; ++k)
+                for (int a = 0; a < h; ++a) K[((size_t)g.cbs[(size_t)k] * h + a) * d + t] = x[(size_t)(k * h + a)];
         }
     };
     std::vector<std::thread> pool;

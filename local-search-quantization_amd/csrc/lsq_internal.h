@@ -268,7 +268,8 @@ int lsq_launch_quantize_norms(hipStream_t s, const uint8_t *codes, int stride, c
 // ---- LSQR codebook update on the device (lsq_lsqr.hip) ---------------------------------------------------------------------------------------
 struct lsq_lsqr_state;
 void lsq_lsqr_free(lsq_lsqr_state *st);
-int lsq_lsqr_update_codebooks(hipStream_t s, lsq_lsqr_state **st, const float *dX, const uint8_t *dcodes, int d, int64_t n, int m, float *dK, int *iters_out);
+int lsq_lsqr_update_codebooks(hipStream_t s, lsq_lsqr_state **st, const float *dX, const uint8_t *dcodes, const uint8_t *cover, int d, int64_t n, int m,
+                              float *dK, int *iters_out);      // cover: HOST bytes [m][d] (0 / 1) of a structured update, or null
 // the rows of a code matrix sorted by (codebook j, code) once per call: keys and segment starts live in `buf` (shared by lsq_lsqr.hip and lsq_spgl1.hip)
 int lsq_sort_rows_by_code(hipStream_t s, DevBuf &buf, const uint8_t *dcodes, int64_t n, int m, const uint64_t **sorted, const int64_t **seg);
 

@@ -14,9 +14,23 @@
 // The norms are summed in a fixed order too (partial sums of fixed item sets, combined in a fixed order), so a call returns the same bits every time;
 // S'u is added in the host's own order, the norms are not (the host adds its squares one by one: the double sums differ in their last bits, their Float32 roundings have not differed on any tested problem -- tests require 1e-5 and compare both solvers with scipy's).
 // One iteration = two passes over U (n d floats each, the second through the sorted rows, m times) and a few over V, plus d-thread scalar kernels.
+//
+// The STRUCTURED update (update_codebooks_generic / update_codebooks_chain, src/codebook_update.jl:104-158) is the same solver under a cover map
+// dim2C (d x m, 0 / 1): system t sees the columns of the codebooks that cover t only, K[other columns, t] = 0, maxiter_t = max(n, |cbs(t)| h).
+// Two lists are derived from the map once per call and kept in device memory (struct Cover):
+//     per dimension t   the covering codebooks, ascending, as nibbles of one 64-bit word (m <= 16) + their count     -> the row pass gathers |cbs(t)| rows of V
+//     per codebook j    the dimensions it covers, ascending, + their count                                          -> the column pass indexes its threads over them
+// and the two passes over U are instantiated a second time (template <bool MAP>) to walk them; without a map (MAP = false) their code, grids and
+// arithmetic are the unstructured ones.  The V-sized passes (lsqr_reduce modes 1 and 2, lsqr_xw_update) are NOT restricted: V and W are cleared at the
+// start of a structured call, the column pass never writes an uncovered (column, t) entry, so it stays +0.0 through v *= ia, x += t1 w and w = t2 w + v,
+// and the sums run over all columns as they do -- adding +0.0 to a non-negative double changes nothing, and since h is a multiple of 4 a covered column
+// falls in the same one of the four partial sums, in the same order, as in the compact numbering of the covered codebooks: the bits of this solver run
+// on the sub-problem (X restricted to the dimensions of one cover set, the codes to its codebooks).  K_out ends with exact zeros outside the cover.
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
+#include <cstring>
+#include <vector>
 
 #include "lsq_internal.h"
 
@@ -29,6 +43,14 @@ struct Scal {        // per-system scalars, arrays of d floats each
     int *done;       // 1: the system has stopped
     double *sumU, *sumV, *dk2;
     int *active;     // [1] systems still running (written by the last scalar kernel of an iteration)
+};
+
+// the cover map of a structured update as the two passes read it (device memory; unused when MAP = false)
+struct Cover {
+    const uint64_t *row_ids;  // [d] the codebooks covering t, ascending: id k in bits 4 k .. 4 k + 3
+    const uint8_t *row_cnt;   // [d] how many
+    const int *col_dims;      // [m][d] the dimensions codebook j covers, ascending (the first col_cnt[j] entries of row j)
+    const int *col_cnt;       // [m]
 };
 
 constexpr int TB = 64;        // systems (dimensions) per block column
@@ -54,8 +76,12 @@ __global__ void lsqr_segments(const uint64_t *__restrict__ sorted, int64_t total
 
 // first pass: u = b.  later passes: u = S v - alpha (u ib)   (u is stored UNSCALED: fl(u ib) -- the host's scaled vector -- is formed wherever it is read).
 // part[block][t] = the block's sum of u^2 (double, rows ascending).
+// MAP: a (row, t) item gathers V for the codebooks of t's list only (trip count |cbs(t)| instead of m, same eight-rows-in-flight shape).  Lanes are
+// consecutive t: where their lists agree (everywhere but across a boundary between two cover sets) the code bytes and the V rows of a load are the
+// same for the whole wave, as without a map.
+template <bool MAP>
 __global__ __launch_bounds__(256) void lsqr_u_update(const float *__restrict__ X, float *__restrict__ U, const float *__restrict__ V, const uint8_t *__restrict__ codes,
-                                                     int64_t n, int d, int m, Scal S, double *__restrict__ part, int init) {
+                                                     int64_t n, int d, int m, Scal S, double *__restrict__ part, int init, Cover C) {
     const int t = blockIdx.y * TB + (threadIdx.x & (TB - 1));
     const int sub = threadIdx.x >> 6;
     const int64_t r0 = ((int64_t)blockIdx.x * 4 + sub) * RS;
@@ -64,6 +90,8 @@ __global__ __launch_bounds__(256) void lsqr_u_update(const float *__restrict__ X
     if (t < d && !(S.done[t])) {
         const float alpha = S.alpha[t], ib = S.ib[t];
         const int64_t r1 = (r0 + RS < n) ? r0 + RS : n;
+        const int cnt = MAP ? (int)C.row_cnt[t] : m;               // codebooks added per row
+        const uint64_t ids = MAP ? C.row_ids[t] : 0;
         int64_t i = r0;
         constexpr int G = 8;                                       // rows in flight: their loads are issued together, the sums keep the row order
         for (; i + G <= r1; i += G) {
@@ -75,7 +103,8 @@ __global__ __launch_bounds__(256) void lsqr_u_update(const float *__restrict__ X
                 float old[G], sv[G];
 #pragma unroll
                 for (int q = 0; q < G; ++q) { old[q] = U[(i + q) * d + t]; sv[q] = 0.0f; }
-                for (int j = 0; j < m; ++j) {                      // codebooks ascending within every row, as the host adds them
+                for (int k = 0; k < cnt; ++k) {                    // codebooks ascending within every row, as the host adds them
+                    const int j = MAP ? (int)((ids >> (4 * k)) & 15) : k;
                     float g[G];
 #pragma unroll
                     for (int q = 0; q < G; ++q) g[q] = V[((int64_t)j * LSQ_H + codes[(i + q) * m + j]) * d + t];
@@ -94,7 +123,7 @@ __global__ __launch_bounds__(256) void lsqr_u_update(const float *__restrict__ X
             else {
                 const uint8_t *c = codes + i * m;
                 float sv = 0.0f;
-                for (int j = 0; j < m; ++j) sv += V[((int64_t)j * LSQ_H + c[j]) * d + t];
+                for (int k = 0; k < cnt; ++k) { const int j = MAP ? (int)((ids >> (4 * k)) & 15) : k; sv += V[((int64_t)j * LSQ_H + c[j]) * d + t]; }
                 u = -alpha * (U[i * d + t] * ib) + sv;
             }
             U[i * d + t] = u;
@@ -107,20 +136,32 @@ __global__ __launch_bounds__(256) void lsqr_u_update(const float *__restrict__ X
 }
 
 // v = (float)(S'(u ib))  (first pass)  or  (float)(-beta v + S'(u ib)):  one thread per (column, system) walks the column's rows in ascending order
+// MAP: the threads of column c (codebook c / h) are indexed over the dimensions that codebook covers, compactly (grid.y = ceil(longest list / TB)): a
+// chain's ~2 d / (m - 1) dimensions per codebook fill one or two waves, and inside a block of consecutive covered dimensions the lanes' loads of
+// U[row d + t] stay contiguous.  Uncovered (c, t) entries are never written.
+template <bool MAP>
 __global__ __launch_bounds__(TB) void lsqr_v_update(float *__restrict__ V, const float *__restrict__ U, const uint64_t *__restrict__ sorted,
-                                                    const int64_t *__restrict__ seg, int d, Scal S, int first) {
-    const int c = blockIdx.x, t = blockIdx.y * TB + threadIdx.x;
+                                                    const int64_t *__restrict__ seg, int d, Scal S, int first, Cover C) {
+    const int c = blockIdx.x;
+    int t = blockIdx.y * TB + threadIdx.x;
+    if (MAP) {
+        const int j = c / LSQ_H;
+        if (t >= C.col_cnt[j]) return;
+        t = C.col_dims[(int64_t)j * d + t];
+    }
     if (t >= d || S.done[t] || !(S.beta[t] > 0.0f)) return;
     const float ib = S.ib[t];
     const int64_t e0 = seg[c], e1 = seg[c + 1];
     double acc = 0.0;
     int64_t e = e0;
-    for (; e + 8 <= e1; e += 8) {                                 // eight rows in flight; the additions stay in row order
-        float u[8];
+    constexpr int F = MAP ? 16 : 8;                               // rows in flight (the additions stay in row order).  With a map the grid is a few waves
+                                                                  // per SIMD and the walk is bound by its latency, not by bytes: twice the loads per round trip
+    for (; e + F <= e1; e += F) {
+        float u[F];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) u[q] = U[(int64_t)(uint32_t)sorted[e + q] * d + t];
+        for (int q = 0; q < F; ++q) u[q] = U[(int64_t)(uint32_t)sorted[e + q] * d + t];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) acc += (double)(u[q] * ib);
+        for (int q = 0; q < F; ++q) acc += (double)(u[q] * ib);
     }
     for (; e < e1; ++e) acc += (double)(U[(int64_t)(uint32_t)sorted[e] * d + t] * ib);
     const int64_t o = (int64_t)c * d + t;
@@ -239,7 +280,9 @@ __global__ void lsqr_scal_rotate(int d, Scal S) {                  // after a v 
     S.tau[t] = sn * phi;
 }
 
-__global__ void lsqr_scal_stop(int d, Scal S, float atol, float btol, float ctol) {      // after the x / w pass: norm estimates and the stopping rules of Paige & Saunders
+// after the x / w pass: norm estimates and the stopping rules of Paige & Saunders.  maxit (structured update; else null): system t also stops after
+// maxit[t] iterations, itn being the 1-based number of the iteration just done (without a map every system has the host loop's bound)
+__global__ void lsqr_scal_stop(int d, Scal S, float atol, float btol, float ctol, const int *__restrict__ maxit, int itn) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= d || S.done[t]) return;
     const float rho = S.rho[t], phi = S.phi[t], theta = S.theta[t], tau = S.tau[t], alpha = S.alpha[t], Anorm = S.Anorm[t], bnorm = S.bnorm[t];
@@ -267,6 +310,7 @@ __global__ void lsqr_scal_stop(int d, Scal S, float atol, float btol, float ctol
     const float rtol = btol + atol * Anorm * xnorm / bnorm;
     bool stop = (1 + test3 <= 1) || (1 + test2 <= 1) || (1 + tt1 <= 1);
     stop = stop || (test3 <= ctol) || (test2 <= atol) || (test1 <= rtol);
+    if (maxit) stop = stop || itn >= maxit[t];
     if (stop) S.done[t] = 1;
     else atomicAdd(S.active, 1);
 }
@@ -297,18 +341,22 @@ int lsq_sort_rows_by_code(hipStream_t s, DevBuf &buf, const uint8_t *dcodes, int
 struct lsq_lsqr_state {
     DevBuf work;      // U, V, W, the per-block norm partials and the per-system scalars of one update
     DevBuf keys;      // (column, row) keys: unsorted, sorted, segment starts, the sort's temporary storage
+    DevBuf cover;     // structured update: the two lists of the cover map and the per-system iteration bounds
+    std::vector<char> cover_host;      // their host image (lives until the call's first synchronisation)
 };
 
 void lsq_lsqr_free(lsq_lsqr_state *st) {
     if (!st) return;
     st->work.release();
     st->keys.release();
+    st->cover.release();
     delete st;
 }
 
-// dX [n][d], dcodes [n][m] u8 0-based, dK [m*256][d] (output); all device pointers.  iters_out (optional, host): iterations of the slowest system.
-int lsq_lsqr_update_codebooks(hipStream_t s, lsq_lsqr_state **pst, const float *dX, const uint8_t *dcodes, int d, int64_t n, int m, float *dK,
-                              int *iters_out) {
+// dX [n][d], dcodes [n][m] u8 0-based, dK [m*256][d] (output; fully written): device pointers.  cover: HOST bytes [m][d], 0 / 1 (checked by the caller), or
+// null = the unstructured update.  iters_out (optional, host): iterations of the slowest system.
+int lsq_lsqr_update_codebooks(hipStream_t s, lsq_lsqr_state **pst, const float *dX, const uint8_t *dcodes, const uint8_t *cover, int d, int64_t n, int m,
+                              float *dK, int *iters_out) {
     if (!*pst) *pst = new lsq_lsqr_state();
     lsq_lsqr_state *st = *pst;
     const int cols = m * LSQ_H;
@@ -336,6 +384,39 @@ int lsq_lsqr_update_codebooks(hipStream_t s, lsq_lsqr_state **pst, const float *
     S.active = reinterpret_cast<int *>(dbl + 3 * d);
     LSQ_HIP(hipMemsetAsync(base + off_sc, 0, wtotal - off_sc, s));      // scalars, done flags, double sums, the counter
 
+    // structured update: the two lists of the cover map and the per-system iteration bounds, built here and uploaded once per call
+    Cover C{nullptr, nullptr, nullptr, nullptr};
+    const int *maxit = nullptr;
+    int longest = d, widest = m;                                 // the longest list of a codebook, the most codebooks on a dimension
+    if (cover) {
+        const size_t o_ids = 0, o_dims = o_ids + (size_t)d * 8, o_cnt = o_dims + (size_t)m * d * 4, o_maxit = o_cnt + (size_t)m * 4,
+                     o_rcnt = o_maxit + (size_t)d * 4, ctotal = o_rcnt + (size_t)d;
+        st->cover_host.assign(ctotal, 0);
+        char *hb = st->cover_host.data();
+        uint64_t *ids = reinterpret_cast<uint64_t *>(hb + o_ids);
+        int *dims = reinterpret_cast<int *>(hb + o_dims), *ccnt = reinterpret_cast<int *>(hb + o_cnt), *mi = reinterpret_cast<int *>(hb + o_maxit);
+        uint8_t *rcnt = reinterpret_cast<uint8_t *>(hb + o_rcnt);
+        longest = 0; widest = 0;
+        for (int j = 0; j < m; ++j)
+            for (int t = 0; t < d; ++t)
+                if (cover[(size_t)j * d + t]) {
+                    ids[t] |= (uint64_t)j << (4 * rcnt[t]++);    // j ascending: the list of t is ascending
+                    dims[(size_t)j * d + ccnt[j]++] = t;
+                }
+        for (int j = 0; j < m; ++j) longest = ccnt[j] > longest ? ccnt[j] : longest;
+        for (int t = 0; t < d; ++t) {
+            widest = rcnt[t] > widest ? rcnt[t] : widest;
+            mi[t] = (int)(n > (int64_t)rcnt[t] * LSQ_H ? n : (int64_t)rcnt[t] * LSQ_H);      // max(size(S[:, rcbs])), IterativeSolvers' default
+        }
+        LSQ_TRY(st->cover.ensure(ctotal));
+        char *db = st->cover.as<char>();
+        LSQ_HIP(hipMemcpyAsync(db, hb, ctotal, hipMemcpyHostToDevice, s));
+        C = Cover{reinterpret_cast<const uint64_t *>(db + o_ids), reinterpret_cast<const uint8_t *>(db + o_rcnt), reinterpret_cast<const int *>(db + o_dims),
+                  reinterpret_cast<const int *>(db + o_cnt)};
+        maxit = reinterpret_cast<const int *>(db + o_maxit);
+        LSQ_HIP(hipMemsetAsync(base + off_V, 0, off_part - off_V, s));      // V and W: an uncovered entry is never written and must read +0.0
+    }
+
     // the rows sorted by code, once per call
     const uint64_t *sorted = nullptr;
     const int64_t *seg = nullptr;
@@ -343,17 +424,19 @@ int lsq_lsqr_update_codebooks(hipStream_t s, lsq_lsqr_state **pst, const float *
 
     const dim3 rows_grid((unsigned)nblocks, (unsigned)((d + TB - 1) / TB));
     const dim3 cols_grid((unsigned)((cols + 63) / 64), (unsigned)((d + TB - 1) / TB));
-    const dim3 seg_grid((unsigned)cols, (unsigned)((d + TB - 1) / TB));
+    const dim3 seg_grid((unsigned)cols, (unsigned)((longest + TB - 1) / TB > 0 ? (longest + TB - 1) / TB : 1));
     const unsigned sgrid = (unsigned)((d + 127) / 128);
     const float tol = sqrtf(1.1920929e-07f);                      // sqrt(eps(Float32)): IterativeSolvers' default atol = btol
     const float ctol = 1.0f / 1e8f;
-    const int64_t maxiter = n > cols ? n : cols;
+    const int64_t maxiter = n > (int64_t)widest * LSQ_H ? n : (int64_t)widest * LSQ_H;      // the largest per-system bound (no map: max(n, cols))
+    const auto u_update = cover ? lsqr_u_update<true> : lsqr_u_update<false>;
+    const auto v_update = cover ? lsqr_v_update<true> : lsqr_v_update<false>;
 
     // start: beta u = b, alpha v = S' u, w = v, x = 0
-    hipLaunchKernelGGL(lsqr_u_update, rows_grid, dim3(256), 0, s, dX, U, V, dcodes, n, d, m, S, part, 1);
+    hipLaunchKernelGGL(u_update, rows_grid, dim3(256), 0, s, dX, U, V, dcodes, n, d, m, S, part, 1, C);
     hipLaunchKernelGGL(lsqr_reduce, dim3((unsigned)((d + TB - 1) / TB)), dim3(256), 0, s, part, nblocks, V, cols, d, S, 0);
     hipLaunchKernelGGL(lsqr_scal_beta, dim3(sgrid), dim3(128), 0, s, d, S, 1);
-    hipLaunchKernelGGL(lsqr_v_update, seg_grid, dim3(TB), 0, s, V, U, sorted, seg, d, S, 1);
+    hipLaunchKernelGGL(v_update, seg_grid, dim3(TB), 0, s, V, U, sorted, seg, d, S, 1, C);
     hipLaunchKernelGGL(lsqr_reduce, dim3((unsigned)((d + TB - 1) / TB)), dim3(256), 0, s, part, nblocks, V, cols, d, S, 1);
     hipLaunchKernelGGL(lsqr_scal_init, dim3(sgrid), dim3(128), 0, s, d, S);
     hipLaunchKernelGGL(lsqr_xw_update, cols_grid, dim3(256), 0, s, V, W, dK, cols, d, S, 1);
@@ -366,15 +449,15 @@ int lsq_lsqr_update_codebooks(hipStream_t s, lsq_lsqr_state **pst, const float *
         const int burst = itn < 8 ? 4 : 2;                        // iterations between two looks at the counter (a frozen system costs nothing but its slot)
         for (int b = 0; b < burst && itn < maxiter; ++b, ++itn) {
             LSQ_HIP(hipMemsetAsync(S.active, 0, sizeof(int), s));
-            hipLaunchKernelGGL(lsqr_u_update, rows_grid, dim3(256), 0, s, dX, U, V, dcodes, n, d, m, S, part, 0);
+            hipLaunchKernelGGL(u_update, rows_grid, dim3(256), 0, s, dX, U, V, dcodes, n, d, m, S, part, 0, C);
             hipLaunchKernelGGL(lsqr_reduce, dim3((unsigned)((d + TB - 1) / TB)), dim3(256), 0, s, part, nblocks, V, cols, d, S, 0);
             hipLaunchKernelGGL(lsqr_scal_beta, dim3(sgrid), dim3(128), 0, s, d, S, 0);
-            hipLaunchKernelGGL(lsqr_v_update, seg_grid, dim3(TB), 0, s, V, U, sorted, seg, d, S, 0);
+            hipLaunchKernelGGL(v_update, seg_grid, dim3(TB), 0, s, V, U, sorted, seg, d, S, 0, C);
             hipLaunchKernelGGL(lsqr_reduce, dim3((unsigned)((d + TB - 1) / TB)), dim3(256), 0, s, part, nblocks, V, cols, d, S, 1);
             hipLaunchKernelGGL(lsqr_scal_rotate, dim3(sgrid), dim3(128), 0, s, d, S);
             hipLaunchKernelGGL(lsqr_reduce, dim3((unsigned)((d + TB - 1) / TB)), dim3(256), 0, s, part, nblocks, W, cols, d, S, 2);
             hipLaunchKernelGGL(lsqr_xw_update, cols_grid, dim3(256), 0, s, V, W, dK, cols, d, S, 0);
-            hipLaunchKernelGGL(lsqr_scal_stop, dim3(sgrid), dim3(128), 0, s, d, S, tol, tol, ctol);
+            hipLaunchKernelGGL(lsqr_scal_stop, dim3(sgrid), dim3(128), 0, s, d, S, tol, tol, ctol, maxit, (int)itn + 1);
         }
         LSQ_HIP(hipMemcpyAsync(&active, S.active, sizeof(int), hipMemcpyDeviceToHost, s));
         LSQ_HIP(hipStreamSynchronize(s));

@@ -298,6 +298,46 @@ class Engine:
             self._check(self._L.lsq_update_codebooks_dev(self._h, dX.data_ptr(), dcodes.data_ptr(), d, n, m, h, dK.data_ptr(), C.byref(it)))
         return dK, int(it.value)
 
+    # -- the structured codebook update: update_codebooks_generic / update_codebooks_chain (codebook_update.jl:104-158) ------------------
+    def update_codebooks_struct(self, X, B, dim2C, m, h=H):
+        """X (n,d) f32, B (n,m) int16 1-based, dim2C (d,m) 0/1 (codebook j covers dimension t) or None (every codebook covers everything): host arrays
+        -> K (m*h,d) least-squares codebooks over the covering codebooks only, exactly zero elsewhere; LSQR iterations   [lsq_update_codebooks_struct_gpu]"""
+        X, B = _np(X, np.float32), _np(B, np.int16)
+        n, d = X.shape
+        if B.shape != (n, m):
+            raise ValueError("shape mismatch: X %s B %s m=%d" % (X.shape, B.shape, m))
+        cover = None if dim2C is None else cover_bytes(dim2C, d, m)
+        K = np.empty((m * h, d), dtype=np.float32)
+        it = C.c_int(0)
+        self._check(self._L.lsq_update_codebooks_struct_gpu(self._h, X.ctypes.data, B.ctypes.data, None if cover is None else cover.ctypes.data, d, n, m, h,
+                                                            K.ctypes.data, C.byref(it)))
+        return K, int(it.value)
+
+    def update_codebooks_struct_dev(self, dX, dcodes, ddim2C, m, h=H, out=None):
+        """device tensors: X (n,d) f32, codes (n,m) uint8 0-based; dim2C (d,m) 0/1 as a device tensor (uint8 or bool), a host array, or None
+        -> K (m*h,d) f32 tensor (`out` when given: it may hold anything), LSQR iterations   [lsq_update_codebooks_struct_dev]"""
+        import torch
+        assert dX.is_cuda and dcodes.is_cuda and dX.dtype == torch.float32 and dcodes.dtype == torch.uint8 and dX.is_contiguous() and dcodes.is_contiguous()
+        n, d = dX.shape
+        if dcodes.shape != (n, m):
+            raise ValueError("shape mismatch")
+        if ddim2C is None:
+            dcover = None
+        elif isinstance(ddim2C, torch.Tensor):
+            if tuple(ddim2C.shape) != (d, m):
+                raise ValueError("dim2C must be (d, m) = (%d, %d), got %s" % (d, m, tuple(ddim2C.shape)))
+            dcover = ddim2C.to(device=dX.device, dtype=torch.uint8).t().contiguous()          # Julia's d x m in memory: [m][d]
+        else:
+            dcover = torch.from_numpy(cover_bytes(ddim2C, d, m)).to(dX.device)
+        dK = out if out is not None else torch.empty((m * h, d), dtype=torch.float32, device=dX.device)
+        if tuple(dK.shape) != (m * h, d) or dK.dtype != torch.float32 or not dK.is_cuda or not dK.is_contiguous():
+            raise ValueError("out must be a contiguous (m*h, d) = (%d, %d) f32 device tensor" % (m * h, d))
+        it = C.c_int(0)
+        with self._on_torch_stream():
+            self._check(self._L.lsq_update_codebooks_struct_dev(self._h, dX.data_ptr(), dcodes.data_ptr(), None if dcover is None else dcover.data_ptr(),
+                                                                d, n, m, h, dK.data_ptr(), C.byref(it)))
+        return dK, int(it.value)
+
     # -- the sparse codebook update: SPGL1's LASSO mode (csrc/lsq_spgl1.hip) ---------------------------------
     @staticmethod
     def _spgl1_params(opt_tol, max_iter):
@@ -492,6 +532,15 @@ class Engine:
 
 
 # -- host-only pieces of the path (no GPU needed) ---------------------------------------------
+
+def cover_bytes(dim2C, d, m):
+    """A cover map given as a (d, m) array of 0 / 1 (the reference's dim2C, codebook_update.jl:134-136) -> the bytes the C-ABI reads: Julia's column-major
+    d x m, i.e. a contiguous (m, d) uint8 array.  Values are passed on as they are (the library rejects anything but 0 and 1)."""
+    a = np.asarray(dim2C)
+    if a.shape != (d, m):
+        raise ValueError("dim2C must be (d, m) = (%d, %d), got %s" % (d, m, a.shape))
+    return np.ascontiguousarray(a.T.astype(np.uint8))
+
 
 def check_spgl1_args(xshape, bshape, m, h, tau, S, kshape=None, opt_tol=None, max_iter=None):
     """The argument rules of lsq_update_codebooks_spgl1, checked before any device is touched: X (n, d), codes (n, m), K_init (m h, d)."""

@@ -11,7 +11,10 @@ The two data-parallel steps run ON THE DEVICE through the C-ABI (csrc/lsq_init.h
 their k-means (`lsq_assign_codewords`: every sub-space of a vector set in one call, codebooks padded to d rows) and ChainQ's Viterbi encoder
 (`lsq_encode_viterbi`).  Like the rest of the engine they need h == 256 and a gfx950 device -- there is no CPU fallback; the numpy restatement of
 these steps lives in oracle/init_oracle.py as the checker (tests only).  What stays on the host is the glue around them: k-means++ seeding, cluster
-means, the Procrustes SVD, the chain's per-dimension LSQR (scipy), and the scalar k-means of the norm codebook (an O(n log h) sorted search).
+means, the Procrustes SVD, and the scalar k-means of the norm codebook (an O(n log h) sorted search).  The chain's structured LSQR codebook update runs
+by default in scipy (float64, a Python loop over the dimensions: the checker's own path); `solver="host"` selects the C-ABI host solver
+(lsq_update_codebooks_struct) and `engine=<Engine>` the device solver (lsq_update_codebooks_struct_gpu / _dev), which train_chainq_dev uses with X,
+codes and codebooks resident in HBM.
 PARITY UNPINNED: the reference delegates to Clustering.jl k-means, StatsBase sampling and IterativeSolvers LSQR,
 none vendored or version-pinned, and has no tests for them; what is mirrored is the algorithm and the interfaces.
 Shapes follow Julia: X is d x n, codes B are m x n Int16 **1-based**, codebooks are lists of (rows x h) matrices.
@@ -20,8 +23,8 @@ import numpy as np
 
 from .engine import splitarray
 
-__all__ = ["train_pq", "quantize_pq", "qerror_pq", "train_opq", "quantize_opq", "get_cbdims_chain",
-           "update_codebooks_chain", "encoding_viterbi", "train_chainq", "kmeans"]
+__all__ = ["train_pq", "quantize_pq", "qerror_pq", "train_opq", "quantize_opq", "get_cbdims_chain", "update_codebooks_generic",
+           "update_codebooks_chain", "encoding_viterbi", "train_chainq", "train_chainq_dev", "kmeans"]
 
 
 def _f32(a):
@@ -241,7 +244,10 @@ def train_opq(X, m, h, niter, init="natural", V=False, *, seed=0, engine=None):
 # ---- ChainQ (src/chainq/chainq.jl, src/encodings/encode_chain.jl, src/codebook_update.jl:88-169) -------------------
 def get_cbdims_chain(d, m):
     """Dimensions each codebook of a chain covers: consecutive codebooks overlap on one of the m-1 blocks.
-    src/codebook_update.jl:88-102.  Returns m 0-based slices."""
+    src/codebook_update.jl:88-102.  Returns m 0-based slices.  A chain needs m >= 2 codebooks and one dimension per block, d >= m - 1."""
+    if m < 2 or d < m - 1:
+        from ._lib import LSQ_EINVAL, LsqError
+        raise LsqError(LSQ_EINVAL, "get_cbdims_chain: a chain needs m >= 2 and d >= m - 1, got d=%d m=%d" % (d, m))
     sub = splitarray(d, m - 1)
     od = [slice(sub[0][0], sub[0][1])]
     for i in range(1, m - 1):
@@ -250,29 +256,63 @@ def get_cbdims_chain(d, m):
     return od
 
 
-def update_codebooks_chain(X, B, h, V=False):
-    """Least-squares codebooks under the chain's dimension structure: for every dimension t only the codebooks that
-    cover t are fitted (LSQR on the corresponding columns of the one-hot code matrix).  src/codebook_update.jl:104-169"""
-    from scipy.sparse import csr_matrix
-    from scipy.sparse.linalg import lsqr
+def _cover_map(odims, d, m):
+    """dim2C of the reference (codebook_update.jl:134-136): (d, m) uint8, 1 where codebook i covers dimension t.  odims: per codebook a slice or an index list."""
+    dim2C = np.zeros((d, m), dtype=np.uint8)
+    for i in range(m):
+        dim2C[odims[i], i] = 1
+    return dim2C
+
+
+def update_codebooks_generic(X, B, h, odimsfunc, V=False, *, nthreads=0, engine=None, solver=None):
+    """Least-squares codebooks under a dimension structure: odimsfunc(d, m) says which dimensions each codebook has, and for every dimension t only
+    the codebooks that cover t are fitted (LSQR on the corresponding columns of the one-hot code matrix); the others stay zero there.
+    src/codebook_update.jl:104-158.  Three solvers of the same systems (atol = btol = sqrt(eps_f32), conlim = 1e8):
+      solver=None, engine=None   scipy's LSQR in float64, a Python loop over the dimensions (the default);
+      solver="host"              the C-ABI host solver, f32 LSQR on `nthreads` cores (lsq_update_codebooks_struct);
+      engine=<Engine>            the device solver, all dimensions at once (lsq_update_codebooks_struct_gpu)."""
+    if solver not in (None, "host"):
+        raise ValueError("solver must be None or 'host', got %r" % (solver,))
     X = _f32(X)
     d, n = X.shape
+    m = np.shape(B)[0]
+    od = odimsfunc(d, m)
+    if solver == "host" or engine is not None:
+        from . import _lib
+        Xr = np.ascontiguousarray(X.T)
+        Br = np.ascontiguousarray(np.asarray(B, dtype=np.int16).T)
+        dim2C = _cover_map(od, d, m)
+        if solver == "host":
+            K = np.empty((m * h, d), dtype=np.float32)
+            cover = np.ascontiguousarray(dim2C.T)
+            _lib.check(_lib.load().lsq_update_codebooks_struct(Xr.ctypes.data, Br.ctypes.data, cover.ctypes.data, d, n, m, h, int(nthreads), K.ctypes.data))
+        else:
+            K, _ = engine.update_codebooks_struct(Xr, Br, dim2C, m, h=h)
+        return [np.ascontiguousarray(K[i * h:(i + 1) * h].T) for i in range(m)]
+    from scipy.sparse import csr_matrix
+    from scipy.sparse.linalg import lsqr
     B = np.asarray(B, dtype=np.int64)
-    m = B.shape[0]
-    od = get_cbdims_chain(d, m)
+    covers = _cover_map(od, d, m)
     cols = (B - 1 + (np.arange(m) * h)[:, None]).T.reshape(-1)                     # sparsify_codes, src/utils.jl:50-69
     S = csr_matrix((np.ones(n * m, dtype=np.float32), (np.repeat(np.arange(n), m), cols)), shape=(n, m * h)).tocsc()
     K = np.zeros((d, m * h), dtype=np.float32)
     tol = float(np.sqrt(np.finfo(np.float32).eps))
     cache = {}
     for t in range(d):
-        cbs = tuple(i for i in range(m) if od[i].start <= t < od[i].stop)
+        cbs = tuple(int(i) for i in np.nonzero(covers[t])[0])
+        if not cbs:
+            continue
         if cbs not in cache:
             idx = np.concatenate([np.arange(i * h, (i + 1) * h) for i in cbs])
             cache[cbs] = (idx, S[:, idx])
         idx, St = cache[cbs]
         K[t, idx] = lsqr(St, X[t].astype(np.float64), atol=tol, btol=tol, conlim=1e8)[0].astype(np.float32)
     return [np.ascontiguousarray(K[:, i * h:(i + 1) * h]) for i in range(m)]
+
+
+def update_codebooks_chain(X, B, h, V=False, *, nthreads=0, engine=None, solver=None):
+    """update_codebooks_generic with the chain's structure (get_cbdims_chain).  src/codebook_update.jl:160-169"""
+    return update_codebooks_generic(X, B, h, get_cbdims_chain, V, nthreads=nthreads, engine=engine, solver=solver)
 
 
 def encoding_viterbi(X, C, V=False, *, engine=None):
@@ -291,14 +331,18 @@ def _qerror_full(X, B, C):
     return float(((X - rec) ** 2).sum()) / X.shape[1]
 
 
-def train_chainq(X, m, h, R, B, C, niter, V=False, *, engine=None):
+def train_chainq(X, m, h, R, B, C, niter, V=False, *, engine=None, device_update=False):
     """train_chainq(X, m, h, R, B, C, niter) -> C, B, R, obj.  src/chainq/chainq.jl:10-58
-    B: initial codes (e.g. OPQ's); the incoming C is only a placeholder, as in the reference (re-fitted at :27)."""
+    B: initial codes (e.g. OPQ's); the incoming C is only a placeholder, as in the reference (re-fitted at :27).
+    device_update: the structured LSQR codebook update on the device too (needs `engine`), as train_lsq's keyword."""
     X = _f32(X)
     R = _f32(R)
     B = np.asarray(B, dtype=np.int16)
     RX = R.T @ X
-    C = update_codebooks_chain(RX, B, h, V)                      # :27
+    if device_update and engine is None:
+        raise ValueError("device_update=True needs engine=<Engine>")
+    upd = {"engine": engine} if device_update else {}           # default: update_codebooks_chain(X, B, h, V), the scipy path
+    C = update_codebooks_chain(RX, B, h, V, **upd)                     # :27
     B = encoding_viterbi(RX, C, V, engine=engine)                # :31
     obj = np.zeros(niter + 1, dtype=np.float32)
     for it in range(niter + 1):
@@ -310,6 +354,42 @@ def train_chainq(X, m, h, R, B, C, niter, V=False, *, engine=None):
             CB += C[i][:, B[i].astype(np.int64) - 1]
         R = _procrustes(X, CB)                                   # :44-45
         RX = R.T @ X
-        C = update_codebooks_chain(RX, B, h, V)
+        C = update_codebooks_chain(RX, B, h, V, **upd)
         B = encoding_viterbi(RX, C, V, engine=engine)
     return C, B, R, obj
+
+
+def train_chainq_dev(dX, m, h, R, dB, niter, *, engine):
+    """src/chainq/chainq.jl:10-58 with X, the codes and the codebooks resident in HBM: the structured LSQR codebook update (lsq_update_codebooks_struct_dev)
+    and the Viterbi encode (lsq_encode_viterbi_dev) on device tensors.  dX (n, d) f32, dB (n, m) uint8 0-BASED: CUDA/HIP torch tensors; R (d, d) host.
+    -> (dK (m*h, d) tensor: the codebooks of the rotated space, zero outside the chain's dimensions; dB (n, m) uint8 tensor; R (d, d) f32 host; obj (niter + 1,) f32).
+    torch is the glue around the two steps, on the device: the rotation R'X, the reconstruction, the objective and the d x d product X CB' (float64).  Per
+    iteration only that d x d matrix, R and the scalar objective cross to the host, where the Procrustes SVD runs in float64 as in train_chainq."""
+    import torch
+    n, d = dX.shape
+    dev = dX.device
+    dcover = torch.from_numpy(_cover_map(get_cbdims_chain(d, m), d, m)).to(dev)
+    offs = (torch.arange(m, device=dev, dtype=torch.int64) * h)[None, :]
+    dX64 = None
+
+    def rotate(Rm):
+        return (dX @ torch.as_tensor(np.ascontiguousarray(Rm, dtype=np.float32), device=dev)).contiguous()       # rows of (R'X)'
+
+    R = _f32(R)
+    dXr = rotate(R)
+    dB = dB.contiguous()
+    dK, _ = engine.update_codebooks_struct_dev(dXr, dB, dcover, m, h=h)          # :27
+    dB = engine.encode_viterbi_dev(dXr, dK, m, h=h)                               # :31
+    obj = np.zeros(niter + 1, dtype=np.float32)
+    for it in range(niter + 1):
+        dCB = dK[dB.to(torch.int64) + offs].sum(dim=1)                            # (n, d): the reconstructions
+        obj[it] = float(((dXr - dCB).double() ** 2).sum().item()) / n
+        if dX64 is None:
+            dX64 = dX.double()
+        M = (dX64.T @ dCB.double()).cpu().numpy()                                 # X CB' (d x d), float64
+        U, _, Vt = np.linalg.svd(M, full_matrices=False)                          # :44-45
+        R = (U @ Vt).astype(np.float32)
+        dXr = rotate(R)
+        dK, _ = engine.update_codebooks_struct_dev(dXr, dB, dcover, m, h=h, out=dK)
+        dB = engine.encode_viterbi_dev(dXr, dK, m, h=h)
+    return dK, dB, R, obj

@@ -60,7 +60,8 @@ def main():
     m, h, niter, knn = (7, 256, 10, 1000) if name == "SIFT1M" else (4, 256, 3, 50)     # demo_lsq_gpu.jl:13-20
     C, B, R, err = lsq.train_opq(x_train, m, h, niter, "natural", True)
     print("Error after OPQ is %e" % err[-1])
-    C, B, R, err = lsq.train_chainq(x_train, m, h, R, B, C, niter)
+    with lsq.Engine(0) as eng:                                              # ChainQ with its structured codebook update on the device as well
+        C, B, R, err = lsq.train_chainq(x_train, m, h, R, B, C, niter, engine=eng, device_update=True)
     print("Error after ChainQ is %e" % err[-1])
     ilsiter, icmiter, randord, npert = 8, 4, True, 4
     C, B, cbnorms, B_norms, obj = lsq.train_lsq(x_train, m, h, R, B, C, niter, ilsiter, icmiter, randord, min(npert, m), True)
