@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 1000
+#define LSQ_VERSION 1100
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -410,6 +410,39 @@ LSQ_API int lsq_encode_viterbi_dev(lsq_ctx *ctx, const float *d_X, const float *
  * Host form: B m x n Int16 1-based; _dev: codes [n][m] uint8 0-based.  h must be 256. */
 LSQ_API int lsq_assign_codewords(lsq_ctx *ctx, const float *X, const float *K, int d, int64_t n, int m, int h, int16_t *B, float *minval);
 LSQ_API int lsq_assign_codewords_dev(lsq_ctx *ctx, const float *d_X, const float *d_K, int d, int64_t n, int m, int h, uint8_t *d_B, float *d_minval);
+
+/* ---- PQ / OPQ training resident on the device: cluster means and k-means++ seeding (csrc/lsq_kmeans.hip; since v1100) -------------------------
+ * Both steps run for all m sub-spaces of a vector set in one call.  The sub-space structure is the cover map dim2C of the structured update above (d x m
+ * in Julia's order, one byte per entry, 0 or 1), here HOST memory in BOTH forms: it is checked before anything is launched, every codebook must cover
+ * at least one dimension (else LSQ_EINVAL), and a _dev call enqueues its work on the context's stream without waiting for the device.  PQ / OPQ: codebook j
+ * covers splitarray(1:d, m)[j]; plain k-means is m = 1 with every dimension covered.  K is d x (m*h) = hcat of the codebooks padded to d rows -- what
+ * lsq_assign_codewords takes -- and exactly +0.0 outside the cover.  h must be 256, m <= 16.  Host forms: X d x n, B m x n Int16 1-based; _dev: device
+ * pointers, codes [n][m] uint8 0-BASED.  No atomics anywhere: the same bits on every call.
+ *
+ * update_centers!(X, assignments, centers, counts)      src/opq/kmeans.jl:77-123
+ * For codebook j, code c and covered dimension t: the values X[t, i] of the vectors i holding code c, added in ascending i with plain Float32 adds from
+ * +0.0, divided by their count in double and rounded to Float32 (numpy's np.add.at followed by `f32 /= int64`: the bits of this package's host trainers).
+ * counts (optional, m*h Int32) receives the cluster sizes.  An empty cluster takes its column of K_prev (OPQ keeps the old codeword) or, with K_prev = NULL,
+ * zero, as the reference leaves it (:86,112); its count is 0 either way.  K_prev may be K_out.  n = 0: every cluster is empty.  n m < 2^31. */
+LSQ_API int lsq_update_centers(lsq_ctx *ctx, const float *X, const int16_t *B, const uint8_t *dim2C, const float *K_prev, int d, int64_t n, int m, int h,
+                               float *K_out, int *counts);
+LSQ_API int lsq_update_centers_dev(lsq_ctx *ctx, const float *d_X, const uint8_t *d_codes, const uint8_t *dim2C, const float *d_K_prev, int d, int64_t n,
+                                   int m, int h, float *d_K_out, int *d_counts);
+/* k-means++ seeding: Clustering.kmeans(X, h, init=:kmpp)      src/pq/PQ.jl:60 (Clustering.jl is neither vendored nor pinned: PARITY UNPINNED)
+ * D^2 sampling with the caller's random numbers: u is HOST memory, m x h doubles in [0, 1) (row j for sub-space j; anything else: LSQ_EINVAL); the library
+ * holds no generator and the result is a function of (X, u).  Per sub-space j:
+ *     step 0       row min(n - 1, floor(u[j][0] n));
+ *     step k >= 1  d2[i] = min(d2[i], SUM_t (x_it - c_t)^2) -- Float32, direct form over the covered dimensions ascending, no FMA -- with c the row chosen
+ *                  at step k - 1; tot = SUM_i d2[i] in double; tot > 0: the first row whose double prefix sum exceeds u[j][k] tot (a row at distance 0 is
+ *                  never chosen); tot = 0 (fewer distinct rows than steps): row min(n - 1, floor(u[j][k] n)).
+ * The double sums run in a fixed order that depends on n alone (block partial sums of fixed row sets combined in a fixed order: csrc/lsq_kmeans.hip), so
+ * two calls choose the same rows; another summation order can choose a neighbouring row where u tot falls within rounding (2 n 2^-53 tot) of a boundary.
+ * K_out: the chosen rows restricted to the cover.  idx_out (optional, m x h Int64, row-major [m][h]): their 0-based indices.  d2_out (optional, [n][m]
+ * Float32, vector-major): the squared distance of every vector to the nearest of ALL h chosen rows.  n = 0: K_out = 0, indices -1, d2 untouched. */
+LSQ_API int lsq_kmeanspp_seed(lsq_ctx *ctx, const float *X, const uint8_t *dim2C, const double *u, int d, int64_t n, int m, int h, float *K_out,
+                              int64_t *idx_out, float *d2_out);
+LSQ_API int lsq_kmeanspp_seed_dev(lsq_ctx *ctx, const float *d_X, const uint8_t *dim2C, const double *u, int d, int64_t n, int m, int h, float *d_K_out,
+                                  int64_t *d_idx_out, float *d_d2_out);
 
 /* ---- (4) device-side generators used by the benchmark harness -----------------------------
  * X[i][t] = float(uniform integer 0..255) (SIFT-like);  codes uniform 0..h-1 (randinit);

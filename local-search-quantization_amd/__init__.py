@@ -19,7 +19,7 @@ from .reference_api import (  # noqa: F401
 )
 from .initializers import (  # noqa: F401
     train_pq, quantize_pq, train_opq, quantize_opq, train_chainq, train_chainq_dev, encoding_viterbi, update_codebooks_chain, update_codebooks_generic,
-    get_cbdims_chain,
+    get_cbdims_chain, kmeans_dev, train_pq_dev, train_opq_dev, codebooks_from_padded,
 )
 from . import distributed  # noqa: F401
 
@@ -29,4 +29,5 @@ __all__ = [
     "quantize_norms", "reconstruct", "update_codebooks", "train_lsq", "train_lsq_dev", "train_pq", "quantize_pq", "train_opq", "quantize_opq",
     "train_chainq", "train_chainq_dev", "encoding_viterbi", "update_codebooks_chain", "update_codebooks_generic", "get_cbdims_chain", "fvecs_read", "ivecs_read", "bvecs_read",
     "update_codebooks_spgl1", "update_codebooks_spgl1_threshold", "train_lsq_sparse", "knn_exact",
+    "kmeans_dev", "train_pq_dev", "train_opq_dev", "codebooks_from_padded",
 ]

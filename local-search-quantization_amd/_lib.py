@@ -116,6 +116,10 @@ SIGNATURES = {
     "lsq_encode_viterbi_dev": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp]),
     "lsq_assign_codewords": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp]),
     "lsq_assign_codewords_dev": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp]),
+    "lsq_update_centers": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp]),
+    "lsq_update_centers_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp]),
+    "lsq_kmeanspp_seed": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp]),
+    "lsq_kmeanspp_seed_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "lsq_synth_data_u8_dev": (_i, [_vp, _u64, _u64, _i64, _i, _vp]),
     "lsq_randinit_dev": (_i, [_vp, _u64, _u64, _i64, _i, _i, _vp]),
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),

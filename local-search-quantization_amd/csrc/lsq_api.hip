@@ -96,6 +96,7 @@ struct lsq_ctx {
     int64_t call_I = 0, call_q16_chunks = 0;
     float *q_colshift = nullptr;                       // inside qscratch: the per-candidate shift of the unary levels (double-centred tables)
     lsq_lsqr_state *lsqr = nullptr;                    // device LSQR (lsq_lsqr.hip): work buffers, created on first use
+    lsq_kmeans_state *kmeans = nullptr;                // cluster means and k-means++ seeding (lsq_kmeans.hip): work buffers, created on first use
     lsq_spgl1_state *spgl1 = nullptr;                  // device SPGL1 (lsq_spgl1.hip): work buffers, created on first use
     lsq_adc_state *adc = nullptr;                      // device ADC scan (lsq_adc.hip): buffers, created on first use
     lsq_linscan_stats adc_stats{};
@@ -235,6 +236,7 @@ extern "C" int lsq_destroy(lsq_ctx *c) {
     lsq_adc_free(c->adc);
     lsq_lsqr_free(c->lsqr);
     lsq_spgl1_free(c->spgl1);
+    lsq_kmeans_free(c->kmeans);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->copy_done) (void)hipEventDestroy(c->copy_done);
@@ -1561,6 +1563,95 @@ extern "C" int lsq_assign_codewords_dev(lsq_ctx *c, const float *dX, const float
 }
 extern "C" int lsq_assign_codewords(lsq_ctx *c, const float *X, const float *K, int d, int64_t n, int m, int h, int16_t *B, float *minval) {
     return init_codes_host(c, "lsq_assign_codewords", X, K, d, n, m, h, B, minval, false);
+}
+
+// ---- cluster means and k-means++ seeding (lsq_kmeans.hip) -----------------------------------------------------------------------------------------
+// the cover map of these entries is HOST memory in both forms: its d m bytes are checked before anything is launched, so a _dev call never waits for the device
+static int kmeans_args(const char *fn, lsq_ctx *c, const uint8_t *dim2C, int d, int64_t n, int m, int h) {
+    LSQ_TRY(use_device(c));
+    LSQ_TRY(check_shape(fn, d, n, m, h));
+    if (!dim2C) { lsq_set_error("%s: null dim2C (plain k-means is m = 1 with every dimension covered)", fn); return LSQ_EINVAL; }
+    LSQ_TRY(check_cover(fn, dim2C, d, m));
+    for (int j = 0; j < m; ++j) {
+        int cnt = 0;
+        for (int t = 0; t < d; ++t) cnt += dim2C[(size_t)j * d + t];
+        if (cnt == 0) { lsq_set_error("%s: codebook %d covers no dimension", fn, j); return LSQ_EINVAL; }
+    }
+    return LSQ_OK;
+}
+
+extern "C" int lsq_update_centers_dev(lsq_ctx *c, const float *d_X, const uint8_t *d_codes, const uint8_t *dim2C, const float *d_K_prev, int d, int64_t n,
+                                      int m, int h, float *d_K_out, int *d_counts) {
+    LSQ_TRY(kmeans_args("lsq_update_centers_dev", c, dim2C, d, n, m, h));
+    if (!d_K_out || (n > 0 && (!d_X || !d_codes))) { lsq_set_error("lsq_update_centers_dev: null pointer"); return LSQ_EINVAL; }
+    if (n * (int64_t)m >= (int64_t)1 << 31) { lsq_set_error("lsq_update_centers_dev: n * m = %lld exceeds 2^31 - 1", (long long)(n * m)); return LSQ_EINVAL; }
+    return lsq_kmeans_update_centers(c->stream, &c->kmeans, d_X, d_codes, dim2C, d_K_prev, d, n, m, d_K_out, d_counts);
+}
+
+extern "C" int lsq_update_centers(lsq_ctx *c, const float *X, const int16_t *B, const uint8_t *dim2C, const float *K_prev, int d, int64_t n, int m, int h,
+                                  float *K_out, int *counts) {
+    LSQ_TRY(kmeans_args("lsq_update_centers", c, dim2C, d, n, m, h));
+    if (!K_out || (n > 0 && (!X || !B))) { lsq_set_error("lsq_update_centers: null pointer"); return LSQ_EINVAL; }
+    if (n * (int64_t)m >= (int64_t)1 << 31) { lsq_set_error("lsq_update_centers: n * m = %lld exceeds 2^31 - 1", (long long)(n * m)); return LSQ_EINVAL; }
+    const AsyncOff sync_here(c);
+    const size_t kbytes = sizeof(float) * (size_t)m * LSQ_H * d;
+    LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)std::max<int64_t>(n, 1) * d));
+    LSQ_TRY(c->sK.ensure(kbytes));
+    LSQ_TRY(c->sF32.ensure(sizeof(int) * (size_t)m * LSQ_H));
+    c->tables_valid = false;
+    if (n > 0) LSQ_HIP(hipMemcpyAsync(c->sX.p, X, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
+    if (K_prev) LSQ_HIP(hipMemcpyAsync(c->sK.p, K_prev, kbytes, hipMemcpyHostToDevice, c->stream));      // in place: an empty cluster keeps the entry it finds
+    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));                          // records of stride 8 / 16 -> tight [n][m] below
+    LSQ_TRY(c->sTight.ensure((size_t)std::max<int64_t>(n, 1) * m));
+    if (n > 0) LSQ_TRY(lsq_launch_codes_compact(c->stream, c->recCur.as<uint8_t>(), n, m, c->sTight.as<uint8_t>()));
+    LSQ_TRY(lsq_kmeans_update_centers(c->stream, &c->kmeans, c->sX.as<float>(), c->sTight.as<uint8_t>(), dim2C, K_prev ? c->sK.as<float>() : nullptr, d, n, m,
+                                      c->sK.as<float>(), c->sF32.as<int>()));
+    LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, kbytes, hipMemcpyDeviceToHost, c->stream));
+    if (counts) LSQ_HIP(hipMemcpyAsync(counts, c->sF32.p, sizeof(int) * (size_t)m * LSQ_H, hipMemcpyDeviceToHost, c->stream));
+    LSQ_HIP(hipStreamSynchronize(c->stream));
+    return LSQ_OK;
+}
+
+static int kmeanspp_u(const char *fn, const double *u, int m) {
+    if (!u) { lsq_set_error("%s: null u", fn); return LSQ_EINVAL; }
+    for (int e = 0; e < m * LSQ_H; ++e)
+        if (!(u[e] >= 0.0 && u[e] < 1.0)) { lsq_set_error("%s: u[%d] = %g lies outside [0, 1)", fn, e, u[e]); return LSQ_EINVAL; }
+    return LSQ_OK;
+}
+
+extern "C" int lsq_kmeanspp_seed_dev(lsq_ctx *c, const float *d_X, const uint8_t *dim2C, const double *u, int d, int64_t n, int m, int h, float *d_K_out,
+                                     int64_t *d_idx_out, float *d_d2_out) {
+    LSQ_TRY(kmeans_args("lsq_kmeanspp_seed_dev", c, dim2C, d, n, m, h));
+    LSQ_TRY(kmeanspp_u("lsq_kmeanspp_seed_dev", u, m));
+    if (!d_K_out || (n > 0 && !d_X)) { lsq_set_error("lsq_kmeanspp_seed_dev: null pointer"); return LSQ_EINVAL; }
+    if (n == 0) {                                                             // no row to choose: zero codebooks, indices -1, d2 empty
+        LSQ_HIP(hipMemsetAsync(d_K_out, 0, sizeof(float) * (size_t)m * LSQ_H * d, c->stream));
+        if (d_idx_out) LSQ_TRY(lsq_kmeans_fill_i64(c->stream, d_idx_out, (int64_t)m * LSQ_H, -1));
+        return LSQ_OK;
+    }
+    return lsq_kmeans_seed(c->stream, &c->kmeans, d_X, dim2C, u, d, n, m, d_K_out, d_idx_out, d_d2_out);
+}
+
+extern "C" int lsq_kmeanspp_seed(lsq_ctx *c, const float *X, const uint8_t *dim2C, const double *u, int d, int64_t n, int m, int h, float *K_out,
+                                 int64_t *idx_out, float *d2_out) {
+    LSQ_TRY(kmeans_args("lsq_kmeanspp_seed", c, dim2C, d, n, m, h));
+    LSQ_TRY(kmeanspp_u("lsq_kmeanspp_seed", u, m));
+    if (!K_out || (n > 0 && !X)) { lsq_set_error("lsq_kmeanspp_seed: null pointer"); return LSQ_EINVAL; }
+    const AsyncOff sync_here(c);
+    const size_t kbytes = sizeof(float) * (size_t)m * LSQ_H * d, ibytes = sizeof(int64_t) * (size_t)m * LSQ_H, dbytes = sizeof(float) * (size_t)n * m;
+    LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)std::max<int64_t>(n, 1) * d));
+    LSQ_TRY(c->sK.ensure(kbytes));
+    LSQ_TRY(c->sF32.ensure(ibytes + dbytes + 16));
+    c->tables_valid = false;
+    int64_t *didx = c->sF32.as<int64_t>();
+    float *dd2 = reinterpret_cast<float *>(c->sF32.as<char>() + ibytes);
+    if (n > 0) LSQ_HIP(hipMemcpyAsync(c->sX.p, X, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
+    LSQ_TRY(lsq_kmeanspp_seed_dev(c, c->sX.as<float>(), dim2C, u, d, n, m, h, c->sK.as<float>(), didx, d2_out && n > 0 ? dd2 : nullptr));
+    LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, kbytes, hipMemcpyDeviceToHost, c->stream));
+    if (idx_out) LSQ_HIP(hipMemcpyAsync(idx_out, didx, ibytes, hipMemcpyDeviceToHost, c->stream));
+    if (d2_out && n > 0) LSQ_HIP(hipMemcpyAsync(d2_out, dd2, dbytes, hipMemcpyDeviceToHost, c->stream));
+    LSQ_HIP(hipStreamSynchronize(c->stream));
+    return LSQ_OK;
 }
 
 // ---- device-side generators ---------------------------------------------------------------------

@@ -273,6 +273,17 @@ int lsq_lsqr_update_codebooks(hipStream_t s, lsq_lsqr_state **st, const float *d
 // the rows of a code matrix sorted by (codebook j, code) once per call: keys and segment starts live in `buf` (shared by lsq_lsqr.hip and lsq_spgl1.hip)
 int lsq_sort_rows_by_code(hipStream_t s, DevBuf &buf, const uint8_t *dcodes, int64_t n, int m, const uint64_t **sorted, const int64_t **seg);
 
+// ---- cluster means and k-means++ seeding on the device (lsq_kmeans.hip) -------------------------------------------------------------------------------
+struct lsq_kmeans_state;
+void lsq_kmeans_free(lsq_kmeans_state *st);
+// cover: HOST bytes [m][d] (0 / 1, no empty codebook); dKprev optional (may be dK); dcounts optional [m*256] int32
+int lsq_kmeans_update_centers(hipStream_t s, lsq_kmeans_state **st, const float *dX, const uint8_t *dcodes, const uint8_t *cover, const float *dKprev, int d,
+                              int64_t n, int m, float *dK, int *dcounts);
+// u: HOST [m][256] doubles in [0, 1); didx optional [m][256] int64; dd2 optional [n][m] f32; n >= 1
+int lsq_kmeans_seed(hipStream_t s, lsq_kmeans_state **st, const float *dX, const uint8_t *cover, const double *u, int d, int64_t n, int m, float *dK,
+                    int64_t *didx, float *dd2);
+int lsq_kmeans_fill_i64(hipStream_t s, int64_t *p, int64_t count, int64_t v);
+
 // ---- SPGL1 (LASSO) codebook update on the device (lsq_spgl1.hip) ---------------------------------------------------------------------------------
 struct lsq_spgl1_state;
 void lsq_spgl1_free(lsq_spgl1_state *st);

@@ -433,6 +433,90 @@ class Engine:
             self._check(self._L.lsq_assign_codewords_dev(self._h, dX.data_ptr(), dK.data_ptr(), d, n, m, h, dB.data_ptr(), dmin.data_ptr() if want_min else None))
         return (dB, dmin) if want_min else dB
 
+    # -- PQ / OPQ training resident on the device: cluster means and k-means++ seeding (csrc/lsq_kmeans.hip) ----------------
+    @staticmethod
+    def _host_cover(dim2C, d, m):
+        """dim2C (d, m) 0/1 as a host array or a tensor (copied to the host: the library checks the map before it launches anything) -> (m, d) bytes"""
+        if hasattr(dim2C, "detach"):
+            dim2C = dim2C.detach().cpu().numpy()
+        return cover_bytes(dim2C, d, m)
+
+    def update_centers(self, X, B, dim2C, m, K_prev=None, h=H):
+        """X (n,d) f32, B (n,m) int16 1-based, dim2C (d,m) 0/1, K_prev (m*h,d) or None: host arrays -> (K (m*h,d): per codebook and code the mean of its
+        rows over the covered dimensions, rows added in ascending order in f32; an empty cluster keeps its row of K_prev (None: zero); exact zeros outside
+        the cover.  counts (m*h,) int32)   [lsq_update_centers]"""
+        X, B = _np(X, np.float32), _np(B, np.int16)
+        n, d = X.shape
+        if B.shape != (n, m):
+            raise ValueError("shape mismatch: X %s B %s m=%d" % (X.shape, B.shape, m))
+        cover = self._host_cover(dim2C, d, m)
+        Kp = None if K_prev is None else _np(K_prev, np.float32)
+        if Kp is not None and Kp.shape != (m * h, d):
+            raise ValueError("K_prev must be (m*h, d) = (%d, %d), got %s" % (m * h, d, Kp.shape))
+        K = np.empty((m * h, d), dtype=np.float32)
+        counts = np.zeros(m * h, dtype=np.int32)
+        self._check(self._L.lsq_update_centers(self._h, X.ctypes.data, B.ctypes.data, cover.ctypes.data, None if Kp is None else Kp.ctypes.data, d, n, m, h,
+                                               K.ctypes.data, counts.ctypes.data))
+        return K, counts
+
+    def update_centers_dev(self, dX, dcodes, dim2C, m, K_prev=None, h=H, out=None, counts=None):
+        """device tensors: X (n,d) f32, codes (n,m) uint8 0-based, K_prev (m*h,d) f32 or None (it may be `out`); dim2C (d,m) 0/1 on the HOST
+        -> (K (m*h,d) f32 tensor (`out` when given: it may hold anything), counts (m*h,) int32 tensor).  Nothing waits for the device   [lsq_update_centers_dev]"""
+        import torch
+        assert dX.is_cuda and dcodes.is_cuda and dX.dtype == torch.float32 and dcodes.dtype == torch.uint8 and dX.is_contiguous() and dcodes.is_contiguous()
+        n, d = dX.shape
+        if dcodes.shape != (n, m):
+            raise ValueError("shape mismatch")
+        cover = self._host_cover(dim2C, d, m)
+        dK = out if out is not None else torch.empty((m * h, d), dtype=torch.float32, device=dX.device)
+        for name, t in (("out", dK), ("K_prev", K_prev)):
+            if t is not None and (tuple(t.shape) != (m * h, d) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous (m*h, d) = (%d, %d) f32 device tensor" % (name, m * h, d))
+        dcnt = counts if counts is not None else torch.empty(m * h, dtype=torch.int32, device=dX.device)
+        if tuple(dcnt.shape) != (m * h,) or dcnt.dtype != torch.int32 or not dcnt.is_cuda or not dcnt.is_contiguous():
+            raise ValueError("counts must be a contiguous (m*h,) int32 device tensor")
+        with self._on_torch_stream():
+            self._check(self._L.lsq_update_centers_dev(self._h, dX.data_ptr(), dcodes.data_ptr(), cover.ctypes.data, None if K_prev is None else K_prev.data_ptr(),
+                                                       d, n, m, h, dK.data_ptr(), dcnt.data_ptr()))
+        return dK, dcnt
+
+    @staticmethod
+    def _seed_u(u, m, h):
+        u = _np(u, np.float64)
+        if u.shape != (m, h):
+            raise ValueError("u must be (m, h) = (%d, %d) doubles in [0, 1), got %s" % (m, h, u.shape))
+        return u
+
+    def kmeanspp_seed(self, X, dim2C, u, m, h=H):
+        """k-means++ (D^2) seeding of all m sub-spaces.  X (n,d) f32, dim2C (d,m) 0/1, u (m,h) doubles in [0,1) drawn by the caller: host arrays
+        -> (K (m*h,d): the chosen rows restricted to the cover, idx (m,h) int64 0-based row indices, d2 (n,m) f32 squared distance to the nearest chosen row)
+        [lsq_kmeanspp_seed]"""
+        X = _np(X, np.float32)
+        n, d = X.shape
+        cover, u = self._host_cover(dim2C, d, m), self._seed_u(u, m, h)
+        K = np.empty((m * h, d), dtype=np.float32)
+        idx = np.empty((m, h), dtype=np.int64)
+        d2 = np.empty((n, m), dtype=np.float32)
+        self._check(self._L.lsq_kmeanspp_seed(self._h, X.ctypes.data, cover.ctypes.data, u.ctypes.data, d, n, m, h, K.ctypes.data, idx.ctypes.data, d2.ctypes.data))
+        return K, idx, d2
+
+    def kmeanspp_seed_dev(self, dX, dim2C, u, m, h=H, want_idx=True, want_d2=False, out=None):
+        """The same on a device tensor X (n,d) f32; dim2C and u on the HOST -> (K (m*h,d) f32 tensor, idx (m,h) int64 tensor or None, d2 (n,m) f32 tensor or
+        None).  2 h - 1 launches in stream order, nothing waits for the device   [lsq_kmeanspp_seed_dev]"""
+        import torch
+        assert dX.is_cuda and dX.dtype == torch.float32 and dX.is_contiguous()
+        n, d = dX.shape
+        cover, u = self._host_cover(dim2C, d, m), self._seed_u(u, m, h)
+        dK = out if out is not None else torch.empty((m * h, d), dtype=torch.float32, device=dX.device)
+        if tuple(dK.shape) != (m * h, d) or dK.dtype != torch.float32 or not dK.is_cuda or not dK.is_contiguous():
+            raise ValueError("out must be a contiguous (m*h, d) = (%d, %d) f32 device tensor" % (m * h, d))
+        didx = torch.empty((m, h), dtype=torch.int64, device=dX.device) if want_idx else None
+        dd2 = torch.empty((n, m), dtype=torch.float32, device=dX.device) if want_d2 else None
+        with self._on_torch_stream():
+            self._check(self._L.lsq_kmeanspp_seed_dev(self._h, dX.data_ptr(), cover.ctypes.data, u.ctypes.data, d, n, m, h, dK.data_ptr(),
+                                                      didx.data_ptr() if want_idx else None, dd2.data_ptr() if want_d2 and n > 0 else None))
+        return dK, didx, dd2
+
     def linscan_stats(self):
         t = _lib.LinscanStats()
         self._check(self._L.lsq_get_linscan_stats(self._h, C.byref(t)))

@@ -10,8 +10,10 @@ Mirrors of the reference's trainers with the reference's names, argument order a
 The two data-parallel steps run ON THE DEVICE through the C-ABI (csrc/lsq_init.hip; round 6): the nearest-codeword assignment of PQ / OPQ and of
 their k-means (`lsq_assign_codewords`: every sub-space of a vector set in one call, codebooks padded to d rows) and ChainQ's Viterbi encoder
 (`lsq_encode_viterbi`).  Like the rest of the engine they need h == 256 and a gfx950 device -- there is no CPU fallback; the numpy restatement of
-these steps lives in oracle/init_oracle.py as the checker (tests only).  What stays on the host is the glue around them: k-means++ seeding, cluster
-means, the Procrustes SVD, and the scalar k-means of the norm codebook (an O(n log h) sorted search).  The chain's structured LSQR codebook update runs
+these steps lives in oracle/init_oracle.py as the checker (tests only).  What stays on the host in train_pq / train_opq is the glue around them: k-means++
+seeding, cluster means, the Procrustes SVD, and the scalar k-means of the norm codebook (an O(n log h) sorted search).  kmeans_dev / train_pq_dev /
+train_opq_dev are the resident forms: seeding and cluster means on the device too (lsq_kmeanspp_seed_dev, lsq_update_centers_dev: csrc/lsq_kmeans.hip), X,
+codes and codebooks in HBM throughout; only the d x d Procrustes SVD stays on the host.  The chain's structured LSQR codebook update runs
 by default in scipy (float64, a Python loop over the dimensions: the checker's own path); `solver="host"` selects the C-ABI host solver
 (lsq_update_codebooks_struct) and `engine=<Engine>` the device solver (lsq_update_codebooks_struct_gpu / _dev), which train_chainq_dev uses with X,
 codes and codebooks resident in HBM.
@@ -24,7 +26,8 @@ import numpy as np
 from .engine import splitarray
 
 __all__ = ["train_pq", "quantize_pq", "qerror_pq", "train_opq", "quantize_opq", "get_cbdims_chain", "update_codebooks_generic",
-           "update_codebooks_chain", "encoding_viterbi", "train_chainq", "train_chainq_dev", "kmeans"]
+           "update_codebooks_chain", "encoding_viterbi", "train_chainq", "train_chainq_dev", "kmeans", "kmeans_dev", "train_pq_dev", "train_opq_dev",
+           "codebooks_from_padded"]
 
 
 def _f32(a):
@@ -129,20 +132,25 @@ def _centers(X, a, h, rng, old=None):
     return C
 
 
-def kmeans(X, h, niter=25, seed=0, engine=None):
+def kmeans(X, h, niter=25, seed=0, engine=None, init=None):
     """Lloyd k-means with k-means++ seeding on the columns of X (r x n) -> centers (r x h), assignments (n,) 0-based, total cost.
-    Stands in for Clustering.jl's `kmeans(X, h, init=:kmpp)` (src/pq/PQ.jl:60)."""
+    Stands in for Clustering.jl's `kmeans(X, h, init=:kmpp)` (src/pq/PQ.jl:60).  init: explicit initial centers (r x h); the seeding is skipped."""
     X = _f32(X)
     r, n = X.shape
     rng = np.random.default_rng(seed)
-    C = np.empty((r, h), dtype=np.float32)
-    C[:, 0] = X[:, rng.integers(n)]
-    d2 = ((X - C[:, :1]) ** 2).sum(axis=0)
-    for k in range(1, h):
-        tot = float(d2.sum())
-        idx = rng.integers(n) if tot <= 0 else int(np.searchsorted(np.cumsum(d2), rng.random() * tot))
-        C[:, k] = X[:, min(idx, n - 1)]
-        d2 = np.minimum(d2, ((X - C[:, k:k + 1]) ** 2).sum(axis=0))
+    if init is not None:
+        C = _f32(init).copy()
+        if C.shape != (r, h):
+            raise ValueError("init must be (r, h) = (%d, %d), got %s" % (r, h, C.shape))
+    else:
+        C = np.empty((r, h), dtype=np.float32)
+        C[:, 0] = X[:, rng.integers(n)]
+        d2 = ((X - C[:, :1]) ** 2).sum(axis=0)
+        for k in range(1, h):
+            tot = float(d2.sum())
+            idx = rng.integers(n) if tot <= 0 else int(np.searchsorted(np.cumsum(d2), rng.random() * tot))
+            C[:, k] = X[:, min(idx, n - 1)]
+            d2 = np.minimum(d2, ((X - C[:, k:k + 1]) ** 2).sum(axis=0))
     a, cost = _assign(C, X, engine)
     for _ in range(niter):
         C = _centers(X, a, h, rng)
@@ -173,13 +181,13 @@ def qerror_pq(X, B, C):
     return err / X.shape[1]
 
 
-def train_pq(X, m, h, V=False, *, seed=0, engine=None):
-    """train_pq(X, m, h) -> C, B, error.  src/pq/PQ.jl:44-76 (k-means per subspace)."""
+def train_pq(X, m, h, V=False, *, seed=0, engine=None, init=None):
+    """train_pq(X, m, h) -> C, B, error.  src/pq/PQ.jl:44-76 (k-means per subspace).  init: m explicit initial codebooks (subdim x h); no seeding then."""
     X = _f32(X)
     sd = _subdims(X.shape[0], m)
     C, B = [], []
     for i in range(m):
-        c, a, cost = kmeans(X[sd[i]], h, seed=seed + i, engine=engine)
+        c, a, cost = kmeans(X[sd[i]], h, seed=seed + i, engine=engine, init=None if init is None else init[i])
         C.append(c)
         B.append(a + 1)
         if V:
@@ -392,4 +400,155 @@ def train_chainq_dev(dX, m, h, R, dB, niter, *, engine):
         dXr = rotate(R)
         dK, _ = engine.update_codebooks_struct_dev(dXr, dB, dcover, m, h=h, out=dK)
         dB = engine.encode_viterbi_dev(dXr, dK, m, h=h)
+    return dK, dB, R, obj
+
+
+# ---- PQ / OPQ resident on the device (csrc/lsq_kmeans.hip) -----------------------------------------------------------------------------
+def codebooks_from_padded(K, d, m):
+    """The padded (m h, d) codebook layout of the resident trainers (array or tensor) -> the list of (subdim x h) codebooks train_pq / train_opq return."""
+    if hasattr(K, "detach"):
+        K = K.detach().cpu().numpy()
+    K = _f32(K)
+    h = K.shape[0] // m
+    if K.shape != (m * h, d):
+        raise ValueError("K must be (m*h, d) with d = %d, got %s" % (d, K.shape))
+    sd = _subdims(d, m)
+    return [np.ascontiguousarray(K[i * h:(i + 1) * h, sd[i]].T) for i in range(m)]
+
+
+def _padded(C, d, m, h):
+    """list of (subdim x h) codebooks, or an (m h, d) array -> (m h, d) f32, zero outside each sub-space"""
+    if isinstance(C, (list, tuple)):
+        sd = _subdims(d, m)
+        K = np.zeros((m * h, d), dtype=np.float32)
+        for i in range(m):
+            K[i * h:(i + 1) * h, sd[i]] = _f32(C[i]).T
+        return K
+    K = _f32(C)
+    if K.shape != (m * h, d):
+        raise ValueError("initial codebooks must be (m*h, d) = (%d, %d), got %s" % (m * h, d, K.shape))
+    return K
+
+
+def _check_wide(cover, what):
+    if cover.sum(axis=0).min() < 2:
+        raise ValueError("%s: a sub-space of width < 2 (d == m) is not served on the device; use the host trainers (train_pq / train_opq / kmeans) there" % what)
+
+
+def kmeans_dev(dX, h, niter=25, seed=0, *, engine, dim2C=None, init=None):
+    """Lloyd k-means of all sub-spaces of a device tensor in lock-step: dX (n, d) f32 CUDA/HIP tensor, dim2C (d, m) 0/1 host array (None: plain k-means,
+    m = 1) -> (dK (m*h, d) tensor, zero outside each sub-space; dB (n, m) uint8 0-based tensor; total cost).
+    Seeding by lsq_kmeanspp_seed_dev with u = default_rng(seed).random((m, h)), or the given `init` codebooks ((m*h, d) array or tensor); assignment by
+    lsq_assign_codewords_dev; means by lsq_update_centers_dev.  A sub-space whose codes did not change has converged and is frozen (centres, codes, no more
+    re-seeds): the state the host kmeans() leaves at its `break`.  An empty cluster is re-seeded with a random data row drawn from default_rng(seed + j) for
+    sub-space j in ascending cluster order, as kmeans() of train_pq's i-th sub-space does; the counts cross the bus only when some cluster is empty."""
+    import torch
+    n, d = dX.shape
+    dev = dX.device
+    cover = np.ones((d, 1), dtype=np.uint8) if dim2C is None else np.ascontiguousarray(np.asarray(dim2C).astype(np.uint8))
+    if cover.ndim != 2 or cover.shape[0] != d:
+        raise ValueError("dim2C must be (d, m) with d = %d, got %s" % (d, cover.shape))
+    m = cover.shape[1]
+    _check_wide(cover, "kmeans_dev")
+    if n < 1:
+        raise ValueError("kmeans_dev: no data")
+    if init is None:
+        u = np.random.default_rng(seed).random((m, h))
+        dK, _, _ = engine.kmeanspp_seed_dev(dX, cover, u, m, h=h, want_idx=False)
+    elif hasattr(init, "detach"):
+        dK = init.detach().to(device=dev, dtype=torch.float32).clone().contiguous()
+        if tuple(dK.shape) != (m * h, d):
+            raise ValueError("init must be (m*h, d) = (%d, %d), got %s" % (m * h, d, tuple(dK.shape)))
+    else:
+        dK = torch.from_numpy(_padded(init, d, m, h).copy()).to(dev)
+    dims = [torch.from_numpy(np.nonzero(cover[:, j])[0]).to(dev) for j in range(m)]
+    rngs = [np.random.default_rng(seed + j) for j in range(m)]
+    dB, dmin = engine.assign_codewords_dev(dX, dK, m, h=h, want_min=True)
+    active = np.ones(m, dtype=bool)
+    dKn = torch.empty_like(dK)
+    dcnt = torch.empty(m * h, dtype=torch.int32, device=dev)
+    for _ in range(niter):
+        engine.update_centers_dev(dX, dB, cover, m, h=h, out=dKn, counts=dcnt)
+        nempty = (dcnt.view(m, h) == 0).sum(dim=1).cpu().numpy()
+        cnt = dcnt.view(m, h).cpu().numpy() if nempty[active].any() else None
+        for j in np.nonzero(active)[0]:
+            dK[j * h:(j + 1) * h] = dKn[j * h:(j + 1) * h]
+            if cnt is not None and nempty[j]:
+                ks = np.nonzero(cnt[j] == 0)[0]
+                rows = torch.as_tensor(np.array([rngs[j].integers(n) for _k in ks], dtype=np.int64), device=dev)
+                dK[(torch.as_tensor(ks + j * h, device=dev))[:, None], dims[j][None, :]] = dX[rows[:, None], dims[j][None, :]]
+        dB2, dmin = engine.assign_codewords_dev(dX, dK, m, h=h, want_min=True)
+        changed = (dB2 != dB).any(dim=0).cpu().numpy()
+        dB = dB2                                                 # a frozen sub-space's centres did not move: its codes are the same bits
+        active &= changed
+        if not active.any():
+            break
+    xsq = (dX.double() ** 2) @ torch.from_numpy(cover.astype(np.float64)).to(dev)      # (n, m): ||x_sub||^2
+    cost = float((dmin.double() + xsq).clamp_min(0).sum().item())
+    return dK, dB, cost
+
+
+def train_pq_dev(dX, m, h, *, seed=0, engine, init=None):
+    """train_pq on a device tensor (src/pq/PQ.jl:44-76): dX (n, d) f32 -> (dK (m*h, d) padded codebooks, dB (n, m) uint8 0-based, error).
+    init: m explicit initial codebooks (a list of (subdim x h), as train_pq's, or the padded (m*h, d) layout); no seeding then."""
+    import torch
+    n, d = dX.shape
+    if d < m:
+        raise ValueError("train_pq_dev: d = %d < m = %d" % (d, m))
+    cover = _cover_map(_subdims(d, m), d, m)
+    _check_wide(cover, "train_pq_dev")
+    if init is not None and not hasattr(init, "detach"):
+        init = _padded(init, d, m, h)
+    dK, dB, _ = kmeans_dev(dX, h, seed=seed, engine=engine, dim2C=cover, init=init)
+    offs = (torch.arange(m, device=dX.device, dtype=torch.int64) * h)[None, :]
+    err = float(((dX - dK[dB.to(torch.int64) + offs].sum(dim=1)).double() ** 2).sum().item()) / n
+    return dK, dB, err
+
+
+def train_opq_dev(dX, m, h, niter, init="natural", *, seed=0, engine):
+    """train_opq on a device tensor (src/opq/OPQ.jl:21-101): dX (n, d) f32 -> (dK (m*h, d): the codebooks of the rotated space, padded; dB (n, m) uint8
+    0-based (feeds train_chainq_dev); R (d, d) f32 host; obj (niter + 1,) f32).  The generator, its draw order (the "random" rotation, then h sampled rows per
+    sub-space) and the empty-cluster rule (the old codeword stays) are train_opq's; only the sampled indices are uploaded.  torch is the glue on the device:
+    the rotation X R, the reconstruction, the objective and the d x d product X CB' (float64); per iteration that matrix, R and the objective cross the bus
+    and the Procrustes SVD runs on the host in float64."""
+    import torch
+    n, d = dX.shape
+    dev = dX.device
+    if d < m:
+        raise ValueError("train_opq_dev: d = %d < m = %d" % (d, m))
+    sd = _subdims(d, m)
+    cover = _cover_map(sd, d, m)
+    _check_wide(cover, "train_opq_dev")
+    if n < h:
+        raise ValueError("train_opq_dev: n = %d < h = %d: the initial codebooks are h rows sampled without replacement" % (n, h))
+    rng = np.random.default_rng(seed)
+    if init == "natural":
+        R = np.eye(d, dtype=np.float32)
+    elif init == "random":
+        R = np.linalg.svd(rng.standard_normal((d, d)))[0].astype(np.float32)
+    else:
+        raise ValueError("Intialization %s unknown" % init)
+
+    def rotate(Rm):
+        return (dX @ torch.as_tensor(np.ascontiguousarray(Rm, dtype=np.float32), device=dev)).contiguous()       # rows of (R'X)'
+
+    dXr = rotate(R)
+    dK = torch.zeros((m * h, d), dtype=torch.float32, device=dev)
+    for i in range(m):                                                          # :46-50
+        rows = torch.from_numpy(rng.choice(n, h, replace=False).astype(np.int64)).to(dev)
+        dK[i * h:(i + 1) * h, sd[i]] = dXr[rows, sd[i]]
+    offs = (torch.arange(m, device=dev, dtype=torch.int64) * h)[None, :]
+    dB = engine.assign_codewords_dev(dXr, dK, m, h=h)
+    dX64 = dX.double()
+    obj = np.zeros(niter + 1, dtype=np.float32)
+    for it in range(niter + 1):
+        dCB = dK[dB.to(torch.int64) + offs].sum(dim=1)                          # (n, d): the reconstructions in the rotated space
+        dR = torch.as_tensor(R, device=dev)
+        obj[it] = float(((dCB @ dR.T - dX).double() ** 2).sum().item()) / n
+        M = (dX64.T @ dCB.double()).cpu().numpy()                               # X CB' (d x d), float64
+        U, _, Vt = np.linalg.svd(M, full_matrices=False)                        # :78-79
+        R = (U @ Vt).astype(np.float32)
+        dXr = rotate(R)
+        engine.update_centers_dev(dXr, dB, cover, m, K_prev=dK, h=h, out=dK)    # :85-86
+        dB = engine.assign_codewords_dev(dXr, dK, m, h=h)                       # :88-91
     return dK, dB, R, obj

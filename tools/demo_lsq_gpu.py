@@ -1,7 +1,10 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [nread_train] [nread_base] [nquery]
+
+--resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
+the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
 
 needs $LSQ_DATA_DIR/sift/{sift_learn,sift_base,sift_query}.fvecs and sift_groundtruth.ivecs (TEXMEX layout).  The file's ground truth
 describes the full 10^6-vector base only: for a prefix of it (nread_base < 10^6) and for the stand-in, the ground truth is exact k-NN of the base
@@ -50,21 +53,44 @@ def load(nt, nb, nq):
     return "synthetic", xt, xb, xq, ground_truth(xb, xq)
 
 
+def train_resident(x_train, m, h, niter, ilsiter, icmiter, randord, npert):
+    """the three training stages on one device tensor -> what train_lsq returns, in its host shapes"""
+    import torch
+    t0 = time.perf_counter()
+    with lsq.Engine(0) as eng:
+        dX = torch.from_numpy(np.ascontiguousarray(x_train.T)).cuda()
+        dK, dB, R, err = lsq.train_opq_dev(dX, m, h, niter, "natural", engine=eng)
+        print("Error after OPQ is %e" % err[-1])
+        dK, dB, R, err = lsq.train_chainq_dev(dX, m, h, R, dB, niter, engine=eng)
+        print("Error after ChainQ is %e" % err[-1])
+        dK, dB, cbnorms, B_norms, obj = lsq.train_lsq_dev(dX, m, h, dB, niter, ilsiter, icmiter, randord, npert, engine=eng, R=R)
+        torch.cuda.synchronize()
+        K = dK.cpu().numpy()
+        B = np.ascontiguousarray(dB.cpu().numpy().T.astype(np.int16) + 1)
+    print("Error after LSQ is %e; the three resident trainers took %.3f s" % (obj[-1], time.perf_counter() - t0))
+    return [np.ascontiguousarray(K[i * h:(i + 1) * h].T) for i in range(m)], B, cbnorms, B_norms, obj
+
+
 def main():
+    args = [a for a in sys.argv[1:] if a != "--resident"]
+    resident = len(args) != len(sys.argv) - 1
     real = bool(os.environ.get("LSQ_DATA_DIR"))
-    nt = int(sys.argv[1]) if len(sys.argv) > 1 else (10_000 if real else 3000)
-    nb = int(sys.argv[2]) if len(sys.argv) > 2 else (1_000_000 if real else 6000)
-    nq = int(sys.argv[3]) if len(sys.argv) > 3 else (10_000 if real else 64)
+    nt = int(args[0]) if len(args) > 0 else (10_000 if real else 3000)
+    nb = int(args[1]) if len(args) > 1 else (1_000_000 if real else 6000)
+    nq = int(args[2]) if len(args) > 2 else (10_000 if real else 64)
     name, x_train, x_base, x_query, gt = load(nt, nb, nq)
     d = x_train.shape[0]
     m, h, niter, knn = (7, 256, 10, 1000) if name == "SIFT1M" else (4, 256, 3, 50)     # demo_lsq_gpu.jl:13-20
-    C, B, R, err = lsq.train_opq(x_train, m, h, niter, "natural", True)
-    print("Error after OPQ is %e" % err[-1])
-    with lsq.Engine(0) as eng:                                              # ChainQ with its structured codebook update on the device as well
-        C, B, R, err = lsq.train_chainq(x_train, m, h, R, B, C, niter, engine=eng, device_update=True)
-    print("Error after ChainQ is %e" % err[-1])
     ilsiter, icmiter, randord, npert = 8, 4, True, 4
-    C, B, cbnorms, B_norms, obj = lsq.train_lsq(x_train, m, h, R, B, C, niter, ilsiter, icmiter, randord, min(npert, m), True)
+    if resident:
+        C, B, cbnorms, B_norms, obj = train_resident(x_train, m, h, niter, ilsiter, icmiter, randord, min(npert, m))
+    else:
+        C, B, R, err = lsq.train_opq(x_train, m, h, niter, "natural", True)
+        print("Error after OPQ is %e" % err[-1])
+        with lsq.Engine(0) as eng:                                          # ChainQ with its structured codebook update on the device as well
+            C, B, R, err = lsq.train_chainq(x_train, m, h, R, B, C, niter, engine=eng, device_update=True)
+        print("Error after ChainQ is %e" % err[-1])
+        C, B, cbnorms, B_norms, obj = lsq.train_lsq(x_train, m, h, R, B, C, niter, ilsiter, icmiter, randord, min(npert, m), True)
     B_base = lsq.randinit(x_base.shape[1], m, h)
     t0 = time.perf_counter()
     Bs, objs = lsq.encode_icm_cuda(x_base, B_base, C, [16], icmiter, min(npert, m), randord, 2, True)
