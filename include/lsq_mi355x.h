@@ -95,7 +95,9 @@ LSQ_API int lsq_device_count(int *count);
 LSQ_API int lsq_create(lsq_ctx **ctx, int device);
 LSQ_API int lsq_destroy(lsq_ctx *ctx);
 /* Launch on the caller's hipStream_t (e.g. torch's current stream).  NULL = HIP's default (null)
- * stream; option "own_stream" switches back to the context's private non-blocking stream. */
+ * stream; option "own_stream" switches back to the context's private non-blocking stream.
+ * Nothing orders work on the new stream behind un-awaited work this context enqueued on the old one: the caller
+ * must have awaited the old stream (lsq_synchronize, or its own stream / device synchronisation) before every switch. */
 LSQ_API int lsq_set_stream(lsq_ctx *ctx, void *hip_stream);
 /* Options: "chunk" (vectors per resident chunk, default 1015808 = 256 blocks x 3968 vectors: one pass of the walk kernel per block), "profile" (0/1), "own_stream",
  *   "schedule" -- how the ICM node updates run; all give bit-identical codes:

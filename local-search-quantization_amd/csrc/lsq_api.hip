@@ -58,7 +58,6 @@ struct lsq_ctx {
                              // with exact refinement, one launch per ILS iteration (chunks below q16_min vectors / non-finite data: schedule 4);
     int64_t q16_min = 65536; // schedule 6: smaller chunks take schedule 4 (every block is light there: nothing to filter)
     int tables_changed = 1;  // schedule 6: the pair tables were rebuilt since the last lsq_launch_q16_prepare
-    int new_call = 1;        // schedule 6: no chunk of this call has reset the level parameters' counters yet
     // Host-buffer entry points called again with the SAME codebooks (the trainer's chained encoding_icm, demos/demo_lsq.jl:48-51 / LSQ.jl:54-57 -- the
     // reference rebuilds its binaries in every call, encode_icm.jl:145, with identical results): the uploaded K, ||c||^2, the pair tables and what the
     // filtered walk derives from them are still in this context -- one memcmp of the caller's K against a host copy decides
@@ -93,7 +92,6 @@ struct lsq_ctx {
     DevBuf road;
     int64_t fallback_div = 64;                         // option "filter_fallback_div": the chunk goes to the f32 walk when flagged pairs * div > all pairs (0 = never)
     int64_t filter_fallback_chunks = 0;                // chunks the filter handed to the f32 walk (unusable bounds or too many out-of-range vectors)
-    int64_t call_I = 0, call_q16_chunks = 0;
     float *q_colshift = nullptr;                       // inside qscratch: the per-candidate shift of the unary levels (double-centred tables)
     lsq_lsqr_state *lsqr = nullptr;                    // device LSQR (lsq_lsqr.hip): work buffers, created on first use
     lsq_kmeans_state *kmeans = nullptr;                // cluster means and k-means++ seeding (lsq_kmeans.hip): work buffers, created on first use
@@ -538,8 +536,6 @@ static int q16_prepare_chunk(lsq_ctx *c, const float *dX, const float *dK, int d
         LSQ_TRY(c->qsigma.ensure(sizeof(float) * (size_t)cn * m));      // per-(vector, node) unary shift: levels only (lsq_icmq.hip)
         LSQ_TRY(c->qflag.ensure(sizeof(unsigned short) * (size_t)(cn + 2)));
         LSQ_TRY(c->qp.ensure(sizeof(lsq_q16_params)));
-        if (c->new_call && !c->small_packed) LSQ_HIP(hipMemsetAsync(c->qp.p, 0, sizeof(lsq_q16_params), c->stream));      // first chunk of a call: ok = 0, oor = 0 (packed: begin_call's fill)
-        c->new_call = 0;
         char *sc = c->qscratch.as<char>();
         if (Xsample) LSQ_TRY(c->sSigmaS.ensure(sizeof(float) * (size_t)nsample_rows * m));
         LSQ_TRY(lsq_launch_q16_prepare(c->stream, dX, cn, d, dK, c->sci.as<float>(), c->T.as<float>(), m, c->Tq.as<uint16_t>(),
@@ -560,7 +556,6 @@ static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m);
 static int build_unaries(lsq_ctx *c, const float *dX, const float *dK, int d, int64_t cn, int m, int slice, int64_t r0, int64_t rows) {
     c->chunk_q16 = false;
     const bool q16 = slice > 0 && r0 == 0 && rows == cn && use_q16(c, cn);
-    if (q16) c->call_q16_chunks += 1;
     if (q16) LSQ_TRY(q16_prepare_chunk(c, dX, dK, d, cn, m));      // 16-bit filtered walk: the GEMM below then also emits the u16 planes
     {
         Timer t(c, CAT_UNARIES);
@@ -608,7 +603,6 @@ static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m) {
 static int build_unaries_from_host(lsq_ctx *c, const float *Xh, float *dXc, const float *dK, int d, int64_t cn, int m, int slice) {
     c->chunk_q16 = false;
     const bool q16 = slice > 0 && use_q16(c, cn);
-    if (q16) c->call_q16_chunks += 1;
     const size_t row_bytes = sizeof(float) * (size_t)d;
     int64_t prow = (int64_t)((uint64_t)c->panel_bytes / row_bytes) / 128 * 128;      // ~48 MB panels, whole 128-row tiles
     if (prow < 128) prow = 128;
@@ -654,10 +648,7 @@ static int build_unaries_from_host(lsq_ctx *c, const float *Xh, float *dXc, cons
     });
     } catch (...) {      // no thread to be had: nothing may escape the C ABI -- one-piece upload on the compute stream, then the ordinary build
         LSQ_HIP(hipMemcpyAsync(dXc, Xh, (size_t)cn * row_bytes, hipMemcpyHostToDevice, c->stream));
-        if (q16) {      // the flags / counters the sample-mode prepare left behind are rebuilt by the full-chunk prepare inside build_unaries
-            c->call_q16_chunks -= 1;
-            c->tables_changed = 1;
-        }
+        if (q16) c->tables_changed = 1;      // the flags / counters the sample-mode prepare left behind are rebuilt by the full-chunk prepare inside build_unaries
         return build_unaries(c, dXc, dK, d, cn, m, slice, 0, cn);
     }
     int rc = LSQ_OK;
@@ -758,7 +749,6 @@ template <class Snap>
 static int encode_chunk(lsq_ctx *c, const float *dXc, const float *dK, int64_t cn, uint64_t goff, const EncodeParams &P, int64_t I, Snap snap,
                         bool unaries_ready = false) {
     const int cs = lsq_code_stride(P.m);
-    c->call_I = I;
     if (!unaries_ready) LSQ_TRY(build_unaries(c, dXc, dK, P.d, cn, P.m, lsq_walk_slice_width(P.m), 0, cn));
     LSQ_TRY(c->recNew.ensure((size_t)cn * cs));
     LSQ_TRY(c->prev.ensure(sizeof(float) * (size_t)cn));
@@ -853,8 +843,6 @@ static int begin_call(lsq_ctx *c, int64_t I, int nr) {
     LSQ_TRY(c->qp.ensure(sizeof(lsq_q16_params)));
     if (!c->async_mode) LSQ_TRY(fold_pending(c));             // statistics an earlier async call left on the device (synchronises)
     c->walk_counters = c->active.as<unsigned long long>();
-    c->call_q16_chunks = 0;
-    c->new_call = 1;
     c->small_packed = c->counters.view && c->obj.view && c->bad.view && c->qp.view && c->active.view && c->road.view;
     if (c->small_packed) {
         // one fill: counters, sums, flags, level parameters (+ the walk counters and the road words unless async calls are still accumulating)
@@ -868,6 +856,7 @@ static int begin_call(lsq_ctx *c, int64_t I, int nr) {
     LSQ_HIP(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * 2 * (size_t)std::max<int64_t>(I, 1), c->stream));
     LSQ_HIP(hipMemsetAsync(c->obj.p, 0, sizeof(double) * (size_t)std::max(nr, 1), c->stream));
     LSQ_HIP(hipMemsetAsync(c->bad.p, 0, sizeof(int), c->stream));
+    LSQ_HIP(hipMemsetAsync(c->qp.p, 0, sizeof(lsq_q16_params), c->stream));      // the level parameters' per-call counter (oor): the packed fill above covers it
     return LSQ_OK;
 }
 
@@ -1268,8 +1257,7 @@ extern "C" int lsq_encode_icm_fully(lsq_ctx *c, int16_t *B, const float *X, cons
     LSQ_TRY(upload_xk(c, X, K, d, n, m));
     LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));
     LSQ_TRY(prepare_tables(c, c->sK.as<float>(), d, m));
-    c->call_I = 0;                                     // the worker has no accept step and no probe memory: always the configured road
-    c->walk_counters = nullptr;
+    c->walk_counters = nullptr;                        // the worker has no accept step and no probe memory: always the configured road
     LSQ_TRY(build_unaries(c, c->sX.as<float>(), c->sK.as<float>(), d, n, m, lsq_walk_slice_width(m), 0, n));
     LSQ_TRY(c->recNew.ensure((size_t)n * lsq_code_stride(m)));
     int32_t order[LSQ_MAX_M];
