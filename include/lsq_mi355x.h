@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 1100
+#define LSQ_VERSION 1200
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -145,6 +145,38 @@ LSQ_API int lsq_get_timings_sized(lsq_ctx *ctx, void *out, size_t bytes);
  * the visiting order (mod 64), summed over ILS iterations, chunks and calls since the last lsq_reset_timings: the device-side
  * counterpart of the reference's per-iteration "% equal / % better" prints, for the sweeps.  out[count], count <= 64. */
 LSQ_API int lsq_get_walk_trace(lsq_ctx *ctx, int64_t *out, int count);
+/* Read-only snapshot of what the LAST resident chunk of the last encode call left in the context for the 16-bit filtered walk (schedule 6; since v1200):
+ * the inputs of the inequality the filter's window rests on (csrc/lsq_icmq.hip, BOUND), for a checker outside the library.  Computes nothing and changes
+ * no result: one hipMemcpyAsync of default kind on the context's stream, so `dst` may be host or device memory (wait for the stream before reading it).
+ * With cn = the chunk's rows, SLQ = 32 (m <= 8) or 16 candidates per 16-bit slice, SLF = SLQ / 2 per f32 slice, h = 256:
+ *   LSQ_SNAP_PARAMS  lsq_q16_snapshot_params below (the library's level parameters as the walk reads them)
+ *   LSQ_SNAP_UQ      u16 [m][h / SLQ][cn][SLQ]                   unary levels:  candidate a of (node j, row i) at ((j * (h / SLQ) + a / SLQ) * cn + i) * SLQ + a % SLQ
+ *   LSQ_SNAP_TQ      u16 [m][h / SLQ][(m - 1) * h][SLQ]          table levels of node j, conditioning table kk (codebook k = kk + (kk >= j)) and code b: row
+ *                                                                R(kk, b) of slice a / SLQ, where with S = 4 (SLQ = 32) or 8 (SLQ = 16) slots per line and
+ *                                                                n0 = min(m - 1, S):  R = b * n0 + kk  (kk < S),  R = n0 * h + b * (m - 1 - n0) + (kk - S)  (kk >= S)
+ *   LSQ_SNAP_QFLAG   u16 [cn]                                    bit j: the pair (row, node j) lies outside the sampled level range and takes the f32 routine
+ *   LSQ_SNAP_U       f32 [m][h / SLF][cn][SLF]                   the f32 unaries, slice-major like the levels
+ *   LSQ_SNAP_T       f32 [m][m][h][h]                            the f32 pair tables: T[j][k][b][a] (the diagonal blocks j == k are never read)
+ * info (optional) receives 6 values: cn, the chunk's first row within the call, m, SLQ, SLF, and 1 when the chunk stayed on the filtered walk to its end
+ * (0: the probe after its first ILS iteration handed the rest to the f32 walk; the levels are resident either way).
+ * LSQ_EINVAL: no filtered chunk is resident (no encode yet, a chunk below "q16_min", a verdict for the f32 walk, option "async" -- its verdict stays on the
+ * device --, or a later call that rebuilt the unaries or the tables), `bytes` smaller than the item, or an unknown `what`. */
+enum { LSQ_SNAP_PARAMS = 0, LSQ_SNAP_UQ = 1, LSQ_SNAP_TQ = 2, LSQ_SNAP_QFLAG = 3, LSQ_SNAP_U = 4, LSQ_SNAP_T = 5 };
+typedef struct lsq_q16_snapshot_node {
+    float loU, invD, D;      /* unary levels start at loU; the common step of node j and its f32 reciprocal */
+    float hiq;               /* largest unary level inside the sampled range: a pair with a level outside [0, hiq] is flagged */
+    int32_t window;          /* levels: the exact argmin lies within `window` of the smallest level sum (65535: everything is refined) */
+    int32_t pad_;
+    double slack;            /* bound of |C_i + D Q[a] - s_f32[a]|; window = floor(2 slack / D) + 1 */
+} lsq_q16_snapshot_node;
+typedef struct lsq_q16_snapshot_params {
+    int32_t ok;              /* 1: usable bounds */
+    int32_t oor;             /* values outside the sampled level range so far in the call */
+    int32_t nflag;           /* flagged (row, node) pairs of the chunk */
+    int32_t pad_;
+    lsq_q16_snapshot_node node[16];
+} lsq_q16_snapshot_params;
+LSQ_API int lsq_get_q16_snapshot(lsq_ctx *ctx, int what, void *dst, size_t bytes, int64_t *info);
 LSQ_API int lsq_reset_timings(lsq_ctx *ctx);
 LSQ_API int lsq_synchronize(lsq_ctx *ctx);
 

@@ -44,6 +44,18 @@ class LinscanStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Q16SnapshotNode(C.Structure):
+    _fields_ = [("loU", C.c_float), ("invD", C.c_float), ("D", C.c_float), ("hiq", C.c_float), ("window", C.c_int32), ("pad_", C.c_int32),
+                ("slack", C.c_double)]
+
+
+class Q16SnapshotParams(C.Structure):
+    _fields_ = [("ok", C.c_int32), ("oor", C.c_int32), ("nflag", C.c_int32), ("pad_", C.c_int32), ("node", Q16SnapshotNode * 16)]
+
+
+SNAP_PARAMS, SNAP_UQ, SNAP_TQ, SNAP_QFLAG, SNAP_U, SNAP_T = 0, 1, 2, 3, 4, 5
+
+
 class Spgl1Params(C.Structure):
     _fields_ = [("opt_tol", C.c_double), ("max_iter", C.c_int64)]
 
@@ -72,6 +84,7 @@ SIGNATURES = {
     "lsq_get_timings": (_i, [_vp, C.POINTER(Timings)]),
     "lsq_get_timings_sized": (_i, [_vp, _vp, C.c_size_t]),
     "lsq_get_walk_trace": (_i, [_vp, _vp, _i]),
+    "lsq_get_q16_snapshot": (_i, [_vp, _i, _vp, C.c_size_t, _vp]),
     "lsq_reset_timings": (_i, [_vp]),
     "lsq_synchronize": (_i, [_vp]),
     "lsq_multi_create": (_i, [C.POINTER(_vp), _vp, _i]),

@@ -83,6 +83,11 @@ struct lsq_ctx {
     bool small_packed = false;                                 // this call: every window still in place (an outgrown one gets an allocation of its own)
     DevBuf Uq, Tq, qp, qscratch, qflag, qsigma;                // 16-bit filtered walk: u16 unary planes, u16 slice tables, lsq_q16_params, bound scratch, per-vector out-of-range flags
     bool chunk_q16 = false;                            // the resident chunk runs the filtered walk (set by build_unaries from the chunk's verdict)
+    // what lsq_get_q16_snapshot needs to know of the last chunk whose unaries were built: its levels are resident (the verdict named the filtered walk),
+    // its rows and m, and its first row within the call
+    bool snap_resident = false;
+    int64_t snap_cn = 0, snap_row0 = 0, call_row0 = 0;
+    int snap_m = 0;
     // option "async" (lsq_encode_icm_dev only): no host round trip inside the call and none at its end -- the chunk's road (verdict after the unary
     // GEMM, probe after the first ILS iteration) is decided by one-thread kernels into `road`, BOTH walks are enqueued every ILS iteration and the one
     // the word does not name returns at once; objective sums and counters are copied to the caller's (device or pinned) buffers on the stream
@@ -349,6 +354,41 @@ extern "C" int lsq_get_walk_trace(lsq_ctx *c, int64_t *out, int count) {
     return LSQ_OK;
 }
 
+// The level parameters, the levels and the f32 terms they were taken of, as the last filtered chunk left them: a copy in stream order, nothing else
+static_assert(sizeof(lsq_q16_snapshot_params) == sizeof(lsq_q16_params) && sizeof(lsq_q16_snapshot_node) == sizeof(lsq_q16_node) &&
+              offsetof(lsq_q16_snapshot_params, node) == offsetof(lsq_q16_params, node) && offsetof(lsq_q16_snapshot_node, window) == offsetof(lsq_q16_node, window) &&
+              offsetof(lsq_q16_snapshot_node, slack) == offsetof(lsq_q16_node, slack) && offsetof(lsq_q16_snapshot_node, hiq) == offsetof(lsq_q16_node, hiq),
+              "the public snapshot structure restates lsq_q16_params");
+extern "C" int lsq_get_q16_snapshot(lsq_ctx *c, int what, void *dst, size_t bytes, int64_t *info) {
+    LSQ_TRY(use_device(c));
+    if (!c->snap_resident) {
+        lsq_set_error("lsq_get_q16_snapshot: no filtered chunk is resident (the last chunk whose unaries were built did not take the 16-bit filtered walk)");
+        return LSQ_EINVAL;
+    }
+    const size_t cn = (size_t)c->snap_cn, m = (size_t)c->snap_m;
+    const DevBuf *src = nullptr;
+    size_t need = 0;
+    switch (what) {
+    case LSQ_SNAP_PARAMS: src = &c->qp; need = sizeof(lsq_q16_params); break;
+    case LSQ_SNAP_UQ: src = &c->Uq; need = sizeof(uint16_t) * m * cn * LSQ_H; break;
+    case LSQ_SNAP_TQ: src = &c->Tq; need = sizeof(uint16_t) * m * (m - 1) * LSQ_H * LSQ_H; break;
+    case LSQ_SNAP_QFLAG: src = &c->qflag; need = sizeof(unsigned short) * cn; break;
+    case LSQ_SNAP_U: src = &c->U; need = sizeof(float) * m * cn * LSQ_H; break;
+    case LSQ_SNAP_T: src = &c->T; need = sizeof(float) * m * m * LSQ_H * LSQ_H; break;
+    default: lsq_set_error("lsq_get_q16_snapshot: unknown item %d", what); return LSQ_EINVAL;
+    }
+    if (need > 0 && (!dst || bytes < need || src->cap < need)) {
+        lsq_set_error("lsq_get_q16_snapshot: item %d takes %zu bytes, the buffer has %zu", what, need, dst ? bytes : (size_t)0);
+        return LSQ_EINVAL;
+    }
+    if (info) {
+        info[0] = c->snap_cn; info[1] = c->snap_row0; info[2] = c->snap_m;
+        info[3] = lsq_q16_slice_width(c->snap_m); info[4] = lsq_walk_slice_width(c->snap_m); info[5] = c->chunk_q16 ? 1 : 0;
+    }
+    if (need > 0) LSQ_HIP(hipMemcpyAsync(dst, src->p, need, hipMemcpyDefault, c->stream));
+    return LSQ_OK;
+}
+
 extern "C" int lsq_reset_timings(lsq_ctx *c) {
     LSQ_TRY(use_device(c));
     LSQ_TRY(fold_pending(c));
@@ -501,6 +541,7 @@ static int check_codes_host(const char *fn, const int16_t *B, int64_t n, int m, 
 static int prepare_tables(lsq_ctx *c, const float *dK, int d, int m) {
     Timer t(c, CAT_TABLES);
     c->tables_changed = 1;
+    c->snap_resident = false;       // the f32 tables the resident levels were taken of are about to change
     c->tables_valid = false;        // whoever knows the host copy of dK marks it valid again (host_codebooks)
     const int mh = m * LSQ_H;
     LSQ_TRY(c->sci.ensure(sizeof(float) * (size_t)mh));
@@ -574,6 +615,7 @@ static int build_unaries(lsq_ctx *c, const float *dX, const float *dK, int d, in
 // which road the chunk takes after its unary GEMM (filtered walk / f32 walk): on the host, or -- option "async" -- by a one-thread kernel
 static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m) {
     c->chunk_road_dev = false;
+    c->snap_resident = false;
     if (q16 && c->async_mode) {
         // option "async": the same verdict taken by a one-thread kernel; both walks are enqueued and the word picks (run_sweeps)
         LSQ_TRY(c->road.ensure(2 * sizeof(unsigned)));
@@ -591,6 +633,8 @@ static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m) {
         LSQ_HIP(hipStreamSynchronize(c->stream));
         if (verdict[0] == 1 && (int64_t)verdict[2] * c->fallback_div <= cn * (int64_t)m) c->chunk_q16 = true;
         else c->filter_fallback_chunks += 1;
+        c->snap_resident = c->chunk_q16;
+        c->snap_cn = cn; c->snap_m = m; c->snap_row0 = c->call_row0;
     }
     return LSQ_OK;
 }
@@ -835,6 +879,8 @@ static int validate_encode(const char *fn, int d, int64_t n, int m, int h, const
 }
 
 static int begin_call(lsq_ctx *c, int64_t I, int nr) {
+    c->call_row0 = 0;
+    c->snap_resident = false;       // the per-call block (the level parameters among it) is zeroed below
     LSQ_TRY(c->counters.ensure(sizeof(unsigned long long) * 2 * (size_t)std::max<int64_t>(I, 1)));
     LSQ_TRY(c->obj.ensure(sizeof(double) * (size_t)std::max(nr, 1)));
     LSQ_TRY(c->bad.ensure(sizeof(int)));
@@ -932,6 +978,7 @@ extern "C" int lsq_encode_icm_dev(lsq_ctx *c, const float *dX, const uint8_t *dB
     const int cs = lsq_code_stride(m);
     for (int64_t off = 0; off < n; off += c->chunk) {
         const int64_t cn = std::min<int64_t>(c->chunk, n - off);
+        c->call_row0 = off;
         LSQ_TRY(c->recCur.ensure((size_t)cn * cs));
         {
             Timer t(c, CAT_OTHER);
@@ -1003,6 +1050,7 @@ static int encode_host(lsq_ctx *c, const char *fn, const float *X, const int16_t
     int which = 0;
     for (int64_t off = 0; off < n; off += c->chunk, which ^= 1) {
         const int64_t cn = std::min<int64_t>(c->chunk, n - off);
+        c->call_row0 = off;
         LSQ_TRY(xb[which]->ensure(sizeof(float) * (size_t)cn * d));
         LSQ_TRY(c->sB16.ensure(sizeof(int16_t) * (size_t)cn * m));
         LSQ_TRY(c->sOut16.ensure(sizeof(int16_t) * (size_t)cn * m * nr));
@@ -1258,6 +1306,7 @@ extern "C" int lsq_encode_icm_fully(lsq_ctx *c, int16_t *B, const float *X, cons
     LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));
     LSQ_TRY(prepare_tables(c, c->sK.as<float>(), d, m));
     c->walk_counters = nullptr;                        // the worker has no accept step and no probe memory: always the configured road
+    c->call_row0 = 0;
     LSQ_TRY(build_unaries(c, c->sX.as<float>(), c->sK.as<float>(), d, n, m, lsq_walk_slice_width(m), 0, n));
     LSQ_TRY(c->recNew.ensure((size_t)n * lsq_code_stride(m)));
     int32_t order[LSQ_MAX_M];

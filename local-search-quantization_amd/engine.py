@@ -96,6 +96,36 @@ class Engine:
     def reset_timings(self):
         self._check(self._L.lsq_reset_timings(self._h))
 
+    def q16_snapshot(self):
+        """What the last resident chunk of the last encode call left behind for the 16-bit filtered walk: the inputs of the inequality its window rests on
+        (csrc/lsq_icmq.hip, BOUND), read-only   [lsq_get_q16_snapshot].  Raises LsqError (LSQ_EINVAL) when no filtered chunk is resident.
+        -> dict: rows (cn), row0 (the chunk's first row within the call), m, slq / slf (candidates per 16-bit / f32 slice), filtered (the chunk stayed on the
+           filtered walk to its end), params {ok, oor, nflag, loU, invD, D, hiq (f32 arrays [m]), window (int [m]), slack (f64 [m])}, and device tensors
+           Uq u16 [m][256/slq][cn][slq], Tq u16 [m][256/slq][(m-1)*256][slq], qflag u16 [cn], U f32 [m][256/slf][cn][slf], T f32 [m][m][256][256]
+           (torch has no uint16 arithmetic: the u16 items come as int16 tensors holding the same bits)."""
+        import torch
+        P = _lib.Q16SnapshotParams()
+        info = np.zeros(6, dtype=np.int64)
+        torch.cuda.current_stream(self.device).synchronize()      # the tensors below are written on the context's stream, not on torch's
+        self._check(self._L.lsq_get_q16_snapshot(self._h, _lib.SNAP_PARAMS, C.addressof(P), C.sizeof(P), info.ctypes.data))
+        cn, row0, m, slq, slf, filtered = (int(v) for v in info)
+        dev = torch.device("cuda", self.device)
+        shapes = {"Uq": (_lib.SNAP_UQ, torch.int16, (m, H // slq, cn, slq)), "Tq": (_lib.SNAP_TQ, torch.int16, (m, H // slq, (m - 1) * H, slq)),
+                  "qflag": (_lib.SNAP_QFLAG, torch.int16, (cn,)), "U": (_lib.SNAP_U, torch.float32, (m, H // slf, cn, slf)),
+                  "T": (_lib.SNAP_T, torch.float32, (m, m, H, H))}
+        out = {"rows": cn, "row0": row0, "m": m, "slq": slq, "slf": slf, "filtered": bool(filtered)}
+        for name, (what, dtype, shape) in shapes.items():
+            t = torch.empty(shape, dtype=dtype, device=dev)
+            self._check(self._L.lsq_get_q16_snapshot(self._h, what, t.data_ptr(), t.numel() * t.element_size(), None))
+            out[name] = t
+        self.synchronize()
+        nodes = [P.node[j] for j in range(m)]
+        out["params"] = {"ok": int(P.ok), "oor": int(P.oor), "nflag": int(P.nflag),
+                         "loU": np.array([q.loU for q in nodes], dtype=np.float32), "invD": np.array([q.invD for q in nodes], dtype=np.float32),
+                         "D": np.array([q.D for q in nodes], dtype=np.float32), "hiq": np.array([q.hiq for q in nodes], dtype=np.float32),
+                         "window": np.array([q.window for q in nodes], dtype=np.int64), "slack": np.array([q.slack for q in nodes], dtype=np.float64)}
+        return out
+
     # -- (1) whole call, host buffers -------------------------------------------------------
     def encode_icm(self, X, B, K, m, ilsiters, icmiter, npert, randord, seed=0, nsplits=1, global_offset=0,
                    verbose=False, h=H):

@@ -191,7 +191,8 @@ def test_short_and_600_iteration_encodes_in_the_other_orders(lsq, oracle, order)
 
 def test_panel_upload_pipeline_then_the_one_piece_upload_on_one_context(walk):
     """A host-buffer encode through the panel upload pipeline, then the same call with the pipeline off on the same context: both equal the oracle (the
-    baseline's check) and the fresh context's counters -- as far as the level parameters the pipeline leaves behind can be reached without a hook."""
+    baseline's check) and the fresh context's counters.  (The level parameters the pipeline leaves behind are held to their bound by
+    tests/test_gpu_q16_bound.py, case host_sample, through lsq_get_q16_snapshot.)"""
     op = walk.ops["encode_icm"]
     inp = walk.inputs_for(op.name, 1)
     n, d, m = inp["shape"]
