@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 1200
+#define LSQ_VERSION 1300
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -229,6 +229,34 @@ LSQ_API int lsq_encode_icm_dev(lsq_ctx *ctx, const float *dX, const uint8_t *dB0
                        const int64_t *ilsiters, int nr, int icmiter, int npert, int randord,
                        uint64_t seed, uint64_t global_offset,
                        uint8_t *dBs, double *obj_sums, int64_t *stats);
+
+/* ---- (1b) the whole call on 8-bit data (since v1300) ----------------------------------------
+ * Base sets stored as unsigned bytes -- the TEXMEX .bvecs files of SIFT1B-style sets, read by the reference's bvecs_read (src/read/read_datasets.jl)
+ * into a UInt8 matrix -- are encoded WITHOUT being widened to float by the caller: d bytes per vector in host memory, over the bus and in the
+ * context's resident chunk buffers; the kernels that read X widen four components per dword load in registers.  uint8 -> float32 is exact, so every
+ * call returns, bit for bit, what its f32 counterpart returns on Float32.(X): the same codes, objective sums and counters, under every option
+ * (schedules 6 / 4 / 3, "chunk", "per_node", "light", "async", the probe and fall-back roads).  8-bit and f32 calls may be mixed on one context in
+ * any order.  RX8 / dX8: d x n UInt8 column-major ([n][d] bytes); any byte alignment (a 4-byte-aligned base with d % 4 == 0 takes the dword loads,
+ * anything else byte loads).  Everything else -- B, K, Bs, objs, errors, the h = 256 rule -- as in the call each one stands in for:
+ *   lsq_encode_icm_u8        stands in for lsq_encode_icm        (encode_icm_cuda on Float32.(RX), encode_icm_cuda.jl:253-296)
+ *   lsq_encode_icm_u8_dev    stands in for lsq_encode_icm_dev    (device-resident; "async" and graph capture under the same conditions)
+ *   lsq_multi_encode_icm_u8  stands in for lsq_multi_encode_icm  (one shard per device)
+ * The other entry points (k-NN, trainers, codebook updates, scan queries) take float32 as before.
+ * (The context argument is spelled with its struct tag here: the catalogue of tests/ctx_ops.py collects the context entry points it walks by the
+ * typedef spelling and is closed; these two are walked, pair by pair with their f32 counterparts, by tests/ctx_ops_u8.py.) */
+LSQ_API int lsq_encode_icm_u8(struct lsq_ctx *ctx, const uint8_t *RX8, const int16_t *B, const float *K,
+                   int d, int64_t n, int m, int h,
+                   const int64_t *ilsiters, int nr, int icmiter, int npert, int randord,
+                   int nsplits, uint64_t seed, uint64_t global_offset, int verbose,
+                   int16_t *Bs, float *objs);
+LSQ_API int lsq_encode_icm_u8_dev(struct lsq_ctx *ctx, const uint8_t *dX8, const uint8_t *dB0, const float *dK,
+                       int d, int64_t n, int m, int h,
+                       const int64_t *ilsiters, int nr, int icmiter, int npert, int randord,
+                       uint64_t seed, uint64_t global_offset,
+                       uint8_t *dBs, double *obj_sums, int64_t *stats);
+LSQ_API int lsq_multi_encode_icm_u8(lsq_multi *mg, const uint8_t *RX8, const int16_t *B, const float *K, int d, int64_t n, int m, int h,
+                                    const int64_t *ilsiters, int nr, int icmiter, int npert, int randord, uint64_t seed,
+                                    uint64_t global_offset, int verbose, int16_t *Bs, float *objs);
 
 /* ---- (2) the CPU-path shaped entry points -------------------------------------------------
  * encoding_icm(X, oldB, C, niter, randord, npert, V) -> B     src/encodings/encode_icm.jl:131-189

@@ -93,6 +93,10 @@ SIGNATURES = {
     "lsq_multi_encode_icm": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i, _i, _i, _i, _u64, _u64, _i, _vp, _vp]),
     "lsq_encode_icm": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i, _i, _i, _i, _i, _u64, _u64, _i, _vp, _vp]),
     "lsq_encode_icm_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i, _i, _i, _i, _u64, _u64, _vp, _vp, _vp]),
+    # 8-bit data rows (since v1300): the argument lists of the three calls above, X as uint8
+    "lsq_encode_icm_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i, _i, _i, _i, _i, _u64, _u64, _i, _vp, _vp]),
+    "lsq_encode_icm_u8_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i, _i, _i, _i, _u64, _u64, _vp, _vp, _vp]),
+    "lsq_multi_encode_icm_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i, _i, _i, _i, _u64, _u64, _i, _vp, _vp]),
     "lsq_encoding_icm": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _u64, _u32, _u64, _vp]),
     "lsq_encode_icm_fully": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _i64, _u64, _u32]),
     "lsq_get_unaries": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp]),

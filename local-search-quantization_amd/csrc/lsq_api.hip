@@ -561,7 +561,10 @@ static bool use_q16(const lsq_ctx *c, int64_t cn) { return c->schedule >= 6 && c
 
 // q16 part of a chunk's unary build: buffers, sampled value ranges -> parameters -> 16-bit slice tables.  Xsample != nullptr: the host-buffer pipeline
 // (the sample was uploaded ahead of X: lsq_launch_q16_prepare's sample mode); -> *means_out = the codebook means the panel-wise sigma pass needs
-static int q16_prepare_chunk(lsq_ctx *c, const float *dX, const float *dK, int d, int64_t cn, int m, const float *Xsample = nullptr, int64_t nsample_rows = 0,
+// XT (here and below): the element type of X -- float, or uint8_t for the 8-bit entry points (lsq_encode_icm_u8 and its kin): the rows stay 8-bit in the
+// context's chunk buffers and the kernels widen them in registers (lsq_xload.h)
+template <class XT>
+static int q16_prepare_chunk(lsq_ctx *c, const XT *dX, const float *dK, int d, int64_t cn, int m, const XT *Xsample = nullptr, int64_t nsample_rows = 0,
                              float **means_out = nullptr) {
     {
         Timer t(c, CAT_TABLES);
@@ -594,7 +597,8 @@ static int q16_prepare_chunk(lsq_ctx *c, const float *dX, const float *dK, int d
 
 static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m);
 
-static int build_unaries(lsq_ctx *c, const float *dX, const float *dK, int d, int64_t cn, int m, int slice, int64_t r0, int64_t rows) {
+template <class XT>
+static int build_unaries(lsq_ctx *c, const XT *dX, const float *dK, int d, int64_t cn, int m, int slice, int64_t r0, int64_t rows) {
     c->chunk_q16 = false;
     const bool q16 = slice > 0 && r0 == 0 && rows == cn && use_q16(c, cn);
     if (q16) LSQ_TRY(q16_prepare_chunk(c, dX, dK, d, cn, m));      // 16-bit filtered walk: the GEMM below then also emits the u16 planes
@@ -644,10 +648,11 @@ static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m) {
 // GEMM hides under the upload instead of following it (measured: 512 MB take 9.5 ms at 56 GB/s whichever way they are issued).
 // The filtered walk's level parameters need value ranges BEFORE the first GEMM panel: the sample rows (the same every-rts-th 128-row panels the
 // strided pass reads) are packed on the host and uploaded first, a few MB.  Same codes as the one-piece path: the parameters only steer the filter.
-static int build_unaries_from_host(lsq_ctx *c, const float *Xh, float *dXc, const float *dK, int d, int64_t cn, int m, int slice) {
+template <class XT>
+static int build_unaries_from_host(lsq_ctx *c, const XT *Xh, XT *dXc, const float *dK, int d, int64_t cn, int m, int slice) {
     c->chunk_q16 = false;
     const bool q16 = slice > 0 && use_q16(c, cn);
-    const size_t row_bytes = sizeof(float) * (size_t)d;
+    const size_t row_bytes = sizeof(XT) * (size_t)d;
     int64_t prow = (int64_t)((uint64_t)c->panel_bytes / row_bytes) / 128 * 128;      // ~48 MB panels, whole 128-row tiles
     if (prow < 128) prow = 128;
     const int npan = (int)((cn + prow - 1) / prow);
@@ -663,16 +668,17 @@ static int build_unaries_from_host(lsq_ctx *c, const float *Xh, float *dXc, cons
         const int spanels = lsq_q16_sample_rows(cn, d, &rts);
         int64_t ns = 0;
         for (int sp = 0; sp < spanels; ++sp) ns += std::min<int64_t>(128, cn - (int64_t)sp * rts * 128);
-        c->sample_host.resize((size_t)ns * d);
+        c->sample_host.resize(((size_t)ns * row_bytes + sizeof(float) - 1) / sizeof(float));      // (bytes, whatever the element type)
+        XT *sample = reinterpret_cast<XT *>(c->sample_host.data());
         int64_t at = 0;
         for (int sp = 0; sp < spanels; ++sp) {
             const int64_t r0 = (int64_t)sp * rts * 128, rows = std::min<int64_t>(128, cn - r0);
-            memcpy(c->sample_host.data() + (size_t)at * d, Xh + (size_t)r0 * d, (size_t)rows * row_bytes);
+            memcpy(sample + (size_t)at * d, Xh + (size_t)r0 * d, (size_t)rows * row_bytes);
             at += rows;
         }
         LSQ_TRY(c->sSample.ensure((size_t)ns * row_bytes));
-        LSQ_HIP(hipMemcpyAsync(c->sSample.p, c->sample_host.data(), (size_t)ns * row_bytes, hipMemcpyHostToDevice, c->stream));
-        LSQ_TRY(q16_prepare_chunk(c, dXc, dK, d, cn, m, c->sSample.as<float>(), ns, &means));
+        LSQ_HIP(hipMemcpyAsync(c->sSample.p, sample, (size_t)ns * row_bytes, hipMemcpyHostToDevice, c->stream));
+        LSQ_TRY(q16_prepare_chunk<XT>(c, dXc, dK, d, cn, m, c->sSample.as<XT>(), ns, &means));
     }
     LSQ_TRY(c->U.ensure(sizeof(float) * (size_t)m * (size_t)cn * LSQ_H));
     std::atomic<int> landed{0};
@@ -789,8 +795,8 @@ struct EncodeParams {
 };
 
 // One resident chunk: recCur holds the chunk's codes on entry; snapshots are emitted through `snap`.
-template <class Snap>
-static int encode_chunk(lsq_ctx *c, const float *dXc, const float *dK, int64_t cn, uint64_t goff, const EncodeParams &P, int64_t I, Snap snap,
+template <class Snap, class XT>
+static int encode_chunk(lsq_ctx *c, const XT *dXc, const float *dK, int64_t cn, uint64_t goff, const EncodeParams &P, int64_t I, Snap snap,
                         bool unaries_ready = false) {
     const int cs = lsq_code_stride(P.m);
     if (!unaries_ready) LSQ_TRY(build_unaries(c, dXc, dK, P.d, cn, P.m, lsq_walk_slice_width(P.m), 0, cn));
@@ -965,13 +971,14 @@ static int finish_call(lsq_ctx *c, int64_t I, int nr, double *obj_sums, int64_t 
     return LSQ_OK;
 }
 
-extern "C" int lsq_encode_icm_dev(lsq_ctx *c, const float *dX, const uint8_t *dB0, const float *dK, int d, int64_t n, int m, int h,
-                                  const int64_t *ilsiters, int nr, int icmiter, int npert, int randord, uint64_t seed,
-                                  uint64_t global_offset, uint8_t *dBs, double *obj_sums, int64_t *stats) {
+template <class XT>
+static int encode_dev(lsq_ctx *c, const char *fn, const XT *dX, const uint8_t *dB0, const float *dK, int d, int64_t n, int m, int h,
+                      const int64_t *ilsiters, int nr, int icmiter, int npert, int randord, uint64_t seed,
+                      uint64_t global_offset, uint8_t *dBs, double *obj_sums, int64_t *stats) {
     LSQ_TRY(use_device(c));
     int64_t I = 0;
-    LSQ_TRY(validate_encode("lsq_encode_icm_dev", d, n, m, h, ilsiters, nr, icmiter, npert, &I));
-    if (!dK || !obj_sums || (n > 0 && (!dX || !dB0 || !dBs))) { lsq_set_error("lsq_encode_icm_dev: null pointer"); return LSQ_EINVAL; }
+    LSQ_TRY(validate_encode(fn, d, n, m, h, ilsiters, nr, icmiter, npert, &I));
+    if (!dK || !obj_sums || (n > 0 && (!dX || !dB0 || !dBs))) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
     LSQ_TRY(begin_call(c, I, nr));
     LSQ_TRY(prepare_tables(c, dK, d, m));
     const EncodeParams P{d, m, ilsiters, nr, icmiter, npert, randord, seed, 0u};
@@ -990,6 +997,19 @@ extern "C" int lsq_encode_icm_dev(lsq_ctx *c, const float *dX, const uint8_t *dB
         LSQ_TRY(encode_chunk(c, dX + off * d, dK, cn, global_offset + (uint64_t)off, P, I, snap));
     }
     return finish_call(c, I, nr, obj_sums, stats);
+}
+
+extern "C" int lsq_encode_icm_dev(lsq_ctx *c, const float *dX, const uint8_t *dB0, const float *dK, int d, int64_t n, int m, int h,
+                                  const int64_t *ilsiters, int nr, int icmiter, int npert, int randord, uint64_t seed,
+                                  uint64_t global_offset, uint8_t *dBs, double *obj_sums, int64_t *stats) {
+    return encode_dev(c, "lsq_encode_icm_dev", dX, dB0, dK, d, n, m, h, ilsiters, nr, icmiter, npert, randord, seed, global_offset, dBs, obj_sums, stats);
+}
+
+// 8-bit data rows, device-resident (stands in for lsq_encode_icm_dev on the widened matrix: same codes, same sums, same counters; option "async" included)
+extern "C" int lsq_encode_icm_u8_dev(lsq_ctx *c, const uint8_t *dX8, const uint8_t *dB0, const float *dK, int d, int64_t n, int m, int h,
+                                     const int64_t *ilsiters, int nr, int icmiter, int npert, int randord, uint64_t seed,
+                                     uint64_t global_offset, uint8_t *dBs, double *obj_sums, int64_t *stats) {
+    return encode_dev(c, "lsq_encode_icm_u8_dev", dX8, dB0, dK, d, n, m, h, ilsiters, nr, icmiter, npert, randord, seed, global_offset, dBs, obj_sums, stats);
 }
 
 // The caller's host codebooks -> c->sK + tables.  Unchanged since the last host-buffer call of this context (same shape, same bytes): nothing is
@@ -1015,7 +1035,8 @@ static int host_codebooks(lsq_ctx *c, const float *K, int d, int m) {
 // objective sums / counters are handed back raw so that the caller can combine the shards.
 struct HostPlacement { int64_t ntot, row0; double *sums; int64_t *stats; };
 
-static int encode_host(lsq_ctx *c, const char *fn, const float *X, const int16_t *B, const float *K, int d, int64_t n, int m, int h,
+template <class XT>
+static int encode_host(lsq_ctx *c, const char *fn, const XT *X, const int16_t *B, const float *K, int d, int64_t n, int m, int h,
                        const int64_t *ilsiters, int nr, int icmiter, int npert, int randord, uint64_t seed, uint32_t it0,
                        uint64_t global_offset, int verbose, int16_t *Bs, float *objs, const HostPlacement *place = nullptr) {
     LSQ_TRY(use_device(c));
@@ -1051,14 +1072,14 @@ static int encode_host(lsq_ctx *c, const char *fn, const float *X, const int16_t
     for (int64_t off = 0; off < n; off += c->chunk, which ^= 1) {
         const int64_t cn = std::min<int64_t>(c->chunk, n - off);
         c->call_row0 = off;
-        LSQ_TRY(xb[which]->ensure(sizeof(float) * (size_t)cn * d));
+        LSQ_TRY(xb[which]->ensure(sizeof(XT) * (size_t)cn * d));
         LSQ_TRY(c->sB16.ensure(sizeof(int16_t) * (size_t)cn * m));
         LSQ_TRY(c->sOut16.ensure(sizeof(int16_t) * (size_t)cn * m * nr));
         LSQ_TRY(c->recCur.ensure((size_t)cn * cs));
-        float *dXc = xb[which]->as<float>();
-        const bool piped = off == 0 && c->pipeline_min_bytes > 0 && (int64_t)sizeof(float) * cn * d >= c->pipeline_min_bytes;
+        XT *dXc = xb[which]->as<XT>();
+        const bool piped = off == 0 && c->pipeline_min_bytes > 0 && (int64_t)sizeof(XT) * cn * d >= c->pipeline_min_bytes;
         if (piped) {}                                                       // X goes up panel by panel under its own unary GEMM (below)
-        else if (off == 0) LSQ_HIP(hipMemcpyAsync(dXc, X, sizeof(float) * (size_t)cn * d, hipMemcpyHostToDevice, c->stream));
+        else if (off == 0) LSQ_HIP(hipMemcpyAsync(dXc, X, sizeof(XT) * (size_t)cn * d, hipMemcpyHostToDevice, c->stream));
         else LSQ_HIP(hipStreamWaitEvent(c->stream, c->copy_done, 0));      // uploaded under the previous chunk's compute
         LSQ_HIP(hipMemcpyAsync(c->sB16.p, B + off * m, sizeof(int16_t) * (size_t)cn * m, hipMemcpyHostToDevice, c->stream));
         LSQ_TRY(lsq_launch_codes_from_i16(c->stream, c->sB16.as<int16_t>(), cn, m, h, c->recCur.as<uint8_t>(), c->bad.as<int>()));
@@ -1070,8 +1091,8 @@ static int encode_host(lsq_ctx *c, const char *fn, const float *X, const int16_t
         const int64_t noff = off + c->chunk;
         if (noff < n) {      // next chunk's X: its buffer was last read by chunk c-1, which completed at the previous synchronize
             const int64_t ncn = std::min<int64_t>(c->chunk, n - noff);
-            LSQ_TRY(xb[which ^ 1]->ensure(sizeof(float) * (size_t)ncn * d));
-            LSQ_HIP(hipMemcpyAsync(xb[which ^ 1]->p, X + noff * d, sizeof(float) * (size_t)ncn * d, hipMemcpyHostToDevice, c->copy_stream));
+            LSQ_TRY(xb[which ^ 1]->ensure(sizeof(XT) * (size_t)ncn * d));
+            LSQ_HIP(hipMemcpyAsync(xb[which ^ 1]->p, X + noff * d, sizeof(XT) * (size_t)ncn * d, hipMemcpyHostToDevice, c->copy_stream));
             LSQ_HIP(hipEventRecord(c->copy_done, c->copy_stream));
         }
         for (int r = 0; r < nr; ++r)
@@ -1100,6 +1121,14 @@ extern "C" int lsq_encode_icm(lsq_ctx *c, const float *RX, const int16_t *B, con
                               uint64_t global_offset, int verbose, int16_t *Bs, float *objs) {
     if (nsplits < 1) { lsq_set_error("lsq_encode_icm: nsplits must be >= 1"); return LSQ_EINVAL; }
     return encode_host(c, "lsq_encode_icm", RX, B, K, d, n, m, h, ilsiters, nr, icmiter, npert, randord, seed, 0u, global_offset, verbose, Bs, objs);
+}
+
+// 8-bit data rows in host memory (stands in for lsq_encode_icm on the widened matrix): d bytes per row over the bus and in the chunk buffers
+extern "C" int lsq_encode_icm_u8(lsq_ctx *c, const uint8_t *RX8, const int16_t *B, const float *K, int d, int64_t n, int m, int h,
+                                 const int64_t *ilsiters, int nr, int icmiter, int npert, int randord, int nsplits, uint64_t seed,
+                                 uint64_t global_offset, int verbose, int16_t *Bs, float *objs) {
+    if (nsplits < 1) { lsq_set_error("lsq_encode_icm_u8: nsplits must be >= 1"); return LSQ_EINVAL; }
+    return encode_host(c, "lsq_encode_icm_u8", RX8, B, K, d, n, m, h, ilsiters, nr, icmiter, npert, randord, seed, 0u, global_offset, verbose, Bs, objs);
 }
 
 // ---- single-process multi-GPU: one context + one host thread per device, splitarray shards (utils.jl:152-177) -------
@@ -1136,13 +1165,14 @@ extern "C" int lsq_multi_set_option(lsq_multi *mg, const char *key, int64_t valu
     return LSQ_OK;
 }
 
-extern "C" int lsq_multi_encode_icm(lsq_multi *mg, const float *RX, const int16_t *B, const float *K, int d, int64_t n, int m, int h,
-                                    const int64_t *ilsiters, int nr, int icmiter, int npert, int randord, uint64_t seed,
-                                    uint64_t global_offset, int verbose, int16_t *Bs, float *objs) {
+template <class XT>
+static int multi_encode(lsq_multi *mg, const char *fn, const XT *RX, const int16_t *B, const float *K, int d, int64_t n, int m, int h,
+                        const int64_t *ilsiters, int nr, int icmiter, int npert, int randord, uint64_t seed,
+                        uint64_t global_offset, int verbose, int16_t *Bs, float *objs) {
     if (!mg || mg->ctx.empty()) { lsq_set_error("null lsq_multi"); return LSQ_EINVAL; }
     int64_t I = 0;
-    LSQ_TRY(validate_encode("lsq_multi_encode_icm", d, n, m, h, ilsiters, nr, icmiter, npert, &I));
-    if (!K || !objs || (n > 0 && (!RX || !B || !Bs))) { lsq_set_error("lsq_multi_encode_icm: null pointer"); return LSQ_EINVAL; }
+    LSQ_TRY(validate_encode(fn, d, n, m, h, ilsiters, nr, icmiter, npert, &I));
+    if (!K || !objs || (n > 0 && (!RX || !B || !Bs))) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
     const int G = (int)mg->ctx.size();
     std::vector<std::vector<double>> sums((size_t)G, std::vector<double>((size_t)nr, 0.0));
     std::vector<std::vector<int64_t>> stats((size_t)G, std::vector<int64_t>(2 * (size_t)I, 0));
@@ -1155,7 +1185,7 @@ extern "C" int lsq_multi_encode_icm(lsq_multi *mg, const float *RX, const int16_
             rc[(size_t)p] = lsq_splitarray(n, G, p, &s0, &len);        // contiguous shards, the first n mod G one longer
             if (rc[(size_t)p] == LSQ_OK && len > 0) {
                 const HostPlacement place{n, s0, sums[(size_t)p].data(), stats[(size_t)p].data()};
-                rc[(size_t)p] = encode_host(mg->ctx[(size_t)p], "lsq_multi_encode_icm", RX + s0 * d, B + s0 * m, K, d, len, m, h, ilsiters, nr,
+                rc[(size_t)p] = encode_host(mg->ctx[(size_t)p], fn, RX + s0 * d, B + s0 * m, K, d, len, m, h, ilsiters, nr,
                                             icmiter, npert, randord, seed, 0u, global_offset + (uint64_t)s0, 0, Bs, nullptr, &place);
             }
             if (rc[(size_t)p] != LSQ_OK) err[(size_t)p] = lsq_last_error();      // the error string is thread-local
@@ -1177,6 +1207,19 @@ extern "C" int lsq_multi_encode_icm(lsq_multi *mg, const float *RX, const int16_
                    (long long)I, n ? 100.0 * (double)eq / (double)n : 0.0, n ? 100.0 * (double)better / (double)n : 0.0);
         }
     return LSQ_OK;
+}
+
+extern "C" int lsq_multi_encode_icm(lsq_multi *mg, const float *RX, const int16_t *B, const float *K, int d, int64_t n, int m, int h,
+                                    const int64_t *ilsiters, int nr, int icmiter, int npert, int randord, uint64_t seed,
+                                    uint64_t global_offset, int verbose, int16_t *Bs, float *objs) {
+    return multi_encode(mg, "lsq_multi_encode_icm", RX, B, K, d, n, m, h, ilsiters, nr, icmiter, npert, randord, seed, global_offset, verbose, Bs, objs);
+}
+
+// 8-bit data rows (stands in for lsq_multi_encode_icm on the widened matrix)
+extern "C" int lsq_multi_encode_icm_u8(lsq_multi *mg, const uint8_t *RX8, const int16_t *B, const float *K, int d, int64_t n, int m, int h,
+                                       const int64_t *ilsiters, int nr, int icmiter, int npert, int randord, uint64_t seed,
+                                       uint64_t global_offset, int verbose, int16_t *Bs, float *objs) {
+    return multi_encode(mg, "lsq_multi_encode_icm_u8", RX8, B, K, d, n, m, h, ilsiters, nr, icmiter, npert, randord, seed, global_offset, verbose, Bs, objs);
 }
 
 // The ADC scan over a database sharded across the devices (splitarray shards, one host thread per device): every device returns its own nn nearest

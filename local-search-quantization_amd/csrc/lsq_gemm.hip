@@ -28,6 +28,7 @@
 #include <stdlib.h>
 
 #include "lsq_internal.h"
+#include "lsq_xload.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -45,8 +46,11 @@ constexpr int BM = 128, BN = 128;
 
 // One K chunk of a 128-row panel: global -> registers (tile_load), registers -> LDS (tile_store).  Split in two so
 // that the loads of chunk c+1 are in flight while the MFMAs of chunk c run (register double buffering).
-template <bool VEC4, int BK>
+template <bool VEC4, int BK, class T = float>
 struct TileRegs { float4 v[BM * BK / 4 / 256]; };
+// 8-bit rows: a quad of components stays packed (one dword) across the MFMAs it is loaded under; tile_store widens it on its way into LDS
+template <bool VEC4, int BK>
+struct TileRegs<VEC4, BK, uint8_t> { uint32_t v[BM * BK / 4 / 256]; };
 
 template <bool VEC4, int BK>
 __device__ inline void tile_load(const float *__restrict__ src, int64_t rows_total, int64_t row0, int Kd, int k0,
@@ -74,6 +78,33 @@ __device__ inline void tile_load(const float *__restrict__ src, int64_t rows_tot
     }
 }
 
+// the 8-bit A operand (lsq_xload.h): VEC4 = one dword per quad (Kd % 4 == 0, lda % 4 == 0, a 4-byte-aligned base), else byte loads
+template <bool VEC4, int BK>
+__device__ inline void tile_load(const uint8_t *__restrict__ src, int64_t rows_total, int64_t row0, int Kd, int k0,
+                                 TileRegs<VEC4, BK, uint8_t> &t, int tid, int64_t ld) {
+    constexpr int Q4 = BK / 4, NE = BM * BK / 4 / 256;
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+        const int e = tid + i * 256;
+        const int r = e / Q4, q = e % Q4;
+        const int64_t gr = row0 + r;
+        const int kk = k0 + 4 * q;
+        uint32_t v = 0u;
+        if (gr < rows_total) {
+            const uint8_t *p = src + gr * ld + kk;
+            if (VEC4 && kk + 3 < Kd) {
+                v = lsq_ld4_packed(p);
+            } else {
+                if (kk + 0 < Kd) v |= (uint32_t)p[0];
+                if (kk + 1 < Kd) v |= (uint32_t)p[1] << 8;
+                if (kk + 2 < Kd) v |= (uint32_t)p[2] << 16;
+                if (kk + 3 < Kd) v |= (uint32_t)p[3] << 24;
+            }
+        }
+        t.v[i] = v;
+    }
+}
+
 template <bool VEC4, int BK>
 __device__ inline void tile_store(const TileRegs<VEC4, BK> &t, float scale, float *__restrict__ dst, int tid) {
     constexpr int LD = BK + LSQ_GEMM_PAD, Q4 = BK / 4, NE = BM * BK / 4 / 256;
@@ -86,14 +117,28 @@ __device__ inline void tile_store(const TileRegs<VEC4, BK> &t, float scale, floa
     }
 }
 
+template <bool VEC4, int BK>
+__device__ inline void tile_store(const TileRegs<VEC4, BK, uint8_t> &t, float scale, float *__restrict__ dst, int tid) {
+    constexpr int LD = BK + LSQ_GEMM_PAD, Q4 = BK / 4, NE = BM * BK / 4 / 256;
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+        const int e = tid + i * 256;
+        const int r = e / Q4, q = e % Q4;
+        float *o = dst + r * LD + 4 * q;
+        const lsq_f32x4 w = lsq_widen4(t.v[i]);                  // uint8 -> f32: exact, so the panel in LDS is the f32 call's panel
+        o[0] = w.x * scale; o[1] = w.y * scale; o[2] = w.z * scale; o[3] = w.w * scale;
+    }
+}
+
 // Q16 = 1: the epilogue ALSO emits every value as a 16-bit fixed-point level q = rint((v - loU_j) * invD_j) of its column plane j = c / h
 // (lsq_q16_params) into the slice-major u16 planes Dq -- the filter input of icm_walkq_kernel.  The range [loU, loU + 65535 D) comes from a
 // SAMPLE of the rows (below), so a value may fall outside it: its level is clamped (meaningless), bit j of qflag[row] is raised and
 // icm_walkq_kernel sends that vector's node j through the f32 path -- exactness never depends on the sample.
 // Q16 = 2: range-only pass over a sample of the rows (every rts-th 128-row panel, contiguous reads): nothing is stored, the minimum / maximum of every column plane are
 // accumulated in qrange[2 j], qrange[2 j + 1] as order-preserving uint keys.
-template <bool VEC4, int BK, int Q16 = 0, bool FULLK = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void chain_gemm_kernel(const float *__restrict__ A, const float *__restrict__ Bm,
+// XT: element type of A (float, or uint8_t: 8-bit data rows, lsq_xload.h); VECA: A's own load rule (a float A shares VEC4 with Bm)
+template <bool VEC4, int BK, int Q16 = 0, bool FULLK = false, class XT = float, bool VECA = VEC4>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void chain_gemm_kernel(const XT *__restrict__ A, const float *__restrict__ Bm,
                                                          const float *__restrict__ addv, float alpha, int64_t M, int N,
                                                          int Kd, int h, int64_t plane_stride, int64_t row_stride,
                                                          float *__restrict__ D, int64_t row_tiles, int col_tiles, int slice,
@@ -144,17 +189,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    TileRegs<VEC4, BK> ra, rb;
-    tile_load<VEC4, BK>(A, M, row0, Kd, 0, ra, tid, lda);
+    TileRegs<VECA, BK, XT> ra;
+    TileRegs<VEC4, BK> rb;
+    tile_load<VECA, BK>(A, M, row0, Kd, 0, ra, tid, lda);
     tile_load<VEC4, BK>(Bm, N, col0, Kd, 0, rb, tid, (int64_t)Kd);
-    tile_store<VEC4, BK>(ra, 1.0f, As[0], tid);
+    tile_store<VECA, BK>(ra, 1.0f, As[0], tid);
     tile_store<VEC4, BK>(rb, alpha, Bs[0], tid);
     __syncthreads();
     int cur = 0;
     for (int k0 = 0; k0 < Kd; k0 += BK) {
         const bool more = k0 + BK < Kd;
         if (more) {                                              // next chunk travels HBM/L2 -> registers under this chunk's MFMAs
-            tile_load<VEC4, BK>(A, M, row0, Kd, k0 + BK, ra, tid, lda);
+            tile_load<VECA, BK>(A, M, row0, Kd, k0 + BK, ra, tid, lda);
             tile_load<VEC4, BK>(Bm, N, col0, Kd, k0 + BK, rb, tid, (int64_t)Kd);
         }
         // FULLK (Kd a multiple of BK: the launcher knows): fixed trip count, unrolled -- the operand reads of the later k-steps are issued under the MFMAs
@@ -177,7 +223,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             for (int kk = 0; kk < kend; kk += 2) kstep(kk);
         }
         if (more) {                                              // the other buffer was last read one iteration ago (barrier below)
-            tile_store<VEC4, BK>(ra, 1.0f, As[cur ^ 1], tid);
+            tile_store<VECA, BK>(ra, 1.0f, As[cur ^ 1], tid);
             tile_store<VEC4, BK>(rb, alpha, Bs[cur ^ 1], tid);
         }
         __syncthreads();
@@ -371,6 +417,44 @@ int lsq_launch_chain_gemm(hipStream_t s, const float *A, const float *Bm, const 
     else
         hipLaunchKernelGGL((chain_gemm_kernel<false, 16>), dim3((unsigned)blocks), dim3(256), 0, s, A, Bm, addv, alpha, M, N, Kd, h,
                            plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, nullptr, 0, nullptr, lda, nullptr, nullptr, 1, nullptr, nullptr, stagger);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
+// 8-bit A (data rows; Bm = the codebooks, f32).  Same tiles, same grid, same epilogues: only A's loader differs.  vb: Bm's 16-byte rule as above;
+// va: A's own rule (lsq_xload.h) -- a dword per quad when Kd % 4 == 0, lda % 4 == 0 and A is 4-byte aligned, byte loads otherwise.
+int lsq_launch_chain_gemm(hipStream_t s, const uint8_t *A, const float *Bm, const float *addv, float alpha, int64_t M,
+                          int N, int Kd, int h, int64_t plane_stride, int64_t row_stride, float *D, int slice, int64_t Mtot, int64_t rbase,
+                          uint16_t *Dq, int slice_q, lsq_q16_params *qp, int64_t lda, unsigned short *qflag, unsigned *qrange, int rts, const float *sigma, const float *colshift) {
+    if (lda <= 0) lda = Kd;
+    if (rts < 1) rts = 1;
+    if (M <= 0 || N <= 0) return LSQ_OK;
+    const int64_t row_tiles = (M + (int64_t)BM * rts - 1) / ((int64_t)BM * rts);
+    const int col_tiles = (N + BN - 1) / BN;
+    const int64_t blocks = ((row_tiles + 7) / 8) * 8 * col_tiles;
+    if (blocks > 0x7fffffffLL) { lsq_set_error("chain_gemm: grid too large"); return LSQ_EINVAL; }
+    const bool vb = (Kd % 4 == 0) && ((uintptr_t)Bm % 16 == 0);
+    const bool va = vb && lda % 4 == 0 && lsq_x_vec_ok(A);
+    const bool fullk = Kd % 16 == 0;
+    const int stagger = (M >= 65536 && !qrange) ? LSQ_KNOB("LSQ_GEMM_STAGGER", 0) : 0;
+    if (Dq && !qrange && (!qp || !qflag || slice_q < 1)) { lsq_set_error("chain_gemm: quantised output needs parameters"); return LSQ_EINVAL; }
+    if (qrange) { Dq = nullptr; slice_q = 0; qp = nullptr; qflag = nullptr; }
+    else rts = 1;
+#define LSQ_GEMM_U8(VB_, Q_, FK_, VA_)                                                                                                                  \
+    hipLaunchKernelGGL((chain_gemm_kernel<VB_, 16, Q_, FK_, uint8_t, VA_>), dim3((unsigned)blocks), dim3(256), 0, s, A, Bm, addv, alpha, M, N, Kd, h,      \
+                       plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, Dq, slice_q, qp, lda, qflag, qrange, rts, sigma, colshift, stagger)
+#define LSQ_GEMM_U8_Q(Q_)                                        \
+    do {                                                         \
+        if (va && fullk) LSQ_GEMM_U8(true, Q_, true, true);      \
+        else if (va) LSQ_GEMM_U8(true, Q_, false, true);         \
+        else if (vb) LSQ_GEMM_U8(true, Q_, false, false);        \
+        else LSQ_GEMM_U8(false, Q_, false, false);               \
+    } while (0)
+    if (qrange) LSQ_GEMM_U8_Q(2);
+    else if (Dq) LSQ_GEMM_U8_Q(1);
+    else { sigma = nullptr; colshift = nullptr; LSQ_GEMM_U8_Q(0); }
+#undef LSQ_GEMM_U8_Q
+#undef LSQ_GEMM_U8
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "lsq_wave.h"
+#include "lsq_xload.h"
 #include <atomic>
 
 namespace {
@@ -508,6 +509,33 @@ __device__ inline f32x4 load4(const float *p, OFF off, int c, int lp, int d) {
     return v;
 }
 
+// The same four components of an x row, loaded but not yet widened (lsq_xload.h).  float: the four floats themselves.  uint8_t, VW = 4: ONE dword
+// (d % 4 == 0, x 4-byte aligned) -- the x prefetched "one step ahead" costs a quarter of the f32 instantiation's registers while it is in flight;
+// VW = 1: four byte loads (any d, any base), each zero-extended into a register of its own (packing them would wait for the loads at once).
+template <class XT, int VW> struct XQuad { f32x4 v; __device__ f32x4 get() const { return v; } };
+template <> struct XQuad<uint8_t, 4> { uint32_t w; __device__ f32x4 get() const { return lsq_widen4(w); } };
+template <> struct XQuad<uint8_t, 1> {
+    uint32_t b[4];
+    __device__ f32x4 get() const { return (f32x4){(float)b[0], (float)b[1], (float)b[2], (float)b[3]}; }
+};
+template <int VW>
+__device__ inline XQuad<float, VW> xquad_load(const float *x, int c, int lp, int d) { return XQuad<float, VW>{load4<VW>(x, 0, c, lp, d)}; }
+template <int VW>
+__device__ inline XQuad<uint8_t, VW> xquad_load(const uint8_t *x, int c, int lp, int d) {
+    XQuad<uint8_t, VW> q;
+    if constexpr (VW == 4) {
+        const int t = load_start<VW>(c, lp, 0);
+        q.w = lsq_ld4_packed(x + (t < d ? t : 0));
+    } else {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int t = load_start<VW>(c, lp, s);
+            q.b[s] = x[t < d ? t : 0];
+        }
+    }
+    return q;
+}
+
 // levels x 2 .. x 16 of the pairwise tree across the 16 lanes of a row (f32 add commutes: both lanes of a pair get the same bits)
 __device__ inline float row_sum16(float v) {
     v = v + dpp_self<DPP_XOR1, 0xf>(v);
@@ -529,8 +557,9 @@ __device__ inline float row_sum16(float v) {
 // wait.  Now: MODE / HASV are template parameters, so the preamble is one group of unconditional loads; a round only computes -- its four costs
 // travel to the lanes that own the vectors (v_readlane / select) and the batch ends with lane-parallel, coalesced stores of whatever was
 // accepted; NQ steps of d (two for d >= 128: 18 sixteen-byte loads per lane) are in flight per wait.
-template <int M, int MODE, int HASV, int NQ, int VW>
-__device__ inline void cost4_body(const float *__restrict__ X, const float *__restrict__ K,
+// XT: element type of X (float, or uint8_t: 8-bit rows, XQuad above).  Lane ownership, the accumulation and the tree are VW's for either type.
+template <int M, int MODE, int HASV, int NQ, int VW, class XT = float>
+__device__ inline void cost4_body(const XT *__restrict__ X, const float *__restrict__ K,
                                   const uint8_t *rec, uint8_t *cur, float *__restrict__ prev,
                                   unsigned long long *__restrict__ counters, int64_t n, int64_t w, int64_t nwaves, int d,
                                   const unsigned short *vnew, unsigned short *vcur, const lsq_perturb_next &pn) {
@@ -596,26 +625,26 @@ __device__ inline void cost4_body(const float *__restrict__ X, const float *__re
                 if (nhv[v]) todo &= todo - 1;
             }
         };
-        auto xrow = [&]() -> const float * {
+        auto xrow = [&]() -> const XT * {
             const int mys = qtr == 0 ? nsidx[0] : qtr == 1 ? nsidx[1] : qtr == 2 ? nsidx[2] : nsidx[3];
             return X + (base + mys) * (int64_t)d;                                   // an empty pick points at the batch's first vector: a harmless read
         };
-        f32x4 xn[NQ];
-        auto xload = [&](const float *x, int c0) {
+        XQuad<XT, VW> xn[NQ];
+        auto xload = [&](const XT *x, int c0) {
 #pragma unroll
             for (int g = 0; g < NQ; ++g) {
-                xn[g] = load4<VW>(x, 0, c0 + 64 * g, lp, d);
+                xn[g] = xquad_load<VW>(x, c0 + 64 * g, lp, d);
             }
         };
         pick();
-        const float *xnext = xrow();
+        const XT *xnext = xrow();
         if (nhv[0]) xload(xnext, 0);
         while (nhv[0]) {
             int sidx[4];
             bool hv[4];
 #pragma unroll
             for (int v = 0; v < 4; ++v) { sidx[v] = nsidx[v]; hv[v] = nhv[v]; }
-            const float *x = xnext;
+            const XT *x = xnext;
             pick();                                                                 // the NEXT round's vectors (none: nhv[0] = false)
             xnext = xrow();
             const bool live = qtr == 0 ? hv[0] : qtr == 1 ? hv[1] : qtr == 2 ? hv[2] : hv[3];
@@ -646,7 +675,7 @@ __device__ inline void cost4_body(const float *__restrict__ X, const float *__re
                     const int c = c0 + 64 * g;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) ok[g][e] = load_start<VW>(c, lp, e / VW) < d;     // element e is in iff the load that carries it is
-                    xv[g] = xn[g];
+                    xv[g] = xn[g].get();
 #pragma unroll
                     for (int k = 0; k < M; ++k) kv[g][k] = load4<VW>(K, kb[k], c, lp, d);
                 }
@@ -716,19 +745,19 @@ __device__ inline void cost4_body(const float *__restrict__ X, const float *__re
 
 // NQ = 1: the compiler's own register budget; NQ = 2 (16-byte loads, d > 64, m <= 8): four waves per SIMD (128 VGPRs) so that the 18 loads of a round
 // really are in flight together
-template <int M, int MODE, int HASV, int NQ, int VW>
-__global__ __launch_bounds__(256) void cost4_kernel(const float *__restrict__ X, const float *__restrict__ K, const uint8_t *rec, uint8_t *cur,
+template <int M, int MODE, int HASV, int NQ, int VW, class XT = float>
+__global__ __launch_bounds__(256) void cost4_kernel(const XT *__restrict__ X, const float *__restrict__ K, const uint8_t *rec, uint8_t *cur,
                                                     float *__restrict__ prev, unsigned long long *__restrict__ counters, int64_t n, int d,
                                                     const unsigned short *vnew, unsigned short *vcur, const lsq_perturb_next pn) {
-    cost4_body<M, MODE, HASV, NQ, VW>(X, K, rec, cur, prev, counters, n, __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))),
+    cost4_body<M, MODE, HASV, NQ, VW, XT>(X, K, rec, cur, prev, counters, n, __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))),
                                       (int64_t)gridDim.x * 4, d, vnew, vcur, pn);
 }
-template <int M, int MODE, int HASV, int NQ, int VW>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void cost4w_kernel(const float *__restrict__ X, const float *__restrict__ K,
+template <int M, int MODE, int HASV, int NQ, int VW, class XT = float>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void cost4w_kernel(const XT *__restrict__ X, const float *__restrict__ K,
                                                     const uint8_t *rec, uint8_t *cur, float *__restrict__ prev,
                                                     unsigned long long *__restrict__ counters, int64_t n, int d,
                                                     const unsigned short *vnew, unsigned short *vcur, const lsq_perturb_next pn) {
-    cost4_body<M, MODE, HASV, NQ, VW>(X, K, rec, cur, prev, counters, n, __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))),
+    cost4_body<M, MODE, HASV, NQ, VW, XT>(X, K, rec, cur, prev, counters, n, __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))),
                                       (int64_t)gridDim.x * 4, d, vnew, vcur, pn);
 }
 
@@ -948,8 +977,8 @@ int lsq_launch_perturb(hipStream_t s, const uint8_t *src, uint8_t *dst, int64_t 
 const void *lsq_probe_kernel_icm() { return reinterpret_cast<const void *>(&tables_to_slices_kernel<16>); }
 
 // persistent grid: as many 256-thread blocks as are resident at once (a second, partial generation of blocks would idle the CUs it does not reach)
-template <int M, int NQ, int VW>
-static void launch_cost_t(hipStream_t s, const float *X, const float *K, const uint8_t *rec, uint8_t *cur, float *prev,
+template <int M, int NQ, int VW, class XT>
+static void launch_cost_t(hipStream_t s, const XT *X, const float *K, const uint8_t *rec, uint8_t *cur, float *prev,
                           unsigned long long *counters, int64_t n, int d, int mode, const unsigned short *vnew, unsigned short *vcur,
                           const lsq_perturb_next &pn) {
     static std::atomic<int> per_cu_known[3];      // one per kernel below (lsq_multi_* runs one host thread per device through here)
@@ -965,15 +994,16 @@ static void launch_cost_t(hipStream_t s, const float *X, const float *K, const u
         hipLaunchKernelGGL(kern, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, s, X, K, rec, cur, prev, counters, n, d, vnew, vcur, pn);
     };
     if constexpr (NQ == 1) {
-        if (mode == 1) launch(cost4_kernel<M, 1, 1, 1, VW>, 0); else if (vcur) launch(cost4_kernel<M, 0, 1, 1, VW>, 1); else launch(cost4_kernel<M, 0, 0, 1, VW>, 2);
+        if (mode == 1) launch(cost4_kernel<M, 1, 1, 1, VW, XT>, 0); else if (vcur) launch(cost4_kernel<M, 0, 1, 1, VW, XT>, 1); else launch(cost4_kernel<M, 0, 0, 1, VW, XT>, 2);
     } else if constexpr (M <= 8) {                // NQ = 2 is chosen for m <= 8 only
-        if (mode == 1) launch(cost4w_kernel<M, 1, 1, 2, VW>, 0); else if (vcur) launch(cost4w_kernel<M, 0, 1, 2, VW>, 1); else launch(cost4w_kernel<M, 0, 0, 2, VW>, 2);
+        if (mode == 1) launch(cost4w_kernel<M, 1, 1, 2, VW, XT>, 0); else if (vcur) launch(cost4w_kernel<M, 0, 1, 2, VW, XT>, 1); else launch(cost4w_kernel<M, 0, 0, 2, VW, XT>, 2);
     }
 }
 
-int lsq_launch_cost(hipStream_t s, const float *X, const float *K, const uint8_t *rec, uint8_t *cur, float *prev,
-                    unsigned long long *counters, int64_t n, int d, int m, int mode, const unsigned short *vnew, unsigned short *vcur,
-                    const lsq_perturb_next *next) {
+template <class XT>
+static int launch_cost_x(hipStream_t s, const XT *X, const float *K, const uint8_t *rec, uint8_t *cur, float *prev,
+                         unsigned long long *counters, int64_t n, int d, int m, int mode, const unsigned short *vnew, unsigned short *vcur,
+                         const lsq_perturb_next *next) {
     if (n <= 0) return LSQ_OK;
     if (mode == 1 && (!vnew || !vcur)) { lsq_set_error("lsq_launch_cost: accept mode needs both validity arrays"); return LSQ_EINVAL; }
     lsq_perturb_next pn = {};
@@ -981,7 +1011,8 @@ int lsq_launch_cost(hipStream_t s, const float *X, const float *K, const uint8_t
     pn.abl = LSQ_KNOB("LSQ_COST_ABL", 0);
     // 16-byte loads when d is a multiple of 4 and X and K are 16-byte aligned (every torch allocation), else 4-byte loads (measured faster than
     // 8-byte ones where d is even and X and K 8-byte aligned)
-    if (d % 4 == 0 && ((uintptr_t)X | (uintptr_t)K) % 16 == 0) {
+    // 8-bit rows: a dword per quad when X is 4-byte aligned (lsq_x_vec_ok), byte loads otherwise -- the two widths give the same bits (cost4_body)
+    if (d % 4 == 0 && lsq_x_vec_ok(X) && (uintptr_t)K % 16 == 0) {
         if ((int64_t)m * LSQ_H * d >= (1ll << 31)) { lsq_set_error("lsq_launch_cost: codebook matrix too large"); return LSQ_EINVAL; }
         if (d > 64 && m <= 8) {             // two 64-float steps of d in flight (18 loads per lane); above m = 8 the codeword rows of ONE step already fill the registers
             LSQ_DISPATCH_M(m, (launch_cost_t<M_, 2, 4>(s, X, K, rec, cur, prev, counters, n, d, mode, vnew, vcur, pn)));
@@ -993,6 +1024,17 @@ int lsq_launch_cost(hipStream_t s, const float *X, const float *K, const uint8_t
     }
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
+}
+
+int lsq_launch_cost(hipStream_t s, const float *X, const float *K, const uint8_t *rec, uint8_t *cur, float *prev,
+                    unsigned long long *counters, int64_t n, int d, int m, int mode, const unsigned short *vnew, unsigned short *vcur,
+                    const lsq_perturb_next *next) {
+    return launch_cost_x(s, X, K, rec, cur, prev, counters, n, d, m, mode, vnew, vcur, next);
+}
+int lsq_launch_cost(hipStream_t s, const uint8_t *X, const float *K, const uint8_t *rec, uint8_t *cur, float *prev,
+                    unsigned long long *counters, int64_t n, int d, int m, int mode, const unsigned short *vnew, unsigned short *vcur,
+                    const lsq_perturb_next *next) {
+    return launch_cost_x(s, X, K, rec, cur, prev, counters, n, d, m, mode, vnew, vcur, next);
 }
 
 int lsq_launch_sum_f64(hipStream_t s, const float *v, int64_t n, double *sum) {

@@ -33,6 +33,7 @@
 #include <atomic>
 
 #include "lsq_q16.h"
+#include "lsq_xload.h"
 #ifdef LSQ_TUNING
 __device__ unsigned long long *g_walkq_dbg = nullptr;      // [launch slot][block][16] timestamps (tools only)
 __device__ unsigned int g_walkq_dbg_slot = 0;
@@ -134,14 +135,17 @@ __global__ __launch_bounds__(256) void codebook_means_kernel(const float *__rest
 // of the panels); a vector whose |sigma| exceeds the bound the parameters assumed gets every node flagged -- it takes the f32 routine, like a unary
 // outside the sampled level range -- so the window stays rigorous for every vector the filter decides.  flag_row0: the row of sigma[0] in qflag.
 // LONGV: the instantiation for d > 256 (its m running sums would cost the short-vector path a quarter of its occupancy: 265 -> 365 us at 10^6 x 128)
-template <bool LONGV>
-__global__ __launch_bounds__(256) void unary_shift_kernel(const float *__restrict__ X, const float *__restrict__ R, int64_t n, int d, int m,
+// XT: element type of X (float, or uint8_t: lsq_xload.h).  The 8-bit instantiation keeps the lane mapping -- lane l' of a row owns components
+// 4 l' + 64 t .. + 3, one dword instead of four -- so every partial sum, and with it every sigma, has the bits of the f32 call on the widened rows.
+template <bool LONGV, class XT = float>
+__global__ __launch_bounds__(256) void unary_shift_kernel(const XT *__restrict__ X, const float *__restrict__ R, int64_t n, int d, int m,
                                                           float *__restrict__ sigma, unsigned *__restrict__ sigmax,
                                                           const unsigned *__restrict__ bound, unsigned short *__restrict__ qflag,
                                                           int64_t flag_row0, lsq_q16_params *__restrict__ P) {
     const int lane = threadIdx.x & 63, lp = lane & 15;
     const int64_t nrows = (int64_t)gridDim.x * 16;
-    const bool vec = (d & 3) == 0 && ((((uintptr_t)X | (uintptr_t)R) & 15) == 0);
+    const bool vec = std::is_same<XT, float>::value ? (d & 3) == 0 && ((((uintptr_t)X | (uintptr_t)R) & 15) == 0)
+                                                    : (d & 3) == 0 && (((uintptr_t)X & 3) == 0) && (((uintptr_t)R & 15) == 0);      // 8-bit rows: their own rule
     float amax = 0.0f;
     // whole waves stay together (the DPP row sums read neighbour lanes): the loop bound is wave-uniform, dead rows are masked
     const int64_t first = ((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63)) >> 4;      // the wave's first row
@@ -159,12 +163,12 @@ __global__ __launch_bounds__(256) void unary_shift_kernel(const float *__restric
         const bool live = i < n;
         float rmax = 0.0f;
         bool rnan = false;
-        const float *x = X + (live ? i : 0) * (int64_t)d;
+        const XT *x = X + (live ? i : 0) * (int64_t)d;
         if (!LONGV && vec && d <= 256) {                            // the vector stays in registers (16 floats per lane) while the m means pass by (L1)
             f32x4 xr[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t)
-                xr[t] = 4 * lp + 64 * t < d ? *reinterpret_cast<const f32x4 *>(x + 4 * lp + 64 * t) : (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+                xr[t] = 4 * lp + 64 * t < d ? lsq_ld4(x + 4 * lp + 64 * t) : (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
             for (int j = 0; j < m; ++j) {
                 const float *r = R + (int64_t)j * d + 4 * lp;
                 float acc = 0.0f;
@@ -194,7 +198,7 @@ __global__ __launch_bounds__(256) void unary_shift_kernel(const float *__restric
                 f32x4 xr[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
-                    xr[t] = c0 + 4 * lp + 64 * t < d ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(x + c0 + 4 * lp + 64 * t)) : (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+                    xr[t] = c0 + 4 * lp + 64 * t < d ? lsq_ld4_nt(x + c0 + 4 * lp + 64 * t) : (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                 for (int j = 0; j < LSQ_MAX_M; ++j) {
                     if (j < m) {
@@ -229,11 +233,11 @@ __global__ __launch_bounds__(256) void unary_shift_kernel(const float *__restric
             float acc = 0.0f;
             if (vec) {
                 for (int t = 4 * lp; t < d; t += 64) {
-                    const f32x4 xv = *reinterpret_cast<const f32x4 *>(x + t), rv = *reinterpret_cast<const f32x4 *>(r + t);
+                    const f32x4 xv = lsq_ld4(x + t), rv = *reinterpret_cast<const f32x4 *>(r + t);
                     acc += xv.x * rv.x + xv.y * rv.y + xv.z * rv.z + xv.w * rv.w;
                 }
             } else {
-                for (int t = lp; t < d; t += 16) acc += x[t] * r[t];
+                for (int t = lp; t < d; t += 16) acc += (float)x[t] * r[t];
             }
             acc = acc + dpp_self<DPP_XOR1, 0xf>(acc);
             acc = acc + dpp_self<DPP_XOR2, 0xf>(acc);
@@ -255,10 +259,11 @@ __global__ __launch_bounds__(64) void q16_range_init_kernel(unsigned *__restrict
     if (t < 2 * LSQ_MAX_M + 4) qrange[t] = (t < 2 * m && !(t & 1)) ? 0xffffffffu : 0u;
 }
 
-static void launch_unary_shift(dim3 grid, hipStream_t s, const float *X, const float *R, int64_t n, int d, int m, float *sigma, unsigned *sigmax,
+template <class XT>
+static void launch_unary_shift(dim3 grid, hipStream_t s, const XT *X, const float *R, int64_t n, int d, int m, float *sigma, unsigned *sigmax,
                                const unsigned *bound = nullptr, unsigned short *qflag = nullptr, int64_t flag_row0 = 0, lsq_q16_params *P = nullptr) {
-    if (d > 256) hipLaunchKernelGGL(unary_shift_kernel<true>, grid, dim3(256), 0, s, X, R, n, d, m, sigma, sigmax, bound, qflag, flag_row0, P);
-    else hipLaunchKernelGGL(unary_shift_kernel<false>, grid, dim3(256), 0, s, X, R, n, d, m, sigma, sigmax, bound, qflag, flag_row0, P);
+    if (d > 256) hipLaunchKernelGGL((unary_shift_kernel<true, XT>), grid, dim3(256), 0, s, X, R, n, d, m, sigma, sigmax, bound, qflag, flag_row0, P);
+    else hipLaunchKernelGGL((unary_shift_kernel<false, XT>), grid, dim3(256), 0, s, X, R, n, d, m, sigma, sigmax, bound, qflag, flag_row0, P);
 }
 #define LSQ_SHIFT_LAUNCH(D_, GRID_, S_, ...) launch_unary_shift(GRID_, S_, __VA_ARGS__)
 
@@ -1118,7 +1123,8 @@ int lsq_launch_q16_probe(hipStream_t s, const unsigned long long *probe, unsigne
 
 const void *lsq_probe_kernel_icmq() { return reinterpret_cast<const void *>(&q16_range_init_kernel); }
 
-int lsq_launch_unary_shift_panel(hipStream_t s, const float *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
+template <class XT>
+static int unary_shift_panel_t(hipStream_t s, const XT *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
                                  unsigned short *qflag, int64_t row0, lsq_q16_params *P) {
     if (rows <= 0) return LSQ_OK;
     const int64_t shift_blocks = (rows * 16 + 255) / 256;
@@ -1129,6 +1135,15 @@ int lsq_launch_unary_shift_panel(hipStream_t s, const float *Xp, int64_t rows, i
     return LSQ_OK;
 }
 
+int lsq_launch_unary_shift_panel(hipStream_t s, const float *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
+                                 unsigned short *qflag, int64_t row0, lsq_q16_params *P) {
+    return unary_shift_panel_t(s, Xp, rows, d, m, means, sigma_p, qrange, qflag, row0, P);
+}
+int lsq_launch_unary_shift_panel(hipStream_t s, const uint8_t *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
+                                 unsigned short *qflag, int64_t row0, lsq_q16_params *P) {
+    return unary_shift_panel_t(s, Xp, rows, d, m, means, sigma_p, qrange, qflag, row0, P);
+}
+
 int lsq_q16_sample_rows(int64_t n, int d, int64_t *rts_out) {
     const int64_t nsample = d <= 128 ? 16384 : (d <= 512 ? 8192 : 4096);      // the pass costs 2 d m h flops per sampled vector: fewer of them at large d
     const int64_t rts = n > nsample ? n / nsample : 1;
@@ -1136,10 +1151,11 @@ int lsq_q16_sample_rows(int64_t n, int d, int64_t *rts_out) {
     return (int)((n + 128 * rts - 1) / (128 * rts));      // number of 128-row panels in the sample (the last one may be short)
 }
 
-int lsq_launch_q16_prepare(hipStream_t s, const float *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, uint16_t *Tq,
-                           int *bad, float *trange, unsigned *qrange, unsigned short *qflag, lsq_q16_params *P, int tables_changed,
-                           float *rowmin, float *means, float *sigma, float *colmean, float *colshift, const float *Xsample, int64_t nsample_rows,
-                           float *sigma_sample) {
+template <class XT>
+static int q16_prepare_t(hipStream_t s, const XT *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, uint16_t *Tq,
+                         int *bad, float *trange, unsigned *qrange, unsigned short *qflag, lsq_q16_params *P, int tables_changed,
+                         float *rowmin, float *means, float *sigma, float *colmean, float *colshift, const XT *Xsample, int64_t nsample_rows,
+                         float *sigma_sample) {
     // bad[0]: a non-finite pair table (per call); rowmin / colmean [m*m*256], colshift [m*256], means [m*d]: per call; sigma [n*m]: per chunk;
     // qrange[2*16 + 1]: sample flag, [2*16 + 2]: max |sigma|
     if (tables_changed) {
@@ -1181,6 +1197,21 @@ int lsq_launch_q16_prepare(hipStream_t s, const float *X, int64_t n, int d, cons
     }
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
+}
+
+int lsq_launch_q16_prepare(hipStream_t s, const float *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, uint16_t *Tq,
+                           int *bad, float *trange, unsigned *qrange, unsigned short *qflag, lsq_q16_params *P, int tables_changed,
+                           float *rowmin, float *means, float *sigma, float *colmean, float *colshift, const float *Xsample, int64_t nsample_rows,
+                           float *sigma_sample) {
+    return q16_prepare_t(s, X, n, d, K, sci, T, m, Tq, bad, trange, qrange, qflag, P, tables_changed, rowmin, means, sigma, colmean, colshift, Xsample,
+                         nsample_rows, sigma_sample);
+}
+int lsq_launch_q16_prepare(hipStream_t s, const uint8_t *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, uint16_t *Tq,
+                           int *bad, float *trange, unsigned *qrange, unsigned short *qflag, lsq_q16_params *P, int tables_changed,
+                           float *rowmin, float *means, float *sigma, float *colmean, float *colshift, const uint8_t *Xsample, int64_t nsample_rows,
+                           float *sigma_sample) {
+    return q16_prepare_t(s, X, n, d, K, sci, T, m, Tq, bad, trange, qrange, qflag, P, tables_changed, rowmin, means, sigma, colmean, colshift, Xsample,
+                         nsample_rows, sigma_sample);
 }
 
 template <int M>

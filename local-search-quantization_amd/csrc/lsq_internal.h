@@ -139,6 +139,11 @@ int lsq_launch_chain_gemm(hipStream_t s, const float *A, const float *Bm, const 
 // taken (and in the range-only pass); the f32 output D is not shifted.  A shift common to all candidates of a node update cannot change its argmin (lsq_icmq.hip).
 // lda: row stride of A in floats (0 = Kd).  rts: range-only pass over every rts-th 128-row panel of A.  qflag [Mtot] u16 (Mtot even-padded): bit j raised when a value of
 // plane j fell outside the level range (Dq output).  qrange != nullptr: range-only pass, nothing stored; qrange[2 j], [2 j + 1] = min / max keys.
+// 8-bit data rows (A = X as uint8_t, lda in bytes): the same contract and, uint8 -> f32 being exact, the same bits as the call above on the widened rows
+int lsq_launch_chain_gemm(hipStream_t s, const uint8_t *A, const float *Bm, const float *addv, float alpha,
+                          int64_t M, int N, int Kd, int h, int64_t plane_stride, int64_t row_stride, float *D, int slice,
+                          int64_t Mtot, int64_t rbase, uint16_t *Dq = nullptr, int slice_q = 0, struct lsq_q16_params *qp = nullptr,
+                          int64_t lda = 0, unsigned short *qflag = nullptr, unsigned *qrange = nullptr, int rts = 1, const float *sigma = nullptr, const float *colshift = nullptr);
 // sci[r] = chain_t(Kb[r][t]^2)
 int lsq_launch_sqnorms(hipStream_t s, const float *Kb, int rows, int d, float *sci);
 
@@ -181,9 +186,15 @@ int lsq_launch_q16_prepare(hipStream_t s, const float *X, int64_t n, int d, cons
 // Xsample (optional; the host-buffer pipeline): the rows the strided sample pass would read -- every rts-th 128-row panel, lsq_q16_sample_rows -- already
 // compacted on the device; the level parameters come from them alone (max |sigma| widened x2) and X itself is not touched: its sigma are computed panel by
 // panel as the panels land (lsq_launch_unary_shift_panel: vectors beyond the assumed |sigma| bound are flagged for the f32 routine).
+int lsq_launch_q16_prepare(hipStream_t s, const uint8_t *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, uint16_t *Tq,
+                           int *bad, float *trange, unsigned *qrange, unsigned short *qflag, lsq_q16_params *P, int tables_changed,
+                           float *rowmin, float *means, float *sigma, float *colmean, float *colshift, const uint8_t *Xsample = nullptr,
+                           int64_t nsample_rows = 0, float *sigma_sample = nullptr);      // 8-bit rows
 int lsq_q16_sample_rows(int64_t n, int d, int64_t *rts_out);      // -> number of 128-row sample panels; *rts_out = the panel stride
 int lsq_launch_unary_shift_panel(hipStream_t s, const float *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
                                  unsigned short *qflag, int64_t row0, lsq_q16_params *P);
+int lsq_launch_unary_shift_panel(hipStream_t s, const uint8_t *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
+                                 unsigned short *qflag, int64_t row0, lsq_q16_params *P);      // 8-bit rows
 // rowmin [m*m*256], means [m*d], colmean [m*m*256], colshift [m*256] (per call), sigma [n*m] (per chunk); trange: 3 floats per pair table
 int lsq_launch_icm_walkq(hipStream_t s, const float *U, const uint16_t *Uq, const uint16_t *Tq, const float *T, uint8_t *rec, unsigned short *valid,
                          int64_t n, int m, const int32_t *order, int nnodes, int pos0, int use_skip, unsigned long long *active_total, int light,
@@ -205,6 +216,10 @@ int lsq_launch_cost(hipStream_t s, const float *X, const float *K, const uint8_t
                     unsigned long long *counters, int64_t n, int d, int m, int mode,
                     const unsigned short *vnew, unsigned short *vcur,
                     const lsq_perturb_next *next = nullptr);      // accept also copies the validity mask
+int lsq_launch_cost(hipStream_t s, const uint8_t *X, const float *K, const uint8_t *rec, uint8_t *cur, float *prev,
+                    unsigned long long *counters, int64_t n, int d, int m, int mode,
+                    const unsigned short *vnew, unsigned short *vcur,
+                    const lsq_perturb_next *next = nullptr);      // 8-bit rows of X (lsq_xload.h): the same costs, bit for bit
 // *sum += SUM_i v[i]  (f64)
 int lsq_launch_sum_f64(hipStream_t s, const float *v, int64_t n, double *sum);
 

@@ -44,8 +44,8 @@ def encode_sharded(X_shard, B0_shard, K, m, ilsiters, icmiter, npert, randord, s
     """Encode this rank's shard; returns (codes_shard, objs, stats[, gathered]) where
     objs = global objective per checkpoint (float32), stats = global (I, 2) counters.
 
-    X_shard/B0_shard/K: device torch tensors for the HIP encoder ((n_r, d) f32, (n_r, m) u8 0-based,
-    (m*256, d) f32).  K needs to be valid on rank 0 only: it is broadcast in place.
+    X_shard/B0_shard/K: device torch tensors for the HIP encoder ((n_r, d) f32 -- or uint8: an 8-bit shard is
+    passed through as it is and stays 8-bit on the device --, (n_r, m) u8 0-based, (m*256, d) f32).  K needs to be valid on rank 0 only: it is broadcast in place.
     """
     import torch
     import torch.distributed as dist

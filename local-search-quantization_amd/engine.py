@@ -2,6 +2,7 @@
 
 Row-major conventions (the Julia buffers seen from numpy, see include/lsq_mi355x.h):
     X (n, d) float32 | K (m*h, d) float32 | B (n, m) int16 1-based (host) / uint8 0-based (device)
+    X (n, d) uint8 (the encode calls only: .bvecs base sets stay 8-bit end to end, the lsq_*_u8 entry points)
 torch is used only as the owner of device memory and streams; every computation happens inside
 liblsq_mi355x.so.
 """
@@ -19,6 +20,19 @@ IT_AUTO = 0xFFFFFFFF      # LSQ_IT_AUTO: the context counts the ILS iterations o
 def _np(a, dtype):
     a = np.ascontiguousarray(a, dtype=dtype)
     return a
+
+
+def _x_host(X):
+    """The data matrix of an encode call as a C-contiguous host array -> (array, is_u8).  uint8 (numpy, or a CPU torch tensor) stays uint8 and takes
+    the 8-bit entry points; int8 is refused (bytes of a .bvecs file are unsigned: a signed view would encode other vectors); anything else is
+    converted to float32 as it always was.  A non-contiguous array is copied, whatever its type."""
+    dt = getattr(X, "dtype", None)
+    name = str(dt).replace("torch.", "") if dt is not None else ""
+    if name == "int8":
+        raise TypeError("int8 data is not accepted: 8-bit base sets are unsigned (uint8); view or convert the array explicitly")
+    if name == "uint8":
+        return np.ascontiguousarray(X, dtype=np.uint8), True
+    return _np(X, np.float32), False
 
 
 class Engine:
@@ -129,15 +143,17 @@ class Engine:
     # -- (1) whole call, host buffers -------------------------------------------------------
     def encode_icm(self, X, B, K, m, ilsiters, icmiter, npert, randord, seed=0, nsplits=1, global_offset=0,
                    verbose=False, h=H):
-        """-> Bs (nr, n, m) int16 1-based, objs (nr,) float32   [lsq_encode_icm]"""
-        X, K, B = _np(X, np.float32), _np(K, np.float32), _np(B, np.int16)
+        """-> Bs (nr, n, m) int16 1-based, objs (nr,) float32   [lsq_encode_icm; uint8 X: lsq_encode_icm_u8, the rows stay 8-bit]"""
+        X, u8 = _x_host(X)
+        K, B = _np(K, np.float32), _np(B, np.int16)
         n, d = X.shape
         self._check_shapes(X, K, B, m, h)
         ils = _np(ilsiters, np.int64).reshape(-1)
         nr = ils.shape[0]
         Bs = np.empty((nr, n, m), dtype=np.int16)
         objs = np.zeros(nr, dtype=np.float32)
-        self._check(self._L.lsq_encode_icm(self._h, X.ctypes.data, B.ctypes.data, K.ctypes.data, d, n, m, h,
+        call = self._L.lsq_encode_icm_u8 if u8 else self._L.lsq_encode_icm
+        self._check(call(self._h, X.ctypes.data, B.ctypes.data, K.ctypes.data, d, n, m, h,
                                           ils.ctypes.data, nr, int(icmiter), int(npert), int(bool(randord)),
                                           int(nsplits), int(seed), int(global_offset), int(bool(verbose)),
                                           Bs.ctypes.data, objs.ctypes.data))
@@ -146,14 +162,18 @@ class Engine:
     # -- (1b) whole call, device-resident torch tensors -------------------------------------
     def encode_icm_dev(self, dX, dB0, dK, m, ilsiters, icmiter, npert, randord, seed=0, global_offset=0,
                        out=None, h=H, nonblocking=False):
-        """dX (n,d) f32, dB0 (n,m) u8 0-based, dK (m*h,d) f32: CUDA/HIP torch tensors.
+        """dX (n,d) f32 or uint8 (8-bit rows: lsq_encode_icm_u8_dev, any byte offset into a larger buffer), dB0 (n,m) u8 0-based, dK (m*h,d) f32:
+        CUDA/HIP torch tensors.
         -> dBs (nr, n, m) uint8 tensor, obj_sums (nr,) float64 numpy (SUM of costs), stats (I, 2) int64.
         nonblocking=True (option "async"): nothing in the call waits for the device; obj_sums and stats come back as DEVICE tensors, valid after the
         caller has synchronised torch's current stream (the call can be captured into a graph from its second use on a shape on)."""
         import torch
         assert dX.is_cuda and dB0.is_cuda and dK.is_cuda, "device tensors required"
-        assert dX.dtype == torch.float32 and dK.dtype == torch.float32 and dB0.dtype == torch.uint8
+        if dX.dtype == torch.int8:
+            raise TypeError("int8 data is not accepted: 8-bit base sets are unsigned (uint8)")
+        assert dX.dtype in (torch.float32, torch.uint8) and dK.dtype == torch.float32 and dB0.dtype == torch.uint8
         assert dX.is_contiguous() and dB0.is_contiguous() and dK.is_contiguous()
+        call = self._L.lsq_encode_icm_u8_dev if dX.dtype == torch.uint8 else self._L.lsq_encode_icm_dev
         n, d = dX.shape
         if dB0.shape != (n, m) or dK.shape != (m * h, d):
             raise ValueError("shape mismatch: X %s B %s K %s m=%d h=%d" % (tuple(dX.shape), tuple(dB0.shape), tuple(dK.shape), m, h))
@@ -167,7 +187,7 @@ class Engine:
             with self._on_torch_stream():
                 self.set_option("async", 1)
                 try:
-                    self._check(self._L.lsq_encode_icm_dev(self._h, dX.data_ptr(), dB0.data_ptr(), dK.data_ptr(), d, n, m, h,
+                    self._check(call(self._h, dX.data_ptr(), dB0.data_ptr(), dK.data_ptr(), d, n, m, h,
                                                            ils.ctypes.data, nr, int(icmiter), int(npert), int(bool(randord)),
                                                            int(seed), int(global_offset), dBs.data_ptr(), obj_t.data_ptr(), stats_t.data_ptr()))
                 finally:
@@ -176,7 +196,7 @@ class Engine:
         obj = np.zeros(nr, dtype=np.float64)
         stats = np.zeros((I, 2), dtype=np.int64)
         with self._on_torch_stream():
-            self._check(self._L.lsq_encode_icm_dev(self._h, dX.data_ptr(), dB0.data_ptr(), dK.data_ptr(), d, n, m, h,
+            self._check(call(self._h, dX.data_ptr(), dB0.data_ptr(), dK.data_ptr(), d, n, m, h,
                                                    ils.ctypes.data, nr, int(icmiter), int(npert), int(bool(randord)),
                                                    int(seed), int(global_offset), dBs.data_ptr(), obj.ctypes.data,
                                                    stats.ctypes.data))
@@ -717,8 +737,9 @@ class MultiEngine:
 
     def encode_icm(self, X, B, K, m, ilsiters, icmiter, npert, randord, seed=0, nsplits=1, global_offset=0,
                    verbose=False, h=H):
-        """-> Bs (nr, n, m) int16 1-based, objs (nr,) float32   [lsq_multi_encode_icm]"""
-        X, K, B = _np(X, np.float32), _np(K, np.float32), _np(B, np.int16)
+        """-> Bs (nr, n, m) int16 1-based, objs (nr,) float32   [lsq_multi_encode_icm; uint8 X: lsq_multi_encode_icm_u8]"""
+        X, u8 = _x_host(X)
+        K, B = _np(K, np.float32), _np(B, np.int16)
         n, d = X.shape
         if B.shape != (n, m) or K.shape != (m * h, d):
             raise ValueError("shape mismatch: X %s B %s K %s m=%d h=%d" % (X.shape, B.shape, K.shape, m, h))
@@ -726,7 +747,8 @@ class MultiEngine:
         nr = ils.shape[0]
         Bs = np.empty((nr, n, m), dtype=np.int16)
         objs = np.zeros(nr, dtype=np.float32)
-        _lib.check(self._L.lsq_multi_encode_icm(self._h, X.ctypes.data, B.ctypes.data, K.ctypes.data, d, n, m, h,
+        call = self._L.lsq_multi_encode_icm_u8 if u8 else self._L.lsq_multi_encode_icm
+        _lib.check(call(self._h, X.ctypes.data, B.ctypes.data, K.ctypes.data, d, n, m, h,
                                                 ils.ctypes.data, nr, int(icmiter), int(npert), int(bool(randord)),
                                                 int(seed), int(global_offset), int(bool(verbose)), Bs.ctypes.data, objs.ctypes.data))
         return Bs, objs

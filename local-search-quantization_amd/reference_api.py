@@ -43,15 +43,24 @@ def _X_of(X):
     return np.ascontiguousarray(np.asarray(X, dtype=np.float32).T)       # (d, n) -> (n, d)
 
 
+def _X8_of(X):
+    """encode_icm_cuda's data matrix: a uint8 (d, n) matrix -- what bvecs_read returns -- stays uint8 ((n, d), the 8-bit entry points); int8 is refused
+    by the engine; everything else is float32 as before."""
+    if getattr(X, "dtype", None) in (np.dtype(np.uint8), np.dtype(np.int8)):
+        return np.ascontiguousarray(np.asarray(X).T)
+    return _X_of(X)
+
+
 def _B_of(B):
     return np.ascontiguousarray(np.asarray(B, dtype=np.int16).T)         # (m, n) -> (n, m)
 
 
 def encode_icm_cuda(RX, B, C, ilsiters, icmiter, npert, randord, nsplits=2, V=False, *, seed=0, engine=None):
-    """-> (Bs, objs): Bs = list of (m, n) int16 1-based matrices, objs = float32 vector."""
+    """-> (Bs, objs): Bs = list of (m, n) int16 1-based matrices, objs = float32 vector.
+    RX may be the UInt8 matrix bvecs_read returns: it is handed over un-widened (lsq_encode_icm_u8) and gives what Float32.(RX) gives."""
     eng = engine or default_engine()
     m, d, h = _dims(C)
-    Bs, objs = eng.encode_icm(_X_of(RX), _B_of(B), _K_of(C), m, list(ilsiters), icmiter, npert, randord,
+    Bs, objs = eng.encode_icm(_X8_of(RX), _B_of(B), _K_of(C), m, list(ilsiters), icmiter, npert, randord,
                               seed=seed, nsplits=nsplits, verbose=V, h=h)
     return [Bs[r].T for r in range(Bs.shape[0])], objs
 

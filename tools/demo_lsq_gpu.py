@@ -1,10 +1,14 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
+
+--bvecs: the base set stays 8-bit end to end -- read with bvecs_read from the first *base*.bvecs file under $LSQ_DATA_DIR (SIFT1B layout: learn, base and
+query .bvecs files and an .ivecs ground truth side by side), else the synthetic stand-in quantised to bytes -- and is handed to encode_icm_cuda as
+uint8 (lsq_encode_icm_u8: d bytes per vector over the bus and in HBM).  Training set and queries are widened: the trainers, k-NN and the scan take f32.
 
 needs $LSQ_DATA_DIR/sift/{sift_learn,sift_base,sift_query}.fvecs and sift_groundtruth.ivecs (TEXMEX layout).  The file's ground truth
 describes the full 10^6-vector base only: for a prefix of it (nread_base < 10^6) and for the stand-in, the ground truth is exact k-NN of the base
@@ -32,10 +36,43 @@ def ground_truth(xb, xq):
     return ids[0]
 
 
-def load(nt, nb, nq):
+def find_bvecs():
+    """-> (learn, base, query) .bvecs paths of the first directory under $LSQ_DATA_DIR that has all three, or None"""
+    root = os.environ.get("LSQ_DATA_DIR")
+    if not root:
+        return None
+    for dirpath, _, files in sorted(os.walk(root)):
+        got = {}
+        for f in sorted(files):
+            if f.endswith(".bvecs"):
+                for role in ("learn", "base", "query"):
+                    if role in f:
+                        got.setdefault(role, os.path.join(dirpath, f))
+        if len(got) == 3:
+            return got["learn"], got["base"], got["query"]
+    return None
+
+
+def load_bvecs(nt, nb, nq):
+    """-> name, x_train f32, x_base UINT8, x_query f32, ground truth (exact k-NN of the base actually encoded)"""
+    paths = find_bvecs()
+    if paths:
+        xt8, xb8, xq8 = lsq.bvecs_read(nt, paths[0]), lsq.bvecs_read(nb, paths[1]), lsq.bvecs_read(nq, paths[2])
+        name = "bvecs"
+    else:
+        print("no learn / base / query .bvecs under $LSQ_DATA_DIR -- running the synthetic stand-in quantised to bytes")
+        _, xt, xb, xq, _ = load(nt, nb, nq, want_gt=False, synthetic=True)
+        lo, hi = min(xt.min(), xb.min(), xq.min()), max(xt.max(), xb.max(), xq.max())
+        xt8, xb8, xq8 = (np.rint((x - lo) * (255.0 / (hi - lo))).astype(np.uint8) for x in (xt, xb, xq))
+        name = "synthetic"
+    xq = xq8.astype(np.float32)
+    return name, xt8.astype(np.float32), xb8, xq, ground_truth(xb8.astype(np.float32), xq)      # (k-NN takes f32: a widened copy for the ground truth only)
+
+
+def load(nt, nb, nq, want_gt=True, synthetic=False):
     base = os.path.join(os.environ.get("LSQ_DATA_DIR", ""), "sift")
     names = ["sift_learn.fvecs", "sift_base.fvecs", "sift_query.fvecs", "sift_groundtruth.ivecs"]
-    if os.environ.get("LSQ_DATA_DIR") and all(os.path.exists(os.path.join(base, f)) for f in names):
+    if not synthetic and os.environ.get("LSQ_DATA_DIR") and all(os.path.exists(os.path.join(base, f)) for f in names):
         xt = lsq.fvecs_read(nt, os.path.join(base, names[0]))
         xb = lsq.fvecs_read(nb, os.path.join(base, names[1]))
         xq = lsq.fvecs_read(nq, os.path.join(base, names[2]))
@@ -50,7 +87,7 @@ def load(nt, nb, nq):
     cen = rng.standard_normal((d, k)).astype(np.float32) * 3.0
     allx = (cen[:, rng.integers(k, size=nt + nb + nq)] + 0.35 * rng.standard_normal((d, nt + nb + nq))).astype(np.float32)
     xt, xb, xq = allx[:, :nt], allx[:, nt:nt + nb], allx[:, nt + nb:]
-    return "synthetic", xt, xb, xq, ground_truth(xb, xq)
+    return "synthetic", xt, xb, xq, ground_truth(xb, xq) if want_gt else None
 
 
 def train_resident(x_train, m, h, niter, ilsiter, icmiter, randord, npert):
@@ -72,15 +109,15 @@ def train_resident(x_train, m, h, niter, ilsiter, icmiter, randord, npert):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--resident"]
-    resident = len(args) != len(sys.argv) - 1
+    args = [a for a in sys.argv[1:] if a not in ("--resident", "--bvecs")]
+    resident, bvecs = "--resident" in sys.argv[1:], "--bvecs" in sys.argv[1:]
     real = bool(os.environ.get("LSQ_DATA_DIR"))
     nt = int(args[0]) if len(args) > 0 else (10_000 if real else 3000)
     nb = int(args[1]) if len(args) > 1 else (1_000_000 if real else 6000)
     nq = int(args[2]) if len(args) > 2 else (10_000 if real else 64)
-    name, x_train, x_base, x_query, gt = load(nt, nb, nq)
+    name, x_train, x_base, x_query, gt = load_bvecs(nt, nb, nq) if bvecs else load(nt, nb, nq)
     d = x_train.shape[0]
-    m, h, niter, knn = (7, 256, 10, 1000) if name == "SIFT1M" else (4, 256, 3, 50)     # demo_lsq_gpu.jl:13-20
+    m, h, niter, knn = (7, 256, 10, 1000) if name in ("SIFT1M", "bvecs") else (4, 256, 3, 50)     # demo_lsq_gpu.jl:13-20
     ilsiter, icmiter, randord, npert = 8, 4, True, 4
     if resident:
         C, B, cbnorms, B_norms, obj = train_resident(x_train, m, h, niter, ilsiter, icmiter, randord, min(npert, m))
@@ -96,7 +133,9 @@ def main():
     Bs, objs = lsq.encode_icm_cuda(x_base, B_base, C, [16], icmiter, min(npert, m), randord, 2, True)
     dt = time.perf_counter() - t0
     B_base = Bs[-1]
-    print("Encoded %d base vectors in %.3f s (%.0f vectors/s, host buffers); error in base is %e" % (x_base.shape[1], dt, x_base.shape[1] / dt, objs[-1]))
+    print("Encoded %d base vectors in %.3f s (%.0f vectors/s, host buffers, %s rows); error in base is %e" % (x_base.shape[1], dt, x_base.shape[1] / dt,
+                                                                                                       x_base.dtype, objs[-1]))
+    assert x_base.dtype == (np.uint8 if bvecs else np.float32)
     with lsq.Engine(0) as eng:                                              # norm quantisation on the device (lsq_quantize_norms), checked against the mirror
         nidx = lsq.quantize_norms(B_base, C, cbnorms, engine=eng)
     assert np.array_equal(nidx, lsq.quantize_norms(B_base, C, cbnorms)), "device and host norm quantisation disagree"
