@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 1300
+#define LSQ_VERSION 1400
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -135,6 +135,8 @@ LSQ_API int lsq_set_stream(lsq_ctx *ctx, void *hip_stream);
  *        lists, convergence counter, the cover map) and wait.
  *   "ils_counter": the next iteration index used by lsq_encoding_icm / lsq_encode_icm_fully when called with it = LSQ_IT_AUTO
  *        (starts at 0, advances by one per such call).
+ *   "rerank_batch" (default 0): queries per batch of the re-rank stage of every lsq_index created on this context; 0 = automatic (batches of at most
+ *        2^28 (query, candidate) records, like the scans).  A test hook: small shapes cross batch boundaries.  Same results.
  *   (liblsq_mi355x_tuning.so only) "ablation": timing-only kernel variants whose results are garbage. */
 LSQ_API int lsq_set_option(lsq_ctx *ctx, const char *key, int64_t value);
 LSQ_API int lsq_get_timings(lsq_ctx *ctx, lsq_timings *out);      /* writes the v400 layout only (everything before table_reuses: a caller built against any header since v400 is never overrun); the fields appended since come through: */
@@ -379,6 +381,63 @@ typedef struct lsq_linscan_stats {
     double lut_ms, sample_ms, scan_ms, select_ms;
 } lsq_linscan_stats;
 LSQ_API int lsq_get_linscan_stats(lsq_ctx *ctx, lsq_linscan_stats *out);
+
+/* ---- (3e) two-stage search: exact re-rank of ADC shortlists, on a resident index (since v1400) ---------------------------------------------------
+ * Stage one is the scan of linscan_lsq, src/linscan/Linscan.jl:46-73 (lsq_linscan_dev above).  Stage two HAS NO COUNTERPART IN THE REFERENCE, whose
+ * recall figures are those of the ADC distances alone: every query's shortlist is re-ordered by the true distance to the stored vectors,
+ *   dist = ((0 + e_0*e_0) + e_1*e_1) + ... + e_{d-1}*e_{d-1},   e_s = x[s] - q[s]       (f32, s ascending, every op rounded, no FMA)
+ * -- lsq_knn_exact's rule: a re-ranked distance has the bits lsq_knn_exact gives for the same (query, row).  A uint8 base (base_u8 = 1: the un-widened rows
+ * of a .bvecs set) is widened in registers (exact): the bits of the f32 call on the widened matrix.  Any byte alignment and any ldb >= d; the loads are
+ * 16 bytes, 4 bytes or single bytes wide by what the base pointer and the row pitch in bytes are both multiples of.
+ *   cand [nq][L] int32 ids in the caller's id_base (0 or 1); dists / ids [nq][nn], ids int32 in the same id_base.
+ *   Result per query: the nn smallest (dist, id) pairs among its L candidates in lexicographic order; ties go to the smaller id; NaN distances sort
+ *   after every number.  An id that occurs twice is returned twice.  An id outside [id_base, id_base + n) is never dereferenced: it sorts after everything,
+ *   NaN included, and is reported as (+inf, id_base - 1).
+ * LSQ_EINVAL: nn < 1, nn > L, d < 1, ldb < d, ldq < d, n < 1, an id_base other than 0 / 1, a null pointer.
+ *   lsq_rerank_cpu  host cores, std::thread workers (nthreads 0 = all), no context: the checker and the engine-less road. */
+LSQ_API int lsq_rerank_cpu(float *dists, int *ids, const void *base, int base_u8, const float *queries, const int *cand, int n, int nq, int d, int ldb,
+                           int ldq, int L, int nn, int id_base, int nthreads);
+/* The index: a handle that keeps the database RESIDENT on a context's device -- codes, norms and codebooks for stage one, the base rows for stage two -- so
+ * that a C or Julia caller uploads it once instead of once per lsq_linscan call.
+ *   on_device = 0: host buffers, copied once at creation and owned by the index;  on_device = 1: device pointers, borrowed -- the caller keeps them alive.
+ *   codes == NULL: a base-only index (re-rank only; codebooks / dbnorms / m / h are ignored);  base == NULL: a scan-only index.  One of them must be set.
+ * The index runs on the context's device and on the stream the context is bound to at each call; the context must outlive it, and -- like the context --
+ * it serves one host thread at a time.  It owns its own scratch (scan state, record buffers): calls on the index and calls on the context do not disturb
+ * each other, and neither do two indexes of one context.  Limits of lsq_linscan: h == 256, 1 <= m <= 16; n <= 2^31 - 2. */
+typedef struct lsq_index lsq_index;
+typedef struct lsq_index_desc {
+    int64_t n;
+    int d, m, h;
+    const uint8_t *codes;        /* [n][m] uint8 0-based, or NULL */
+    const float *codebooks;      /* [m*h][d] */
+    const float *dbnorms;        /* [n] */
+    const void *base;            /* [n][ldb] float32 or uint8, or NULL */
+    int base_u8, ldb;
+    int on_device;
+} lsq_index_desc;
+typedef struct lsq_index_stats {
+    int64_t queries;             /* queries answered (search + rerank), accumulated since creation */
+    int64_t rows;                /* candidate rows gathered by stage two */
+    int64_t invalid;             /* candidate ids outside the base: skipped, never dereferenced */
+    int64_t batches;             /* batches of stage two */
+    double scan_ms, gather_ms, select_ms;      /* with the context's option "profile" = 1: stage one; stage two's distances; stage two's sort + hand-out */
+} lsq_index_stats;
+LSQ_API int lsq_index_create(lsq_index **out, lsq_ctx *ctx, const lsq_index_desc *desc);
+LSQ_API int lsq_index_destroy(lsq_index *ix);
+/* shortlist == 0: the ADC scan alone -- the results of lsq_linscan_dev bit for bit (ADC distances, 1-BASED int32 ids).
+ * shortlist = L >= nn: the scan for L, then the re-rank of every query's L ids to nn -- exact distances, 1-based ids.  L <= n and L <= 2^28.
+ * q_scan [nq][ldq] is what the scan reads (the ROTATED queries of linscan_lsq, R'X), q_exact [nq][ldq] what the re-rank reads (the queries in the base
+ * set's own frame; may equal q_scan, ignored when shortlist == 0).  The rotation stays with the caller, as in linscan_lsq: a device GEMM would not give
+ * numpy's bits.  on_device: 0 = q_scan, q_exact, dists, ids are host buffers, 1 = device buffers.  dists / ids [nq][nn]. */
+LSQ_API int lsq_index_search(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_exact, int nq, int ldq, int shortlist, int nn,
+                             int on_device);
+/* Stage two alone, on the caller's candidates (see lsq_rerank_cpu; the same bits): how the 0-based shortlists of lsq_linscan_pq(_dev) are re-ranked.
+ * L <= 2^28 (candidates may repeat, so L may exceed n): one query's records are one batch. */
+LSQ_API int lsq_index_rerank(lsq_index *ix, float *dists, int *ids, const float *queries, const int *cand, int nq, int ldq, int L, int nn, int id_base,
+                             int on_device);
+LSQ_API int lsq_index_get_stats(lsq_index *ix, lsq_index_stats *out);
+/* LSQ_EINVAL for all of them: a null pointer, nn > L, shortlist > n, a re-rank on an index without base rows, a search on an index without codes;
+ * nothing is launched then. */
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB      src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

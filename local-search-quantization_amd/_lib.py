@@ -44,6 +44,19 @@ class LinscanStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class IndexDesc(C.Structure):
+    _fields_ = [("n", C.c_int64), ("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("codes", C.c_void_p), ("codebooks", C.c_void_p),
+                ("dbnorms", C.c_void_p), ("base", C.c_void_p), ("base_u8", C.c_int), ("ldb", C.c_int), ("on_device", C.c_int)]
+
+
+class IndexStats(C.Structure):
+    _fields_ = [("queries", C.c_int64), ("rows", C.c_int64), ("invalid", C.c_int64), ("batches", C.c_int64),
+                ("scan_ms", C.c_double), ("gather_ms", C.c_double), ("select_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Q16SnapshotNode(C.Structure):
     _fields_ = [("loU", C.c_float), ("invD", C.c_float), ("D", C.c_float), ("hiq", C.c_float), ("window", C.c_int32), ("pad_", C.c_int32),
                 ("slack", C.c_double)]
@@ -118,6 +131,13 @@ SIGNATURES = {
     "lsq_knn_exact_cpu": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
     "lsq_knn_exact": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "lsq_knn_exact_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    # two-stage search (since v1400): the host checker of the re-rank, and the resident index
+    "lsq_rerank_cpu": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "lsq_index_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(IndexDesc)]),
+    "lsq_index_destroy": (_i, [_vp]),
+    "lsq_index_search": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "lsq_index_rerank": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    "lsq_index_get_stats": (_i, [_vp, C.POINTER(IndexStats)]),
     "lsq_quantize_norms": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "lsq_quantize_norms_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "lsq_update_codebooks": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _vp]),

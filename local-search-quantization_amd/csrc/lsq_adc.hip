@@ -758,3 +758,17 @@ int lsq_adc_search_exact_host(hipStream_t s, lsq_adc_state **pst, float *dists, 
     LSQ_HIP(hipStreamSynchronize(s));
     return LSQ_OK;
 }
+
+// The exhaustive road's selection for another producer of MODE 1 records (lsq_rerank.hip): full segments, sorted on end_bit bits, the first nn gathered
+int lsq_adc_select_full(lsq_adc_state **pst, hipStream_t s, const uint64_t *recs, uint64_t *sorted, int *seg, int q0, int nqb, int cap, int nn,
+                        float *dists, int *idx, int idbits, int end_bit, int id_sub) {
+    if (!*pst) *pst = new lsq_adc_state();
+    int *begin = seg, *end = seg + nqb;
+    hipLaunchKernelGGL(adc_segments_kernel, dim3((unsigned)((nqb + 255) / 256)), dim3(256), 0, s, (const unsigned *)nullptr, nqb, cap, nn, begin, end,
+                       (int *)nullptr);
+    LSQ_TRY(sort_segments(*pst, s, recs, sorted, (int64_t)nqb * cap, nqb, begin, end, end_bit));
+    hipLaunchKernelGGL(adc_gather_kernel, dim3((unsigned)((nn + 255) / 256 < 64 ? (nn + 255) / 256 : 64), (unsigned)nqb), dim3(256), 0, s, sorted,
+                       (const int *)nullptr, (const int *)nullptr, q0, nqb, cap, nn, dists, idx, idbits, id_sub);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}

@@ -104,6 +104,7 @@ struct lsq_ctx {
     lsq_adc_state *adc = nullptr;                      // device ADC scan (lsq_adc.hip): buffers, created on first use
     lsq_linscan_stats adc_stats{};
     int adc_exhaustive = 0, adc_rank = 0;              // options "linscan_exhaustive", "linscan_rank": test hooks of the scan's selection
+    int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
     DevBuf sX, sX2, sK, sB16, sOut16, sTight, sF32;    // staging for the host-buffer entry points (sX/sX2: double-buffered X chunks)
     DevBuf sSample, sSigmaS;                           // host-buffer pipeline: the level sample (compacted rows of X) and its sigma
     std::vector<float> sample_host;                    // ... packed on the host before its upload
@@ -291,6 +292,10 @@ extern "C" int lsq_set_option(lsq_ctx *c, const char *key, int64_t value) {
     else if (!strcmp(key, "linscan_rank")) {
         if (value < 0) { lsq_set_error("linscan_rank must be >= 0"); return LSQ_EINVAL; }
         c->adc_rank = (int)value;
+    }
+    else if (!strcmp(key, "rerank_batch")) {
+        if (value < 0) { lsq_set_error("rerank_batch must be >= 0"); return LSQ_EINVAL; }
+        c->rerank_batch = value;
     }
     else if (!strcmp(key, "ils_counter")) {
         if (value < 0 || value >= (int64_t)LSQ_IT_AUTO) { lsq_set_error("ils_counter must lie in 0..2^32-2"); return LSQ_EINVAL; }
@@ -483,6 +488,240 @@ extern "C" int lsq_knn_exact(lsq_ctx *c, float *dists, uint32_t *ids, const floa
 extern "C" int lsq_get_linscan_stats(lsq_ctx *c, lsq_linscan_stats *out) {
     if (!c || !out) { lsq_set_error("lsq_get_linscan_stats: null argument"); return LSQ_EINVAL; }
     *out = c->adc_stats;
+    return LSQ_OK;
+}
+
+// ---- two-stage search on a resident index: the ADC scan (lsq_adc.hip), then the exact re-rank of its shortlists (lsq_rerank.hip) -------------------------
+struct lsq_index {
+    lsq_ctx *ctx = nullptr;
+    int64_t n = 0;
+    int d = 0, m = 0, base_u8 = 0;
+    int64_t ldb = 0;
+    const uint8_t *codes = nullptr;                    // device pointers: the index's own copies (host-buffer description) or the caller's (borrowed)
+    const float *K = nullptr, *norms = nullptr;
+    const void *base = nullptr;
+    DevBuf own_codes, own_K, own_norms, own_base;
+    lsq_adc_state *adc = nullptr;                      // the scan's state of THIS index: never ctx->adc
+    DevBuf rec_a, rec_b, seg, counter;                 // stage two: records, sorted records, segment bounds, the invalid-id counter
+    DevBuf short_d, short_i;                           // stage one's shortlist [nq][L]
+    DevBuf s_qscan, s_qexact, s_cand, s_dists, s_ids;  // staging of host-buffer calls, and of scan queries whose rows are not d floats apart
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    lsq_index_stats stats{};
+};
+
+extern "C" int lsq_index_destroy(lsq_index *ix) {
+    if (!ix) return LSQ_OK;
+    (void)hipSetDevice(ix->ctx->device);
+    (void)hipStreamSynchronize(ix->ctx->stream);
+    DevBuf *bufs[] = {&ix->own_codes, &ix->own_K, &ix->own_norms, &ix->own_base, &ix->rec_a, &ix->rec_b, &ix->seg, &ix->counter, &ix->short_d, &ix->short_i,
+                      &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids};
+    for (DevBuf *b : bufs) b->release();
+    lsq_adc_free(ix->adc);
+    for (hipEvent_t e : ix->ev) if (e) (void)hipEventDestroy(e);
+    delete ix;
+    return LSQ_OK;
+}
+
+static int index_adopt(lsq_index *ix, DevBuf &own, const void *src, size_t bytes, int on_device, const void **dst) {
+    if (on_device) { *dst = src; return LSQ_OK; }
+    LSQ_TRY(own.ensure(bytes));
+    LSQ_HIP(hipMemcpyAsync(own.p, src, bytes, hipMemcpyHostToDevice, ix->ctx->stream));
+    *dst = own.p;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_create(lsq_index **out, lsq_ctx *c, const lsq_index_desc *desc) {
+    if (!out) { lsq_set_error("lsq_index_create: null out pointer"); return LSQ_EINVAL; }
+    *out = nullptr;
+    if (!c || !desc) { lsq_set_error("lsq_index_create: null %s", c ? "description" : "context"); return LSQ_EINVAL; }
+    if (!desc->codes && !desc->base) { lsq_set_error("lsq_index_create: neither codes nor base rows"); return LSQ_EINVAL; }
+    if (desc->n < 1 || desc->n > (int64_t)INT32_MAX - 1 || desc->d < 1) {
+        lsq_set_error("lsq_index_create: needs 1 <= n <= 2^31 - 2 and d >= 1 (got n=%lld d=%d)", (long long)desc->n, desc->d);
+        return LSQ_EINVAL;
+    }
+    if (desc->codes) {
+        if (desc->h != LSQ_H || desc->m < 1 || desc->m > LSQ_MAX_M) {
+            lsq_set_error("lsq_index_create: needs h == 256 and 1 <= m <= 16 (got h=%d m=%d)", desc->h, desc->m);
+            return LSQ_EINVAL;
+        }
+        if (!desc->codebooks || !desc->dbnorms) { lsq_set_error("lsq_index_create: codes without codebooks or dbnorms"); return LSQ_EINVAL; }
+    }
+    if (desc->base && desc->ldb < desc->d) { lsq_set_error("lsq_index_create: needs ldb >= d (got ldb=%d d=%d)", desc->ldb, desc->d); return LSQ_EINVAL; }
+    if (desc->base && !desc->base_u8 && ((uintptr_t)desc->base & 3) != 0) { lsq_set_error("lsq_index_create: the f32 base is not 4-byte aligned"); return LSQ_EINVAL; }
+    LSQ_TRY(use_device(c));
+    lsq_index *ix = new lsq_index();
+    ix->ctx = c;
+    ix->n = desc->n; ix->d = desc->d; ix->m = desc->codes ? desc->m : 0; ix->base_u8 = desc->base_u8 != 0; ix->ldb = desc->ldb;
+    const size_t n = (size_t)desc->n, d = (size_t)desc->d;
+    int rc = LSQ_OK;
+    if (desc->codes) {
+        rc = index_adopt(ix, ix->own_codes, desc->codes, n * (size_t)desc->m, desc->on_device, reinterpret_cast<const void **>(&ix->codes));
+        if (rc == LSQ_OK) rc = index_adopt(ix, ix->own_K, desc->codebooks, sizeof(float) * (size_t)desc->m * LSQ_H * d, desc->on_device, reinterpret_cast<const void **>(&ix->K));
+        if (rc == LSQ_OK) rc = index_adopt(ix, ix->own_norms, desc->dbnorms, sizeof(float) * n, desc->on_device, reinterpret_cast<const void **>(&ix->norms));
+    }
+    if (rc == LSQ_OK && desc->base)      // rows up to the d-th element of the last one
+        rc = index_adopt(ix, ix->own_base, desc->base, ((n - 1) * (size_t)desc->ldb + d) * (desc->base_u8 ? 1 : sizeof(float)), desc->on_device, &ix->base);
+    if (rc == LSQ_OK) rc = ix->counter.ensure(sizeof(unsigned long long));
+    if (rc == LSQ_OK && hipStreamSynchronize(c->stream) != hipSuccess) { lsq_set_error("lsq_index_create: the upload failed"); rc = LSQ_EHIP; }
+    if (rc != LSQ_OK) { (void)lsq_index_destroy(ix); return rc; }
+    *out = ix;
+    return LSQ_OK;
+}
+
+// stage two on device buffers: queries [nq][ldq], cand [nq][L] -> dists / ids [nq][nn], in batches of queries
+static int index_rerank_dev(lsq_index *ix, float *d_dists, int *d_ids, const float *d_q, int64_t ldq, const int *d_cand, int nq, int L, int nn, int id_base) {
+    lsq_ctx *c = ix->ctx;
+    hipStream_t s = c->stream;
+    const bool timed = c->profile != 0;
+    if (timed) for (hipEvent_t &e : ix->ev) if (!e) LSQ_HIP(hipEventCreate(&e));
+    // two record buffers of qb L <= 2^28 entries (L <= 2^28: both callers check it before anything is launched); hipcub counts items in int
+    int64_t qb = c->rerank_batch > 0 ? c->rerank_batch : (int64_t)(1u << 28) / L;
+    if (qb > (int64_t)(1u << 28) / L) qb = (int64_t)(1u << 28) / L;
+    if (qb > 16384) qb = 16384;                       // (the hand-out's grid counts queries in its y dimension)
+    if (qb < 1) qb = 1;
+    if (qb > nq) qb = nq;
+    LSQ_TRY(ix->rec_a.ensure(sizeof(uint64_t) * (size_t)qb * L));
+    LSQ_TRY(ix->rec_b.ensure(sizeof(uint64_t) * (size_t)qb * L));
+    LSQ_TRY(ix->seg.ensure(sizeof(int) * 2 * (size_t)qb));
+    LSQ_HIP(hipMemsetAsync(ix->counter.p, 0, sizeof(unsigned long long), s));
+    const int idbits = lsq_rerank_idbits(ix->n);
+    for (int q0 = 0; q0 < nq; q0 += (int)qb) {
+        const int nqb = (int)std::min<int64_t>(qb, nq - q0);
+        if (timed) LSQ_HIP(hipEventRecord(ix->ev[0], s));
+        LSQ_TRY(lsq_rerank_launch(s, ix->base, ix->base_u8, ix->ldb, ix->n, d_q, ldq, d_cand, q0, nqb, L, ix->d, id_base, ix->rec_a.as<uint64_t>(), idbits,
+                                  ix->counter.as<unsigned long long>()));
+        if (timed) LSQ_HIP(hipEventRecord(ix->ev[1], s));
+        // records: (outside-the-base bit, distance key, row + 1); the gather hands out row + 1 - (1 - id_base)
+        LSQ_TRY(lsq_adc_select_full(&ix->adc, s, ix->rec_a.as<uint64_t>(), ix->rec_b.as<uint64_t>(), ix->seg.as<int>(), q0, nqb, L, nn, d_dists, d_ids, idbits,
+                                    33 + idbits, 1 - id_base));
+        if (timed) {
+            LSQ_HIP(hipEventRecord(ix->ev[2], s));
+            LSQ_HIP(hipEventSynchronize(ix->ev[2]));
+            float a = 0, b = 0;
+            LSQ_HIP(hipEventElapsedTime(&a, ix->ev[0], ix->ev[1]));
+            LSQ_HIP(hipEventElapsedTime(&b, ix->ev[1], ix->ev[2]));
+            ix->stats.gather_ms += a; ix->stats.select_ms += b;
+        }
+        ix->stats.batches += 1;
+    }
+    unsigned long long bad = 0;
+    LSQ_HIP(hipMemcpyAsync(&bad, ix->counter.p, sizeof(bad), hipMemcpyDeviceToHost, s));
+    LSQ_HIP(hipStreamSynchronize(s));
+    ix->stats.invalid += (int64_t)bad;
+    ix->stats.rows += (int64_t)nq * L - (int64_t)bad;
+    return LSQ_OK;
+}
+
+// rows [rows][ld] of src (host or device) -> dst on the device: as they are when `pack` is 0 (ld floats apart), compacted to `width` floats otherwise
+static int index_stage_rows(lsq_index *ix, DevBuf &buf, const float *src, int rows, int64_t ld, int width, bool pack, const float **dst, int64_t *ld_out) {
+    hipStream_t s = ix->ctx->stream;
+    if (pack && ld != width) {
+        LSQ_TRY(buf.ensure(sizeof(float) * (size_t)rows * width));
+        LSQ_HIP(hipMemcpy2DAsync(buf.p, sizeof(float) * (size_t)width, src, sizeof(float) * (size_t)ld, sizeof(float) * (size_t)width, (size_t)rows,
+                                 hipMemcpyDefault, s));
+        *ld_out = width;
+    } else {
+        const size_t floats = (size_t)(rows - 1) * (size_t)ld + (size_t)width;
+        LSQ_TRY(buf.ensure(sizeof(float) * floats));
+        LSQ_HIP(hipMemcpyAsync(buf.p, src, sizeof(float) * floats, hipMemcpyDefault, s));
+        *ld_out = ld;
+    }
+    *dst = buf.as<float>();
+    return LSQ_OK;
+}
+
+static int index_call_check(const char *fn, lsq_index *ix, const void *dists, const void *ids, int nq, int64_t ldq, int nn) {
+    if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
+    if (nq < 0 || nn < 1 || ldq < ix->d) { lsq_set_error("%s: needs nq >= 0, nn >= 1, ldq >= d (got nq=%d nn=%d ldq=%lld d=%d)", fn, nq, nn, (long long)ldq, ix->d); return LSQ_EINVAL; }
+    if (!dists || !ids) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_rerank(lsq_index *ix, float *dists, int *ids, const float *queries, const int *cand, int nq, int ldq, int L, int nn, int id_base,
+                                int on_device) {
+    LSQ_TRY(index_call_check("lsq_index_rerank", ix, dists, ids, nq, ldq, nn));
+    if (!ix->base) { lsq_set_error("lsq_index_rerank: the index holds no base rows"); return LSQ_EINVAL; }
+    LSQ_TRY(lsq_rerank_check("lsq_index_rerank", dists, ids, ix->base, queries, cand, ix->n, nq, ix->d, ix->ldb, ldq, L, nn, id_base));
+    if (L > (1 << 28)) { lsq_set_error("lsq_index_rerank: needs L <= 2^28 candidates per query (got %d)", L); return LSQ_EINVAL; }      // a batch is >= 1 query
+    if (nq == 0) return LSQ_OK;
+    LSQ_TRY(use_device(ix->ctx));
+    AsyncOff blocking(ix->ctx);
+    hipStream_t s = ix->ctx->stream;
+    if (on_device) {
+        LSQ_TRY(index_rerank_dev(ix, dists, ids, queries, ldq, cand, nq, L, nn, id_base));
+    } else {
+        const float *dq = nullptr;
+        int64_t ld = 0;
+        LSQ_TRY(index_stage_rows(ix, ix->s_qexact, queries, nq, ldq, ix->d, false, &dq, &ld));
+        LSQ_TRY(ix->s_cand.ensure(sizeof(int) * (size_t)nq * L));
+        LSQ_TRY(ix->s_dists.ensure(sizeof(float) * (size_t)nq * nn));
+        LSQ_TRY(ix->s_ids.ensure(sizeof(int) * (size_t)nq * nn));
+        LSQ_HIP(hipMemcpyAsync(ix->s_cand.p, cand, sizeof(int) * (size_t)nq * L, hipMemcpyHostToDevice, s));
+        LSQ_TRY(index_rerank_dev(ix, ix->s_dists.as<float>(), ix->s_ids.as<int>(), dq, ld, ix->s_cand.as<int>(), nq, L, nn, id_base));
+        LSQ_HIP(hipMemcpyAsync(dists, ix->s_dists.p, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipMemcpyAsync(ids, ix->s_ids.p, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipStreamSynchronize(s));
+    }
+    ix->stats.queries += nq;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_search(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_exact, int nq, int ldq, int shortlist, int nn,
+                                int on_device) {
+    LSQ_TRY(index_call_check("lsq_index_search", ix, dists, ids, nq, ldq, nn));
+    if (!ix->codes) { lsq_set_error("lsq_index_search: the index holds no codes"); return LSQ_EINVAL; }
+    if (shortlist < 0 || (shortlist > 0 && shortlist < nn)) { lsq_set_error("lsq_index_search: needs shortlist == 0 or shortlist >= nn (got shortlist=%d nn=%d)", shortlist, nn); return LSQ_EINVAL; }
+    const int L = shortlist > 0 ? shortlist : nn;
+    if (L > ix->n) { lsq_set_error("lsq_index_search: %s=%d exceeds the database size %lld", shortlist > 0 ? "shortlist" : "nn", L, (long long)ix->n); return LSQ_EINVAL; }
+    if (shortlist > (1 << 28)) { lsq_set_error("lsq_index_search: needs shortlist <= 2^28 (got %d)", shortlist); return LSQ_EINVAL; }
+    if (shortlist > 0 && !ix->base) { lsq_set_error("lsq_index_search: a shortlist needs base rows, the index holds none"); return LSQ_EINVAL; }
+    if (!q_scan || (shortlist > 0 && !q_exact)) { lsq_set_error("lsq_index_search: null pointer"); return LSQ_EINVAL; }
+    if (nq == 0) return LSQ_OK;
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    AsyncOff blocking(c);
+    hipStream_t s = c->stream;
+    const int d = ix->d;
+    // the scan reads query rows d floats apart
+    const float *dqs = q_scan;
+    int64_t ld = ldq;
+    if (!on_device || ldq != d) LSQ_TRY(index_stage_rows(ix, ix->s_qscan, q_scan, nq, ldq, d, true, &dqs, &ld));
+    const float *dqe = q_exact;
+    int64_t lde = ldq;
+    if (shortlist > 0 && !on_device) LSQ_TRY(index_stage_rows(ix, ix->s_qexact, q_exact, nq, ldq, d, false, &dqe, &lde));
+    float *out_d = dists;
+    int *out_i = ids;
+    if (!on_device) {
+        LSQ_TRY(ix->s_dists.ensure(sizeof(float) * (size_t)nq * nn));
+        LSQ_TRY(ix->s_ids.ensure(sizeof(int) * (size_t)nq * nn));
+        out_d = ix->s_dists.as<float>();
+        out_i = ix->s_ids.as<int>();
+    }
+    float *scan_d = out_d;
+    int *scan_i = out_i;
+    if (shortlist > 0) {
+        LSQ_TRY(ix->short_d.ensure(sizeof(float) * (size_t)nq * L));
+        LSQ_TRY(ix->short_i.ensure(sizeof(int) * (size_t)nq * L));
+        scan_d = ix->short_d.as<float>();
+        scan_i = ix->short_i.as<int>();
+    }
+    lsq_linscan_stats st{};
+    LSQ_TRY(lsq_adc_search(s, &ix->adc, scan_d, scan_i, ix->codes, dqs, ix->K, ix->norms, nq, (int)ix->n, ix->m, d, L, c->adc_exhaustive, c->adc_rank, &st,
+                           c->profile));
+    ix->stats.scan_ms += st.lut_ms + st.sample_ms + st.scan_ms + st.select_ms;
+    if (shortlist > 0) LSQ_TRY(index_rerank_dev(ix, out_d, out_i, dqe, lde, scan_i, nq, L, nn, 1));      // the scan's ids are 1-based
+    if (!on_device) {
+        LSQ_HIP(hipMemcpyAsync(dists, out_d, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipMemcpyAsync(ids, out_i, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipStreamSynchronize(s));
+    }
+    ix->stats.queries += nq;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_stats(lsq_index *ix, lsq_index_stats *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_stats: null argument"); return LSQ_EINVAL; }
+    *out = ix->stats;
     return LSQ_OK;
 }
 

@@ -272,6 +272,19 @@ int lsq_knn_launch_scan(hipStream_t s, int mode, const float *X, int ldb, const 
 int lsq_knn_exact_check(const char *fn, const void *dists, const void *ids, const void *base, const void *queries, int n, int nq, int d, int ldb,
                         int ldq, int nn);
 
+// ---- exact re-rank of shortlists (lsq_rerank.hip): the distance producer of stage two, and the pieces of the scans' selection that serve it ---------
+// records (distance key << idbits | row + 1) of queries q0 .. q0 + nqb - 1 to out[slot * L + s]; cand [.][L] ids in id_base; a candidate outside
+// [id_base, id_base + n) is not dereferenced: bit 32 + idbits, the key of +inf and id field 0 (sort the records on 33 + idbits bits).  *invalid += those
+int lsq_rerank_idbits(int64_t n);
+int lsq_rerank_launch(hipStream_t s, const void *base, int base_u8, int64_t ldb, int64_t n, const float *Q, int64_t ldq, const int *cand, int q0, int nqb,
+                      int L, int d, int id_base, uint64_t *out, int idbits, unsigned long long *invalid);
+int lsq_rerank_check(const char *fn, const void *dists, const void *ids, const void *base, const void *queries, const void *cand, int64_t n, int nq, int d,
+                     int64_t ldb, int64_t ldq, int L, int nn, int id_base);
+// the exhaustive road's selection over full segments of `cap` records (lsq_adc.hip: adc_segments_kernel, sort_segments, adc_gather_kernel): sorted on
+// end_bit bits, the first nn of every segment handed out as dists / idx [q0 + slot][nn] with idx = id field - id_sub.  seg: 2 nqb ints of scratch
+int lsq_adc_select_full(lsq_adc_state **st, hipStream_t s, const uint64_t *recs, uint64_t *sorted, int *seg, int q0, int nqb, int cap, int nn,
+                        float *dists, int *idx, int idbits, int end_bit, int id_sub);
+
 // argument checks of the PQ / OPQ scan (lsq_linscan.hip), shared by the host drop-in and the device scan
 int lsq_linscan_pq_check(const char *fn, const void *dists, const void *res, const void *codes, const void *centers, const void *queries, int N,
                          uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim);

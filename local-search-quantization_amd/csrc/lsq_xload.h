@@ -13,6 +13,10 @@
 // A loaded-but-not-yet-widened quad stays PACKED (one VGPR) until it is consumed: the GEMM's register double buffer and the cost kernel's "x one
 // step ahead" hold a quarter of the registers the f32 instantiation holds, and the convert sits next to the arithmetic, not next to the load (a
 // convert right behind the load would put the wait for it in front of the work the load is meant to hide under).
+//
+// One more reader of X keeps a loader of its own: the exact re-rank (lsq_rerank.hip, rr_load16) fetches 16-byte PIECES of a 128-byte line, not quads,
+// and so adds a 16-byte road to the dword / byte rule above.  It shares lsq_widen4 and the packed-until-consumed rule; a change to the alignment
+// rule here has to be made there too.
 #pragma once
 
 #include <stdint.h>

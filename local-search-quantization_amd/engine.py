@@ -8,6 +8,7 @@ liblsq_mi355x.so.
 """
 import contextlib
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -42,6 +43,7 @@ class Engine:
         h = C.c_void_p()
         self._check(self._L.lsq_create(C.byref(h), int(device)))
         self._h = h
+        self._indexes = weakref.WeakSet()             # the Index objects made on this context: closed before it
         self.device = int(device)
         if chunk is not None:
             self.set_option("chunk", int(chunk))
@@ -58,6 +60,8 @@ class Engine:
     # -- lifetime -------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
+            for ix in list(getattr(self, "_indexes", ())):      # an index needs its context to free what it holds on the device
+                ix.close()
             self._L.lsq_destroy(self._h)
             self._h = None
 
@@ -293,6 +297,18 @@ class Engine:
         with self._on_torch_stream():
             self._check(self._L.lsq_knn_exact_dev(self._h, dists.data_ptr(), ids.data_ptr(), dXb.data_ptr(), dXq.data_ptr(), n, nq, d, ldb, ldq, int(k)))
         return dists, ids
+
+    # -- (1d) two-stage search on a resident index ------------------------------------------
+    def index(self, codes, K, dbnorms, m, base=None, h=H, d=None):
+        """An Index of HOST arrays, copied once and owned by the index: codes (n,m) uint8 0-based, K (m*h,d), dbnorms (n,), base (n,ldb) float32 or
+        uint8 (the un-widened rows of a .bvecs set) or None (scan only).  codes=None: a base-only index (re-rank only), which reads the first d
+        components of a base row (default: all of them)   [lsq_index_create]"""
+        return Index(self, codes, K, dbnorms, m, base, h, d, on_device=False)
+
+    def index_dev(self, dcodes, dK, dnorms, m, base=None, h=H, d=None):
+        """The same on device-resident torch tensors, BORROWED: the index keeps references to them; searches take and return tensors.  base: a 2-d
+        tensor or a view of one with unit column stride, at any byte offset."""
+        return Index(self, dcodes, dK, dnorms, m, base, h, d, on_device=True)
 
     def quantize_norms(self, B, K, cbnorms, m, h=H):
         """B (n,m) int16 1-based, K (m*h,d), cbnorms (<= 256,): host arrays.
@@ -663,6 +679,136 @@ class Engine:
             raise ValueError("K must be (m*h, d) = (%d, %d), got %s" % (m * h, d, K.shape))
         if B.shape != (n, m):
             raise ValueError("B must be (n, m) = (%d, %d), got %s" % (n, m, B.shape))
+
+
+# -- the resident index (made by Engine.index / Engine.index_dev) --------------------------------
+
+class Index:
+    """A resident database on an Engine's device: the ADC scan (stage one) and the exact re-rank of its shortlists (stage two)   [lsq_index_*].
+    Made by Engine.index (host arrays in and out) or Engine.index_dev (torch tensors in and out, on torch's current stream)."""
+
+    def __init__(self, engine, codes, K, dbnorms, m, base, h, d, on_device):
+        self._eng, self._L, self._dev, self._h = engine, engine._L, bool(on_device), None
+        desc = _lib.IndexDesc()
+        if self._dev:
+            import torch
+            for t, dt in ((codes, torch.uint8), (K, torch.float32), (dbnorms, torch.float32)):
+                if t is not None:
+                    assert t.is_cuda and t.dtype == dt and t.is_contiguous(), "contiguous device tensors required"
+            if base is not None:
+                assert base.is_cuda and base.dtype in (torch.float32, torch.uint8) and base.dim() == 2 and base.stride(1) == 1
+            ptr = lambda t: t.data_ptr()      # noqa: E731
+            u8 = base is not None and base.dtype == torch.uint8
+            ldb = 0 if base is None else (base.stride(0) if base.shape[0] > 1 else base.shape[1])
+        else:
+            codes = None if codes is None else _np(codes, np.uint8)
+            K = None if K is None else _np(K, np.float32)
+            dbnorms = None if dbnorms is None else _np(dbnorms, np.float32)
+            if base is not None:
+                base, u8 = _x_host(base)
+            else:
+                u8 = False
+            ptr = lambda a: a.ctypes.data      # noqa: E731
+            ldb = 0 if base is None else base.shape[1]
+        if codes is None and base is None:
+            raise ValueError("an index needs codes, base rows or both")
+        n = int(codes.shape[0] if codes is not None else base.shape[0])
+        d = int(K.shape[1] if codes is not None else (d or base.shape[1]))
+        if codes is not None and (tuple(codes.shape) != (n, m) or tuple(K.shape) != (m * h, d) or tuple(dbnorms.shape) != (n,)):
+            raise ValueError("shape mismatch: codes %s K %s dbnorms %s m=%d h=%d" % (tuple(codes.shape), tuple(K.shape), tuple(dbnorms.shape), m, h))
+        if base is not None and (base.shape[0] != n or base.shape[1] < d):
+            raise ValueError("shape mismatch: base %s for n=%d d=%d" % (tuple(base.shape), n, d))
+        desc.n, desc.d, desc.m, desc.h = n, d, int(m), int(h)
+        desc.codes = ptr(codes) if codes is not None else None
+        desc.codebooks = ptr(K) if codes is not None else None
+        desc.dbnorms = ptr(dbnorms) if codes is not None else None
+        desc.base = ptr(base) if base is not None else None
+        desc.base_u8, desc.ldb, desc.on_device = int(u8), int(ldb), int(self._dev)
+        self._keep = (codes, K, dbnorms, base)      # borrowed device tensors stay alive with the index
+        self.n, self.d, self.m = n, d, int(m)
+        handle = C.c_void_p()
+        with self._stream():
+            engine._check(self._L.lsq_index_create(C.byref(handle), engine._h, C.byref(desc)))
+        self._h = handle
+        engine._indexes.add(self)
+
+    def _stream(self):
+        return self._eng._on_torch_stream() if self._dev else contextlib.nullcontext()
+
+    def _queries(self, Q):
+        if self._dev:
+            import torch
+            assert Q.is_cuda and Q.dtype == torch.float32 and Q.dim() == 2 and Q.is_contiguous(), "contiguous device f32 queries required"
+            return Q, Q.data_ptr()
+        Q = _np(Q, np.float32)
+        return Q, Q.ctypes.data
+
+    def _outputs(self, nq, k, like):
+        if self._dev:
+            import torch
+            dists = torch.empty((nq, k), dtype=torch.float32, device=like.device)
+            ids = torch.empty((nq, k), dtype=torch.int32, device=like.device)
+            return dists, ids, dists.data_ptr(), ids.data_ptr()
+        dists, ids = np.zeros((nq, k), dtype=np.float32), np.zeros((nq, k), dtype=np.int32)
+        return dists, ids, dists.ctypes.data, ids.ctypes.data
+
+    def search(self, Q_scan, k, shortlist=0, Q_exact=None):
+        """Q_scan (nq,d): what the scan reads (the rotated queries of linscan_lsq); Q_exact (nq,d): the queries in the base set's own frame (default:
+        Q_scan).  shortlist=0: the ADC scan alone, Engine.linscan's results; shortlist=L>=k: scan for L, re-rank to k by exact distance.
+        -> dists (nq,k) float32 ascending, ids (nq,k) int32 1-BASED   [lsq_index_search]"""
+        Qs, ps = self._queries(Q_scan)
+        Qe, pe = self._queries(Q_exact) if Q_exact is not None else (Qs, ps)
+        if tuple(Qe.shape) != tuple(Qs.shape) or Qs.shape[1] != self.d:
+            raise ValueError("shape mismatch: Q_scan %s Q_exact %s d=%d" % (tuple(Qs.shape), tuple(Qe.shape), self.d))
+        nq = Qs.shape[0]
+        dists, ids, pd, pi = self._outputs(nq, int(k), Qs)
+        with self._stream():
+            self._eng._check(self._L.lsq_index_search(self._h, pd, pi, ps, pe, nq, self.d, int(shortlist), int(k), int(self._dev)))
+        return dists, ids
+
+    def rerank(self, Q, cand, k, id_base=1):
+        """Stage two alone: cand (nq,L) int32 ids in id_base (the 0-based shortlists of linscan_pq: id_base=0).
+        -> dists (nq,k) float32 exact, ascending, ids (nq,k) int32 in id_base; an id outside the base comes last as (+inf, id_base-1)   [lsq_index_rerank]"""
+        Q, pq = self._queries(Q)
+        if self._dev:
+            import torch
+            assert cand.is_cuda and cand.dtype == torch.int32 and cand.dim() == 2 and cand.is_contiguous(), "contiguous device int32 candidates required"
+            pc = cand.data_ptr()
+        else:
+            cand = _np(cand, np.int32)
+            pc = cand.ctypes.data
+        if cand.ndim != 2 or cand.shape[0] != Q.shape[0] or Q.shape[1] != self.d:
+            raise ValueError("shape mismatch: Q %s cand %s d=%d" % (tuple(Q.shape), tuple(cand.shape), self.d))
+        nq, L = cand.shape
+        dists, ids, pd, pi = self._outputs(nq, int(k), Q)
+        with self._stream():
+            self._eng._check(self._L.lsq_index_rerank(self._h, pd, pi, pq, pc, nq, self.d, int(L), int(k), int(id_base), int(self._dev)))
+        return dists, ids
+
+    def stats(self):
+        st = _lib.IndexStats()
+        self._eng._check(self._L.lsq_index_get_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        # Engine.close closes its indexes first.  Should the context be gone all the same, the handle is dropped, not destroyed: lsq_index_destroy would
+        # reach through the freed context, and lsq_destroy knows nothing of the index's buffers, which then stay allocated until the process ends.
+        if getattr(self, "_h", None) and getattr(self._eng, "_h", None):
+            self._L.lsq_index_destroy(self._h)
+        self._h = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 # -- host-only pieces of the path (no GPU needed) ---------------------------------------------

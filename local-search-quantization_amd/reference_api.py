@@ -194,6 +194,49 @@ def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0):
     return dists.T, ids.T + np.uint32(1)
 
 
+def _base_rows(X_base):
+    """(d, n) base set -> (n, d) rows; the uint8 matrix bvecs_read returns stays uint8 (the 8-bit road), everything else is float32"""
+    if getattr(X_base, "dtype", None) == np.dtype(np.uint8):
+        return np.ascontiguousarray(np.asarray(X_base).T)
+    return _X_of(X_base)
+
+
+def rerank(X_base, X_query, ids, k, *, engine=None, nthreads=0):
+    """Stage two of a two-stage search -- no counterpart in the reference, which reports the recall of the ADC order: every query's candidates
+    re-ordered by the exact distance of knn_exact.  X_base (d, n) Float32 or the UInt8 matrix of bvecs_read, X_query (d, nq), ids (L, nq) 1-based (what
+    linscan_lsq / linscan_pq / linscan_opq return).  -> dists (k, nq) float32 ascending, ids (k, nq) int32 1-based; ties by smaller id, NaN last, an id
+    outside 1..n last of all as (+inf, 0).  engine=None: the host cores (lsq_rerank_cpu); engine=<Engine>: the device -- same results bit for bit."""
+    from . import _lib
+    Xb, Xq = _base_rows(X_base), _X_of(X_query)
+    cand = np.ascontiguousarray(np.asarray(ids).astype(np.int64).T.astype(np.int32))      # (nq, L)
+    if Xb.shape[1] != Xq.shape[1] or cand.shape[0] != Xq.shape[0]:
+        raise ValueError("rerank: base %s, queries %s, ids %s" % (Xb.shape, Xq.shape, cand.shape))
+    if engine is not None:
+        with engine.index(None, None, None, 0, base=Xb) as ix:
+            dists, out = ix.rerank(Xq, cand, k, id_base=1)
+    else:
+        (n, d), (nq, L) = Xb.shape, cand.shape
+        dists = np.zeros((nq, k), dtype=np.float32)
+        out = np.zeros((nq, k), dtype=np.int32)
+        _lib.check(_lib.load().lsq_rerank_cpu(dists.ctypes.data, out.ctypes.data, Xb.ctypes.data, int(Xb.dtype == np.uint8), Xq.ctypes.data,
+                                              cand.ctypes.data, n, nq, d, d, d, L, int(k), 1, int(nthreads)))
+    return dists.T, out.T
+
+
+def linscan_lsq_rerank(B, X, C, dbnorms, R, X_base, shortlist, k, *, engine=None, nthreads=0):
+    """linscan_lsq for `shortlist` neighbours, then rerank to k: the scan reads R'X, the re-rank X against X_base (both in the base set's own frame).
+    -> dists (k, nq) exact float32, ids (k, nq) int32 1-based.  engine=<Engine>: one resident index does both stages on the device (lsq_index_search)."""
+    if engine is None:
+        _, res = linscan_lsq(B, X, C, dbnorms, R, shortlist, nthreads=nthreads)
+        return rerank(X_base, X, res, k, nthreads=nthreads)
+    codes = np.ascontiguousarray(np.asarray(B, dtype=np.uint8).T)
+    RX = np.ascontiguousarray((np.asarray(R, dtype=np.float32).T @ np.asarray(X, dtype=np.float32)).T)
+    m, _, h = _dims(C)
+    with engine.index(codes, _K_of(C), np.ascontiguousarray(dbnorms, dtype=np.float32), m, base=_base_rows(X_base), h=h) as ix:
+        dists, ids = ix.search(RX, k, shortlist=shortlist, Q_exact=_X_of(X))
+    return dists.T, ids.T
+
+
 def eval_recall(ids_gnd, ids_predicted, k, V=False):
     """recall@N curve (src/linscan/Linscan.jl:76-117): ids_gnd (nq,), ids_predicted (k, nq), same id base.
     -> recall_at_i (k,) with recall_at_i[i-1] = fraction of queries whose true neighbour ranks <= i."""

@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -9,6 +9,10 @@ the codes and codebooks stay in HBM between the stages; the rest of the flow is 
 --bvecs: the base set stays 8-bit end to end -- read with bvecs_read from the first *base*.bvecs file under $LSQ_DATA_DIR (SIFT1B layout: learn, base and
 query .bvecs files and an .ivecs ground truth side by side), else the synthetic stand-in quantised to bytes -- and is handed to encode_icm_cuda as
 uint8 (lsq_encode_icm_u8: d bytes per vector over the bus and in HBM).  Training set and queries are widened: the trainers, k-NN and the scan take f32.
+
+--rerank L: after the ADC scan, the two-stage search on a resident index (Engine.index: the codes, norms, codebooks and the base rows uploaded once):
+the scan's L nearest re-ordered by exact distance to the stored vectors -- f32 rows, or the un-widened 8-bit rows with --bvecs -- and the recall curve of the
+re-ranked lists printed next to the ADC one.  The reference has no such stage: its recall is that of the ADC order.
 
 needs $LSQ_DATA_DIR/sift/{sift_learn,sift_base,sift_query}.fvecs and sift_groundtruth.ivecs (TEXMEX layout).  The file's ground truth
 describes the full 10^6-vector base only: for a prefix of it (nread_base < 10^6) and for the stand-in, the ground truth is exact k-NN of the base
@@ -109,8 +113,14 @@ def train_resident(x_train, m, h, niter, ilsiter, icmiter, randord, npert):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--resident", "--bvecs")]
-    resident, bvecs = "--resident" in sys.argv[1:], "--bvecs" in sys.argv[1:]
+    argv = sys.argv[1:]
+    shortlist = 0
+    if "--rerank" in argv:
+        at = argv.index("--rerank")
+        shortlist = int(argv[at + 1])
+        del argv[at:at + 2]
+    args = [a for a in argv if a not in ("--resident", "--bvecs")]
+    resident, bvecs = "--resident" in argv, "--bvecs" in argv
     real = bool(os.environ.get("LSQ_DATA_DIR"))
     nt = int(args[0]) if len(args) > 0 else (10_000 if real else 3000)
     nb = int(args[1]) if len(args) > 1 else (1_000_000 if real else 6000)
@@ -151,6 +161,20 @@ def main():
     print("Searched %d queries: device %.3f s (host buffers, incl. copies), host %.3f s; identical results" % (x_query.shape[1], t_dev, t_host))
     rec = lsq.eval_recall(gt, idx.astype(np.uint32), knn, True)
     print("%s: recall@1 = %.4f, recall@%d = %.4f" % (name, rec[0], knn, rec[knn - 1]))
+    if shortlist:
+        L = min(shortlist, x_base.shape[1])
+        keep = min(knn, L)
+        t0 = time.perf_counter()
+        with lsq.Engine(0) as eng:                                          # stage two: the scan's L nearest re-ordered by exact distance, on a resident index
+            rd, ridx = lsq.linscan_lsq_rerank((B_base - 1).astype(np.uint8), x_query, C, db_norms, np.eye(d, dtype=np.float32), x_base, L, keep, engine=eng)
+        t_two = time.perf_counter() - t0
+        rrec = lsq.eval_recall(gt, ridx.astype(np.uint32), keep)
+        print("Two-stage search (shortlist %d, %s rows resident): %.3f s incl. the upload of the index" % (L, x_base.dtype, t_two))
+        print("     r@   ADC      re-ranked")
+        for i in (1, 2, 5, 10, 20, 50, 100, 200, 500, 1000):
+            if i <= keep:
+                print("%7d   %.4f   %.4f" % (i, rec[i - 1], rrec[i - 1]))
+        print("%s: recall@1 after re-ranking %d = %.4f (ADC: %.4f)" % (name, L, rrec[0], rec[0]))
 
 
 if __name__ == "__main__":
