@@ -24,7 +24,7 @@
 //           road directly.  rocPRIM's segmented radix sort (hipcub) does the sorting.
 // NaN distances (the reference's partial_sort has no defined order for them) sort after everything else here.
 //
-// The reference's other scan, linscan_aqd_query for PQ / OPQ codes (src/linscan/cpp/linscan_aqd.cpp:37-114; lsq_adc_search_pq), runs on the same
+// The reference's other scan, linscan_aqd_query for PQ / OPQ codes (src/linscan/cpp/linscan_aqd.cpp:37-114; LSQ_SEARCH_PQ), runs on the same
 // machinery: adc_pq_lut_kernel builds the sub-space squared-distance tables in the same layout, adc_scan_kernel drops the norm term (NORM = false)
 // and reads code rows dim1codes bytes apart, and the gather hands out 0-based ids.
 #include <hipcub/hipcub.hpp>
@@ -408,7 +408,8 @@ __global__ void adc_gather_kernel(const uint64_t *__restrict__ sorted, const int
 
 struct lsq_adc_state {
     DevBuf lut, keys_a, keys_b, tau, count, seg, fail, qsel, tmp;
-    DevBuf h_codes, h_q, h_k, h_norms, h_dists, h_idx;      // staging of the host-buffer entry point
+    // staging of the host-buffer entry point: the database (code rows, or the base rows of an exact search), the queries, the tables, the norms, the results
+    DevBuf h_db, h_q, h_tables, h_norms, h_dists, h_idx;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     bool attr_set = false;
 };
@@ -416,30 +417,22 @@ struct lsq_adc_state {
 void lsq_adc_free(lsq_adc_state *st) {
     if (!st) return;
     DevBuf *all[] = {&st->lut, &st->keys_a, &st->keys_b, &st->tau, &st->count, &st->seg, &st->fail, &st->qsel, &st->tmp,
-                  &st->h_codes, &st->h_q, &st->h_k, &st->h_norms, &st->h_dists, &st->h_idx};
+                  &st->h_db, &st->h_q, &st->h_tables, &st->h_norms, &st->h_dists, &st->h_idx};
     for (DevBuf *b : all) b->release();
     for (hipEvent_t e : st->ev) if (e) (void)hipEventDestroy(e);
     delete st;
 }
 
+int lsq_adc_idbits(int64_t n) {
+    int idbits = 1;                                   // ids 1 .. n in the record's id field
+    while (idbits < 32 && ((uint64_t)n >> idbits) != 0) ++idbits;
+    return idbits;
+}
+
 namespace {
 
-// What one call searches.  LSQ (dbnorms set): K = [m h][d] codebooks, tables -2<q, c>, + dbnorms[i], 1-based ids out.  PQ / OPQ (dbnorms null):
-// K = [m][h][d] sub-space centres (d = subdim), squared-distance tables, no norm term, 0-based ids out.  Exact (base set): no codes, no tables;
-// lsq_knn.hip computes the squared distances to the float rows base[i * bstride ..] directly, 0-based ids out.
-struct AdcInput {
-    const uint8_t *codes; int cstride;       // [n][cstride] u8 0-based, the first m bytes of a row used
-    const float *Q; int qstride;             // query rows, qstride floats apart
-    const float *K;
-    const float *dbnorms;
-    int n, m, d;
-    const float *base = nullptr; int bstride = 0;
-    bool exact() const { return base != nullptr; }
-    bool pq() const { return dbnorms == nullptr; }
-};
-
 template <int QT, int MODE>
-int launch_scan(hipStream_t s, const float *LUT, const AdcInput &in, int nqb, int stride, int ns, const uint32_t *tau, unsigned *count, int cap,
+int launch_scan(hipStream_t s, const float *LUT, const lsq_search_input &in, int nqb, int stride, int ns, const uint32_t *tau, unsigned *count, int cap,
                 uint64_t *out, int idbits) {
     const int tiles = (nqb + QT - 1) / QT;
     const int n = in.n, m = in.m;
@@ -472,8 +465,8 @@ int launch_scan(hipStream_t s, const float *LUT, const AdcInput &in, int nqb, in
         else if (words && m == 16) ADC_LAUNCH(4, NORMV); \
         else ADC_LAUNCH(0, NORMV);                \
     } while (0)
-    if (in.pq()) ADC_LAUNCH_MW(false);
-    else ADC_LAUNCH_MW(true);
+    if (in.kind == LSQ_SEARCH_LSQ) ADC_LAUNCH_MW(true);
+    else ADC_LAUNCH_MW(false);
 #undef ADC_LAUNCH_MW
 #undef ADC_LAUNCH
     LSQ_HIP(hipGetLastError());
@@ -482,20 +475,20 @@ int launch_scan(hipStream_t s, const float *LUT, const AdcInput &in, int nqb, in
 
 // the scan of either producer: the table walk of adc_scan_kernel, or the exact distances of lsq_knn.hip (which reads the queries itself)
 template <int QT, int MODE>
-int launch_producer(hipStream_t s, const float *LUT, const AdcInput &in, const int *qsel, int q0, int nqb, int stride, int ns, const uint32_t *tau,
-                    unsigned *count, int cap, uint64_t *out, int idbits) {
-    if (in.exact())
+int launch_producer(hipStream_t s, const float *LUT, const lsq_search_input &in, const int *qsel, int q0, int nqb, int stride, int ns,
+                    const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits) {
+    if (in.kind == LSQ_SEARCH_EXACT)
         return lsq_knn_launch_scan(s, MODE, in.base, in.bstride, in.Q, in.qstride, qsel, q0, nqb, in.n, in.d, stride, ns, tau, count, cap, out, idbits);
     return launch_scan<QT, MODE>(s, LUT, in, nqb, stride, ns, tau, count, cap, out, idbits);
 }
 
 template <int QT>
-int launch_lut(hipStream_t s, const AdcInput &in, const int *qsel, int q0, int nqb, float *LUT) {
+int launch_lut(hipStream_t s, const lsq_search_input &in, const int *qsel, int q0, int nqb, float *LUT) {
     const int tiles = (nqb + QT - 1) / QT, entries = in.m * LSQ_H, d = in.d;
     if (tiles == 0) return LSQ_OK;
     const int kc = d < ADC_KC ? d : ADC_KC;
     const size_t lds = sizeof(float) * (size_t)QT * kc;
-    if (in.pq()) {
+    if (in.kind == LSQ_SEARCH_PQ) {
         LSQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&adc_pq_lut_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((adc_pq_lut_kernel<QT>), dim3((unsigned)in.m, (unsigned)tiles), dim3(LSQ_H), lds, s, in.Q, in.K, qsel, q0, nqb, in.qstride,
                            d, entries, LUT);
@@ -516,6 +509,22 @@ int sort_segments(lsq_adc_state *st, hipStream_t s, const uint64_t *in, uint64_t
     LSQ_HIP(hipcub::DeviceSegmentedRadixSort::SortKeys(st->tmp.p, bytes, in, out, (int)items, segs, begin, end, 0, end_bit, s));
     return LSQ_OK;
 }
+
+}  // namespace
+
+int lsq_adc_select(lsq_adc_state **pst, hipStream_t s, const uint64_t *recs, uint64_t *sorted, int *seg, const unsigned *count, int *fail,
+                   const int *qsel, int q0, int nqb, int cap, int nn, float *dists, int *idx, int idbits, int end_bit, int id_sub) {
+    if (!*pst) *pst = new lsq_adc_state();
+    int *begin = seg, *end = seg + nqb;
+    hipLaunchKernelGGL(adc_segments_kernel, dim3((unsigned)((nqb + 255) / 256)), dim3(256), 0, s, count, nqb, cap, nn, begin, end, fail);
+    LSQ_TRY(sort_segments(*pst, s, recs, sorted, (int64_t)nqb * cap, nqb, begin, end, end_bit));
+    hipLaunchKernelGGL(adc_gather_kernel, dim3((unsigned)((nn + 255) / 256 < 64 ? (nn + 255) / 256 : 64), (unsigned)nqb), dim3(256), 0, s, sorted,
+                       fail, qsel, q0, nqb, cap, nn, dists, idx, idbits, id_sub);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
+namespace {
 
 struct Plan { int ns, stride, r, cap; bool exhaustive; };
 
@@ -539,34 +548,27 @@ Plan make_plan(int n, int nn, int force_exhaustive) {
 }
 
 template <int QT>
-int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const AdcInput &in, const int *qsel, int q0, int nqb, int nn, const Plan &P,
-              int *h_fail, lsq_linscan_stats *stats, bool timed) {
-    const int n = in.n, entries = in.m * LSQ_H, tiles = (nqb + QT - 1) / QT, id_base = in.pq() ? 1 : 0;
-    int idbits = 1;                                   // ids 1 .. n: the records are (distance key << idbits | id), sorted on their 32 + idbits bits
-    while (idbits < 32 && ((uint64_t)n >> idbits) != 0) ++idbits;
-    if (!in.exact()) LSQ_TRY(st->lut.ensure(sizeof(float) * (size_t)tiles * entries * QT));
+int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const lsq_search_input &in, const int *qsel, int q0, int nqb, int nn,
+              const Plan &P, int *h_fail, lsq_linscan_stats *stats, bool timed) {
+    const int n = in.n, entries = in.m * LSQ_H, tiles = (nqb + QT - 1) / QT;
+    const bool tables = in.kind != LSQ_SEARCH_EXACT;
+    const int idbits = lsq_adc_idbits(n);             // the records are (distance key << idbits | id), sorted on their 32 + idbits bits
+    if (tables) LSQ_TRY(st->lut.ensure(sizeof(float) * (size_t)tiles * entries * QT));
     LSQ_TRY(st->seg.ensure(sizeof(int) * 2 * (size_t)nqb));
     LSQ_TRY(st->fail.ensure(sizeof(int) * (size_t)nqb));
-    int *begin = st->seg.as<int>(), *end = begin + nqb;
     if (timed) LSQ_HIP(hipEventRecord(st->ev[0], s));
-    if (!in.exact()) LSQ_TRY(launch_lut<QT>(s, in, qsel, q0, nqb, st->lut.as<float>()));
+    if (tables) LSQ_TRY(launch_lut<QT>(s, in, qsel, q0, nqb, st->lut.as<float>()));
     if (timed) LSQ_HIP(hipEventRecord(st->ev[1], s));
-    const unsigned gblocks = (unsigned)((nqb + 255) / 256);
-    int seg_len;
     if (P.exhaustive) {
-        seg_len = n;
         LSQ_TRY(st->keys_a.ensure(sizeof(uint64_t) * (size_t)nqb * n));
         LSQ_TRY(st->keys_b.ensure(sizeof(uint64_t) * (size_t)nqb * n));
         if (timed) { LSQ_HIP(hipEventRecord(st->ev[2], s)); }
         LSQ_TRY((launch_producer<QT, 1>(s, st->lut.as<float>(), in, qsel, q0, nqb, 1, n, nullptr, nullptr, n, st->keys_a.as<uint64_t>(), idbits)));
         if (timed) LSQ_HIP(hipEventRecord(st->ev[3], s));
-        hipLaunchKernelGGL(adc_segments_kernel, dim3(gblocks), dim3(256), 0, s, (const unsigned *)nullptr, nqb, n, nn, begin, end, (int *)nullptr);
-        LSQ_TRY(sort_segments(st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), (int64_t)nqb * n, nqb, begin, end, 32 + idbits));
-        hipLaunchKernelGGL(adc_gather_kernel, dim3((unsigned)((nn + 255) / 256 < 64 ? (nn + 255) / 256 : 64), (unsigned)nqb), dim3(256), 0, s,
-                           st->keys_b.as<uint64_t>(), (const int *)nullptr, qsel, q0, nqb, n, nn, dists, idx, idbits, id_base);
+        LSQ_TRY(lsq_adc_select(&st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), st->seg.as<int>(), nullptr, nullptr, qsel, q0, nqb, n, nn,
+                               dists, idx, idbits, 32 + idbits, in.id_sub()));
         if (stats) stats->candidates += (int64_t)nqb * n;
     } else {
-        seg_len = P.cap;
         const size_t items = (size_t)nqb * (size_t)(P.cap > P.ns ? P.cap : P.ns);
         LSQ_TRY(st->keys_a.ensure(sizeof(uint64_t) * items));
         LSQ_TRY(st->keys_b.ensure(sizeof(uint64_t) * items));
@@ -582,10 +584,8 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const Ad
         LSQ_TRY((launch_producer<QT, 0>(s, st->lut.as<float>(), in, qsel, q0, nqb, 1, n, st->tau.as<uint32_t>(), st->count.as<unsigned>(), P.cap,
                                         st->keys_a.as<uint64_t>(), idbits)));
         if (timed) LSQ_HIP(hipEventRecord(st->ev[3], s));
-        hipLaunchKernelGGL(adc_segments_kernel, dim3(gblocks), dim3(256), 0, s, st->count.as<unsigned>(), nqb, P.cap, nn, begin, end, st->fail.as<int>());
-        LSQ_TRY(sort_segments(st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), (int64_t)nqb * P.cap, nqb, begin, end, 32 + idbits));
-        hipLaunchKernelGGL(adc_gather_kernel, dim3((unsigned)((nn + 255) / 256 < 64 ? (nn + 255) / 256 : 64), (unsigned)nqb), dim3(256), 0, s,
-                           st->keys_b.as<uint64_t>(), st->fail.as<int>(), qsel, q0, nqb, P.cap, nn, dists, idx, idbits, id_base);
+        LSQ_TRY(lsq_adc_select(&st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(),
+                               st->fail.as<int>(), qsel, q0, nqb, P.cap, nn, dists, idx, idbits, 32 + idbits, in.id_sub()));
         LSQ_HIP(hipMemcpyAsync(h_fail, st->fail.p, sizeof(int) * (size_t)nqb, hipMemcpyDeviceToHost, s));
         if (stats) {
             std::vector<unsigned> hc((size_t)nqb);
@@ -594,8 +594,6 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const Ad
             for (unsigned c : hc) stats->candidates += c;
         }
     }
-    (void)seg_len;
-    LSQ_HIP(hipGetLastError());
     if (timed) {
         LSQ_HIP(hipEventRecord(st->ev[4], s));
         LSQ_HIP(hipEventSynchronize(st->ev[4]));
@@ -604,7 +602,7 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const Ad
         LSQ_HIP(hipEventElapsedTime(&b, st->ev[1], st->ev[2]));
         LSQ_HIP(hipEventElapsedTime(&c, st->ev[2], st->ev[3]));
         LSQ_HIP(hipEventElapsedTime(&e, st->ev[3], st->ev[4]));
-        if (in.exact()) a = 0.0f;                     // no tables
+        if (!tables) a = 0.0f;
         stats->lut_ms += a; stats->sample_ms += b; stats->scan_ms += c; stats->select_ms += e;
     } else {
         LSQ_HIP(hipStreamSynchronize(s));
@@ -612,16 +610,18 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const Ad
     return LSQ_OK;
 }
 
-// All pointers are device pointers.  force_exhaustive: test hook (every query by the exhaustive road).
-int adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const AdcInput &in, int nq, int nn, int force_exhaustive, int sample_override,
-               lsq_linscan_stats *stats, int timed) {
+}  // namespace
+
+int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const lsq_search_input &in, int nq, int nn, const lsq_search_opts &opt) {
     if (!*pst) *pst = new lsq_adc_state();
     lsq_adc_state *st = *pst;
+    lsq_linscan_stats *stats = opt.stats;
     const int n = in.n;
+    const bool timed = opt.timed != 0;
     if (timed) for (hipEvent_t &e : st->ev) if (!e) LSQ_HIP(hipEventCreate(&e));
-    Plan P = make_plan(n, nn, force_exhaustive);
-    if (!P.exhaustive && sample_override > 0) {      // test hook: a deliberately wrong threshold rank (forces the fallback road)
-        P.r = sample_override < P.ns ? sample_override : P.ns;
+    Plan P = make_plan(n, nn, opt.force_exhaustive);
+    if (!P.exhaustive && opt.rank_override > 0) {    // test hook: a deliberately wrong threshold rank (forces the fallback road)
+        P.r = opt.rank_override < P.ns ? opt.rank_override : P.ns;
     }
     const bool wide = in.m <= 8;                     // 16 queries per block up to m = 8 (128 KiB of tables), 8 above
     const int64_t per_query = P.exhaustive ? n : (P.cap > P.ns ? P.cap : P.ns);
@@ -635,8 +635,8 @@ int adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const
     for (int q0 = 0; q0 < nq; q0 += (int)qb) {
         const int nqb = (int)std::min<int64_t>(qb, nq - q0);
         h_fail.assign((size_t)nqb, 0);
-        if (wide) LSQ_TRY(run_batch<16>(st, s, dists, idx, in, nullptr, q0, nqb, nn, P, h_fail.data(), stats, timed != 0));
-        else LSQ_TRY(run_batch<8>(st, s, dists, idx, in, nullptr, q0, nqb, nn, P, h_fail.data(), stats, timed != 0));
+        if (wide) LSQ_TRY(run_batch<16>(st, s, dists, idx, in, nullptr, q0, nqb, nn, P, h_fail.data(), stats, timed));
+        else LSQ_TRY(run_batch<8>(st, s, dists, idx, in, nullptr, q0, nqb, nn, P, h_fail.data(), stats, timed));
         if (!P.exhaustive) {
             LSQ_HIP(hipStreamSynchronize(s));
             for (int t = 0; t < nqb; ++t) if (h_fail[(size_t)t]) failed.push_back(q0 + t);
@@ -655,8 +655,8 @@ int adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const
         for (size_t f0 = 0; f0 < failed.size(); f0 += (size_t)fb) {
             const int nqb = (int)std::min<size_t>((size_t)fb, failed.size() - f0);
             const int *qs = st->qsel.as<int>() + f0;
-            if (wide) LSQ_TRY(run_batch<16>(st, s, dists, idx, in, qs, 0, nqb, nn, E, nullptr, stats, timed != 0));
-            else LSQ_TRY(run_batch<8>(st, s, dists, idx, in, qs, 0, nqb, nn, E, nullptr, stats, timed != 0));
+            if (wide) LSQ_TRY(run_batch<16>(st, s, dists, idx, in, qs, 0, nqb, nn, E, nullptr, stats, timed));
+            else LSQ_TRY(run_batch<8>(st, s, dists, idx, in, qs, 0, nqb, nn, E, nullptr, stats, timed));
             if (stats) stats->batches += 1;
         }
         if (stats) stats->fallback_queries += (int64_t)failed.size();
@@ -666,109 +666,40 @@ int adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const
     return LSQ_OK;
 }
 
-}  // namespace
-
-int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const uint8_t *codes, const float *Q, const float *K,
-                   const float *dbnorms, int nq, int n, int m, int d, int nn, int force_exhaustive, int sample_override, lsq_linscan_stats *stats,
-                   int timed) {
-    const AdcInput in{codes, m, Q, d, K, dbnorms, n, m, d};
-    return adc_search(s, pst, dists, idx, in, nq, nn, force_exhaustive, sample_override, stats, timed);
-}
-
-// host-buffer entry: upload, search, download
-int lsq_adc_search_host(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const unsigned char *codes, const float *Q, const float *K,
-                        const float *dbnorms, int nq, int n, int m, int d, int nn, int force_exhaustive, int sample_override, lsq_linscan_stats *stats,
-                        int timed) {
+// Host-buffer entry: upload what the reference reads of every operand -- rows up to their last element read, so a buffer need not extend to the end of
+// its last row's stride --, search, download.  The callers guarantee n >= 1 and nq >= 1: the extents count whole strides up to the LAST row.
+int lsq_adc_search_host(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const lsq_search_input &host, int nq, int nn,
+                        const lsq_search_opts &opt) {
     if (!*pst) *pst = new lsq_adc_state();
     lsq_adc_state *st = *pst;
-    LSQ_TRY(st->h_codes.ensure((size_t)n * m + 16));
-    LSQ_TRY(st->h_q.ensure(sizeof(float) * (size_t)nq * d));
-    LSQ_TRY(st->h_k.ensure(sizeof(float) * (size_t)m * LSQ_H * d));
-    LSQ_TRY(st->h_norms.ensure(sizeof(float) * (size_t)n));
-    LSQ_TRY(st->h_dists.ensure(sizeof(float) * (size_t)nq * nn));
-    LSQ_TRY(st->h_idx.ensure(sizeof(int) * (size_t)nq * nn));
-    LSQ_HIP(hipMemcpyAsync(st->h_codes.p, codes, (size_t)n * m, hipMemcpyHostToDevice, s));
-    LSQ_HIP(hipMemcpyAsync(st->h_q.p, Q, sizeof(float) * (size_t)nq * d, hipMemcpyHostToDevice, s));
-    LSQ_HIP(hipMemcpyAsync(st->h_k.p, K, sizeof(float) * (size_t)m * LSQ_H * d, hipMemcpyHostToDevice, s));
-    LSQ_HIP(hipMemcpyAsync(st->h_norms.p, dbnorms, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
-    LSQ_TRY(lsq_adc_search(s, pst, st->h_dists.as<float>(), st->h_idx.as<int>(), st->h_codes.as<uint8_t>(), st->h_q.as<float>(), st->h_k.as<float>(),
-                           st->h_norms.as<float>(), nq, n, m, d, nn, force_exhaustive, sample_override, stats, timed));
-    LSQ_HIP(hipMemcpyAsync(dists, st->h_dists.p, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
-    LSQ_HIP(hipMemcpyAsync(idx, st->h_idx.p, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
+    const bool exact = host.kind == LSQ_SEARCH_EXACT;
+    const size_t n = (size_t)host.n, m = (size_t)host.m, d = (size_t)host.d;
+    const size_t db_bytes = exact ? sizeof(float) * ((n - 1) * (size_t)host.bstride + d) : (n - 1) * (size_t)host.cstride + m;
+    const size_t q_bytes = sizeof(float) * ((size_t)(nq - 1) * (size_t)host.qstride + (size_t)host.query_width());
+    const size_t table_bytes = exact ? 0 : sizeof(float) * m * LSQ_H * d, out_items = (size_t)nq * (size_t)nn;
+    lsq_search_input in = host;
+    LSQ_TRY(st->h_db.ensure(db_bytes + (exact ? 0 : 16)));      // code rows: 16 bytes of slack past the last one, allocated and never uploaded
+    LSQ_TRY(st->h_q.ensure(q_bytes));
+    LSQ_TRY(st->h_dists.ensure(sizeof(float) * out_items));
+    LSQ_TRY(st->h_idx.ensure(sizeof(int) * out_items));
+    LSQ_HIP(hipMemcpyAsync(st->h_db.p, exact ? (const void *)host.base : (const void *)host.codes, db_bytes, hipMemcpyHostToDevice, s));
+    LSQ_HIP(hipMemcpyAsync(st->h_q.p, host.Q, q_bytes, hipMemcpyHostToDevice, s));
+    if (exact) in.base = st->h_db.as<float>();
+    else in.codes = st->h_db.as<uint8_t>();
+    in.Q = st->h_q.as<float>();
+    if (!exact) {
+        LSQ_TRY(st->h_tables.ensure(table_bytes));
+        LSQ_HIP(hipMemcpyAsync(st->h_tables.p, host.K, table_bytes, hipMemcpyHostToDevice, s));
+        in.K = st->h_tables.as<float>();
+    }
+    if (host.kind == LSQ_SEARCH_LSQ) {
+        LSQ_TRY(st->h_norms.ensure(sizeof(float) * n));
+        LSQ_HIP(hipMemcpyAsync(st->h_norms.p, host.dbnorms, sizeof(float) * n, hipMemcpyHostToDevice, s));
+        in.dbnorms = st->h_norms.as<float>();
+    }
+    LSQ_TRY(lsq_adc_search(s, pst, st->h_dists.as<float>(), st->h_idx.as<int>(), in, nq, nn, opt));
+    LSQ_HIP(hipMemcpyAsync(dists, st->h_dists.p, sizeof(float) * out_items, hipMemcpyDeviceToHost, s));
+    LSQ_HIP(hipMemcpyAsync(idx, st->h_idx.p, sizeof(int) * out_items, hipMemcpyDeviceToHost, s));
     LSQ_HIP(hipStreamSynchronize(s));
-    return LSQ_OK;
-}
-
-// PQ / OPQ (linscan_aqd.cpp): codes [n][cstride], centres [m][h][subdim], query rows qstride floats apart; ids out 0-based
-int lsq_adc_search_pq(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const uint8_t *codes, int cstride, const float *centers,
-                      const float *Q, int qstride, int nq, int n, int m, int subdim, int nn, int force_exhaustive, int sample_override,
-                      lsq_linscan_stats *stats, int timed) {
-    const AdcInput in{codes, cstride, Q, qstride, centers, nullptr, n, m, subdim};
-    return adc_search(s, pst, dists, idx, in, nq, nn, force_exhaustive, sample_override, stats, timed);
-}
-
-// host-buffer entry: upload what the reference reads (rows up to their m-th byte / (m subdim)-th float), search, download
-int lsq_adc_search_pq_host(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const uint8_t *codes, int cstride, const float *centers,
-                           const float *Q, int qstride, int nq, int n, int m, int subdim, int nn, int force_exhaustive, int sample_override,
-                           lsq_linscan_stats *stats, int timed) {
-    if (!*pst) *pst = new lsq_adc_state();
-    lsq_adc_state *st = *pst;
-    const size_t code_bytes = (size_t)(n - 1) * cstride + m, q_floats = (size_t)(nq - 1) * qstride + (size_t)m * subdim;
-    LSQ_TRY(st->h_codes.ensure(code_bytes + 16));
-    LSQ_TRY(st->h_q.ensure(sizeof(float) * q_floats));
-    LSQ_TRY(st->h_k.ensure(sizeof(float) * (size_t)m * LSQ_H * subdim));
-    LSQ_TRY(st->h_dists.ensure(sizeof(float) * (size_t)nq * nn));
-    LSQ_TRY(st->h_idx.ensure(sizeof(int) * (size_t)nq * nn));
-    LSQ_HIP(hipMemcpyAsync(st->h_codes.p, codes, code_bytes, hipMemcpyHostToDevice, s));
-    LSQ_HIP(hipMemcpyAsync(st->h_q.p, Q, sizeof(float) * q_floats, hipMemcpyHostToDevice, s));
-    LSQ_HIP(hipMemcpyAsync(st->h_k.p, centers, sizeof(float) * (size_t)m * LSQ_H * subdim, hipMemcpyHostToDevice, s));
-    LSQ_TRY(lsq_adc_search_pq(s, pst, st->h_dists.as<float>(), st->h_idx.as<int>(), st->h_codes.as<uint8_t>(), cstride, st->h_k.as<float>(),
-                              st->h_q.as<float>(), qstride, nq, n, m, subdim, nn, force_exhaustive, sample_override, stats, timed));
-    LSQ_HIP(hipMemcpyAsync(dists, st->h_dists.p, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
-    LSQ_HIP(hipMemcpyAsync(idx, st->h_idx.p, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
-    LSQ_HIP(hipStreamSynchronize(s));
-    return LSQ_OK;
-}
-
-// exact k-NN: base rows [n][ldb], query rows [nq][ldq] (d floats of each read); ids out 0-based
-int lsq_adc_search_exact(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const float *base, int ldb, const float *Q, int ldq, int nq, int n,
-                         int d, int nn, int force_exhaustive, int sample_override, lsq_linscan_stats *stats, int timed) {
-    AdcInput in{nullptr, 0, Q, ldq, nullptr, nullptr, n, 0, d};
-    in.base = base;
-    in.bstride = ldb;
-    return adc_search(s, pst, dists, idx, in, nq, nn, force_exhaustive, sample_override, stats, timed);
-}
-
-// host-buffer entry: upload the rows up to their d-th float, search, download
-int lsq_adc_search_exact_host(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, const float *base, int ldb, const float *Q, int ldq, int nq,
-                              int n, int d, int nn, int force_exhaustive, int sample_override, lsq_linscan_stats *stats, int timed) {
-    if (!*pst) *pst = new lsq_adc_state();
-    lsq_adc_state *st = *pst;
-    const size_t b_floats = (size_t)(n - 1) * ldb + d, q_floats = (size_t)(nq - 1) * ldq + d;
-    LSQ_TRY(st->h_k.ensure(sizeof(float) * b_floats));
-    LSQ_TRY(st->h_q.ensure(sizeof(float) * q_floats));
-    LSQ_TRY(st->h_dists.ensure(sizeof(float) * (size_t)nq * nn));
-    LSQ_TRY(st->h_idx.ensure(sizeof(int) * (size_t)nq * nn));
-    LSQ_HIP(hipMemcpyAsync(st->h_k.p, base, sizeof(float) * b_floats, hipMemcpyHostToDevice, s));
-    LSQ_HIP(hipMemcpyAsync(st->h_q.p, Q, sizeof(float) * q_floats, hipMemcpyHostToDevice, s));
-    LSQ_TRY(lsq_adc_search_exact(s, pst, st->h_dists.as<float>(), st->h_idx.as<int>(), st->h_k.as<float>(), ldb, st->h_q.as<float>(), ldq, nq, n, d, nn,
-                                 force_exhaustive, sample_override, stats, timed));
-    LSQ_HIP(hipMemcpyAsync(dists, st->h_dists.p, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
-    LSQ_HIP(hipMemcpyAsync(idx, st->h_idx.p, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
-    LSQ_HIP(hipStreamSynchronize(s));
-    return LSQ_OK;
-}
-
-// The exhaustive road's selection for another producer of MODE 1 records (lsq_rerank.hip): full segments, sorted on end_bit bits, the first nn gathered
-int lsq_adc_select_full(lsq_adc_state **pst, hipStream_t s, const uint64_t *recs, uint64_t *sorted, int *seg, int q0, int nqb, int cap, int nn,
-                        float *dists, int *idx, int idbits, int end_bit, int id_sub) {
-    if (!*pst) *pst = new lsq_adc_state();
-    int *begin = seg, *end = seg + nqb;
-    hipLaunchKernelGGL(adc_segments_kernel, dim3((unsigned)((nqb + 255) / 256)), dim3(256), 0, s, (const unsigned *)nullptr, nqb, cap, nn, begin, end,
-                       (int *)nullptr);
-    LSQ_TRY(sort_segments(*pst, s, recs, sorted, (int64_t)nqb * cap, nqb, begin, end, end_bit));
-    hipLaunchKernelGGL(adc_gather_kernel, dim3((unsigned)((nn + 255) / 256 < 64 ? (nn + 255) / 256 : 64), (unsigned)nqb), dim3(256), 0, s, sorted,
-                       (const int *)nullptr, (const int *)nullptr, q0, nqb, cap, nn, dists, idx, idbits, id_sub);
-    LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }

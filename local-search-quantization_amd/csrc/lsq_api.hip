@@ -103,7 +103,7 @@ struct lsq_ctx {
     lsq_spgl1_state *spgl1 = nullptr;                  // device SPGL1 (lsq_spgl1.hip): work buffers, created on first use
     lsq_adc_state *adc = nullptr;                      // device ADC scan (lsq_adc.hip): buffers, created on first use
     lsq_linscan_stats adc_stats{};
-    int adc_exhaustive = 0, adc_rank = 0;              // options "linscan_exhaustive", "linscan_rank": test hooks of the scan's selection
+    lsq_search_opts search;                            // options "linscan_exhaustive", "linscan_rank": test hooks of the scan's selection (search_opts fills in the rest per call)
     int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
     DevBuf sX, sX2, sK, sB16, sOut16, sTight, sF32;    // staging for the host-buffer entry points (sX/sX2: double-buffered X chunks)
     DevBuf sSample, sSigmaS;                           // host-buffer pipeline: the level sample (compacted rows of X) and its sigma
@@ -288,10 +288,10 @@ extern "C" int lsq_set_option(lsq_ctx *c, const char *key, int64_t value) {
         if (value < 0) { lsq_set_error("filter_fallback_div must be >= 0"); return LSQ_EINVAL; }
         c->fallback_div = value;
     }
-    else if (!strcmp(key, "linscan_exhaustive")) c->adc_exhaustive = value != 0;
+    else if (!strcmp(key, "linscan_exhaustive")) c->search.force_exhaustive = value != 0;
     else if (!strcmp(key, "linscan_rank")) {
         if (value < 0) { lsq_set_error("linscan_rank must be >= 0"); return LSQ_EINVAL; }
-        c->adc_rank = (int)value;
+        c->search.rank_override = (int)value;
     }
     else if (!strcmp(key, "rerank_batch")) {
         if (value < 0) { lsq_set_error("rerank_batch must be >= 0"); return LSQ_EINVAL; }
@@ -417,14 +417,33 @@ static int linscan_check(const char *fn, const void *a, const void *b, const voi
     return LSQ_OK;
 }
 
+// the context's hooks, with where this call's statistics go and whether its phases are timed
+static lsq_search_opts search_opts(const lsq_ctx *c, lsq_linscan_stats *stats) {
+    lsq_search_opts o = c->search;
+    o.stats = stats;
+    o.timed = c->profile;
+    return o;
+}
+
+// the three kinds of search (lsq_search_input); the pointers are all device pointers or all host pointers
+static lsq_search_input lsq_input(const uint8_t *codes, const float *Q, const float *K, const float *dbnorms, int n, int m, int d) {
+    return {LSQ_SEARCH_LSQ, codes, m, Q, d, K, dbnorms, n, m, d, nullptr, 0};
+}
+static lsq_search_input pq_input(const uint8_t *codes, int cstride, const float *centers, const float *Q, int qstride, int n, int m, int subdim) {
+    return {LSQ_SEARCH_PQ, codes, cstride, Q, qstride, centers, nullptr, n, m, subdim, nullptr, 0};
+}
+static lsq_search_input exact_input(const float *base, int ldb, const float *Q, int ldq, int n, int d) {
+    return {LSQ_SEARCH_EXACT, nullptr, 0, Q, ldq, nullptr, nullptr, n, 0, d, base, ldb};
+}
+
 extern "C" int lsq_linscan_dev(lsq_ctx *c, float *d_dists, int *d_idx, const uint8_t *d_codes, const float *d_queries, const float *d_codebooks,
                                const float *d_dbnorms, int nqueries, int ncodes, int m, int h, int d, int nn) {
     if (!c) { lsq_set_error("lsq_linscan_dev: null context"); return LSQ_EINVAL; }
     LSQ_TRY(linscan_check("lsq_linscan_dev", d_dists, d_idx, d_codes, d_queries, d_codebooks, d_dbnorms, nqueries, ncodes, m, h, d, nn));
     if (nqueries == 0) return LSQ_OK;
     LSQ_TRY(use_device(c));
-    return lsq_adc_search(c->stream, &c->adc, d_dists, d_idx, d_codes, d_queries, d_codebooks, d_dbnorms, nqueries, ncodes, m, d, nn, c->adc_exhaustive,
-                          c->adc_rank, &c->adc_stats, c->profile);
+    return lsq_adc_search(c->stream, &c->adc, d_dists, d_idx, lsq_input(d_codes, d_queries, d_codebooks, d_dbnorms, ncodes, m, d), nqueries, nn,
+                          search_opts(c, &c->adc_stats));
 }
 
 extern "C" int lsq_linscan(lsq_ctx *c, float *dists, int *idx, const unsigned char *codes, const float *queries, const float *codebooks,
@@ -433,8 +452,8 @@ extern "C" int lsq_linscan(lsq_ctx *c, float *dists, int *idx, const unsigned ch
     LSQ_TRY(linscan_check("lsq_linscan", dists, idx, codes, queries, codebooks, dbnorms, nqueries, ncodes, m, h, d, nn));
     if (nqueries == 0) return LSQ_OK;
     LSQ_TRY(use_device(c));
-    return lsq_adc_search_host(c->stream, &c->adc, dists, idx, codes, queries, codebooks, dbnorms, nqueries, ncodes, m, d, nn, c->adc_exhaustive,
-                               c->adc_rank, &c->adc_stats, c->profile);
+    return lsq_adc_search_host(c->stream, &c->adc, dists, idx, lsq_input(codes, queries, codebooks, dbnorms, ncodes, m, d), nqueries, nn,
+                               search_opts(c, &c->adc_stats));
 }
 
 // the PQ / OPQ scan: the host drop-in's checks (lsq_linscan.hip), then the device limits of lsq_linscan
@@ -452,8 +471,8 @@ extern "C" int lsq_linscan_pq_dev(lsq_ctx *c, float *d_dists, uint32_t *d_res, c
     LSQ_TRY(linscan_pq_check("lsq_linscan_pq_dev", d_dists, d_res, d_codes, d_centers, d_queries, N, NQ, B, K, dim1codes, dim1queries, subdim));
     if (NQ == 0) return LSQ_OK;
     LSQ_TRY(use_device(c));
-    return lsq_adc_search_pq(c->stream, &c->adc, d_dists, reinterpret_cast<int *>(d_res), d_codes, dim1codes, d_centers, d_queries, dim1queries,
-                             (int)NQ, N, B / 8, subdim, K, c->adc_exhaustive, c->adc_rank, &c->adc_stats, c->profile);
+    return lsq_adc_search(c->stream, &c->adc, d_dists, reinterpret_cast<int *>(d_res),
+                          pq_input(d_codes, dim1codes, d_centers, d_queries, dim1queries, N, B / 8, subdim), (int)NQ, K, search_opts(c, &c->adc_stats));
 }
 
 extern "C" int lsq_linscan_pq(lsq_ctx *c, float *dists, uint32_t *res, const uint8_t *codes, const float *centers, const float *queries, int N,
@@ -462,8 +481,8 @@ extern "C" int lsq_linscan_pq(lsq_ctx *c, float *dists, uint32_t *res, const uin
     LSQ_TRY(linscan_pq_check("lsq_linscan_pq", dists, res, codes, centers, queries, N, NQ, B, K, dim1codes, dim1queries, subdim));
     if (NQ == 0) return LSQ_OK;
     LSQ_TRY(use_device(c));
-    return lsq_adc_search_pq_host(c->stream, &c->adc, dists, reinterpret_cast<int *>(res), codes, dim1codes, centers, queries, dim1queries, (int)NQ,
-                                  N, B / 8, subdim, K, c->adc_exhaustive, c->adc_rank, &c->adc_stats, c->profile);
+    return lsq_adc_search_host(c->stream, &c->adc, dists, reinterpret_cast<int *>(res), pq_input(codes, dim1codes, centers, queries, dim1queries, N, B / 8, subdim),
+                               (int)NQ, K, search_opts(c, &c->adc_stats));
 }
 
 // exact k-NN: the host drop-in's checks (lsq_linscan.hip), then the device search (lsq_knn.hip under lsq_adc.hip's selection)
@@ -472,8 +491,8 @@ extern "C" int lsq_knn_exact_dev(lsq_ctx *c, float *d_dists, uint32_t *d_ids, co
     if (!c) { lsq_set_error("lsq_knn_exact_dev: null context"); return LSQ_EINVAL; }
     LSQ_TRY(lsq_knn_exact_check("lsq_knn_exact_dev", d_dists, d_ids, d_base, d_queries, n, nq, d, ldb, ldq, nn));
     LSQ_TRY(use_device(c));
-    return lsq_adc_search_exact(c->stream, &c->adc, d_dists, reinterpret_cast<int *>(d_ids), d_base, ldb, d_queries, ldq, nq, n, d, nn, c->adc_exhaustive,
-                                c->adc_rank, &c->adc_stats, c->profile);
+    return lsq_adc_search(c->stream, &c->adc, d_dists, reinterpret_cast<int *>(d_ids), exact_input(d_base, ldb, d_queries, ldq, n, d), nq, nn,
+                          search_opts(c, &c->adc_stats));
 }
 
 extern "C" int lsq_knn_exact(lsq_ctx *c, float *dists, uint32_t *ids, const float *base, const float *queries, int n, int nq, int d, int ldb, int ldq,
@@ -481,8 +500,8 @@ extern "C" int lsq_knn_exact(lsq_ctx *c, float *dists, uint32_t *ids, const floa
     if (!c) { lsq_set_error("lsq_knn_exact: null context"); return LSQ_EINVAL; }
     LSQ_TRY(lsq_knn_exact_check("lsq_knn_exact", dists, ids, base, queries, n, nq, d, ldb, ldq, nn));
     LSQ_TRY(use_device(c));
-    return lsq_adc_search_exact_host(c->stream, &c->adc, dists, reinterpret_cast<int *>(ids), base, ldb, queries, ldq, nq, n, d, nn, c->adc_exhaustive,
-                                     c->adc_rank, &c->adc_stats, c->profile);
+    return lsq_adc_search_host(c->stream, &c->adc, dists, reinterpret_cast<int *>(ids), exact_input(base, ldb, queries, ldq, n, d), nq, nn,
+                               search_opts(c, &c->adc_stats));
 }
 
 extern "C" int lsq_get_linscan_stats(lsq_ctx *c, lsq_linscan_stats *out) {
@@ -584,7 +603,7 @@ static int index_rerank_dev(lsq_index *ix, float *d_dists, int *d_ids, const flo
     LSQ_TRY(ix->rec_b.ensure(sizeof(uint64_t) * (size_t)qb * L));
     LSQ_TRY(ix->seg.ensure(sizeof(int) * 2 * (size_t)qb));
     LSQ_HIP(hipMemsetAsync(ix->counter.p, 0, sizeof(unsigned long long), s));
-    const int idbits = lsq_rerank_idbits(ix->n);
+    const int idbits = lsq_adc_idbits(ix->n);
     for (int q0 = 0; q0 < nq; q0 += (int)qb) {
         const int nqb = (int)std::min<int64_t>(qb, nq - q0);
         if (timed) LSQ_HIP(hipEventRecord(ix->ev[0], s));
@@ -592,8 +611,8 @@ static int index_rerank_dev(lsq_index *ix, float *d_dists, int *d_ids, const flo
                                   ix->counter.as<unsigned long long>()));
         if (timed) LSQ_HIP(hipEventRecord(ix->ev[1], s));
         // records: (outside-the-base bit, distance key, row + 1); the gather hands out row + 1 - (1 - id_base)
-        LSQ_TRY(lsq_adc_select_full(&ix->adc, s, ix->rec_a.as<uint64_t>(), ix->rec_b.as<uint64_t>(), ix->seg.as<int>(), q0, nqb, L, nn, d_dists, d_ids, idbits,
-                                    33 + idbits, 1 - id_base));
+        LSQ_TRY(lsq_adc_select(&ix->adc, s, ix->rec_a.as<uint64_t>(), ix->rec_b.as<uint64_t>(), ix->seg.as<int>(), nullptr, nullptr, nullptr, q0, nqb, L, nn,
+                               d_dists, d_ids, idbits, 33 + idbits, 1 - id_base));
         if (timed) {
             LSQ_HIP(hipEventRecord(ix->ev[2], s));
             LSQ_HIP(hipEventSynchronize(ix->ev[2]));
@@ -645,7 +664,6 @@ extern "C" int lsq_index_rerank(lsq_index *ix, float *dists, int *ids, const flo
     if (L > (1 << 28)) { lsq_set_error("lsq_index_rerank: needs L <= 2^28 candidates per query (got %d)", L); return LSQ_EINVAL; }      // a batch is >= 1 query
     if (nq == 0) return LSQ_OK;
     LSQ_TRY(use_device(ix->ctx));
-    AsyncOff blocking(ix->ctx);
     hipStream_t s = ix->ctx->stream;
     if (on_device) {
         LSQ_TRY(index_rerank_dev(ix, dists, ids, queries, ldq, cand, nq, L, nn, id_base));
@@ -679,7 +697,6 @@ extern "C" int lsq_index_search(lsq_index *ix, float *dists, int *ids, const flo
     if (nq == 0) return LSQ_OK;
     lsq_ctx *c = ix->ctx;
     LSQ_TRY(use_device(c));
-    AsyncOff blocking(c);
     hipStream_t s = c->stream;
     const int d = ix->d;
     // the scan reads query rows d floats apart
@@ -706,8 +723,7 @@ extern "C" int lsq_index_search(lsq_index *ix, float *dists, int *ids, const flo
         scan_i = ix->short_i.as<int>();
     }
     lsq_linscan_stats st{};
-    LSQ_TRY(lsq_adc_search(s, &ix->adc, scan_d, scan_i, ix->codes, dqs, ix->K, ix->norms, nq, (int)ix->n, ix->m, d, L, c->adc_exhaustive, c->adc_rank, &st,
-                           c->profile));
+    LSQ_TRY(lsq_adc_search(s, &ix->adc, scan_d, scan_i, lsq_input(ix->codes, dqs, ix->K, ix->norms, (int)ix->n, ix->m, d), nq, L, search_opts(c, &st)));
     ix->stats.scan_ms += st.lut_ms + st.sample_ms + st.scan_ms + st.select_ms;
     if (shortlist > 0) LSQ_TRY(index_rerank_dev(ix, out_d, out_i, dqe, lde, scan_i, nq, L, nn, 1));      // the scan's ids are 1-based
     if (!on_device) {

@@ -245,26 +245,31 @@ __device__ inline float lsq_adc_unkey(uint32_t k) {
 }
 struct lsq_adc_state;      // buffers of the scan, owned by the context
 void lsq_adc_free(lsq_adc_state *st);
-// device pointers; force_exhaustive / rank_override: test hooks (options "linscan_exhaustive", "linscan_rank")
-int lsq_adc_search(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const uint8_t *codes, const float *Q, const float *K, const float *dbnorms,
-                   int nq, int n, int m, int d, int nn, int force_exhaustive, int rank_override, lsq_linscan_stats *stats, int timed);
-int lsq_adc_search_host(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const unsigned char *codes, const float *Q, const float *K,
-                        const float *dbnorms, int nq, int n, int m, int d, int nn, int force_exhaustive, int rank_override, lsq_linscan_stats *stats,
-                        int timed);
-// PQ / OPQ (no norm term, 0-based ids out): codes [n][cstride] u8, centers [m][256][subdim], query rows qstride floats apart
-int lsq_adc_search_pq(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const uint8_t *codes, int cstride, const float *centers,
-                      const float *Q, int qstride, int nq, int n, int m, int subdim, int nn, int force_exhaustive, int rank_override,
-                      lsq_linscan_stats *stats, int timed);
-int lsq_adc_search_pq_host(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const uint8_t *codes, int cstride, const float *centers,
-                           const float *Q, int qstride, int nq, int n, int m, int subdim, int nn, int force_exhaustive, int rank_override,
-                           lsq_linscan_stats *stats, int timed);
-
-// exact k-NN (no tables; lsq_knn.hip produces the distances for the same selection): base rows [n][ldb], query rows [nq][ldq], d floats of each
-// read; ids out 0-based
-int lsq_adc_search_exact(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const float *base, int ldb, const float *Q, int ldq, int nq, int n,
-                         int d, int nn, int force_exhaustive, int rank_override, lsq_linscan_stats *stats, int timed);
-int lsq_adc_search_exact_host(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const float *base, int ldb, const float *Q, int ldq, int nq,
-                              int n, int d, int nn, int force_exhaustive, int rank_override, lsq_linscan_stats *stats, int timed);
+// What one call searches.  LSQ: K = [m h][d] codebooks, tables -2<q, c>, + dbnorms[i], 1-based ids out.  PQ / OPQ: K = [m][h][d] sub-space centres
+// (d = subdim), squared-distance tables, no norm term, 0-based ids out.  Exact k-NN: no codes, no tables; lsq_knn.hip computes the squared distances to
+// the float rows base[i * bstride ..] for the same selection, 0-based ids out.
+enum lsq_search_kind { LSQ_SEARCH_LSQ, LSQ_SEARCH_PQ, LSQ_SEARCH_EXACT };
+struct lsq_search_input {
+    lsq_search_kind kind;
+    const uint8_t *codes; int cstride;       // [n][cstride] u8 0-based, the first m bytes of a row used
+    const float *Q; int qstride;             // query rows, qstride floats apart
+    const float *K;
+    const float *dbnorms;
+    int n, m, d;
+    const float *base; int bstride;          // exact: [n][bstride] f32, the first d floats of a row used
+    int query_width() const { return kind == LSQ_SEARCH_PQ ? m * d : d; }      // floats of a query row that are read
+    int id_sub() const { return kind == LSQ_SEARCH_LSQ ? 0 : 1; }              // ids leave as (the record's id field 1 .. n) - id_sub
+};
+// how a call searches: the test hooks of the selection (options "linscan_exhaustive", "linscan_rank"), where its statistics go, and whether its
+// phases are timed (then stats is not null)
+struct lsq_search_opts {
+    int force_exhaustive = 0, rank_override = 0;
+    lsq_linscan_stats *stats = nullptr;
+    int timed = 0;
+};
+// every pointer of `in` a device pointer / a host pointer (staged: upload, search, download); dists, idx [nq][nn] likewise
+int lsq_adc_search(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const lsq_search_input &in, int nq, int nn, const lsq_search_opts &opt);
+int lsq_adc_search_host(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const lsq_search_input &in, int nq, int nn, const lsq_search_opts &opt);
 // the exact scan of one batch in adc_scan_kernel's three modes (0: against tau, 1: every record, 2: sample keys); qsel optional
 int lsq_knn_launch_scan(hipStream_t s, int mode, const float *X, int ldb, const float *Q, int ldq, const int *qsel, int q0, int nqb, int n, int d,
                         int stride, int ns, const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits);
@@ -275,15 +280,17 @@ int lsq_knn_exact_check(const char *fn, const void *dists, const void *ids, cons
 // ---- exact re-rank of shortlists (lsq_rerank.hip): the distance producer of stage two, and the pieces of the scans' selection that serve it ---------
 // records (distance key << idbits | row + 1) of queries q0 .. q0 + nqb - 1 to out[slot * L + s]; cand [.][L] ids in id_base; a candidate outside
 // [id_base, id_base + n) is not dereferenced: bit 32 + idbits, the key of +inf and id field 0 (sort the records on 33 + idbits bits).  *invalid += those
-int lsq_rerank_idbits(int64_t n);
 int lsq_rerank_launch(hipStream_t s, const void *base, int base_u8, int64_t ldb, int64_t n, const float *Q, int64_t ldq, const int *cand, int q0, int nqb,
                       int L, int d, int id_base, uint64_t *out, int idbits, unsigned long long *invalid);
 int lsq_rerank_check(const char *fn, const void *dists, const void *ids, const void *base, const void *queries, const void *cand, int64_t n, int nq, int d,
                      int64_t ldb, int64_t ldq, int L, int nn, int id_base);
-// the exhaustive road's selection over full segments of `cap` records (lsq_adc.hip: adc_segments_kernel, sort_segments, adc_gather_kernel): sorted on
-// end_bit bits, the first nn of every segment handed out as dists / idx [q0 + slot][nn] with idx = id field - id_sub.  seg: 2 nqb ints of scratch
-int lsq_adc_select_full(lsq_adc_state **st, hipStream_t s, const uint64_t *recs, uint64_t *sorted, int *seg, int q0, int nqb, int cap, int nn,
-                        float *dists, int *idx, int idbits, int end_bit, int id_sub);
+// The selection of every producer of records (lsq_adc.hip: adc_segments_kernel, sort_segments, adc_gather_kernel) over nqb lists of `cap` slots: the
+// first count[slot] records of a list (count null: all cap of them) are sorted on end_bit bits and the first nn handed out as dists / idx [query][nn],
+// query = qsel[slot] or q0 + slot, idx = id field - id_sub.  fail (optional, with count): fail[slot] = 1 and nothing handed out for a list that holds
+// fewer than nn records or overflowed.  seg: 2 nqb ints of scratch.  idbits: the width of the id field 1 .. n
+int lsq_adc_idbits(int64_t n);
+int lsq_adc_select(lsq_adc_state **st, hipStream_t s, const uint64_t *recs, uint64_t *sorted, int *seg, const unsigned *count, int *fail, const int *qsel,
+                   int q0, int nqb, int cap, int nn, float *dists, int *idx, int idbits, int end_bit, int id_sub);
 
 // argument checks of the PQ / OPQ scan (lsq_linscan.hip), shared by the host drop-in and the device scan
 int lsq_linscan_pq_check(const char *fn, const void *dists, const void *res, const void *codes, const void *centers, const void *queries, int N,

@@ -182,12 +182,6 @@ int launch(hipStream_t s, const T *X, int64_t ldb, int64_t n, const float *Q, in
 
 }  // namespace
 
-int lsq_rerank_idbits(int64_t n) {
-    int idbits = 1;                                   // ids 1 .. n in the record's id field
-    while (idbits < 31 && ((uint64_t)n >> idbits) != 0) ++idbits;
-    return idbits;
-}
-
 int lsq_rerank_launch(hipStream_t s, const void *base, int base_u8, int64_t ldb, int64_t n, const float *Q, int64_t ldq, const int *cand, int q0, int nqb,
                       int L, int d, int id_base, uint64_t *out, int idbits, unsigned long long *invalid) {
     if (nqb <= 0 || L <= 0) return LSQ_OK;

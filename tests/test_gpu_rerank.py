@@ -173,7 +173,12 @@ def _state_ops(lsq):
     cand = rng.integers(0, n, (nq, 70)).astype(np.int32)
     Xe = rng.integers(0, 256, (300, d)).astype(np.float32)
     B0 = rng.integers(1, H + 1, (300, m)).astype(np.int16)
-    make = {"a": lambda e: e.index(codes, K, dbn, m, base=Xb), "b": lambda e: e.index(codes2, K2, dbn2, 2, base=np.minimum(np.abs(Xb2) * 40, 255).astype(np.uint8))}
+    # the host-buffer searches share one set of staging buffers: every kind of them, at two shapes, and one call that grows the buffers for the rest
+    pq_codes = rng.integers(0, H, (1500, 7)).astype(np.uint8)                   # 3 of the 7 bytes of a row are codes
+    pq_C = rng.standard_normal((3, H, 5)).astype(np.float32)
+    pq_Q = rng.standard_normal((11, 17)).astype(np.float32)                     # 15 of the 17 floats of a row are read
+    codes3, K3, dbn3, _, Xq3 = _database(70000, 16, 8, 16, 80)                  # above the exhaustive road's limit of 65536 codes
+    make ={"a": lambda e: e.index(codes, K, dbn, m, base=Xb), "b": lambda e: e.index(codes2, K2, dbn2, 2, base=np.minimum(np.abs(Xb2) * 40, 255).astype(np.uint8))}
     ops = {
         "index.search": lambda e, ix: ix["a"].search(Xq, 5, shortlist=60),
         "index.rerank": lambda e, ix: ix["a"].rerank(Xq, cand, 70, id_base=0),
@@ -181,6 +186,10 @@ def _state_ops(lsq):
         "linscan": lambda e, ix: e.linscan(codes, Xq, K, dbn, m, 25),
         "knn_exact": lambda e, ix: e.knn_exact(Xb, Xq, 7),
         "encode_icm": lambda e, ix: e.encode_icm(Xe, B0, K, m, [2], 2, 2, True, seed=3),
+        "linscan_pq": lambda e, ix: e.linscan_pq(pq_codes, pq_Q, pq_C, 3, 20, 5),
+        "knn_exact2": lambda e, ix: e.knn_exact(Xb2, Xq2, 5),
+        "linscan2": lambda e, ix: e.linscan(codes2, Xq2, K2, dbn2, 2, 9),
+        "linscan_big": lambda e, ix: e.linscan(codes3, Xq3, K3, dbn3, 8, 10),
     }
     return make, ops
 
