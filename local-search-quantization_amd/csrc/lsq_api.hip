@@ -48,6 +48,16 @@ enum : size_t { SMALL_COUNTERS = 0, SMALL_OBJ = 8192, SMALL_BAD = 8704, SMALL_QP
 static_assert(sizeof(lsq_q16_params) <= SMALL_ACTIVE - SMALL_QP && sizeof(unsigned long long) * LSQ_WALK_COUNTERS <= SMALL_ROAD - SMALL_ACTIVE &&
               sizeof(unsigned long long) * LSQ_WALK_COUNTERS <= SMALL_BYTES - SMALL_PROBE, "the per-call block's windows");
 
+// The road of the resident chunk -- which kernel runs its node updates, and who decided -- and what lsq_get_q16_snapshot needs to know of it after the
+// call.  Forgotten where a chunk's unaries start to be built (start_chunk), written by the verdict (q16_verdict) and the probe (encode_chunk), read by run_sweeps.
+struct ChunkRoad {
+    bool filtered = false;      // the chunk runs the 16-bit filtered walk
+    bool on_device = false;     // option "async": the road lives in road[0] (2 = filtered, 0 = f32), BOTH walks are enqueued and the word picks
+    bool resident = false;      // the chunk's levels are resident: the host verdict named the filtered walk (a later probe may still leave it) ...
+    int64_t cn = 0, row0 = 0;   // ... its rows and its first row within the call
+    int m = 0;
+};
+
 struct lsq_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -75,29 +85,23 @@ struct lsq_ctx {
     // workspace
     DevBuf sci, T, Ts, U, vCur, vNew, active, recCur, recNew, prev, counters, obj, bad;
     DevBuf probe;                                      // walk counters of a chunk's FIRST ILS iteration on the filtered path (read back: is the filter paying off?)
-    unsigned long long *walk_counters = nullptr;       // where the walk launches accumulate their statistics (c->active, or c->probe during that first iteration)
     int64_t probe_div = 8;                             // option "filter_probe_div": after the first iteration the chunk goes to the f32 walk when
                                                        // (refined + f32-routed) * div > recomputed node updates (0 = never)
     DevBuf small;                                              // one block for the small per-call words below (counters, obj, bad, qp, active, road, probe are windows into it)
     char *small_host = nullptr;                                // its pinned mirror
     bool small_packed = false;                                 // this call: every window still in place (an outgrown one gets an allocation of its own)
     DevBuf Uq, Tq, qp, qscratch, qflag, qsigma;                // 16-bit filtered walk: u16 unary planes, u16 slice tables, lsq_q16_params, bound scratch, per-vector out-of-range flags
-    bool chunk_q16 = false;                            // the resident chunk runs the filtered walk (set by build_unaries from the chunk's verdict)
-    // what lsq_get_q16_snapshot needs to know of the last chunk whose unaries were built: its levels are resident (the verdict named the filtered walk),
-    // its rows and m, and its first row within the call
-    bool snap_resident = false;
-    int64_t snap_cn = 0, snap_row0 = 0, call_row0 = 0;
-    int snap_m = 0;
+    lsq_q16_work qw;                                   // ... their pointers, mapped once per chunk (q16_map)
+    ChunkRoad chunk_road;
+    int64_t call_row0 = 0;                             // first row of the chunk being encoded within its call
     // option "async" (lsq_encode_icm_dev only): no host round trip inside the call and none at its end -- the chunk's road (verdict after the unary
     // GEMM, probe after the first ILS iteration) is decided by one-thread kernels into `road`, BOTH walks are enqueued every ILS iteration and the one
     // the word does not name returns at once; objective sums and counters are copied to the caller's (device or pinned) buffers on the stream
     int async_mode = 0;
-    bool chunk_road_dev = false;                       // this chunk's road lives in road[0] (2 = filtered, 0 = f32), not in chunk_q16
     bool pending_fold = false;                         // async calls left walk statistics in `active` / road[1]: folded at the next synchronising entry point
     DevBuf road;
     int64_t fallback_div = 64;                         // option "filter_fallback_div": the chunk goes to the f32 walk when flagged pairs * div > all pairs (0 = never)
     int64_t filter_fallback_chunks = 0;                // chunks the filter handed to the f32 walk (unusable bounds or too many out-of-range vectors)
-    float *q_colshift = nullptr;                       // inside qscratch: the per-candidate shift of the unary levels (double-centred tables)
     lsq_lsqr_state *lsqr = nullptr;                    // device LSQR (lsq_lsqr.hip): work buffers, created on first use
     lsq_kmeans_state *kmeans = nullptr;                // cluster means and k-means++ seeding (lsq_kmeans.hip): work buffers, created on first use
     lsq_spgl1_state *spgl1 = nullptr;                  // device SPGL1 (lsq_spgl1.hip): work buffers, created on first use
@@ -123,7 +127,8 @@ struct lsq_ctx {
 };
 
 static int fold_pending(lsq_ctx *c);
-struct AsyncOff {        // option "async" applies to lsq_encode_icm_dev alone: every other entry point returns results through host memory it must wait for
+struct AsyncOff {        // option "async" applies to the device-resident encodes alone: the other entry points that reach its readers (q16_verdict, begin_call,
+                         // finish_call) return results through host memory they must wait for
     lsq_ctx *c; int saved;
     explicit AsyncOff(lsq_ctx *ctx) : c(ctx), saved(ctx ? ctx->async_mode : 0) { if (c) c->async_mode = 0; }
     ~AsyncOff() { if (c) c->async_mode = saved; }
@@ -366,11 +371,11 @@ static_assert(sizeof(lsq_q16_snapshot_params) == sizeof(lsq_q16_params) && sizeo
               "the public snapshot structure restates lsq_q16_params");
 extern "C" int lsq_get_q16_snapshot(lsq_ctx *c, int what, void *dst, size_t bytes, int64_t *info) {
     LSQ_TRY(use_device(c));
-    if (!c->snap_resident) {
+    if (!c->chunk_road.resident) {
         lsq_set_error("lsq_get_q16_snapshot: no filtered chunk is resident (the last chunk whose unaries were built did not take the 16-bit filtered walk)");
         return LSQ_EINVAL;
     }
-    const size_t cn = (size_t)c->snap_cn, m = (size_t)c->snap_m;
+    const size_t cn = (size_t)c->chunk_road.cn, m = (size_t)c->chunk_road.m;
     const DevBuf *src = nullptr;
     size_t need = 0;
     switch (what) {
@@ -387,8 +392,8 @@ extern "C" int lsq_get_q16_snapshot(lsq_ctx *c, int what, void *dst, size_t byte
         return LSQ_EINVAL;
     }
     if (info) {
-        info[0] = c->snap_cn; info[1] = c->snap_row0; info[2] = c->snap_m;
-        info[3] = lsq_q16_slice_width(c->snap_m); info[4] = lsq_walk_slice_width(c->snap_m); info[5] = c->chunk_q16 ? 1 : 0;
+        info[0] = c->chunk_road.cn; info[1] = c->chunk_road.row0; info[2] = c->chunk_road.m;
+        info[3] = lsq_q16_slice_width(c->chunk_road.m); info[4] = lsq_walk_slice_width(c->chunk_road.m); info[5] = c->chunk_road.filtered ? 1 : 0;
     }
     if (need > 0) LSQ_HIP(hipMemcpyAsync(dst, src->p, need, hipMemcpyDefault, c->stream));
     return LSQ_OK;
@@ -796,7 +801,7 @@ static int check_codes_host(const char *fn, const int16_t *B, int64_t n, int m, 
 static int prepare_tables(lsq_ctx *c, const float *dK, int d, int m) {
     Timer t(c, CAT_TABLES);
     c->tables_changed = 1;
-    c->snap_resident = false;       // the f32 tables the resident levels were taken of are about to change
+    c->chunk_road.resident = false;      // the f32 tables the resident levels were taken of are about to change
     c->tables_valid = false;        // whoever knows the host copy of dK marks it valid again (host_codebooks)
     const int mh = m * LSQ_H;
     LSQ_TRY(c->sci.ensure(sizeof(float) * (size_t)mh));
@@ -811,76 +816,98 @@ static int prepare_tables(lsq_ctx *c, const float *dK, int d, int m) {
     return LSQ_OK;
 }
 
-// unaries of rows [r0, r0 + rows) of a cn-vector chunk (dX points at the chunk's first vector)
+// A chunk's unaries start here: what the last chunk left is forgotten (the ONE reset of the chunk state).  -> the chunk builds levels for the filtered walk
 static bool use_q16(const lsq_ctx *c, int64_t cn) { return c->schedule >= 6 && cn >= c->q16_min; }
+static bool start_chunk(lsq_ctx *c, int64_t cn, int slice) {
+    c->chunk_road = ChunkRoad{};
+    return slice > 0 && use_q16(c, cn);
+}
 
-// q16 part of a chunk's unary build: buffers, sampled value ranges -> parameters -> 16-bit slice tables.  Xsample != nullptr: the host-buffer pipeline
-// (the sample was uploaded ahead of X: lsq_launch_q16_prepare's sample mode); -> *means_out = the codebook means the panel-wise sigma pass needs
+// The ONE map of the filter's device memory (lsq_q16_work): buffers sized for a chunk of cn vectors, the scratch block carved.  Layout of qscratch (bytes):
+// [16] bad, [64, 208) the range keys and the four words after them, [256 ..) table ranges (3 m m floats), then from the next multiple of 256 row minima and
+// column means (m m h floats each), the unary's column shift (m h floats), codebook means (m d floats).  nsample_rows > 0: room for the sample's sigma too.
+static int q16_map(lsq_ctx *c, int d, int64_t cn, int m, int64_t nsample_rows) {
+    LSQ_TRY(c->Uq.ensure(sizeof(uint16_t) * (size_t)m * (size_t)cn * LSQ_H));
+    LSQ_TRY(c->Tq.ensure(sizeof(uint16_t) * (size_t)m * (size_t)(m > 1 ? m - 1 : 1) * LSQ_H * LSQ_H));
+    const size_t off_bad = 16, off_qrange = 64, off_trange = 256;
+    static_assert(off_qrange + sizeof(unsigned) * lsq_q16_work::Q_WORDS <= off_trange, "the range words end before the table ranges");
+    const size_t off_rowmin = (off_trange + sizeof(float) * 3 * (size_t)m * m + 255) & ~(size_t)255;
+    const size_t off_colmean = off_rowmin + sizeof(float) * (size_t)m * m * LSQ_H;
+    const size_t off_colshift = off_colmean + sizeof(float) * (size_t)m * m * LSQ_H;
+    const size_t off_means = off_colshift + sizeof(float) * (size_t)m * LSQ_H;
+    LSQ_TRY(c->qscratch.ensure(off_means + sizeof(float) * (size_t)m * d));
+    LSQ_TRY(c->qsigma.ensure(sizeof(float) * (size_t)cn * m));      // per-(vector, node) unary shift: levels only (lsq_icmq.hip)
+    LSQ_TRY(c->qflag.ensure(sizeof(unsigned short) * (size_t)(cn + 2)));
+    LSQ_TRY(c->qp.ensure(sizeof(lsq_q16_params)));
+    if (nsample_rows > 0) LSQ_TRY(c->sSigmaS.ensure(sizeof(float) * (size_t)nsample_rows * m));
+    char *sc = c->qscratch.as<char>();
+    lsq_q16_work &w = c->qw;
+    w = lsq_q16_work{};
+    w.Tq = c->Tq.as<uint16_t>(); w.Uq = c->Uq.as<uint16_t>();
+    w.bad = reinterpret_cast<int *>(sc + off_bad);
+    w.qrange = reinterpret_cast<unsigned *>(sc + off_qrange);
+    w.trange = reinterpret_cast<float *>(sc + off_trange);
+    w.rowmin = reinterpret_cast<float *>(sc + off_rowmin);
+    w.colmean = reinterpret_cast<float *>(sc + off_colmean);
+    w.colshift = reinterpret_cast<float *>(sc + off_colshift);
+    w.means = reinterpret_cast<float *>(sc + off_means);
+    w.sigma = c->qsigma.as<float>();
+    w.qflag = c->qflag.as<unsigned short>();
+    w.P = c->qp.as<lsq_q16_params>();
+    return LSQ_OK;
+}
+
+// q16 part of a chunk's unary build: the map, sampled value ranges -> parameters -> 16-bit slice tables.  Xsample != nullptr: the host-buffer pipeline
+// (the sample was uploaded ahead of X: lsq_launch_q16_prepare's sample mode)
 // XT (here and below): the element type of X -- float, or uint8_t for the 8-bit entry points (lsq_encode_icm_u8 and its kin): the rows stay 8-bit in the
 // context's chunk buffers and the kernels widen them in registers (lsq_xload.h)
 template <class XT>
-static int q16_prepare_chunk(lsq_ctx *c, const XT *dX, const float *dK, int d, int64_t cn, int m, const XT *Xsample = nullptr, int64_t nsample_rows = 0,
-                             float **means_out = nullptr) {
-    {
-        Timer t(c, CAT_TABLES);
-        LSQ_TRY(c->Uq.ensure(sizeof(uint16_t) * (size_t)m * (size_t)cn * LSQ_H));
-        LSQ_TRY(c->Tq.ensure(sizeof(uint16_t) * (size_t)m * (size_t)(m > 1 ? m - 1 : 1) * LSQ_H * LSQ_H));
-        // scratch: [16] bad, [64..200) range keys, [256..) table ranges (3 m m floats), row minima and column means (m m h floats each), the unary's
-        // column shift (m h floats), codebook means (m d floats)
-        const size_t off_rowmin = (256 + sizeof(float) * 3 * (size_t)m * m + 255) & ~(size_t)255;
-        const size_t off_colmean = off_rowmin + sizeof(float) * (size_t)m * m * LSQ_H;
-        const size_t off_colshift = off_colmean + sizeof(float) * (size_t)m * m * LSQ_H;
-        const size_t off_means = off_colshift + sizeof(float) * (size_t)m * LSQ_H;
-        LSQ_TRY(c->qscratch.ensure(off_means + sizeof(float) * (size_t)m * d));
-        LSQ_TRY(c->qsigma.ensure(sizeof(float) * (size_t)cn * m));      // per-(vector, node) unary shift: levels only (lsq_icmq.hip)
-        LSQ_TRY(c->qflag.ensure(sizeof(unsigned short) * (size_t)(cn + 2)));
-        LSQ_TRY(c->qp.ensure(sizeof(lsq_q16_params)));
-        char *sc = c->qscratch.as<char>();
-        if (Xsample) LSQ_TRY(c->sSigmaS.ensure(sizeof(float) * (size_t)nsample_rows * m));
-        LSQ_TRY(lsq_launch_q16_prepare(c->stream, dX, cn, d, dK, c->sci.as<float>(), c->T.as<float>(), m, c->Tq.as<uint16_t>(),
-                                       reinterpret_cast<int *>(sc + 16), reinterpret_cast<float *>(sc + 256), reinterpret_cast<unsigned *>(sc + 64),
-                                       c->qflag.as<unsigned short>(), c->qp.as<lsq_q16_params>(), c->tables_changed,
-                                       reinterpret_cast<float *>(sc + off_rowmin), reinterpret_cast<float *>(sc + off_means), c->qsigma.as<float>(),
-                                       reinterpret_cast<float *>(sc + off_colmean), reinterpret_cast<float *>(sc + off_colshift), Xsample, nsample_rows,
-                                       Xsample ? c->sSigmaS.as<float>() : nullptr));
-        c->q_colshift = reinterpret_cast<float *>(sc + off_colshift);
-        c->tables_changed = 0;
-        if (means_out) *means_out = reinterpret_cast<float *>(sc + off_means);
-    }
+static int q16_prepare_chunk(lsq_ctx *c, const XT *dX, const float *dK, int d, int64_t cn, int m, const XT *Xsample = nullptr, int64_t nsample_rows = 0) {
+    Timer t(c, CAT_TABLES);
+    LSQ_TRY(q16_map(c, d, cn, m, Xsample ? nsample_rows : 0));
+    if (Xsample) { c->qw.Xsample = Xsample; c->qw.nsample_rows = nsample_rows; c->qw.sigma_sample = c->sSigmaS.as<float>(); }
+    LSQ_TRY(lsq_launch_q16_prepare(c->stream, dX, cn, d, dK, c->sci.as<float>(), c->T.as<float>(), m, c->qw, c->tables_changed));
+    c->tables_changed = 0;
     return LSQ_OK;
+}
+
+// the unary GEMM of rows [r0, r0 + rows) of a cn-vector chunk (dXc points at the chunk's first vector); q16: it also emits the u16 level planes
+// row-major  (slice == 0): U[(j*cn + i)*h + a]                      = chain(x_i[t] * -2 K[j,a][t]) + sci[j,a]
+// slice-major (slice = SL): U[j*cn*h + ((a/SL)*cn + i)*SL + a%SL]   (same values, LDS-slice schedule)
+template <class XT>
+static int unary_gemm(lsq_ctx *c, const XT *dXc, const float *dK, int d, int64_t cn, int m, int slice, int64_t r0, int64_t rows, bool q16) {
+    lsq_gemm_q16 levels;
+    if (q16) {
+        const lsq_q16_work &w = c->qw;
+        levels.Dq = w.Uq; levels.slice_q = lsq_q16_slice_width(m); levels.qp = w.P; levels.qflag = w.qflag; levels.sigma = w.sigma; levels.colshift = w.colshift;
+    }
+    return lsq_launch_chain_gemm(c->stream, dXc + (size_t)r0 * d, dK, c->sci.as<float>(), -2.0f, rows, m * LSQ_H, d, LSQ_H, cn * (int64_t)LSQ_H, LSQ_H,
+                                 c->U.as<float>(), slice, cn, r0, q16 ? &levels : nullptr);
 }
 
 static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m);
 
+// unaries of rows [r0, r0 + rows) of a cn-vector chunk (dX points at the chunk's first vector)
 template <class XT>
 static int build_unaries(lsq_ctx *c, const XT *dX, const float *dK, int d, int64_t cn, int m, int slice, int64_t r0, int64_t rows) {
-    c->chunk_q16 = false;
-    const bool q16 = slice > 0 && r0 == 0 && rows == cn && use_q16(c, cn);
+    const bool q16 = start_chunk(c, cn, slice) && r0 == 0 && rows == cn;
     if (q16) LSQ_TRY(q16_prepare_chunk(c, dX, dK, d, cn, m));      // 16-bit filtered walk: the GEMM below then also emits the u16 planes
     {
         Timer t(c, CAT_UNARIES);
         LSQ_TRY(c->U.ensure(sizeof(float) * (size_t)m * (size_t)cn * LSQ_H));
-        // row-major  (slice == 0): U[(j*cn + i)*h + a]                      = chain(x_i[t] * -2 K[j,a][t]) + sci[j,a]
-        // slice-major (slice = SL): U[j*cn*h + ((a/SL)*cn + i)*SL + a%SL]   (same values, LDS-slice schedule)
-        uint16_t *dq = q16 ? c->Uq.as<uint16_t>() : nullptr;
-        LSQ_TRY(lsq_launch_chain_gemm(c->stream, dX + r0 * d, dK, c->sci.as<float>(), -2.0f, rows, m * LSQ_H, d, LSQ_H, cn * (int64_t)LSQ_H, LSQ_H,
-                                      c->U.as<float>(), slice, cn, r0, dq, dq ? lsq_q16_slice_width(m) : 0, dq ? c->qp.as<lsq_q16_params>() : nullptr, 0,
-                                      dq ? c->qflag.as<unsigned short>() : nullptr, nullptr, 1, dq ? c->qsigma.as<float>() : nullptr,
-                                      dq ? c->q_colshift : nullptr));
+        LSQ_TRY(unary_gemm(c, dX, dK, d, cn, m, slice, r0, rows, q16));
     }
     return q16_verdict(c, q16, cn, m);
 }
 
 // which road the chunk takes after its unary GEMM (filtered walk / f32 walk): on the host, or -- option "async" -- by a one-thread kernel
 static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m) {
-    c->chunk_road_dev = false;
-    c->snap_resident = false;
     if (q16 && c->async_mode) {
         // option "async": the same verdict taken by a one-thread kernel; both walks are enqueued and the word picks (run_sweeps)
         LSQ_TRY(c->road.ensure(2 * sizeof(unsigned)));
         LSQ_TRY(lsq_launch_q16_road(c->stream, c->qp.as<lsq_q16_params>(), c->road.as<unsigned>(), cn * (int64_t)m, c->fallback_div));
-        c->chunk_q16 = true;
-        c->chunk_road_dev = true;
+        c->chunk_road.filtered = true;
+        c->chunk_road.on_device = true;
     } else if (q16) {
         // The chunk's verdict (three words, ONE host round trip per resident chunk -- 10^6 vectors, ~50 ms of work): usable bounds, and few enough
         // (vector, node) pairs outside the sampled level range.  Such pairs take the one-wave-per-vector f32 routine inside the filtered walk (~5x the
@@ -890,10 +917,10 @@ static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m) {
         int verdict[3] = {0, 0, 0};      // lsq_q16_params: ok, oor, nflag
         LSQ_HIP(hipMemcpyAsync(verdict, c->qp.p, sizeof(verdict), hipMemcpyDeviceToHost, c->stream));
         LSQ_HIP(hipStreamSynchronize(c->stream));
-        if (verdict[0] == 1 && (int64_t)verdict[2] * c->fallback_div <= cn * (int64_t)m) c->chunk_q16 = true;
+        if (verdict[0] == 1 && (int64_t)verdict[2] * c->fallback_div <= cn * (int64_t)m) c->chunk_road.filtered = true;
         else c->filter_fallback_chunks += 1;
-        c->snap_resident = c->chunk_q16;
-        c->snap_cn = cn; c->snap_m = m; c->snap_row0 = c->call_row0;
+        c->chunk_road.resident = c->chunk_road.filtered;
+        c->chunk_road.cn = cn; c->chunk_road.m = m; c->chunk_road.row0 = c->call_row0;
     }
     return LSQ_OK;
 }
@@ -905,8 +932,7 @@ static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m) {
 // strided pass reads) are packed on the host and uploaded first, a few MB.  Same codes as the one-piece path: the parameters only steer the filter.
 template <class XT>
 static int build_unaries_from_host(lsq_ctx *c, const XT *Xh, XT *dXc, const float *dK, int d, int64_t cn, int m, int slice) {
-    c->chunk_q16 = false;
-    const bool q16 = slice > 0 && use_q16(c, cn);
+    const bool q16 = start_chunk(c, cn, slice);
     const size_t row_bytes = sizeof(XT) * (size_t)d;
     int64_t prow = (int64_t)((uint64_t)c->panel_bytes / row_bytes) / 128 * 128;      // ~48 MB panels, whole 128-row tiles
     if (prow < 128) prow = 128;
@@ -917,7 +943,6 @@ static int build_unaries_from_host(lsq_ctx *c, const XT *Xh, XT *dXc, const floa
         LSQ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         c->panel_ev.push_back(e);
     }
-    float *means = nullptr;
     if (q16) {
         int64_t rts = 1;
         const int spanels = lsq_q16_sample_rows(cn, d, &rts);
@@ -933,7 +958,7 @@ static int build_unaries_from_host(lsq_ctx *c, const XT *Xh, XT *dXc, const floa
         }
         LSQ_TRY(c->sSample.ensure((size_t)ns * row_bytes));
         LSQ_HIP(hipMemcpyAsync(c->sSample.p, sample, (size_t)ns * row_bytes, hipMemcpyHostToDevice, c->stream));
-        LSQ_TRY(q16_prepare_chunk<XT>(c, dXc, dK, d, cn, m, c->sSample.as<XT>(), ns, &means));
+        LSQ_TRY(q16_prepare_chunk<XT>(c, dXc, dK, d, cn, m, c->sSample.as<XT>(), ns));
     }
     LSQ_TRY(c->U.ensure(sizeof(float) * (size_t)m * (size_t)cn * LSQ_H));
     std::atomic<int> landed{0};
@@ -957,8 +982,6 @@ static int build_unaries_from_host(lsq_ctx *c, const XT *Xh, XT *dXc, const floa
         return build_unaries(c, dXc, dK, d, cn, m, slice, 0, cn);
     }
     int rc = LSQ_OK;
-    uint16_t *dq = q16 ? c->Uq.as<uint16_t>() : nullptr;
-    char *sc = q16 ? c->qscratch.as<char>() : nullptr;
     for (int p = 0; p < npan && rc == LSQ_OK; ++p) {
         for (int spins = 0; landed.load(std::memory_order_acquire) <= p; ++spins) {      // a panel takes ~1 ms to go up: poll briefly, then sleep instead of burning the core
             if (spins < 64) std::this_thread::yield();
@@ -968,12 +991,8 @@ static int build_unaries_from_host(lsq_ctx *c, const XT *Xh, XT *dXc, const floa
         const int64_t r0 = (int64_t)p * prow, rows = std::min<int64_t>(prow, cn - r0);
         if (hipStreamWaitEvent(c->stream, c->panel_ev[(size_t)p], 0) != hipSuccess) { lsq_set_error("hipStreamWaitEvent failed"); rc = LSQ_EHIP; break; }
         Timer t(c, CAT_UNARIES);
-        if (q16) rc = lsq_launch_unary_shift_panel(c->stream, dXc + (size_t)r0 * d, rows, d, m, means, c->qsigma.as<float>() + (size_t)r0 * m,
-                                                   reinterpret_cast<unsigned *>(sc + 64), c->qflag.as<unsigned short>(), r0, c->qp.as<lsq_q16_params>());
-        if (rc == LSQ_OK)
-            rc = lsq_launch_chain_gemm(c->stream, dXc + (size_t)r0 * d, dK, c->sci.as<float>(), -2.0f, rows, m * LSQ_H, d, LSQ_H, cn * (int64_t)LSQ_H, LSQ_H,
-                                       c->U.as<float>(), slice, cn, r0, dq, dq ? lsq_q16_slice_width(m) : 0, dq ? c->qp.as<lsq_q16_params>() : nullptr, 0,
-                                       dq ? c->qflag.as<unsigned short>() : nullptr, nullptr, 1, dq ? c->qsigma.as<float>() : nullptr, dq ? c->q_colshift : nullptr);
+        if (q16) rc = lsq_launch_unary_shift_panel(c->stream, dXc + (size_t)r0 * d, rows, d, m, c->qw, r0);
+        if (rc == LSQ_OK) rc = unary_gemm(c, dXc, dK, d, cn, m, slice, r0, rows, q16);
     }
     feeder.join();
     if (herr != hipSuccess) { lsq_set_error("upload of X failed: %s", hipGetErrorString(herr)); return herr == hipErrorOutOfMemory ? LSQ_ENOMEM : LSQ_EHIP; }
@@ -981,61 +1000,48 @@ static int build_unaries_from_host(lsq_ctx *c, const XT *Xh, XT *dXc, const floa
     return q16_verdict(c, q16, cn, m);
 }
 
+// nsweeps sweeps over the chunk's m nodes in `order`.  stats: where the walk launches accumulate their statistics (the call's block, the probe's, or nullptr)
 // ref_rec / ref_valid: the vectors' current records and validity masks (read-only during the sweeps), or nullptr
 // first_sweep: position of the first of the nsweeps sweeps inside its ILS iteration (the per-position trace counters only)
-static int run_sweeps(lsq_ctx *c, uint8_t *rec, unsigned short *valid, int64_t cn, int m, const int32_t *order, int nsweeps,
+static int run_sweeps(lsq_ctx *c, uint8_t *rec, unsigned short *valid, int64_t cn, int m, const int32_t *order, int nsweeps, unsigned long long *stats,
                       const uint8_t *ref_rec = nullptr, const unsigned short *ref_valid = nullptr, int first_sweep = 0) {
     if (nsweeps <= 0) return LSQ_OK;
     const int pos_base = first_sweep * m;
     Timer t(c, CAT_ICM);
-    if (c->schedule >= 4) {
-        // the whole ILS iteration (nsweeps x m node updates) in ONE launch: a block owns its vectors throughout
-        std::vector<int32_t> seq((size_t)nsweeps * m);
-        for (int sw = 0; sw < nsweeps; ++sw)
-            for (int q = 0; q < m; ++q) seq[(size_t)sw * m + q] = order[q];
-        if (c->chunk_q16 && valid) {
-            // 16-bit filtered walk on the level planes of this chunk (build_unaries read the chunk's verdict); 64 node updates per launch
-            const lsq_q16_params *P = c->qp.as<lsq_q16_params>();
-            const size_t per_launch = c->per_node ? 1 : 64;
-            const unsigned *gate = c->chunk_road_dev ? c->road.as<unsigned>() : nullptr;      // option "async": runs iff road[0] == 2
-            for (size_t done = 0; done < seq.size(); done += per_launch) {
-                const int cntn = (int)std::min<size_t>(per_launch, seq.size() - done);
-                LSQ_TRY(lsq_launch_icm_walkq(c->stream, c->U.as<float>(), c->Uq.as<uint16_t>(), c->Tq.as<uint16_t>(), c->T.as<float>(), rec, valid, cn, m,
-                                             seq.data() + done, cntn, pos_base + (int)done, c->skip, c->walk_counters, c->light,
-                                             c->fallback ? ref_rec : nullptr, c->fallback ? ref_valid : nullptr, P, c->qflag.as<unsigned short>(), gate));
-            }
-            c->icm_launches += ((int64_t)seq.size() + (int64_t)per_launch - 1) / (int64_t)per_launch;
-            if (c->chunk_road_dev) {      // ... and the f32 walk behind it idles on the same word (road[0] != 0) or does the work (road[0] == 0)
-                LSQ_TRY(lsq_launch_icm_walk(c->stream, c->U.as<float>(), c->Ts.as<float>(), c->T.as<float>(), rec, valid, cn, m, seq.data(), (int)seq.size(), pos_base,
-                                            c->skip, c->walk_counters, c->ablation, c->light, c->fallback ? ref_rec : nullptr, c->fallback ? ref_valid : nullptr,
-                                            reinterpret_cast<const int *>(c->road.as<unsigned>())));
-                c->icm_launches += ((int64_t)seq.size() + 63) / 64;
-            }
-            return LSQ_OK;
-        }
-        {
-            // a chunk so small that every block of the walk kernel would be light (at most `light` vectors each): a wave owns its vectors through
-            // the whole launch instead (icm_wave_kernel: no compaction, no barriers, records and validity words in registers)
-            int per_pass = 0, npass = 0;
-            lsq_walk_geometry(cn, m, &per_pass, &npass, nullptr);
-            const int light_max = c->light >= 0 ? c->light : 256;
-            if (c->ablation == 0 && per_pass <= light_max && per_pass <= c->wave_max) {
-                LSQ_TRY(lsq_launch_icm_wave(c->stream, c->U.as<float>(), c->T.as<float>(), rec, valid, cn, m, seq.data(), (int)seq.size(), pos_base, c->skip,
-                                            c->walk_counters, c->fallback ? ref_rec : nullptr, c->fallback ? ref_valid : nullptr));
-                c->icm_launches += ((int64_t)seq.size() + 63) / 64;
-                return LSQ_OK;
-            }
-        }
-        LSQ_TRY(lsq_launch_icm_walk(c->stream, c->U.as<float>(), c->Ts.as<float>(), c->T.as<float>(), rec, valid, cn, m, seq.data(), (int)seq.size(), pos_base, c->skip,
-                                    c->walk_counters, c->ablation, c->light, c->fallback ? ref_rec : nullptr, c->fallback ? ref_valid : nullptr));
-        c->icm_launches += ((int64_t)seq.size() + 63) / 64;
+    if (!c->fallback) { ref_rec = nullptr; ref_valid = nullptr; }
+    std::vector<int32_t> seq((size_t)nsweeps * m);
+    for (int sw = 0; sw < nsweeps; ++sw)
+        for (int q = 0; q < m; ++q) seq[(size_t)sw * m + q] = order[q];
+    // The road, decided once.  Schedule 3: the f32 walk, a launch per node update.  Schedule >= 4: a block owns its vectors through a launch of up to 64 node
+    // updates (a whole ILS iteration where it fits) -- on the 16-bit filtered walk where the chunk's verdict named it, else on the f32 walk or, for a chunk so
+    // small that every block of the walk kernel would be light (at most `light` vectors each), on icm_wave_kernel: a wave owns its vectors instead (no
+    // compaction, no barriers, records and validity words in registers).
+    enum { F32, WAVE, FILTERED } road = F32;
+    int per_launch = 64;
+    if (c->schedule < 4) per_launch = 1;
+    else if (c->chunk_road.filtered && valid) {
+        road = FILTERED;
+        if (c->per_node) per_launch = 1;      // (profiling: per-sweep timings / counters)
     } else {
-        for (int sw = 0; sw < nsweeps; ++sw)
-            for (int q = 0; q < m; ++q)
-                LSQ_TRY(lsq_launch_icm_walk(c->stream, c->U.as<float>(), c->Ts.as<float>(), c->T.as<float>(), rec, valid, cn, m, &order[q], 1, pos_base + sw * m + q, c->skip,
-                                            c->walk_counters, c->ablation, c->light, c->fallback ? ref_rec : nullptr, c->fallback ? ref_valid : nullptr));
-        c->icm_launches += (int64_t)nsweeps * m;
+        int per_pass = 0, npass = 0;
+        lsq_walk_geometry(cn, lsq_walk_pp(m, lsq_walk_slice_width(m)), &per_pass, &npass);
+        const int light_max = c->light >= 0 ? c->light : 256;
+        if (c->ablation == 0 && per_pass <= light_max && per_pass <= c->wave_max) road = WAVE;
     }
+    // option "async": the filtered walk runs iff road[0] == 2, and the f32 walk enqueued behind it idles on the same word (road[0] != 0) or does the work
+    const bool both = road == FILTERED && c->chunk_road.on_device;
+    const float *U = c->U.as<float>(), *T = c->T.as<float>();
+    int launched = 0;
+    if (road == FILTERED)
+        LSQ_TRY(lsq_launch_icm_walkq(c->stream, U, c->Uq.as<uint16_t>(), c->Tq.as<uint16_t>(), T, rec, valid, cn, m, seq.data(), (int)seq.size(), pos_base, per_launch,
+                                     c->skip, stats, c->light, ref_rec, ref_valid, c->qp.as<lsq_q16_params>(), c->qflag.as<unsigned short>(),
+                                     both ? c->road.as<unsigned>() : nullptr, &launched));
+    if (road == WAVE)
+        LSQ_TRY(lsq_launch_icm_wave(c->stream, U, T, rec, valid, cn, m, seq.data(), (int)seq.size(), pos_base, 64, c->skip, stats, ref_rec, ref_valid, &launched));
+    if (road == F32 || both)
+        LSQ_TRY(lsq_launch_icm_walk(c->stream, U, c->Ts.as<float>(), T, rec, valid, cn, m, seq.data(), (int)seq.size(), pos_base, both ? 64 : per_launch, c->skip, stats,
+                                    c->ablation, c->light, ref_rec, ref_valid, both ? reinterpret_cast<const int *>(c->road.as<unsigned>()) : nullptr, &launched));
+    c->icm_launches += launched;
     return LSQ_OK;
 }
 
@@ -1064,6 +1070,7 @@ static int encode_chunk(lsq_ctx *c, const XT *dXc, const float *dK, int64_t cn, 
     uint8_t *cur = c->recCur.as<uint8_t>(), *nw = c->recNew.as<uint8_t>();
     float *prev = c->prev.as<float>();
     unsigned long long *counters = c->counters.as<unsigned long long>();
+    unsigned long long *totals = c->active.as<unsigned long long>(), *probed = nullptr;      // the walk statistics of the call, and of a probed first iteration
     // The perturbation of ILS iteration t (encode_icm.jl:55-70) rides on the exit of the cost kernel that precedes it: every lane there knows
     // its vector's final record and validity word, so the copy-and-perturb pass over the records and its launch are gone (lsq_perturb stays
     // as the stand-alone entry point).
@@ -1080,37 +1087,35 @@ static int encode_chunk(lsq_ctx *c, const XT *dXc, const float *dK, int64_t cn, 
         // The probe: the walk counters of the chunk's first ILS iteration -- or, in a call of ONE iteration (the trainer's chained encoding_icm), of that
         // iteration's first sweep, the launch being split there -- are read back; a filter that decides too little hands the REST to the f32 walk.
         // Nothing is remembered across calls (round 3 kept a per-shape verdict: it could not tell two data sets of one shape apart).
-        const bool probing = it == 0 && c->chunk_q16 && c->probe_div > 0 && (I > 1 || P.icmiter > 1);
+        const bool probing = it == 0 && c->chunk_road.filtered && c->probe_div > 0 && (I > 1 || P.icmiter > 1);
         // a call of ONE iteration probes its first sweeps: two of them when there are at least three (after the first sweep of an iteration EVERY node of every
         // vector has just been recomputed, which dilutes the hard / recomputed ratio the threshold was calibrated on -- ADVICE r4), else one
         const int probe_sweeps = I > 1 ? P.icmiter : (P.icmiter >= 3 ? 2 : 1);
         if (probing) {
             LSQ_TRY(c->probe.ensure(sizeof(unsigned long long) * LSQ_WALK_COUNTERS));
             LSQ_HIP(hipMemsetAsync(c->probe.p, 0, sizeof(unsigned long long) * LSQ_WALK_COUNTERS, c->stream));
-            c->walk_counters = c->probe.as<unsigned long long>();
+            probed = c->probe.as<unsigned long long>();
         }
-        LSQ_TRY(run_sweeps(c, nw, vnew, cn, P.m, order, probing ? probe_sweeps : P.icmiter, cur, vcur, 0));
-        if (probing && c->chunk_road_dev) {
+        LSQ_TRY(run_sweeps(c, nw, vnew, cn, P.m, order, probing ? probe_sweeps : P.icmiter, probing ? probed : totals, cur, vcur, 0));
+        if (probing && c->chunk_road.on_device) {
             // option "async": the same probe by a one-thread kernel (it also adds the probed launches' statistics to the call's)
-            c->walk_counters = c->active.as<unsigned long long>();
-            LSQ_TRY(lsq_launch_q16_probe(c->stream, c->probe.as<unsigned long long>(), c->active.as<unsigned long long>(), c->road.as<unsigned>(), c->probe_div));
-            LSQ_TRY(run_sweeps(c, nw, vnew, cn, P.m, order, P.icmiter - probe_sweeps, cur, vcur, probe_sweeps));
+            LSQ_TRY(lsq_launch_q16_probe(c->stream, probed, totals, c->road.as<unsigned>(), c->probe_div));
+            LSQ_TRY(run_sweeps(c, nw, vnew, cn, P.m, order, P.icmiter - probe_sweeps, totals, cur, vcur, probe_sweeps));
         } else if (probing) {
             // Is the filter paying off on THIS chunk?  A level step blown up by a few extreme values (scale-mixture / heavy-tailed data) leaves most
             // node updates ambiguous: each then costs an exact refinement (or, past the block's 1024 records, the one-wave f32 routine) on top of the
             // level walk, and the f32 walk is several times faster (measured: Cauchy-scaled vectors 2.2 M vectors/s filtered, 13 M on the f32 walk).
             // The first ILS iteration's counters tell; the f32 unaries are resident either way, so the remaining iterations just change road.
-            c->walk_counters = c->active.as<unsigned long long>();
             unsigned long long act[LSQ_WALK_COUNTERS] = {0};
             LSQ_HIP(hipMemcpyAsync(act, c->probe.p, sizeof(act), hipMemcpyDeviceToHost, c->stream));
             LSQ_HIP(hipStreamSynchronize(c->stream));
             fold_walk_counters(c, act);
             const unsigned long long hard = act[4 + LSQ_WALK_TRACE] + act[4 + LSQ_WALK_TRACE + 2];
             if ((double)hard * (double)c->probe_div > (double)act[0]) {      // the same arithmetic as q16_probe_kernel (option "async")
-                c->chunk_q16 = false;
+                c->chunk_road.filtered = false;
                 c->filter_fallback_chunks += 1;
             }
-            LSQ_TRY(run_sweeps(c, nw, vnew, cn, P.m, order, P.icmiter - probe_sweeps, cur, vcur, probe_sweeps));      // the rest of a single-iteration call
+            LSQ_TRY(run_sweeps(c, nw, vnew, cn, P.m, order, P.icmiter - probe_sweeps, totals, cur, vcur, probe_sweeps));      // the rest of a single-iteration call
         }
         {
             Timer t(c, CAT_COST);
@@ -1141,7 +1146,7 @@ static int validate_encode(const char *fn, int d, int64_t n, int m, int h, const
 
 static int begin_call(lsq_ctx *c, int64_t I, int nr) {
     c->call_row0 = 0;
-    c->snap_resident = false;       // the per-call block (the level parameters among it) is zeroed below
+    c->chunk_road.resident = false;      // the per-call block (the level parameters among it) is zeroed below
     LSQ_TRY(c->counters.ensure(sizeof(unsigned long long) * 2 * (size_t)std::max<int64_t>(I, 1)));
     LSQ_TRY(c->obj.ensure(sizeof(double) * (size_t)std::max(nr, 1)));
     LSQ_TRY(c->bad.ensure(sizeof(int)));
@@ -1149,7 +1154,6 @@ static int begin_call(lsq_ctx *c, int64_t I, int nr) {
     LSQ_TRY(c->road.ensure(2 * sizeof(unsigned)));
     LSQ_TRY(c->qp.ensure(sizeof(lsq_q16_params)));
     if (!c->async_mode) LSQ_TRY(fold_pending(c));             // statistics an earlier async call left on the device (synchronises)
-    c->walk_counters = c->active.as<unsigned long long>();
     c->small_packed = c->counters.view && c->obj.view && c->bad.view && c->qp.view && c->active.view && c->road.view;
     if (c->small_packed) {
         // one fill: counters, sums, flags, level parameters (+ the walk counters and the road words unless async calls are still accumulating)
@@ -1603,7 +1607,6 @@ extern "C" int lsq_encode_icm_fully(lsq_ctx *c, int16_t *B, const float *X, cons
     LSQ_TRY(upload_xk(c, X, K, d, n, m));
     LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));
     LSQ_TRY(prepare_tables(c, c->sK.as<float>(), d, m));
-    c->walk_counters = nullptr;                        // the worker has no accept step and no probe memory: always the configured road
     c->call_row0 = 0;
     LSQ_TRY(build_unaries(c, c->sX.as<float>(), c->sK.as<float>(), d, n, m, lsq_walk_slice_width(m), 0, n));
     LSQ_TRY(c->recNew.ensure((size_t)n * lsq_code_stride(m)));
@@ -1613,7 +1616,8 @@ extern "C" int lsq_encode_icm_fully(lsq_ctx *c, int16_t *B, const float *X, cons
     LSQ_TRY(c->active.ensure(sizeof(unsigned long long) * LSQ_WALK_COUNTERS));
     LSQ_HIP(hipMemsetAsync(c->vNew.p, 0, sizeof(unsigned short) * (size_t)n, c->stream));
     LSQ_TRY(lsq_launch_perturb(c->stream, c->recCur.as<uint8_t>(), c->recNew.as<uint8_t>(), n, m, npert, seed, it, (uint64_t)(idx_first - 1), nullptr, nullptr));
-    LSQ_TRY(run_sweeps(c, c->recNew.as<uint8_t>(), c->vNew.as<unsigned short>(), n, m, order, niter));
+    // (no statistics: the worker has no accept step and no probe memory -- always the configured road)
+    LSQ_TRY(run_sweeps(c, c->recNew.as<uint8_t>(), c->vNew.as<unsigned short>(), n, m, order, niter, nullptr));
     LSQ_TRY(lsq_launch_codes_to_i16(c->stream, c->recNew.as<uint8_t>(), n, m, c->sB16.as<int16_t>()));
     LSQ_HIP(hipMemcpyAsync(B, c->sB16.p, sizeof(int16_t) * (size_t)n * m, hipMemcpyDeviceToHost, c->stream));
     LSQ_HIP(hipStreamSynchronize(c->stream));
@@ -1692,6 +1696,22 @@ extern "C" int lsq_quantize_norms_dev(lsq_ctx *c, const uint8_t *d_codes, const 
     return lsq_launch_quantize_norms(c->stream, d_codes, m, d_K, d_cbnorms, ncb, n, d, m, d_idx_out, nullptr, d_dbnorms, d_norms);
 }
 
+// What the host-buffer codebook updates stage: X up (sX), the tables cache dropped (sK is about to hold other codebooks), optionally the codebooks K_up into
+// K_buf, then the codes up and compacted to tight [n][m] (sTight) -- enqueued in this order
+static int stage_training_set(lsq_ctx *c, const float *X, const int16_t *B, int d, int64_t n, int m, int h, const float *K_up = nullptr, DevBuf *K_buf = nullptr) {
+    const size_t kbytes = sizeof(float) * (size_t)m * LSQ_H * d;
+    LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)std::max<int64_t>(n, 1) * d));
+    LSQ_TRY(c->sK.ensure(kbytes));
+    if (K_up) LSQ_TRY(K_buf->ensure(kbytes));
+    c->tables_valid = false;
+    if (n > 0) LSQ_HIP(hipMemcpyAsync(c->sX.p, X, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
+    if (K_up) LSQ_HIP(hipMemcpyAsync(K_buf->p, K_up, kbytes, hipMemcpyHostToDevice, c->stream));
+    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));                          // records of stride 8 / 16 -> tight [n][m] below
+    LSQ_TRY(c->sTight.ensure((size_t)std::max<int64_t>(n, 1) * m));
+    if (n > 0) LSQ_TRY(lsq_launch_codes_compact(c->stream, c->recCur.as<uint8_t>(), n, m, c->sTight.as<uint8_t>()));
+    return LSQ_OK;
+}
+
 // the LSQR codebook update on the device (lsq_lsqr.hip).  cover: HOST bytes of a structured update's map (checked here), or null = the unstructured update
 static int check_cover(const char *fn, const uint8_t *dim2C, int d, int m) {      // d x m bytes in Julia's column-major order ([m][d] here), every entry 0 or 1
     for (int64_t e = 0; dim2C && e < (int64_t)d * m; ++e)
@@ -1720,13 +1740,7 @@ static int update_codebooks_gpu(const char *fn, lsq_ctx *c, const float *X, cons
     LSQ_TRY(check_shape(fn, d, n, m, h));
     if (n < 1 || !X || !B || !K_out) { lsq_set_error("%s: bad arguments", fn); return LSQ_EINVAL; }
     LSQ_TRY(check_cover(fn, dim2C, d, m));
-    LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)n * d));
-    LSQ_TRY(c->sK.ensure(sizeof(float) * (size_t)m * LSQ_H * d));
-    c->tables_valid = false;
-    LSQ_HIP(hipMemcpyAsync(c->sX.p, X, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
-    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));                          // records of stride 8 / 16 -> tight [n][m] below
-    LSQ_TRY(c->sTight.ensure((size_t)n * m));
-    LSQ_TRY(lsq_launch_codes_compact(c->stream, c->recCur.as<uint8_t>(), n, m, c->sTight.as<uint8_t>()));
+    LSQ_TRY(stage_training_set(c, X, B, d, n, m, h));
     LSQ_TRY(lsq_lsqr_update_codebooks(c->stream, &c->lsqr, c->sX.as<float>(), c->sTight.as<uint8_t>(), dim2C, d, n, m, c->sK.as<float>(), iterations));
     LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, sizeof(float) * (size_t)m * LSQ_H * d, hipMemcpyDeviceToHost, c->stream));
     LSQ_HIP(hipStreamSynchronize(c->stream));
@@ -1778,7 +1792,6 @@ extern "C" int lsq_update_codebooks_spgl1_dev(lsq_ctx *c, const float *d_X, cons
     int64_t max_iter = 0;
     LSQ_TRY(spgl1_args("lsq_update_codebooks_spgl1_dev", c, d, n, m, h, tau, params, &opt_tol, &max_iter));
     if (!d_X || !d_codes || !d_K_out) { lsq_set_error("lsq_update_codebooks_spgl1_dev: null pointer"); return LSQ_EINVAL; }
-    const AsyncOff sync_here(c);
     return lsq_spgl1_update_codebooks(c->stream, &c->spgl1, d_X, d_codes, d, n, m, tau, d_K_init, S, opt_tol, max_iter, d_K_out, info);
 }
 
@@ -1788,20 +1801,10 @@ extern "C" int lsq_update_codebooks_spgl1(lsq_ctx *c, const float *X, const int1
     int64_t max_iter = 0;
     LSQ_TRY(spgl1_args("lsq_update_codebooks_spgl1", c, d, n, m, h, tau, params, &opt_tol, &max_iter));
     if (!X || !B || !K_out) { lsq_set_error("lsq_update_codebooks_spgl1: null pointer"); return LSQ_EINVAL; }
-    const AsyncOff sync_here(c);
-    const size_t kbytes = sizeof(float) * (size_t)m * LSQ_H * d;
-    LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)n * d));
-    LSQ_TRY(c->sK.ensure(kbytes));
-    if (K_init) LSQ_TRY(c->sF32.ensure(kbytes));
-    c->tables_valid = false;
-    LSQ_HIP(hipMemcpyAsync(c->sX.p, X, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
-    if (K_init) LSQ_HIP(hipMemcpyAsync(c->sF32.p, K_init, kbytes, hipMemcpyHostToDevice, c->stream));
-    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));                          // records of stride 8 / 16 -> tight [n][m] below
-    LSQ_TRY(c->sTight.ensure((size_t)n * m));
-    LSQ_TRY(lsq_launch_codes_compact(c->stream, c->recCur.as<uint8_t>(), n, m, c->sTight.as<uint8_t>()));
+    LSQ_TRY(stage_training_set(c, X, B, d, n, m, h, K_init, &c->sF32));
     LSQ_TRY(lsq_spgl1_update_codebooks(c->stream, &c->spgl1, c->sX.as<float>(), c->sTight.as<uint8_t>(), d, n, m, tau,
                                        K_init ? c->sF32.as<float>() : nullptr, S, opt_tol, max_iter, c->sK.as<float>(), info));
-    LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, kbytes, hipMemcpyDeviceToHost, c->stream));
+    LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, sizeof(float) * (size_t)m * LSQ_H * d, hipMemcpyDeviceToHost, c->stream));
     LSQ_HIP(hipStreamSynchronize(c->stream));
     return LSQ_OK;
 }
@@ -1846,7 +1849,6 @@ extern "C" int lsq_perturb(lsq_ctx *c, int16_t *B, int64_t n, int m, int h, int 
 // returns), so the codes are integer functions of exactly the numbers oracle/init_oracle.py works on.
 static int init_codes_dev(lsq_ctx *c, const char *fn, const float *dX, const float *dK, int d, int64_t n, int m, int h, uint8_t *dB, float *dmin, bool chain) {
     LSQ_TRY(use_device(c));
-    const AsyncOff sync_here(c);
     LSQ_TRY(check_shape(fn, d, n, m, h));
     if (chain && m < 2) { lsq_set_error("%s: a chain needs at least two codebooks", fn); return LSQ_EINVAL; }
     if (!dK || (n > 0 && (!dX || !dB))) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
@@ -1928,17 +1930,9 @@ extern "C" int lsq_update_centers(lsq_ctx *c, const float *X, const int16_t *B, 
     LSQ_TRY(kmeans_args("lsq_update_centers", c, dim2C, d, n, m, h));
     if (!K_out || (n > 0 && (!X || !B))) { lsq_set_error("lsq_update_centers: null pointer"); return LSQ_EINVAL; }
     if (n * (int64_t)m >= (int64_t)1 << 31) { lsq_set_error("lsq_update_centers: n * m = %lld exceeds 2^31 - 1", (long long)(n * m)); return LSQ_EINVAL; }
-    const AsyncOff sync_here(c);
     const size_t kbytes = sizeof(float) * (size_t)m * LSQ_H * d;
-    LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)std::max<int64_t>(n, 1) * d));
-    LSQ_TRY(c->sK.ensure(kbytes));
     LSQ_TRY(c->sF32.ensure(sizeof(int) * (size_t)m * LSQ_H));
-    c->tables_valid = false;
-    if (n > 0) LSQ_HIP(hipMemcpyAsync(c->sX.p, X, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
-    if (K_prev) LSQ_HIP(hipMemcpyAsync(c->sK.p, K_prev, kbytes, hipMemcpyHostToDevice, c->stream));      // in place: an empty cluster keeps the entry it finds
-    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));                          // records of stride 8 / 16 -> tight [n][m] below
-    LSQ_TRY(c->sTight.ensure((size_t)std::max<int64_t>(n, 1) * m));
-    if (n > 0) LSQ_TRY(lsq_launch_codes_compact(c->stream, c->recCur.as<uint8_t>(), n, m, c->sTight.as<uint8_t>()));
+    LSQ_TRY(stage_training_set(c, X, B, d, n, m, h, K_prev, &c->sK));      // K_prev in place: an empty cluster keeps the entry it finds
     LSQ_TRY(lsq_kmeans_update_centers(c->stream, &c->kmeans, c->sX.as<float>(), c->sTight.as<uint8_t>(), dim2C, K_prev ? c->sK.as<float>() : nullptr, d, n, m,
                                       c->sK.as<float>(), c->sF32.as<int>()));
     LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, kbytes, hipMemcpyDeviceToHost, c->stream));
@@ -1972,7 +1966,6 @@ extern "C" int lsq_kmeanspp_seed(lsq_ctx *c, const float *X, const uint8_t *dim2
     LSQ_TRY(kmeans_args("lsq_kmeanspp_seed", c, dim2C, d, n, m, h));
     LSQ_TRY(kmeanspp_u("lsq_kmeanspp_seed", u, m));
     if (!K_out || (n > 0 && !X)) { lsq_set_error("lsq_kmeanspp_seed: null pointer"); return LSQ_EINVAL; }
-    const AsyncOff sync_here(c);
     const size_t kbytes = sizeof(float) * (size_t)m * LSQ_H * d, ibytes = sizeof(int64_t) * (size_t)m * LSQ_H, dbytes = sizeof(float) * (size_t)n * m;
     LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)std::max<int64_t>(n, 1) * d));
     LSQ_TRY(c->sK.ensure(kbytes));

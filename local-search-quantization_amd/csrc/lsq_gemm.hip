@@ -365,12 +365,12 @@ __global__ __launch_bounds__(64) void sqnorms_kernel(const float *__restrict__ K
 }  // namespace
 
 int lsq_launch_chain_gemm(hipStream_t s, const float *A, const float *Bm, const float *addv, float alpha, int64_t M,
-                          int N, int Kd, int h, int64_t plane_stride, int64_t row_stride, float *D, int slice, int64_t Mtot, int64_t rbase,
-                          uint16_t *Dq, int slice_q, lsq_q16_params *qp, int64_t lda, unsigned short *qflag, unsigned *qrange, int rts, const float *sigma, const float *colshift) {
-    if (lda <= 0) lda = Kd;
-    if (rts < 1) rts = 1;
+                          int N, int Kd, int h, int64_t plane_stride, int64_t row_stride, float *D, int slice, int64_t Mtot, int64_t rbase, const lsq_gemm_q16 *q) {
+    lsq_gemm_q16 o = q ? *q : lsq_gemm_q16{};      // no description: no second output
+    if (o.rts < 1) o.rts = 1;
+    const int64_t lda = Kd;                          // rows of A are packed
     if (M <= 0 || N <= 0) return LSQ_OK;
-    const int64_t row_tiles = (M + (int64_t)BM * rts - 1) / ((int64_t)BM * rts);
+    const int64_t row_tiles = (M + (int64_t)BM * o.rts - 1) / ((int64_t)BM * o.rts);
     const int col_tiles = (N + BN - 1) / BN;
     const int64_t blocks = ((row_tiles + 7) / 8) * 8 * col_tiles;
     if (blocks > 0x7fffffffLL) { lsq_set_error("chain_gemm: grid too large"); return LSQ_EINVAL; }
@@ -379,29 +379,29 @@ int lsq_launch_chain_gemm(hipStream_t s, const float *A, const float *Bm, const 
     const bool fullk = Kd % 16 == 0;
     const int stagger = (M >= 65536) ? LSQ_KNOB("LSQ_GEMM_STAGGER", 0) : 0;      // units of s_sleep(127) = 8128 clocks per quarter
     // K chunks of 8 or 16 only: both fit four resident blocks per CU (the kernel is compiled for 4 waves per SIMD)
-    if (qrange) {          // range-only pass
+    if (o.qrange) {          // range-only pass
         if (vec4 && lda % 4 == 0)
             if (fullk) hipLaunchKernelGGL((chain_gemm_kernel<true, 16, 2, true>), dim3((unsigned)blocks), dim3(256), 0, s, A, Bm, addv, alpha, M, N, Kd, h,
-                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, nullptr, 0, nullptr, lda, nullptr, qrange, rts, sigma, colshift, 0);
+                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, nullptr, 0, nullptr, lda, nullptr, o.qrange, o.rts, o.sigma, o.colshift, 0);
             else hipLaunchKernelGGL((chain_gemm_kernel<true, 16, 2>), dim3((unsigned)blocks), dim3(256), 0, s, A, Bm, addv, alpha, M, N, Kd, h,
-                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, nullptr, 0, nullptr, lda, nullptr, qrange, rts, sigma, colshift, 0);
+                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, nullptr, 0, nullptr, lda, nullptr, o.qrange, o.rts, o.sigma, o.colshift, 0);
         else
             hipLaunchKernelGGL((chain_gemm_kernel<false, 16, 2>), dim3((unsigned)blocks), dim3(256), 0, s, A, Bm, addv, alpha, M, N, Kd, h,
-                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, nullptr, 0, nullptr, lda, nullptr, qrange, rts, sigma, colshift, 0);
+                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, nullptr, 0, nullptr, lda, nullptr, o.qrange, o.rts, o.sigma, o.colshift, 0);
         LSQ_HIP(hipGetLastError());
         return LSQ_OK;
     }
-    if (Dq) {
-        if (!qp || !qflag || slice_q < 1) { lsq_set_error("chain_gemm: quantised output needs parameters"); return LSQ_EINVAL; }
+    if (o.Dq) {
+        if (!o.qp || !o.qflag || o.slice_q < 1) { lsq_set_error("chain_gemm: quantised output needs parameters"); return LSQ_EINVAL; }
         if (vec4 && fullk)
             hipLaunchKernelGGL((chain_gemm_kernel<true, 16, 1, true>), dim3((unsigned)blocks), dim3(256), 0, s, A, Bm, addv, alpha, M, N, Kd, h,
-                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, Dq, slice_q, qp, lda, qflag, nullptr, 1, sigma, colshift, stagger);
+                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, o.Dq, o.slice_q, o.qp, lda, o.qflag, nullptr, 1, o.sigma, o.colshift, stagger);
         else if (vec4)
             hipLaunchKernelGGL((chain_gemm_kernel<true, 16, 1>), dim3((unsigned)blocks), dim3(256), 0, s, A, Bm, addv, alpha, M, N, Kd, h,
-                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, Dq, slice_q, qp, lda, qflag, nullptr, 1, sigma, colshift, stagger);
+                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, o.Dq, o.slice_q, o.qp, lda, o.qflag, nullptr, 1, o.sigma, o.colshift, stagger);
         else
             hipLaunchKernelGGL((chain_gemm_kernel<false, 16, 1>), dim3((unsigned)blocks), dim3(256), 0, s, A, Bm, addv, alpha, M, N, Kd, h,
-                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, Dq, slice_q, qp, lda, qflag, nullptr, 1, sigma, colshift, stagger);
+                               plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, o.Dq, o.slice_q, o.qp, lda, o.qflag, nullptr, 1, o.sigma, o.colshift, stagger);
         LSQ_HIP(hipGetLastError());
         return LSQ_OK;
     }
@@ -424,25 +424,25 @@ int lsq_launch_chain_gemm(hipStream_t s, const float *A, const float *Bm, const 
 // 8-bit A (data rows; Bm = the codebooks, f32).  Same tiles, same grid, same epilogues: only A's loader differs.  vb: Bm's 16-byte rule as above;
 // va: A's own rule (lsq_xload.h) -- a dword per quad when Kd % 4 == 0, lda % 4 == 0 and A is 4-byte aligned, byte loads otherwise.
 int lsq_launch_chain_gemm(hipStream_t s, const uint8_t *A, const float *Bm, const float *addv, float alpha, int64_t M,
-                          int N, int Kd, int h, int64_t plane_stride, int64_t row_stride, float *D, int slice, int64_t Mtot, int64_t rbase,
-                          uint16_t *Dq, int slice_q, lsq_q16_params *qp, int64_t lda, unsigned short *qflag, unsigned *qrange, int rts, const float *sigma, const float *colshift) {
-    if (lda <= 0) lda = Kd;
-    if (rts < 1) rts = 1;
+                          int N, int Kd, int h, int64_t plane_stride, int64_t row_stride, float *D, int slice, int64_t Mtot, int64_t rbase, const lsq_gemm_q16 *q) {
+    lsq_gemm_q16 o = q ? *q : lsq_gemm_q16{};      // no description: no second output
+    if (o.rts < 1) o.rts = 1;
+    const int64_t lda = Kd;                          // rows of A are packed
     if (M <= 0 || N <= 0) return LSQ_OK;
-    const int64_t row_tiles = (M + (int64_t)BM * rts - 1) / ((int64_t)BM * rts);
+    const int64_t row_tiles = (M + (int64_t)BM * o.rts - 1) / ((int64_t)BM * o.rts);
     const int col_tiles = (N + BN - 1) / BN;
     const int64_t blocks = ((row_tiles + 7) / 8) * 8 * col_tiles;
     if (blocks > 0x7fffffffLL) { lsq_set_error("chain_gemm: grid too large"); return LSQ_EINVAL; }
     const bool vb = (Kd % 4 == 0) && ((uintptr_t)Bm % 16 == 0);
     const bool va = vb && lda % 4 == 0 && lsq_x_vec_ok(A);
     const bool fullk = Kd % 16 == 0;
-    const int stagger = (M >= 65536 && !qrange) ? LSQ_KNOB("LSQ_GEMM_STAGGER", 0) : 0;
-    if (Dq && !qrange && (!qp || !qflag || slice_q < 1)) { lsq_set_error("chain_gemm: quantised output needs parameters"); return LSQ_EINVAL; }
-    if (qrange) { Dq = nullptr; slice_q = 0; qp = nullptr; qflag = nullptr; }
-    else rts = 1;
+    const int stagger = (M >= 65536 && !o.qrange) ? LSQ_KNOB("LSQ_GEMM_STAGGER", 0) : 0;
+    if (o.Dq && !o.qrange && (!o.qp || !o.qflag || o.slice_q < 1)) { lsq_set_error("chain_gemm: quantised output needs parameters"); return LSQ_EINVAL; }
+    if (o.qrange) { o.Dq = nullptr; o.slice_q = 0; o.qp = nullptr; o.qflag = nullptr; }
+    else o.rts = 1;
 #define LSQ_GEMM_U8(VB_, Q_, FK_, VA_)                                                                                                                  \
     hipLaunchKernelGGL((chain_gemm_kernel<VB_, 16, Q_, FK_, uint8_t, VA_>), dim3((unsigned)blocks), dim3(256), 0, s, A, Bm, addv, alpha, M, N, Kd, h,      \
-                       plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, Dq, slice_q, qp, lda, qflag, qrange, rts, sigma, colshift, stagger)
+                       plane_stride, row_stride, D, row_tiles, col_tiles, slice, Mtot, rbase, o.Dq, o.slice_q, o.qp, lda, o.qflag, o.qrange, o.rts, o.sigma, o.colshift, stagger)
 #define LSQ_GEMM_U8_Q(Q_)                                        \
     do {                                                         \
         if (va && fullk) LSQ_GEMM_U8(true, Q_, true, true);      \
@@ -450,9 +450,9 @@ int lsq_launch_chain_gemm(hipStream_t s, const uint8_t *A, const float *Bm, cons
         else if (vb) LSQ_GEMM_U8(true, Q_, false, false);        \
         else LSQ_GEMM_U8(false, Q_, false, false);               \
     } while (0)
-    if (qrange) LSQ_GEMM_U8_Q(2);
-    else if (Dq) LSQ_GEMM_U8_Q(1);
-    else { sigma = nullptr; colshift = nullptr; LSQ_GEMM_U8_Q(0); }
+    if (o.qrange) LSQ_GEMM_U8_Q(2);
+    else if (o.Dq) LSQ_GEMM_U8_Q(1);
+    else { o.sigma = nullptr; o.colshift = nullptr; LSQ_GEMM_U8_Q(0); }
 #undef LSQ_GEMM_U8_Q
 #undef LSQ_GEMM_U8
     LSQ_HIP(hipGetLastError());

@@ -843,18 +843,6 @@ inline unsigned thread_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
 
 
-// geometry of a walk launch over n vectors: vectors per pass (<= the LDS budget PP), number of passes (= segments), grid
-void lsq_walk_geometry(int64_t n, int m, int *per_pass, int *npass, int *pp_cap) {
-    const int PP = lsq_walk_pp(m, lsq_walk_slice_width(m));
-    const int64_t rounds = (n + 256 * (int64_t)PP - 1) / (256 * (int64_t)PP);          // passes per CU
-    int64_t per = rounds > 0 ? (n + 256 * rounds - 1) / (256 * rounds) : 1;
-    if (per > PP) per = PP;
-    if (per < 1) per = 1;
-    *per_pass = (int)per;
-    *npass = (int)((n + per - 1) / per);
-    if (pp_cap) *pp_cap = PP;
-}
-
 template <int M, int SL, int ABL = 0, int DEPTH = 2, int NT = 1024>
 static int launch_walk_t(hipStream_t s, const float *U, const float *Ts, const float *T, uint8_t *rec, unsigned short *valid, int64_t n,
                          const WalkNodes &nodes, int use_skip, unsigned long long *active_total, int light,
@@ -864,7 +852,7 @@ static int launch_walk_t(hipStream_t s, const float *U, const float *Ts, const f
     constexpr int LDS_BYTES = TAB * 16 + PP * 8 + PP * 2;                // slice table + packed running best + active list
     static_assert(LDS_BYTES + 256 <= 160 * 1024, "slice table + running best must fit the 160 KiB LDS");
     int per_pass = 1, npass = 1;
-    lsq_walk_geometry(n, M, &per_pass, &npass, nullptr);
+    lsq_walk_geometry(n, PP, &per_pass, &npass);
     // blocks with at most this many active vectors gather from L2 instead of staging (option "light"; thresholds 96..1024 measured)
     const int direct_max = light >= 0 ? light : LSQ_KNOB("LSQ_WALK_DIRECT", 256);
     const int skip = (use_skip && valid) ? 1 : 0;
@@ -877,21 +865,12 @@ static int launch_walk_t(hipStream_t s, const float *U, const float *Ts, const f
     return LSQ_OK;
 }
 
-// `order[nnodes]`: the node updates to run back to back inside the launch (1 = one node; icmiter*m = a whole ILS iteration)
+// `order[nnodes]`: the node updates to run back to back inside a launch (max_per = 1: one node; icmiter*m entries = a whole ILS iteration)
 int lsq_launch_icm_walk(hipStream_t s, const float *U, const float *Ts, const float *T, uint8_t *rec, unsigned short *valid, int64_t n, int m,
-                        const int32_t *order, int nnodes, int pos0, int use_skip, unsigned long long *active_total, int ablation, int light,
-                        const uint8_t *ref_rec, const unsigned short *ref_valid, const int *idle_if_set) {
+                        const int32_t *order, int nnodes, int pos0, int max_per, int use_skip, unsigned long long *active_total, int ablation, int light,
+                        const uint8_t *ref_rec, const unsigned short *ref_valid, const int *idle_if_set, int *launched) {
     if (n <= 0 || nnodes <= 0) return LSQ_OK;
-    if (m < 1 || m > LSQ_MAX_M) { lsq_set_error("m = %d out of range 1..16", m); return LSQ_EINVAL; }
-    for (int done = 0; done < nnodes; done += LSQ_WALK_MAX_NODES) {
-        WalkNodes nodes;
-        nodes.count = (nnodes - done < LSQ_WALK_MAX_NODES) ? nnodes - done : LSQ_WALK_MAX_NODES;
-        nodes.pos0 = pos0 + done;
-        for (int t = 0; t < nodes.count; ++t) {
-            const int j = order[done + t];
-            if (j < 0 || j >= m) { lsq_set_error("node %d out of range 0..%d", j, m - 1); return LSQ_EINVAL; }
-            nodes.j[t] = (uint8_t)j;
-        }
+    return for_walk_launches(order, nnodes, pos0, m, max_per, launched, [&](const WalkNodes &nodes) -> int {
         // m >= 14: up to 15 table reads in flight + 8 staged table registers per thread do not fit 128 VGPRs (measured at
         // m = 16: 67..100 spilled registers, 1.5..2.5x slower) -> 512-thread blocks (256 VGPRs per wave), more U items in
         // flight instead.  m = 9..13 fit (<= 4 spills) and are 3-5 % faster with 1024 threads (measured for every m).
@@ -900,13 +879,10 @@ int lsq_launch_icm_walk(hipStream_t s, const float *U, const float *Ts, const fl
 #define LSQ_WALK_CASE_BIG(MM) case MM: LSQ_TRY((launch_walk_t<MM, 8, 0, 4, 512>(LSQ_WALK_ARGS))); break;
 #define LSQ_WALK_CASE(MM) case MM: LSQ_TRY((launch_walk_t<MM, 16, 0, 3>(LSQ_WALK_ARGS))); break;
 #ifdef LSQ_TUNING      // timing-only variants: profiling library only (results of the ablations are garbage)
-        bool handled = true;
-        if (m == 8 && ablation == 1) { LSQ_TRY((launch_walk_t<8, 16, 1>(LSQ_WALK_ARGS)));
-        } else if (m == 8 && ablation == 2) { LSQ_TRY((launch_walk_t<8, 16, 2>(LSQ_WALK_ARGS)));
-        } else if (m == 8 && ablation == 3) { LSQ_TRY((launch_walk_t<8, 16, 3>(LSQ_WALK_ARGS)));
-        } else if (m == 8 && ablation == 4) { LSQ_TRY((launch_walk_t<8, 16, 4>(LSQ_WALK_ARGS)));
-        } else handled = false;
-        if (handled) continue;
+        if (m == 8 && ablation == 1) return launch_walk_t<8, 16, 1>(LSQ_WALK_ARGS);
+        if (m == 8 && ablation == 2) return launch_walk_t<8, 16, 2>(LSQ_WALK_ARGS);
+        if (m == 8 && ablation == 3) return launch_walk_t<8, 16, 3>(LSQ_WALK_ARGS);
+        if (m == 8 && ablation == 4) return launch_walk_t<8, 16, 4>(LSQ_WALK_ARGS);
 #else
         (void)ablation;
 #endif
@@ -920,8 +896,8 @@ int lsq_launch_icm_walk(hipStream_t s, const float *U, const float *Ts, const fl
 #undef LSQ_WALK_CASE
 #undef LSQ_WALK_CASE_BIG
 #undef LSQ_WALK_CASE_MID
-    }
-    return LSQ_OK;
+        return LSQ_OK;
+    });
 }
 
 int lsq_launch_tables_to_slices(hipStream_t s, const float *T, float *Ts, int m, int sl) {
@@ -944,25 +920,17 @@ int lsq_launch_tables_to_slices(hipStream_t s, const float *T, float *Ts, int m,
 // small chunks (at most `light` vectors per block of the walk kernel): every node update of the sequence in launches of <= 64, a wave per
 // LSQ_LIGHT_LB vectors
 int lsq_launch_icm_wave(hipStream_t s, const float *U, const float *T, uint8_t *rec, unsigned short *valid, int64_t n, int m, const int32_t *order,
-                        int nnodes, int pos0, int use_skip, unsigned long long *active_total, const uint8_t *ref_rec, const unsigned short *ref_valid,
-                        const int *idle_if_set) {
+                        int nnodes, int pos0, int max_per, int use_skip, unsigned long long *active_total, const uint8_t *ref_rec,
+                        const unsigned short *ref_valid, int *launched) {
     if (n <= 0 || nnodes <= 0) return LSQ_OK;
-    if (m < 1 || m > LSQ_MAX_M) { lsq_set_error("m = %d out of range 1..16", m); return LSQ_EINVAL; }
     const int skip = (use_skip && valid) ? 1 : 0;
-    for (int done = 0; done < nnodes; done += LSQ_WALK_MAX_NODES) {
-        WalkNodes nodes;
-        nodes.count = (nnodes - done < LSQ_WALK_MAX_NODES) ? nnodes - done : LSQ_WALK_MAX_NODES;
-        nodes.pos0 = pos0 + done;
-        for (int t = 0; t < nodes.count; ++t) {
-            const int j = order[done + t];
-            if (j < 0 || j >= m) { lsq_set_error("node %d out of range 0..%d", j, m - 1); return LSQ_EINVAL; }
-            nodes.j[t] = (uint8_t)j;
-        }
+    LSQ_TRY(for_walk_launches(order, nnodes, pos0, m, max_per, launched, [&](const WalkNodes &nodes) -> int {
         const int lb = LSQ_LIGHT_LB(m);
         const unsigned grid = (unsigned)((n + 4 * lb - 1) / (4 * lb));
         LSQ_DISPATCH_M(m, hipLaunchKernelGGL(icm_wave_kernel<M_>, dim3(grid), dim3(256), 0, s, U, T, rec, valid, n, nodes, lsq_walk_slice_width(m), skip,
-                                             active_total, skip ? ref_rec : nullptr, skip ? ref_valid : nullptr, idle_if_set));
-    }
+                                             active_total, skip ? ref_rec : nullptr, skip ? ref_valid : nullptr, static_cast<const int *>(nullptr)));
+        return LSQ_OK;
+    }));
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }

@@ -1124,25 +1124,18 @@ int lsq_launch_q16_probe(hipStream_t s, const unsigned long long *probe, unsigne
 const void *lsq_probe_kernel_icmq() { return reinterpret_cast<const void *>(&q16_range_init_kernel); }
 
 template <class XT>
-static int unary_shift_panel_t(hipStream_t s, const XT *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
-                                 unsigned short *qflag, int64_t row0, lsq_q16_params *P) {
+int lsq_launch_unary_shift_panel(hipStream_t s, const XT *Xp, int64_t rows, int d, int m, const lsq_q16_work &w, int64_t row0) {
     if (rows <= 0) return LSQ_OK;
     const int64_t shift_blocks = (rows * 16 + 255) / 256;
     // the chunk maximum is not collected here (a scratch word takes it): the parameters were fixed from the sample
-    LSQ_SHIFT_LAUNCH(d, dim3((unsigned)(shift_blocks < 2048 ? shift_blocks : 2048)), s, Xp, means, rows, d, m, sigma_p,
-                       qrange + 2 * LSQ_MAX_M + 3, qrange + 2 * LSQ_MAX_M + 2, qflag, row0, P);
+    LSQ_SHIFT_LAUNCH(d, dim3((unsigned)(shift_blocks < 2048 ? shift_blocks : 2048)), s, Xp, w.means, rows, d, m, w.sigma + (size_t)row0 * m,
+                       &w.qrange[lsq_q16_work::Q_PANEL_SINK], &w.qrange[lsq_q16_work::Q_SIGBOUND], w.qflag, row0, w.P);
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }
 
-int lsq_launch_unary_shift_panel(hipStream_t s, const float *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
-                                 unsigned short *qflag, int64_t row0, lsq_q16_params *P) {
-    return unary_shift_panel_t(s, Xp, rows, d, m, means, sigma_p, qrange, qflag, row0, P);
-}
-int lsq_launch_unary_shift_panel(hipStream_t s, const uint8_t *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
-                                 unsigned short *qflag, int64_t row0, lsq_q16_params *P) {
-    return unary_shift_panel_t(s, Xp, rows, d, m, means, sigma_p, qrange, qflag, row0, P);
-}
+template int lsq_launch_unary_shift_panel(hipStream_t, const float *, int64_t, int, int, const lsq_q16_work &, int64_t);
+template int lsq_launch_unary_shift_panel(hipStream_t, const uint8_t *, int64_t, int, int, const lsq_q16_work &, int64_t);      // 8-bit rows
 
 int lsq_q16_sample_rows(int64_t n, int d, int64_t *rts_out) {
     const int64_t nsample = d <= 128 ? 16384 : (d <= 512 ? 8192 : 4096);      // the pass costs 2 d m h flops per sampled vector: fewer of them at large d
@@ -1152,67 +1145,54 @@ int lsq_q16_sample_rows(int64_t n, int d, int64_t *rts_out) {
 }
 
 template <class XT>
-static int q16_prepare_t(hipStream_t s, const XT *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, uint16_t *Tq,
-                         int *bad, float *trange, unsigned *qrange, unsigned short *qflag, lsq_q16_params *P, int tables_changed,
-                         float *rowmin, float *means, float *sigma, float *colmean, float *colshift, const XT *Xsample, int64_t nsample_rows,
-                         float *sigma_sample) {
-    // bad[0]: a non-finite pair table (per call); rowmin / colmean [m*m*256], colshift [m*256], means [m*d]: per call; sigma [n*m]: per chunk;
-    // qrange[2*16 + 1]: sample flag, [2*16 + 2]: max |sigma|
+int lsq_launch_q16_prepare(hipStream_t s, const XT *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, const lsq_q16_work &w,
+                           int tables_changed) {
+    using W = lsq_q16_work;
+    const XT *Xsample = static_cast<const XT *>(w.Xsample);
+    unsigned *sigmax = &w.qrange[W::Q_SIGMAX];      // the sigma pass collects max |sigma| here; q16_params_kernel reads it and leaves the bound it assumed in Q_SIGBOUND, the word after
+    static_assert(W::Q_SIGBOUND == W::Q_SIGMAX + 1 && W::Q_WORDS == 2 * LSQ_MAX_M + 4, "q16_params_kernel's sigrange[0 .. 1], q16_range_init_kernel's fill");
     if (tables_changed) {
-        LSQ_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
-        hipLaunchKernelGGL(table_colmean_kernel, dim3((unsigned)(m * m)), dim3(256), 0, s, T, m, colmean);
-        hipLaunchKernelGGL(unary_colshift_kernel, dim3((unsigned)m), dim3(256), 0, s, colmean, m, colshift);
-        if (m > 1) hipLaunchKernelGGL(table_range_kernel, dim3((unsigned)(m * m)), dim3(256), 0, s, T, m, colmean, trange, rowmin, bad);
-        hipLaunchKernelGGL(codebook_means_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)m), dim3(256), 0, s, K, m, d, means);
+        LSQ_HIP(hipMemsetAsync(w.bad, 0, sizeof(int), s));
+        hipLaunchKernelGGL(table_colmean_kernel, dim3((unsigned)(m * m)), dim3(256), 0, s, T, m, w.colmean);
+        hipLaunchKernelGGL(unary_colshift_kernel, dim3((unsigned)m), dim3(256), 0, s, w.colmean, m, w.colshift);
+        if (m > 1) hipLaunchKernelGGL(table_range_kernel, dim3((unsigned)(m * m)), dim3(256), 0, s, T, m, w.colmean, w.trange, w.rowmin, w.bad);
+        hipLaunchKernelGGL(codebook_means_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)m), dim3(256), 0, s, K, m, d, w.means);
     }
     // sampled range of the SHIFTED unaries: about 16 384 vectors at d <= 128 (every rts-th panel of 128 consecutive ones) through the range-only GEMM pass
-    hipLaunchKernelGGL(q16_range_init_kernel, dim3(1), dim3(64), 0, s, qrange, m);      // zeros; min slots start at the largest key (one launch: m + 1 fills cost 5 us each)
+    hipLaunchKernelGGL(q16_range_init_kernel, dim3(1), dim3(64), 0, s, w.qrange, m);      // zeros; min slots start at the largest key (one launch: m + 1 fills cost 5 us each)
+    lsq_gemm_q16 range;
+    range.qrange = w.qrange; range.colshift = w.colshift;
     if (Xsample) {
         // host-buffer pipeline: the sample (the same rows the strided pass would read) was uploaded ahead of the panels, compacted; sigma of the sample,
         // its maximum (widened below) and the value ranges come from it alone; the panels' own sigma follow panel by panel (lsq_launch_unary_shift_panel)
-        const int64_t shift_blocks = (nsample_rows * 16 + 255) / 256;
-        LSQ_SHIFT_LAUNCH(d, dim3((unsigned)(shift_blocks < 2048 ? shift_blocks : 2048)), s, Xsample, means, nsample_rows, d, m,
-                           sigma_sample, qrange + 2 * LSQ_MAX_M + 1);
-        LSQ_TRY(lsq_launch_chain_gemm(s, Xsample, K, sci, -2.0f, nsample_rows, m * LSQ_H, d, LSQ_H, 0, 0, nullptr, 0, nsample_rows, 0, nullptr, 0, nullptr, 0, nullptr,
-                                      qrange, 1, sigma_sample, colshift));
-        LSQ_HIP(hipMemsetAsync(qflag, 0, sizeof(unsigned short) * (size_t)((n + 1) & ~(int64_t)1), s));
+        const int64_t shift_blocks = (w.nsample_rows * 16 + 255) / 256;
+        LSQ_SHIFT_LAUNCH(d, dim3((unsigned)(shift_blocks < 2048 ? shift_blocks : 2048)), s, Xsample, w.means, w.nsample_rows, d, m, w.sigma_sample, sigmax);
+        range.sigma = w.sigma_sample;
+        LSQ_TRY(lsq_launch_chain_gemm(s, Xsample, K, sci, -2.0f, w.nsample_rows, m * LSQ_H, d, LSQ_H, 0, 0, nullptr, 0, w.nsample_rows, 0, &range));
+        LSQ_HIP(hipMemsetAsync(w.qflag, 0, sizeof(unsigned short) * (size_t)((n + 1) & ~(int64_t)1), s));
     } else if (n > 0) {
         const int64_t shift_blocks = (n * 16 + 255) / 256;           // 16 vectors per block per pass, at most 8 blocks per CU in flight
-        LSQ_SHIFT_LAUNCH(d, dim3((unsigned)(shift_blocks < 2048 ? shift_blocks : 2048)), s, X, means, n, d, m, sigma,
-                           qrange + 2 * LSQ_MAX_M + 1);
+        LSQ_SHIFT_LAUNCH(d, dim3((unsigned)(shift_blocks < 2048 ? shift_blocks : 2048)), s, X, w.means, n, d, m, w.sigma, sigmax);
         int64_t rts64 = 1;
         (void)lsq_q16_sample_rows(n, d, &rts64);
-        const int rts = (int)rts64;
-        LSQ_TRY(lsq_launch_chain_gemm(s, X, K, sci, -2.0f, n, m * LSQ_H, d, LSQ_H, 0, 0, nullptr, 0, n, 0, nullptr, 0, nullptr, 0, nullptr, qrange, rts, sigma,
-                                      colshift));
-        LSQ_HIP(hipMemsetAsync(qflag, 0, sizeof(unsigned short) * (size_t)((n + 1) & ~(int64_t)1), s));
+        range.rts = (int)rts64; range.sigma = w.sigma;
+        LSQ_TRY(lsq_launch_chain_gemm(s, X, K, sci, -2.0f, n, m * LSQ_H, d, LSQ_H, 0, 0, nullptr, 0, n, 0, &range));
+        LSQ_HIP(hipMemsetAsync(w.qflag, 0, sizeof(unsigned short) * (size_t)((n + 1) & ~(int64_t)1), s));
     }
-    hipLaunchKernelGGL(q16_params_kernel, dim3(1), dim3(64), 0, s, trange, bad, qrange, m, P, qrange + 2 * LSQ_MAX_M + 1, Xsample ? 2.0f : 1.0f);
+    hipLaunchKernelGGL(q16_params_kernel, dim3(1), dim3(64), 0, s, w.trange, w.bad, w.qrange, m, w.P, sigmax, Xsample ? 2.0f : 1.0f);
     if (m > 1) {
         const int slq = lsq_q16_slice_width(m);
         const int64_t total = (int64_t)m * (LSQ_H / slq) * (m - 1) * LSQ_H * (slq / 8);
         const unsigned grid = (unsigned)((total + 255) / 256);
-        if (slq == 32) hipLaunchKernelGGL(tables_to_q16_slices_kernel<32>, dim3(grid), dim3(256), 0, s, T, Tq, m, P, rowmin, colmean);
-        else hipLaunchKernelGGL(tables_to_q16_slices_kernel<16>, dim3(grid), dim3(256), 0, s, T, Tq, m, P, rowmin, colmean);
+        if (slq == 32) hipLaunchKernelGGL(tables_to_q16_slices_kernel<32>, dim3(grid), dim3(256), 0, s, T, w.Tq, m, w.P, w.rowmin, w.colmean);
+        else hipLaunchKernelGGL(tables_to_q16_slices_kernel<16>, dim3(grid), dim3(256), 0, s, T, w.Tq, m, w.P, w.rowmin, w.colmean);
     }
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }
 
-int lsq_launch_q16_prepare(hipStream_t s, const float *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, uint16_t *Tq,
-                           int *bad, float *trange, unsigned *qrange, unsigned short *qflag, lsq_q16_params *P, int tables_changed,
-                           float *rowmin, float *means, float *sigma, float *colmean, float *colshift, const float *Xsample, int64_t nsample_rows,
-                           float *sigma_sample) {
-    return q16_prepare_t(s, X, n, d, K, sci, T, m, Tq, bad, trange, qrange, qflag, P, tables_changed, rowmin, means, sigma, colmean, colshift, Xsample,
-                         nsample_rows, sigma_sample);
-}
-int lsq_launch_q16_prepare(hipStream_t s, const uint8_t *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, uint16_t *Tq,
-                           int *bad, float *trange, unsigned *qrange, unsigned short *qflag, lsq_q16_params *P, int tables_changed,
-                           float *rowmin, float *means, float *sigma, float *colmean, float *colshift, const uint8_t *Xsample, int64_t nsample_rows,
-                           float *sigma_sample) {
-    return q16_prepare_t(s, X, n, d, K, sci, T, m, Tq, bad, trange, qrange, qflag, P, tables_changed, rowmin, means, sigma, colmean, colshift, Xsample,
-                         nsample_rows, sigma_sample);
-}
+template int lsq_launch_q16_prepare(hipStream_t, const float *, int64_t, int, const float *, const float *, const float *, int, const lsq_q16_work &, int);
+template int lsq_launch_q16_prepare(hipStream_t, const uint8_t *, int64_t, int, const float *, const float *, const float *, int, const lsq_q16_work &, int);      // 8-bit rows
 
 template <int M>
 static int launch_walkq_t(hipStream_t s, const float *U, const uint16_t *Uq, const uint16_t *Tq, const float *T, uint8_t *rec, unsigned short *valid,
@@ -1223,10 +1203,8 @@ static int launch_walkq_t(hipStream_t s, const float *U, const uint16_t *Uq, con
     constexpr int LDS_BYTES = RT::lds_bytes() + WALKQ_MISC_BYTES;      // slice table + two smallest keys + active list (+ validity mirror) + the block's scalars
     static_assert(LDS_BYTES <= 160 * 1024 && WALKQ_MISC_BYTES <= 768, "slice table + keys must fit the 160 KiB LDS");
     constexpr int NBLK = 256;
-    const int64_t rounds = (n + NBLK * (int64_t)PP - 1) / (NBLK * (int64_t)PP);      // passes per block
-    int64_t per = rounds > 0 ? (n + NBLK * rounds - 1) / (NBLK * rounds) : 1;
-    per = per > PP ? PP : (per < 1 ? 1 : per);
-    const int per_pass = (int)per, npass = (int)((n + per - 1) / per);
+    int per_pass = 1, npass = 1;
+    lsq_walk_geometry(n, PP, &per_pass, &npass);
     const int direct_max = light >= 0 ? light : LSQ_KNOB("LSQ_WALK_DIRECT", 160);
     const int skip = (use_skip && valid) ? 1 : 0;
     static LdsOptIn optin;
@@ -1250,20 +1228,12 @@ static int launch_walkq_t(hipStream_t s, const float *U, const uint16_t *Uq, con
 
 // the filtered counterpart of lsq_launch_icm_walk (the caller has read the chunk's verdict on the host)
 int lsq_launch_icm_walkq(hipStream_t s, const float *U, const uint16_t *Uq, const uint16_t *Tq, const float *T, uint8_t *rec, unsigned short *valid,
-                         int64_t n, int m, const int32_t *order, int nnodes, int pos0, int use_skip, unsigned long long *active_total, int light,
-                         const uint8_t *ref_rec, const unsigned short *ref_valid, const lsq_q16_params *P, const unsigned short *qflag, const unsigned *gate) {
+                         int64_t n, int m, const int32_t *order, int nnodes, int pos0, int max_per, int use_skip, unsigned long long *active_total, int light,
+                         const uint8_t *ref_rec, const unsigned short *ref_valid, const lsq_q16_params *P, const unsigned short *qflag, const unsigned *gate,
+                         int *launched) {
     if (n <= 0 || nnodes <= 0) return LSQ_OK;
-    if (m < 1 || m > LSQ_MAX_M) { lsq_set_error("m = %d out of range 1..16", m); return LSQ_EINVAL; }
-    for (int done = 0; done < nnodes; done += LSQ_WALK_MAX_NODES) {
-        WalkNodes nodes;
-        nodes.count = (nnodes - done < LSQ_WALK_MAX_NODES) ? nnodes - done : LSQ_WALK_MAX_NODES;
-        nodes.pos0 = pos0 + done;
-        for (int t = 0; t < nodes.count; ++t) {
-            const int j = order[done + t];
-            if (j < 0 || j >= m) { lsq_set_error("node %d out of range 0..%d", j, m - 1); return LSQ_EINVAL; }
-            nodes.j[t] = (uint8_t)j;
-        }
+    return for_walk_launches(order, nnodes, pos0, m, max_per, launched, [&](const WalkNodes &nodes) -> int {
         LSQ_DISPATCH_M(m, LSQ_TRY((launch_walkq_t<M_>(s, U, Uq, Tq, T, rec, valid, n, nodes, use_skip, active_total, light, ref_rec, ref_valid, P, qflag, gate))));
-    }
-    return LSQ_OK;
+        return LSQ_OK;
+    });
 }

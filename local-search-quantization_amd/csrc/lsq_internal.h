@@ -129,21 +129,25 @@ const void *lsq_probe_kernel_icmq();
 //          = (c / h) * plane_stride + ((c % h) / slice) * (Mtot * slice) + (c % h) % slice + r * slice   (slice-major)
 // Chain = k-ascending fmaf from +0.  The launch covers output rows [rbase, rbase + M) of a Mtot-row result (A points at
 // row rbase): row r above counts from rbase -- lets the caller build the unaries panel by panel under the H2D copies.
-// Optional second output (Dq != nullptr): the same values as 16-bit fixed-point levels in slice-major u16 planes of slice width slice_q,
+// Optional second output (q != nullptr, q->Dq != nullptr): the same values as 16-bit fixed-point levels in slice-major u16 planes of slice width slice_q,
 // Dq[(c / h) * Mtot * h + ((c % h) / slice_q) * Mtot * slice_q + r * slice_q + (c % h) % slice_q] = rint((v + colshift[c] + sigma[r][c / h] - qp->node[c / h].loU) * invD).
+struct lsq_gemm_q16 {
+    uint16_t *Dq = nullptr; int slice_q = 0;
+    lsq_q16_params *qp = nullptr;
+    unsigned short *qflag = nullptr;      // [Mtot] u16 (Mtot even-padded): bit j raised when a value of plane j fell outside the level range
+    // sigma (optional, [Mtot][N / h] floats) / colshift (optional, [N] floats): per-(row, plane) and per-column shifts added to a value before its LEVEL is taken (and
+    // in the range-only pass); the f32 output D is not shifted.  A shift common to all candidates of a node update cannot change its argmin (lsq_icmq.hip).
+    const float *sigma = nullptr, *colshift = nullptr;
+    // qrange != nullptr: range-only pass over every rts-th 128-row panel of A, nothing stored; qrange[2 j], [2 j + 1] = min / max keys
+    unsigned *qrange = nullptr; int rts = 1;
+};
 int lsq_launch_chain_gemm(hipStream_t s, const float *A, const float *Bm, const float *addv, float alpha,
                           int64_t M, int N, int Kd, int h, int64_t plane_stride, int64_t row_stride, float *D, int slice,
-                          int64_t Mtot, int64_t rbase, uint16_t *Dq = nullptr, int slice_q = 0, struct lsq_q16_params *qp = nullptr,
-                          int64_t lda = 0, unsigned short *qflag = nullptr, unsigned *qrange = nullptr, int rts = 1, const float *sigma = nullptr, const float *colshift = nullptr);
-// sigma (optional, [Mtot][N / h] floats) / colshift (optional, [N] floats): per-(row, plane) and per-column shifts added to a value before its LEVEL is
-// taken (and in the range-only pass); the f32 output D is not shifted.  A shift common to all candidates of a node update cannot change its argmin (lsq_icmq.hip).
-// lda: row stride of A in floats (0 = Kd).  rts: range-only pass over every rts-th 128-row panel of A.  qflag [Mtot] u16 (Mtot even-padded): bit j raised when a value of
-// plane j fell outside the level range (Dq output).  qrange != nullptr: range-only pass, nothing stored; qrange[2 j], [2 j + 1] = min / max keys.
-// 8-bit data rows (A = X as uint8_t, lda in bytes): the same contract and, uint8 -> f32 being exact, the same bits as the call above on the widened rows
+                          int64_t Mtot, int64_t rbase, const lsq_gemm_q16 *q = nullptr);
+// 8-bit data rows (A = X as uint8_t, Kd bytes apart): the same contract and, uint8 -> f32 being exact, the same bits as the call above on the widened rows
 int lsq_launch_chain_gemm(hipStream_t s, const uint8_t *A, const float *Bm, const float *addv, float alpha,
                           int64_t M, int N, int Kd, int h, int64_t plane_stride, int64_t row_stride, float *D, int slice,
-                          int64_t Mtot, int64_t rbase, uint16_t *Dq = nullptr, int slice_q = 0, struct lsq_q16_params *qp = nullptr,
-                          int64_t lda = 0, unsigned short *qflag = nullptr, unsigned *qrange = nullptr, int rts = 1, const float *sigma = nullptr, const float *colshift = nullptr);
+                          int64_t Mtot, int64_t rbase, const lsq_gemm_q16 *q = nullptr);
 // sci[r] = chain_t(Kb[r][t]^2)
 int lsq_launch_sqnorms(hipStream_t s, const float *Kb, int rows, int d, float *sci);
 
@@ -163,43 +167,72 @@ int lsq_launch_perturb(hipStream_t s, const uint8_t *src, uint8_t *dst, int64_t 
 constexpr int lsq_walk_slice_width(int m) { return m <= 8 ? 16 : 8; }      // f32 candidates per slice
 constexpr int lsq_q16_slice_width(int m) { return 2 * lsq_walk_slice_width(m); }      // candidates per 16-bit slice: the same bytes per piece as the f32 walk
 int lsq_launch_tables_to_slices(hipStream_t s, const float *T, float *Ts, int m, int sl);
+// vectors per block pass of the f32 LDS-walk kernel: table + 10 B per vector must fit the 160 KiB LDS
+constexpr int lsq_walk_pp(int M, int SL) {
+    const int avail = 160 * 1024 - 256 - (M - 1) * LSQ_H * (SL / 4) * 16;      // bytes left beside the slice table
+    const int pp = avail / 10 / 64 * 64;
+    return pp > 4096 ? 4096 : pp;                                             // 4096 up to m = 14 (SL = 8), 4032 at m = 16
+}
+// geometry of a walk launch (f32 or filtered) over n vectors, 256 blocks: vectors per pass (<= the kernel's LDS budget pp), number of passes (= segments)
+inline void lsq_walk_geometry(int64_t n, int pp, int *per_pass, int *npass) {
+    const int64_t rounds = (n + 256 * (int64_t)pp - 1) / (256 * (int64_t)pp);          // passes per block
+    int64_t per = rounds > 0 ? (n + 256 * rounds - 1) / (256 * rounds) : 1;
+    per = per > pp ? pp : (per < 1 ? 1 : per);
+    *per_pass = (int)per;
+    *npass = (int)((n + per - 1) / per);
+}
 // valid (optional): validity masks, maintained by the kernel; use_skip: skip vectors whose bit j is set (exact);
 // active_total (optional): += number of vectors actually recomputed; ablation != 0: timing-only variants (m = 8), garbage results.
 // U is the slice-major unary buffer of ALL nodes; T (optional) the row-major tables for light blocks' L2 gathers; order[nnodes] = node updates run back to back inside the launch
 // (a block owns its vectors for the whole launch): 1 entry = one node update, icmiter*m entries = a whole ILS iteration.
-void lsq_walk_geometry(int64_t n, int m, int *per_pass, int *npass, int *pp_cap);      // segments of the walk kernel over n vectors
+// The three walk launchers cut order[nnodes] into launches of at most max_per node updates (1 .. 64 = LSQ_WALK_MAX_NODES; lsq_wave.h holds the one splitter) and
+// add the number of launches they made to *launched (optional).
 int lsq_launch_icm_wave(hipStream_t s, const float *U, const float *T, uint8_t *rec, unsigned short *valid, int64_t n, int m, const int32_t *order,
-                        int nnodes, int pos0, int use_skip, unsigned long long *active_total, const uint8_t *ref_rec, const unsigned short *ref_valid,
-                        const int *idle_if_set = nullptr);      // chunks in which every block would be light: a wave owns its vectors through the launch
+                        int nnodes, int pos0, int max_per, int use_skip, unsigned long long *active_total, const uint8_t *ref_rec,
+                        const unsigned short *ref_valid, int *launched);      // chunks in which every block would be light: a wave owns its vectors through the launch
 int lsq_launch_icm_walk(hipStream_t s, const float *U, const float *Ts, const float *T, uint8_t *rec, unsigned short *valid, int64_t n, int m,
-                        const int32_t *order, int nnodes, int pos0, int use_skip, unsigned long long *active_total, int ablation, int light,
-                        const uint8_t *ref_rec, const unsigned short *ref_valid, const int *idle_if_set = nullptr);
+                        const int32_t *order, int nnodes, int pos0, int max_per, int use_skip, unsigned long long *active_total, int ablation, int light,
+                        const uint8_t *ref_rec, const unsigned short *ref_valid, const int *idle_if_set, int *launched);
 // idle_if_set (optional, device): the launch does nothing when *idle_if_set != 0 (the filtered walk handled it)
-// 16-bit filtered walk (lsq_icmq.hip).  lsq_launch_q16_prepare: per chunk, after the pair tables and before the unary GEMM -- bounds,
-// parameters P and the 16-bit slice tables Tq [m][256/SLQ][m-1][256][SLQ]; tables_changed = 1 on the first chunk of a call.
-// bad (1 int), trange (3 m m floats), qrange (2 * 16 + 2 u32): scratch.  lsq_launch_icm_walkq: same contract as lsq_launch_icm_walk plus
-// Uq (the GEMM's u16 planes), Tq and P; the caller launches it only after reading the chunk's verdict (P->ok, P->nflag) on the host.
-int lsq_launch_q16_prepare(hipStream_t s, const float *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, uint16_t *Tq,
-                           int *bad, float *trange, unsigned *qrange, unsigned short *qflag, lsq_q16_params *P, int tables_changed,
-                           float *rowmin, float *means, float *sigma, float *colmean, float *colshift, const float *Xsample = nullptr,
-                           int64_t nsample_rows = 0, float *sigma_sample = nullptr);
-// Xsample (optional; the host-buffer pipeline): the rows the strided sample pass would read -- every rts-th 128-row panel, lsq_q16_sample_rows -- already
-// compacted on the device; the level parameters come from them alone (max |sigma| widened x2) and X itself is not touched: its sigma are computed panel by
-// panel as the panels land (lsq_launch_unary_shift_panel: vectors beyond the assumed |sigma| bound are flagged for the f32 routine).
-int lsq_launch_q16_prepare(hipStream_t s, const uint8_t *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, uint16_t *Tq,
-                           int *bad, float *trange, unsigned *qrange, unsigned short *qflag, lsq_q16_params *P, int tables_changed,
-                           float *rowmin, float *means, float *sigma, float *colmean, float *colshift, const uint8_t *Xsample = nullptr,
-                           int64_t nsample_rows = 0, float *sigma_sample = nullptr);      // 8-bit rows
+// 16-bit filtered walk (lsq_icmq.hip).  The device memory its host side passes around, mapped ONCE (carved by q16_map in lsq_api.hip; no launcher does pointer
+// arithmetic of its own).  Per call: bad (1 int: a non-finite pair table), trange (3 floats per pair table), rowmin / colmean [m*m*256], colshift [m*256], means
+// [m*d]; per chunk: sigma [n*m], qflag, Uq (the GEMM's u16 planes), qrange.  Tq: the 16-bit slice tables [m][256/SLQ][m-1][256][SLQ].
+struct lsq_q16_work {
+    // qrange: 2 * LSQ_MAX_M range keys (min / max per node), then four words
+    enum { Q_NONFINITE = 2 * LSQ_MAX_M,      // raised by the range pass: a non-finite value in the sample
+           Q_SIGMAX,                         // max |sigma| of the chunk -- or of its sample -- as the sigma pass collects it (bit pattern of a non-negative float)
+           Q_SIGBOUND,                       // the |sigma| bound the parameters assumed (q16_params_kernel writes it): the panel passes flag vectors beyond it
+           Q_PANEL_SINK,                     // where a panel pass's own maximum goes: nothing reads it, the parameters were fixed from the sample
+           Q_WORDS };                        // q16_range_init_kernel fills exactly these
+    uint16_t *Tq = nullptr, *Uq = nullptr;
+    int *bad = nullptr;
+    float *trange = nullptr;
+    unsigned *qrange = nullptr;
+    unsigned short *qflag = nullptr;
+    lsq_q16_params *P = nullptr;
+    float *rowmin = nullptr, *colmean = nullptr, *colshift = nullptr, *means = nullptr, *sigma = nullptr;
+    // sample mode (the host-buffer pipeline): the rows the strided sample pass would read -- every rts-th 128-row panel, lsq_q16_sample_rows -- already compacted on
+    // the device, in X's element type; the level parameters come from them alone (max |sigma| widened x2) and X itself is not touched: its sigma are computed panel
+    // by panel as the panels land (lsq_launch_unary_shift_panel: vectors beyond the assumed |sigma| bound are flagged for the f32 routine)
+    const void *Xsample = nullptr;
+    int64_t nsample_rows = 0;
+    float *sigma_sample = nullptr;
+};
+// lsq_launch_q16_prepare: per chunk, after the pair tables and before the unary GEMM -- bounds, parameters P and Tq; tables_changed = 1 on the first chunk of a call.
+// XT: float, or uint8_t for 8-bit rows (the two instantiations lsq_icmq.hip provides)
+template <class XT>
+int lsq_launch_q16_prepare(hipStream_t s, const XT *X, int64_t n, int d, const float *K, const float *sci, const float *T, int m, const lsq_q16_work &w,
+                           int tables_changed);
 int lsq_q16_sample_rows(int64_t n, int d, int64_t *rts_out);      // -> number of 128-row sample panels; *rts_out = the panel stride
-int lsq_launch_unary_shift_panel(hipStream_t s, const float *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
-                                 unsigned short *qflag, int64_t row0, lsq_q16_params *P);
-int lsq_launch_unary_shift_panel(hipStream_t s, const uint8_t *Xp, int64_t rows, int d, int m, const float *means, float *sigma_p, unsigned *qrange,
-                                 unsigned short *qflag, int64_t row0, lsq_q16_params *P);      // 8-bit rows
-// rowmin [m*m*256], means [m*d], colmean [m*m*256], colshift [m*256] (per call), sigma [n*m] (per chunk); trange: 3 floats per pair table
+// sigma (and flags) of the chunk's rows [row0, row0 + rows), Xp pointing at the first of them
+template <class XT>
+int lsq_launch_unary_shift_panel(hipStream_t s, const XT *Xp, int64_t rows, int d, int m, const lsq_q16_work &w, int64_t row0);
+// lsq_launch_icm_walkq: same contract as lsq_launch_icm_walk plus Uq, Tq and P; the caller launches it only after reading the chunk's verdict (P->ok, P->nflag) on
+// the host -- or gives it a gate
 int lsq_launch_icm_walkq(hipStream_t s, const float *U, const uint16_t *Uq, const uint16_t *Tq, const float *T, uint8_t *rec, unsigned short *valid,
-                         int64_t n, int m, const int32_t *order, int nnodes, int pos0, int use_skip, unsigned long long *active_total, int light,
+                         int64_t n, int m, const int32_t *order, int nnodes, int pos0, int max_per, int use_skip, unsigned long long *active_total, int light,
                          const uint8_t *ref_rec, const unsigned short *ref_valid, const lsq_q16_params *P, const unsigned short *qflag,
-                         const unsigned *gate = nullptr);
+                         const unsigned *gate, int *launched);
 // option "async": the chunk's road decided on the device (lsq_icmq.hip): road[0] = 2 filtered walk / 0 f32 walk, road[1] = chunks handed over
 int lsq_launch_q16_road(hipStream_t s, const lsq_q16_params *P, unsigned *road, int64_t pairs, int64_t fallback_div);
 int lsq_launch_q16_probe(hipStream_t s, const unsigned long long *probe, unsigned long long *totals, unsigned *road, int64_t probe_div);

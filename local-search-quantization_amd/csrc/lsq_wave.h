@@ -71,13 +71,6 @@ __device__ inline int wave_first_argmin(f32x4 s, int lane) {
     return best;
 }
 
-// vectors per block pass of the LDS-walk kernel: table + 10 B per vector must fit the 160 KiB LDS
-constexpr int lsq_walk_pp(int M, int SL) {
-    const int avail = 160 * 1024 - 256 - (M - 1) * LSQ_H * (SL / 4) * 16;      // bytes left beside the slice table
-    const int pp = avail / 10 / 64 * 64;
-    return pp > 4096 ? 4096 : pp;                                             // 4096 up to m = 14 (SL = 8), 4032 at m = 16
-}
-
 // Code j of vector i changes: the whole record leaves as aligned words (a wave's stores cover whole lines: no byte-masked partial writes);
 // callers skip the store when the code is unchanged.
 template <int CS>
@@ -252,6 +245,27 @@ __device__ inline void light_update(uint8_t *__restrict__ rec, unsigned short *_
 #define LSQ_WALK_MAX_NODES 64
 struct WalkNodes { int count; int pos0; uint8_t j[LSQ_WALK_MAX_NODES]; };      // kernel argument: the node updates of one launch, in order; pos0 = position of j[0] in the ILS iteration's node sequence (trace counters)
 
+// The ONE splitter of the three walk launchers: order[nnodes] (node updates run back to back, the first at position pos0) goes to launch(nodes) in pieces of
+// at most max_per node updates (1 = a launch per node update; anything outside 1 .. LSQ_WALK_MAX_NODES = as many as a launch holds); *launched (optional) += the
+// launches made.
+template <class Launch>
+int for_walk_launches(const int32_t *order, int nnodes, int pos0, int m, int max_per, int *launched, Launch launch) {
+    if (m < 1 || m > LSQ_MAX_M) { lsq_set_error("m = %d out of range 1..16", m); return LSQ_EINVAL; }
+    if (max_per < 1 || max_per > LSQ_WALK_MAX_NODES) max_per = LSQ_WALK_MAX_NODES;
+    for (int done = 0; done < nnodes; done += max_per) {
+        WalkNodes nodes;
+        nodes.count = (nnodes - done < max_per) ? nnodes - done : max_per;
+        nodes.pos0 = pos0 + done;
+        for (int t = 0; t < nodes.count; ++t) {
+            const int j = order[done + t];
+            if (j < 0 || j >= m) { lsq_set_error("node %d out of range 0..%d", j, m - 1); return LSQ_EINVAL; }
+            nodes.j[t] = (uint8_t)j;
+        }
+        LSQ_TRY(launch(nodes));
+        if (launched) *launched += 1;
+    }
+    return LSQ_OK;
+}
 
 // One-time, per-device opt-in to > 64 KiB of dynamic LDS for one kernel instantiation.  lsq_multi_* runs one host thread
 // per device through the launchers, so the "done" flags are guarded (unsynchronised function-local statics).

@@ -37,9 +37,10 @@ MUTANTS = [
      "    return LSQ_OK;\n",
      "default", ("encode_icm_fully_auto", "encoding_icm_auto")),
     # the road word of option "async": a blocking call still gated by the device word the async call before it used
+    # (the ONE reset of the chunk state, where a chunk's unaries start to be built, carries the old `on_device` over)
     ("q16_verdict_keeps_chunk_road_dev",
-     "static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m) {\n    c->chunk_road_dev = false;\n",
-     "static int q16_verdict(lsq_ctx *c, bool q16, int64_t cn, int m) {\n",
+     "    c->chunk_road = ChunkRoad{};\n",
+     "    c->chunk_road = ChunkRoad{false, c->chunk_road.on_device};\n",
      "s6_forced", ("encode_icm_dev_nb", "encode_icm_dev")),
     # the statistics of option "async": never folded into timings(), wiped by the next call
     ("finish_call_keeps_pending_fold",

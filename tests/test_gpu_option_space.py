@@ -3,8 +3,8 @@
 A. the light / staged switch of both walk kernels (`nact <= direct_max`, csrc/lsq_icmq.hip and csrc/lsq_icm.hip) with the threshold moved through every
    block's activity range, so that a block alternates between the two routines inside one launch -- they share the records, the validity words and, for
    m <= 8, the LDS validity mirror; every instantiation family; two passes per block with the mirror reloaded in between (option `chunk` above its default);
-B. node sequences longer than one launch holds (icmiter * m > 64 = LSQ_WALK_MAX_NODES): run_sweeps and the three launchers split them, the per-position
-   trace wraps modulo 64 (lsq_internal.h), option `per_node` cuts them into single node updates, the filter probe into two parts;
+B. node sequences longer than one launch holds (icmiter * m > 64 = LSQ_WALK_MAX_NODES): the three launchers' one splitter cuts them (lsq_wave.h), the
+   per-position trace wraps modulo 64 (lsq_internal.h), option `per_node` cuts them into single node updates, the filter probe into two parts;
 C. every PAIR of option values (tests/option_space.py), one encode per row of a covering array.
 
 The reference is always the CPU oracle (oracle.encode_icm: it executes every node update and knows nothing about roads): codes equal, objectives within
@@ -329,12 +329,17 @@ def test_long_node_sequences_walk_roads(lsq, oracle, m, J):
 
     a = long_road(lsq, P, "s6 forced", FORCED, 1, light0=False,
                   expect=lambda t: t["filtered_blocks"] > 0 and t["staged_blocks"] == 0 and t["light_blocks"] == 0)
-    long_road(lsq, P, "s6 default light", dict(schedule=6, q16_min=0, filter_probe_div=0, filter_fallback_div=0), 2)
+    # icm_launches in closed form (run_sweeps, csrc/lsq_api.hip): with schedule >= 4 one run_sweeps call issues its nsweeps * m node updates in launches of at
+    # most 64 -- ceil(nsweeps * m / 64) of them on the filtered walk, the f32 walk and the wave kernel alike -- and without the probe encode_chunk calls it
+    # once per ILS iteration with nsweeps = J: nl launches per iteration, whichever road the chunk's verdict names
+    long_road(lsq, P, "s6 default light", dict(schedule=6, q16_min=0, filter_probe_div=0, filter_fallback_div=0), 2,
+              expect=lambda t: t["icm_launches"] == 2 * nl)
     long_road(lsq, P, "s4 light=0", dict(schedule=4, light=0), 2, light0=False,
               expect=lambda t: t["staged_blocks"] > 0 and t["light_blocks"] == 0 and t["filtered_blocks"] == 0 and t["icm_launches"] == 2 * nl)
     long_road(lsq, P, "s3", dict(schedule=3), 1, expect=lambda t: t["icm_launches"] == J * m)
     long_road(lsq, wave_problem(m, J), "wave kernel", {}, 2, light0=False,
-              expect=lambda t: t["light_blocks"] > 0 and t["staged_blocks"] == 0 and t["filtered_blocks"] == 0)
+              expect=lambda t: t["light_blocks"] > 0 and t["staged_blocks"] == 0 and t["filtered_blocks"] == 0 and t["icm_launches"] == 2 * nl)
+    # (2048 rows < q16_min: no filtered walk, so no probe; 8 vectors per block <= wave_max: the wave kernel's launcher, nl launches in each of two iterations)
     # per_node = 1: one launch per node update -- the same codes, accept counters, walk counters and trace as the launches of 64
     b = long_road(lsq, P, "s6 forced per_node", dict(FORCED, per_node=1), 1, light0=False,
                   expect=lambda t: t["icm_launches"] == J * m)
@@ -351,10 +356,22 @@ def test_long_node_sequences_entry_points(lsq, oracle, m, J):
     word: both walks are enqueued), the 8-bit device call, the filter probe left on -- in a call of one iteration it splits the iteration's sweeps in two, in a
     call of two it reads the first iteration's counters --, and the two CPU-shaped calls (niter * m > 64)."""
     P = long_problem(m, J)
-    long_road(lsq, P, "async", {}, 2, nonblocking=True)
-    long_road(lsq, P, "u8 device call", {}, 1, u8=True)
+    # icm_launches in closed form, from run_sweeps and encode_chunk (csrc/lsq_api.hip).  One run_sweeps call of nsweeps sweeps makes ceil(nsweeps * m / 64)
+    # launches on whichever walk it takes (schedule >= 4, per_node = 0), and none when nsweeps = 0.
+    nl = -(-J * m // 64)                                         # ... of a whole iteration
+    # The probe (filter_probe_div > 0, a chunk the verdict gave to the filtered walk) cuts the FIRST iteration into probe_sweeps and the rest, two run_sweeps
+    # calls.  A call of two iterations: probe_sweeps = J, the rest is empty -- nl + 0, then nl for the second iteration, probed or not.  A call of one
+    # iteration: probe_sweeps = 2 (J >= 3 in every pair), so ceil(2 m / 64) + ceil((J - 2) m / 64); the second part takes the road the probe chose, at the
+    # same count (280 vectors per block > wave_max: never the wave kernel).
+    assert J >= 3
+    split = -(-2 * m // 64) + -(-(J - 2) * m // 64)
+    # option "async": the verdict and the probe are device words, so every run_sweeps call enqueues the filtered launches AND the f32 launches behind them:
+    # iteration one nl + nl (+ an empty rest), iteration two nl + nl
+    long_road(lsq, P, "async", {}, 2, nonblocking=True, expect=lambda t: t["icm_launches"] == 4 * nl)
+    long_road(lsq, P, "u8 device call", {}, 1, u8=True, expect=lambda t: t["icm_launches"] == split)      # the defaults probe: one iteration, cut in two
     for nsnap in (1, 2):
-        long_road(lsq, P, "probe on, %d iteration(s)" % nsnap, dict(schedule=6, q16_min=0, filter_probe_div=8), nsnap)
+        long_road(lsq, P, "probe on, %d iteration(s)" % nsnap, dict(schedule=6, q16_min=0, filter_probe_div=8), nsnap,
+                  expect=lambda t: t["icm_launches"] == (split if nsnap == 1 else 2 * nl))
     # lsq_encoding_icm: one ILS iteration with the accept rule = the call's first snapshot (it = 0)
     with lsq.Engine(0) as eng:
         eng.reset_timings()
@@ -362,6 +379,7 @@ def test_long_node_sequences_entry_points(lsq, oracle, m, J):
         t, tr = eng.timings(), eng.walk_trace()
     assert np.array_equal(B1, P.ref[0]), "encoding_icm: %d rows differ from the oracle" % int((B1 != P.ref[0]).any(axis=1).sum())
     assert tr.sum() == t["icm_node_updates"] > 0
+    assert t["icm_launches"] == split, (t["icm_launches"], split)      # one iteration under the default probe: cut in two, as above
     # lsq_encode_icm_fully: perturbation + sweeps without the accept step (the oracle's worker), on the first 20 480 rows, filtered walk forced and defaults
     Xs, Bs = P.X[:NFULLY], P.B0[:NFULLY]
     want = oracle.encode_icm_fully(Xs, Bs, P.K, m, H, J, True, P.npert, seed=SEED, it=0)
