@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 1400
+#define LSQ_VERSION 1500
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -137,6 +137,7 @@ LSQ_API int lsq_set_stream(lsq_ctx *ctx, void *hip_stream);
  *        (starts at 0, advances by one per such call).
  *   "rerank_batch" (default 0): queries per batch of the re-rank stage of every lsq_index created on this context; 0 = automatic (batches of at most
  *        2^28 (query, candidate) records, like the scans).  A test hook: small shapes cross batch boundaries.  Same results.
+ *   "knn_u8_int" (0/1, default 1): 0 = lsq_index_knn widens 8-bit rows and queries even where its integer road applies.  A test hook: same results.
  *   (liblsq_mi355x_tuning.so only) "ablation": timing-only kernel variants whose results are garbage. */
 LSQ_API int lsq_set_option(lsq_ctx *ctx, const char *key, int64_t value);
 LSQ_API int lsq_get_timings(lsq_ctx *ctx, lsq_timings *out);      /* writes the v400 layout only (everything before table_reuses: a caller built against any header since v400 is never overrun); the fields appended since come through: */
@@ -438,6 +439,36 @@ LSQ_API int lsq_index_rerank(lsq_index *ix, float *dists, int *ids, const float 
 LSQ_API int lsq_index_get_stats(lsq_index *ix, lsq_index_stats *out);
 /* LSQ_EINVAL for all of them: a null pointer, nn > L, shortlist > n, a re-rank on an index without base rows, a search on an index without codes;
  * nothing is launched then. */
+
+/* ---- (3f) exact k-NN on the index's resident base rows, f32 or un-widened uint8 (since v1500) -----------------------------------------------------
+ * The ground truth of a recall figure (what the reference reads from sift_groundtruth.ivecs and feeds to eval_recall, src/linscan/Linscan.jl:76-117)
+ * from the base the index already holds: a .bvecs set is never widened to f32, on the host or in HBM.  ONE contract for every road: per query the nn
+ * smallest (dist, id) pairs over the base rows, dist with the bits lsq_knn_exact gives for the same (query, row) on the widened matrices, ties to the
+ * smaller id, NaN last; ids int32 in the caller's id_base (0 or 1) as in lsq_index_rerank.
+ *   f32 base:                      lsq_knn_exact_dev on the resident rows, ids shifted by id_base.
+ *   uint8 base, f32 queries or d > 258:  the same kernel, bytes widened in registers (exact).
+ *   uint8 base, uint8 queries, d <= 258: D = |x|^2 + |q|^2 - 2<x, q> in 32-bit integers (v_dot4_u32_u8), dist = (float)D.  The same bits: every term of the
+ *        f32 chain is an integer <= 255^2 and its partial sums only grow, so while the final D <= 2^24 no step rounds; d*255^2 <= 2^24 up to d = 258.
+ * queries [nq][ldq] f32 (queries_u8 = 0, 4-byte aligned) or uint8 (queries_u8 = 1, any byte alignment), ldq in ELEMENTS; dists / ids [nq][nn];
+ * on_device: 0 = queries, dists, ids are host buffers, 1 = device buffers.  The call uses the index's own scan state; options "linscan_exhaustive",
+ * "linscan_rank" and "profile" act as on lsq_knn_exact_dev, "knn_u8_int" = 0 takes the integer road out.
+ * LSQ_EINVAL, nothing launched: an index without base rows, nn < 1, nn > n, nq < 1, ldq < d, an id_base other than 0 / 1, f32 queries not 4-byte
+ * aligned, a null pointer. */
+LSQ_API int lsq_index_knn(lsq_index *ix, float *dists, int *ids, const void *queries, int queries_u8, int nq, int ldq, int nn, int id_base, int on_device);
+/* what the LAST lsq_index_knn call did (a struct of its own: lsq_index_stats is ABI and keeps its size) */
+typedef struct lsq_index_knn_info {
+    int64_t queries, rows, batches;      /* queries answered, base rows scanned, batches of the selection */
+    int64_t fallback_queries;            /* queries redone by the exhaustive road */
+    int64_t exhaustive;                  /* 1 = every distance written and sorted */
+    int64_t int_road;                    /* 1 = the integer road ran */
+    double norms_ms, scan_ms, select_ms; /* with option "profile" = 1: the integer road's norms; sample + scan; sort + hand-out */
+} lsq_index_knn_info;
+LSQ_API int lsq_index_get_knn_info(lsq_index *ix, lsq_index_knn_info *out);
+/* The host drop-in and checker (no context): lsq_knn_exact_cpu for base rows and queries that are f32 or uint8 (base_u8 / queries_u8) at ANY byte
+ * alignment, ldb / ldq in elements; uint8 elements are widened (exact) and the f32 chain runs: the bits of lsq_knn_exact_cpu on the widened matrices.
+ * ids uint32 0-based.  LSQ_EINVAL as lsq_knn_exact_cpu. */
+LSQ_API int lsq_knn_exact_u8_cpu(float *dists, uint32_t *ids, const void *base, int base_u8, const void *queries, int queries_u8, int n, int nq, int d,
+                                 int ldb, int ldq, int nn, int nthreads);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB      src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

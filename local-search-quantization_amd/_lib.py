@@ -49,6 +49,14 @@ class IndexDesc(C.Structure):
                 ("dbnorms", C.c_void_p), ("base", C.c_void_p), ("base_u8", C.c_int), ("ldb", C.c_int), ("on_device", C.c_int)]
 
 
+class IndexKnnInfo(C.Structure):
+    _fields_ = [("queries", C.c_int64), ("rows", C.c_int64), ("batches", C.c_int64), ("fallback_queries", C.c_int64), ("exhaustive", C.c_int64),
+                ("int_road", C.c_int64), ("norms_ms", C.c_double), ("scan_ms", C.c_double), ("select_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class IndexStats(C.Structure):
     _fields_ = [("queries", C.c_int64), ("rows", C.c_int64), ("invalid", C.c_int64), ("batches", C.c_int64),
                 ("scan_ms", C.c_double), ("gather_ms", C.c_double), ("select_ms", C.c_double)]
@@ -138,6 +146,9 @@ SIGNATURES = {
     "lsq_index_search": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "lsq_index_rerank": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "lsq_index_get_stats": (_i, [_vp, C.POINTER(IndexStats)]),
+    "lsq_index_knn": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    "lsq_index_get_knn_info": (_i, [_vp, C.POINTER(IndexKnnInfo)]),
+    "lsq_knn_exact_u8_cpu": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i]),
     "lsq_quantize_norms": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "lsq_quantize_norms_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "lsq_update_codebooks": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _vp]),

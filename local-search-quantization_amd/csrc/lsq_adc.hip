@@ -478,7 +478,7 @@ template <int QT, int MODE>
 int launch_producer(hipStream_t s, const float *LUT, const lsq_search_input &in, const int *qsel, int q0, int nqb, int stride, int ns,
                     const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits) {
     if (in.kind == LSQ_SEARCH_EXACT)
-        return lsq_knn_launch_scan(s, MODE, in.base, in.bstride, in.Q, in.qstride, qsel, q0, nqb, in.n, in.d, stride, ns, tau, count, cap, out, idbits);
+        return lsq_knn_launch_scan(s, MODE, in, qsel, q0, nqb, stride, ns, tau, count, cap, out, idbits);
     return launch_scan<QT, MODE>(s, LUT, in, nqb, stride, ns, tau, count, cap, out, idbits);
 }
 
@@ -490,12 +490,12 @@ int launch_lut(hipStream_t s, const lsq_search_input &in, const int *qsel, int q
     const size_t lds = sizeof(float) * (size_t)QT * kc;
     if (in.kind == LSQ_SEARCH_PQ) {
         LSQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&adc_pq_lut_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((adc_pq_lut_kernel<QT>), dim3((unsigned)in.m, (unsigned)tiles), dim3(LSQ_H), lds, s, in.Q, in.K, qsel, q0, nqb, in.qstride,
-                           d, entries, LUT);
+        hipLaunchKernelGGL((adc_pq_lut_kernel<QT>), dim3((unsigned)in.m, (unsigned)tiles), dim3(LSQ_H), lds, s, static_cast<const float *>(in.Q), in.K, qsel, q0, nqb,
+                           in.qstride, d, entries, LUT);
     } else {
         LSQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&adc_lut_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((adc_lut_kernel<QT>), dim3((unsigned)((entries + 255) / 256), (unsigned)tiles), dim3(256), lds, s, in.Q, in.K, qsel, q0,
-                           nqb, d, entries, LUT);
+        hipLaunchKernelGGL((adc_lut_kernel<QT>), dim3((unsigned)((entries + 255) / 256), (unsigned)tiles), dim3(256), lds, s, static_cast<const float *>(in.Q), in.K,
+                           qsel, q0, nqb, d, entries, LUT);
     }
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
@@ -674,8 +674,8 @@ int lsq_adc_search_host(hipStream_t s, lsq_adc_state **pst, float *dists, int *i
     lsq_adc_state *st = *pst;
     const bool exact = host.kind == LSQ_SEARCH_EXACT;
     const size_t n = (size_t)host.n, m = (size_t)host.m, d = (size_t)host.d;
-    const size_t db_bytes = exact ? sizeof(float) * ((n - 1) * (size_t)host.bstride + d) : (n - 1) * (size_t)host.cstride + m;
-    const size_t q_bytes = sizeof(float) * ((size_t)(nq - 1) * (size_t)host.qstride + (size_t)host.query_width());
+    const size_t db_bytes = exact ? host.base_elem() * ((n - 1) * (size_t)host.bstride + d) : (n - 1) * (size_t)host.cstride + m;
+    const size_t q_bytes = host.query_elem() * ((size_t)(nq - 1) * (size_t)host.qstride + (size_t)host.query_width());
     const size_t table_bytes = exact ? 0 : sizeof(float) * m * LSQ_H * d, out_items = (size_t)nq * (size_t)nn;
     lsq_search_input in = host;
     LSQ_TRY(st->h_db.ensure(db_bytes + (exact ? 0 : 16)));      // code rows: 16 bytes of slack past the last one, allocated and never uploaded
@@ -684,9 +684,9 @@ int lsq_adc_search_host(hipStream_t s, lsq_adc_state **pst, float *dists, int *i
     LSQ_TRY(st->h_idx.ensure(sizeof(int) * out_items));
     LSQ_HIP(hipMemcpyAsync(st->h_db.p, exact ? (const void *)host.base : (const void *)host.codes, db_bytes, hipMemcpyHostToDevice, s));
     LSQ_HIP(hipMemcpyAsync(st->h_q.p, host.Q, q_bytes, hipMemcpyHostToDevice, s));
-    if (exact) in.base = st->h_db.as<float>();
+    if (exact) in.base = st->h_db.p;
     else in.codes = st->h_db.as<uint8_t>();
-    in.Q = st->h_q.as<float>();
+    in.Q = st->h_q.p;
     if (!exact) {
         LSQ_TRY(st->h_tables.ensure(table_bytes));
         LSQ_HIP(hipMemcpyAsync(st->h_tables.p, host.K, table_bytes, hipMemcpyHostToDevice, s));

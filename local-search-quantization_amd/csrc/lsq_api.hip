@@ -108,6 +108,7 @@ struct lsq_ctx {
     lsq_adc_state *adc = nullptr;                      // device ADC scan (lsq_adc.hip): buffers, created on first use
     lsq_linscan_stats adc_stats{};
     lsq_search_opts search;                            // options "linscan_exhaustive", "linscan_rank": test hooks of the scan's selection (search_opts fills in the rest per call)
+    int knn_u8_int = 1;                                // option "knn_u8_int": 0 = lsq_index_knn widens 8-bit rows and queries even where the integer road applies; a test hook
     int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
     DevBuf sX, sX2, sK, sB16, sOut16, sTight, sF32;    // staging for the host-buffer entry points (sX/sX2: double-buffered X chunks)
     DevBuf sSample, sSigmaS;                           // host-buffer pipeline: the level sample (compacted rows of X) and its sigma
@@ -298,6 +299,7 @@ extern "C" int lsq_set_option(lsq_ctx *c, const char *key, int64_t value) {
         if (value < 0) { lsq_set_error("linscan_rank must be >= 0"); return LSQ_EINVAL; }
         c->search.rank_override = (int)value;
     }
+    else if (!strcmp(key, "knn_u8_int")) c->knn_u8_int = value != 0;
     else if (!strcmp(key, "rerank_batch")) {
         if (value < 0) { lsq_set_error("rerank_batch must be >= 0"); return LSQ_EINVAL; }
         c->rerank_batch = value;
@@ -432,13 +434,19 @@ static lsq_search_opts search_opts(const lsq_ctx *c, lsq_linscan_stats *stats) {
 
 // the three kinds of search (lsq_search_input); the pointers are all device pointers or all host pointers
 static lsq_search_input lsq_input(const uint8_t *codes, const float *Q, const float *K, const float *dbnorms, int n, int m, int d) {
-    return {LSQ_SEARCH_LSQ, codes, m, Q, d, K, dbnorms, n, m, d, nullptr, 0};
+    lsq_search_input in{};
+    in.kind = LSQ_SEARCH_LSQ; in.codes = codes; in.cstride = m; in.Q = Q; in.qstride = d; in.K = K; in.dbnorms = dbnorms; in.n = n; in.m = m; in.d = d;
+    return in;
 }
 static lsq_search_input pq_input(const uint8_t *codes, int cstride, const float *centers, const float *Q, int qstride, int n, int m, int subdim) {
-    return {LSQ_SEARCH_PQ, codes, cstride, Q, qstride, centers, nullptr, n, m, subdim, nullptr, 0};
+    lsq_search_input in{};
+    in.kind = LSQ_SEARCH_PQ; in.codes = codes; in.cstride = cstride; in.Q = Q; in.qstride = qstride; in.K = centers; in.n = n; in.m = m; in.d = subdim;
+    return in;
 }
-static lsq_search_input exact_input(const float *base, int ldb, const float *Q, int ldq, int n, int d) {
-    return {LSQ_SEARCH_EXACT, nullptr, 0, Q, ldq, nullptr, nullptr, n, 0, d, base, ldb};
+static lsq_search_input exact_input(const void *base, int base_u8, int ldb, const void *Q, int q_u8, int ldq, int n, int d) {
+    lsq_search_input in{};
+    in.kind = LSQ_SEARCH_EXACT; in.Q = Q; in.qstride = ldq; in.n = n; in.d = d; in.base = base; in.bstride = ldb; in.base_u8 = base_u8; in.q_u8 = q_u8;
+    return in;
 }
 
 extern "C" int lsq_linscan_dev(lsq_ctx *c, float *d_dists, int *d_idx, const uint8_t *d_codes, const float *d_queries, const float *d_codebooks,
@@ -496,7 +504,7 @@ extern "C" int lsq_knn_exact_dev(lsq_ctx *c, float *d_dists, uint32_t *d_ids, co
     if (!c) { lsq_set_error("lsq_knn_exact_dev: null context"); return LSQ_EINVAL; }
     LSQ_TRY(lsq_knn_exact_check("lsq_knn_exact_dev", d_dists, d_ids, d_base, d_queries, n, nq, d, ldb, ldq, nn));
     LSQ_TRY(use_device(c));
-    return lsq_adc_search(c->stream, &c->adc, d_dists, reinterpret_cast<int *>(d_ids), exact_input(d_base, ldb, d_queries, ldq, n, d), nq, nn,
+    return lsq_adc_search(c->stream, &c->adc, d_dists, reinterpret_cast<int *>(d_ids), exact_input(d_base, 0, ldb, d_queries, 0, ldq, n, d), nq, nn,
                           search_opts(c, &c->adc_stats));
 }
 
@@ -505,7 +513,7 @@ extern "C" int lsq_knn_exact(lsq_ctx *c, float *dists, uint32_t *ids, const floa
     if (!c) { lsq_set_error("lsq_knn_exact: null context"); return LSQ_EINVAL; }
     LSQ_TRY(lsq_knn_exact_check("lsq_knn_exact", dists, ids, base, queries, n, nq, d, ldb, ldq, nn));
     LSQ_TRY(use_device(c));
-    return lsq_adc_search_host(c->stream, &c->adc, dists, reinterpret_cast<int *>(ids), exact_input(base, ldb, queries, ldq, n, d), nq, nn,
+    return lsq_adc_search_host(c->stream, &c->adc, dists, reinterpret_cast<int *>(ids), exact_input(base, 0, ldb, queries, 0, ldq, n, d), nq, nn,
                                search_opts(c, &c->adc_stats));
 }
 
@@ -529,8 +537,10 @@ struct lsq_index {
     DevBuf rec_a, rec_b, seg, counter;                 // stage two: records, sorted records, segment bounds, the invalid-id counter
     DevBuf short_d, short_i;                           // stage one's shortlist [nq][L]
     DevBuf s_qscan, s_qexact, s_cand, s_dists, s_ids;  // staging of host-buffer calls, and of scan queries whose rows are not d floats apart
+    DevBuf nrm_x, nrm_q;                               // lsq_index_knn's integer road: uint32 squared norms of the rows and of the queries, refilled at every call
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     lsq_index_stats stats{};
+    lsq_index_knn_info knn{};
 };
 
 extern "C" int lsq_index_destroy(lsq_index *ix) {
@@ -538,7 +548,7 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     (void)hipSetDevice(ix->ctx->device);
     (void)hipStreamSynchronize(ix->ctx->stream);
     DevBuf *bufs[] = {&ix->own_codes, &ix->own_K, &ix->own_norms, &ix->own_base, &ix->rec_a, &ix->rec_b, &ix->seg, &ix->counter, &ix->short_d, &ix->short_i,
-                      &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids};
+                      &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q};
     for (DevBuf *b : bufs) b->release();
     lsq_adc_free(ix->adc);
     for (hipEvent_t e : ix->ev) if (e) (void)hipEventDestroy(e);
@@ -737,6 +747,80 @@ extern "C" int lsq_index_search(lsq_index *ix, float *dists, int *ids, const flo
         LSQ_HIP(hipStreamSynchronize(s));
     }
     ix->stats.queries += nq;
+    return LSQ_OK;
+}
+
+// exact k-NN over the resident base rows: lsq_knn_exact_dev's search (lsq_adc_search on the "exact" input) with the index's own scan state
+extern "C" int lsq_index_knn(lsq_index *ix, float *dists, int *ids, const void *queries, int queries_u8, int nq, int ldq, int nn, int id_base,
+                             int on_device) {
+    if (!ix) { lsq_set_error("lsq_index_knn: null index"); return LSQ_EINVAL; }
+    if (!ix->base) { lsq_set_error("lsq_index_knn: the index holds no base rows"); return LSQ_EINVAL; }
+    if (!dists || !ids || !queries) { lsq_set_error("lsq_index_knn: null pointer"); return LSQ_EINVAL; }
+    if (nq < 1 || ldq < ix->d) { lsq_set_error("lsq_index_knn: needs nq >= 1 and ldq >= d (got nq=%d ldq=%d d=%d)", nq, ldq, ix->d); return LSQ_EINVAL; }
+    if (nn < 1 || nn > ix->n) { lsq_set_error("lsq_index_knn: needs 1 <= nn <= n (got nn=%d n=%lld)", nn, (long long)ix->n); return LSQ_EINVAL; }
+    if (id_base != 0 && id_base != 1) { lsq_set_error("lsq_index_knn: id_base must be 0 or 1 (got %d)", id_base); return LSQ_EINVAL; }
+    const int q_u8 = queries_u8 != 0;
+    if (!q_u8 && ((uintptr_t)queries & 3) != 0) { lsq_set_error("lsq_index_knn: the f32 queries are not 4-byte aligned"); return LSQ_EINVAL; }
+    if (ix->ldb > (int64_t)INT32_MAX) { lsq_set_error("lsq_index_knn: needs ldb <= 2^31 - 1"); return LSQ_EINVAL; }
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    const int n = (int)ix->n, d = ix->d;
+    const size_t qe = q_u8 ? 1 : sizeof(float), out_items = (size_t)nq * (size_t)nn;
+    const void *dq = queries;
+    float *out_d = dists;
+    int *out_i = ids;
+    if (!on_device) {                                 // query rows up to the d-th element of the last one, as they lie
+        const size_t q_bytes = qe * ((size_t)(nq - 1) * (size_t)ldq + (size_t)d);
+        LSQ_TRY(ix->s_qexact.ensure(q_bytes));
+        LSQ_TRY(ix->s_dists.ensure(sizeof(float) * out_items));
+        LSQ_TRY(ix->s_ids.ensure(sizeof(int) * out_items));
+        LSQ_HIP(hipMemcpyAsync(ix->s_qexact.p, queries, q_bytes, hipMemcpyHostToDevice, s));
+        dq = ix->s_qexact.p;
+        out_d = ix->s_dists.as<float>();
+        out_i = ix->s_ids.as<int>();
+    }
+    lsq_search_input in = exact_input(ix->base, ix->base_u8, (int)ix->ldb, dq, q_u8, ldq, n, d);
+    in.id_base = id_base;
+    const bool int_road = ix->base_u8 && q_u8 && d <= 258 && c->knn_u8_int;      // d 255^2 <= 2^24: (float)D is the chain's result
+    lsq_index_knn_info info{};
+    if (int_road) {
+        // nothing is cached across calls: a borrowed base may have changed since the last one
+        const bool timed = c->profile != 0;
+        if (timed) for (hipEvent_t &e : ix->ev) if (!e) LSQ_HIP(hipEventCreate(&e));
+        LSQ_TRY(ix->nrm_x.ensure(sizeof(uint32_t) * (size_t)n));
+        LSQ_TRY(ix->nrm_q.ensure(sizeof(uint32_t) * (size_t)nq));
+        if (timed) LSQ_HIP(hipEventRecord(ix->ev[0], s));
+        LSQ_TRY(lsq_knn_launch_norms_u8(s, static_cast<const uint8_t *>(ix->base), ix->ldb, n, d, ix->nrm_x.as<uint32_t>()));
+        LSQ_TRY(lsq_knn_launch_norms_u8(s, static_cast<const uint8_t *>(dq), ldq, nq, d, ix->nrm_q.as<uint32_t>()));
+        if (timed) {
+            LSQ_HIP(hipEventRecord(ix->ev[1], s));
+            LSQ_HIP(hipEventSynchronize(ix->ev[1]));
+            float ms = 0;
+            LSQ_HIP(hipEventElapsedTime(&ms, ix->ev[0], ix->ev[1]));
+            info.norms_ms = ms;
+        }
+        in.xnorms = ix->nrm_x.as<uint32_t>();
+        in.qnorms = ix->nrm_q.as<uint32_t>();
+    }
+    lsq_linscan_stats st{};
+    LSQ_TRY(lsq_adc_search(s, &ix->adc, out_d, out_i, in, nq, nn, search_opts(c, &st)));
+    if (!on_device) {
+        LSQ_HIP(hipMemcpyAsync(dists, out_d, sizeof(float) * out_items, hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipMemcpyAsync(ids, out_i, sizeof(int) * out_items, hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipStreamSynchronize(s));
+    }
+    info.queries = nq; info.rows = n; info.batches = st.batches; info.fallback_queries = st.fallback_queries; info.exhaustive = st.exhaustive;
+    info.int_road = int_road ? 1 : 0;
+    info.scan_ms = st.sample_ms + st.scan_ms; info.select_ms = st.select_ms;
+    ix->knn = info;
+    ix->stats.queries += nq;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_knn_info(lsq_index *ix, lsq_index_knn_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_knn_info: null argument"); return LSQ_EINVAL; }
+    *out = ix->knn;
     return LSQ_OK;
 }
 

@@ -280,18 +280,25 @@ struct lsq_adc_state;      // buffers of the scan, owned by the context
 void lsq_adc_free(lsq_adc_state *st);
 // What one call searches.  LSQ: K = [m h][d] codebooks, tables -2<q, c>, + dbnorms[i], 1-based ids out.  PQ / OPQ: K = [m][h][d] sub-space centres
 // (d = subdim), squared-distance tables, no norm term, 0-based ids out.  Exact k-NN: no codes, no tables; lsq_knn.hip computes the squared distances to
-// the float rows base[i * bstride ..] for the same selection, 0-based ids out.
+// the rows base[i * bstride ..] for the same selection, ids out in id_base (0 unless the caller says otherwise).  What the rows and the queries of an
+// exact search are made of is said HERE and nowhere else: f32, or the un-widened bytes of a .bvecs set (base_u8 / q_u8; strides in elements).  xnorms
+// [n] / qnorms [queries] (uint32 squared norms, lsq_knn_launch_norms_u8) select the integer road: set only for uint8 x uint8 with d <= 258.
 enum lsq_search_kind { LSQ_SEARCH_LSQ, LSQ_SEARCH_PQ, LSQ_SEARCH_EXACT };
 struct lsq_search_input {
     lsq_search_kind kind;
     const uint8_t *codes; int cstride;       // [n][cstride] u8 0-based, the first m bytes of a row used
-    const float *Q; int qstride;             // query rows, qstride floats apart
+    const void *Q; int qstride;              // query rows, qstride elements apart (f32 for the table scans)
     const float *K;
     const float *dbnorms;
     int n, m, d;
-    const float *base; int bstride;          // exact: [n][bstride] f32, the first d floats of a row used
-    int query_width() const { return kind == LSQ_SEARCH_PQ ? m * d : d; }      // floats of a query row that are read
-    int id_sub() const { return kind == LSQ_SEARCH_LSQ ? 0 : 1; }              // ids leave as (the record's id field 1 .. n) - id_sub
+    const void *base; int bstride;           // exact: [n][bstride], the first d elements of a row used
+    int base_u8 = 0, q_u8 = 0;               // exact: element types of base / Q (0: f32, 1: uint8)
+    const uint32_t *xnorms = nullptr, *qnorms = nullptr;
+    int id_base = 0;                         // exact: ids leave as row + id_base
+    int query_width() const { return kind == LSQ_SEARCH_PQ ? m * d : d; }      // elements of a query row that are read
+    int id_sub() const { return kind == LSQ_SEARCH_LSQ ? 0 : 1 - id_base; }    // ids leave as (the record's id field 1 .. n) - id_sub
+    size_t base_elem() const { return base_u8 ? 1 : sizeof(float); }
+    size_t query_elem() const { return q_u8 ? 1 : sizeof(float); }
 };
 // how a call searches: the test hooks of the selection (options "linscan_exhaustive", "linscan_rank"), where its statistics go, and whether its
 // phases are timed (then stats is not null)
@@ -303,9 +310,11 @@ struct lsq_search_opts {
 // every pointer of `in` a device pointer / a host pointer (staged: upload, search, download); dists, idx [nq][nn] likewise
 int lsq_adc_search(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const lsq_search_input &in, int nq, int nn, const lsq_search_opts &opt);
 int lsq_adc_search_host(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const lsq_search_input &in, int nq, int nn, const lsq_search_opts &opt);
-// the exact scan of one batch in adc_scan_kernel's three modes (0: against tau, 1: every record, 2: sample keys); qsel optional
-int lsq_knn_launch_scan(hipStream_t s, int mode, const float *X, int ldb, const float *Q, int ldq, const int *qsel, int q0, int nqb, int n, int d,
-                        int stride, int ns, const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits);
+// the exact scan of one batch in adc_scan_kernel's three modes (0: against tau, 1: every record, 2: sample keys); qsel optional.  Routes on in's element
+// types and norms (lsq_knn.hip)
+int lsq_knn_launch_scan(hipStream_t s, int mode, const lsq_search_input &in, const int *qsel, int q0, int nqb, int stride, int ns, const uint32_t *tau,
+                        unsigned *count, int cap, uint64_t *out, int idbits);
+int lsq_knn_launch_norms_u8(hipStream_t s, const uint8_t *X, int64_t ld, int n, int d, uint32_t *out);
 // argument checks of exact k-NN (lsq_linscan.hip), shared by the host drop-in and the device search
 int lsq_knn_exact_check(const char *fn, const void *dists, const void *ids, const void *base, const void *queries, int n, int nq, int d, int ldb,
                         int ldq, int nn);

@@ -270,3 +270,66 @@ extern "C" int lsq_knn_exact_cpu(float *dists, uint32_t *ids, const float *base,
     for (auto &th : pool) th.join();
     return LSQ_OK;
 }
+
+// ---- the same for rows and queries that are f32 or uint8 at any byte alignment: elements are read one at a time (memcpy for f32), uint8 widened, and
+// the f32 chain above runs on them -- the contract for EVERY d; the device's integer road (lsq_knn.hip) is held to these bits, not the other way round.
+namespace {
+
+inline float knn_elem(const uint8_t *p, bool u8, int64_t i) {
+    if (u8) return (float)p[i];
+    float v;
+    memcpy(&v, p + 4 * i, 4);
+    return v;
+}
+
+void knn_queries_any(float *dists, uint32_t *ids, const uint8_t *base, bool base_u8, const uint8_t *queries, bool q_u8, int q0, int q1, int n, int d,
+                     int ldb, int ldq, int nn) {
+    std::vector<uint64_t> heap;
+    heap.reserve((size_t)nn + 1);
+    std::vector<float> q((size_t)d), x((size_t)d);
+    for (int qi = q0; qi < q1; ++qi) {
+        for (int s = 0; s < d; ++s) q[(size_t)s] = knn_elem(queries, q_u8, (int64_t)qi * ldq + s);
+        heap.clear();
+        for (int i = 0; i < n; ++i) {
+            for (int s = 0; s < d; ++s) x[(size_t)s] = knn_elem(base, base_u8, (int64_t)i * ldb + s);
+            float acc = 0.0f;
+            for (int s = 0; s < d; ++s) {
+                const float e = x[(size_t)s] - q[(size_t)s];
+                acc += e * e;                                           // product rounded, then the add (-ffp-contract=off)
+            }
+            const uint64_t cand = pq_key(acc, (uint32_t)i);
+            if ((int)heap.size() < nn) {
+                heap.push_back(cand);
+                std::push_heap(heap.begin(), heap.end());
+            } else if (cand < heap.front()) {
+                std::pop_heap(heap.begin(), heap.end());
+                heap.back() = cand;
+                std::push_heap(heap.begin(), heap.end());
+            }
+        }
+        std::sort_heap(heap.begin(), heap.end());
+        for (int j = 0; j < nn; ++j) {
+            dists[(size_t)qi * nn + j] = pq_unkey(heap[(size_t)j]);
+            ids[(size_t)qi * nn + j] = (uint32_t)heap[(size_t)j];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int lsq_knn_exact_u8_cpu(float *dists, uint32_t *ids, const void *base, int base_u8, const void *queries, int queries_u8, int n, int nq, int d,
+                                    int ldb, int ldq, int nn, int nthreads) {
+    LSQ_TRY(lsq_knn_exact_check("lsq_knn_exact_u8_cpu", dists, ids, base, queries, n, nq, d, ldb, ldq, nn));
+    int nt = nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency();
+    if (nt < 1) nt = 1;
+    if (nt > nq) nt = nq;
+    std::vector<std::thread> pool;
+    pool.reserve((size_t)nt);
+    for (int t = 0; t < nt; ++t) {
+        const int q0 = (int)((int64_t)nq * t / nt), q1 = (int)((int64_t)nq * (t + 1) / nt);
+        pool.emplace_back(knn_queries_any, dists, ids, static_cast<const uint8_t *>(base), base_u8 != 0, static_cast<const uint8_t *>(queries),
+                          queries_u8 != 0, q0, q1, n, d, ldb, ldq, nn);
+    }
+    for (auto &th : pool) th.join();
+    return LSQ_OK;
+}

@@ -36,6 +36,10 @@ def _x_host(X):
     return _np(X, np.float32), False
 
 
+def _is_u8(a):
+    return str(getattr(a, "dtype", "")).replace("torch.", "") == "uint8"
+
+
 class Engine:
     def __init__(self, device=0, chunk=None, profile=False, schedule=None, skip=None, tuning=False):
         """tuning=True loads liblsq_mi355x_tuning.so (same ABI + option "ablation", environment knobs, clock stamps)."""
@@ -268,8 +272,15 @@ class Engine:
         return dists, ids
 
     def knn_exact(self, Xb, Xq, k):
-        """Exact k-NN (the ground truth of a recall figure).  Xb (n, d) base rows, Xq (nq, d) queries: host arrays.
-        -> dists (nq,k) float32 ascending, ids (nq,k) uint32 0-BASED; ties by smaller id, NaN last   [lsq_knn_exact]"""
+        """Exact k-NN (the ground truth of a recall figure).  Xb (n, d) base rows, Xq (nq, d) queries: host arrays, float32 -- or a uint8 base (the
+        un-widened rows of a .bvecs set) with uint8 or float queries, which goes through a temporary base-only Index and is never widened.
+        -> dists (nq,k) float32 ascending, ids (nq,k) uint32 0-BASED; ties by smaller id, NaN last   [lsq_knn_exact / lsq_index_knn]"""
+        if _is_u8(Xb):
+            if Xb.ndim != 2 or Xq.ndim != 2 or Xb.shape[1] != Xq.shape[1]:
+                raise ValueError("shape mismatch: base %s queries %s" % (tuple(Xb.shape), tuple(Xq.shape)))
+            with self.index(None, None, None, 0, base=Xb) as ix:
+                dists, ids = ix.knn(Xq, k)
+            return dists, ids.view(np.uint32)
         Xb, Xq = _np(Xb, np.float32), _np(Xq, np.float32)
         if Xb.ndim != 2 or Xq.ndim != 2 or Xb.shape[1] != Xq.shape[1]:
             raise ValueError("shape mismatch: base %s queries %s" % (Xb.shape, Xq.shape))
@@ -280,9 +291,15 @@ class Engine:
         return dists, ids
 
     def knn_exact_dev(self, dXb, dXq, k):
-        """The same on device-resident f32 torch tensors (n, d) / (nq, d); row views with unit column stride are read in place.
-        -> (dists (nq,k) f32, ids (nq,k) 0-based) tensors; the ids tensor is int32 holding the uint32 bits   [lsq_knn_exact_dev]"""
+        """The same on device-resident torch tensors (n, d) / (nq, d), f32 -- or a uint8 base with uint8 or f32 queries (a temporary Index that borrows
+        the base); row views with unit column stride are read in place.
+        -> (dists (nq,k) f32, ids (nq,k) 0-based) tensors; the ids tensor is int32 holding the uint32 bits   [lsq_knn_exact_dev / lsq_index_knn]"""
         import torch
+        if dXb.dtype == torch.uint8:
+            if dXb.dim() != 2 or dXq.dim() != 2 or dXb.shape[1] != dXq.shape[1]:
+                raise ValueError("shape mismatch: base %s queries %s" % (tuple(dXb.shape), tuple(dXq.shape)))
+            with self.index_dev(None, None, None, 0, base=dXb) as ix:
+                return ix.knn(dXq, k)
         assert dXb.is_cuda and dXq.is_cuda and dXb.dtype == torch.float32 and dXq.dtype == torch.float32, "device f32 tensors required"
         if dXb.dim() != 2 or dXq.dim() != 2 or dXb.shape[1] != dXq.shape[1]:
             raise ValueError("shape mismatch: base %s queries %s" % (tuple(dXb.shape), tuple(dXq.shape)))
@@ -784,6 +801,36 @@ class Index:
         with self._stream():
             self._eng._check(self._L.lsq_index_rerank(self._h, pd, pi, pq, pc, nq, self.d, int(L), int(k), int(id_base), int(self._dev)))
         return dists, ids
+
+    def knn(self, Q, k, id_base=0):
+        """Exact k-NN over the resident base rows (f32, or uint8 never widened): the ground truth of a recall figure.  Q (nq,>=d) float32 or uint8 rows
+        with unit column stride, any row pitch and byte offset (numpy on an Engine.index, torch on an Engine.index_dev); the first d columns are read.
+        -> dists (nq,k) float32 ascending with lsq_knn_exact's bits, ids (nq,k) int32 in id_base; ties by smaller id   [lsq_index_knn]"""
+        u8 = _is_u8(Q)
+        if self._dev:
+            import torch
+            assert Q.is_cuda and Q.dtype in (torch.float32, torch.uint8) and Q.dim() == 2 and Q.stride(1) == 1, "device f32 / uint8 query rows required"
+            ldq, pq = (Q.stride(0) if Q.shape[0] > 1 else Q.shape[1]), Q.data_ptr()
+        else:
+            Q = np.asarray(Q)
+            if Q.dtype != np.uint8:
+                Q = np.asarray(Q, dtype=np.float32)
+            if Q.ndim != 2 or Q.strides[1] != Q.itemsize or Q.strides[0] % Q.itemsize or (Q.shape[0] > 1 and Q.strides[0] < Q.shape[1] * Q.itemsize):
+                Q = np.ascontiguousarray(Q)
+            ldq, pq = (Q.strides[0] // Q.itemsize if Q.shape[0] > 1 else Q.shape[1]), Q.ctypes.data
+        if Q.ndim != 2 or Q.shape[1] < self.d:
+            raise ValueError("shape mismatch: Q %s d=%d" % (tuple(Q.shape), self.d))
+        nq = Q.shape[0]
+        dists, ids, pd, pi = self._outputs(nq, int(k), Q)
+        with self._stream():
+            self._eng._check(self._L.lsq_index_knn(self._h, pd, pi, pq, int(u8), nq, int(ldq), int(k), int(id_base), int(self._dev)))
+        return dists, ids
+
+    def knn_info(self):
+        """what the last knn call did: queries, rows, batches, fallback_queries, exhaustive, int_road, norms_ms / scan_ms / select_ms (with profile=True)"""
+        st = _lib.IndexKnnInfo()
+        self._eng._check(self._L.lsq_index_get_knn_info(self._h, C.byref(st)))
+        return st.as_dict()
 
     def stats(self):
         st = _lib.IndexStats()

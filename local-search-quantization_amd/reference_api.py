@@ -176,21 +176,29 @@ def linscan_opq(B, X, C, b, R, k=10000, *, engine=None):
 
 def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0):
     """Exact k-NN, the ground truth of a recall figure (what the reference reads from sift_groundtruth.ivecs, for any base).
-    X_base (d, n), X_query (d, nq) Float32 in Julia shapes.  -> dists (k, nq) float32 ascending, ids (k, nq) uint32 1-BASED, so that
-    eval_recall(ids[0, :], idx, knn) works directly.  dist = ((0 + e_0^2) + e_1^2) + ..., e_s = x[s] - q[s] in f32; ties by smaller id, NaN last.
-    engine=None: the host cores (lsq_knn_exact_cpu, nthreads 0 = all); engine=<Engine>: the device (lsq_knn_exact) -- same results bit for bit."""
+    X_base (d, n), X_query (d, nq) Float32 in Julia shapes, or the UInt8 matrices of bvecs_read, which are handed through un-widened (same results as
+    after astype(float32), by contract).  -> dists (k, nq) float32 ascending, ids (k, nq) uint32 1-BASED, so that eval_recall(ids[0, :], idx, knn) works
+    directly.  dist = ((0 + e_0^2) + e_1^2) + ..., e_s = x[s] - q[s] in f32; ties by smaller id, NaN last.
+    engine=None: the host cores (lsq_knn_exact_cpu / lsq_knn_exact_u8_cpu, nthreads 0 = all); engine=<Engine>: the device -- same results bit for bit."""
     from . import _lib
-    Xb, Xq = _X_of(X_base), _X_of(X_query)
+    Xb, Xq = _base_rows(X_base), _base_rows(X_query)
     if Xb.shape[1] != Xq.shape[1]:
         raise ValueError("knn_exact: base d=%d, queries d=%d" % (Xb.shape[1], Xq.shape[1]))
+    b8, q8 = Xb.dtype == np.uint8, Xq.dtype == np.uint8
+    if q8 and not b8:
+        Xq, q8 = Xq.astype(np.float32), False
     if engine is not None:
         dists, ids = engine.knn_exact(Xb, Xq, k)
     else:
         (n, d), nq = Xb.shape, Xq.shape[0]
         dists = np.zeros((nq, k), dtype=np.float32)
         ids = np.zeros((nq, k), dtype=np.uint32)
-        _lib.check(_lib.load().lsq_knn_exact_cpu(dists.ctypes.data, ids.ctypes.data, Xb.ctypes.data, Xq.ctypes.data, n, nq, d, d, d, int(k),
-                                                 int(nthreads)))
+        if b8:
+            _lib.check(_lib.load().lsq_knn_exact_u8_cpu(dists.ctypes.data, ids.ctypes.data, Xb.ctypes.data, 1, Xq.ctypes.data, int(q8), n, nq, d, d, d,
+                                                        int(k), int(nthreads)))
+        else:
+            _lib.check(_lib.load().lsq_knn_exact_cpu(dists.ctypes.data, ids.ctypes.data, Xb.ctypes.data, Xq.ctypes.data, n, nq, d, d, d, int(k),
+                                                     int(nthreads)))
     return dists.T, ids.T + np.uint32(1)
 
 

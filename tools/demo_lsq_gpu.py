@@ -8,7 +8,8 @@ the codes and codebooks stay in HBM between the stages; the rest of the flow is 
 
 --bvecs: the base set stays 8-bit end to end -- read with bvecs_read from the first *base*.bvecs file under $LSQ_DATA_DIR (SIFT1B layout: learn, base and
 query .bvecs files and an .ivecs ground truth side by side), else the synthetic stand-in quantised to bytes -- and is handed to encode_icm_cuda as
-uint8 (lsq_encode_icm_u8: d bytes per vector over the bus and in HBM).  Training set and queries are widened: the trainers, k-NN and the scan take f32.
+uint8 (lsq_encode_icm_u8: d bytes per vector over the bus and in HBM).  The ground truth is exact k-NN of the 8-bit queries over the un-widened 8-bit base
+(lsq_index_knn: integer distances, the f32 chain's bits).  Training set and scan queries are widened: the trainers and the scan take f32.
 
 --rerank L: after the ADC scan, the two-stage search on a resident index (Engine.index: the codes, norms, codebooks and the base rows uploaded once):
 the scan's L nearest re-ordered by exact distance to the stored vectors -- f32 rows, or the un-widened 8-bit rows with --bvecs -- and the recall curve of the
@@ -32,11 +33,12 @@ lsq = importlib.import_module("local-search-quantization_amd")
 
 
 def ground_truth(xb, xq):
-    """1-based id of each query's nearest base vector: exact k-NN on the device (lsq_knn_exact)"""
+    """1-based id of each query's nearest base vector: exact k-NN on the device (lsq_knn_exact; uint8 matrices stay uint8: lsq_index_knn)"""
     t0 = time.perf_counter()
     with lsq.Engine(0) as eng:
         _, ids = lsq.knn_exact(xb, xq, 1, engine=eng)
-    print("Ground truth of %d queries in %d base vectors: %.3f s (exact k-NN on the device)" % (xq.shape[1], xb.shape[1], time.perf_counter() - t0))
+    print("Ground truth of %d queries in %d base vectors: %.3f s (exact k-NN on the device, %s rows)" % (xq.shape[1], xb.shape[1], time.perf_counter() - t0,
+                                                                                                       xb.dtype))
     return ids[0]
 
 
@@ -70,7 +72,7 @@ def load_bvecs(nt, nb, nq):
         xt8, xb8, xq8 = (np.rint((x - lo) * (255.0 / (hi - lo))).astype(np.uint8) for x in (xt, xb, xq))
         name = "synthetic"
     xq = xq8.astype(np.float32)
-    return name, xt8.astype(np.float32), xb8, xq, ground_truth(xb8.astype(np.float32), xq)      # (k-NN takes f32: a widened copy for the ground truth only)
+    return name, xt8.astype(np.float32), xb8, xq, ground_truth(xb8, xq8)      # from the 8-bit base as it is: no widened copy
 
 
 def load(nt, nb, nq, want_gt=True, synthetic=False):
