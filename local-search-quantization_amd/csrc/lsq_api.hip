@@ -110,7 +110,14 @@ struct lsq_ctx {
     lsq_search_opts search;                            // options "linscan_exhaustive", "linscan_rank": test hooks of the scan's selection (search_opts fills in the rest per call)
     int knn_u8_int = 1;                                // option "knn_u8_int": 0 = lsq_index_knn widens 8-bit rows and queries even where the integer road applies; a test hook
     int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
-    DevBuf sX, sX2, sK, sB16, sOut16, sTight, sF32;    // staging for the host-buffer entry points (sX/sX2: double-buffered X chunks)
+    // Staging for the host-buffer entry points.  Who writes what (a later call may assume NOTHING of their contents, except sK under tables_valid):
+    //   sX, sX2  X: one chunk at a time, double-buffered, by the pipelined encode; the whole X by stage_X
+    //   sK       the call's codebooks: uploaded (host_codebooks; claim_sK: K, K_prev) or computed into it (claim_sK: LSQR, SPGL1, the seeding).
+    //            tables_valid says that sK, sci, T and what the filtered walk derives from them still belong to hostK
+    //   sB16     int16 1-based codes on their way up (stage_codes, the pipelined encode) or down (fetch_codes, the pipelined encode's snapshots)
+    //   sTight   tight [n][m] codes: stage_codes' for the solvers, the initialisers' result
+    //   sOut16   quantize_norms' indices;  sF32: small arrays, the slices a call carves (carve_f32) and names in that line
+    DevBuf sX, sX2, sK, sB16, sOut16, sTight, sF32;
     DevBuf sSample, sSigmaS;                           // host-buffer pipeline: the level sample (compacted rows of X) and its sigma
     std::vector<float> sample_host;                    // ... packed on the host before its upload
     std::vector<hipEvent_t> panel_ev;                  // ... one event per uploaded panel
@@ -1355,6 +1362,17 @@ extern "C" int lsq_encode_icm_u8_dev(lsq_ctx *c, const uint8_t *dX8, const uint8
     return encode_dev(c, "lsq_encode_icm_u8_dev", dX8, dB0, dK, d, n, m, h, ilsiters, nr, icmiter, npert, randord, seed, global_offset, dBs, obj_sums, stats);
 }
 
+// sK is claimed for this call -- as an input (K uploaded here, or K_prev by stage()) or as an output (LSQR, SPGL1, the seeding).  The ONE place that drops
+// the host-table cache because sK changes.  It is the first thing such a call does that can fail: from here on sK / the tables are in flux, and a failure
+// must not leave the cache claiming the OLD codebooks
+static size_t codebook_bytes(int d, int m) { return sizeof(float) * (size_t)m * LSQ_H * d; }
+static int claim_sK(lsq_ctx *c, int d, int m, const float *K = nullptr) {
+    c->tables_valid = false;        // sK is about to hold other codebooks than the cached tables were built from
+    LSQ_TRY(c->sK.ensure(codebook_bytes(d, m)));
+    if (K) LSQ_HIP(hipMemcpyAsync(c->sK.p, K, codebook_bytes(d, m), hipMemcpyHostToDevice, c->stream));
+    return LSQ_OK;
+}
+
 // The caller's host codebooks -> c->sK + tables.  Unchanged since the last host-buffer call of this context (same shape, same bytes): nothing is
 // uploaded or rebuilt.
 static int host_codebooks(lsq_ctx *c, const float *K, int d, int m) {
@@ -1363,9 +1381,7 @@ static int host_codebooks(lsq_ctx *c, const float *K, int d, int m) {
         c->table_reuses += 1;
         return LSQ_OK;
     }
-    c->tables_valid = false;        // from here on sK / the tables are in flux: a failure below must not leave the cache claiming the OLD codebooks
-    LSQ_TRY(c->sK.ensure(kbytes));
-    LSQ_HIP(hipMemcpyAsync(c->sK.p, K, kbytes, hipMemcpyHostToDevice, c->stream));
+    LSQ_TRY(claim_sK(c, d, m, K));
     LSQ_TRY(prepare_tables(c, c->sK.as<float>(), d, m));
     c->hostK.assign(K, K + count);        // (the pageable copy above has read K by the time it returns)
     c->hostK_d = d; c->hostK_m = m;
@@ -1649,33 +1665,68 @@ extern "C" int lsq_encoding_icm(lsq_ctx *c, const float *X, const int16_t *oldB,
     return rc;
 }
 
-// upload helpers for the fine-grained entry points
-static int upload_xk(lsq_ctx *c, const float *X, const float *K, int d, int64_t n, int m) {
-    const size_t kbytes = sizeof(float) * (size_t)m * LSQ_H * d;
-    c->tables_valid = false;        // sK is about to hold other codebooks than the cached tables were built from
-    LSQ_TRY(c->sK.ensure(kbytes));
-    LSQ_HIP(hipMemcpyAsync(c->sK.p, K, kbytes, hipMemcpyHostToDevice, c->stream));
-    if (X) {
-        LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)std::max<int64_t>(n, 1) * d));
-        if (n > 0) LSQ_HIP(hipMemcpyAsync(c->sX.p, X, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
-    }
+// ---- host-buffer calls (everything below that is neither the pipelined encode nor a search) ---------------------------------------------------------------
+// A host form is: checks -> stage -> its launch sequence on device pointers -> fetch -> ONE wait.  The functions up to fetch_codes() are the
+// stage / fetch / wait part (with claim_sK, next to host_codebooks); which buffer they fill is listed at lsq_ctx's staging buffers.
+
+// what an entry checks first: the context, the shape, then `ok` (its pointers and counts)
+static int entry_args(const char *fn, lsq_ctx *c, int d, int64_t n, int m, int h, bool ok, const char *what = "null pointer") {
+    LSQ_TRY(use_device(c));
+    LSQ_TRY(check_shape(fn, d, n, m, h));
+    if (!ok) { lsq_set_error("%s: %s", fn, what); return LSQ_EINVAL; }
     return LSQ_OK;
 }
 
-static int upload_codes(lsq_ctx *c, const int16_t *B, int64_t n, int m, int h, DevBuf &rec) {
+static int stage_X(lsq_ctx *c, const float *X, int d, int64_t n) {        // -> sX, sized for at least one row; no rows, no copy
+    LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)std::max<int64_t>(n, 1) * d));
+    if (n > 0) LSQ_HIP(hipMemcpyAsync(c->sX.p, X, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
+    return LSQ_OK;
+}
+
+// The caller's int16 1-based codes -> records in recCur [, and tight [n][m] in sTight], range-checked on the device.  The wait that reads the verdict is here:
+// a call with a bad code returns before any kernel of its own work is enqueued and before any output is written
+static int stage_codes(lsq_ctx *c, const int16_t *B, int64_t n, int m, int h, bool tight = false) {
     LSQ_TRY(c->sB16.ensure(sizeof(int16_t) * (size_t)std::max<int64_t>(n, 1) * m));
-    LSQ_TRY(rec.ensure((size_t)std::max<int64_t>(n, 1) * lsq_code_stride(m)));
+    LSQ_TRY(c->recCur.ensure((size_t)std::max<int64_t>(n, 1) * lsq_code_stride(m)));
     LSQ_TRY(c->bad.ensure(sizeof(int)));
     LSQ_HIP(hipMemsetAsync(c->bad.p, 0, sizeof(int), c->stream));
     if (n > 0) {
         LSQ_HIP(hipMemcpyAsync(c->sB16.p, B, sizeof(int16_t) * (size_t)n * m, hipMemcpyHostToDevice, c->stream));
-        LSQ_TRY(lsq_launch_codes_from_i16(c->stream, c->sB16.as<int16_t>(), n, m, h, rec.as<uint8_t>(), c->bad.as<int>()));
+        LSQ_TRY(lsq_launch_codes_from_i16(c->stream, c->sB16.as<int16_t>(), n, m, h, c->recCur.as<uint8_t>(), c->bad.as<int>()));
     }
     int bad = 0;
     LSQ_HIP(hipMemcpyAsync(&bad, c->bad.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     LSQ_HIP(hipStreamSynchronize(c->stream));
     if (bad) { lsq_set_error("input codes must lie in 1..%d", h); return LSQ_ECODE; }
+    if (tight) LSQ_TRY(c->sTight.ensure((size_t)std::max<int64_t>(n, 1) * m));
+    if (tight && n > 0) LSQ_TRY(lsq_launch_codes_compact(c->stream, c->recCur.as<uint8_t>(), n, m, c->sTight.as<uint8_t>()));
     return LSQ_OK;
+}
+
+// sF32 is a call's block of small arrays: the slices the call names, in the order given, each on a 16-byte boundary.  A call carves ONCE (a second carve may
+// move the block) and says in that line what its slices hold
+struct Slice { size_t bytes; void *p = nullptr; template <class T> T *as() const { return static_cast<T *>(p); } };
+static int carve_f32(lsq_ctx *c, std::initializer_list<Slice *> slices) {
+    size_t total = 0;
+    for (Slice *s : slices) total += (s->bytes + 15) & ~(size_t)15;
+    LSQ_TRY(c->sF32.ensure(total));
+    char *p = c->sF32.as<char>();
+    for (Slice *s : slices) { s->p = p; p += (s->bytes + 15) & ~(size_t)15; }
+    return LSQ_OK;
+}
+
+// a small array up (into a slice, or K_prev into the claimed sK); a result down -- a null dst is an output the caller did not ask for; the call's one trailing wait
+static int stage(lsq_ctx *c, void *dst, const void *src, size_t bytes) { LSQ_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream)); return LSQ_OK; }
+static int fetch(lsq_ctx *c, void *dst, const void *src, size_t bytes) { if (dst) LSQ_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream)); return LSQ_OK; }
+static int finish(lsq_ctx *c) { LSQ_HIP(hipStreamSynchronize(c->stream)); return LSQ_OK; }
+
+// the records in recNew (from_tight: sTight's [n][m], expanded into recNew first) -> int16 1-based in sB16 -> the caller's B
+static int fetch_codes(lsq_ctx *c, int16_t *B, int64_t n, int m, bool from_tight = false) {
+    LSQ_TRY(c->sB16.ensure(sizeof(int16_t) * (size_t)n * m));
+    if (from_tight) LSQ_TRY(c->recNew.ensure((size_t)n * lsq_code_stride(m)));
+    if (from_tight) LSQ_TRY(lsq_launch_codes_expand(c->stream, c->sTight.as<uint8_t>(), n, m, c->recNew.as<uint8_t>()));
+    LSQ_TRY(lsq_launch_codes_to_i16(c->stream, c->recNew.as<uint8_t>(), n, m, c->sB16.as<int16_t>()));
+    return fetch(c, B, c->sB16.p, sizeof(int16_t) * (size_t)n * m);
 }
 
 extern "C" int lsq_encode_icm_fully(lsq_ctx *c, int16_t *B, const float *X, const float *K, int d, int64_t n, int m, int h, int niter,
@@ -1688,8 +1739,9 @@ extern "C" int lsq_encode_icm_fully(lsq_ctx *c, int16_t *B, const float *X, cons
     if (autoit) it = c->auto_it;
     if (n == 0) return LSQ_OK;
     if (n > c->chunk) { lsq_set_error("lsq_encode_icm_fully: n = %lld exceeds the resident chunk (%lld); raise option \"chunk\"", (long long)n, (long long)c->chunk); return LSQ_EINVAL; }
-    LSQ_TRY(upload_xk(c, X, K, d, n, m));
-    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));
+    LSQ_TRY(claim_sK(c, d, m, K));
+    LSQ_TRY(stage_X(c, X, d, n));
+    LSQ_TRY(stage_codes(c, B, n, m, h));
     LSQ_TRY(prepare_tables(c, c->sK.as<float>(), d, m));
     c->call_row0 = 0;
     LSQ_TRY(build_unaries(c, c->sX.as<float>(), c->sK.as<float>(), d, n, m, lsq_walk_slice_width(m), 0, n));
@@ -1702,296 +1754,250 @@ extern "C" int lsq_encode_icm_fully(lsq_ctx *c, int16_t *B, const float *X, cons
     LSQ_TRY(lsq_launch_perturb(c->stream, c->recCur.as<uint8_t>(), c->recNew.as<uint8_t>(), n, m, npert, seed, it, (uint64_t)(idx_first - 1), nullptr, nullptr));
     // (no statistics: the worker has no accept step and no probe memory -- always the configured road)
     LSQ_TRY(run_sweeps(c, c->recNew.as<uint8_t>(), c->vNew.as<unsigned short>(), n, m, order, niter, nullptr));
-    LSQ_TRY(lsq_launch_codes_to_i16(c->stream, c->recNew.as<uint8_t>(), n, m, c->sB16.as<int16_t>()));
-    LSQ_HIP(hipMemcpyAsync(B, c->sB16.p, sizeof(int16_t) * (size_t)n * m, hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
+    LSQ_TRY(fetch_codes(c, B, n, m));
+    LSQ_TRY(finish(c));
     if (autoit && c->auto_it < LSQ_IT_AUTO - 1u) ++c->auto_it;
     return LSQ_OK;
 }
 
 extern "C" int lsq_get_unaries(lsq_ctx *c, const float *X, const float *K, int d, int64_t n, int m, int h, float *U) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape("lsq_get_unaries", d, n, m, h));
-    if (!K || (n > 0 && (!X || !U))) { lsq_set_error("lsq_get_unaries: null pointer"); return LSQ_EINVAL; }
+    LSQ_TRY(entry_args("lsq_get_unaries", c, d, n, m, h, K && (n == 0 || (X && U))));
     if (n == 0) return LSQ_OK;
-    LSQ_TRY(upload_xk(c, X, K, d, n, m));
+    LSQ_TRY(claim_sK(c, d, m, K));
+    LSQ_TRY(stage_X(c, X, d, n));
     LSQ_TRY(c->sci.ensure(sizeof(float) * (size_t)m * LSQ_H));
     LSQ_TRY(lsq_launch_sqnorms(c->stream, c->sK.as<float>(), m * LSQ_H, d, c->sci.as<float>()));
     LSQ_TRY(build_unaries(c, c->sX.as<float>(), c->sK.as<float>(), d, n, m, 0, 0, n));
-    LSQ_HIP(hipMemcpyAsync(U, c->U.p, sizeof(float) * (size_t)m * n * LSQ_H, hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    return LSQ_OK;
+    LSQ_TRY(fetch(c, U, c->U.p, sizeof(float) * (size_t)m * n * LSQ_H));
+    return finish(c);
 }
 
 extern "C" int lsq_get_binaries(lsq_ctx *c, const float *K, int d, int m, int h, float *T) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape("lsq_get_binaries", d, 0, m, h));
-    if (!K || !T) { lsq_set_error("lsq_get_binaries: null pointer"); return LSQ_EINVAL; }
-    LSQ_TRY(upload_xk(c, nullptr, K, d, 0, m));
+    LSQ_TRY(entry_args("lsq_get_binaries", c, d, 0, m, h, K && T));
+    LSQ_TRY(claim_sK(c, d, m, K));
     LSQ_TRY(prepare_tables(c, c->sK.as<float>(), d, m));
-    LSQ_HIP(hipMemcpyAsync(T, c->T.p, sizeof(float) * (size_t)m * m * LSQ_H * LSQ_H, hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    return LSQ_OK;
+    LSQ_TRY(fetch(c, T, c->T.p, sizeof(float) * (size_t)m * m * LSQ_H * LSQ_H));
+    return finish(c);
+}
+
+// veccost and qerror: K, X and the codes up, then the cost of the staged records -> prev[n]
+static int cost_of_staged(lsq_ctx *c, const float *X, const int16_t *B, const float *K, int d, int64_t n, int m, int h) {
+    LSQ_TRY(claim_sK(c, d, m, K));
+    LSQ_TRY(stage_X(c, X, d, n));
+    LSQ_TRY(stage_codes(c, B, n, m, h));
+    LSQ_TRY(c->prev.ensure(sizeof(float) * (size_t)n));
+    return lsq_launch_cost(c->stream, c->sX.as<float>(), c->sK.as<float>(), c->recCur.as<uint8_t>(), c->recCur.as<uint8_t>(), c->prev.as<float>(), nullptr, n, d,
+                           m, 0, nullptr, nullptr);
 }
 
 extern "C" int lsq_veccost(lsq_ctx *c, const float *X, const int16_t *B, const float *K, int d, int64_t n, int m, int h, float *cost) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape("lsq_veccost", d, n, m, h));
-    if (!K || (n > 0 && (!X || !B || !cost))) { lsq_set_error("lsq_veccost: null pointer"); return LSQ_EINVAL; }
+    LSQ_TRY(entry_args("lsq_veccost", c, d, n, m, h, K && (n == 0 || (X && B && cost))));
     if (n == 0) return LSQ_OK;
-    LSQ_TRY(upload_xk(c, X, K, d, n, m));
-    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));
-    LSQ_TRY(c->prev.ensure(sizeof(float) * (size_t)n));
-    LSQ_TRY(lsq_launch_cost(c->stream, c->sX.as<float>(), c->sK.as<float>(), c->recCur.as<uint8_t>(), c->recCur.as<uint8_t>(),
-                            c->prev.as<float>(), nullptr, n, d, m, 0, nullptr, nullptr));
-    LSQ_HIP(hipMemcpyAsync(cost, c->prev.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
+    LSQ_TRY(cost_of_staged(c, X, B, K, d, n, m, h));
+    LSQ_TRY(fetch(c, cost, c->prev.p, sizeof(float) * (size_t)n));
+    return finish(c);
+}
+
+extern "C" int lsq_qerror(lsq_ctx *c, const float *X, const int16_t *B, const float *K, int d, int64_t n, int m, int h, double *out) {
+    LSQ_TRY(entry_args("lsq_qerror", c, d, n, m, h, out && K && (n == 0 || (X && B))));
+    *out = 0.0;
+    if (n == 0) return LSQ_OK;
+    LSQ_TRY(c->obj.ensure(sizeof(double)));
+    LSQ_TRY(cost_of_staged(c, X, B, K, d, n, m, h));
+    LSQ_HIP(hipMemsetAsync(c->obj.p, 0, sizeof(double), c->stream));
+    LSQ_TRY(lsq_launch_sum_f64(c->stream, c->prev.as<float>(), n, c->obj.as<double>()));
+    double sum = 0.0;
+    LSQ_TRY(fetch(c, &sum, c->obj.p, sizeof(double)));
+    LSQ_TRY(finish(c));
+    *out = sum / (double)n;
     return LSQ_OK;
+}
+
+extern "C" int lsq_perturb(lsq_ctx *c, int16_t *B, int64_t n, int m, int h, int npert, uint64_t seed, uint32_t it, uint64_t global_offset) {
+    LSQ_TRY(entry_args("lsq_perturb", c, 1, n, m, h, npert >= 0 && (n == 0 || B), "bad arguments"));
+    if (n == 0) return LSQ_OK;
+    LSQ_TRY(stage_codes(c, B, n, m, h));
+    LSQ_TRY(c->recNew.ensure((size_t)n * lsq_code_stride(m)));
+    LSQ_TRY(lsq_launch_perturb(c->stream, c->recCur.as<uint8_t>(), c->recNew.as<uint8_t>(), n, m, npert, seed, it, global_offset, nullptr, nullptr));
+    LSQ_TRY(fetch_codes(c, B, n, m));
+    return finish(c);
+}
+
+// ---- the pairs: a host form and its _dev twin are ONE function.  `host` says which memory its pointers name -- and which codes: int16 1-based in host
+// memory, tight uint8 0-based on the device.  The checks come first, in the order both forms have always had; then the host form stages, both launch the
+// same sequence on device pointers, and the host form fetches and waits. -------------------------------------------------------------------------------------
+static int quantize_norms(const char *fn, lsq_ctx *c, bool host, const void *codes, const float *K, const float *cbnorms, int ncb, int d, int64_t n, int m, int h,
+                          void *idx_out, float *dbnorms, float *norms) {
+    LSQ_TRY(use_device(c));
+    LSQ_TRY(check_shape(fn, d, n, m, h));
+    if (ncb < 1 || ncb > LSQ_H) { lsq_set_error("%s: ncb=%d must lie in 1..256", fn, ncb); return LSQ_EINVAL; }
+    if (!K || !cbnorms || (n > 0 && !codes)) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    if (!host) return lsq_launch_quantize_norms(c->stream, static_cast<const uint8_t *>(codes), m, K, cbnorms, ncb, n, d, m, static_cast<uint8_t *>(idx_out), nullptr, dbnorms, norms);
+    if (n == 0) return LSQ_OK;
+    Slice cb{sizeof(float) * LSQ_H}, db{sizeof(float) * (size_t)n}, nr{sizeof(float) * (size_t)n};      // sF32: the norm table | dbnorms | norms
+    LSQ_TRY(claim_sK(c, d, m, K));
+    LSQ_TRY(stage_codes(c, static_cast<const int16_t *>(codes), n, m, h));
+    LSQ_TRY(carve_f32(c, {&cb, &db, &nr}));
+    LSQ_TRY(c->sOut16.ensure(sizeof(int16_t) * (size_t)n));
+    LSQ_TRY(stage(c, cb.p, cbnorms, sizeof(float) * (size_t)ncb));
+    LSQ_TRY(lsq_launch_quantize_norms(c->stream, c->recCur.as<uint8_t>(), lsq_code_stride(m), c->sK.as<float>(), cb.as<float>(), ncb, n, d, m, nullptr,
+                                      c->sOut16.as<int16_t>(), db.as<float>(), nr.as<float>()));
+    LSQ_TRY(fetch(c, idx_out, c->sOut16.p, sizeof(int16_t) * (size_t)n));
+    LSQ_TRY(fetch(c, dbnorms, db.p, db.bytes));
+    LSQ_TRY(fetch(c, norms, nr.p, nr.bytes));
+    return finish(c);
 }
 
 extern "C" int lsq_quantize_norms(lsq_ctx *c, const int16_t *B, const float *K, const float *cbnorms, int ncb, int d, int64_t n, int m, int h,
                                   int16_t *idx_out, float *dbnorms, float *norms) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape("lsq_quantize_norms", d, n, m, h));
-    if (ncb < 1 || ncb > LSQ_H) { lsq_set_error("lsq_quantize_norms: ncb=%d must lie in 1..256", ncb); return LSQ_EINVAL; }
-    if (!K || !cbnorms || (n > 0 && !B)) { lsq_set_error("lsq_quantize_norms: null pointer"); return LSQ_EINVAL; }
-    if (n == 0) return LSQ_OK;
-    LSQ_TRY(upload_xk(c, nullptr, K, d, n, m));
-    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));
-    LSQ_TRY(c->sF32.ensure(sizeof(float) * ((size_t)LSQ_H + 2 * (size_t)n)));
-    LSQ_TRY(c->sOut16.ensure(sizeof(int16_t) * (size_t)n));
-    float *dcb = c->sF32.as<float>(), *ddb = dcb + LSQ_H, *dnr = ddb + n;
-    LSQ_HIP(hipMemcpyAsync(dcb, cbnorms, sizeof(float) * (size_t)ncb, hipMemcpyHostToDevice, c->stream));
-    LSQ_TRY(lsq_launch_quantize_norms(c->stream, c->recCur.as<uint8_t>(), lsq_code_stride(m), c->sK.as<float>(), dcb, ncb, n, d, m, nullptr,
-                                      c->sOut16.as<int16_t>(), ddb, dnr));
-    if (idx_out) LSQ_HIP(hipMemcpyAsync(idx_out, c->sOut16.p, sizeof(int16_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (dbnorms) LSQ_HIP(hipMemcpyAsync(dbnorms, ddb, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (norms) LSQ_HIP(hipMemcpyAsync(norms, dnr, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    return LSQ_OK;
+    return quantize_norms("lsq_quantize_norms", c, true, B, K, cbnorms, ncb, d, n, m, h, idx_out, dbnorms, norms);
 }
-
 extern "C" int lsq_quantize_norms_dev(lsq_ctx *c, const uint8_t *d_codes, const float *d_K, const float *d_cbnorms, int ncb, int d, int64_t n, int m,
                                       int h, uint8_t *d_idx_out, float *d_dbnorms, float *d_norms) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape("lsq_quantize_norms_dev", d, n, m, h));
-    if (ncb < 1 || ncb > LSQ_H) { lsq_set_error("lsq_quantize_norms_dev: ncb=%d must lie in 1..256", ncb); return LSQ_EINVAL; }
-    if (!d_K || !d_cbnorms || (n > 0 && !d_codes)) { lsq_set_error("lsq_quantize_norms_dev: null pointer"); return LSQ_EINVAL; }
-    return lsq_launch_quantize_norms(c->stream, d_codes, m, d_K, d_cbnorms, ncb, n, d, m, d_idx_out, nullptr, d_dbnorms, d_norms);
+    return quantize_norms("lsq_quantize_norms_dev", c, false, d_codes, d_K, d_cbnorms, ncb, d, n, m, h, d_idx_out, d_dbnorms, d_norms);
 }
 
-// What the host-buffer codebook updates stage: X up (sX), the tables cache dropped (sK is about to hold other codebooks), optionally the codebooks K_up into
-// K_buf, then the codes up and compacted to tight [n][m] (sTight) -- enqueued in this order
-static int stage_training_set(lsq_ctx *c, const float *X, const int16_t *B, int d, int64_t n, int m, int h, const float *K_up = nullptr, DevBuf *K_buf = nullptr) {
-    const size_t kbytes = sizeof(float) * (size_t)m * LSQ_H * d;
-    LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)std::max<int64_t>(n, 1) * d));
-    LSQ_TRY(c->sK.ensure(kbytes));
-    if (K_up) LSQ_TRY(K_buf->ensure(kbytes));
-    c->tables_valid = false;
-    if (n > 0) LSQ_HIP(hipMemcpyAsync(c->sX.p, X, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
-    if (K_up) LSQ_HIP(hipMemcpyAsync(K_buf->p, K_up, kbytes, hipMemcpyHostToDevice, c->stream));
-    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));                          // records of stride 8 / 16 -> tight [n][m] below
-    LSQ_TRY(c->sTight.ensure((size_t)std::max<int64_t>(n, 1) * m));
-    if (n > 0) LSQ_TRY(lsq_launch_codes_compact(c->stream, c->recCur.as<uint8_t>(), n, m, c->sTight.as<uint8_t>()));
-    return LSQ_OK;
-}
-
-// the LSQR codebook update on the device (lsq_lsqr.hip).  cover: HOST bytes of a structured update's map (checked here), or null = the unstructured update
-static int check_cover(const char *fn, const uint8_t *dim2C, int d, int m) {      // d x m bytes in Julia's column-major order ([m][d] here), every entry 0 or 1
+// the LSQR codebook update on the device (lsq_lsqr.hip).  dim2C: a structured update's map -- d x m bytes in Julia's column-major order ([m][d] here), every
+// entry 0 or 1; in the memory `host` names -- or null = the unstructured update
+static int check_cover(const char *fn, const uint8_t *dim2C, int d, int m) {
     for (int64_t e = 0; dim2C && e < (int64_t)d * m; ++e)
         if (dim2C[e] > 1) { lsq_set_error("%s: dim2C[%lld] = %d is neither 0 nor 1", fn, (long long)e, (int)dim2C[e]); return LSQ_EINVAL; }
     return LSQ_OK;
 }
 
-static int update_codebooks_dev(const char *fn, lsq_ctx *c, const float *d_X, const uint8_t *d_codes, const uint8_t *d_dim2C, int d, int64_t n, int m, int h,
-                                float *d_K_out, int *iterations) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape(fn, d, n, m, h));
-    if (n < 1 || !d_X || !d_codes || !d_K_out) { lsq_set_error("%s: bad arguments", fn); return LSQ_EINVAL; }
-    std::vector<uint8_t> cover;                                               // the map's d m bytes: read back, checked and turned into the two lists on the host
-    if (d_dim2C) {
+static int update_codebooks(const char *fn, lsq_ctx *c, bool host, const float *X, const void *codes, const uint8_t *dim2C, int d, int64_t n, int m, int h,
+                            float *K_out, int *iterations) {
+    LSQ_TRY(entry_args(fn, c, d, n, m, h, n >= 1 && X && codes && K_out, "bad arguments"));
+    std::vector<uint8_t> cover;                                               // a _dev form's map: read back; checked and turned into the two lists on the host
+    if (!host && dim2C) {
         cover.resize((size_t)d * m);
-        LSQ_HIP(hipMemcpyAsync(cover.data(), d_dim2C, cover.size(), hipMemcpyDeviceToHost, c->stream));
-        LSQ_HIP(hipStreamSynchronize(c->stream));
-        LSQ_TRY(check_cover(fn, cover.data(), d, m));
+        LSQ_TRY(fetch(c, cover.data(), dim2C, cover.size()));
+        LSQ_TRY(finish(c));
+        dim2C = cover.data();
     }
-    return lsq_lsqr_update_codebooks(c->stream, &c->lsqr, d_X, d_codes, d_dim2C ? cover.data() : nullptr, d, n, m, d_K_out, iterations);
-}
-
-static int update_codebooks_gpu(const char *fn, lsq_ctx *c, const float *X, const int16_t *B, const uint8_t *dim2C, int d, int64_t n, int m, int h, float *K_out,
-                                int *iterations) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape(fn, d, n, m, h));
-    if (n < 1 || !X || !B || !K_out) { lsq_set_error("%s: bad arguments", fn); return LSQ_EINVAL; }
     LSQ_TRY(check_cover(fn, dim2C, d, m));
-    LSQ_TRY(stage_training_set(c, X, B, d, n, m, h));
+    if (!host) return lsq_lsqr_update_codebooks(c->stream, &c->lsqr, X, static_cast<const uint8_t *>(codes), dim2C, d, n, m, K_out, iterations);
+    LSQ_TRY(claim_sK(c, d, m));
+    LSQ_TRY(stage_X(c, X, d, n));
+    LSQ_TRY(stage_codes(c, static_cast<const int16_t *>(codes), n, m, h, true));
     LSQ_TRY(lsq_lsqr_update_codebooks(c->stream, &c->lsqr, c->sX.as<float>(), c->sTight.as<uint8_t>(), dim2C, d, n, m, c->sK.as<float>(), iterations));
-    LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, sizeof(float) * (size_t)m * LSQ_H * d, hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    return LSQ_OK;
+    LSQ_TRY(fetch(c, K_out, c->sK.p, codebook_bytes(d, m)));
+    return finish(c);
 }
 
 extern "C" int lsq_update_codebooks_dev(lsq_ctx *c, const float *d_X, const uint8_t *d_codes, int d, int64_t n, int m, int h, float *d_K_out,
                                         int *iterations) {
-    return update_codebooks_dev("lsq_update_codebooks_dev", c, d_X, d_codes, nullptr, d, n, m, h, d_K_out, iterations);
+    return update_codebooks("lsq_update_codebooks_dev", c, false, d_X, d_codes, nullptr, d, n, m, h, d_K_out, iterations);
 }
-
 extern "C" int lsq_update_codebooks_gpu(lsq_ctx *c, const float *X, const int16_t *B, int d, int64_t n, int m, int h, float *K_out, int *iterations) {
-    return update_codebooks_gpu("lsq_update_codebooks_gpu", c, X, B, nullptr, d, n, m, h, K_out, iterations);
+    return update_codebooks("lsq_update_codebooks_gpu", c, true, X, B, nullptr, d, n, m, h, K_out, iterations);
 }
-
 // the structured update: update_codebooks_generic / update_codebooks_chain (src/codebook_update.jl:104-158); a null map is the unstructured call
 extern "C" int lsq_update_codebooks_struct_dev(lsq_ctx *c, const float *d_X, const uint8_t *d_codes, const uint8_t *d_dim2C, int d, int64_t n, int m, int h,
                                                float *d_K_out, int *iterations) {
-    return update_codebooks_dev(d_dim2C ? "lsq_update_codebooks_struct_dev" : "lsq_update_codebooks_dev", c, d_X, d_codes, d_dim2C, d, n, m, h, d_K_out, iterations);
+    return update_codebooks(d_dim2C ? "lsq_update_codebooks_struct_dev" : "lsq_update_codebooks_dev", c, false, d_X, d_codes, d_dim2C, d, n, m, h, d_K_out, iterations);
 }
-
 extern "C" int lsq_update_codebooks_struct_gpu(lsq_ctx *c, const float *X, const int16_t *B, const uint8_t *dim2C, int d, int64_t n, int m, int h, float *K_out,
                                                int *iterations) {
-    return update_codebooks_gpu(dim2C ? "lsq_update_codebooks_struct_gpu" : "lsq_update_codebooks_gpu", c, X, B, dim2C, d, n, m, h, K_out, iterations);
+    return update_codebooks(dim2C ? "lsq_update_codebooks_struct_gpu" : "lsq_update_codebooks_gpu", c, true, X, B, dim2C, d, n, m, h, K_out, iterations);
 }
 
-// ---- the SPGL1 (LASSO) codebook update (lsq_spgl1.hip) ----------------------------------------------------------------------------------------
-// arguments first (no device needed to reject them), then the context: a NULL context on a machine without a device is LSQ_ENODEV
-static int spgl1_args(const char *fn, lsq_ctx *c, int d, int64_t n, int m, int h, double tau, const lsq_spgl1_params *p, double *opt_tol,
-                      int64_t *max_iter) {
+// the SPGL1 (LASSO) codebook update (lsq_spgl1.hip).  Arguments first (no device needed to reject them), then the context: a NULL context on a machine
+// without a device is LSQ_ENODEV; the pointers last
+static int update_codebooks_spgl1(const char *fn, lsq_ctx *c, bool host, const float *X, const void *codes, int d, int64_t n, int m, int h, double tau,
+                                  const float *K_init, int64_t S, const lsq_spgl1_params *p, float *K_out, lsq_spgl1_info *info) {
     LSQ_TRY(check_shape(fn, d, n, m, h));
     if (n < 1) { lsq_set_error("%s: n=%lld must be >= 1", fn, (long long)n); return LSQ_EINVAL; }
     if (!(tau >= 0.0)) { lsq_set_error("%s: tau=%g must be a number >= 0", fn, tau); return LSQ_EINVAL; }
     if (p && (p->opt_tol != p->opt_tol || p->opt_tol >= 1.0)) { lsq_set_error("%s: opt_tol=%g must be below 1", fn, p->opt_tol); return LSQ_EINVAL; }
-    *opt_tol = p && p->opt_tol > 0.0 ? p->opt_tol : 1e-4;
-    *max_iter = p && p->max_iter > 0 ? p->max_iter : 10 * n * (int64_t)d;        // spgSetParms: iterations = 10 length(b)
+    const double opt_tol = p && p->opt_tol > 0.0 ? p->opt_tol : 1e-4;
+    const int64_t max_iter = p && p->max_iter > 0 ? p->max_iter : 10 * n * (int64_t)d;        // spgSetParms: iterations = 10 length(b)
     if (!c) {
         int count = 0;
         if (lsq_device_count(&count) != LSQ_OK || count <= 0) { lsq_set_error("%s: no HIP device visible (this library has no CPU fallback)", fn); return LSQ_ENODEV; }
         lsq_set_error("%s: null lsq_ctx", fn);
         return LSQ_EINVAL;
     }
-    return use_device(c);
+    LSQ_TRY(use_device(c));
+    if (!X || !codes || !K_out) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    if (!host) return lsq_spgl1_update_codebooks(c->stream, &c->spgl1, X, static_cast<const uint8_t *>(codes), d, n, m, tau, K_init, S, opt_tol, max_iter, K_out, info);
+    Slice k0{K_init ? codebook_bytes(d, m) : 0};                                  // sF32: the start K_init
+    LSQ_TRY(claim_sK(c, d, m));
+    LSQ_TRY(carve_f32(c, {&k0}));
+    LSQ_TRY(stage_X(c, X, d, n));
+    if (K_init) LSQ_TRY(stage(c, k0.p, K_init, k0.bytes));
+    LSQ_TRY(stage_codes(c, static_cast<const int16_t *>(codes), n, m, h, true));
+    LSQ_TRY(lsq_spgl1_update_codebooks(c->stream, &c->spgl1, c->sX.as<float>(), c->sTight.as<uint8_t>(), d, n, m, tau, K_init ? k0.as<float>() : nullptr, S,
+                                       opt_tol, max_iter, c->sK.as<float>(), info));
+    LSQ_TRY(fetch(c, K_out, c->sK.p, codebook_bytes(d, m)));
+    return finish(c);
 }
 
 extern "C" int lsq_update_codebooks_spgl1_dev(lsq_ctx *c, const float *d_X, const uint8_t *d_codes, int d, int64_t n, int m, int h, double tau,
                                               const float *d_K_init, int64_t S, const lsq_spgl1_params *params, float *d_K_out, lsq_spgl1_info *info) {
-    double opt_tol = 0.0;
-    int64_t max_iter = 0;
-    LSQ_TRY(spgl1_args("lsq_update_codebooks_spgl1_dev", c, d, n, m, h, tau, params, &opt_tol, &max_iter));
-    if (!d_X || !d_codes || !d_K_out) { lsq_set_error("lsq_update_codebooks_spgl1_dev: null pointer"); return LSQ_EINVAL; }
-    return lsq_spgl1_update_codebooks(c->stream, &c->spgl1, d_X, d_codes, d, n, m, tau, d_K_init, S, opt_tol, max_iter, d_K_out, info);
+    return update_codebooks_spgl1("lsq_update_codebooks_spgl1_dev", c, false, d_X, d_codes, d, n, m, h, tau, d_K_init, S, params, d_K_out, info);
 }
-
 extern "C" int lsq_update_codebooks_spgl1(lsq_ctx *c, const float *X, const int16_t *B, int d, int64_t n, int m, int h, double tau, const float *K_init,
                                           int64_t S, const lsq_spgl1_params *params, float *K_out, lsq_spgl1_info *info) {
-    double opt_tol = 0.0;
-    int64_t max_iter = 0;
-    LSQ_TRY(spgl1_args("lsq_update_codebooks_spgl1", c, d, n, m, h, tau, params, &opt_tol, &max_iter));
-    if (!X || !B || !K_out) { lsq_set_error("lsq_update_codebooks_spgl1: null pointer"); return LSQ_EINVAL; }
-    LSQ_TRY(stage_training_set(c, X, B, d, n, m, h, K_init, &c->sF32));
-    LSQ_TRY(lsq_spgl1_update_codebooks(c->stream, &c->spgl1, c->sX.as<float>(), c->sTight.as<uint8_t>(), d, n, m, tau,
-                                       K_init ? c->sF32.as<float>() : nullptr, S, opt_tol, max_iter, c->sK.as<float>(), info));
-    LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, sizeof(float) * (size_t)m * LSQ_H * d, hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    return LSQ_OK;
+    return update_codebooks_spgl1("lsq_update_codebooks_spgl1", c, true, X, B, d, n, m, h, tau, K_init, S, params, K_out, info);
 }
 
-extern "C" int lsq_qerror(lsq_ctx *c, const float *X, const int16_t *B, const float *K, int d, int64_t n, int m, int h, double *out) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape("lsq_qerror", d, n, m, h));
-    if (!out || !K || (n > 0 && (!X || !B))) { lsq_set_error("lsq_qerror: null pointer"); return LSQ_EINVAL; }
-    *out = 0.0;
+// The initialisers' data-parallel steps (lsq_init.hip).  Both are "unaries of a chunk, then one kernel": the unaries are the path's own
+// (row-major f32 planes of the chain GEMM -- the bits lsq_get_unaries returns), so the codes are integer functions of exactly the numbers
+// oracle/init_oracle.py works on.  B: int16 1-based [n][m] (host) or tight uint8 0-based (device)
+static int init_codes(lsq_ctx *c, const char *fn, bool host, const float *X, const float *K, int d, int64_t n, int m, int h, void *B, float *minval, bool chain) {
+    const bool short_chain = chain && m < 2;        // a _dev form says so before it looks at its pointers, a host form once it has rows: as they always did
+    const char *needs_two = "a chain needs at least two codebooks";
+    LSQ_TRY(entry_args(fn, c, d, n, m, h, host || !short_chain, needs_two));
+    if (!K || (n > 0 && (!X || !B))) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
     if (n == 0) return LSQ_OK;
-    LSQ_TRY(upload_xk(c, X, K, d, n, m));
-    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));
-    LSQ_TRY(c->prev.ensure(sizeof(float) * (size_t)n));
-    LSQ_TRY(c->obj.ensure(sizeof(double)));
-    LSQ_HIP(hipMemsetAsync(c->obj.p, 0, sizeof(double), c->stream));
-    LSQ_TRY(lsq_launch_cost(c->stream, c->sX.as<float>(), c->sK.as<float>(), c->recCur.as<uint8_t>(), c->recCur.as<uint8_t>(),
-                            c->prev.as<float>(), nullptr, n, d, m, 0, nullptr, nullptr));
-    LSQ_TRY(lsq_launch_sum_f64(c->stream, c->prev.as<float>(), n, c->obj.as<double>()));
-    double sum = 0.0;
-    LSQ_HIP(hipMemcpyAsync(&sum, c->obj.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    *out = sum / (double)n;
-    return LSQ_OK;
-}
-
-extern "C" int lsq_perturb(lsq_ctx *c, int16_t *B, int64_t n, int m, int h, int npert, uint64_t seed, uint32_t it, uint64_t global_offset) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape("lsq_perturb", 1, n, m, h));
-    if (npert < 0 || (n > 0 && !B)) { lsq_set_error("lsq_perturb: bad arguments"); return LSQ_EINVAL; }
-    if (n == 0) return LSQ_OK;
-    LSQ_TRY(upload_codes(c, B, n, m, h, c->recCur));
-    LSQ_TRY(c->recNew.ensure((size_t)n * lsq_code_stride(m)));
-    LSQ_TRY(lsq_launch_perturb(c->stream, c->recCur.as<uint8_t>(), c->recNew.as<uint8_t>(), n, m, npert, seed, it, global_offset, nullptr, nullptr));
-    LSQ_TRY(lsq_launch_codes_to_i16(c->stream, c->recNew.as<uint8_t>(), n, m, c->sB16.as<int16_t>()));
-    LSQ_HIP(hipMemcpyAsync(B, c->sB16.p, sizeof(int16_t) * (size_t)n * m, hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    return LSQ_OK;
-}
-
-// ---- the initialisers' data-parallel steps (lsq_init.hip) ---------------------------------------------------------------------
-// Both are "unaries of a chunk, then one kernel": the unaries are the path's own (row-major f32 planes of the chain GEMM -- the bits lsq_get_unaries
-// returns), so the codes are integer functions of exactly the numbers oracle/init_oracle.py works on.
-static int init_codes_dev(lsq_ctx *c, const char *fn, const float *dX, const float *dK, int d, int64_t n, int m, int h, uint8_t *dB, float *dmin, bool chain) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape(fn, d, n, m, h));
-    if (chain && m < 2) { lsq_set_error("%s: a chain needs at least two codebooks", fn); return LSQ_EINVAL; }
-    if (!dK || (n > 0 && (!dX || !dB))) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
-    if (n == 0) return LSQ_OK;
-    if (chain) LSQ_TRY(prepare_tables(c, dK, d, m));                  // ||c||^2 and the pair tables (the chain reads the m - 1 adjacent ones)
+    if (short_chain) { lsq_set_error("%s: %s", fn, needs_two); return LSQ_EINVAL; }
+    Slice mins{host && minval ? sizeof(float) * (size_t)n * m : 0};              // sF32: the minima
+    uint8_t *dB = static_cast<uint8_t *>(B);
+    float *dmin = minval;
+    if (host) {
+        LSQ_TRY(claim_sK(c, d, m, K));
+        LSQ_TRY(stage_X(c, X, d, n));
+        LSQ_TRY(c->sTight.ensure((size_t)n * m));
+        LSQ_TRY(carve_f32(c, {&mins}));
+        X = c->sX.as<float>(); K = c->sK.as<float>(); dB = c->sTight.as<uint8_t>(); dmin = minval ? mins.as<float>() : nullptr;
+    }
+    if (chain) LSQ_TRY(prepare_tables(c, K, d, m));                   // ||c||^2 and the pair tables (the chain reads the m - 1 adjacent ones)
     else {
         c->tables_valid = false;
         LSQ_TRY(c->sci.ensure(sizeof(float) * (size_t)m * LSQ_H));
-        LSQ_TRY(lsq_launch_sqnorms(c->stream, dK, m * LSQ_H, d, c->sci.as<float>()));
+        LSQ_TRY(lsq_launch_sqnorms(c->stream, K, m * LSQ_H, d, c->sci.as<float>()));
     }
     for (int64_t off = 0; off < n; off += c->chunk) {
         const int64_t cn = std::min<int64_t>(c->chunk, n - off);
-        LSQ_TRY(build_unaries(c, dX + off * d, dK, d, cn, m, 0, 0, cn));
+        LSQ_TRY(build_unaries(c, X + off * d, K, d, cn, m, 0, 0, cn));
         Timer t(c, CAT_OTHER);
         if (chain) LSQ_TRY(lsq_launch_viterbi(c->stream, c->U.as<float>(), c->T.as<float>(), cn, m, dB + off * m));
         else LSQ_TRY(lsq_launch_unary_argmin(c->stream, c->U.as<float>(), cn, m, dB + off * m, dmin ? dmin + off * m : nullptr));
     }
-    return LSQ_OK;
-}
-
-static int init_codes_host(lsq_ctx *c, const char *fn, const float *X, const float *K, int d, int64_t n, int m, int h, int16_t *B, float *minval, bool chain) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape(fn, d, n, m, h));
-    if (!K || (n > 0 && (!X || !B))) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
-    if (n == 0) return LSQ_OK;
-    LSQ_TRY(upload_xk(c, X, K, d, n, m));
-    LSQ_TRY(c->sTight.ensure((size_t)n * m));
-    LSQ_TRY(c->sB16.ensure(sizeof(int16_t) * (size_t)n * m));
-    float *dmin = nullptr;
-    if (minval) { LSQ_TRY(c->sF32.ensure(sizeof(float) * (size_t)n * m)); dmin = c->sF32.as<float>(); }
-    LSQ_TRY(init_codes_dev(c, fn, c->sX.as<float>(), c->sK.as<float>(), d, n, m, h, c->sTight.as<uint8_t>(), dmin, chain));
-    LSQ_TRY(c->recNew.ensure((size_t)n * lsq_code_stride(m)));
-    LSQ_TRY(lsq_launch_codes_expand(c->stream, c->sTight.as<uint8_t>(), n, m, c->recNew.as<uint8_t>()));
-    LSQ_TRY(lsq_launch_codes_to_i16(c->stream, c->recNew.as<uint8_t>(), n, m, c->sB16.as<int16_t>()));
-    LSQ_HIP(hipMemcpyAsync(B, c->sB16.p, sizeof(int16_t) * (size_t)n * m, hipMemcpyDeviceToHost, c->stream));
-    if (minval) LSQ_HIP(hipMemcpyAsync(minval, dmin, sizeof(float) * (size_t)n * m, hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    return LSQ_OK;
+    if (!host) return LSQ_OK;
+    LSQ_TRY(fetch_codes(c, static_cast<int16_t *>(B), n, m, true));
+    LSQ_TRY(fetch(c, minval, mins.p, mins.bytes));
+    return finish(c);
 }
 
 extern "C" int lsq_encode_viterbi_dev(lsq_ctx *c, const float *dX, const float *dK, int d, int64_t n, int m, int h, uint8_t *dB) {
-    return init_codes_dev(c, "lsq_encode_viterbi_dev", dX, dK, d, n, m, h, dB, nullptr, true);
+    return init_codes(c, "lsq_encode_viterbi_dev", false, dX, dK, d, n, m, h, dB, nullptr, true);
 }
 extern "C" int lsq_encode_viterbi(lsq_ctx *c, const float *X, const float *K, int d, int64_t n, int m, int h, int16_t *B) {
-    return init_codes_host(c, "lsq_encode_viterbi", X, K, d, n, m, h, B, nullptr, true);
+    return init_codes(c, "lsq_encode_viterbi", true, X, K, d, n, m, h, B, nullptr, true);
 }
 extern "C" int lsq_assign_codewords_dev(lsq_ctx *c, const float *dX, const float *dK, int d, int64_t n, int m, int h, uint8_t *dB, float *d_minval) {
-    return init_codes_dev(c, "lsq_assign_codewords_dev", dX, dK, d, n, m, h, dB, d_minval, false);
+    return init_codes(c, "lsq_assign_codewords_dev", false, dX, dK, d, n, m, h, dB, d_minval, false);
 }
 extern "C" int lsq_assign_codewords(lsq_ctx *c, const float *X, const float *K, int d, int64_t n, int m, int h, int16_t *B, float *minval) {
-    return init_codes_host(c, "lsq_assign_codewords", X, K, d, n, m, h, B, minval, false);
+    return init_codes(c, "lsq_assign_codewords", true, X, K, d, n, m, h, B, minval, false);
 }
 
-// ---- cluster means and k-means++ seeding (lsq_kmeans.hip) -----------------------------------------------------------------------------------------
-// the cover map of these entries is HOST memory in both forms: its d m bytes are checked before anything is launched, so a _dev call never waits for the device
+// Cluster means and k-means++ seeding (lsq_kmeans.hip).  The cover map of these entries is HOST memory in both forms: its d m bytes are checked before
+// anything is launched, so a _dev call never waits for the device
 static int kmeans_args(const char *fn, lsq_ctx *c, const uint8_t *dim2C, int d, int64_t n, int m, int h) {
-    LSQ_TRY(use_device(c));
-    LSQ_TRY(check_shape(fn, d, n, m, h));
-    if (!dim2C) { lsq_set_error("%s: null dim2C (plain k-means is m = 1 with every dimension covered)", fn); return LSQ_EINVAL; }
+    LSQ_TRY(entry_args(fn, c, d, n, m, h, dim2C != nullptr, "null dim2C (plain k-means is m = 1 with every dimension covered)"));
     LSQ_TRY(check_cover(fn, dim2C, d, m));
     for (int j = 0; j < m; ++j) {
         int cnt = 0;
@@ -2001,69 +2007,69 @@ static int kmeans_args(const char *fn, lsq_ctx *c, const uint8_t *dim2C, int d, 
     return LSQ_OK;
 }
 
+static int update_centers(const char *fn, lsq_ctx *c, bool host, const float *X, const void *codes, const uint8_t *dim2C, const float *K_prev, int d, int64_t n,
+                          int m, int h, float *K_out, int *counts) {
+    LSQ_TRY(kmeans_args(fn, c, dim2C, d, n, m, h));
+    if (!K_out || (n > 0 && (!X || !codes))) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    if (n * (int64_t)m >= (int64_t)1 << 31) { lsq_set_error("%s: n * m = %lld exceeds 2^31 - 1", fn, (long long)(n * m)); return LSQ_EINVAL; }
+    if (!host) return lsq_kmeans_update_centers(c->stream, &c->kmeans, X, static_cast<const uint8_t *>(codes), dim2C, K_prev, d, n, m, K_out, counts);
+    Slice cnt{sizeof(int) * (size_t)m * LSQ_H};                                   // sF32: the cluster counts
+    LSQ_TRY(claim_sK(c, d, m));
+    LSQ_TRY(carve_f32(c, {&cnt}));
+    LSQ_TRY(stage_X(c, X, d, n));
+    if (K_prev) LSQ_TRY(stage(c, c->sK.p, K_prev, codebook_bytes(d, m)));          // K_prev in place: an empty cluster keeps the entry it finds
+    LSQ_TRY(stage_codes(c, static_cast<const int16_t *>(codes), n, m, h, true));
+    LSQ_TRY(lsq_kmeans_update_centers(c->stream, &c->kmeans, c->sX.as<float>(), c->sTight.as<uint8_t>(), dim2C, K_prev ? c->sK.as<float>() : nullptr, d, n, m,
+                                      c->sK.as<float>(), cnt.as<int>()));
+    LSQ_TRY(fetch(c, K_out, c->sK.p, codebook_bytes(d, m)));
+    LSQ_TRY(fetch(c, counts, cnt.p, cnt.bytes));
+    return finish(c);
+}
+
 extern "C" int lsq_update_centers_dev(lsq_ctx *c, const float *d_X, const uint8_t *d_codes, const uint8_t *dim2C, const float *d_K_prev, int d, int64_t n,
                                       int m, int h, float *d_K_out, int *d_counts) {
-    LSQ_TRY(kmeans_args("lsq_update_centers_dev", c, dim2C, d, n, m, h));
-    if (!d_K_out || (n > 0 && (!d_X || !d_codes))) { lsq_set_error("lsq_update_centers_dev: null pointer"); return LSQ_EINVAL; }
-    if (n * (int64_t)m >= (int64_t)1 << 31) { lsq_set_error("lsq_update_centers_dev: n * m = %lld exceeds 2^31 - 1", (long long)(n * m)); return LSQ_EINVAL; }
-    return lsq_kmeans_update_centers(c->stream, &c->kmeans, d_X, d_codes, dim2C, d_K_prev, d, n, m, d_K_out, d_counts);
+    return update_centers("lsq_update_centers_dev", c, false, d_X, d_codes, dim2C, d_K_prev, d, n, m, h, d_K_out, d_counts);
 }
-
 extern "C" int lsq_update_centers(lsq_ctx *c, const float *X, const int16_t *B, const uint8_t *dim2C, const float *K_prev, int d, int64_t n, int m, int h,
                                   float *K_out, int *counts) {
-    LSQ_TRY(kmeans_args("lsq_update_centers", c, dim2C, d, n, m, h));
-    if (!K_out || (n > 0 && (!X || !B))) { lsq_set_error("lsq_update_centers: null pointer"); return LSQ_EINVAL; }
-    if (n * (int64_t)m >= (int64_t)1 << 31) { lsq_set_error("lsq_update_centers: n * m = %lld exceeds 2^31 - 1", (long long)(n * m)); return LSQ_EINVAL; }
-    const size_t kbytes = sizeof(float) * (size_t)m * LSQ_H * d;
-    LSQ_TRY(c->sF32.ensure(sizeof(int) * (size_t)m * LSQ_H));
-    LSQ_TRY(stage_training_set(c, X, B, d, n, m, h, K_prev, &c->sK));      // K_prev in place: an empty cluster keeps the entry it finds
-    LSQ_TRY(lsq_kmeans_update_centers(c->stream, &c->kmeans, c->sX.as<float>(), c->sTight.as<uint8_t>(), dim2C, K_prev ? c->sK.as<float>() : nullptr, d, n, m,
-                                      c->sK.as<float>(), c->sF32.as<int>()));
-    LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, kbytes, hipMemcpyDeviceToHost, c->stream));
-    if (counts) LSQ_HIP(hipMemcpyAsync(counts, c->sF32.p, sizeof(int) * (size_t)m * LSQ_H, hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    return LSQ_OK;
+    return update_centers("lsq_update_centers", c, true, X, B, dim2C, K_prev, d, n, m, h, K_out, counts);
 }
 
-static int kmeanspp_u(const char *fn, const double *u, int m) {
+static int kmeanspp_seed(const char *fn, lsq_ctx *c, bool host, const float *X, const uint8_t *dim2C, const double *u, int d, int64_t n, int m, int h, float *K_out,
+                         int64_t *idx_out, float *d2_out) {
+    LSQ_TRY(kmeans_args(fn, c, dim2C, d, n, m, h));
     if (!u) { lsq_set_error("%s: null u", fn); return LSQ_EINVAL; }
     for (int e = 0; e < m * LSQ_H; ++e)
         if (!(u[e] >= 0.0 && u[e] < 1.0)) { lsq_set_error("%s: u[%d] = %g lies outside [0, 1)", fn, e, u[e]); return LSQ_EINVAL; }
-    return LSQ_OK;
+    if (!K_out || (n > 0 && !X)) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    Slice idx{sizeof(int64_t) * (size_t)m * LSQ_H}, d2{sizeof(float) * (size_t)n * m};      // sF32 (host form): the chosen rows' indices | d2
+    float *dK = K_out, *dd2 = d2_out;
+    int64_t *didx = idx_out;
+    if (host) {
+        if (n == 0) d2_out = nullptr;                                         // d2 is empty
+        LSQ_TRY(claim_sK(c, d, m));
+        LSQ_TRY(carve_f32(c, {&idx, &d2}));
+        LSQ_TRY(stage_X(c, X, d, n));
+        X = c->sX.as<float>(); dK = c->sK.as<float>(); didx = idx.as<int64_t>(); dd2 = d2_out ? d2.as<float>() : nullptr;
+    }
+    if (n == 0) {                                                             // no row to choose: zero codebooks, indices -1, d2 empty
+        LSQ_HIP(hipMemsetAsync(dK, 0, codebook_bytes(d, m), c->stream));
+        if (didx) LSQ_TRY(lsq_kmeans_fill_i64(c->stream, didx, (int64_t)m * LSQ_H, -1));
+    } else LSQ_TRY(lsq_kmeans_seed(c->stream, &c->kmeans, X, dim2C, u, d, n, m, dK, didx, dd2));
+    if (!host) return LSQ_OK;
+    LSQ_TRY(fetch(c, K_out, dK, codebook_bytes(d, m)));
+    LSQ_TRY(fetch(c, idx_out, didx, idx.bytes));
+    LSQ_TRY(fetch(c, d2_out, dd2, d2.bytes));
+    return finish(c);
 }
 
 extern "C" int lsq_kmeanspp_seed_dev(lsq_ctx *c, const float *d_X, const uint8_t *dim2C, const double *u, int d, int64_t n, int m, int h, float *d_K_out,
                                      int64_t *d_idx_out, float *d_d2_out) {
-    LSQ_TRY(kmeans_args("lsq_kmeanspp_seed_dev", c, dim2C, d, n, m, h));
-    LSQ_TRY(kmeanspp_u("lsq_kmeanspp_seed_dev", u, m));
-    if (!d_K_out || (n > 0 && !d_X)) { lsq_set_error("lsq_kmeanspp_seed_dev: null pointer"); return LSQ_EINVAL; }
-    if (n == 0) {                                                             // no row to choose: zero codebooks, indices -1, d2 empty
-        LSQ_HIP(hipMemsetAsync(d_K_out, 0, sizeof(float) * (size_t)m * LSQ_H * d, c->stream));
-        if (d_idx_out) LSQ_TRY(lsq_kmeans_fill_i64(c->stream, d_idx_out, (int64_t)m * LSQ_H, -1));
-        return LSQ_OK;
-    }
-    return lsq_kmeans_seed(c->stream, &c->kmeans, d_X, dim2C, u, d, n, m, d_K_out, d_idx_out, d_d2_out);
+    return kmeanspp_seed("lsq_kmeanspp_seed_dev", c, false, d_X, dim2C, u, d, n, m, h, d_K_out, d_idx_out, d_d2_out);
 }
-
 extern "C" int lsq_kmeanspp_seed(lsq_ctx *c, const float *X, const uint8_t *dim2C, const double *u, int d, int64_t n, int m, int h, float *K_out,
                                  int64_t *idx_out, float *d2_out) {
-    LSQ_TRY(kmeans_args("lsq_kmeanspp_seed", c, dim2C, d, n, m, h));
-    LSQ_TRY(kmeanspp_u("lsq_kmeanspp_seed", u, m));
-    if (!K_out || (n > 0 && !X)) { lsq_set_error("lsq_kmeanspp_seed: null pointer"); return LSQ_EINVAL; }
-    const size_t kbytes = sizeof(float) * (size_t)m * LSQ_H * d, ibytes = sizeof(int64_t) * (size_t)m * LSQ_H, dbytes = sizeof(float) * (size_t)n * m;
-    LSQ_TRY(c->sX.ensure(sizeof(float) * (size_t)std::max<int64_t>(n, 1) * d));
-    LSQ_TRY(c->sK.ensure(kbytes));
-    LSQ_TRY(c->sF32.ensure(ibytes + dbytes + 16));
-    c->tables_valid = false;
-    int64_t *didx = c->sF32.as<int64_t>();
-    float *dd2 = reinterpret_cast<float *>(c->sF32.as<char>() + ibytes);
-    if (n > 0) LSQ_HIP(hipMemcpyAsync(c->sX.p, X, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
-    LSQ_TRY(lsq_kmeanspp_seed_dev(c, c->sX.as<float>(), dim2C, u, d, n, m, h, c->sK.as<float>(), didx, d2_out && n > 0 ? dd2 : nullptr));
-    LSQ_HIP(hipMemcpyAsync(K_out, c->sK.p, kbytes, hipMemcpyDeviceToHost, c->stream));
-    if (idx_out) LSQ_HIP(hipMemcpyAsync(idx_out, didx, ibytes, hipMemcpyDeviceToHost, c->stream));
-    if (d2_out && n > 0) LSQ_HIP(hipMemcpyAsync(d2_out, dd2, dbytes, hipMemcpyDeviceToHost, c->stream));
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    return LSQ_OK;
+    return kmeanspp_seed("lsq_kmeanspp_seed", c, true, X, dim2C, u, d, n, m, h, K_out, idx_out, d2_out);
 }
 
 // ---- device-side generators ---------------------------------------------------------------------

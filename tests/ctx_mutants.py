@@ -15,7 +15,8 @@ import sys
 
 # (name, old, new, profile, pair)
 MUTANTS = [
-    # the host-table cache (hostK / tables_valid), site 1: the fine-grained entry points stage other codebooks in sK
+    # the host-table cache (hostK / tables_valid), site 1: claim_sK, the one place where a host-buffer call takes sK for other codebooks
+    # (the name is that of the helper that held the line before claim_sK: the built copies and their reports are known by it)
     ("upload_xk_keeps_tables_valid",
      "    c->tables_valid = false;        // sK is about to hold other codebooks than the cached tables were built from\n",
      "    // (mutant) sK is about to hold other codebooks than the cached tables were built from\n",
