@@ -22,7 +22,14 @@ class LsqError(RuntimeError):
         self.code = code
 
 
-class Timings(C.Structure):
+class _Struct(C.Structure):
+    """a struct of the header; as_dict: its fields by name (the statistics and info structs are handed out that way)"""
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Timings(_Struct):
     _fields_ = [("tables_ms", C.c_double), ("unaries_ms", C.c_double), ("perturb_ms", C.c_double),
                 ("icm_ms", C.c_double), ("cost_ms", C.c_double), ("other_ms", C.c_double),
                 ("icm_launches", C.c_int64), ("icm_node_updates", C.c_int64),
@@ -31,62 +38,47 @@ class Timings(C.Structure):
                 ("filter_fallback_chunks", C.c_int64), ("xs_launches", C.c_int64), ("xs_fallback_launches", C.c_int64),
                 ("table_reuses", C.c_int64)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class LinscanStats(C.Structure):
+class LinscanStats(_Struct):
     _fields_ = [("queries", C.c_int64), ("codes", C.c_int64), ("candidates", C.c_int64), ("fallback_queries", C.c_int64),
                 ("batches", C.c_int64), ("exhaustive", C.c_int64), ("threshold_rank", C.c_int64), ("list_capacity", C.c_int64),
                 ("lut_ms", C.c_double), ("sample_ms", C.c_double), ("scan_ms", C.c_double), ("select_ms", C.c_double)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class IndexDesc(C.Structure):
+class IndexDesc(_Struct):
     _fields_ = [("n", C.c_int64), ("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("codes", C.c_void_p), ("codebooks", C.c_void_p),
                 ("dbnorms", C.c_void_p), ("base", C.c_void_p), ("base_u8", C.c_int), ("ldb", C.c_int), ("on_device", C.c_int)]
 
 
-class IndexKnnInfo(C.Structure):
+class IndexKnnInfo(_Struct):
     _fields_ = [("queries", C.c_int64), ("rows", C.c_int64), ("batches", C.c_int64), ("fallback_queries", C.c_int64), ("exhaustive", C.c_int64),
                 ("int_road", C.c_int64), ("norms_ms", C.c_double), ("scan_ms", C.c_double), ("select_ms", C.c_double)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class IndexStats(C.Structure):
+class IndexStats(_Struct):
     _fields_ = [("queries", C.c_int64), ("rows", C.c_int64), ("invalid", C.c_int64), ("batches", C.c_int64),
                 ("scan_ms", C.c_double), ("gather_ms", C.c_double), ("select_ms", C.c_double)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class Q16SnapshotNode(C.Structure):
+class Q16SnapshotNode(_Struct):
     _fields_ = [("loU", C.c_float), ("invD", C.c_float), ("D", C.c_float), ("hiq", C.c_float), ("window", C.c_int32), ("pad_", C.c_int32),
                 ("slack", C.c_double)]
 
 
-class Q16SnapshotParams(C.Structure):
+class Q16SnapshotParams(_Struct):
     _fields_ = [("ok", C.c_int32), ("oor", C.c_int32), ("nflag", C.c_int32), ("pad_", C.c_int32), ("node", Q16SnapshotNode * 16)]
 
 
 SNAP_PARAMS, SNAP_UQ, SNAP_TQ, SNAP_QFLAG, SNAP_U, SNAP_T = 0, 1, 2, 3, 4, 5
 
 
-class Spgl1Params(C.Structure):
+class Spgl1Params(_Struct):
     _fields_ = [("opt_tol", C.c_double), ("max_iter", C.c_int64)]
 
 
-class Spgl1Info(C.Structure):
+class Spgl1Info(_Struct):
     _fields_ = [("status", C.c_int), ("iterations", C.c_int64), ("line_search_trials", C.c_int64), ("f", C.c_double), ("rel_gap", C.c_double),
                 ("l1", C.c_double), ("tau", C.c_double), ("nnz_before_threshold", C.c_int64), ("nnz", C.c_int64)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 SPGL1_OPTIMAL, SPGL1_ITERATIONS, SPGL1_LINE_ERROR = 0, 1, 2

@@ -8,6 +8,8 @@ import re
 import numpy as np
 import pytest
 
+from engine_calls import _Recorder, _offline
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = 256
 U8 = {"lsq_encode_icm_u8": "lsq_encode_icm", "lsq_encode_icm_u8_dev": "lsq_encode_icm_dev", "lsq_multi_encode_icm_u8": "lsq_multi_encode_icm"}
@@ -53,25 +55,6 @@ def test_null_context_is_einval(lsq):
     assert L.lsq_encode_icm_u8_dev(None, None, None, None, 8, 4, 2, H, ils.ctypes.data, 1, 1, 1, 1, 0, 0, None, None, None) == lsq._lib.LSQ_EINVAL
     assert L.lsq_multi_encode_icm_u8(None, None, None, None, 8, 4, 2, H, ils.ctypes.data, 1, 1, 1, 1, 0, 0, 0, None, None) == lsq._lib.LSQ_EINVAL
     assert b"null" in L.lsq_last_error()
-
-
-class _Recorder:
-    """stands in for the ctypes library: every symbol is a function that records its call and reports success"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def fn(*args):
-            self.calls.append((name, args))
-            return 0
-        return fn
-
-
-def _offline(cls):
-    obj = cls.__new__(cls)
-    obj._L, obj._h = _Recorder(), C.c_void_p(1)
-    return obj
 
 
 def _problem(n=6, d=8, m=2, seed=0):
