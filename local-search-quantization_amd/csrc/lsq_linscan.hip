@@ -23,13 +23,28 @@
 
 namespace {
 
-typedef std::pair<float, int> DistId;      // lexicographic < : distance, then id -- std::pair's own order
+// A (dist, id) pair as ONE 64-bit key: order-preserving distance bits << 32 | id.  Its integer order is the lexicographic pair order for every non-NaN
+// distance (no sum of the scans below is ever -0.0: each chain starts from +0.0) and puts NaN last, as one NaN -- what the device scan does.  A
+// std::pair<float, int> has no order with a NaN in it: a heap built on it loses its invariant and hands back NaN among, or before, the finite distances.
+inline uint64_t pq_key(float v, uint32_t id) {
+    uint32_t b;
+    memcpy(&b, &v, 4);
+    const uint32_t k = v != v ? 0xffffffffu : b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+    return ((uint64_t)k << 32) | id;
+}
+inline float pq_unkey(uint64_t key) {
+    const uint32_t k = (uint32_t)(key >> 32);
+    const uint32_t b = k == 0xffffffffu ? 0x7fc00000u : ((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+    float v;
+    memcpy(&v, &b, 4);
+    return v;
+}
 
 void scan_queries(float *dists, int *idx, const unsigned char *codes, const float *queries, const float *codebooks,
                   const float *dbnorms, int q0, int q1, int ncodes, int m, int h, int d, int nn) {
     const int total = m * h;
     std::vector<float> table((size_t)total);
-    std::vector<DistId> heap;
+    std::vector<uint64_t> heap;
     heap.reserve((size_t)nn + 1);
     for (int q = q0; q < q1; ++q) {
         const float *query = queries + (size_t)q * d;
@@ -41,24 +56,31 @@ void scan_queries(float *dists, int *idx, const unsigned char *codes, const floa
         }
         heap.clear();
         const unsigned char *code = codes;
+        bool full = false;
+        float worst = 0.0f;                                             // the heap's largest distance once it is full
         for (int i = 0; i < ncodes; ++i, code += m) {
             float acc = 0.0f;
             for (int k = 0; k < m; ++k) acc += table[(size_t)h * k + code[k]];
             acc += dbnorms[i];
-            const DistId cand(acc, i + 1);
-            if ((int)heap.size() < nn) {
+            if (full && acc > worst) continue;                          // strictly farther (false with a NaN on either side: the keys decide)
+            const uint64_t cand = pq_key(acc, (uint32_t)(i + 1));      // ids are 1-BASED (:75)
+            if (!full) {
                 heap.push_back(cand);
                 std::push_heap(heap.begin(), heap.end());               // max-heap on (dist, id)
             } else if (cand < heap.front()) {
                 std::pop_heap(heap.begin(), heap.end());
                 heap.back() = cand;
                 std::push_heap(heap.begin(), heap.end());
+            } else {
+                continue;
             }
+            full = (int)heap.size() == nn;
+            if (full) worst = pq_unkey(heap.front());
         }
         std::sort_heap(heap.begin(), heap.end());                       // ascending (dist, id)
         for (int r = 0; r < nn; ++r) {
-            dists[(size_t)q * nn + r] = heap[(size_t)r].first;
-            idx[(size_t)q * nn + r] = heap[(size_t)r].second;
+            dists[(size_t)q * nn + r] = pq_unkey(heap[(size_t)r]);
+            idx[(size_t)q * nn + r] = (int)(uint32_t)heap[(size_t)r];
         }
     }
 }
@@ -96,24 +118,9 @@ extern "C" int lsq_linscan_aqd_query_extra_byte(float *dists, int *idx, const un
 //   result           = the K smallest (dist, id) pairs in lexicographic order, ids 0-BASED uint32 (:93-101)
 //
 // The reference's chunks of 10^7 pairs return exactly the K lexicographically smallest pairs (what a pair left over from an earlier chunk
-// could displace was already smaller); a bounded heap per query does the same.  Pairs are held as 64-bit keys (order-preserving distance bits
-// << 32 | id): the lexicographic order for every non-NaN distance, and NaN last (the reference's partial_sort leaves NaN undefined) -- what the
-// device scan does.
+// could displace was already smaller); a bounded heap per query does the same, on the 64-bit keys of pq_key above (NaN last: the reference's
+// partial_sort leaves NaN undefined).
 namespace {
-
-inline uint64_t pq_key(float v, uint32_t id) {
-    uint32_t b;
-    memcpy(&b, &v, 4);
-    const uint32_t k = v != v ? 0xffffffffu : b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
-    return ((uint64_t)k << 32) | id;
-}
-inline float pq_unkey(uint64_t key) {
-    const uint32_t k = (uint32_t)(key >> 32);
-    const uint32_t b = k == 0xffffffffu ? 0x7fc00000u : ((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-    float v;
-    memcpy(&v, &b, 4);
-    return v;
-}
 
 void pq_scan_queries(float *dists, uint32_t *res, const uint8_t *codes, const float *centers, const float *queries, int64_t q0, int64_t q1,
                      int N, int m, int K, int dim1codes, int dim1queries, int subdim) {
