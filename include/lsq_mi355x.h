@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 1500
+#define LSQ_VERSION 1600
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -562,6 +562,48 @@ LSQ_API int lsq_encode_viterbi_dev(lsq_ctx *ctx, const float *d_X, const float *
  * Host form: B m x n Int16 1-based; _dev: codes [n][m] uint8 0-based.  h must be 256. */
 LSQ_API int lsq_assign_codewords(lsq_ctx *ctx, const float *X, const float *K, int d, int64_t n, int m, int h, int16_t *B, float *minval);
 LSQ_API int lsq_assign_codewords_dev(lsq_ctx *ctx, const float *d_X, const float *d_K, int d, int64_t n, int m, int h, uint8_t *d_B, float *d_minval);
+
+/* ---- the beam-search encoder on resident codebooks (csrc/lsq_beam.hip; since v1600) -----------------------------------------------------------
+ * THE REFERENCE HAS NO COUNTERPART.  It stands beside the random start of every encode there -- randinit, src/encodings/encode_icm.jl:55-70 and
+ * demos/demo_lsq_gpu.jl:46, which its codes can replace as the B0 of lsq_encode_icm(_dev) -- and beside the chain's exact DP, src/encodings/
+ * encode_chain.jl:2-89 (lsq_encode_viterbi), which it generalises from the m - 1 adjacent pair tables to all of them: the classical encoder of additive
+ * quantisation and of residual quantisers, beam search over the full pair tables.  Deterministic, no RNG.  Per vector i, with U = what lsq_get_unaries
+ * returns, T = what lsq_get_binaries returns, the visiting order o_0 .. o_{m-1} (a permutation of 0 .. m-1; NULL = ascending) and beam width L:
+ *   stage 0       candidates v(0, a) = U[o_0][i][a];
+ *   stage t >= 1  for every live beam p in rank order, score S_p and codes b^p:  s = U[o_t][i][.];  then for r = 0 .. t-1 in stage order
+ *                 s[a] = s[a] + T[o_t][o_r][b^p_{o_r}][a]  (plain f32 adds, never fused);  then v(p, a) = S_p + s[a], one rounded add;
+ *   selection     the min(L, L_t * 256) smallest triples (v, p, a) in lexicographic order become the next beams, ranked in that order (ties: the smaller
+ *                 parent rank, then the smaller code); a child's score is v, its codes are the parent's plus b_{o_t} = a;
+ *   output        the codes of the rank-0 beam after stage m - 1 and, optionally, its score S_0 (f32): ||x||^2 + S_0 is the vector's veccost up to rounding.
+ * Inputs are finite; nothing is promised about NaN except that every code written lies in 0 .. 255.  tests/beam_check.py restates this in numpy; the
+ * kernel returns its codes and score bits.
+ * The handle: lsq_encoder_create COPIES the codebooks ([m*h][d]; host memory, or device memory with on_device = 1) and builds ||c||^2 and the m x m pair
+ * tables ONCE; it owns all its scratch (tables, one chunk's unaries, staging), so calls on it and calls on the context do not disturb each other -- the
+ * context's table cache and chunk state are untouched -- and neither do two encoders of one context.  It runs on the context's device and on the stream the
+ * context is bound to at each call; the context must outlive it; like the context it serves one host thread at a time.  chunk: vectors per pass (0 = the
+ * default 65 536: 512 MB of unaries at m = 8).
+ * lsq_encoder_beam: X [n][d] float32 (x_u8 = 0) or uint8 (x_u8 = 1: the un-widened rows of a .bvecs set; the bits of the f32 call on the widened rows).
+ *   on_device = 0: X, codes, score are HOST buffers, codes int16 1-BASED [n][m] (the boundary's type, as in lsq_encode_viterbi);
+ *   on_device = 1: device buffers, codes uint8 0-based [n][m] -- exactly the dB0 of lsq_encode_icm_dev.
+ *   order: m int32 in HOST memory in both forms (or NULL), checked before any launch.  score: [n] float32 or NULL.
+ * LSQ_EINVAL with nothing launched: a null handle, description or pointer (X / codes with n > 0), h != 256, m outside 1 .. 16, d < 1, chunk < 0, beam
+ * outside 1 .. 32, n < 0, an order that is not a permutation.  n = 0 is LSQ_OK. */
+typedef struct lsq_encoder lsq_encoder;
+typedef struct lsq_encoder_desc {
+    int d, m, h;
+    const float *codebooks;      /* [m*h][d] */
+    int on_device;
+    int64_t chunk;               /* vectors per pass, 0 = default */
+} lsq_encoder_desc;
+typedef struct lsq_encoder_info {        /* the last lsq_encoder_beam call */
+    int64_t vectors, chunks;
+    int64_t beam;
+    double unaries_ms, beam_ms;  /* with the context's option "profile" = 1: the unary GEMMs; the beam kernel */
+} lsq_encoder_info;
+LSQ_API int lsq_encoder_create(lsq_encoder **out, lsq_ctx *ctx, const lsq_encoder_desc *desc);
+LSQ_API int lsq_encoder_destroy(lsq_encoder *en);
+LSQ_API int lsq_encoder_beam(lsq_encoder *en, const void *X, int x_u8, int64_t n, int beam, const int32_t *order, void *codes, float *score, int on_device);
+LSQ_API int lsq_encoder_get_info(lsq_encoder *en, lsq_encoder_info *out);
 
 /* ---- PQ / OPQ training resident on the device: cluster means and k-means++ seeding (csrc/lsq_kmeans.hip; since v1100) -------------------------
  * Both steps run for all m sub-spaces of a vector set in one call.  The sub-space structure is the cover map dim2C of the structured update above (d x m

@@ -60,6 +60,14 @@ class IndexStats(_Struct):
                 ("scan_ms", C.c_double), ("gather_ms", C.c_double), ("select_ms", C.c_double)]
 
 
+class EncoderDesc(_Struct):
+    _fields_ = [("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("codebooks", C.c_void_p), ("on_device", C.c_int), ("chunk", C.c_int64)]
+
+
+class EncoderInfo(_Struct):
+    _fields_ = [("vectors", C.c_int64), ("chunks", C.c_int64), ("beam", C.c_int64), ("unaries_ms", C.c_double), ("beam_ms", C.c_double)]
+
+
 class Q16SnapshotNode(_Struct):
     _fields_ = [("loU", C.c_float), ("invD", C.c_float), ("D", C.c_float), ("hiq", C.c_float), ("window", C.c_int32), ("pad_", C.c_int32),
                 ("slack", C.c_double)]
@@ -141,6 +149,11 @@ SIGNATURES = {
     "lsq_index_knn": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "lsq_index_get_knn_info": (_i, [_vp, C.POINTER(IndexKnnInfo)]),
     "lsq_knn_exact_u8_cpu": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i]),
+    # the beam-search encoder on resident codebooks (since v1600)
+    "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
+    "lsq_encoder_destroy": (_i, [_vp]),
+    "lsq_encoder_beam": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _i]),
+    "lsq_encoder_get_info": (_i, [_vp, C.POINTER(EncoderInfo)]),
     "lsq_quantize_norms": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "lsq_quantize_norms_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "lsq_update_codebooks": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _vp]),

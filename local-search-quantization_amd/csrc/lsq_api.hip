@@ -837,6 +837,135 @@ extern "C" int lsq_index_get_stats(lsq_index *ix, lsq_index_stats *out) {
     return LSQ_OK;
 }
 
+// ---- the beam-search encoder on resident codebooks (lsq_beam.hip): a handle with its own copy of the codebooks, ||c||^2 and pair tables built once, and its own
+// scratch.  Nothing of the context is read but its device, its stream and option "profile"; nothing of it is written --------------------------------------------
+struct lsq_encoder {
+    lsq_ctx *ctx = nullptr;
+    int d = 0, m = 0;
+    int64_t chunk = 65536;
+    DevBuf K, sci, T;                                  // the codebooks' copy, ||c||^2, T[j][k][b][a] = 2 <c_kb, c_ja>
+    DevBuf U;                                          // one chunk's row-major f32 unary planes [m][cn][256]
+    DevBuf sX, sCodes, sScore;                         // staging of host-buffer calls: a chunk's rows, its int16 codes, its scores
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    lsq_encoder_info info{};
+};
+
+extern "C" int lsq_encoder_destroy(lsq_encoder *en) {
+    if (!en) return LSQ_OK;
+    (void)hipSetDevice(en->ctx->device);
+    (void)hipStreamSynchronize(en->ctx->stream);
+    DevBuf *bufs[] = {&en->K, &en->sci, &en->T, &en->U, &en->sX, &en->sCodes, &en->sScore};
+    for (DevBuf *b : bufs) b->release();
+    for (hipEvent_t e : en->ev) if (e) (void)hipEventDestroy(e);
+    delete en;
+    return LSQ_OK;
+}
+
+static int encoder_build(lsq_encoder *en, const float *codebooks, int on_device) {
+    hipStream_t s = en->ctx->stream;
+    const int mh = en->m * LSQ_H;
+    LSQ_TRY(en->K.ensure(sizeof(float) * (size_t)mh * en->d));
+    LSQ_TRY(en->sci.ensure(sizeof(float) * (size_t)mh));
+    LSQ_TRY(en->T.ensure(sizeof(float) * (size_t)mh * mh));
+    LSQ_HIP(hipMemcpyAsync(en->K.p, codebooks, sizeof(float) * (size_t)mh * en->d, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    // the path's own numbers: ||c||^2 as the unary GEMM adds it, and the table GEMM of prepare_tables (rows (k, b), columns (j, a))
+    LSQ_TRY(lsq_launch_sqnorms(s, en->K.as<float>(), mh, en->d, en->sci.as<float>()));
+    LSQ_TRY(lsq_launch_chain_gemm(s, en->K.as<float>(), en->K.as<float>(), nullptr, 2.0f, mh, mh, en->d, LSQ_H, (int64_t)en->m * LSQ_H * LSQ_H, LSQ_H,
+                                  en->T.as<float>(), 0, mh, 0));
+    LSQ_HIP(hipStreamSynchronize(s));
+    return LSQ_OK;
+}
+
+extern "C" int lsq_encoder_create(lsq_encoder **out, lsq_ctx *c, const lsq_encoder_desc *desc) {
+    if (!out) { lsq_set_error("lsq_encoder_create: null out pointer"); return LSQ_EINVAL; }
+    *out = nullptr;
+    if (!c || !desc) { lsq_set_error("lsq_encoder_create: null %s", c ? "description" : "context"); return LSQ_EINVAL; }
+    if (desc->h != LSQ_H || desc->m < 1 || desc->m > LSQ_MAX_M || desc->d < 1) {
+        lsq_set_error("lsq_encoder_create: needs h == 256, 1 <= m <= 16 and d >= 1 (got h=%d m=%d d=%d)", desc->h, desc->m, desc->d);
+        return LSQ_EINVAL;
+    }
+    if (desc->chunk < 0) { lsq_set_error("lsq_encoder_create: needs chunk >= 0 (got %lld)", (long long)desc->chunk); return LSQ_EINVAL; }
+    if (!desc->codebooks) { lsq_set_error("lsq_encoder_create: null codebooks"); return LSQ_EINVAL; }
+    LSQ_TRY(use_device(c));
+    lsq_encoder *en = new lsq_encoder();
+    en->ctx = c;
+    en->d = desc->d; en->m = desc->m;
+    if (desc->chunk > 0) en->chunk = desc->chunk;
+    const int rc = encoder_build(en, desc->codebooks, desc->on_device);
+    if (rc != LSQ_OK) { (void)lsq_encoder_destroy(en); return rc; }
+    *out = en;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_encoder_beam(lsq_encoder *en, const void *X, int x_u8, int64_t n, int beam, const int32_t *order, void *codes, float *score,
+                                int on_device) {
+    if (!en) { lsq_set_error("lsq_encoder_beam: null encoder"); return LSQ_EINVAL; }
+    if (n < 0 || beam < 1 || beam > 32) { lsq_set_error("lsq_encoder_beam: needs n >= 0 and 1 <= beam <= 32 (got n=%lld beam=%d)", (long long)n, beam); return LSQ_EINVAL; }
+    if (n > 0 && (!X || !codes)) { lsq_set_error("lsq_encoder_beam: null pointer"); return LSQ_EINVAL; }
+    const int m = en->m, d = en->d;
+    uint8_t ord[LSQ_MAX_M];
+    unsigned seen = 0;
+    for (int t = 0; t < m; ++t) {
+        const int32_t o = order ? order[t] : t;
+        if (o < 0 || o >= m || (seen >> o & 1u)) { lsq_set_error("lsq_encoder_beam: the visiting order is not a permutation of 0 .. %d", m - 1); return LSQ_EINVAL; }
+        seen |= 1u << o;
+        ord[t] = (uint8_t)o;
+    }
+    if (n == 0) return LSQ_OK;
+    lsq_ctx *c = en->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    const bool timed = c->profile != 0;
+    if (timed) for (hipEvent_t &e : en->ev) if (!e) LSQ_HIP(hipEventCreate(&e));
+    const size_t elem = x_u8 ? 1 : sizeof(float);
+    lsq_encoder_info info{};
+    info.vectors = n; info.beam = beam;
+    for (int64_t off = 0; off < n; off += en->chunk) {
+        const int64_t cn = std::min<int64_t>(en->chunk, n - off);
+        const char *Xc = static_cast<const char *>(X) + (size_t)off * d * elem;
+        void *out_codes = on_device ? static_cast<void *>(static_cast<uint8_t *>(codes) + off * m) : nullptr;
+        float *out_score = on_device && score ? score + off : nullptr;
+        if (!on_device) {
+            LSQ_TRY(en->sX.ensure((size_t)cn * d * elem));
+            LSQ_TRY(en->sCodes.ensure(sizeof(int16_t) * (size_t)cn * m));
+            if (score) LSQ_TRY(en->sScore.ensure(sizeof(float) * (size_t)cn));
+            LSQ_HIP(hipMemcpyAsync(en->sX.p, Xc, (size_t)cn * d * elem, hipMemcpyHostToDevice, s));
+            Xc = en->sX.as<char>(); out_codes = en->sCodes.p; out_score = score ? en->sScore.as<float>() : nullptr;
+        }
+        LSQ_TRY(en->U.ensure(sizeof(float) * (size_t)m * (size_t)cn * LSQ_H));
+        if (timed) LSQ_HIP(hipEventRecord(en->ev[0], s));
+        // row-major planes U[(j cn + i) 256 + a] = chain(x_i[t] * -2 K[j, a][t]) + ||c_ja||^2: the bits of lsq_get_unaries
+        if (x_u8) LSQ_TRY(lsq_launch_chain_gemm(s, reinterpret_cast<const uint8_t *>(Xc), en->K.as<float>(), en->sci.as<float>(), -2.0f, cn, m * LSQ_H, d, LSQ_H,
+                                                cn * (int64_t)LSQ_H, LSQ_H, en->U.as<float>(), 0, cn, 0));
+        else LSQ_TRY(lsq_launch_chain_gemm(s, reinterpret_cast<const float *>(Xc), en->K.as<float>(), en->sci.as<float>(), -2.0f, cn, m * LSQ_H, d, LSQ_H,
+                                           cn * (int64_t)LSQ_H, LSQ_H, en->U.as<float>(), 0, cn, 0));
+        if (timed) LSQ_HIP(hipEventRecord(en->ev[1], s));
+        LSQ_TRY(lsq_launch_beam(s, en->U.as<float>(), en->T.as<float>(), cn, m, beam, ord, out_codes, on_device ? 0 : 1, out_score));
+        if (timed) {
+            LSQ_HIP(hipEventRecord(en->ev[2], s));
+            LSQ_HIP(hipEventSynchronize(en->ev[2]));
+            float a = 0, b = 0;
+            LSQ_HIP(hipEventElapsedTime(&a, en->ev[0], en->ev[1]));
+            LSQ_HIP(hipEventElapsedTime(&b, en->ev[1], en->ev[2]));
+            info.unaries_ms += a; info.beam_ms += b;
+        }
+        if (!on_device) {        // in stream order: the next chunk's kernels overwrite the staging only after these copies
+            LSQ_HIP(hipMemcpyAsync(static_cast<int16_t *>(codes) + off * m, en->sCodes.p, sizeof(int16_t) * (size_t)cn * m, hipMemcpyDeviceToHost, s));
+            if (score) LSQ_HIP(hipMemcpyAsync(score + off, en->sScore.p, sizeof(float) * (size_t)cn, hipMemcpyDeviceToHost, s));
+        }
+        info.chunks += 1;
+    }
+    if (!on_device) LSQ_HIP(hipStreamSynchronize(s));
+    en->info = info;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_encoder_get_info(lsq_encoder *en, lsq_encoder_info *out) {
+    if (!en || !out) { lsq_set_error("lsq_encoder_get_info: null argument"); return LSQ_EINVAL; }
+    *out = en->info;
+    return LSQ_OK;
+}
+
 extern "C" int lsq_synchronize(lsq_ctx *c) {
     LSQ_TRY(use_device(c));
     LSQ_HIP(hipStreamSynchronize(c->stream));

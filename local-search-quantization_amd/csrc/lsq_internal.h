@@ -265,6 +265,10 @@ int lsq_launch_synth_codebooks(hipStream_t s, uint64_t seed, int m, int h, int d
 int lsq_launch_viterbi(hipStream_t s, const float *U, const float *T, int64_t n, int m, uint8_t *codes);            // encode_chain.jl:2-89
 int lsq_launch_unary_argmin(hipStream_t s, const float *U, int64_t n, int m, uint8_t *codes, float *minval);     // PQ.jl:12-41, kmeans.jl:6-75; minval optional [n][m]
 
+// ---- the beam-search encoder (lsq_beam.hip): U, T as above; order[m] HOST bytes, checked to be a permutation of 0 .. m-1 before the launch; codes: tight
+// [n][m] u8 0-based, or (codes_i16) int16 1-BASED [n][m]; score optional [n] (the rank-0 beam's S: ||x||^2 + S is the vector's cost) ----------------------------
+int lsq_launch_beam(hipStream_t s, const float *U, const float *T, int64_t n, int m, int L, const uint8_t *order, void *codes, int codes_i16, float *score);
+
 // ---- device ADC scan (lsq_adc.hip) ----------------------------------------------------------------------------------------------------
 // distance keys of the scans' records: order-preserving (a < b  <=>  key(a) < key(b)), NaN last
 __device__ inline uint32_t lsq_adc_key(float v) {

@@ -134,7 +134,7 @@ class Engine:
         h = C.c_void_p()
         self._check(self._L.lsq_create(C.byref(h), int(device)))
         self._h = h
-        self._indexes = weakref.WeakSet()             # the Index objects made on this context: closed before it
+        self._indexes = weakref.WeakSet()             # the handles made on this context (Index, Encoder objects): closed before it
         self.device = int(device)
         if chunk is not None:
             self.set_option("chunk", int(chunk))
@@ -151,7 +151,7 @@ class Engine:
     # -- lifetime -------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
-            for ix in list(getattr(self, "_indexes", ())):      # an index needs its context to free what it holds on the device
+            for ix in list(getattr(self, "_indexes", ())):      # an index or encoder needs its context to free what it holds on the device
                 ix.close()
             self._L.lsq_destroy(self._h)
             self._h = None
@@ -366,6 +366,16 @@ class Engine:
         """The same on device-resident torch tensors, BORROWED: the index keeps references to them; searches take and return tensors.  base: a 2-d
         tensor or a view of one with unit column stride, at any byte offset."""
         return Index(self, dcodes, dK, dnorms, m, base, h, d, on_device=True)
+
+    # -- (1e) the beam-search encoder on resident codebooks ----------------------------------
+    def encoder(self, K, m, chunk=0, h=H):
+        """An Encoder of HOST codebooks K (m*h,d), copied once: ||c||^2 and the pair tables are built here, not per call.  Its beam() takes and returns
+        host arrays.  chunk: vectors per pass (0 = the library's default)   [lsq_encoder_create]"""
+        return Encoder(self, K, m, chunk, h, on_device=False)
+
+    def encoder_dev(self, dK, m, chunk=0, h=H):
+        """The same from a device tensor dK (copied as well); its beam() takes and returns torch tensors, on torch's current stream."""
+        return Encoder(self, dK, m, chunk, h, on_device=True)
 
     def quantize_norms(self, B, K, cbnorms, m, h=H):
         """B (n,m) int16 1-based, K (m*h,d), cbnorms (<= 256,): host arrays.
@@ -712,6 +722,69 @@ class Index:
             self._L.lsq_index_destroy(self._h)
         self._h = None
         self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+# -- the beam-search encoder (made by Engine.encoder / Engine.encoder_dev) ------------------------
+
+class Encoder:
+    """Beam search over the full pair tables on codebooks resident on an Engine's device   [lsq_encoder_*]: deterministic codes that can replace the
+    random start of an ILS encode.  Made by Engine.encoder (host arrays in and out) or Engine.encoder_dev (torch tensors in and out)."""
+
+    _side = property(lambda self: _DEVICE if self._dev else _HOST)
+
+    def __init__(self, engine, K, m, chunk, h, on_device):
+        self._eng, self._L, self._dev, self._h = engine, engine._L, bool(on_device), None
+        side = self._side
+        K = side.take(K, _F32, "K")
+        _shapes(("K", K, (int(m) * h, None)))
+        desc = _lib.EncoderDesc()
+        desc.d, desc.m, desc.h, desc.codebooks, desc.on_device, desc.chunk = int(K.shape[1]), int(m), int(h), side.ptr(K), int(self._dev), int(chunk)
+        self.d, self.m = int(K.shape[1]), int(m)
+        handle = C.c_void_p()
+        engine._call(side, "lsq_encoder_create", engine._h, C.byref(desc), h=C.byref(handle))      # the codebooks are copied: K is not kept
+        self._h = handle
+        engine._indexes.add(self)
+
+    def beam(self, X, L, order=None, want_score=False):
+        """X (n,d) float32 or uint8 rows (the un-widened bytes of a .bvecs set: the bits of the float32 call), beam width 1 <= L <= 32, order: the
+        codebooks' visiting order (a permutation of range(m), host integers; None: ascending).
+        -> codes (n,m): int16 1-based (host) / uint8 0-based (device: the B0 of encode_icm_dev) [, score (n,) float32: ||x||^2 + score is the
+        vector's veccost]   [lsq_encoder_beam]"""
+        side = self._side
+        X, u8 = side.take_x(X, "X")
+        _shapes(("X", X, (None, self.d)))
+        n, p = X.shape[0], side.ptr
+        o = None if order is None else _HOST.take(order, _I32, "order").reshape(-1)
+        if o is not None:
+            _shapes(("order", o, (self.m,)))
+        codes = side.new((n, self.m), side.codes, X)
+        score = side.new(n, _F32, X) if want_score else None
+        self._eng._call(side, "lsq_encoder_beam", p(X), int(u8), n, int(L), _array_address(o), p(codes), p(score), int(self._dev), h=self._h)
+        return (codes, score) if want_score else codes
+
+    def info(self):
+        """the last beam call: vectors, chunks, beam, unaries_ms / beam_ms (with profile=True)"""
+        st = _lib.EncoderInfo()
+        self._eng._call(_HOST, "lsq_encoder_get_info", C.byref(st), h=self._h)
+        return st.as_dict()
+
+    def close(self):
+        # as Index.close: Engine.close closes its encoders first; without a context the handle is dropped, not destroyed
+        if getattr(self, "_h", None) and getattr(self._eng, "_h", None):
+            self._L.lsq_encoder_destroy(self._h)
+        self._h = None
 
     def __del__(self):
         try:

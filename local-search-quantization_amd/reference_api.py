@@ -119,6 +119,23 @@ def qerror(X, B, C, *, engine=None):
     return eng.qerror(_X_of(X), _B_of(B), _K_of(C), m, h=h)
 
 
+def beam_order(C):
+    """The visiting order of encode_beam that starts with the codebooks that carry the most energy: 0-based codebook indices by descending mean
+    ||c||^2 (float64 means; equal means keep their ascending order)."""
+    e = [float((np.asarray(Cj, dtype=np.float64) ** 2).sum(axis=0).mean()) for Cj in C]
+    return np.argsort(-np.asarray(e), kind="stable").astype(np.int32)
+
+
+def encode_beam(X, C, L, order=None, *, engine=None):
+    """Beam search of width L over the full pair tables (no counterpart in the reference; a deterministic start that can stand in for randinit).
+    X d x n Float32 (or the UInt8 matrix bvecs_read returns), C the m codebooks (d x h), order: 0-based visiting order (None: ascending; beam_order(C):
+    by energy) -> B m x n Int16 1-based."""
+    eng = engine or default_engine()
+    m, d, h = _dims(C)
+    with eng.encoder(_K_of(C), m, h=h) as enc:
+        return enc.beam(_X8_of(X), L, order=order).T
+
+
 def linscan_lsq(B, X, C, dbnorms, R, k=10000, *, nthreads=0, engine=None):
     """Linear scan with LSQ codes + separately stored norms  (src/linscan/Linscan.jl:46-73).
     B (m, n) uint8 0-based; X (d, nq) queries; C list of (d, h); dbnorms (n,); R (d, d) rotation.

@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--init beam:L] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -10,6 +10,9 @@ the codes and codebooks stay in HBM between the stages; the rest of the flow is 
 query .bvecs files and an .ivecs ground truth side by side), else the synthetic stand-in quantised to bytes -- and is handed to encode_icm_cuda as
 uint8 (lsq_encode_icm_u8: d bytes per vector over the bus and in HBM).  The ground truth is exact k-NN of the 8-bit queries over the un-widened 8-bit base
 (lsq_index_knn: integer distances, the f32 chain's bits).  Training set and scan queries are widened: the trainers and the scan take f32.
+
+--init beam:L: the base set's initial codes come from the beam-search encoder (encode_beam, width L, codebooks visited by descending energy: beam_order)
+instead of randinit (demos/demo_lsq_gpu.jl:46); the rest of the flow is unchanged.  Default: randinit, as the reference.
 
 --rerank L: after the ADC scan, the two-stage search on a resident index (Engine.index: the codes, norms, codebooks and the base rows uploaded once):
 the scan's L nearest re-ordered by exact distance to the stored vectors -- f32 rows, or the un-widened 8-bit rows with --bvecs -- and the recall curve of the
@@ -121,6 +124,13 @@ def main():
         at = argv.index("--rerank")
         shortlist = int(argv[at + 1])
         del argv[at:at + 2]
+    init = "random"
+    if "--init" in argv:
+        at = argv.index("--init")
+        init = argv[at + 1]
+        del argv[at:at + 2]
+        if init != "random" and not (init.startswith("beam:") and init[5:].isdigit()):
+            raise SystemExit("--init takes `random` or `beam:L`, got %r" % init)
     args = [a for a in argv if a not in ("--resident", "--bvecs")]
     resident, bvecs = "--resident" in argv, "--bvecs" in argv
     real = bool(os.environ.get("LSQ_DATA_DIR"))
@@ -140,7 +150,13 @@ def main():
             C, B, R, err = lsq.train_chainq(x_train, m, h, R, B, C, niter, engine=eng, device_update=True)
         print("Error after ChainQ is %e" % err[-1])
         C, B, cbnorms, B_norms, obj = lsq.train_lsq(x_train, m, h, R, B, C, niter, ilsiter, icmiter, randord, min(npert, m), True)
-    B_base = lsq.randinit(x_base.shape[1], m, h)
+    if init.startswith("beam:"):
+        t0 = time.perf_counter()
+        with lsq.Engine(0) as eng:
+            B_base = lsq.encode_beam(x_base, C, int(init[5:]), order=lsq.beam_order(C), engine=eng)
+        print("Initial codes of the base set by beam search of width %s: %.3f s (host buffers)" % (init[5:], time.perf_counter() - t0))
+    else:
+        B_base = lsq.randinit(x_base.shape[1], m, h)
     t0 = time.perf_counter()
     Bs, objs = lsq.encode_icm_cuda(x_base, B_base, C, [16], icmiter, min(npert, m), randord, 2, True)
     dt = time.perf_counter() - t0
