@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 1600
+#define LSQ_VERSION 1700
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -469,6 +469,63 @@ LSQ_API int lsq_index_get_knn_info(lsq_index *ix, lsq_index_knn_info *out);
  * ids uint32 0-based.  LSQ_EINVAL as lsq_knn_exact_cpu. */
 LSQ_API int lsq_knn_exact_u8_cpu(float *dists, uint32_t *ids, const void *base, int base_u8, const void *queries, int queries_u8, int n, int nq, int d,
                                  int ldb, int ldq, int nn, int nthreads);
+
+/* ---- (3g) inverted lists (IVF) on the resident index: a search that reads only the probed lists (since v1700) ------------------------------------
+ * THE REFERENCE HAS NO COUNTERPART: linscan_lsq (src/linscan/Linscan.jl:46-73) reads every code for every query.  Here a coarse partition -- nlist
+ * centroids and the list of every row, both the caller's (the library neither trains nor assigns them) -- is laid over an index that holds codes, and
+ * a query reads the rows of its nprobe nearest lists alone.
+ *   probed lists   the nprobe smallest (dist, list id) pairs, dist = lsq_knn_exact's distance of the query's q_coarse row to the centroid (f32 direct
+ *                  form, dimensions ascending, every op rounded, no FMA), ties to the smaller id, NaN last: the exact search with the centroids as base.
+ *   distance       of a row i of a probed list l: lsq_linscan's bits, (((0 + table[0 h + b_i0]) + table[1 h + b_i1]) + ...) + dbnorms[i], the tables built
+ *                  from the query's q_scan row; with LSQ_IVF_ADD_COARSE one more rounded add, (... + dbnorms[i]) + dist(q, l) -- what residual codes need
+ *                  (encode x - c_l, store |r^|^2 + 2<c_l, r^> as dbnorms: the sum is |q - c_l - r^|^2).
+ *   result         per query the nn smallest (dist, id) pairs over all rows of its probed lists, lexicographic; ids are the ORIGINAL row ids, 1-BASED int32
+ *                  as in lsq_index_search; ties to the smaller original id; NaN after every number; where the probed lists hold fewer than nn rows the
+ *                  remaining entries are (+inf, 0), after everything, NaN included (lsq_index_rerank's id outside the base).  Empty lists are legal.
+ *   shortlist      0: the result above.  L >= nn: the result above for L, then lsq_index_rerank's stage two on those ids with q_exact: exact distances;
+ *                  the (+inf, 0) entries are never dereferenced and stay last.  L <= 2^28.
+ * With nprobe = nlist and no flag the result is lsq_index_search(shortlist = 0)'s bit for bit.  lsq_index_search, _rerank and _knn are unchanged by lists.
+ * lsq_index_set_lists builds the inverted layout on the device -- rows grouped by list and, within a list, ascending by original id: one radix sort of
+ * (list, row) keys, no atomic decides a position, the same bits on every call -- as OWNED copies (m + 8 bytes per row: codes, norm, original id; whether
+ * the index borrows its codes or not), plus the centroids and nlist + 1 offsets.  It may be called again to replace the lists; a call that fails its
+ * range check (made on the device before anything is laid out) leaves the former lists in place.  centroids / list_of_row: host (on_device = 0) or device.
+ * lsq_index_search_ivf: q_scan, q_coarse (NULL = q_scan), q_exact (read when shortlist > 0) [nq][ldq] f32; dists / ids [nq][nn]; on_device as in
+ * lsq_index_search.  Two roads, the same results: every record of every probed row written and sorted (LSQ_IVF_EVERY_RECORD forces it; it is also the
+ * fallback), or the HEAD -- the first probed lists, in rank order, that hold nn rows together -- written in full, its nn-th record an exact upper bound
+ * tau of the answer's nn-th, and the other lists appending only records with !(dist > tau) to 8 nn + 256 further slots; a query that overflows them is
+ * redone on the first road.  LSQ_IVF_TEST_BATCH is a test hook: batches of at most 8 queries (lsq_ivf_info.batch_queries says what a call used).
+ * Runs on the context's stream with the index's own scratch; options "linscan_exhaustive" / "linscan_rank" act on the coarse search, "profile" fills
+ * the four times.
+ * LSQ_EINVAL, nothing launched: a null handle or pointer, an index without codes, a search before set_lists, nprobe outside 1 .. nlist, nlist outside
+ * 1 .. 2^24, nn < 1, shortlist neither 0 nor >= nn, shortlist > 0 without base rows, a flag outside the three.  A list_of_row entry outside [0, nlist)
+ * is LSQ_EINVAL too, found by the one kernel that reads the entries, before any of them is used as an offset. */
+typedef struct lsq_ivf_desc {
+    int nlist;
+    const float *centroids;        /* [nlist][d] */
+    const int32_t *list_of_row;    /* [n], 0-based list of every row */
+    int on_device;
+} lsq_ivf_desc;
+enum { LSQ_IVF_ADD_COARSE = 1, LSQ_IVF_EVERY_RECORD = 2, LSQ_IVF_TEST_BATCH = 4 };
+typedef struct lsq_ivf_info {            /* the last lsq_index_search_ivf call */
+    int64_t queries, probed_rows;        /* queries answered; rows of their probed lists, summed */
+    int64_t records;                     /* records written to the sort's input, padding included, both roads */
+    int64_t threshold_queries;           /* queries answered by the thresholded road */
+    int64_t fallback_queries;            /* queries whose tail overflowed: redone with every record */
+    int64_t batches;
+    int64_t batch_queries, tail_capacity;        /* the plan: queries per batch (the larger of the two roads'), tail slots per query */
+    double coarse_ms, lut_ms, scan_ms, select_ms;        /* with option "profile" = 1 */
+} lsq_ivf_info;
+LSQ_API int lsq_index_set_lists(lsq_index *ix, const lsq_ivf_desc *desc);
+LSQ_API int lsq_index_search_ivf(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_coarse, const float *q_exact, int nq, int ldq,
+                                 int nprobe, int shortlist, int nn, int flags, int on_device);
+LSQ_API int lsq_index_get_ivf_info(lsq_index *ix, lsq_ivf_info *out);
+/* The host checker and engine-less road (no context, std::thread workers, nthreads 0 = all): the index's ingredients as plain arrays -- codes [n][m],
+ * codebooks [m*h][d], dbnorms [n], centroids [nlist][d], list_of_row [n] -- and the contract's result for shortlist = 0.  Tables and distances by
+ * lsq_linscan_aqd_query_extra_byte's arithmetic, coarse distances by lsq_knn_exact_cpu's.  It walks the rows in their original order and knows nothing of
+ * the inverted layout.  q_coarse NULL = q_scan.  LSQ_EINVAL as above, and for h outside 1 .. 256, m < 1, d < 1, n < 1, nq < 0, ldq < d. */
+LSQ_API int lsq_ivf_search_cpu(float *dists, int *ids, const uint8_t *codes, const float *codebooks, const float *dbnorms, const float *centroids,
+                               const int32_t *list_of_row, const float *q_scan, const float *q_coarse, int n, int m, int h, int d, int nlist, int nq,
+                               int ldq, int nprobe, int nn, int flags, int nthreads);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB      src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

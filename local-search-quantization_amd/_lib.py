@@ -60,6 +60,19 @@ class IndexStats(_Struct):
                 ("scan_ms", C.c_double), ("gather_ms", C.c_double), ("select_ms", C.c_double)]
 
 
+class IvfDesc(_Struct):
+    _fields_ = [("nlist", C.c_int), ("centroids", C.c_void_p), ("list_of_row", C.c_void_p), ("on_device", C.c_int)]
+
+
+class IvfInfo(_Struct):
+    _fields_ = [("queries", C.c_int64), ("probed_rows", C.c_int64), ("records", C.c_int64), ("threshold_queries", C.c_int64),
+                ("fallback_queries", C.c_int64), ("batches", C.c_int64), ("batch_queries", C.c_int64), ("tail_capacity", C.c_int64),
+                ("coarse_ms", C.c_double), ("lut_ms", C.c_double), ("scan_ms", C.c_double), ("select_ms", C.c_double)]
+
+
+IVF_ADD_COARSE, IVF_EVERY_RECORD, IVF_TEST_BATCH = 1, 2, 4
+
+
 class EncoderDesc(_Struct):
     _fields_ = [("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("codebooks", C.c_void_p), ("on_device", C.c_int), ("chunk", C.c_int64)]
 
@@ -149,6 +162,11 @@ SIGNATURES = {
     "lsq_index_knn": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "lsq_index_get_knn_info": (_i, [_vp, C.POINTER(IndexKnnInfo)]),
     "lsq_knn_exact_u8_cpu": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i]),
+    # inverted lists on the index (since v1700), and their host checker
+    "lsq_index_set_lists": (_i, [_vp, C.POINTER(IvfDesc)]),
+    "lsq_index_search_ivf": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
+    "lsq_index_get_ivf_info": (_i, [_vp, C.POINTER(IvfInfo)]),
+    "lsq_ivf_search_cpu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),

@@ -524,6 +524,12 @@ int lsq_adc_select(lsq_adc_state **pst, hipStream_t s, const uint64_t *recs, uin
     return LSQ_OK;
 }
 
+// the tables of queries q0 .. q0 + nqb - 1 (or qsel[0 .. nqb)) in adc_lut_kernel's tile layout, for a scan outside this file (lsq_ivf.hip)
+int lsq_adc_launch_lut(hipStream_t s, const lsq_search_input &in, const int *qsel, int q0, int nqb, float *LUT) {
+    if (lsq_adc_lut_qt(in.m) == 16) return launch_lut<16>(s, in, qsel, q0, nqb, LUT);
+    return launch_lut<8>(s, in, qsel, q0, nqb, LUT);
+}
+
 namespace {
 
 struct Plan { int ns, stride, r, cap; bool exhaustive; };
@@ -623,7 +629,7 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
     if (!P.exhaustive && opt.rank_override > 0) {    // test hook: a deliberately wrong threshold rank (forces the fallback road)
         P.r = opt.rank_override < P.ns ? opt.rank_override : P.ns;
     }
-    const bool wide = in.m <= 8;                     // 16 queries per block up to m = 8 (128 KiB of tables), 8 above
+    const bool wide = lsq_adc_lut_qt(in.m) == 16;    // 16 queries per block up to m = 8 (128 KiB of tables), 8 above
     const int64_t per_query = P.exhaustive ? n : (P.cap > P.ns ? P.cap : P.ns);
     // batches of queries: two key buffers of per_query entries each, at most ~2 GiB apiece, and hipcub counts items in int
     int64_t qb = (int64_t)(1u << 28) / per_query;

@@ -545,6 +545,8 @@ struct lsq_index {
     DevBuf short_d, short_i;                           // stage one's shortlist [nq][L]
     DevBuf s_qscan, s_qexact, s_cand, s_dists, s_ids;  // staging of host-buffer calls, and of scan queries whose rows are not d floats apart
     DevBuf nrm_x, nrm_q;                               // lsq_index_knn's integer road: uint32 squared norms of the rows and of the queries, refilled at every call
+    lsq_ivf_state *ivf = nullptr;                      // the inverted lists (lsq_ivf.hip): layout and scratch of THIS index; null until lsq_index_set_lists
+    DevBuf s_qcoarse;                                  // lsq_index_search_ivf's staging of host q_coarse rows
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     lsq_index_stats stats{};
     lsq_index_knn_info knn{};
@@ -555,9 +557,10 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     (void)hipSetDevice(ix->ctx->device);
     (void)hipStreamSynchronize(ix->ctx->stream);
     DevBuf *bufs[] = {&ix->own_codes, &ix->own_K, &ix->own_norms, &ix->own_base, &ix->rec_a, &ix->rec_b, &ix->seg, &ix->counter, &ix->short_d, &ix->short_i,
-                      &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q};
+                      &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q, &ix->s_qcoarse};
     for (DevBuf *b : bufs) b->release();
     lsq_adc_free(ix->adc);
+    lsq_ivf_free(ix->ivf);
     for (hipEvent_t e : ix->ev) if (e) (void)hipEventDestroy(e);
     delete ix;
     return LSQ_OK;
@@ -834,6 +837,75 @@ extern "C" int lsq_index_get_knn_info(lsq_index *ix, lsq_index_knn_info *out) {
 extern "C" int lsq_index_get_stats(lsq_index *ix, lsq_index_stats *out) {
     if (!ix || !out) { lsq_set_error("lsq_index_get_stats: null argument"); return LSQ_EINVAL; }
     *out = ix->stats;
+    return LSQ_OK;
+}
+
+// ---- inverted lists on the index (lsq_ivf.hip): the layout, then a search over each query's probed lists with stage two behind it ----------------------
+extern "C" int lsq_index_set_lists(lsq_index *ix, const lsq_ivf_desc *desc) {
+    if (!ix || !desc) { lsq_set_error("lsq_index_set_lists: null %s", ix ? "description" : "index"); return LSQ_EINVAL; }
+    if (!ix->codes) { lsq_set_error("lsq_index_set_lists: the index holds no codes"); return LSQ_EINVAL; }
+    if (desc->nlist < 1 || desc->nlist > (1 << 24)) { lsq_set_error("lsq_index_set_lists: needs 1 <= nlist <= 2^24 (got %d)", desc->nlist); return LSQ_EINVAL; }
+    if (!desc->centroids || !desc->list_of_row) { lsq_set_error("lsq_index_set_lists: null pointer"); return LSQ_EINVAL; }
+    LSQ_TRY(use_device(ix->ctx));
+    return lsq_ivf_set_lists(ix->ctx->stream, &ix->ivf, ix->codes, ix->norms, ix->n, ix->m, ix->d, desc);
+}
+
+extern "C" int lsq_index_search_ivf(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_coarse, const float *q_exact, int nq, int ldq,
+                                    int nprobe, int shortlist, int nn, int flags, int on_device) {
+    LSQ_TRY(index_call_check("lsq_index_search_ivf", ix, dists, ids, nq, ldq, nn));
+    if (!ix->codes) { lsq_set_error("lsq_index_search_ivf: the index holds no codes"); return LSQ_EINVAL; }
+    const int nlist = lsq_ivf_nlist(ix->ivf);
+    if (nlist < 1) { lsq_set_error("lsq_index_search_ivf: the index has no lists (call lsq_index_set_lists first)"); return LSQ_EINVAL; }
+    if (flags & ~(LSQ_IVF_ADD_COARSE | LSQ_IVF_EVERY_RECORD | LSQ_IVF_TEST_BATCH)) { lsq_set_error("lsq_index_search_ivf: unknown flags %d", flags); return LSQ_EINVAL; }
+    if (nprobe < 1 || nprobe > nlist) { lsq_set_error("lsq_index_search_ivf: needs 1 <= nprobe <= nlist (got nprobe=%d nlist=%d)", nprobe, nlist); return LSQ_EINVAL; }
+    if (shortlist < 0 || (shortlist > 0 && shortlist < nn)) { lsq_set_error("lsq_index_search_ivf: needs shortlist == 0 or shortlist >= nn (got shortlist=%d nn=%d)", shortlist, nn); return LSQ_EINVAL; }
+    const int L = shortlist > 0 ? shortlist : nn;
+    if (L > (1 << 28)) { lsq_set_error("lsq_index_search_ivf: needs nn and shortlist <= 2^28 (got %d)", L); return LSQ_EINVAL; }
+    if (shortlist > 0 && !ix->base) { lsq_set_error("lsq_index_search_ivf: a shortlist needs base rows, the index holds none"); return LSQ_EINVAL; }
+    if (!q_scan || (shortlist > 0 && !q_exact)) { lsq_set_error("lsq_index_search_ivf: null pointer"); return LSQ_EINVAL; }
+    if (nq == 0) return LSQ_OK;
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    const int d = ix->d;
+    if (!q_coarse) q_coarse = q_scan;
+    // the tables read query rows d floats apart; the coarse search and the re-rank read rows as they lie
+    const float *dqs = q_scan, *dqc = q_coarse, *dqe = q_exact;
+    int64_t ld = ldq, ldc = ldq, lde = ldq;
+    if (!on_device || ldq != d) LSQ_TRY(index_stage_rows(ix, ix->s_qscan, q_scan, nq, ldq, d, true, &dqs, &ld));
+    if (!on_device) LSQ_TRY(index_stage_rows(ix, ix->s_qcoarse, q_coarse, nq, ldq, d, false, &dqc, &ldc));
+    if (shortlist > 0 && !on_device) LSQ_TRY(index_stage_rows(ix, ix->s_qexact, q_exact, nq, ldq, d, false, &dqe, &lde));
+    float *out_d = dists;
+    int *out_i = ids;
+    if (!on_device) {
+        LSQ_TRY(ix->s_dists.ensure(sizeof(float) * (size_t)nq * nn));
+        LSQ_TRY(ix->s_ids.ensure(sizeof(int) * (size_t)nq * nn));
+        out_d = ix->s_dists.as<float>();
+        out_i = ix->s_ids.as<int>();
+    }
+    float *scan_d = out_d;
+    int *scan_i = out_i;
+    if (shortlist > 0) {
+        LSQ_TRY(ix->short_d.ensure(sizeof(float) * (size_t)nq * L));
+        LSQ_TRY(ix->short_i.ensure(sizeof(int) * (size_t)nq * L));
+        scan_d = ix->short_d.as<float>();
+        scan_i = ix->short_i.as<int>();
+    }
+    LSQ_TRY(lsq_ivf_search(s, ix->ivf, &ix->adc, ix->K, scan_d, scan_i, dqs, dqc, ldc, nq, nprobe, L, flags, c->search, c->profile));
+    // the scan's ids are 1-based; its (+inf, 0) entries are ids outside the base: never dereferenced, last
+    if (shortlist > 0) LSQ_TRY(index_rerank_dev(ix, out_d, out_i, dqe, lde, scan_i, nq, L, nn, 1));
+    if (!on_device) {
+        LSQ_HIP(hipMemcpyAsync(dists, out_d, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipMemcpyAsync(ids, out_i, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipStreamSynchronize(s));
+    }
+    ix->stats.queries += nq;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_ivf_info(lsq_index *ix, lsq_ivf_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_ivf_info: null argument"); return LSQ_EINVAL; }
+    lsq_ivf_get_info(ix->ivf, out);
     return LSQ_OK;
 }
 

@@ -338,6 +338,23 @@ int lsq_adc_idbits(int64_t n);
 int lsq_adc_select(lsq_adc_state **st, hipStream_t s, const uint64_t *recs, uint64_t *sorted, int *seg, const unsigned *count, int *fail, const int *qsel,
                    int q0, int nqb, int cap, int nn, float *dists, int *idx, int idbits, int end_bit, int id_sub);
 
+// adc_lut_kernel's tables for another scan (lsq_ivf.hip): LUT[(slot / QT) * m * 256 * QT + e * QT + slot % QT] = entry e of the table of query q0 + slot (or
+// qsel[slot]), QT = lsq_adc_lut_qt(m) queries per tile; LUT holds ceil(nqb / QT) tiles
+inline int lsq_adc_lut_qt(int m) { return m <= 8 ? 16 : 8; }
+int lsq_adc_launch_lut(hipStream_t s, const lsq_search_input &in, const int *qsel, int q0, int nqb, float *LUT);
+
+// ---- inverted lists on a resident index (lsq_ivf.hip): the layout lsq_index_set_lists builds and the search over the probed lists -----------------------
+struct lsq_ivf_state;
+void lsq_ivf_free(lsq_ivf_state *st);
+int lsq_ivf_nlist(const lsq_ivf_state *st);      // 0: no lists yet
+void lsq_ivf_get_info(const lsq_ivf_state *st, lsq_ivf_info *out);
+// codes [n][m], norms [n]: the index's device arrays; desc as lsq_index_set_lists takes it.  A bad list_of_row entry leaves the former lists as they were
+int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **st, const uint8_t *codes, const float *norms, int64_t n, int m, int d, const lsq_ivf_desc *desc);
+// device pointers: K [m*256][d], q_scan [nq][d], q_coarse [nq][ldc], dists / ids [nq][nn] (ADC distances, original ids 1-based, (+inf, 0) past the probed
+// rows).  adc: the index's scan state (the coarse search and the selection run on it); coarse: how the coarse search runs (the context's hooks)
+int lsq_ivf_search(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *K, float *dists, int *ids, const float *q_scan,
+                   const float *q_coarse, int64_t ldc, int nq, int nprobe, int nn, int flags, const lsq_search_opts &coarse, int timed);
+
 // argument checks of the PQ / OPQ scan (lsq_linscan.hip), shared by the host drop-in and the device scan
 int lsq_linscan_pq_check(const char *fn, const void *dists, const void *res, const void *codes, const void *centers, const void *queries, int N,
                          uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim);

@@ -704,6 +704,41 @@ class Index:
         self._eng._call(side, "lsq_index_knn", p(dists), p(ids), p(Q), int(u8), nq, int(side.pitch(Q)), int(k), int(id_base), int(self._dev), h=self._h)
         return dists, ids
 
+    def set_lists(self, centroids, assign):
+        """Lay inverted lists over the index's codes: centroids (nlist,d) float32, assign (n,) int32 0-based list of every row (train_coarse and
+        ivf_assign make them).  The index copies what it needs; calling it again replaces the lists   [lsq_index_set_lists]"""
+        side = self._side
+        cent, lor = side.take(centroids, _F32, "centroids"), side.take(assign, _I32, "assign")
+        _shapes(("centroids", cent, (None, self.d)), ("assign", lor, (self.n,)))
+        desc, p = _lib.IvfDesc(), side.ptr
+        desc.nlist, desc.centroids, desc.list_of_row, desc.on_device = int(cent.shape[0]), p(cent), p(lor), int(self._dev)
+        self._eng._call(side, "lsq_index_set_lists", C.byref(desc), h=self._h)
+        self.nlist = int(cent.shape[0])
+
+    def search_ivf(self, Q_scan, k, nprobe, shortlist=0, Q_coarse=None, Q_exact=None, add_coarse=False, every_record=False, flags=0):
+        """search() over the rows of each query's nprobe nearest lists alone.  Q_coarse (nq,d): what is compared with the centroids (default: Q_scan);
+        add_coarse: one more rounded add of the coarse distance (residual codes); every_record: the road that writes and sorts every probed row.
+        -> dists (nq,k) float32 ascending, ids (nq,k) int32 1-BASED original row ids; (+inf, 0) where the probed lists hold fewer than k rows
+        [lsq_index_search_ivf]"""
+        side = self._side
+        Qs = side.take(Q_scan, _F32, "Q_scan")
+        Qc = Qs if Q_coarse is None else side.take(Q_coarse, _F32, "Q_coarse")
+        Qe = Qs if Q_exact is None else side.take(Q_exact, _F32, "Q_exact")
+        _shapes(("Q_scan", Qs, (None, self.d)), ("Q_coarse", Qc, tuple(Qs.shape)), ("Q_exact", Qe, tuple(Qs.shape)))
+        nq, p = Qs.shape[0], side.ptr
+        dists, ids = side.topk(nq, int(k), Qs)
+        fl = int(flags) | (_lib.IVF_ADD_COARSE if add_coarse else 0) | (_lib.IVF_EVERY_RECORD if every_record else 0)
+        self._eng._call(side, "lsq_index_search_ivf", p(dists), p(ids), p(Qs), p(Qc), p(Qe), nq, self.d, int(nprobe), int(shortlist), int(k), fl,
+                        int(self._dev), h=self._h)
+        return dists, ids
+
+    def ivf_info(self):
+        """what the last search_ivf call did: queries, probed_rows, records, threshold_queries, fallback_queries, batches, batch_queries,
+        tail_capacity, coarse_ms / lut_ms / scan_ms / select_ms (with profile=True)"""
+        st = _lib.IvfInfo()
+        self._eng._call(_HOST, "lsq_index_get_ivf_info", C.byref(st), h=self._h)
+        return st.as_dict()
+
     def knn_info(self):
         """what the last knn call did: queries, rows, batches, fallback_queries, exhaustive, int_road, norms_ms / scan_ms / select_ms (with profile=True)"""
         st = _lib.IndexKnnInfo()

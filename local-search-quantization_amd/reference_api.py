@@ -262,6 +262,56 @@ def linscan_lsq_rerank(B, X, C, dbnorms, R, X_base, shortlist, k, *, engine=None
     return dists.T, ids.T
 
 
+# -- the coarse partition of an inverted-list search (Index.set_lists / Index.search_ivf).  No counterpart in the reference; ROW arrays, as Engine and Index
+# take them: X (n, d), centroids (nlist, d), codes (n, m) uint8 0-based, K (m*h, d) --------------------------------------------------------------------------
+
+def ivf_assign(X, centroids, engine=None, *, nthreads=0):
+    """The nearest centroid of every row: exact k-NN with one neighbour and the centroids as base (ties to the smaller list, NaN last) -- the rule by which
+    Index.search_ivf picks a query's lists.  -> (n,) int32 0-based.  engine=None: the host cores; engine=<Engine>: the device, the same ids."""
+    from . import _lib
+    X, cent = np.ascontiguousarray(X, dtype=np.float32), np.ascontiguousarray(centroids, dtype=np.float32)
+    if X.ndim != 2 or cent.ndim != 2 or X.shape[1] != cent.shape[1]:
+        raise ValueError("ivf_assign: X %s, centroids %s" % (X.shape, cent.shape))
+    if engine is not None:
+        _, ids = engine.knn_exact(cent, X, 1)
+    else:
+        (n, d), nlist = X.shape, cent.shape[0]
+        dists, ids = np.zeros((n, 1), dtype=np.float32), np.zeros((n, 1), dtype=np.uint32)
+        _lib.check(_lib.load().lsq_knn_exact_cpu(dists.ctypes.data, ids.ctypes.data, cent.ctypes.data, X.ctypes.data, nlist, n, d, d, d, 1, int(nthreads)))
+    return np.ascontiguousarray(ids[:, 0]).astype(np.int32)
+
+
+def train_coarse(X, nlist, niter=10, seed=0, engine=None):
+    """Seeded Lloyd iterations for the coarse centroids: nlist distinct rows of X to start (numpy's default_rng(seed)), assignment by ivf_assign, means in
+    numpy (float64 sums, rounded to float32); an empty cluster keeps its centroid.  -> (centroids (nlist, d) float32, assign (n,) int32), assign being
+    ivf_assign's of the returned centroids."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    n, d = X.shape
+    if not 1 <= nlist <= n:
+        raise ValueError("train_coarse: needs 1 <= nlist <= n (got nlist=%d n=%d)" % (nlist, n))
+    cent = X[np.sort(np.random.default_rng(seed).choice(n, nlist, replace=False))].copy()
+    assign = ivf_assign(X, cent, engine)
+    for _ in range(niter):
+        sums = np.zeros((nlist, d), dtype=np.float64)
+        np.add.at(sums, assign, X)
+        counts = np.bincount(assign, minlength=nlist)
+        live = counts > 0
+        cent[live] = (sums[live] / counts[live, None]).astype(np.float32)
+        assign = ivf_assign(X, cent, engine)
+    return cent, assign
+
+
+def ivf_residual_norms(codes, K, centroids, assign):
+    """The scalar a residual index stores as dbnorms: with r^ the reconstruction of a row's codes (of x - c_l) and c_l its list's centroid,
+    |r^|^2 + 2 <c_l, r^> (float64, rounded to float32), so that the scan's sum plus the coarse distance (add_coarse=True) is |q - c_l - r^|^2."""
+    codes, K = np.asarray(codes), np.asarray(K, dtype=np.float32)
+    m = codes.shape[1]
+    h = K.shape[0] // m
+    recon = sum(K[j * h + codes[:, j].astype(np.int64)] for j in range(m)).astype(np.float64)
+    c = np.asarray(centroids, dtype=np.float64)[np.asarray(assign, dtype=np.int64)]
+    return ((recon * recon).sum(1) + 2.0 * (c * recon).sum(1)).astype(np.float32)
+
+
 def eval_recall(ids_gnd, ids_predicted, k, V=False):
     """recall@N curve (src/linscan/Linscan.jl:76-117): ids_gnd (nq,), ids_predicted (k, nq), same id base.
     -> recall_at_i (k,) with recall_at_i[i-1] = fraction of queries whose true neighbour ranks <= i."""

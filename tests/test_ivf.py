@@ -1,0 +1,163 @@
+"""The inverted-list search without a GPU: the host checker lsq_ivf_search_cpu against the numpy statement of the contract (tests/ivf_check.py) and against
+the exhaustive host scan, the boundary (header, binding, version), and every argument the library refuses before it needs a device."""
+import ctypes as C
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ivf_check as ic  # noqa: E402
+from knn_check import same_bits  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+H = 256
+
+
+def test_boundary_declares_exports_and_binds_the_four_symbols(lsq):
+    hdr = open(os.path.join(ROOT, "include", "lsq_mi355x.h")).read()
+    assert int(re.search(r"#define LSQ_VERSION (\d+)", hdr).group(1)) >= 1700
+    L, tun = lsq._lib.load(), lsq._lib.load(tuning=True)
+    assert L.lsq_version() >= 1700
+    for s in ("lsq_index_set_lists", "lsq_index_search_ivf", "lsq_index_get_ivf_info", "lsq_ivf_search_cpu"):
+        assert re.search(r"LSQ_API int %s\(" % s, hdr), s
+        assert s in lsq._lib.SIGNATURES and hasattr(L, s) and hasattr(tun, s)
+    assert re.search(r"LSQ_IVF_ADD_COARSE = 1, LSQ_IVF_EVERY_RECORD = 2", hdr)
+    assert (lsq._lib.IVF_ADD_COARSE, lsq._lib.IVF_EVERY_RECORD) == (ic.ADD_COARSE, ic.EVERY_RECORD) == (1, 2)
+    # the info struct of the binding has the header's fields, in order
+    body = re.search(r"typedef struct lsq_ivf_info \{(.*?)\} lsq_ivf_info;", hdr, flags=re.S).group(1)
+    fields = re.findall(r"\b(\w+)\s*[,;]", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    assert fields == [f for f, _ in lsq._lib.IvfInfo._fields_]
+    for name in ("ivf_assign", "train_coarse", "ivf_residual_norms"):
+        assert callable(getattr(lsq, name))
+    assert all(hasattr(lsq.Index, f) for f in ("set_lists", "search_ivf", "ivf_info"))
+
+
+@pytest.mark.parametrize("shape", ic.SHAPES, ids=lambda s: "d%d-m%d-nlist%d-nprobe%d-nn%d-nq%d" % s)
+@pytest.mark.parametrize("add", [False, True], ids=["plain", "add_coarse"])
+def test_host_checker_returns_the_numpy_contract(lsq, shape, add):
+    d, m, nlist, nprobe, nn, nq = shape
+    p = ic.problem(ic.N, d, m, nlist, nq, 7 + sum(shape))
+    p[2][5::97] = np.float32(np.nan)                                         # NaN norms: after every number, before the padding
+    rc, dd, di = ic.ivf_cpu(lsq._lib.load(), *p, nprobe, nn, flags=ic.ADD_COARSE if add else 0)
+    assert rc == 0, lsq._lib.load().lsq_last_error()
+    rd, ri = ic.ivf_np(*p, nprobe, nn, add_coarse=add)
+    assert same_bits(dd, rd) and np.array_equal(di, ri)
+    # one thread and all of them: the same result
+    rc1, d1, i1 = ic.ivf_cpu(lsq._lib.load(), *p, nprobe, nn, flags=ic.ADD_COARSE if add else 0, nthreads=1)
+    assert rc1 == 0 and same_bits(d1, dd) and np.array_equal(i1, di)
+
+
+def test_padding_entries_follow_nan_when_the_probed_lists_are_short(lsq):
+    codes, K, dbn, cent, lor, Qs, Qc = ic.problem(ic.N, 32, 8, 40, 5, 3)
+    lor[:] = 0
+    lor[:4] = 3                                                              # list 3 holds rows 1 .. 4 (1-based), one of them with a NaN norm
+    dbn[1] = np.float32(np.nan)
+    cent[3] = 1000.0
+    Qc[:] = 1000.0                                                           # every query probes list 3 first
+    rc, dd, di = ic.ivf_cpu(lsq._lib.load(), codes, K, dbn, cent, lor, Qs, Qc, 1, 10)
+    assert rc == 0
+    assert np.array_equal(np.sort(di[:, :3], axis=1), np.tile([1, 3, 4], (5, 1))) and np.all(di[:, 3] == 2) and np.all(np.isnan(dd[:, 3]))
+    assert np.all(di[:, 4:] == 0) and np.all(np.isposinf(dd[:, 4:]))
+    rd, ri = ic.ivf_np(codes, K, dbn, cent, lor, Qs, Qc, 1, 10)
+    assert same_bits(dd, rd) and np.array_equal(di, ri)
+
+
+@pytest.mark.parametrize("small_int", [False, True], ids=["gauss", "ties"])
+def test_every_list_probed_is_the_exhaustive_host_scan(lsq, small_int):
+    """nprobe = nlist, no flag: the distances, ids and tie order of lsq_linscan_aqd_query_extra_byte"""
+    L = lsq._lib.load()
+    n, d, m, nlist, nq, nn = 2500, 32, 8, 7, 9, 300
+    codes, K, dbn, cent, lor, Qs, Qc = ic.problem(n, d, m, nlist, nq, 21, small_int=small_int)
+    if small_int:
+        codes[n // 2:] = codes[:n - n // 2]                                  # duplicated code rows, in other lists
+        dbn[n // 2:] = dbn[:n - n // 2]
+    rc, dd, di = ic.ivf_cpu(L, codes, K, dbn, cent, lor, Qs, Qc, nlist, nn)
+    assert rc == 0
+    sd, si = np.zeros((nq, nn), np.float32), np.zeros((nq, nn), np.int32)
+    assert L.lsq_linscan_aqd_query_extra_byte(sd.ctypes.data, si.ctypes.data, codes.ctypes.data, Qs.ctypes.data, K.ctypes.data, dbn.ctypes.data, nq, n, m,
+                                              H, d, nn, 0) == 0
+    assert same_bits(dd, sd) and np.array_equal(di, si)
+    if small_int:
+        assert any(len(np.unique(row)) < nn for row in dd)                   # the ties are there
+
+
+def test_equidistant_centroids_go_to_the_smaller_list(lsq):
+    codes, K, dbn, cent, lor, Qs, Qc = ic.problem(2000, 5, 7, 7, 6, 33, small_int=True, lists="random")
+    cent[4] = cent[2]                                                        # lists 2 and 4 tie for every query
+    Qc[:] = cent[2]
+    _, probes = ic.probes_np(cent, Qc, 1)
+    assert np.all(probes == 2)
+    rc, dd, di = ic.ivf_cpu(lsq._lib.load(), codes, K, dbn, cent, lor, Qs, Qc, 1, 10)
+    assert rc == 0 and np.all(lor[di - 1] == 2)
+    rd, ri = ic.ivf_np(codes, K, dbn, cent, lor, Qs, Qc, 1, 10)
+    assert same_bits(dd, rd) and np.array_equal(di, ri)
+
+
+def test_helpers_assign_train_and_residual_norms(lsq):
+    rng = np.random.default_rng(5)
+    centres = rng.standard_normal((6, 8)).astype(np.float32) * 8
+    X = (centres[rng.integers(0, 6, 600)] + rng.standard_normal((600, 8))).astype(np.float32)
+    cent, assign = lsq.train_coarse(X, 6, niter=5, seed=1)
+    assert cent.shape == (6, 8) and cent.dtype == np.float32 and assign.shape == (600,) and assign.dtype == np.int32
+    assert np.array_equal(assign, lsq.ivf_assign(X, cent)) and np.array_equal(lsq.train_coarse(X, 6, niter=5, seed=1)[0], cent)
+    d2 = ((X[:, None, :].astype(np.float64) - cent[None].astype(np.float64)) ** 2).sum(2)
+    assert np.mean(assign == d2.argmin(1)) > 0.99                            # (f32 against f64: a near-tie may differ)
+    # an empty cluster keeps its centroid: two identical rows of X cannot both win
+    Xd = np.repeat(X[:3], 4, axis=0)
+    c2, a2 = lsq.train_coarse(Xd, 3, niter=2, seed=0)
+    assert c2.shape == (3, 8) and np.all(np.isfinite(c2))
+    # the residual form: the scan's sum plus the coarse distance is |q - c - r^|^2
+    m = 2
+    K = rng.standard_normal((m * H, 8)).astype(np.float32)
+    codes = rng.integers(0, H, (600, m)).astype(np.uint8)
+    dbn = lsq.ivf_residual_norms(codes, K, cent, assign)
+    recon = sum(K[j * H + codes[:, j].astype(np.int64)] for j in range(m)).astype(np.float64)
+    q = rng.standard_normal(8)
+    want = ((q[None] - cent[assign] - recon) ** 2).sum(1)
+    got = -2 * (recon @ q) + dbn + ((q[None] - cent[assign]) ** 2).sum(1)
+    assert np.allclose(got, want, rtol=1e-5, atol=1e-4)
+
+
+def _cpu_args(p, nprobe=3, nn=5, flags=0):
+    codes, K, dbn, cent, lor, Qs, Qc = p
+    (n, m), (nq, d) = codes.shape, Qs.shape
+    dd, di = np.zeros((nq, nn), np.float32), np.zeros((nq, nn), np.int32)
+    keep = (dd, di, codes, K, dbn, cent, lor, Qs, Qc)
+    return keep, [a.ctypes.data for a in keep] + [n, m, H, d, cent.shape[0], nq, d, nprobe, nn, flags, 0]
+
+
+def test_host_checker_refuses_bad_arguments(lsq):
+    L, EINVAL = lsq._lib.load(), lsq._lib.LSQ_EINVAL
+    p = ic.problem(300, 5, 2, 7, 3, 1)
+    keep, good = _cpu_args(p)
+    assert L.lsq_ivf_search_cpu(*good) == 0
+    for k in range(8):                                                       # a null pointer, one at a time (q_coarse may be null: it is q_scan then)
+        bad = list(good)
+        bad[k] = None
+        assert L.lsq_ivf_search_cpu(*bad) == EINVAL and b"null" in L.lsq_last_error()
+    nocoarse = list(good)
+    nocoarse[8] = None
+    assert L.lsq_ivf_search_cpu(*nocoarse) == 0
+    names = ["n", "m", "h", "d", "nlist", "nq", "ldq", "nprobe", "nn", "flags"]
+    for name, value in (("nprobe", 0), ("nprobe", 8), ("nlist", 0), ("nlist", (1 << 24) + 1), ("nn", 0), ("flags", 8), ("flags", -1), ("ldq", 4),
+                        ("n", 0), ("m", 0), ("h", 257), ("d", 0), ("nq", -1)):
+        bad = list(good)
+        bad[9 + names.index(name)] = value
+        assert L.lsq_ivf_search_cpu(*bad) == EINVAL, (name, value)
+    for entry in (-1, 7):                                                    # a list_of_row entry outside [0, nlist)
+        p[4][11] = entry
+        assert L.lsq_ivf_search_cpu(*good) == EINVAL and b"list_of_row" in L.lsq_last_error()
+    p[4][11] = 0
+    assert L.lsq_ivf_search_cpu(*good) == 0 and keep is not None
+
+
+def test_index_symbols_refuse_a_null_handle(lsq):
+    L, EINVAL = lsq._lib.load(), lsq._lib.LSQ_EINVAL
+    desc, info = lsq._lib.IvfDesc(), lsq._lib.IvfInfo()
+    buf = np.zeros(64, np.float32)
+    assert L.lsq_index_set_lists(None, C.byref(desc)) == EINVAL
+    assert L.lsq_index_search_ivf(None, buf.ctypes.data, buf.ctypes.data, buf.ctypes.data, None, None, 1, 5, 1, 0, 1, 0, 0) == EINVAL
+    assert L.lsq_index_get_ivf_info(None, C.byref(info)) == EINVAL

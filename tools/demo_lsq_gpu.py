@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--init beam:L] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE] [--init beam:L] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -17,6 +17,9 @@ instead of randinit (demos/demo_lsq_gpu.jl:46); the rest of the flow is unchange
 --rerank L: after the ADC scan, the two-stage search on a resident index (Engine.index: the codes, norms, codebooks and the base rows uploaded once):
 the scan's L nearest re-ordered by exact distance to the stored vectors -- f32 rows, or the un-widened 8-bit rows with --bvecs -- and the recall curve of the
 re-ranked lists printed next to the ADC one.  The reference has no such stage: its recall is that of the ADC order.
+
+--ivf NLIST:NPROBE: after the ADC scan, inverted lists over the same codes (train_coarse on the base rows, Index.set_lists) and the search that reads
+each query's NPROBE nearest lists alone (Index.search_ivf); its recall curve is printed next to the exhaustive one.  The reference has no such search.
 
 needs $LSQ_DATA_DIR/sift/{sift_learn,sift_base,sift_query}.fvecs and sift_groundtruth.ivecs (TEXMEX layout).  The file's ground truth
 describes the full 10^6-vector base only: for a prefix of it (nread_base < 10^6) and for the stand-in, the ground truth is exact k-NN of the base
@@ -131,6 +134,15 @@ def main():
         del argv[at:at + 2]
         if init != "random" and not (init.startswith("beam:") and init[5:].isdigit()):
             raise SystemExit("--init takes `random` or `beam:L`, got %r" % init)
+    ivf = None
+    if "--ivf" in argv:
+        at = argv.index("--ivf")
+        try:
+            ivf = tuple(int(x) for x in argv[at + 1].split(":"))
+            assert len(ivf) == 2 and 1 <= ivf[1] <= ivf[0]
+        except (ValueError, AssertionError, IndexError):
+            raise SystemExit("--ivf takes NLIST:NPROBE with 1 <= NPROBE <= NLIST")
+        del argv[at:at + 2]
     args = [a for a in argv if a not in ("--resident", "--bvecs")]
     resident, bvecs = "--resident" in argv, "--bvecs" in argv
     real = bool(os.environ.get("LSQ_DATA_DIR"))
@@ -193,6 +205,26 @@ def main():
             if i <= keep:
                 print("%7d   %.4f   %.4f" % (i, rec[i - 1], rrec[i - 1]))
         print("%s: recall@1 after re-ranking %d = %.4f (ADC: %.4f)" % (name, L, rrec[0], rec[0]))
+    if ivf:
+        nlist, nprobe = min(ivf[0], x_base.shape[1]), ivf[1]
+        nprobe = min(nprobe, nlist)
+        rows = np.ascontiguousarray(np.asarray(x_base, dtype=np.float32).T)
+        Q = np.ascontiguousarray(x_query.T)
+        with lsq.Engine(0) as eng:                                          # inverted lists over the same codes: the scan reads the probed lists alone
+            cent, assign = lsq.train_coarse(rows, nlist, niter=10, seed=0, engine=eng)
+            with eng.index((B_base - 1).astype(np.uint8).T, np.ascontiguousarray(np.hstack(C).T), db_norms, m) as ix:
+                ix.set_lists(cent, assign)
+                t0 = time.perf_counter()
+                _, iidx = ix.search_ivf(Q, knn, nprobe)
+                t_ivf = time.perf_counter() - t0
+                info = ix.ivf_info()
+        irec = lsq.eval_recall(gt, np.ascontiguousarray(iidx.T).astype(np.uint32), knn)
+        print("IVF search (nlist %d, nprobe %d): %.3f s on the resident index; %.0f of %d rows probed per query, %d of %d queries on the thresholded road"
+              % (nlist, nprobe, t_ivf, info["probed_rows"] / Q.shape[0], x_base.shape[1], info["threshold_queries"], Q.shape[0]))
+        print("     r@   exhaustive   IVF")
+        for i in (1, 2, 5, 10, 20, 50, 100, 200, 500, 1000):
+            if i <= knn:
+                print("%7d   %.4f       %.4f" % (i, rec[i - 1], irec[i - 1]))
 
 
 if __name__ == "__main__":
