@@ -28,3 +28,28 @@ def beam_exact(X, K, m, L, order=None, h=256):
         codes = np.take_along_axis(codes, (idx // h)[:, :, None], axis=1)
         codes[:, :, j] = idx % h
     return codes[:, 0, :].copy(), S[:, 0].astype(np.float32)
+
+
+def cost_and_score_bound(X, K, m, codes, h=256):
+    """float64 reconstruction error ||x - sum_j c_j||^2 of 0-based codes (n, m), and the bound on |(||x||^2 + score) - that| for an f32 score of the contract.
+
+    In real arithmetic ||x||^2 + score IS the reconstruction error: score = sum_j (||c_j||^2 - 2 <x, c_j>) + sum_{j > k} 2 <c_k, c_j>.  The f32 score is that
+    sum evaluated with rounding, whatever the order: every leaf (a product x_s c_js, c_js^2 or c_ks c_js; the factors 2 are exact) passes through at most
+        d      rounded operations of its own dot product (the product, d - 1 accumulations; an FMA takes one away),
+        2      to join the codeword's norm and the unary,
+        N - 1  additions among the N = m + m (m - 1) / 2 unaries and table entries (a stage's adds and the S + s of every later stage)
+    so the computed score is sum_leaves leaf * prod (1 + delta_i) over at most c = d + 2 + N factors, |delta_i| <= u = 2^-24, and (Higham, Accuracy and
+    Stability of Numerical Algorithms, lemma 3.1) |error| <= gamma_c * M with gamma_c = c u / (1 - c u) and M the sum of the leaves' magnitudes:
+        M = sum_j sum_s (c_js^2 + 2 |x_s c_js|) + sum_{j > k} sum_s 2 |c_ks c_js|.
+    The float64 side (this function and the caller's ||x||^2 + score) follows the same count with u = 2^-53 over leaves of magnitude <= ||x||^2 + M."""
+    X64, K64 = np.asarray(X, dtype=np.float64), np.asarray(K, dtype=np.float64)
+    d = X64.shape[1]
+    C = [K64[j * h + np.asarray(codes)[:, j]] for j in range(m)]               # the chosen codewords, (n, d) each
+    cost = ((X64 - sum(C)) ** 2).sum(1)
+    M = sum((c * c).sum(1) + 2 * np.abs(X64 * c).sum(1) for c in C)
+    for j in range(m):
+        for k in range(j):
+            M = M + 2 * np.abs(C[k] * C[j]).sum(1)
+    c = d + 2 + m + m * (m - 1) // 2
+    gamma = lambda u: c * u / (1 - c * u)                                    # noqa: E731
+    return cost, gamma(2.0 ** -24) * M + gamma(2.0 ** -53) * ((X64 * X64).sum(1) + M)

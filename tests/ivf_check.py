@@ -76,9 +76,24 @@ def tail_hits_np(codes, K, dbn, cent, lor, Qs, Qc, nprobe, nn, add_coarse=False)
         if rows < nn:
             out.append((rows, 0, 0))
             continue
-        tau = np.sort(order_keys(dist[q, in_head]))[nn - 1]
-        out.append((rows, int(in_tail.sum()), int((order_keys(dist[q, in_tail]) <= tau).sum()) if tau != 0xFFFFFFFF else int(in_tail.sum())))
+        head_d = dist[q, in_head]
+        tau = head_d[np.argsort(order_keys(head_d), kind="stable")[nn - 1]]    # NaN sorts last: a NaN tau keeps every record
+        with np.errstate(invalid="ignore"):
+            out.append((rows, int(in_tail.sum()), int((~(dist[q, in_tail] > tau)).sum())))         # !(dist > tau): ties kept, a NaN on either side kept
     return out
+
+
+def roads_np(hits, nn):
+    """-> (tail_capacity, fall-back query numbers, records) of the thresholded road by the plan of DESIGN.md (inverted lists, "Plan"): a thresholded segment
+    holds the longest head (at least nn records: a short head is padded) plus min(longest tail, 8 nn + 256) slots, never more than the longest query's rows; a
+    query whose head and tail hits do not fit its segment is redone with every record.  records: what the segments held, the redone queries' second segments
+    included.  hits: tail_hits_np's, with at least one non-empty tail"""
+    max_rows = max(max(h[0] + h[1], nn) for h in hits)
+    tail_cap = min(max(h[1] for h in hits), 8 * nn + 256)
+    cap = min(max(max(h[0], nn) for h in hits) + tail_cap, max_rows)
+    fallback = [q for q, h in enumerate(hits) if max(h[0], nn) + h[2] > cap]
+    records = sum(min(max(h[0], nn) + h[2], cap) for h in hits) + sum(max(hits[q][0] + hits[q][1], nn) for q in fallback)
+    return tail_cap, fallback, records
 
 
 def ivf_cpu(lib, codes, K, dbn, cent, lor, Qs, Qc, nprobe, nn, flags=0, nthreads=0):
@@ -126,7 +141,104 @@ def problem(n, d, m, nlist, nq, seed, small_int=False, lists="skewed"):
     return codes, K, dbn, cent, lor, Qs, Qc
 
 
-# (d, m, nlist, nprobe, nn, nq): every value of the issue's grid at least once; m = 8, 16 take the dword loader, 1 and 7 the byte loader
+# (d, m, nlist, nprobe, nn, nq): every value of the issue's grid at least once; m = 8, 16 take the dword loader, 1 and 7 the byte loader; the last four:
+# m = 4 and 12 (the one- and three-dword loaders; at m = 12 the tables come in 8-query tiles, which 37 queries cross), m = 2 and 15 (byte loader)
 SHAPES = [(5, 1, 1, 1, 1, 1), (32, 7, 7, 3, 10, 37), (32, 8, 40, 3, 300, 37), (5, 16, 40, 40, 10, 37), (32, 8, 7, 7, 300, 1), (5, 7, 40, 1, 1, 37),
-          (32, 16, 7, 1, 300, 37), (32, 8, 40, 40, 1, 37), (5, 8, 7, 3, 10, 1), (32, 1, 40, 3, 10, 37), (5, 16, 1, 1, 300, 37), (32, 7, 40, 40, 300, 1)]
+          (32, 16, 7, 1, 300, 37), (32, 8, 40, 40, 1, 37), (5, 8, 7, 3, 10, 1), (32, 1, 40, 3, 10, 37), (5, 16, 1, 1, 300, 37), (32, 7, 40, 40, 300, 1),
+          (32, 4, 40, 3, 10, 37), (32, 12, 40, 3, 300, 37), (5, 2, 7, 3, 10, 37), (32, 15, 40, 40, 10, 37)]
 N = 3000
+
+
+# ---- named problems: each returns (the seven arrays of problem(), nprobe, nn).  tests/test_ivf.py holds lsq_ivf_search_cpu to ivf_np on each,
+# tests/test_gpu_ivf.py the device to lsq_ivf_search_cpu and its road counts to tail_hits_np / roads_np ------------------------------------------------
+SCAN_BLOCKS = 2048                                                           # the scan gives a query min(ceil(SCAN_BLOCKS / queries of the batch), nprobe) blocks
+
+
+def scan_splits(nqb, nprobe):
+    return min(-(-SCAN_BLOCKS // nqb), nprobe)
+
+
+def stride_problem(which):
+    """more (query, list) pairs than SCAN_BLOCKS: a block walks several lists with one staged table.  "m8": 300 queries, 40 of 40 skewed lists, 7 blocks
+    per query (5 or 6 lists each); every query has a tail of up to 1333 hits, and none overflows: segments are sized by the longest head, and some
+    query's head holds the 1500-row list.  "m12": 128 queries, 33 of 64 lists, 16 blocks per query (2 or 3 lists each); 59 queries overflow, 69 do not"""
+    d, m, nlist, nprobe, nn, nq = {"m8": (32, 8, 40, 40, 10, 300), "m12": (32, 12, 64, 33, 10, 128)}[which]
+    return problem(N, d, m, nlist, nq, 94 + m, lists="skewed"), nprobe, nn
+
+
+def _even(d, m, nq, seed, small_int=False):
+    """3000 rows, 40 lists of 75: row i is the (i // 40)-th row of list i % 40"""
+    return problem(N, d, m, 40, nq, seed, small_int=small_int, lists="even")
+
+
+def capacity_problem(t):
+    """every probed row has the same code row; the first t rows of every list have norm 1, the others 2 + (position in the list).  nn = 1: the head is the
+    nearest list, tau its norm-1 rows' distance, and exactly t rows of each of the 8 tail lists tie it (small integers: every sum exact).  8 t = 264 at
+    t = 33 is the tail's capacity 8 nn + 256 to the record; t = 34 is 8 over"""
+    codes, K, dbn, cent, lor, Qs, Qc = _even(5, 8, 37, 92, small_int=True)
+    codes[:] = codes[0]
+    at = np.arange(N) // 40
+    dbn[:] = np.where(at < t, 1, 2 + at).astype(np.float32)
+    return (codes, K, dbn, cent, lor, Qs, Qc), 9, 1
+
+
+def _two_groups(seed):
+    """the even layout with lists 0 .. 19 far from lists 20 .. 39; even queries probe the first group alone, odd queries the second"""
+    codes, K, dbn, cent, lor, Qs, Qc = _even(32, 8, 37, seed)
+    cent[:20] += np.float32(10)
+    cent[20:] -= np.float32(10)
+    rng = np.random.default_rng(seed + 1000)
+    near = rng.integers(0, 20, 37) + 20 * (np.arange(37) % 2)
+    Qc[:] = cent[near] + np.float32(0.25) * rng.standard_normal((37, 32)).astype(np.float32)
+    return codes, K, dbn, cent, lor, Qs, Qc
+
+
+def mixed_problem():
+    """every row of lists 0 .. 19 is row 0 again: the 19 even queries' 7 x 75 tail rows all tie tau and overflow, the 18 odd queries see random rows and do
+    not.  With TEST_BATCH the failed queries 0, 2, .. 36 are three fall-back batches (8, 8, 3) of a non-contiguous selection"""
+    codes, K, dbn, cent, lor, Qs, Qc = _two_groups(93)
+    first = lor < 20
+    codes[first] = codes[0]
+    dbn[first] = dbn[0]
+    return (codes, K, dbn, cent, lor, Qs, Qc), 8, 1
+
+
+def nan_tau_problem():
+    """NaN norms in all of lists 0 .. 19: an even query's head has no number, its tau is NaN and every tail record is kept (and overflows); a sprinkling of
+    +inf and -inf norms in lists 20 .. 39, where the odd queries search"""
+    codes, K, dbn, cent, lor, Qs, Qc = _two_groups(95)
+    dbn[lor < 20] = np.float32(np.nan)
+    second = np.flatnonzero(lor >= 20)
+    dbn[second[3::29]] = np.float32(np.inf)
+    dbn[second[11::31]] = np.float32(-np.inf)
+    return (codes, K, dbn, cent, lor, Qs, Qc), 8, 5
+
+
+def short_list_problem():
+    """one probed list of four rows against nn = 10, their distances a number, -inf, +inf and NaN: the real +inf row and the NaN row come before the
+    (+inf, 0) padding records, which only the bit above the key tells from a real +inf"""
+    codes, K, dbn, cent, lor, Qs, Qc = problem(N, 32, 8, 40, 5, 3)
+    lor[:] = 0
+    lor[:4] = 3
+    dbn[1:4] = np.array([-np.inf, np.inf, np.nan], dtype=np.float32)
+    cent[3] = 1000.0
+    Qc[:] = 1000.0
+    return (codes, K, dbn, cent, lor, Qs, Qc), 1, 10
+
+
+def layout_problem(n, nlist):
+    """lists 0, 1, 2 and the last three empty (list 0 empty: the first sorted position opens four lists at once; runs of three empty lists), nlist at a
+    power of two and one above, n at a power of two (the id n needs the top bit of the record's id field) and one below.  The last row is made the strictly
+    nearest row of query 0: the best probed row again, with a smaller norm"""
+    codes, K, dbn, cent, lor, Qs, Qc = problem(n, 32, 8, nlist, 37, 96 + nlist, lists="random")
+    lor[:] = 3 + lor % (nlist - 6)
+    nprobe, nn = 12, 10
+    best = int(ivf_np(codes, K, dbn, cent, lor, Qs[:1], Qc[:1], nprobe, 1)[1][0, 0]) - 1
+    codes[n - 1], lor[n - 1], dbn[n - 1] = codes[best], lor[best], dbn[best] - np.float32(1)
+    return (codes, K, dbn, cent, lor, Qs, Qc), nprobe, nn
+
+
+PROBLEMS = {"stride-m8": lambda: stride_problem("m8"), "stride-m12": lambda: stride_problem("m12"), "capacity-33": lambda: capacity_problem(33),
+            "capacity-34": lambda: capacity_problem(34), "mixed": mixed_problem, "nan-tau": nan_tau_problem, "short-list": short_list_problem,
+            "layout-n2047-nlist64": lambda: layout_problem(2047, 64), "layout-n2048-nlist64": lambda: layout_problem(2048, 64),
+            "layout-n2047-nlist65": lambda: layout_problem(2047, 65), "layout-n2048-nlist65": lambda: layout_problem(2048, 65)}

@@ -10,7 +10,7 @@ import pytest
 
 import engine_calls as ec
 import oracle.init_oracle as ini
-from beam_check import beam_exact
+from beam_check import beam_exact, cost_and_score_bound
 from conftest import make_problem
 from engine_calls import D, H, M, N
 
@@ -74,10 +74,7 @@ def test_two_codebooks_and_a_full_beam_is_brute_force(oracle):
         assert (codes[i, 0], codes[i, 1]) == (best[1], best[2]) and score[i].tobytes() == np.float32(best[0]).tobytes()
 
 
-@pytest.mark.parametrize("order", [None, [2, 0, 3, 1]])
-def test_beam_of_one_is_the_greedy_loop(oracle, order):
-    m = 4
-    X, K = _gauss(2, 12, 25, m)
+def _greedy_loop_agrees(oracle, X, K, m, order):
     codes, score = beam_exact(X, K, m, 1, order)
     U, T = oracle.unaries(X, K, m, H), oracle.tables(K, m, H)
     o = list(range(m)) if order is None else order
@@ -91,6 +88,35 @@ def test_beam_of_one_is_the_greedy_loop(oracle, order):
             b[j] = int(np.argmin(v))
             S = v[b[j]]
         assert [b[j] for j in range(m)] == codes[i].tolist() and np.float32(S).tobytes() == score[i].tobytes()
+
+
+@pytest.mark.parametrize("order", [None, [2, 0, 3, 1]])
+def test_beam_of_one_is_the_greedy_loop(oracle, order):
+    m = 4
+    X, K = _gauss(2, 12, 25, m)
+    _greedy_loop_agrees(oracle, X, K, m, order)
+
+
+@pytest.mark.parametrize("kind", ["gauss", "int"])
+def test_beam_of_one_is_the_greedy_loop_past_eight_codebooks(oracle, kind):
+    """what tests/test_gpu_beam.py holds the greedy kernel's second code word to: m = 11, ascending and the high-first order; small integers: exact ties"""
+    m = 11
+    X, K = _gauss(6, 12, 25, m)
+    if kind == "int":
+        rng = np.random.default_rng(6)
+        X, K = rng.integers(-3, 4, X.shape).astype(np.float32), rng.integers(-2, 3, K.shape).astype(np.float32)
+    for order in (None, [10, 0, 9, 1, 8, 2, 7, 3, 6, 4, 5]):
+        _greedy_loop_agrees(oracle, X, K, m, order)
+
+
+def test_all_equal_candidates_resolve_by_position():
+    """one codeword everywhere and rows of zeros: every candidate of every stage ties, and the (v, p, a) rule leaves code 0 in every codebook"""
+    m, d = 4, 16
+    c = np.random.default_rng(7).integers(-2, 3, size=d).astype(np.float32)
+    X, K = np.zeros((9, d), np.float32), np.tile(c, (m * H, 1))
+    for L in (1, 4, 32):
+        codes, score = beam_exact(X, K, m, L)
+        assert not codes.any() and np.all(score == np.float32(m * m * (c * c).sum()))
 
 
 def test_one_codebook_is_the_nearest_codeword():
@@ -113,6 +139,23 @@ def test_score_is_the_cost_minus_the_norm(oracle):
         rel = np.abs(got - cost) / cost
         print("L=%d: max relative difference %.3g" % (L, rel.max()))
         assert rel.max() <= 1e-5
+
+
+def test_score_is_the_float64_reconstruction_error_within_the_derived_bound():
+    """the checker's own f32 score at the shape tests/test_gpu_beam.py holds the device's to: the bound of cost_and_score_bound is derived, not measured,
+    and a correct f32 evaluation stays far inside it (largest ratio here: 0.00647 at L = 1, 0.0049 at L = 16); a score off by one table entry is far outside"""
+    d, n, m = 128, 300, 8
+    rng = np.random.default_rng(100 + d + n + m)
+    X = rng.standard_normal((n, d)).astype(np.float32)
+    K = (rng.standard_normal((m * H, d)) / m).astype(np.float32)
+    for L in (1, 16):
+        codes, score = beam_exact(X, K, m, L)
+        cost, bound = cost_and_score_bound(X, K, m, codes)
+        err = np.abs((X.astype(np.float64) ** 2).sum(1) + score.astype(np.float64) - cost)
+        print("L=%d: max |error| / bound %.3g (max bound / cost %.3g)" % (L, (err / bound).max(), (bound / cost).max()))
+        assert np.all(err <= bound)
+        entry = 2 * (K[codes[:, 0]].astype(np.float64) * K[H + codes[:, 1]]).sum(1)          # T[1][0][b_0][b_1], left out of the score
+        assert np.mean(np.abs(entry) - err > bound) > 0.9                                     # |error without it| >= |entry| - |error with it|
 
 
 def test_a_wider_beam_finds_a_lower_score():

@@ -1,14 +1,16 @@
 """The beam-search encoder on the device (csrc/lsq_beam.hip behind lsq_encoder_*) against its numpy checker (tests/beam_check.py): codes AND score bits,
 host form and device form, at the smallest shapes at which its pieces can go wrong -- L = 1 (the greedy kernel), odd L, L at its cap, m = 1, 2 and 16,
 n = 1 and n ragged against the greedy kernel's four vectors per block, duplicated codewords and small-integer data (exact ties at the selection
-boundary, within and across parents) -- and the handle's contract: order, chunks, 8-bit rows, independence from the context and from other encoders,
+boundary, within and across parents), and the routes a shape threshold selects: codebooks 8 .. 15 of the greedy kernel in both visiting orders, a wave's
+second vector (n above the grids' 4096 blocks in one launch), widths strictly inside an instantiation's range (2, 9 .. 15, 17 .. 31), every candidate
+tying, the score against a float64 reconstruction error within a derived bound -- and the handle's contract: order, chunks, 8-bit rows, independence from the context and from other encoders,
 its codes as the start of an ILS encode, rejections, lifetime."""
 import functools
 
 import numpy as np
 import pytest
 
-from beam_check import beam_exact
+from beam_check import beam_exact, cost_and_score_bound
 
 pytestmark = pytest.mark.gpu
 H = 256
@@ -75,6 +77,92 @@ def test_codes_and_score_bits_vs_checker(engine, d, n, m, L, kind):
         assert np.array_equal(enc.beam(X, L).astype(np.int64) - 1, want[0])          # without the score
     with engine.encoder_dev(_dev(K), m) as enc:
         _same(*_dev_beam(enc, X, L), want)
+
+
+def _both_forms(engine, d, n, m, L, kind, order=None):
+    """codes and score bits of the host form and of the device form against the checker -> the host form's info()"""
+    X, K = _case(d, n, m, kind)
+    want = _want(d, n, m, L, kind, order)
+    with engine.encoder(K, m) as enc:
+        _same(*_host_beam(enc, X, L, order=None if order is None else list(order)), want)
+        info = enc.info()
+    with engine.encoder_dev(_dev(K), m) as enc:
+        _same(*_dev_beam(enc, X, L, order=None if order is None else np.array(order, dtype=np.int64)), want)
+    assert info["vectors"] == n and info["beam"] == L
+    return info
+
+
+def _high_first(m):
+    """a visiting order that starts with the highest codebook and alternates high and low ones: m = 11 -> 10 0 9 1 8 2 7 3 6 4 5"""
+    lo, hi = list(range(m // 2)), list(range(m - 1, m // 2 - 1, -1))
+    return tuple(x for pair in zip(hi, lo + [None]) for x in pair if x is not None)
+
+
+@pytest.mark.parametrize("order", ["ascending", "high-first"])
+@pytest.mark.parametrize("d,n,m,kind", [(16, 130, 16, "gauss"), (16, 131, 9, "gauss"), (16, 67, 13, "gauss"), (20, 64, 11, "int")])
+def test_greedy_codebooks_8_to_15(engine, d, n, m, kind, order):
+    """L = 1 with m > 8: the greedy kernel keeps the codes of codebooks 8 .. 15 in a second word.  Ascending fills the first word before the second; the
+    other order writes and reads the second word first and switches words at every stage.  Small integers: exact ties inside the wave's first minimum"""
+    o = None if order == "ascending" else _high_first(m)
+    assert m > 8 and (o is None or (sorted(o) == list(range(m)) and o[0] >= 8 and o[1] < 8))
+    _both_forms(engine, d, n, m, 1, kind, o)
+
+
+@pytest.mark.parametrize("n,m", [(1, 3), (2, 3), (3, 3), (5, 3), (1, 16)])
+def test_greedy_ragged_last_block(engine, n, m):
+    """L = 1 serves four vectors per block: a last block with one, two and three of them, a whole block and one more"""
+    assert n % 4 != 0
+    _both_forms(engine, 16, n, m, 1, "gauss")
+
+
+@pytest.mark.parametrize("d,n,m,L,kind", [(8, 16500, 2, 1, "gauss"), (8, 4200, 3, 2, "gauss"), (8, 4200, 3, 5, "gauss"), (8, 4200, 3, 5, "int")])
+def test_a_wave_encodes_a_second_vector(engine, d, n, m, L, kind):
+    """the grids stop at 4096 blocks -- four vectors a block at L = 1, one otherwise -- so in ONE launch of more vectors than that some wave goes round its
+    vector loop again: the stride, the beam state and the candidate keys left in LDS by the vector before (small integers: ties that stale keys would win)"""
+    assert n > 4096 * (4 if L == 1 else 1)
+    assert _both_forms(engine, d, n, m, L, kind)["chunks"] == 1               # the whole n was one launch
+
+
+@pytest.mark.parametrize("d,n,m,L,kind", [(16, 70, 4, 2, "gauss"), (16, 70, 4, 2, "dup"), (16, 70, 6, 9, "gauss"), (16, 70, 6, 12, "dup"), (16, 70, 6, 15, "gauss"),
+                                          (16, 70, 5, 17, "gauss"), (16, 70, 5, 24, "dup"), (16, 70, 5, 31, "gauss"), (16, 70, 13, 17, "dup"),
+                                          (16, 70, 13, 24, "gauss"), (16, 70, 13, 31, "gauss")])
+def test_widths_below_their_instantiation(engine, d, n, m, L, kind):
+    """beam_kernel<LMAX> serves every L <= LMAX in {2, 4, 8, 16, 32}, its register slots past L clamped to the last parent: L = 2 (LMAX = 2 itself), L strictly
+    inside (8, 16) and (16, 32).  In the last range 4 L lies strictly between 64 and 128: some lanes read a second slot of the re-scanned column, some do not"""
+    assert L == 2 or 8 < L < 16 or (16 < L < 32 and 64 < 4 * L < 128)
+    assert m > 2                                                             # a stage with L parents and a stage after it
+    _both_forms(engine, d, n, m, L, kind)
+
+
+@pytest.mark.parametrize("L", [4, 32])
+def test_every_candidate_ties(engine, L):
+    """one codeword 256 m times and rows of zeros: all 256 L_t candidates of every stage share a key, position alone decides, and the answer is code 0
+    everywhere (the checker says so too) with the score of four equal codewords"""
+    d, n, m = 16, 9, 4
+    c = np.random.default_rng(7).integers(-2, 3, size=d).astype(np.float32)
+    X, K = np.zeros((n, d), np.float32), np.ascontiguousarray(np.tile(c, (m * H, 1)))
+    want = beam_exact(X, K, m, L)
+    assert not want[0].any() and np.all(want[1] == np.float32(m * m * (c * c).sum()))
+    with engine.encoder(K, m) as enc:
+        _same(*_host_beam(enc, X, L), want)
+    with engine.encoder_dev(_dev(K), m) as enc:
+        _same(*_dev_beam(enc, X, L), want)
+
+
+def test_score_plus_norm_is_the_float64_reconstruction_error(engine):
+    """||x||^2 + score against the reconstruction error of the returned codes in float64 numpy -- no device cost kernel on either side -- within the bound
+    beam_check.cost_and_score_bound derives from the contract's operation count (c = d + 2 + m + m (m - 1) / 2 = 166 rounded operations on any leaf:
+    gamma_c 2^-24 times the leaves' magnitudes).  On the MI355X the largest ratio to the bound was 0.00595 at L = 1 and 0.00547 at L = 16 (the bound itself: 4.5e-5 of the cost)"""
+    d, n, m = 128, 300, 8
+    X, K = _case(d, n, m, "gauss")
+    K = np.ascontiguousarray(K / np.float32(m))
+    with engine.encoder(K, m) as enc:
+        for L in (1, 16):
+            codes, s = _host_beam(enc, X, L)
+            cost, bound = cost_and_score_bound(X, K, m, codes)
+            err = np.abs((X.astype(np.float64) ** 2).sum(1) + s.astype(np.float64) - cost)
+            print("L=%d: max |error| / bound %.3g (max bound / cost %.3g)" % (L, (err / bound).max(), (bound / cost).max()))
+            assert np.all(err <= bound)
 
 
 def test_visiting_order(lsq, engine):

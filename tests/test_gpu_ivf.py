@@ -1,5 +1,8 @@
 """The inverted-list search on the device (lsq_index_set_lists, lsq_index_search_ivf) against the host checker lsq_ivf_search_cpu bit for bit: both roads,
-host and device forms, the padding, ties and NaN, batches, the two identities of the contract, stage two behind it, and the state of a shared context."""
+host and device forms, the padding, ties and NaN, batches, the two identities of the contract, stage two behind it, and the state of a shared context.
+The named problems of tests/ivf_check.py reach the routes a shape selects -- a block that walks several lists, every loader width, a tail filled to the
+record and eight over, some queries redone over several fall-back batches, a NaN tau, infinities beside the padding, the layout's edges -- and hold
+lsq_ivf_info's road counts to what the numpy checker predicts (tail_hits_np, roads_np)."""
 import ctypes as C
 import os
 import sys
@@ -38,8 +41,9 @@ def _search(ix, Qs, Qc, k, nprobe, **kw):
     return ix.search_ivf(Qs, k, nprobe, Q_coarse=Qc, **kw)
 
 
-def _both_roads(lsq, ixs, p, nprobe, nn, what, flags=0):
-    """default and forced every-record road, with and without the coarse add, on every index: all equal to the checker"""
+def _both_roads(lsq, ixs, p, nprobe, nn, what, flags=0, roads=None):
+    """default and forced every-record road, with and without the coarse add, on every index: all equal to the checker.  roads: _roads' prediction, which
+    the default road's counts are then held to"""
     L = lsq._lib.load()
     Qs, Qc = p[5], p[6]
     for add in (False, True):
@@ -53,6 +57,32 @@ def _both_roads(lsq, ixs, p, nprobe, nn, what, flags=0):
                 assert info["queries"] == Qs.shape[0] and info["threshold_queries"] + info["fallback_queries"] in (0, Qs.shape[0])
                 if every:
                     assert info["threshold_queries"] == 0 and info["fallback_queries"] == 0 and info["tail_capacity"] == 0
+                elif roads is not None:
+                    cap, fallback, records = roads[add][1]
+                    assert (info["tail_capacity"], info["fallback_queries"], info["threshold_queries"], info["records"]) == \
+                        (cap, len(fallback), Qs.shape[0] - len(fallback), records), (what, add, ix._dev)
+
+
+def _roads(p, nprobe, nn):
+    """per coarse-add flag: (tail_hits_np's counts, roads_np's prediction from them) -- which road every query takes, worked out from the checker alone"""
+    out = {}
+    for add in (False, True):
+        hits = ic.tail_hits_np(*p, nprobe, nn, add_coarse=add)
+        assert max(h[1] for h in hits) > 0                                   # some query has a tail: the call is thresholded
+        out[add] = (hits, ic.roads_np(hits, nn))
+    return out
+
+
+def _run_named(lsq, engine, name, flags=0):
+    """a named problem of ivf_check through _both_roads, its road counts held to the checker's -> (arrays, nprobe, nn, roads, host index's plain result)"""
+    p, nprobe, nn = ic.PROBLEMS[name]()
+    roads = _roads(p, nprobe, nn)
+    hix, dix = _indexes(engine, p)
+    with hix, dix:
+        _both_roads(lsq, (hix, dix), p, nprobe, nn, name, flags=flags, roads=roads)
+        got = hix.search_ivf(p[5], nn, nprobe, Q_coarse=p[6], flags=flags)
+        batches = hix.ivf_info()["batches"]
+    return p, nprobe, nn, roads, got, batches
 
 
 @pytest.mark.parametrize("shape", ic.SHAPES, ids=lambda s: "d%d-m%d-nlist%d-nprobe%d-nn%d-nq%d" % s)
@@ -145,6 +175,79 @@ def test_identical_rows_overflow_the_tail_and_fall_back(lsq, engine):
             info = ix.ivf_info()
             assert same_bits(dd, rd) and np.array_equal(di, ri)
             assert info["fallback_queries"] == nq and info["threshold_queries"] == 0 and info["tail_capacity"] == 264
+
+
+@pytest.mark.parametrize("name,flags,splits", [("stride-m8", 0, 7), ("stride-m8", ic.TEST_BATCH, 40), ("stride-m12", 0, 16)],
+                         ids=["m8-splits7", "m8-test-batch", "m12-splits16"])
+def test_a_block_walks_several_lists(lsq, engine, name, flags, splits):
+    """more (query, list) pairs than the scan has blocks for: the stride of a block's list loop, the staged table used for a second list, and the
+    thresholded tail's first list (the head's length) combined with that stride.  Without the batch flag a query gets `splits` < nprobe blocks"""
+    p, nprobe, nn, roads, _, batches = _run_named(lsq, engine, name, flags=flags)
+    nq = p[5].shape[0]
+    assert nq * nprobe > ic.SCAN_BLOCKS
+    assert ic.scan_splits(8 if flags else nq, nprobe) == splits and (flags or 1 < -(-nprobe // splits) <= 6)       # lists per block: up to 6, up to 3
+    assert all(h[1] > 0 for h in roads[False][0])                            # every query has a tail
+    if name == "stride-m12":                                                 # and here some overflow it and some do not: the redone queries are a subset
+        assert 0 < len(roads[False][1][1]) < nq
+    if flags:
+        assert batches == -(-nq // 8) + -(-len(roads[False][1][1]) // 8)
+
+
+@pytest.mark.parametrize("t,over", [(33, False), (34, True)], ids=["fills-the-tail", "eight-over"])
+def test_tail_filled_to_the_record_and_eight_over(lsq, engine, t, over):
+    """a segment fails with count > capacity and the scan writes at < capacity: 264 tail records within tau against 264 slots stay on the thresholded road,
+    272 send every query to the every-record road"""
+    p, nprobe, nn, roads, _, _ = _run_named(lsq, engine, "capacity-%d" % t)
+    nq = p[5].shape[0]
+    hits, (cap, fallback, records) = roads[False]
+    assert cap == 8 * nn + 256 and all(h == (75, 8 * 75, 8 * t) for h in hits) and (8 * t > cap) == over and 8 * 33 == cap
+    assert fallback == (list(range(nq)) if over else []) and (over or records == nq * (75 + cap))
+
+
+@pytest.mark.parametrize("flags", [0, ic.TEST_BATCH], ids=["one-batch", "test-batch"])
+def test_some_queries_fall_back_and_others_do_not(lsq, engine, flags):
+    """the even queries overflow their tails (every record ties tau), the odd ones do not: the redone queries are a non-contiguous selection, and with
+    batches of 8 they are three batches, the second and third starting 8 and 16 entries into it"""
+    p, nprobe, nn, roads, _, batches = _run_named(lsq, engine, "mixed", flags=flags)
+    nq = p[5].shape[0]
+    hits, (cap, fallback, _) = roads[False]
+    assert fallback == list(range(0, nq, 2)) and len(fallback) == 19 and all(hits[q][2] == 7 * 75 for q in fallback)
+    assert max(hits[q][2] for q in range(1, nq, 2)) <= cap == 264
+    assert batches == (5 + 3 if flags else 1 + 1)                            # thresholded batches + fall-back batches
+
+
+def test_nan_tau_keeps_every_record_and_infinities_order(lsq, engine):
+    """a head without a number: tau is NaN, !(dist > tau) keeps every tail record, the query overflows and is redone; +inf and -inf norms elsewhere"""
+    p, nprobe, nn, roads, (dd, di), _ = _run_named(lsq, engine, "nan-tau")
+    nq = p[5].shape[0]
+    for add in (False, True):
+        hits, (cap, fallback, _) = roads[add]
+        assert fallback == list(range(0, nq, 2)) and all(hits[q][2] == hits[q][1] == 7 * 75 for q in fallback)     # kept: all of the tail
+    assert np.all(np.isnan(dd[0::2])) and np.all(di[0::2] > 0)               # NaN distances with their real ids, the nn smallest ids of the probed rows
+    assert np.all(np.isneginf(dd[1::2, 0])) and not np.any(np.isnan(dd[1::2]))
+
+
+def test_real_infinities_and_nan_come_before_the_padding(lsq, engine):
+    p, nprobe, nn = ic.PROBLEMS["short-list"]()
+    hix, dix = _indexes(engine, p)
+    with hix, dix:
+        _both_roads(lsq, (hix, dix), p, nprobe, nn, "short-list")
+        for ix in (hix, dix):
+            dd, di = _search(ix, p[5], p[6], nn, nprobe)
+            assert np.array_equal(di, np.tile([2, 1, 3, 4, 0, 0, 0, 0, 0, 0], (5, 1)))
+            assert np.all(np.isneginf(dd[:, 0])) and np.all(np.isfinite(dd[:, 1])) and np.all(np.isposinf(dd[:, 2])) and np.all(np.isnan(dd[:, 3]))
+            assert np.all(np.isposinf(dd[:, 4:]))
+
+
+@pytest.mark.parametrize("n", [2047, 2048])
+@pytest.mark.parametrize("nlist", [64, 65])
+def test_layout_edges(lsq, engine, n, nlist):
+    """lists 0, 1, 2 and the last three empty, nlist at a power of two and one above it, n at a power of two and one below it; the last row, whose id n is
+    the largest the record's id field holds, is the nearest row of query 0.  Both forms of set_lists (host arrays, device tensors: _indexes)"""
+    p, nprobe, nn, roads, (dd, di), _ = _run_named(lsq, engine, "layout-n%d-nlist%d" % (n, nlist))
+    lor = p[4]
+    assert p[0].shape[0] == n and p[3].shape[0] == nlist and lor.min() == 3 and lor.max() == nlist - 4
+    assert di[0, 0] == n and (n & (n - 1) == 0) == (n == 2048)
 
 
 def _database(n, d, m, nq, seed):

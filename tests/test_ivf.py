@@ -50,6 +50,52 @@ def test_host_checker_returns_the_numpy_contract(lsq, shape, add):
     assert rc1 == 0 and same_bits(d1, dd) and np.array_equal(i1, di)
 
 
+@pytest.mark.parametrize("name", list(ic.PROBLEMS))
+def test_host_checker_returns_the_numpy_contract_on_the_named_problems(lsq, name):
+    """the chain tests/test_gpu_ivf.py rests on: the device is held to lsq_ivf_search_cpu, which is held to ivf_np here, with and without the coarse add"""
+    p, nprobe, nn = ic.PROBLEMS[name]()
+    for add in (False, True):
+        rc, dd, di = ic.ivf_cpu(lsq._lib.load(), *p, nprobe, nn, flags=ic.ADD_COARSE if add else 0)
+        assert rc == 0, lsq._lib.load().lsq_last_error()
+        rd, ri = ic.ivf_np(*p, nprobe, nn, add_coarse=add)
+        assert same_bits(dd, rd) and np.array_equal(di, ri), (name, add)
+
+
+def test_named_problems_are_what_their_names_say():
+    """what the device tests take for granted of the builders, from the numpy checker alone: which queries overflow their tails, by how much, and why"""
+    for name, splits in (("stride-m8", 7), ("stride-m12", 16)):
+        p, nprobe, nn = ic.PROBLEMS[name]()
+        hits = ic.tail_hits_np(*p, nprobe, nn)
+        assert p[5].shape[0] * nprobe > ic.SCAN_BLOCKS and ic.scan_splits(p[5].shape[0], nprobe) == splits < nprobe and all(h[1] > 0 for h in hits)
+    assert 0 < len(ic.roads_np(hits, nn)[1]) < p[5].shape[0]                 # stride-m12: some queries overflow, some do not
+    for t, over in ((33, 0), (34, 37)):
+        p, nprobe, nn = ic.capacity_problem(t)
+        hits = ic.tail_hits_np(*p, nprobe, nn)
+        cap, fallback, records = ic.roads_np(hits, nn)
+        assert cap == 264 and all(h == (75, 600, 8 * t) for h in hits) and len(fallback) == over
+        assert over or records == 37 * (75 + 264)
+    p, nprobe, nn = ic.mixed_problem()
+    hits = ic.tail_hits_np(*p, nprobe, nn)
+    assert ic.roads_np(hits, nn)[:2] == (264, list(range(0, 37, 2))) and all(h[2] == 525 for h in hits[0::2]) and max(h[2] for h in hits[1::2]) <= 264
+    p, nprobe, nn = ic.nan_tau_problem()
+    rd, ri = ic.ivf_np(*p, nprobe, nn)
+    for add in (False, True):
+        hits = ic.tail_hits_np(*p, nprobe, nn, add_coarse=add)
+        assert ic.roads_np(hits, nn)[:2] == (296, list(range(0, 37, 2))) and all(h[2] == h[1] == 525 for h in hits[0::2])
+    assert np.all(np.isnan(rd[0::2])) and np.all(ri[0::2] > 0) and np.all(np.isneginf(rd[1::2, 0])) and not np.any(np.isnan(rd[1::2]))
+    assert np.any(np.isposinf(p[2][p[4] >= 20])) and np.any(np.isneginf(p[2][p[4] >= 20]))
+    p, nprobe, nn = ic.short_list_problem()
+    rd, ri = ic.ivf_np(*p, nprobe, nn)
+    assert np.array_equal(ri, np.tile([2, 1, 3, 4, 0, 0, 0, 0, 0, 0], (5, 1)))
+    assert np.all(np.isneginf(rd[:, 0]) & np.isfinite(rd[:, 1]) & np.isposinf(rd[:, 2]) & np.isnan(rd[:, 3])) and np.all(np.isposinf(rd[:, 4:]))
+    for n in (2047, 2048):
+        for nlist in (64, 65):
+            p, nprobe, nn = ic.layout_problem(n, nlist)
+            counts = np.bincount(p[4], minlength=nlist)
+            assert not counts[:3].any() and not counts[-3:].any() and counts[3:-3].all() and p[0].shape[0] == n and p[3].shape[0] == nlist
+            assert ic.ivf_np(*p, nprobe, nn)[1][0, 0] == n and n in ic.ivf_np(*p, nprobe, nn, add_coarse=True)[1][0]
+
+
 def test_padding_entries_follow_nan_when_the_probed_lists_are_short(lsq):
     codes, K, dbn, cent, lor, Qs, Qc = ic.problem(ic.N, 32, 8, 40, 5, 3)
     lor[:] = 0
