@@ -410,7 +410,7 @@ struct lsq_adc_state {
     DevBuf lut, keys_a, keys_b, tau, count, seg, fail, qsel, tmp;
     // staging of the host-buffer entry point: the database (code rows, or the base rows of an exact search), the queries, the tables, the norms, the results
     DevBuf h_db, h_q, h_tables, h_norms, h_dists, h_idx;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    PhaseClock<5> clock;                         // table, sample, scan, selection of one batch
     bool attr_set = false;
 };
 
@@ -419,8 +419,13 @@ void lsq_adc_free(lsq_adc_state *st) {
     DevBuf *all[] = {&st->lut, &st->keys_a, &st->keys_b, &st->tau, &st->count, &st->seg, &st->fail, &st->qsel, &st->tmp,
                   &st->h_db, &st->h_q, &st->h_tables, &st->h_norms, &st->h_dists, &st->h_idx};
     for (DevBuf *b : all) b->release();
-    for (hipEvent_t e : st->ev) if (e) (void)hipEventDestroy(e);
+    st->clock.release();
     delete st;
+}
+
+int64_t lsq_adc_batch_queries(int64_t per_query) {
+    const int64_t qb = (int64_t)(1u << 28) / per_query;
+    return qb > 16384 ? 16384 : (qb < 1 ? 1 : qb);
 }
 
 int lsq_adc_idbits(int64_t n) {
@@ -562,15 +567,16 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ls
     if (tables) LSQ_TRY(st->lut.ensure(sizeof(float) * (size_t)tiles * entries * QT));
     LSQ_TRY(st->seg.ensure(sizeof(int) * 2 * (size_t)nqb));
     LSQ_TRY(st->fail.ensure(sizeof(int) * (size_t)nqb));
-    if (timed) LSQ_HIP(hipEventRecord(st->ev[0], s));
+    LSQ_TRY(st->clock.begin(timed));
+    LSQ_TRY(st->clock.mark(s));
     if (tables) LSQ_TRY(launch_lut<QT>(s, in, qsel, q0, nqb, st->lut.as<float>()));
-    if (timed) LSQ_HIP(hipEventRecord(st->ev[1], s));
+    LSQ_TRY(st->clock.mark(s));
     if (P.exhaustive) {
         LSQ_TRY(st->keys_a.ensure(sizeof(uint64_t) * (size_t)nqb * n));
         LSQ_TRY(st->keys_b.ensure(sizeof(uint64_t) * (size_t)nqb * n));
-        if (timed) { LSQ_HIP(hipEventRecord(st->ev[2], s)); }
+        LSQ_TRY(st->clock.mark(s));
         LSQ_TRY((launch_producer<QT, 1>(s, st->lut.as<float>(), in, qsel, q0, nqb, 1, n, nullptr, nullptr, n, st->keys_a.as<uint64_t>(), idbits)));
-        if (timed) LSQ_HIP(hipEventRecord(st->ev[3], s));
+        LSQ_TRY(st->clock.mark(s));
         LSQ_TRY(lsq_adc_select(&st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), st->seg.as<int>(), nullptr, nullptr, qsel, q0, nqb, n, nn,
                                dists, idx, idbits, 32 + idbits, in.id_sub()));
         if (stats) stats->candidates += (int64_t)nqb * n;
@@ -585,11 +591,11 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ls
                                         idbits)));
         hipLaunchKernelGGL(adc_rank_select_kernel, dim3((unsigned)nqb), dim3(256), 0, s, st->keys_b.as<uint32_t>(), P.r, st->tau.as<uint32_t>());
         LSQ_HIP(hipMemsetAsync(st->count.p, 0, sizeof(unsigned) * (size_t)nqb, s));
-        if (timed) LSQ_HIP(hipEventRecord(st->ev[2], s));
+        LSQ_TRY(st->clock.mark(s));
         // the scan proper
         LSQ_TRY((launch_producer<QT, 0>(s, st->lut.as<float>(), in, qsel, q0, nqb, 1, n, st->tau.as<uint32_t>(), st->count.as<unsigned>(), P.cap,
                                         st->keys_a.as<uint64_t>(), idbits)));
-        if (timed) LSQ_HIP(hipEventRecord(st->ev[3], s));
+        LSQ_TRY(st->clock.mark(s));
         LSQ_TRY(lsq_adc_select(&st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(),
                                st->fail.as<int>(), qsel, q0, nqb, P.cap, nn, dists, idx, idbits, 32 + idbits, in.id_sub()));
         LSQ_HIP(hipMemcpyAsync(h_fail, st->fail.p, sizeof(int) * (size_t)nqb, hipMemcpyDeviceToHost, s));
@@ -600,16 +606,12 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ls
             for (unsigned c : hc) stats->candidates += c;
         }
     }
+    LSQ_TRY(st->clock.mark(s));
     if (timed) {
-        LSQ_HIP(hipEventRecord(st->ev[4], s));
-        LSQ_HIP(hipEventSynchronize(st->ev[4]));
-        float a = 0, b = 0, c = 0, e = 0;
-        LSQ_HIP(hipEventElapsedTime(&a, st->ev[0], st->ev[1]));
-        LSQ_HIP(hipEventElapsedTime(&b, st->ev[1], st->ev[2]));
-        LSQ_HIP(hipEventElapsedTime(&c, st->ev[2], st->ev[3]));
-        LSQ_HIP(hipEventElapsedTime(&e, st->ev[3], st->ev[4]));
-        if (!tables) a = 0.0f;
-        stats->lut_ms += a; stats->sample_ms += b; stats->scan_ms += c; stats->select_ms += e;
+        float ms[4];
+        LSQ_TRY(st->clock.read(ms));
+        if (tables) stats->lut_ms += ms[0];
+        stats->sample_ms += ms[1]; stats->scan_ms += ms[2]; stats->select_ms += ms[3];
     } else {
         LSQ_HIP(hipStreamSynchronize(s));
     }
@@ -624,17 +626,13 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
     lsq_linscan_stats *stats = opt.stats;
     const int n = in.n;
     const bool timed = opt.timed != 0;
-    if (timed) for (hipEvent_t &e : st->ev) if (!e) LSQ_HIP(hipEventCreate(&e));
     Plan P = make_plan(n, nn, opt.force_exhaustive);
     if (!P.exhaustive && opt.rank_override > 0) {    // test hook: a deliberately wrong threshold rank (forces the fallback road)
         P.r = opt.rank_override < P.ns ? opt.rank_override : P.ns;
     }
     const bool wide = lsq_adc_lut_qt(in.m) == 16;    // 16 queries per block up to m = 8 (128 KiB of tables), 8 above
     const int64_t per_query = P.exhaustive ? n : (P.cap > P.ns ? P.cap : P.ns);
-    // batches of queries: two key buffers of per_query entries each, at most ~2 GiB apiece, and hipcub counts items in int
-    int64_t qb = (int64_t)(1u << 28) / per_query;
-    if (qb < 1) qb = 1;
-    if (qb > 16384) qb = 16384;
+    int64_t qb = lsq_adc_batch_queries(per_query);   // two key buffers of per_query entries per query; whole tiles of 16 queries
     if (qb > 16) qb &= ~(int64_t)15;
     std::vector<int> h_fail;
     std::vector<int> failed;
@@ -653,8 +651,8 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
         // the exhaustive road for the queries whose candidate list came out short or overflowed
         Plan E = P;
         E.exhaustive = true; E.cap = n;
-        int64_t fb = (int64_t)(1u << 28) / n;
-        if (fb < 1) fb = 1;
+        static_assert(ADC_SMALL_N >= 16384, "n > ADC_SMALL_N on this road: the rule's limit of 16384 queries is never what decides here");
+        int64_t fb = lsq_adc_batch_queries(n);
         if (fb > 16) fb &= ~(int64_t)15;
         LSQ_TRY(st->qsel.ensure(sizeof(int) * failed.size()));
         LSQ_HIP(hipMemcpyAsync(st->qsel.p, failed.data(), sizeof(int) * failed.size(), hipMemcpyHostToDevice, s));

@@ -547,7 +547,7 @@ struct lsq_index {
     DevBuf nrm_x, nrm_q;                               // lsq_index_knn's integer road: uint32 squared norms of the rows and of the queries, refilled at every call
     lsq_ivf_state *ivf = nullptr;                      // the inverted lists (lsq_ivf.hip): layout and scratch of THIS index; null until lsq_index_set_lists
     DevBuf s_qcoarse;                                  // lsq_index_search_ivf's staging of host q_coarse rows
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    PhaseClock<3> clock;                               // a re-rank batch's gather and selection; lsq_index_knn's norm pass
     lsq_index_stats stats{};
     lsq_index_knn_info knn{};
 };
@@ -561,7 +561,7 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     for (DevBuf *b : bufs) b->release();
     lsq_adc_free(ix->adc);
     lsq_ivf_free(ix->ivf);
-    for (hipEvent_t e : ix->ev) if (e) (void)hipEventDestroy(e);
+    ix->clock.release();
     delete ix;
     return LSQ_OK;
 }
@@ -616,13 +616,9 @@ extern "C" int lsq_index_create(lsq_index **out, lsq_ctx *c, const lsq_index_des
 static int index_rerank_dev(lsq_index *ix, float *d_dists, int *d_ids, const float *d_q, int64_t ldq, const int *d_cand, int nq, int L, int nn, int id_base) {
     lsq_ctx *c = ix->ctx;
     hipStream_t s = c->stream;
-    const bool timed = c->profile != 0;
-    if (timed) for (hipEvent_t &e : ix->ev) if (!e) LSQ_HIP(hipEventCreate(&e));
-    // two record buffers of qb L <= 2^28 entries (L <= 2^28: both callers check it before anything is launched); hipcub counts items in int
-    int64_t qb = c->rerank_batch > 0 ? c->rerank_batch : (int64_t)(1u << 28) / L;
-    if (qb > (int64_t)(1u << 28) / L) qb = (int64_t)(1u << 28) / L;
-    if (qb > 16384) qb = 16384;                       // (the hand-out's grid counts queries in its y dimension)
-    if (qb < 1) qb = 1;
+    // L record slots per query (L <= 2^28: every caller checks it before anything is launched); option "rerank_batch" only makes batches smaller
+    int64_t qb = lsq_adc_batch_queries(L);
+    if (c->rerank_batch > 0 && c->rerank_batch < qb) qb = c->rerank_batch;
     if (qb > nq) qb = nq;
     LSQ_TRY(ix->rec_a.ensure(sizeof(uint64_t) * (size_t)qb * L));
     LSQ_TRY(ix->rec_b.ensure(sizeof(uint64_t) * (size_t)qb * L));
@@ -631,21 +627,18 @@ static int index_rerank_dev(lsq_index *ix, float *d_dists, int *d_ids, const flo
     const int idbits = lsq_adc_idbits(ix->n);
     for (int q0 = 0; q0 < nq; q0 += (int)qb) {
         const int nqb = (int)std::min<int64_t>(qb, nq - q0);
-        if (timed) LSQ_HIP(hipEventRecord(ix->ev[0], s));
+        LSQ_TRY(ix->clock.begin(c->profile != 0));
+        LSQ_TRY(ix->clock.mark(s));
         LSQ_TRY(lsq_rerank_launch(s, ix->base, ix->base_u8, ix->ldb, ix->n, d_q, ldq, d_cand, q0, nqb, L, ix->d, id_base, ix->rec_a.as<uint64_t>(), idbits,
                                   ix->counter.as<unsigned long long>()));
-        if (timed) LSQ_HIP(hipEventRecord(ix->ev[1], s));
+        LSQ_TRY(ix->clock.mark(s));
         // records: (outside-the-base bit, distance key, row + 1); the gather hands out row + 1 - (1 - id_base)
         LSQ_TRY(lsq_adc_select(&ix->adc, s, ix->rec_a.as<uint64_t>(), ix->rec_b.as<uint64_t>(), ix->seg.as<int>(), nullptr, nullptr, nullptr, q0, nqb, L, nn,
                                d_dists, d_ids, idbits, 33 + idbits, 1 - id_base));
-        if (timed) {
-            LSQ_HIP(hipEventRecord(ix->ev[2], s));
-            LSQ_HIP(hipEventSynchronize(ix->ev[2]));
-            float a = 0, b = 0;
-            LSQ_HIP(hipEventElapsedTime(&a, ix->ev[0], ix->ev[1]));
-            LSQ_HIP(hipEventElapsedTime(&b, ix->ev[1], ix->ev[2]));
-            ix->stats.gather_ms += a; ix->stats.select_ms += b;
-        }
+        LSQ_TRY(ix->clock.mark(s));
+        float ms[2];
+        LSQ_TRY(ix->clock.read(ms));                  // (untimed: zeros, and no wait)
+        ix->stats.gather_ms += ms[0]; ix->stats.select_ms += ms[1];
         ix->stats.batches += 1;
     }
     unsigned long long bad = 0;
@@ -656,23 +649,55 @@ static int index_rerank_dev(lsq_index *ix, float *d_dists, int *d_ids, const flo
     return LSQ_OK;
 }
 
-// rows [rows][ld] of src (host or device) -> dst on the device: as they are when `pack` is 0 (ld floats apart), compacted to `width` floats otherwise
-static int index_stage_rows(lsq_index *ix, DevBuf &buf, const float *src, int rows, int64_t ld, int width, bool pack, const float **dst, int64_t *ld_out) {
-    hipStream_t s = ix->ctx->stream;
-    if (pack && ld != width) {
-        LSQ_TRY(buf.ensure(sizeof(float) * (size_t)rows * width));
-        LSQ_HIP(hipMemcpy2DAsync(buf.p, sizeof(float) * (size_t)width, src, sizeof(float) * (size_t)ld, sizeof(float) * (size_t)width, (size_t)rows,
-                                 hipMemcpyDefault, s));
-        *ld_out = width;
-    } else {
-        const size_t floats = (size_t)(rows - 1) * (size_t)ld + (size_t)width;
-        LSQ_TRY(buf.ensure(sizeof(float) * floats));
-        LSQ_HIP(hipMemcpyAsync(buf.p, src, sizeof(float) * floats, hipMemcpyDefault, s));
-        *ld_out = ld;
+// The buffers of one call on an index, said once for its four entry points (the recipe of the host forms): where the device reads the call's
+// rows, where it writes the results, and how the call ends.  dev: the caller's pointers are device pointers (on_device)
+struct IndexCall {
+    lsq_index *ix;
+    int nq;
+    bool dev;
+    float *dists = nullptr, *out_d = nullptr;
+    int *ids = nullptr, *out_i = nullptr;
+    size_t items = 0;
+    // nq rows of `width` elements of `elem` bytes, ld elements apart, at src (host or device) -> device rows *dst, *ld_out apart.  stage = 0: read where they
+    // lie.  Otherwise copied to buf: as they lie up to the width-th element of the last row (pack = 0), or compacted to `width` elements apart
+    template <class T>
+    int rows(DevBuf &buf, const T *src, size_t elem, int64_t ld, int width, bool pack, bool stage, const T **dst, int64_t *ld_out) {
+        hipStream_t s = ix->ctx->stream;
+        *dst = src; *ld_out = ld;
+        if (!stage) return LSQ_OK;
+        if (pack && ld != width) {
+            LSQ_TRY(buf.ensure(elem * (size_t)nq * width));
+            LSQ_HIP(hipMemcpy2DAsync(buf.p, elem * (size_t)width, src, elem * (size_t)ld, elem * (size_t)width, (size_t)nq, hipMemcpyDefault, s));
+            *ld_out = width;
+        } else {
+            const size_t bytes = elem * ((size_t)(nq - 1) * (size_t)ld + (size_t)width);
+            LSQ_TRY(buf.ensure(bytes));
+            LSQ_HIP(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyDefault, s));
+        }
+        *dst = static_cast<const T *>(buf.p);
+        return LSQ_OK;
     }
-    *dst = buf.as<float>();
-    return LSQ_OK;
-}
+    // results [nq][nn]: the device form writes straight into the caller's arrays, the host form into the index's staging
+    int outputs(float *caller_d, int *caller_i, int nn) {
+        dists = out_d = caller_d; ids = out_i = caller_i; items = (size_t)nq * (size_t)nn;
+        if (dev) return LSQ_OK;
+        LSQ_TRY(ix->s_dists.ensure(sizeof(float) * items));
+        LSQ_TRY(ix->s_ids.ensure(sizeof(int) * items));
+        out_d = ix->s_dists.as<float>(); out_i = ix->s_ids.as<int>();
+        return LSQ_OK;
+    }
+    // host form: the two fetches and the call's one wait of its own
+    int finish() {
+        if (!dev) {
+            hipStream_t s = ix->ctx->stream;
+            LSQ_HIP(hipMemcpyAsync(dists, out_d, sizeof(float) * items, hipMemcpyDeviceToHost, s));
+            LSQ_HIP(hipMemcpyAsync(ids, out_i, sizeof(int) * items, hipMemcpyDeviceToHost, s));
+            LSQ_HIP(hipStreamSynchronize(s));
+        }
+        ix->stats.queries += nq;
+        return LSQ_OK;
+    }
+};
 
 static int index_call_check(const char *fn, lsq_index *ix, const void *dists, const void *ids, int nq, int64_t ldq, int nn) {
     if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
@@ -689,75 +714,73 @@ extern "C" int lsq_index_rerank(lsq_index *ix, float *dists, int *ids, const flo
     if (L > (1 << 28)) { lsq_set_error("lsq_index_rerank: needs L <= 2^28 candidates per query (got %d)", L); return LSQ_EINVAL; }      // a batch is >= 1 query
     if (nq == 0) return LSQ_OK;
     LSQ_TRY(use_device(ix->ctx));
-    hipStream_t s = ix->ctx->stream;
-    if (on_device) {
-        LSQ_TRY(index_rerank_dev(ix, dists, ids, queries, ldq, cand, nq, L, nn, id_base));
-    } else {
-        const float *dq = nullptr;
-        int64_t ld = 0;
-        LSQ_TRY(index_stage_rows(ix, ix->s_qexact, queries, nq, ldq, ix->d, false, &dq, &ld));
-        LSQ_TRY(ix->s_cand.ensure(sizeof(int) * (size_t)nq * L));
-        LSQ_TRY(ix->s_dists.ensure(sizeof(float) * (size_t)nq * nn));
-        LSQ_TRY(ix->s_ids.ensure(sizeof(int) * (size_t)nq * nn));
-        LSQ_HIP(hipMemcpyAsync(ix->s_cand.p, cand, sizeof(int) * (size_t)nq * L, hipMemcpyHostToDevice, s));
-        LSQ_TRY(index_rerank_dev(ix, ix->s_dists.as<float>(), ix->s_ids.as<int>(), dq, ld, ix->s_cand.as<int>(), nq, L, nn, id_base));
-        LSQ_HIP(hipMemcpyAsync(dists, ix->s_dists.p, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
-        LSQ_HIP(hipMemcpyAsync(ids, ix->s_ids.p, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
-        LSQ_HIP(hipStreamSynchronize(s));
-    }
-    ix->stats.queries += nq;
+    IndexCall call{ix, nq, on_device != 0};
+    const float *dq = nullptr;
+    const int *dc = nullptr;
+    int64_t ld = 0, ldc = 0;
+    LSQ_TRY(call.rows(ix->s_qexact, queries, sizeof(float), ldq, ix->d, false, !on_device, &dq, &ld));      // both as they lie
+    LSQ_TRY(call.rows(ix->s_cand, cand, sizeof(int), L, L, false, !on_device, &dc, &ldc));
+    LSQ_TRY(call.outputs(dists, ids, nn));
+    LSQ_TRY(index_rerank_dev(ix, call.out_d, call.out_i, dq, ld, dc, nq, L, nn, id_base));
+    return call.finish();
+}
+
+// the shortlist of a two-stage call -> *L, the length of stage one's lists
+static int index_shortlist(const char *fn, int shortlist, int nn, int *L) {
+    if (shortlist < 0 || (shortlist > 0 && shortlist < nn)) { lsq_set_error("%s: needs shortlist == 0 or shortlist >= nn (got shortlist=%d nn=%d)", fn, shortlist, nn); return LSQ_EINVAL; }
+    *L = shortlist > 0 ? shortlist : nn;
     return LSQ_OK;
 }
 
-extern "C" int lsq_index_search(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_exact, int nq, int ldq, int shortlist, int nn,
-                                int on_device) {
-    LSQ_TRY(index_call_check("lsq_index_search", ix, dists, ids, nq, ldq, nn));
-    if (!ix->codes) { lsq_set_error("lsq_index_search: the index holds no codes"); return LSQ_EINVAL; }
-    if (shortlist < 0 || (shortlist > 0 && shortlist < nn)) { lsq_set_error("lsq_index_search: needs shortlist == 0 or shortlist >= nn (got shortlist=%d nn=%d)", shortlist, nn); return LSQ_EINVAL; }
-    const int L = shortlist > 0 ? shortlist : nn;
-    if (L > ix->n) { lsq_set_error("lsq_index_search: %s=%d exceeds the database size %lld", shortlist > 0 ? "shortlist" : "nn", L, (long long)ix->n); return LSQ_EINVAL; }
-    if (shortlist > (1 << 28)) { lsq_set_error("lsq_index_search: needs shortlist <= 2^28 (got %d)", shortlist); return LSQ_EINVAL; }
-    if (shortlist > 0 && !ix->base) { lsq_set_error("lsq_index_search: a shortlist needs base rows, the index holds none"); return LSQ_EINVAL; }
-    if (!q_scan || (shortlist > 0 && !q_exact)) { lsq_set_error("lsq_index_search: null pointer"); return LSQ_EINVAL; }
+// The two-stage road, after the entry point's own checks: stage1(scan_d, scan_i, dqs, L) -> int fills lists [nq][L] of (distance, 1-based id) from the scan
+// queries dqs [nq][d]; with a shortlist these are re-ranked to nn by exact distance (an id outside the base, stage one's (+inf, 0), is never dereferenced
+// and comes last), without one they are the results
+template <class Stage1>
+static int index_two_stage(const char *fn, IndexCall &call, float *dists, int *ids, const float *q_scan, const float *q_exact, int ldq, int shortlist,
+                           int nn, int L, Stage1 stage1) {
+    lsq_index *ix = call.ix;
+    const int nq = call.nq, d = ix->d;
+    if (shortlist > 0 && !ix->base) { lsq_set_error("%s: a shortlist needs base rows, the index holds none", fn); return LSQ_EINVAL; }
+    if (!q_scan || (shortlist > 0 && !q_exact)) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
     if (nq == 0) return LSQ_OK;
-    lsq_ctx *c = ix->ctx;
-    LSQ_TRY(use_device(c));
-    hipStream_t s = c->stream;
-    const int d = ix->d;
-    // the scan reads query rows d floats apart
-    const float *dqs = q_scan;
-    int64_t ld = ldq;
-    if (!on_device || ldq != d) LSQ_TRY(index_stage_rows(ix, ix->s_qscan, q_scan, nq, ldq, d, true, &dqs, &ld));
-    const float *dqe = q_exact;
-    int64_t lde = ldq;
-    if (shortlist > 0 && !on_device) LSQ_TRY(index_stage_rows(ix, ix->s_qexact, q_exact, nq, ldq, d, false, &dqe, &lde));
-    float *out_d = dists;
-    int *out_i = ids;
-    if (!on_device) {
-        LSQ_TRY(ix->s_dists.ensure(sizeof(float) * (size_t)nq * nn));
-        LSQ_TRY(ix->s_ids.ensure(sizeof(int) * (size_t)nq * nn));
-        out_d = ix->s_dists.as<float>();
-        out_i = ix->s_ids.as<int>();
-    }
-    float *scan_d = out_d;
-    int *scan_i = out_i;
+    LSQ_TRY(use_device(ix->ctx));
+    // stage one reads query rows d floats apart; the re-rank reads rows as they lie
+    const float *dqs = nullptr, *dqe = nullptr;
+    int64_t ld = 0, lde = 0;
+    LSQ_TRY(call.rows(ix->s_qscan, q_scan, sizeof(float), ldq, d, true, !call.dev || ldq != d, &dqs, &ld));
+    if (shortlist > 0) LSQ_TRY(call.rows(ix->s_qexact, q_exact, sizeof(float), ldq, d, false, !call.dev, &dqe, &lde));
+    LSQ_TRY(call.outputs(dists, ids, nn));
+    float *scan_d = call.out_d;
+    int *scan_i = call.out_i;
     if (shortlist > 0) {
         LSQ_TRY(ix->short_d.ensure(sizeof(float) * (size_t)nq * L));
         LSQ_TRY(ix->short_i.ensure(sizeof(int) * (size_t)nq * L));
         scan_d = ix->short_d.as<float>();
         scan_i = ix->short_i.as<int>();
     }
-    lsq_linscan_stats st{};
-    LSQ_TRY(lsq_adc_search(s, &ix->adc, scan_d, scan_i, lsq_input(ix->codes, dqs, ix->K, ix->norms, (int)ix->n, ix->m, d), nq, L, search_opts(c, &st)));
-    ix->stats.scan_ms += st.lut_ms + st.sample_ms + st.scan_ms + st.select_ms;
-    if (shortlist > 0) LSQ_TRY(index_rerank_dev(ix, out_d, out_i, dqe, lde, scan_i, nq, L, nn, 1));      // the scan's ids are 1-based
-    if (!on_device) {
-        LSQ_HIP(hipMemcpyAsync(dists, out_d, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
-        LSQ_HIP(hipMemcpyAsync(ids, out_i, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
-        LSQ_HIP(hipStreamSynchronize(s));
-    }
-    ix->stats.queries += nq;
-    return LSQ_OK;
+    LSQ_TRY(stage1(scan_d, scan_i, dqs, L));
+    if (shortlist > 0) LSQ_TRY(index_rerank_dev(ix, call.out_d, call.out_i, dqe, lde, scan_i, nq, L, nn, 1));
+    return call.finish();
+}
+
+extern "C" int lsq_index_search(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_exact, int nq, int ldq, int shortlist, int nn,
+                                int on_device) {
+    LSQ_TRY(index_call_check("lsq_index_search", ix, dists, ids, nq, ldq, nn));
+    if (!ix->codes) { lsq_set_error("lsq_index_search: the index holds no codes"); return LSQ_EINVAL; }
+    int L = 0;
+    LSQ_TRY(index_shortlist("lsq_index_search", shortlist, nn, &L));
+    if (L > ix->n) { lsq_set_error("lsq_index_search: %s=%d exceeds the database size %lld", shortlist > 0 ? "shortlist" : "nn", L, (long long)ix->n); return LSQ_EINVAL; }
+    if (shortlist > (1 << 28)) { lsq_set_error("lsq_index_search: needs shortlist <= 2^28 (got %d)", shortlist); return LSQ_EINVAL; }
+    lsq_ctx *c = ix->ctx;
+    IndexCall call{ix, nq, on_device != 0};
+    return index_two_stage("lsq_index_search", call, dists, ids, q_scan, q_exact, ldq, shortlist, nn, L,
+                           [&](float *scan_d, int *scan_i, const float *dqs, int len) -> int {      // the ADC scan of every row
+        lsq_linscan_stats st{};
+        LSQ_TRY(lsq_adc_search(c->stream, &ix->adc, scan_d, scan_i, lsq_input(ix->codes, dqs, ix->K, ix->norms, (int)ix->n, ix->m, ix->d), nq, len,
+                               search_opts(c, &st)));
+        ix->stats.scan_ms += st.lut_ms + st.sample_ms + st.scan_ms + st.select_ms;
+        return LSQ_OK;
+    });
 }
 
 // exact k-NN over the resident base rows: lsq_knn_exact_dev's search (lsq_adc_search on the "exact" input) with the index's own scan state
@@ -776,55 +799,37 @@ extern "C" int lsq_index_knn(lsq_index *ix, float *dists, int *ids, const void *
     LSQ_TRY(use_device(c));
     hipStream_t s = c->stream;
     const int n = (int)ix->n, d = ix->d;
-    const size_t qe = q_u8 ? 1 : sizeof(float), out_items = (size_t)nq * (size_t)nn;
-    const void *dq = queries;
-    float *out_d = dists;
-    int *out_i = ids;
-    if (!on_device) {                                 // query rows up to the d-th element of the last one, as they lie
-        const size_t q_bytes = qe * ((size_t)(nq - 1) * (size_t)ldq + (size_t)d);
-        LSQ_TRY(ix->s_qexact.ensure(q_bytes));
-        LSQ_TRY(ix->s_dists.ensure(sizeof(float) * out_items));
-        LSQ_TRY(ix->s_ids.ensure(sizeof(int) * out_items));
-        LSQ_HIP(hipMemcpyAsync(ix->s_qexact.p, queries, q_bytes, hipMemcpyHostToDevice, s));
-        dq = ix->s_qexact.p;
-        out_d = ix->s_dists.as<float>();
-        out_i = ix->s_ids.as<int>();
-    }
+    IndexCall call{ix, nq, on_device != 0};
+    const void *dq = nullptr;
+    int64_t ld = 0;
+    LSQ_TRY(call.rows(ix->s_qexact, queries, q_u8 ? 1 : sizeof(float), ldq, d, false, !on_device, &dq, &ld));      // as they lie
+    LSQ_TRY(call.outputs(dists, ids, nn));
     lsq_search_input in = exact_input(ix->base, ix->base_u8, (int)ix->ldb, dq, q_u8, ldq, n, d);
     in.id_base = id_base;
     const bool int_road = ix->base_u8 && q_u8 && d <= 258 && c->knn_u8_int;      // d 255^2 <= 2^24: (float)D is the chain's result
     lsq_index_knn_info info{};
     if (int_road) {
         // nothing is cached across calls: a borrowed base may have changed since the last one
-        const bool timed = c->profile != 0;
-        if (timed) for (hipEvent_t &e : ix->ev) if (!e) LSQ_HIP(hipEventCreate(&e));
         LSQ_TRY(ix->nrm_x.ensure(sizeof(uint32_t) * (size_t)n));
         LSQ_TRY(ix->nrm_q.ensure(sizeof(uint32_t) * (size_t)nq));
-        if (timed) LSQ_HIP(hipEventRecord(ix->ev[0], s));
+        LSQ_TRY(ix->clock.begin(c->profile != 0));
+        LSQ_TRY(ix->clock.mark(s));
         LSQ_TRY(lsq_knn_launch_norms_u8(s, static_cast<const uint8_t *>(ix->base), ix->ldb, n, d, ix->nrm_x.as<uint32_t>()));
         LSQ_TRY(lsq_knn_launch_norms_u8(s, static_cast<const uint8_t *>(dq), ldq, nq, d, ix->nrm_q.as<uint32_t>()));
-        if (timed) {
-            LSQ_HIP(hipEventRecord(ix->ev[1], s));
-            LSQ_HIP(hipEventSynchronize(ix->ev[1]));
-            float ms = 0;
-            LSQ_HIP(hipEventElapsedTime(&ms, ix->ev[0], ix->ev[1]));
-            info.norms_ms = ms;
-        }
+        LSQ_TRY(ix->clock.mark(s));
+        float ms[2];
+        LSQ_TRY(ix->clock.read(ms));
+        info.norms_ms = ms[0];
         in.xnorms = ix->nrm_x.as<uint32_t>();
         in.qnorms = ix->nrm_q.as<uint32_t>();
     }
     lsq_linscan_stats st{};
-    LSQ_TRY(lsq_adc_search(s, &ix->adc, out_d, out_i, in, nq, nn, search_opts(c, &st)));
-    if (!on_device) {
-        LSQ_HIP(hipMemcpyAsync(dists, out_d, sizeof(float) * out_items, hipMemcpyDeviceToHost, s));
-        LSQ_HIP(hipMemcpyAsync(ids, out_i, sizeof(int) * out_items, hipMemcpyDeviceToHost, s));
-        LSQ_HIP(hipStreamSynchronize(s));
-    }
+    LSQ_TRY(lsq_adc_search(s, &ix->adc, call.out_d, call.out_i, in, nq, nn, search_opts(c, &st)));
+    LSQ_TRY(call.finish());
     info.queries = nq; info.rows = n; info.batches = st.batches; info.fallback_queries = st.fallback_queries; info.exhaustive = st.exhaustive;
     info.int_road = int_road ? 1 : 0;
     info.scan_ms = st.sample_ms + st.scan_ms; info.select_ms = st.select_ms;
     ix->knn = info;
-    ix->stats.queries += nq;
     return LSQ_OK;
 }
 
@@ -858,49 +863,18 @@ extern "C" int lsq_index_search_ivf(lsq_index *ix, float *dists, int *ids, const
     if (nlist < 1) { lsq_set_error("lsq_index_search_ivf: the index has no lists (call lsq_index_set_lists first)"); return LSQ_EINVAL; }
     if (flags & ~(LSQ_IVF_ADD_COARSE | LSQ_IVF_EVERY_RECORD | LSQ_IVF_TEST_BATCH)) { lsq_set_error("lsq_index_search_ivf: unknown flags %d", flags); return LSQ_EINVAL; }
     if (nprobe < 1 || nprobe > nlist) { lsq_set_error("lsq_index_search_ivf: needs 1 <= nprobe <= nlist (got nprobe=%d nlist=%d)", nprobe, nlist); return LSQ_EINVAL; }
-    if (shortlist < 0 || (shortlist > 0 && shortlist < nn)) { lsq_set_error("lsq_index_search_ivf: needs shortlist == 0 or shortlist >= nn (got shortlist=%d nn=%d)", shortlist, nn); return LSQ_EINVAL; }
-    const int L = shortlist > 0 ? shortlist : nn;
+    int L = 0;
+    LSQ_TRY(index_shortlist("lsq_index_search_ivf", shortlist, nn, &L));
     if (L > (1 << 28)) { lsq_set_error("lsq_index_search_ivf: needs nn and shortlist <= 2^28 (got %d)", L); return LSQ_EINVAL; }
-    if (shortlist > 0 && !ix->base) { lsq_set_error("lsq_index_search_ivf: a shortlist needs base rows, the index holds none"); return LSQ_EINVAL; }
-    if (!q_scan || (shortlist > 0 && !q_exact)) { lsq_set_error("lsq_index_search_ivf: null pointer"); return LSQ_EINVAL; }
-    if (nq == 0) return LSQ_OK;
     lsq_ctx *c = ix->ctx;
-    LSQ_TRY(use_device(c));
-    hipStream_t s = c->stream;
-    const int d = ix->d;
-    if (!q_coarse) q_coarse = q_scan;
-    // the tables read query rows d floats apart; the coarse search and the re-rank read rows as they lie
-    const float *dqs = q_scan, *dqc = q_coarse, *dqe = q_exact;
-    int64_t ld = ldq, ldc = ldq, lde = ldq;
-    if (!on_device || ldq != d) LSQ_TRY(index_stage_rows(ix, ix->s_qscan, q_scan, nq, ldq, d, true, &dqs, &ld));
-    if (!on_device) LSQ_TRY(index_stage_rows(ix, ix->s_qcoarse, q_coarse, nq, ldq, d, false, &dqc, &ldc));
-    if (shortlist > 0 && !on_device) LSQ_TRY(index_stage_rows(ix, ix->s_qexact, q_exact, nq, ldq, d, false, &dqe, &lde));
-    float *out_d = dists;
-    int *out_i = ids;
-    if (!on_device) {
-        LSQ_TRY(ix->s_dists.ensure(sizeof(float) * (size_t)nq * nn));
-        LSQ_TRY(ix->s_ids.ensure(sizeof(int) * (size_t)nq * nn));
-        out_d = ix->s_dists.as<float>();
-        out_i = ix->s_ids.as<int>();
-    }
-    float *scan_d = out_d;
-    int *scan_i = out_i;
-    if (shortlist > 0) {
-        LSQ_TRY(ix->short_d.ensure(sizeof(float) * (size_t)nq * L));
-        LSQ_TRY(ix->short_i.ensure(sizeof(int) * (size_t)nq * L));
-        scan_d = ix->short_d.as<float>();
-        scan_i = ix->short_i.as<int>();
-    }
-    LSQ_TRY(lsq_ivf_search(s, ix->ivf, &ix->adc, ix->K, scan_d, scan_i, dqs, dqc, ldc, nq, nprobe, L, flags, c->search, c->profile));
-    // the scan's ids are 1-based; its (+inf, 0) entries are ids outside the base: never dereferenced, last
-    if (shortlist > 0) LSQ_TRY(index_rerank_dev(ix, out_d, out_i, dqe, lde, scan_i, nq, L, nn, 1));
-    if (!on_device) {
-        LSQ_HIP(hipMemcpyAsync(dists, out_d, sizeof(float) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
-        LSQ_HIP(hipMemcpyAsync(ids, out_i, sizeof(int) * (size_t)nq * nn, hipMemcpyDeviceToHost, s));
-        LSQ_HIP(hipStreamSynchronize(s));
-    }
-    ix->stats.queries += nq;
-    return LSQ_OK;
+    IndexCall call{ix, nq, on_device != 0};
+    return index_two_stage("lsq_index_search_ivf", call, dists, ids, q_scan, q_exact, ldq, shortlist, nn, L,
+                           [&](float *scan_d, int *scan_i, const float *dqs, int len) -> int {      // the scan of each query's probed lists
+        const float *dqc = nullptr;                   // the coarse search reads rows as they lie
+        int64_t ldc = 0;
+        LSQ_TRY(call.rows(ix->s_qcoarse, q_coarse ? q_coarse : q_scan, sizeof(float), ldq, ix->d, false, !on_device, &dqc, &ldc));
+        return lsq_ivf_search(c->stream, ix->ivf, &ix->adc, ix->K, scan_d, scan_i, dqs, dqc, ldc, nq, nprobe, len, flags, c->search, c->profile);
+    });
 }
 
 extern "C" int lsq_index_get_ivf_info(lsq_index *ix, lsq_ivf_info *out) {
@@ -918,7 +892,7 @@ struct lsq_encoder {
     DevBuf K, sci, T;                                  // the codebooks' copy, ||c||^2, T[j][k][b][a] = 2 <c_kb, c_ja>
     DevBuf U;                                          // one chunk's row-major f32 unary planes [m][cn][256]
     DevBuf sX, sCodes, sScore;                         // staging of host-buffer calls: a chunk's rows, its int16 codes, its scores
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    PhaseClock<3> clock;                               // a chunk's unaries and its beam search
     lsq_encoder_info info{};
 };
 
@@ -928,7 +902,7 @@ extern "C" int lsq_encoder_destroy(lsq_encoder *en) {
     (void)hipStreamSynchronize(en->ctx->stream);
     DevBuf *bufs[] = {&en->K, &en->sci, &en->T, &en->U, &en->sX, &en->sCodes, &en->sScore};
     for (DevBuf *b : bufs) b->release();
-    for (hipEvent_t e : en->ev) if (e) (void)hipEventDestroy(e);
+    en->clock.release();
     delete en;
     return LSQ_OK;
 }
@@ -987,8 +961,6 @@ extern "C" int lsq_encoder_beam(lsq_encoder *en, const void *X, int x_u8, int64_
     lsq_ctx *c = en->ctx;
     LSQ_TRY(use_device(c));
     hipStream_t s = c->stream;
-    const bool timed = c->profile != 0;
-    if (timed) for (hipEvent_t &e : en->ev) if (!e) LSQ_HIP(hipEventCreate(&e));
     const size_t elem = x_u8 ? 1 : sizeof(float);
     lsq_encoder_info info{};
     info.vectors = n; info.beam = beam;
@@ -1005,22 +977,19 @@ extern "C" int lsq_encoder_beam(lsq_encoder *en, const void *X, int x_u8, int64_
             Xc = en->sX.as<char>(); out_codes = en->sCodes.p; out_score = score ? en->sScore.as<float>() : nullptr;
         }
         LSQ_TRY(en->U.ensure(sizeof(float) * (size_t)m * (size_t)cn * LSQ_H));
-        if (timed) LSQ_HIP(hipEventRecord(en->ev[0], s));
+        LSQ_TRY(en->clock.begin(c->profile != 0));
+        LSQ_TRY(en->clock.mark(s));
         // row-major planes U[(j cn + i) 256 + a] = chain(x_i[t] * -2 K[j, a][t]) + ||c_ja||^2: the bits of lsq_get_unaries
         if (x_u8) LSQ_TRY(lsq_launch_chain_gemm(s, reinterpret_cast<const uint8_t *>(Xc), en->K.as<float>(), en->sci.as<float>(), -2.0f, cn, m * LSQ_H, d, LSQ_H,
                                                 cn * (int64_t)LSQ_H, LSQ_H, en->U.as<float>(), 0, cn, 0));
         else LSQ_TRY(lsq_launch_chain_gemm(s, reinterpret_cast<const float *>(Xc), en->K.as<float>(), en->sci.as<float>(), -2.0f, cn, m * LSQ_H, d, LSQ_H,
                                            cn * (int64_t)LSQ_H, LSQ_H, en->U.as<float>(), 0, cn, 0));
-        if (timed) LSQ_HIP(hipEventRecord(en->ev[1], s));
+        LSQ_TRY(en->clock.mark(s));
         LSQ_TRY(lsq_launch_beam(s, en->U.as<float>(), en->T.as<float>(), cn, m, beam, ord, out_codes, on_device ? 0 : 1, out_score));
-        if (timed) {
-            LSQ_HIP(hipEventRecord(en->ev[2], s));
-            LSQ_HIP(hipEventSynchronize(en->ev[2]));
-            float a = 0, b = 0;
-            LSQ_HIP(hipEventElapsedTime(&a, en->ev[0], en->ev[1]));
-            LSQ_HIP(hipEventElapsedTime(&b, en->ev[1], en->ev[2]));
-            info.unaries_ms += a; info.beam_ms += b;
-        }
+        LSQ_TRY(en->clock.mark(s));
+        float ms[2];
+        LSQ_TRY(en->clock.read(ms));                  // (untimed: zeros, and no wait)
+        info.unaries_ms += ms[0]; info.beam_ms += ms[1];
         if (!on_device) {        // in stream order: the next chunk's kernels overwrite the staging only after these copies
             LSQ_HIP(hipMemcpyAsync(static_cast<int16_t *>(codes) + off * m, en->sCodes.p, sizeof(int16_t) * (size_t)cn * m, hipMemcpyDeviceToHost, s));
             if (score) LSQ_HIP(hipMemcpyAsync(score + off, en->sScore.p, sizeof(float) * (size_t)cn, hipMemcpyDeviceToHost, s));

@@ -58,6 +58,32 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// ---- the phase clock of a timed call (option "profile"): up to N marks on the stream, read as the N - 1 times between neighbours.  Owned by the state whose
+// phases it times; the context's Timer (lsq_api.hip) is another thing: its pairs are resolved lazily, these before the call returns ----------------------
+template <int N>
+struct PhaseClock {
+    hipEvent_t ev[N] = {};
+    int marks = 0;
+    bool timed = false;
+    int begin(bool on) {        // a new run of marks; the events are made at the first timed one
+        timed = on; marks = 0;
+        if (timed) for (hipEvent_t &e : ev) if (!e) LSQ_HIP(hipEventCreate(&e));
+        return LSQ_OK;
+    }
+    int mark(hipStream_t s) {
+        if (timed && marks < N) LSQ_HIP(hipEventRecord(ev[marks++], s));
+        return LSQ_OK;
+    }
+    int read(float *ms) {       // ms[N - 1]; waits for the last mark; 0 for the intervals that were not marked
+        for (int e = 0; e + 1 < N; ++e) ms[e] = 0.0f;
+        if (!timed || marks < 2) return LSQ_OK;
+        LSQ_HIP(hipEventSynchronize(ev[marks - 1]));
+        for (int e = 0; e + 1 < marks; ++e) LSQ_HIP(hipEventElapsedTime(&ms[e], ev[e], ev[e + 1]));
+        return LSQ_OK;
+    }
+    void release() { for (hipEvent_t &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; } }
+};
+
 // ---- Philox4x32-10 (Random123; Salmon et al. SC'11), shared by host and device -----------
 // Stream layout (build-defined, mirrored by oracle/lsq_oracle.c):
 //   counter = (idx_lo, idx_hi, it, (domain << 16) | (word >> 2)),  key = (seed_lo, seed_hi),
@@ -335,6 +361,9 @@ int lsq_rerank_check(const char *fn, const void *dists, const void *ids, const v
 // query = qsel[slot] or q0 + slot, idx = id field - id_sub.  fail (optional, with count): fail[slot] = 1 and nothing handed out for a list that holds
 // fewer than nn records or overflowed.  seg: 2 nqb ints of scratch.  idbits: the width of the id field 1 .. n
 int lsq_adc_idbits(int64_t n);
+// queries per batch of a producer that fills per_query record slots for each: two record buffers of at most 2^28 entries (~2 GiB apiece, and hipcub counts
+// items in int), at most 16384 queries (the hand-out's grid counts them in its y dimension), at least one
+int64_t lsq_adc_batch_queries(int64_t per_query);
 int lsq_adc_select(lsq_adc_state **st, hipStream_t s, const uint64_t *recs, uint64_t *sorted, int *seg, const unsigned *count, int *fail, const int *qsel,
                    int q0, int nqb, int cap, int nn, float *dists, int *idx, int idbits, int end_bit, int id_sub);
 

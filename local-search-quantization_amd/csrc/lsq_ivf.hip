@@ -204,7 +204,7 @@ struct lsq_ivf_state {
     DevBuf cent, codes, norms, ids, off;                             // the layout: centroids, and per position the code row, the norm, the original id
     DevBuf s_lor, keys_a, keys_b, tmp, flag;                         // set_lists' scratch
     DevBuf cd, ci, pos, plan, lut, rec_a, rec_b, seg, count, fail, qsel, head_d, head_i;      // the search's
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    PhaseClock<6> clock;                                             // one batch: tables, scan, selection and, thresholded, the tail's scan and selection
     lsq_ivf_info info{};
 };
 
@@ -213,7 +213,7 @@ void lsq_ivf_free(lsq_ivf_state *st) {
     DevBuf *all[] = {&st->cent, &st->codes, &st->norms, &st->ids, &st->off, &st->s_lor, &st->keys_a, &st->keys_b, &st->tmp, &st->flag, &st->cd, &st->ci,
                      &st->pos, &st->plan, &st->lut, &st->rec_a, &st->rec_b, &st->seg, &st->count, &st->fail, &st->qsel, &st->head_d, &st->head_i};
     for (DevBuf *b : all) b->release();
-    for (hipEvent_t e : st->ev) if (e) (void)hipEventDestroy(e);
+    st->clock.release();
     delete st;
 }
 
@@ -291,11 +291,10 @@ int run_batch(const Chunk &c, const int *qsel, int q0, int nqb, int cap, bool th
     LSQ_TRY(st->seg.ensure(sizeof(int) * 2 * (size_t)nqb));
     LSQ_TRY(st->count.ensure(sizeof(unsigned) * (size_t)nqb));
     LSQ_TRY(st->fail.ensure(sizeof(int) * (size_t)nqb));
-    int nev = 0;
-    auto mark = [&]() -> int { if (c.timed) LSQ_HIP(hipEventRecord(st->ev[nev++], s)); return LSQ_OK; };
-    LSQ_TRY(mark());
+    LSQ_TRY(st->clock.begin(c.timed));
+    LSQ_TRY(st->clock.mark(s));
     LSQ_TRY(lsq_adc_launch_lut(s, c.in, qsel, q0, nqb, st->lut.as<float>()));
-    LSQ_TRY(mark());
+    LSQ_TRY(st->clock.mark(s));
     IvfScan a{};
     a.LUT = st->lut.as<float>(); a.QT = QT;
     a.codes = st->codes.as<uint8_t>(); a.norms = st->norms.as<float>(); a.ids = st->ids.as<int>(); a.off = st->off.as<int>();
@@ -307,34 +306,34 @@ int run_batch(const Chunk &c, const int *qsel, int q0, int nqb, int cap, bool th
     // records: (padding bit, distance key, original id + 1), sorted on 33 + idbits bits; the hand-out drops the bit: (+inf, 0) for padding
     if (!thresholded) {
         LSQ_TRY(launch_scan<0>(s, a, nqb, words));
-        LSQ_TRY(mark());
+        LSQ_TRY(st->clock.mark(s));
         LSQ_TRY(lsq_adc_select(c.adc, s, st->rec_a.as<uint64_t>(), st->rec_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(), nullptr, qsel, q0,
                                nqb, cap, c.nn, c.dists, c.ids, c.idbits, 33 + c.idbits, 0));
     } else {
         LSQ_TRY(st->head_d.ensure(sizeof(float) * (size_t)nqb * c.nn));
         LSQ_TRY(st->head_i.ensure(sizeof(int) * (size_t)nqb * c.nn));
         LSQ_TRY(launch_scan<1>(s, a, nqb, words));
-        LSQ_TRY(mark());
+        LSQ_TRY(st->clock.mark(s));
         // the head, sorted: head_d[slot][nn - 1] is tau
         LSQ_TRY(lsq_adc_select(c.adc, s, st->rec_a.as<uint64_t>(), st->rec_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(), nullptr, nullptr, 0,
                                nqb, cap, c.nn, st->head_d.as<float>(), st->head_i.as<int>(), c.idbits, 33 + c.idbits, 0));
-        LSQ_TRY(mark());
+        LSQ_TRY(st->clock.mark(s));
         a.tau = st->head_d.as<float>();
         LSQ_TRY(launch_scan<2>(s, a, nqb, words));
-        LSQ_TRY(mark());
+        LSQ_TRY(st->clock.mark(s));
         LSQ_TRY(lsq_adc_select(c.adc, s, st->rec_a.as<uint64_t>(), st->rec_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(), st->fail.as<int>(),
                                qsel, q0, nqb, cap, c.nn, c.dists, c.ids, c.idbits, 33 + c.idbits, 0));
         LSQ_HIP(hipMemcpyAsync(h_fail, st->fail.p, sizeof(int) * (size_t)nqb, hipMemcpyDeviceToHost, s));
     }
-    LSQ_TRY(mark());
+    LSQ_TRY(st->clock.mark(s));
     std::vector<unsigned> hc((size_t)nqb);
     LSQ_HIP(hipMemcpyAsync(hc.data(), st->count.p, sizeof(unsigned) * (size_t)nqb, hipMemcpyDeviceToHost, s));
     LSQ_HIP(hipStreamSynchronize(s));
     for (unsigned v : hc) st->info.records += v < (unsigned)cap ? v : (unsigned)cap;
     st->info.batches += 1;
     if (c.timed) {
-        float ms[5] = {0, 0, 0, 0, 0};
-        for (int e = 0; e + 1 < nev; ++e) LSQ_HIP(hipEventElapsedTime(&ms[e], st->ev[e], st->ev[e + 1]));
+        float ms[5];
+        LSQ_TRY(st->clock.read(ms));
         st->info.lut_ms += ms[0];
         st->info.scan_ms += ms[1] + (thresholded ? ms[3] : 0.0f);
         st->info.select_ms += ms[2] + (thresholded ? ms[4] : 0.0f);
@@ -343,11 +342,8 @@ int run_batch(const Chunk &c, const int *qsel, int q0, int nqb, int cap, bool th
 }
 
 int64_t batch_queries(int cap, int flags) {
-    // two record buffers of qb cap <= 2^28 entries (one query's records are one batch); hipcub counts items in int; the hand-out's grid counts queries in y
-    int64_t qb = (int64_t)(1u << 28) / cap;
-    if (qb > 16384) qb = 16384;
-    if ((flags & LSQ_IVF_TEST_BATCH) && qb > IVF_TEST_BATCH) qb = IVF_TEST_BATCH;
-    return qb < 1 ? 1 : qb;
+    const int64_t qb = lsq_adc_batch_queries(cap);                   // cap record slots per query (one query's records are one batch)
+    return (flags & LSQ_IVF_TEST_BATCH) && qb > IVF_TEST_BATCH ? IVF_TEST_BATCH : qb;
 }
 
 int run_chunk(Chunk &c, const float *q_coarse, int64_t ldc, const lsq_search_opts &coarse) {
@@ -423,7 +419,6 @@ int run_chunk(Chunk &c, const float *q_coarse, int64_t ldc, const lsq_search_opt
 int lsq_ivf_search(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *K, float *dists, int *ids, const float *q_scan,
                    const float *q_coarse, int64_t ldc, int nq, int nprobe, int nn, int flags, const lsq_search_opts &coarse, int timed) {
     st->info = lsq_ivf_info{};
-    if (timed) for (hipEvent_t &e : st->ev) if (!e) LSQ_HIP(hipEventCreate(&e));
     // chunks of queries whose per-(query, probe) words stay below 2^28
     int64_t qc = (int64_t)(1u << 28) / ((int64_t)nprobe + 1);
     if (qc < 1) qc = 1;

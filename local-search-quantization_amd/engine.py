@@ -629,15 +629,56 @@ class Engine:
 
 # -- the resident index (made by Engine.index / Engine.index_dev) --------------------------------
 
-class Index:
+class _Handle:
+    """The life of a handle made on an Engine's context (Index, Encoder): the side its calls take, how it is made and freed, how its info structs are read."""
+
+    _destroy = None                                   # the symbol that frees the handle
+    _side = property(lambda self: _DEVICE if self._dev else _HOST)
+
+    def _bind(self, engine, on_device):
+        self._eng, self._L, self._dev, self._h, self._keep = engine, engine._L, bool(on_device), None, None
+        return self._side
+
+    def _create(self, sym, desc):
+        handle = C.c_void_p()
+        self._eng._call(self._side, sym, self._eng._h, C.byref(desc), h=C.byref(handle))
+        self._h = handle
+        self._eng._indexes.add(self)
+
+    def _info(self, sym, struct):
+        st = struct()
+        self._eng._call(_HOST, sym, C.byref(st), h=self._h)
+        return st.as_dict()
+
+    def close(self):
+        # Engine.close closes its handles first.  Should the context be gone all the same, the handle is dropped, not destroyed: its destroy call would
+        # reach through the freed context, and lsq_destroy knows nothing of the handle's buffers, which then stay allocated until the process ends.
+        if getattr(self, "_h", None) and getattr(self._eng, "_h", None):
+            getattr(self._L, self._destroy)(self._h)
+        self._h = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Index(_Handle):
     """A resident database on an Engine's device: the ADC scan (stage one) and the exact re-rank of its shortlists (stage two)   [lsq_index_*].
     Made by Engine.index (host arrays in and out) or Engine.index_dev (torch tensors in and out, on torch's current stream)."""
 
-    _side = property(lambda self: _DEVICE if self._dev else _HOST)
+    _destroy = "lsq_index_destroy"
 
     def __init__(self, engine, codes, K, dbnorms, m, base, h, d, on_device):
-        self._eng, self._L, self._dev, self._h = engine, engine._L, bool(on_device), None
-        side = self._side
+        side = self._bind(engine, on_device)
         codes, K, dbnorms = side.maybe(codes, _U8, "codes"), side.maybe(K, _F32, "K"), side.maybe(dbnorms, _F32, "dbnorms")
         u8 = False
         if base is not None:
@@ -657,22 +698,23 @@ class Index:
         desc.base, desc.base_u8, desc.ldb, desc.on_device = p(base), int(u8), 0 if base is None else int(side.pitch(base)), int(self._dev)
         self._keep = (codes, K, dbnorms, base)      # borrowed device tensors stay alive with the index
         self.n, self.d, self.m = n, d, int(m)
-        handle = C.c_void_p()
-        engine._call(side, "lsq_index_create", engine._h, C.byref(desc), h=C.byref(handle))
-        self._h = handle
-        engine._indexes.add(self)
+        self._create("lsq_index_create", desc)
+
+    def _search_args(self, Q_scan, k, **others):
+        """the queries of a two-stage search, each of the others (name=array or None) defaulting to Q_scan -> Qs, the others in order, dists, ids"""
+        side = self._side
+        Qs = side.take(Q_scan, _F32, "Q_scan")
+        Qo = [Qs if a is None else side.take(a, _F32, name) for name, a in others.items()]
+        _shapes(("Q_scan", Qs, (None, self.d)), *((name, a, tuple(Qs.shape)) for name, a in zip(others, Qo)))
+        return (Qs, *Qo, *side.topk(Qs.shape[0], int(k), Qs))
 
     def search(self, Q_scan, k, shortlist=0, Q_exact=None):
         """Q_scan (nq,d): what the scan reads (the rotated queries of linscan_lsq); Q_exact (nq,d): the queries in the base set's own frame (default:
         Q_scan).  shortlist=0: the ADC scan alone, Engine.linscan's results; shortlist=L>=k: scan for L, re-rank to k by exact distance.
         -> dists (nq,k) float32 ascending, ids (nq,k) int32 1-BASED   [lsq_index_search]"""
-        side = self._side
-        Qs = side.take(Q_scan, _F32, "Q_scan")
-        Qe = Qs if Q_exact is None else side.take(Q_exact, _F32, "Q_exact")
-        _shapes(("Q_scan", Qs, (None, self.d)), ("Q_exact", Qe, tuple(Qs.shape)))
-        nq, p = Qs.shape[0], side.ptr
-        dists, ids = side.topk(nq, int(k), Qs)
-        self._eng._call(side, "lsq_index_search", p(dists), p(ids), p(Qs), p(Qe), nq, self.d, int(shortlist), int(k), int(self._dev), h=self._h)
+        Qs, Qe, dists, ids = self._search_args(Q_scan, k, Q_exact=Q_exact)
+        side, p = self._side, self._side.ptr
+        self._eng._call(side, "lsq_index_search", p(dists), p(ids), p(Qs), p(Qe), Qs.shape[0], self.d, int(shortlist), int(k), int(self._dev), h=self._h)
         return dists, ids
 
     def rerank(self, Q, cand, k, id_base=1):
@@ -720,77 +762,42 @@ class Index:
         add_coarse: one more rounded add of the coarse distance (residual codes); every_record: the road that writes and sorts every probed row.
         -> dists (nq,k) float32 ascending, ids (nq,k) int32 1-BASED original row ids; (+inf, 0) where the probed lists hold fewer than k rows
         [lsq_index_search_ivf]"""
-        side = self._side
-        Qs = side.take(Q_scan, _F32, "Q_scan")
-        Qc = Qs if Q_coarse is None else side.take(Q_coarse, _F32, "Q_coarse")
-        Qe = Qs if Q_exact is None else side.take(Q_exact, _F32, "Q_exact")
-        _shapes(("Q_scan", Qs, (None, self.d)), ("Q_coarse", Qc, tuple(Qs.shape)), ("Q_exact", Qe, tuple(Qs.shape)))
-        nq, p = Qs.shape[0], side.ptr
-        dists, ids = side.topk(nq, int(k), Qs)
+        Qs, Qc, Qe, dists, ids = self._search_args(Q_scan, k, Q_coarse=Q_coarse, Q_exact=Q_exact)
+        side, p = self._side, self._side.ptr
         fl = int(flags) | (_lib.IVF_ADD_COARSE if add_coarse else 0) | (_lib.IVF_EVERY_RECORD if every_record else 0)
-        self._eng._call(side, "lsq_index_search_ivf", p(dists), p(ids), p(Qs), p(Qc), p(Qe), nq, self.d, int(nprobe), int(shortlist), int(k), fl,
+        self._eng._call(side, "lsq_index_search_ivf", p(dists), p(ids), p(Qs), p(Qc), p(Qe), Qs.shape[0], self.d, int(nprobe), int(shortlist), int(k), fl,
                         int(self._dev), h=self._h)
         return dists, ids
 
     def ivf_info(self):
         """what the last search_ivf call did: queries, probed_rows, records, threshold_queries, fallback_queries, batches, batch_queries,
         tail_capacity, coarse_ms / lut_ms / scan_ms / select_ms (with profile=True)"""
-        st = _lib.IvfInfo()
-        self._eng._call(_HOST, "lsq_index_get_ivf_info", C.byref(st), h=self._h)
-        return st.as_dict()
+        return self._info("lsq_index_get_ivf_info", _lib.IvfInfo)
 
     def knn_info(self):
         """what the last knn call did: queries, rows, batches, fallback_queries, exhaustive, int_road, norms_ms / scan_ms / select_ms (with profile=True)"""
-        st = _lib.IndexKnnInfo()
-        self._eng._call(_HOST, "lsq_index_get_knn_info", C.byref(st), h=self._h)
-        return st.as_dict()
+        return self._info("lsq_index_get_knn_info", _lib.IndexKnnInfo)
 
     def stats(self):
-        st = _lib.IndexStats()
-        self._eng._call(_HOST, "lsq_index_get_stats", C.byref(st), h=self._h)
-        return st.as_dict()
-
-    def close(self):
-        # Engine.close closes its indexes first.  Should the context be gone all the same, the handle is dropped, not destroyed: lsq_index_destroy would
-        # reach through the freed context, and lsq_destroy knows nothing of the index's buffers, which then stay allocated until the process ends.
-        if getattr(self, "_h", None) and getattr(self._eng, "_h", None):
-            self._L.lsq_index_destroy(self._h)
-        self._h = None
-        self._keep = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._info("lsq_index_get_stats", _lib.IndexStats)
 
 
 # -- the beam-search encoder (made by Engine.encoder / Engine.encoder_dev) ------------------------
 
-class Encoder:
+class Encoder(_Handle):
     """Beam search over the full pair tables on codebooks resident on an Engine's device   [lsq_encoder_*]: deterministic codes that can replace the
     random start of an ILS encode.  Made by Engine.encoder (host arrays in and out) or Engine.encoder_dev (torch tensors in and out)."""
 
-    _side = property(lambda self: _DEVICE if self._dev else _HOST)
+    _destroy = "lsq_encoder_destroy"
 
     def __init__(self, engine, K, m, chunk, h, on_device):
-        self._eng, self._L, self._dev, self._h = engine, engine._L, bool(on_device), None
-        side = self._side
+        side = self._bind(engine, on_device)
         K = side.take(K, _F32, "K")
         _shapes(("K", K, (int(m) * h, None)))
         desc = _lib.EncoderDesc()
         desc.d, desc.m, desc.h, desc.codebooks, desc.on_device, desc.chunk = int(K.shape[1]), int(m), int(h), side.ptr(K), int(self._dev), int(chunk)
         self.d, self.m = int(K.shape[1]), int(m)
-        handle = C.c_void_p()
-        engine._call(side, "lsq_encoder_create", engine._h, C.byref(desc), h=C.byref(handle))      # the codebooks are copied: K is not kept
-        self._h = handle
-        engine._indexes.add(self)
+        self._create("lsq_encoder_create", desc)      # the codebooks are copied: K is not kept
 
     def beam(self, X, L, order=None, want_score=False):
         """X (n,d) float32 or uint8 rows (the un-widened bytes of a .bvecs set: the bits of the float32 call), beam width 1 <= L <= 32, order: the
@@ -811,27 +818,7 @@ class Encoder:
 
     def info(self):
         """the last beam call: vectors, chunks, beam, unaries_ms / beam_ms (with profile=True)"""
-        st = _lib.EncoderInfo()
-        self._eng._call(_HOST, "lsq_encoder_get_info", C.byref(st), h=self._h)
-        return st.as_dict()
-
-    def close(self):
-        # as Index.close: Engine.close closes its encoders first; without a context the handle is dropped, not destroyed
-        if getattr(self, "_h", None) and getattr(self._eng, "_h", None):
-            self._L.lsq_encoder_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._info("lsq_encoder_get_info", _lib.EncoderInfo)
 
 
 # -- host-only pieces of the path (no GPU needed) ---------------------------------------------
