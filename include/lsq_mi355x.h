@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 1700
+#define LSQ_VERSION 1800
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -526,6 +526,48 @@ LSQ_API int lsq_index_get_ivf_info(lsq_index *ix, lsq_ivf_info *out);
 LSQ_API int lsq_ivf_search_cpu(float *dists, int *ids, const uint8_t *codes, const float *codebooks, const float *dbnorms, const float *centroids,
                                const int32_t *list_of_row, const float *q_scan, const float *q_coarse, int n, int m, int h, int d, int nlist, int nq,
                                int ldq, int nprobe, int nn, int flags, int nthreads);
+
+/* ---- (3h) the packed index: rows of m code bytes and ONE norm byte, searched as stored (since v1800) ---------------------------------------------------
+ * What the reference computes for a base set is m code bytes and one norm byte per vector -- quantize_norms' index into the <= 256 scalar centroids
+ * cbnorms that train_lsq learns (src/utils.jl:6-31): the "64-bit code" at m = 7 -- and what it searches is the widened array cbnorms[index]
+ * (demos/demo_lsq_gpu.jl:57-60).  A packed index keeps the byte: row i is its m code bytes followed by its norm byte c_i, m + 1 bytes in an allocation
+ * the index OWNS, and cbnorms is held once per index.  THE CONTRACT IS AN IDENTITY: every call on a packed index returns bit for bit what the same call
+ * returns on an lsq_index_create index with dbnorms[i] = cbnorms[c_i] -- distances, ids, tie order, NaN order, padding records.  The arithmetic is
+ * lsq_linscan's, dist = ((((0 + t_0) + t_1) + ...) + t_{m-1}) + cbnorms[c_i], the last operand read from a 256-entry table beside the query tables
+ * instead of from a float per row.  lsq_index_search, _set_lists, _search_ivf, _rerank, _knn and their getters take a packed index unchanged; the
+ * inverted layout of a packed index holds m + 5 bytes per row (the packed row and the original id).  The scans read rows as dwords when m + 1 is a
+ * multiple of 4 (m = 3, 7, 11, 15), as bytes otherwise.
+ *   codes [n][m] uint8 0-based; norm_codes [n] uint8 0-based (lsq_quantize_norms_dev's d_idx_out as it is); cbnorms [ncb] f32, 1 <= ncb <= 256.  The three
+ *   are read ONCE, in stream order, before the call returns -- on_device = 1 included: the caller may free or overwrite them afterwards.  codebooks and base
+ *   are copied (on_device = 0) or borrowed (on_device = 1) exactly as in lsq_index_create.
+ * LSQ_EINVAL: the limits of lsq_index_create; codes == NULL (a base-only index is lsq_index_create's); a null norm_codes, cbnorms or codebooks; ncb outside
+ * 1 .. 256; a norm byte >= ncb -- found on the device by the one kernel that reads the bytes, which counts them, before the index exists: *out stays
+ * NULL and nothing is kept. */
+typedef struct lsq_index_packed_desc {
+    int64_t n;
+    int d, m, h;
+    const uint8_t *codes;        /* [n][m] uint8 0-based */
+    const uint8_t *norm_codes;   /* [n] uint8 0-based */
+    const float *cbnorms;        /* [ncb] */
+    int ncb;
+    const float *codebooks;      /* [m*h][d] */
+    const void *base;            /* [n][ldb] float32 or uint8, or NULL */
+    int base_u8, ldb;
+    int on_device;
+} lsq_index_packed_desc;
+typedef struct lsq_index_packed_info {   /* all zero on an index that is not packed */
+    int64_t row_bytes;                   /* m + 1 */
+    int64_t ivf_row_bytes;               /* m + 5 once lists are set, else 0 */
+    int64_t ncb;
+    int64_t dword_rows;                  /* 1 = the scans read rows as dwords */
+    int64_t resident_bytes;              /* the packed rows and the norm table: n (m + 1) + 4 ncb */
+} lsq_index_packed_info;
+LSQ_API int lsq_index_create_packed(lsq_index **out, lsq_ctx *ctx, const lsq_index_packed_desc *desc);
+LSQ_API int lsq_index_get_packed_info(lsq_index *ix, lsq_index_packed_info *out);
+/* The selection statistics of the LAST lsq_index_search call's scan (any index; lsq_get_linscan_stats' struct, this call's figures alone): exhaustive,
+ * threshold_rank, list_capacity, candidates, fallback_queries, batches -- what tells a scan that sampled other rows from one that did not when the
+ * fallback road has repaired the results. */
+LSQ_API int lsq_index_get_scan_stats(lsq_index *ix, lsq_linscan_stats *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB      src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

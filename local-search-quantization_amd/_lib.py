@@ -73,6 +73,16 @@ class IvfInfo(_Struct):
 IVF_ADD_COARSE, IVF_EVERY_RECORD, IVF_TEST_BATCH = 1, 2, 4
 
 
+class IndexPackedDesc(_Struct):
+    _fields_ = [("n", C.c_int64), ("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("codes", C.c_void_p), ("norm_codes", C.c_void_p),
+                ("cbnorms", C.c_void_p), ("ncb", C.c_int), ("codebooks", C.c_void_p), ("base", C.c_void_p), ("base_u8", C.c_int), ("ldb", C.c_int),
+                ("on_device", C.c_int)]
+
+
+class IndexPackedInfo(_Struct):
+    _fields_ = [("row_bytes", C.c_int64), ("ivf_row_bytes", C.c_int64), ("ncb", C.c_int64), ("dword_rows", C.c_int64), ("resident_bytes", C.c_int64)]
+
+
 class EncoderDesc(_Struct):
     _fields_ = [("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("codebooks", C.c_void_p), ("on_device", C.c_int), ("chunk", C.c_int64)]
 
@@ -167,6 +177,10 @@ SIGNATURES = {
     "lsq_index_search_ivf": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
     "lsq_index_get_ivf_info": (_i, [_vp, C.POINTER(IvfInfo)]),
     "lsq_ivf_search_cpu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    # the packed index: rows of m code bytes and one norm byte (since v1800), and the selection statistics of an index's last scan
+    "lsq_index_create_packed": (_i, [C.POINTER(_vp), _vp, C.POINTER(IndexPackedDesc)]),
+    "lsq_index_get_packed_info": (_i, [_vp, C.POINTER(IndexPackedInfo)]),
+    "lsq_index_get_scan_stats": (_i, [_vp, C.POINTER(LinscanStats)]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),

@@ -25,7 +25,7 @@
 // NaN distances (the reference's partial_sort has no defined order for them) sort after everything else here.
 //
 // The reference's other scan, linscan_aqd_query for PQ / OPQ codes (src/linscan/cpp/linscan_aqd.cpp:37-114; LSQ_SEARCH_PQ), runs on the same
-// machinery: adc_pq_lut_kernel builds the sub-space squared-distance tables in the same layout, adc_scan_kernel drops the norm term (NORM = false)
+// machinery: adc_pq_lut_kernel builds the sub-space squared-distance tables in the same layout, adc_scan_kernel drops the norm term (ADC_NORM_NONE)
 // and reads code rows dim1codes bytes apart, and the gather hands out 0-based ids.
 #include <hipcub/hipcub.hpp>
 
@@ -150,27 +150,37 @@ struct AdcStage {
 };
 
 // MODE 0: append (key << idbits | id) of every distance <= tau to the query's candidate list;  MODE 1: write every (key << idbits | id) of the strided
-// subset i = s * stride, s < ns, to out[slot * ns + s];  MODE 2: the same subset, keys only (u32).  MW > 0: m = 4 MW = cstride, codes read as
-// dwords; MW = 0: any m, byte reads of rows cstride bytes apart.  NORM: + dbnorms[i] (LSQ); without it the distance is the table sum alone (PQ).
+// subset i = s * stride, s < ns, to out[slot * ns + s];  MODE 2: the same subset, keys only (u32).  MW > 0: rows of 4 MW = cstride bytes, read as
+// dwords; MW = 0: any m, byte reads of rows cstride bytes apart.  NORM, the last operand of the distance: ADC_NORM_NONE -- none, the table sum alone (PQ);
+// ADC_NORM_F32 -- dbnorms[i] (LSQ); ADC_NORM_BYTE -- a PACKED row: its m code bytes, then the norm byte c_i (m = 4 MW - 1 on the dword loader), and
+// dbnorms is the norm table of 256 floats, staged once per block behind the query tables: one ds_read_b32 that the lanes of a code share.
 // A lane owns one code and four queries per step.  The codes of the NEXT batch of U steps are requested before the current batch is walked: a
 // code's bytes come from L2 (~1 us away), its 16-byte table reads from LDS (~0.1 us), and without the prefetch the walk waits for L2 once per
 // code (measured: 7 of 28 TB/s of LDS gathers).
-template <int QT, int MODE, int MW, bool NORM>
+enum { ADC_NORM_NONE = 0, ADC_NORM_F32 = 1, ADC_NORM_BYTE = 2 };
+constexpr int ADC_NORM_TABLE = 256;          // floats of the staged norm table (entries >= ncb are padding, never addressed)
+template <int QT, int MODE, int MW, int NORM>
 __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void adc_scan_kernel(const float *__restrict__ LUT, const uint8_t *__restrict__ codes,
                                                                     const float *__restrict__ dbnorms, int n, int m, int cstride, int nqb, int stride, int ns,
                                                                     int per_block, const uint32_t *__restrict__ tau, unsigned *__restrict__ count,
                                                                     int cap, uint64_t *__restrict__ out, int idbits) {
-    extern __shared__ __attribute__((aligned(16))) float lut[];      // [m * 256][QT], then the emission staging of MODE 0 (AdcStage)
+    extern __shared__ __attribute__((aligned(16))) float lut[];      // [m * 256][QT], the norm table (ADC_NORM_BYTE), then the emission staging of MODE 0 (AdcStage)
     constexpr int NQ = QT / 4, CPW = 64 / NQ;                        // query quads, codes per wave step
     constexpr int U = MW == 0 ? 1 : (MW <= 2 ? 4 : 2);               // steps per batch
     constexpr int G = (MW == 1 || MW == 2) ? 2 : 1;                  // steps whose table reads are in flight together (<= 64 registers of them)
     constexpr int CW = MW > 0 ? MW : 1;
+    constexpr int NT = NORM == ADC_NORM_BYTE ? 4 * CW - 1 : 4 * CW;  // bytes of a dword-loaded row that index tables
+    constexpr int NTAB = NORM == ADC_NORM_BYTE ? ADC_NORM_TABLE : 0;
     const int tile = blockIdx.x;
     const int entries = m * LSQ_H;
     {
         const f32x4 *src = reinterpret_cast<const f32x4 *>(LUT + (int64_t)tile * entries * QT);
         f32x4 *dst = reinterpret_cast<f32x4 *>(lut);
         for (int t = threadIdx.x; t < entries * QT / 4; t += ADC_SCAN_THREADS) dst[t] = src[t];
+    }
+    const float *ntab = lut + (size_t)entries * QT;
+    if constexpr (NORM == ADC_NORM_BYTE) {
+        if (threadIdx.x < ADC_NORM_TABLE) lut[(size_t)entries * QT + threadIdx.x] = dbnorms[threadIdx.x];
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -189,7 +199,7 @@ __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_e
     // MODE 0: a pair that passes the threshold is parked in the wave's LDS staging list; a full list is flushed with ONE global atomic per query
     // (16 lanes, one wait) instead of one returning atomic -- a round trip to L2 that stalls the wave -- per pair (measured: 0.45 ms per 1000
     // candidates per query at 10^4 queries).
-    AdcStage *stage = reinterpret_cast<AdcStage *>(lut + (size_t)entries * QT) + wave;
+    AdcStage *stage = reinterpret_cast<AdcStage *>(lut + (size_t)entries * QT + NTAB) + wave;
     if (MODE == 0 && lane == 0) stage->n = 0;
     auto flush = [&]() {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -226,7 +236,7 @@ __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_e
 #pragma unroll
                 for (int t = 0; t < CW; ++t) bt.w[u][t] = cp[t];
             }
-            if (NORM) bt.nrm[u] = dbnorms[i];
+            if (NORM == ADC_NORM_F32) bt.nrm[u] = dbnorms[i];
         }
     };
     Batch cur, nxt;
@@ -240,14 +250,17 @@ __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_e
             // all table reads of G steps are requested before the first is consumed (the LDS round trip is paid once per group, not once per read)
             f32x4 v[G][MW > 0 ? 4 * CW : 1];
             f32x4 dist[G];
+            float nb[G];                                             // ADC_NORM_BYTE on the dword loader: cbnorms[c_i], requested with the table reads
             if (MW > 0) {
 #pragma unroll
-                for (int g = 0; g < G; ++g)
+                for (int g = 0; g < G; ++g) {
 #pragma unroll
-                    for (int j = 0; j < 4 * CW; ++j) {
+                    for (int j = 0; j < NT; ++j) {
                         const uint32_t b = (cur.w[u0 + g][j >> 2] >> (8 * (j & 3))) & 0xffu;
                         v[g][j] = lut4[(j * LSQ_H + (int)b) * NQ + qq];
                     }
+                    if constexpr (NORM == ADC_NORM_BYTE) nb[g] = ntab[cur.w[u0 + g][CW - 1] >> 24];
+                }
             }
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -255,15 +268,18 @@ __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_e
                 f32x4 acc = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
                 if (MW > 0) {
 #pragma unroll
-                    for (int j = 0; j < 4 * CW; ++j) acc = acc + v[g][j];
+                    for (int j = 0; j < NT; ++j) acc = acc + v[g][j];
                 } else {
                     const int64_t i = (int64_t)(s < last ? s : first) * (MODE == 0 ? 1 : stride);
                     const uint8_t *cp = codes + i * cstride;
                     for (int j = 0; j < m; ++j) acc = acc + lut4[(j * LSQ_H + (int)cp[j]) * NQ + qq];
+                    if constexpr (NORM == ADC_NORM_BYTE) nb[g] = ntab[cp[m]];
                 }
-                if constexpr (NORM) {
+                if constexpr (NORM == ADC_NORM_F32) {
                     const float nrm = cur.nrm[u0 + g];
                     dist[g] = acc + (f32x4){nrm, nrm, nrm, nrm};
+                } else if constexpr (NORM == ADC_NORM_BYTE) {
+                    dist[g] = acc + (f32x4){nb[g], nb[g], nb[g], nb[g]};
                 } else {
                     dist[g] = acc;
                 }
@@ -403,8 +419,27 @@ __global__ void adc_gather_kernel(const uint64_t *__restrict__ sorted, const int
     }
 }
 
+// the packed rows of lsq_index_create_packed: row i = its m code bytes, then its norm byte.  The one kernel that reads the caller's norm bytes: *bad += those
+// >= ncb (a count for the host's verdict: no address depends on it, here or later -- the scans' norm table holds 256 entries)
+__global__ void adc_pack_kernel(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ norm_codes, int64_t n, int m, int ncb,
+                                uint8_t *__restrict__ rows, unsigned *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t *src = codes + i * m;
+    uint8_t *dst = rows + i * (m + 1);
+    for (int j = 0; j < m; ++j) dst[j] = src[j];
+    const uint8_t c = norm_codes[i];
+    dst[m] = c;
+    if ((int)c >= ncb) atomicAdd(bad, 1u);
+}
 
 }  // namespace
+
+int lsq_adc_launch_pack(hipStream_t s, const uint8_t *codes, const uint8_t *norm_codes, int64_t n, int m, int ncb, uint8_t *rows, unsigned *bad) {
+    hipLaunchKernelGGL(adc_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, codes, norm_codes, n, m, ncb, rows, bad);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
 
 struct lsq_adc_state {
     DevBuf lut, keys_a, keys_b, tau, count, seg, fail, qsel, tmp;
@@ -452,8 +487,10 @@ int launch_scan(hipStream_t s, const float *LUT, const lsq_search_input &in, int
     int per_block = (total + ranges - 1) / ranges;
     per_block = (per_block + 255) & ~255;
     ranges = (total + per_block - 1) / per_block;
-    const size_t lds = sizeof(float) * (size_t)m * LSQ_H * QT + (MODE == 0 ? sizeof(AdcStage) * (ADC_SCAN_THREADS / 64) : 0);
-    const bool words = (m % 4 == 0) && in.cstride == m && (((uintptr_t)in.codes & 3) == 0);
+    const bool packed = in.kind == LSQ_SEARCH_LSQ && in.packed;
+    const int rowb = packed ? m + 1 : m;             // bytes of a row that are read
+    const size_t lds = sizeof(float) * ((size_t)m * LSQ_H * QT + (packed ? ADC_NORM_TABLE : 0)) + (MODE == 0 ? sizeof(AdcStage) * (ADC_SCAN_THREADS / 64) : 0);
+    const bool words = (rowb % 4 == 0) && in.cstride == rowb && (((uintptr_t)in.codes & 3) == 0);
     const dim3 grid((unsigned)tiles, (unsigned)ranges), block(ADC_SCAN_THREADS);
 #define ADC_LAUNCH(MWV, NORMV)                                                                                                              \
     do {                                                                                                                                    \
@@ -464,14 +501,15 @@ int launch_scan(hipStream_t s, const float *LUT, const lsq_search_input &in, int
     } while (0)
 #define ADC_LAUNCH_MW(NORMV)                      \
     do {                                          \
-        if (words && m == 4) ADC_LAUNCH(1, NORMV);       \
-        else if (words && m == 8) ADC_LAUNCH(2, NORMV);  \
-        else if (words && m == 12) ADC_LAUNCH(3, NORMV); \
-        else if (words && m == 16) ADC_LAUNCH(4, NORMV); \
+        if (words && rowb == 4) ADC_LAUNCH(1, NORMV);       \
+        else if (words && rowb == 8) ADC_LAUNCH(2, NORMV);  \
+        else if (words && rowb == 12) ADC_LAUNCH(3, NORMV); \
+        else if (words && rowb == 16) ADC_LAUNCH(4, NORMV); \
         else ADC_LAUNCH(0, NORMV);                \
     } while (0)
-    if (in.kind == LSQ_SEARCH_LSQ) ADC_LAUNCH_MW(true);
-    else ADC_LAUNCH_MW(false);
+    if (packed) ADC_LAUNCH_MW(ADC_NORM_BYTE);
+    else if (in.kind == LSQ_SEARCH_LSQ) ADC_LAUNCH_MW(ADC_NORM_F32);
+    else ADC_LAUNCH_MW(ADC_NORM_NONE);
 #undef ADC_LAUNCH_MW
 #undef ADC_LAUNCH
     LSQ_HIP(hipGetLastError());

@@ -540,6 +540,9 @@ struct lsq_index {
     const float *K = nullptr, *norms = nullptr;
     const void *base = nullptr;
     DevBuf own_codes, own_K, own_norms, own_base;
+    int packed = 0, ncb = 0;                           // lsq_index_create_packed: codes = own_codes = rows of m + 1 bytes (code bytes, norm byte), norms = own_norms =
+                                                       // the norm table padded to 256 floats; nothing else reads either
+    lsq_linscan_stats scan{};                          // the selection statistics of the last lsq_index_search scan
     lsq_adc_state *adc = nullptr;                      // the scan's state of THIS index: never ctx->adc
     DevBuf rec_a, rec_b, seg, counter;                 // stage two: records, sorted records, segment bounds, the invalid-id counter
     DevBuf short_d, short_i;                           // stage one's shortlist [nq][L]
@@ -609,6 +612,83 @@ extern "C" int lsq_index_create(lsq_index **out, lsq_ctx *c, const lsq_index_des
     if (rc == LSQ_OK && hipStreamSynchronize(c->stream) != hipSuccess) { lsq_set_error("lsq_index_create: the upload failed"); rc = LSQ_EHIP; }
     if (rc != LSQ_OK) { (void)lsq_index_destroy(ix); return rc; }
     *out = ix;
+    return LSQ_OK;
+}
+
+// The packed index: the caller's (codes, norm bytes) become rows the index owns, cbnorms a table of 256 floats; everything else is lsq_index_create's
+extern "C" int lsq_index_create_packed(lsq_index **out, lsq_ctx *c, const lsq_index_packed_desc *desc) {
+    const char *fn = "lsq_index_create_packed";
+    if (!out) { lsq_set_error("%s: null out pointer", fn); return LSQ_EINVAL; }
+    *out = nullptr;
+    if (!c || !desc) { lsq_set_error("%s: null %s", fn, c ? "description" : "context"); return LSQ_EINVAL; }
+    if (!desc->codes) { lsq_set_error("%s: no codes (a base-only index is lsq_index_create's)", fn); return LSQ_EINVAL; }
+    if (desc->n < 1 || desc->n > (int64_t)INT32_MAX - 1 || desc->d < 1) {
+        lsq_set_error("%s: needs 1 <= n <= 2^31 - 2 and d >= 1 (got n=%lld d=%d)", fn, (long long)desc->n, desc->d);
+        return LSQ_EINVAL;
+    }
+    if (desc->h != LSQ_H || desc->m < 1 || desc->m > LSQ_MAX_M) { lsq_set_error("%s: needs h == 256 and 1 <= m <= 16 (got h=%d m=%d)", fn, desc->h, desc->m); return LSQ_EINVAL; }
+    if (!desc->codebooks || !desc->norm_codes || !desc->cbnorms) { lsq_set_error("%s: codes without codebooks, norm_codes or cbnorms", fn); return LSQ_EINVAL; }
+    if (desc->ncb < 1 || desc->ncb > 256) { lsq_set_error("%s: needs 1 <= ncb <= 256 (got %d)", fn, desc->ncb); return LSQ_EINVAL; }
+    if (desc->base && desc->ldb < desc->d) { lsq_set_error("%s: needs ldb >= d (got ldb=%d d=%d)", fn, desc->ldb, desc->d); return LSQ_EINVAL; }
+    if (desc->base && !desc->base_u8 && ((uintptr_t)desc->base & 3) != 0) { lsq_set_error("%s: the f32 base is not 4-byte aligned", fn); return LSQ_EINVAL; }
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    lsq_index *ix = new lsq_index();
+    ix->ctx = c;
+    ix->n = desc->n; ix->d = desc->d; ix->m = desc->m; ix->base_u8 = desc->base_u8 != 0; ix->ldb = desc->ldb;
+    ix->packed = 1; ix->ncb = desc->ncb;
+    const size_t n = (size_t)desc->n, d = (size_t)desc->d, m = (size_t)desc->m;
+    DevBuf s_codes, s_nc;                              // the host form's staging of what the pack kernel reads: gone when the call returns
+    unsigned bad = 0;
+    auto build = [&]() -> int {
+        const uint8_t *dcodes = desc->codes, *dnc = desc->norm_codes;
+        if (!desc->on_device) {
+            LSQ_TRY(s_codes.ensure(n * m));
+            LSQ_TRY(s_nc.ensure(n));
+            LSQ_HIP(hipMemcpyAsync(s_codes.p, desc->codes, n * m, hipMemcpyHostToDevice, s));
+            LSQ_HIP(hipMemcpyAsync(s_nc.p, desc->norm_codes, n, hipMemcpyHostToDevice, s));
+            dcodes = s_codes.as<uint8_t>(); dnc = s_nc.as<uint8_t>();
+        }
+        LSQ_TRY(ix->own_codes.ensure(n * (m + 1) + 16));      // 16 bytes of slack past the last row, never read
+        LSQ_TRY(ix->own_norms.ensure(sizeof(float) * 256));
+        LSQ_TRY(ix->counter.ensure(sizeof(unsigned long long)));
+        LSQ_HIP(hipMemsetAsync(ix->counter.p, 0, sizeof(unsigned long long), s));
+        LSQ_HIP(hipMemsetAsync(ix->own_norms.p, 0, sizeof(float) * 256, s));       // entries >= ncb: never addressed
+        LSQ_HIP(hipMemcpyAsync(ix->own_norms.p, desc->cbnorms, sizeof(float) * (size_t)desc->ncb, desc->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        LSQ_TRY(lsq_adc_launch_pack(s, dcodes, dnc, desc->n, desc->m, desc->ncb, ix->own_codes.as<uint8_t>(), ix->counter.as<unsigned>()));
+        LSQ_HIP(hipMemcpyAsync(&bad, ix->counter.p, sizeof(bad), hipMemcpyDeviceToHost, s));
+        ix->codes = ix->own_codes.as<uint8_t>();
+        ix->norms = ix->own_norms.as<float>();
+        LSQ_TRY(index_adopt(ix, ix->own_K, desc->codebooks, sizeof(float) * m * LSQ_H * d, desc->on_device, reinterpret_cast<const void **>(&ix->K)));
+        if (desc->base)
+            LSQ_TRY(index_adopt(ix, ix->own_base, desc->base, ((n - 1) * (size_t)desc->ldb + d) * (desc->base_u8 ? 1 : sizeof(float)), desc->on_device, &ix->base));
+        if (hipStreamSynchronize(s) != hipSuccess) { lsq_set_error("%s: the upload failed", fn); return LSQ_EHIP; }
+        if (bad) { lsq_set_error("%s: %u norm bytes lie outside [0, %d)", fn, bad, desc->ncb); return LSQ_EINVAL; }
+        return LSQ_OK;
+    };
+    const int rc = build();
+    if (rc != LSQ_OK && rc != LSQ_EINVAL) (void)hipStreamSynchronize(s);      // nothing in flight reads the staging when it goes
+    s_codes.release(); s_nc.release();
+    if (rc != LSQ_OK) { (void)lsq_index_destroy(ix); return rc; }
+    *out = ix;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_packed_info(lsq_index *ix, lsq_index_packed_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_packed_info: null argument"); return LSQ_EINVAL; }
+    *out = lsq_index_packed_info{};
+    if (!ix->packed) return LSQ_OK;
+    out->row_bytes = ix->m + 1;
+    out->ivf_row_bytes = lsq_ivf_nlist(ix->ivf) > 0 ? ix->m + 5 : 0;
+    out->ncb = ix->ncb;
+    out->dword_rows = (ix->m + 1) % 4 == 0 ? 1 : 0;
+    out->resident_bytes = ix->n * (int64_t)(ix->m + 1) + 4 * (int64_t)ix->ncb;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_scan_stats(lsq_index *ix, lsq_linscan_stats *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_scan_stats: null argument"); return LSQ_EINVAL; }
+    *out = ix->scan;
     return LSQ_OK;
 }
 
@@ -776,8 +856,10 @@ extern "C" int lsq_index_search(lsq_index *ix, float *dists, int *ids, const flo
     return index_two_stage("lsq_index_search", call, dists, ids, q_scan, q_exact, ldq, shortlist, nn, L,
                            [&](float *scan_d, int *scan_i, const float *dqs, int len) -> int {      // the ADC scan of every row
         lsq_linscan_stats st{};
-        LSQ_TRY(lsq_adc_search(c->stream, &ix->adc, scan_d, scan_i, lsq_input(ix->codes, dqs, ix->K, ix->norms, (int)ix->n, ix->m, ix->d), nq, len,
-                               search_opts(c, &st)));
+        lsq_search_input in = lsq_input(ix->codes, dqs, ix->K, ix->norms, (int)ix->n, ix->m, ix->d);
+        if (ix->packed) { in.packed = 1; in.cstride = ix->m + 1; }      // rows with their norm byte; norms is the table
+        LSQ_TRY(lsq_adc_search(c->stream, &ix->adc, scan_d, scan_i, in, nq, len, search_opts(c, &st)));
+        ix->scan = st;
         ix->stats.scan_ms += st.lut_ms + st.sample_ms + st.scan_ms + st.select_ms;
         return LSQ_OK;
     });
@@ -852,7 +934,7 @@ extern "C" int lsq_index_set_lists(lsq_index *ix, const lsq_ivf_desc *desc) {
     if (desc->nlist < 1 || desc->nlist > (1 << 24)) { lsq_set_error("lsq_index_set_lists: needs 1 <= nlist <= 2^24 (got %d)", desc->nlist); return LSQ_EINVAL; }
     if (!desc->centroids || !desc->list_of_row) { lsq_set_error("lsq_index_set_lists: null pointer"); return LSQ_EINVAL; }
     LSQ_TRY(use_device(ix->ctx));
-    return lsq_ivf_set_lists(ix->ctx->stream, &ix->ivf, ix->codes, ix->norms, ix->n, ix->m, ix->d, desc);
+    return lsq_ivf_set_lists(ix->ctx->stream, &ix->ivf, ix->codes, ix->norms, ix->packed, ix->n, ix->m, ix->d, desc);
 }
 
 extern "C" int lsq_index_search_ivf(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_coarse, const float *q_exact, int nq, int ldq,

@@ -325,6 +325,7 @@ struct lsq_search_input {
     int base_u8 = 0, q_u8 = 0;               // exact: element types of base / Q (0: f32, 1: uint8)
     const uint32_t *xnorms = nullptr, *qnorms = nullptr;
     int id_base = 0;                         // exact: ids leave as row + id_base
+    int packed = 0;                          // LSQ: rows of cstride = m + 1 bytes, the last one the norm byte c_i; dbnorms = the norm table padded to 256 floats
     int query_width() const { return kind == LSQ_SEARCH_PQ ? m * d : d; }      // elements of a query row that are read
     int id_sub() const { return kind == LSQ_SEARCH_LSQ ? 0 : 1 - id_base; }    // ids leave as (the record's id field 1 .. n) - id_sub
     size_t base_elem() const { return base_u8 ? 1 : sizeof(float); }
@@ -367,6 +368,9 @@ int64_t lsq_adc_batch_queries(int64_t per_query);
 int lsq_adc_select(lsq_adc_state **st, hipStream_t s, const uint64_t *recs, uint64_t *sorted, int *seg, const unsigned *count, int *fail, const int *qsel,
                    int q0, int nqb, int cap, int nn, float *dists, int *idx, int idbits, int end_bit, int id_sub);
 
+// rows[i] = (codes[i][0 .. m), norm_codes[i]), m + 1 bytes apart; *bad += norm bytes >= ncb (a count: nothing depends on it but the caller's verdict)
+int lsq_adc_launch_pack(hipStream_t s, const uint8_t *codes, const uint8_t *norm_codes, int64_t n, int m, int ncb, uint8_t *rows, unsigned *bad);
+
 // adc_lut_kernel's tables for another scan (lsq_ivf.hip): LUT[(slot / QT) * m * 256 * QT + e * QT + slot % QT] = entry e of the table of query q0 + slot (or
 // qsel[slot]), QT = lsq_adc_lut_qt(m) queries per tile; LUT holds ceil(nqb / QT) tiles
 inline int lsq_adc_lut_qt(int m) { return m <= 8 ? 16 : 8; }
@@ -377,8 +381,10 @@ struct lsq_ivf_state;
 void lsq_ivf_free(lsq_ivf_state *st);
 int lsq_ivf_nlist(const lsq_ivf_state *st);      // 0: no lists yet
 void lsq_ivf_get_info(const lsq_ivf_state *st, lsq_ivf_info *out);
-// codes [n][m], norms [n]: the index's device arrays; desc as lsq_index_set_lists takes it.  A bad list_of_row entry leaves the former lists as they were
-int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **st, const uint8_t *codes, const float *norms, int64_t n, int m, int d, const lsq_ivf_desc *desc);
+// codes [n][m], norms [n]: the index's device arrays (packed: rows [n][m + 1] and the norm table of 256 floats, which the index keeps alive); desc as
+// lsq_index_set_lists takes it.  A bad list_of_row entry leaves the former lists as they were
+int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **st, const uint8_t *codes, const float *norms, int packed, int64_t n, int m, int d,
+                      const lsq_ivf_desc *desc);
 // device pointers: K [m*256][d], q_scan [nq][d], q_coarse [nq][ldc], dists / ids [nq][nn] (ADC distances, original ids 1-based, (+inf, 0) past the probed
 // rows).  adc: the index's scan state (the coarse search and the selection run on it); coarse: how the coarse search runs (the context's hooks)
 int lsq_ivf_search(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *K, float *dists, int *ids, const float *q_scan,

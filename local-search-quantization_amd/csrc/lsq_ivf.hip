@@ -10,7 +10,8 @@
 //
 // What is new here is the layout and the scan:
 //   LAYOUT  lsq_ivf_set_lists sorts the keys (list << 32 | row) once (hipcub radix sort: stable, no atomics, the same bits on every call) and gathers codes,
-//           norms and original ids into that order: list l is rows off[l] .. off[l + 1] of three arrays, ascending by original id inside.
+//           norms and original ids into that order: list l is rows off[l] .. off[l + 1] of three arrays, ascending by original id inside.  A PACKED index
+//           (lsq_index_create_packed) has two: rows of m + 1 bytes -- the code bytes and the norm byte -- and the ids; its norms are a table of 256 floats.
 //   PLAN    ivf_plan_kernel, one thread per query: the prefix sums of its probed lists' lengths in rank order (where each list's records go), the HEAD
 //           -- the first lists that hold nn rows together -- and the totals the host sizes its batches by.
 //   SCAN    ivf_scan_kernel: a block owns ONE query and every gridDim.y-th of its probed lists.  The query's table -- m KiB, against the 128 KiB tile of
@@ -71,6 +72,16 @@ __global__ void ivf_layout_kernel(const uint64_t *__restrict__ sorted, int64_t n
     iids[p] = (int)row;
 }
 
+// the layout of a PACKED index: rows of m + 1 bytes (code bytes, norm byte) and the original id -- m + 5 bytes per row and no norm array
+__global__ void ivf_layout_packed_kernel(const uint64_t *__restrict__ sorted, int64_t n, int rowb, const uint8_t *__restrict__ rows,
+                                         uint8_t *__restrict__ irows, int *__restrict__ iids) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int64_t row = (int64_t)(uint32_t)sorted[p];
+    for (int j = 0; j < rowb; ++j) irows[p * rowb + j] = rows[row * rowb + j];
+    iids[p] = (int)row;
+}
+
 // ---- the plan of a query: pos[q][r] = rows of its probed lists of rank < r (pos[q][nprobe] = all of them); plan[q] = {rows, rows of the head, lists of
 // the head}.  The head: the first lists, in rank order, that together hold at least nn rows; all of them when there are fewer than nn rows
 __global__ void ivf_plan_kernel(const int *__restrict__ probe, const int *__restrict__ off, int nq, int nprobe, int nn, int *__restrict__ pos,
@@ -106,10 +117,12 @@ struct IvfScan {
 };
 
 // PART 0: every record of every probed list; 1: the same of the head's lists; 2: the records with !(dist > tau) of the lists after the head, appended.
-// MW > 0: m = 4 MW, codes read as dwords (rows m bytes apart in an allocation of the index's own: aligned); MW = 0: any m, byte reads.
-template <int MW, int PART>
+// MW > 0: rows of 4 MW bytes, read as dwords (an allocation of the index's own: aligned); MW = 0: any m, byte reads.  PACKED: a row is its m code bytes and
+// then its norm byte (m = 4 MW - 1 on the dword loader), a.norms is the norm table of 256 floats, staged beside the query's table.
+template <int MW, int PART, bool PACKED = false>
 __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const IvfScan a) {
-    __shared__ float lut[LSQ_MAX_M * LSQ_H];                         // the query's table: m KiB used
+    __shared__ float lut[LSQ_MAX_M * LSQ_H + (PACKED ? 256 : 0)];    // the query's table: m KiB used; PACKED: the norm table behind all 16 KiB
+    constexpr int NT = PACKED ? 4 * MW - 1 : 4 * MW;                 // bytes of a dword-loaded row that index tables
     const int t = threadIdx.x, slot = blockIdx.x;
     const int q = a.qsel ? a.qsel[slot] : a.q0 + slot;
     const int *pl = a.plan + 3 * (int64_t)q;
@@ -128,6 +141,7 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const IvfScan a) 
     {
         const float *__restrict__ src = a.LUT + (int64_t)(slot / a.QT) * entries * a.QT + slot % a.QT;
         for (int e = t; e < entries; e += IVF_THREADS) lut[e] = src[(int64_t)e * a.QT];
+        if constexpr (PACKED) lut[LSQ_MAX_M * LSQ_H + t] = a.norms[t];      // (IVF_THREADS == 256 entries)
     }
     __syncthreads();
     const int *__restrict__ probe = a.probe + (int64_t)q * a.nprobe;
@@ -144,18 +158,22 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const IvfScan a) 
             const bool live = i < len;
             const int64_t row = (int64_t)b + (live ? i : 0);
             float acc = 0.0f;
+            float nrm;
             if constexpr (MW > 0) {
                 const uint32_t *cp = reinterpret_cast<const uint32_t *>(a.codes + row * (4 * MW));
                 uint32_t w[MW > 0 ? MW : 1];
 #pragma unroll
                 for (int k = 0; k < MW; ++k) w[k] = cp[k];
 #pragma unroll
-                for (int j = 0; j < 4 * MW; ++j) acc = acc + lut[j * LSQ_H + (int)((w[j >> 2] >> (8 * (j & 3))) & 0xffu)];
+                for (int j = 0; j < NT; ++j) acc = acc + lut[j * LSQ_H + (int)((w[j >> 2] >> (8 * (j & 3))) & 0xffu)];
+                if constexpr (PACKED) nrm = lut[LSQ_MAX_M * LSQ_H + (int)(w[MW > 0 ? MW - 1 : 0] >> 24)];
             } else {
-                const uint8_t *cp = a.codes + row * a.m;
+                const uint8_t *cp = a.codes + row * (PACKED ? a.m + 1 : a.m);
                 for (int j = 0; j < a.m; ++j) acc = acc + lut[j * LSQ_H + (int)cp[j]];
+                if constexpr (PACKED) nrm = lut[LSQ_MAX_M * LSQ_H + (int)cp[a.m]];
             }
-            float dist = acc + a.norms[row];
+            if constexpr (!PACKED) nrm = a.norms[row];
+            float dist = acc + nrm;
             if (a.add) dist = dist + cq;                             // one more rounded add
             const uint64_t rec = ((uint64_t)lsq_adc_key(dist) << a.idbits) | (uint64_t)(uint32_t)(a.ids[row] + 1);      // the ORIGINAL id, 1-based
             if (PART != 2) {
@@ -178,18 +196,23 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const IvfScan a) 
 }
 
 template <int PART>
-int launch_scan(hipStream_t s, const IvfScan &a, int nqb, bool words) {
+int launch_scan(hipStream_t s, const IvfScan &a, int nqb, bool packed) {
+    const int rowb = packed ? a.m + 1 : a.m;                         // bytes of a row: the dword loader takes whole words
     // enough blocks to fill the chip a few times over when the queries are few; a block's lists share one staged table
     int splits = (2048 + nqb - 1) / nqb;
     if (splits > a.nprobe) splits = a.nprobe;
     if (splits > 65535) splits = 65535;
     if (splits < 1) splits = 1;
     const dim3 grid((unsigned)nqb, (unsigned)splits), block(IVF_THREADS);
-#define IVF_LAUNCH(MWV) hipLaunchKernelGGL((ivf_scan_kernel<MWV, PART>), grid, block, 0, s, a)
-    if (words && a.m == 4) IVF_LAUNCH(1);
-    else if (words && a.m == 8) IVF_LAUNCH(2);
-    else if (words && a.m == 12) IVF_LAUNCH(3);
-    else if (words && a.m == 16) IVF_LAUNCH(4);
+#define IVF_LAUNCH(MWV)                                                                                 \
+    do {                                                                                                \
+        if (packed) hipLaunchKernelGGL((ivf_scan_kernel<MWV, PART, true>), grid, block, 0, s, a);       \
+        else hipLaunchKernelGGL((ivf_scan_kernel<MWV, PART, false>), grid, block, 0, s, a);             \
+    } while (0)
+    if (rowb == 4) IVF_LAUNCH(1);
+    else if (rowb == 8) IVF_LAUNCH(2);
+    else if (rowb == 12) IVF_LAUNCH(3);
+    else if (rowb == 16) IVF_LAUNCH(4);
     else IVF_LAUNCH(0);
 #undef IVF_LAUNCH
     LSQ_HIP(hipGetLastError());
@@ -199,9 +222,10 @@ int launch_scan(hipStream_t s, const IvfScan &a, int nqb, bool words) {
 }  // namespace
 
 struct lsq_ivf_state {
-    int nlist = 0, m = 0, d = 0;
+    int nlist = 0, m = 0, d = 0, packed = 0;
     int64_t n = 0;
-    DevBuf cent, codes, norms, ids, off;                             // the layout: centroids, and per position the code row, the norm, the original id
+    const float *table = nullptr;                                    // packed: the index's norm table (256 floats, alive as long as the index)
+    DevBuf cent, codes, norms, ids, off;                             // the layout: centroids, and per position the code row (packed: with its norm byte), the norm (not packed), the original id
     DevBuf s_lor, keys_a, keys_b, tmp, flag;                         // set_lists' scratch
     DevBuf cd, ci, pos, plan, lut, rec_a, rec_b, seg, count, fail, qsel, head_d, head_i;      // the search's
     PhaseClock<6> clock;                                             // one batch: tables, scan, selection and, thresholded, the tail's scan and selection
@@ -221,7 +245,8 @@ int lsq_ivf_nlist(const lsq_ivf_state *st) { return st ? st->nlist : 0; }
 
 void lsq_ivf_get_info(const lsq_ivf_state *st, lsq_ivf_info *out) { *out = st ? st->info : lsq_ivf_info{}; }
 
-int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **pst, const uint8_t *codes, const float *norms, int64_t n, int m, int d, const lsq_ivf_desc *desc) {
+int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **pst, const uint8_t *codes, const float *norms, int packed, int64_t n, int m, int d,
+                      const lsq_ivf_desc *desc) {
     if (!*pst) *pst = new lsq_ivf_state();
     lsq_ivf_state *st = *pst;
     const int nlist = desc->nlist;
@@ -254,17 +279,22 @@ int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **pst, const uint8_t *codes, 
     LSQ_TRY(st->tmp.ensure(bytes > 0 ? bytes : 16));
     LSQ_HIP(hipcub::DeviceRadixSort::SortKeys(st->tmp.p, bytes, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), (int)n, 0, 32 + list_bits, s));
     LSQ_TRY(st->cent.ensure(sizeof(float) * (size_t)nlist * d));
-    LSQ_TRY(st->codes.ensure((size_t)n * m + 16));                   // 16 bytes of slack past the last row, never read
-    LSQ_TRY(st->norms.ensure(sizeof(float) * (size_t)n));
+    const int rowb = packed ? m + 1 : m;
+    LSQ_TRY(st->codes.ensure((size_t)n * rowb + 16));                // 16 bytes of slack past the last row, never read
+    if (!packed) LSQ_TRY(st->norms.ensure(sizeof(float) * (size_t)n));
     LSQ_TRY(st->ids.ensure(sizeof(int) * (size_t)n));
     LSQ_TRY(st->off.ensure(sizeof(int) * ((size_t)nlist + 1)));
     LSQ_HIP(hipMemcpyAsync(st->cent.p, desc->centroids, sizeof(float) * (size_t)nlist * d, hipMemcpyDefault, s));
     hipLaunchKernelGGL(ivf_offsets_kernel, dim3(blocks_n1), dim3(256), 0, s, st->keys_b.as<uint64_t>(), n, nlist, st->off.as<int>());
-    hipLaunchKernelGGL(ivf_layout_kernel, dim3(blocks_n), dim3(256), 0, s, st->keys_b.as<uint64_t>(), n, m, codes, norms, st->codes.as<uint8_t>(),
-                       st->norms.as<float>(), st->ids.as<int>());
+    if (packed)
+        hipLaunchKernelGGL(ivf_layout_packed_kernel, dim3(blocks_n), dim3(256), 0, s, st->keys_b.as<uint64_t>(), n, rowb, codes, st->codes.as<uint8_t>(),
+                           st->ids.as<int>());
+    else
+        hipLaunchKernelGGL(ivf_layout_kernel, dim3(blocks_n), dim3(256), 0, s, st->keys_b.as<uint64_t>(), n, m, codes, norms, st->codes.as<uint8_t>(),
+                           st->norms.as<float>(), st->ids.as<int>());
     LSQ_HIP(hipGetLastError());
     LSQ_HIP(hipStreamSynchronize(s));
-    st->nlist = nlist; st->n = n; st->m = m; st->d = d;
+    st->nlist = nlist; st->n = n; st->m = m; st->d = d; st->packed = packed; st->table = packed ? norms : nullptr;
     return LSQ_OK;
 }
 
@@ -297,29 +327,29 @@ int run_batch(const Chunk &c, const int *qsel, int q0, int nqb, int cap, bool th
     LSQ_TRY(st->clock.mark(s));
     IvfScan a{};
     a.LUT = st->lut.as<float>(); a.QT = QT;
-    a.codes = st->codes.as<uint8_t>(); a.norms = st->norms.as<float>(); a.ids = st->ids.as<int>(); a.off = st->off.as<int>();
+    a.codes = st->codes.as<uint8_t>(); a.norms = st->packed ? st->table : st->norms.as<float>(); a.ids = st->ids.as<int>(); a.off = st->off.as<int>();
     a.probe = st->ci.as<int>(); a.coarse = st->cd.as<float>(); a.pos = st->pos.as<int>(); a.plan = st->plan.as<int>();
     a.qsel = qsel; a.q0 = q0;
     a.nprobe = c.nprobe; a.m = m; a.nn = c.nn; a.cap = cap; a.idbits = c.idbits; a.add = (c.flags & LSQ_IVF_ADD_COARSE) ? 1 : 0;
     a.count = st->count.as<unsigned>(); a.out = st->rec_a.as<uint64_t>();
-    const bool words = m % 4 == 0;
+    const bool packed = st->packed != 0;
     // records: (padding bit, distance key, original id + 1), sorted on 33 + idbits bits; the hand-out drops the bit: (+inf, 0) for padding
     if (!thresholded) {
-        LSQ_TRY(launch_scan<0>(s, a, nqb, words));
+        LSQ_TRY(launch_scan<0>(s, a, nqb, packed));
         LSQ_TRY(st->clock.mark(s));
         LSQ_TRY(lsq_adc_select(c.adc, s, st->rec_a.as<uint64_t>(), st->rec_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(), nullptr, qsel, q0,
                                nqb, cap, c.nn, c.dists, c.ids, c.idbits, 33 + c.idbits, 0));
     } else {
         LSQ_TRY(st->head_d.ensure(sizeof(float) * (size_t)nqb * c.nn));
         LSQ_TRY(st->head_i.ensure(sizeof(int) * (size_t)nqb * c.nn));
-        LSQ_TRY(launch_scan<1>(s, a, nqb, words));
+        LSQ_TRY(launch_scan<1>(s, a, nqb, packed));
         LSQ_TRY(st->clock.mark(s));
         // the head, sorted: head_d[slot][nn - 1] is tau
         LSQ_TRY(lsq_adc_select(c.adc, s, st->rec_a.as<uint64_t>(), st->rec_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(), nullptr, nullptr, 0,
                                nqb, cap, c.nn, st->head_d.as<float>(), st->head_i.as<int>(), c.idbits, 33 + c.idbits, 0));
         LSQ_TRY(st->clock.mark(s));
         a.tau = st->head_d.as<float>();
-        LSQ_TRY(launch_scan<2>(s, a, nqb, words));
+        LSQ_TRY(launch_scan<2>(s, a, nqb, packed));
         LSQ_TRY(st->clock.mark(s));
         LSQ_TRY(lsq_adc_select(c.adc, s, st->rec_a.as<uint64_t>(), st->rec_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(), st->fail.as<int>(),
                                qsel, q0, nqb, cap, c.nn, c.dists, c.ids, c.idbits, 33 + c.idbits, 0));

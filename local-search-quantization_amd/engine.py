@@ -367,6 +367,17 @@ class Engine:
         tensor or a view of one with unit column stride, at any byte offset."""
         return Index(self, dcodes, dK, dnorms, m, base, h, d, on_device=True)
 
+    def index_packed(self, codes, K, norm_codes, cbnorms, m, base=None, h=H):
+        """An Index that keeps the norm BYTE: codes (n,m) uint8 0-based, norm_codes (n,) uint8 0-based indexes into cbnorms (<= 256,) float32 -- what
+        quantize_norms computes -- packed into rows of m + 1 bytes that the index owns.  Every search returns the bits of Engine.index(codes, K,
+        cbnorms[norm_codes], m, base)   [lsq_index_create_packed]"""
+        return Index(self, codes, K, None, m, base, h, None, on_device=False, packed=(norm_codes, cbnorms))
+
+    def index_packed_dev(self, dcodes, dK, dnorm_codes, dcbnorms, m, base=None, h=H):
+        """The same from device tensors (quantize_norms_dev's idx as it is).  dcodes, dnorm_codes and dcbnorms are read once, before this returns: they
+        may be freed or overwritten afterwards; dK and base are borrowed as in index_dev."""
+        return Index(self, dcodes, dK, None, m, base, h, None, on_device=True, packed=(dnorm_codes, dcbnorms))
+
     # -- (1e) the beam-search encoder on resident codebooks ----------------------------------
     def encoder(self, K, m, chunk=0, h=H):
         """An Encoder of HOST codebooks K (m*h,d), copied once: ||c||^2 and the pair tables are built here, not per call.  Its beam() takes and returns
@@ -677,12 +688,14 @@ class Index(_Handle):
 
     _destroy = "lsq_index_destroy"
 
-    def __init__(self, engine, codes, K, dbnorms, m, base, h, d, on_device):
+    def __init__(self, engine, codes, K, dbnorms, m, base, h, d, on_device, packed=None):
         side = self._bind(engine, on_device)
         codes, K, dbnorms = side.maybe(codes, _U8, "codes"), side.maybe(K, _F32, "K"), side.maybe(dbnorms, _F32, "dbnorms")
         u8 = False
         if base is not None:
             base, u8 = side.take_x(base, "base", rows=True)
+        if packed is not None:
+            return self._init_packed(side, codes, K, packed, m, base, u8, h)
         if codes is None and base is None:
             raise ValueError("an index needs codes, base rows or both")
         n = int(codes.shape[0] if codes is not None else base.shape[0])
@@ -699,6 +712,27 @@ class Index(_Handle):
         self._keep = (codes, K, dbnorms, base)      # borrowed device tensors stay alive with the index
         self.n, self.d, self.m = n, d, int(m)
         self._create("lsq_index_create", desc)
+
+    def _init_packed(self, side, codes, K, packed, m, base, u8, h):
+        """the packed form (Engine.index_packed): the norm bytes and their table instead of dbnorms; checked here, refused before any library call"""
+        if codes is None or K is None:
+            raise ValueError("a packed index needs codes and codebooks")
+        if not side.dev and np.asarray(packed[0]).dtype != _U8:      # the host side converts values, but a norm byte is an index: never narrowed silently
+            raise TypeError("norm_codes must be uint8, got %s" % np.asarray(packed[0]).dtype)
+        nc, cb = side.take(packed[0], _U8, "norm_codes"), side.take(packed[1], _F32, "cbnorms")
+        n, d = int(codes.shape[0]), int(K.shape[1])
+        _shapes(("codes", codes, (n, m)), ("K", K, (m * h, d)), ("norm_codes", nc, (n,)), ("cbnorms", cb, (None,)))
+        if not 1 <= int(cb.shape[0]) <= 256:
+            raise ValueError("cbnorms must hold 1 .. 256 entries, got %d" % int(cb.shape[0]))
+        if base is not None:
+            _shapes(("base", base, (n, max(d, base.shape[1]))))
+        desc, p = _lib.IndexPackedDesc(), side.ptr
+        desc.n, desc.d, desc.m, desc.h = n, d, int(m), int(h)
+        desc.codes, desc.norm_codes, desc.cbnorms, desc.ncb, desc.codebooks = p(codes), p(nc), p(cb), int(cb.shape[0]), p(K)
+        desc.base, desc.base_u8, desc.ldb, desc.on_device = p(base), int(u8), 0 if base is None else int(side.pitch(base)), int(self._dev)
+        self._keep = (K, base)                      # what a device index borrows; codes, norm bytes and table were copied
+        self.n, self.d, self.m = n, d, int(m)
+        self._create("lsq_index_create_packed", desc)
 
     def _search_args(self, Q_scan, k, **others):
         """the queries of a two-stage search, each of the others (name=array or None) defaulting to Q_scan -> Qs, the others in order, dists, ids"""
@@ -780,6 +814,14 @@ class Index(_Handle):
 
     def stats(self):
         return self._info("lsq_index_get_stats", _lib.IndexStats)
+
+    def packed_info(self):
+        """row_bytes (m + 1), ivf_row_bytes (m + 5 once lists are set), ncb, dword_rows, resident_bytes; all zero on an index that is not packed"""
+        return self._info("lsq_index_get_packed_info", _lib.IndexPackedInfo)
+
+    def scan_stats(self):
+        """the selection statistics of the last search()'s scan: Engine.linscan_stats' fields, this call's figures alone"""
+        return self._info("lsq_index_get_scan_stats", _lib.LinscanStats)
 
 
 # -- the beam-search encoder (made by Engine.encoder / Engine.encoder_dev) ------------------------

@@ -160,6 +160,37 @@ def linscan_lsq(B, X, C, dbnorms, R, k=10000, *, nthreads=0, engine=None):
     return dists.T, res.T
 
 
+def linscan_lsq_bytes(B, X, C, cbnorms, B_norms, R, k=10000, *, engine=None, nthreads=0):
+    """linscan_lsq on the codes as train_lsq and quantize_norms leave them: the norm of a vector is ONE BYTE, an index into cbnorms, and is never widened
+    to a float per vector (the reference does that one line before its scan, demos/demo_lsq_gpu.jl:57-60).
+    B (m, n) uint8 0-based; X (d, nq); C list of (d, h); cbnorms (ncb <= 256,) float32; B_norms (n,) integers 1-BASED as quantize_norms returns them.
+    -> linscan_lsq(B, X, C, cbnorms[B_norms - 1], R, k)'s arrays exactly.
+    engine=<Engine>: a packed index (Engine.index_packed) of m + 1 bytes per vector; engine=None: the norms widened in numpy, the host scan."""
+    cb = np.asarray(cbnorms)
+    bn = np.asarray(B_norms)
+    Bm = np.asarray(B)
+    if cb.dtype != np.float32:
+        raise TypeError("cbnorms must be float32, got %s" % cb.dtype)
+    if bn.dtype.kind not in "iu":
+        raise TypeError("B_norms must be an integer array (1-based indexes into cbnorms), got %s" % bn.dtype)
+    if Bm.dtype != np.uint8:
+        raise TypeError("B must be uint8 (0-based codes), got %s" % Bm.dtype)
+    if cb.ndim != 1 or not 1 <= cb.shape[0] <= 256:
+        raise ValueError("cbnorms must be a vector of 1 .. 256 entries, got shape %s" % (cb.shape,))
+    if Bm.ndim != 2 or bn.ndim != 1 or bn.shape[0] != Bm.shape[1]:
+        raise ValueError("B_norms must hold one entry per code: B %s, B_norms %s" % (Bm.shape, bn.shape))
+    if bn.size and (int(bn.min()) < 1 or int(bn.max()) > cb.shape[0]):
+        raise ValueError("B_norms must lie in 1 .. %d (got %d .. %d)" % (cb.shape[0], int(bn.min()), int(bn.max())))
+    if engine is None:
+        return linscan_lsq(Bm, X, C, cb[bn.astype(np.int64) - 1], R, k, nthreads=nthreads)
+    codes = np.ascontiguousarray(Bm.T)
+    RX = np.ascontiguousarray((np.asarray(R, dtype=np.float32).T @ np.asarray(X, dtype=np.float32)).T)
+    h = np.asarray(C[0]).shape[1]
+    with engine.index_packed(codes, _K_of(C), (bn.astype(np.int64) - 1).astype(np.uint8), np.ascontiguousarray(cb), codes.shape[1], h=h) as ix:
+        dists, res = ix.search(RX, k)
+    return dists.T, res.T
+
+
 def linscan_pq(B, X, C, b, k=10000, *, engine=None):
     """Linear scan with PQ codes  (src/linscan/Linscan.jl:5-26 -> linscan_aqd_query, src/linscan/cpp/linscan_aqd.cpp:37-114).
     B (m, n) uint8 0-based; X (d, nq) queries; C list of (subdim, h) centre matrices; b bits per code (8 m); d % m == 0 (Cint(d/m)).

@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE] [--init beam:L] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -20,6 +20,10 @@ re-ranked lists printed next to the ADC one.  The reference has no such stage: i
 
 --ivf NLIST:NPROBE: after the ADC scan, inverted lists over the same codes (train_coarse on the base rows, Index.set_lists) and the search that reads
 each query's NPROBE nearest lists alone (Index.search_ivf); its recall curve is printed next to the exhaustive one.  The reference has no such search.
+
+--norm-byte: the norm byte that quantize_norms computes stays a byte up to the search: a packed index (Engine.index_packed, rows of m code bytes and one
+norm byte: the 64-bit code at m = 7) is searched through linscan_lsq_bytes, and its ids and distances are checked to equal the float-norm run's.  The
+reference widens the byte to a float per vector one line before its scan (demo_lsq_gpu.jl:57-60).
 
 needs $LSQ_DATA_DIR/sift/{sift_learn,sift_base,sift_query}.fvecs and sift_groundtruth.ivecs (TEXMEX layout).  The file's ground truth
 describes the full 10^6-vector base only: for a prefix of it (nread_base < 10^6) and for the stand-in, the ground truth is exact k-NN of the base
@@ -143,8 +147,8 @@ def main():
         except (ValueError, AssertionError, IndexError):
             raise SystemExit("--ivf takes NLIST:NPROBE with 1 <= NPROBE <= NLIST")
         del argv[at:at + 2]
-    args = [a for a in argv if a not in ("--resident", "--bvecs")]
-    resident, bvecs = "--resident" in argv, "--bvecs" in argv
+    args = [a for a in argv if a not in ("--resident", "--bvecs", "--norm-byte")]
+    resident, bvecs, norm_byte = "--resident" in argv, "--bvecs" in argv, "--norm-byte" in argv
     real = bool(os.environ.get("LSQ_DATA_DIR"))
     nt = int(args[0]) if len(args) > 0 else (10_000 if real else 3000)
     nb = int(args[1]) if len(args) > 1 else (1_000_000 if real else 6000)
@@ -191,6 +195,15 @@ def main():
     print("Searched %d queries: device %.3f s (host buffers, incl. copies), host %.3f s; identical results" % (x_query.shape[1], t_dev, t_host))
     rec = lsq.eval_recall(gt, idx.astype(np.uint32), knn, True)
     print("%s: recall@1 = %.4f, recall@%d = %.4f" % (name, rec[0], knn, rec[knn - 1]))
+    if norm_byte:
+        t0 = time.perf_counter()
+        with lsq.Engine(0) as eng:                                          # the same scan on rows of m + 1 bytes: the norm stays the byte quantize_norms made
+            bd, bidx = lsq.linscan_lsq_bytes((B_base - 1).astype(np.uint8), x_query, C, np.asarray(cbnorms, dtype=np.float32), nidx,
+                                             np.eye(d, dtype=np.float32), knn, engine=eng)
+        t_byte = time.perf_counter() - t0
+        assert np.array_equal(bidx, idx) and np.array_equal(bd.view(np.uint32), dists.view(np.uint32)), "the packed index and the float-norm scan disagree"
+        print("Norm byte kept (%d bytes per vector resident instead of %d): %.3f s incl. the upload of the index; ids and distances equal the float-norm run's"
+              % (m + 1, m + 4, t_byte))
     if shortlist:
         L = min(shortlist, x_base.shape[1])
         keep = min(knn, L)
