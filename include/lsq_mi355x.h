@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 1800
+#define LSQ_VERSION 1900
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -568,6 +568,77 @@ LSQ_API int lsq_index_get_packed_info(lsq_index *ix, lsq_index_packed_info *out)
  * threshold_rank, list_capacity, candidates, fallback_queries, batches -- what tells a scan that sampled other rows from one that did not when the
  * fallback road has repaired the results. */
 LSQ_API int lsq_index_get_scan_stats(lsq_index *ix, lsq_linscan_stats *out);
+
+/* ---- (3i) the coarse partition: building a residual inverted-list index resident on the device (csrc/lsq_partition.hip; since v1900) ---------------------
+ * THE REFERENCE HAS NO COUNTERPART.  (3g) searches residual codes (LSQ_IVF_ADD_COARSE); these eleven symbols BUILD them: every step between "a base set
+ * in HBM" and "a residual index with lists set" that is not already the resident trainer's or encoder's -- nearest centroid, cluster means, residuals,
+ * the scalar a residual row stores -- on f32 rows or the un-widened uint8 rows of a .bvecs set, each with a host checker that fixes its bits.
+ * The handle: lsq_partition_create COPIES nlist x d f32 centroids (host memory, or device memory with on_device = 1) -- lsq_partition_update replaces
+ * them, so they are never borrowed --, owns its scratch and runs on the context's device and on the stream the context is bound to at each call; the
+ * context must outlive it; like the context it serves one host thread at a time.  Nothing of the context is written: calls on the partition and calls
+ * on the context, or on an index or encoder of the same context, do not disturb each other.
+ * X [n][ldx] f32 (x_u8 = 0, 4-byte aligned) or uint8 (x_u8 = 1, any byte alignment); ldx, ldr in ELEMENTS; only the first d elements of a row are read
+ * or written.  on_device: 0 = every array of the call is a host buffer (uploaded, computed, downloaded), 1 = device buffers.  Every call waits for the
+ * device (a control word comes back); n = 0 is LSQ_OK and touches nothing.
+ *
+ * assign      list_of_row[i] = the first of the (dist, list id) pairs of lsq_index_knn / lsq_knn_exact with the centroids as base and nn = 1: f32
+ *             direct form, dimensions ascending, every op rounded, no FMA; ties to the smaller list, NaN last -- the rule lsq_index_search_ivf probes by
+ *             and the ids lsq_knn_exact_u8_cpu returns for (base = centroids, queries = X).  uint8 rows are widened in registers (exact).  dist
+ *             (optional, [n]) receives the distance.  The search is the exact search of (3f) on a base-only index inside the handle.
+ * update      one Lloyd half-step.  For every list l with at least one row and every dimension t: the values (double)x_it of its rows in ASCENDING ROW
+ *             ID, added one after another from +0.0 in float64, divided by (double)count and rounded to f32 (numpy: np.add.at on float64 sums, then
+ *             sums / counts and .astype(float32)).  A list without rows keeps its centroid's bits.  counts (optional, [nlist] int32) receives the list
+ *             sizes.  No atomics: rows are grouped by the radix sort of lsq_index_set_lists, two calls give the same bits.
+ * residuals   R[i][t] = x_it - c_{l_i, t}: one rounded f32 subtraction (uint8 widened first, exact); NaN, +-inf and -0.0 as IEEE gives them.  By what
+ *             the base pointer and the pitch in bytes are both multiples of, four components of an f32 row travel as one 16-byte load or four
+ *             dwords, four of a uint8 row as one dword or four bytes (lsq_partition_info.loader_bytes: 16, 4 or 1).
+ * code_norms  the scalar a residual index stores.  With r^_t the reconstruction of a row's codes in lsq_quantize_norms' order (codebooks ascending from
+ *             the first codeword) and c the centroid of the row's list:  a = chain over t ascending of a + r^_t r^_t from 0 (the bits of
+ *             lsq_quantize_norms_dev's norms);  b = chain of b + c_t r^_t from 0;  s = a + (b + b); every product and add rounded, no FMA.  norms
+ *             (optional with cbnorms) receives s.  With cbnorms (1 <= ncb <= 256): norm_codes (optional) the 0-based first minimum of
+ *             (s - cbnorms[j])^2 in f32 (lsq_quantize_norms' rule), dbnorms (optional) cbnorms[code] -- what lsq_index_create and
+ *             lsq_index_create_packed take.  With cbnorms NULL, norms must be given and the other two outputs are ignored.  codes [n][m] uint8
+ *             0-based, codebooks [m*h][d], h = 256, 1 <= m <= 16.
+ * LSQ_EINVAL, nothing launched: a null handle or pointer, nlist outside 1 .. 2^24, d < 1, n < 0 or n > 2^31 - 2, ldx < d, ldr < d, f32 rows not 4-byte
+ * aligned, h != 256, m outside 1 .. 16, ncb outside 1 .. 256.  A list_of_row entry outside [0, nlist) is LSQ_EINVAL too: it is found on the device and never
+ * used as an offset; update then leaves the centroids as they were, residuals and code_norms leave their outputs unspecified. */
+typedef struct lsq_partition lsq_partition;
+typedef struct lsq_partition_desc {
+    int nlist, d;
+    const float *centroids;      /* [nlist][d] */
+    int on_device;
+} lsq_partition_desc;
+enum { LSQ_PARTITION_ASSIGN = 1, LSQ_PARTITION_UPDATE = 2, LSQ_PARTITION_RESIDUALS = 3, LSQ_PARTITION_CODE_NORMS = 4 };
+typedef struct lsq_partition_info {      /* the last call on the handle */
+    int64_t call;                        /* LSQ_PARTITION_*: which one (0: none yet) */
+    int64_t rows;                        /* n */
+    int64_t lists_touched, empty_lists;  /* update: lists with rows (their centroids were replaced) and without; other calls: 0 */
+    int64_t loader_bytes;                /* residuals: 16, 4 or 1 -- how wide the loads of X were; update: the element size; other calls: 0 */
+    int64_t max_list_rows;               /* update: the longest list (the longest chain of dependent float64 adds) */
+    double group_ms, kernel_ms;          /* with the context's option "profile" = 1: update's keys + sort + offsets; the call's own kernel (assign: the search) */
+} lsq_partition_info;
+LSQ_API int lsq_partition_create(lsq_partition **out, lsq_ctx *ctx, const lsq_partition_desc *desc);
+LSQ_API int lsq_partition_destroy(lsq_partition *p);
+LSQ_API int lsq_partition_get_centroids(lsq_partition *p, float *out, int on_device);
+LSQ_API int lsq_partition_get_info(lsq_partition *p, lsq_partition_info *out);
+LSQ_API int lsq_partition_assign(lsq_partition *p, const void *X, int x_u8, int64_t n, int ldx, int32_t *list_of_row, float *dist, int on_device);
+LSQ_API int lsq_partition_update(lsq_partition *p, const void *X, int x_u8, int64_t n, int ldx, const int32_t *list_of_row, int32_t *counts,
+                                 int on_device);
+LSQ_API int lsq_partition_residuals(lsq_partition *p, const void *X, int x_u8, int64_t n, int ldx, const int32_t *list_of_row, float *R, int ldr,
+                                    int on_device);
+LSQ_API int lsq_partition_code_norms(lsq_partition *p, const uint8_t *codes, const float *codebooks, int64_t n, int m, int h,
+                                     const int32_t *list_of_row, const float *cbnorms, int ncb, float *norms, uint8_t *norm_codes, float *dbnorms,
+                                     int on_device);
+/* The host checkers and engine-less roads (no context, std::thread workers, nthreads 0 = all): the three contracts above on plain arrays, bit for bit.
+ * centroids [nlist][d]: read (residuals, code_norms) or updated in place (update).  assign's checker is lsq_knn_exact_u8_cpu with nn = 1 and the
+ * centroids as base.  LSQ_EINVAL as above; a list_of_row entry outside [0, nlist) is found before anything is written. */
+LSQ_API int lsq_partition_update_cpu(float *centroids, int32_t *counts, const void *X, int x_u8, int64_t n, int d, int ldx, const int32_t *list_of_row,
+                                     int nlist, int nthreads);
+LSQ_API int lsq_partition_residuals_cpu(float *R, int ldr, const void *X, int x_u8, int64_t n, int d, int ldx, const float *centroids,
+                                        const int32_t *list_of_row, int nlist, int nthreads);
+LSQ_API int lsq_partition_code_norms_cpu(float *norms, uint8_t *norm_codes, float *dbnorms, const uint8_t *codes, const float *codebooks,
+                                         const float *centroids, const int32_t *list_of_row, int64_t n, int m, int h, int d, int nlist,
+                                         const float *cbnorms, int ncb, int nthreads);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB      src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

@@ -91,6 +91,18 @@ class EncoderInfo(_Struct):
     _fields_ = [("vectors", C.c_int64), ("chunks", C.c_int64), ("beam", C.c_int64), ("unaries_ms", C.c_double), ("beam_ms", C.c_double)]
 
 
+class PartitionDesc(_Struct):
+    _fields_ = [("nlist", C.c_int), ("d", C.c_int), ("centroids", C.c_void_p), ("on_device", C.c_int)]
+
+
+class PartitionInfo(_Struct):
+    _fields_ = [("call", C.c_int64), ("rows", C.c_int64), ("lists_touched", C.c_int64), ("empty_lists", C.c_int64), ("loader_bytes", C.c_int64),
+                ("max_list_rows", C.c_int64), ("group_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
+PARTITION_ASSIGN, PARTITION_UPDATE, PARTITION_RESIDUALS, PARTITION_CODE_NORMS = 1, 2, 3, 4
+
+
 class Q16SnapshotNode(_Struct):
     _fields_ = [("loU", C.c_float), ("invD", C.c_float), ("D", C.c_float), ("hiq", C.c_float), ("window", C.c_int32), ("pad_", C.c_int32),
                 ("slack", C.c_double)]
@@ -186,6 +198,18 @@ SIGNATURES = {
     "lsq_encoder_destroy": (_i, [_vp]),
     "lsq_encoder_beam": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _i]),
     "lsq_encoder_get_info": (_i, [_vp, C.POINTER(EncoderInfo)]),
+    # the coarse partition of a residual inverted-list index (since v1900), and its host checkers
+    "lsq_partition_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(PartitionDesc)]),
+    "lsq_partition_destroy": (_i, [_vp]),
+    "lsq_partition_get_centroids": (_i, [_vp, _vp, _i]),
+    "lsq_partition_get_info": (_i, [_vp, C.POINTER(PartitionInfo)]),
+    "lsq_partition_assign": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i]),
+    "lsq_partition_update": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i]),
+    "lsq_partition_residuals": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i, _i]),
+    "lsq_partition_code_norms": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i]),
+    "lsq_partition_update_cpu": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i, _i]),
+    "lsq_partition_residuals_cpu": (_i, [_vp, _i, _vp, _i, _i64, _i, _i, _vp, _vp, _i, _i]),
+    "lsq_partition_code_norms_cpu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _i, _i]),
     "lsq_quantize_norms": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "lsq_quantize_norms_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "lsq_update_codebooks": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _vp]),

@@ -148,6 +148,13 @@ static int use_device(lsq_ctx *ctx) {
     return LSQ_OK;
 }
 
+int lsq_ctx_bind(lsq_ctx *c, hipStream_t *stream, int *profile) {
+    LSQ_TRY(use_device(c));
+    *stream = c->stream;
+    *profile = c->profile;
+    return LSQ_OK;
+}
+
 struct Timer {        // brackets a group of launches with an event pair when profiling is on
     lsq_ctx *c; int cat; hipEvent_t a = nullptr, b = nullptr; bool on;
     Timer(lsq_ctx *ctx, int category) : c(ctx), cat(category), on(ctx->profile != 0) {

@@ -390,6 +390,23 @@ int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **st, const uint8_t *codes, c
 int lsq_ivf_search(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *K, float *dists, int *ids, const float *q_scan,
                    const float *q_coarse, int64_t ldc, int nq, int nprobe, int nn, int flags, const lsq_search_opts &coarse, int timed);
 
+// ---- rows grouped by list (lsq_ivf.hip): the sort behind lsq_index_set_lists and lsq_partition_update.  Scratch of whoever groups: the staged list of a
+// host-buffer call, the keys (list << 32 | row) before and after the sort, the sort's workspace and the range check's counter ------------------------------
+struct lsq_row_groups {
+    DevBuf s_lor, keys_a, keys_b, tmp, flag;
+    void release() { s_lor.release(); keys_a.release(); keys_b.release(); tmp.release(); flag.release(); }
+};
+// the keys and the range check: *bad = entries outside [0, nlist), read back (the call waits); with *bad != 0 nothing may be sorted
+int lsq_rows_keys(hipStream_t s, lsq_row_groups &g, const int32_t *list_of_row, int on_device, int64_t n, int nlist, unsigned *bad);
+// *sorted = the keys list by list and, within a list, ascending by row (in g: valid until the next lsq_rows_keys on it)
+int lsq_rows_sort(hipStream_t s, lsq_row_groups &g, int64_t n, int nlist, const uint64_t **sorted);
+// off[l] = the first position of list l in the sorted keys, off[nlist] = n
+int lsq_rows_offsets(hipStream_t s, const uint64_t *sorted, int64_t n, int nlist, int *off);
+
+// ---- what a handle that lives in a file of its own (lsq_partition.hip) needs of its context (lsq_api.hip): its device made current, the stream it is bound
+// to now, option "profile".  Nothing of the context is written ------------------------------------------------------------------------------------------
+int lsq_ctx_bind(lsq_ctx *c, hipStream_t *stream, int *profile);
+
 // argument checks of the PQ / OPQ scan (lsq_linscan.hip), shared by the host drop-in and the device scan
 int lsq_linscan_pq_check(const char *fn, const void *dists, const void *res, const void *codes, const void *centers, const void *queries, int N,
                          uint32_t NQ, int B, int K, int dim1codes, int dim1queries, int subdim);

@@ -221,12 +221,51 @@ int launch_scan(hipStream_t s, const IvfScan &a, int nqb, bool packed) {
 
 }  // namespace
 
+// ---- rows grouped by list: the one sort behind lsq_index_set_lists and lsq_partition_update (lsq_partition.hip) -----------------------------------------
+// keys (list << 32 | row), ~0 for an entry outside [0, nlist): *bad = how many of those (the call waits for the count); nothing else has been touched then
+int lsq_rows_keys(hipStream_t s, lsq_row_groups &g, const int32_t *list_of_row, int on_device, int64_t n, int nlist, unsigned *bad) {
+    const int32_t *lor = list_of_row;
+    if (!on_device) {
+        LSQ_TRY(g.s_lor.ensure(sizeof(int32_t) * (size_t)n));
+        LSQ_HIP(hipMemcpyAsync(g.s_lor.p, list_of_row, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+        lor = g.s_lor.as<int32_t>();
+    }
+    LSQ_TRY(g.keys_a.ensure(sizeof(uint64_t) * (size_t)n));
+    LSQ_TRY(g.keys_b.ensure(sizeof(uint64_t) * (size_t)n));
+    LSQ_TRY(g.flag.ensure(sizeof(unsigned)));
+    LSQ_HIP(hipMemsetAsync(g.flag.p, 0, sizeof(unsigned), s));
+    hipLaunchKernelGGL(ivf_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lor, n, nlist, g.keys_a.as<uint64_t>(), g.flag.as<unsigned>());
+    LSQ_HIP(hipGetLastError());
+    LSQ_HIP(hipMemcpyAsync(bad, g.flag.p, sizeof(*bad), hipMemcpyDeviceToHost, s));
+    LSQ_HIP(hipStreamSynchronize(s));
+    return LSQ_OK;
+}
+
+// the keys sorted (hipcub radix sort: stable, no atomics, the same bits on every call): list by list and, within a list, ascending by row
+int lsq_rows_sort(hipStream_t s, lsq_row_groups &g, int64_t n, int nlist, const uint64_t **sorted) {
+    int list_bits = 1;
+    while ((nlist - 1) >> list_bits) ++list_bits;
+    size_t bytes = 0;
+    LSQ_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, g.keys_a.as<uint64_t>(), g.keys_b.as<uint64_t>(), (int)n, 0, 32 + list_bits, s));
+    LSQ_TRY(g.tmp.ensure(bytes > 0 ? bytes : 16));
+    LSQ_HIP(hipcub::DeviceRadixSort::SortKeys(g.tmp.p, bytes, g.keys_a.as<uint64_t>(), g.keys_b.as<uint64_t>(), (int)n, 0, 32 + list_bits, s));
+    *sorted = g.keys_b.as<uint64_t>();
+    return LSQ_OK;
+}
+
+// off[l] = the first position of list l in the sorted keys, off[nlist] = n
+int lsq_rows_offsets(hipStream_t s, const uint64_t *sorted, int64_t n, int nlist, int *off) {
+    hipLaunchKernelGGL(ivf_offsets_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s, sorted, n, nlist, off);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
 struct lsq_ivf_state {
     int nlist = 0, m = 0, d = 0, packed = 0;
     int64_t n = 0;
     const float *table = nullptr;                                    // packed: the index's norm table (256 floats, alive as long as the index)
     DevBuf cent, codes, norms, ids, off;                             // the layout: centroids, and per position the code row (packed: with its norm byte), the norm (not packed), the original id
-    DevBuf s_lor, keys_a, keys_b, tmp, flag;                         // set_lists' scratch
+    lsq_row_groups rows;                                             // set_lists' scratch: the rows grouped by list
     DevBuf cd, ci, pos, plan, lut, rec_a, rec_b, seg, count, fail, qsel, head_d, head_i;      // the search's
     PhaseClock<6> clock;                                             // one batch: tables, scan, selection and, thresholded, the tail's scan and selection
     lsq_ivf_info info{};
@@ -234,9 +273,10 @@ struct lsq_ivf_state {
 
 void lsq_ivf_free(lsq_ivf_state *st) {
     if (!st) return;
-    DevBuf *all[] = {&st->cent, &st->codes, &st->norms, &st->ids, &st->off, &st->s_lor, &st->keys_a, &st->keys_b, &st->tmp, &st->flag, &st->cd, &st->ci,
+    DevBuf *all[] = {&st->cent, &st->codes, &st->norms, &st->ids, &st->off, &st->cd, &st->ci,
                      &st->pos, &st->plan, &st->lut, &st->rec_a, &st->rec_b, &st->seg, &st->count, &st->fail, &st->qsel, &st->head_d, &st->head_i};
     for (DevBuf *b : all) b->release();
+    st->rows.release();
     st->clock.release();
     delete st;
 }
@@ -250,34 +290,17 @@ int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **pst, const uint8_t *codes, 
     if (!*pst) *pst = new lsq_ivf_state();
     lsq_ivf_state *st = *pst;
     const int nlist = desc->nlist;
-    const unsigned blocks_n = (unsigned)((n + 255) / 256), blocks_n1 = (unsigned)((n + 1 + 255) / 256);
-    const int32_t *lor = desc->list_of_row;
-    if (!desc->on_device) {
-        LSQ_TRY(st->s_lor.ensure(sizeof(int32_t) * (size_t)n));
-        LSQ_HIP(hipMemcpyAsync(st->s_lor.p, desc->list_of_row, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-        lor = st->s_lor.as<int32_t>();
-    }
+    const unsigned blocks_n = (unsigned)((n + 255) / 256);
     // the range check: the one kernel that reads the entries; nothing of the layout is touched before its verdict
-    LSQ_TRY(st->keys_a.ensure(sizeof(uint64_t) * (size_t)n));
-    LSQ_TRY(st->keys_b.ensure(sizeof(uint64_t) * (size_t)n));
-    LSQ_TRY(st->flag.ensure(sizeof(unsigned)));
-    LSQ_HIP(hipMemsetAsync(st->flag.p, 0, sizeof(unsigned), s));
-    hipLaunchKernelGGL(ivf_keys_kernel, dim3(blocks_n), dim3(256), 0, s, lor, n, nlist, st->keys_a.as<uint64_t>(), st->flag.as<unsigned>());
-    LSQ_HIP(hipGetLastError());
     unsigned bad = 0;
-    LSQ_HIP(hipMemcpyAsync(&bad, st->flag.p, sizeof(bad), hipMemcpyDeviceToHost, s));
-    LSQ_HIP(hipStreamSynchronize(s));
+    LSQ_TRY(lsq_rows_keys(s, st->rows, desc->list_of_row, desc->on_device, n, nlist, &bad));
     if (bad) {
         lsq_set_error("lsq_index_set_lists: %u entries of list_of_row lie outside [0, %d)", bad, nlist);
         return LSQ_EINVAL;
     }
     st->nlist = 0;                                                   // no lists while they are rebuilt
-    int list_bits = 1;
-    while ((nlist - 1) >> list_bits) ++list_bits;
-    size_t bytes = 0;
-    LSQ_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), (int)n, 0, 32 + list_bits, s));
-    LSQ_TRY(st->tmp.ensure(bytes > 0 ? bytes : 16));
-    LSQ_HIP(hipcub::DeviceRadixSort::SortKeys(st->tmp.p, bytes, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), (int)n, 0, 32 + list_bits, s));
+    const uint64_t *sorted = nullptr;
+    LSQ_TRY(lsq_rows_sort(s, st->rows, n, nlist, &sorted));
     LSQ_TRY(st->cent.ensure(sizeof(float) * (size_t)nlist * d));
     const int rowb = packed ? m + 1 : m;
     LSQ_TRY(st->codes.ensure((size_t)n * rowb + 16));                // 16 bytes of slack past the last row, never read
@@ -285,13 +308,12 @@ int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **pst, const uint8_t *codes, 
     LSQ_TRY(st->ids.ensure(sizeof(int) * (size_t)n));
     LSQ_TRY(st->off.ensure(sizeof(int) * ((size_t)nlist + 1)));
     LSQ_HIP(hipMemcpyAsync(st->cent.p, desc->centroids, sizeof(float) * (size_t)nlist * d, hipMemcpyDefault, s));
-    hipLaunchKernelGGL(ivf_offsets_kernel, dim3(blocks_n1), dim3(256), 0, s, st->keys_b.as<uint64_t>(), n, nlist, st->off.as<int>());
+    LSQ_TRY(lsq_rows_offsets(s, sorted, n, nlist, st->off.as<int>()));
     if (packed)
-        hipLaunchKernelGGL(ivf_layout_packed_kernel, dim3(blocks_n), dim3(256), 0, s, st->keys_b.as<uint64_t>(), n, rowb, codes, st->codes.as<uint8_t>(),
-                           st->ids.as<int>());
+        hipLaunchKernelGGL(ivf_layout_packed_kernel, dim3(blocks_n), dim3(256), 0, s, sorted, n, rowb, codes, st->codes.as<uint8_t>(), st->ids.as<int>());
     else
-        hipLaunchKernelGGL(ivf_layout_kernel, dim3(blocks_n), dim3(256), 0, s, st->keys_b.as<uint64_t>(), n, m, codes, norms, st->codes.as<uint8_t>(),
-                           st->norms.as<float>(), st->ids.as<int>());
+        hipLaunchKernelGGL(ivf_layout_kernel, dim3(blocks_n), dim3(256), 0, s, sorted, n, m, codes, norms, st->codes.as<uint8_t>(), st->norms.as<float>(),
+                           st->ids.as<int>());
     LSQ_HIP(hipGetLastError());
     LSQ_HIP(hipStreamSynchronize(s));
     st->nlist = nlist; st->n = n; st->m = m; st->d = d; st->packed = packed; st->table = packed ? norms : nullptr;

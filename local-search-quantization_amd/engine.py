@@ -388,6 +388,16 @@ class Engine:
         """The same from a device tensor dK (copied as well); its beam() takes and returns torch tensors, on torch's current stream."""
         return Encoder(self, dK, m, chunk, h, on_device=True)
 
+    # -- (1f) the coarse partition of a residual inverted-list index --------------------------
+    def partition(self, centroids):
+        """A Partition of HOST centroids (nlist,d) float32, copied once (update() replaces the copy): nearest-centroid assignment, cluster means,
+        residuals and the scalar a residual index stores, on host arrays   [lsq_partition_create]"""
+        return Partition(self, centroids, on_device=False)
+
+    def partition_dev(self, dcentroids):
+        """The same from a device tensor (copied as well); its methods take and return torch tensors, on torch's current stream."""
+        return Partition(self, dcentroids, on_device=True)
+
     def quantize_norms(self, B, K, cbnorms, m, h=H):
         """B (n,m) int16 1-based, K (m*h,d), cbnorms (<= 256,): host arrays.
         -> idx (n,) int16 1-based index of the nearest norm centroid, dbnorms (n,) = cbnorms[idx-1], norms (n,) unquantised   [lsq_quantize_norms]"""
@@ -861,6 +871,121 @@ class Encoder(_Handle):
     def info(self):
         """the last beam call: vectors, chunks, beam, unaries_ms / beam_ms (with profile=True)"""
         return self._info("lsq_encoder_get_info", _lib.EncoderInfo)
+
+
+# -- the coarse partition (made by Engine.partition / Engine.partition_dev) -----------------------
+
+class Partition(_Handle):
+    """nlist coarse centroids resident on an Engine's device and the four steps that build a residual inverted-list index on them   [lsq_partition_*]:
+    assign (the nearest centroid, Index.search_ivf's own rule), update (one Lloyd half-step, numpy's float64 bits), residuals (x - c) and code_norms
+    (|r^|^2 + 2 <c, r^>, the dbnorms or norm bytes of a residual index).  Rows X (n,d) are float32 or uint8 (the un-widened bytes of a .bvecs set) and
+    may be row views: unit column stride, any pitch, uint8 at any byte offset.  Made by Engine.partition (host arrays in and out) or
+    Engine.partition_dev (torch tensors in and out)."""
+
+    _destroy = "lsq_partition_destroy"
+
+    def __init__(self, engine, centroids, on_device):
+        side = self._bind(engine, on_device)
+        cent = side.take(centroids, _F32, "centroids")
+        _shapes(("centroids", cent, (None, None)))
+        desc = _lib.PartitionDesc()
+        desc.nlist, desc.d, desc.centroids, desc.on_device = int(cent.shape[0]), int(cent.shape[1]), side.ptr(cent), int(self._dev)
+        self.nlist, self.d = int(cent.shape[0]), int(cent.shape[1])
+        self._create("lsq_partition_create", desc)    # the centroids are copied: cent is not kept
+
+    def _rows(self, X, name, dtype=None):
+        """rows read (or, with dtype, written) in place -> (array, is_u8).  The device side verifies; the host side converts what is not already a row
+        view of the right type"""
+        side = self._side
+        if side.dev:
+            X, u8 = (side.take(X, dtype, name, rows=True), False) if dtype else side.take_x(X, name, rows=True)
+            if X.shape[0] > 1 and X.stride(0) < X.shape[1]:
+                raise ValueError("%s: rows must be at least d elements apart (got strides %s)" % (name, X.stride()))
+        else:
+            if _dtname(X) == "int8":
+                raise TypeError("int8 data is not accepted: 8-bit base sets are unsigned (uint8); view or convert the array explicitly")
+            u8 = dtype is None and _dtname(X) == "uint8"
+            want = dtype or (_U8 if u8 else _F32)
+            if dtype is not None and (not isinstance(X, np.ndarray) or X.dtype != dtype):
+                raise TypeError("%s must be a %s array (it is written in place)" % (name, dtype.__name__))
+            X = np.asarray(X, dtype=want)
+            if X.ndim != 2 or X.strides[1] != X.itemsize or X.strides[0] % X.itemsize or (X.shape[0] > 1 and X.strides[0] < X.shape[1] * X.itemsize):
+                if dtype is not None:
+                    raise ValueError("%s must be 2-d rows with unit column stride (it is written in place)" % name)
+                X = np.ascontiguousarray(X)
+        _shapes((name, X, (None, self.d)))
+        return X, u8
+
+    def _lists(self, assign, n):
+        lor = self._side.take(assign, _I32, "assign")
+        _shapes(("assign", lor, (n,)))
+        return lor
+
+    def assign(self, X, want_dist=False):
+        """-> assign (n,) int32 0-based: the nearest centroid of every row by the exact search's rule (ties to the smaller list, NaN last) -- ivf_assign's
+        ids [, dist (n,) float32: the distance]   [lsq_partition_assign]"""
+        side = self._side
+        X, u8 = self._rows(X, "X")
+        n, p = X.shape[0], side.ptr
+        lor = side.new(n, _I32, X, zero=True)
+        dist = side.new(n, _F32, X, zero=True) if want_dist else None
+        if n:
+            self._eng._call(side, "lsq_partition_assign", p(X), int(u8), n, int(side.pitch(X)), p(lor), p(dist), int(self._dev), h=self._h)
+        return (lor, dist) if want_dist else lor
+
+    def update(self, X, assign, want_counts=False):
+        """One Lloyd half-step: every list with rows gets the mean of its rows -- float64 sums in ascending row id, divided by the count, rounded to
+        float32 (train_coarse's numpy bits) --, a list without rows keeps its centroid.  -> counts (nlist,) int32 or None   [lsq_partition_update]"""
+        side = self._side
+        X, u8 = self._rows(X, "X")
+        n, p = X.shape[0], side.ptr
+        lor = self._lists(assign, n)
+        counts = side.new(self.nlist, _I32, X, zero=True) if want_counts else None
+        self._eng._call(side, "lsq_partition_update", p(X) if n else None, int(u8), n, int(side.pitch(X)), p(lor) if n else None, p(counts),
+                        int(self._dev), h=self._h)
+        return counts
+
+    def residuals(self, X, assign, out=None):
+        """-> R (n,d) float32, R[i] = X[i] - centroid[assign[i]] (one rounded subtraction; uint8 rows widened first).  out: float32 rows written in
+        place (a row view with a pitch of its own is allowed: nothing between the rows is touched)   [lsq_partition_residuals]"""
+        side = self._side
+        X, u8 = self._rows(X, "X")
+        n, p = X.shape[0], side.ptr
+        lor = self._lists(assign, n)
+        R = side.new((n, self.d), _F32, X) if out is None else self._rows(out, "out", _F32)[0]
+        _shapes(("out", R, (n, self.d)))
+        if n:
+            self._eng._call(side, "lsq_partition_residuals", p(X), int(u8), n, int(side.pitch(X)), p(lor), p(R), int(side.pitch(R)), int(self._dev), h=self._h)
+        return R
+
+    def code_norms(self, codes, K, assign, cbnorms=None, h=H):
+        """The scalar a residual row stores: s = |r^|^2 + 2 <c, r^> in float32 chains (r^: the reconstruction of the row's codes, c: its list's centroid).
+        codes (n,m) uint8 0-based, K (m*h,d).  cbnorms=None -> norms (n,) float32 (the input of the norm k-means).  cbnorms (<= 256,) -> (norms, norm_codes
+        (n,) uint8: the first nearest entry, dbnorms (n,) = cbnorms[norm_codes]): what Engine.index / index_packed take   [lsq_partition_code_norms]"""
+        side = self._side
+        codes, K = side.take(codes, _U8, "codes"), side.take(K, _F32, "K")
+        cb = None if cbnorms is None else side.take(cbnorms, _F32, "cbnorms").reshape(-1)
+        _shapes(("codes", codes, (None, None)), ("K", K, (None, self.d)))
+        (n, m), p = codes.shape, side.ptr
+        _shapes(("K", K, (m * h, self.d)))
+        lor = self._lists(assign, n)
+        norms = side.new(n, _F32, K, zero=True)
+        nc, dbn = (None, None) if cb is None else (side.new(n, _U8, K, zero=True), side.new(n, _F32, K, zero=True))
+        self._eng._call(side, "lsq_partition_code_norms", p(codes) if n else None, p(K), n, int(m), int(h), p(lor) if n else None, p(cb),
+                        0 if cb is None else int(cb.shape[0]), p(norms), p(nc), p(dbn), int(self._dev), h=self._h)
+        return norms if cb is None else (norms, nc, dbn)
+
+    def centroids(self):
+        """-> the current centroids (nlist,d) float32: a copy   [lsq_partition_get_centroids]"""
+        side = self._side
+        out = side.new((self.nlist, self.d), _F32, self._eng._device())
+        self._eng._call(side, "lsq_partition_get_centroids", side.ptr(out), int(self._dev), h=self._h)
+        return out
+
+    def info(self):
+        """the last call: call (1 assign, 2 update, 3 residuals, 4 code_norms), rows, lists_touched / empty_lists / max_list_rows (update), loader_bytes
+        (residuals: 16, 4 or 1), group_ms / kernel_ms (with profile=True)"""
+        return self._info("lsq_partition_get_info", _lib.PartitionInfo)
 
 
 # -- host-only pieces of the path (no GPU needed) ---------------------------------------------

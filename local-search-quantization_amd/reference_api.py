@@ -343,6 +343,54 @@ def ivf_residual_norms(codes, K, centroids, assign):
     return ((recon * recon).sum(1) + 2.0 * (c * recon).sum(1)).astype(np.float32)
 
 
+def train_coarse_dev(dX, nlist, niter=10, seed=0, *, engine):
+    """train_coarse with everything resident in HBM: dX (n, d) float32 or uint8 device tensor (8-bit rows are never widened).  The same start rows
+    (numpy's default_rng(seed).choice, gathered on the device), then Partition.assign and Partition.update alternated.
+    -> (Partition, dassign (n,) int32 tensor); its centroids and assignment are bit-identical to train_coarse(X, nlist, niter, seed, engine)."""
+    import torch
+    n = int(dX.shape[0])
+    if not 1 <= nlist <= n:
+        raise ValueError("train_coarse_dev: needs 1 <= nlist <= n (got nlist=%d n=%d)" % (nlist, n))
+    rows = torch.from_numpy(np.sort(np.random.default_rng(seed).choice(n, nlist, replace=False)).astype(np.int64)).to(dX.device)
+    part = engine.partition_dev(dX[rows].to(torch.float32).contiguous())      # (uint8 -> float32 is exact)
+    dassign = part.assign(dX)
+    for _ in range(niter):
+        part.update(dX, dassign)
+        dassign = part.assign(dX)
+    return part, dassign
+
+
+def build_ivf_residual_index(dX, partition, dK, m, *, engine, ilsiters, icmiter, npert, randord, seed=0, dB0=None, cbnorms=None, base=None, report=None):
+    """A residual inverted-list index built on the device: assign -> residuals -> encode_icm_dev on the residuals -> code_norms -> index_dev (cbnorms=None:
+    float norms) or index_packed_dev (cbnorms (<= 256,): norm bytes) -> set_lists.  dX (n, d) float32 or uint8 device tensor, never widened: its
+    residuals are the only float32 copy and are dropped after the encode.  partition: a device Partition (train_coarse_dev); dK (m*256, d): codebooks
+    trained on residuals (train_lsq_dev on a training set's residuals); ilsiters: the ILS iterations (an int, or a list whose last entry counts); dB0:
+    the start codes (default randinit_dev(seed)); base: the rows a shortlist is re-ranked on, or None; report: a dict that receives what the build made on
+    the way (assign, codes: device tensors; obj: the mean squared error |x - c_l - r^|^2 the encode reports), or None.
+    ONE FRAME: the rotation stays with the caller.  Codebooks in a rotated frame mean a partition trained on R'X; queries then go in as
+    Q_scan = Q_coarse = R'q with add_coarse=True, Q_exact in the base's own frame.  -> the Index, lists set."""
+    import torch
+    dassign = partition.assign(dX)
+    dR = partition.residuals(dX, dassign)
+    n = int(dX.shape[0])
+    if dB0 is None:
+        dB0 = engine.randinit_dev(seed, n, m, device=dX.device)
+    ils = [int(ilsiters)] if np.isscalar(ilsiters) else list(ilsiters)
+    dBs, sums, _ = engine.encode_icm_dev(dR, dB0, dK, m, ils, icmiter, npert, randord, seed=seed)
+    del dR
+    dcodes = dBs[-1]
+    if report is not None:
+        report.update(assign=dassign, codes=dcodes, obj=float(sums[-1]) / max(n, 1))
+    if cbnorms is None:
+        ix = engine.index_dev(dcodes, dK, partition.code_norms(dcodes, dK, dassign), m, base=base)
+    else:
+        dcb = torch.as_tensor(np.asarray(cbnorms, dtype=np.float32) if not hasattr(cbnorms, "is_cuda") else cbnorms).to(dX.device).contiguous()
+        _, dnc, _ = partition.code_norms(dcodes, dK, dassign, dcb)
+        ix = engine.index_packed_dev(dcodes, dK, dnc, dcb, m, base=base)
+    ix.set_lists(partition.centroids(), dassign)
+    return ix
+
+
 def eval_recall(ids_gnd, ids_predicted, k, V=False):
     """recall@N curve (src/linscan/Linscan.jl:76-117): ids_gnd (nq,), ids_predicted (k, nq), same id base.
     -> recall_at_i (k,) with recall_at_i[i-1] = fraction of queries whose true neighbour ranks <= i."""

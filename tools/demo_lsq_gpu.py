@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE [--residual]] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -20,6 +20,11 @@ re-ranked lists printed next to the ADC one.  The reference has no such stage: i
 
 --ivf NLIST:NPROBE: after the ADC scan, inverted lists over the same codes (train_coarse on the base rows, Index.set_lists) and the search that reads
 each query's NPROBE nearest lists alone (Index.search_ivf); its recall curve is printed next to the exhaustive one.  The reference has no such search.
+
+--residual (with --ivf): the form of IVF that encodes what the coarse quantiser leaves, built resident on the device at the same m and NPROBE: the same
+centroids, codebooks from the three resident trainers run on the training set's residuals (Partition.assign / residuals), the base set -- f32, or un-widened
+bytes with --bvecs -- through build_ivf_residual_index, searched with add_coarse; with --norm-byte the norm codebook is the scalar k-means of the training
+residuals' code_norms and the index is packed.  Its recall curve is printed as a third column.
 
 --norm-byte: the norm byte that quantize_norms computes stays a byte up to the search: a packed index (Engine.index_packed, rows of m code bytes and one
 norm byte: the 64-bit code at m = 7) is searched through linscan_lsq_bytes, and its ids and distances are checked to equal the float-norm run's.  The
@@ -106,22 +111,54 @@ def load(nt, nb, nq, want_gt=True, synthetic=False):
     return "synthetic", xt, xb, xq, ground_truth(xb, xq) if want_gt else None
 
 
+def train_resident_dev(eng, dX, m, h, niter, ilsiter, icmiter, randord, npert, what=""):
+    """the three training stages on one device tensor -> train_lsq_dev's result"""
+    dK, dB, R, err = lsq.train_opq_dev(dX, m, h, niter, "natural", engine=eng)
+    print("Error after OPQ%s is %e" % (what, err[-1]))
+    dK, dB, R, err = lsq.train_chainq_dev(dX, m, h, R, dB, niter, engine=eng)
+    print("Error after ChainQ%s is %e" % (what, err[-1]))
+    return lsq.train_lsq_dev(dX, m, h, dB, niter, ilsiter, icmiter, randord, npert, engine=eng, R=R)
+
+
 def train_resident(x_train, m, h, niter, ilsiter, icmiter, randord, npert):
-    """the three training stages on one device tensor -> what train_lsq returns, in its host shapes"""
+    """... uploaded once -> what train_lsq returns, in its host shapes"""
     import torch
     t0 = time.perf_counter()
     with lsq.Engine(0) as eng:
         dX = torch.from_numpy(np.ascontiguousarray(x_train.T)).cuda()
-        dK, dB, R, err = lsq.train_opq_dev(dX, m, h, niter, "natural", engine=eng)
-        print("Error after OPQ is %e" % err[-1])
-        dK, dB, R, err = lsq.train_chainq_dev(dX, m, h, R, dB, niter, engine=eng)
-        print("Error after ChainQ is %e" % err[-1])
-        dK, dB, cbnorms, B_norms, obj = lsq.train_lsq_dev(dX, m, h, dB, niter, ilsiter, icmiter, randord, npert, engine=eng, R=R)
+        dK, dB, cbnorms, B_norms, obj = train_resident_dev(eng, dX, m, h, niter, ilsiter, icmiter, randord, npert)
         torch.cuda.synchronize()
         K = dK.cpu().numpy()
         B = np.ascontiguousarray(dB.cpu().numpy().T.astype(np.int16) + 1)
     print("Error after LSQ is %e; the three resident trainers took %.3f s" % (obj[-1], time.perf_counter() - t0))
     return [np.ascontiguousarray(K[i * h:(i + 1) * h].T) for i in range(m)], B, cbnorms, B_norms, obj
+
+
+def residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, npert, nprobe, knn, norm_byte):
+    """the residual index over the SAME centroids and lists, resident on the device -> (recall curve, seconds of the build, error in base)"""
+    import torch
+    dXt = torch.from_numpy(np.ascontiguousarray(x_train.T)).cuda()
+    dXb = torch.from_numpy(np.ascontiguousarray(x_base.T)).cuda()            # f32, or the un-widened bytes of --bvecs
+    with eng.partition_dev(torch.from_numpy(cent).cuda()) as part:
+        # codebooks for residuals: the three resident trainers, as for the rows themselves, on the training set's residuals
+        ta = part.assign(dXt)
+        dK, dBt, _, _, obj = train_resident_dev(eng, part.residuals(dXt, ta), m, h, niter, ilsiter, icmiter, randord, npert, " of the residuals")
+        print("Error after LSQ of the residuals is %e" % obj[-1])
+        cb = None
+        if norm_byte:                                                       # the norm codebook: the host scalar k-means of train_lsq_dev, fed with code_norms
+            nrm = part.code_norms(dBt, dK, ta).cpu().numpy()
+            cb = lsq.initializers.kmeans(nrm.reshape(1, -1), min(h, nrm.shape[0]), niter=100, seed=0)[0].reshape(-1).astype(np.float32)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rep = {}
+        ix = lsq.build_ivf_residual_index(dXb, part, dK, m, engine=eng, ilsiters=[16], icmiter=icmiter, npert=npert, randord=randord, cbnorms=cb, report=rep)
+        torch.cuda.synchronize()
+        t_build = time.perf_counter() - t0
+        assert np.array_equal(rep["assign"].cpu().numpy(), assign), "the device assignment differs from ivf_assign's"
+        with ix:
+            _, ridx = ix.search_ivf(torch.from_numpy(Q).cuda(), knn, nprobe, add_coarse=True)
+            ridx = ridx.cpu().numpy()
+    return lsq.eval_recall(gt, np.ascontiguousarray(ridx.T).astype(np.uint32), knn), t_build, rep["obj"]
 
 
 def main():
@@ -147,8 +184,10 @@ def main():
         except (ValueError, AssertionError, IndexError):
             raise SystemExit("--ivf takes NLIST:NPROBE with 1 <= NPROBE <= NLIST")
         del argv[at:at + 2]
-    args = [a for a in argv if a not in ("--resident", "--bvecs", "--norm-byte")]
-    resident, bvecs, norm_byte = "--resident" in argv, "--bvecs" in argv, "--norm-byte" in argv
+    args = [a for a in argv if a not in ("--resident", "--bvecs", "--norm-byte", "--residual")]
+    resident, bvecs, norm_byte, residual = "--resident" in argv, "--bvecs" in argv, "--norm-byte" in argv, "--residual" in argv
+    if residual and not ivf:
+        raise SystemExit("--residual needs --ivf NLIST:NPROBE")
     real = bool(os.environ.get("LSQ_DATA_DIR"))
     nt = int(args[0]) if len(args) > 0 else (10_000 if real else 3000)
     nb = int(args[1]) if len(args) > 1 else (1_000_000 if real else 6000)
@@ -231,13 +270,19 @@ def main():
                 _, iidx = ix.search_ivf(Q, knn, nprobe)
                 t_ivf = time.perf_counter() - t0
                 info = ix.ivf_info()
+            if residual:
+                rrec_ivf, t_res, mse = residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, min(npert, m), nprobe,
+                                                    knn, norm_byte)
         irec = lsq.eval_recall(gt, np.ascontiguousarray(iidx.T).astype(np.uint32), knn)
         print("IVF search (nlist %d, nprobe %d): %.3f s on the resident index; %.0f of %d rows probed per query, %d of %d queries on the thresholded road"
               % (nlist, nprobe, t_ivf, info["probed_rows"] / Q.shape[0], x_base.shape[1], info["threshold_queries"], Q.shape[0]))
-        print("     r@   exhaustive   IVF")
+        if residual:
+            print("Residual IVF index (%s rows, %s norms) built on the device in %.3f s; error in base is %e (plain codes: %e)"
+                  % (x_base.dtype, "byte" if norm_byte else "float", t_res, mse, objs[-1]))
+        print("     r@   exhaustive   IVF" + ("          residual IVF" if residual else ""))
         for i in (1, 2, 5, 10, 20, 50, 100, 200, 500, 1000):
             if i <= knn:
-                print("%7d   %.4f       %.4f" % (i, rec[i - 1], irec[i - 1]))
+                print("%7d   %.4f       %.4f" % (i, rec[i - 1], irec[i - 1]) + ("       %.4f" % rrec_ivf[i - 1] if residual else ""))
 
 
 if __name__ == "__main__":
