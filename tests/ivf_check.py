@@ -238,6 +238,79 @@ def layout_problem(n, nlist):
     return (codes, K, dbn, cent, lor, Qs, Qc), nprobe, nn
 
 
+# ---- many lists: nlist from 65 536 up, where the coarse search leaves the exhaustive road (tests/select_model.py, plan) and nlist >> n -----------------
+MANY = 65537                                                                 # ADC_SMALL_N + 1: the first nlist whose coarse search samples and bets
+
+
+def padding_ok(ids):
+    """the condition of every many-lists case, on the CHECKER's ids: at most a quarter of the result slots are padding (id 0) and no query is all
+    padding -- a case cannot pass by comparing infinities"""
+    ids = np.asarray(ids)
+    return bool((ids == 0).sum() * 4 <= ids.size and np.all((ids != 0).any(axis=1)))
+
+
+def many_lists_problem():
+    """262 148 rows on 65 537 random lists (about 4 each), 64 probed: heads of 10 .. 15 rows, tails of about 240, none overflowing"""
+    return problem(262148, 8, 8, MANY, 37, seed=5, lists="random"), 64, 10
+
+
+def near_lists(cent, Qc, n, nprobe, scatter=5, seed=0):
+    """list_of_row for nlist >> n: row i lies in the ((i // nq) % nprobe)-th nearest list of query i % nq by the host exact search (lsq_knn_exact_cpu),
+    so that the probed lists hold rows at all; every scatter-th row goes to a random list instead, one row is forced into list 0 and one into the last"""
+    import importlib
+    lsq = importlib.import_module("local-search-quantization_amd")
+    nlist, nq = cent.shape[0], Qc.shape[0]
+    ids = lsq.knn_exact(np.ascontiguousarray(cent.T), np.ascontiguousarray(Qc.T), nprobe)[1].T.astype(np.int64) - 1      # (nq, nprobe), 0-based
+    i = np.arange(n)
+    lor = ids[i % nq, (i // nq) % nprobe].astype(np.int32)
+    lor[::scatter] = np.random.default_rng(seed).integers(0, nlist, lor[::scatter].shape[0])
+    lor[1], lor[2] = 0, nlist - 1
+    return lor
+
+
+def coarse_stats(cent, Qc, nprobe, **plan_args):
+    """what the coarse step of a search -- the exact search of Qc on the centroids for nprobe neighbours -- must decide, by the model of the selection
+    (select_model.predict): exhaustive, threshold_rank, list_capacity, fallback_queries, candidates, batches"""
+    import select_model as SM
+    return SM.predict(knn_dists(cent, Qc), nprobe, **plan_args)["stats"]
+
+
+def list_edge_problem(nlist, n=2048):
+    """layout_problem's pattern at the values where the grouping sort's list bits change (8 -> 9 at 257, 16 -> 17 at 65 537): lists 0, 1, 2 and the last
+    three empty, the last row (id n, a power of two) the nearest of query 0.  From 65 536 on the rows are placed by near_lists and the ends cleared"""
+    if nlist <= 1024:
+        return layout_problem(n, nlist)
+    codes, K, dbn, cent, lor, Qs, Qc = problem(n, 32, 8, nlist, 37, 96 + nlist, lists="random")
+    nprobe, nn = 12, 10
+    lor = np.clip(near_lists(cent, Qc, n, nprobe), 3, nlist - 4).astype(np.int32)
+    best = int(ivf_np(codes, K, dbn, cent, lor, Qs[:1], Qc[:1], nprobe, 1)[1][0, 0]) - 1
+    codes[n - 1], lor[n - 1], dbn[n - 1] = codes[best], lor[best], dbn[best] - np.float32(1)
+    return (codes, K, dbn, cent, lor, Qs, Qc), nprobe, nn
+
+
+def many_probes_problem():
+    """nprobe = 1024 of 65 537 lists, nn = 100, 5 queries: the coarse plan is r = 352, cap = 3200 (select_model.plan(65537, 1024))"""
+    codes, K, dbn, cent, lor, Qs, Qc = problem(8192, 8, 8, MANY, 5, seed=13, lists="random")
+    return (codes, K, dbn, cent, near_lists(cent, Qc, 8192, 1024), Qs, Qc), 1024, 100
+
+
+def duplicated_centroids_problem():
+    """40 000 centroids equal to 0.5 * Qc[0]: they tie at query 0's coarse threshold, its candidate list overflows and the coarse search redoes that
+    query alone (a mixed coarse batch); the ties go to the smaller list id"""
+    codes, K, dbn, cent, lor, Qs, Qc = problem(20000, 8, 8, MANY, 37, seed=12, lists="random")
+    cent[5000:45000] = np.float32(0.5) * Qc[0]
+    return (codes, K, dbn, cent, lor, Qs, Qc), 32, 10
+
+
+BOUND = 1 << 24                                                              # the contract's largest nlist
+
+
+def bound_problem(nlist=BOUND):
+    """nlist >> n: 4096 rows on 2^24 lists, d = 2, placed by near_lists"""
+    codes, K, dbn, cent, lor, Qs, Qc = problem(4096, 2, 8, nlist, 8, seed=11, lists="random")
+    return (codes, K, dbn, cent, near_lists(cent, Qc, 4096, 16), Qs, Qc), 16, 10
+
+
 PROBLEMS = {"stride-m8": lambda: stride_problem("m8"), "stride-m12": lambda: stride_problem("m12"), "capacity-33": lambda: capacity_problem(33),
             "capacity-34": lambda: capacity_problem(34), "mixed": mixed_problem, "nan-tau": nan_tau_problem, "short-list": short_list_problem,
             "layout-n2047-nlist64": lambda: layout_problem(2047, 64), "layout-n2048-nlist64": lambda: layout_problem(2048, 64),

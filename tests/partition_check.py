@@ -186,6 +186,35 @@ def ladder_lists(nlist_extra=3):
     return lists, int(lists.max()) + 2                                                             # and the last one
 
 
+TIE = (70, 60000)      # assign_problem: two centroids with the same bits
+
+
+def assign_problem(nlist, u8=False, n=2000, d=8, seed=0):
+    """-> (centroids (nlist, d) f32, X (n, d) f32 or uint8), values * 40 + 128 (uint8: both clipped to 0 .. 254 and floored).  Centroids TIE[0] and TIE[1]
+    are equal and row n // 2 lies one step beside them in every dimension: an exact tie, the smaller list wins.  Row 7 equals centroid 123: distance +0.0"""
+    rng = np.random.default_rng(seed + nlist)
+    cent = (rng.standard_normal((nlist, d)) * 40 + 128).astype(np.float32)
+    X = (rng.standard_normal((n, d)) * 40 + 128).astype(np.float32)
+    if u8:
+        cent, X = np.floor(np.clip(cent, 0, 254)), np.floor(np.clip(X, 0, 254))
+    cent[TIE[1]] = cent[TIE[0]]
+    X[n // 2] = cent[TIE[0]] + np.float32(1)
+    X[7] = cent[123]
+    return cent, (X.astype(np.uint8) if u8 else X)
+
+
+def duplicated_centroids(n=300, d=8, nlist=65537, seed=12):
+    """-> (centroids, X): centroids 5000 .. 44 999 are one point v, the first 100 rows lie beside v (40 000 lists tie at the threshold of their coarse
+    search, the smallest wins), the other rows are anywhere"""
+    rng = np.random.default_rng(seed)
+    cent = rng.standard_normal((nlist, d)).astype(np.float32)
+    X = rng.standard_normal((n, d)).astype(np.float32)
+    v = np.float32(0.5) * X[0]
+    cent[5000:45000] = v
+    X[:100] = v + np.float32(0.01) * rng.standard_normal((100, d)).astype(np.float32)
+    return cent, X
+
+
 def code_problem(n, d, m, nlist, seed, scale=1.0):
     rng = np.random.default_rng(seed)
     K = (rng.standard_normal((m * H, d)) * scale).astype(np.float32)

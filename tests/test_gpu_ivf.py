@@ -2,10 +2,12 @@
 host and device forms, the padding, ties and NaN, batches, the two identities of the contract, stage two behind it, and the state of a shared context.
 The named problems of tests/ivf_check.py reach the routes a shape selects -- a block that walks several lists, every loader width, a tail filled to the
 record and eight over, some queries redone over several fall-back batches, a NaN tau, infinities beside the padding, the layout's edges -- and hold
-lsq_ivf_info's road counts to what the numpy checker predicts (tail_hits_np, roads_np)."""
+lsq_ivf_info's road counts to what the numpy checker predicts (tail_hits_np, roads_np).  The last section runs 256 .. 2^24 lists: the list-bit edges of the
+grouping sort, the coarse search on its sampled road and under the context's two search options, nlist >> n."""
 import ctypes as C
 import os
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -376,3 +378,170 @@ def test_every_refusal_launches_nothing(lsq, engine):
         assert search(fix._h, shortlist=10) == EINVAL                         # a shortlist without q_exact
         assert search(fix._h, shortlist=10, q_exact=Xq.ctypes.data) == 0
         assert L.lsq_index_get_ivf_info(ix._h, None) == EINVAL
+
+
+# ---- many lists: nlist from 2^16 to the contract's 2^24 (the problems of ivf_check, which tests/test_ivf.py holds to the numpy statement) ----------------
+def _set_lists(ix, cent, lor):
+    if ix._dev:
+        import torch
+        cent, lor = torch.from_numpy(cent).cuda(), torch.from_numpy(lor).cuda()
+    ix.set_lists(cent, lor)
+
+
+def _many(lsq, ixs, p, nprobe, nn, what, roads=None):
+    """_both_roads behind the padding condition: the checker's own result holds rows, so that no case passes by comparing infinities"""
+    for add in (0, ic.ADD_COARSE):
+        rc, _, ri = ic.ivf_cpu(lsq._lib.load(), *p, nprobe, nn, flags=add)
+        assert rc == 0 and ic.padding_ok(ri), (what, add)
+    _both_roads(lsq, ixs, p, nprobe, nn, what, roads=roads)
+
+
+def _coarse_search(engine, cent, Qc, nprobe):
+    """the coarse step on its own -- engine.knn_exact_dev(centroids, Q_coarse, nprobe) -- -> its scan statistics, fallback_queries this call's alone"""
+    import torch
+    before = engine.linscan_stats()["fallback_queries"]
+    engine.knn_exact_dev(torch.from_numpy(cent).cuda(), torch.from_numpy(Qc).cuda(), nprobe)
+    st = engine.linscan_stats()
+    st["fallback_queries"] -= before
+    return st
+
+
+@pytest.mark.parametrize("nlist", [256, 257, 65536, 65537])
+def test_list_bit_edges_of_the_grouping_sort(lsq, engine, nlist):
+    """reaches: lsq_rows_sort on 40, 41, 48 and 49 key bits (8, 9, 16, 17 list bits); from 65 536 on one thread of ivf_offsets_kernel opens runs of
+    thousands of empty lists; at 65 537 the coarse step of search_ivf leaves the exhaustive road.  Evidence: ivf_info against roads_np, the direct
+    search's `exhaustive`"""
+    p, nprobe, nn = ic.list_edge_problem(nlist)
+    counts = np.bincount(p[4], minlength=nlist)
+    assert not counts[:3].any() and not counts[-3:].any() and (nlist < 65536 or (counts == 0).sum() > 64000)
+    hix, dix = _indexes(engine, p)
+    with hix, dix:
+        assert hix.nlist == dix.nlist == nlist
+        _many(lsq, (hix, dix), p, nprobe, nn, nlist, roads=_roads(p, nprobe, nn))
+        assert _coarse_search(engine, p[3], p[6], nprobe)["exhaustive"] == (1 if nlist <= 65536 else 0)
+        if nlist == 65537:                                                   # set_lists again with another partition: the second one wins
+            cent2 = np.ascontiguousarray(p[3][np.random.default_rng(3).permutation(nlist)])
+            lor2 = ic.near_lists(cent2, p[6], p[0].shape[0], nprobe, seed=1)
+            assert not np.array_equal(lor2, p[4])
+            p2 = p[:3] + (cent2, lor2) + p[5:]
+            for ix in (hix, dix):
+                _set_lists(ix, cent2, lor2)
+            _many(lsq, (hix, dix), p2, nprobe, nn, "second partition", roads=_roads(p2, nprobe, nn))
+
+
+def test_many_lists_under_every_coarse_road(lsq, engine):
+    """reaches: the sampled coarse search (65 537 centroids, rank 45, lists of 640) as the coarse step of search_ivf, and c->search's two options handed to
+    it.  Evidence: ivf_info against roads_np (276, no fall-back, 7809 records); the direct exact search on the same arrays under the same options"""
+    p, nprobe, nn = ic.many_lists_problem()
+    nq = p[5].shape[0]
+    roads = _roads(p, nprobe, nn)
+    assert roads[False][1] == (276, [], 7809)
+    want = {add: ic.ivf_cpu(lsq._lib.load(), *p, nprobe, nn, flags=ic.ADD_COARSE if add else 0) for add in (False, True)}
+    model = ic.coarse_stats(p[3], p[6], nprobe)
+    hix, dix = _indexes(engine, p)
+    with hix, dix:
+        for ix in (hix, dix):                                                # (set again: the same lists, for the printed times)
+            t0 = time.perf_counter()
+            _set_lists(ix, p[3], p[4])
+            t1 = time.perf_counter()
+            _search(ix, p[5], p[6], nn, nprobe)
+            print("nlist = 65537, n = 262148, %s form: set_lists (copies included) %.4f s, search_ivf of %d queries with nprobe = %d %.4f s"
+                  % ("device" if ix._dev else "host", t1 - t0, nq, nprobe, time.perf_counter() - t1))
+        _many(lsq, (hix, dix), p, nprobe, nn, "many-lists", roads=roads)
+        try:
+            for option in (None, "linscan_exhaustive", "linscan_rank"):
+                if option:
+                    engine.set_option(option, 1)
+                for ix in (hix, dix):
+                    for add in (False, True):
+                        dd, di = _search(ix, p[5], p[6], nn, nprobe, add_coarse=add)
+                        assert same_bits(dd, want[add][1]) and np.array_equal(di, want[add][2]), (option, ix._dev, add)
+                st = _coarse_search(engine, p[3], p[6], nprobe)
+                print("coarse search of %d queries on 65537 centroids for %d, option %s: %s" % (nq, nprobe, option, {k: st[k] for k in
+                      ("exhaustive", "threshold_rank", "list_capacity", "fallback_queries", "candidates")}))
+                if option is None:                                           # the model's plan (select_model.plan(65537, 64)) and its count of redone queries
+                    assert (st["exhaustive"], st["threshold_rank"], st["list_capacity"]) == (0, 45, 640)
+                    assert st["fallback_queries"] == model["fallback_queries"] < nq
+                elif option == "linscan_exhaustive":
+                    assert st["exhaustive"] == 1 and st["fallback_queries"] == 0
+                else:
+                    assert st["exhaustive"] == 0 and st["threshold_rank"] == 1 and st["fallback_queries"] == nq
+                if option:
+                    engine.set_option(option, 0)
+        finally:
+            engine.set_option("linscan_rank", 0)
+            engine.set_option("linscan_exhaustive", 0)
+
+
+@pytest.mark.parametrize("m", [7, 8], ids=["m7-dword-rows", "m8-byte-rows"])
+def test_many_lists_on_a_packed_index(lsq, engine, m):
+    """reaches: the packed scan (8-byte rows on the dword loader, 9-byte rows on the byte loader) behind the sampled coarse search, lists of about four
+    rows.  Evidence: packed_info's row geometry, ivf_info's thresholded queries"""
+    import packed_check as pk
+    codes, K, dbn, cent, lor, Qs, Qc = ic.problem(262148, 8, m, ic.MANY, 37, seed=5, lists="random")
+    cb, nc = pk.quantize(dbn)
+    p, nprobe, nn = (codes, K, cb[nc], cent, lor, Qs, Qc), 64, 10
+    with engine.index_packed(codes, K, nc, cb, m) as packed:
+        packed.set_lists(cent, lor)
+        info = packed.packed_info()
+        assert (info["row_bytes"], info["ivf_row_bytes"], info["dword_rows"]) == (m + 1, m + 5, 1 if m == 7 else 0) and packed.nlist == ic.MANY
+        _many(lsq, (packed,), p, nprobe, nn, ("packed", m))
+        packed.search_ivf(Qs, nn, nprobe, Q_coarse=Qc)
+        info = packed.ivf_info()
+        assert info["threshold_queries"] + info["fallback_queries"] == 37 and info["tail_capacity"] > 0
+
+
+def test_many_probes(lsq, engine):
+    """reaches: nprobe = 1024 of 65 537 lists -- the coarse search's plan r = 352, cap = 3200, ivf_plan_kernel's prefix of 1025 positions with long runs
+    of equal ones (most probed lists are empty), 2048 / 5 scan blocks per query.  Evidence: ivf_info against roads_np, the direct search's plan"""
+    p, nprobe, nn = ic.many_probes_problem()
+    roads = _roads(p, nprobe, nn)
+    hix, dix = _indexes(engine, p)
+    with hix, dix:
+        _many(lsq, (hix, dix), p, nprobe, nn, "many-probes", roads=roads)
+    st = _coarse_search(engine, p[3], p[6], nprobe)
+    assert (st["exhaustive"], st["threshold_rank"], st["list_capacity"]) == (0, 352, 3200)
+    assert st["fallback_queries"] == ic.coarse_stats(p[3], p[6], nprobe)["fallback_queries"]
+
+
+def test_duplicated_centroids_make_a_mixed_coarse_batch(lsq, engine):
+    """reaches: a coarse search in which some queries are served by their candidate lists and query 0 -- 40 000 centroids tie at its threshold -- is
+    redone, inside search_ivf; the ties go to the smaller list id.  Evidence: the direct search's 1 <= fallback_queries < nq"""
+    p, nprobe, nn = ic.duplicated_centroids_problem()
+    nq = p[5].shape[0]
+    hix, dix = _indexes(engine, p)
+    with hix, dix:
+        _many(lsq, (hix, dix), p, nprobe, nn, "duplicated-centroids", roads=_roads(p, nprobe, nn))
+    st = _coarse_search(engine, p[3], p[6], nprobe)
+    assert 1 <= st["fallback_queries"] < nq and st["fallback_queries"] == ic.coarse_stats(p[3], p[6], nprobe)["fallback_queries"], st
+
+
+def test_the_contracts_bound_on_nlist(lsq, engine):
+    """reaches: nlist = 2^24 (24 list bits: 56 key bits, the contract's most), offsets of 2^24 + 1 entries opened by 4097 threads, a coarse search over
+    2^24 centroids with stride 1024, centroid rows at l * d up to 2^25.  Evidence: Index.nlist, probed_rows of ivf_info against the checker's lists"""
+    import torch
+    p, nprobe, nn = ic.bound_problem()
+    codes, K, dbn, cent, lor, Qs, Qc = p
+    nlist = cent.shape[0]
+    assert nlist == ic.BOUND
+    counts = np.bincount(lor, minlength=nlist)
+    hix = engine.index(codes, K, dbn, 8)
+    dix = engine.index_dev(*[torch.from_numpy(a).cuda() for a in (codes, K, dbn)], 8)
+    dcent, dlor = torch.from_numpy(cent).cuda(), torch.from_numpy(lor).cuda()
+    with hix, dix:
+        for ix, args in ((hix, (cent, lor)), (dix, (dcent, dlor))):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ix.set_lists(*args)
+            torch.cuda.synchronize()
+            print("set_lists at nlist = %d, n = %d, %s form: %.3f s" % (nlist, codes.shape[0], "device" if ix._dev else "host", time.perf_counter() - t0))
+        assert hix.nlist == dix.nlist == nlist
+        for k in (nprobe, 1):
+            t0 = time.perf_counter()
+            _many(lsq, (hix, dix), p, k, nn, ("bound", k))
+            print("nprobe = %d: checker twice and 8 searches in %.3f s" % (k, time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            got = hix.search_ivf(Qs, nn, k, Q_coarse=Qc)
+            print("search_ivf at nlist = %d, nprobe = %d, host form: %.3f s" % (nlist, k, time.perf_counter() - t0))
+            probes = lsq.knn_exact(np.ascontiguousarray(cent.T), np.ascontiguousarray(Qc.T), k)[1].T.astype(np.int64) - 1
+            assert hix.ivf_info()["probed_rows"] == int(counts[probes].sum()) and np.all(got[1] > 0)

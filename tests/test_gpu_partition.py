@@ -1,14 +1,17 @@
 """The coarse partition on the device: every call of lsq_partition_* held bit for bit to its host checker (which tests/test_partition.py holds to the numpy
 statement of the contract), host and device forms, at the smallest shapes at which each kernel can go wrong; then the two functions built on them,
-train_coarse_dev and build_ivf_residual_index, against the host statement of the same build."""
+train_coarse_dev and build_ivf_residual_index, against the host statement of the same build; and all of it again at 65 536 .. 2^24 lists."""
+import contextlib
 import ctypes as C
 import os
 import sys
+import time
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ivf_check as ic  # noqa: E402
 import partition_check as pc  # noqa: E402
 from knn_check import same_bits  # noqa: E402
 
@@ -403,3 +406,269 @@ def test_partition_calls_leave_the_context_and_its_indexes_alone(lsq, engine, to
     for got in (before, after):
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2])
         assert same_bits(got[3], want[3]) and np.array_equal(got[4], want[4])
+
+
+# ---- many lists: 2^16 .. 2^24 centroids ---------------------------------------------------------------------------------------------------------------
+MANY, BOUND = ic.MANY, ic.BOUND
+
+
+def _nearest_search(engine, torch, cent, X):
+    """the search an assignment borrows, on its own: engine.knn_exact_dev(centroids, rows, 1) -> its statistics, fallback_queries this call's alone"""
+    before = engine.linscan_stats()["fallback_queries"]
+    engine.knn_exact_dev(torch.from_numpy(cent).cuda(), torch.from_numpy(np.ascontiguousarray(X)).cuda(), 1)
+    st = engine.linscan_stats()
+    st["fallback_queries"] -= before
+    return st
+
+
+OPTIONS = (None, "linscan_exhaustive", "linscan_rank")      # the context's coarse roads: default, every query exhaustive, every query redone (rank 1)
+
+
+@contextlib.contextmanager
+def _option(engine, option):
+    """the shared context under one search option, reset whatever happens"""
+    if option:
+        engine.set_option(option, 1)
+    try:
+        yield
+    finally:
+        engine.set_option("linscan_rank", 0)
+        engine.set_option("linscan_exhaustive", 0)
+
+
+@pytest.mark.parametrize("u8", [False, True], ids=["f32", "u8"])
+@pytest.mark.parametrize("nlist", [65536, 65537])
+def test_assign_on_either_side_of_the_sampled_search(lsq, engine, torch, nlist, u8):
+    """reaches: Partition.assign through the exhaustive road (65 536 centroids) and the sampled one (65 537), and the context's two search options handed
+    to it.  Evidence: the direct nearest-centroid search's statistics under the same options"""
+    cent, X = pc.assign_problem(nlist, u8)
+    n = X.shape[0]
+    want = lsq.ivf_assign(X, cent)                                                    # the host cores
+    ref, acc = pc.assign_np(X[:200], cent)
+    wdist = acc[np.arange(200), ref]
+    assert np.array_equal(want[:200], ref) and want[n // 2] == pc.TIE[0] and want[7] == 123
+    views = (X, pc.row_view(X, 1, offset=3) if u8 else pc.row_view(X, 3, offset=1))
+    with engine.partition_dev(torch.from_numpy(cent).cuda()) as part, engine.partition(cent) as hpart:
+        for option in OPTIONS:
+            with _option(engine, option):
+                for v in views:
+                    got, dist = part.assign(to_dev(torch, v)[0], want_dist=True)
+                    assert np.array_equal(got.cpu().numpy(), want) and same_bits(dist.cpu().numpy()[:200], wdist), (option, v.strides)
+                    hgot, hdist = hpart.assign(v, want_dist=True)
+                    assert np.array_equal(hgot, want) and same_bits(hdist[:200], wdist), (option, v.strides)
+                assert part.info()["call"] == lsq._lib.PARTITION_ASSIGN and part.info()["rows"] == n
+                st = _nearest_search(engine, torch, cent, X.astype(np.float32))
+            assert st["exhaustive"] == (1 if option == "linscan_exhaustive" or nlist <= 65536 else 0), (option, st)
+            if nlist > 65536 and option is None:
+                assert st["threshold_rank"] == 10 and st["list_capacity"] == 320 and st["fallback_queries"] < n      # select_model.plan(65537, 1)
+            if nlist > 65536 and option == "linscan_rank":                            # (one neighbour: the sample's minimum serves its query)
+                assert st["threshold_rank"] == 1
+
+
+def test_assign_with_duplicated_centroids(lsq, engine, torch):
+    """reaches: an assignment whose coarse batch is mixed -- the rows beside 40 000 equal centroids overflow their candidate lists and are redone, the
+    others are served.  Evidence: the direct search's 1 <= fallback_queries < n"""
+    cent, X = pc.duplicated_centroids()
+    want = lsq.ivf_assign(X, cent)
+    ref, acc = pc.assign_np(X, cent)
+    assert np.array_equal(want, ref) and np.all(want[:100] == 5000)
+    with engine.partition_dev(torch.from_numpy(cent).cuda()) as part, engine.partition(cent) as hpart:
+        got, dist = part.assign(torch.from_numpy(X).cuda(), want_dist=True)
+        assert np.array_equal(got.cpu().numpy(), want) and same_bits(dist.cpu().numpy(), acc[np.arange(X.shape[0]), ref])
+        assert np.array_equal(hpart.assign(X), want)
+    st = _nearest_search(engine, torch, cent, X)
+    assert st["exhaustive"] == 0 and 1 <= st["fallback_queries"] < X.shape[0], st
+    assert st["fallback_queries"] == ic.coarse_stats(cent, X, 1)["fallback_queries"]
+
+
+def test_update_at_65537_lists(lsq, engine, torch):
+    """reaches: update_kernel on 65 537 blocks, about 1200 of which find their list empty; the grouping sort on 49 key bits behind an update.
+    Evidence: partition info's empty_lists, lists_touched and max_list_rows, exact (_update_both)"""
+    X = pc.decades(262148, 5, 6)
+    assign = lists_for(262148, MANY, 5)
+    cent = np.random.default_rng(2).standard_normal((MANY, 5)).astype(np.float32)
+    got, counts = _update_both(lsq, engine, torch, cent, X, assign)
+    want, wc = pc.update_np(cent, X, assign)
+    assert same_bits(got, want) and np.array_equal(counts, wc) and 500 < int((wc == 0).sum()) < 2000
+    assert same_bits(got[wc == 0], cent[wc == 0])                                     # empty lists keep their centroid's bits
+    _timed_update(engine, torch, cent, X, assign)
+
+
+def _timed_update(engine, torch, cent, X, assign):
+    """one device-form update on resident tensors, its wall time printed -> the handle's info"""
+    with engine.partition_dev(torch.from_numpy(cent).cuda()) as part:
+        dX, dassign = torch.from_numpy(X).cuda(), torch.from_numpy(assign).cuda()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        part.update(dX, dassign)
+        torch.cuda.synchronize()
+        print("update at nlist = %d, n = %d, d = %d, device form: %.4f s" % (cent.shape[0], X.shape[0], X.shape[1], time.perf_counter() - t0))
+        return part.info()
+
+
+def test_update_at_the_contracts_bound(lsq, engine, torch):
+    """reaches: update_kernel on 2^24 blocks of which 950 have rows (2^24 - 950 atomic adds on one word), ivf_offsets_kernel's threads opening runs of
+    tens of thousands of empty lists, counts of 2^24 entries.  Evidence: partition info's empty_lists = 2^24 - 950, exact"""
+    (_, _, _, cent, assign, _, _), _, _ = ic.bound_problem()
+    X = pc.decades(assign.shape[0], 2, 8)
+    got, counts = _update_both(lsq, engine, torch, cent, X, assign)
+    want, wc = pc.update_np(cent, X, assign)
+    assert same_bits(got, want) and np.array_equal(counts, wc) and int((wc == 0).sum()) == BOUND - 950 and int(wc.max()) == 26
+    info = _timed_update(engine, torch, cent, X, assign)
+    assert (info["empty_lists"], info["lists_touched"], info["max_list_rows"]) == (BOUND - 950, 950, 26)
+
+
+def _residuals_and_code_norms(lsq, engine, torch, nlist, d, lists, n=257, m=3):
+    L = lsq._lib.load()
+    codes, K, cent, _ = pc.code_problem(n, d, m, nlist, d + nlist % 1000)
+    assign = np.resize(np.asarray(lists, dtype=np.int32), n)
+    X = np.random.default_rng(d).standard_normal((n, d)).astype(np.float32)
+    rc, wantR = pc.residuals_cpu(L, X, cent, assign)
+    rc2, ws, _, _ = pc.code_norms_cpu(L, codes, K, cent, assign)
+    assert rc == 0 and rc2 == 0 and not same_bits(wantR, X)
+    with engine.partition_dev(torch.from_numpy(cent).cuda()) as part, engine.partition(cent) as hpart:
+        dassign = torch.from_numpy(assign).cuda()
+        assert pc.same(part.residuals(torch.from_numpy(X).cuda(), dassign).cpu().numpy(), wantR) and pc.same(hpart.residuals(X, assign), wantR)
+        assert part.info()["call"] == lsq._lib.PARTITION_RESIDUALS and part.info()["rows"] == n
+        assert pc.same(part.code_norms(torch.from_numpy(codes).cuda(), torch.from_numpy(K).cuda(), dassign).cpu().numpy(), ws)
+        assert pc.same(hpart.code_norms(codes, K, assign), ws)
+        assert part.nlist == nlist and int(assign.max()) == nlist - 1
+
+
+@pytest.mark.parametrize("d", [5, 128])
+def test_residuals_and_code_norms_read_the_last_centroids_of_65537(lsq, engine, torch, d):
+    """reaches: residual_kernel / code_norms_kernel at centroid offsets l * d for l = 0, 65 535, 65 536 = nlist - 1 (the first l past 16 bits).
+    Evidence: the rows' lists and the handle's nlist"""
+    _residuals_and_code_norms(lsq, engine, torch, MANY, d, [0, 65535, 65536, MANY - 1])
+
+
+def test_residuals_and_code_norms_read_the_last_centroid_of_the_bound(lsq, engine, torch):
+    """reaches: the same kernels at l = 2^24 - 1, d = 2: the last centroid row the contract allows"""
+    _residuals_and_code_norms(lsq, engine, torch, BOUND, 2, [BOUND - 1, 0, BOUND - 1, 65536])
+
+
+def test_train_coarse_dev_is_train_coarse_at_65537_lists(lsq, engine, torch):
+    """reaches: assign and update alternated on 65 537 centroids (the sampled search with 70 000 queries, most lists of one row); the baseline runs the
+    context's exact search through host buffers, another caller of the same selection.  Evidence: bit-equal centroids, 500 rows held to the host cores"""
+    X = np.random.default_rng(21).standard_normal((70000, 4)).astype(np.float32)
+    cent, assign = lsq.train_coarse(X, MANY, 2, 3, engine)
+    part, dassign = lsq.train_coarse_dev(torch.from_numpy(X).cuda(), MANY, 2, 3, engine=engine)
+    with part:
+        assert part.nlist == MANY and same_bits(part.centroids().cpu().numpy(), cent) and np.array_equal(dassign.cpu().numpy(), assign)
+    rows = np.arange(0, 70000, 140)
+    assert np.array_equal(assign[rows], lsq.ivf_assign(X[rows], cent))                # the host cores
+    assert _nearest_search(engine, torch, cent, X[rows])["exhaustive"] == 0
+
+
+BN, BD, BM = 70000, 16, 4
+
+
+@pytest.fixture(scope="module")
+def big_build(lsq, engine, torch):
+    """`build` at 65 537 lists: the centroids are 65 537 rows of X (train_coarse without a Lloyd step: every list holds its own seed row, none is empty),
+    and the HOST statement of the build on them, made once"""
+    rng = np.random.default_rng(78)
+    X = rng.standard_normal((BN, BD)).astype(np.float32)
+    K = (rng.standard_normal((BM * H, BD)) / BM).astype(np.float32)
+    Q = (X[rng.integers(0, BN, 37)] + np.float32(0.05) * rng.standard_normal((37, BD))).astype(np.float32)
+    cent, assign = lsq.train_coarse(X, MANY, 0, 3, engine)
+    rows = np.arange(0, BN, 140)
+    assert np.array_equal(assign[rows], lsq.ivf_assign(X[rows], cent)) and np.bincount(assign, minlength=MANY).min() >= 1
+    R = X - cent[assign]
+    dK = torch.from_numpy(K).cuda()
+    dB0 = engine.randinit_dev(5, BN, BM)
+    dBs, _, _ = engine.encode_icm_dev(torch.from_numpy(R).cuda(), dB0, dK, BM, [ILS], 2, 2, True, seed=5)
+    codes = dBs[-1].cpu().numpy()
+    rc, norms, _, _ = pc.code_norms_cpu(lsq._lib.load(), codes, K, cent, assign)
+    assert rc == 0
+    cb = np.quantile(norms, np.linspace(0, 1, 256)).astype(np.float32)
+    rc, _, nc, dbn = pc.code_norms_cpu(lsq._lib.load(), codes, K, cent, assign, cb)
+    assert rc == 0
+    return dict(X=X, K=K, Q=Q, cent=cent, assign=assign, codes=codes, norms=norms, cb=cb, nc=nc, dbn=dbn, dK=dK, dB0=dB0)
+
+
+@pytest.mark.parametrize("packed", [False, True], ids=["plain", "packed"])
+def test_the_device_build_at_65537_lists_searches_like_the_host_statement(lsq, engine, torch, big_build, packed):
+    """reaches: build_ivf_residual_index on 65 537 lists -- assign, residuals, code_norms and set_lists at that nlist in one chain -- and its search at
+    nprobe = 1 (one list of one or two rows) and 64.  Evidence: Index.nlist, no padding in the reference's ids"""
+    b = big_build
+    dX, dQ = torch.from_numpy(b["X"]).cuda(), torch.from_numpy(b["Q"]).cuda()
+    with engine.partition_dev(torch.from_numpy(b["cent"]).cuda()) as part:
+        ix = lsq.build_ivf_residual_index(dX, part, b["dK"], BM, engine=engine, ilsiters=ILS, icmiter=2, npert=2, randord=True, seed=5, dB0=b["dB0"],
+                                          cbnorms=b["cb"] if packed else None)
+    ref = (engine.index_packed(b["codes"], b["K"], b["nc"], b["cb"], BM) if packed else engine.index(b["codes"], b["K"], b["norms"], BM))
+    ref.set_lists(b["cent"], b["assign"])
+    with ix, ref:
+        assert ix.nlist == MANY and bool(ix.packed_info()["row_bytes"]) == packed
+        for nprobe, nn in ((1, 1), (64, 10)):
+            dd, di = ix.search_ivf(dQ, nn, nprobe, add_coarse=True)
+            rd, ri = ref.search_ivf(b["Q"], nn, nprobe, add_coarse=True)
+            assert ic.padding_ok(ri) and np.all(ri > 0)
+            assert same_bits(dd.cpu().numpy(), rd) and np.array_equal(di.cpu().numpy(), ri), nprobe
+            if packed:
+                continue
+            # the distances are |q - c_l - r^|^2: float64, the tolerance of the same identity in tests/test_ivf.py
+            ids = ri.astype(np.int64) - 1
+            recon = sum(b["K"][j * H + b["codes"][:, j].astype(np.int64)] for j in range(BM)).astype(np.float64)
+            full = b["cent"][b["assign"]].astype(np.float64) + recon
+            want = ((b["Q"][:, None, :].astype(np.float64) - full[ids]) ** 2).sum(2)
+            print("nlist 65537 nprobe", nprobe, "max |dist - f64|", float(np.abs(rd - want).max()))
+            assert np.allclose(rd, want, rtol=1e-5, atol=1e-4)
+
+
+# ---- small routes --------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("want_counts", [False, True], ids=["no-counts", "counts"])
+def test_update_without_rows_keeps_the_centroids(lsq, engine, torch, want_counts):
+    """n = 0 has a branch of its own: the centroids keep their bits, the counts are zeroed on either side, info = (UPDATE, rows 0, empty_lists nlist)"""
+    cent = np.random.default_rng(1).standard_normal((9, 5)).astype(np.float32)
+    with engine.partition_dev(torch.from_numpy(cent).cuda()) as part, engine.partition(cent) as hpart:
+        for p, X, lists in ((part, torch.zeros(0, 5, device="cuda"), torch.zeros(0, dtype=torch.int32, device="cuda")),
+                            (hpart, np.zeros((0, 5), np.float32), np.zeros(0, np.int32)),
+                            (hpart, np.zeros((0, 5), np.uint8), np.zeros(0, np.int32))):
+            if want_counts and p._dev:                                                # (the wrapper hands over zeroed counts: fill the raw call's by hand)
+                counts = torch.full((9,), -7, dtype=torch.int32, device="cuda")
+                torch.cuda.synchronize()
+                assert lsq._lib.load().lsq_partition_update(p._h, None, 0, 0, 5, None, counts.data_ptr(), 1) == 0
+                assert bool((counts == 0).all())
+            elif want_counts:
+                counts = np.full(9, -7, np.int32)
+                assert lsq._lib.load().lsq_partition_update(p._h, None, int(X.dtype == np.uint8), 0, 5, None, counts.ctypes.data, 0) == 0
+                assert not counts.any()
+            got = p.update(X, lists, want_counts=want_counts)
+            assert (got is None) == (not want_counts) and (got is None or not np.asarray(got.cpu() if p._dev else got).any())
+            info = p.info()
+            assert (info["call"], info["rows"], info["empty_lists"], info["lists_touched"]) == (lsq._lib.PARTITION_UPDATE, 0, 9, 0)
+            after = p.centroids()
+            assert same_bits(after.cpu().numpy() if p._dev else after, cent)
+
+
+def test_host_forms_without_rows_write_nothing(lsq, engine):
+    """n = 0 through the raw symbols (the wrapper returns before the library for an empty array): success, nothing written, null pointers allowed"""
+    L = lsq._lib.load()
+    cent = np.random.default_rng(2).standard_normal((4, 8)).astype(np.float32)
+    lists, dist, R, norms = np.full(3, -7, np.int32), np.full(3, -7, np.float32), np.full((3, 8), -7, np.float32), np.full(3, -7, np.float32)
+    K, codes = np.zeros((2 * H, 8), np.float32), np.zeros((3, 2), np.uint8)
+    with engine.partition(cent) as part:
+        h, x = part._h, R.ctypes.data
+        assert L.lsq_partition_assign(h, x, 0, 0, 8, lists.ctypes.data, dist.ctypes.data, 0) == 0 and L.lsq_partition_assign(h, None, 0, 0, 8, None, None, 0) == 0
+        assert L.lsq_partition_residuals(h, x, 0, 0, 8, lists.ctypes.data, R.ctypes.data, 8, 0) == 0
+        assert L.lsq_partition_residuals(h, None, 1, 0, 8, None, None, 8, 0) == 0
+        assert L.lsq_partition_code_norms(h, codes.ctypes.data, K.ctypes.data, 0, 2, H, lists.ctypes.data, None, 0, norms.ctypes.data, None, None, 0) == 0
+        assert L.lsq_partition_code_norms(h, None, K.ctypes.data, 0, 2, H, None, None, 0, norms.ctypes.data, None, None, 0) == 0
+        assert np.all(lists == -7) and np.all(dist == -7) and np.all(R == -7) and np.all(norms == -7)
+        assert part.assign(np.zeros((0, 8), np.float32)).shape == (0,) and part.residuals(np.zeros((0, 8), np.float32), np.zeros(0, np.int32)).shape == (0, 8)
+        assert part.code_norms(np.zeros((0, 2), np.uint8), K, np.zeros(0, np.int32)).shape == (0,)
+        assert same_bits(part.centroids(), cent)
+
+
+def test_a_closed_engine_closes_its_partitions(lsq):
+    cent = np.random.default_rng(3).standard_normal((5, 4)).astype(np.float32)
+    X = np.random.default_rng(4).standard_normal((50, 4)).astype(np.float32)
+    eng = lsq.Engine(0)
+    part = eng.partition(cent)
+    want = part.assign(X)
+    eng.close()
+    assert part._h is None
+    part.close()                                                                      # and closing it again is harmless
+    with lsq.Engine(0) as eng2, eng2.partition(cent) as part2:
+        assert np.array_equal(part2.assign(X), want) and np.array_equal(want, lsq.ivf_assign(X, cent))

@@ -96,6 +96,73 @@ def test_named_problems_are_what_their_names_say():
             assert ic.ivf_np(*p, nprobe, nn)[1][0, 0] == n and n in ic.ivf_np(*p, nprobe, nn, add_coarse=True)[1][0]
 
 
+# ---- many lists: the problems of tests/test_gpu_many_lists.py, from the checkers alone ---------------------------------------------------------------
+def _checked(lsq, p, nprobe, nn, numpy=True):
+    """lsq_ivf_search_cpu on the problem, with and without the coarse add: the padding condition, and (numpy) ivf_np's bits"""
+    for add in (False, True):
+        rc, dd, di = ic.ivf_cpu(lsq._lib.load(), *p, nprobe, nn, flags=ic.ADD_COARSE if add else 0)
+        assert rc == 0 and ic.padding_ok(di), (add, int((di == 0).sum()))
+        if numpy:
+            rd, ri = ic.ivf_np(*p, nprobe, nn, add_coarse=add)
+            assert same_bits(dd, rd) and np.array_equal(di, ri), add
+    return di
+
+
+def test_padding_condition_refuses_results_that_compare_infinities():
+    assert ic.padding_ok(np.array([[1, 2, 3, 0], [4, 5, 6, 7]])) and not ic.padding_ok(np.array([[1, 2, 0, 0], [4, 5, 6, 0]]))
+    assert not ic.padding_ok(np.array([[0], [1], [2], [3], [4]]))                 # under a quarter, but one query is all padding
+
+
+def test_many_lists_problem_is_what_its_name_says(lsq):
+    """65 537 lists of about four rows, 64 probed: the three numbers of roads_np are pinned, so that the problem cannot drift into one that tests nothing"""
+    p, nprobe, nn = ic.many_lists_problem()
+    assert p[0].shape == (262148, 8) and p[3].shape == (ic.MANY, 8) and (nprobe, nn) == (64, 10)
+    di = _checked(lsq, p, nprobe, nn)
+    assert not np.any(di == 0)                                               # no slot is padding
+    hits = ic.tail_hits_np(*p, nprobe, nn)
+    assert min(h[0] for h in hits) == 10 and max(h[0] for h in hits) == 15 and 200 < min(h[1] for h in hits) and max(h[1] for h in hits) == 276
+    assert ic.roads_np(hits, nn) == (276, [], 7809)
+    # the coarse step by the model of the selection: the sampled road, rank 45, lists of 640; the options send it down the other two roads
+    st = ic.coarse_stats(p[3], p[6], nprobe)
+    assert (st["exhaustive"], st["threshold_rank"], st["list_capacity"]) == (0, 45, 640) and 0 <= st["fallback_queries"] < 37
+    assert ic.coarse_stats(p[3], p[6], nprobe, rank=1)["fallback_queries"] == 37 and ic.coarse_stats(p[3], p[6], nprobe, force_exhaustive=1)["exhaustive"] == 1
+
+
+@pytest.mark.parametrize("nlist", [256, 257, 65536, 65537])
+def test_list_edge_problems_keep_the_layout_pattern(lsq, nlist):
+    p, nprobe, nn = ic.list_edge_problem(nlist)
+    counts = np.bincount(p[4], minlength=nlist)
+    assert p[3].shape[0] == nlist and p[0].shape[0] == 2048 and not counts[:3].any() and not counts[-3:].any()
+    assert nlist < 65536 or (counts == 0).sum() > 64000                      # nlist >> n: runs of thousands of empty lists
+    _checked(lsq, p, nprobe, nn)
+    assert ic.ivf_np(*p, nprobe, nn)[1][0, 0] == 2048                        # the last row, id n, is query 0's nearest
+    assert ic.coarse_stats(p[3], p[6], nprobe)["exhaustive"] == (nlist <= 65536)      # the coarse search changes roads between the last two
+
+
+def test_many_probes_and_duplicated_centroid_problems(lsq):
+    p, nprobe, nn = ic.many_probes_problem()
+    _checked(lsq, p, nprobe, nn)
+    st = ic.coarse_stats(p[3], p[6], nprobe)
+    assert (st["exhaustive"], st["threshold_rank"], st["list_capacity"]) == (0, 352, 3200)
+    p, nprobe, nn = ic.duplicated_centroids_problem()
+    di = _checked(lsq, p, nprobe, nn)
+    assert (di == 0).sum() == 45                                             # of 370 slots
+    st = ic.coarse_stats(p[3], p[6], nprobe)                                 # a mixed coarse batch: query 0 overflows on the 40 000 ties, others are served
+    assert 1 <= st["fallback_queries"] < 37 and ic.coarse_stats(p[3], p[6][:1], nprobe)["fallback_queries"] == 1
+    probes = ic.probes_np(p[3], p[6][:1], nprobe)[1][0]
+    tied = probes[(probes >= 5000) & (probes < 45000)]                       # the ties go to the smaller list ids, after the few nearer centroids
+    assert 8 <= tied.shape[0] < nprobe and np.array_equal(tied, np.arange(5000, 5000 + tied.shape[0])) and np.array_equal(tied, probes[-tied.shape[0]:])
+
+
+def test_near_lists_put_rows_into_probed_lists_at_the_bound(lsq):
+    """nlist = 2^24, 4096 rows: no padding at nprobe = 16 or 1, although all but 950 lists are empty"""
+    p, nprobe, nn = ic.bound_problem()
+    counts = np.bincount(p[4], minlength=ic.BOUND)
+    assert p[3].shape == (ic.BOUND, 2) and counts[0] == 1 and counts[-1] == 1 and ((counts > 0).sum(), counts.max()) == (950, 26)
+    for k in (nprobe, 1):
+        assert not np.any(_checked(lsq, p, k, nn, numpy=False) == 0)
+
+
 def test_padding_entries_follow_nan_when_the_probed_lists_are_short(lsq):
     codes, K, dbn, cent, lor, Qs, Qc = ic.problem(ic.N, 32, 8, 40, 5, 3)
     lor[:] = 0

@@ -117,6 +117,39 @@ def test_update_cpu_on_row_views_uint8_rows_and_the_list_ladder(lsq):
         assert rc == 0 and same_bits(got, want) and np.array_equal(counts, wc)
 
 
+# ---- many lists: the problems of tests/test_gpu_partition.py above 65 536 lists, from the host alone ----------------------------------------------------
+@pytest.mark.parametrize("u8", [False, True], ids=["f32", "u8"])
+@pytest.mark.parametrize("nlist", [65536, 65537])
+def test_assign_problem_has_its_tie_and_its_zero_distance(lsq, nlist, u8):
+    """the host cores (ivf_assign) against the numpy statement on the rows the device's distances are held to"""
+    cent, X = pc.assign_problem(nlist, u8)
+    rows = np.r_[0:198, 7, X.shape[0] // 2]
+    want = lsq.ivf_assign(X[rows], cent)
+    ref, acc = pc.assign_np(X[rows], cent)
+    assert np.array_equal(want, ref) and X.dtype == (np.uint8 if u8 else np.float32) and cent.shape == (nlist, 8)
+    assert want[-1] == pc.TIE[0] and 7.9 < acc[-1, pc.TIE[0]] == acc[-1, pc.TIE[1]] < 8.1 and want[-2] == 123 and acc[-2, 123] == 0
+    assert len(set(want.tolist())) > 150                                              # the rows spread over the lists
+
+
+def test_duplicated_centroids_split_the_rows_of_a_coarse_search():
+    """by the model of the selection: the rows beside the 40 000 equal centroids overflow their candidate lists, and not every row does"""
+    import ivf_check as ic
+    cent, X = pc.duplicated_centroids()
+    st = ic.coarse_stats(cent, X, 1)
+    assert st["exhaustive"] == 0 and 100 <= st["fallback_queries"] < X.shape[0]
+    assert np.all(pc.assign_np(X[:100], cent)[0] == 5000)
+
+
+def test_update_cpu_is_the_numpy_statement_at_65537_lists(lsq):
+    X = pc.decades(262148, 5, 6)
+    assign = np.random.default_rng(5).integers(0, 65537, 262148).astype(np.int32)
+    cent = np.random.default_rng(2).standard_normal((65537, 5)).astype(np.float32)
+    rc, got, counts = pc.update_cpu(lsq._lib.load(), cent, X, assign)
+    want, wc = pc.update_np(cent, X, assign)
+    assert rc == 0 and same_bits(got, want) and np.array_equal(counts, wc) and 500 < (wc == 0).sum() < 2000
+    assert same_bits(got[wc == 0], cent[wc == 0])
+
+
 # ---- residuals ------------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("d", [1, 3, 4, 5, 16, 127, 128, 130])
 def test_residuals_cpu_is_the_numpy_statement(lsq, d):
