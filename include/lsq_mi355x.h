@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 1900
+#define LSQ_VERSION 2000
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -640,7 +640,57 @@ LSQ_API int lsq_partition_code_norms_cpu(float *norms, uint8_t *norm_codes, floa
                                          const float *centroids, const int32_t *list_of_row, int64_t n, int m, int h, int d, int nlist,
                                          const float *cbnorms, int ncb, int nthreads);
 
-/* quantize_norms(B, C, cbnorms) -> dbnormsB      src/utils.jl:6-31: per database vector the squared norm of its reconstruction
+/* ---- (3j) row filters on the resident index: search only the allowed rows (csrc/lsq_filter.hip; since v2000) -------------------------------------------
+ * THE REFERENCE HAS NO COUNTERPART: its scan answers over every code.  A filter is a set A of allowed rows, 0 <= row < n, OWNED by the index: deletions
+ * (a tombstone list with LSQ_FILTER_DENY), predicates (a boolean mask the caller computed), and the ground truth of a filtered recall figure
+ * (lsq_index_knn under the same filter).  An index without a filter behaves exactly as before v2000.
+ *   contract     while a filter is set, lsq_index_search, lsq_index_search_ivf and lsq_index_knn return, per query, THE RESULT THE SAME CALL WOULD RETURN
+ *                FOR nn = (all candidate rows), WITH EVERY ROW OUTSIDE A REMOVED, TRUNCATED TO nn.  The distance bits of every returned row and their
+ *                order -- (dist, id) lexicographic, ties to the smaller original id, NaN after every number -- are unchanged; ids are the original ones
+ *                in the id base the call already uses.  Where fewer than nn allowed rows exist (or are probed) the remaining entries are
+ *                (+inf, id_base - 1), after everything, NaN included: (+inf, 0) for the 1-based searches, what lsq_index_search_ivf already returns past
+ *                its probed rows.  nn <= n stays the argument rule; nn > |A| is legal.
+ *   shortlist    shortlist = L: stage one under the filter for L, then stage two as it is; padding entries are never dereferenced and stay last.
+ *   re-rank      lsq_index_rerank IGNORES the filter: the candidates are the caller's choice.
+ *   identities   a filter that allows every row, and a cleared filter, give the unfiltered call's result bit for bit.
+ *   lists        the filter and the inverted lists are independent: lsq_index_set_lists and lsq_index_set_filter may be called in either order and
+ *                either may be replaced later.  lsq_ivf_info.probed_rows counts the filtered rows of the probed lists too (they are read); the head of
+ *                the thresholded road is chosen on ALLOWED counts, so its nn-th record is a finite, exact bound whenever the probed lists hold nn
+ *                allowed rows.
+ *   inputs       LSQ_FILTER_BITS: uint32 [ceil(n/32)], bit (i & 31) of word i >> 5 = row i; bits at or past n are ignored.  LSQ_FILTER_BYTES: uint8
+ *                [n], non-zero = set (a numpy / torch bool array as it is).  LSQ_FILTER_IDS: int32 [count] row ids in id_base (0 or 1), duplicates
+ *                legal.  LSQ_FILTER_DENY: the set rows are the EXCLUDED ones.  on_device: 0 = a host array, 1 = a device array.  The filter is always a
+ *                copy (n/8 bytes, 4 bytes per 32 rows of prefix and 4 bytes per allowed row; with inverted lists the same bitmap and prefix once more in
+ *                layout order): the caller's array may be freed or changed when the call returns.  desc == NULL clears the filter.
+ *   roads        dense: the scans read every row and the bit beside it; a filtered row leaves as the record of an id outside the base.  compact: the
+ *                scans walk the ascending list of allowed rows.  The same distances, bit for bit.  Compact is taken when allowed <=
+ *                lsq_filter_info.crossover_rows (n / 2, measured) -- except, on an index of more than 65 536 rows, for 65 536 allowed rows or fewer
+ *                with allowed * c > n (c = 64 for lsq_index_search, 8 for lsq_index_knn): so few rows take the selection that writes and sorts every
+ *                distance, which costs c dense steps per row.  LSQ_FILTER_FORCE_DENSE / _COMPACT are test hooks that override the rule.
+ *                lsq_index_search_ivf reads the inverted layout with the filter's bits in layout order (there is no compact form of the layout).
+ * LSQ_EINVAL with nothing changed and the former filter left in place: a null handle, null data, an unknown form or flag, both FORCE flags, count < 0, an
+ * id_base other than 0 / 1, an IDS entry outside [id_base, id_base + n) -- found by the one kernel that reads the entries, which counts them, before any
+ * of them is used as an address. */
+enum { LSQ_FILTER_BITS = 0, LSQ_FILTER_BYTES = 1, LSQ_FILTER_IDS = 2 };                    /* form */
+enum { LSQ_FILTER_DENY = 1, LSQ_FILTER_FORCE_DENSE = 2, LSQ_FILTER_FORCE_COMPACT = 4 };    /* flags; the two FORCE flags are test hooks */
+typedef struct lsq_filter_desc {
+    int form;
+    const void *data;     /* BITS: uint32 [ceil(n/32)]; BYTES: uint8 [n]; IDS: int32 [count] */
+    int64_t count;        /* IDS only */
+    int id_base;          /* IDS only: 0 or 1 */
+    int flags;            /* LSQ_FILTER_DENY | one FORCE flag */
+    int on_device;
+} lsq_filter_desc;
+typedef struct lsq_filter_info {
+    int64_t active, n, allowed;
+    int64_t lists, lists_without_allowed;   /* 0 / 0 without inverted lists (or without a filter) */
+    int64_t road;                           /* last search / knn call: 0 unfiltered, 1 dense, 2 compact */
+    int64_t crossover_rows;                 /* compact road taken by default when allowed <= this (and outside the band described above) */
+} lsq_filter_info;
+LSQ_API int lsq_index_set_filter(lsq_index *ix, const lsq_filter_desc *desc);   /* desc == NULL clears */
+LSQ_API int lsq_index_get_filter_info(lsq_index *ix, lsq_filter_info *out);
+
+/* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of
  * (norm - cbnorms[j])^2 like findmin.  `dbnorms` (optional) receives cbnorms[index] -- what the scan consumes (demos/demo_lsq_gpu.jl:57-60);
  * `norms` (optional) the unquantised norms (the input of the reference's norm k-means, src/lsq/LSQ.jl:80-84).  PARITY UNPINNED: the reference's

@@ -83,6 +83,19 @@ class IndexPackedInfo(_Struct):
     _fields_ = [("row_bytes", C.c_int64), ("ivf_row_bytes", C.c_int64), ("ncb", C.c_int64), ("dword_rows", C.c_int64), ("resident_bytes", C.c_int64)]
 
 
+class FilterDesc(_Struct):
+    _fields_ = [("form", C.c_int), ("data", C.c_void_p), ("count", C.c_int64), ("id_base", C.c_int), ("flags", C.c_int), ("on_device", C.c_int)]
+
+
+class FilterInfo(_Struct):
+    _fields_ = [("active", C.c_int64), ("n", C.c_int64), ("allowed", C.c_int64), ("lists", C.c_int64), ("lists_without_allowed", C.c_int64),
+                ("road", C.c_int64), ("crossover_rows", C.c_int64)]
+
+
+FILTER_BITS, FILTER_BYTES, FILTER_IDS = 0, 1, 2
+FILTER_DENY, FILTER_FORCE_DENSE, FILTER_FORCE_COMPACT = 1, 2, 4
+
+
 class EncoderDesc(_Struct):
     _fields_ = [("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("codebooks", C.c_void_p), ("on_device", C.c_int), ("chunk", C.c_int64)]
 
@@ -193,6 +206,8 @@ SIGNATURES = {
     "lsq_index_create_packed": (_i, [C.POINTER(_vp), _vp, C.POINTER(IndexPackedDesc)]),
     "lsq_index_get_packed_info": (_i, [_vp, C.POINTER(IndexPackedInfo)]),
     "lsq_index_get_scan_stats": (_i, [_vp, C.POINTER(LinscanStats)]),
+    "lsq_index_set_filter": (_i, [_vp, C.POINTER(FilterDesc)]),
+    "lsq_index_get_filter_info": (_i, [_vp, C.POINTER(FilterInfo)]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),

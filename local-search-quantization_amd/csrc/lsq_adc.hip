@@ -42,6 +42,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int ADC_SAMPLE = 16384;            // sample size of the threshold estimate
 constexpr int ADC_SMALL_N = 65536;           // databases up to this size: exhaustive road (every distance written and sorted)
+static_assert(ADC_SMALL_N == LSQ_SELECT_SMALL_N, "a filter's default road (lsq_internal.h) is chosen by this limit");
 constexpr int ADC_SCAN_THREADS = 1024;
 constexpr int ADC_KC = 1024;                 // LUT build: dimensions staged per pass
 
@@ -157,13 +158,19 @@ struct AdcStage {
 // A lane owns one code and four queries per step.  The codes of the NEXT batch of U steps are requested before the current batch is walked: a
 // code's bytes come from L2 (~1 us away), its 16-byte table reads from LDS (~0.1 us), and without the prefetch the walk waits for L2 once per
 // code (measured: 7 of 28 TB/s of LDS gathers).
+// FILT (a row filter, lsq_filter.hip): frows == nullptr -- the DENSE road: the walk is the unfiltered one and the word of fbits that holds row i's bit is
+// fetched with its code (one dword per 32 consecutive rows); a filtered row does not pass (MODE 0), leaves as the record of an id outside the base -- the bit
+// above the key, the key of +inf, id field 0 (MODE 1) -- or as the key 0xffffffff (MODE 2).  frows != nullptr -- the COMPACT road: position s of the walk is row
+// frows[s] (fetched in the prefetch stage, s < n = the number of allowed rows); MODE 1 pads the positions n <= s < ns with the same record.  The
+// distance of a row is computed by the same instructions on the same operands on both roads.  FILT = false: the kernel as it was, the two arguments unread.
 enum { ADC_NORM_NONE = 0, ADC_NORM_F32 = 1, ADC_NORM_BYTE = 2 };
 constexpr int ADC_NORM_TABLE = 256;          // floats of the staged norm table (entries >= ncb are padding, never addressed)
-template <int QT, int MODE, int MW, int NORM>
+template <int QT, int MODE, int MW, int NORM, bool FILT = false>
 __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void adc_scan_kernel(const float *__restrict__ LUT, const uint8_t *__restrict__ codes,
                                                                     const float *__restrict__ dbnorms, int n, int m, int cstride, int nqb, int stride, int ns,
                                                                     int per_block, const uint32_t *__restrict__ tau, unsigned *__restrict__ count,
-                                                                    int cap, uint64_t *__restrict__ out, int idbits) {
+                                                                    int cap, uint64_t *__restrict__ out, int idbits,
+                                                                    const uint32_t *__restrict__ fbits, const int *__restrict__ frows) {
     extern __shared__ __attribute__((aligned(16))) float lut[];      // [m * 256][QT], the norm table (ADC_NORM_BYTE), then the emission staging of MODE 0 (AdcStage)
     constexpr int NQ = QT / 4, CPW = 64 / NQ;                        // query quads, codes per wave step
     constexpr int U = MW == 0 ? 1 : (MW <= 2 ? 4 : 2);               // steps per batch
@@ -225,12 +232,30 @@ __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_e
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     };
 
-    struct Batch { uint32_t w[U][CW]; float nrm[U]; };
+    struct Batch { uint32_t w[U][CW]; float nrm[U]; int row[FILT ? U : 1]; uint32_t ok[FILT ? U : 1]; };
+    const bool compact = FILT && frows != nullptr;                   // (block-uniform)
+    // FILT: the row of walk position s and whether it leaves a record; a dead position (s >= last, or past the allowed rows) reads row 0, which every index has
+    auto row_of = [&](int s, uint32_t &ok) -> int64_t {
+        const int64_t at = (int64_t)(s < last ? s : first) * (MODE == 0 ? 1 : stride);
+        if (compact) {
+            const bool have = s < last && at < n;
+            ok = have ? 1u : 0u;
+            return have ? (int64_t)frows[at] : 0;
+        }
+        ok = (fbits[at >> 5] >> (at & 31)) & 1u;
+        return at;
+    };
     auto fetch = [&](Batch &bt, int s0) {                            // codes s0 + u * CPW + cs, u < U (dead ones read the block's first code)
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int s = s0 + u * CPW + cs;
-            const int64_t i = (int64_t)(s < last ? s : first) * (MODE == 0 ? 1 : stride);
+            int64_t i;
+            if constexpr (FILT) {
+                i = row_of(s, bt.ok[u]);
+                bt.row[u] = (int)i;
+            } else {
+                i = (int64_t)(s < last ? s : first) * (MODE == 0 ? 1 : stride);
+            }
             if (MW > 0) {
                 const uint32_t *cp = reinterpret_cast<const uint32_t *>(codes + i * (4 * CW));
 #pragma unroll
@@ -270,7 +295,7 @@ __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_e
 #pragma unroll
                     for (int j = 0; j < NT; ++j) acc = acc + v[g][j];
                 } else {
-                    const int64_t i = (int64_t)(s < last ? s : first) * (MODE == 0 ? 1 : stride);
+                    const int64_t i = FILT ? (int64_t)cur.row[u0 + g] : (int64_t)(s < last ? s : first) * (MODE == 0 ? 1 : stride);
                     const uint8_t *cp = codes + i * cstride;
                     for (int j = 0; j < m; ++j) acc = acc + lut4[(j * LSQ_H + (int)cp[j]) * NQ + qq];
                     if constexpr (NORM == ADC_NORM_BYTE) nb[g] = ntab[cp[m]];
@@ -288,17 +313,24 @@ __global__ __launch_bounds__(ADC_SCAN_THREADS) __attribute__((amdgpu_waves_per_e
             for (int g = 0; g < G; ++g) {
                 const int s = s0 + (u0 + g) * CPW + cs;
                 const bool live = s < last;
-                const int64_t i = (int64_t)(live ? s : first) * (MODE == 0 ? 1 : stride);
+                const int64_t i = FILT ? (int64_t)cur.row[u0 + g] : (int64_t)(live ? s : first) * (MODE == 0 ? 1 : stride);
+                const bool allowed = FILT ? cur.ok[u0 + g] != 0u : true;
                 const float dv[4] = {dist[g].x, dist[g].y, dist[g].z, dist[g].w};
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     // MODE 0: one test per query; a wave enters the body for ~16 % of its steps per query (list of 2.8 nn entries, nn = 1000, n = 10^6)
-                    const bool hit = MODE == 0 ? (live && !(dv[c] > tf[c])) : live;
+                    const bool hit = MODE == 0 ? (live && allowed && !(dv[c] > tf[c])) : live;
                     if (!hit) continue;
                     const int slot = slot0 + c;
                     if (slot >= nqb) continue;
-                    const uint32_t key = lsq_adc_key(dv[c]);
-                    const uint64_t rec = ((uint64_t)key << idbits) | (uint64_t)(i + 1);      // ids are 1-BASED (:75)
+                    uint32_t key = lsq_adc_key(dv[c]);
+                    uint64_t rec = ((uint64_t)key << idbits) | (uint64_t)(i + 1);      // ids are 1-BASED (:75)
+                    if constexpr (FILT && MODE != 0) {
+                        if (!allowed) {                                  // the record of an id outside the base: after everything, NaN included
+                            key = 0xffffffffu;
+                            rec = (1ull << (32 + idbits)) | ((uint64_t)lsq_adc_key(__builtin_inff()) << idbits);
+                        }
+                    }
                     if (MODE == 1) {
                         out[(int64_t)slot * ns + s] = rec;
                     } else if (MODE == 2) {
@@ -475,7 +507,7 @@ template <int QT, int MODE>
 int launch_scan(hipStream_t s, const float *LUT, const lsq_search_input &in, int nqb, int stride, int ns, const uint32_t *tau, unsigned *count, int cap,
                 uint64_t *out, int idbits) {
     const int tiles = (nqb + QT - 1) / QT;
-    const int n = in.n, m = in.m;
+    const int n = in.rows_walked(), m = in.m;            // compact road: the allowed rows
     const int total = MODE == 0 ? n : ns;
     if (tiles == 0 || total == 0) return LSQ_OK;
     // enough blocks to fill the chip a few times over, ranges long enough that the table load (m KiB per query) is amortised
@@ -492,12 +524,20 @@ int launch_scan(hipStream_t s, const float *LUT, const lsq_search_input &in, int
     const size_t lds = sizeof(float) * ((size_t)m * LSQ_H * QT + (packed ? ADC_NORM_TABLE : 0)) + (MODE == 0 ? sizeof(AdcStage) * (ADC_SCAN_THREADS / 64) : 0);
     const bool words = (rowb % 4 == 0) && in.cstride == rowb && (((uintptr_t)in.codes & 3) == 0);
     const dim3 grid((unsigned)tiles, (unsigned)ranges), block(ADC_SCAN_THREADS);
-#define ADC_LAUNCH(MWV, NORMV)                                                                                                              \
+    const uint32_t *fbits = in.filter_bits;
+    const int *frows = in.filter_rows;
+#define ADC_LAUNCH_F(MWV, NORMV, FILTV)                                                                                                     \
     do {                                                                                                                                    \
-        LSQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&adc_scan_kernel<QT, MODE, MWV, NORMV>),                                  \
+        LSQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&adc_scan_kernel<QT, MODE, MWV, NORMV, FILTV>),                           \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                                  \
-        hipLaunchKernelGGL((adc_scan_kernel<QT, MODE, MWV, NORMV>), grid, block, lds, s, LUT, in.codes, in.dbnorms, n, m, in.cstride, nqb,   \
-                           stride, ns, per_block, tau, count, cap, out, idbits);                                                            \
+        hipLaunchKernelGGL((adc_scan_kernel<QT, MODE, MWV, NORMV, FILTV>), grid, block, lds, s, LUT, in.codes, in.dbnorms, n, m, in.cstride, \
+                           nqb, stride, ns, per_block, tau, count, cap, out, idbits, fbits, frows);                                         \
+    } while (0)
+    // a filter is an index's (LSQ rows): the PQ scan has no filtered instantiation
+#define ADC_LAUNCH(MWV, NORMV)                                                    \
+    do {                                                                          \
+        if (NORMV != ADC_NORM_NONE && in.filtered()) ADC_LAUNCH_F(MWV, (NORMV != ADC_NORM_NONE ? NORMV : ADC_NORM_F32), true); \
+        else ADC_LAUNCH_F(MWV, NORMV, false);                                     \
     } while (0)
 #define ADC_LAUNCH_MW(NORMV)                      \
     do {                                          \
@@ -512,6 +552,7 @@ int launch_scan(hipStream_t s, const float *LUT, const lsq_search_input &in, int
     else ADC_LAUNCH_MW(ADC_NORM_NONE);
 #undef ADC_LAUNCH_MW
 #undef ADC_LAUNCH
+#undef ADC_LAUNCH_F
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }
@@ -599,9 +640,13 @@ Plan make_plan(int n, int nn, int force_exhaustive) {
 template <int QT>
 int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const lsq_search_input &in, const int *qsel, int q0, int nqb, int nn,
               const Plan &P, int *h_fail, lsq_linscan_stats *stats, bool timed) {
-    const int n = in.n, entries = in.m * LSQ_H, tiles = (nqb + QT - 1) / QT;
+    // n: the record slots of a query on the exhaustive road.  Under a filter's compact road the walk is over the allowed rows, padded to nn slots where
+    // they are fewer; a filtered call sorts on one bit more, the bit of the record of an id outside the base (what filtered rows and padding leave as)
+    const int n = in.filter_rows ? std::max(in.filter_count, nn) : in.n;
+    const int entries = in.m * LSQ_H, tiles = (nqb + QT - 1) / QT;
     const bool tables = in.kind != LSQ_SEARCH_EXACT;
-    const int idbits = lsq_adc_idbits(n);             // the records are (distance key << idbits | id), sorted on their 32 + idbits bits
+    const int idbits = lsq_adc_idbits(in.n);          // the records are (distance key << idbits | id), sorted on their 32 + idbits bits
+    const int end_bit = (in.filtered() ? 33 : 32) + idbits;
     if (tables) LSQ_TRY(st->lut.ensure(sizeof(float) * (size_t)tiles * entries * QT));
     LSQ_TRY(st->seg.ensure(sizeof(int) * 2 * (size_t)nqb));
     LSQ_TRY(st->fail.ensure(sizeof(int) * (size_t)nqb));
@@ -616,7 +661,7 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ls
         LSQ_TRY((launch_producer<QT, 1>(s, st->lut.as<float>(), in, qsel, q0, nqb, 1, n, nullptr, nullptr, n, st->keys_a.as<uint64_t>(), idbits)));
         LSQ_TRY(st->clock.mark(s));
         LSQ_TRY(lsq_adc_select(&st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), st->seg.as<int>(), nullptr, nullptr, qsel, q0, nqb, n, nn,
-                               dists, idx, idbits, 32 + idbits, in.id_sub()));
+                               dists, idx, idbits, end_bit, in.id_sub()));
         if (stats) stats->candidates += (int64_t)nqb * n;
     } else {
         const size_t items = (size_t)nqb * (size_t)(P.cap > P.ns ? P.cap : P.ns);
@@ -635,7 +680,7 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ls
                                         st->keys_a.as<uint64_t>(), idbits)));
         LSQ_TRY(st->clock.mark(s));
         LSQ_TRY(lsq_adc_select(&st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(),
-                               st->fail.as<int>(), qsel, q0, nqb, P.cap, nn, dists, idx, idbits, 32 + idbits, in.id_sub()));
+                               st->fail.as<int>(), qsel, q0, nqb, P.cap, nn, dists, idx, idbits, end_bit, in.id_sub()));
         LSQ_HIP(hipMemcpyAsync(h_fail, st->fail.p, sizeof(int) * (size_t)nqb, hipMemcpyDeviceToHost, s));
         if (stats) {
             std::vector<unsigned> hc((size_t)nqb);
@@ -662,14 +707,17 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
     if (!*pst) *pst = new lsq_adc_state();
     lsq_adc_state *st = *pst;
     lsq_linscan_stats *stats = opt.stats;
-    const int n = in.n;
+    // a filter's compact road walks the allowed rows alone: the plan is that of a database of |A| rows asked for min(nn, |A|), and a query's record slots
+    // on the exhaustive road are padded up to nn (run_batch).  Every other call: n rows, n slots
+    const int n = in.rows_walked();
+    const int slots = in.filter_rows ? std::max(n, nn) : n;
     const bool timed = opt.timed != 0;
-    Plan P = make_plan(n, nn, opt.force_exhaustive);
+    Plan P = make_plan(n, in.filter_rows ? std::min(nn, n) : nn, opt.force_exhaustive);
     if (!P.exhaustive && opt.rank_override > 0) {    // test hook: a deliberately wrong threshold rank (forces the fallback road)
         P.r = opt.rank_override < P.ns ? opt.rank_override : P.ns;
     }
     const bool wide = lsq_adc_lut_qt(in.m) == 16;    // 16 queries per block up to m = 8 (128 KiB of tables), 8 above
-    const int64_t per_query = P.exhaustive ? n : (P.cap > P.ns ? P.cap : P.ns);
+    const int64_t per_query = P.exhaustive ? slots : (P.cap > P.ns ? P.cap : P.ns);
     int64_t qb = lsq_adc_batch_queries(per_query);   // two key buffers of per_query entries per query; whole tiles of 16 queries
     if (qb > 16) qb &= ~(int64_t)15;
     std::vector<int> h_fail;
@@ -688,9 +736,9 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
     if (!failed.empty()) {
         // the exhaustive road for the queries whose candidate list came out short or overflowed
         Plan E = P;
-        E.exhaustive = true; E.cap = n;
+        E.exhaustive = true; E.cap = slots;
         static_assert(ADC_SMALL_N >= 16384, "n > ADC_SMALL_N on this road: the rule's limit of 16384 queries is never what decides here");
-        int64_t fb = lsq_adc_batch_queries(n);
+        int64_t fb = lsq_adc_batch_queries(slots);
         if (fb > 16) fb &= ~(int64_t)15;
         LSQ_TRY(st->qsel.ensure(sizeof(int) * failed.size()));
         LSQ_HIP(hipMemcpyAsync(st->qsel.p, failed.data(), sizeof(int) * failed.size(), hipMemcpyHostToDevice, s));

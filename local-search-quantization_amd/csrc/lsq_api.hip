@@ -560,7 +560,21 @@ struct lsq_index {
     PhaseClock<3> clock;                               // a re-rank batch's gather and selection; lsq_index_knn's norm pass
     lsq_index_stats stats{};
     lsq_index_knn_info knn{};
+    lsq_filter_state *filter = nullptr;                // the row filter (lsq_filter.hip): null until lsq_index_set_filter; owned copies of THIS index
 };
+
+// the filter as a scan over all rows takes it: nothing without one; else the compact road -- the ascending list of allowed rows -- where the measured rule
+// says so (lsq_filter_compact_by_default; sort_over_scan: the call's constant) or forced, the dense road -- the bitmap beside every row -- otherwise.
+// *road: 0 unfiltered, 1 dense, 2 compact
+static void index_apply_filter(lsq_index *ix, lsq_search_input *in, int *road, int64_t sort_over_scan) {
+    *road = 0;
+    if (!lsq_filter_active(ix->filter)) return;
+    const lsq_filter_view v = lsq_filter_get(ix->filter);
+    const bool compact = v.force == LSQ_FILTER_FORCE_COMPACT || (v.force == 0 && lsq_filter_compact_by_default(ix->n, v.allowed, sort_over_scan));
+    if (compact) { in->filter_rows = v.rows; in->filter_count = (int)v.allowed; }
+    else in->filter_bits = v.bits;
+    *road = compact ? 2 : 1;
+}
 
 extern "C" int lsq_index_destroy(lsq_index *ix) {
     if (!ix) return LSQ_OK;
@@ -571,6 +585,7 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     for (DevBuf *b : bufs) b->release();
     lsq_adc_free(ix->adc);
     lsq_ivf_free(ix->ivf);
+    lsq_filter_free(ix->filter);
     ix->clock.release();
     delete ix;
     return LSQ_OK;
@@ -865,6 +880,9 @@ extern "C" int lsq_index_search(lsq_index *ix, float *dists, int *ids, const flo
         lsq_linscan_stats st{};
         lsq_search_input in = lsq_input(ix->codes, dqs, ix->K, ix->norms, (int)ix->n, ix->m, ix->d);
         if (ix->packed) { in.packed = 1; in.cstride = ix->m + 1; }      // rows with their norm byte; norms is the table
+        int road = 0;
+        index_apply_filter(ix, &in, &road, 64);
+        lsq_filter_note_road(ix->filter, road);
         LSQ_TRY(lsq_adc_search(c->stream, &ix->adc, scan_d, scan_i, in, nq, len, search_opts(c, &st)));
         ix->scan = st;
         ix->stats.scan_ms += st.lut_ms + st.sample_ms + st.scan_ms + st.select_ms;
@@ -913,6 +931,9 @@ extern "C" int lsq_index_knn(lsq_index *ix, float *dists, int *ids, const void *
         in.qnorms = ix->nrm_q.as<uint32_t>();
     }
     lsq_linscan_stats st{};
+    int road = 0;
+    index_apply_filter(ix, &in, &road, 8);
+    lsq_filter_note_road(ix->filter, road);
     LSQ_TRY(lsq_adc_search(s, &ix->adc, call.out_d, call.out_i, in, nq, nn, search_opts(c, &st)));
     LSQ_TRY(call.finish());
     info.queries = nq; info.rows = n; info.batches = st.batches; info.fallback_queries = st.fallback_queries; info.exhaustive = st.exhaustive;
@@ -934,6 +955,14 @@ extern "C" int lsq_index_get_stats(lsq_index *ix, lsq_index_stats *out) {
     return LSQ_OK;
 }
 
+// the filter's bitmap in the order of the inverted layout: rebuilt whenever the lists or the filter change (a no-op while either is missing)
+static int index_filter_layout(lsq_index *ix) {
+    if (!ix->filter) return LSQ_OK;
+    const int *ids = nullptr, *off = nullptr;
+    lsq_ivf_layout(ix->ivf, &ids, &off);
+    return lsq_filter_layout(ix->ctx->stream, ix->filter, ids, off, ix->n, lsq_ivf_nlist(ix->ivf));
+}
+
 // ---- inverted lists on the index (lsq_ivf.hip): the layout, then a search over each query's probed lists with stage two behind it ----------------------
 extern "C" int lsq_index_set_lists(lsq_index *ix, const lsq_ivf_desc *desc) {
     if (!ix || !desc) { lsq_set_error("lsq_index_set_lists: null %s", ix ? "description" : "index"); return LSQ_EINVAL; }
@@ -941,7 +970,8 @@ extern "C" int lsq_index_set_lists(lsq_index *ix, const lsq_ivf_desc *desc) {
     if (desc->nlist < 1 || desc->nlist > (1 << 24)) { lsq_set_error("lsq_index_set_lists: needs 1 <= nlist <= 2^24 (got %d)", desc->nlist); return LSQ_EINVAL; }
     if (!desc->centroids || !desc->list_of_row) { lsq_set_error("lsq_index_set_lists: null pointer"); return LSQ_EINVAL; }
     LSQ_TRY(use_device(ix->ctx));
-    return lsq_ivf_set_lists(ix->ctx->stream, &ix->ivf, ix->codes, ix->norms, ix->packed, ix->n, ix->m, ix->d, desc);
+    LSQ_TRY(lsq_ivf_set_lists(ix->ctx->stream, &ix->ivf, ix->codes, ix->norms, ix->packed, ix->n, ix->m, ix->d, desc));
+    return index_filter_layout(ix);                   // a filter's layout-order bits follow the new lists
 }
 
 extern "C" int lsq_index_search_ivf(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_coarse, const float *q_exact, int nq, int ldq,
@@ -962,13 +992,34 @@ extern "C" int lsq_index_search_ivf(lsq_index *ix, float *dists, int *ids, const
         const float *dqc = nullptr;                   // the coarse search reads rows as they lie
         int64_t ldc = 0;
         LSQ_TRY(call.rows(ix->s_qcoarse, q_coarse ? q_coarse : q_scan, sizeof(float), ldq, ix->d, false, !on_device, &dqc, &ldc));
-        return lsq_ivf_search(c->stream, ix->ivf, &ix->adc, ix->K, scan_d, scan_i, dqs, dqc, ldc, nq, nprobe, len, flags, c->search, c->profile);
+        if (!lsq_filter_active(ix->filter))
+            return lsq_ivf_search(c->stream, ix->ivf, &ix->adc, ix->K, scan_d, scan_i, dqs, dqc, ldc, nq, nprobe, len, flags, c->search, c->profile);
+        // under a filter: the inverted layout is read as it lies, with the filter's bits in layout order (the dense road; the layout has no compact form)
+        const lsq_filter_view v = lsq_filter_get(ix->filter);
+        if (!v.lbits) { lsq_set_error("lsq_index_search_ivf: the filter has no bits in layout order (a failed lsq_index_set_lists / _set_filter?)"); return LSQ_EINVAL; }
+        lsq_filter_note_road(ix->filter, 1);
+        return lsq_ivf_search(c->stream, ix->ivf, &ix->adc, ix->K, scan_d, scan_i, dqs, dqc, ldc, nq, nprobe, len, flags, c->search, c->profile, &v);
     });
 }
 
 extern "C" int lsq_index_get_ivf_info(lsq_index *ix, lsq_ivf_info *out) {
     if (!ix || !out) { lsq_set_error("lsq_index_get_ivf_info: null argument"); return LSQ_EINVAL; }
     lsq_ivf_get_info(ix->ivf, out);
+    return LSQ_OK;
+}
+
+// ---- row filters on the index (lsq_filter.hip): the allowed rows, owned; lsq_index_search, _search_ivf and _knn answer over them alone --------------------
+extern "C" int lsq_index_set_filter(lsq_index *ix, const lsq_filter_desc *desc) {
+    if (!ix) { lsq_set_error("lsq_index_set_filter: null index"); return LSQ_EINVAL; }
+    if (!desc) { lsq_filter_clear(ix->filter); return LSQ_OK; }
+    LSQ_TRY(use_device(ix->ctx));
+    LSQ_TRY(lsq_filter_set(ix->ctx->stream, &ix->filter, ix->n, desc));
+    return index_filter_layout(ix);
+}
+
+extern "C" int lsq_index_get_filter_info(lsq_index *ix, lsq_filter_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_filter_info: null argument"); return LSQ_EINVAL; }
+    lsq_filter_get_info(ix->filter, ix->n, out);
     return LSQ_OK;
 }
 

@@ -326,6 +326,14 @@ struct lsq_search_input {
     const uint32_t *xnorms = nullptr, *qnorms = nullptr;
     int id_base = 0;                         // exact: ids leave as row + id_base
     int packed = 0;                          // LSQ: rows of cstride = m + 1 bytes, the last one the norm byte c_i; dbnorms = the norm table padded to 256 floats
+    // a row filter (lsq_filter.hip), LSQ and exact kinds.  filter_bits: bit (i & 31) of word i >> 5 = row i is allowed -- the DENSE road: every row is read, a
+    // filtered one leaves as the record of an id outside the base (or does not leave).  filter_rows [filter_count]: the allowed rows ascending -- the COMPACT
+    // road: the scan walks them instead of 0 .. n-1 (filter_bits is then ignored).  Both null: no filter, the scans' unfiltered instantiations
+    const uint32_t *filter_bits = nullptr;
+    const int *filter_rows = nullptr;
+    int filter_count = 0;
+    bool filtered() const { return filter_bits != nullptr || filter_rows != nullptr; }
+    int rows_walked() const { return filter_rows ? filter_count : n; }      // rows a full scan reads
     int query_width() const { return kind == LSQ_SEARCH_PQ ? m * d : d; }      // elements of a query row that are read
     int id_sub() const { return kind == LSQ_SEARCH_LSQ ? 0 : 1 - id_base; }    // ids leave as (the record's id field 1 .. n) - id_sub
     size_t base_elem() const { return base_u8 ? 1 : sizeof(float); }
@@ -388,7 +396,44 @@ int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **st, const uint8_t *codes, c
 // device pointers: K [m*256][d], q_scan [nq][d], q_coarse [nq][ldc], dists / ids [nq][nn] (ADC distances, original ids 1-based, (+inf, 0) past the probed
 // rows).  adc: the index's scan state (the coarse search and the selection run on it); coarse: how the coarse search runs (the context's hooks)
 int lsq_ivf_search(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *K, float *dists, int *ids, const float *q_scan,
-                   const float *q_coarse, int64_t ldc, int nq, int nprobe, int nn, int flags, const lsq_search_opts &coarse, int timed);
+                   const float *q_coarse, int64_t ldc, int nq, int nprobe, int nn, int flags, const lsq_search_opts &coarse, int timed,
+                   const struct lsq_filter_view *flt = nullptr);      // flt (lsq_filter.hip): its layout-order bits restrict the answer to the allowed rows
+
+// ---- row filters on a resident index (lsq_filter.hip): the set of allowed rows as the scans read it ---------------------------------------------------
+struct lsq_filter_state;
+void lsq_filter_free(lsq_filter_state *st);
+// what a scan is handed: bits [ceil(n/32)] (bits at and past n are zero), rows [allowed] ascending; the layout-order bitmap lbits (bit p = allowed(ids[p]))
+// and the exclusive prefix lpre [ceil(n/32) + 1] of its words' popcounts, both null without inverted lists.  A view is valid until the next set / clear
+struct lsq_filter_view {
+    const uint32_t *bits = nullptr;
+    const int *rows = nullptr;
+    int64_t allowed = 0;
+    const uint32_t *lbits = nullptr;
+    const int *lpre = nullptr;
+    int force = 0;                           // LSQ_FILTER_FORCE_DENSE / LSQ_FILTER_FORCE_COMPACT / 0
+};
+// desc as lsq_index_set_filter takes it (never null here).  A refusal leaves *st as it was.  The call waits for the device (the count comes back)
+int lsq_filter_set(hipStream_t s, lsq_filter_state **st, int64_t n, const lsq_filter_desc *desc);
+void lsq_filter_clear(lsq_filter_state *st);
+bool lsq_filter_active(const lsq_filter_state *st);
+lsq_filter_view lsq_filter_get(const lsq_filter_state *st);
+// the layout-order bitmap and its prefix for the inverted layout ids [n] / off [nlist + 1] (device); nlist = 0 drops them.  Called whenever either changed
+int lsq_filter_layout(hipStream_t s, lsq_filter_state *st, const int *ids, const int *off, int64_t n, int nlist);
+void lsq_filter_note_road(lsq_filter_state *st, int road);      // the last search / knn call's road: 0 unfiltered, 1 dense, 2 compact
+void lsq_filter_get_info(const lsq_filter_state *st, int64_t n, lsq_filter_info *out);
+// The default road (measured: profiles/filter.jsonl).  Compact when allowed <= crossover = n / 2: walking |A| rows through one indirection beat
+// reading n rows and their bits at every measured fraction from 1/2 down -- except in one band.  Up to LSQ_SELECT_SMALL_N rows the selection writes and
+// sorts EVERY distance (lsq_adc.hip: ADC_SMALL_N), which costs sort_over_scan times a dense scan's step per (query, row): where the dense road would still
+// be on the thresholded selection (n above the limit), the compact road pays only when allowed * sort_over_scan <= n.  sort_over_scan: 64 for the ADC scan
+// (measured 70 at m = 8), 8 for exact k-NN (6.8 at d = 128, f32) -- one shape each, rounded
+constexpr int64_t LSQ_SELECT_SMALL_N = 65536;
+inline int64_t lsq_filter_crossover(int64_t n) { return n / 2; }
+inline bool lsq_filter_compact_by_default(int64_t n, int64_t allowed, int64_t sort_over_scan) {
+    if (allowed > lsq_filter_crossover(n)) return false;
+    return !(n > LSQ_SELECT_SMALL_N && allowed <= LSQ_SELECT_SMALL_N && allowed * sort_over_scan > n);
+}
+// the inverted layout a filter's layout bits are built over: ids [n] original row of every position, off [nlist + 1]; both null without lists
+void lsq_ivf_layout(const lsq_ivf_state *st, const int **ids, const int **off);
 
 // ---- rows grouped by list (lsq_ivf.hip): the sort behind lsq_index_set_lists and lsq_partition_update.  Scratch of whoever groups: the staged list of a
 // host-buffer call, the keys (list << 32 | row) before and after the sort, the sort's workspace and the range check's counter ------------------------------

@@ -30,6 +30,7 @@
 
 #include <algorithm>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "lsq_internal.h"
@@ -84,18 +85,26 @@ __global__ void ivf_layout_packed_kernel(const uint64_t *__restrict__ sorted, in
 
 // ---- the plan of a query: pos[q][r] = rows of its probed lists of rank < r (pos[q][nprobe] = all of them); plan[q] = {rows, rows of the head, lists of
 // the head}.  The head: the first lists, in rank order, that together hold at least nn rows; all of them when there are fewer than nn rows
+// Under a row filter (lbits / lpre: its bitmap in layout order and the prefix of its words' popcounts, lsq_filter.hip; null: none) the head is chosen on
+// ALLOWED rows -- its nn-th record is then a finite, exact bound whenever the probed lists hold nn allowed rows -- while every position and total stays
+// that of the full lengths
+__device__ inline int ivf_allowed_before(const uint32_t *__restrict__ lbits, const int *__restrict__ lpre, int p) {
+    const int w = p >> 5, b = p & 31;                                // (b == 0: the word is not read -- p may be n, one past the last word)
+    return lpre[w] + (b ? __popc(lbits[w] & ((1u << b) - 1u)) : 0);
+}
 __global__ void ivf_plan_kernel(const int *__restrict__ probe, const int *__restrict__ off, int nq, int nprobe, int nn, int *__restrict__ pos,
-                                int *__restrict__ plan) {
+                                int *__restrict__ plan, const uint32_t *__restrict__ lbits, const int *__restrict__ lpre) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nq) return;
     const int *pr = probe + (int64_t)q * nprobe;
     int *ps = pos + (int64_t)q * (nprobe + 1);
-    int sum = 0, head_n = nprobe, head_rows = -1;
+    int sum = 0, head_n = nprobe, head_rows = -1, allowed = 0;
     for (int r = 0; r < nprobe; ++r) {
         const int l = pr[r];
         ps[r] = sum;
         sum += off[l + 1] - off[l];                                  // disjoint lists: at most n < 2^31 in all
-        if (head_rows < 0 && sum >= nn) { head_n = r + 1; head_rows = sum; }
+        if (lpre) allowed += ivf_allowed_before(lbits, lpre, off[l + 1]) - ivf_allowed_before(lbits, lpre, off[l]);
+        if (head_rows < 0 && (lpre ? allowed : sum) >= nn) { head_n = r + 1; head_rows = sum; }
     }
     ps[nprobe] = sum;
     plan[3 * (int64_t)q] = sum;
@@ -115,12 +124,20 @@ struct IvfScan {
     unsigned *count;                                 // [slot]: records in the segment
     uint64_t *out;                                   // [slot][cap]
 };
+// what a FILTERED scan is launched with: the same, and a row filter's bitmap in layout order.  A type of its own: the unfiltered kernels keep their
+// argument block, byte for byte
+struct IvfScanF : IvfScan {
+    const uint32_t *lbits;
+};
 
 // PART 0: every record of every probed list; 1: the same of the head's lists; 2: the records with !(dist > tau) of the lists after the head, appended.
 // MW > 0: rows of 4 MW bytes, read as dwords (an allocation of the index's own: aligned); MW = 0: any m, byte reads.  PACKED: a row is its m code bytes and
 // then its norm byte (m = 4 MW - 1 on the dword loader), a.norms is the norm table of 256 floats, staged beside the query's table.
-template <int MW, int PART, bool PACKED = false>
-__global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const IvfScan a) {
+// FILT (a row filter): bit p of a.lbits says whether layout row p is allowed -- read where the row's code is read, no gather through a.ids.  PART 0 / 1: a
+// filtered row writes the padding record into its slot (the segment is sized by list lengths: every slot up to `have` is written); PART 2 appends allowed
+// rows only.  FILT = false: the kernel as it was.
+template <int MW, int PART, bool PACKED = false, bool FILT = false>
+__global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const std::conditional_t<FILT, IvfScanF, IvfScan> a) {
     __shared__ float lut[LSQ_MAX_M * LSQ_H + (PACKED ? 256 : 0)];    // the query's table: m KiB used; PACKED: the norm table behind all 16 KiB
     constexpr int NT = PACKED ? 4 * MW - 1 : 4 * MW;                 // bytes of a dword-loaded row that index tables
     const int t = threadIdx.x, slot = blockIdx.x;
@@ -175,12 +192,17 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const IvfScan a) 
             if constexpr (!PACKED) nrm = a.norms[row];
             float dist = acc + nrm;
             if (a.add) dist = dist + cq;                             // one more rounded add
-            const uint64_t rec = ((uint64_t)lsq_adc_key(dist) << a.idbits) | (uint64_t)(uint32_t)(a.ids[row] + 1);      // the ORIGINAL id, 1-based
+            uint64_t rec = ((uint64_t)lsq_adc_key(dist) << a.idbits) | (uint64_t)(uint32_t)(a.ids[row] + 1);      // the ORIGINAL id, 1-based
+            bool allowed = true;
+            if constexpr (FILT) {
+                allowed = ((a.lbits[row >> 5] >> (row & 31)) & 1u) != 0;
+                if (!allowed) rec = (1ull << (32 + a.idbits)) | ((uint64_t)lsq_adc_key(__builtin_inff()) << a.idbits);
+            }
             if (PART != 2) {
                 const int at = p0 + i;                               // < the query's rows <= cap: the host sized cap by them
                 if (live && at < a.cap) out[at] = rec;
             } else {
-                const bool hit = live && !(dist > tau);              // a NaN on either side is kept
+                const bool hit = live && allowed && !(dist > tau);   // a NaN on either side is kept
                 const unsigned long long mask = __ballot(hit);
                 if (mask) {                                          // (wave-uniform) one atomic for the wave's records of this step
                     const int leader = __ffsll((long long)mask) - 1;
@@ -196,7 +218,10 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const IvfScan a) 
 }
 
 template <int PART>
-int launch_scan(hipStream_t s, const IvfScan &a, int nqb, bool packed) {
+int launch_scan(hipStream_t s, const IvfScan &a, int nqb, bool packed, const uint32_t *lbits) {
+    IvfScanF f;
+    static_cast<IvfScan &>(f) = a;
+    f.lbits = lbits;
     const int rowb = packed ? a.m + 1 : a.m;                         // bytes of a row: the dword loader takes whole words
     // enough blocks to fill the chip a few times over when the queries are few; a block's lists share one staged table
     int splits = (2048 + nqb - 1) / nqb;
@@ -206,7 +231,10 @@ int launch_scan(hipStream_t s, const IvfScan &a, int nqb, bool packed) {
     const dim3 grid((unsigned)nqb, (unsigned)splits), block(IVF_THREADS);
 #define IVF_LAUNCH(MWV)                                                                                 \
     do {                                                                                                \
-        if (packed) hipLaunchKernelGGL((ivf_scan_kernel<MWV, PART, true>), grid, block, 0, s, a);       \
+        if (lbits) {                                                                                    \
+            if (packed) hipLaunchKernelGGL((ivf_scan_kernel<MWV, PART, true, true>), grid, block, 0, s, f);    \
+            else hipLaunchKernelGGL((ivf_scan_kernel<MWV, PART, false, true>), grid, block, 0, s, f);          \
+        } else if (packed) hipLaunchKernelGGL((ivf_scan_kernel<MWV, PART, true>), grid, block, 0, s, a);       \
         else hipLaunchKernelGGL((ivf_scan_kernel<MWV, PART, false>), grid, block, 0, s, a);             \
     } while (0)
     if (rowb == 4) IVF_LAUNCH(1);
@@ -283,6 +311,12 @@ void lsq_ivf_free(lsq_ivf_state *st) {
 
 int lsq_ivf_nlist(const lsq_ivf_state *st) { return st ? st->nlist : 0; }
 
+void lsq_ivf_layout(const lsq_ivf_state *st, const int **ids, const int **off) {
+    const bool have = st && st->nlist > 0;
+    *ids = have ? st->ids.as<int>() : nullptr;
+    *off = have ? st->off.as<int>() : nullptr;
+}
+
 void lsq_ivf_get_info(const lsq_ivf_state *st, lsq_ivf_info *out) { *out = st ? st->info : lsq_ivf_info{}; }
 
 int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **pst, const uint8_t *codes, const float *norms, int packed, int64_t n, int m, int d,
@@ -330,6 +364,7 @@ struct Chunk {                       // one run of queries whose plan fits the s
     float *dists; int *ids;
     int nq, nprobe, nn, flags, idbits;
     bool timed;
+    const uint32_t *lbits; const int *lpre;      // a row filter in layout order (lsq_filter.hip), or null
 };
 
 // one batch on either road: slots 0 .. nqb - 1 are queries q0 .. (or qsel[.]).  thresholded: h_fail[slot] = 1 for a query whose segment overflowed
@@ -357,21 +392,21 @@ int run_batch(const Chunk &c, const int *qsel, int q0, int nqb, int cap, bool th
     const bool packed = st->packed != 0;
     // records: (padding bit, distance key, original id + 1), sorted on 33 + idbits bits; the hand-out drops the bit: (+inf, 0) for padding
     if (!thresholded) {
-        LSQ_TRY(launch_scan<0>(s, a, nqb, packed));
+        LSQ_TRY(launch_scan<0>(s, a, nqb, packed, c.lbits));
         LSQ_TRY(st->clock.mark(s));
         LSQ_TRY(lsq_adc_select(c.adc, s, st->rec_a.as<uint64_t>(), st->rec_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(), nullptr, qsel, q0,
                                nqb, cap, c.nn, c.dists, c.ids, c.idbits, 33 + c.idbits, 0));
     } else {
         LSQ_TRY(st->head_d.ensure(sizeof(float) * (size_t)nqb * c.nn));
         LSQ_TRY(st->head_i.ensure(sizeof(int) * (size_t)nqb * c.nn));
-        LSQ_TRY(launch_scan<1>(s, a, nqb, packed));
+        LSQ_TRY(launch_scan<1>(s, a, nqb, packed, c.lbits));
         LSQ_TRY(st->clock.mark(s));
         // the head, sorted: head_d[slot][nn - 1] is tau
         LSQ_TRY(lsq_adc_select(c.adc, s, st->rec_a.as<uint64_t>(), st->rec_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(), nullptr, nullptr, 0,
                                nqb, cap, c.nn, st->head_d.as<float>(), st->head_i.as<int>(), c.idbits, 33 + c.idbits, 0));
         LSQ_TRY(st->clock.mark(s));
         a.tau = st->head_d.as<float>();
-        LSQ_TRY(launch_scan<2>(s, a, nqb, packed));
+        LSQ_TRY(launch_scan<2>(s, a, nqb, packed, c.lbits));
         LSQ_TRY(st->clock.mark(s));
         LSQ_TRY(lsq_adc_select(c.adc, s, st->rec_a.as<uint64_t>(), st->rec_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(), st->fail.as<int>(),
                                qsel, q0, nqb, cap, c.nn, c.dists, c.ids, c.idbits, 33 + c.idbits, 0));
@@ -416,7 +451,7 @@ int run_chunk(Chunk &c, const float *q_coarse, int64_t ldc, const lsq_search_opt
     LSQ_TRY(st->pos.ensure(sizeof(int) * (size_t)nq * ((size_t)nprobe + 1)));
     LSQ_TRY(st->plan.ensure(sizeof(int) * 3 * (size_t)nq));
     hipLaunchKernelGGL(ivf_plan_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, st->ci.as<int>(), st->off.as<int>(), nq, nprobe, nn,
-                       st->pos.as<int>(), st->plan.as<int>());
+                       st->pos.as<int>(), st->plan.as<int>(), c.lbits, c.lpre);
     LSQ_HIP(hipGetLastError());
     std::vector<int> plan(3 * (size_t)nq);
     LSQ_HIP(hipMemcpyAsync(plan.data(), st->plan.p, sizeof(int) * plan.size(), hipMemcpyDeviceToHost, s));
@@ -469,7 +504,8 @@ int run_chunk(Chunk &c, const float *q_coarse, int64_t ldc, const lsq_search_opt
 }  // namespace
 
 int lsq_ivf_search(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *K, float *dists, int *ids, const float *q_scan,
-                   const float *q_coarse, int64_t ldc, int nq, int nprobe, int nn, int flags, const lsq_search_opts &coarse, int timed) {
+                   const float *q_coarse, int64_t ldc, int nq, int nprobe, int nn, int flags, const lsq_search_opts &coarse, int timed,
+                   const lsq_filter_view *flt) {
     st->info = lsq_ivf_info{};
     // chunks of queries whose per-(query, probe) words stay below 2^28
     int64_t qc = (int64_t)(1u << 28) / ((int64_t)nprobe + 1);
@@ -481,6 +517,7 @@ int lsq_ivf_search(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const 
         c.in = lsq_search_input{};
         c.in.kind = LSQ_SEARCH_LSQ; c.in.Q = q_scan + c0 * st->d; c.in.qstride = st->d; c.in.K = K; c.in.n = (int)st->n; c.in.m = st->m; c.in.d = st->d;
         c.dists = dists + c0 * nn; c.ids = ids + c0 * nn;
+        c.lbits = flt ? flt->lbits : nullptr; c.lpre = flt ? flt->lpre : nullptr;
         LSQ_TRY(run_chunk(c, q_coarse + c0 * ldc, ldc, coarse));
     }
     st->info.queries = nq;

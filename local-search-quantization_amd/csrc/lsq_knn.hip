@@ -47,11 +47,31 @@ constexpr int KNN_RL = KNN_RT * KNN_KD / KNN_THREADS;      // staged row floats 
 // MODE 0: append (key << idbits | i + 1) of every distance <= tau to the query's candidate list;  MODE 1: write every record of the strided subset
 // i = s * stride, s < ns, to out[slot * ns + s];  MODE 2: the same subset, keys only (u32).  Query of slot: qsel[slot] (fallback) or q0 + slot.
 // TX / TQ: the element types of the rows and of the queries, float or uint8_t (widened where the staged registers are stored to LDS).
-template <int MODE, typename TX, typename TQ>
+// FILT (a row filter, lsq_filter.hip; adc_scan_kernel's rule): frows == nullptr -- dense: walk position p IS the row and its bit of fbits decides whether it
+// leaves a record; frows != nullptr -- compact: position p < nlive is row frows[p], positions past nlive (MODE 1's padding up to nn) are staged as zeros.
+// A row that is filtered or padding does not pass (MODE 0), or leaves as the record of an id outside the base (MODE 1) / the key 0xffffffff (MODE 2).
+// FILT = false: the kernel as it was, the three arguments unread.
+template <bool FILT>
+__device__ inline int64_t knn_filter_row(int64_t p, const uint32_t *__restrict__ fbits, const int *__restrict__ frows, int nlive, bool &allowed) {
+    if constexpr (!FILT) { allowed = true; return p; }
+    if (frows) {
+        allowed = p < nlive;
+        return allowed ? (int64_t)frows[p] : 0;                      // (row 0 exists; a padding position never dereferences it)
+    }
+    allowed = ((fbits[p >> 5] >> (p & 31)) & 1u) != 0;
+    return p;
+}
+// the record of an id outside the base (lsq_rerank.hip): the bit above the key, the key of +inf, id field 0
+__device__ inline uint64_t knn_outside_record(int idbits) {
+    return (1ull << (32 + idbits)) | ((uint64_t)lsq_adc_key(__builtin_inff()) << idbits);
+}
+
+template <int MODE, typename TX, typename TQ, bool FILT = false>
 __global__ __launch_bounds__(KNN_THREADS) void knn_scan_kernel(const TX *__restrict__ X, int ldb, const TQ *__restrict__ Q, int ldq,
                                                                const int *__restrict__ qsel, int q0, int nqb, int d, int stride, int total,
                                                                int per_block, const uint32_t *__restrict__ tau, unsigned *__restrict__ count,
-                                                               int cap, uint64_t *__restrict__ out, int idbits) {
+                                                               int cap, uint64_t *__restrict__ out, int idbits,
+                                                               const uint32_t *__restrict__ fbits, const int *__restrict__ frows, int nlive) {
     __shared__ __attribute__((aligned(16))) float qs[KNN_KD * KNN_QP];
     __shared__ __attribute__((aligned(16))) float xs[KNN_KD * KNN_RP];
     const int t = threadIdx.x, tile = blockIdx.x;
@@ -75,7 +95,13 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_scan_kernel(const TX *__restr
 #pragma unroll
         for (int j = 0; j < KNN_RL; ++j) {
             const int s = r0 + sr + 16 * j;
-            xreg[j] = (s < last && k < d) ? X[(int64_t)s * stride * ldb + k] : (TX)0;
+            if constexpr (FILT) {
+                bool have = false;
+                const int64_t row = s < last ? knn_filter_row<FILT>((int64_t)s * stride, fbits, frows, nlive, have) : 0;
+                xreg[j] = (s < last && (have || !frows) && k < d) ? X[row * ldb + k] : (TX)0;
+            } else {
+                xreg[j] = (s < last && k < d) ? X[(int64_t)s * stride * ldb + k] : (TX)0;
+            }
         }
     };
     // compute roles: query group qg owns queries 4 qg .. 4 qg + 3 and 64 + 4 qg .. 64 + 4 qg + 3, row group rg rows 4 rg .. 4 rg + 3
@@ -124,7 +150,9 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_scan_kernel(const TX *__restr
         for (int j = 0; j < 4; ++j) {
             const int s = r0 + 4 * rg + j;
             if (s >= last) continue;
-            const int64_t i = (int64_t)s * stride;
+            bool allowed = true;
+            const int64_t i = knn_filter_row<FILT>((int64_t)s * stride, fbits, frows, nlive, allowed);
+            if (FILT && MODE == 0 && !allowed) continue;
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 const int p = c >> 1;
@@ -132,8 +160,9 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_scan_kernel(const TX *__restr
                 const int slot = tile * KNN_QT + (c < 4 ? 4 * qg + c : 64 + 4 * qg + c - 4);
                 if (slot >= nqb) continue;
                 if (MODE == 0 && dv > tf[c]) continue;              // emit unless dist > tau (a NaN on either side emits)
-                const uint32_t key = lsq_adc_key(dv);
-                const uint64_t rec = ((uint64_t)key << idbits) | (uint64_t)(i + 1);      // 1-based in the record; the gather hands out 0-based ids
+                uint32_t key = lsq_adc_key(dv);
+                uint64_t rec = ((uint64_t)key << idbits) | (uint64_t)(i + 1);      // 1-based in the record; the gather hands out 0-based ids
+                if (FILT && !allowed) { key = 0xffffffffu; rec = knn_outside_record(idbits); }
                 if (MODE == 1) {
                     out[(int64_t)slot * total + s] = rec;
                 } else if (MODE == 2) {
@@ -185,12 +214,13 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_norms_u8_kernel(const uint8_t
 // knn_scan_kernel's tile, modes, records, grid and per_block rule on PACKED dwords: LDS holds [dword][row] with the same padded pitches, KNN_KD dwords
 // (64 dimensions) staged per pass; per dword step a lane issues three ds_read_b128 and 32 v_dot4_u32_u8.  xn [n] / qn [queries]: the squared norms
 // (knn_norms_u8_kernel).  D = xn + qn - 2 acc is exact and (float)D is the chain's result (d <= 258: the top of this file).
-template <int MODE>
+template <int MODE, bool FILT = false>
 __global__ __launch_bounds__(KNN_THREADS) void knn_scan_u8_kernel(const uint8_t *__restrict__ X, int ldb, int vecx, const uint8_t *__restrict__ Q, int ldq,
                                                                   int vecq, const uint32_t *__restrict__ xn, const uint32_t *__restrict__ qn,
                                                                   const int *__restrict__ qsel, int q0, int nqb, int d, int stride, int total,
                                                                   int per_block, const uint32_t *__restrict__ tau, unsigned *__restrict__ count,
-                                                                  int cap, uint64_t *__restrict__ out, int idbits) {
+                                                                  int cap, uint64_t *__restrict__ out, int idbits,
+                                                                  const uint32_t *__restrict__ fbits, const int *__restrict__ frows, int nlive) {
     __shared__ __attribute__((aligned(16))) uint32_t qs[KNN_KD * KNN_QP];
     __shared__ __attribute__((aligned(16))) uint32_t xs[KNN_KD * KNN_RP];
     const int t = threadIdx.x, tile = blockIdx.x;
@@ -213,7 +243,13 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_scan_u8_kernel(const uint8_t 
 #pragma unroll
         for (int j = 0; j < KNN_RL; ++j) {
             const int s = r0 + sr + 16 * j;
-            xreg[j] = s < last ? knn_ld_packed(X + (int64_t)s * stride * ldb, w, d, vecx != 0) : 0u;              // rows >= last: zero
+            if constexpr (FILT) {
+                bool have = false;
+                const int64_t row = s < last ? knn_filter_row<FILT>((int64_t)s * stride, fbits, frows, nlive, have) : 0;
+                xreg[j] = (s < last && (have || !frows)) ? knn_ld_packed(X + row * ldb, w, d, vecx != 0) : 0u;
+            } else {
+                xreg[j] = s < last ? knn_ld_packed(X + (int64_t)s * stride * ldb, w, d, vecx != 0) : 0u;              // rows >= last: zero
+            }
         }
     };
     // compute roles: those of knn_scan_kernel
@@ -261,7 +297,9 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_scan_u8_kernel(const uint8_t 
         for (int j = 0; j < 4; ++j) {
             const int s = r0 + 4 * rg + j;
             if (s >= last) continue;
-            const int64_t i = (int64_t)s * stride;
+            bool allowed = true;
+            const int64_t i = knn_filter_row<FILT>((int64_t)s * stride, fbits, frows, nlive, allowed);
+            if (FILT && MODE == 0 && !allowed) continue;
             const uint32_t nx = xn[i];
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
@@ -269,8 +307,9 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_scan_u8_kernel(const uint8_t 
                 const int slot = tile * KNN_QT + (c < 4 ? 4 * qg + c : 64 + 4 * qg + c - 4);
                 if (slot >= nqb) continue;
                 if (MODE == 0 && dv > tf[c]) continue;
-                const uint32_t key = lsq_adc_key(dv);
-                const uint64_t rec = ((uint64_t)key << idbits) | (uint64_t)(i + 1);
+                uint32_t key = lsq_adc_key(dv);
+                uint64_t rec = ((uint64_t)key << idbits) | (uint64_t)(i + 1);
+                if (FILT && !allowed) { key = 0xffffffffu; rec = knn_outside_record(idbits); }
                 if (MODE == 1) {
                     out[(int64_t)slot * total + s] = rec;
                 } else if (MODE == 2) {
@@ -285,17 +324,22 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_scan_u8_kernel(const uint8_t 
 }
 
 // the three modes of one producer; K(MODE) names the instantiation
+#define KNN_LAUNCH_FILT(K, F, ...)                                                                  \
+    do {                                                                                            \
+        if (mode == 0) hipLaunchKernelGGL((K(0, F)), grid, block, 0, s, __VA_ARGS__);                \
+        else if (mode == 1) hipLaunchKernelGGL((K(1, F)), grid, block, 0, s, __VA_ARGS__);           \
+        else hipLaunchKernelGGL((K(2, F)), grid, block, 0, s, __VA_ARGS__);                          \
+    } while (0)
 #define KNN_LAUNCH_MODES(K, ...)                                                                    \
     do {                                                                                            \
-        if (mode == 0) hipLaunchKernelGGL((K(0)), grid, block, 0, s, __VA_ARGS__);                   \
-        else if (mode == 1) hipLaunchKernelGGL((K(1)), grid, block, 0, s, __VA_ARGS__);              \
-        else hipLaunchKernelGGL((K(2)), grid, block, 0, s, __VA_ARGS__);                             \
+        if (in.filtered()) KNN_LAUNCH_FILT(K, true, __VA_ARGS__, in.filter_bits, in.filter_rows, in.filter_count);   \
+        else KNN_LAUNCH_FILT(K, false, __VA_ARGS__, nullptr, nullptr, 0);                            \
     } while (0)
-#define KNN_INT(M) knn_scan_u8_kernel<M>
-#define KNN_FF(M) knn_scan_kernel<M, float, float>
-#define KNN_BF(M) knn_scan_kernel<M, uint8_t, float>
-#define KNN_FB(M) knn_scan_kernel<M, float, uint8_t>
-#define KNN_BB(M) knn_scan_kernel<M, uint8_t, uint8_t>
+#define KNN_INT(M, F) knn_scan_u8_kernel<M, F>
+#define KNN_FF(M, F) knn_scan_kernel<M, float, float, F>
+#define KNN_BF(M, F) knn_scan_kernel<M, uint8_t, float, F>
+#define KNN_FB(M, F) knn_scan_kernel<M, float, uint8_t, F>
+#define KNN_BB(M, F) knn_scan_kernel<M, uint8_t, uint8_t, F>
 
 }  // namespace
 
@@ -313,7 +357,7 @@ int lsq_knn_launch_norms_u8(hipStream_t s, const uint8_t *X, int64_t ld, int n, 
 // chosen by what `in` says its rows and queries are made of: the integer road when it carries norms, a widened instantiation otherwise.
 int lsq_knn_launch_scan(hipStream_t s, int mode, const lsq_search_input &in, const int *qsel, int q0, int nqb, int stride, int ns, const uint32_t *tau,
                         unsigned *count, int cap, uint64_t *out, int idbits) {
-    const int n = in.n, d = in.d, ldb = in.bstride, ldq = in.qstride;
+    const int n = in.rows_walked(), d = in.d, ldb = in.bstride, ldq = in.qstride;      // compact road of a filter: the allowed rows
     const int tiles = (nqb + KNN_QT - 1) / KNN_QT;
     const int total = mode == 0 ? n : ns;
     if (tiles == 0 || total == 0) return LSQ_OK;

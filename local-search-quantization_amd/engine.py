@@ -833,6 +833,56 @@ class Index(_Handle):
         """the selection statistics of the last search()'s scan: Engine.linscan_stats' fields, this call's figures alone"""
         return self._info("lsq_index_get_scan_stats", _lib.LinscanStats)
 
+    _ROADS = {None: 0, "dense": _lib.FILTER_FORCE_DENSE, "compact": _lib.FILTER_FORCE_COMPACT}
+
+    def set_filter(self, mask=None, bits=None, ids=None, deny=False, id_base=0, road=None):
+        """Restrict search, search_ivf and knn to a set of allowed rows, given in exactly one of three forms (numpy on an Engine.index, torch tensors on an
+        Engine.index_dev): mask (n,) bool / uint8, non-zero = set; bits (ceil(n/32),) uint32 (a device tensor may be int32: the same bits), bit i & 31 of
+        word i >> 5 = row i; ids (count,) int32 row ids in id_base, duplicates legal.  deny: the set rows are the EXCLUDED ones.  Each call then returns what
+        it would return for every candidate row with the rows outside the set removed, truncated to k and padded with (+inf, id_base - 1); rerank ignores the
+        filter.  The index keeps a copy.  road: None (by the number of allowed rows), "dense" or "compact" -- test hooks, the same results
+        [lsq_index_set_filter]"""
+        given = [(name, a) for name, a in (("mask", mask), ("bits", bits), ("ids", ids)) if a is not None]
+        if len(given) != 1:
+            raise ValueError("set_filter needs exactly one of mask, bits, ids (got %s)" % (", ".join(nm for nm, _ in given) or "none"))
+        if road not in self._ROADS:
+            raise ValueError("road must be None, 'dense' or 'compact', got %r" % (road,))
+        side, (name, a) = self._side, given[0]
+        desc = _lib.FilterDesc()
+        if name == "mask":
+            if _dtname(a) not in ("bool", "uint8"):
+                raise TypeError("mask must be bool or uint8, got %s" % (_dtname(a) or type(a).__name__))
+            if side.dev:
+                import torch
+                a = side.take(a.view(torch.uint8) if _dtname(a) == "bool" and getattr(a, "is_cuda", False) else a, _U8, "mask")
+            else:
+                a = np.ascontiguousarray(a).view(_U8)
+            _shapes(("mask", a, (self.n,)))
+            desc.form = _lib.FILTER_BYTES
+        elif name == "bits":
+            if side.dev:
+                a = side.take(a, np.int32 if _dtname(a) == "int32" else np.uint32, "bits")
+            else:
+                a = np.ascontiguousarray(a, dtype=np.uint32)
+            _shapes(("bits", a, ((self.n + 31) // 32,)))
+            desc.form = _lib.FILTER_BITS
+        else:
+            a = side.take(a, _I32, "ids")
+            _shapes(("ids", a, (None,)))
+            desc.form, desc.count, desc.id_base = _lib.FILTER_IDS, int(a.shape[0]), int(id_base)
+        desc.data = side.ptr(a) if a.shape[0] > 0 else side.ptr(side.new((1,), _I32, a))      # an empty id list still names an array
+        desc.flags, desc.on_device = (_lib.FILTER_DENY if deny else 0) | self._ROADS[road], int(self._dev)
+        self._eng._call(side, "lsq_index_set_filter", C.byref(desc), h=self._h)
+
+    def clear_filter(self):
+        """drop the filter: every call answers over all rows again, bit for bit as before   [lsq_index_set_filter(NULL)]"""
+        self._eng._call(self._side, "lsq_index_set_filter", None, h=self._h)
+
+    def filter_info(self):
+        """active, n, allowed, lists / lists_without_allowed (0 without inverted lists), road of the last search / search_ivf / knn call (0 unfiltered,
+        1 dense, 2 compact), crossover_rows (compact by default when allowed <= this, outside the band the header describes)"""
+        return self._info("lsq_index_get_filter_info", _lib.FilterInfo)
+
 
 # -- the beam-search encoder (made by Engine.encoder / Engine.encoder_dev) ------------------------
 

@@ -30,6 +30,10 @@ residuals' code_norms and the index is packed.  Its recall curve is printed as a
 norm byte: the 64-bit code at m = 7) is searched through linscan_lsq_bytes, and its ids and distances are checked to equal the float-norm run's.  The
 reference widens the byte to a float per vector one line before its scan (demo_lsq_gpu.jl:57-60).
 
+--filter FRACTION: a seeded random mask that allows about FRACTION of the base rows is laid over a resident index (Index.set_filter); the ADC search -- and,
+where given, the --ivf and --rerank variants -- then answer over the allowed rows alone, and their recall is taken against Index.knn under the SAME mask on
+the same resident base rows.  The reference has no such search.
+
 needs $LSQ_DATA_DIR/sift/{sift_learn,sift_base,sift_query}.fvecs and sift_groundtruth.ivecs (TEXMEX layout).  The file's ground truth
 describes the full 10^6-vector base only: for a prefix of it (nread_base < 10^6) and for the stand-in, the ground truth is exact k-NN of the base
 actually encoded, computed on the device (knn_exact).  The data is
@@ -184,6 +188,15 @@ def main():
         except (ValueError, AssertionError, IndexError):
             raise SystemExit("--ivf takes NLIST:NPROBE with 1 <= NPROBE <= NLIST")
         del argv[at:at + 2]
+    fraction = None
+    if "--filter" in argv:
+        at = argv.index("--filter")
+        try:
+            fraction = float(argv[at + 1])
+            assert 0.0 < fraction <= 1.0
+        except (ValueError, AssertionError, IndexError):
+            raise SystemExit("--filter takes a FRACTION in (0, 1]")
+        del argv[at:at + 2]
     args = [a for a in argv if a not in ("--resident", "--bvecs", "--norm-byte", "--residual")]
     resident, bvecs, norm_byte, residual = "--resident" in argv, "--bvecs" in argv, "--norm-byte" in argv, "--residual" in argv
     if residual and not ivf:
@@ -283,6 +296,43 @@ def main():
         for i in (1, 2, 5, 10, 20, 50, 100, 200, 500, 1000):
             if i <= knn:
                 print("%7d   %.4f       %.4f" % (i, rec[i - 1], irec[i - 1]) + ("       %.4f" % rrec_ivf[i - 1] if residual else ""))
+    if fraction is not None:
+        filtered_recall(fraction, name, x_base, x_query, B_base, C, db_norms, m, knn, shortlist, ivf)
+
+
+def filtered_recall(fraction, name, x_base, x_query, B_base, C, db_norms, m, knn, shortlist, ivf):
+    """--filter: the searches over the allowed rows of a seeded random mask, their recall against Index.knn under the same mask"""
+    n = x_base.shape[1]
+    allowed = np.random.default_rng(0).random(n) < fraction
+    rows = np.ascontiguousarray(x_base.T)                                    # f32, or the un-widened bytes of --bvecs
+    Q = np.ascontiguousarray(x_query.T.astype(np.float32))
+    with lsq.Engine(0) as eng, eng.index((B_base - 1).astype(np.uint8).T, np.ascontiguousarray(np.hstack(C).T), db_norms, m, base=rows) as ix:
+        ix.set_filter(mask=allowed)
+        info = ix.filter_info()
+        keep = max(1, min(knn, info["allowed"]))
+        _, truth = ix.knn(Q, 1, id_base=1)                                   # the ground truth: exact k-NN over the allowed rows
+        gt = truth[:, 0].astype(np.uint32)
+        curves = {}
+        _, ids = ix.search(Q, keep)
+        curves["ADC"] = lsq.eval_recall(gt, np.ascontiguousarray(ids.T).astype(np.uint32), keep)
+        road = {0: "unfiltered", 1: "dense", 2: "compact"}[ix.filter_info()["road"]]
+        if shortlist:
+            L = min(max(shortlist, keep), n)
+            _, ids = ix.search(Q, keep, shortlist=L, Q_exact=Q)
+            curves["re-ranked %d" % L] = lsq.eval_recall(gt, np.ascontiguousarray(ids.T).astype(np.uint32), keep)
+        if ivf:
+            nlist = min(ivf[0], n)
+            nprobe = min(ivf[1], nlist)
+            cent, assign = lsq.train_coarse(np.asarray(rows, dtype=np.float32), nlist, niter=10, seed=0, engine=eng)
+            ix.set_lists(cent, assign)
+            _, ids = ix.search_ivf(Q, keep, nprobe)
+            curves["IVF %d:%d" % (nlist, nprobe)] = lsq.eval_recall(gt, np.ascontiguousarray(ids.T).astype(np.uint32), keep)
+    print("Filtered search (%d of %d rows allowed, %s road; ground truth: exact k-NN under the same mask)" % (info["allowed"], n, road))
+    print("     r@   " + "   ".join("%-12s" % k for k in curves))
+    for i in (1, 2, 5, 10, 20, 50, 100, 200, 500, 1000):
+        if i <= keep:
+            print("%7d   " % i + "   ".join("%-12.4f" % c[i - 1] for c in curves.values()))
+    print("%s: filtered recall@1 = %.4f at fraction %g" % (name, curves["ADC"][0], fraction))
 
 
 if __name__ == "__main__":
