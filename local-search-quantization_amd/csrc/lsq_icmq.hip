@@ -34,15 +34,29 @@
 
 #include "lsq_q16.h"
 #include "lsq_xload.h"
+// How the slice loop's waves set their scheduling priority (walk_slices): the shipped library's setting -- four levels by quartile of the wave's own items --
+// is a constant there, so no branch on it survives; the tuning build reads the variants below from a knob.
+#ifndef LSQ_WALKQ_PRIO_SHIPPED
+#define LSQ_WALKQ_PRIO_SHIPPED 1
+#endif
 #ifdef LSQ_TUNING
 __device__ unsigned long long *g_walkq_dbg = nullptr;      // [launch slot][block][16] timestamps (tools only)
 __device__ unsigned int g_walkq_dbg_slot = 0;
 __device__ unsigned long long *g_walkq_dbg_cur = nullptr;   // block 0's record of the running launch (for q16_refine's stamps)
 __device__ unsigned long long *g_walkq_blk = nullptr;       // [block][2] start / end clock of every block of the latest launch (tools only: launch tails)
-#define LSQ_WALKQ_DBG_WORDS (24 + 2 * 65)                  // 24 phase stamps of the launch's last node, then start clock / active count of every node + the end clock
+#define LSQ_WALKQ_DBG_WAVE0 (24 + 2 * 65)                  // first of 16 words: the clock at which wave w of block 0 finished its items of slice step 4 (last node)
+#define LSQ_WALKQ_DBG_WORDS (LSQ_WALKQ_DBG_WAVE0 + 16)     // 24 phase stamps of the launch's last node, then start clock / active count of every node + the end clock, then the 16 wave stamps
 #define DBG_STAMP(k) do { if (dbgp && threadIdx.x == 0) dbgp[k] = wall_clock64(); } while (0)
+#define DBG_WAVE_STAMP(w) do { if (dbgp && (threadIdx.x & 63) == 0) dbgp[LSQ_WALKQ_DBG_WAVE0 + (w)] = wall_clock64(); } while (0)
+// Tuning build: which waves are served first inside a slice step is a knob (LSQ_WALKQ_PRIO, handed to the kernel in bits 16 .. of `abl`):
+//   bits 0-1  priority by progress in the item loop: 0 none, 1 four levels by quartile of the wave's items, 2 two levels (behind / past the half-way point),
+//             3 the four levels set before every item instead of once per DEPTH items
+//   bit 2     the fixed phases (staging stores, decide, refinement) at the top level
+//   bit 3     the waves that hold one item more than the others are the LAST r waves instead of the first r
+#define LSQ_WALKQ_PRIO_MODE(abl) ((abl) >> 16)
 #else
 #define DBG_STAMP(k) do {} while (0)
+#define LSQ_WALKQ_PRIO_MODE(abl) LSQ_WALKQ_PRIO_SHIPPED
 #endif
 
 namespace {
@@ -538,6 +552,7 @@ __global__ __launch_bounds__(WalkqRot<M>::NT) __attribute__((amdgpu_waves_per_eu
     if (g_walkq_blk && threadIdx.x == 0) g_walkq_blk[2 * blockIdx.x] = wall_clock64();
 #endif
     if ((uint32_t)(uintptr_t)(lds_char *)lds_walkq != 0u) __builtin_trap();      // the rotated placement addresses LDS by number: the segment must start at 0
+    if (LSQ_WALKQ_PRIO_MODE(abl) & 4) __builtin_amdgcn_s_setprio(3);
     u32x4 *tab = lds_walkq;
     constexpr bool HOLE = RT::HOLE;                                                              // bestA in the free slot of the table's second group (m <= 8)
     constexpr bool LHOLE = RT::LHOLE;                                                            // the active list in the free slot of the second group (m > 8)
@@ -655,14 +670,38 @@ __global__ __launch_bounds__(WalkqRot<M>::NT) __attribute__((amdgpu_waves_per_eu
             }
         };
         prefetch_tab(0);
-        const int ipw = (wave * VPW < nact) ? (nact - wave * VPW + step - 1) / step : 0;
+        // Which wave owns which items never changes a result (integer level sums, ds_min keys per vector); wslot only names the wave's place in the
+        // round-robin hand-out, and with it which waves hold the one item more when nact is no multiple of a round.
+        const int prio = LSQ_WALKQ_PRIO_MODE(abl);           // uniform (a kernel argument; a constant in the shipped library)
+        const int wslot = (prio & 8) ? NW - 1 - wave : wave;
+        const int ipw = (wslot * VPW < nact) ? (nact - wslot * VPW + step - 1) / step : 0;
+        // priority by progress: a wave that is behind in its own items is served before one that is ahead (s_setprio: scalar, no LDS, no VGPR).
+        // The thresholds are scalars, so that the branches around the s_setprio are scalar branches (the instruction ignores EXEC).
+        const int ipw_u = (prio & 3) ? __builtin_amdgcn_readfirstlane(ipw) : 0;
+        const int h1 = (ipw_u + 3) >> 2, h2 = (ipw_u + 1) >> 1, h3 = (3 * ipw_u + 3) >> 2;
+        auto item_prio = [&](int t) {
+            const int tu = __builtin_amdgcn_readfirstlane(t);
+            if ((prio & 3) == 1 || (prio & 3) == 3) {
+                if (tu < h1) __builtin_amdgcn_s_setprio(3);
+                else if (tu < h2) __builtin_amdgcn_s_setprio(2);
+                else if (tu < h3) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+            } else if ((prio & 3) == 2) {
+                if (tu < h2) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+            } else if (prio & 4) __builtin_amdgcn_s_setprio(0);
+        };
+        auto fixed_prio = [&]() {                            // back to the level of the fixed phases before the barrier
+            if (prio & 4) __builtin_amdgcn_s_setprio(3);
+            else if (prio & 3) __builtin_amdgcn_s_setprio(0);
+        };
         int ls = 0, lit = 0;
         // the slice plane of the level stream the NEXT loaded item belongs to: advanced when the wave's items wrap around (uniform, scalar)
         const char *ub = reinterpret_cast<const char *>(Uqj + lo * RT::SLQ);
         const char *const rb = reinterpret_cast<const char *>(rec + lo * CS);
         const int64_t plane_bytes = n * (int64_t)(RT::SLQ * 2);
         auto load_next = [&](Item &it) {
-            int ci = wave * VPW + lit * step + v;
+            int ci = wslot * VPW + lit * step + v;
             ci = ci < nact ? ci : nact - 1;
             uint32_t li = (uint32_t)ci;
             if (!dense) {
@@ -814,18 +853,21 @@ __global__ __launch_bounds__(WalkqRot<M>::NT) __attribute__((amdgpu_waves_per_eu
 #ifdef LSQ_TUNING
             if (slice == 4) DBG_STAMP(21);
 #endif
-            int c0 = wave * VPW, t = 0;
+            int c0 = wslot * VPW, t = 0;
             auto run = [&](auto P_) {
                 constexpr int PH = decltype(P_)::value;
                 for (; t + RT::DEPTH <= ipw; t += RT::DEPTH) {
+                    if ((prio & 3) != 3) item_prio(t);           // once per DEPTH items
 #pragma unroll
                     for (int e = 0; e < RT::DEPTH; ++e) {
+                        if ((prio & 3) == 3) item_prio(t + e);
                         compute(buf[(PH + e) % RT::DEPTH], slice, c0); load_next(buf[(PH + e) % RT::DEPTH]); c0 += step;
                     }
                 }
 #pragma unroll
                 for (int e = 0; e < RT::DEPTH - 1; ++e)
                     if (t < ipw) {
+                        item_prio(t);
                         compute(buf[(PH + e) % RT::DEPTH], slice, c0); load_next(buf[(PH + e) % RT::DEPTH]); c0 += step;
                         ++t; phase = (PH + e + 1) % RT::DEPTH;
                     }
@@ -838,8 +880,9 @@ __global__ __launch_bounds__(WalkqRot<M>::NT) __attribute__((amdgpu_waves_per_eu
             };
             try_phase(std::integral_constant<int, 0>{}); try_phase(std::integral_constant<int, 1>{});
             try_phase(std::integral_constant<int, 2>{}); try_phase(std::integral_constant<int, 3>{});
+            fixed_prio();
 #ifdef LSQ_TUNING
-            if (slice == 4) DBG_STAMP(22);
+            if (slice == 4) { DBG_STAMP(22); DBG_WAVE_STAMP(wave); }
 #endif
         }
         __syncthreads();
@@ -1077,7 +1120,7 @@ __global__ __launch_bounds__(WalkqRot<M>::NT) __attribute__((amdgpu_waves_per_eu
 }  // namespace
 
 #ifdef LSQ_TUNING
-// tools only: device buffer of 4096 x LSQ_WALKQ_DBG_WORDS (154) u64 that block 0 of every icm_walkq_kernel launch fills with phase timestamps (wall_clock64)
+// tools only: device buffer of 4096 x LSQ_WALKQ_DBG_WORDS (170) u64 that block 0 of every icm_walkq_kernel launch fills with phase timestamps (wall_clock64)
 extern "C" __attribute__((visibility("default"))) int lsq_tuning_set_walkq_debug(void *buf) {
     unsigned zero = 0;
     LSQ_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_walkq_dbg), &buf, sizeof(buf)));
@@ -1221,7 +1264,8 @@ static int launch_walkq_t(hipStream_t s, const float *U, const uint16_t *Uq, con
     if (static_lds != 0) { lsq_set_error("icm_walkq_kernel<%d>: %d bytes of static LDS in a kernel that addresses LDS from 0", M, static_lds); return LSQ_EHIP; }
     const unsigned grid = (unsigned)(npass < NBLK ? npass : NBLK);
     hipLaunchKernelGGL((icm_walkq_kernel<M>), dim3(grid), dim3(RT::NT), LDS_BYTES, s, U, Uq, Tq, T, rec, valid, n, nodes, per_pass, skip,
-                       direct_max, active_total, skip ? ref_rec : nullptr, skip ? ref_valid : nullptr, P, lsq_walk_slice_width(M), qflag, LSQ_KNOB("LSQ_Q16_ABL", 0), gate);
+                       direct_max, active_total, skip ? ref_rec : nullptr, skip ? ref_valid : nullptr, P, lsq_walk_slice_width(M), qflag,
+                       LSQ_KNOB("LSQ_Q16_ABL", 0) | (LSQ_KNOB("LSQ_WALKQ_PRIO", LSQ_WALKQ_PRIO_SHIPPED) << 16), gate);
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }

@@ -1,5 +1,6 @@
 """tools/walkq_phases.py [n] -- run ON THE GPU BOX with the tuning library.  Phase timestamps (wall_clock64, 100 MHz) of block 0 of
-every icm_walkq_kernel launch (option per_node = 1: one launch per node update): compaction / per-slice walk / decide / redo."""
+every icm_walkq_kernel launch (option per_node = 1: one launch per node update): compaction / per-slice walk / decide / redo; then, per node update,
+when each of block 0's 16 waves finished its items of slice step 4 (LSQ_WALKQ_PRIO=0: without the waves' priorities; unset: as shipped)."""
 import ctypes as C, importlib, sys
 import numpy as np, torch
 sys.path.insert(0, '.')
@@ -8,7 +9,8 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 per_node = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 m = int(sys.argv[4]) if len(sys.argv) > 4 else 8
 L = lsq._lib.load(tuning=True)
-W = 24 + 2 * 65
+WAVE0 = 24 + 2 * 65                  # LSQ_WALKQ_DBG_WAVE0: the clock at which each of block 0's 16 waves finished its items of slice step 4
+W = WAVE0 + 16
 buf = torch.zeros((4096, W), dtype=torch.int64, device="cuda")
 L.lsq_tuning_set_walkq_debug.restype = C.c_int
 L.lsq_tuning_set_walkq_debug.argtypes = [C.c_void_p]
@@ -39,6 +41,24 @@ for li, r in enumerate(rows[:72]):
     s4 = [(int(r[k]) - int(r[7])) / 100.0 if r[k] else -1 for k in (20, 21, 22)]
     print("%3d nact %5d amb %3d total %7.1f us | compact %5.1f (scan @%4.1f barrier @%4.1f list @%4.1f) pre %5.1f | slices %s (slice 4: stores+barrier @%4.1f prefetch issued @%4.1f items @%4.1f) | decide %5.1f refine+ %5.1f" %
           (li, r[14], r[15], (ts[-1] - ts[0]) / 100.0, d[0], cs[0], cs[1], cs[2], d[1], " ".join("%5.1f" % x for x in d[2:11]), s4[0], s4[1], s4[2], d[11], d[12]))
+
+# slice step 4 of every node update, wave by wave: when each of block 0's 16 waves had finished its items (us after the step's first barrier), the spread
+# (last - first) among the four waves of a SIMD (waves w, w + 4, w + 8, w + 12) and the step's length (to the next step's first barrier)
+print("== slice step 4 by wave: finish of the wave's items (us), spread per SIMD, step length; LSQ_WALKQ_PRIO=%s" % __import__("os").environ.get("LSQ_WALKQ_PRIO", "unset"))
+spreads = []
+for li, r in enumerate(rows[:72]):
+    if r[13] == 0 or r[7] == 0 or not all(r[WAVE0:WAVE0 + 16]):
+        continue
+    fin = [(int(r[WAVE0 + w]) - int(r[7])) / 100.0 for w in range(16)]
+    sp = [max(fin[s::4]) - min(fin[s::4]) for s in range(4)]
+    steplen = (int(r[8]) - int(r[7])) / 100.0
+    spreads.append((int(r[14]), max(sp), steplen, max(fin), min(fin)))
+    print("%3d nact %5d | waves %s | spread per SIMD %s | first %5.1f last %5.1f step %5.1f" %
+          (li, r[14], " ".join("%5.1f" % x for x in fin), " ".join("%4.1f" % x for x in sp), min(fin), max(fin), steplen))
+for name, sel in (("dense (nact >= 3000)", [s for s in spreads if s[0] >= 3000]), ("sparse (nact < 1000)", [s for s in spreads if s[0] < 1000])):
+    if sel:
+        print("   %s: %d node updates, mean of the largest per-SIMD spread %.2f us, mean first finish %.2f, mean last finish %.2f, mean step %.2f us" %
+              (name, len(sel), np.mean([s[1] for s in sel]), np.mean([s[4] for s in sel]), np.mean([s[3] for s in sel]), np.mean([s[2] for s in sel])))
 
 if not per_node:
     # one launch per ILS iteration: block 0's clock at the start of every node update of its first pass (the production schedule)
