@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 2000
+#define LSQ_VERSION 2100
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -689,6 +689,53 @@ typedef struct lsq_filter_info {
 } lsq_filter_info;
 LSQ_API int lsq_index_set_filter(lsq_index *ix, const lsq_filter_desc *desc);   /* desc == NULL clears */
 LSQ_API int lsq_index_get_filter_info(lsq_index *ix, lsq_filter_info *out);
+
+/* ---- (3k) appending rows to the resident index: lsq_index_add, with the inverted lists merged on the device (csrc/lsq_grow.hip; since v2100) ---------------
+ * THE REFERENCE HAS NO COUNTERPART.  An index of n rows takes `count` more: they become rows n .. n + count - 1 (0-based).
+ *   contract     (Identity G) after a successful lsq_index_add EVERY CALL ON THE INDEX RETURNS, BIT FOR BIT, WHAT IT RETURNS ON AN INDEX FRESHLY BUILT over
+ *                the concatenated arrays, given lsq_index_set_lists with the same centroids and the concatenated list_of_row, and a filter that is the old
+ *                allowed set plus every new row: distances, ids, tie order, NaN order, padding records, and the deterministic statistics (the layout is
+ *                the same array for array).  Codebooks, centroids and cbnorms are the index's own and do not change.
+ *   filter       new rows are ALLOWED.  A caller with a predicate sets its filter again; lsq_index_set_filter afterwards sees the new n.
+ *   ownership    an index created with on_device = 1 BORROWS codes, norms and base.  The first add with count > 0 (or the first reserve) ADOPTS them: one
+ *                device-to-device copy into owned storage with capacity; when that call has returned the caller's arrays are never read again.
+ *                Codebooks stay borrowed.  The arrays of lsq_index_add_desc are read once, in stream order, before the call returns (on_device = 1
+ *                too).  The owned base keeps the index's pitch; added rows of another pitch are re-pitched on the way in.
+ *   capacity     growth is geometric, FACTOR 3/2: an add that does not fit re-allocates to max(n + count, capacity + capacity / 2) rows.  Re-allocation
+ *                keeps the contents (allocate, copy, swap, free): THE TRANSIENT PEAK IS OLD PLUS NEW.  lsq_index_reserve(rows) makes the adds up to `rows`
+ *                rows free of RE-ALLOCATION OF THE INDEX'S OWNED STORAGE -- the flat arrays and both halves of the layout: what `reallocations` counts.  Scratch
+ *                is not covered: the keys and workspace of the sort, the filter's spare buffers and a packed index's staging are sized at the first add
+ *                that needs them (a few MB at 10^6 rows) and kept.  The inverted layout is kept in two capacity-sized halves (the merge is written out of place into the spare
+ *                one): with lists, the layout's bytes are resident twice from the first add on.
+ *   atomicity    validate first, commit last.  A REFUSED call (LSQ_EINVAL) leaves the index exactly as it was: every answer, every info struct, n, lists and
+ *                filter.  The list ids and the norm bytes of the new rows are range-checked on the device, by the one kernel that reads them, before any
+ *                is used as an offset and before anything of the index is written.  A call that fails later (LSQ_ENOMEM, LSQ_EHIP) leaves every answer,
+ *                n, the lists and the filter as they were -- nothing is committed before the last step --, but the storage may already have moved:
+ *                lsq_index_growth_info.capacity_rows and .adopted may have grown (adopted storage holds the same rows; `reallocations` is not advanced).
+ * LSQ_EINVAL (nothing launched unless noted): a null handle or desc; count < 0; n + count > 2^31 - 2; a required array missing; dbnorms given to a packed
+ * index or norm_codes to a plain one; list_of_row given when no lists are set; ldb < d; an f32 base that is not 4-byte aligned; a list_of_row entry outside
+ * [0, nlist) (device); a norm byte >= ncb (device); reserve(rows < n).  count == 0 is a legal no-op and adopts nothing. */
+typedef struct lsq_index_add_desc {
+    int64_t count;               /* rows appended: they become rows n .. n + count - 1 (0-based) */
+    const uint8_t *codes;        /* [count][m] uint8 0-based        -- required iff the index holds codes */
+    const float   *dbnorms;      /* [count]                         -- required iff plain index with codes */
+    const uint8_t *norm_codes;   /* [count] uint8 0-based           -- required iff packed index */
+    const void    *base;         /* [count][ldb] f32 or uint8, the index's own type -- required iff the index holds base rows */
+    int ldb;                     /* pitch of `base` in elements, >= d; need not equal the index's pitch */
+    const int32_t *list_of_row;  /* [count] 0-based list ids        -- required iff lists are set */
+    int on_device;               /* 0 host arrays, 1 device arrays -- independent of how the index was created */
+} lsq_index_add_desc;
+typedef struct lsq_index_growth_info {
+    int64_t n, capacity_rows;    /* rows held; rows the owned storage holds without another allocation (n while the arrays are borrowed) */
+    int64_t adds, rows_added;    /* successful lsq_index_add calls with count > 0 since creation; their rows */
+    int64_t reallocations;       /* times owned storage was re-allocated by add / reserve (one per call that re-allocated) */
+    int64_t adopted;             /* 1 once borrowed arrays have been copied into owned storage */
+    int64_t merged_rows;         /* last add: positions of the inverted layout written (0 without lists) */
+    double append_ms, merge_ms, filter_ms;   /* last add, with option "profile" = 1 */
+} lsq_index_growth_info;
+LSQ_API int lsq_index_add(lsq_index *ix, const lsq_index_add_desc *desc);
+LSQ_API int lsq_index_reserve(lsq_index *ix, int64_t rows);       /* capacity for at least `rows` rows in total */
+LSQ_API int lsq_index_get_growth_info(lsq_index *ix, lsq_index_growth_info *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

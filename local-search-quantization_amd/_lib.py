@@ -92,6 +92,16 @@ class FilterInfo(_Struct):
                 ("road", C.c_int64), ("crossover_rows", C.c_int64)]
 
 
+class IndexAddDesc(_Struct):
+    _fields_ = [("count", C.c_int64), ("codes", C.c_void_p), ("dbnorms", C.c_void_p), ("norm_codes", C.c_void_p), ("base", C.c_void_p), ("ldb", C.c_int),
+                ("list_of_row", C.c_void_p), ("on_device", C.c_int)]
+
+
+class IndexGrowthInfo(_Struct):
+    _fields_ = [("n", C.c_int64), ("capacity_rows", C.c_int64), ("adds", C.c_int64), ("rows_added", C.c_int64), ("reallocations", C.c_int64),
+                ("adopted", C.c_int64), ("merged_rows", C.c_int64), ("append_ms", C.c_double), ("merge_ms", C.c_double), ("filter_ms", C.c_double)]
+
+
 FILTER_BITS, FILTER_BYTES, FILTER_IDS = 0, 1, 2
 FILTER_DENY, FILTER_FORCE_DENSE, FILTER_FORCE_COMPACT = 1, 2, 4
 
@@ -208,6 +218,10 @@ SIGNATURES = {
     "lsq_index_get_scan_stats": (_i, [_vp, C.POINTER(LinscanStats)]),
     "lsq_index_set_filter": (_i, [_vp, C.POINTER(FilterDesc)]),
     "lsq_index_get_filter_info": (_i, [_vp, C.POINTER(FilterInfo)]),
+    # appending rows to the index (since v2100)
+    "lsq_index_add": (_i, [_vp, C.POINTER(IndexAddDesc)]),
+    "lsq_index_reserve": (_i, [_vp, _i64]),
+    "lsq_index_get_growth_info": (_i, [_vp, C.POINTER(IndexGrowthInfo)]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),
@@ -249,6 +263,8 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
+MIN_VERSION = 2100      # the version floor: the oldest library that exports every symbol above with these structs
+
 _libs = {}
 
 
@@ -274,6 +290,8 @@ def load(tuning=False):
             fn = getattr(lib, name)       # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args
+        if lib.lsq_version() < MIN_VERSION:
+            raise RuntimeError("%s is version %d, this binding needs %d or later: rebuild it" % (path, lib.lsq_version(), MIN_VERSION))
         _libs[path] = lib
     return _libs[path]
 

@@ -561,6 +561,10 @@ struct lsq_index {
     lsq_index_stats stats{};
     lsq_index_knn_info knn{};
     lsq_filter_state *filter = nullptr;                // the row filter (lsq_filter.hip): null until lsq_index_set_filter; owned copies of THIS index
+    int64_t cap_rows = 0;                              // lsq_index_add: rows the flat arrays hold without another allocation (n until the first add / reserve)
+    lsq_index_growth_info grow{};
+    DevBuf g_codes, g_nc, g_rows;                      // lsq_index_add on a packed index: staging of host codes and norm bytes, the new rows packed
+    PhaseClock<4> gclock;                              // an add's append, merge and filter phases
 };
 
 // the filter as a scan over all rows takes it: nothing without one; else the compact road -- the ascending list of allowed rows -- where the measured rule
@@ -581,8 +585,9 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     (void)hipSetDevice(ix->ctx->device);
     (void)hipStreamSynchronize(ix->ctx->stream);
     DevBuf *bufs[] = {&ix->own_codes, &ix->own_K, &ix->own_norms, &ix->own_base, &ix->rec_a, &ix->rec_b, &ix->seg, &ix->counter, &ix->short_d, &ix->short_i,
-                      &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q, &ix->s_qcoarse};
+                      &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q, &ix->s_qcoarse, &ix->g_codes, &ix->g_nc, &ix->g_rows};
     for (DevBuf *b : bufs) b->release();
+    ix->gclock.release();
     lsq_adc_free(ix->adc);
     lsq_ivf_free(ix->ivf);
     lsq_filter_free(ix->filter);
@@ -633,6 +638,7 @@ extern "C" int lsq_index_create(lsq_index **out, lsq_ctx *c, const lsq_index_des
     if (rc == LSQ_OK) rc = ix->counter.ensure(sizeof(unsigned long long));
     if (rc == LSQ_OK && hipStreamSynchronize(c->stream) != hipSuccess) { lsq_set_error("lsq_index_create: the upload failed"); rc = LSQ_EHIP; }
     if (rc != LSQ_OK) { (void)lsq_index_destroy(ix); return rc; }
+    ix->cap_rows = ix->n;
     *out = ix;
     return LSQ_OK;
 }
@@ -692,6 +698,7 @@ extern "C" int lsq_index_create_packed(lsq_index **out, lsq_ctx *c, const lsq_in
     if (rc != LSQ_OK && rc != LSQ_EINVAL) (void)hipStreamSynchronize(s);      // nothing in flight reads the staging when it goes
     s_codes.release(); s_nc.release();
     if (rc != LSQ_OK) { (void)lsq_index_destroy(ix); return rc; }
+    ix->cap_rows = ix->n;
     *out = ix;
     return LSQ_OK;
 }
@@ -971,6 +978,10 @@ extern "C" int lsq_index_set_lists(lsq_index *ix, const lsq_ivf_desc *desc) {
     if (!desc->centroids || !desc->list_of_row) { lsq_set_error("lsq_index_set_lists: null pointer"); return LSQ_EINVAL; }
     LSQ_TRY(use_device(ix->ctx));
     LSQ_TRY(lsq_ivf_set_lists(ix->ctx->stream, &ix->ivf, ix->codes, ix->norms, ix->packed, ix->n, ix->m, ix->d, desc));
+    if (ix->cap_rows > ix->n) {                       // an index with capacity (lsq_index_reserve / _add): the layout's halves get it too
+        int moved = 0;
+        LSQ_TRY(lsq_ivf_reserve(ix->ctx->stream, ix->ivf, ix->cap_rows, &moved));
+    }
     return index_filter_layout(ix);                   // a filter's layout-order bits follow the new lists
 }
 
@@ -1020,6 +1031,148 @@ extern "C" int lsq_index_set_filter(lsq_index *ix, const lsq_filter_desc *desc) 
 extern "C" int lsq_index_get_filter_info(lsq_index *ix, lsq_filter_info *out) {
     if (!ix || !out) { lsq_set_error("lsq_index_get_filter_info: null argument"); return LSQ_EINVAL; }
     lsq_filter_get_info(ix->filter, ix->n, out);
+    return LSQ_OK;
+}
+
+// ---- appending rows (lsq_grow.hip): the flat arrays in owned storage with capacity, the inverted layout merged, the filter extended ---------
+// What depends on n, and what an add does about it: ix->n (committed last); the flat arrays (appended past n, invisible until then); lsq_ivf_state's
+// layout, off and n (merged into the spare half, swapped at the commit); lsq_filter_state's bits / prefix / rows / n (rebuilt beside the one in force,
+// swapped) and its layout-order bits (lsq_filter_layout again); the scan state's sample and record buffers, stage two's records, nrm_x and every staging
+// buffer are sized from the call's own n at every call (DevBuf::ensure) and hold nothing across calls; idbits and the selection's road are computed per call
+static size_t index_row_bytes(const lsq_index *ix) { return (size_t)(ix->packed ? ix->m + 1 : ix->m); }
+static size_t index_base_elem(const lsq_index *ix) { return ix->base_u8 ? 1 : sizeof(float); }
+static bool index_borrows(const lsq_index *ix) {
+    return (ix->codes && ix->codes != ix->own_codes.p) || (ix->codes && !ix->packed && ix->norms != ix->own_norms.p) || (ix->base && ix->base != ix->own_base.p);
+}
+
+// the flat arrays in owned storage that holds `cap` rows: borrowed ones are adopted (copied once), owned ones that are too small move with their contents
+static int index_capacity(lsq_index *ix, int64_t cap, int *moved) {
+    hipStream_t s = ix->ctx->stream;
+    const size_t n = (size_t)ix->n, rowb = index_row_bytes(ix);
+    const bool borrowed = index_borrows(ix);
+    const size_t before[3] = {ix->own_codes.cap, ix->own_norms.cap, ix->own_base.cap};
+    if (ix->codes) {
+        LSQ_TRY(lsq_devbuf_grow(s, ix->own_codes, (size_t)cap * rowb + 16, n * rowb, ix->codes));      // 16 bytes of slack past the last row, never read
+        ix->codes = ix->own_codes.as<uint8_t>();
+        if (!ix->packed) {
+            LSQ_TRY(lsq_devbuf_grow(s, ix->own_norms, sizeof(float) * (size_t)cap, sizeof(float) * n, ix->norms));
+            ix->norms = ix->own_norms.as<float>();
+        }
+    }
+    if (ix->base) {
+        const size_t e = index_base_elem(ix);
+        LSQ_TRY(lsq_devbuf_grow(s, ix->own_base, (size_t)cap * (size_t)ix->ldb * e, ((n - 1) * (size_t)ix->ldb + (size_t)ix->d) * e, ix->base));
+        ix->base = ix->own_base.p;
+    }
+    if (before[0] != ix->own_codes.cap || before[1] != ix->own_norms.cap || before[2] != ix->own_base.cap) *moved = 1;
+    if (borrowed) ix->grow.adopted = 1;
+    if (cap > ix->cap_rows) ix->cap_rows = cap;
+    return LSQ_OK;
+}
+
+static lsq_grow_shape index_shape(const lsq_index *ix) {
+    lsq_grow_shape sh{};
+    sh.n = ix->n; sh.d = ix->d; sh.has_codes = ix->codes != nullptr; sh.has_base = ix->base != nullptr; sh.packed = ix->packed; sh.base_u8 = ix->base_u8;
+    sh.has_lists = lsq_ivf_nlist(ix->ivf) > 0;
+    return sh;
+}
+
+extern "C" int lsq_index_reserve(lsq_index *ix, int64_t rows) {
+    if (!ix) { lsq_set_error("lsq_index_reserve: null index"); return LSQ_EINVAL; }
+    if (const char *why = lsq_grow_reserve_refusal(ix->n, rows)) { lsq_set_error("lsq_index_reserve: %s (rows=%lld n=%lld)", why, (long long)rows, (long long)ix->n); return LSQ_EINVAL; }
+    LSQ_TRY(use_device(ix->ctx));
+    const int64_t cap = rows > ix->cap_rows ? rows : ix->cap_rows;
+    int moved = 0;
+    LSQ_TRY(index_capacity(ix, cap, &moved));
+    LSQ_TRY(lsq_ivf_reserve(ix->ctx->stream, ix->ivf, cap, &moved));
+    LSQ_HIP(hipStreamSynchronize(ix->ctx->stream));
+    ix->grow.reallocations += moved;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_add(lsq_index *ix, const lsq_index_add_desc *desc) {
+    const char *fn = "lsq_index_add";
+    if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
+    if (const char *why = lsq_grow_add_refusal(index_shape(ix), desc)) { lsq_set_error("%s: %s", fn, why); return LSQ_EINVAL; }
+    if (desc->count == 0) return LSQ_OK;
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    const int64_t n = ix->n, count = desc->count;
+    const size_t rowb = index_row_bytes(ix), m = (size_t)ix->m;
+    const bool lists = lsq_ivf_nlist(ix->ivf) > 0;
+    const hipMemcpyKind kind = desc->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    // 1. the range checks, on the device, by the kernels that read the entries: nothing of the index has been written when either refuses
+    if (lists) {
+        unsigned bad = 0;
+        LSQ_TRY(lsq_ivf_add_check(s, ix->ivf, desc->list_of_row, desc->on_device, count, &bad));
+        if (bad) { lsq_set_error("%s: %u entries of list_of_row lie outside [0, %d)", fn, bad, lsq_ivf_nlist(ix->ivf)); return LSQ_EINVAL; }
+    }
+    if (ix->packed) {                                 // the new rows through create_packed's interleave and norm-byte check, into scratch
+        const uint8_t *dcodes = desc->codes, *dnc = desc->norm_codes;
+        if (!desc->on_device) {
+            LSQ_TRY(ix->g_codes.ensure((size_t)count * m));
+            LSQ_TRY(ix->g_nc.ensure((size_t)count));
+            LSQ_HIP(hipMemcpyAsync(ix->g_codes.p, desc->codes, (size_t)count * m, hipMemcpyHostToDevice, s));
+            LSQ_HIP(hipMemcpyAsync(ix->g_nc.p, desc->norm_codes, (size_t)count, hipMemcpyHostToDevice, s));
+            dcodes = ix->g_codes.as<uint8_t>(); dnc = ix->g_nc.as<uint8_t>();
+        }
+        LSQ_TRY(ix->g_rows.ensure((size_t)count * rowb));
+        LSQ_HIP(hipMemsetAsync(ix->counter.p, 0, sizeof(unsigned long long), s));
+        LSQ_TRY(lsq_adc_launch_pack(s, dcodes, dnc, count, ix->m, ix->ncb, ix->g_rows.as<uint8_t>(), ix->counter.as<unsigned>()));
+        unsigned bad = 0;
+        LSQ_HIP(hipMemcpyAsync(&bad, ix->counter.p, sizeof(bad), hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipStreamSynchronize(s));
+        if (bad) { lsq_set_error("%s: %u norm bytes lie outside [0, %d)", fn, bad, ix->ncb); return LSQ_EINVAL; }
+    }
+    // 2. capacity (and adoption): the answers do not depend on where the arrays lie
+    int moved = 0;
+    const int64_t cap = n + count > ix->cap_rows ? lsq_grow_capacity(ix->cap_rows, n + count) : ix->cap_rows;
+    LSQ_TRY(index_capacity(ix, cap, &moved));
+    LSQ_TRY(ix->gclock.begin(c->profile != 0));
+    LSQ_TRY(ix->gclock.mark(s));
+    // 3. the flat arrays, past row n: not part of the index until n moves
+    if (ix->codes) {
+        uint8_t *at = ix->own_codes.as<uint8_t>() + (size_t)n * rowb;
+        if (ix->packed) LSQ_HIP(hipMemcpyAsync(at, ix->g_rows.p, (size_t)count * rowb, hipMemcpyDeviceToDevice, s));
+        else {
+            LSQ_HIP(hipMemcpyAsync(at, desc->codes, (size_t)count * rowb, kind, s));
+            LSQ_HIP(hipMemcpyAsync(ix->own_norms.as<float>() + n, desc->dbnorms, sizeof(float) * (size_t)count, kind, s));
+        }
+    }
+    if (ix->base) {                                   // re-pitched on the way in: the owned base keeps the index's pitch
+        const size_t e = index_base_elem(ix);
+        LSQ_HIP(hipMemcpy2DAsync(static_cast<char *>(ix->own_base.p) + (size_t)n * (size_t)ix->ldb * e, (size_t)ix->ldb * e, desc->base, (size_t)desc->ldb * e,
+                                 (size_t)ix->d * e, (size_t)count, kind, s));
+    }
+    LSQ_TRY(ix->gclock.mark(s));
+    // 4. the inverted layout, merged into its spare half; 5. the filter, rebuilt beside the one in force
+    if (lists)
+        LSQ_TRY(lsq_ivf_add_merge(s, ix->ivf, ix->own_codes.as<uint8_t>() + (size_t)n * rowb, ix->packed ? nullptr : ix->own_norms.as<float>() + n, count, cap, &moved));
+    LSQ_TRY(ix->gclock.mark(s));
+    LSQ_TRY(lsq_filter_grow(s, ix->filter, n + count));
+    LSQ_TRY(ix->gclock.mark(s));
+    LSQ_HIP(hipStreamSynchronize(s));
+    // 6. the commit
+    if (lists) lsq_ivf_add_commit(ix->ivf, count);
+    lsq_filter_grow_commit(ix->filter, n + count);
+    ix->n = n + count;
+    float ms[3];
+    LSQ_TRY(ix->gclock.read(ms));
+    ix->grow.adds += 1; ix->grow.rows_added += count; ix->grow.reallocations += moved;
+    ix->grow.merged_rows = lists ? n + count : 0;
+    ix->grow.append_ms = ms[0]; ix->grow.merge_ms = ms[1]; ix->grow.filter_ms = ms[2];
+    if (lists && moved) {                             // the half that was the layout is smaller than the new one: sized now (nothing to keep), so that the
+        int again = 0;                                // adds that fit the capacity allocate nothing.  A failure here costs nothing: the next add asks again
+        (void)lsq_ivf_reserve(s, ix->ivf, cap, &again);
+    }
+    return index_filter_layout(ix);                   // the filter's layout-order bits follow the new layout
+}
+
+extern "C" int lsq_index_get_growth_info(lsq_index *ix, lsq_index_growth_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_growth_info: null argument"); return LSQ_EINVAL; }
+    *out = ix->grow;
+    out->n = ix->n; out->capacity_rows = ix->cap_rows;
     return LSQ_OK;
 }
 

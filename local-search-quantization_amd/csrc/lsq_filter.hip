@@ -246,6 +246,36 @@ int lsq_filter_set(hipStream_t s, lsq_filter_state **pst, int64_t n, const lsq_f
     return LSQ_OK;
 }
 
+// ---- lsq_index_add's part: the filter of n_new rows = the one in force and every row from its n on.  Built in the spare buffers like a set call's (the
+// bitmap copied and extended: lsq_grow.hip; count, prefix and row list by the kernels above), in force at the commit
+int lsq_filter_grow(hipStream_t s, lsq_filter_state *st, int64_t n_new) {
+    if (!lsq_filter_active(st) || n_new <= st->n) return LSQ_OK;
+    const int64_t nwords = (n_new + 31) / 32, owords = (st->n + 31) / 32, allowed = st->allowed + (n_new - st->n);
+    FilterBufs &nb = st->next;
+    LSQ_TRY(nb.bits.ensure(sizeof(uint32_t) * (size_t)nwords));
+    LSQ_TRY(nb.pre.ensure(sizeof(int) * ((size_t)nwords + 1)));
+    LSQ_TRY(nb.rows.ensure(sizeof(int) * (size_t)allowed));
+    LSQ_TRY(st->cnt.ensure(sizeof(int) * ((size_t)nwords + 1)));
+    uint32_t *words = nb.bits.as<uint32_t>();
+    LSQ_HIP(hipMemsetAsync(words, 0, sizeof(uint32_t) * (size_t)nwords, s));
+    LSQ_HIP(hipMemcpyAsync(words, st->cur.bits.p, sizeof(uint32_t) * (size_t)owords, hipMemcpyDeviceToDevice, s));      // (its bits at and past the former n are zero)
+    LSQ_TRY(lsq_grow_launch_set_bits(s, words, st->n, n_new));
+    hipLaunchKernelGGL(flt_finish_kernel, dim3(blocks_for(nwords + 1)), dim3(FLT_THREADS), 0, s, words, n_new, nwords, 0, st->cnt.as<int>());
+    LSQ_HIP(hipGetLastError());
+    LSQ_TRY(exclusive_sum(s, st->tmp, st->cnt.as<int>(), nb.pre.as<int>(), nwords + 1));
+    hipLaunchKernelGGL(flt_compact_kernel, dim3(blocks_for(nwords)), dim3(FLT_THREADS), 0, s, words, nb.pre.as<int>(), nwords, nb.rows.as<int>());
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
+void lsq_filter_grow_commit(lsq_filter_state *st, int64_t n_new) {
+    if (!lsq_filter_active(st) || n_new <= st->n) return;
+    std::swap(st->cur, st->next);
+    st->allowed += n_new - st->n;
+    st->n = n_new;
+    st->nlist = 0; st->lists_without = 0;            // lsq_filter_layout rebuilds the layout-order bits
+}
+
 int lsq_filter_layout(hipStream_t s, lsq_filter_state *st, const int *ids, const int *off, int64_t n, int nlist) {
     if (!st) return LSQ_OK;
     st->nlist = 0; st->lists_without = 0;

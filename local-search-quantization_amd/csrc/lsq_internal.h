@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "../../include/lsq_mi355x.h"
+#include "lsq_grow_check.h"
 
 #define LSQ_H 256          // candidates per codebook: one wave x float4 per lane
 #define LSQ_MAX_M 16
@@ -447,6 +448,34 @@ int lsq_rows_keys(hipStream_t s, lsq_row_groups &g, const int32_t *list_of_row, 
 int lsq_rows_sort(hipStream_t s, lsq_row_groups &g, int64_t n, int nlist, const uint64_t **sorted);
 // off[l] = the first position of list l in the sorted keys, off[nlist] = n
 int lsq_rows_offsets(hipStream_t s, const uint64_t *sorted, int64_t n, int nlist, int *off);
+
+// ---- appending rows to a resident index (lsq_grow.hip: the new kernels; the states' own parts live beside the states, in lsq_ivf.hip and lsq_filter.hip) --
+// a buffer grown WITH its contents: allocate `bytes`, copy the first `keep` bytes device to device on s, swap, free the old block (hipFree waits for the
+// device, so the copy has landed).  The transient peak is old plus new.  A view, or a buffer already that large, is left alone
+int lsq_devbuf_grow(hipStream_t s, DevBuf &b, size_t bytes, size_t keep, const void *src = nullptr);      // src: where the contents are now (null: in b)
+// the merge of the inverted layout, out of place.  Old position q of list l moves to q + add_off[l]; the j-th sorted new key (list l, new row r = its low
+// word) lands at off[l + 1] + j with id n + r; noff[l] = off[l] + add_off[l].  src / dst: the layout's code rows (rowb bytes), norms (null: packed) and ids;
+// add_rows [count][rowb] / add_norms [count]: the new rows in the order they were appended.  dst buffers hold (n + count) rows and 16 bytes of slack
+struct lsq_grow_merge {
+    const uint8_t *src_codes; const float *src_norms; const int *src_ids; const int *off;
+    uint8_t *dst_codes; float *dst_norms; int *dst_ids; int *noff;
+    const int *add_off; const uint64_t *sorted; const uint8_t *add_rows; const float *add_norms;
+    int64_t n, count; int nlist, rowb;
+};
+int lsq_grow_launch_merge(hipStream_t s, const lsq_grow_merge &g);
+// words: bits n0 .. n1 - 1 set (the words past n0's own are whole: the caller zeroed or copied everything before n0, nothing after it matters before this)
+int lsq_grow_launch_set_bits(hipStream_t s, uint32_t *words, int64_t n0, int64_t n1);
+// the inverted lists' part (lsq_ivf.hip).  check: the keys of the `count` new rows and the range check (*bad: entries outside [0, nlist); the call waits) --
+// nothing of the layout is touched.  reserve: both halves of the layout hold cap_rows rows (*realloc = 1 when anything was allocated).  merge: the layout of
+// n + count rows written into the spare half (after check, same count); commit: the spare half becomes the layout
+int lsq_ivf_add_check(hipStream_t s, lsq_ivf_state *st, const int32_t *list_of_row, int on_device, int64_t count, unsigned *bad);
+int lsq_ivf_reserve(hipStream_t s, lsq_ivf_state *st, int64_t cap_rows, int *realloc);
+int lsq_ivf_add_merge(hipStream_t s, lsq_ivf_state *st, const uint8_t *add_rows, const float *add_norms, int64_t count, int64_t cap_rows, int *realloc);
+void lsq_ivf_add_commit(lsq_ivf_state *st, int64_t count);
+// the filter's part (lsq_filter.hip): the filter of n_new rows -- the former bits and every row from the former n on -- built beside the one in force;
+// commit puts it in force (the layout-order bits are then lsq_filter_layout's to rebuild).  Both do nothing without an active filter
+int lsq_filter_grow(hipStream_t s, lsq_filter_state *st, int64_t n_new);
+void lsq_filter_grow_commit(lsq_filter_state *st, int64_t n_new);
 
 // ---- what a handle that lives in a file of its own (lsq_partition.hip) needs of its context (lsq_api.hip): its device made current, the stream it is bound
 // to now, option "profile".  Nothing of the context is written ------------------------------------------------------------------------------------------

@@ -294,6 +294,7 @@ struct lsq_ivf_state {
     const float *table = nullptr;                                    // packed: the index's norm table (256 floats, alive as long as the index)
     DevBuf cent, codes, norms, ids, off;                             // the layout: centroids, and per position the code row (packed: with its norm byte), the norm (not packed), the original id
     lsq_row_groups rows;                                             // set_lists' scratch: the rows grouped by list
+    DevBuf alt_codes, alt_norms, alt_ids, alt_off, add_off;          // lsq_index_add: the spare half a merge is written into (it becomes the layout at the commit), the new rows' offsets
     DevBuf cd, ci, pos, plan, lut, rec_a, rec_b, seg, count, fail, qsel, head_d, head_i;      // the search's
     PhaseClock<6> clock;                                             // one batch: tables, scan, selection and, thresholded, the tail's scan and selection
     lsq_ivf_info info{};
@@ -301,7 +302,7 @@ struct lsq_ivf_state {
 
 void lsq_ivf_free(lsq_ivf_state *st) {
     if (!st) return;
-    DevBuf *all[] = {&st->cent, &st->codes, &st->norms, &st->ids, &st->off, &st->cd, &st->ci,
+    DevBuf *all[] = {&st->cent, &st->codes, &st->norms, &st->ids, &st->off, &st->alt_codes, &st->alt_norms, &st->alt_ids, &st->alt_off, &st->add_off, &st->cd, &st->ci,
                      &st->pos, &st->plan, &st->lut, &st->rec_a, &st->rec_b, &st->seg, &st->count, &st->fail, &st->qsel, &st->head_d, &st->head_i};
     for (DevBuf *b : all) b->release();
     st->rows.release();
@@ -352,6 +353,62 @@ int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **pst, const uint8_t *codes, 
     LSQ_HIP(hipStreamSynchronize(s));
     st->nlist = nlist; st->n = n; st->m = m; st->d = d; st->packed = packed; st->table = packed ? norms : nullptr;
     return LSQ_OK;
+}
+
+// ---- lsq_index_add's part (the kernels: lsq_grow.hip) ---------------------------------------------------------------------------------------------------
+// The layout of n + count rows is written into the spare half and swapped in at the commit: until then every search reads the former one.  Nothing else
+// of this state depends on n: the search's scratch is sized per call, idbits and the scan's input are read from st->n at every call
+int lsq_ivf_add_check(hipStream_t s, lsq_ivf_state *st, const int32_t *list_of_row, int on_device, int64_t count, unsigned *bad) {
+    return lsq_rows_keys(s, st->rows, list_of_row, on_device, count, st->nlist, bad);
+}
+
+namespace {
+// bytes of the layout's arrays at a capacity of `rows` rows (code rows end in 16 bytes of slack, never read as rows)
+size_t ivf_code_bytes(const lsq_ivf_state *st, int64_t rows) { return (size_t)rows * (size_t)(st->packed ? st->m + 1 : st->m) + 16; }
+int ivf_ensure_spare(lsq_ivf_state *st, int64_t cap_rows, int *realloc) {
+    const size_t before[3] = {st->alt_codes.cap, st->alt_norms.cap, st->alt_ids.cap};
+    LSQ_TRY(st->alt_codes.ensure(ivf_code_bytes(st, cap_rows)));
+    if (!st->packed) LSQ_TRY(st->alt_norms.ensure(sizeof(float) * (size_t)cap_rows));
+    LSQ_TRY(st->alt_ids.ensure(sizeof(int) * (size_t)cap_rows));
+    LSQ_TRY(st->alt_off.ensure(sizeof(int) * ((size_t)st->nlist + 1)));
+    LSQ_TRY(st->add_off.ensure(sizeof(int) * ((size_t)st->nlist + 1)));
+    if (before[0] != st->alt_codes.cap || before[1] != st->alt_norms.cap || before[2] != st->alt_ids.cap) *realloc = 1;
+    return LSQ_OK;
+}
+}  // namespace
+
+int lsq_ivf_reserve(hipStream_t s, lsq_ivf_state *st, int64_t cap_rows, int *realloc) {
+    if (!st || st->nlist < 1) return LSQ_OK;
+    LSQ_TRY(ivf_ensure_spare(st, cap_rows, realloc));
+    const size_t before[3] = {st->codes.cap, st->norms.cap, st->ids.cap};
+    const int rowb = st->packed ? st->m + 1 : st->m;
+    LSQ_TRY(lsq_devbuf_grow(s, st->codes, ivf_code_bytes(st, cap_rows), (size_t)st->n * rowb));
+    if (!st->packed) LSQ_TRY(lsq_devbuf_grow(s, st->norms, sizeof(float) * (size_t)cap_rows, sizeof(float) * (size_t)st->n));
+    LSQ_TRY(lsq_devbuf_grow(s, st->ids, sizeof(int) * (size_t)cap_rows, sizeof(int) * (size_t)st->n));
+    if (before[0] != st->codes.cap || before[1] != st->norms.cap || before[2] != st->ids.cap) *realloc = 1;
+    return LSQ_OK;
+}
+
+int lsq_ivf_add_merge(hipStream_t s, lsq_ivf_state *st, const uint8_t *add_rows, const float *add_norms, int64_t count, int64_t cap_rows, int *realloc) {
+    LSQ_TRY(ivf_ensure_spare(st, cap_rows, realloc));
+    const uint64_t *sorted = nullptr;
+    LSQ_TRY(lsq_rows_sort(s, st->rows, count, st->nlist, &sorted));
+    LSQ_TRY(lsq_rows_offsets(s, sorted, count, st->nlist, st->add_off.as<int>()));
+    lsq_grow_merge g{};
+    g.src_codes = st->codes.as<uint8_t>(); g.src_norms = st->packed ? nullptr : st->norms.as<float>(); g.src_ids = st->ids.as<int>(); g.off = st->off.as<int>();
+    g.dst_codes = st->alt_codes.as<uint8_t>(); g.dst_norms = st->packed ? nullptr : st->alt_norms.as<float>(); g.dst_ids = st->alt_ids.as<int>();
+    g.noff = st->alt_off.as<int>();
+    g.add_off = st->add_off.as<int>(); g.sorted = sorted; g.add_rows = add_rows; g.add_norms = add_norms;
+    g.n = st->n; g.count = count; g.nlist = st->nlist; g.rowb = st->packed ? st->m + 1 : st->m;
+    return lsq_grow_launch_merge(s, g);
+}
+
+void lsq_ivf_add_commit(lsq_ivf_state *st, int64_t count) {
+    std::swap(st->codes, st->alt_codes);
+    std::swap(st->norms, st->alt_norms);
+    std::swap(st->ids, st->alt_ids);
+    std::swap(st->off, st->alt_off);
+    st->n += count;
 }
 
 namespace {

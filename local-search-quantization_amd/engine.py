@@ -704,6 +704,7 @@ class Index(_Handle):
         u8 = False
         if base is not None:
             base, u8 = side.take_x(base, "base", rows=True)
+        self._u8, self._has_codes, self._has_base, self._packed = u8, codes is not None, base is not None, packed is not None
         if packed is not None:
             return self._init_packed(side, codes, K, packed, m, base, u8, h)
         if codes is None and base is None:
@@ -882,6 +883,52 @@ class Index(_Handle):
         """active, n, allowed, lists / lists_without_allowed (0 without inverted lists), road of the last search / search_ivf / knn call (0 unfiltered,
         1 dense, 2 compact), crossover_rows (compact by default when allowed <= this, outside the band the header describes)"""
         return self._info("lsq_index_get_filter_info", _lib.FilterInfo)
+
+    def add(self, codes=None, dbnorms=None, norm_codes=None, base=None, assign=None):
+        """Append rows: they become rows n .. n + count - 1 (0-based), and every call then answers as on an index built over the concatenation, with the
+        concatenated lists and a filter that allows the new rows too.  What the index holds is what must be given: codes (count,m) uint8 0-based with
+        dbnorms (count,) float32 -- a packed index: norm_codes (count,) uint8 instead --, base (count,>=d) rows of the index's own type with unit column
+        stride and any pitch, assign (count,) int32 0-based lists once lists are set.  All numpy arrays or all torch device tensors, whichever way the
+        index was made; they are read before the call returns.  A device index that borrowed its arrays copies them once, at the first add or reserve
+        [lsq_index_add]"""
+        given = [(nm, a) for nm, a in (("codes", codes), ("dbnorms", dbnorms), ("norm_codes", norm_codes), ("base", base), ("assign", assign)) if a is not None]
+        if not given:
+            raise ValueError("add needs the arrays of the new rows")
+        on_dev = [bool(getattr(a, "is_cuda", False)) for _, a in given]
+        if any(on_dev) != all(on_dev):
+            raise TypeError("add takes numpy arrays or torch device tensors, not both: %s" % ", ".join("%s %s" % (nm, "device" if v else "host") for (nm, _), v in zip(given, on_dev)))
+        side = _DEVICE if on_dev[0] else _HOST
+        if not side.dev and norm_codes is not None and np.asarray(norm_codes).dtype != _U8:      # a norm byte is an index: never narrowed silently
+            raise TypeError("norm_codes must be uint8, got %s" % np.asarray(norm_codes).dtype)
+        codes, dbnorms, nc, lor = side.maybe(codes, _U8, "codes"), side.maybe(dbnorms, _F32, "dbnorms"), side.maybe(norm_codes, _U8, "norm_codes"), side.maybe(assign, _I32, "assign")
+        if base is not None:
+            u8 = _dtname(base) == "uint8"
+            if u8 != self._u8:
+                raise TypeError("base rows must have the index's own type (%s), got %s" % ("uint8" if self._u8 else "float32", _dtname(base)))
+            if side.dev:
+                base, _ = side.take_x(base, "base", rows=True)
+            else:                                       # a row view of the right type is read in place: any pitch and byte offset
+                base = np.asarray(base, dtype=_U8 if u8 else _F32)
+                if base.ndim != 2 or base.strides[1] != base.itemsize or base.strides[0] % base.itemsize or (base.shape[0] > 1 and base.strides[0] < base.shape[1] * base.itemsize):
+                    base = np.ascontiguousarray(base)
+        count = int(next(a for a in (codes, dbnorms, nc, base, lor) if a is not None).shape[0])
+        _shapes(("codes", codes, (count, self.m)), ("dbnorms", dbnorms, (count,)), ("norm_codes", nc, (count,)), ("assign", lor, (count,)),
+                ("base", base, (count, max(self.d, base.shape[-1] if base is not None else 0))))
+        desc, p = _lib.IndexAddDesc(), side.ptr
+        desc.count, desc.codes, desc.dbnorms, desc.norm_codes, desc.list_of_row = count, p(codes), p(dbnorms), p(nc), p(lor)
+        desc.base, desc.ldb, desc.on_device = p(base), 0 if base is None else int(side.pitch(base)), int(side.dev)
+        try:
+            self._eng._call(side, "lsq_index_add", C.byref(desc), h=self._h)
+        finally:
+            self.n = int(self.growth_info()["n"])
+
+    def reserve(self, rows):
+        """capacity for at least `rows` rows in all: the adds up to there re-allocate nothing (a device index adopts its borrowed arrays now)   [lsq_index_reserve]"""
+        self._eng._call(self._side, "lsq_index_reserve", int(rows), h=self._h)
+
+    def growth_info(self):
+        """n, capacity_rows, adds, rows_added, reallocations, adopted, merged_rows (last add), append_ms / merge_ms / filter_ms (last add, with profile=True)"""
+        return self._info("lsq_index_get_growth_info", _lib.IndexGrowthInfo)
 
 
 # -- the beam-search encoder (made by Engine.encoder / Engine.encoder_dev) ------------------------

@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE [--residual]] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -29,6 +29,11 @@ residuals' code_norms and the index is packed.  Its recall curve is printed as a
 --norm-byte: the norm byte that quantize_norms computes stays a byte up to the search: a packed index (Engine.index_packed, rows of m code bytes and one
 norm byte: the 64-bit code at m = 7) is searched through linscan_lsq_bytes, and its ids and distances are checked to equal the float-norm run's.  The
 reference widens the byte to a float per vector one line before its scan (demo_lsq_gpu.jl:57-60).
+
+--grow FRACTION (with --ivf): the index is built on the first 1 - FRACTION of the base and the rest is APPENDED (Index.add): the partition is fixed, so the
+new rows' lists come from Partition.assign row by row -- with --residual their residuals, codes and code_norms too (Partition.residuals, encode_icm_dev at
+global_offset = the rows already held, Partition.code_norms).  The recall curve of the grown index is printed next to that of the whole build; whether the
+two coincide exactly depends on the encoder being deterministic per row under global_offset, and the demo says which it saw.
 
 --filter FRACTION: a seeded random mask that allows about FRACTION of the base rows is laid over a resident index (Index.set_filter); the ADC search -- and,
 where given, the --ivf and --rerank variants -- then answer over the allowed rows alone, and their recall is taken against Index.knn under the SAME mask on
@@ -138,8 +143,9 @@ def train_resident(x_train, m, h, niter, ilsiter, icmiter, randord, npert):
     return [np.ascontiguousarray(K[i * h:(i + 1) * h].T) for i in range(m)], B, cbnorms, B_norms, obj
 
 
-def residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, npert, nprobe, knn, norm_byte):
-    """the residual index over the SAME centroids and lists, resident on the device -> (recall curve, seconds of the build, error in base)"""
+def residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, npert, nprobe, knn, norm_byte, n0=None):
+    """the residual index over the SAME centroids and lists, resident on the device -> (recall curve, seconds of the build, error in base, and with n0 the
+    recall curve of the index built on the first n0 rows and grown by the rest -- else None)"""
     import torch
     dXt = torch.from_numpy(np.ascontiguousarray(x_train.T)).cuda()
     dXb = torch.from_numpy(np.ascontiguousarray(x_base.T)).cuda()            # f32, or the un-widened bytes of --bvecs
@@ -162,7 +168,26 @@ def residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter
         with ix:
             _, ridx = ix.search_ivf(torch.from_numpy(Q).cuda(), knn, nprobe, add_coarse=True)
             ridx = ridx.cpu().numpy()
-    return lsq.eval_recall(gt, np.ascontiguousarray(ridx.T).astype(np.uint32), knn), t_build, rep["obj"]
+        grec = None
+        if n0 is not None:                                                  # --grow: the same build on the first n0 rows, the rest appended
+            gx = lsq.build_ivf_residual_index(dXb[:n0], part, dK, m, engine=eng, ilsiters=[16], icmiter=icmiter, npert=npert, randord=randord, cbnorms=cb)
+            with gx:
+                dXn = dXb[n0:]
+                ta = part.assign(dXn)
+                nnew = int(dXn.shape[0])
+                dBs, _, _ = eng.encode_icm_dev(part.residuals(dXn, ta), eng.randinit_dev(0, nnew, m, device=dXn.device, global_offset=n0), dK, m, [16], icmiter,
+                                               npert, randord, seed=0, global_offset=n0)
+                if cb is None:
+                    gx.add(codes=dBs[-1], dbnorms=part.code_norms(dBs[-1], dK, ta), assign=ta)
+                else:
+                    _, dnc, _ = part.code_norms(dBs[-1], dK, ta, torch.from_numpy(cb).cuda())
+                    gx.add(codes=dBs[-1], norm_codes=dnc, assign=ta)
+                _, gidx = gx.search_ivf(torch.from_numpy(Q).cuda(), knn, nprobe, add_coarse=True)
+                same = bool(torch.equal(gidx.cpu(), torch.from_numpy(ridx)))
+                print("Residual IVF index grown from %d to %d rows (Index.add): %d rows held, results %s the whole build's"
+                      % (n0, n0 + nnew, gx.n, "EQUAL" if same else "differ from"))
+                grec = lsq.eval_recall(gt, np.ascontiguousarray(gidx.cpu().numpy().T).astype(np.uint32), knn)
+    return lsq.eval_recall(gt, np.ascontiguousarray(ridx.T).astype(np.uint32), knn), t_build, rep["obj"], grec
 
 
 def main():
@@ -197,6 +222,17 @@ def main():
         except (ValueError, AssertionError, IndexError):
             raise SystemExit("--filter takes a FRACTION in (0, 1]")
         del argv[at:at + 2]
+    grow = None
+    if "--grow" in argv:
+        at = argv.index("--grow")
+        try:
+            grow = float(argv[at + 1])
+            assert 0.0 < grow < 1.0
+        except (ValueError, AssertionError, IndexError):
+            raise SystemExit("--grow takes a FRACTION in (0, 1)")
+        del argv[at:at + 2]
+        if not ivf:
+            raise SystemExit("--grow needs --ivf NLIST:NPROBE")
     args = [a for a in argv if a not in ("--resident", "--bvecs", "--norm-byte", "--residual")]
     resident, bvecs, norm_byte, residual = "--resident" in argv, "--bvecs" in argv, "--norm-byte" in argv, "--residual" in argv
     if residual and not ivf:
@@ -283,19 +319,33 @@ def main():
                 _, iidx = ix.search_ivf(Q, knn, nprobe)
                 t_ivf = time.perf_counter() - t0
                 info = ix.ivf_info()
+            nb_all = x_base.shape[1]
+            n0 = max(1, nb_all - max(1, int(round(grow * nb_all)))) if grow else None
+            grec = gres = None
+            if grow:                                                        # the index on the first n0 rows, the rest appended; lists of the new rows: Partition.assign
+                codes_all = np.ascontiguousarray((B_base - 1).astype(np.uint8).T)
+                with eng.index(codes_all[:n0], np.ascontiguousarray(np.hstack(C).T), db_norms[:n0], m) as gx, eng.partition(cent) as part:
+                    gx.set_lists(cent, assign[:n0])
+                    new_lists = np.asarray(part.assign(rows[n0:]), dtype=np.int32)
+                    gx.add(codes=codes_all[n0:], dbnorms=db_norms[n0:], assign=new_lists)
+                    _, gidx = gx.search_ivf(Q, knn, nprobe)
+                    print("IVF index grown from %d to %d rows (Index.add); the new rows' lists %s ivf_assign's; results %s the whole build's"
+                          % (n0, gx.n, "equal" if np.array_equal(new_lists, assign[n0:]) else "DIFFER from", "EQUAL" if np.array_equal(gidx, iidx) else "differ from"))
+                grec = lsq.eval_recall(gt, np.ascontiguousarray(gidx.T).astype(np.uint32), knn)
             if residual:
-                rrec_ivf, t_res, mse = residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, min(npert, m), nprobe,
-                                                    knn, norm_byte)
+                rrec_ivf, t_res, mse, gres = residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, min(npert, m),
+                                                          nprobe, knn, norm_byte, n0)
         irec = lsq.eval_recall(gt, np.ascontiguousarray(iidx.T).astype(np.uint32), knn)
         print("IVF search (nlist %d, nprobe %d): %.3f s on the resident index; %.0f of %d rows probed per query, %d of %d queries on the thresholded road"
               % (nlist, nprobe, t_ivf, info["probed_rows"] / Q.shape[0], x_base.shape[1], info["threshold_queries"], Q.shape[0]))
         if residual:
             print("Residual IVF index (%s rows, %s norms) built on the device in %.3f s; error in base is %e (plain codes: %e)"
                   % (x_base.dtype, "byte" if norm_byte else "float", t_res, mse, objs[-1]))
-        print("     r@   exhaustive   IVF" + ("          residual IVF" if residual else ""))
+        print("     r@   exhaustive   IVF" + ("          residual IVF" if residual else "") + ("     grown IVF" if grow else "") + ("   grown residual IVF" if gres is not None else ""))
         for i in (1, 2, 5, 10, 20, 50, 100, 200, 500, 1000):
             if i <= knn:
-                print("%7d   %.4f       %.4f" % (i, rec[i - 1], irec[i - 1]) + ("       %.4f" % rrec_ivf[i - 1] if residual else ""))
+                print("%7d   %.4f       %.4f" % (i, rec[i - 1], irec[i - 1]) + ("       %.4f" % rrec_ivf[i - 1] if residual else "")
+                      + ("         %.4f" % grec[i - 1] if grow else "") + ("      %.4f" % gres[i - 1] if gres is not None else ""))
     if fraction is not None:
         filtered_recall(fraction, name, x_base, x_query, B_base, C, db_norms, m, knn, shortlist, ivf)
 
