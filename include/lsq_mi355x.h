@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 2100
+#define LSQ_VERSION 2200
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -736,6 +736,50 @@ typedef struct lsq_index_growth_info {
 LSQ_API int lsq_index_add(lsq_index *ix, const lsq_index_add_desc *desc);
 LSQ_API int lsq_index_reserve(lsq_index *ix, int64_t rows);       /* capacity for at least `rows` rows in total */
 LSQ_API int lsq_index_get_growth_info(lsq_index *ix, lsq_index_growth_info *out);
+
+/* ---- (3l) removing rows from the resident index: lsq_index_remove (tombstones) and lsq_index_compact (the rows leave; csrc/lsq_compact.hip; since v2200) ----
+ * THE REFERENCE HAS NO COUNTERPART.
+ *   remove       (Identity R) after a successful lsq_index_remove the index is, for every call and every field of lsq_filter_info but `road`, the index
+ *                after lsq_index_set_filter(BITS = (the allowed set in force, or every row if none) minus the given rows).  A FORCE flag of the filter in
+ *                force stays.  Duplicates and rows already removed are legal; count == 0 is a no-op and creates no filter.  The ids are range-checked on
+ *                the device by the one kernel that reads them, before any is used as an address and before anything is written: a refused call leaves
+ *                the filter and every answer as they were.  lsq_index_rerank ignores the filter, as ever.
+ *   compact      A = the allowed set in force, n' = |A| >= 1.  The rows outside A LEAVE: the surviving rows keep their order and become rows 0 .. n' - 1
+ *                (old_of_new = the filter's ascending row list).  (Identity C) afterwards EVERY CALL ON THE INDEX RETURNS, BIT FOR BIT, WHAT IT RETURNS ON
+ *                AN INDEX FRESHLY BUILT over the surviving rows in that order, given lsq_index_set_lists with the same centroids and the survivors' lists
+ *                (same nlist: lists may become empty) and NO filter: distances, ids, tie order, NaN order, padding records, every deterministic statistic
+ *                (the layout is the same array for array).  (Identity M) for nn <= n' the filtered answer before the call and the answer after it have the
+ *                same distance bits, and id_after = new_of_old[id_before].  Codebooks, centroids and cbnorms do not change.  The filter is cleared.
+ *                Without an active filter nothing is dropped (LSQ_OK, identity maps; LSQ_COMPACT_SHRINK still acts).
+ *   ownership    a borrowing index (on_device = 1, never added to) is ADOPTED BY THE GATHER: the survivors are written straight from the caller's arrays
+ *                into owned storage; the caller's arrays are never written, and never read once the call has returned.  (Without an active filter and
+ *                without LSQ_COMPACT_SHRINK nothing moves and a borrowing index keeps borrowing.)
+ *   capacity     capacity_rows is kept: adds into the freed rows re-allocate nothing.  LSQ_COMPACT_SHRINK sizes the owned arrays and both halves of the
+ *                layout to n' rows.
+ *   atomicity    validate, allocate, write beside, one wait, commit.  A refused call changes nothing; a call that fails later (LSQ_ENOMEM, LSQ_EHIP) leaves
+ *                every answer, n, the lists and the filter as they were.  THE PRICE: until the commit the old and the new arrays coexist -- the transient
+ *                peak is old plus new of everything the index owns.
+ * LSQ_EINVAL: a null handle; remove: count < 0 or > 2^31 - 1, null ids with count > 0, id_base not 0 or 1, an id outside [id_base, id_base + n) (device);
+ * compact: unknown flags, id_base not 0 or 1, no allowed row. */
+enum { LSQ_COMPACT_SHRINK = 1 };
+typedef struct lsq_index_compact_desc {
+    int32_t *old_of_new;         /* optional out [allowed]: the former row of every new row, ascending, in id_base */
+    int32_t *new_of_old;         /* optional out [n]: the new row of every former row in id_base, -1 for a removed row */
+    int id_base;                 /* 0 or 1, for both maps */
+    int flags;                   /* LSQ_COMPACT_SHRINK */
+    int on_device;               /* 0 host arrays, 1 device arrays (the maps) */
+} lsq_index_compact_desc;
+typedef struct lsq_index_compact_info {
+    int64_t n_before, n_after;   /* last compact */
+    int64_t removes, rows_tombstoned;    /* successful lsq_index_remove calls with count > 0 since creation; the bits they newly cleared */
+    int64_t compactions, rows_dropped;   /* successful lsq_index_compact calls since creation; the rows that left */
+    int64_t moved_bytes;         /* last compact: destination bytes written, flat arrays plus layout */
+    int64_t shrunk;              /* last compact: 1 when LSQ_COMPACT_SHRINK re-sized the storage */
+    double tombstone_ms, gather_ms, layout_ms;   /* last remove; last compact's flat gather and layout phases -- with option "profile" = 1 */
+} lsq_index_compact_info;
+LSQ_API int lsq_index_remove (lsq_index *ix, const int32_t *ids, int64_t count, int id_base, int on_device);
+LSQ_API int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *desc);   /* desc == NULL: no map wanted, no flags */
+LSQ_API int lsq_index_get_compact_info(lsq_index *ix, lsq_index_compact_info *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

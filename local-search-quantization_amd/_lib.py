@@ -102,6 +102,17 @@ class IndexGrowthInfo(_Struct):
                 ("adopted", C.c_int64), ("merged_rows", C.c_int64), ("append_ms", C.c_double), ("merge_ms", C.c_double), ("filter_ms", C.c_double)]
 
 
+class IndexCompactDesc(_Struct):
+    _fields_ = [("old_of_new", C.c_void_p), ("new_of_old", C.c_void_p), ("id_base", C.c_int), ("flags", C.c_int), ("on_device", C.c_int)]
+
+
+class IndexCompactInfo(_Struct):
+    _fields_ = [("n_before", C.c_int64), ("n_after", C.c_int64), ("removes", C.c_int64), ("rows_tombstoned", C.c_int64), ("compactions", C.c_int64),
+                ("rows_dropped", C.c_int64), ("moved_bytes", C.c_int64), ("shrunk", C.c_int64), ("tombstone_ms", C.c_double), ("gather_ms", C.c_double),
+                ("layout_ms", C.c_double)]
+
+
+COMPACT_SHRINK = 1
 FILTER_BITS, FILTER_BYTES, FILTER_IDS = 0, 1, 2
 FILTER_DENY, FILTER_FORCE_DENSE, FILTER_FORCE_COMPACT = 1, 2, 4
 
@@ -222,6 +233,10 @@ SIGNATURES = {
     "lsq_index_add": (_i, [_vp, C.POINTER(IndexAddDesc)]),
     "lsq_index_reserve": (_i, [_vp, _i64]),
     "lsq_index_get_growth_info": (_i, [_vp, C.POINTER(IndexGrowthInfo)]),
+    # removing rows from the index (since v2200)
+    "lsq_index_remove": (_i, [_vp, _vp, _i64, _i, _i]),
+    "lsq_index_compact": (_i, [_vp, C.POINTER(IndexCompactDesc)]),
+    "lsq_index_get_compact_info": (_i, [_vp, C.POINTER(IndexCompactInfo)]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),
@@ -263,7 +278,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 2100      # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 2200     # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

@@ -565,6 +565,9 @@ struct lsq_index {
     lsq_index_growth_info grow{};
     DevBuf g_codes, g_nc, g_rows;                      // lsq_index_add on a packed index: staging of host codes and norm bytes, the new rows packed
     PhaseClock<4> gclock;                              // an add's append, merge and filter phases
+    lsq_index_compact_info cinfo{};                    // lsq_index_remove / _compact
+    DevBuf c_old, c_new;                               // lsq_index_compact into host arrays: the maps on the device
+    PhaseClock<3> cclock;                              // a remove's tombstones; a compact's gather and layout phases
 };
 
 // the filter as a scan over all rows takes it: nothing without one; else the compact road -- the ascending list of allowed rows -- where the measured rule
@@ -585,9 +588,11 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     (void)hipSetDevice(ix->ctx->device);
     (void)hipStreamSynchronize(ix->ctx->stream);
     DevBuf *bufs[] = {&ix->own_codes, &ix->own_K, &ix->own_norms, &ix->own_base, &ix->rec_a, &ix->rec_b, &ix->seg, &ix->counter, &ix->short_d, &ix->short_i,
-                      &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q, &ix->s_qcoarse, &ix->g_codes, &ix->g_nc, &ix->g_rows};
+                      &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q, &ix->s_qcoarse, &ix->g_codes, &ix->g_nc, &ix->g_rows,
+                      &ix->c_old, &ix->c_new};
     for (DevBuf *b : bufs) b->release();
     ix->gclock.release();
+    ix->cclock.release();
     lsq_adc_free(ix->adc);
     lsq_ivf_free(ix->ivf);
     lsq_filter_free(ix->filter);
@@ -1173,6 +1178,147 @@ extern "C" int lsq_index_get_growth_info(lsq_index *ix, lsq_index_growth_info *o
     if (!ix || !out) { lsq_set_error("lsq_index_get_growth_info: null argument"); return LSQ_EINVAL; }
     *out = ix->grow;
     out->n = ix->n; out->capacity_rows = ix->cap_rows;
+    return LSQ_OK;
+}
+
+// ---- removing rows (lsq_filter.hip: the tombstones; lsq_compact.hip: the rows leave) ----------------------------------------------------------
+extern "C" int lsq_index_remove(lsq_index *ix, const int32_t *ids, int64_t count, int id_base, int on_device) {
+    const char *fn = "lsq_index_remove";
+    if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
+    if (const char *why = lsq_compact_remove_refusal(ids, count, id_base)) { lsq_set_error("%s: %s (count=%lld id_base=%d)", fn, why, (long long)count, id_base); return LSQ_EINVAL; }
+    if (count == 0) return LSQ_OK;                    // a no-op: no filter is created
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    LSQ_TRY(ix->cclock.begin(c->profile != 0));
+    LSQ_TRY(ix->cclock.mark(s));
+    unsigned bad = 0;
+    int64_t cleared = 0;
+    LSQ_TRY(lsq_filter_remove(s, &ix->filter, ix->n, ids, count, id_base, on_device, &bad, &cleared));
+    if (bad) { lsq_set_error("%s: %u ids lie outside [%d, %lld)", fn, bad, id_base, (long long)(id_base + ix->n)); return LSQ_EINVAL; }
+    const int rc = index_filter_layout(ix);           // the layout-order bits follow the new filter
+    LSQ_TRY(ix->cclock.mark(s));
+    float ms[2];
+    LSQ_TRY(ix->cclock.read(ms));
+    ix->cinfo.removes += 1; ix->cinfo.rows_tombstoned += cleared; ix->cinfo.tombstone_ms = ms[0];
+    return rc;
+}
+
+namespace {
+struct ScopedBuf {                                     // a buffer of one call: what it holds when the call ends is freed (after a commit: the former array)
+    DevBuf b;
+    ~ScopedBuf() { b.release(); }
+};
+}  // namespace
+
+// What depends on n, for a SHRINKING n (the audit of lsq_index_add, again): ix->n, cap_rows and the flat pointers (committed last, the arrays written
+// beside); lsq_ivf_state's layout, off and n (written into the spare half, swapped at the commit); lsq_filter_state (cleared: the survivors are all
+// allowed; its layout-order state reset); grow.n (read from ix->n); nrm_x, the scan state's buffers, stage two's records and every staging buffer are
+// sized from the call's own n at every call and hold nothing across calls -- a smaller n finds them large enough
+extern "C" int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *desc) {
+    const char *fn = "lsq_index_compact";
+    if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
+    if (const char *why = lsq_compact_refusal(desc)) { lsq_set_error("%s: %s (flags=%d id_base=%d)", fn, why, desc->flags, desc->id_base); return LSQ_EINVAL; }
+    const bool active = lsq_filter_active(ix->filter);
+    const lsq_filter_view v = lsq_filter_get(ix->filter);
+    if (const char *why = lsq_compact_allowed_refusal(active, v.allowed)) { lsq_set_error("%s: %s", fn, why); return LSQ_EINVAL; }
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    const int flags = desc ? desc->flags : 0, id_base = desc ? desc->id_base : 0;
+    const bool shrink = (flags & LSQ_COMPACT_SHRINK) != 0, lists = lsq_ivf_nlist(ix->ivf) > 0;
+    const int64_t n = ix->n, n2 = active ? v.allowed : n;
+    const int64_t cap = lsq_compact_capacity(ix->cap_rows, n2, flags);
+    const size_t rowb = index_row_bytes(ix), e = index_base_elem(ix);
+    if (active && lists && !v.lbits) { lsq_set_error("%s: the filter has no bits in layout order (a failed lsq_index_set_lists / _set_filter?)", fn); return LSQ_EINVAL; }
+    // the caller's maps: written on the device, into the caller's arrays or into scratch that is copied out
+    int32_t *h_old = desc ? desc->old_of_new : nullptr, *h_new = desc ? desc->new_of_old : nullptr;
+    int32_t *d_old = h_old, *d_new = h_new;
+    const bool host_maps = desc && !desc->on_device;
+    if (host_maps && h_old) { LSQ_TRY(ix->c_old.ensure(sizeof(int32_t) * (size_t)n2)); d_old = ix->c_old.as<int32_t>(); }
+    if (host_maps && h_new) { LSQ_TRY(ix->c_new.ensure(sizeof(int32_t) * (size_t)n)); d_new = ix->c_new.as<int32_t>(); }
+    auto maps = [&]() -> int {
+        LSQ_TRY(lsq_compact_launch_maps(s, active ? v.bits : nullptr, v.pre, v.rows, n, n2, id_base, d_old, d_new));
+        if (host_maps && h_old) LSQ_HIP(hipMemcpyAsync(h_old, d_old, sizeof(int32_t) * (size_t)n2, hipMemcpyDeviceToHost, s));
+        if (host_maps && h_new) LSQ_HIP(hipMemcpyAsync(h_new, d_new, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+        return LSQ_OK;
+    };
+    int64_t bytes = 0, shrunk = 0;
+    float ms[2] = {0.0f, 0.0f};
+    if (!active) {                                    // nothing leaves.  LSQ_COMPACT_SHRINK: owned storage with spare capacity is re-allocated to n rows
+        if (shrink && ix->cap_rows > n && !index_borrows(ix)) {      // (each array: allocate, copy, swap, free -- the same rows wherever they lie)
+            if (ix->codes) {
+                LSQ_TRY(lsq_devbuf_fit(s, ix->own_codes, (size_t)n * rowb + 16, (size_t)n * rowb));
+                ix->codes = ix->own_codes.as<uint8_t>();
+                if (!ix->packed) {
+                    LSQ_TRY(lsq_devbuf_fit(s, ix->own_norms, sizeof(float) * (size_t)n, sizeof(float) * (size_t)n));
+                    ix->norms = ix->own_norms.as<float>();
+                }
+            }
+            if (ix->base) {
+                LSQ_TRY(lsq_devbuf_fit(s, ix->own_base, (size_t)n * (size_t)ix->ldb * e, ((size_t)(n - 1) * (size_t)ix->ldb + (size_t)ix->d) * e));
+                ix->base = ix->own_base.p;
+            }
+            LSQ_TRY(lsq_ivf_fit(s, ix->ivf, n));
+            ix->cap_rows = n;
+            shrunk = 1;
+        }
+        LSQ_TRY(maps());
+        LSQ_HIP(hipStreamSynchronize(s));
+    } else {
+        // 1. the flat arrays, gathered into fresh storage of `cap` rows: straight from the caller's arrays where the index borrows them
+        ScopedBuf codes, norms, base;
+        LSQ_TRY(ix->cclock.begin(c->profile != 0));
+        LSQ_TRY(ix->cclock.mark(s));
+        if (ix->codes) {
+            LSQ_TRY(codes.b.ensure((size_t)cap * rowb + 16));       // 16 bytes of slack past the last row, never read
+            LSQ_TRY(lsq_compact_launch_gather(s, ix->codes, codes.b.p, v.rows, (int64_t)rowb, n2, (int64_t)rowb, &bytes));
+            if (!ix->packed) {
+                LSQ_TRY(norms.b.ensure(sizeof(float) * (size_t)cap));
+                LSQ_TRY(lsq_compact_launch_gather(s, ix->norms, norms.b.p, v.rows, 4, n2, 4, &bytes));
+            }
+        }
+        if (ix->base) {                               // the pitch is kept; the last row ends at its d-th element, in the source as in the copy
+            LSQ_TRY(base.b.ensure((size_t)cap * (size_t)ix->ldb * e));
+            LSQ_TRY(lsq_compact_launch_gather(s, ix->base, base.b.p, v.rows, (int64_t)((size_t)ix->ldb * e), n2, (int64_t)((size_t)ix->d * e), &bytes));
+        }
+        LSQ_TRY(ix->cclock.mark(s));
+        // 2. the inverted layout, into its spare half
+        if (lists) {
+            const int *lsel = nullptr;
+            LSQ_TRY(lsq_filter_layout_rows(s, ix->filter, n, &lsel));
+            LSQ_TRY(lsq_ivf_compact(s, ix->ivf, v, lsel, n2, cap, shrink, &bytes));
+        }
+        LSQ_TRY(ix->cclock.mark(s));
+        LSQ_TRY(maps());
+        LSQ_HIP(hipStreamSynchronize(s));             // the one wait: everything is written, nothing is in force
+        LSQ_TRY(ix->cclock.read(ms));
+        // 3. the commit
+        if (index_borrows(ix)) ix->grow.adopted = 1;
+        if (ix->codes) {
+            std::swap(ix->own_codes, codes.b);
+            ix->codes = ix->own_codes.as<uint8_t>();
+            if (!ix->packed) { std::swap(ix->own_norms, norms.b); ix->norms = ix->own_norms.as<float>(); }
+        }
+        if (ix->base) { std::swap(ix->own_base, base.b); ix->base = ix->own_base.p; }
+        if (lists) lsq_ivf_compact_commit(ix->ivf, n2);
+        lsq_filter_clear(ix->filter);                 // every surviving row is allowed
+        ix->n = n2;
+        ix->cap_rows = cap;
+        (void)index_filter_layout(ix);                // (no filter: the layout-order state is reset, nothing is launched)
+        if (lists && shrink) (void)lsq_ivf_fit(s, ix->ivf, n2);      // the half that was the layout.  A failure costs nothing: the next add sizes it
+        shrunk = shrink ? 1 : 0;
+    }
+    ix->cinfo.n_before = n; ix->cinfo.n_after = n2;
+    ix->cinfo.compactions += 1; ix->cinfo.rows_dropped += n - n2;
+    ix->cinfo.moved_bytes = bytes; ix->cinfo.shrunk = shrunk;
+    ix->cinfo.gather_ms = ms[0]; ix->cinfo.layout_ms = ms[1];
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_compact_info(lsq_index *ix, lsq_index_compact_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_compact_info: null argument"); return LSQ_EINVAL; }
+    *out = ix->cinfo;
     return LSQ_OK;
 }
 

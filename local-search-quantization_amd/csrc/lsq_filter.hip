@@ -15,7 +15,8 @@
 // Inputs: BYTES -> bits by one ballot per 64 rows; IDS -> a range check (the one kernel that reads the entries counts the bad ones and turns none of them
 // into an address), then atomicOr into zeroed words (OR commutes: the same bits on every call, duplicates are harmless); BITS -> copied.  DENY inverts the
 // words; the bits at and past n are then zeroed in the last word.  Everything is built into fresh buffers and swapped in at the end, so a refused call
-// leaves the former filter in force.
+// leaves the former filter in force.  lsq_index_remove (further down) is a fourth input: the bitmap in force copied, the given rows' bits cleared with
+// atomicAnd by the one kernel that reads the ids, then the same finish / prefix / row-list kernels and the same swap.
 #include <hipcub/hipcub.hpp>
 
 #include <utility>
@@ -60,6 +61,17 @@ __global__ __launch_bounds__(FLT_THREADS) void flt_ids_kernel(const int32_t *__r
     const int64_t row = (int64_t)ids[t] - id_base;
     if (row < 0 || row >= n) { atomicAdd(bad, 1u); return; }
     atomicOr(&words[row >> 5], 1u << (row & 31));
+}
+
+// lsq_index_remove: ids in id_base -> their bits CLEARED in a copy of the bitmap in force (AND commutes: the same bits on every call, duplicates and
+// rows already removed are harmless); *bad += entries outside [id_base, id_base + n): counted, never used as an address
+__global__ __launch_bounds__(FLT_THREADS) void flt_remove_kernel(const int32_t *__restrict__ ids, int64_t count, int id_base, int64_t n,
+                                                                 uint32_t *__restrict__ words, unsigned *__restrict__ bad) {
+    const int64_t t = (int64_t)blockIdx.x * FLT_THREADS + threadIdx.x;
+    if (t >= count) return;
+    const int64_t row = (int64_t)ids[t] - id_base;
+    if (row < 0 || row >= n) { atomicAdd(bad, 1u); return; }
+    atomicAnd(&words[row >> 5], ~(1u << (row & 31)));
 }
 
 // DENY: inverted; the bits at and past n zeroed; cnt[w] = popcount, cnt[nwords] = 0 (the scan's last output is then the total)
@@ -124,6 +136,7 @@ struct lsq_filter_state {
     int force = 0;
     FilterBufs cur, next;                            // the filter in force; the one a set call is building
     DevBuf lbits, lpre;                              // layout order (with inverted lists)
+    DevBuf lrows;                                    // lsq_index_compact: the set bits of lbits, ascending -- the compact form of the layout, for one call
     int nlist = 0;
     int64_t lists_without = 0;
     DevBuf cnt, tmp, flag, stage;                    // popcounts, the scan's workspace, a counter, a host input's staging
@@ -133,7 +146,7 @@ struct lsq_filter_state {
 void lsq_filter_free(lsq_filter_state *st) {
     if (!st) return;
     st->cur.release(); st->next.release();
-    DevBuf *all[] = {&st->lbits, &st->lpre, &st->cnt, &st->tmp, &st->flag, &st->stage};
+    DevBuf *all[] = {&st->lbits, &st->lpre, &st->lrows, &st->cnt, &st->tmp, &st->flag, &st->stage};
     for (DevBuf *b : all) b->release();
     delete st;
 }
@@ -150,6 +163,7 @@ lsq_filter_view lsq_filter_get(const lsq_filter_state *st) {
     if (!lsq_filter_active(st)) return v;
     v.bits = st->cur.bits.as<uint32_t>();
     v.rows = st->cur.rows.as<int>();
+    v.pre = st->cur.pre.as<int>();
     v.allowed = st->allowed;
     v.force = st->force;
     if (st->nlist > 0) { v.lbits = st->lbits.as<uint32_t>(); v.lpre = st->lpre.as<int>(); }
@@ -274,6 +288,64 @@ void lsq_filter_grow_commit(lsq_filter_state *st, int64_t n_new) {
     st->allowed += n_new - st->n;
     st->n = n_new;
     st->nlist = 0; st->lists_without = 0;            // lsq_filter_layout rebuilds the layout-order bits
+}
+
+// ---- lsq_index_remove's part: the filter in force (without one: every row) minus the given rows.  Built in the spare buffers like a set call's: the bitmap
+// copied, the bits cleared by the one kernel that reads the ids -- it counts the bad ones and turns none of them into an address; what it writes is the
+// spare bitmap, which is nothing until the swap --, then count, prefix and row list by the kernels above
+int lsq_filter_remove(hipStream_t s, lsq_filter_state **pst, int64_t n, const int32_t *ids, int64_t count, int id_base, int on_device, unsigned *bad,
+                      int64_t *cleared) {
+    if (!*pst) *pst = new lsq_filter_state();
+    lsq_filter_state *st = *pst;
+    const int64_t nwords = (n + 31) / 32;
+    FilterBufs &nb = st->next;
+    LSQ_TRY(nb.bits.ensure(sizeof(uint32_t) * (size_t)nwords));
+    LSQ_TRY(nb.pre.ensure(sizeof(int) * ((size_t)nwords + 1)));
+    LSQ_TRY(st->cnt.ensure(sizeof(int) * ((size_t)nwords + 1)));
+    LSQ_TRY(st->flag.ensure(sizeof(unsigned)));
+    uint32_t *words = nb.bits.as<uint32_t>();
+    const int32_t *din = ids;
+    if (!on_device) {
+        LSQ_TRY(st->stage.ensure(sizeof(int32_t) * (size_t)count));
+        LSQ_HIP(hipMemcpyAsync(st->stage.p, ids, sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, s));
+        din = st->stage.as<int32_t>();
+    }
+    if (st->active) LSQ_HIP(hipMemcpyAsync(words, st->cur.bits.p, sizeof(uint32_t) * (size_t)nwords, hipMemcpyDeviceToDevice, s));
+    else LSQ_HIP(hipMemsetAsync(words, 0xff, sizeof(uint32_t) * (size_t)nwords, s));      // (the bits at and past n: zeroed by the finish kernel)
+    LSQ_HIP(hipMemsetAsync(st->flag.p, 0, sizeof(unsigned), s));
+    hipLaunchKernelGGL(flt_remove_kernel, dim3(blocks_for(count)), dim3(FLT_THREADS), 0, s, din, count, id_base, n, words, st->flag.as<unsigned>());
+    LSQ_HIP(hipGetLastError());
+    LSQ_HIP(hipMemcpyAsync(bad, st->flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    LSQ_HIP(hipStreamSynchronize(s));
+    if (*bad) return LSQ_OK;                          // the caller refuses: only the spare bitmap was written
+    hipLaunchKernelGGL(flt_finish_kernel, dim3(blocks_for(nwords + 1)), dim3(FLT_THREADS), 0, s, words, n, nwords, 0, st->cnt.as<int>());
+    LSQ_HIP(hipGetLastError());
+    LSQ_TRY(exclusive_sum(s, st->tmp, st->cnt.as<int>(), nb.pre.as<int>(), nwords + 1));
+    int allowed = 0;
+    LSQ_HIP(hipMemcpyAsync(&allowed, nb.pre.as<int>() + nwords, sizeof(int), hipMemcpyDeviceToHost, s));
+    LSQ_HIP(hipStreamSynchronize(s));
+    LSQ_TRY(nb.rows.ensure(sizeof(int) * (size_t)(allowed > 0 ? allowed : 1)));
+    hipLaunchKernelGGL(flt_compact_kernel, dim3(blocks_for(nwords)), dim3(FLT_THREADS), 0, s, words, nb.pre.as<int>(), nwords, nb.rows.as<int>());
+    LSQ_HIP(hipGetLastError());
+    LSQ_HIP(hipStreamSynchronize(s));
+    *cleared = (st->active ? st->allowed : n) - allowed;
+    std::swap(st->cur, st->next);
+    if (!st->active) st->force = 0;                   // a FORCE flag of the filter in force stays in force
+    st->active = true; st->n = n; st->allowed = allowed;
+    st->nlist = 0; st->lists_without = 0;            // lsq_filter_layout rebuilds the layout-order bits
+    return LSQ_OK;
+}
+
+// ---- lsq_index_compact's part: the compact form of the layout -- the positions of the allowed rows, ascending -- from the layout-order bitmap and its
+// prefix by the kernel that makes the row list; lpre[nwords] = their number = allowed
+int lsq_filter_layout_rows(hipStream_t s, lsq_filter_state *st, int64_t n, const int **lsel) {
+    if (!lsq_filter_active(st) || st->nlist < 1) { lsq_set_error("lsq_index_compact: the filter has no bits in layout order"); return LSQ_EINVAL; }
+    const int64_t nwords = (n + 31) / 32;
+    LSQ_TRY(st->lrows.ensure(sizeof(int) * (size_t)(st->allowed > 0 ? st->allowed : 1)));
+    hipLaunchKernelGGL(flt_compact_kernel, dim3(blocks_for(nwords)), dim3(FLT_THREADS), 0, s, st->lbits.as<uint32_t>(), st->lpre.as<int>(), nwords, st->lrows.as<int>());
+    LSQ_HIP(hipGetLastError());
+    *lsel = st->lrows.as<int>();
+    return LSQ_OK;
 }
 
 int lsq_filter_layout(hipStream_t s, lsq_filter_state *st, const int *ids, const int *off, int64_t n, int nlist) {

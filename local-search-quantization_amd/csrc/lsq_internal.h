@@ -8,6 +8,7 @@
 
 #include "../../include/lsq_mi355x.h"
 #include "lsq_grow_check.h"
+#include "lsq_compact_check.h"
 
 #define LSQ_H 256          // candidates per codebook: one wave x float4 per lane
 #define LSQ_MAX_M 16
@@ -412,6 +413,7 @@ struct lsq_filter_view {
     const uint32_t *lbits = nullptr;
     const int *lpre = nullptr;
     int force = 0;                           // LSQ_FILTER_FORCE_DENSE / LSQ_FILTER_FORCE_COMPACT / 0
+    const int *pre = nullptr;                // the exclusive prefix [ceil(n/32) + 1] of the popcounts of bits' words (lsq_index_compact: a row's rank)
 };
 // desc as lsq_index_set_filter takes it (never null here).  A refusal leaves *st as it was.  The call waits for the device (the count comes back)
 int lsq_filter_set(hipStream_t s, lsq_filter_state **st, int64_t n, const lsq_filter_desc *desc);
@@ -476,6 +478,36 @@ void lsq_ivf_add_commit(lsq_ivf_state *st, int64_t count);
 // commit puts it in force (the layout-order bits are then lsq_filter_layout's to rebuild).  Both do nothing without an active filter
 int lsq_filter_grow(hipStream_t s, lsq_filter_state *st, int64_t n_new);
 void lsq_filter_grow_commit(lsq_filter_state *st, int64_t n_new);
+
+// ---- removing rows from a resident index (lsq_compact.hip: the new kernels; the states' own parts live beside the states) -----------------------------
+// one stream gathered: dst row j = src row sel[j], rows rowb bytes apart in both, rows_out rows of which the last is lastb <= rowb bytes long.  dst is
+// 16-byte aligned and holds the stream's bytes; every dword read of src holds a wanted byte.  *bytes (optional) += the destination bytes
+int lsq_compact_launch_gather(hipStream_t s, const void *src, void *dst, const int *sel, int64_t rowb, int64_t rows_out, int64_t lastb, int64_t *bytes);
+// the inverted layout of the survivors, out of place: position j of dst = position lsel[j] of src (lsel: the set bits of lbits, ascending), its id the rank
+// of the old id under (bits, pre); noff[l] = the set bits of lbits below off[l]
+struct lsq_compact_layout {
+    const uint8_t *src_codes; const float *src_norms; const int *src_ids; const int *off;
+    uint8_t *dst_codes; float *dst_norms; int *dst_ids; int *noff;
+    const uint32_t *lbits; const int *lpre; const int *lsel; const uint32_t *bits; const int *pre;
+    int64_t rows_out; int nlist, rowb;
+};
+int lsq_compact_launch_layout(hipStream_t s, const lsq_compact_layout &g, int64_t *bytes);
+// the caller's maps in id_base (either may be null): new_of_old [n] (-1: removed), old_of_new [allowed].  bits == null: identities (rows is not read)
+int lsq_compact_launch_maps(hipStream_t s, const uint32_t *bits, const int *pre, const int *rows, int64_t n, int64_t allowed, int id_base, int *old_of_new,
+                            int *new_of_old);
+// an owned buffer re-allocated to exactly `bytes` with its first `keep` bytes (allocate, copy, swap, free); nothing to do for an empty one or a view
+int lsq_devbuf_fit(hipStream_t s, DevBuf &b, size_t bytes, size_t keep);
+// the filter's part (lsq_filter.hip).  remove: the filter in force (or every row) minus the given rows, built beside it and put in force -- *bad: ids
+// outside [id_base, id_base + n), then nothing has changed; *cleared: the bits newly cleared.  The call waits.  layout_rows: the set bits of the
+// layout-order bitmap, ascending ([allowed] ints of the filter's scratch, valid until the next filter call)
+int lsq_filter_remove(hipStream_t s, lsq_filter_state **st, int64_t n, const int32_t *ids, int64_t count, int id_base, int on_device, unsigned *bad,
+                      int64_t *cleared);
+int lsq_filter_layout_rows(hipStream_t s, lsq_filter_state *st, int64_t n, const int **lsel);
+// the inverted lists' part (lsq_ivf.hip).  compact: the layout of the rows_out survivors written into the spare half (sized cap_rows; exact: re-allocated
+// to just that); commit: the spare half becomes the layout of rows_out rows; fit: both halves re-allocated to exactly `rows` rows, contents kept
+int lsq_ivf_compact(hipStream_t s, lsq_ivf_state *st, const lsq_filter_view &v, const int *lsel, int64_t rows_out, int64_t cap_rows, bool exact, int64_t *bytes);
+void lsq_ivf_compact_commit(lsq_ivf_state *st, int64_t rows_out);
+int lsq_ivf_fit(hipStream_t s, lsq_ivf_state *st, int64_t rows);
 
 // ---- what a handle that lives in a file of its own (lsq_partition.hip) needs of its context (lsq_api.hip): its device made current, the stream it is bound
 // to now, option "profile".  Nothing of the context is written ------------------------------------------------------------------------------------------

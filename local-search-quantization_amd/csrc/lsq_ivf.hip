@@ -411,6 +411,41 @@ void lsq_ivf_add_commit(lsq_ivf_state *st, int64_t count) {
     st->n += count;
 }
 
+// ---- lsq_index_compact's part (the kernels: lsq_compact.hip) ----------------------------------------------------------------------------------------------
+// The layout of the surviving rows is written into the spare half and swapped in at the commit, as an add's merge is.  exact (LSQ_COMPACT_SHRINK): the
+// spare half is dropped and made again at just cap_rows rows (it holds nothing); the other half follows after the commit (lsq_ivf_fit)
+int lsq_ivf_compact(hipStream_t s, lsq_ivf_state *st, const lsq_filter_view &v, const int *lsel, int64_t rows_out, int64_t cap_rows, bool exact, int64_t *bytes) {
+    if (exact) { st->alt_codes.release(); st->alt_norms.release(); st->alt_ids.release(); }
+    int moved = 0;
+    LSQ_TRY(ivf_ensure_spare(st, cap_rows, &moved));
+    lsq_compact_layout g{};
+    g.src_codes = st->codes.as<uint8_t>(); g.src_norms = st->packed ? nullptr : st->norms.as<float>(); g.src_ids = st->ids.as<int>(); g.off = st->off.as<int>();
+    g.dst_codes = st->alt_codes.as<uint8_t>(); g.dst_norms = st->packed ? nullptr : st->alt_norms.as<float>(); g.dst_ids = st->alt_ids.as<int>();
+    g.noff = st->alt_off.as<int>();
+    g.lbits = v.lbits; g.lpre = v.lpre; g.lsel = lsel; g.bits = v.bits; g.pre = v.pre;
+    g.rows_out = rows_out; g.nlist = st->nlist; g.rowb = st->packed ? st->m + 1 : st->m;
+    return lsq_compact_launch_layout(s, g, bytes);
+}
+
+void lsq_ivf_compact_commit(lsq_ivf_state *st, int64_t rows_out) {
+    std::swap(st->codes, st->alt_codes);
+    std::swap(st->norms, st->alt_norms);
+    std::swap(st->ids, st->alt_ids);
+    std::swap(st->off, st->alt_off);
+    st->n = rows_out;
+}
+
+int lsq_ivf_fit(hipStream_t s, lsq_ivf_state *st, int64_t rows) {
+    if (!st || st->nlist < 1) return LSQ_OK;
+    const size_t rowb = (size_t)(st->packed ? st->m + 1 : st->m), n = (size_t)st->n;
+    LSQ_TRY(lsq_devbuf_fit(s, st->codes, ivf_code_bytes(st, rows), n * rowb));
+    if (!st->packed) LSQ_TRY(lsq_devbuf_fit(s, st->norms, sizeof(float) * (size_t)rows, sizeof(float) * n));
+    LSQ_TRY(lsq_devbuf_fit(s, st->ids, sizeof(int) * (size_t)rows, sizeof(int) * n));
+    LSQ_TRY(lsq_devbuf_fit(s, st->alt_codes, ivf_code_bytes(st, rows), 0));
+    if (!st->packed) LSQ_TRY(lsq_devbuf_fit(s, st->alt_norms, sizeof(float) * (size_t)rows, 0));
+    return lsq_devbuf_fit(s, st->alt_ids, sizeof(int) * (size_t)rows, 0);
+}
+
 namespace {
 
 struct Chunk {                       // one run of queries whose plan fits the scratch: everything below counts queries from its first

@@ -930,6 +930,41 @@ class Index(_Handle):
         """n, capacity_rows, adds, rows_added, reallocations, adopted, merged_rows (last add), append_ms / merge_ms / filter_ms (last add, with profile=True)"""
         return self._info("lsq_index_get_growth_info", _lib.IndexGrowthInfo)
 
+    def remove(self, ids, id_base=0):
+        """Hide rows for good: ids (count,) int32 row ids in id_base, a numpy array or a torch device tensor on either kind of index; duplicates and rows
+        already removed are legal.  Every call then answers as after set_filter(the allowed rows in force, or all rows, minus these); a forced road of
+        the filter in force stays.  An id outside the index refuses the call and changes nothing.  The rows still occupy memory and scan time until
+        compact()   [lsq_index_remove]"""
+        side = _DEVICE if getattr(ids, "is_cuda", False) else _HOST
+        ids = side.take(ids, _I32, "ids")
+        _shapes(("ids", ids, (None,)))
+        count = int(ids.shape[0])
+        self._eng._call(side, "lsq_index_remove", side.ptr(ids) if count else None, count, int(id_base), int(side.dev), h=self._h)
+
+    def compact(self, shrink=False, want_map=True):
+        """The rows outside the filter in force LEAVE the index (no filter: none does): the survivors keep their order and become rows 0 .. n' - 1, every
+        call then answers bit for bit as on an index freshly built over them, and the filter is gone.  shrink: the storage is sized to n' rows instead of
+        keeping its capacity for later adds.  -> old_of_new (n',) int32 0-based, the former row of every row (numpy on a host index, a device tensor on a
+        device index); None with want_map=False.  Index.n follows   [lsq_index_compact]"""
+        side = self._side
+        desc = _lib.IndexCompactDesc()
+        desc.flags, desc.id_base, desc.on_device = (_lib.COMPACT_SHRINK if shrink else 0), 0, int(side.dev)
+        out = None
+        if want_map:
+            info = self.filter_info()
+            out = side.new((int(info["allowed"] if info["active"] else info["n"]),), _I32, self._eng._device() if side.dev else None)
+            desc.old_of_new = side.ptr(out) if out.shape[0] else None
+        try:
+            self._eng._call(side, "lsq_index_compact", C.byref(desc), h=self._h)
+        finally:
+            self.n = int(self.growth_info()["n"])
+        return out
+
+    def compact_info(self):
+        """n_before / n_after / moved_bytes / shrunk (last compact), removes, rows_tombstoned, compactions, rows_dropped (since creation), tombstone_ms (last
+        remove) and gather_ms / layout_ms (last compact) with profile=True"""
+        return self._info("lsq_index_get_compact_info", _lib.IndexCompactInfo)
+
 
 # -- the beam-search encoder (made by Engine.encoder / Engine.encoder_dev) ------------------------
 

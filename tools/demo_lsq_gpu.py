@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--delete FRACTION] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -38,6 +38,11 @@ two coincide exactly depends on the encoder being deterministic per row under gl
 --filter FRACTION: a seeded random mask that allows about FRACTION of the base rows is laid over a resident index (Index.set_filter); the ADC search -- and,
 where given, the --ivf and --rerank variants -- then answer over the allowed rows alone, and their recall is taken against Index.knn under the SAME mask on
 the same resident base rows.  The reference has no such search.
+
+--delete FRACTION (alone or beside --ivf, --residual, --grow, whose sections run as before): a seeded random FRACTION of the base rows is removed from a
+resident index (Index.remove: tombstones) and the recall of the ADC search -- and of the --ivf search over the same codes -- is taken against Index.knn over
+the rows that are left; then Index.compact makes the rows leave, the same searches run again, and their ids, taken back through old_of_new, must name the
+same rows: the demo asserts it and prints the two recall curves side by side.
 
 needs $LSQ_DATA_DIR/sift/{sift_learn,sift_base,sift_query}.fvecs and sift_groundtruth.ivecs (TEXMEX layout).  The file's ground truth
 describes the full 10^6-vector base only: for a prefix of it (nread_base < 10^6) and for the stand-in, the ground truth is exact k-NN of the base
@@ -222,6 +227,15 @@ def main():
         except (ValueError, AssertionError, IndexError):
             raise SystemExit("--filter takes a FRACTION in (0, 1]")
         del argv[at:at + 2]
+    delete = None
+    if "--delete" in argv:
+        at = argv.index("--delete")
+        try:
+            delete = float(argv[at + 1])
+            assert 0.0 < delete < 1.0
+        except (ValueError, AssertionError, IndexError):
+            raise SystemExit("--delete takes a FRACTION in (0, 1)")
+        del argv[at:at + 2]
     grow = None
     if "--grow" in argv:
         at = argv.index("--grow")
@@ -348,6 +362,50 @@ def main():
                       + ("         %.4f" % grec[i - 1] if grow else "") + ("      %.4f" % gres[i - 1] if gres is not None else ""))
     if fraction is not None:
         filtered_recall(fraction, name, x_base, x_query, B_base, C, db_norms, m, knn, shortlist, ivf)
+    if delete is not None:
+        deleted_recall(delete, name, x_base, x_query, B_base, C, db_norms, m, knn, ivf)
+
+
+def deleted_recall(fraction, name, x_base, x_query, B_base, C, db_norms, m, knn, ivf):
+    """--delete: a seeded random fraction of the rows removed (Index.remove: tombstones), the recall of the searches over the rest against Index.knn over
+    the rest; then Index.compact -- the rows leave --, the same searches again, and their ids, taken back through old_of_new, must be the same sets"""
+    n = x_base.shape[1]
+    gone = np.flatnonzero(np.random.default_rng(1).random(n) < fraction).astype(np.int32)
+    gone = gone[: n - 1]                                                     # an index holds at least one row
+    rows = np.ascontiguousarray(x_base.T)
+    Q = np.ascontiguousarray(x_query.T.astype(np.float32))
+    keep = max(1, min(knn, n - gone.shape[0]))
+    with lsq.Engine(0) as eng, eng.index((B_base - 1).astype(np.uint8).T, np.ascontiguousarray(np.hstack(C).T), db_norms, m, base=rows) as ix:
+        nprobe = 0
+        if ivf:
+            nlist = min(ivf[0], n)
+            nprobe = min(ivf[1], nlist)
+            cent, assign = lsq.train_coarse(np.asarray(rows, dtype=np.float32), nlist, niter=10, seed=0, engine=eng)
+            ix.set_lists(cent, assign)
+
+        def curves(back):
+            """name -> (recall curve, ids 1-based in the numbering before the compact); back: None, or old_of_new"""
+            to_old = (lambda ids: ids) if back is None else (lambda ids: np.where(ids > 0, back[np.maximum(ids, 1) - 1] + 1, 0))
+            _, truth = ix.knn(Q, 1, id_base=1)                               # the ground truth: exact k-NN over the rows that are left
+            gt = to_old(truth)[:, 0].astype(np.uint32)
+            out = {}
+            for label, ids in [("ADC", ix.search(Q, keep)[1])] + ([("IVF %d:%d" % (nlist, nprobe), ix.search_ivf(Q, keep, nprobe)[1])] if ivf else []):
+                ids = to_old(ids)
+                out[label] = (lsq.eval_recall(gt, np.ascontiguousarray(ids.T).astype(np.uint32), keep), ids)
+            return out
+        ix.remove(gone)
+        under = curves(None)
+        old_of_new = ix.compact()
+        after = curves(old_of_new)
+        info = ix.compact_info()
+    print("Deleted %d of %d rows (Index.remove), then compacted to %d rows (Index.compact, %d bytes moved)" % (gone.shape[0], n, info["n_after"], info["moved_bytes"]))
+    print("     r@   " + "   ".join("%-24s" % (k + " tombstones / compact") for k in under))
+    for i in (1, 2, 5, 10, 20, 50, 100, 200, 500, 1000):
+        if i <= keep:
+            print("%7d   " % i + "   ".join("%-.4f / %-15.4f" % (under[k][0][i - 1], after[k][0][i - 1]) for k in under))
+    for k in under:
+        assert np.array_equal(np.sort(under[k][1], axis=1), np.sort(after[k][1], axis=1)), "%s: the ids after the compact are not the ids under the tombstones" % k
+    print("%s: recall@1 after deleting a fraction of %g = %.4f; the answers under tombstones and after the compact name the same rows" % (name, fraction, under["ADC"][0][0]))
 
 
 def filtered_recall(fraction, name, x_base, x_query, B_base, C, db_norms, m, knn, shortlist, ivf):
