@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 2200
+#define LSQ_VERSION 2300
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -138,6 +138,8 @@ LSQ_API int lsq_set_stream(lsq_ctx *ctx, void *hip_stream);
  *   "rerank_batch" (default 0): queries per batch of the re-rank stage of every lsq_index created on this context; 0 = automatic (batches of at most
  *        2^28 (query, candidate) records, like the scans).  A test hook: small shapes cross batch boundaries.  Same results.
  *   "knn_u8_int" (0/1, default 1): 0 = lsq_index_knn widens 8-bit rows and queries even where its integer road applies.  A test hook: same results.
+ *   "range_batch" (default 0): records per fill batch of lsq_index_range_search on every lsq_index created on this context; 0 = automatic (2^28).  A
+ *        test hook: small shapes cross batch boundaries, and a query larger than the budget is a batch of its own.  Same results.
  *   (liblsq_mi355x_tuning.so only) "ablation": timing-only kernel variants whose results are garbage. */
 LSQ_API int lsq_set_option(lsq_ctx *ctx, const char *key, int64_t value);
 LSQ_API int lsq_get_timings(lsq_ctx *ctx, lsq_timings *out);      /* writes the v400 layout only (everything before table_reuses: a caller built against any header since v400 is never overrun); the fields appended since come through: */
@@ -780,6 +782,57 @@ typedef struct lsq_index_compact_info {
 LSQ_API int lsq_index_remove (lsq_index *ix, const int32_t *ids, int64_t count, int id_base, int on_device);
 LSQ_API int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *desc);   /* desc == NULL: no map wanted, no flags */
 LSQ_API int lsq_index_get_compact_info(lsq_index *ix, lsq_index_compact_info *out);
+
+/* ---- (3m) range search on the resident index: every row within a radius (csrc/lsq_range.hip; since v2300) ----------------------------------------------
+ * THE REFERENCE HAS NO COUNTERPART.  For every query q with radius r_q the result is every (dist(q, i), id_i) over the CANDIDATE ROWS i with
+ * dist(q, i) <= r_q, in (dist, id) lexicographic order -- no padding, no truncation, a result of variable length.
+ *   candidates   nprobe == 0: every row of the index.  nprobe >= 1: the rows of the query's nprobe nearest lists, chosen as lsq_index_search_ivf chooses
+ *                them.  Under a row filter (3j): the allowed rows among those.
+ *   dist         bit for bit the value lsq_index_search (nprobe == 0) or lsq_index_search_ivf (nprobe >= 1, with or without LSQ_IVF_ADD_COARSE) gives
+ *                the same (query, row): the same tables, the same add order, the norm last, then the coarse add.
+ *   comparison   IEEE <=: a NaN distance or a NaN radius returns nothing; r = +inf returns every candidate with a non-NaN distance, r = -inf nothing.
+ *                Ties go to the smaller id.  Ids are original rows, 1-based, as the two search calls return them.
+ *   identity     THE RESULT OF q IS THE LONGEST PREFIX WITH dist <= r_q OF THE FULL RANKING THE EXISTING CALL RETURNS FOR nn = (all candidate rows), with
+ *                that ranking's own (+inf, 0) padding dropped.  So a packed index answers as the plain index with dbnorms[i] = cbnorms[c_i]; nprobe ==
+ *                nlist without a flag answers as nprobe == 0; after add / remove / compact the result is that of the index identities G / R / C name.
+ *   two passes   a COUNT pass and a FILL pass walk the same rows: the counts size every query's segment exactly, nothing overflows and nothing is redone.
+ *                The fill runs in batches of at most 2^28 records (option "range_batch": a test hook; the results are the same for every value); a
+ *                query larger than the budget is a batch of its own.
+ * lsq_index_range_search writes lims [nq + 1] as a CSR -- query q's results are entries lims[q] .. lims[q + 1] - 1, lims[0] = 0 -- and HOLDS the result in
+ * device buffers owned by the index (8 bytes per result).  It waits for the device (the counts come back to plan the batches).  nq == 0: LSQ_OK,
+ * lims[0] = 0, an empty held result.  lsq_index_range_fetch copies the held result of the last successful range search: exactly lims[nq] entries of
+ * each array; capacity < lims[nq], or no held result: LSQ_EINVAL and nothing written.  It may be called more than once.  The held result is dropped, and
+ * its memory released, by the next range search on the index and by every call that changes what a search would see: lsq_index_add / _remove with
+ * count > 0, lsq_index_compact, lsq_index_set_lists, lsq_index_set_filter.  Search calls do not drop it.
+ * lsq_range_search_cpu is the host drop-in and the engine-less road: plain arrays, no context, std::thread workers, the arithmetic of
+ * lsq_linscan_aqd_query_extra_byte and lsq_ivf_search_cpu.  centroids == NULL or nprobe == 0: every row; else list_of_row [n], nlist, nprobe, flags as
+ * lsq_ivf_search_cpu takes them.  allowed (optional): [n] bytes, non-zero = the row is a candidate.  Two-call protocol: lims is always written; dists / ids
+ * are written only if lims[nq] <= capacity (and both are non-null), and are otherwise untouched.
+ * LSQ_EINVAL, nothing launched: a null handle or pointer (q_coarse may be null: q_scan), an index without codes, nq < 0, ldq < d, nprobe < 0, nprobe >= 1
+ * before lsq_index_set_lists, nprobe > nlist, a flag other than LSQ_IVF_ADD_COARSE, LSQ_IVF_ADD_COARSE with nprobe == 0.  A refused call leaves a held
+ * result as it was. */
+typedef struct lsq_range_info {          /* the last lsq_index_range_search call; fields are only ever appended */
+    int64_t queries;
+    int64_t rows_walked;         /* rows one pass read, summed over the queries (every row / the allowed rows / the probed lists' rows) */
+    int64_t results;             /* = lims[nq] */
+    int64_t max_per_query;
+    int64_t batches;             /* fill batches launched (a batch without records launches nothing and is not counted) */
+    int64_t road;                /* 0 unfiltered, 1 dense (the bitmap beside every row), 2 compact (the allowed rows alone); 0 or 1 with nprobe >= 1 */
+    int64_t held_bytes;          /* device bytes of the held result */
+    double coarse_ms, lut_ms, count_ms, fill_ms, sort_ms;      /* with option "profile" = 1; sort_ms includes the hand-out */
+} lsq_range_info;
+/* nprobe == 0: every row (no lists needed; q_coarse ignored).  nprobe >= 1: the probed lists, rule and flags of lsq_index_search_ivf
+ * (LSQ_IVF_ADD_COARSE; q_coarse NULL = q_scan).  radius [nq] f32, q_scan / q_coarse [nq][ldq]; lims [nq + 1] int64 out.
+ * on_device: 0 = q_scan, q_coarse, radius, lims are host arrays, 1 = device arrays. */
+LSQ_API int lsq_index_range_search(lsq_index *ix, int64_t *lims, const float *q_scan, const float *q_coarse, const float *radius,
+                                   int nq, int ldq, int nprobe, int flags, int on_device);
+/* dists / ids [capacity]: host (on_device = 0) or device arrays, whatever the form of the search that made the result */
+LSQ_API int lsq_index_range_fetch(lsq_index *ix, float *dists, int *ids, int64_t capacity, int on_device);
+LSQ_API int lsq_index_get_range_info(lsq_index *ix, lsq_range_info *out);
+LSQ_API int lsq_range_search_cpu(int64_t *lims, float *dists, int *ids, int64_t capacity, const uint8_t *codes, const float *codebooks,
+                                 const float *dbnorms, const float *centroids, const int32_t *list_of_row, int nlist, int nprobe, int flags,
+                                 const uint8_t *allowed, const float *q_scan, const float *q_coarse, const float *radius, int n, int m, int h, int d,
+                                 int nq, int ldq, int nthreads);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

@@ -112,6 +112,12 @@ class IndexCompactInfo(_Struct):
                 ("layout_ms", C.c_double)]
 
 
+class RangeInfo(_Struct):
+    _fields_ = [("queries", C.c_int64), ("rows_walked", C.c_int64), ("results", C.c_int64), ("max_per_query", C.c_int64), ("batches", C.c_int64),
+                ("road", C.c_int64), ("held_bytes", C.c_int64), ("coarse_ms", C.c_double), ("lut_ms", C.c_double), ("count_ms", C.c_double),
+                ("fill_ms", C.c_double), ("sort_ms", C.c_double)]
+
+
 COMPACT_SHRINK = 1
 FILTER_BITS, FILTER_BYTES, FILTER_IDS = 0, 1, 2
 FILTER_DENY, FILTER_FORCE_DENSE, FILTER_FORCE_COMPACT = 1, 2, 4
@@ -237,6 +243,11 @@ SIGNATURES = {
     "lsq_index_remove": (_i, [_vp, _vp, _i64, _i, _i]),
     "lsq_index_compact": (_i, [_vp, C.POINTER(IndexCompactDesc)]),
     "lsq_index_get_compact_info": (_i, [_vp, C.POINTER(IndexCompactInfo)]),
+    # range search on the index: every row within a radius, and its host drop-in (since v2300)
+    "lsq_index_range_search": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "lsq_index_range_fetch": (_i, [_vp, _vp, _vp, _i64, _i]),
+    "lsq_index_get_range_info": (_i, [_vp, C.POINTER(RangeInfo)]),
+    "lsq_range_search_cpu": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),
@@ -278,7 +289,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 2200     # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 2300     # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

@@ -110,6 +110,7 @@ struct lsq_ctx {
     lsq_search_opts search;                            // options "linscan_exhaustive", "linscan_rank": test hooks of the scan's selection (search_opts fills in the rest per call)
     int knn_u8_int = 1;                                // option "knn_u8_int": 0 = lsq_index_knn widens 8-bit rows and queries even where the integer road applies; a test hook
     int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
+    int64_t range_batch = 0;                           // option "range_batch": records per fill batch of lsq_index_range_search (0 = automatic); a test hook
     // Staging for the host-buffer entry points.  Who writes what (a later call may assume NOTHING of their contents, except sK under tables_valid):
     //   sX, sX2  X: one chunk at a time, double-buffered, by the pipelined encode; the whole X by stage_X
     //   sK       the call's codebooks: uploaded (host_codebooks; claim_sK: K, K_prev) or computed into it (claim_sK: LSQR, SPGL1, the seeding).
@@ -317,6 +318,10 @@ extern "C" int lsq_set_option(lsq_ctx *c, const char *key, int64_t value) {
     else if (!strcmp(key, "rerank_batch")) {
         if (value < 0) { lsq_set_error("rerank_batch must be >= 0"); return LSQ_EINVAL; }
         c->rerank_batch = value;
+    }
+    else if (!strcmp(key, "range_batch")) {
+        if (value < 0 || value > LSQ_RANGE_BATCH_RECORDS) { lsq_set_error("range_batch must lie in 0..2^28"); return LSQ_EINVAL; }
+        c->range_batch = value;
     }
     else if (!strcmp(key, "ils_counter")) {
         if (value < 0 || value >= (int64_t)LSQ_IT_AUTO) { lsq_set_error("ils_counter must lie in 0..2^32-2"); return LSQ_EINVAL; }
@@ -568,6 +573,8 @@ struct lsq_index {
     lsq_index_compact_info cinfo{};                    // lsq_index_remove / _compact
     DevBuf c_old, c_new;                               // lsq_index_compact into host arrays: the maps on the device
     PhaseClock<3> cclock;                              // a remove's tombstones; a compact's gather and layout phases
+    lsq_range_state *range = nullptr;                  // range search (lsq_range.hip): its scratch and the HELD result of the last one; null until the first
+    DevBuf s_radius;                                   // lsq_index_range_search's staging of host radii
 };
 
 // the filter as a scan over all rows takes it: nothing without one; else the compact road -- the ascending list of allowed rows -- where the measured rule
@@ -589,8 +596,9 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     (void)hipStreamSynchronize(ix->ctx->stream);
     DevBuf *bufs[] = {&ix->own_codes, &ix->own_K, &ix->own_norms, &ix->own_base, &ix->rec_a, &ix->rec_b, &ix->seg, &ix->counter, &ix->short_d, &ix->short_i,
                       &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q, &ix->s_qcoarse, &ix->g_codes, &ix->g_nc, &ix->g_rows,
-                      &ix->c_old, &ix->c_new};
+                      &ix->c_old, &ix->c_new, &ix->s_radius};
     for (DevBuf *b : bufs) b->release();
+    lsq_range_free(ix->range);
     ix->gclock.release();
     ix->cclock.release();
     lsq_adc_free(ix->adc);
@@ -983,6 +991,7 @@ extern "C" int lsq_index_set_lists(lsq_index *ix, const lsq_ivf_desc *desc) {
     if (!desc->centroids || !desc->list_of_row) { lsq_set_error("lsq_index_set_lists: null pointer"); return LSQ_EINVAL; }
     LSQ_TRY(use_device(ix->ctx));
     LSQ_TRY(lsq_ivf_set_lists(ix->ctx->stream, &ix->ivf, ix->codes, ix->norms, ix->packed, ix->n, ix->m, ix->d, desc));
+    lsq_range_drop(ix->range);
     if (ix->cap_rows > ix->n) {                       // an index with capacity (lsq_index_reserve / _add): the layout's halves get it too
         int moved = 0;
         LSQ_TRY(lsq_ivf_reserve(ix->ctx->stream, ix->ivf, ix->cap_rows, &moved));
@@ -1024,12 +1033,85 @@ extern "C" int lsq_index_get_ivf_info(lsq_index *ix, lsq_ivf_info *out) {
     return LSQ_OK;
 }
 
+// ---- range search on the index (lsq_range.hip): every candidate row within a radius; the result is HELD by the index until fetched or dropped ----
+extern "C" int lsq_index_range_search(lsq_index *ix, int64_t *lims, const float *q_scan, const float *q_coarse, const float *radius, int nq, int ldq,
+                                      int nprobe, int flags, int on_device) {
+    const char *fn = "lsq_index_range_search";
+    if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
+    const int nlist = lsq_ivf_nlist(ix->ivf);
+    if (const char *why = lsq_range_refusal(lims, q_scan, radius, ix->codes != nullptr, nlist, ix->d, nq, ldq, nprobe, flags)) {
+        lsq_set_error("%s: %s (nq=%d ldq=%d d=%d nprobe=%d nlist=%d flags=%d)", fn, why, nq, ldq, ix->d, nprobe, nlist, flags);
+        return LSQ_EINVAL;
+    }
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    const bool dev = on_device != 0;
+    lsq_range_call call;
+    call.nq = nq; call.nprobe = nprobe; call.flags = flags;
+    call.budget = lsq_range_budget(c->range_batch);
+    call.timed = c->profile ? 1 : 0;
+    call.in = lsq_input(ix->codes, nullptr, ix->K, ix->norms, (int)ix->n, ix->m, ix->d);
+    if (ix->packed) { call.in.packed = 1; call.in.cstride = ix->m + 1; }      // rows with their norm byte; norms is the table
+    const bool filtered = lsq_filter_active(ix->filter);
+    if (nprobe == 0) {
+        // the filter's road: compact when forced, or when at most half of the rows are allowed.  The selection-cost band of lsq_filter_compact_by_default
+        // does not apply: nothing is selected here, the walk is all there is
+        if (filtered) {
+            const lsq_filter_view v = lsq_filter_get(ix->filter);
+            const bool compact = v.force == LSQ_FILTER_FORCE_COMPACT || (v.force == 0 && v.allowed <= lsq_filter_crossover(ix->n));
+            if (compact) { call.in.filter_rows = v.rows; call.in.filter_count = (int)v.allowed; }
+            else call.in.filter_bits = v.bits;
+            call.road = compact ? 2 : 1;
+        }
+    } else {
+        if (filtered) {
+            const lsq_filter_view v = lsq_filter_get(ix->filter);
+            if (!v.lbits) { lsq_set_error("%s: the filter has no bits in layout order (a failed lsq_index_set_lists / _set_filter?)", fn); return LSQ_EINVAL; }
+            call.lbits = v.lbits;
+            call.road = 1;
+        }
+        call.ivf = ix->ivf; call.adc = &ix->adc; call.coarse = c->search;
+    }
+    std::vector<int64_t> staged;
+    int64_t *h_lims = lims;
+    if (dev) { staged.resize((size_t)nq + 1); h_lims = staged.data(); call.lims_dev = lims; }
+    if (nq > 0) {
+        // the scan reads query rows d floats apart, the coarse search rows as they lie; the host form stages both, and the radii
+        IndexCall rows{ix, nq, dev};
+        const float *dqs = nullptr, *dqc = nullptr, *drad = nullptr;
+        int64_t ld = 0, ldc = 0, ldr = 0;
+        LSQ_TRY(rows.rows(ix->s_qscan, q_scan, sizeof(float), ldq, ix->d, true, !dev || ldq != ix->d, &dqs, &ld));
+        if (nprobe >= 1) LSQ_TRY(rows.rows(ix->s_qcoarse, q_coarse ? q_coarse : q_scan, sizeof(float), ldq, ix->d, false, !dev, &dqc, &ldc));
+        LSQ_TRY(rows.rows(ix->s_radius, radius, sizeof(float), 1, 1, false, !dev, &drad, &ldr));
+        call.in.Q = dqs; call.in.qstride = ix->d;
+        call.q_coarse = dqc; call.ldc = ldc; call.radius = drad;
+    }
+    lsq_filter_note_road(ix->filter, call.road);
+    LSQ_TRY(lsq_range_search(s, &ix->range, call, h_lims));
+    ix->stats.queries += nq;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_range_fetch(lsq_index *ix, float *dists, int *ids, int64_t capacity, int on_device) {
+    if (!ix) { lsq_set_error("lsq_index_range_fetch: null index"); return LSQ_EINVAL; }
+    LSQ_TRY(use_device(ix->ctx));
+    return lsq_range_fetch(ix->ctx->stream, ix->range, dists, ids, capacity, on_device);
+}
+
+extern "C" int lsq_index_get_range_info(lsq_index *ix, lsq_range_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_range_info: null argument"); return LSQ_EINVAL; }
+    lsq_range_get_info(ix->range, out);
+    return LSQ_OK;
+}
+
 // ---- row filters on the index (lsq_filter.hip): the allowed rows, owned; lsq_index_search, _search_ivf and _knn answer over them alone --------------------
 extern "C" int lsq_index_set_filter(lsq_index *ix, const lsq_filter_desc *desc) {
     if (!ix) { lsq_set_error("lsq_index_set_filter: null index"); return LSQ_EINVAL; }
-    if (!desc) { lsq_filter_clear(ix->filter); return LSQ_OK; }
+    if (!desc) { lsq_filter_clear(ix->filter); lsq_range_drop(ix->range); return LSQ_OK; }
     LSQ_TRY(use_device(ix->ctx));
     LSQ_TRY(lsq_filter_set(ix->ctx->stream, &ix->filter, ix->n, desc));
+    lsq_range_drop(ix->range);
     return index_filter_layout(ix);
 }
 
@@ -1162,6 +1244,7 @@ extern "C" int lsq_index_add(lsq_index *ix, const lsq_index_add_desc *desc) {
     if (lists) lsq_ivf_add_commit(ix->ivf, count);
     lsq_filter_grow_commit(ix->filter, n + count);
     ix->n = n + count;
+    lsq_range_drop(ix->range);                        // a held range result answers for the former rows
     float ms[3];
     LSQ_TRY(ix->gclock.read(ms));
     ix->grow.adds += 1; ix->grow.rows_added += count; ix->grow.reallocations += moved;
@@ -1196,6 +1279,7 @@ extern "C" int lsq_index_remove(lsq_index *ix, const int32_t *ids, int64_t count
     int64_t cleared = 0;
     LSQ_TRY(lsq_filter_remove(s, &ix->filter, ix->n, ids, count, id_base, on_device, &bad, &cleared));
     if (bad) { lsq_set_error("%s: %u ids lie outside [%d, %lld)", fn, bad, id_base, (long long)(id_base + ix->n)); return LSQ_EINVAL; }
+    lsq_range_drop(ix->range);
     const int rc = index_filter_layout(ix);           // the layout-order bits follow the new filter
     LSQ_TRY(ix->cclock.mark(s));
     float ms[2];
@@ -1309,6 +1393,7 @@ extern "C" int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *de
         if (lists && shrink) (void)lsq_ivf_fit(s, ix->ivf, n2);      // the half that was the layout.  A failure costs nothing: the next add sizes it
         shrunk = shrink ? 1 : 0;
     }
+    lsq_range_drop(ix->range);
     ix->cinfo.n_before = n; ix->cinfo.n_after = n2;
     ix->cinfo.compactions += 1; ix->cinfo.rows_dropped += n - n2;
     ix->cinfo.moved_bytes = bytes; ix->cinfo.shrunk = shrunk;

@@ -9,6 +9,7 @@
 #include "../../include/lsq_mi355x.h"
 #include "lsq_grow_check.h"
 #include "lsq_compact_check.h"
+#include "lsq_range_check.h"
 
 #define LSQ_H 256          // candidates per codebook: one wave x float4 per lane
 #define LSQ_MAX_M 16
@@ -400,6 +401,39 @@ int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **st, const uint8_t *codes, c
 int lsq_ivf_search(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *K, float *dists, int *ids, const float *q_scan,
                    const float *q_coarse, int64_t ldc, int nq, int nprobe, int nn, int flags, const lsq_search_opts &coarse, int timed,
                    const struct lsq_filter_view *flt = nullptr);      // flt (lsq_filter.hip): its layout-order bits restrict the answer to the allowed rows
+
+// the coarse step of lsq_ivf_search on its own, for a scan outside lsq_ivf.hip (lsq_range.hip): the probed lists of nq queries in rank order and their
+// coarse distances ([nq][nprobe], device, in st's scratch: valid until the next call on st), and the layout they index
+struct lsq_ivf_probes {
+    const int *probe; const float *coarse;
+    const uint8_t *codes; const float *norms; const int *ids; const int *off;      // norms: per position, or (packed) the norm table of 256 floats
+    int64_t n; int nlist, m, d, packed;
+};
+int lsq_ivf_coarse(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *q_coarse, int64_t ldc, int nq, int nprobe, const lsq_search_opts &coarse,
+                   int timed, lsq_ivf_probes *out, double *coarse_ms);
+
+// ---- range search on a resident index (lsq_range.hip): every candidate row within a radius, held by the index until fetched or dropped ------------------
+struct lsq_range_state;
+void lsq_range_free(lsq_range_state *st);
+void lsq_range_drop(lsq_range_state *st);            // the held result leaves and its memory is released (st may be null)
+void lsq_range_get_info(const lsq_range_state *st, lsq_range_info *out);
+// one call, every pointer a device pointer.  in: the rows as lsq_adc_search takes them (kind LSQ, Q = q_scan rows d floats apart, a filter's road already
+// chosen); on the list road (nprobe >= 1) only Q, K, n, m, d of it are read and the rows are ivf's layout
+struct lsq_range_call {
+    lsq_search_input in;
+    const float *radius = nullptr;                   // [nq]
+    int nq = 0, nprobe = 0, flags = 0;
+    lsq_ivf_state *ivf = nullptr; lsq_adc_state **adc = nullptr;      // list road: the lists, and the scan state the coarse search runs on
+    const float *q_coarse = nullptr; int64_t ldc = 0;
+    lsq_search_opts coarse;                          // how the coarse search runs (the context's hooks)
+    const uint32_t *lbits = nullptr;                 // list road under a filter: its bits in layout order
+    int64_t budget = 0;                              // records per fill batch (lsq_range_budget)
+    int timed = 0, road = 0;
+    int64_t *lims_dev = nullptr;                     // optional: lims [nq + 1] also written here
+};
+// h_lims [nq + 1]: HOST.  Drops the former held result first; on success the new one is held.  Waits for the device
+int lsq_range_search(hipStream_t s, lsq_range_state **st, const lsq_range_call &call, int64_t *h_lims);
+int lsq_range_fetch(hipStream_t s, lsq_range_state *st, float *dists, int *ids, int64_t capacity, int on_device);
 
 // ---- row filters on a resident index (lsq_filter.hip): the set of allowed rows as the scans read it ---------------------------------------------------
 struct lsq_filter_state;

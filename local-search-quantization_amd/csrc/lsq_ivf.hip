@@ -446,6 +446,27 @@ int lsq_ivf_fit(hipStream_t s, lsq_ivf_state *st, int64_t rows) {
     return lsq_devbuf_fit(s, st->alt_ids, sizeof(int) * (size_t)rows, 0);
 }
 
+// the probed lists of nq queries: the exact search with the centroids as base, on the index's scan state -> st->ci (lists in rank order) and st->cd (their
+// coarse distances), [nq][nprobe].  out (optional): those two and the layout, for a scan outside this file (lsq_range.hip); valid until the next call on st
+int lsq_ivf_coarse(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *q_coarse, int64_t ldc, int nq, int nprobe, const lsq_search_opts &coarse,
+                   int timed, lsq_ivf_probes *out, double *coarse_ms) {
+    LSQ_TRY(st->cd.ensure(sizeof(float) * (size_t)nq * nprobe));
+    LSQ_TRY(st->ci.ensure(sizeof(int) * (size_t)nq * nprobe));
+    lsq_search_input ex{};
+    ex.kind = LSQ_SEARCH_EXACT; ex.Q = q_coarse; ex.qstride = (int)ldc; ex.n = st->nlist; ex.d = st->d; ex.base = st->cent.p; ex.bstride = st->d;
+    lsq_linscan_stats cs{};
+    lsq_search_opts co = coarse;
+    co.stats = &cs; co.timed = timed ? 1 : 0;
+    LSQ_TRY(lsq_adc_search(s, adc, st->cd.as<float>(), st->ci.as<int>(), ex, nq, nprobe, co));
+    if (coarse_ms) *coarse_ms = cs.lut_ms + cs.sample_ms + cs.scan_ms + cs.select_ms;
+    if (out) {
+        out->probe = st->ci.as<int>(); out->coarse = st->cd.as<float>();
+        out->codes = st->codes.as<uint8_t>(); out->norms = st->packed ? st->table : st->norms.as<float>(); out->ids = st->ids.as<int>(); out->off = st->off.as<int>();
+        out->n = st->n; out->nlist = st->nlist; out->m = st->m; out->d = st->d; out->packed = st->packed;
+    }
+    return LSQ_OK;
+}
+
 namespace {
 
 struct Chunk {                       // one run of queries whose plan fits the scratch: everything below counts queries from its first
@@ -529,16 +550,10 @@ int run_chunk(Chunk &c, const float *q_coarse, int64_t ldc, const lsq_search_opt
     lsq_ivf_state *st = c.st;
     hipStream_t s = c.s;
     const int nq = c.nq, nprobe = c.nprobe, nn = c.nn;
-    // the probed lists: the exact search with the centroids as base, on the index's scan state
-    LSQ_TRY(st->cd.ensure(sizeof(float) * (size_t)nq * nprobe));
-    LSQ_TRY(st->ci.ensure(sizeof(int) * (size_t)nq * nprobe));
-    lsq_search_input ex{};
-    ex.kind = LSQ_SEARCH_EXACT; ex.Q = q_coarse; ex.qstride = (int)ldc; ex.n = st->nlist; ex.d = st->d; ex.base = st->cent.p; ex.bstride = st->d;
-    lsq_linscan_stats cs{};
-    lsq_search_opts co = coarse;
-    co.stats = &cs; co.timed = c.timed ? 1 : 0;
-    LSQ_TRY(lsq_adc_search(s, c.adc, st->cd.as<float>(), st->ci.as<int>(), ex, nq, nprobe, co));
-    st->info.coarse_ms += cs.lut_ms + cs.sample_ms + cs.scan_ms + cs.select_ms;
+    // the probed lists
+    double coarse_ms = 0.0;
+    LSQ_TRY(lsq_ivf_coarse(s, st, c.adc, q_coarse, ldc, nq, nprobe, coarse, c.timed ? 1 : 0, nullptr, &coarse_ms));
+    st->info.coarse_ms += coarse_ms;
     // the plan
     LSQ_TRY(st->pos.ensure(sizeof(int) * (size_t)nq * ((size_t)nprobe + 1)));
     LSQ_TRY(st->plan.ensure(sizeof(int) * 3 * (size_t)nq));

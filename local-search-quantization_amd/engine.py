@@ -814,6 +814,38 @@ class Index(_Handle):
                         int(self._dev), h=self._h)
         return dists, ids
 
+    def range_search(self, Q_scan, radius, nprobe=0, Q_coarse=None, add_coarse=False):
+        """Every candidate row within `radius` of each query: radius a scalar or (nq,) float32, compared as dist <= radius (a NaN on either side returns
+        nothing).  nprobe=0: every row; nprobe>=1: the rows of the query's nprobe nearest lists, chosen and (add_coarse) measured as search_ivf does.
+        Under a filter: the allowed rows alone.  The distances are search()'s / search_ivf()'s own bits, so a query's result is the longest prefix
+        within the radius of the ranking those return for k = all candidate rows.
+        -> lims (nq+1,) int64, dists (lims[-1],) float32, ids (lims[-1],) int32 1-BASED: query q's results are entries lims[q] .. lims[q+1]-1, ascending by
+        (dist, id); numpy on an Engine.index, torch tensors on an Engine.index_dev   [lsq_index_range_search, lsq_index_range_fetch]"""
+        side, p = self._side, self._side.ptr
+        Qs = side.take(Q_scan, _F32, "Q_scan")
+        Qc = Qs if Q_coarse is None else side.take(Q_coarse, _F32, "Q_coarse")
+        nq = int(Qs.shape[0])
+        if np.ndim(radius) == 0 and not hasattr(radius, "is_cuda"):      # one radius for every query
+            rad = side.new((nq,), _F32, Qs)
+            rad[...] = float(radius)
+        else:
+            rad = side.take(radius, _F32, "radius")
+        _shapes(("Q_scan", Qs, (None, self.d)), ("Q_coarse", Qc, tuple(Qs.shape)), ("radius", rad, (nq,)))
+        lims = side.new((nq + 1,), _I64, Qs, zero=True)
+        spare = side.new((1,), _F32, Qs)                # nq == 0: an empty array still names one
+        qs, qc, rd = (p(a) if nq else p(spare) for a in (Qs, Qc, rad))
+        fl = _lib.IVF_ADD_COARSE if add_coarse else 0
+        self._eng._call(side, "lsq_index_range_search", p(lims), qs, qc if int(nprobe) else None, rd, nq, self.d, int(nprobe), fl, int(self._dev), h=self._h)
+        total = int(self.range_info()["results"])
+        dists, ids = side.new((total,), _F32, Qs), side.new((total,), _I32, Qs)
+        self._eng._call(side, "lsq_index_range_fetch", p(dists) if total else None, p(ids) if total else None, total, int(self._dev), h=self._h)
+        return lims, dists, ids
+
+    def range_info(self):
+        """what the last range_search call did: queries, rows_walked, results, max_per_query, batches, road (0 unfiltered, 1 dense, 2 compact), held_bytes,
+        coarse_ms / lut_ms / count_ms / fill_ms / sort_ms (with profile=True)"""
+        return self._info("lsq_index_get_range_info", _lib.RangeInfo)
+
     def ivf_info(self):
         """what the last search_ivf call did: queries, probed_rows, records, threshold_queries, fallback_queries, batches, batch_queries,
         tail_capacity, coarse_ms / lut_ms / scan_ms / select_ms (with profile=True)"""

@@ -160,6 +160,57 @@ def linscan_lsq(B, X, C, dbnorms, R, k=10000, *, nthreads=0, engine=None):
     return dists.T, res.T
 
 
+def range_search_lsq(B, X, C, dbnorms, R, radius, *, centroids=None, assign=None, nprobe=0, add_coarse=False, X_coarse=None, allowed=None, nthreads=0):
+    """Range search with LSQ codes on the host, for callers without an engine (lsq_range_search_cpu; the reference has no counterpart): every code
+    whose ADC distance -- linscan_lsq's, bit for bit -- to a query is <= that query's radius.
+    B (m, n) uint8 0-based; X (d, nq) queries; C list of (d, h); dbnorms (n,); R (d, d) rotation; radius a scalar or (nq,).  nprobe >= 1 with centroids
+    (d, nlist) and assign (n,) 0-based lists: only the codes of each query's nprobe nearest lists (X_coarse (d, nq): what is compared with the centroids,
+    default the rotated queries; add_coarse: the coarse distance added, for residual codes).  allowed (n,) bool: only those codes.
+    -> lims (nq+1,) int64, dists (lims[-1],) float32, ids (lims[-1],) int32 1-based: query q's results are entries lims[q] .. lims[q+1]-1, ascending by
+    (dist, id).  An engine's resident index answers the same question on the device: Index.range_search."""
+    from . import _lib
+    codes = np.ascontiguousarray(np.asarray(B, dtype=np.uint8).T)                # (n, m)
+    RX = np.ascontiguousarray((np.asarray(R, dtype=np.float32).T @ np.asarray(X, dtype=np.float32)).T)   # (nq, d)
+    K = _K_of(C)
+    dbn = np.ascontiguousarray(dbnorms, dtype=np.float32)
+    (n, m), (nq, d) = codes.shape, RX.shape
+    h = np.asarray(C[0]).shape[1]
+    rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (nq,)))
+    cent = lor = qc = None
+    nlist = 0
+    if int(nprobe) >= 1:
+        if centroids is None or assign is None:
+            raise ValueError("nprobe >= 1 needs centroids and assign")
+        cent = np.ascontiguousarray(np.asarray(centroids, dtype=np.float32).T)   # (nlist, d)
+        lor = np.ascontiguousarray(assign, dtype=np.int32)
+        nlist = cent.shape[0]
+        if cent.shape[1] != d or lor.shape != (n,):
+            raise ValueError("shape mismatch: centroids %s, expected (%d, nlist); assign %s, expected (%d,)" % (np.asarray(centroids).shape, d, lor.shape, n))
+        if X_coarse is not None:
+            qc = np.ascontiguousarray(np.asarray(X_coarse, dtype=np.float32).T)
+            if qc.shape != (nq, d):
+                raise ValueError("shape mismatch: X_coarse %s, expected (%d, %d)" % (np.asarray(X_coarse).shape, d, nq))
+    mask = None
+    if allowed is not None:
+        mask = np.ascontiguousarray(np.asarray(allowed) != 0).view(np.uint8)
+        if mask.shape != (n,):
+            raise ValueError("shape mismatch: allowed %s, expected (%d,)" % (mask.shape, n))
+    ptr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
+    lims = np.zeros(nq + 1, dtype=np.int64)
+
+    def call(dists, ids, capacity):
+        _lib.check(_lib.load().lsq_range_search_cpu(lims.ctypes.data, ptr(dists), ptr(ids), capacity, codes.ctypes.data, K.ctypes.data, dbn.ctypes.data,
+                                                    ptr(cent), ptr(lor), nlist, int(nprobe), _lib.IVF_ADD_COARSE if add_coarse else 0, ptr(mask),
+                                                    RX.ctypes.data, ptr(qc), rad.ctypes.data, n, m, h, d, nq, d, int(nthreads)))
+
+    call(None, None, 0)                                 # the two-call protocol: the counts, then arrays of exactly that size
+    total = int(lims[-1])
+    dists, ids = np.zeros(total, dtype=np.float32), np.zeros(total, dtype=np.int32)
+    if total:
+        call(dists, ids, total)
+    return lims, dists, ids
+
+
 def linscan_lsq_bytes(B, X, C, cbnorms, B_norms, R, k=10000, *, engine=None, nthreads=0):
     """linscan_lsq on the codes as train_lsq and quantize_norms leave them: the norm of a vector is ONE BYTE, an index into cbnorms, and is never widened
     to a float per vector (the reference does that one line before its scan, demos/demo_lsq_gpu.jl:57-60).

@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--delete FRACTION] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--delete FRACTION] [--radius R] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -43,6 +43,12 @@ the same resident base rows.  The reference has no such search.
 resident index (Index.remove: tombstones) and the recall of the ADC search -- and of the --ivf search over the same codes -- is taken against Index.knn over
 the rows that are left; then Index.compact makes the rows leave, the same searches run again, and their ids, taken back through old_of_new, must name the
 same rows: the demo asserts it and prints the two recall curves side by side.
+
+--radius R (alone or beside --ivf and --filter, whose sections run as before): range search on a resident index (Index.range_search) -- every base row
+whose ADC distance to the query is <= R, R in the scan's own units (the distances linscan_lsq prints), or `auto`: the median over the queries of the 10th
+neighbour's distance.  The mean, minimum and maximum result counts are printed; with --ivf also the share of the exhaustive range result that the search
+over the probed lists returns (it can only miss rows: its distances are the same bits); with --filter the counts under the mask.  The reference has no such
+search.
 
 needs $LSQ_DATA_DIR/sift/{sift_learn,sift_base,sift_query}.fvecs and sift_groundtruth.ivecs (TEXMEX layout).  The file's ground truth
 describes the full 10^6-vector base only: for a prefix of it (nread_base < 10^6) and for the stand-in, the ground truth is exact k-NN of the base
@@ -236,6 +242,14 @@ def main():
         except (ValueError, AssertionError, IndexError):
             raise SystemExit("--delete takes a FRACTION in (0, 1)")
         del argv[at:at + 2]
+    radius = None
+    if "--radius" in argv:
+        at = argv.index("--radius")
+        try:
+            radius = argv[at + 1] if argv[at + 1] == "auto" else float(argv[at + 1])
+        except (ValueError, IndexError):
+            raise SystemExit("--radius takes a distance R or `auto`")
+        del argv[at:at + 2]
     grow = None
     if "--grow" in argv:
         at = argv.index("--grow")
@@ -364,6 +378,50 @@ def main():
         filtered_recall(fraction, name, x_base, x_query, B_base, C, db_norms, m, knn, shortlist, ivf)
     if delete is not None:
         deleted_recall(delete, name, x_base, x_query, B_base, C, db_norms, m, knn, ivf)
+    if radius is not None:
+        if radius == "auto":
+            radius = float(np.median(dists[min(10, knn) - 1]))
+        range_counts(radius, name, x_base, x_query, B_base, C, db_norms, m, ivf, fraction)
+
+
+def range_counts(radius, name, x_base, x_query, B_base, C, db_norms, m, ivf, fraction):
+    """--radius: every row within ADC distance `radius` of each query (Index.range_search): the result counts over all rows, over the probed lists of
+    --ivf (and the share of the exhaustive result they hold), and under the mask of --filter"""
+    n = x_base.shape[1]
+    Q = np.ascontiguousarray(x_query.T.astype(np.float32))
+
+    def line(label, lims):
+        c = np.diff(lims)
+        return "%-28s mean %10.2f   min %8d   max %8d" % (label, c.mean(), c.min(), c.max())
+
+    out = []
+    with lsq.Engine(0) as eng, eng.index((B_base - 1).astype(np.uint8).T, np.ascontiguousarray(np.hstack(C).T), db_norms, m) as ix:
+        t0 = time.perf_counter()
+        lims, rd, ri = ix.range_search(Q, radius)
+        t_all = time.perf_counter() - t0
+        info = ix.range_info()
+        out.append(line("every row", lims))
+        if ivf:
+            nlist = min(ivf[0], n)
+            nprobe = min(ivf[1], nlist)
+            cent, assign = lsq.train_coarse(np.ascontiguousarray(np.asarray(x_base, dtype=np.float32).T), nlist, niter=10, seed=0, engine=eng)
+            ix.set_lists(cent, assign)
+            ilims, _, iids = ix.range_search(Q, radius, nprobe=nprobe)
+            # the probed lists' result is a subset of the exhaustive one (the same distance bits): the share is a ratio of counts
+            share = float(ilims[-1]) / max(float(lims[-1]), 1.0)
+            assert all(np.isin(iids[ilims[q]:ilims[q + 1]], ri[lims[q]:lims[q + 1]]).all() for q in range(min(Q.shape[0], 16)))
+            out.append(line("IVF %d:%d" % (nlist, nprobe), ilims) + "   share of the exhaustive result %.4f" % share)
+        if fraction is not None:
+            allowed = np.random.default_rng(0).random(n) < fraction
+            ix.set_filter(mask=allowed)
+            flims, _, fids = ix.range_search(Q, radius)
+            assert allowed[fids - 1].all()
+            out.append(line("filter %g (%s road)" % (fraction, {0: "unfiltered", 1: "dense", 2: "compact"}[ix.range_info()["road"]]), flims))
+    print("Range search (radius %g, %d queries, %d rows): %.3f s on the resident index incl. the fetch; %d results held in %d bytes, %d fill batch(es)"
+          % (radius, Q.shape[0], n, t_all, info["results"], info["held_bytes"], info["batches"]))
+    for text in out:
+        print("   " + text)
+    print("%s: mean range result at radius %g = %.2f rows" % (name, radius, np.diff(lims).mean()))
 
 
 def deleted_recall(fraction, name, x_base, x_query, B_base, C, db_norms, m, knn, ivf):
