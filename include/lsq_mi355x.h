@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 2300
+#define LSQ_VERSION 2400
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -833,6 +833,60 @@ LSQ_API int lsq_range_search_cpu(int64_t *lims, float *dists, int *ids, int64_t 
                                  const float *dbnorms, const float *centroids, const int32_t *list_of_row, int nlist, int nprobe, int flags,
                                  const uint8_t *allowed, const float *q_scan, const float *q_coarse, const float *radius, int n, int m, int h, int d,
                                  int nq, int ldq, int nthreads);
+
+/* ---- (3n) decode: the vectors the codes stand for, and search by stored row (csrc/lsq_recon.hip; since v2400) -------------------------------------------
+ * reconstruct(B, C)     src/utils.jl:203-223.  For a code row b (m bytes, 0-based) and codebooks K [m h][d]
+ *     x^[t] = (((+0.0f + K[(0 h + b_0) d + t]) + K[(1 h + b_1) d + t]) + ...) + K[((m - 1) h + b_(m-1)) d + t]
+ * in f32, every add rounded, codebooks ascending, the sum STARTING FROM +0.0 as the reference's zeros / += does: a component whose m codewords are all -0.0
+ * is +0.0 (lsq_quantize_norms starts from the first codeword: fine for a norm, not for these bits).  With the coarse flag one more rounded add follows:
+ * x^[t] + centroid[l][t], l the list the row belongs to (a residual index, (3i): the stored codes are of x - c_l).  Every form below returns these bits;
+ * where the contract's value is a NaN the result is a NaN of any payload.
+ *   lsq_reconstruct_cpu    the host checker and the engine-less road: plain arrays, no context, std::thread workers.  ids == NULL: rows 0 .. count - 1; else
+ *                          ids [count] int32 in id_base.  centroids [..][d] and list_of_row [n] are read only with LSQ_RECON_ADD_COARSE.  It takes any
+ *                          1 <= h <= 256 (codebook j starts at row j h of K; a code >= h: LSQ_EINVAL); an index holds h = 256 (lsq_index_create), and the
+ *                          device kernel is built for that stride alone.
+ *   lsq_index_reconstruct  from the index's own resident codes and codebooks.  ids == NULL: rows [start, start + count) (start 0-based); else ids [count] int32
+ *                          in id_base 0 or 1, in any order, repeats allowed (start is ignored).  out [count][ldo]; ids and out are host arrays (on_device =
+ *                          0) or device arrays (1).  LSQ_RECON_ADD_COARSE adds the centroid of the row's list and needs lsq_index_set_lists; the row ->
+ *                          list map is derived on the device from the inverted layout and kept until lsq_index_set_lists / _add / _compact change the
+ *                          layout, then rebuilt on demand.  LSQ_RECON_PAD_NAN: an id outside [id_base, id_base + n) gives a row of 0x7FC00000; it is never
+ *                          dereferenced and is counted (lsq_index_recon_info.invalid) -- this is how search results decode: the (+inf, 0) padding of
+ *                          lsq_index_search_ivf and the id_base - 1 of a filtered search are such ids.  Without that flag a bad id is LSQ_EINVAL, found
+ *                          BEFORE anything is written to out.  Plain and packed indexes, borrowed and owned arrays, after add / remove / compact alike.
+ *                          NOT AFFECTED BY A ROW FILTER (3j): a filtered-out or tombstoned row stays addressable until lsq_index_compact removes it.  The call
+ *                          changes nothing a search would see: a held range result (3m) stays fetchable.  It waits for the device.  A host call (on_device =
+ *                          0) is decoded and fetched in chunks of rows (64 MiB of output at a time; option "recon_chunk" = rows per chunk: a test hook,
+ *                          the same bits).
+ *                          LSQ_EINVAL, nothing launched: a null handle or pointer (count > 0), an index without codes, count < 0, ldo < d, a range past n, an
+ *                          id_base other than 0 / 1, a flag outside the two, the coarse flag without lists.  count == 0: LSQ_OK.
+ *   lsq_index_search_rows  searches whose queries are STORED ROWS: rows [nq] int32 in id_base (host or device, on_device).  The rows are decoded into staging
+ *                          the index owns -- with the coarse add exactly when flags carries LSQ_IVF_ADD_COARSE -- and then nprobe == 0 is
+ *                          lsq_index_search(shortlist = 0) on those queries, nprobe >= 1 is lsq_index_search_ivf(shortlist = 0, q_coarse = q_scan, flags).
+ *                          THE RESULT IS BIT FOR BIT WHAT THOSE CALLS RETURN FOR q = lsq_index_reconstruct(rows, ...), the filter and the statistics
+ *                          included (ids 1-based as theirs).  A composition: it adds no scan kernel.  NO SELF-EXCLUSION: with quantised norms a row need
+ *                          not be its own nearest neighbour, and it is returned like any other row.  flags: those of lsq_index_search_ivf (none but 0 with
+ *                          nprobe == 0).  A row outside the index: LSQ_EINVAL, dists / ids untouched. */
+#define LSQ_RECON_ADD_COARSE 1
+#define LSQ_RECON_PAD_NAN 2
+#define LSQ_RECON_ROAD_DWORD 1       /* lsq_index_recon_info.road: dword loads and stores (odd d, odd pitch, unaligned out) */
+#define LSQ_RECON_ROAD_VEC16 2       /* 16-byte loads and stores */
+#define LSQ_RECON_ROAD_CODE_DWORDS 4 /* or-ed in: the code rows went by dword loads (a pitch of whole dwords), else by bytes */
+typedef struct lsq_index_recon_info {    /* the last lsq_index_reconstruct / lsq_index_search_rows call; fields are only ever appended */
+    int64_t rows;                /* rows decoded (valid ids) */
+    int64_t invalid;             /* ids outside the index: padded with LSQ_RECON_PAD_NAN, or the reason of a refusal */
+    int64_t map_rebuilt;         /* 1: this call built the row -> list map */
+    int64_t map_rebuilds;        /* since the index was made */
+    int64_t road;                /* LSQ_RECON_ROAD_* of the decode kernel */
+    int64_t calls;               /* since the index was made */
+    double map_ms, decode_ms;    /* with option "profile" = 1 */
+} lsq_index_recon_info;
+LSQ_API int lsq_reconstruct_cpu(float *out, int64_t ldo, const uint8_t *codes, int64_t ldc, const float *K, const int32_t *ids, int64_t count,
+                                int id_base, int64_t n, int m, int h, int d, const float *centroids, const int32_t *list_of_row, int flags, int nthreads);
+LSQ_API int lsq_index_reconstruct(lsq_index *ix, float *out, int64_t ldo, const int32_t *ids, int64_t start, int64_t count, int id_base, int flags,
+                                  int on_device);
+LSQ_API int lsq_index_search_rows(lsq_index *ix, float *dists, int *ids_out, const int32_t *rows, int nq, int id_base, int nn, int nprobe, int flags,
+                                  int on_device);
+LSQ_API int lsq_index_get_recon_info(lsq_index *ix, lsq_index_recon_info *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

@@ -13,7 +13,7 @@ from . import _lib  # noqa: F401
 from .engine import Engine, Index, Encoder, Partition, MultiEngine, randinit as randinit_rows, node_order, splitarray as split_ranges, device_count  # noqa: F401
 from .reference_api import (  # noqa: F401
     encode_icm_cuda, encoding_icm, encode_icm_fully, get_unaries, get_binaries, veccost, qerror,
-    randinit, splitarray, default_engine, linscan_lsq, linscan_pq, linscan_opq, eval_recall, quantize_norms, reconstruct,
+    randinit, splitarray, default_engine, linscan_lsq, linscan_pq, linscan_opq, eval_recall, quantize_norms, reconstruct, reconstruct_cpu,
     fvecs_read, ivecs_read, bvecs_read, update_codebooks, train_lsq, train_lsq_dev,
     update_codebooks_spgl1, update_codebooks_spgl1_threshold, train_lsq_sparse, knn_exact, rerank, linscan_lsq_rerank, encode_beam, beam_order,
     ivf_assign, train_coarse, ivf_residual_norms, linscan_lsq_bytes, train_coarse_dev, build_ivf_residual_index, range_search_lsq,
@@ -31,5 +31,5 @@ __all__ = [
     "train_chainq", "train_chainq_dev", "encoding_viterbi", "update_codebooks_chain", "update_codebooks_generic", "get_cbdims_chain", "fvecs_read", "ivecs_read", "bvecs_read",
     "update_codebooks_spgl1", "update_codebooks_spgl1_threshold", "train_lsq_sparse", "knn_exact",
     "kmeans_dev", "train_pq_dev", "train_opq_dev", "codebooks_from_padded", "Index", "rerank", "linscan_lsq_rerank", "Encoder", "encode_beam", "beam_order",
-    "ivf_assign", "train_coarse", "ivf_residual_norms", "linscan_lsq_bytes", "Partition", "train_coarse_dev", "build_ivf_residual_index", "range_search_lsq",
+    "ivf_assign", "train_coarse", "ivf_residual_norms", "linscan_lsq_bytes", "Partition", "train_coarse_dev", "build_ivf_residual_index", "range_search_lsq", "reconstruct_cpu",
 ]

@@ -112,6 +112,15 @@ class IndexCompactInfo(_Struct):
                 ("layout_ms", C.c_double)]
 
 
+class IndexReconInfo(_Struct):
+    _fields_ = [("rows", C.c_int64), ("invalid", C.c_int64), ("map_rebuilt", C.c_int64), ("map_rebuilds", C.c_int64), ("road", C.c_int64),
+                ("calls", C.c_int64), ("map_ms", C.c_double), ("decode_ms", C.c_double)]
+
+
+RECON_ADD_COARSE, RECON_PAD_NAN = 1, 2
+RECON_ROAD_DWORD, RECON_ROAD_VEC16, RECON_ROAD_CODE_DWORDS = 1, 2, 4
+
+
 class RangeInfo(_Struct):
     _fields_ = [("queries", C.c_int64), ("rows_walked", C.c_int64), ("results", C.c_int64), ("max_per_query", C.c_int64), ("batches", C.c_int64),
                 ("road", C.c_int64), ("held_bytes", C.c_int64), ("coarse_ms", C.c_double), ("lut_ms", C.c_double), ("count_ms", C.c_double),
@@ -248,6 +257,11 @@ SIGNATURES = {
     "lsq_index_range_fetch": (_i, [_vp, _vp, _vp, _i64, _i]),
     "lsq_index_get_range_info": (_i, [_vp, C.POINTER(RangeInfo)]),
     "lsq_range_search_cpu": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
+    # decode and search by stored row (since v2400)
+    "lsq_reconstruct_cpu": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
+    "lsq_index_reconstruct": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i]),
+    "lsq_index_search_rows": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    "lsq_index_get_recon_info": (_i, [_vp, C.POINTER(IndexReconInfo)]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),
@@ -289,7 +303,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 2300     # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 2400     # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

@@ -111,6 +111,7 @@ struct lsq_ctx {
     int knn_u8_int = 1;                                // option "knn_u8_int": 0 = lsq_index_knn widens 8-bit rows and queries even where the integer road applies; a test hook
     int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
     int64_t range_batch = 0;                           // option "range_batch": records per fill batch of lsq_index_range_search (0 = automatic); a test hook
+    int64_t recon_chunk = 0;                           // option "recon_chunk": rows per staging chunk of a host-buffer lsq_index_reconstruct (0 = automatic); a test hook
     // Staging for the host-buffer entry points.  Who writes what (a later call may assume NOTHING of their contents, except sK under tables_valid):
     //   sX, sX2  X: one chunk at a time, double-buffered, by the pipelined encode; the whole X by stage_X
     //   sK       the call's codebooks: uploaded (host_codebooks; claim_sK: K, K_prev) or computed into it (claim_sK: LSQR, SPGL1, the seeding).
@@ -322,6 +323,10 @@ extern "C" int lsq_set_option(lsq_ctx *c, const char *key, int64_t value) {
     else if (!strcmp(key, "range_batch")) {
         if (value < 0 || value > LSQ_RANGE_BATCH_RECORDS) { lsq_set_error("range_batch must lie in 0..2^28"); return LSQ_EINVAL; }
         c->range_batch = value;
+    }
+    else if (!strcmp(key, "recon_chunk")) {
+        if (value < 0) { lsq_set_error("recon_chunk must be >= 0"); return LSQ_EINVAL; }
+        c->recon_chunk = value;
     }
     else if (!strcmp(key, "ils_counter")) {
         if (value < 0 || value >= (int64_t)LSQ_IT_AUTO) { lsq_set_error("ils_counter must lie in 0..2^32-2"); return LSQ_EINVAL; }
@@ -575,6 +580,11 @@ struct lsq_index {
     PhaseClock<3> cclock;                              // a remove's tombstones; a compact's gather and layout phases
     lsq_range_state *range = nullptr;                  // range search (lsq_range.hip): its scratch and the HELD result of the last one; null until the first
     DevBuf s_radius;                                   // lsq_index_range_search's staging of host radii
+    DevBuf r_lor, r_ids, r_out, r_q;                   // the decode (lsq_recon.hip): the row -> list map [n], staged host ids, a host call's staged output chunk,
+                                                       // lsq_index_search_rows' decoded queries [nq][d]
+    bool r_lor_valid = false;                          // r_lor answers for the inverted layout in force (lsq_index_set_lists / _add / _compact clear it)
+    lsq_index_recon_info rinfo{};
+    PhaseClock<3> rclock;                              // a decode's map and decode phases
 };
 
 // the filter as a scan over all rows takes it: nothing without one; else the compact road -- the ascending list of allowed rows -- where the measured rule
@@ -596,11 +606,12 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     (void)hipStreamSynchronize(ix->ctx->stream);
     DevBuf *bufs[] = {&ix->own_codes, &ix->own_K, &ix->own_norms, &ix->own_base, &ix->rec_a, &ix->rec_b, &ix->seg, &ix->counter, &ix->short_d, &ix->short_i,
                       &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q, &ix->s_qcoarse, &ix->g_codes, &ix->g_nc, &ix->g_rows,
-                      &ix->c_old, &ix->c_new, &ix->s_radius};
+                      &ix->c_old, &ix->c_new, &ix->s_radius, &ix->r_lor, &ix->r_ids, &ix->r_out, &ix->r_q};
     for (DevBuf *b : bufs) b->release();
     lsq_range_free(ix->range);
     ix->gclock.release();
     ix->cclock.release();
+    ix->rclock.release();
     lsq_adc_free(ix->adc);
     lsq_ivf_free(ix->ivf);
     lsq_filter_free(ix->filter);
@@ -990,6 +1001,7 @@ extern "C" int lsq_index_set_lists(lsq_index *ix, const lsq_ivf_desc *desc) {
     if (desc->nlist < 1 || desc->nlist > (1 << 24)) { lsq_set_error("lsq_index_set_lists: needs 1 <= nlist <= 2^24 (got %d)", desc->nlist); return LSQ_EINVAL; }
     if (!desc->centroids || !desc->list_of_row) { lsq_set_error("lsq_index_set_lists: null pointer"); return LSQ_EINVAL; }
     LSQ_TRY(use_device(ix->ctx));
+    ix->r_lor_valid = false;
     LSQ_TRY(lsq_ivf_set_lists(ix->ctx->stream, &ix->ivf, ix->codes, ix->norms, ix->packed, ix->n, ix->m, ix->d, desc));
     lsq_range_drop(ix->range);
     if (ix->cap_rows > ix->n) {                       // an index with capacity (lsq_index_reserve / _add): the layout's halves get it too
@@ -1242,6 +1254,7 @@ extern "C" int lsq_index_add(lsq_index *ix, const lsq_index_add_desc *desc) {
     LSQ_HIP(hipStreamSynchronize(s));
     // 6. the commit
     if (lists) lsq_ivf_add_commit(ix->ivf, count);
+    ix->r_lor_valid = false;
     lsq_filter_grow_commit(ix->filter, n + count);
     ix->n = n + count;
     lsq_range_drop(ix->range);                        // a held range result answers for the former rows
@@ -1394,6 +1407,7 @@ extern "C" int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *de
         shrunk = shrink ? 1 : 0;
     }
     lsq_range_drop(ix->range);
+    ix->r_lor_valid = false;
     ix->cinfo.n_before = n; ix->cinfo.n_after = n2;
     ix->cinfo.compactions += 1; ix->cinfo.rows_dropped += n - n2;
     ix->cinfo.moved_bytes = bytes; ix->cinfo.shrunk = shrunk;
@@ -1404,6 +1418,141 @@ extern "C" int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *de
 extern "C" int lsq_index_get_compact_info(lsq_index *ix, lsq_index_compact_info *out) {
     if (!ix || !out) { lsq_set_error("lsq_index_get_compact_info: null argument"); return LSQ_EINVAL; }
     *out = ix->cinfo;
+    return LSQ_OK;
+}
+
+// ---- decode from the index's own codes, and search by stored row (lsq_recon.hip) -------------------------------------------------------------
+// What both entry points share, after their own checks: the selection checked (a bad id without PAD: LSQ_EINVAL before anything is written anywhere), the
+// row -> list map brought up to date, and `emit(call, r0, cn, &road)` called for chunks of at most `chunk` rows of the selection -- call: the decode of the
+// chunk, its output left to emit.  ids: host (ids_dev = false: checked here, staged) or device (the one kernel that reads them counts the bad ones)
+template <class Emit>
+static int index_decode(const char *fn, lsq_index *ix, const int32_t *ids, bool ids_dev, int64_t start, int64_t count, int id_base, int flags, int64_t chunk,
+                        Emit emit) {
+    lsq_ctx *c = ix->ctx;
+    hipStream_t s = c->stream;
+    const bool coarse = (flags & LSQ_RECON_ADD_COARSE) != 0, pad = (flags & LSQ_RECON_PAD_NAN) != 0;
+    const int32_t *d_ids = ids;
+    int64_t bad = 0;
+    if (ids && !ids_dev) {
+        bad = lsq_recon_count_bad_ids(ids, count, id_base, ix->n);
+        if (bad && !pad) { ix->rinfo.invalid = bad; lsq_set_error("%s: %lld ids lie outside [%d, %lld)", fn, (long long)bad, id_base, (long long)(id_base + ix->n)); return LSQ_EINVAL; }
+        LSQ_TRY(ix->r_ids.ensure(sizeof(int32_t) * (size_t)count));
+        LSQ_HIP(hipMemcpyAsync(ix->r_ids.p, ids, sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, s));
+        d_ids = ix->r_ids.as<int32_t>();
+    } else if (ids) {
+        unsigned found = 0;
+        LSQ_HIP(hipMemsetAsync(ix->counter.p, 0, sizeof(unsigned long long), s));
+        LSQ_TRY(lsq_recon_launch_check_ids(s, ids, count, id_base, ix->n, ix->counter.as<unsigned>()));
+        LSQ_HIP(hipMemcpyAsync(&found, ix->counter.p, sizeof(found), hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipStreamSynchronize(s));
+        bad = found;
+        if (bad && !pad) { ix->rinfo.invalid = bad; lsq_set_error("%s: %lld ids lie outside [%d, %lld)", fn, (long long)bad, id_base, (long long)(id_base + ix->n)); return LSQ_EINVAL; }
+    }
+    LSQ_TRY(ix->rclock.begin(c->profile != 0));
+    LSQ_TRY(ix->rclock.mark(s));
+    int rebuilt = 0;
+    if (coarse && !ix->r_lor_valid) {
+        const int *lids = nullptr, *loff = nullptr;
+        lsq_ivf_layout(ix->ivf, &lids, &loff);
+        LSQ_TRY(ix->r_lor.ensure(sizeof(int32_t) * (size_t)ix->n));
+        LSQ_TRY(lsq_recon_launch_lor(s, lids, loff, ix->n, lsq_ivf_nlist(ix->ivf), ix->r_lor.as<int32_t>()));
+        ix->r_lor_valid = true;
+        rebuilt = 1;
+    }
+    LSQ_TRY(ix->rclock.mark(s));
+    lsq_recon_call r;
+    r.codes = ix->codes; r.ldc = (int64_t)index_row_bytes(ix); r.K = ix->K; r.d = ix->d; r.m = ix->m; r.n = ix->n;
+    r.id_base = id_base; r.pad_nan = pad ? 1 : 0;
+    if (coarse) { r.cent = lsq_ivf_centroids(ix->ivf); r.lor = ix->r_lor.as<int32_t>(); r.nlist = lsq_ivf_nlist(ix->ivf); }
+    int road = 0;
+    for (int64_t r0 = 0; r0 < count; r0 += chunk) {
+        const int64_t cn = std::min<int64_t>(chunk, count - r0);
+        r.ids = d_ids ? d_ids + r0 : nullptr; r.start = start + r0; r.count = cn;
+        LSQ_TRY(emit(r, r0, cn, &road));
+    }
+    LSQ_TRY(ix->rclock.mark(s));
+    LSQ_HIP(hipStreamSynchronize(s));
+    float ms[2];
+    LSQ_TRY(ix->rclock.read(ms));
+    ix->rinfo.rows = count - bad; ix->rinfo.invalid = bad; ix->rinfo.map_rebuilt = rebuilt; ix->rinfo.map_rebuilds += rebuilt; ix->rinfo.road = road;
+    ix->rinfo.calls += 1; ix->rinfo.map_ms = ms[0]; ix->rinfo.decode_ms = ms[1];
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_reconstruct(lsq_index *ix, float *out, int64_t ldo, const int32_t *ids, int64_t start, int64_t count, int id_base, int flags,
+                                     int on_device) {
+    const char *fn = "lsq_index_reconstruct";
+    if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
+    if (!ix->codes) { lsq_set_error("%s: the index holds no codes", fn); return LSQ_EINVAL; }
+    if (ldo < ix->d) { lsq_set_error("%s: needs ldo >= d (got ldo=%lld d=%d)", fn, (long long)ldo, ix->d); return LSQ_EINVAL; }
+    if (const char *why = lsq_recon_select_refusal(ids, start, count, id_base, ix->n, flags, lsq_ivf_nlist(ix->ivf) > 0)) {
+        lsq_set_error("%s: %s (start=%lld count=%lld id_base=%d flags=%d n=%lld)", fn, why, (long long)start, (long long)count, id_base, flags, (long long)ix->n);
+        return LSQ_EINVAL;
+    }
+    if (count > 0 && !out) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    if (((uintptr_t)out & 3) != 0) { lsq_set_error("%s: out is not 4-byte aligned", fn); return LSQ_EINVAL; }
+    if (count == 0) return LSQ_OK;
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    const int d = ix->d;
+    if (on_device)                                    // one launch, straight into the caller's rows
+        return index_decode(fn, ix, ids, true, ids ? 0 : start, count, id_base, flags, count, [&](lsq_recon_call &r, int64_t r0, int64_t cn, int *road) -> int {
+            r.out = out + r0 * ldo; r.ldo = ldo;
+            return lsq_recon_launch(s, r, road);
+        });
+    // host form: chunks of rows decoded d floats apart into the index's staging, each row's d floats copied out
+    const int64_t rows = lsq_recon_chunk_rows(count, d, c->recon_chunk);
+    LSQ_TRY(ix->r_out.ensure(sizeof(float) * (size_t)rows * d));
+    return index_decode(fn, ix, ids, false, ids ? 0 : start, count, id_base, flags, rows, [&](lsq_recon_call &r, int64_t r0, int64_t cn, int *road) -> int {
+        r.out = ix->r_out.as<float>(); r.ldo = d;
+        LSQ_TRY(lsq_recon_launch(s, r, road));
+        LSQ_HIP(hipMemcpy2DAsync(out + r0 * ldo, sizeof(float) * (size_t)ldo, ix->r_out.p, sizeof(float) * (size_t)d, sizeof(float) * (size_t)d, (size_t)cn,
+                                 hipMemcpyDeviceToHost, s));
+        return LSQ_OK;
+    });
+}
+
+// searches whose queries are stored rows: the rows decoded into r_q, then the existing entry point on those queries -- their checks, roads and statistics
+extern "C" int lsq_index_search_rows(lsq_index *ix, float *dists, int *ids_out, const int32_t *rows, int nq, int id_base, int nn, int nprobe, int flags,
+                                     int on_device) {
+    const char *fn = "lsq_index_search_rows";
+    LSQ_TRY(index_call_check(fn, ix, dists, ids_out, nq, ix ? ix->d : 0, nn));
+    if (!ix->codes) { lsq_set_error("%s: the index holds no codes", fn); return LSQ_EINVAL; }
+    if (nprobe < 0) { lsq_set_error("%s: needs nprobe >= 0 (got %d)", fn, nprobe); return LSQ_EINVAL; }
+    if (id_base != 0 && id_base != 1) { lsq_set_error("%s: id_base must be 0 or 1 (got %d)", fn, id_base); return LSQ_EINVAL; }
+    if (nq > 0 && !rows) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    const int nlist = lsq_ivf_nlist(ix->ivf);
+    // what the search behind it would refuse is refused here, before the decode: nothing is launched for a call that cannot be answered
+    if (nprobe == 0) {
+        if (flags != 0) { lsq_set_error("%s: flags %d need nprobe >= 1", fn, flags); return LSQ_EINVAL; }
+        if (nn > ix->n) { lsq_set_error("%s: nn=%d exceeds the database size %lld", fn, nn, (long long)ix->n); return LSQ_EINVAL; }
+    } else {
+        if (nlist < 1) { lsq_set_error("%s: the index has no lists (call lsq_index_set_lists first)", fn); return LSQ_EINVAL; }
+        if (flags & ~(LSQ_IVF_ADD_COARSE | LSQ_IVF_EVERY_RECORD | LSQ_IVF_TEST_BATCH)) { lsq_set_error("%s: unknown flags %d", fn, flags); return LSQ_EINVAL; }
+        if (nprobe > nlist) { lsq_set_error("%s: needs nprobe <= nlist (got nprobe=%d nlist=%d)", fn, nprobe, nlist); return LSQ_EINVAL; }
+        if (nn > (1 << 28)) { lsq_set_error("%s: needs nn <= 2^28 (got %d)", fn, nn); return LSQ_EINVAL; }
+    }
+    if (nq == 0) return LSQ_OK;
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    LSQ_TRY(ix->r_q.ensure(sizeof(float) * (size_t)nq * ix->d));
+    const int rflags = (nprobe >= 1 && (flags & LSQ_IVF_ADD_COARSE)) ? LSQ_RECON_ADD_COARSE : 0;
+    LSQ_TRY(index_decode(fn, ix, rows, on_device != 0, 0, nq, id_base, rflags, nq, [&](lsq_recon_call &r, int64_t r0, int64_t cn, int *road) -> int {
+        r.out = ix->r_q.as<float>() + r0 * ix->d; r.ldo = ix->d;
+        return lsq_recon_launch(s, r, road);
+    }));
+    // the queries are device rows; a host call's dists / ids_out are host arrays: the entry points below stage query rows by address (hipMemcpyDefault), so
+    // the host form reads r_q as it would read the caller's rows
+    const float *q = ix->r_q.as<float>();
+    if (nprobe == 0) return lsq_index_search(ix, dists, ids_out, q, nullptr, nq, ix->d, 0, nn, on_device);
+    return lsq_index_search_ivf(ix, dists, ids_out, q, q, nullptr, nq, ix->d, nprobe, 0, nn, flags, on_device);
+}
+
+extern "C" int lsq_index_get_recon_info(lsq_index *ix, lsq_index_recon_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_recon_info: null argument"); return LSQ_EINVAL; }
+    *out = ix->rinfo;
     return LSQ_OK;
 }
 

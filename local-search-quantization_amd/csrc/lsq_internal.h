@@ -10,6 +10,7 @@
 #include "lsq_grow_check.h"
 #include "lsq_compact_check.h"
 #include "lsq_range_check.h"
+#include "lsq_recon_check.h"
 
 #define LSQ_H 256          // candidates per codebook: one wave x float4 per lane
 #define LSQ_MAX_M 16
@@ -542,6 +543,29 @@ int lsq_filter_layout_rows(hipStream_t s, lsq_filter_state *st, int64_t n, const
 int lsq_ivf_compact(hipStream_t s, lsq_ivf_state *st, const lsq_filter_view &v, const int *lsel, int64_t rows_out, int64_t cap_rows, bool exact, int64_t *bytes);
 void lsq_ivf_compact_commit(lsq_ivf_state *st, int64_t rows_out);
 int lsq_ivf_fit(hipStream_t s, lsq_ivf_state *st, int64_t rows);
+
+// ---- decode on the device (lsq_recon.hip): the vectors the codes stand for ---------------------------------------------------------------
+// one decode, every pointer a device pointer: out row r (r < count; rows ldo floats apart) = the reconstruction of row ids[r] - id_base (ids != null) or
+// start + r of codes (rows ldc >= m bytes apart, n of them addressable), from +0.0, codebooks ascending; cent != null: one more rounded add of
+// cent[lor[row]] (both [..][d] / [n]).  An id outside [0, n) writes a row of 0x7FC00000 with pad_nan and nothing without (the caller has refused it before).
+// No allocation, no wait: graph-capturable.  *road (optional): LSQ_RECON_ROAD_* of the launch
+struct lsq_recon_call {
+    const uint8_t *codes = nullptr; int64_t ldc = 0;
+    const float *K = nullptr; int d = 0, m = 0;
+    int64_t n = 0;
+    const int32_t *ids = nullptr; int id_base = 0;
+    int64_t start = 0, count = 0;
+    float *out = nullptr; int64_t ldo = 0;
+    const float *cent = nullptr; const int32_t *lor = nullptr; int nlist = 0;
+    int pad_nan = 0;
+};
+int lsq_recon_launch(hipStream_t s, const lsq_recon_call &c, int *road);
+// *bad (device, zeroed by the caller) += the ids outside [id_base, id_base + n)
+int lsq_recon_launch_check_ids(hipStream_t s, const int32_t *ids, int64_t count, int id_base, int64_t n, unsigned *bad);
+// lor [n] = the list of every original row, from the inverted layout ids [n] / off [nlist + 1]
+int lsq_recon_launch_lor(hipStream_t s, const int *ids, const int *off, int64_t n, int nlist, int32_t *lor);
+// the centroids of the inverted lists [nlist][d] (lsq_ivf.hip); null without lists
+const float *lsq_ivf_centroids(const lsq_ivf_state *st);
 
 // ---- what a handle that lives in a file of its own (lsq_partition.hip) needs of its context (lsq_api.hip): its device made current, the stream it is bound
 // to now, option "profile".  Nothing of the context is written ------------------------------------------------------------------------------------------

@@ -318,6 +318,8 @@ void lsq_ivf_layout(const lsq_ivf_state *st, const int **ids, const int **off) {
     *off = have ? st->off.as<int>() : nullptr;
 }
 
+const float *lsq_ivf_centroids(const lsq_ivf_state *st) { return st && st->nlist > 0 ? st->cent.as<float>() : nullptr; }
+
 void lsq_ivf_get_info(const lsq_ivf_state *st, lsq_ivf_info *out) { *out = st ? st->info : lsq_ivf_info{}; }
 
 int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **pst, const uint8_t *codes, const float *norms, int packed, int64_t n, int m, int d,

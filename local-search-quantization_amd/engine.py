@@ -997,6 +997,55 @@ class Index(_Handle):
         remove) and gather_ms / layout_ms (last compact) with profile=True"""
         return self._info("lsq_index_get_compact_info", _lib.IndexCompactInfo)
 
+    def reconstruct(self, ids=None, start=0, count=None, add_coarse=False, pad_nan=False, id_base=0, out=None):
+        """The vectors the index's codes stand for.  ids=None: rows start .. start + count - 1 (count=None: to the last row); else ids (count,) int32 in
+        id_base, any order, repeats allowed -- numpy on an Engine.index, a device tensor on an Engine.index_dev.  add_coarse: plus the centroid of the
+        row's list (a residual index; needs set_lists).  pad_nan: an id outside the index gives a row of NaN and is counted in recon_info()["invalid"]
+        -- this decodes search results, whose padding ids lie outside; without it such an id refuses the call and nothing is written.  A filter
+        changes nothing: a removed row is addressable until compact().  out: (count, >=d) float32 rows to write into (the same kind of array)
+        -> (count, d) float32   [lsq_index_reconstruct]"""
+        side, p = self._side, self._side.ptr
+        if ids is not None:
+            ids = side.take(ids, _I32, "ids")
+            _shapes(("ids", ids, (None,)))
+            count, start = int(ids.shape[0]), 0
+        elif count is None:
+            count = self.n - int(start)
+        count = int(count)
+        if out is None:
+            out = side.new((max(count, 0), self.d), _F32, self._eng._device() if side.dev else None, zero=True)
+        elif side.dev:
+            out = side.take(out, _F32, "out", rows=True)
+        elif not (isinstance(out, np.ndarray) and out.dtype == _F32 and out.ndim == 2 and out.strides[1] == 4 and out.strides[0] % 4 == 0):
+            raise ValueError("out must be a 2-d float32 numpy array of rows with unit column stride")
+        _shapes(("out", out, (max(count, 0), max(self.d, out.shape[1]))))
+        fl = (_lib.RECON_ADD_COARSE if add_coarse else 0) | (_lib.RECON_PAD_NAN if pad_nan else 0)
+        ldo = int(side.pitch(out)) if out.shape[0] > 1 else int(out.shape[1])
+        self._eng._call(side, "lsq_index_reconstruct", p(out) if count > 0 else None, ldo, p(ids) if ids is not None and count > 0 else None, int(start), count,
+                        int(id_base), fl, int(self._dev), h=self._h)
+        return out
+
+    def search_rows(self, rows, k, nprobe=0, add_coarse=False, id_base=0):
+        """Neighbours of STORED rows: rows (nq,) int32 in id_base (numpy / device tensor as the index).  The rows are decoded on the device (with the
+        centroid of their list when add_coarse) and searched: nprobe=0 is search(reconstruct(rows), k), nprobe>=1 is search_ivf(reconstruct(rows,
+        add_coarse), k, nprobe, add_coarse=add_coarse) -- bit for bit, the filter in force included.  No self-exclusion: a row is returned like any
+        other, and with quantised norms it need not come first.
+        -> dists (nq,k) float32 ascending, ids (nq,k) int32 1-BASED   [lsq_index_search_rows]"""
+        side, p = self._side, self._side.ptr
+        rows = side.take(rows, _I32, "rows")
+        _shapes(("rows", rows, (None,)))
+        nq = int(rows.shape[0])
+        dists, ids = side.topk(nq, int(k), self._eng._device() if side.dev else None)
+        fl = _lib.IVF_ADD_COARSE if add_coarse else 0
+        self._eng._call(side, "lsq_index_search_rows", p(dists), p(ids), p(rows) if nq else None, nq, int(id_base), int(k), int(nprobe), fl, int(self._dev),
+                        h=self._h)
+        return dists, ids
+
+    def recon_info(self):
+        """the last reconstruct / search_rows call: rows decoded, invalid ids, map_rebuilt (the row -> list map was built by it), map_rebuilds and calls
+        (since creation), road (_lib.RECON_ROAD_*), map_ms / decode_ms (with profile=True)"""
+        return self._info("lsq_index_get_recon_info", _lib.IndexReconInfo)
+
 
 # -- the beam-search encoder (made by Engine.encoder / Engine.encoder_dev) ------------------------
 

@@ -683,6 +683,35 @@ def reconstruct(B, C):
     return CB
 
 
+def reconstruct_cpu(codes, K, m, *, ids=None, id_base=0, out=None, centroids=None, assign=None, add_coarse=False, pad_nan=False, h=256, nthreads=0):
+    """The decode on the host, for callers without an engine and as the device's checker (lsq_reconstruct_cpu): codes (n, >=m) uint8 0-based rows with
+    unit column stride (any row pitch), K (m*h, d) -> (count, d) float32: rows 0 .. n-1, or rows ids (count,) int32 in id_base.  add_coarse: plus
+    centroids[assign[row]] (centroids (nlist, d), assign (n,) int32); pad_nan: an id outside the rows gives a row of NaN.  out: (count, >=d) float32
+    rows to write into."""
+    from . import _lib
+    codes = np.asarray(codes, dtype=np.uint8)
+    if codes.ndim != 2 or codes.strides[1] != 1:
+        codes = np.ascontiguousarray(codes)
+    K = np.ascontiguousarray(K, dtype=np.float32)
+    n, d = int(codes.shape[0]), int(K.shape[1])
+    ldc = int(codes.strides[0]) if n > 1 else int(codes.shape[1])
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+    count = n if ids is None else int(ids.shape[0])
+    if out is None:
+        out = np.zeros((count, d), dtype=np.float32)
+    if out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != count or out.shape[1] < d or out.strides[1] != 4 or out.strides[0] % 4:
+        raise ValueError("out must be (count, >=d) float32 rows with unit column stride")
+    ldo = int(out.strides[0] // 4) if count > 1 else int(out.shape[1])
+    cent = None if centroids is None else np.ascontiguousarray(centroids, dtype=np.float32)
+    lor = None if assign is None else np.ascontiguousarray(assign, dtype=np.int32)
+    ptr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
+    fl = (_lib.RECON_ADD_COARSE if add_coarse else 0) | (_lib.RECON_PAD_NAN if pad_nan else 0)
+    _lib.check(_lib.load().lsq_reconstruct_cpu(ptr(out), ldo, ptr(codes), ldc, ptr(K), ptr(ids), count, int(id_base), n, int(m), int(h), d, ptr(cent),
+                                               ptr(lor), fl, int(nthreads)))
+    return out
+
+
 def quantize_norms(B, C, cbnorms, *, engine=None):
     """src/utils.jl:6-31: squared norm of every reconstruction (f32, dimensions ascending), then the index
     (1-based Int16) of the nearest scalar centroid in `cbnorms`; ties -> lowest index (findmin).

@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--delete FRACTION] [--radius R] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--delete FRACTION] [--radius R] [--reconstruct] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -43,6 +43,9 @@ the same resident base rows.  The reference has no such search.
 resident index (Index.remove: tombstones) and the recall of the ADC search -- and of the --ivf search over the same codes -- is taken against Index.knn over
 the rows that are left; then Index.compact makes the rows leave, the same searches run again, and their ids, taken back through old_of_new, must name the
 same rows: the demo asserts it and prints the two recall curves side by side.
+
+--reconstruct: the base prefix decoded from the resident codes (Index.reconstruct) with its mean squared error against the base rows, with --ivf ...
+--residual also the residual index decoded with the coarse add, and one search whose queries are stored rows (Index.search_rows).
 
 --radius R (alone or beside --ivf and --filter, whose sections run as before): range search on a resident index (Index.range_search) -- every base row
 whose ADC distance to the query is <= R, R in the scan's own units (the distances linscan_lsq prints), or `auto`: the median over the queries of the 10th
@@ -154,7 +157,7 @@ def train_resident(x_train, m, h, niter, ilsiter, icmiter, randord, npert):
     return [np.ascontiguousarray(K[i * h:(i + 1) * h].T) for i in range(m)], B, cbnorms, B_norms, obj
 
 
-def residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, npert, nprobe, knn, norm_byte, n0=None):
+def residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, npert, nprobe, knn, norm_byte, n0=None, recon=False):
     """the residual index over the SAME centroids and lists, resident on the device -> (recall curve, seconds of the build, error in base, and with n0 the
     recall curve of the index built on the first n0 rows and grown by the rest -- else None)"""
     import torch
@@ -179,6 +182,12 @@ def residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter
         with ix:
             _, ridx = ix.search_ivf(torch.from_numpy(Q).cuda(), knn, nprobe, add_coarse=True)
             ridx = ridx.cpu().numpy()
+            if recon:                                                       # --reconstruct: the residual codes decoded with the centroid of each row's list
+                pre = min(int(dXb.shape[0]), 100000)
+                xh = ix.reconstruct(count=pre, add_coarse=True)
+                mse = float(((dXb[:pre].float() - xh).double() ** 2).sum(dim=1).mean().item())
+                print("Decoded %d rows of the residual index on the device (centroid + residual codes): mean squared error against the base rows %e; row -> list "
+                      "map built once (%d)" % (pre, mse, ix.recon_info()["map_rebuilds"]))
         grec = None
         if n0 is not None:                                                  # --grow: the same build on the first n0 rows, the rest appended
             gx = lsq.build_ivf_residual_index(dXb[:n0], part, dK, m, engine=eng, ilsiters=[16], icmiter=icmiter, npert=npert, randord=randord, cbnorms=cb)
@@ -261,8 +270,8 @@ def main():
         del argv[at:at + 2]
         if not ivf:
             raise SystemExit("--grow needs --ivf NLIST:NPROBE")
-    args = [a for a in argv if a not in ("--resident", "--bvecs", "--norm-byte", "--residual")]
-    resident, bvecs, norm_byte, residual = "--resident" in argv, "--bvecs" in argv, "--norm-byte" in argv, "--residual" in argv
+    args = [a for a in argv if a not in ("--resident", "--bvecs", "--norm-byte", "--residual", "--reconstruct")]
+    resident, bvecs, norm_byte, residual, recon = "--resident" in argv, "--bvecs" in argv, "--norm-byte" in argv, "--residual" in argv, "--reconstruct" in argv
     if residual and not ivf:
         raise SystemExit("--residual needs --ivf NLIST:NPROBE")
     real = bool(os.environ.get("LSQ_DATA_DIR"))
@@ -362,7 +371,7 @@ def main():
                 grec = lsq.eval_recall(gt, np.ascontiguousarray(gidx.T).astype(np.uint32), knn)
             if residual:
                 rrec_ivf, t_res, mse, gres = residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, min(npert, m),
-                                                          nprobe, knn, norm_byte, n0)
+                                                          nprobe, knn, norm_byte, n0, recon)
         irec = lsq.eval_recall(gt, np.ascontiguousarray(iidx.T).astype(np.uint32), knn)
         print("IVF search (nlist %d, nprobe %d): %.3f s on the resident index; %.0f of %d rows probed per query, %d of %d queries on the thresholded road"
               % (nlist, nprobe, t_ivf, info["probed_rows"] / Q.shape[0], x_base.shape[1], info["threshold_queries"], Q.shape[0]))
@@ -382,6 +391,29 @@ def main():
         if radius == "auto":
             radius = float(np.median(dists[min(10, knn) - 1]))
         range_counts(radius, name, x_base, x_query, B_base, C, db_norms, m, ivf, fraction)
+    if recon:
+        reconstruct_rows(name, x_base, B_base, C, db_norms, m, knn)
+
+
+def reconstruct_rows(name, x_base, B_base, C, db_norms, m, knn):
+    """--reconstruct: the base prefix decoded from the resident codes (Index.reconstruct) and its mean squared error against the base rows -- the encode's
+    objective, measured from the index alone -- then one search whose queries are stored rows (Index.search_rows)"""
+    n = x_base.shape[1]
+    pre, k = min(n, 100000), min(knn, 10)
+    with lsq.Engine(0) as eng, eng.index((B_base - 1).astype(np.uint8).T, np.ascontiguousarray(np.hstack(C).T), db_norms, m) as ix:
+        t0 = time.perf_counter()
+        xh = ix.reconstruct(count=pre)
+        dt = time.perf_counter() - t0
+        assert np.array_equal(xh.view(np.uint32), np.ascontiguousarray(lsq.reconstruct(B_base[:, :pre], C).T).view(np.uint32)) or np.isnan(xh).any(), \
+            "the device decode and the numpy mirror disagree"
+        mse = float(((np.asarray(x_base[:, :pre], dtype=np.float32).T.astype(np.float64) - xh) ** 2).sum(axis=1).mean())
+        rows = np.arange(0, n, max(1, n // 8), dtype=np.int32)[:8]
+        dists, ids = ix.search_rows(rows, k)
+        own = int(sum(int(rows[q]) + 1 == int(ids[q, 0]) for q in range(rows.shape[0])))
+    print("Decoded %d base rows from the resident codes in %.3f s (host buffers, incl. the fetch), the numpy mirror's bits; mean squared error against the base "
+          "rows %e" % (pre, dt, mse))
+    print("%s: neighbours of %d stored rows (search_rows, k = %d): %d of them are their own nearest row (no self-exclusion; quantised norms)"
+          % (name, rows.shape[0], k, own, ))
 
 
 def range_counts(radius, name, x_base, x_query, B_base, C, db_norms, m, ivf, fraction):
