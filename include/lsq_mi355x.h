@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 2400
+#define LSQ_VERSION 2500
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -396,6 +396,8 @@ LSQ_API int lsq_get_linscan_stats(lsq_ctx *ctx, lsq_linscan_stats *out);
  *   Result per query: the nn smallest (dist, id) pairs among its L candidates in lexicographic order; ties go to the smaller id; NaN distances sort
  *   after every number.  An id that occurs twice is returned twice.  An id outside [id_base, id_base + n) is never dereferenced: it sorts after everything,
  *   NaN included, and is reported as (+inf, id_base - 1).
+ * base_u8 = LSQ_BASE_F16 / LSQ_BASE_BF16 (since v2500, (3o)): rows of 2-byte elements, 2-byte aligned, widened likewise -- the bits of the f32 call on
+ * the widened matrix; 16-byte, 4-byte or 2-byte loads by the same rule (the last, partial dword of an odd-d row travels as one 2-byte load).
  * LSQ_EINVAL: nn < 1, nn > L, d < 1, ldb < d, ldq < d, n < 1, an id_base other than 0 / 1, a null pointer.
  *   lsq_rerank_cpu  host cores, std::thread workers (nthreads 0 = all), no context: the checker and the engine-less road. */
 LSQ_API int lsq_rerank_cpu(float *dists, int *ids, const void *base, int base_u8, const float *queries, const int *cand, int n, int nq, int d, int ldb,
@@ -414,8 +416,9 @@ typedef struct lsq_index_desc {
     const uint8_t *codes;        /* [n][m] uint8 0-based, or NULL */
     const float *codebooks;      /* [m*h][d] */
     const float *dbnorms;        /* [n] */
-    const void *base;            /* [n][ldb] float32 or uint8, or NULL */
-    int base_u8, ldb;
+    const void *base;            /* [n][ldb] float32, uint8, binary16 or bfloat16 (base_u8 says which), or NULL */
+    int base_u8, ldb;            /* base_u8 is the FORMAT of the base rows (since v2500, (3o)): 0 f32, 1 uint8, LSQ_BASE_F16, LSQ_BASE_BF16; any other non-zero value
+                                    means uint8, as it did while the field was a flag.  ldb in elements */
     int on_device;
 } lsq_index_desc;
 typedef struct lsq_index_stats {
@@ -468,7 +471,7 @@ typedef struct lsq_index_knn_info {
 LSQ_API int lsq_index_get_knn_info(lsq_index *ix, lsq_index_knn_info *out);
 /* The host drop-in and checker (no context): lsq_knn_exact_cpu for base rows and queries that are f32 or uint8 (base_u8 / queries_u8) at ANY byte
  * alignment, ldb / ldq in elements; uint8 elements are widened (exact) and the f32 chain runs: the bits of lsq_knn_exact_cpu on the widened matrices.
- * ids uint32 0-based.  LSQ_EINVAL as lsq_knn_exact_cpu. */
+ * ids uint32 0-based.  LSQ_EINVAL as lsq_knn_exact_cpu.  base_u8 = LSQ_BASE_F16 / LSQ_BASE_BF16 (since v2500, (3o)): half rows, widened likewise. */
 LSQ_API int lsq_knn_exact_u8_cpu(float *dists, uint32_t *ids, const void *base, int base_u8, const void *queries, int queries_u8, int n, int nq, int d,
                                  int ldb, int ldq, int nn, int nthreads);
 
@@ -887,6 +890,57 @@ LSQ_API int lsq_index_reconstruct(lsq_index *ix, float *out, int64_t ldo, const 
 LSQ_API int lsq_index_search_rows(lsq_index *ix, float *dists, int *ids_out, const int32_t *rows, int nq, int id_base, int nn, int nprobe, int flags,
                                   int on_device);
 LSQ_API int lsq_index_get_recon_info(lsq_index *ix, lsq_index_recon_info *out);
+
+/* ---- (3o) half-precision base rows: binary16 and bfloat16 (csrc/lsq_half.hip; since v2500) ---------------------------------------------------------------
+ * THE REFERENCE HAS NO COUNTERPART: it keeps no base rows at all (its recall figures are those of the ADC distances, src/linscan/Linscan.jl:76-117).  The
+ * index's second copy of the base set -- what the exact re-rank (3e) and exact k-NN (3f) read -- may hold 2-byte elements: 2 d bytes per row beside the
+ * m or m + 1 bytes of codes, instead of 4 d.
+ *   LSQ_BASE_F16   IEEE binary16.          LSQ_BASE_BF16   the upper 16 bits of a binary32.
+ * Both go in the base_u8 field of lsq_index_desc / lsq_index_packed_desc and in the base_u8 argument of lsq_rerank_cpu / lsq_knn_exact_u8_cpu; the field
+ * keeps its place and size.  A half base must be 2-byte aligned (LSQ_EINVAL otherwise; the f32 rule asks for 4); ldb is in elements, >= d, and may be odd.
+ * lsq_index_add takes appended base rows in the index's own format.
+ *   IDENTITY W.  Widening a half to f32 is exact (subnormals are kept, never flushed; +-inf and NaN stay what they are), and every kernel widens in registers
+ *   right before the arithmetic, as the 8-bit rows do ((3e), (3f)).  So an index whose base rows are the halves H returns, for EVERY call that reads base rows --
+ *   lsq_index_rerank, lsq_index_search / _search_ivf with a shortlist, lsq_index_knn on its unfiltered, dense-filter and compact-filter roads -- and after
+ *   lsq_index_add / _remove / _compact / _reserve, what the same index over the f32 matrix widen(H) returns: distances and ids bit for bit, NaN where that
+ *   call has NaN, every statistic that does not count bytes or name the format.  Queries stay f32 (or uint8 for lsq_index_knn); the integer road of (3f)
+ *   does not apply.
+ *   IDENTITY N.  Narrowing is round-to-nearest-even.  binary16: overflow (from 65520 on) to +-inf, subnormals kept, NaN to a NaN -- the bits of numpy's
+ *   astype(float16).  bfloat16: for a non-NaN x with bits u, (u + 0x7fff + ((u >> 16) & 1)) >> 16 (the carry may reach the exponent, and f32 max becomes inf);
+ *   NaN to a NaN, payload not pinned.  Device and host give the same bits for every non-NaN input.
+ *   lsq_narrow_rows_cpu     beside lsq_rerank_cpu: the host narrowing, no context, std::thread workers (nthreads 0 = all).  dst row i (ldd halves apart, 2-byte
+ *                           aligned) = narrow(src row i, lds floats apart), d components each; nothing else of dst is written.  The checker of the device
+ *                           narrowing and the road the host binding uses.  LSQ_EINVAL, nothing written: a format other than the two, n < 0, d < 1, lds < d,
+ *                           ldd < d, a null or misaligned pointer.
+ *   lsq_index_narrow_base   beside lsq_index_compact: the index's resident F32 base rows are converted ON THE DEVICE into rows of `format` that the index owns,
+ *                           dense (ldb becomes d).  Afterwards the index is, for every call, the index created over narrow(base).  A borrowed f32 base is left
+ *                           untouched and dropped from the index (the caller may free it); an owned one is freed after the convert.  THE TRANSIENT PEAK IS OLD
+ *                           PLUS NEW: 6 d bytes per row until the call returns.  The capacity of an owned base (lsq_index_reserve) is kept.  Like
+ *                           lsq_index_add and lsq_index_compact it drops a held range result (3m).  It waits for the device.  LSQ_EINVAL, NOTHING CHANGED: an
+ *                           index without base rows, a base that is not f32 (a second call included), a format other than the two.
+ *   lsq_index_get_base      beside lsq_index_reconstruct, which returns what the CODES stand for: this returns the STORED base rows [start, start + count),
+ *                           widened to f32 whatever the format (an f32 base: a copy; a uint8 base: widened).  out [count][ldo] host (on_device = 0: widened
+ *                           into staging in chunks of rows and fetched, 64 MiB at a time; option "recon_chunk" as for lsq_index_reconstruct) or device (1).
+ *                           NOT AFFECTED BY A ROW FILTER.  It changes nothing.  LSQ_EINVAL BEFORE ANYTHING IS WRITTEN: a range that leaves [0, n], ldo < d, an
+ *                           index without base rows, a null (count > 0) or misaligned out.  count == 0: LSQ_OK.
+ *   lsq_index_get_base_info beside lsq_index_get_packed_info: what the base rows are now, and what the last lsq_index_narrow_base did. */
+#define LSQ_BASE_F16 2
+#define LSQ_BASE_BF16 3
+typedef struct lsq_index_base_info {     /* fields are only ever appended */
+    int64_t format;              /* 0 f32, 1 uint8, LSQ_BASE_F16, LSQ_BASE_BF16; all zero on an index without base rows */
+    int64_t elem_bytes;          /* 4, 1, 2 */
+    int64_t ldb;                 /* elements between rows */
+    int64_t owned;               /* 1: the index owns the rows; 0: it borrows the caller's */
+    int64_t resident_bytes;      /* ((n - 1) ldb + d) elem_bytes: the rows up to the d-th element of the last one */
+    int64_t to_inf;              /* the last lsq_index_narrow_base: finite values that became +-inf */
+    int64_t to_zero;             /*   non-zero values that became +-0 */
+    int64_t nans;                /*   NaNs */
+    double narrow_ms;            /*   its kernel, with option "profile" = 1 */
+} lsq_index_base_info;
+LSQ_API int lsq_narrow_rows_cpu(void *dst, const float *src, int64_t n, int d, int64_t lds, int64_t ldd, int format, int nthreads);
+LSQ_API int lsq_index_narrow_base(lsq_index *ix, int format);
+LSQ_API int lsq_index_get_base(lsq_index *ix, float *out, int64_t start, int64_t count, int64_t ldo, int on_device);
+LSQ_API int lsq_index_get_base_info(lsq_index *ix, lsq_index_base_info *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

@@ -117,6 +117,12 @@ class IndexReconInfo(_Struct):
                 ("calls", C.c_int64), ("map_ms", C.c_double), ("decode_ms", C.c_double)]
 
 
+class IndexBaseInfo(_Struct):
+    _fields_ = [("format", C.c_int64), ("elem_bytes", C.c_int64), ("ldb", C.c_int64), ("owned", C.c_int64), ("resident_bytes", C.c_int64),
+                ("to_inf", C.c_int64), ("to_zero", C.c_int64), ("nans", C.c_int64), ("narrow_ms", C.c_double)]
+
+
+BASE_F32, BASE_U8, BASE_F16, BASE_BF16 = 0, 1, 2, 3       # the format a base_u8 field / argument stands for (LSQ_BASE_F16, LSQ_BASE_BF16)
 RECON_ADD_COARSE, RECON_PAD_NAN = 1, 2
 RECON_ROAD_DWORD, RECON_ROAD_VEC16, RECON_ROAD_CODE_DWORDS = 1, 2, 4
 
@@ -262,6 +268,11 @@ SIGNATURES = {
     "lsq_index_reconstruct": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i]),
     "lsq_index_search_rows": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "lsq_index_get_recon_info": (_i, [_vp, C.POINTER(IndexReconInfo)]),
+    # half-precision base rows (since v2500): the host narrowing, the device narrowing of a resident base, the stored rows read back
+    "lsq_narrow_rows_cpu": (_i, [_vp, _vp, _i64, _i, _i64, _i64, _i, _i]),
+    "lsq_index_narrow_base": (_i, [_vp, _i]),
+    "lsq_index_get_base": (_i, [_vp, _vp, _i64, _i64, _i64, _i]),
+    "lsq_index_get_base_info": (_i, [_vp, C.POINTER(IndexBaseInfo)]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),
@@ -303,7 +314,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 2400     # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 2500     # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

@@ -551,7 +551,7 @@ extern "C" int lsq_get_linscan_stats(lsq_ctx *c, lsq_linscan_stats *out) {
 struct lsq_index {
     lsq_ctx *ctx = nullptr;
     int64_t n = 0;
-    int d = 0, m = 0, base_u8 = 0;
+    int d = 0, m = 0, base_u8 = 0;                      // base_u8: the FORMAT of the base rows (lsq_base_format: 0 f32, 1 uint8, LSQ_BASE_F16, LSQ_BASE_BF16)
     int64_t ldb = 0;
     const uint8_t *codes = nullptr;                    // device pointers: the index's own copies (host-buffer description) or the caller's (borrowed)
     const float *K = nullptr, *norms = nullptr;
@@ -585,6 +585,10 @@ struct lsq_index {
     bool r_lor_valid = false;                          // r_lor answers for the inverted layout in force (lsq_index_set_lists / _add / _compact clear it)
     lsq_index_recon_info rinfo{};
     PhaseClock<3> rclock;                              // a decode's map and decode phases
+    DevBuf h_counts;                                   // lsq_index_narrow_base: the three counters of the convert
+    lsq_narrow_counts hcounts{};                       // ... read back, and its time
+    double narrow_ms = 0.0;
+    PhaseClock<2> hclock;
 };
 
 // the filter as a scan over all rows takes it: nothing without one; else the compact road -- the ascending list of allowed rows -- where the measured rule
@@ -606,12 +610,13 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     (void)hipStreamSynchronize(ix->ctx->stream);
     DevBuf *bufs[] = {&ix->own_codes, &ix->own_K, &ix->own_norms, &ix->own_base, &ix->rec_a, &ix->rec_b, &ix->seg, &ix->counter, &ix->short_d, &ix->short_i,
                       &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q, &ix->s_qcoarse, &ix->g_codes, &ix->g_nc, &ix->g_rows,
-                      &ix->c_old, &ix->c_new, &ix->s_radius, &ix->r_lor, &ix->r_ids, &ix->r_out, &ix->r_q};
+                      &ix->c_old, &ix->c_new, &ix->s_radius, &ix->r_lor, &ix->r_ids, &ix->r_out, &ix->r_q, &ix->h_counts};
     for (DevBuf *b : bufs) b->release();
     lsq_range_free(ix->range);
     ix->gclock.release();
     ix->cclock.release();
     ix->rclock.release();
+    ix->hclock.release();
     lsq_adc_free(ix->adc);
     lsq_ivf_free(ix->ivf);
     lsq_filter_free(ix->filter);
@@ -645,11 +650,11 @@ extern "C" int lsq_index_create(lsq_index **out, lsq_ctx *c, const lsq_index_des
         if (!desc->codebooks || !desc->dbnorms) { lsq_set_error("lsq_index_create: codes without codebooks or dbnorms"); return LSQ_EINVAL; }
     }
     if (desc->base && desc->ldb < desc->d) { lsq_set_error("lsq_index_create: needs ldb >= d (got ldb=%d d=%d)", desc->ldb, desc->d); return LSQ_EINVAL; }
-    if (desc->base && !desc->base_u8 && ((uintptr_t)desc->base & 3) != 0) { lsq_set_error("lsq_index_create: the f32 base is not 4-byte aligned"); return LSQ_EINVAL; }
+    if (desc->base) if (const char *why = lsq_base_align_refusal(lsq_base_format(desc->base_u8), desc->base)) { lsq_set_error("lsq_index_create: %s", why); return LSQ_EINVAL; }
     LSQ_TRY(use_device(c));
     lsq_index *ix = new lsq_index();
     ix->ctx = c;
-    ix->n = desc->n; ix->d = desc->d; ix->m = desc->codes ? desc->m : 0; ix->base_u8 = desc->base_u8 != 0; ix->ldb = desc->ldb;
+    ix->n = desc->n; ix->d = desc->d; ix->m = desc->codes ? desc->m : 0; ix->base_u8 = lsq_base_format(desc->base_u8); ix->ldb = desc->ldb;
     const size_t n = (size_t)desc->n, d = (size_t)desc->d;
     int rc = LSQ_OK;
     if (desc->codes) {
@@ -658,7 +663,7 @@ extern "C" int lsq_index_create(lsq_index **out, lsq_ctx *c, const lsq_index_des
         if (rc == LSQ_OK) rc = index_adopt(ix, ix->own_norms, desc->dbnorms, sizeof(float) * n, desc->on_device, reinterpret_cast<const void **>(&ix->norms));
     }
     if (rc == LSQ_OK && desc->base)      // rows up to the d-th element of the last one
-        rc = index_adopt(ix, ix->own_base, desc->base, ((n - 1) * (size_t)desc->ldb + d) * (desc->base_u8 ? 1 : sizeof(float)), desc->on_device, &ix->base);
+        rc = index_adopt(ix, ix->own_base, desc->base, ((n - 1) * (size_t)desc->ldb + d) * lsq_base_elem_bytes(ix->base_u8), desc->on_device, &ix->base);
     if (rc == LSQ_OK) rc = ix->counter.ensure(sizeof(unsigned long long));
     if (rc == LSQ_OK && hipStreamSynchronize(c->stream) != hipSuccess) { lsq_set_error("lsq_index_create: the upload failed"); rc = LSQ_EHIP; }
     if (rc != LSQ_OK) { (void)lsq_index_destroy(ix); return rc; }
@@ -682,12 +687,12 @@ extern "C" int lsq_index_create_packed(lsq_index **out, lsq_ctx *c, const lsq_in
     if (!desc->codebooks || !desc->norm_codes || !desc->cbnorms) { lsq_set_error("%s: codes without codebooks, norm_codes or cbnorms", fn); return LSQ_EINVAL; }
     if (desc->ncb < 1 || desc->ncb > 256) { lsq_set_error("%s: needs 1 <= ncb <= 256 (got %d)", fn, desc->ncb); return LSQ_EINVAL; }
     if (desc->base && desc->ldb < desc->d) { lsq_set_error("%s: needs ldb >= d (got ldb=%d d=%d)", fn, desc->ldb, desc->d); return LSQ_EINVAL; }
-    if (desc->base && !desc->base_u8 && ((uintptr_t)desc->base & 3) != 0) { lsq_set_error("%s: the f32 base is not 4-byte aligned", fn); return LSQ_EINVAL; }
+    if (desc->base) if (const char *why = lsq_base_align_refusal(lsq_base_format(desc->base_u8), desc->base)) { lsq_set_error("%s: %s", fn, why); return LSQ_EINVAL; }
     LSQ_TRY(use_device(c));
     hipStream_t s = c->stream;
     lsq_index *ix = new lsq_index();
     ix->ctx = c;
-    ix->n = desc->n; ix->d = desc->d; ix->m = desc->m; ix->base_u8 = desc->base_u8 != 0; ix->ldb = desc->ldb;
+    ix->n = desc->n; ix->d = desc->d; ix->m = desc->m; ix->base_u8 = lsq_base_format(desc->base_u8); ix->ldb = desc->ldb;
     ix->packed = 1; ix->ncb = desc->ncb;
     const size_t n = (size_t)desc->n, d = (size_t)desc->d, m = (size_t)desc->m;
     DevBuf s_codes, s_nc;                              // the host form's staging of what the pack kernel reads: gone when the call returns
@@ -713,7 +718,7 @@ extern "C" int lsq_index_create_packed(lsq_index **out, lsq_ctx *c, const lsq_in
         ix->norms = ix->own_norms.as<float>();
         LSQ_TRY(index_adopt(ix, ix->own_K, desc->codebooks, sizeof(float) * m * LSQ_H * d, desc->on_device, reinterpret_cast<const void **>(&ix->K)));
         if (desc->base)
-            LSQ_TRY(index_adopt(ix, ix->own_base, desc->base, ((n - 1) * (size_t)desc->ldb + d) * (desc->base_u8 ? 1 : sizeof(float)), desc->on_device, &ix->base));
+            LSQ_TRY(index_adopt(ix, ix->own_base, desc->base, ((n - 1) * (size_t)desc->ldb + d) * lsq_base_elem_bytes(ix->base_u8), desc->on_device, &ix->base));
         if (hipStreamSynchronize(s) != hipSuccess) { lsq_set_error("%s: the upload failed", fn); return LSQ_EHIP; }
         if (bad) { lsq_set_error("%s: %u norm bytes lie outside [0, %d)", fn, bad, desc->ncb); return LSQ_EINVAL; }
         return LSQ_OK;
@@ -944,7 +949,7 @@ extern "C" int lsq_index_knn(lsq_index *ix, float *dists, int *ids, const void *
     LSQ_TRY(call.outputs(dists, ids, nn));
     lsq_search_input in = exact_input(ix->base, ix->base_u8, (int)ix->ldb, dq, q_u8, ldq, n, d);
     in.id_base = id_base;
-    const bool int_road = ix->base_u8 && q_u8 && d <= 258 && c->knn_u8_int;      // d 255^2 <= 2^24: (float)D is the chain's result
+    const bool int_road = ix->base_u8 == 1 && q_u8 && d <= 258 && c->knn_u8_int;      // d 255^2 <= 2^24: (float)D is the chain's result
     lsq_index_knn_info info{};
     if (int_road) {
         // nothing is cached across calls: a borrowed base may have changed since the last one
@@ -1139,7 +1144,7 @@ extern "C" int lsq_index_get_filter_info(lsq_index *ix, lsq_filter_info *out) {
 // swapped) and its layout-order bits (lsq_filter_layout again); the scan state's sample and record buffers, stage two's records, nrm_x and every staging
 // buffer are sized from the call's own n at every call (DevBuf::ensure) and hold nothing across calls; idbits and the selection's road are computed per call
 static size_t index_row_bytes(const lsq_index *ix) { return (size_t)(ix->packed ? ix->m + 1 : ix->m); }
-static size_t index_base_elem(const lsq_index *ix) { return ix->base_u8 ? 1 : sizeof(float); }
+static size_t index_base_elem(const lsq_index *ix) { return lsq_base_elem_bytes(ix->base_u8); }      // 4, 1 or 2
 static bool index_borrows(const lsq_index *ix) {
     return (ix->codes && ix->codes != ix->own_codes.p) || (ix->codes && !ix->packed && ix->norms != ix->own_norms.p) || (ix->base && ix->base != ix->own_base.p);
 }
@@ -1418,6 +1423,92 @@ extern "C" int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *de
 extern "C" int lsq_index_get_compact_info(lsq_index *ix, lsq_index_compact_info *out) {
     if (!ix || !out) { lsq_set_error("lsq_index_get_compact_info: null argument"); return LSQ_EINVAL; }
     *out = ix->cinfo;
+    return LSQ_OK;
+}
+
+// ---- half-precision base rows (lsq_half.hip): the resident f32 rows narrowed in place of themselves, and the stored rows read back ---------------
+// What depends on the base rows' format, and what a narrowing does about it: ix->base, ldb, base_u8 (committed last, after the one wait, the new rows written
+// beside the old); own_base (swapped: an owned f32 base is freed here, a borrowed one is the caller's); cap_rows (kept: the new rows are sized for it).  The
+// scan state, stage two's records, nrm_x and every staging buffer are sized per call and hold nothing across calls; the integer road of lsq_index_knn asks for
+// uint8 rows at every call
+extern "C" int lsq_index_narrow_base(lsq_index *ix, int format) {
+    const char *fn = "lsq_index_narrow_base";
+    if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
+    if (const char *why = lsq_narrow_base_refusal(ix->base != nullptr, ix->base_u8, format)) { lsq_set_error("%s: %s (format=%d)", fn, why, format); return LSQ_EINVAL; }
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    const size_t rows = (size_t)(ix->cap_rows > ix->n ? ix->cap_rows : ix->n), d = (size_t)ix->d;
+    ScopedBuf half;                                   // what it holds when the call ends is freed: the new rows after a failure, the former owned rows after the commit
+    LSQ_TRY(half.b.ensure(rows * d * 2));
+    LSQ_TRY(ix->h_counts.ensure(3 * sizeof(unsigned long long)));
+    LSQ_HIP(hipMemsetAsync(ix->h_counts.p, 0, 3 * sizeof(unsigned long long), s));
+    LSQ_TRY(ix->hclock.begin(c->profile != 0));
+    LSQ_TRY(ix->hclock.mark(s));
+    LSQ_TRY(lsq_half_launch_narrow(s, static_cast<const float *>(ix->base), ix->ldb, half.b.p, ix->n, ix->d, format, ix->h_counts.as<unsigned long long>()));
+    LSQ_TRY(ix->hclock.mark(s));
+    unsigned long long cnt[3] = {0, 0, 0};
+    LSQ_HIP(hipMemcpyAsync(cnt, ix->h_counts.p, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    LSQ_HIP(hipStreamSynchronize(s));                 // the one wait: everything is written, nothing is in force
+    float ms[1];
+    LSQ_TRY(ix->hclock.read(ms));
+    std::swap(ix->own_base, half.b);                  // the commit
+    ix->base = ix->own_base.p;
+    ix->ldb = ix->d;
+    ix->base_u8 = format;
+    lsq_range_drop(ix->range);
+    ix->hcounts.to_inf = (int64_t)cnt[0]; ix->hcounts.to_zero = (int64_t)cnt[1]; ix->hcounts.nans = (int64_t)cnt[2];
+    ix->narrow_ms = ms[0];
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_base(lsq_index *ix, float *out, int64_t start, int64_t count, int64_t ldo, int on_device) {
+    const char *fn = "lsq_index_get_base";
+    if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
+    if (const char *why = lsq_get_base_refusal(ix->base != nullptr, ix->n, ix->d, start, count, ldo, out)) {
+        lsq_set_error("%s: %s (start=%lld count=%lld ldo=%lld n=%lld d=%d)", fn, why, (long long)start, (long long)count, (long long)ldo, (long long)ix->n, ix->d);
+        return LSQ_EINVAL;
+    }
+    if (count == 0) return LSQ_OK;
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    const size_t e = index_base_elem(ix), d = (size_t)ix->d;
+    const char *first = static_cast<const char *>(ix->base) + (size_t)start * (size_t)ix->ldb * e;
+    if (ix->base_u8 == 0) {                           // f32 rows: a copy, each row's d floats
+        LSQ_HIP(hipMemcpy2DAsync(out, sizeof(float) * (size_t)ldo, first, sizeof(float) * (size_t)ix->ldb, sizeof(float) * d, (size_t)count,
+                                 on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipStreamSynchronize(s));
+        return LSQ_OK;
+    }
+    if (on_device) {                                  // one launch, straight into the caller's rows
+        LSQ_TRY(lsq_half_launch_widen(s, first, ix->base_u8, ix->ldb, out, ldo, count, ix->d));
+        LSQ_HIP(hipStreamSynchronize(s));
+        return LSQ_OK;
+    }
+    // host form: chunks of rows widened d floats apart into the index's staging (lsq_index_reconstruct's), each row's d floats copied out
+    const int64_t rows = lsq_base_chunk_rows(count, ix->d, c->recon_chunk);
+    LSQ_TRY(ix->r_out.ensure(sizeof(float) * (size_t)rows * d));
+    for (int64_t r0 = 0; r0 < count; r0 += rows) {
+        const int64_t cn = std::min<int64_t>(rows, count - r0);
+        LSQ_TRY(lsq_half_launch_widen(s, first + (size_t)r0 * (size_t)ix->ldb * e, ix->base_u8, ix->ldb, ix->r_out.as<float>(), ix->d, cn, ix->d));
+        LSQ_HIP(hipMemcpy2DAsync(out + r0 * ldo, sizeof(float) * (size_t)ldo, ix->r_out.p, sizeof(float) * d, sizeof(float) * d, (size_t)cn, hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipStreamSynchronize(s));             // the staging is written again by the next chunk
+    }
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_base_info(lsq_index *ix, lsq_index_base_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_base_info: null argument"); return LSQ_EINVAL; }
+    *out = lsq_index_base_info{};
+    if (!ix->base) return LSQ_OK;
+    out->format = ix->base_u8;
+    out->elem_bytes = (int64_t)index_base_elem(ix);
+    out->ldb = ix->ldb;
+    out->owned = ix->base == ix->own_base.p ? 1 : 0;
+    out->resident_bytes = ((ix->n - 1) * ix->ldb + ix->d) * (int64_t)index_base_elem(ix);
+    out->to_inf = ix->hcounts.to_inf; out->to_zero = ix->hcounts.to_zero; out->nans = ix->hcounts.nans;
+    out->narrow_ms = ix->narrow_ms;
     return LSQ_OK;
 }
 

@@ -10,7 +10,7 @@
 struct lsq_grow_shape {
     int64_t n;
     int d;
-    int has_codes, has_base, packed, base_u8, has_lists;
+    int has_codes, has_base, packed, base_u8, has_lists;      // base_u8: the format of the base rows (0 f32, 1 uint8, LSQ_BASE_F16, LSQ_BASE_BF16)
 };
 
 constexpr int64_t LSQ_GROW_MAX_ROWS = (int64_t)INT32_MAX - 1;        // 2^31 - 2: lsq_index_create's bound on n
@@ -41,6 +41,7 @@ inline const char *lsq_grow_add_refusal(const lsq_grow_shape &ix, const lsq_inde
         if (!desc->base) return "the index holds base rows: base is required";
         if (desc->ldb < ix.d) return "ldb < d";
         if (!ix.base_u8 && ((uintptr_t)desc->base & 3) != 0) return "the f32 base is not 4-byte aligned";
+        if ((ix.base_u8 == LSQ_BASE_F16 || ix.base_u8 == LSQ_BASE_BF16) && ((uintptr_t)desc->base & 1) != 0) return "the half-precision base is not 2-byte aligned";
     }
     return nullptr;
 }

@@ -11,6 +11,7 @@
 #include "lsq_compact_check.h"
 #include "lsq_range_check.h"
 #include "lsq_recon_check.h"
+#include "lsq_half_check.h"
 
 #define LSQ_H 256          // candidates per codebook: one wave x float4 per lane
 #define LSQ_MAX_M 16
@@ -326,7 +327,7 @@ struct lsq_search_input {
     const float *dbnorms;
     int n, m, d;
     const void *base; int bstride;           // exact: [n][bstride], the first d elements of a row used
-    int base_u8 = 0, q_u8 = 0;               // exact: element types of base / Q (0: f32, 1: uint8)
+    int base_u8 = 0, q_u8 = 0;               // exact: element types of base / Q (0: f32, 1: uint8; base also LSQ_BASE_F16 / LSQ_BASE_BF16 -- a FORMAT, normalised by lsq_base_format)
     const uint32_t *xnorms = nullptr, *qnorms = nullptr;
     int id_base = 0;                         // exact: ids leave as row + id_base
     int packed = 0;                          // LSQ: rows of cstride = m + 1 bytes, the last one the norm byte c_i; dbnorms = the norm table padded to 256 floats
@@ -340,7 +341,7 @@ struct lsq_search_input {
     int rows_walked() const { return filter_rows ? filter_count : n; }      // rows a full scan reads
     int query_width() const { return kind == LSQ_SEARCH_PQ ? m * d : d; }      // elements of a query row that are read
     int id_sub() const { return kind == LSQ_SEARCH_LSQ ? 0 : 1 - id_base; }    // ids leave as (the record's id field 1 .. n) - id_sub
-    size_t base_elem() const { return base_u8 ? 1 : sizeof(float); }
+    size_t base_elem() const { return lsq_base_elem_bytes(base_u8); }
     size_t query_elem() const { return q_u8 ? 1 : sizeof(float); }
 };
 // how a call searches: the test hooks of the selection (options "linscan_exhaustive", "linscan_rank"), where its statistics go, and whether its
@@ -566,6 +567,13 @@ int lsq_recon_launch_check_ids(hipStream_t s, const int32_t *ids, int64_t count,
 int lsq_recon_launch_lor(hipStream_t s, const int *ids, const int *off, int64_t n, int nlist, int32_t *lor);
 // the centroids of the inverted lists [nlist][d] (lsq_ivf.hip); null without lists
 const float *lsq_ivf_centroids(const lsq_ivf_state *st);
+
+// ---- half-precision base rows (lsq_half.hip): the streaming converts between f32 rows and rows of 2-byte (or 1-byte) elements -------------------
+// dst row i (d halves apart: DENSE, 16-byte aligned) = narrow(src row i, lds floats apart; src 4-byte aligned), format LSQ_BASE_F16 / LSQ_BASE_BF16.  counts
+// (device, zeroed by the caller) [0] += finite values that became +-inf, [1] += non-zero values that became +-0, [2] += NaNs.  No allocation, no wait
+int lsq_half_launch_narrow(hipStream_t s, const float *src, int64_t lds, void *dst, int64_t n, int d, int format, unsigned long long *counts);
+// dst row r (ldo floats apart, 4-byte aligned) = widen(src row r, lds elements apart) for count rows of d elements of `format` (1: uint8, or a half format)
+int lsq_half_launch_widen(hipStream_t s, const void *src, int format, int64_t lds, float *dst, int64_t ldo, int64_t count, int d);
 
 // ---- what a handle that lives in a file of its own (lsq_partition.hip) needs of its context (lsq_api.hip): its device made current, the stream it is bound
 // to now, option "profile".  Nothing of the context is written ------------------------------------------------------------------------------------------

@@ -46,7 +46,8 @@ constexpr int KNN_RL = KNN_RT * KNN_KD / KNN_THREADS;      // staged row floats 
 
 // MODE 0: append (key << idbits | i + 1) of every distance <= tau to the query's candidate list;  MODE 1: write every record of the strided subset
 // i = s * stride, s < ns, to out[slot * ns + s];  MODE 2: the same subset, keys only (u32).  Query of slot: qsel[slot] (fallback) or q0 + slot.
-// TX / TQ: the element types of the rows and of the queries, float or uint8_t (widened where the staged registers are stored to LDS).
+// TX / TQ: the element types of the rows and of the queries, float or uint8_t (widened where the staged registers are stored to LDS); TX also lsq_f16 /
+// lsq_bf16 (lsq_xload.h), widened at the same place.
 // FILT (a row filter, lsq_filter.hip; adc_scan_kernel's rule): frows == nullptr -- dense: walk position p IS the row and its bit of fbits decides whether it
 // leaves a record; frows != nullptr -- compact: position p < nlive is row frows[p], positions past nlive (MODE 1's padding up to nn) are staged as zeros.
 // A row that is filtered or padding does not pass (MODE 0), or leaves as the record of an id outside the base (MODE 1) / the key 0xffffffff (MODE 2).
@@ -340,6 +341,11 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_scan_u8_kernel(const uint8_t 
 #define KNN_BF(M, F) knn_scan_kernel<M, uint8_t, float, F>
 #define KNN_FB(M, F) knn_scan_kernel<M, float, uint8_t, F>
 #define KNN_BB(M, F) knn_scan_kernel<M, uint8_t, uint8_t, F>
+// half rows (lsq_xload.h): 2-byte loads, widened (exact) at the staging store like the bytes -- f32 or uint8 queries, no road of their own
+#define KNN_HF(M, F) knn_scan_kernel<M, lsq_f16, float, F>
+#define KNN_HB(M, F) knn_scan_kernel<M, lsq_f16, uint8_t, F>
+#define KNN_GF(M, F) knn_scan_kernel<M, lsq_bf16, float, F>
+#define KNN_GB(M, F) knn_scan_kernel<M, lsq_bf16, uint8_t, F>
 
 }  // namespace
 
@@ -378,6 +384,13 @@ int lsq_knn_launch_scan(hipStream_t s, int mode, const lsq_search_input &in, con
         const int vecx = lsq_x_vec_ok(Xb) && (ldb & 3) == 0, vecq = lsq_x_vec_ok(Qb) && (ldq & 3) == 0;
         KNN_LAUNCH_MODES(KNN_INT, Xb, ldb, vecx, Qb, ldq, vecq, in.xnorms, in.qnorms, qsel, q0, nqb, d, st, total, per_block, tau, count, cap,
                          out, idbits);
+    } else if (in.base_u8 == LSQ_BASE_F16 || in.base_u8 == LSQ_BASE_BF16) {
+        const lsq_f16 *Xh = static_cast<const lsq_f16 *>(in.base);
+        const lsq_bf16 *Xg = static_cast<const lsq_bf16 *>(in.base);
+        if (in.base_u8 == LSQ_BASE_F16 && in.q_u8) KNN_LAUNCH_MODES(KNN_HB, Xh, ldb, Qb, ldq, qsel, q0, nqb, d, st, total, per_block, tau, count, cap, out, idbits);
+        else if (in.base_u8 == LSQ_BASE_F16) KNN_LAUNCH_MODES(KNN_HF, Xh, ldb, Qf, ldq, qsel, q0, nqb, d, st, total, per_block, tau, count, cap, out, idbits);
+        else if (in.q_u8) KNN_LAUNCH_MODES(KNN_GB, Xg, ldb, Qb, ldq, qsel, q0, nqb, d, st, total, per_block, tau, count, cap, out, idbits);
+        else KNN_LAUNCH_MODES(KNN_GF, Xg, ldb, Qf, ldq, qsel, q0, nqb, d, st, total, per_block, tau, count, cap, out, idbits);
     } else if (in.base_u8 && in.q_u8) {
         KNN_LAUNCH_MODES(KNN_BB, Xb, ldb, Qb, ldq, qsel, q0, nqb, d, st, total, per_block, tau, count, cap, out, idbits);
     } else if (in.base_u8) {

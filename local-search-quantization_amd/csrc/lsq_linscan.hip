@@ -282,14 +282,19 @@ extern "C" int lsq_knn_exact_cpu(float *dists, uint32_t *ids, const float *base,
 // the f32 chain above runs on them -- the contract for EVERY d; the device's integer road (lsq_knn.hip) is held to these bits, not the other way round.
 namespace {
 
-inline float knn_elem(const uint8_t *p, bool u8, int64_t i) {
-    if (u8) return (float)p[i];
+inline float knn_elem(const uint8_t *p, int fmt, int64_t i) {     // fmt: lsq_base_format's (0 f32, 1 uint8, the two halves)
+    if (fmt == 1) return (float)p[i];
+    if (fmt) {
+        uint16_t h;
+        memcpy(&h, p + 2 * i, 2);
+        return lsq_widen_half(h, fmt);
+    }
     float v;
     memcpy(&v, p + 4 * i, 4);
     return v;
 }
 
-void knn_queries_any(float *dists, uint32_t *ids, const uint8_t *base, bool base_u8, const uint8_t *queries, bool q_u8, int q0, int q1, int n, int d,
+void knn_queries_any(float *dists, uint32_t *ids, const uint8_t *base, int base_u8, const uint8_t *queries, int q_u8, int q0, int q1, int n, int d,
                      int ldb, int ldq, int nn) {
     std::vector<uint64_t> heap;
     heap.reserve((size_t)nn + 1);
@@ -334,8 +339,8 @@ extern "C" int lsq_knn_exact_u8_cpu(float *dists, uint32_t *ids, const void *bas
     pool.reserve((size_t)nt);
     for (int t = 0; t < nt; ++t) {
         const int q0 = (int)((int64_t)nq * t / nt), q1 = (int)((int64_t)nq * (t + 1) / nt);
-        pool.emplace_back(knn_queries_any, dists, ids, static_cast<const uint8_t *>(base), base_u8 != 0, static_cast<const uint8_t *>(queries),
-                          queries_u8 != 0, q0, q1, n, d, ldb, ldq, nn);
+        pool.emplace_back(knn_queries_any, dists, ids, static_cast<const uint8_t *>(base), lsq_base_format(base_u8), static_cast<const uint8_t *>(queries),
+                          queries_u8 != 0 ? 1 : 0, q0, q1, n, d, ldb, ldq, nn);
     }
     for (auto &th : pool) th.join();
     return LSQ_OK;

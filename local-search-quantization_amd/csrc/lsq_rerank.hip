@@ -20,7 +20,9 @@
 //            -- never -0 -- unchanged (the reason given at the top of lsq_knn.hip).  Nothing past the d-th component of a row is ever loaded.
 //
 // Alignment (the rule of lsq_xload.h, per 16-byte piece): one 16-byte load when the row pitch in bytes and the base are multiples of 16; dword loads
-// when they are multiples of 4 (every f32 matrix; a uint8 matrix with ldb % 4 == 0 on a 4-byte-aligned base); byte loads otherwise.
+// when they are multiples of 4 (every f32 matrix; a uint8 matrix with ldb % 4 == 0 on a 4-byte-aligned base); byte loads otherwise.  Half rows (lsq_f16 /
+// lsq_bf16, lsq_xload.h): 2 components per dword, 64 per line; dword loads when pitch and base are multiples of 4, the last, partial dword of an
+// odd-d row as one 2-byte load; 2-byte loads otherwise (an odd ldb, a base at an odd element).  A half base is 2-byte aligned (checked where it is taken).
 //
 // The kernel is a distance PRODUCER for the scans' selection (lsq_adc.hip): it writes records (lsq_adc_key(dist) << idbits | id + 1) to
 // out[slot * L + s], the layout of the scans' MODE 1, and the exhaustive road's segments / segmented sort / gather serve it unchanged.  A candidate id
@@ -60,6 +62,18 @@ __device__ inline u32x4 rr_load16(const uint8_t *p, int valid) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (4 * j < valid) w.v[j] = reinterpret_cast<const uint32_t *>(p)[j];
+    } else if (sizeof(T) == 2) {                                    // half rows below the 16-byte road, and the tail of a half row
+        if (ALIGN >= 4) {                                           // whole dwords; the last, partial dword of an odd-d row as one 2-byte load
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (4 * j + 4 <= valid) w.v[j] = reinterpret_cast<const uint32_t *>(p)[j];
+                else if (4 * j + 2 <= valid) w.v[j] = reinterpret_cast<const uint16_t *>(p)[2 * j];
+            }
+        } else {                                                    // an odd pitch or a base at an odd element: 2-byte loads
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (2 * j < valid) w.v[j >> 1] |= (uint32_t)reinterpret_cast<const uint16_t *>(p)[j] << (16 * (j & 1));
+        }
     } else {                                                        // 8-bit rows at any byte offset, and the tail of an 8-bit row
 #pragma unroll
         for (int j = 0; j < 16; ++j)
@@ -74,6 +88,16 @@ __device__ inline float rr_consume(float acc, uint32_t w, const float *__restric
     if (sizeof(T) == 4) {
         const float e = __uint_as_float(w) - ((!TAIL || k0 < d) ? q[k0] : 0.0f);      // x - q, rounded; the square, rounded; then the add (no FMA)
         return acc + e * e;
+    }
+    if constexpr (sizeof(T) == 2) {                                 // two halves of the dword, widened here (exact): the same chain
+        const lsq_f32x2 h = lsq_widen2<T>(w);
+        const float hv[2] = {h.x, h.y};
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const float e = hv[c] - ((!TAIL || k0 + c < d) ? q[k0 + c] : 0.0f);
+            acc = acc + e * e;
+        }
+        return acc;
     }
     const lsq_f32x4 x = lsq_widen4(w);
     const float xv[4] = {x.x, x.y, x.z, x.w};
@@ -174,6 +198,10 @@ int launch(hipStream_t s, const T *X, int64_t ldb, int64_t n, const float *Q, in
     if ((a & 15) == 0) RR_LAUNCH(16);
     else if ((a & 3) == 0) RR_LAUNCH(4);
     else if constexpr (sizeof(T) == 1) RR_LAUNCH(1);
+    else if constexpr (sizeof(T) == 2) {
+        if ((a & 1) != 0) { lsq_set_error("re-rank: the half-precision base is not 2-byte aligned"); return LSQ_EINVAL; }
+        RR_LAUNCH(2);
+    }
     else { lsq_set_error("re-rank: the f32 base is not 4-byte aligned"); return LSQ_EINVAL; }
 #undef RR_LAUNCH
     LSQ_HIP(hipGetLastError());
@@ -185,7 +213,10 @@ int launch(hipStream_t s, const T *X, int64_t ldb, int64_t n, const float *Q, in
 int lsq_rerank_launch(hipStream_t s, const void *base, int base_u8, int64_t ldb, int64_t n, const float *Q, int64_t ldq, const int *cand, int q0, int nqb,
                       int L, int d, int id_base, uint64_t *out, int idbits, unsigned long long *invalid) {
     if (nqb <= 0 || L <= 0) return LSQ_OK;
-    if (base_u8) return launch(s, static_cast<const uint8_t *>(base), ldb, n, Q, ldq, cand, q0, nqb, L, d, id_base, out, idbits, invalid);
+    const int fmt = lsq_base_format(base_u8);
+    if (fmt == LSQ_BASE_F16) return launch(s, static_cast<const lsq_f16 *>(base), ldb, n, Q, ldq, cand, q0, nqb, L, d, id_base, out, idbits, invalid);
+    if (fmt == LSQ_BASE_BF16) return launch(s, static_cast<const lsq_bf16 *>(base), ldb, n, Q, ldq, cand, q0, nqb, L, d, id_base, out, idbits, invalid);
+    if (fmt) return launch(s, static_cast<const uint8_t *>(base), ldb, n, Q, ldq, cand, q0, nqb, L, d, id_base, out, idbits, invalid);
     return launch(s, static_cast<const float *>(base), ldb, n, Q, ldq, cand, q0, nqb, L, d, id_base, out, idbits, invalid);
 }
 
@@ -249,6 +280,8 @@ int lsq_rerank_check(const char *fn, const void *dists, const void *ids, const v
 extern "C" int lsq_rerank_cpu(float *dists, int *ids, const void *base, int base_u8, const float *queries, const int *cand, int n, int nq, int d,
                               int ldb, int ldq, int L, int nn, int id_base, int nthreads) {
     LSQ_TRY(lsq_rerank_check("lsq_rerank_cpu", dists, ids, base, queries, cand, n, nq, d, ldb, ldq, L, nn, id_base));
+    const int fmt = lsq_base_format(base_u8);
+    if (const char *why = lsq_base_align_refusal(lsq_base_is_half(fmt) ? fmt : 1, base)) { lsq_set_error("lsq_rerank_cpu: %s", why); return LSQ_EINVAL; }
     if (nq == 0) return LSQ_OK;
     int nt = nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency();
     if (nt < 1) nt = 1;
@@ -257,7 +290,13 @@ extern "C" int lsq_rerank_cpu(float *dists, int *ids, const void *base, int base
     pool.reserve((size_t)nt);
     for (int t = 0; t < nt; ++t) {
         const int q0 = (int)((int64_t)nq * t / nt), q1 = (int)((int64_t)nq * (t + 1) / nt);
-        if (base_u8)
+        if (fmt == LSQ_BASE_F16)
+            pool.emplace_back(rerank_queries<lsq_f16>, dists, ids, static_cast<const lsq_f16 *>(base), queries, cand, n, q0, q1, d, (int64_t)ldb,
+                              (int64_t)ldq, L, nn, id_base);
+        else if (fmt == LSQ_BASE_BF16)
+            pool.emplace_back(rerank_queries<lsq_bf16>, dists, ids, static_cast<const lsq_bf16 *>(base), queries, cand, n, q0, q1, d, (int64_t)ldb,
+                              (int64_t)ldq, L, nn, id_base);
+        else if (fmt)
             pool.emplace_back(rerank_queries<uint8_t>, dists, ids, static_cast<const uint8_t *>(base), queries, cand, n, q0, q1, d, (int64_t)ldb,
                               (int64_t)ldq, L, nn, id_base);
         else

@@ -17,11 +17,71 @@
 // One more reader of X keeps a loader of its own: the exact re-rank (lsq_rerank.hip, rr_load16) fetches 16-byte PIECES of a 128-byte line, not quads,
 // and so adds a 16-byte road to the dword / byte rule above.  It shares lsq_widen4 and the packed-until-consumed rule; a change to the alignment
 // rule here has to be made there too.
+//
+// Half-precision rows (the BASE rows of a resident index only: lsq_rerank.hip, lsq_knn.hip, lsq_half.hip) follow the same rule.  lsq_f16 is
+// IEEE binary16, lsq_bf16 the upper 16 bits of a binary32; widening either is exact -- subnormals included, nothing is flushed -- so an instantiation on
+// them returns the bits of the f32 one on the widened matrix.  Two halves of one dword stay packed until consumed: lsq_widen2.
 #pragma once
 
 #include <stdint.h>
 
+#include "lsq_half_check.h"
+
 typedef float lsq_f32x4 __attribute__((ext_vector_type(4)));
+typedef float lsq_f32x2 __attribute__((ext_vector_type(2)));
+
+// the 2-byte element types: the stored bits, (T)0 and an exact (float) -- what a kernel templated on the row type asks of it.  The device converts with
+// v_cvt_f32_f16 / a shift, the host with the integer rules of lsq_half_check.h: the same value either way
+struct lsq_f16 {
+    uint16_t b;
+    lsq_f16() = default;
+    __host__ __device__ explicit lsq_f16(int) : b(0) {}
+    __host__ __device__ explicit operator float() const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return (float)__builtin_bit_cast(_Float16, b);
+#else
+        return lsq_widen_f16(b);
+#endif
+    }
+};
+struct lsq_bf16 {
+    uint16_t b;
+    lsq_bf16() = default;
+    __host__ __device__ explicit lsq_bf16(int) : b(0) {}
+    __host__ __device__ explicit operator float() const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __uint_as_float((uint32_t)b << 16);
+#else
+        return lsq_widen_bf16(b);
+#endif
+    }
+};
+
+// two halves of one dword (component e in bits 16 e ..) -> two floats (exact).  bf16: a shift and a mask; f16: the two converts
+template <typename T> __device__ inline lsq_f32x2 lsq_widen2(uint32_t w);
+template <> __device__ inline lsq_f32x2 lsq_widen2<lsq_bf16>(uint32_t w) {
+    lsq_f32x2 v;
+    v.x = __uint_as_float(w << 16);
+    v.y = __uint_as_float(w & 0xffff0000u);
+    return v;
+}
+template <> __device__ inline lsq_f32x2 lsq_widen2<lsq_f16>(uint32_t w) {
+    lsq_f32x2 v;
+    v.x = (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xffffu));
+    v.y = (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
+    return v;
+}
+
+// f32 -> half, round to nearest even (Identity N; the host's rule: lsq_narrow_f16 / lsq_narrow_bf16).  f16: (_Float16)x is v_cvt_f16_f32, which rounds to
+// nearest even, keeps subnormals and overflows to inf -- NOT the packed convert that rounds toward zero.  bf16: the integer rule in plain C++, whose NaN and
+// subnormal behaviour is the rule's by construction
+template <typename T> __device__ inline uint32_t lsq_narrow1(float x);
+template <> __device__ inline uint32_t lsq_narrow1<lsq_f16>(float x) { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x); }
+template <> __device__ inline uint32_t lsq_narrow1<lsq_bf16>(float x) {
+    const uint32_t u = __float_as_uint(x);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x0040u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
 
 // host: may rows of X (row stride ld elements, ld % 4 == 0 required by the caller) be fetched four components per load?
 static inline bool lsq_x_vec_ok(const float *X) { return ((uintptr_t)X & 15) == 0; }

@@ -95,6 +95,68 @@ class _Side:
 
 _HOST, _DEVICE = _Side(False), _Side(True)
 
+# half-precision base rows (Engine.index(..., base_format=), Index.narrow_base): name -> (the library's format, the dtype a host array of such rows has --
+# bfloat16 travels as the uint16 BITS, numpy has no such type --, the dtype of a device tensor)
+_HALF = {"f16": (_lib.BASE_F16, np.float16, "float16"), "bf16": (_lib.BASE_BF16, np.uint16, "bfloat16")}
+_HALF_BY_CODE = {v[0]: (k,) + v[1:] for k, v in _HALF.items()}
+_FORMAT_NAMES = {_lib.BASE_F32: "float32", _lib.BASE_U8: "uint8", _lib.BASE_F16: "float16", _lib.BASE_BF16: "bfloat16"}
+
+
+def base_format_code(fmt):
+    """None -> None, "f16" / "bf16" -> LSQ_BASE_F16 / LSQ_BASE_BF16; anything else is a ValueError (raised before any library call)"""
+    if fmt is None:
+        return None
+    if not isinstance(fmt, str) or fmt not in _HALF:
+        raise ValueError("base_format must be None, \"f16\" or \"bf16\", got %r" % (fmt,))
+    return _HALF[fmt][0]
+
+
+def _row_view(a, dtype):
+    """a 2-d host array as rows with unit column stride and a pitch of whole elements, read in place where it already is that"""
+    a = np.asarray(a, dtype=dtype)
+    if a.ndim != 2 or a.strides[1] != a.itemsize or a.strides[0] % a.itemsize or (a.shape[0] > 1 and a.strides[0] < a.shape[1] * a.itemsize):
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def _host_half_rows(L, check, base, code):
+    """host rows for a half-precision base of format `code`: rows already in the format are taken as they are (float16 for "f16", the uint16 bits for
+    "bf16"), float rows are narrowed by lsq_narrow_rows_cpu (round to nearest even); any other dtype is a TypeError, raised before any library call"""
+    name, np_dtype, _ = _HALF_BY_CODE[code]
+    dt = _dtname(base)
+    if dt == np.dtype(np_dtype).name:
+        return _row_view(base, np_dtype)
+    if dt == "int8":
+        raise TypeError("int8 data is not accepted: 8-bit base sets are unsigned (uint8); view or convert the array explicitly")
+    if not (dt.startswith("float") or dt == ""):
+        raise TypeError("base rows for base_format=%r must be float rows to narrow or %s rows%s, got %s" % (
+            name, np.dtype(np_dtype).name, " holding the bfloat16 bits" if code == _lib.BASE_BF16 else "", dt))
+    X = _row_view(base, _F32)
+    n, d = X.shape
+    out = np.zeros((n, d), dtype=np.uint16)
+    check(L.lsq_narrow_rows_cpu(out.ctypes.data, X.ctypes.data, n, d, int(_HOST.pitch(X)), d, code, 0))
+    return out.view(np_dtype)
+
+
+def _device_half_rows(base, code, name="base"):
+    """a device tensor of base rows under base_format `code` (None: the dtype alone decides) -> (tensor, its format, the format to narrow to afterwards or
+    None).  float16 / bfloat16 tensors are borrowed as they are and a contradicting base_format is a TypeError; a float32 tensor with a format is taken as
+    float32 and narrowed on the device once the index exists"""
+    if not getattr(base, "is_cuda", False):
+        raise TypeError("%s must be a device tensor, got %s" % (name, "a CPU tensor" if hasattr(base, "is_cuda") else type(base).__name__))
+    dt = _dtname(base)
+    have = {"float16": _lib.BASE_F16, "bfloat16": _lib.BASE_BF16}.get(dt)
+    if have is not None:
+        if code is not None and code != have:
+            raise TypeError("%s is a %s tensor, which contradicts base_format=%r" % (name, dt, _HALF_BY_CODE[code][0]))
+        if base.dim() != 2 or base.stride(1) != 1:
+            raise ValueError("%s must be 2-d rows with unit column stride, got shape %s strides %s" % (name, tuple(base.shape), base.stride()))
+        return base, have, None
+    if code is not None and dt != "float32":
+        raise TypeError("%s must be float32 (narrowed on the device), float16 or bfloat16 for base_format=%r, got %s" % (name, _HALF_BY_CODE[code][0], dt))
+    base, u8 = _DEVICE.take_x(base, name, rows=True)
+    return base, _lib.BASE_U8 if u8 else _lib.BASE_F32, code
+
 
 def _fits(shape, want):
     return len(shape) == len(want) and all(w is None or w == s for s, w in zip(shape, want))
@@ -330,13 +392,13 @@ class Engine:
         return self._knn_exact(_HOST, Xb, Xq, k)
 
     def knn_exact_dev(self, dXb, dXq, k):
-        """The same on device-resident torch tensors (n, d) / (nq, d), f32 -- or a uint8 base with uint8 or f32 queries (a temporary Index that borrows
-        the base); row views with unit column stride are read in place.
+        """The same on device-resident torch tensors (n, d) / (nq, d), f32 -- or a uint8, float16 or bfloat16 base with uint8 or f32 queries (a temporary
+        Index that borrows the base: the bits of the call on the widened base); row views with unit column stride are read in place.
         -> (dists (nq,k) f32, ids (nq,k) 0-based) tensors; the ids tensor is int32 holding the uint32 bits   [lsq_knn_exact_dev / lsq_index_knn]"""
         return self._knn_exact(_DEVICE, dXb, dXq, k)
 
     def _knn_exact(self, side, Xb, Xq, k):
-        u8 = _dtname(Xb) == "uint8"
+        u8 = _dtname(Xb) == "uint8" or (side.dev and _dtname(Xb) in ("float16", "bfloat16"))      # never widened: the temporary base-only Index
         if not u8:
             Xb, Xq = side.take(Xb, _F32, "base", rows=True), side.take(Xq, _F32, "queries", rows=True)
         _shapes(("base", Xb, (None, None)), ("queries", Xq, (None, Xb.shape[-1])))
@@ -356,27 +418,32 @@ class Engine:
         return dists, ids
 
     # -- (1d) two-stage search on a resident index ------------------------------------------
-    def index(self, codes, K, dbnorms, m, base=None, h=H, d=None):
+    def index(self, codes, K, dbnorms, m, base=None, h=H, d=None, base_format=None):
         """An Index of HOST arrays, copied once and owned by the index: codes (n,m) uint8 0-based, K (m*h,d), dbnorms (n,), base (n,ldb) float32 or
         uint8 (the un-widened rows of a .bvecs set) or None (scan only).  codes=None: a base-only index (re-rank only), which reads the first d
-        components of a base row (default: all of them)   [lsq_index_create]"""
-        return Index(self, codes, K, dbnorms, m, base, h, d, on_device=False)
+        components of a base row (default: all of them).  base_format="f16" / "bf16": the index keeps HALF-PRECISION base rows (2 d bytes per row): float
+        rows are narrowed on the host, round to nearest even (narrow_rows); a float16 array ("f16") or a uint16 array of bfloat16 bits ("bf16") is taken
+        as it is.  Every call that reads base rows then returns what the index over the widened rows returns.  base_format=None: as ever -- a float16 array
+        is widened to float32   [lsq_index_create]"""
+        return Index(self, codes, K, dbnorms, m, base, h, d, on_device=False, base_format=base_format)
 
-    def index_dev(self, dcodes, dK, dnorms, m, base=None, h=H, d=None):
+    def index_dev(self, dcodes, dK, dnorms, m, base=None, h=H, d=None, base_format=None):
         """The same on device-resident torch tensors, BORROWED: the index keeps references to them; searches take and return tensors.  base: a 2-d
-        tensor or a view of one with unit column stride, at any byte offset."""
-        return Index(self, dcodes, dK, dnorms, m, base, h, d, on_device=True)
+        tensor or a view of one with unit column stride, at any byte offset.  A torch.float16 or torch.bfloat16 base is borrowed as it is (the dtype
+        decides; a contradicting base_format is a TypeError); a float32 base with base_format="f16" / "bf16" is narrowed on the device into rows the index
+        owns (Index.narrow_base) and is not kept."""
+        return Index(self, dcodes, dK, dnorms, m, base, h, d, on_device=True, base_format=base_format)
 
-    def index_packed(self, codes, K, norm_codes, cbnorms, m, base=None, h=H):
+    def index_packed(self, codes, K, norm_codes, cbnorms, m, base=None, h=H, base_format=None):
         """An Index that keeps the norm BYTE: codes (n,m) uint8 0-based, norm_codes (n,) uint8 0-based indexes into cbnorms (<= 256,) float32 -- what
         quantize_norms computes -- packed into rows of m + 1 bytes that the index owns.  Every search returns the bits of Engine.index(codes, K,
         cbnorms[norm_codes], m, base)   [lsq_index_create_packed]"""
-        return Index(self, codes, K, None, m, base, h, None, on_device=False, packed=(norm_codes, cbnorms))
+        return Index(self, codes, K, None, m, base, h, None, on_device=False, packed=(norm_codes, cbnorms), base_format=base_format)
 
-    def index_packed_dev(self, dcodes, dK, dnorm_codes, dcbnorms, m, base=None, h=H):
+    def index_packed_dev(self, dcodes, dK, dnorm_codes, dcbnorms, m, base=None, h=H, base_format=None):
         """The same from device tensors (quantize_norms_dev's idx as it is).  dcodes, dnorm_codes and dcbnorms are read once, before this returns: they
         may be freed or overwritten afterwards; dK and base are borrowed as in index_dev."""
-        return Index(self, dcodes, dK, None, m, base, h, None, on_device=True, packed=(dnorm_codes, dcbnorms))
+        return Index(self, dcodes, dK, None, m, base, h, None, on_device=True, packed=(dnorm_codes, dcbnorms), base_format=base_format)
 
     # -- (1e) the beam-search encoder on resident codebooks ----------------------------------
     def encoder(self, K, m, chunk=0, h=H):
@@ -698,15 +765,24 @@ class Index(_Handle):
 
     _destroy = "lsq_index_destroy"
 
-    def __init__(self, engine, codes, K, dbnorms, m, base, h, d, on_device, packed=None):
+    def __init__(self, engine, codes, K, dbnorms, m, base, h, d, on_device, packed=None, base_format=None):
         side = self._bind(engine, on_device)
+        code = base_format_code(base_format)           # an unknown format is refused here, before anything is taken
         codes, K, dbnorms = side.maybe(codes, _U8, "codes"), side.maybe(K, _F32, "K"), side.maybe(dbnorms, _F32, "dbnorms")
-        u8 = False
-        if base is not None:
+        u8, narrow_to = False, None                      # u8: what the description's base_u8 field carries -- the FORMAT of the base rows
+        if base is None:
+            if code is not None:
+                raise ValueError("base_format=%r needs base rows" % (base_format,))
+        elif side.dev:
+            base, u8, narrow_to = _device_half_rows(base, code)
+        elif code is not None:
+            base, u8 = _host_half_rows(self._L, engine._check, base, code), code
+        else:
             base, u8 = side.take_x(base, "base", rows=True)
-        self._u8, self._has_codes, self._has_base, self._packed = u8, codes is not None, base is not None, packed is not None
+        self._u8, self._fmt, self._has_codes, self._has_base, self._packed = int(u8) == _lib.BASE_U8, int(u8), codes is not None, base is not None, packed is not None
         if packed is not None:
-            return self._init_packed(side, codes, K, packed, m, base, u8, h)
+            self._init_packed(side, codes, K, packed, m, base, u8, h)
+            return self._narrow_after(narrow_to)
         if codes is None and base is None:
             raise ValueError("an index needs codes, base rows or both")
         n = int(codes.shape[0] if codes is not None else base.shape[0])
@@ -723,6 +799,18 @@ class Index(_Handle):
         self._keep = (codes, K, dbnorms, base)      # borrowed device tensors stay alive with the index
         self.n, self.d, self.m = n, d, int(m)
         self._create("lsq_index_create", desc)
+        self._narrow_after(narrow_to)
+
+    def _narrow_after(self, code):
+        """a device index made from a float32 tensor with a base_format: narrowed now, the borrowed float32 rows let go"""
+        if code is None:
+            return
+        try:
+            self.narrow_base(_HALF_BY_CODE[code][0])
+        except Exception:
+            self.close()
+            raise
+        self._keep = tuple(None if i == len(self._keep) - 1 else a for i, a in enumerate(self._keep))      # base is the last of what is kept
 
     def _init_packed(self, side, codes, K, packed, m, base, u8, h):
         """the packed form (Engine.index_packed): the norm bytes and their table instead of dbnorms; checked here, refused before any library call"""
@@ -774,7 +862,7 @@ class Index(_Handle):
         return dists, ids
 
     def knn(self, Q, k, id_base=0):
-        """Exact k-NN over the resident base rows (f32, or uint8 never widened): the ground truth of a recall figure.  Q (nq,>=d) float32 or uint8 rows
+        """Exact k-NN over the resident base rows (f32; uint8, float16 and bfloat16 rows are widened in registers, never in memory): the ground truth of a recall figure.  Q (nq,>=d) float32 or uint8 rows
         with unit column stride, any row pitch and byte offset (numpy on an Engine.index, torch on an Engine.index_dev); the first d columns are read.
         -> dists (nq,k) float32 ascending with lsq_knn_exact's bits, ids (nq,k) int32 in id_base; ties by smaller id   [lsq_index_knn]"""
         side = self._side
@@ -920,7 +1008,8 @@ class Index(_Handle):
         """Append rows: they become rows n .. n + count - 1 (0-based), and every call then answers as on an index built over the concatenation, with the
         concatenated lists and a filter that allows the new rows too.  What the index holds is what must be given: codes (count,m) uint8 0-based with
         dbnorms (count,) float32 -- a packed index: norm_codes (count,) uint8 instead --, base (count,>=d) rows of the index's own type with unit column
-        stride and any pitch, assign (count,) int32 0-based lists once lists are set.  All numpy arrays or all torch device tensors, whichever way the
+        stride and any pitch (a half-precision index: host float rows are narrowed, float16 rows / uint16 bfloat16 bits are taken as they are; device
+        tensors must have the index's dtype), assign (count,) int32 0-based lists once lists are set.  All numpy arrays or all torch device tensors, whichever way the
         index was made; they are read before the call returns.  A device index that borrowed its arrays copies them once, at the first add or reserve
         [lsq_index_add]"""
         given = [(nm, a) for nm, a in (("codes", codes), ("dbnorms", dbnorms), ("norm_codes", norm_codes), ("base", base), ("assign", assign)) if a is not None]
@@ -933,7 +1022,15 @@ class Index(_Handle):
         if not side.dev and norm_codes is not None and np.asarray(norm_codes).dtype != _U8:      # a norm byte is an index: never narrowed silently
             raise TypeError("norm_codes must be uint8, got %s" % np.asarray(norm_codes).dtype)
         codes, dbnorms, nc, lor = side.maybe(codes, _U8, "codes"), side.maybe(dbnorms, _F32, "dbnorms"), side.maybe(norm_codes, _U8, "norm_codes"), side.maybe(assign, _I32, "assign")
-        if base is not None:
+        fmt = self._format()
+        if base is not None and fmt in _HALF_BY_CODE:      # a half index: host float rows are narrowed, rows already in the format are taken as they are
+            if side.dev:
+                base, have, _ = _device_half_rows(base, None)
+                if have != fmt:
+                    raise TypeError("base rows must have the index's own type (%s), got %s" % (_FORMAT_NAMES[fmt], _dtname(base)))
+            else:
+                base = _host_half_rows(self._L, self._eng._check, base, fmt)
+        elif base is not None:
             u8 = _dtname(base) == "uint8"
             if u8 != self._u8:
                 raise TypeError("base rows must have the index's own type (%s), got %s" % ("uint8" if self._u8 else "float32", _dtname(base)))
@@ -1045,6 +1142,44 @@ class Index(_Handle):
         """the last reconstruct / search_rows call: rows decoded, invalid ids, map_rebuilt (the row -> list map was built by it), map_rebuilds and calls
         (since creation), road (_lib.RECON_ROAD_*), map_ms / decode_ms (with profile=True)"""
         return self._info("lsq_index_get_recon_info", _lib.IndexReconInfo)
+
+    def _format(self):
+        """the format of the base rows (_lib.BASE_*)"""
+        return getattr(self, "_fmt", _lib.BASE_U8 if self._u8 else _lib.BASE_F32)
+
+    def narrow_base(self, fmt):
+        """Convert the index's resident FLOAT32 base rows, on the device, into half-precision rows the index owns ("f16" / "bf16", round to nearest
+        even; dense rows).  Afterwards the index is the index created over the narrowed rows: 2 d bytes per row instead of 4 d.  A borrowed float32
+        tensor is left untouched and no longer used.  Both copies exist until the call returns.  base_info() reports what narrowing cost: values that
+        became inf or zero   [lsq_index_narrow_base]"""
+        code = base_format_code(fmt)
+        if code is None:
+            raise ValueError("narrow_base needs a format: \"f16\" or \"bf16\"")
+        self._eng._call(self._side, "lsq_index_narrow_base", code, h=self._h)
+        self._fmt, self._u8 = code, False
+
+    def base_info(self):
+        """format (_lib.BASE_*), elem_bytes, ldb, owned, resident_bytes of the base rows (all zero without any); to_inf / to_zero / nans and narrow_ms
+        (with profile=True) of the last narrow_base"""
+        return self._info("lsq_index_get_base_info", _lib.IndexBaseInfo)
+
+    def base_rows(self, start=0, count=None, out=None):
+        """The STORED base rows start .. start + count - 1 (count=None: to the last row), widened to float32 whatever their format -- reconstruct()
+        returns what the codes stand for, this what the re-rank reads.  A filter changes nothing.  out: (count, >=d) float32 rows to write into (numpy
+        on an Engine.index, a device tensor on an Engine.index_dev)
+        -> (count, d) float32   [lsq_index_get_base]"""
+        side, p = self._side, self._side.ptr
+        count = self.n - int(start) if count is None else int(count)
+        if out is None:
+            out = side.new((max(count, 0), self.d), _F32, self._eng._device() if side.dev else None, zero=True)
+        elif side.dev:
+            out = side.take(out, _F32, "out", rows=True)
+        elif not (isinstance(out, np.ndarray) and out.dtype == _F32 and out.ndim == 2 and out.strides[1] == 4 and out.strides[0] % 4 == 0):
+            raise ValueError("out must be a 2-d float32 numpy array of rows with unit column stride")
+        _shapes(("out", out, (max(count, 0), max(self.d, out.shape[1]))))
+        ldo = int(side.pitch(out)) if out.shape[0] > 1 else int(out.shape[1])
+        self._eng._call(side, "lsq_index_get_base", p(out) if count > 0 else None, int(start), count, ldo, int(self._dev), h=self._h)
+        return out
 
 
 # -- the beam-search encoder (made by Engine.encoder / Engine.encoder_dev) ------------------------

@@ -330,16 +330,38 @@ def rerank(X_base, X_query, ids, k, *, engine=None, nthreads=0):
     return dists.T, out.T
 
 
-def linscan_lsq_rerank(B, X, C, dbnorms, R, X_base, shortlist, k, *, engine=None, nthreads=0):
+def narrow_rows(X, fmt, *, nthreads=0):
+    """Rows of float32 narrowed to half precision on the host (lsq_narrow_rows_cpu), round to nearest even: fmt "f16" -> a float16 array (the bits of
+    X.astype(np.float16)), "bf16" -> a uint16 array holding the upper 16 bits of the rounded float32 (numpy has no bfloat16).  X (n, d) rows with unit
+    column stride (a row view is read in place).  What Engine.index(base=..., base_format=fmt) uploads."""
+    from . import _lib
+    from .engine import base_format_code
+    code = base_format_code(fmt)
+    if code is None:
+        raise ValueError("narrow_rows needs a format: \"f16\" or \"bf16\"")
+    X = np.asarray(X, dtype=np.float32)
+    if X.ndim != 2 or X.strides[1] != 4 or X.strides[0] % 4 or (X.shape[0] > 1 and X.strides[0] < X.shape[1] * 4):
+        X = np.ascontiguousarray(X)
+    n, d = X.shape
+    out = np.zeros((n, d), dtype=np.uint16)
+    lds = int(X.strides[0] // 4) if n > 1 else d
+    _lib.check(_lib.load().lsq_narrow_rows_cpu(out.ctypes.data if n else None, X.ctypes.data if n else None, n, d, max(lds, d), d, code, int(nthreads)))
+    return out.view(np.float16) if code == _lib.BASE_F16 else out
+
+
+def linscan_lsq_rerank(B, X, C, dbnorms, R, X_base, shortlist, k, *, engine=None, nthreads=0, base_format=None):
     """linscan_lsq for `shortlist` neighbours, then rerank to k: the scan reads R'X, the re-rank X against X_base (both in the base set's own frame).
-    -> dists (k, nq) exact float32, ids (k, nq) int32 1-based.  engine=<Engine>: one resident index does both stages on the device (lsq_index_search)."""
+    -> dists (k, nq) exact float32, ids (k, nq) int32 1-based.  engine=<Engine>: one resident index does both stages on the device (lsq_index_search).
+    base_format="f16" / "bf16" (with an engine): the index keeps its base rows in half precision (Engine.index's base_format)."""
     if engine is None:
+        if base_format is not None:
+            raise ValueError("base_format needs an engine: the host road keeps no resident base")
         _, res = linscan_lsq(B, X, C, dbnorms, R, shortlist, nthreads=nthreads)
         return rerank(X_base, X, res, k, nthreads=nthreads)
     codes = np.ascontiguousarray(np.asarray(B, dtype=np.uint8).T)
     RX = np.ascontiguousarray((np.asarray(R, dtype=np.float32).T @ np.asarray(X, dtype=np.float32)).T)
     m, _, h = _dims(C)
-    with engine.index(codes, _K_of(C), np.ascontiguousarray(dbnorms, dtype=np.float32), m, base=_base_rows(X_base), h=h) as ix:
+    with engine.index(codes, _K_of(C), np.ascontiguousarray(dbnorms, dtype=np.float32), m, base=_base_rows(X_base), h=h, base_format=base_format) as ix:
         dists, ids = ix.search(RX, k, shortlist=shortlist, Q_exact=_X_of(X))
     return dists.T, ids.T
 

@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--delete FRACTION] [--radius R] [--reconstruct] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L [--base-format f16|bf16]] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--delete FRACTION] [--radius R] [--reconstruct] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -14,6 +14,8 @@ uint8 (lsq_encode_icm_u8: d bytes per vector over the bus and in HBM).  The grou
 --init beam:L: the base set's initial codes come from the beam-search encoder (encode_beam, width L, codebooks visited by descending energy: beam_order)
 instead of randinit (demos/demo_lsq_gpu.jl:46); the rest of the flow is unchanged.  Default: randinit, as the reference.
 
+--base-format f16|bf16 (with --rerank L): the same two-stage search once more over half-precision base rows (Engine.index(..., base_format=)), its recall
+curve printed beside the float32 one: what the format costs.
 --rerank L: after the ADC scan, the two-stage search on a resident index (Engine.index: the codes, norms, codebooks and the base rows uploaded once):
 the scan's L nearest re-ordered by exact distance to the stored vectors -- f32 rows, or the un-widened 8-bit rows with --bvecs -- and the recall curve of the
 re-ranked lists printed next to the ADC one.  The reference has no such stage: its recall is that of the ADC order.
@@ -210,8 +212,20 @@ def residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter
     return lsq.eval_recall(gt, np.ascontiguousarray(ridx.T).astype(np.uint32), knn), t_build, rep["obj"], grec
 
 
+BASE_FORMAT = None                               # --base-format f16 | bf16 (with --rerank): the recall curve of half-precision base rows beside the f32 one
+
+
 def main():
+    global BASE_FORMAT
     argv = sys.argv[1:]
+    if "--base-format" in argv:
+        at = argv.index("--base-format")
+        BASE_FORMAT = argv[at + 1]
+        del argv[at:at + 2]
+        if BASE_FORMAT not in ("f16", "bf16"):
+            raise SystemExit("--base-format takes f16 or bf16, got %r" % BASE_FORMAT)
+        if "--rerank" not in argv:
+            raise SystemExit("--base-format needs --rerank L")
     shortlist = 0
     if "--rerank" in argv:
         at = argv.index("--rerank")
@@ -337,11 +351,17 @@ def main():
             rd, ridx = lsq.linscan_lsq_rerank((B_base - 1).astype(np.uint8), x_query, C, db_norms, np.eye(d, dtype=np.float32), x_base, L, keep, engine=eng)
         t_two = time.perf_counter() - t0
         rrec = lsq.eval_recall(gt, ridx.astype(np.uint32), keep)
+        hrec = None
+        if BASE_FORMAT:                                                      # --base-format: the same search over half-precision base rows (2 d bytes per row)
+            with lsq.Engine(0) as eng:
+                _, hidx = lsq.linscan_lsq_rerank((B_base - 1).astype(np.uint8), x_query, C, db_norms, np.eye(d, dtype=np.float32),
+                                                 np.asarray(x_base, dtype=np.float32), L, keep, engine=eng, base_format=BASE_FORMAT)
+            hrec = lsq.eval_recall(gt, hidx.astype(np.uint32), keep)
         print("Two-stage search (shortlist %d, %s rows resident): %.3f s incl. the upload of the index" % (L, x_base.dtype, t_two))
-        print("     r@   ADC      re-ranked")
+        print("     r@   ADC      re-ranked" + ("   re-ranked on %s rows" % BASE_FORMAT if BASE_FORMAT else ""))
         for i in (1, 2, 5, 10, 20, 50, 100, 200, 500, 1000):
             if i <= keep:
-                print("%7d   %.4f   %.4f" % (i, rec[i - 1], rrec[i - 1]))
+                print("%7d   %.4f   %.4f" % (i, rec[i - 1], rrec[i - 1]) + ("      %.4f" % hrec[i - 1] if BASE_FORMAT else ""))
         print("%s: recall@1 after re-ranking %d = %.4f (ADC: %.4f)" % (name, L, rrec[0], rec[0]))
     if ivf:
         nlist, nprobe = min(ivf[0], x_base.shape[1]), ivf[1]
