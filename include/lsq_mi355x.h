@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 2500
+#define LSQ_VERSION 2600
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -941,6 +941,91 @@ LSQ_API int lsq_narrow_rows_cpu(void *dst, const float *src, int64_t n, int d, i
 LSQ_API int lsq_index_narrow_base(lsq_index *ix, int format);
 LSQ_API int lsq_index_get_base(lsq_index *ix, float *out, int64_t start, int64_t count, int64_t ldo, int on_device);
 LSQ_API int lsq_index_get_base_info(lsq_index *ix, lsq_index_base_info *out);
+
+/* ---- (3p) snapshots: an index saved to a file, loaded from it, exported as arrays, digested (csrc/lsq_snapshot.hip, csrc/lsq_snapshot_check.h; since v2600) ----
+ * THE REFERENCE HAS NO COUNTERPART for any of the nine symbols below: it keeps no resident index, and its demos write codes with HDF5 by hand.
+ * THE LOGICAL STATE of an index is the set of arrays a caller would pass to build it fresh -- never capacity, scratch, statistics, a held range result or
+ * ownership.  Its canonical form, section by section, in this order (kind = LSQ_SNAP_*):
+ *   CODEBOOKS    f32 [m 256][d]                       with codes          CODES      u8 [n][m]                         with codes
+ *   DBNORMS      f32 [n]                              plain index         NORM_CODES u8 [n]   and  CBNORMS f32 [ncb]   packed index
+ *   BASE         [n][d] in the stored format, dense   with base rows      CENTROIDS  f32 [nlist][d]  and  LIST_OF_ROW i32 [n]   with lists
+ *   FILTER_BITS  u32 [ceil(n/32)], bits at or past n zero                 with an active filter
+ * and the scalars n, d, m, h, packed, ncb, base format, nlist, filter active, the filter's FORCE flag (a forced road survives lsq_index_remove: it is
+ * state) and the allowed count.  Bytes are kept verbatim: NaN payloads survive.
+ * THE FILE (format version 1, everything little-endian) is a function of the logical state alone -- no time, host name or pointer:
+ *   header, 128 bytes:  0 magic "LSQSNAP\0" | 8 u32 version = 1 | 12 u32 endianness marker 0x01020304 | 16 u32 header bytes = 128 | 20 u32 sections |
+ *                       24 i64 n | 32 i32 d | 36 i32 m | 40 i32 h | 44 i32 packed | 48 i32 ncb | 52 i32 base format | 56 i32 nlist |
+ *                       60 i32 flags (1 codes, 2 base rows, 4 filter active) | 64 i32 FORCE flag (0, LSQ_FILTER_FORCE_DENSE, _COMPACT) | 68 i32 zero |
+ *                       72 i64 allowed | 80 i64 file bytes | 88 .. 127 zero
+ *   table:              per section { u32 kind, u32 element bytes, u64 offset, u64 bytes, u64 digest }, then the u64 digest of every byte before it
+ *   sections:           in the order above, the first at the next multiple of 64 after the table, each at the next multiple of 64 after the one before;
+ *                       the padding is zero and is checked; the file ends with the last section's last byte.
+ * THE DIGEST of a byte range that starts at word `first_word` of its section (a word = 4 bytes, little-endian, the last one zero-padded):
+ *     SUM over the range's words w_i, i = first_word, first_word + 1, ...  of  (uint64) fmix32(w_i ^ (uint32)(i * 0x9E3779B1)) * (uint64)(uint32)(2 i + 1)
+ *     + bytes * 0x9E3779B97F4A7C15                                                     all mod 2^64
+ *     fmix32(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16        (murmur3's finaliser, a bijection)
+ * A section's digest is that of all its bytes from word 0.  The digests of ranges that partition a section at multiples of 4 bytes ADD UP to it: blocks,
+ * waves and staging chunks combine by addition, with no atomics and no ordering.  lsq_snapshot_digest_cpu, the kernel snap_digest_kernel and the numpy
+ * statement in tests/snapshot_check.py agree on it bit for bit.
+ *   IDENTITY S.  lsq_index_load(lsq_index_save(ix)) answers every call bit for bit like ix -- searches on every road, re-rank, k-NN, range search, decode,
+ *   base rows, filter info except `road`, and every later lsq_index_add / _remove / _compact / _set_lists -- and like an index built from lsq_index_export.
+ *   IDENTITY F.  The bytes lsq_index_save writes are those lsq_snapshot_write_cpu writes over lsq_index_export's arrays: two indexes that Identities G / R /
+ *   C declare equal save byte-identical files, and lsq_index_digest equals the file's table.
+ *   lsq_index_save          the file at `path` (flags: 0).  Sections move through two pinned staging chunks (option "snapshot_chunk": their bytes, rounded
+ *                           down to a multiple of 64; 0 = the default 8 MiB): the copy of chunk k + 1 runs under the write of chunk k, the host never holds
+ *                           more.  What is canonical in HBM is read where it lies; packed rows, a pitched base, list_of_row are derived on the device first.
+ *                           Digests come from the device.  A borrowing index is saved from the caller's arrays; nothing is adopted, nothing changes.  The
+ *                           bytes go to a temporary file beside `path` that is renamed on success: a failed save leaves a file at `path` as it was.
+ *   lsq_index_load          header and table are validated on the host before anything is allocated; the sections stream into device arrays the new index
+ *                           OWNS; it is built by lsq_index_create / _create_packed / _set_lists / _set_filter on those arrays (their device-side range checks
+ *                           apply: LSQ_EINVAL), and what arrived in HBM is digested there and compared with the table (LSQ_EFORMAT).  On any error *out is
+ *                           NULL and nothing is leaked.
+ *   lsq_index_export        fills the arrays of `out` whose pointers are not NULL (host memory, or device memory with on_device = 1) and every scalar.  An
+ *                           array the index does not have, requested anyway: LSQ_EINVAL before anything is written.
+ *   lsq_index_digest        scalars, section table (with the offsets a file would have) and digests of the logical state; no file involved.
+ *   lsq_index_get_snapshot_info   the last save of / the load that made this index.
+ *   lsq_snapshot_write_cpu / _read_cpu / _inspect_cpu / _digest_cpu   host only, no context: the engine-less road.  write: has codes <=> codes != NULL, has
+ *                           base rows <=> base != NULL, lists <=> nlist > 0, filter <=> filter_active (bits past n are written as zero, `allowed` is
+ *                           recounted).  read: fills the non-NULL arrays (sized from inspect) after verifying every digest.  inspect: header and table, and
+ *                           with verify != 0 every digest and the padding.
+ * LSQ_EIO: open, read, write or rename failed, or a write was short.  LSQ_EFORMAT: not a snapshot, truncated, inconsistent, a digest mismatch, or a newer
+ * format version.  lsq_last_error names the section and what was wrong. */
+enum { LSQ_EIO = -6, LSQ_EFORMAT = -7 };
+enum { LSQ_SNAP_CODEBOOKS = 1, LSQ_SNAP_CODES = 2, LSQ_SNAP_DBNORMS = 3, LSQ_SNAP_NORM_CODES = 4, LSQ_SNAP_CBNORMS = 5, LSQ_SNAP_BASE = 6,
+       LSQ_SNAP_CENTROIDS = 7, LSQ_SNAP_LIST_OF_ROW = 8, LSQ_SNAP_FILTER_BITS = 9, LSQ_SNAP_MAX_SECTIONS = 9 };
+#define LSQ_SNAPSHOT_FORMAT 1
+typedef struct lsq_snapshot_arrays {     /* the logical state as plain arrays; a NULL pointer: not wanted / not there */
+    int64_t n;
+    int d, m, h, packed, ncb, base_format, nlist, filter_active, filter_force, reserved;
+    int64_t allowed;
+    void *codebooks, *codes, *dbnorms, *norm_codes, *cbnorms, *base, *centroids, *list_of_row, *filter_bits;
+} lsq_snapshot_arrays;
+typedef struct lsq_snapshot_section {
+    int64_t kind, elem_bytes, offset, bytes;
+    uint64_t digest;
+} lsq_snapshot_section;
+typedef struct lsq_snapshot_info {
+    int64_t format, n, d, m, h, packed, ncb, base_format, nlist, has_codes, has_base, filter_active, filter_force, allowed;
+    int64_t file_bytes, nsections;
+    uint64_t header_digest;
+    lsq_snapshot_section sections[9];    /* LSQ_SNAP_MAX_SECTIONS of them; the first nsections are filled */
+} lsq_snapshot_info;
+typedef struct lsq_snapshot_io_info {    /* fields are only ever appended */
+    int64_t op;                  /* 0 none, 1 the last lsq_index_save, 2 the lsq_index_load that made the index */
+    int64_t bytes, chunks, chunk_bytes, sections;
+    int64_t host_staging_bytes;  /* pinned host memory the call held: two chunks */
+    double derive_ms, digest_ms, copy_ms;        /* with option "profile" = 1: device time deriving sections, digesting, copying between HBM and the chunks */
+    double file_ms, total_ms;    /* host clock: fwrite / fread; the whole call */
+} lsq_snapshot_io_info;
+LSQ_API int lsq_index_save(lsq_index *ix, const char *path, int flags);
+LSQ_API int lsq_index_load(lsq_index **out, lsq_ctx *ctx, const char *path, int flags);
+LSQ_API int lsq_index_export(lsq_index *ix, lsq_snapshot_arrays *out, int on_device);
+LSQ_API int lsq_index_digest(lsq_index *ix, lsq_snapshot_info *out);
+LSQ_API int lsq_index_get_snapshot_info(lsq_index *ix, lsq_snapshot_io_info *out);
+LSQ_API int lsq_snapshot_write_cpu(const char *path, const lsq_snapshot_arrays *arrays);
+LSQ_API int lsq_snapshot_read_cpu(const char *path, lsq_snapshot_arrays *out);
+LSQ_API int lsq_snapshot_inspect_cpu(const char *path, lsq_snapshot_info *out, int verify);
+LSQ_API int lsq_snapshot_digest_cpu(const void *data, int64_t bytes, int64_t first_word, uint64_t *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

@@ -17,6 +17,7 @@ from .reference_api import (  # noqa: F401
     fvecs_read, ivecs_read, bvecs_read, update_codebooks, train_lsq, train_lsq_dev,
     update_codebooks_spgl1, update_codebooks_spgl1_threshold, train_lsq_sparse, knn_exact, rerank, linscan_lsq_rerank, encode_beam, beam_order,
     ivf_assign, train_coarse, ivf_residual_norms, linscan_lsq_bytes, train_coarse_dev, build_ivf_residual_index, range_search_lsq, narrow_rows,
+    snapshot_info, snapshot_write, snapshot_read, snapshot_digest,
 )
 from .initializers import (  # noqa: F401
     train_pq, quantize_pq, train_opq, quantize_opq, train_chainq, train_chainq_dev, encoding_viterbi, update_codebooks_chain, update_codebooks_generic,
@@ -32,4 +33,5 @@ __all__ = [
     "update_codebooks_spgl1", "update_codebooks_spgl1_threshold", "train_lsq_sparse", "knn_exact",
     "kmeans_dev", "train_pq_dev", "train_opq_dev", "codebooks_from_padded", "Index", "rerank", "linscan_lsq_rerank", "Encoder", "encode_beam", "beam_order",
     "ivf_assign", "train_coarse", "ivf_residual_norms", "linscan_lsq_bytes", "Partition", "train_coarse_dev", "build_ivf_residual_index", "range_search_lsq", "reconstruct_cpu", "narrow_rows",
+    "snapshot_info", "snapshot_write", "snapshot_read", "snapshot_digest",
 ]

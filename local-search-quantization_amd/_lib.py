@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("LSQ_LIB_PATH") or os.path.join(_HERE, "liblsq_mi355x.
 TUNING_LIB_PATH = os.environ.get("LSQ_TUNING_LIB_PATH") or os.path.join(_HERE, "liblsq_mi355x_tuning.so")
 
 LSQ_OK, LSQ_EINVAL, LSQ_EHIP, LSQ_ENOMEM, LSQ_ECODE, LSQ_ENODEV = 0, -1, -2, -3, -4, -5
+LSQ_EIO, LSQ_EFORMAT = -6, -7          # snapshots (since v2600): a file operation failed; not a (valid) snapshot
 
 
 class LsqError(RuntimeError):
@@ -122,6 +123,38 @@ class IndexBaseInfo(_Struct):
                 ("to_inf", C.c_int64), ("to_zero", C.c_int64), ("nans", C.c_int64), ("narrow_ms", C.c_double)]
 
 
+class SnapshotArrays(_Struct):
+    _fields_ = [("n", C.c_int64), ("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("packed", C.c_int), ("ncb", C.c_int), ("base_format", C.c_int),
+                ("nlist", C.c_int), ("filter_active", C.c_int), ("filter_force", C.c_int), ("reserved", C.c_int), ("allowed", C.c_int64),
+                ("codebooks", C.c_void_p), ("codes", C.c_void_p), ("dbnorms", C.c_void_p), ("norm_codes", C.c_void_p), ("cbnorms", C.c_void_p),
+                ("base", C.c_void_p), ("centroids", C.c_void_p), ("list_of_row", C.c_void_p), ("filter_bits", C.c_void_p)]
+
+
+class SnapshotSection(_Struct):
+    _fields_ = [("kind", C.c_int64), ("elem_bytes", C.c_int64), ("offset", C.c_int64), ("bytes", C.c_int64), ("digest", C.c_uint64)]
+
+
+class SnapshotInfo(_Struct):
+    _fields_ = [("format", C.c_int64), ("n", C.c_int64), ("d", C.c_int64), ("m", C.c_int64), ("h", C.c_int64), ("packed", C.c_int64), ("ncb", C.c_int64),
+                ("base_format", C.c_int64), ("nlist", C.c_int64), ("has_codes", C.c_int64), ("has_base", C.c_int64), ("filter_active", C.c_int64),
+                ("filter_force", C.c_int64), ("allowed", C.c_int64), ("file_bytes", C.c_int64), ("nsections", C.c_int64), ("header_digest", C.c_uint64),
+                ("sections", SnapshotSection * 9)]
+
+    def as_dict(self):
+        out = {k: getattr(self, k) for k, _ in self._fields_ if k != "sections"}
+        out["sections"] = [dict(self.sections[k].as_dict(), name=SNAP_NAMES[self.sections[k].kind]) for k in range(self.nsections)]
+        return out
+
+
+class SnapshotIoInfo(_Struct):
+    _fields_ = [("op", C.c_int64), ("bytes", C.c_int64), ("chunks", C.c_int64), ("chunk_bytes", C.c_int64), ("sections", C.c_int64),
+                ("host_staging_bytes", C.c_int64), ("derive_ms", C.c_double), ("digest_ms", C.c_double), ("copy_ms", C.c_double), ("file_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
+# the sections of a snapshot in file order: LSQ_SNAP_* -> the key of the array in Index.export / snapshot_read / snapshot_write
+SNAP_NAMES = {1: "codebooks", 2: "codes", 3: "dbnorms", 4: "norm_codes", 5: "cbnorms", 6: "base", 7: "centroids", 8: "list_of_row", 9: "filter_bits"}
+SNAPSHOT_FORMAT = 1
 BASE_F32, BASE_U8, BASE_F16, BASE_BF16 = 0, 1, 2, 3       # the format a base_u8 field / argument stands for (LSQ_BASE_F16, LSQ_BASE_BF16)
 RECON_ADD_COARSE, RECON_PAD_NAN = 1, 2
 RECON_ROAD_DWORD, RECON_ROAD_VEC16, RECON_ROAD_CODE_DWORDS = 1, 2, 4
@@ -273,6 +306,16 @@ SIGNATURES = {
     "lsq_index_narrow_base": (_i, [_vp, _i]),
     "lsq_index_get_base": (_i, [_vp, _vp, _i64, _i64, _i64, _i]),
     "lsq_index_get_base_info": (_i, [_vp, C.POINTER(IndexBaseInfo)]),
+    # snapshots (since v2600): an index saved, loaded, exported and digested; the host-only writer, reader, inspector and digest
+    "lsq_index_save": (_i, [_vp, C.c_char_p, _i]),
+    "lsq_index_load": (_i, [C.POINTER(_vp), _vp, C.c_char_p, _i]),
+    "lsq_index_export": (_i, [_vp, C.POINTER(SnapshotArrays), _i]),
+    "lsq_index_digest": (_i, [_vp, C.POINTER(SnapshotInfo)]),
+    "lsq_index_get_snapshot_info": (_i, [_vp, C.POINTER(SnapshotIoInfo)]),
+    "lsq_snapshot_write_cpu": (_i, [C.c_char_p, C.POINTER(SnapshotArrays)]),
+    "lsq_snapshot_read_cpu": (_i, [C.c_char_p, C.POINTER(SnapshotArrays)]),
+    "lsq_snapshot_inspect_cpu": (_i, [C.c_char_p, C.POINTER(SnapshotInfo), _i]),
+    "lsq_snapshot_digest_cpu": (_i, [_vp, _i64, _i64, C.POINTER(_u64)]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),
@@ -314,7 +357,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 2500     # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 2600     # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -112,6 +113,7 @@ struct lsq_ctx {
     int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
     int64_t range_batch = 0;                           // option "range_batch": records per fill batch of lsq_index_range_search (0 = automatic); a test hook
     int64_t recon_chunk = 0;                           // option "recon_chunk": rows per staging chunk of a host-buffer lsq_index_reconstruct (0 = automatic); a test hook
+    int64_t snapshot_chunk = 0;                        // option "snapshot_chunk": bytes per staging chunk of lsq_index_save / _load (0 = LSQ_SNAP_CHUNK_DEFAULT); a test hook
     // Staging for the host-buffer entry points.  Who writes what (a later call may assume NOTHING of their contents, except sK under tables_valid):
     //   sX, sX2  X: one chunk at a time, double-buffered, by the pipelined encode; the whole X by stage_X
     //   sK       the call's codebooks: uploaded (host_codebooks; claim_sK: K, K_prev) or computed into it (claim_sK: LSQR, SPGL1, the seeding).
@@ -327,6 +329,10 @@ extern "C" int lsq_set_option(lsq_ctx *c, const char *key, int64_t value) {
     else if (!strcmp(key, "recon_chunk")) {
         if (value < 0) { lsq_set_error("recon_chunk must be >= 0"); return LSQ_EINVAL; }
         c->recon_chunk = value;
+    }
+    else if (!strcmp(key, "snapshot_chunk")) {
+        if (value < 0 || value > (1ll << 30)) { lsq_set_error("snapshot_chunk must lie in 0..2^30"); return LSQ_EINVAL; }
+        c->snapshot_chunk = value;
     }
     else if (!strcmp(key, "ils_counter")) {
         if (value < 0 || value >= (int64_t)LSQ_IT_AUTO) { lsq_set_error("ils_counter must lie in 0..2^32-2"); return LSQ_EINVAL; }
@@ -589,6 +595,7 @@ struct lsq_index {
     lsq_narrow_counts hcounts{};                       // ... read back, and its time
     double narrow_ms = 0.0;
     PhaseClock<2> hclock;
+    lsq_snapshot_io_info sinfo{};                      // the last lsq_index_save, or the lsq_index_load that made this index
 };
 
 // the filter as a scan over all rows takes it: nothing without one; else the compact road -- the ascending list of allowed rows -- where the measured rule
@@ -1644,6 +1651,418 @@ extern "C" int lsq_index_search_rows(lsq_index *ix, float *dists, int *ids_out, 
 extern "C" int lsq_index_get_recon_info(lsq_index *ix, lsq_index_recon_info *out) {
     if (!ix || !out) { lsq_set_error("lsq_index_get_recon_info: null argument"); return LSQ_EINVAL; }
     *out = ix->rinfo;
+    return LSQ_OK;
+}
+
+// ---- snapshots: save, load, export, digest (lsq_snapshot.hip, lsq_snapshot_check.h) -------------------------------------------------------------
+// The logical state of an index as the sections of lsq_snapshot_check.h.  A section is either canonical where it lies in HBM (direct) or derived on the
+// device, chunk by chunk, into a staging chunk (derive(off, len, dst): bytes [off, off + len) of the section's stream to dst; off a multiple of 64).
+namespace {
+struct SnapSection {
+    const void *direct = nullptr;
+    std::function<int(int64_t, int64_t, void *)> derive;
+};
+
+// Two pinned chunks with their events, the device staging chunk, the digest's partials and one accumulator per section.  Slot j & 1 serves chunk j: its
+// events say when the device is done with the pinned chunk (and, under option "profile", how long each phase took)
+struct SnapStage {
+    hipStream_t s = nullptr;
+    char *pin[2] = {nullptr, nullptr};
+    hipEvent_t ev[2][4] = {};
+    bool busy[2] = {false, false};
+    DevBuf dstage, partials, acc;
+    int64_t chunk = 0;
+    bool timed = false, loading = false;
+    lsq_snapshot_io_info info{};
+    int open(lsq_ctx *c, bool load, bool pinned, bool derived) {
+        s = c->stream; timed = c->profile != 0; loading = load;
+        chunk = c->snapshot_chunk > 0 ? c->snapshot_chunk : LSQ_SNAP_CHUNK_DEFAULT;
+        chunk = std::max<int64_t>(LSQ_SNAP_ALIGN, chunk / LSQ_SNAP_ALIGN * LSQ_SNAP_ALIGN);
+        if (pinned) {
+            for (char *&p : pin) LSQ_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), (size_t)chunk, hipHostMallocDefault));
+            for (auto &slot : ev) for (hipEvent_t &e : slot) LSQ_HIP(hipEventCreate(&e));
+        }
+        LSQ_TRY(partials.ensure(sizeof(unsigned long long) * LSQ_SNAP_PARTIALS));
+        LSQ_TRY(acc.ensure(sizeof(unsigned long long) * 16));
+        LSQ_HIP(hipMemsetAsync(acc.p, 0, sizeof(unsigned long long) * 16, s));
+        if (derived) LSQ_TRY(dstage.ensure((size_t)chunk));
+        info = lsq_snapshot_io_info{};
+        info.op = load ? 2 : 1; info.chunk_bytes = chunk; info.host_staging_bytes = pinned ? 2 * chunk : 0;
+        return LSQ_OK;
+    }
+    unsigned long long *slot(int k) { return acc.as<unsigned long long>() + k; }
+    int mark(int sl, int e) {
+        if (timed || e == 3) LSQ_HIP(hipEventRecord(ev[sl][e], s));
+        return LSQ_OK;
+    }
+    int wait(int sl) {                               // the device is done with pinned chunk sl
+        if (!busy[sl]) return LSQ_OK;
+        LSQ_HIP(hipEventSynchronize(ev[sl][3]));
+        busy[sl] = false;
+        if (timed) {
+            float a = 0, b = 0, c = 0;
+            LSQ_HIP(hipEventElapsedTime(&a, ev[sl][0], ev[sl][1]));
+            LSQ_HIP(hipEventElapsedTime(&b, ev[sl][1], ev[sl][2]));
+            LSQ_HIP(hipEventElapsedTime(&c, ev[sl][2], ev[sl][3]));
+            if (loading) { info.copy_ms += a; info.digest_ms += b; }
+            else { info.derive_ms += a; info.digest_ms += b; info.copy_ms += c; }
+        }
+        return LSQ_OK;
+    }
+    int digests(int count, uint64_t *out) {          // the accumulators read back; waits
+        unsigned long long h[16] = {0};
+        LSQ_HIP(hipMemcpyAsync(h, acc.p, sizeof(unsigned long long) * (size_t)count, hipMemcpyDeviceToHost, s));
+        LSQ_HIP(hipStreamSynchronize(s));
+        for (int k = 0; k < count; ++k) out[k] = h[k];
+        return LSQ_OK;
+    }
+    ~SnapStage() {
+        if (s) (void)hipStreamSynchronize(s);       // nothing in flight touches the chunks when they go
+        for (char *p : pin) if (p) (void)hipHostFree(p);
+        for (auto &slot : ev) for (hipEvent_t e : slot) if (e) (void)hipEventDestroy(e);
+        dstage.release(); partials.release(); acc.release();
+    }
+};
+double snap_ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+}  // namespace
+
+static void index_snap_scalars(lsq_index *ix, lsq_snapshot_info *s) {
+    *s = lsq_snapshot_info{};
+    s->n = ix->n; s->d = ix->d;
+    s->has_codes = ix->codes != nullptr; s->has_base = ix->base != nullptr;
+    s->m = s->has_codes ? ix->m : 0; s->h = s->has_codes ? LSQ_H : 0;
+    s->packed = ix->packed ? 1 : 0; s->ncb = ix->packed ? ix->ncb : 0;
+    s->base_format = s->has_base ? ix->base_u8 : 0;
+    s->nlist = lsq_ivf_nlist(ix->ivf);
+    if (lsq_filter_active(ix->filter)) {
+        const lsq_filter_view v = lsq_filter_get(ix->filter);
+        s->filter_active = 1; s->filter_force = v.force & (LSQ_FILTER_FORCE_DENSE | LSQ_FILTER_FORCE_COMPACT); s->allowed = v.allowed;
+    }
+}
+
+// bytes [off, off + len) of the DENSE stream of the base rows (pitch d) gathered from rows ldb elements apart: a ragged first row, whole rows, a ragged last
+static int index_snap_dense_base(lsq_index *ix, int64_t off, int64_t len, void *dstv, hipMemcpyKind kind) {
+    hipStream_t s = ix->ctx->stream;
+    const int64_t e = (int64_t)index_base_elem(ix), rb = (int64_t)ix->d * e, pitch = ix->ldb * e;
+    const char *base = static_cast<const char *>(ix->base);
+    char *dst = static_cast<char *>(dstv);
+    int64_t row = off / rb, left = len;
+    const int64_t col = off - row * rb;
+    if (col) {
+        const int64_t take = std::min(rb - col, left);
+        LSQ_HIP(hipMemcpyAsync(dst, base + row * pitch + col, (size_t)take, kind, s));
+        dst += take; left -= take; ++row;
+    }
+    const int64_t whole = left / rb;
+    if (whole) {
+        LSQ_HIP(hipMemcpy2DAsync(dst, (size_t)rb, base + row * pitch, (size_t)pitch, (size_t)rb, (size_t)whole, kind, s));
+        dst += whole * rb; left -= whole * rb; row += whole;
+    }
+    if (left) LSQ_HIP(hipMemcpyAsync(dst, base + row * pitch, (size_t)left, kind, s));
+    return LSQ_OK;
+}
+
+// the sources of the planned sections.  lor: a buffer of the call that receives the row -> list map (LIST_OF_ROW has no canonical copy in HBM: the layout
+// holds its inverse)
+static int index_snap_sources(lsq_index *ix, const lsq_snapshot_info &s, DevBuf &lor, SnapSection *src, bool *derived) {
+    hipStream_t st = ix->ctx->stream;
+    *derived = false;
+    for (int k = 0; k < (int)s.nsections; ++k) {
+        SnapSection &sec = src[k];
+        switch (s.sections[k].kind) {
+        case LSQ_SNAP_CODEBOOKS: sec.direct = ix->K; break;
+        case LSQ_SNAP_CODES:
+            if (!ix->packed) sec.direct = ix->codes;
+            else sec.derive = [ix, st](int64_t off, int64_t len, void *dst) { return lsq_snap_launch_unpack(st, ix->codes, ix->n, ix->m, static_cast<uint8_t *>(dst), off, len, nullptr, 0, 0); };
+            break;
+        case LSQ_SNAP_DBNORMS: sec.direct = ix->norms; break;
+        case LSQ_SNAP_NORM_CODES:
+            sec.derive = [ix, st](int64_t off, int64_t len, void *dst) { return lsq_snap_launch_unpack(st, ix->codes, ix->n, ix->m, nullptr, 0, 0, static_cast<uint8_t *>(dst), off, len); };
+            break;
+        case LSQ_SNAP_CBNORMS: sec.direct = ix->norms; break;         // the norm table: its first ncb floats
+        case LSQ_SNAP_BASE:
+            if (ix->ldb == ix->d) sec.direct = ix->base;
+            else sec.derive = [ix](int64_t off, int64_t len, void *dst) { return index_snap_dense_base(ix, off, len, dst, hipMemcpyDeviceToDevice); };
+            break;
+        case LSQ_SNAP_CENTROIDS: sec.direct = lsq_ivf_centroids(ix->ivf); break;
+        case LSQ_SNAP_LIST_OF_ROW: {
+            const int *lids = nullptr, *loff = nullptr;
+            lsq_ivf_layout(ix->ivf, &lids, &loff);
+            LSQ_TRY(lor.ensure(sizeof(int32_t) * (size_t)ix->n));
+            LSQ_TRY(lsq_recon_launch_lor(st, lids, loff, ix->n, (int)s.nlist, lor.as<int32_t>()));
+            sec.direct = lor.p;
+            break;
+        }
+        case LSQ_SNAP_FILTER_BITS: sec.direct = lsq_filter_get(ix->filter).bits; break;
+        }
+        if (sec.derive) *derived = true;
+    }
+    return LSQ_OK;
+}
+
+// one section through the stage: derived (or read where it lies), digested into accumulator k and -- with a file -- copied out chunk by chunk, the copy of
+// chunk j + 1 under the write of chunk j
+static int index_snap_stream(SnapStage &st, const SnapSection &sec, int k, int64_t bytes, FILE *f, const char *name) {
+    const int64_t step = (!f && sec.direct) ? std::max<int64_t>(bytes, 1) : st.chunk;      // nothing to stage: one launch over the section where it lies
+    const int64_t nchunks = (bytes + step - 1) / step;
+    auto issue = [&](int64_t j) -> int {
+        const int sl = (int)(j & 1);
+        const int64_t off = j * step, len = std::min(step, bytes - off);
+        if (f) LSQ_TRY(st.mark(sl, 0));
+        const void *src = sec.direct ? static_cast<const char *>(sec.direct) + off : st.dstage.p;
+        if (!sec.direct) LSQ_TRY(sec.derive(off, len, st.dstage.p));
+        if (f) LSQ_TRY(st.mark(sl, 1));
+        LSQ_TRY(lsq_snap_launch_digest(st.s, src, (uint64_t)len, (uint64_t)off / 4, st.partials.as<unsigned long long>(), st.slot(k)));
+        if (f) {
+            LSQ_TRY(st.mark(sl, 2));
+            LSQ_HIP(hipMemcpyAsync(st.pin[sl], src, (size_t)len, hipMemcpyDeviceToHost, st.s));
+            LSQ_TRY(st.mark(sl, 3));
+            st.busy[sl] = true;
+        }
+        return LSQ_OK;
+    };
+    if (nchunks > 0) LSQ_TRY(issue(0));
+    for (int64_t j = 0; j < nchunks; ++j) {
+        if (j + 1 < nchunks) LSQ_TRY(issue(j + 1));
+        if (!f) continue;
+        const int sl = (int)(j & 1);
+        const int64_t len = std::min(step, bytes - j * step);
+        LSQ_TRY(st.wait(sl));
+        const auto t0 = std::chrono::steady_clock::now();
+        if (fwrite(st.pin[sl], 1, (size_t)len, f) != (size_t)len) { lsq_set_error("lsq_index_save: section %s: short write: %s", name, strerror(errno)); return LSQ_EIO; }
+        st.info.file_ms += snap_ms_since(t0);
+    }
+    st.info.chunks += nchunks; st.info.bytes += bytes; st.info.sections += 1;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_save(lsq_index *ix, const char *path, int flags) {
+    const char *fn = "lsq_index_save";
+    if (!ix || !path) { lsq_set_error("%s: null %s", fn, ix ? "path" : "index"); return LSQ_EINVAL; }
+    if (flags != 0) { lsq_set_error("%s: flags must be 0 (got %d)", fn, flags); return LSQ_EINVAL; }
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    const auto t_call = std::chrono::steady_clock::now();
+    lsq_snapshot_info s;
+    lsq_snap_error err;
+    index_snap_scalars(ix, &s);
+    if (!lsq_snap_plan(&s, &err)) { lsq_set_error("%s: %s", fn, err.text); return LSQ_EINVAL; }
+    ScopedBuf lor;
+    SnapSection src[LSQ_SNAP_MAX_SECTIONS];
+    bool derived = false;
+    SnapStage st;                                     // (declared before the file: it waits for the device before the chunks go)
+    LSQ_TRY(index_snap_sources(ix, s, lor.b, src, &derived));
+    LSQ_TRY(st.open(c, false, true, derived));
+    lsq_snap_temp temp(path);
+    lsq_snap_file out;
+    out.f = fopen(temp.tmp.c_str(), "wb");
+    if (!out.f) { lsq_set_error("%s: cannot open %s: %s", fn, temp.tmp.c_str(), strerror(errno)); return LSQ_EIO; }
+    temp.made = true;
+    std::vector<unsigned char> head((size_t)lsq_snap_table_end(s.nsections), 0);      // its place is kept: the digests are known last
+    if (fwrite(head.data(), 1, head.size(), out.f) != head.size()) { lsq_set_error("%s: short write to %s: %s", fn, temp.tmp.c_str(), strerror(errno)); return LSQ_EIO; }
+    int64_t at = (int64_t)head.size();
+    for (int k = 0; k < (int)s.nsections; ++k) {
+        const char *name = lsq_snap_kind_name(s.sections[k].kind);
+        if (!lsq_snap_write_pad(out.f, at, s.sections[k].offset)) { lsq_set_error("%s: section %s: short write: %s", fn, name, strerror(errno)); return LSQ_EIO; }
+        LSQ_TRY(index_snap_stream(st, src[k], k, s.sections[k].bytes, out.f, name));
+        at = s.sections[k].offset + s.sections[k].bytes;
+    }
+    uint64_t dig[LSQ_SNAP_MAX_SECTIONS];
+    LSQ_TRY(st.digests((int)s.nsections, dig));
+    for (int k = 0; k < (int)s.nsections; ++k) s.sections[k].digest = dig[k];
+    lsq_snap_encode(&s, &head);
+    if (fseeko(out.f, 0, SEEK_SET) != 0 || fwrite(head.data(), 1, head.size(), out.f) != head.size() || out.close() != 0) {
+        lsq_set_error("%s: cannot finish %s: %s", fn, temp.tmp.c_str(), strerror(errno));
+        return LSQ_EIO;
+    }
+    if (!temp.commit()) { lsq_set_error("%s: cannot rename %s to %s: %s", fn, temp.tmp.c_str(), path, strerror(errno)); return LSQ_EIO; }
+    st.info.bytes = s.file_bytes;
+    st.info.total_ms = snap_ms_since(t_call);
+    ix->sinfo = st.info;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_digest(lsq_index *ix, lsq_snapshot_info *out) {
+    const char *fn = "lsq_index_digest";
+    if (!ix || !out) { lsq_set_error("%s: null argument", fn); return LSQ_EINVAL; }
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    lsq_snapshot_info s;
+    lsq_snap_error err;
+    index_snap_scalars(ix, &s);
+    if (!lsq_snap_plan(&s, &err)) { lsq_set_error("%s: %s", fn, err.text); return LSQ_EINVAL; }
+    ScopedBuf lor;
+    SnapSection src[LSQ_SNAP_MAX_SECTIONS];
+    bool derived = false;
+    SnapStage st;
+    LSQ_TRY(index_snap_sources(ix, s, lor.b, src, &derived));
+    LSQ_TRY(st.open(c, false, false, derived));
+    for (int k = 0; k < (int)s.nsections; ++k) LSQ_TRY(index_snap_stream(st, src[k], k, s.sections[k].bytes, nullptr, ""));
+    uint64_t dig[LSQ_SNAP_MAX_SECTIONS];
+    LSQ_TRY(st.digests((int)s.nsections, dig));
+    for (int k = 0; k < (int)s.nsections; ++k) s.sections[k].digest = dig[k];
+    std::vector<unsigned char> head;
+    lsq_snap_encode(&s, &head);                       // the header's own digest: that of the file a save would write
+    *out = s;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_export(lsq_index *ix, lsq_snapshot_arrays *out, int on_device) {
+    const char *fn = "lsq_index_export";
+    if (!ix || !out) { lsq_set_error("%s: null argument", fn); return LSQ_EINVAL; }
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t stream = c->stream;
+    lsq_snapshot_info s;
+    lsq_snap_error err;
+    index_snap_scalars(ix, &s);
+    if (!lsq_snap_plan(&s, &err)) { lsq_set_error("%s: %s", fn, err.text); return LSQ_EINVAL; }
+    for (int64_t kind = 1; kind <= LSQ_SNAP_MAX_SECTIONS; ++kind) {      // everything is refused before anything is written
+        bool present = false;
+        for (int k = 0; k < (int)s.nsections; ++k) present = present || s.sections[k].kind == kind;
+        if (lsq_snap_array(out, kind) && !present) { lsq_set_error("%s: the index has no %s", fn, lsq_snap_kind_name(kind)); return LSQ_EINVAL; }
+    }
+    ScopedBuf lor, whole;                             // the host form of a derived section: derived whole on the device, then fetched
+    SnapSection src[LSQ_SNAP_MAX_SECTIONS];
+    bool derived = false;
+    LSQ_TRY(index_snap_sources(ix, s, lor.b, src, &derived));
+    int rc = LSQ_OK;
+    for (int k = 0; rc == LSQ_OK && k < (int)s.nsections; ++k) {
+        void *dst = lsq_snap_array(out, s.sections[k].kind);
+        const int64_t bytes = s.sections[k].bytes;
+        if (!dst) continue;
+        auto copy = [&](const void *from) -> int {
+            LSQ_HIP(hipMemcpyAsync(dst, from, (size_t)bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+            return LSQ_OK;
+        };
+        if (src[k].direct) rc = copy(src[k].direct);
+        else if (on_device) rc = src[k].derive(0, bytes, dst);
+        else if (s.sections[k].kind == LSQ_SNAP_BASE) rc = index_snap_dense_base(ix, 0, bytes, dst, hipMemcpyDeviceToHost);
+        else {
+            rc = whole.b.ensure((size_t)bytes);
+            if (rc == LSQ_OK) rc = src[k].derive(0, bytes, whole.b.p);
+            if (rc == LSQ_OK) rc = copy(whole.b.p);
+            if (rc == LSQ_OK && hipStreamSynchronize(stream) != hipSuccess) { lsq_set_error("%s: the copy failed", fn); rc = LSQ_EHIP; }      // `whole` is written again
+        }
+    }
+    if (hipStreamSynchronize(stream) != hipSuccess && rc == LSQ_OK) { lsq_set_error("%s: the copy failed", fn); rc = LSQ_EHIP; }
+    if (rc != LSQ_OK) return rc;
+    lsq_snap_scalars_out(&s, out);
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_snapshot_info(lsq_index *ix, lsq_snapshot_io_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_snapshot_info: null argument"); return LSQ_EINVAL; }
+    *out = ix->sinfo;
+    return LSQ_OK;
+}
+
+// The load: header and table validated on the host (nothing allocated before), every section streamed through the pinned chunks into a device array of its
+// own and digested THERE, the digests compared with the table, then the index built on those arrays by the roads every other index takes
+extern "C" int lsq_index_load(lsq_index **out, lsq_ctx *c, const char *path, int flags) {
+    const char *fn = "lsq_index_load";
+    if (!out) { lsq_set_error("%s: null out pointer", fn); return LSQ_EINVAL; }
+    *out = nullptr;
+    if (!c || !path) { lsq_set_error("%s: null %s", fn, c ? "path" : "context"); return LSQ_EINVAL; }
+    if (flags != 0) { lsq_set_error("%s: flags must be 0 (got %d)", fn, flags); return LSQ_EINVAL; }
+    LSQ_TRY(use_device(c));
+    const auto t_call = std::chrono::steady_clock::now();
+    lsq_snap_file in;
+    in.f = fopen(path, "rb");
+    if (!in.f) { lsq_set_error("%s: cannot open %s: %s", fn, path, strerror(errno)); return LSQ_EIO; }
+    lsq_snapshot_info s;
+    lsq_snap_error err;
+    if (const int rc = lsq_snap_read_header(in.f, &s, &err)) { lsq_set_error("%s: %s", fn, err.text); return rc; }
+    ScopedBuf buf[LSQ_SNAP_MAX_SECTIONS];
+    SnapStage st;
+    LSQ_TRY(st.open(c, true, true, false));
+    int64_t at = lsq_snap_table_end(s.nsections);
+    for (int k = 0; k < (int)s.nsections; ++k) {
+        const lsq_snapshot_section &sec = s.sections[k];
+        const char *name = lsq_snap_kind_name(sec.kind);
+        if (const int rc = lsq_snap_read_pad(in.f, at, sec.offset, name, &err)) { lsq_set_error("%s: %s", fn, err.text); return rc; }
+        LSQ_TRY(buf[k].b.ensure((size_t)sec.bytes + 16));             // 16 bytes of slack past the last row, never read
+        const int64_t nchunks = (sec.bytes + st.chunk - 1) / st.chunk;
+        for (int64_t j = 0; j < nchunks; ++j) {
+            const int sl = (int)(j & 1);
+            const int64_t off = j * st.chunk, len = std::min(st.chunk, sec.bytes - off);
+            LSQ_TRY(st.wait(sl));                                     // the upload of chunk j - 2 has left the pinned chunk
+            const auto t0 = std::chrono::steady_clock::now();
+            if (fread(st.pin[sl], 1, (size_t)len, in.f) != (size_t)len) { lsq_set_error("%s: section %s: read failed at byte %lld", fn, name, (long long)off); return LSQ_EIO; }
+            st.info.file_ms += snap_ms_since(t0);
+            char *dst = buf[k].b.as<char>() + off;
+            LSQ_TRY(st.mark(sl, 0));
+            LSQ_HIP(hipMemcpyAsync(dst, st.pin[sl], (size_t)len, hipMemcpyHostToDevice, st.s));
+            LSQ_TRY(st.mark(sl, 1));
+            LSQ_TRY(lsq_snap_launch_digest(st.s, dst, (uint64_t)len, (uint64_t)off / 4, st.partials.as<unsigned long long>(), st.slot(k)));
+            LSQ_TRY(st.mark(sl, 2));
+            LSQ_TRY(st.mark(sl, 3));
+            st.busy[sl] = true;
+        }
+        st.info.chunks += nchunks; st.info.sections += 1;
+        at = sec.offset + sec.bytes;
+    }
+    LSQ_TRY(st.wait(0));
+    LSQ_TRY(st.wait(1));
+    uint64_t dig[LSQ_SNAP_MAX_SECTIONS];
+    LSQ_TRY(st.digests((int)s.nsections, dig));
+    for (int k = 0; k < (int)s.nsections; ++k)
+        if (dig[k] != s.sections[k].digest) {
+            lsq_set_error("%s: section %s: digest mismatch (the table says %016llx, what arrived on the device gives %016llx)", fn, lsq_snap_kind_name(s.sections[k].kind),
+                          (unsigned long long)s.sections[k].digest, (unsigned long long)dig[k]);
+            return LSQ_EFORMAT;
+        }
+    auto find = [&](int64_t kind) -> DevBuf * {
+        for (int k = 0; k < (int)s.nsections; ++k) if (s.sections[k].kind == kind) return &buf[k].b;
+        return nullptr;
+    };
+    auto ptr = [&](int64_t kind) -> void * { DevBuf *b = find(kind); return b ? b->p : nullptr; };
+    auto take = [&](int64_t kind, DevBuf &own) { if (DevBuf *b = find(kind)) { own = *b; *b = DevBuf{}; } };      // the index owns the array from here on
+    lsq_index *ix = nullptr;
+    if (!s.packed) {
+        lsq_index_desc d{};
+        d.n = s.n; d.d = (int)s.d; d.m = (int)s.m; d.h = (int)s.h;
+        d.codes = static_cast<const uint8_t *>(ptr(LSQ_SNAP_CODES)); d.codebooks = static_cast<const float *>(ptr(LSQ_SNAP_CODEBOOKS));
+        d.dbnorms = static_cast<const float *>(ptr(LSQ_SNAP_DBNORMS));
+        d.base = ptr(LSQ_SNAP_BASE); d.base_u8 = (int)s.base_format; d.ldb = (int)s.d; d.on_device = 1;
+        LSQ_TRY(lsq_index_create(&ix, c, &d));
+        take(LSQ_SNAP_CODES, ix->own_codes);
+        take(LSQ_SNAP_DBNORMS, ix->own_norms);
+    } else {
+        lsq_index_packed_desc d{};
+        d.n = s.n; d.d = (int)s.d; d.m = (int)s.m; d.h = (int)s.h; d.ncb = (int)s.ncb;
+        d.codes = static_cast<const uint8_t *>(ptr(LSQ_SNAP_CODES)); d.norm_codes = static_cast<const uint8_t *>(ptr(LSQ_SNAP_NORM_CODES));
+        d.cbnorms = static_cast<const float *>(ptr(LSQ_SNAP_CBNORMS)); d.codebooks = static_cast<const float *>(ptr(LSQ_SNAP_CODEBOOKS));
+        d.base = ptr(LSQ_SNAP_BASE); d.base_u8 = (int)s.base_format; d.ldb = (int)s.d; d.on_device = 1;
+        LSQ_TRY(lsq_index_create_packed(&ix, c, &d));                 // a norm byte >= ncb: LSQ_EINVAL from the pack kernel's count
+    }
+    take(LSQ_SNAP_CODEBOOKS, ix->own_K);
+    take(LSQ_SNAP_BASE, ix->own_base);
+    int rc = LSQ_OK;
+    if (s.nlist > 0) {
+        lsq_ivf_desc d{};
+        d.nlist = (int)s.nlist; d.centroids = static_cast<const float *>(ptr(LSQ_SNAP_CENTROIDS)); d.list_of_row = static_cast<const int32_t *>(ptr(LSQ_SNAP_LIST_OF_ROW));
+        d.on_device = 1;
+        rc = lsq_index_set_lists(ix, &d);                             // a list id outside [0, nlist): LSQ_EINVAL from the key kernel's count
+    }
+    if (rc == LSQ_OK && s.filter_active) {
+        const int64_t words = (s.n + 31) / 32;
+        uint32_t last = 0;
+        if (hipMemcpy(&last, static_cast<const uint32_t *>(ptr(LSQ_SNAP_FILTER_BITS)) + (words - 1), 4, hipMemcpyDeviceToHost) != hipSuccess) { lsq_set_error("%s: the read-back failed", fn); rc = LSQ_EHIP; }
+        if (rc == LSQ_OK && s.n % 32 && (last >> (s.n % 32)) != 0) { lsq_set_error("%s: section FILTER_BITS: bits at or past n are set", fn); rc = LSQ_EFORMAT; }
+        lsq_filter_desc d{};
+        d.form = LSQ_FILTER_BITS; d.data = ptr(LSQ_SNAP_FILTER_BITS); d.flags = (int)s.filter_force; d.on_device = 1;
+        if (rc == LSQ_OK) rc = lsq_index_set_filter(ix, &d);
+        if (rc == LSQ_OK && lsq_filter_get(ix->filter).allowed != s.allowed) {
+            lsq_set_error("%s: section FILTER_BITS: %lld bits are set, the header says %lld", fn, (long long)lsq_filter_get(ix->filter).allowed, (long long)s.allowed);
+            rc = LSQ_EFORMAT;
+        }
+    }
+    if (rc != LSQ_OK) { (void)lsq_index_destroy(ix); return rc; }
+    st.info.bytes = s.file_bytes;
+    st.info.total_ms = snap_ms_since(t_call);
+    ix->sinfo = st.info;
+    *out = ix;
     return LSQ_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "lsq_range_check.h"
 #include "lsq_recon_check.h"
 #include "lsq_half_check.h"
+#include "lsq_snapshot_check.h"
 
 #define LSQ_H 256          // candidates per codebook: one wave x float4 per lane
 #define LSQ_MAX_M 16
@@ -574,6 +575,16 @@ const float *lsq_ivf_centroids(const lsq_ivf_state *st);
 int lsq_half_launch_narrow(hipStream_t s, const float *src, int64_t lds, void *dst, int64_t n, int d, int format, unsigned long long *counts);
 // dst row r (ldo floats apart, 4-byte aligned) = widen(src row r, lds elements apart) for count rows of d elements of `format` (1: uint8, or a half format)
 int lsq_half_launch_widen(hipStream_t s, const void *src, int format, int64_t lds, float *dst, int64_t ldo, int64_t count, int d);
+
+// ---- snapshots (lsq_snapshot.hip): the digest of a device byte range and the unpacking of packed rows ----------------------------------------
+// *acc (device) += the digest of `bytes` bytes at p (any alignment) whose first byte is byte 0 of word first_word of its section: chunks of a section add up
+// in stream order.  partials: LSQ_SNAP_PARTIALS 64-bit words of device scratch.  No allocation, no wait
+constexpr int LSQ_SNAP_PARTIALS = 2048;
+int lsq_snap_launch_digest(hipStream_t s, const void *p, uint64_t bytes, uint64_t first_word, unsigned long long *partials, unsigned long long *acc);
+// packed rows [n][m + 1] -> bytes [c0, c0 + cbytes) of the codes stream [n][m] at codes_out and the norm bytes of rows [r0, r0 + rcount) at norms_out (either
+// may be null: not wanted)
+int lsq_snap_launch_unpack(hipStream_t s, const uint8_t *rows, int64_t n, int m, uint8_t *codes_out, int64_t c0, int64_t cbytes, uint8_t *norms_out, int64_t r0,
+                           int64_t rcount);
 
 // ---- what a handle that lives in a file of its own (lsq_partition.hip) needs of its context (lsq_api.hip): its device made current, the stream it is bound
 // to now, option "profile".  Nothing of the context is written ------------------------------------------------------------------------------------------

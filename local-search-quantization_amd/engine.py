@@ -8,6 +8,7 @@ liblsq_mi355x.so.
 """
 import contextlib
 import ctypes as C
+import os
 import weakref
 
 import numpy as np
@@ -444,6 +445,12 @@ class Engine:
         """The same from device tensors (quantize_norms_dev's idx as it is).  dcodes, dnorm_codes and dcbnorms are read once, before this returns: they
         may be freed or overwritten afterwards; dK and base are borrowed as in index_dev."""
         return Index(self, dcodes, dK, None, m, base, h, None, on_device=True, packed=(dnorm_codes, dcbnorms), base_format=base_format)
+
+    def load_index(self, path, dev=False):
+        """The Index a snapshot file holds (Index.save): header and table are validated before anything is allocated, the sections stream into device
+        arrays the index owns, and what arrived on the device is digested there and compared with the file's table.  It answers every call bit for bit
+        like the index that was saved.  dev: its calls take and return torch tensors (as Engine.index_dev's) instead of numpy arrays   [lsq_index_load]"""
+        return Index._loaded(self, path, dev)
 
     # -- (1e) the beam-search encoder on resident codebooks ----------------------------------
     def encoder(self, K, m, chunk=0, h=H):
@@ -1180,6 +1187,87 @@ class Index(_Handle):
         ldo = int(side.pitch(out)) if out.shape[0] > 1 else int(out.shape[1])
         self._eng._call(side, "lsq_index_get_base", p(out) if count > 0 else None, int(start), count, ldo, int(self._dev), h=self._h)
         return out
+
+    # -- snapshots: the logical state saved, loaded, exported, digested ------------------------
+    @classmethod
+    def _loaded(cls, engine, path, dev):
+        self = cls.__new__(cls)
+        self._bind(engine, dev)
+        handle = C.c_void_p()
+        engine._call(self._side, "lsq_index_load", engine._h, os.fsencode(path), 0, h=C.byref(handle))
+        self._h = handle
+        engine._indexes.add(self)
+        self._keep = ()
+        sc = self._snapshot_scalars()
+        self.n, self.d, self.m = int(sc.n), int(sc.d), int(sc.m)
+        self._fmt, self._u8 = int(sc.base_format), int(sc.base_format) == _lib.BASE_U8
+        if sc.nlist:
+            self.nlist = int(sc.nlist)
+        return self
+
+    def _snapshot_scalars(self):
+        """the scalars of the logical state (an export that asks for no array); what the index has follows from them"""
+        a = _lib.SnapshotArrays()
+        self._eng._call(_HOST, "lsq_index_export", C.byref(a), 0, h=self._h)
+        self._has_codes, self._has_base, self._packed = a.m > 0, self._has_base_rows(), bool(a.packed)
+        return a
+
+    def _has_base_rows(self):
+        return bool(self.base_info()["elem_bytes"])
+
+    def save(self, path):
+        """Write the index's logical state -- the arrays a caller would pass to build it fresh, after every add / remove / compact -- to the snapshot
+        file `path` (a temporary beside it, renamed on success).  The file is a function of that state alone: equal indexes save equal bytes
+        [lsq_index_save]"""
+        self._eng._call(self._side, "lsq_index_save", os.fsencode(path), 0, h=self._h)
+
+    def export(self, dev=False):
+        """The logical state as arrays: a dict with only the keys the index has -- codebooks (m*256,d), codes (n,m), dbnorms (n,) or norm_codes (n,) +
+        cbnorms (ncb,), base (n,d) in the stored format (bfloat16 rows: uint16 bits on the host), centroids (nlist,d) + list_of_row (n,), filter_bits
+        (ceil(n/32),) uint32 + filter_force -- numpy arrays, or torch device tensors with dev=True   [lsq_index_export]"""
+        sc = self._snapshot_scalars()
+        side = _DEVICE if dev else _HOST
+        n, d, m = int(sc.n), int(sc.d), int(sc.m)
+        like = self._eng._device() if dev else None
+        want = {}
+        if m:
+            want["codebooks"], want["codes"] = ((m * H, d), _F32), ((n, m), _U8)
+            if sc.packed:
+                want["norm_codes"], want["cbnorms"] = ((n,), _U8), ((int(sc.ncb),), _F32)
+            else:
+                want["dbnorms"] = ((n,), _F32)
+        if self._has_base:
+            fmt = int(sc.base_format)
+            host_dt = {_lib.BASE_F32: _F32, _lib.BASE_U8: _U8, _lib.BASE_F16: np.float16, _lib.BASE_BF16: np.uint16}[fmt]
+            want["base"] = ((n, d), host_dt)
+        if sc.nlist:
+            want["centroids"], want["list_of_row"] = ((int(sc.nlist), d), _F32), ((n,), _I32)
+        if sc.filter_active:
+            want["filter_bits"] = (((n + 31) // 32,), np.uint32)
+        out, a = {}, _lib.SnapshotArrays()
+        for key, (shape, dt) in want.items():
+            if not dev:
+                out[key] = np.zeros(shape, dtype=dt)
+            else:
+                import torch
+                tdt = {"uint32": torch.int32, "uint16": torch.bfloat16}.get(np.dtype(dt).name) or getattr(torch, np.dtype(dt).name)
+                out[key] = torch.empty(shape, dtype=tdt, device=like)      # (filter_bits: the uint32 words as int32; bfloat16 rows as torch.bfloat16)
+            setattr(a, key, side.ptr(out[key]))
+        self._eng._call(side, "lsq_index_export", C.byref(a), int(dev), h=self._h)
+        if sc.filter_active:
+            out["filter_force"] = int(a.filter_force)
+        return out
+
+    def digest(self):
+        """Scalars and per-section digests of the logical state, computed on the device; equal to snapshot_info() of the file save() would write: n, d, m,
+        ..., file_bytes, header_digest, sections = [{name, kind, elem_bytes, offset, bytes, digest}]   [lsq_index_digest]"""
+        return self._info("lsq_index_digest", _lib.SnapshotInfo)
+
+    def snapshot_info(self):
+        """the last save() of this index, or the load that made it: op (1 save, 2 load), bytes, chunks, chunk_bytes, sections, host_staging_bytes, file_ms,
+        total_ms and, with profile=True, derive_ms / digest_ms / copy_ms   [lsq_index_get_snapshot_info]"""
+        return self._info("lsq_index_get_snapshot_info", _lib.SnapshotIoInfo)
+
 
 
 # -- the beam-search encoder (made by Engine.encoder / Engine.encoder_dev) ------------------------

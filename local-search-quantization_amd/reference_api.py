@@ -15,8 +15,12 @@ Same function names, positional arguments, array shapes (Julia d x n / m x n / l
 Extra keyword-only arguments (`seed`, `it`, `engine`) expose what the reference leaves to global
 RNG state.  Everything runs in liblsq_mi355x.so on the GPU; there is no CPU fallback here.
 """
+import ctypes as C
+import os
+
 import numpy as np
 
+from . import _lib
 from . import engine as _engine
 
 _default_engine = None
@@ -792,3 +796,89 @@ def splitarray(x, nparts):
     """x: a range (1-based like Julia's 1:n) -> list of ranges."""
     n = len(x)
     return [x[s:e] for s, e in _engine.splitarray(n, nparts)]
+
+
+# ---- snapshots without an engine: the host-only writer, reader, inspector and digest (lsq_snapshot_*_cpu) ---------------------------------------------
+_SNAP_DTYPES = {"codebooks": np.float32, "codes": np.uint8, "dbnorms": np.float32, "norm_codes": np.uint8, "cbnorms": np.float32, "centroids": np.float32,
+                "list_of_row": np.int32, "filter_bits": np.uint32}
+_SNAP_BASE = {_lib.BASE_F32: np.float32, _lib.BASE_U8: np.uint8, _lib.BASE_F16: np.float16, _lib.BASE_BF16: np.uint16}
+
+
+def snapshot_digest(data, first_word=0):
+    """The digest of the bytes of `data` (anything numpy can view as bytes) taken as the words first_word, first_word + 1, ... of a snapshot section
+    (include/lsq_mi355x.h (3p)); the digests of pieces cut at multiples of 4 bytes add up, mod 2^64, to the digest of the whole   [lsq_snapshot_digest_cpu]"""
+    buf = np.frombuffer(np.ascontiguousarray(data).tobytes(), dtype=np.uint8)
+    out = C.c_uint64()
+    _lib.check(_lib.load().lsq_snapshot_digest_cpu(buf.ctypes.data if buf.size else None, int(buf.size), int(first_word), C.byref(out)))
+    return int(out.value)
+
+
+def snapshot_info(path, verify=False):
+    """Header and section table of a snapshot file: n, d, m, h, packed, ncb, base_format, nlist, has_codes, has_base, filter_active, filter_force, allowed,
+    file_bytes, header_digest and sections = [{name, kind, elem_bytes, offset, bytes, digest}].  verify: every section is read, its digest and the
+    padding before it checked.  No engine, no device   [lsq_snapshot_inspect_cpu]"""
+    info = _lib.SnapshotInfo()
+    _lib.check(_lib.load().lsq_snapshot_inspect_cpu(os.fsencode(path), C.byref(info), int(bool(verify))))
+    return info.as_dict()
+
+
+def snapshot_write(path, *, codebooks=None, codes=None, dbnorms=None, norm_codes=None, cbnorms=None, base=None, base_format=None, centroids=None,
+                   list_of_row=None, filter_bits=None, filter_force=0):
+    """Write a snapshot from host arrays -- the keys of Index.export() -- without an engine: the bytes Index.save() writes for the index built over
+    them.  A plain index gives dbnorms, a packed one norm_codes and cbnorms; base: float32, uint8, float16 rows, or uint16 bfloat16 bits with
+    base_format="bf16"; filter_bits: uint32 words, bits at or past n are dropped   [lsq_snapshot_write_cpu]"""
+    a, keep = _lib.SnapshotArrays(), []
+    given = {"codebooks": codebooks, "codes": codes, "dbnorms": dbnorms, "norm_codes": norm_codes, "cbnorms": cbnorms, "centroids": centroids,
+             "list_of_row": list_of_row, "filter_bits": filter_bits}
+    for key, arr in given.items():
+        if arr is not None:
+            arr = np.ascontiguousarray(arr, dtype=_SNAP_DTYPES[key])
+            keep.append(arr)
+            setattr(a, key, arr.ctypes.data)
+    if codes is None and base is None:
+        raise ValueError("a snapshot needs codes, base rows or both")
+    if codes is not None:
+        if codebooks is None or (dbnorms is None) == (norm_codes is None) or (norm_codes is None) != (cbnorms is None):
+            raise ValueError("codes need codebooks and either dbnorms or norm_codes + cbnorms")
+        a.n, a.m, a.h, a.d = int(keep[1].shape[0]), int(np.asarray(codes).shape[1]), 256, int(np.asarray(codebooks).shape[1])
+        a.packed, a.ncb = int(norm_codes is not None), 0 if cbnorms is None else int(np.asarray(cbnorms).shape[0])
+    if base is not None:
+        base = np.asarray(base)
+        fmt = {"float32": _lib.BASE_F32, "uint8": _lib.BASE_U8, "float16": _lib.BASE_F16}.get(base.dtype.name)
+        if base_format == "bf16" and base.dtype == np.uint16:
+            fmt = _lib.BASE_BF16
+        if fmt is None or (base_format is not None and base_format != {_lib.BASE_F16: "f16", _lib.BASE_BF16: "bf16"}.get(fmt)):
+            raise TypeError("base rows of dtype %s with base_format=%r" % (base.dtype, base_format))
+        base = np.ascontiguousarray(base)
+        keep.append(base)
+        a.base, a.base_format = base.ctypes.data, fmt
+        if codes is None:
+            a.n, a.d = int(base.shape[0]), int(base.shape[1])
+    a.nlist = 0 if centroids is None else int(np.asarray(centroids).shape[0])
+    a.filter_active, a.filter_force = int(filter_bits is not None), int(filter_force)
+    sizes = {"codebooks": a.m * 256 * a.d, "codes": a.n * a.m, "dbnorms": a.n, "norm_codes": a.n, "cbnorms": a.ncb, "centroids": a.nlist * a.d,
+             "list_of_row": a.n, "filter_bits": (a.n + 31) // 32}
+    for key, arr in given.items():
+        if arr is not None and np.asarray(arr).size != sizes[key]:
+            raise ValueError("%s holds %d elements, the shapes ask for %d" % (key, np.asarray(arr).size, sizes[key]))
+    if base is not None and base.shape != (a.n, a.d):
+        raise ValueError("base must be (%d, %d), got %s" % (a.n, a.d, base.shape))
+    _lib.check(_lib.load().lsq_snapshot_write_cpu(os.fsencode(path), C.byref(a)))
+
+
+def snapshot_read(path):
+    """The arrays of a snapshot file as a dict with the keys of Index.export() (only those present; filter_force beside filter_bits), every digest
+    verified.  No engine, no device   [lsq_snapshot_inspect_cpu, lsq_snapshot_read_cpu]"""
+    info = snapshot_info(path)
+    n, d, m = info["n"], info["d"], info["m"]
+    shapes = {"codebooks": (m * 256, d), "codes": (n, m), "dbnorms": (n,), "norm_codes": (n,), "cbnorms": (info["ncb"],), "base": (n, d),
+              "centroids": (info["nlist"], d), "list_of_row": (n,), "filter_bits": ((n + 31) // 32,)}
+    a, out = _lib.SnapshotArrays(), {}
+    for sec in info["sections"]:
+        key = sec["name"]
+        out[key] = np.zeros(shapes[key], dtype=_SNAP_BASE[info["base_format"]] if key == "base" else _SNAP_DTYPES[key])
+        setattr(a, key, out[key].ctypes.data)
+    _lib.check(_lib.load().lsq_snapshot_read_cpu(os.fsencode(path), C.byref(a)))
+    if info["filter_active"]:
+        out["filter_force"] = int(a.filter_force)
+    return out

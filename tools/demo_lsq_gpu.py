@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L [--base-format f16|bf16]] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--delete FRACTION] [--radius R] [--reconstruct] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L [--base-format f16|bf16]] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--delete FRACTION] [--radius R] [--reconstruct] [--save PATH] [--load PATH] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -45,6 +45,9 @@ the same resident base rows.  The reference has no such search.
 resident index (Index.remove: tombstones) and the recall of the ADC search -- and of the --ivf search over the same codes -- is taken against Index.knn over
 the rows that are left; then Index.compact makes the rows leave, the same searches run again, and their ids, taken back through old_of_new, must name the
 same rows: the demo asserts it and prints the two recall curves side by side.
+
+--save PATH / --load PATH: the index over the base codes written to a snapshot file (Index.save; the section table with its digests is printed) / an index read
+back from a snapshot (Engine.load_index) and searched -- the same ids as the exhaustive scan when both name one file.
 
 --reconstruct: the base prefix decoded from the resident codes (Index.reconstruct) with its mean squared error against the base rows, with --ivf ...
 --residual also the residual index decoded with the coarse add, and one search whose queries are stored rows (Index.search_rows).
@@ -273,6 +276,14 @@ def main():
         except (ValueError, IndexError):
             raise SystemExit("--radius takes a distance R or `auto`")
         del argv[at:at + 2]
+    snap = {}
+    for flag in ("--save", "--load"):
+        if flag in argv:
+            at = argv.index(flag)
+            if at + 1 >= len(argv):
+                raise SystemExit("%s takes a PATH" % flag)
+            snap[flag] = argv[at + 1]
+            del argv[at:at + 2]
     grow = None
     if "--grow" in argv:
         at = argv.index("--grow")
@@ -413,6 +424,34 @@ def main():
         range_counts(radius, name, x_base, x_query, B_base, C, db_norms, m, ivf, fraction)
     if recon:
         reconstruct_rows(name, x_base, B_base, C, db_norms, m, knn)
+    if snap:
+        snapshot_roundtrip(snap, name, x_query, B_base, C, db_norms, m, knn, gt, idx)
+
+
+def snapshot_roundtrip(snap, name, x_query, B_base, C, db_norms, m, knn, gt, idx):
+    """--save PATH: the index over the base codes written to a snapshot file (Index.save), its section table printed.  --load PATH: an index read back from
+    a snapshot (Engine.load_index) and searched; its ids are compared with the exhaustive scan's when the file holds as many rows"""
+    Q = np.ascontiguousarray(x_query.T)
+    with lsq.Engine(0) as eng:
+        if "--save" in snap:
+            with eng.index((B_base - 1).astype(np.uint8).T, np.ascontiguousarray(np.hstack(C).T), db_norms, m) as ix:
+                t0 = time.perf_counter()
+                ix.save(snap["--save"])
+                dt = time.perf_counter() - t0
+                info, io = lsq.snapshot_info(snap["--save"], verify=True), ix.snapshot_info()
+                print("Saved the index of %d rows to %s: %d bytes in %d sections and %d chunks, %.3f s; the file's table equals the index's digest: %s"
+                      % (ix.n, snap["--save"], info["file_bytes"], info["nsections"], io["chunks"], dt, info["sections"] == ix.digest()["sections"]))
+                for sec in info["sections"]:
+                    print("   %-12s %12d bytes at %12d   digest %016x" % (sec["name"], sec["bytes"], sec["offset"], sec["digest"]))
+        if "--load" in snap:
+            t0 = time.perf_counter()
+            with eng.load_index(snap["--load"]) as lx:
+                dt = time.perf_counter() - t0
+                _, lidx = lx.search(Q, min(knn, lx.n))
+                print("Loaded an index of %d rows (d = %d, m = %d) from %s in %.3f s" % (lx.n, lx.d, lx.m, snap["--load"], dt))
+                if lx.n == B_base.shape[1]:
+                    lrec = lsq.eval_recall(gt, np.ascontiguousarray(lidx.T).astype(np.uint32), min(knn, lx.n))
+                    print("%s: recall@1 of the loaded index = %.4f; ids %s the exhaustive scan's" % (name, lrec[0], "EQUAL" if np.array_equal(lidx.T, idx) else "differ from"))
 
 
 def reconstruct_rows(name, x_base, B_base, C, db_norms, m, knn):
