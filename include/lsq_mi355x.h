@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 2600
+#define LSQ_VERSION 2700
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -138,6 +138,9 @@ LSQ_API int lsq_set_stream(lsq_ctx *ctx, void *hip_stream);
  *   "rerank_batch" (default 0): queries per batch of the re-rank stage of every lsq_index created on this context; 0 = automatic (batches of at most
  *        2^28 (query, candidate) records, like the scans).  A test hook: small shapes cross batch boundaries.  Same results.
  *   "knn_u8_int" (0/1, default 1): 0 = lsq_index_knn widens 8-bit rows and queries even where its integer road applies.  A test hook: same results.
+ *   "knn_prefilter" (0/1, default 0; since v2700, (3q)): 1 = exact k-NN (lsq_knn_exact, lsq_knn_exact_dev, lsq_index_knn of every lsq_index created on this
+ *        context) pre-filters the thresholded road on the matrix cores.  Same results, bit for bit.
+ *   "knn_prefilter_cap" (default 0): pending pairs per query of the pre-filter; 0 = automatic (twice the list capacity).  A test hook: same results.
  *   "range_batch" (default 0): records per fill batch of lsq_index_range_search on every lsq_index created on this context; 0 = automatic (2^28).  A
  *        test hook: small shapes cross batch boundaries, and a query larger than the budget is a batch of its own.  Same results.
  *   (liblsq_mi355x_tuning.so only) "ablation": timing-only kernel variants whose results are garbage. */
@@ -1026,6 +1029,44 @@ LSQ_API int lsq_snapshot_write_cpu(const char *path, const lsq_snapshot_arrays *
 LSQ_API int lsq_snapshot_read_cpu(const char *path, lsq_snapshot_arrays *out);
 LSQ_API int lsq_snapshot_inspect_cpu(const char *path, lsq_snapshot_info *out, int verify);
 LSQ_API int lsq_snapshot_digest_cpu(const void *data, int64_t bytes, int64_t first_word, uint64_t *out);
+
+/* ---- (3q) the MFMA pre-filter of exact k-NN (csrc/lsq_knnm.hip; since v2700) ------------------------------------------------------------------------------
+ * THE REFERENCE HAS NO COUNTERPART.  Option "knn_prefilter" = 1 lets lsq_knn_exact, lsq_knn_exact_dev (3d) and lsq_index_knn (3f) decide on the f32 matrix cores
+ * which (query, row) pairs can lie within a query's threshold, and compute the direct chain of (3d) only for those.  THE RESULT DOES NOT CHANGE, NOT BY A BIT:
+ * distances, ids, tie order, NaN last, and the statistics candidates, fallback_queries, exhaustive, threshold_rank and list_capacity are those of the call
+ * with the option off.  Per pair the pre-filter evaluates  a = (Nx + Nq) - 2 <x, q>  (Nx, Nq: f32 fma sums of squares; <x, q>: v_mfma_f32_32x32x2_f32) and
+ * drops the pair iff  a > tau_q + kappa_d (Nx + Nq) + eta_d,  where |a - dist| <= kappa_d (Nx + Nq) + eta_d over every rounding of both computations
+ * (lsq_knn_prefilter_bound; proof: DESIGN 4.29) -- so no pair within tau_q is dropped, and NaN or inf anywhere keeps the pair.  Every pair kept is then
+ * computed by the direct chain and judged as before.
+ *   served      it acts on the thresholded road alone (n > 65536, not "linscan_exhaustive"), f32 queries, no row filter, d <= LSQ_KNN_PREFILTER_MAX_D; every
+ *               other call takes the direct road as before and says why (reason).
+ *   overflow    a query keeps at most pending-capacity pairs (twice the list capacity; test hook "knn_prefilter_cap").  A query with more is redone by the
+ *               direct scan; when more than half the queries of a batch overflow, the rest of the call runs with the pre-filter off (switched_off).  Data whose
+ *               norms dwarf its distances (a large common offset) ends there: the window kappa_d (Nx + Nq) exceeds every distance, and the call costs
+ *               one wasted MFMA pass more than the direct call.
+ *   lsq_knn_prefilter_bound   host only, no context: kappa_d = (4 d + 32) 2^-24 1.01 rounded up to f32, eta_d = (4 d + 32) 2^-120.  LSQ_EINVAL: d outside
+ *               1 .. LSQ_KNN_PREFILTER_MAX_D, a null pointer.
+ *   lsq_index_get_knn_prefilter_info   the account of the last lsq_index_knn call of the index.  (The context forms lsq_knn_exact / _dev run the pre-filter
+ *               the same way but have no getter yet: a context symbol belongs in the context walk's catalogue first) */
+#define LSQ_KNN_PREFILTER_MAX_D 16384
+enum { LSQ_KNN_PREFILTER_SERVED = 0,           /* reason: */
+       LSQ_KNN_PREFILTER_NOT_ASKED = 1,        /* option "knn_prefilter" is 0 */
+       LSQ_KNN_PREFILTER_FILTERED = 2,         /* a row filter is in force (dense or compact road) */
+       LSQ_KNN_PREFILTER_U8_QUERIES = 3,       /* uint8 queries (the integer road included) */
+       LSQ_KNN_PREFILTER_EXHAUSTIVE = 4,       /* the exhaustive road: n <= 65536, a large nn, or option "linscan_exhaustive" */
+       LSQ_KNN_PREFILTER_WIDE = 5 };           /* d > LSQ_KNN_PREFILTER_MAX_D */
+typedef struct lsq_knn_prefilter_info {
+    int64_t pairs;               /* (query, row) pairs the MFMA pass judged */
+    int64_t pending;             /* pairs it could not drop (a list stops counting soon after it overflows) */
+    int64_t kept;                /* pairs the recheck appended to the candidate lists: what the direct scan would have appended for these queries */
+    int64_t overflow_queries;    /* queries whose pending list overflowed: redone by the direct scan */
+    int64_t switched_off;        /* 1: more than half of a batch overflowed, the rest of the call ran with the pre-filter off */
+    int64_t served, reason;      /* served 1: the pre-filter ran; 0: the direct road, reason = LSQ_KNN_PREFILTER_* */
+    double kappa, eta;           /* the window's constants at this d (0 when not served) */
+    double norms_ms, mfma_ms, recheck_ms;      /* with option "profile" = 1 */
+} lsq_knn_prefilter_info;
+LSQ_API int lsq_knn_prefilter_bound(int d, float *kappa, float *eta);
+LSQ_API int lsq_index_get_knn_prefilter_info(lsq_index *ix, lsq_knn_prefilter_info *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

@@ -56,6 +56,16 @@ class IndexKnnInfo(_Struct):
                 ("int_road", C.c_int64), ("norms_ms", C.c_double), ("scan_ms", C.c_double), ("select_ms", C.c_double)]
 
 
+class KnnPrefilterInfo(_Struct):
+    _fields_ = [("pairs", C.c_int64), ("pending", C.c_int64), ("kept", C.c_int64), ("overflow_queries", C.c_int64), ("switched_off", C.c_int64),
+                ("served", C.c_int64), ("reason", C.c_int64), ("kappa", C.c_double), ("eta", C.c_double), ("norms_ms", C.c_double),
+                ("mfma_ms", C.c_double), ("recheck_ms", C.c_double)]
+
+
+# lsq_knn_prefilter_info.reason: why a call took the direct road (0: it did not)
+KNN_PREFILTER_NOT_ASKED, KNN_PREFILTER_FILTERED, KNN_PREFILTER_U8_QUERIES, KNN_PREFILTER_EXHAUSTIVE, KNN_PREFILTER_WIDE = 1, 2, 3, 4, 5
+
+
 class IndexStats(_Struct):
     _fields_ = [("queries", C.c_int64), ("rows", C.c_int64), ("invalid", C.c_int64), ("batches", C.c_int64),
                 ("scan_ms", C.c_double), ("gather_ms", C.c_double), ("select_ms", C.c_double)]
@@ -316,6 +326,9 @@ SIGNATURES = {
     "lsq_snapshot_read_cpu": (_i, [C.c_char_p, C.POINTER(SnapshotArrays)]),
     "lsq_snapshot_inspect_cpu": (_i, [C.c_char_p, C.POINTER(SnapshotInfo), _i]),
     "lsq_snapshot_digest_cpu": (_i, [_vp, _i64, _i64, C.POINTER(_u64)]),
+    # the MFMA pre-filter of exact k-NN (since v2700): its window, and what it did in the last knn call of an index
+    "lsq_knn_prefilter_bound": (_i, [_i, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "lsq_index_get_knn_prefilter_info": (_i, [_vp, C.POINTER(KnnPrefilterInfo)]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),
@@ -357,7 +370,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 2600     # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 2700     # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

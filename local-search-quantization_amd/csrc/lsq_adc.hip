@@ -478,15 +478,19 @@ struct lsq_adc_state {
     // staging of the host-buffer entry point: the database (code rows, or the base rows of an exact search), the queries, the tables, the norms, the results
     DevBuf h_db, h_q, h_tables, h_norms, h_dists, h_idx;
     PhaseClock<5> clock;                         // table, sample, scan, selection of one batch
+    // the pre-filter of exact k-NN (lsq_knnm.hip): the call's norms, a batch's pending lists and their counters; its norms / MFMA / recheck clock
+    DevBuf pf_nx, pf_nq, pf_pend, pf_pcount;
+    PhaseClock<3> pf_clock;
     bool attr_set = false;
 };
 
 void lsq_adc_free(lsq_adc_state *st) {
     if (!st) return;
     DevBuf *all[] = {&st->lut, &st->keys_a, &st->keys_b, &st->tau, &st->count, &st->seg, &st->fail, &st->qsel, &st->tmp,
-                  &st->h_db, &st->h_q, &st->h_tables, &st->h_norms, &st->h_dists, &st->h_idx};
+                  &st->h_db, &st->h_q, &st->h_tables, &st->h_norms, &st->h_dists, &st->h_idx, &st->pf_nx, &st->pf_nq, &st->pf_pend, &st->pf_pcount};
     for (DevBuf *b : all) b->release();
     st->clock.release();
+    st->pf_clock.release();
     delete st;
 }
 
@@ -560,9 +564,9 @@ int launch_scan(hipStream_t s, const float *LUT, const lsq_search_input &in, int
 // the scan of either producer: the table walk of adc_scan_kernel, or the exact distances of lsq_knn.hip (which reads the queries itself)
 template <int QT, int MODE>
 int launch_producer(hipStream_t s, const float *LUT, const lsq_search_input &in, const int *qsel, int q0, int nqb, int stride, int ns,
-                    const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits) {
+                    const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits, const lsq_knnm_work *pf = nullptr) {
     if (in.kind == LSQ_SEARCH_EXACT)
-        return lsq_knn_launch_scan(s, MODE, in, qsel, q0, nqb, stride, ns, tau, count, cap, out, idbits);
+        return lsq_knn_launch_scan(s, MODE, in, qsel, q0, nqb, stride, ns, tau, count, cap, out, idbits, pf);
     return launch_scan<QT, MODE>(s, LUT, in, nqb, stride, ns, tau, count, cap, out, idbits);
 }
 
@@ -618,6 +622,10 @@ namespace {
 
 struct Plan { int ns, stride, r, cap; bool exhaustive; };
 
+// the pre-filter of exact k-NN in one call (lsq_knnm.hip): its window, the pending capacity, where its counts go.  run_batch takes that road for a batch
+// whose input says prefilter (never a qsel pass) and reports the queries whose pending list overflowed as fail = LSQ_KNNM_FAIL_OVERFLOW
+struct PfRun { float kappa, eta; int pcap; lsq_knn_prefilter_info *info; bool timed; };
+
 // Threshold rank and list capacity.  The nn-th neighbour of a query has, among the ns sampled codes, a rank that is Binomial(ns, nn / n) ~ Poisson(ks),
 // ks = nn ns / n, on exchangeable data; the list misses it iff that rank reaches r.  r = ks + 5.6 sqrt(ks) + 6 puts this below ~1e-8 per query (small
 // ks: the Poisson tail, e.g. ks = 16.4, r = 45: 3e-9; large ks: 5.6 sigma), and the list then holds r n / ns entries on average (2.7 nn at
@@ -639,7 +647,7 @@ Plan make_plan(int n, int nn, int force_exhaustive) {
 
 template <int QT>
 int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const lsq_search_input &in, const int *qsel, int q0, int nqb, int nn,
-              const Plan &P, int *h_fail, lsq_linscan_stats *stats, bool timed) {
+              const Plan &P, int *h_fail, lsq_linscan_stats *stats, bool timed, const PfRun *pf = nullptr) {
     // n: the record slots of a query on the exhaustive road.  Under a filter's compact road the walk is over the allowed rows, padded to nn slots where
     // they are fewer; a filtered call sorts on one bit more, the bit of the record of an id outside the base (what filtered rows and padding leave as)
     const int n = in.filter_rows ? std::max(in.filter_count, nn) : in.n;
@@ -676,12 +684,39 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ls
         LSQ_HIP(hipMemsetAsync(st->count.p, 0, sizeof(unsigned) * (size_t)nqb, s));
         LSQ_TRY(st->clock.mark(s));
         // the scan proper
+        const bool pre = pf && in.prefilter && !qsel;
+        lsq_knnm_work w;
+        if (pre) {
+            LSQ_TRY(st->pf_pend.ensure(sizeof(uint32_t) * (size_t)nqb * (size_t)pf->pcap));
+            LSQ_TRY(st->pf_pcount.ensure(sizeof(unsigned) * (size_t)nqb));
+            w.nx = st->pf_nx.as<float>(); w.nq = st->pf_nq.as<float>(); w.pend = st->pf_pend.as<uint32_t>(); w.pcount = st->pf_pcount.as<unsigned>();
+            w.pcap = pf->pcap; w.kappa = pf->kappa; w.eta = pf->eta; w.clock = &st->pf_clock;
+            LSQ_TRY(st->pf_clock.begin(pf->timed));
+        }
         LSQ_TRY((launch_producer<QT, 0>(s, st->lut.as<float>(), in, qsel, q0, nqb, 1, n, st->tau.as<uint32_t>(), st->count.as<unsigned>(), P.cap,
-                                        st->keys_a.as<uint64_t>(), idbits)));
+                                        st->keys_a.as<uint64_t>(), idbits, pre ? &w : nullptr)));
         LSQ_TRY(st->clock.mark(s));
         LSQ_TRY(lsq_adc_select(&st, s, st->keys_a.as<uint64_t>(), st->keys_b.as<uint64_t>(), st->seg.as<int>(), st->count.as<unsigned>(),
                                st->fail.as<int>(), qsel, q0, nqb, P.cap, nn, dists, idx, idbits, end_bit, in.id_sub()));
+        if (pre) LSQ_TRY(lsq_knnm_launch_mark(s, w.pcount, w.pcap, st->fail.as<int>(), nqb));
         LSQ_HIP(hipMemcpyAsync(h_fail, st->fail.p, sizeof(int) * (size_t)nqb, hipMemcpyDeviceToHost, s));
+        if (pre) {
+            // what the pre-filter did: an overflowed list left count = 0, so `kept` (and `candidates` below) counts the served queries alone
+            std::vector<unsigned> hp((size_t)nqb), hc((size_t)nqb);
+            LSQ_HIP(hipMemcpyAsync(hp.data(), w.pcount, sizeof(unsigned) * (size_t)nqb, hipMemcpyDeviceToHost, s));
+            LSQ_HIP(hipMemcpyAsync(hc.data(), st->count.p, sizeof(unsigned) * (size_t)nqb, hipMemcpyDeviceToHost, s));
+            LSQ_HIP(hipStreamSynchronize(s));
+            lsq_knn_prefilter_info *fi = pf->info;
+            fi->pairs += (int64_t)nqb * n;
+            for (int t = 0; t < nqb; ++t) {
+                fi->pending += hp[(size_t)t];
+                fi->kept += hc[(size_t)t];
+                if (hp[(size_t)t] > (unsigned)w.pcap) fi->overflow_queries += 1;
+            }
+            float ms[2];
+            LSQ_TRY(st->pf_clock.read(ms));
+            fi->mfma_ms += ms[0]; fi->recheck_ms += ms[1];
+        }
         if (stats) {
             std::vector<unsigned> hc((size_t)nqb);
             LSQ_HIP(hipMemcpyAsync(hc.data(), st->count.p, sizeof(unsigned) * (size_t)nqb, hipMemcpyDeviceToHost, s));
@@ -718,20 +753,70 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
     }
     const bool wide = lsq_adc_lut_qt(in.m) == 16;    // 16 queries per block up to m = 8 (128 KiB of tables), 8 above
     const int64_t per_query = P.exhaustive ? slots : (P.cap > P.ns ? P.cap : P.ns);
-    int64_t qb = lsq_adc_batch_queries(per_query);   // two key buffers of per_query entries per query; whole tiles of 16 queries
+    // the pre-filter of exact k-NN (lsq_knnm.hip): MODE 0 of the thresholded road, f32 queries, no filter.  Everything else: the direct road, as before
+    lsq_search_input cur = in;                       // what the batches are given: `in` with the road decided
+    cur.prefilter = 0;
+    PfRun pf{};
+    if (in.kind == LSQ_SEARCH_EXACT && opt.pf_info) {
+        lsq_knn_prefilter_info *fi = opt.pf_info;
+        *fi = lsq_knn_prefilter_info{};
+        fi->reason = !in.prefilter ? LSQ_KNN_PREFILTER_NOT_ASKED : in.filtered() ? LSQ_KNN_PREFILTER_FILTERED : in.q_u8 ? LSQ_KNN_PREFILTER_U8_QUERIES
+                   : P.exhaustive ? LSQ_KNN_PREFILTER_EXHAUSTIVE : in.d > LSQ_KNN_PREFILTER_MAX_D ? LSQ_KNN_PREFILTER_WIDE : LSQ_KNN_PREFILTER_SERVED;
+        if (fi->reason == LSQ_KNN_PREFILTER_SERVED && nq > 0) {
+            LSQ_TRY(lsq_knn_prefilter_bound(in.d, &pf.kappa, &pf.eta));
+            // twice the list capacity: a third buffer of P.cap record-sized entries per query beside the two record buffers (the batch rule below)
+            const int64_t pcap = opt.prefilter_cap > 0 ? opt.prefilter_cap : 2 * (int64_t)P.cap;
+            pf.pcap = (int)std::min<int64_t>(pcap, n);
+            pf.info = fi; pf.timed = timed;
+            fi->served = 1; fi->kappa = pf.kappa; fi->eta = pf.eta;
+            cur.prefilter = 1;
+            LSQ_TRY(st->pf_nx.ensure(sizeof(float) * (size_t)n));
+            LSQ_TRY(st->pf_nq.ensure(sizeof(float) * (size_t)nq));
+            LSQ_TRY(st->pf_clock.begin(timed));
+            LSQ_TRY(st->pf_clock.mark(s));
+            LSQ_TRY(lsq_knnm_launch_norms(s, in, nq, st->pf_nx.as<float>(), st->pf_nq.as<float>()));
+            LSQ_TRY(st->pf_clock.mark(s));
+            float ms[2];
+            LSQ_TRY(st->pf_clock.read(ms));
+            fi->norms_ms = ms[0];
+        }
+    }
+    int64_t qb = lsq_adc_batch_queries(per_query + (cur.prefilter ? (pf.pcap + 1) / 2 : 0));   // two key buffers of per_query entries per query; whole tiles of 16 queries
     if (qb > 16) qb &= ~(int64_t)15;
     std::vector<int> h_fail;
-    std::vector<int> failed;
+    std::vector<int> failed, redo;
     for (int q0 = 0; q0 < nq; q0 += (int)qb) {
         const int nqb = (int)std::min<int64_t>(qb, nq - q0);
         h_fail.assign((size_t)nqb, 0);
-        if (wide) LSQ_TRY(run_batch<16>(st, s, dists, idx, in, nullptr, q0, nqb, nn, P, h_fail.data(), stats, timed));
-        else LSQ_TRY(run_batch<8>(st, s, dists, idx, in, nullptr, q0, nqb, nn, P, h_fail.data(), stats, timed));
+        if (wide) LSQ_TRY(run_batch<16>(st, s, dists, idx, cur, nullptr, q0, nqb, nn, P, h_fail.data(), stats, timed, &pf));
+        else LSQ_TRY(run_batch<8>(st, s, dists, idx, cur, nullptr, q0, nqb, nn, P, h_fail.data(), stats, timed, &pf));
         if (!P.exhaustive) {
             LSQ_HIP(hipStreamSynchronize(s));
-            for (int t = 0; t < nqb; ++t) if (h_fail[(size_t)t]) failed.push_back(q0 + t);
+            const size_t redo0 = redo.size();
+            for (int t = 0; t < nqb; ++t) {
+                if (h_fail[(size_t)t] == LSQ_KNNM_FAIL_OVERFLOW) redo.push_back(q0 + t);
+                else if (h_fail[(size_t)t]) failed.push_back(q0 + t);
+            }
+            // norms that dwarf the distances (a large common offset): the window passes everything.  One wasted MFMA pass, then the direct road
+            if (cur.prefilter && 2 * (redo.size() - redo0) > (size_t)nqb) { cur.prefilter = 0; pf.info->switched_off = 1; }
         }
         if (stats) stats->batches += 1;
+    }
+    if (!redo.empty()) {
+        // the direct scan, same plan, for the queries whose pending list overflowed; only their failures go on to the exhaustive road
+        cur.prefilter = 0;
+        LSQ_TRY(st->qsel.ensure(sizeof(int) * redo.size()));
+        LSQ_HIP(hipMemcpyAsync(st->qsel.p, redo.data(), sizeof(int) * redo.size(), hipMemcpyHostToDevice, s));
+        for (size_t f0 = 0; f0 < redo.size(); f0 += (size_t)qb) {
+            const int nqb = (int)std::min<size_t>((size_t)qb, redo.size() - f0);
+            const int *qs = st->qsel.as<int>() + f0;
+            h_fail.assign((size_t)nqb, 0);
+            if (wide) LSQ_TRY(run_batch<16>(st, s, dists, idx, cur, qs, 0, nqb, nn, P, h_fail.data(), stats, timed));
+            else LSQ_TRY(run_batch<8>(st, s, dists, idx, cur, qs, 0, nqb, nn, P, h_fail.data(), stats, timed));
+            LSQ_HIP(hipStreamSynchronize(s));
+            for (int t = 0; t < nqb; ++t) if (h_fail[(size_t)t]) failed.push_back(redo[f0 + (size_t)t]);
+            if (stats) stats->batches += 1;
+        }
     }
     if (!failed.empty()) {
         // the exhaustive road for the queries whose candidate list came out short or overflowed

@@ -110,6 +110,8 @@ struct lsq_ctx {
     lsq_linscan_stats adc_stats{};
     lsq_search_opts search;                            // options "linscan_exhaustive", "linscan_rank": test hooks of the scan's selection (search_opts fills in the rest per call)
     int knn_u8_int = 1;                                // option "knn_u8_int": 0 = lsq_index_knn widens 8-bit rows and queries even where the integer road applies; a test hook
+    int knn_prefilter = 0, knn_prefilter_cap = 0;      // options "knn_prefilter" (exact k-NN pre-filters the thresholded road on the matrix cores: lsq_knnm.hip) and "knn_prefilter_cap" (its pending capacity; a test hook)
+    lsq_knn_prefilter_info knn_pf{};                   // ... where the account of the last lsq_knn_exact / lsq_knn_exact_dev call is written (no getter yet: DESIGN 4.29)
     int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
     int64_t range_batch = 0;                           // option "range_batch": records per fill batch of lsq_index_range_search (0 = automatic); a test hook
     int64_t recon_chunk = 0;                           // option "recon_chunk": rows per staging chunk of a host-buffer lsq_index_reconstruct (0 = automatic); a test hook
@@ -318,6 +320,11 @@ extern "C" int lsq_set_option(lsq_ctx *c, const char *key, int64_t value) {
         c->search.rank_override = (int)value;
     }
     else if (!strcmp(key, "knn_u8_int")) c->knn_u8_int = value != 0;
+    else if (!strcmp(key, "knn_prefilter")) c->knn_prefilter = value != 0;
+    else if (!strcmp(key, "knn_prefilter_cap")) {
+        if (value < 0 || value > (int64_t)INT32_MAX) { lsq_set_error("knn_prefilter_cap must lie in 0..2^31-1"); return LSQ_EINVAL; }
+        c->knn_prefilter_cap = (int)value;
+    }
     else if (!strcmp(key, "rerank_batch")) {
         if (value < 0) { lsq_set_error("rerank_batch must be >= 0"); return LSQ_EINVAL; }
         c->rerank_batch = value;
@@ -461,6 +468,13 @@ static lsq_search_opts search_opts(const lsq_ctx *c, lsq_linscan_stats *stats) {
     o.timed = c->profile;
     return o;
 }
+// an exact search: the context's pre-filter options as well (lsq_knnm.hip), and where the call's account of it goes
+static lsq_search_opts exact_opts(const lsq_ctx *c, lsq_linscan_stats *stats, lsq_knn_prefilter_info *pf) {
+    lsq_search_opts o = search_opts(c, stats);
+    o.prefilter_cap = c->knn_prefilter_cap;
+    o.pf_info = pf;
+    return o;
+}
 
 // the three kinds of search (lsq_search_input); the pointers are all device pointers or all host pointers
 static lsq_search_input lsq_input(const uint8_t *codes, const float *Q, const float *K, const float *dbnorms, int n, int m, int d) {
@@ -534,8 +548,9 @@ extern "C" int lsq_knn_exact_dev(lsq_ctx *c, float *d_dists, uint32_t *d_ids, co
     if (!c) { lsq_set_error("lsq_knn_exact_dev: null context"); return LSQ_EINVAL; }
     LSQ_TRY(lsq_knn_exact_check("lsq_knn_exact_dev", d_dists, d_ids, d_base, d_queries, n, nq, d, ldb, ldq, nn));
     LSQ_TRY(use_device(c));
-    return lsq_adc_search(c->stream, &c->adc, d_dists, reinterpret_cast<int *>(d_ids), exact_input(d_base, 0, ldb, d_queries, 0, ldq, n, d), nq, nn,
-                          search_opts(c, &c->adc_stats));
+    lsq_search_input in = exact_input(d_base, 0, ldb, d_queries, 0, ldq, n, d);
+    in.prefilter = c->knn_prefilter;
+    return lsq_adc_search(c->stream, &c->adc, d_dists, reinterpret_cast<int *>(d_ids), in, nq, nn, exact_opts(c, &c->adc_stats, &c->knn_pf));
 }
 
 extern "C" int lsq_knn_exact(lsq_ctx *c, float *dists, uint32_t *ids, const float *base, const float *queries, int n, int nq, int d, int ldb, int ldq,
@@ -543,8 +558,9 @@ extern "C" int lsq_knn_exact(lsq_ctx *c, float *dists, uint32_t *ids, const floa
     if (!c) { lsq_set_error("lsq_knn_exact: null context"); return LSQ_EINVAL; }
     LSQ_TRY(lsq_knn_exact_check("lsq_knn_exact", dists, ids, base, queries, n, nq, d, ldb, ldq, nn));
     LSQ_TRY(use_device(c));
-    return lsq_adc_search_host(c->stream, &c->adc, dists, reinterpret_cast<int *>(ids), exact_input(base, 0, ldb, queries, 0, ldq, n, d), nq, nn,
-                               search_opts(c, &c->adc_stats));
+    lsq_search_input in = exact_input(base, 0, ldb, queries, 0, ldq, n, d);
+    in.prefilter = c->knn_prefilter;
+    return lsq_adc_search_host(c->stream, &c->adc, dists, reinterpret_cast<int *>(ids), in, nq, nn, exact_opts(c, &c->adc_stats, &c->knn_pf));
 }
 
 extern "C" int lsq_get_linscan_stats(lsq_ctx *c, lsq_linscan_stats *out) {
@@ -576,6 +592,7 @@ struct lsq_index {
     PhaseClock<3> clock;                               // a re-rank batch's gather and selection; lsq_index_knn's norm pass
     lsq_index_stats stats{};
     lsq_index_knn_info knn{};
+    lsq_knn_prefilter_info knn_pf{};                   // what the pre-filter (option "knn_prefilter" of the context; lsq_knnm.hip) did in the last lsq_index_knn
     lsq_filter_state *filter = nullptr;                // the row filter (lsq_filter.hip): null until lsq_index_set_filter; owned copies of THIS index
     int64_t cap_rows = 0;                              // lsq_index_add: rows the flat arrays hold without another allocation (n until the first add / reserve)
     lsq_index_growth_info grow{};
@@ -956,6 +973,7 @@ extern "C" int lsq_index_knn(lsq_index *ix, float *dists, int *ids, const void *
     LSQ_TRY(call.outputs(dists, ids, nn));
     lsq_search_input in = exact_input(ix->base, ix->base_u8, (int)ix->ldb, dq, q_u8, ldq, n, d);
     in.id_base = id_base;
+    in.prefilter = c->knn_prefilter;
     const bool int_road = ix->base_u8 == 1 && q_u8 && d <= 258 && c->knn_u8_int;      // d 255^2 <= 2^24: (float)D is the chain's result
     lsq_index_knn_info info{};
     if (int_road) {
@@ -977,7 +995,7 @@ extern "C" int lsq_index_knn(lsq_index *ix, float *dists, int *ids, const void *
     int road = 0;
     index_apply_filter(ix, &in, &road, 8);
     lsq_filter_note_road(ix->filter, road);
-    LSQ_TRY(lsq_adc_search(s, &ix->adc, call.out_d, call.out_i, in, nq, nn, search_opts(c, &st)));
+    LSQ_TRY(lsq_adc_search(s, &ix->adc, call.out_d, call.out_i, in, nq, nn, exact_opts(c, &st, &ix->knn_pf)));
     LSQ_TRY(call.finish());
     info.queries = nq; info.rows = n; info.batches = st.batches; info.fallback_queries = st.fallback_queries; info.exhaustive = st.exhaustive;
     info.int_road = int_road ? 1 : 0;
@@ -989,6 +1007,12 @@ extern "C" int lsq_index_knn(lsq_index *ix, float *dists, int *ids, const void *
 extern "C" int lsq_index_get_knn_info(lsq_index *ix, lsq_index_knn_info *out) {
     if (!ix || !out) { lsq_set_error("lsq_index_get_knn_info: null argument"); return LSQ_EINVAL; }
     *out = ix->knn;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_knn_prefilter_info(lsq_index *ix, lsq_knn_prefilter_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_knn_prefilter_info: null argument"); return LSQ_EINVAL; }
+    *out = ix->knn_pf;
     return LSQ_OK;
 }
 

@@ -338,6 +338,7 @@ struct lsq_search_input {
     const uint32_t *filter_bits = nullptr;
     const int *filter_rows = nullptr;
     int filter_count = 0;
+    int prefilter = 0;                       // exact: option "knn_prefilter" -- MODE 0 of the thresholded road may run on the matrix cores (lsq_knnm.hip); lsq_adc_search decides
     bool filtered() const { return filter_bits != nullptr || filter_rows != nullptr; }
     int rows_walked() const { return filter_rows ? filter_count : n; }      // rows a full scan reads
     int query_width() const { return kind == LSQ_SEARCH_PQ ? m * d : d; }      // elements of a query row that are read
@@ -351,14 +352,32 @@ struct lsq_search_opts {
     int force_exhaustive = 0, rank_override = 0;
     lsq_linscan_stats *stats = nullptr;
     int timed = 0;
+    int prefilter_cap = 0;                   // option "knn_prefilter_cap": the pending capacity of the pre-filter (0 = twice the list capacity); a test hook
+    lsq_knn_prefilter_info *pf_info = nullptr;      // exact searches: what the pre-filter did in this call (always written when set)
 };
 // every pointer of `in` a device pointer / a host pointer (staged: upload, search, download); dists, idx [nq][nn] likewise
 int lsq_adc_search(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const lsq_search_input &in, int nq, int nn, const lsq_search_opts &opt);
 int lsq_adc_search_host(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const lsq_search_input &in, int nq, int nn, const lsq_search_opts &opt);
 // the exact scan of one batch in adc_scan_kernel's three modes (0: against tau, 1: every record, 2: sample keys); qsel optional.  Routes on in's element
 // types and norms (lsq_knn.hip)
+// pf (optional): with in.prefilter, MODE 0 and no qsel the batch takes the pre-filtered road (lsq_knnm.hip) -- the same records in the same lists
+struct lsq_knnm_work;
 int lsq_knn_launch_scan(hipStream_t s, int mode, const lsq_search_input &in, const int *qsel, int q0, int nqb, int stride, int ns, const uint32_t *tau,
-                        unsigned *count, int cap, uint64_t *out, int idbits);
+                        unsigned *count, int cap, uint64_t *out, int idbits, const lsq_knnm_work *pf = nullptr);
+// ---- the MFMA pre-filter of exact k-NN (lsq_knnm.hip).  nx [n] / nq [queries of the CALL]: the squared norms (lsq_knnm_launch_norms); pend
+// [nqb][pcap] row ids and pcount [nqb] (zeroed by the launch): the pending lists of the batch; clock (optional): marked before the MFMA pass, between it and
+// the recheck, and after
+struct lsq_knnm_work {
+    const float *nx = nullptr, *nq = nullptr;
+    uint32_t *pend = nullptr; unsigned *pcount = nullptr; int pcap = 0;
+    float kappa = 0.0f, eta = 0.0f;
+    PhaseClock<3> *clock = nullptr;
+};
+enum { LSQ_KNNM_FAIL_OVERFLOW = 2 };      // fail[slot] of a query whose pending list overflowed (1: the selection's own verdict on its candidate list)
+int lsq_knnm_launch_norms(hipStream_t s, const lsq_search_input &in, int nq, float *nx, float *nqv);
+int lsq_knnm_launch(hipStream_t s, const lsq_search_input &in, int q0, int nqb, const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits,
+                    const lsq_knnm_work &w);
+int lsq_knnm_launch_mark(hipStream_t s, const unsigned *pcount, int pcap, int *fail, int nqb);
 int lsq_knn_launch_norms_u8(hipStream_t s, const uint8_t *X, int64_t ld, int n, int d, uint32_t *out);
 // argument checks of exact k-NN (lsq_linscan.hip), shared by the host drop-in and the device search
 int lsq_knn_exact_check(const char *fn, const void *dists, const void *ids, const void *base, const void *queries, int n, int nq, int d, int ldb,

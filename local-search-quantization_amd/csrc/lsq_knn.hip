@@ -362,7 +362,8 @@ int lsq_knn_launch_norms_u8(hipStream_t s, const uint8_t *X, int64_t ld, int n, 
 // The scan of one batch for adc_search's "exact" input kind.  MODE 0: rows 0 .. n-1 against tau; MODE 1 / 2: rows s * stride, s < ns.  The producer is
 // chosen by what `in` says its rows and queries are made of: the integer road when it carries norms, a widened instantiation otherwise.
 int lsq_knn_launch_scan(hipStream_t s, int mode, const lsq_search_input &in, const int *qsel, int q0, int nqb, int stride, int ns, const uint32_t *tau,
-                        unsigned *count, int cap, uint64_t *out, int idbits) {
+                        unsigned *count, int cap, uint64_t *out, int idbits, const lsq_knnm_work *pf) {
+    if (mode == 0 && in.prefilter && pf && !qsel) return lsq_knnm_launch(s, in, q0, nqb, tau, count, cap, out, idbits, *pf);      // (f32 queries, no filter: lsq_adc_search)
     const int n = in.rows_walked(), d = in.d, ldb = in.bstride, ldq = in.qstride;      // compact road of a filter: the allowed rows
     const int tiles = (nqb + KNN_QT - 1) / KNN_QT;
     const int total = mode == 0 ? n : ns;

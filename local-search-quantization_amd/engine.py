@@ -946,6 +946,11 @@ class Index(_Handle):
         tail_capacity, coarse_ms / lut_ms / scan_ms / select_ms (with profile=True)"""
         return self._info("lsq_index_get_ivf_info", _lib.IvfInfo)
 
+    def knn_prefilter_info(self):
+        """what the MFMA pre-filter (Engine.set_option("knn_prefilter", 1)) did in the last knn call of this index: pairs, pending, kept, overflow_queries,
+        switched_off, served / reason (why the direct road was taken), kappa, eta, norms_ms / mfma_ms / recheck_ms (with profile=True)"""
+        return self._info("lsq_index_get_knn_prefilter_info", _lib.KnnPrefilterInfo)
+
     def knn_info(self):
         """what the last knn call did: queries, rows, batches, fallback_queries, exhaustive, int_road, norms_ms / scan_ms / select_ms (with profile=True)"""
         return self._info("lsq_index_get_knn_info", _lib.IndexKnnInfo)

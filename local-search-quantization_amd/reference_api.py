@@ -277,12 +277,23 @@ def linscan_opq(B, X, C, b, R, k=10000, *, engine=None):
     return linscan_pq(B, RX, C, b, k, engine=engine)
 
 
-def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0):
+def knn_prefilter_bound(d):
+    """-> (kappa_d, eta_d) float32: the window of the MFMA pre-filter of exact k-NN at width d (lsq_knn_prefilter_bound): the pre-filter's expanded-form
+    value a and the direct chain's distance differ by at most kappa_d (|x|^2 + |q|^2) + eta_d, the norms as computed in f32."""
+    from . import _lib
+    kappa, eta = C.c_float(), C.c_float()
+    _lib.check(_lib.load().lsq_knn_prefilter_bound(int(d), C.byref(kappa), C.byref(eta)))
+    return np.float32(kappa.value), np.float32(eta.value)
+
+
+def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0, prefilter=False):
     """Exact k-NN, the ground truth of a recall figure (what the reference reads from sift_groundtruth.ivecs, for any base).
     X_base (d, n), X_query (d, nq) Float32 in Julia shapes, or the UInt8 matrices of bvecs_read, which are handed through un-widened (same results as
     after astype(float32), by contract).  -> dists (k, nq) float32 ascending, ids (k, nq) uint32 1-BASED, so that eval_recall(ids[0, :], idx, knn) works
     directly.  dist = ((0 + e_0^2) + e_1^2) + ..., e_s = x[s] - q[s] in f32; ties by smaller id, NaN last.
-    engine=None: the host cores (lsq_knn_exact_cpu / lsq_knn_exact_u8_cpu, nthreads 0 = all); engine=<Engine>: the device -- same results bit for bit."""
+    engine=None: the host cores (lsq_knn_exact_cpu / lsq_knn_exact_u8_cpu, nthreads 0 = all); engine=<Engine>: the device -- same results bit for bit.
+    prefilter=True (device only): the engine's option "knn_prefilter" is 1 for this call and 0 after it -- the MFMA pre-filter, same results bit for bit;
+    prefilter=False leaves the option as the engine has it."""
     from . import _lib
     Xb, Xq = _base_rows(X_base), _base_rows(X_query)
     if Xb.shape[1] != Xq.shape[1]:
@@ -290,8 +301,16 @@ def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0):
     b8, q8 = Xb.dtype == np.uint8, Xq.dtype == np.uint8
     if q8 and not b8:
         Xq, q8 = Xq.astype(np.float32), False
+    if prefilter and engine is None:
+        raise ValueError("knn_exact: prefilter=True needs an engine (the pre-filter runs on the device)")
     if engine is not None:
-        dists, ids = engine.knn_exact(Xb, Xq, k)
+        if prefilter:
+            engine.set_option("knn_prefilter", 1)
+        try:
+            dists, ids = engine.knn_exact(Xb, Xq, k)
+        finally:
+            if prefilter:
+                engine.set_option("knn_prefilter", 0)
     else:
         (n, d), nq = Xb.shape, Xq.shape[0]
         dists = np.zeros((nq, k), dtype=np.float32)

@@ -58,6 +58,9 @@ neighbour's distance.  The mean, minimum and maximum result counts are printed; 
 over the probed lists returns (it can only miss rows: its distances are the same bits); with --filter the counts under the mask.  The reference has no such
 search.
 
+--knn-prefilter: the ground truth (exact k-NN on the device) runs with option "knn_prefilter" = 1 -- the MFMA pre-filter of csrc/lsq_knnm.hip, the same
+ids bit for bit (Index.knn_prefilter_info gives its account on a resident index).
+
 needs $LSQ_DATA_DIR/sift/{sift_learn,sift_base,sift_query}.fvecs and sift_groundtruth.ivecs (TEXMEX layout).  The file's ground truth
 describes the full 10^6-vector base only: for a prefix of it (nread_base < 10^6) and for the stand-in, the ground truth is exact k-NN of the base
 actually encoded, computed on the device (knn_exact).  The data is
@@ -75,11 +78,14 @@ sys.path.insert(0, ROOT)
 lsq = importlib.import_module("local-search-quantization_amd")
 
 
+KNN_PREFILTER = False      # --knn-prefilter
+
+
 def ground_truth(xb, xq):
     """1-based id of each query's nearest base vector: exact k-NN on the device (lsq_knn_exact; uint8 matrices stay uint8: lsq_index_knn)"""
     t0 = time.perf_counter()
     with lsq.Engine(0) as eng:
-        _, ids = lsq.knn_exact(xb, xq, 1, engine=eng)
+        _, ids = lsq.knn_exact(xb, xq, 1, engine=eng, prefilter=KNN_PREFILTER)
     print("Ground truth of %d queries in %d base vectors: %.3f s (exact k-NN on the device, %s rows)" % (xq.shape[1], xb.shape[1], time.perf_counter() - t0,
                                                                                                        xb.dtype))
     return ids[0]
@@ -219,8 +225,11 @@ BASE_FORMAT = None                               # --base-format f16 | bf16 (wit
 
 
 def main():
-    global BASE_FORMAT
+    global BASE_FORMAT, KNN_PREFILTER
     argv = sys.argv[1:]
+    if "--knn-prefilter" in argv:
+        argv.remove("--knn-prefilter")
+        KNN_PREFILTER = True
     if "--base-format" in argv:
         at = argv.index("--base-format")
         BASE_FORMAT = argv[at + 1]

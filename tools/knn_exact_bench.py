@@ -10,6 +10,13 @@ Every leg's result is compared with (a)'s, bits and ids.  Exit status 1 when (c)
 (a)'s own repeats.  R: the dot4 lane-op rate tools/ubench_dot4.hip printed ("dot4_lane_ops_per_s"); with it (c)'s scan is given as a fraction of the bound
 nq n d / 4 / R.
 
+--prefilter [n nq] [--out PATH]: the MFMA pre-filter (option "knn_prefilter", csrc/lsq_knnm.hip) against the direct call, alternated in one process on one
+resident base (Index.knn), device events, one warm-up, medians of 5: Gaussian rows at d = 128 and d = 960 as f32 and as f16, k in {1, 100, 1000}, and one
+offset set (x + 1000, d = 128, f32, k = 100) whose norms dwarf its distances, to show what a switched-off call costs.  One JSON line per case, appended to
+PATH (default profiles/knn_prefilter.jsonl): the ratio direct / pre-filtered, the MFMA pass as a fraction of its bound 2 nq n d / 157 TF, pending / kept, and
+whether bits and ids equal the direct leg's.  Exit status 1 when they differ anywhere, or when on a Gaussian set the pre-filtered call is not faster than
+the direct one by more than the spread of the direct leg's five repeats.
+
 VALU bound: three f32 element-ops (subtract, multiply, add) per (query, row, dimension), at 32 element-ops/clk/SIMD (packed f32), 4 SIMDs x 256 CUs,
 2.4 GHz: 7.86e13 element-ops/s."""
 import importlib, json, os, sys, time
@@ -117,7 +124,66 @@ def run_u8(n, nq, d, dot4_rate=None, reps=5):
     return ok
 
 
+MFMA_FLOPS = 157e12                          # f32 matrix-core peak
+
+
+def run_prefilter(n, nq, out_path, reps=5):
+    dev = torch.device("cuda:0")
+    ok = True
+    lines = []
+    for d, fmt, offset, ks in [(128, "f32", 0, (1, 100, 1000)), (128, "f16", 0, (1, 100, 1000)), (960, "f32", 0, (1, 100, 1000)),
+                               (960, "f16", 0, (1, 100, 1000)), (128, "f32", 1000, (100,))]:
+        g = torch.Generator(device=dev).manual_seed(2700 + d)
+        rows = torch.randn((n, d), generator=g, device=dev) + offset
+        Q = torch.randn((nq, d), generator=g, device=dev) + offset
+        if fmt == "f16":
+            rows = rows.half()
+        with lsq.Engine(0, profile=True) as eng, eng.index_dev(None, None, None, 0, base=rows) as ix:
+            def leg(pre, k):
+                eng.set_option("knn_prefilter", pre)
+                return ix.knn(Q, k)
+            for k in ks:
+                ms, acct = {0: [], 1: []}, {}
+                same = True
+                for r in range(reps + 1):                           # repeat 0 is the warm-up
+                    res = {}
+                    for pre in (0, 1):
+                        t, res[pre] = _timed(lambda: leg(pre, k))
+                        if r > 0:
+                            ms[pre].append(t)
+                        acct[pre] = (ix.knn_info(), ix.knn_prefilter_info())
+                    same = same and torch.equal(res[0][0].view(torch.int32), res[1][0].view(torch.int32)) and torch.equal(res[0][1], res[1][1])
+                med = {pre: float(np.median(v)) for pre, v in ms.items()}
+                spread = max(ms[0]) - min(ms[0])
+                faster = med[0] - med[1] > spread
+                ok = ok and same and (faster or offset != 0)
+                pf = acct[1][1]
+                bound_ms = 2.0 * nq * n * d / MFMA_FLOPS * 1e3
+                lines.append(json.dumps(dict(
+                    search="knn_prefilter", n=n, nq=nq, d=d, k=k, rows=fmt, offset=offset, reps=reps, direct_ms=round(med[0], 3), prefilter_ms=round(med[1], 3),
+                    direct_spread_ms=round(spread, 3), direct_over_prefilter=round(med[0] / med[1], 3), faster_beyond_spread=faster, same_bits_and_ids=same,
+                    direct_scan_ms=round(acct[0][0]["scan_ms"], 3), prefilter_scan_ms=round(acct[1][0]["scan_ms"], 3), norms_ms=round(pf["norms_ms"], 3),
+                    mfma_ms=round(pf["mfma_ms"], 3), recheck_ms=round(pf["recheck_ms"], 3), mfma_bound_ms=round(bound_ms, 3),
+                    mfma_fraction_of_bound=round(bound_ms / pf["mfma_ms"], 3) if pf["mfma_ms"] > 0 else None, pairs=pf["pairs"], pending=pf["pending"],
+                    kept=pf["kept"], pending_over_kept=round(pf["pending"] / pf["kept"], 4) if pf["kept"] else None, overflow_queries=pf["overflow_queries"],
+                    switched_off=pf["switched_off"], served=pf["served"], kappa=pf["kappa"], fallback_queries=acct[1][0]["fallback_queries"])))
+                print(lines[-1], flush=True)
+        del rows, Q
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write("\n".join(lines) + "\n")
+    return ok
+
+
 if __name__ == "__main__":
+    if "--prefilter" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--prefilter"]
+        out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "knn_prefilter.jsonl")
+        if "--out" in args:
+            i = args.index("--out")
+            out = args[i + 1]
+            del args[i:i + 2]
+        sys.exit(0 if run_prefilter(*(int(x) for x in (args[:2] + ["1000000", "10000"][len(args):])), out_path=out) else 1)
     if "--u8" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--u8"]
         rate = None
