@@ -628,11 +628,45 @@ static void index_apply_filter(lsq_index *ix, lsq_search_input *in, int *road, i
     *road = compact ? 2 : 1;
 }
 
+// The per-row arrays of an index (lsq_grow_check.h: their pitch, width and slack), each with the pointer every search path reads and the buffer that owns the
+// rows unless the caller does.  Whatever allocates, sizes, moves or frees them walks this table
+struct IndexArray {
+    int kind;
+    const void **reader;
+    DevBuf *own;
+    lsq_rows_desc rows;
+    bool borrowed() const { return *reader != own->p; }
+    void repoint() const { *reader = own->p; }                                   // after anything that moved or replaced the owned storage
+    void commit(DevBuf &fresh) const { std::swap(*own, fresh); repoint(); }      // fresh storage in force; `fresh` leaves with the former
+};
+struct IndexArrays {
+    lsq_rows_desc rows[LSQ_ROWS_KINDS];                // by kind; pitch 0: absent
+    IndexArray a[LSQ_ROWS_KINDS];                      // the present ones, in the order codes, norms, base
+    int count = 0;
+    IndexArray *begin() { return a; }
+    IndexArray *end() { return a + count; }
+    IndexArray *find(int kind) { for (IndexArray &x : *this) if (x.kind == kind) return &x; return nullptr; }
+};
+static IndexArray index_array(lsq_index *ix, int kind, const lsq_rows_desc &rows) {
+    if (kind == LSQ_ROWS_CODES) return {kind, reinterpret_cast<const void **>(&ix->codes), &ix->own_codes, rows};
+    if (kind == LSQ_ROWS_NORMS) return {kind, reinterpret_cast<const void **>(&ix->norms), &ix->own_norms, rows};
+    return {kind, &ix->base, &ix->own_base, rows};
+}
+// the arrays of the index's shape (m, packed, d, ldb, base_u8); has_codes / has_base: those of an index under construction, whose pointers are not set yet
+static IndexArrays index_arrays(lsq_index *ix, bool has_codes, bool has_base) {
+    IndexArrays t;
+    lsq_rows_describe(has_codes, ix->packed != 0, ix->m, has_base, ix->d, ix->ldb, ix->base_u8, t.rows);
+    for (int kind = 0; kind < LSQ_ROWS_KINDS; ++kind) if (t.rows[kind].pitch) t.a[t.count++] = index_array(ix, kind, t.rows[kind]);
+    return t;
+}
+static IndexArrays index_arrays(lsq_index *ix) { return index_arrays(ix, ix->codes != nullptr, ix->base != nullptr); }
+
 extern "C" int lsq_index_destroy(lsq_index *ix) {
     if (!ix) return LSQ_OK;
     (void)hipSetDevice(ix->ctx->device);
     (void)hipStreamSynchronize(ix->ctx->stream);
-    DevBuf *bufs[] = {&ix->own_codes, &ix->own_K, &ix->own_norms, &ix->own_base, &ix->rec_a, &ix->rec_b, &ix->seg, &ix->counter, &ix->short_d, &ix->short_i,
+    for (int kind = 0; kind < LSQ_ROWS_KINDS; ++kind) index_array(ix, kind, lsq_rows_desc{}).own->release();      // (own_norms of a packed index: the norm table)
+    DevBuf *bufs[] = {&ix->own_K, &ix->rec_a, &ix->rec_b, &ix->seg, &ix->counter, &ix->short_d, &ix->short_i,
                       &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q, &ix->s_qcoarse, &ix->g_codes, &ix->g_nc, &ix->g_rows,
                       &ix->c_old, &ix->c_new, &ix->s_radius, &ix->r_lor, &ix->r_ids, &ix->r_out, &ix->r_q, &ix->h_counts};
     for (DevBuf *b : bufs) b->release();
@@ -657,37 +691,36 @@ static int index_adopt(lsq_index *ix, DevBuf &own, const void *src, size_t bytes
     return LSQ_OK;
 }
 
+// the argument checks both creates make; own(): those of one create that come between the code bounds and the base's
+static int index_create_check(const char *fn, int64_t n, int d, bool codes, int h, int m, const void *base, int ldb, int base_u8, const std::function<int()> &own) {
+    if (n < 1 || n > LSQ_GROW_MAX_ROWS || d < 1) { lsq_set_error("%s: needs 1 <= n <= 2^31 - 2 and d >= 1 (got n=%lld d=%d)", fn, (long long)n, d); return LSQ_EINVAL; }
+    if (codes && (h != LSQ_H || m < 1 || m > LSQ_MAX_M)) { lsq_set_error("%s: needs h == 256 and 1 <= m <= 16 (got h=%d m=%d)", fn, h, m); return LSQ_EINVAL; }
+    LSQ_TRY(own());
+    if (base && ldb < d) { lsq_set_error("%s: needs ldb >= d (got ldb=%d d=%d)", fn, ldb, d); return LSQ_EINVAL; }
+    if (base) if (const char *why = lsq_base_align_refusal(lsq_base_format(base_u8), base)) { lsq_set_error("%s: %s", fn, why); return LSQ_EINVAL; }
+    return LSQ_OK;
+}
+
 extern "C" int lsq_index_create(lsq_index **out, lsq_ctx *c, const lsq_index_desc *desc) {
-    if (!out) { lsq_set_error("lsq_index_create: null out pointer"); return LSQ_EINVAL; }
+    const char *fn = "lsq_index_create";
+    if (!out) { lsq_set_error("%s: null out pointer", fn); return LSQ_EINVAL; }
     *out = nullptr;
-    if (!c || !desc) { lsq_set_error("lsq_index_create: null %s", c ? "description" : "context"); return LSQ_EINVAL; }
-    if (!desc->codes && !desc->base) { lsq_set_error("lsq_index_create: neither codes nor base rows"); return LSQ_EINVAL; }
-    if (desc->n < 1 || desc->n > (int64_t)INT32_MAX - 1 || desc->d < 1) {
-        lsq_set_error("lsq_index_create: needs 1 <= n <= 2^31 - 2 and d >= 1 (got n=%lld d=%d)", (long long)desc->n, desc->d);
-        return LSQ_EINVAL;
-    }
-    if (desc->codes) {
-        if (desc->h != LSQ_H || desc->m < 1 || desc->m > LSQ_MAX_M) {
-            lsq_set_error("lsq_index_create: needs h == 256 and 1 <= m <= 16 (got h=%d m=%d)", desc->h, desc->m);
-            return LSQ_EINVAL;
-        }
-        if (!desc->codebooks || !desc->dbnorms) { lsq_set_error("lsq_index_create: codes without codebooks or dbnorms"); return LSQ_EINVAL; }
-    }
-    if (desc->base && desc->ldb < desc->d) { lsq_set_error("lsq_index_create: needs ldb >= d (got ldb=%d d=%d)", desc->ldb, desc->d); return LSQ_EINVAL; }
-    if (desc->base) if (const char *why = lsq_base_align_refusal(lsq_base_format(desc->base_u8), desc->base)) { lsq_set_error("lsq_index_create: %s", why); return LSQ_EINVAL; }
+    if (!c || !desc) { lsq_set_error("%s: null %s", fn, c ? "description" : "context"); return LSQ_EINVAL; }
+    if (!desc->codes && !desc->base) { lsq_set_error("%s: neither codes nor base rows", fn); return LSQ_EINVAL; }
+    LSQ_TRY(index_create_check(fn, desc->n, desc->d, desc->codes != nullptr, desc->h, desc->m, desc->base, desc->ldb, desc->base_u8, [&]() -> int {
+        if (desc->codes && (!desc->codebooks || !desc->dbnorms)) { lsq_set_error("%s: codes without codebooks or dbnorms", fn); return LSQ_EINVAL; }
+        return LSQ_OK;
+    }));
     LSQ_TRY(use_device(c));
     lsq_index *ix = new lsq_index();
     ix->ctx = c;
     ix->n = desc->n; ix->d = desc->d; ix->m = desc->codes ? desc->m : 0; ix->base_u8 = lsq_base_format(desc->base_u8); ix->ldb = desc->ldb;
-    const size_t n = (size_t)desc->n, d = (size_t)desc->d;
+    const void *src[LSQ_ROWS_KINDS] = {desc->codes, desc->dbnorms, desc->base};
     int rc = LSQ_OK;
-    if (desc->codes) {
-        rc = index_adopt(ix, ix->own_codes, desc->codes, n * (size_t)desc->m, desc->on_device, reinterpret_cast<const void **>(&ix->codes));
-        if (rc == LSQ_OK) rc = index_adopt(ix, ix->own_K, desc->codebooks, sizeof(float) * (size_t)desc->m * LSQ_H * d, desc->on_device, reinterpret_cast<const void **>(&ix->K));
-        if (rc == LSQ_OK) rc = index_adopt(ix, ix->own_norms, desc->dbnorms, sizeof(float) * n, desc->on_device, reinterpret_cast<const void **>(&ix->norms));
-    }
-    if (rc == LSQ_OK && desc->base)      // rows up to the d-th element of the last one
-        rc = index_adopt(ix, ix->own_base, desc->base, ((n - 1) * (size_t)desc->ldb + d) * lsq_base_elem_bytes(ix->base_u8), desc->on_device, &ix->base);
+    for (IndexArray &a : index_arrays(ix, desc->codes != nullptr, desc->base != nullptr))
+        if (rc == LSQ_OK) rc = index_adopt(ix, *a.own, src[a.kind], a.rows.bytes_used(ix->n), desc->on_device, a.reader);
+    if (rc == LSQ_OK && desc->codes)
+        rc = index_adopt(ix, ix->own_K, desc->codebooks, sizeof(float) * (size_t)desc->m * LSQ_H * (size_t)desc->d, desc->on_device, reinterpret_cast<const void **>(&ix->K));
     if (rc == LSQ_OK) rc = ix->counter.ensure(sizeof(unsigned long long));
     if (rc == LSQ_OK && hipStreamSynchronize(c->stream) != hipSuccess) { lsq_set_error("lsq_index_create: the upload failed"); rc = LSQ_EHIP; }
     if (rc != LSQ_OK) { (void)lsq_index_destroy(ix); return rc; }
@@ -703,15 +736,11 @@ extern "C" int lsq_index_create_packed(lsq_index **out, lsq_ctx *c, const lsq_in
     *out = nullptr;
     if (!c || !desc) { lsq_set_error("%s: null %s", fn, c ? "description" : "context"); return LSQ_EINVAL; }
     if (!desc->codes) { lsq_set_error("%s: no codes (a base-only index is lsq_index_create's)", fn); return LSQ_EINVAL; }
-    if (desc->n < 1 || desc->n > (int64_t)INT32_MAX - 1 || desc->d < 1) {
-        lsq_set_error("%s: needs 1 <= n <= 2^31 - 2 and d >= 1 (got n=%lld d=%d)", fn, (long long)desc->n, desc->d);
-        return LSQ_EINVAL;
-    }
-    if (desc->h != LSQ_H || desc->m < 1 || desc->m > LSQ_MAX_M) { lsq_set_error("%s: needs h == 256 and 1 <= m <= 16 (got h=%d m=%d)", fn, desc->h, desc->m); return LSQ_EINVAL; }
-    if (!desc->codebooks || !desc->norm_codes || !desc->cbnorms) { lsq_set_error("%s: codes without codebooks, norm_codes or cbnorms", fn); return LSQ_EINVAL; }
-    if (desc->ncb < 1 || desc->ncb > 256) { lsq_set_error("%s: needs 1 <= ncb <= 256 (got %d)", fn, desc->ncb); return LSQ_EINVAL; }
-    if (desc->base && desc->ldb < desc->d) { lsq_set_error("%s: needs ldb >= d (got ldb=%d d=%d)", fn, desc->ldb, desc->d); return LSQ_EINVAL; }
-    if (desc->base) if (const char *why = lsq_base_align_refusal(lsq_base_format(desc->base_u8), desc->base)) { lsq_set_error("%s: %s", fn, why); return LSQ_EINVAL; }
+    LSQ_TRY(index_create_check(fn, desc->n, desc->d, true, desc->h, desc->m, desc->base, desc->ldb, desc->base_u8, [&]() -> int {
+        if (!desc->codebooks || !desc->norm_codes || !desc->cbnorms) { lsq_set_error("%s: codes without codebooks, norm_codes or cbnorms", fn); return LSQ_EINVAL; }
+        if (desc->ncb < 1 || desc->ncb > 256) { lsq_set_error("%s: needs 1 <= ncb <= 256 (got %d)", fn, desc->ncb); return LSQ_EINVAL; }
+        return LSQ_OK;
+    }));
     LSQ_TRY(use_device(c));
     hipStream_t s = c->stream;
     lsq_index *ix = new lsq_index();
@@ -719,6 +748,7 @@ extern "C" int lsq_index_create_packed(lsq_index **out, lsq_ctx *c, const lsq_in
     ix->n = desc->n; ix->d = desc->d; ix->m = desc->m; ix->base_u8 = lsq_base_format(desc->base_u8); ix->ldb = desc->ldb;
     ix->packed = 1; ix->ncb = desc->ncb;
     const size_t n = (size_t)desc->n, d = (size_t)desc->d, m = (size_t)desc->m;
+    IndexArrays arrays = index_arrays(ix, true, desc->base != nullptr);
     DevBuf s_codes, s_nc;                              // the host form's staging of what the pack kernel reads: gone when the call returns
     unsigned bad = 0;
     auto build = [&]() -> int {
@@ -730,7 +760,7 @@ extern "C" int lsq_index_create_packed(lsq_index **out, lsq_ctx *c, const lsq_in
             LSQ_HIP(hipMemcpyAsync(s_nc.p, desc->norm_codes, n, hipMemcpyHostToDevice, s));
             dcodes = s_codes.as<uint8_t>(); dnc = s_nc.as<uint8_t>();
         }
-        LSQ_TRY(ix->own_codes.ensure(n * (m + 1) + 16));      // 16 bytes of slack past the last row, never read
+        LSQ_TRY(ix->own_codes.ensure(arrays.rows[LSQ_ROWS_CODES].bytes_for(ix->n)));
         LSQ_TRY(ix->own_norms.ensure(sizeof(float) * 256));
         LSQ_TRY(ix->counter.ensure(sizeof(unsigned long long)));
         LSQ_HIP(hipMemsetAsync(ix->counter.p, 0, sizeof(unsigned long long), s));
@@ -738,11 +768,11 @@ extern "C" int lsq_index_create_packed(lsq_index **out, lsq_ctx *c, const lsq_in
         LSQ_HIP(hipMemcpyAsync(ix->own_norms.p, desc->cbnorms, sizeof(float) * (size_t)desc->ncb, desc->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
         LSQ_TRY(lsq_adc_launch_pack(s, dcodes, dnc, desc->n, desc->m, desc->ncb, ix->own_codes.as<uint8_t>(), ix->counter.as<unsigned>()));
         LSQ_HIP(hipMemcpyAsync(&bad, ix->counter.p, sizeof(bad), hipMemcpyDeviceToHost, s));
-        ix->codes = ix->own_codes.as<uint8_t>();
-        ix->norms = ix->own_norms.as<float>();
+        arrays.find(LSQ_ROWS_CODES)->repoint();
+        ix->norms = ix->own_norms.as<float>();        // (the norm table: not a row array)
         LSQ_TRY(index_adopt(ix, ix->own_K, desc->codebooks, sizeof(float) * m * LSQ_H * d, desc->on_device, reinterpret_cast<const void **>(&ix->K)));
-        if (desc->base)
-            LSQ_TRY(index_adopt(ix, ix->own_base, desc->base, ((n - 1) * (size_t)desc->ldb + d) * lsq_base_elem_bytes(ix->base_u8), desc->on_device, &ix->base));
+        if (const IndexArray *base = arrays.find(LSQ_ROWS_BASE))
+            LSQ_TRY(index_adopt(ix, *base->own, desc->base, base->rows.bytes_used(ix->n), desc->on_device, base->reader));
         if (hipStreamSynchronize(s) != hipSuccess) { lsq_set_error("%s: the upload failed", fn); return LSQ_EHIP; }
         if (bad) { lsq_set_error("%s: %u norm bytes lie outside [0, %d)", fn, bad, desc->ncb); return LSQ_EINVAL; }
         return LSQ_OK;
@@ -760,11 +790,12 @@ extern "C" int lsq_index_get_packed_info(lsq_index *ix, lsq_index_packed_info *o
     if (!ix || !out) { lsq_set_error("lsq_index_get_packed_info: null argument"); return LSQ_EINVAL; }
     *out = lsq_index_packed_info{};
     if (!ix->packed) return LSQ_OK;
-    out->row_bytes = ix->m + 1;
+    const lsq_rows_desc rows = index_arrays(ix).rows[LSQ_ROWS_CODES];
+    out->row_bytes = (int64_t)rows.pitch;
     out->ivf_row_bytes = lsq_ivf_nlist(ix->ivf) > 0 ? ix->m + 5 : 0;
     out->ncb = ix->ncb;
-    out->dword_rows = (ix->m + 1) % 4 == 0 ? 1 : 0;
-    out->resident_bytes = ix->n * (int64_t)(ix->m + 1) + 4 * (int64_t)ix->ncb;
+    out->dword_rows = rows.pitch % 4 == 0 ? 1 : 0;
+    out->resident_bytes = (int64_t)rows.bytes_used(ix->n) + 4 * (int64_t)ix->ncb;
     return LSQ_OK;
 }
 
@@ -1170,36 +1201,24 @@ extern "C" int lsq_index_get_filter_info(lsq_index *ix, lsq_filter_info *out) {
 }
 
 // ---- appending rows (lsq_grow.hip): the flat arrays in owned storage with capacity, the inverted layout merged, the filter extended ---------
-// What depends on n, and what an add does about it: ix->n (committed last); the flat arrays (appended past n, invisible until then); lsq_ivf_state's
-// layout, off and n (merged into the spare half, swapped at the commit); lsq_filter_state's bits / prefix / rows / n (rebuilt beside the one in force,
-// swapped) and its layout-order bits (lsq_filter_layout again); the scan state's sample and record buffers, stage two's records, nrm_x and every staging
-// buffer are sized from the call's own n at every call (DevBuf::ensure) and hold nothing across calls; idbits and the selection's road are computed per call
-static size_t index_row_bytes(const lsq_index *ix) { return (size_t)(ix->packed ? ix->m + 1 : ix->m); }
+// What depends on n beside the row arrays (index_arrays: appended past n, invisible until n moves, which is committed last): lsq_ivf_state's layout, off and
+// n (merged into the spare half, swapped at the commit); lsq_filter_state's bits / prefix / rows / n (rebuilt beside the one in force, swapped) and its
+// layout-order bits (lsq_filter_layout again); a held range result and r_lor_valid (dropped).  Everything else is sized per call and holds nothing across calls
 static size_t index_base_elem(const lsq_index *ix) { return lsq_base_elem_bytes(ix->base_u8); }      // 4, 1 or 2
-static bool index_borrows(const lsq_index *ix) {
-    return (ix->codes && ix->codes != ix->own_codes.p) || (ix->codes && !ix->packed && ix->norms != ix->own_norms.p) || (ix->base && ix->base != ix->own_base.p);
+static bool index_borrows(lsq_index *ix) {
+    for (const IndexArray &a : index_arrays(ix)) if (a.borrowed()) return true;
+    return false;
 }
 
 // the flat arrays in owned storage that holds `cap` rows: borrowed ones are adopted (copied once), owned ones that are too small move with their contents
 static int index_capacity(lsq_index *ix, int64_t cap, int *moved) {
-    hipStream_t s = ix->ctx->stream;
-    const size_t n = (size_t)ix->n, rowb = index_row_bytes(ix);
     const bool borrowed = index_borrows(ix);
-    const size_t before[3] = {ix->own_codes.cap, ix->own_norms.cap, ix->own_base.cap};
-    if (ix->codes) {
-        LSQ_TRY(lsq_devbuf_grow(s, ix->own_codes, (size_t)cap * rowb + 16, n * rowb, ix->codes));      // 16 bytes of slack past the last row, never read
-        ix->codes = ix->own_codes.as<uint8_t>();
-        if (!ix->packed) {
-            LSQ_TRY(lsq_devbuf_grow(s, ix->own_norms, sizeof(float) * (size_t)cap, sizeof(float) * n, ix->norms));
-            ix->norms = ix->own_norms.as<float>();
-        }
+    for (IndexArray &a : index_arrays(ix)) {
+        const size_t before = a.own->cap;
+        LSQ_TRY(lsq_devbuf_grow(ix->ctx->stream, *a.own, a.rows.bytes_for(cap), a.rows.bytes_used(ix->n), *a.reader));
+        a.repoint();
+        if (a.own->cap != before) *moved = 1;         // (a failure further on: the caller's count is not kept)
     }
-    if (ix->base) {
-        const size_t e = index_base_elem(ix);
-        LSQ_TRY(lsq_devbuf_grow(s, ix->own_base, (size_t)cap * (size_t)ix->ldb * e, ((n - 1) * (size_t)ix->ldb + (size_t)ix->d) * e, ix->base));
-        ix->base = ix->own_base.p;
-    }
-    if (before[0] != ix->own_codes.cap || before[1] != ix->own_norms.cap || before[2] != ix->own_base.cap) *moved = 1;
     if (borrowed) ix->grow.adopted = 1;
     if (cap > ix->cap_rows) ix->cap_rows = cap;
     return LSQ_OK;
@@ -1234,7 +1253,9 @@ extern "C" int lsq_index_add(lsq_index *ix, const lsq_index_add_desc *desc) {
     LSQ_TRY(use_device(c));
     hipStream_t s = c->stream;
     const int64_t n = ix->n, count = desc->count;
-    const size_t rowb = index_row_bytes(ix), m = (size_t)ix->m;
+    const IndexArrays arrays = index_arrays(ix);
+    const lsq_rows_desc &rcodes = arrays.rows[LSQ_ROWS_CODES], &rnorms = arrays.rows[LSQ_ROWS_NORMS], &rbase = arrays.rows[LSQ_ROWS_BASE];
+    const size_t m = (size_t)ix->m;
     const bool lists = lsq_ivf_nlist(ix->ivf) > 0;
     const hipMemcpyKind kind = desc->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     // 1. the range checks, on the device, by the kernels that read the entries: nothing of the index has been written when either refuses
@@ -1252,7 +1273,7 @@ extern "C" int lsq_index_add(lsq_index *ix, const lsq_index_add_desc *desc) {
             LSQ_HIP(hipMemcpyAsync(ix->g_nc.p, desc->norm_codes, (size_t)count, hipMemcpyHostToDevice, s));
             dcodes = ix->g_codes.as<uint8_t>(); dnc = ix->g_nc.as<uint8_t>();
         }
-        LSQ_TRY(ix->g_rows.ensure((size_t)count * rowb));
+        LSQ_TRY(ix->g_rows.ensure((size_t)count * rcodes.pitch));
         LSQ_HIP(hipMemsetAsync(ix->counter.p, 0, sizeof(unsigned long long), s));
         LSQ_TRY(lsq_adc_launch_pack(s, dcodes, dnc, count, ix->m, ix->ncb, ix->g_rows.as<uint8_t>(), ix->counter.as<unsigned>()));
         unsigned bad = 0;
@@ -1267,23 +1288,17 @@ extern "C" int lsq_index_add(lsq_index *ix, const lsq_index_add_desc *desc) {
     LSQ_TRY(ix->gclock.begin(c->profile != 0));
     LSQ_TRY(ix->gclock.mark(s));
     // 3. the flat arrays, past row n: not part of the index until n moves
-    if (ix->codes) {
-        uint8_t *at = ix->own_codes.as<uint8_t>() + (size_t)n * rowb;
-        if (ix->packed) LSQ_HIP(hipMemcpyAsync(at, ix->g_rows.p, (size_t)count * rowb, hipMemcpyDeviceToDevice, s));
-        else {
-            LSQ_HIP(hipMemcpyAsync(at, desc->codes, (size_t)count * rowb, kind, s));
-            LSQ_HIP(hipMemcpyAsync(ix->own_norms.as<float>() + n, desc->dbnorms, sizeof(float) * (size_t)count, kind, s));
-        }
-    }
-    if (ix->base) {                                   // re-pitched on the way in: the owned base keeps the index's pitch
-        const size_t e = index_base_elem(ix);
-        LSQ_HIP(hipMemcpy2DAsync(static_cast<char *>(ix->own_base.p) + (size_t)n * (size_t)ix->ldb * e, (size_t)ix->ldb * e, desc->base, (size_t)desc->ldb * e,
-                                 (size_t)ix->d * e, (size_t)count, kind, s));
+    uint8_t *new_codes = ix->own_codes.as<uint8_t>() + (size_t)n * rcodes.pitch;
+    float *new_norms = rnorms.pitch ? ix->own_norms.as<float>() + n : nullptr;
+    if (rcodes.pitch) LSQ_HIP(hipMemcpyAsync(new_codes, ix->packed ? ix->g_rows.p : desc->codes, (size_t)count * rcodes.pitch, ix->packed ? hipMemcpyDeviceToDevice : kind, s));
+    if (rnorms.pitch) LSQ_HIP(hipMemcpyAsync(new_norms, desc->dbnorms, (size_t)count * rnorms.pitch, kind, s));
+    if (rbase.pitch) {                                // re-pitched on the way in: the owned base keeps the index's pitch
+        LSQ_HIP(hipMemcpy2DAsync(static_cast<char *>(ix->own_base.p) + (size_t)n * rbase.pitch, rbase.pitch, desc->base, (size_t)desc->ldb * index_base_elem(ix),
+                                 rbase.width, (size_t)count, kind, s));
     }
     LSQ_TRY(ix->gclock.mark(s));
     // 4. the inverted layout, merged into its spare half; 5. the filter, rebuilt beside the one in force
-    if (lists)
-        LSQ_TRY(lsq_ivf_add_merge(s, ix->ivf, ix->own_codes.as<uint8_t>() + (size_t)n * rowb, ix->packed ? nullptr : ix->own_norms.as<float>() + n, count, cap, &moved));
+    if (lists) LSQ_TRY(lsq_ivf_add_merge(s, ix->ivf, new_codes, new_norms, count, cap, &moved));
     LSQ_TRY(ix->gclock.mark(s));
     LSQ_TRY(lsq_filter_grow(s, ix->filter, n + count));
     LSQ_TRY(ix->gclock.mark(s));
@@ -1344,10 +1359,9 @@ struct ScopedBuf {                                     // a buffer of one call: 
 };
 }  // namespace
 
-// What depends on n, for a SHRINKING n (the audit of lsq_index_add, again): ix->n, cap_rows and the flat pointers (committed last, the arrays written
-// beside); lsq_ivf_state's layout, off and n (written into the spare half, swapped at the commit); lsq_filter_state (cleared: the survivors are all
-// allowed; its layout-order state reset); grow.n (read from ix->n); nrm_x, the scan state's buffers, stage two's records and every staging buffer are
-// sized from the call's own n at every call and hold nothing across calls -- a smaller n finds them large enough
+// What depends on n beside the row arrays, for a SHRINKING n (index_arrays: gathered beside the ones in force; n, cap_rows and the pointers committed last):
+// lsq_ivf_state's layout, off and n (written into the spare half, swapped at the commit); lsq_filter_state (cleared: the survivors are all allowed; its
+// layout-order state reset); a held range result and r_lor_valid (dropped)
 extern "C" int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *desc) {
     const char *fn = "lsq_index_compact";
     if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
@@ -1362,7 +1376,7 @@ extern "C" int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *de
     const bool shrink = (flags & LSQ_COMPACT_SHRINK) != 0, lists = lsq_ivf_nlist(ix->ivf) > 0;
     const int64_t n = ix->n, n2 = active ? v.allowed : n;
     const int64_t cap = lsq_compact_capacity(ix->cap_rows, n2, flags);
-    const size_t rowb = index_row_bytes(ix), e = index_base_elem(ix);
+    IndexArrays arrays = index_arrays(ix);
     if (active && lists && !v.lbits) { lsq_set_error("%s: the filter has no bits in layout order (a failed lsq_index_set_lists / _set_filter?)", fn); return LSQ_EINVAL; }
     // the caller's maps: written on the device, into the caller's arrays or into scratch that is copied out
     int32_t *h_old = desc ? desc->old_of_new : nullptr, *h_new = desc ? desc->new_of_old : nullptr;
@@ -1380,17 +1394,9 @@ extern "C" int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *de
     float ms[2] = {0.0f, 0.0f};
     if (!active) {                                    // nothing leaves.  LSQ_COMPACT_SHRINK: owned storage with spare capacity is re-allocated to n rows
         if (shrink && ix->cap_rows > n && !index_borrows(ix)) {      // (each array: allocate, copy, swap, free -- the same rows wherever they lie)
-            if (ix->codes) {
-                LSQ_TRY(lsq_devbuf_fit(s, ix->own_codes, (size_t)n * rowb + 16, (size_t)n * rowb));
-                ix->codes = ix->own_codes.as<uint8_t>();
-                if (!ix->packed) {
-                    LSQ_TRY(lsq_devbuf_fit(s, ix->own_norms, sizeof(float) * (size_t)n, sizeof(float) * (size_t)n));
-                    ix->norms = ix->own_norms.as<float>();
-                }
-            }
-            if (ix->base) {
-                LSQ_TRY(lsq_devbuf_fit(s, ix->own_base, (size_t)n * (size_t)ix->ldb * e, ((size_t)(n - 1) * (size_t)ix->ldb + (size_t)ix->d) * e));
-                ix->base = ix->own_base.p;
+            for (IndexArray &a : arrays) {
+                LSQ_TRY(lsq_devbuf_fit(s, *a.own, a.rows.bytes_for(n), a.rows.bytes_used(n)));
+                a.repoint();
             }
             LSQ_TRY(lsq_ivf_fit(s, ix->ivf, n));
             ix->cap_rows = n;
@@ -1400,20 +1406,12 @@ extern "C" int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *de
         LSQ_HIP(hipStreamSynchronize(s));
     } else {
         // 1. the flat arrays, gathered into fresh storage of `cap` rows: straight from the caller's arrays where the index borrows them
-        ScopedBuf codes, norms, base;
+        ScopedBuf fresh[LSQ_ROWS_KINDS];
         LSQ_TRY(ix->cclock.begin(c->profile != 0));
         LSQ_TRY(ix->cclock.mark(s));
-        if (ix->codes) {
-            LSQ_TRY(codes.b.ensure((size_t)cap * rowb + 16));       // 16 bytes of slack past the last row, never read
-            LSQ_TRY(lsq_compact_launch_gather(s, ix->codes, codes.b.p, v.rows, (int64_t)rowb, n2, (int64_t)rowb, &bytes));
-            if (!ix->packed) {
-                LSQ_TRY(norms.b.ensure(sizeof(float) * (size_t)cap));
-                LSQ_TRY(lsq_compact_launch_gather(s, ix->norms, norms.b.p, v.rows, 4, n2, 4, &bytes));
-            }
-        }
-        if (ix->base) {                               // the pitch is kept; the last row ends at its d-th element, in the source as in the copy
-            LSQ_TRY(base.b.ensure((size_t)cap * (size_t)ix->ldb * e));
-            LSQ_TRY(lsq_compact_launch_gather(s, ix->base, base.b.p, v.rows, (int64_t)((size_t)ix->ldb * e), n2, (int64_t)((size_t)ix->d * e), &bytes));
+        for (IndexArray &a : arrays) {                // the pitch is kept; the last row ends at its width, in the source as in the copy
+            LSQ_TRY(fresh[a.kind].b.ensure(a.rows.bytes_for(cap)));
+            LSQ_TRY(lsq_compact_launch_gather(s, *a.reader, fresh[a.kind].b.p, v.rows, (int64_t)a.rows.pitch, n2, (int64_t)a.rows.width, &bytes));
         }
         LSQ_TRY(ix->cclock.mark(s));
         // 2. the inverted layout, into its spare half
@@ -1428,12 +1426,7 @@ extern "C" int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *de
         LSQ_TRY(ix->cclock.read(ms));
         // 3. the commit
         if (index_borrows(ix)) ix->grow.adopted = 1;
-        if (ix->codes) {
-            std::swap(ix->own_codes, codes.b);
-            ix->codes = ix->own_codes.as<uint8_t>();
-            if (!ix->packed) { std::swap(ix->own_norms, norms.b); ix->norms = ix->own_norms.as<float>(); }
-        }
-        if (ix->base) { std::swap(ix->own_base, base.b); ix->base = ix->own_base.p; }
+        for (IndexArray &a : arrays) a.commit(fresh[a.kind].b);
         if (lists) lsq_ivf_compact_commit(ix->ivf, n2);
         lsq_filter_clear(ix->filter);                 // every surviving row is allowed
         ix->n = n2;
@@ -1458,10 +1451,8 @@ extern "C" int lsq_index_get_compact_info(lsq_index *ix, lsq_index_compact_info 
 }
 
 // ---- half-precision base rows (lsq_half.hip): the resident f32 rows narrowed in place of themselves, and the stored rows read back ---------------
-// What depends on the base rows' format, and what a narrowing does about it: ix->base, ldb, base_u8 (committed last, after the one wait, the new rows written
-// beside the old); own_base (swapped: an owned f32 base is freed here, a borrowed one is the caller's); cap_rows (kept: the new rows are sized for it).  The
-// scan state, stage two's records, nrm_x and every staging buffer are sized per call and hold nothing across calls; the integer road of lsq_index_knn asks for
-// uint8 rows at every call
+// The new rows are written beside the old, sized for cap_rows, and committed with ldb and base_u8 after the one wait (an owned f32 base is freed here, a
+// borrowed one is the caller's).  Beside the base array only a held range result depends on the format (dropped)
 extern "C" int lsq_index_narrow_base(lsq_index *ix, int format) {
     const char *fn = "lsq_index_narrow_base";
     if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
@@ -1469,9 +1460,10 @@ extern "C" int lsq_index_narrow_base(lsq_index *ix, int format) {
     lsq_ctx *c = ix->ctx;
     LSQ_TRY(use_device(c));
     hipStream_t s = c->stream;
-    const size_t rows = (size_t)(ix->cap_rows > ix->n ? ix->cap_rows : ix->n), d = (size_t)ix->d;
+    lsq_rows_desc narrow[LSQ_ROWS_KINDS];             // the new rows: d halves apart
+    lsq_rows_describe(false, false, 0, true, ix->d, ix->d, format, narrow);
     ScopedBuf half;                                   // what it holds when the call ends is freed: the new rows after a failure, the former owned rows after the commit
-    LSQ_TRY(half.b.ensure(rows * d * 2));
+    LSQ_TRY(half.b.ensure(narrow[LSQ_ROWS_BASE].bytes_for(std::max(ix->cap_rows, ix->n))));
     LSQ_TRY(ix->h_counts.ensure(3 * sizeof(unsigned long long)));
     LSQ_HIP(hipMemsetAsync(ix->h_counts.p, 0, 3 * sizeof(unsigned long long), s));
     LSQ_TRY(ix->hclock.begin(c->profile != 0));
@@ -1483,8 +1475,7 @@ extern "C" int lsq_index_narrow_base(lsq_index *ix, int format) {
     LSQ_HIP(hipStreamSynchronize(s));                 // the one wait: everything is written, nothing is in force
     float ms[1];
     LSQ_TRY(ix->hclock.read(ms));
-    std::swap(ix->own_base, half.b);                  // the commit
-    ix->base = ix->own_base.p;
+    index_array(ix, LSQ_ROWS_BASE, narrow[LSQ_ROWS_BASE]).commit(half.b);
     ix->ldb = ix->d;
     ix->base_u8 = format;
     lsq_range_drop(ix->range);
@@ -1533,11 +1524,12 @@ extern "C" int lsq_index_get_base_info(lsq_index *ix, lsq_index_base_info *out) 
     if (!ix || !out) { lsq_set_error("lsq_index_get_base_info: null argument"); return LSQ_EINVAL; }
     *out = lsq_index_base_info{};
     if (!ix->base) return LSQ_OK;
+    const IndexArray base = *index_arrays(ix).find(LSQ_ROWS_BASE);
     out->format = ix->base_u8;
     out->elem_bytes = (int64_t)index_base_elem(ix);
     out->ldb = ix->ldb;
-    out->owned = ix->base == ix->own_base.p ? 1 : 0;
-    out->resident_bytes = ((ix->n - 1) * ix->ldb + ix->d) * (int64_t)index_base_elem(ix);
+    out->owned = base.borrowed() ? 0 : 1;
+    out->resident_bytes = (int64_t)base.rows.bytes_used(ix->n);
     out->to_inf = ix->hcounts.to_inf; out->to_zero = ix->hcounts.to_zero; out->nans = ix->hcounts.nans;
     out->narrow_ms = ix->narrow_ms;
     return LSQ_OK;
@@ -1583,7 +1575,7 @@ static int index_decode(const char *fn, lsq_index *ix, const int32_t *ids, bool 
     }
     LSQ_TRY(ix->rclock.mark(s));
     lsq_recon_call r;
-    r.codes = ix->codes; r.ldc = (int64_t)index_row_bytes(ix); r.K = ix->K; r.d = ix->d; r.m = ix->m; r.n = ix->n;
+    r.codes = ix->codes; r.ldc = (int64_t)index_arrays(ix).rows[LSQ_ROWS_CODES].pitch; r.K = ix->K; r.d = ix->d; r.m = ix->m; r.n = ix->n;
     r.id_base = id_base; r.pad_nan = pad ? 1 : 0;
     if (coarse) { r.cent = lsq_ivf_centroids(ix->ivf); r.lor = ix->r_lor.as<int32_t>(); r.nlist = lsq_ivf_nlist(ix->ivf); }
     int road = 0;
@@ -1767,7 +1759,8 @@ static void index_snap_scalars(lsq_index *ix, lsq_snapshot_info *s) {
 // bytes [off, off + len) of the DENSE stream of the base rows (pitch d) gathered from rows ldb elements apart: a ragged first row, whole rows, a ragged last
 static int index_snap_dense_base(lsq_index *ix, int64_t off, int64_t len, void *dstv, hipMemcpyKind kind) {
     hipStream_t s = ix->ctx->stream;
-    const int64_t e = (int64_t)index_base_elem(ix), rb = (int64_t)ix->d * e, pitch = ix->ldb * e;
+    const lsq_rows_desc rows = index_arrays(ix).rows[LSQ_ROWS_BASE];
+    const int64_t rb = (int64_t)rows.width, pitch = (int64_t)rows.pitch;
     const char *base = static_cast<const char *>(ix->base);
     char *dst = static_cast<char *>(dstv);
     int64_t row = off / rb, left = len;
@@ -2050,8 +2043,6 @@ extern "C" int lsq_index_load(lsq_index **out, lsq_ctx *c, const char *path, int
         d.dbnorms = static_cast<const float *>(ptr(LSQ_SNAP_DBNORMS));
         d.base = ptr(LSQ_SNAP_BASE); d.base_u8 = (int)s.base_format; d.ldb = (int)s.d; d.on_device = 1;
         LSQ_TRY(lsq_index_create(&ix, c, &d));
-        take(LSQ_SNAP_CODES, ix->own_codes);
-        take(LSQ_SNAP_DBNORMS, ix->own_norms);
     } else {
         lsq_index_packed_desc d{};
         d.n = s.n; d.d = (int)s.d; d.m = (int)s.m; d.h = (int)s.h; d.ncb = (int)s.ncb;
@@ -2061,7 +2052,8 @@ extern "C" int lsq_index_load(lsq_index **out, lsq_ctx *c, const char *path, int
         LSQ_TRY(lsq_index_create_packed(&ix, c, &d));                 // a norm byte >= ncb: LSQ_EINVAL from the pack kernel's count
     }
     take(LSQ_SNAP_CODEBOOKS, ix->own_K);
-    take(LSQ_SNAP_BASE, ix->own_base);
+    const int64_t section_of[LSQ_ROWS_KINDS] = {LSQ_SNAP_CODES, LSQ_SNAP_DBNORMS, LSQ_SNAP_BASE};
+    for (IndexArray &a : index_arrays(ix)) if (a.borrowed()) take(section_of[a.kind], *a.own);      // (a packed index built its own code rows)
     int rc = LSQ_OK;
     if (s.nlist > 0) {
         lsq_ivf_desc d{};

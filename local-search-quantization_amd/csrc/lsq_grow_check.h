@@ -1,4 +1,5 @@
-// lsq_grow_check.h -- the parts of lsq_index_add / lsq_index_reserve that need no device: the argument rules, the 2^31 bound and the capacity arithmetic.
+// lsq_grow_check.h -- the parts of lsq_index_add / lsq_index_reserve that need no device: the argument rules, the 2^31 bound, the capacity arithmetic
+// and the description of the index's per-row arrays (what every allocation, move and copy of them is sized from).
 // Plain C++ over the public header alone, so that a stand-alone host program can exercise them (tools/grow_check_main.cpp).
 #pragma once
 
@@ -50,4 +51,21 @@ inline const char *lsq_grow_reserve_refusal(int64_t n, int64_t rows) {
     if (rows < n) return "rows < n";
     if (rows > LSQ_GROW_MAX_ROWS) return "rows exceeds 2^31 - 2";
     return nullptr;
+}
+
+// ---- the per-row arrays of an index, in bytes: rows `pitch` apart, `width` of each in use, `slack` allocated past the last row of capacity (never read).
+// pitch 0: the index has no such array.  n, cap <= 2^31 - 2, ldb < 2^31 and elements of at most 4 bytes: pitch < 2^33, every product below 2^64
+struct lsq_rows_desc {
+    uint64_t pitch = 0, width = 0, slack = 0;
+    uint64_t bytes_used(int64_t n) const { return (uint64_t)(n - 1) * pitch + width; }      // n >= 1: up to the end of the last row's width
+    uint64_t bytes_for(int64_t cap) const { return (uint64_t)cap * pitch + slack; }         // storage that holds cap rows
+};
+enum { LSQ_ROWS_CODES = 0, LSQ_ROWS_NORMS = 1, LSQ_ROWS_BASE = 2, LSQ_ROWS_KINDS = 3 };
+
+// out[kind]: code rows of m bytes (packed: m + 1, the norm byte last) with 16 bytes of slack, f32 norms beside unpacked codes, base rows of d elements ldb apart
+inline void lsq_rows_describe(bool has_codes, bool packed, int m, bool has_base, int d, int64_t ldb, int base_format, lsq_rows_desc out[LSQ_ROWS_KINDS]) {
+    const uint64_t rowb = (uint64_t)(packed ? m + 1 : m), e = base_format == 0 ? 4u : (base_format == LSQ_BASE_F16 || base_format == LSQ_BASE_BF16) ? 2u : 1u;
+    out[LSQ_ROWS_CODES] = has_codes ? lsq_rows_desc{rowb, rowb, 16} : lsq_rows_desc{};
+    out[LSQ_ROWS_NORMS] = has_codes && !packed ? lsq_rows_desc{4, 4, 0} : lsq_rows_desc{};
+    out[LSQ_ROWS_BASE] = has_base ? lsq_rows_desc{(uint64_t)ldb * e, (uint64_t)d * e, 0} : lsq_rows_desc{};
 }

@@ -388,6 +388,36 @@ def test_two_stage_calls_on_half_rows(lsq, engine, fmt, packed):
                 sd, si = hix.search(Q, L)
                 rc, rd, ri = rerank_cpu(lsq._lib.load(), W, Q, si, d, k, 1)
                 assert rc == 0 and _same(hix.search(Q, k, shortlist=L), (rd, ri))
+    # narrowing an index that has spare capacity: a borrowed f32 base at an odd pitch, reserve, narrow, add -- the narrowed rows are sized for the capacity,
+    # so the rows that follow fit without another allocation
+    n, d, ldb, extra, cap = 200, 12, 13, 100, 320
+    codes, K, dbn, Xb = _database(rng, n + extra, d, m)
+    Hh, W = _halves(Xb, fmt)
+    nc = rng.integers(0, ncb, n + extra, dtype=np.uint8)
+    if packed:
+        dbn = cb[nc]
+    new = {"codes": codes[n:], "norm_codes": nc[n:]} if packed else {"codes": codes[n:], "dbnorms": dbn[n:]}
+    Q = (Xb[rng.integers(0, n, nq)] + 0.25 * rng.standard_normal((nq, d))).astype(np.float32)
+    view, keep = _view(Xb[:n], ldb, 1, np.float32(np.nan))
+    with _make(engine, packed, True, codes[:n], K, dbn[:n], nc[:n], cb, m, W[:n]) as wix:
+        t = _dev
+        hix = engine.index_packed_dev(t(codes[:n]), t(K), t(nc[:n]), t(cb), m, base=view) if packed else engine.index_dev(t(codes[:n]), t(K), t(dbn[:n]), m, base=view)
+        with hix:
+            assert hix.base_info()["ldb"] == ldb and hix.base_info()["owned"] == 0
+            for ix in (hix, wix):
+                ix.reserve(cap)
+            hix.narrow_base(fmt)
+            assert (hix.base_info()["format"], hix.base_info()["ldb"], hix.base_info()["resident_bytes"]) == (HC.FORMATS[fmt], d, 2 * n * d)
+            before = [ix.growth_info()["reallocations"] for ix in (hix, wix)]
+            hix.add(base=Xb[n:], **new)                                      # float32 rows, narrowed by the binding
+            wix.add(base=W[n:], **new)
+            for ix, was in zip((hix, wix), before):
+                g = ix.growth_info()
+                assert (g["reallocations"], g["capacity_rows"], g["n"]) == (was, cap, n + extra)
+            assert HC.same_bits(_call(hix, "base_rows"), W) and HC.same_bits(_call(wix, "base_rows"), W)
+            assert _same(_call(hix, "search", Q, k, shortlist=L), _call(wix, "search", Q, k, shortlist=L))
+            assert _same(_call(hix, "knn", Q, k), _call(wix, "knn", Q, k))
+    assert HC.same_bits(keep[1:1 + n * ldb].view(n, ldb)[:, :d].cpu().numpy(), Xb[:n])      # the borrowed rows are untouched
 
 
 # ---- Identity W through the life cycle: add, remove, compact, add --------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // grow_check_main.cpp -- a stand-alone host program over csrc/lsq_grow_check.h: the argument rules of lsq_index_add / lsq_index_reserve, the 2^31 - 2 bound
-// and the capacity arithmetic, which need no device.  Built with the host compiler alone, usually under -fsanitize=address,undefined (tests/test_index_add.py
+// the capacity arithmetic and the sizes of the index's row arrays (every shape against the written-out formulas, and at the bounds), which need no device.  Built with the host compiler alone, usually under -fsanitize=address,undefined (tests/test_index_add.py
 // does that where the compiler has the runtimes): signed overflow in the bound or in the growth rule is then an error, not a wrong number.
 //   c++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all tools/grow_check_main.cpp -o grow_check && ./grow_check
 #include <stdio.h>
@@ -109,6 +109,53 @@ int main() {
     // the byte counts the library derives from a capacity stay inside size_t: the widest row (17 bytes) and a base of 4096 floats per row at the bound
     const uint64_t rows = (uint64_t)LSQ_GROW_MAX_ROWS;
     EXPECT(rows * 17u + 16u > rows && rows * 4096u * 4u / 4096u / 4u == rows);
+
+    // the row arrays: for every shape the description gives the sizes the library used to write out by hand
+    const int formats[4] = {0, 1, LSQ_BASE_F16, LSQ_BASE_BF16};
+    const uint64_t elem[4] = {4, 1, 2, 2};
+    const uint64_t n = 1000, cap2 = 1500, m = 7, dim = 12;
+    for (int has_codes = 0; has_codes < 2; ++has_codes)
+        for (int pk = 0; pk < 2; ++pk)
+            for (int has_base = 0; has_base < 2; ++has_base)
+                for (int f = 0; f < 4; ++f)
+                    for (uint64_t ldb = dim; ldb <= dim + 1; ++ldb) {
+                        if (pk && !has_codes) continue;
+                        lsq_rows_desc r[LSQ_ROWS_KINDS];
+                        lsq_rows_describe(has_codes != 0, pk != 0, (int)m, has_base != 0, (int)dim, (int64_t)ldb, formats[f], r);
+                        const lsq_rows_desc &cd = r[LSQ_ROWS_CODES], &nd = r[LSQ_ROWS_NORMS], &bd = r[LSQ_ROWS_BASE];
+                        const uint64_t rowb = pk ? m + 1 : m, e = elem[f];
+                        EXPECT((cd.pitch != 0) == (has_codes != 0));
+                        EXPECT((nd.pitch != 0) == (has_codes && !pk));                              // norms exist iff codes && !packed
+                        EXPECT((bd.pitch != 0) == (has_base != 0));
+                        if (has_codes) {
+                            EXPECT(cd.pitch == rowb && cd.width == rowb);
+                            EXPECT(cd.bytes_for((int64_t)cap2) == cap2 * rowb + 16 && cd.bytes_used((int64_t)n) == n * rowb);      // index_capacity
+                            EXPECT(cd.bytes_for((int64_t)n) == n * rowb + 16);                       // the SHRINK fit; create_packed's n * (m + 1) + 16
+                        }
+                        if (has_codes && !pk) {
+                            EXPECT(nd.pitch == 4 && nd.width == 4);                                 // the gather's (4, 4)
+                            EXPECT(nd.bytes_for((int64_t)cap2) == 4 * cap2 && nd.bytes_used((int64_t)n) == 4 * n && nd.bytes_for((int64_t)n) == 4 * n);
+                        }
+                        if (has_base) {
+                            EXPECT(bd.pitch == ldb * e && bd.width == dim * e);                         // the gather's and the 2-D copy's pitch and width
+                            EXPECT(bd.bytes_for((int64_t)cap2) == cap2 * ldb * e && bd.bytes_used((int64_t)n) == ((n - 1) * ldb + dim) * e);
+                            EXPECT(bd.bytes_for((int64_t)n) == n * ldb * e);
+                            EXPECT(bd.bytes_used(1) == dim * e);
+                            if (e == 2 && ldb == dim) EXPECT(bd.bytes_for((int64_t)cap2) == cap2 * dim * 2);      // narrow_base's new buffer
+                        }
+                    }
+    // nothing overflows 64 unsigned bits: the widest arrays at the bounds, against 128-bit arithmetic
+    {
+        lsq_rows_desc r[LSQ_ROWS_KINDS];
+        const int64_t top = LSQ_GROW_MAX_ROWS, wide = INT32_MAX;
+        lsq_rows_describe(true, true, 16, true, INT32_MAX, wide, 0, r);
+        for (const lsq_rows_desc &a : r) {
+            const unsigned __int128 need = (unsigned __int128)top * a.pitch + a.slack, used = (unsigned __int128)(top - 1) * a.pitch + a.width;
+            EXPECT(need <= UINT64_MAX && used <= UINT64_MAX);
+            EXPECT((unsigned __int128)a.bytes_for(top) == need && (unsigned __int128)a.bytes_used(top) == used);
+        }
+        EXPECT(r[LSQ_ROWS_BASE].pitch == (uint64_t)INT32_MAX * 4 && r[LSQ_ROWS_CODES].pitch == 17 && r[LSQ_ROWS_NORMS].pitch == 0);
+    }
     if (failures) printf("grow_check: %d FAILED\n", failures);
     else printf("grow_check: all passed\n");
     return failures ? 1 : 0;
