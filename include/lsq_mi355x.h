@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 2700
+#define LSQ_VERSION 2800
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -140,6 +140,8 @@ LSQ_API int lsq_set_stream(lsq_ctx *ctx, void *hip_stream);
  *   "knn_u8_int" (0/1, default 1): 0 = lsq_index_knn widens 8-bit rows and queries even where its integer road applies.  A test hook: same results.
  *   "knn_prefilter" (0/1, default 0; since v2700, (3q)): 1 = exact k-NN (lsq_knn_exact, lsq_knn_exact_dev, lsq_index_knn of every lsq_index created on this
  *        context) pre-filters the thresholded road on the matrix cores.  Same results, bit for bit.
+ *   "knn_u8_mfma" (0/1, default 0; since v2800, (3r)): 1 = lsq_index_knn runs the thresholded pass of its integer road (uint8 rows x uint8 queries, d <= 258)
+ *                    on the i8 matrix cores: the same results bit for bit.  As for "knn_prefilter", any non-zero value is 1.
  *   "knn_prefilter_cap" (default 0): pending pairs per query of the pre-filter; 0 = automatic (twice the list capacity).  A test hook: same results.
  *   "range_batch" (default 0): records per fill batch of lsq_index_range_search on every lsq_index created on this context; 0 = automatic (2^28).  A
  *        test hook: small shapes cross batch boundaries, and a query larger than the budget is a batch of its own.  Same results.
@@ -1067,6 +1069,27 @@ typedef struct lsq_knn_prefilter_info {
 } lsq_knn_prefilter_info;
 LSQ_API int lsq_knn_prefilter_bound(int d, float *kappa, float *eta);
 LSQ_API int lsq_index_get_knn_prefilter_info(lsq_index *ix, lsq_knn_prefilter_info *out);
+
+/* ---- (3r) exact k-NN of 8-bit sets on the i8 matrix cores (csrc/lsq_knnu.hip; since v2800) --------------------------------------------------------------------
+ * THE REFERENCE HAS NO COUNTERPART.  Option "knn_u8_mfma" = 1 lets lsq_index_knn (3f) run the thresholded pass of its integer road -- uint8 rows, uint8
+ * queries, d <= 258, "knn_u8_int" = 1 -- on v_mfma_i32_32x32x32_i8 instead of v_dot4_u32_u8.  With x' = x - 128, q' = q - 128 the contract's distance is the
+ * integer D = N'_x + N'_q - 2 <x', q'>, which the matrix cores compute exactly in i32: the tile decides D <= tau and appends the final record itself -- no
+ * error window, no recheck.  THE RESULT DOES NOT CHANGE, NOT BY A BIT, and neither do the statistics of lsq_index_get_knn_info.  The sample pass, the
+ * fallback of a query whose list came out short, filtered calls and the exhaustive road stay on the dot4 kernel; "knn_prefilter" stays unserved for
+ * uint8 queries.
+ *   lsq_index_get_knn_mfma_info   the account of the last lsq_index_knn call of the index (written by every call). */
+enum { LSQ_KNN_MFMA_SERVED = 0,                /* reason: */
+       LSQ_KNN_MFMA_NOT_ASKED = 1,             /* option "knn_u8_mfma" is 0 */
+       LSQ_KNN_MFMA_NOT_INTEGER_ROAD = 2,      /* not uint8 x uint8 with d <= 258, or option "knn_u8_int" is 0 */
+       LSQ_KNN_MFMA_FILTERED = 3,              /* a row filter is in force (dense or compact road) */
+       LSQ_KNN_MFMA_EXHAUSTIVE = 4 };          /* the exhaustive road: n <= 65536, a large nn, or option "linscan_exhaustive" */
+typedef struct lsq_knn_mfma_info {
+    int64_t served, reason;      /* served 1: the thresholded pass ran on the i8 matrix cores; 0: the dot4 (or widened) road, reason = LSQ_KNN_MFMA_* */
+    int64_t pairs;               /* (query, row) pairs the matrix-core pass judged */
+    int64_t kept;                /* records it appended to the candidate lists (counted, as on the dot4 road, even past a list's capacity) */
+    double norms_ms, scan_ms;    /* with option "profile" = 1: the shifted norms, the matrix-core pass */
+} lsq_knn_mfma_info;
+LSQ_API int lsq_index_get_knn_mfma_info(lsq_index *ix, lsq_knn_mfma_info *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

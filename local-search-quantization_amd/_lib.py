@@ -62,6 +62,14 @@ class KnnPrefilterInfo(_Struct):
                 ("mfma_ms", C.c_double), ("recheck_ms", C.c_double)]
 
 
+class KnnMfmaInfo(_Struct):
+    _fields_ = [("served", C.c_int64), ("reason", C.c_int64), ("pairs", C.c_int64), ("kept", C.c_int64), ("norms_ms", C.c_double), ("scan_ms", C.c_double)]
+
+
+# lsq_knn_mfma_info.reason: why a call's thresholded pass stayed off the i8 matrix cores (0: it did not)
+KNN_MFMA_NOT_ASKED, KNN_MFMA_NOT_INTEGER_ROAD, KNN_MFMA_FILTERED, KNN_MFMA_EXHAUSTIVE = 1, 2, 3, 4
+
+
 # lsq_knn_prefilter_info.reason: why a call took the direct road (0: it did not)
 KNN_PREFILTER_NOT_ASKED, KNN_PREFILTER_FILTERED, KNN_PREFILTER_U8_QUERIES, KNN_PREFILTER_EXHAUSTIVE, KNN_PREFILTER_WIDE = 1, 2, 3, 4, 5
 
@@ -329,6 +337,8 @@ SIGNATURES = {
     # the MFMA pre-filter of exact k-NN (since v2700): its window, and what it did in the last knn call of an index
     "lsq_knn_prefilter_bound": (_i, [_i, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "lsq_index_get_knn_prefilter_info": (_i, [_vp, C.POINTER(KnnPrefilterInfo)]),
+    # exact k-NN of 8-bit sets on the i8 matrix cores (since v2800): what it did in the last knn call of an index
+    "lsq_index_get_knn_mfma_info": (_i, [_vp, C.POINTER(KnnMfmaInfo)]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),
@@ -370,7 +380,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 2700     # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 2800     # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

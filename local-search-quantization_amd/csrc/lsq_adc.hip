@@ -781,10 +781,20 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
             fi->norms_ms = ms[0];
         }
     }
+    // the i8 matrix-core road of 8-bit sets (lsq_knnu.hip): MODE 0 of the thresholded road, no filter.  The caller has said whether it was asked for
+    // and whether the integer road holds (the shifted norms are there); what is left to decide is known here.  Not served: the norms are taken off the input
+    if (opt.u8_info && opt.u8_info->reason == LSQ_KNN_MFMA_SERVED) {
+        lsq_knn_mfma_info *ui = opt.u8_info;
+        ui->reason = in.filtered() ? LSQ_KNN_MFMA_FILTERED : P.exhaustive ? LSQ_KNN_MFMA_EXHAUSTIVE : LSQ_KNN_MFMA_SERVED;
+        ui->served = ui->reason == LSQ_KNN_MFMA_SERVED && cur.xnorms_s && cur.qnorms_s;
+    }
+    const bool u8_served = opt.u8_info && opt.u8_info->served;
+    if (!u8_served) cur.xnorms_s = cur.qnorms_s = nullptr;
     int64_t qb = lsq_adc_batch_queries(per_query + (cur.prefilter ? (pf.pcap + 1) / 2 : 0));   // two key buffers of per_query entries per query; whole tiles of 16 queries
     if (qb > 16) qb &= ~(int64_t)15;
     std::vector<int> h_fail;
     std::vector<int> failed, redo;
+    double u8_scan_seen = stats ? stats->scan_ms : 0.0;      // stats->scan_ms before the batch: the batch's own MODE 0 pass is the difference
     for (int q0 = 0; q0 < nq; q0 += (int)qb) {
         const int nqb = (int)std::min<int64_t>(qb, nq - q0);
         h_fail.assign((size_t)nqb, 0);
@@ -801,6 +811,17 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
             if (cur.prefilter && 2 * (redo.size() - redo0) > (size_t)nqb) { cur.prefilter = 0; pf.info->switched_off = 1; }
         }
         if (stats) stats->batches += 1;
+        if (u8_served) {
+            // what the matrix-core pass did: count[] of the batch is what it appended (stats->candidates, read back by run_batch, sums the same counts)
+            lsq_knn_mfma_info *ui = opt.u8_info;
+            std::vector<unsigned> hc((size_t)nqb);
+            LSQ_HIP(hipMemcpyAsync(hc.data(), st->count.p, sizeof(unsigned) * (size_t)nqb, hipMemcpyDeviceToHost, s));
+            LSQ_HIP(hipStreamSynchronize(s));
+            ui->pairs += (int64_t)nqb * n;
+            for (unsigned c : hc) ui->kept += c;
+            if (timed && stats) { ui->scan_ms += stats->scan_ms - u8_scan_seen; }
+        }
+        if (stats) u8_scan_seen = stats->scan_ms;
     }
     if (!redo.empty()) {
         // the direct scan, same plan, for the queries whose pending list overflowed; only their failures go on to the exhaustive road

@@ -111,6 +111,7 @@ struct lsq_ctx {
     lsq_search_opts search;                            // options "linscan_exhaustive", "linscan_rank": test hooks of the scan's selection (search_opts fills in the rest per call)
     int knn_u8_int = 1;                                // option "knn_u8_int": 0 = lsq_index_knn widens 8-bit rows and queries even where the integer road applies; a test hook
     int knn_prefilter = 0, knn_prefilter_cap = 0;      // options "knn_prefilter" (exact k-NN pre-filters the thresholded road on the matrix cores: lsq_knnm.hip) and "knn_prefilter_cap" (its pending capacity; a test hook)
+    int knn_u8_mfma = 0;                               // option "knn_u8_mfma": lsq_index_knn's integer road runs its thresholded pass on the i8 matrix cores (lsq_knnu.hip)
     lsq_knn_prefilter_info knn_pf{};                   // ... where the account of the last lsq_knn_exact / lsq_knn_exact_dev call is written (no getter yet: DESIGN 4.29)
     int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
     int64_t range_batch = 0;                           // option "range_batch": records per fill batch of lsq_index_range_search (0 = automatic); a test hook
@@ -321,6 +322,7 @@ extern "C" int lsq_set_option(lsq_ctx *c, const char *key, int64_t value) {
     }
     else if (!strcmp(key, "knn_u8_int")) c->knn_u8_int = value != 0;
     else if (!strcmp(key, "knn_prefilter")) c->knn_prefilter = value != 0;
+    else if (!strcmp(key, "knn_u8_mfma")) c->knn_u8_mfma = value != 0;
     else if (!strcmp(key, "knn_prefilter_cap")) {
         if (value < 0 || value > (int64_t)INT32_MAX) { lsq_set_error("knn_prefilter_cap must lie in 0..2^31-1"); return LSQ_EINVAL; }
         c->knn_prefilter_cap = (int)value;
@@ -469,10 +471,11 @@ static lsq_search_opts search_opts(const lsq_ctx *c, lsq_linscan_stats *stats) {
     return o;
 }
 // an exact search: the context's pre-filter options as well (lsq_knnm.hip), and where the call's account of it goes
-static lsq_search_opts exact_opts(const lsq_ctx *c, lsq_linscan_stats *stats, lsq_knn_prefilter_info *pf) {
+static lsq_search_opts exact_opts(const lsq_ctx *c, lsq_linscan_stats *stats, lsq_knn_prefilter_info *pf, lsq_knn_mfma_info *u8 = nullptr) {
     lsq_search_opts o = search_opts(c, stats);
     o.prefilter_cap = c->knn_prefilter_cap;
     o.pf_info = pf;
+    o.u8_info = u8;
     return o;
 }
 
@@ -586,12 +589,14 @@ struct lsq_index {
     DevBuf rec_a, rec_b, seg, counter;                 // stage two: records, sorted records, segment bounds, the invalid-id counter
     DevBuf short_d, short_i;                           // stage one's shortlist [nq][L]
     DevBuf s_qscan, s_qexact, s_cand, s_dists, s_ids;  // staging of host-buffer calls, and of scan queries whose rows are not d floats apart
+    DevBuf nrm_xs, nrm_qs;                             // ... and, with option "knn_u8_mfma", the int32 squared norms of both shifted by -128 (lsq_knnu.hip), refilled likewise
     DevBuf nrm_x, nrm_q;                               // lsq_index_knn's integer road: uint32 squared norms of the rows and of the queries, refilled at every call
     lsq_ivf_state *ivf = nullptr;                      // the inverted lists (lsq_ivf.hip): layout and scratch of THIS index; null until lsq_index_set_lists
     DevBuf s_qcoarse;                                  // lsq_index_search_ivf's staging of host q_coarse rows
     PhaseClock<3> clock;                               // a re-rank batch's gather and selection; lsq_index_knn's norm pass
     lsq_index_stats stats{};
     lsq_index_knn_info knn{};
+    lsq_knn_mfma_info knn_mf{};                        // what the i8 matrix-core road (option "knn_u8_mfma" of the context; lsq_knnu.hip) did in the last lsq_index_knn
     lsq_knn_prefilter_info knn_pf{};                   // what the pre-filter (option "knn_prefilter" of the context; lsq_knnm.hip) did in the last lsq_index_knn
     lsq_filter_state *filter = nullptr;                // the row filter (lsq_filter.hip): null until lsq_index_set_filter; owned copies of THIS index
     int64_t cap_rows = 0;                              // lsq_index_add: rows the flat arrays hold without another allocation (n until the first add / reserve)
@@ -667,7 +672,7 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     (void)hipStreamSynchronize(ix->ctx->stream);
     for (int kind = 0; kind < LSQ_ROWS_KINDS; ++kind) index_array(ix, kind, lsq_rows_desc{}).own->release();      // (own_norms of a packed index: the norm table)
     DevBuf *bufs[] = {&ix->own_K, &ix->rec_a, &ix->rec_b, &ix->seg, &ix->counter, &ix->short_d, &ix->short_i,
-                      &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q, &ix->s_qcoarse, &ix->g_codes, &ix->g_nc, &ix->g_rows,
+                      &ix->s_qscan, &ix->s_qexact, &ix->s_cand, &ix->s_dists, &ix->s_ids, &ix->nrm_x, &ix->nrm_q, &ix->nrm_xs, &ix->nrm_qs, &ix->s_qcoarse, &ix->g_codes, &ix->g_nc, &ix->g_rows,
                       &ix->c_old, &ix->c_new, &ix->s_radius, &ix->r_lor, &ix->r_ids, &ix->r_out, &ix->r_q, &ix->h_counts};
     for (DevBuf *b : bufs) b->release();
     lsq_range_free(ix->range);
@@ -1022,12 +1027,30 @@ extern "C" int lsq_index_knn(lsq_index *ix, float *dists, int *ids, const void *
         in.xnorms = ix->nrm_x.as<uint32_t>();
         in.qnorms = ix->nrm_q.as<uint32_t>();
     }
+    // the i8 matrix-core road (lsq_knnu.hip): asked for and on the integer road -- lsq_adc_search decides the rest (filter, exhaustive) and fills the account
+    lsq_knn_mfma_info mf{};
+    mf.reason = !c->knn_u8_mfma ? LSQ_KNN_MFMA_NOT_ASKED : !int_road ? LSQ_KNN_MFMA_NOT_INTEGER_ROAD : LSQ_KNN_MFMA_SERVED;
+    if (mf.reason == LSQ_KNN_MFMA_SERVED) {
+        LSQ_TRY(ix->nrm_xs.ensure(sizeof(int32_t) * (size_t)n));
+        LSQ_TRY(ix->nrm_qs.ensure(sizeof(int32_t) * (size_t)nq));
+        LSQ_TRY(ix->clock.begin(c->profile != 0));
+        LSQ_TRY(ix->clock.mark(s));
+        LSQ_TRY(lsq_knnu_launch_norms(s, static_cast<const uint8_t *>(ix->base), ix->ldb, n, d, ix->nrm_xs.as<int32_t>()));
+        LSQ_TRY(lsq_knnu_launch_norms(s, static_cast<const uint8_t *>(dq), ldq, nq, d, ix->nrm_qs.as<int32_t>()));
+        LSQ_TRY(ix->clock.mark(s));
+        float ms[2];
+        LSQ_TRY(ix->clock.read(ms));
+        mf.norms_ms = ms[0];
+        in.xnorms_s = ix->nrm_xs.as<int32_t>();
+        in.qnorms_s = ix->nrm_qs.as<int32_t>();
+    }
     lsq_linscan_stats st{};
     int road = 0;
     index_apply_filter(ix, &in, &road, 8);
     lsq_filter_note_road(ix->filter, road);
-    LSQ_TRY(lsq_adc_search(s, &ix->adc, call.out_d, call.out_i, in, nq, nn, exact_opts(c, &st, &ix->knn_pf)));
+    LSQ_TRY(lsq_adc_search(s, &ix->adc, call.out_d, call.out_i, in, nq, nn, exact_opts(c, &st, &ix->knn_pf, &mf)));
     LSQ_TRY(call.finish());
+    ix->knn_mf = mf;
     info.queries = nq; info.rows = n; info.batches = st.batches; info.fallback_queries = st.fallback_queries; info.exhaustive = st.exhaustive;
     info.int_road = int_road ? 1 : 0;
     info.scan_ms = st.sample_ms + st.scan_ms; info.select_ms = st.select_ms;
@@ -1044,6 +1067,12 @@ extern "C" int lsq_index_get_knn_info(lsq_index *ix, lsq_index_knn_info *out) {
 extern "C" int lsq_index_get_knn_prefilter_info(lsq_index *ix, lsq_knn_prefilter_info *out) {
     if (!ix || !out) { lsq_set_error("lsq_index_get_knn_prefilter_info: null argument"); return LSQ_EINVAL; }
     *out = ix->knn_pf;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_knn_mfma_info(lsq_index *ix, lsq_knn_mfma_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_knn_mfma_info: null argument"); return LSQ_EINVAL; }
+    *out = ix->knn_mf;
     return LSQ_OK;
 }
 

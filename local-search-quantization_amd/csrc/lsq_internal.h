@@ -330,6 +330,9 @@ struct lsq_search_input {
     const void *base; int bstride;           // exact: [n][bstride], the first d elements of a row used
     int base_u8 = 0, q_u8 = 0;               // exact: element types of base / Q (0: f32, 1: uint8; base also LSQ_BASE_F16 / LSQ_BASE_BF16 -- a FORMAT, normalised by lsq_base_format)
     const uint32_t *xnorms = nullptr, *qnorms = nullptr;
+    // exact, integer road, option "knn_u8_mfma": the squared norms of the rows / queries shifted by -128 (lsq_knnu_launch_norms).  Both set: MODE 0 of an
+    // unfiltered batch without qsel runs on the i8 matrix cores (lsq_knnu.hip); lsq_adc_search clears them where the call is not served
+    const int32_t *xnorms_s = nullptr, *qnorms_s = nullptr;
     int id_base = 0;                         // exact: ids leave as row + id_base
     int packed = 0;                          // LSQ: rows of cstride = m + 1 bytes, the last one the norm byte c_i; dbnorms = the norm table padded to 256 floats
     // a row filter (lsq_filter.hip), LSQ and exact kinds.  filter_bits: bit (i & 31) of word i >> 5 = row i is allowed -- the DENSE road: every row is read, a
@@ -354,6 +357,7 @@ struct lsq_search_opts {
     int timed = 0;
     int prefilter_cap = 0;                   // option "knn_prefilter_cap": the pending capacity of the pre-filter (0 = twice the list capacity); a test hook
     lsq_knn_prefilter_info *pf_info = nullptr;      // exact searches: what the pre-filter did in this call (always written when set)
+    lsq_knn_mfma_info *u8_info = nullptr;    // exact searches whose input carries shifted norms: what the i8 matrix-core road did in this call
 };
 // every pointer of `in` a device pointer / a host pointer (staged: upload, search, download); dists, idx [nq][nn] likewise
 int lsq_adc_search(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const lsq_search_input &in, int nq, int nn, const lsq_search_opts &opt);
@@ -379,6 +383,9 @@ int lsq_knnm_launch(hipStream_t s, const lsq_search_input &in, int q0, int nqb, 
                     const lsq_knnm_work &w);
 int lsq_knnm_launch_mark(hipStream_t s, const unsigned *pcount, int pcap, int *fail, int nqb);
 int lsq_knn_launch_norms_u8(hipStream_t s, const uint8_t *X, int64_t ld, int n, int d, uint32_t *out);
+// ---- exact k-NN of 8-bit sets on the i8 matrix cores (lsq_knnu.hip): the shifted norms, and MODE 0 of one unfiltered batch (no qsel) ----
+int lsq_knnu_launch_norms(hipStream_t s, const uint8_t *X, int64_t ld, int n, int d, int32_t *out);
+int lsq_knnu_launch(hipStream_t s, const lsq_search_input &in, int q0, int nqb, const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits);
 // argument checks of exact k-NN (lsq_linscan.hip), shared by the host drop-in and the device search
 int lsq_knn_exact_check(const char *fn, const void *dists, const void *ids, const void *base, const void *queries, int n, int nq, int d, int ldb,
                         int ldq, int nn);

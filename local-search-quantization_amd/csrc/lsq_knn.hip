@@ -180,21 +180,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_scan_kernel(const TX *__restr
 // ---- the integer road ------------------------------------------------------------------------------------------------------------------------------
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// Dword w (components 4 w .. 4 w + 3) of a row of d bytes, component e in byte e, zero from the d-th component on.  vec (lsq_xload.h's rule: the
-// matrix pointer and its row pitch in bytes are multiples of 4): one dword load where all four components exist.  Everything else -- a matrix at any
-// byte offset, an odd pitch, and the LAST, partial dword of any row -- travels as single bytes: nothing at or past the d-th byte of a row is loaded,
-// so nothing outside [base, base + (n - 1) ldb + d) is, and there is no padding to mask.
-__device__ inline uint32_t knn_ld_packed(const uint8_t *__restrict__ row, int w, int d, bool vec) {
-    const int b0 = 4 * w, valid = d - b0;
-    if (valid <= 0) return 0u;
-    if (vec && valid >= 4) return lsq_ld4_packed(row + b0);
-    uint32_t v = 0u;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (e < valid) v |= (uint32_t)row[b0 + e] << (8 * e);
-    return v;
-}
-
+// (knn_ld_packed, the loader of a packed dword of a row of d bytes: lsq_xload.h)
 // out[i] = SUM_s x_i[s]^2 (uint32: <= 258 * 255^2 < 2^24), 16 lanes per row, dot4 of each packed dword with itself
 __global__ __launch_bounds__(KNN_THREADS) void knn_norms_u8_kernel(const uint8_t *__restrict__ X, int64_t ld, int n, int d, int vec,
                                                                    uint32_t *__restrict__ out) {
@@ -364,6 +350,7 @@ int lsq_knn_launch_norms_u8(hipStream_t s, const uint8_t *X, int64_t ld, int n, 
 int lsq_knn_launch_scan(hipStream_t s, int mode, const lsq_search_input &in, const int *qsel, int q0, int nqb, int stride, int ns, const uint32_t *tau,
                         unsigned *count, int cap, uint64_t *out, int idbits, const lsq_knnm_work *pf) {
     if (mode == 0 && in.prefilter && pf && !qsel) return lsq_knnm_launch(s, in, q0, nqb, tau, count, cap, out, idbits, *pf);      // (f32 queries, no filter: lsq_adc_search)
+    if (mode == 0 && in.xnorms_s && in.qnorms_s && !qsel && !in.filtered()) return lsq_knnu_launch(s, in, q0, nqb, tau, count, cap, out, idbits);      // (uint8 x uint8, d <= 258: lsq_adc_search)
     const int n = in.rows_walked(), d = in.d, ldb = in.bstride, ldq = in.qstride;      // compact road of a filter: the allowed rows
     const int tiles = (nqb + KNN_QT - 1) / KNN_QT;
     const int total = mode == 0 ? n : ns;

@@ -100,6 +100,21 @@ __device__ inline lsq_f32x4 lsq_widen4(uint32_t w) {
 // p[0 .. 3] as one packed dword (component e in byte e); p 4-byte aligned
 __device__ inline uint32_t lsq_ld4_packed(const uint8_t *p) { return *reinterpret_cast<const uint32_t *>(p); }
 
+// Dword w (components 4 w .. 4 w + 3) of a row of d bytes, component e in byte e, zero from the d-th component on.  vec (lsq_xload.h's rule: the
+// matrix pointer and its row pitch in bytes are multiples of 4): one dword load where all four components exist.  Everything else -- a matrix at any
+// byte offset, an odd pitch, and the LAST, partial dword of any row -- travels as single bytes: nothing at or past the d-th byte of a row is loaded,
+// so nothing outside [base, base + (n - 1) ldb + d) is, and there is no padding to mask.
+__device__ inline uint32_t knn_ld_packed(const uint8_t *__restrict__ row, int w, int d, bool vec) {
+    const int b0 = 4 * w, valid = d - b0;
+    if (valid <= 0) return 0u;
+    if (vec && valid >= 4) return lsq_ld4_packed(row + b0);
+    uint32_t v = 0u;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (e < valid) v |= (uint32_t)row[b0 + e] << (8 * e);
+    return v;
+}
+
 // p[0 .. 3] widened; float: p 16-byte aligned, uint8_t: p 4-byte aligned
 __device__ inline lsq_f32x4 lsq_ld4(const float *p) { return *reinterpret_cast<const lsq_f32x4 *>(p); }
 __device__ inline lsq_f32x4 lsq_ld4(const uint8_t *p) { return lsq_widen4(lsq_ld4_packed(p)); }

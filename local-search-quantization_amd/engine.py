@@ -951,6 +951,11 @@ class Index(_Handle):
         switched_off, served / reason (why the direct road was taken), kappa, eta, norms_ms / mfma_ms / recheck_ms (with profile=True)"""
         return self._info("lsq_index_get_knn_prefilter_info", _lib.KnnPrefilterInfo)
 
+    def knn_mfma_info(self):
+        """what the i8 matrix-core road (Engine.set_option("knn_u8_mfma", 1)) did in the last knn call of this index: served, reason (_lib.KNN_MFMA_*: why
+        not), pairs, kept, norms_ms / scan_ms (with profile=True)"""
+        return self._info("lsq_index_get_knn_mfma_info", _lib.KnnMfmaInfo)
+
     def knn_info(self):
         """what the last knn call did: queries, rows, batches, fallback_queries, exhaustive, int_road, norms_ms / scan_ms / select_ms (with profile=True)"""
         return self._info("lsq_index_get_knn_info", _lib.IndexKnnInfo)

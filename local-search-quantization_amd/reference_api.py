@@ -286,14 +286,16 @@ def knn_prefilter_bound(d):
     return np.float32(kappa.value), np.float32(eta.value)
 
 
-def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0, prefilter=False):
+def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0, prefilter=False, u8_mfma=False):
     """Exact k-NN, the ground truth of a recall figure (what the reference reads from sift_groundtruth.ivecs, for any base).
     X_base (d, n), X_query (d, nq) Float32 in Julia shapes, or the UInt8 matrices of bvecs_read, which are handed through un-widened (same results as
     after astype(float32), by contract).  -> dists (k, nq) float32 ascending, ids (k, nq) uint32 1-BASED, so that eval_recall(ids[0, :], idx, knn) works
     directly.  dist = ((0 + e_0^2) + e_1^2) + ..., e_s = x[s] - q[s] in f32; ties by smaller id, NaN last.
     engine=None: the host cores (lsq_knn_exact_cpu / lsq_knn_exact_u8_cpu, nthreads 0 = all); engine=<Engine>: the device -- same results bit for bit.
     prefilter=True (device only): the engine's option "knn_prefilter" is 1 for this call and 0 after it -- the MFMA pre-filter, same results bit for bit;
-    prefilter=False leaves the option as the engine has it."""
+    prefilter=False leaves the option as the engine has it.
+    u8_mfma=True (device only), likewise: option "knn_u8_mfma" is 1 for this call and 0 after it -- UInt8 base and queries up to d = 258 run their thresholded
+    pass on the i8 matrix cores, same results bit for bit; every other input is served as without it."""
     from . import _lib
     Xb, Xq = _base_rows(X_base), _base_rows(X_query)
     if Xb.shape[1] != Xq.shape[1]:
@@ -303,14 +305,17 @@ def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0, prefilter=False):
         Xq, q8 = Xq.astype(np.float32), False
     if prefilter and engine is None:
         raise ValueError("knn_exact: prefilter=True needs an engine (the pre-filter runs on the device)")
+    if u8_mfma and engine is None:
+        raise ValueError("knn_exact: u8_mfma=True needs an engine (the matrix-core road runs on the device)")
     if engine is not None:
-        if prefilter:
-            engine.set_option("knn_prefilter", 1)
+        asked = [name for name, on in (("knn_prefilter", prefilter), ("knn_u8_mfma", u8_mfma)) if on]
+        for name in asked:
+            engine.set_option(name, 1)
         try:
             dists, ids = engine.knn_exact(Xb, Xq, k)
         finally:
-            if prefilter:
-                engine.set_option("knn_prefilter", 0)
+            for name in asked:
+                engine.set_option(name, 0)
     else:
         (n, d), nq = Xb.shape, Xq.shape[0]
         dists = np.zeros((nq, k), dtype=np.float32)

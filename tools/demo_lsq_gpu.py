@@ -60,6 +60,8 @@ search.
 
 --knn-prefilter: the ground truth (exact k-NN on the device) runs with option "knn_prefilter" = 1 -- the MFMA pre-filter of csrc/lsq_knnm.hip, the same
 ids bit for bit (Index.knn_prefilter_info gives its account on a resident index).
+--knn-u8-mfma: the ground truth of a .bvecs set (uint8 base and queries) runs with option "knn_u8_mfma" = 1 -- the thresholded pass on the i8 matrix cores
+(csrc/lsq_knnu.hip), the same ids bit for bit; float data is served as without it (Index.knn_mfma_info gives the account on a resident index).
 
 needs $LSQ_DATA_DIR/sift/{sift_learn,sift_base,sift_query}.fvecs and sift_groundtruth.ivecs (TEXMEX layout).  The file's ground truth
 describes the full 10^6-vector base only: for a prefix of it (nread_base < 10^6) and for the stand-in, the ground truth is exact k-NN of the base
@@ -79,13 +81,14 @@ lsq = importlib.import_module("local-search-quantization_amd")
 
 
 KNN_PREFILTER = False      # --knn-prefilter
+KNN_U8_MFMA = False        # --knn-u8-mfma
 
 
 def ground_truth(xb, xq):
     """1-based id of each query's nearest base vector: exact k-NN on the device (lsq_knn_exact; uint8 matrices stay uint8: lsq_index_knn)"""
     t0 = time.perf_counter()
     with lsq.Engine(0) as eng:
-        _, ids = lsq.knn_exact(xb, xq, 1, engine=eng, prefilter=KNN_PREFILTER)
+        _, ids = lsq.knn_exact(xb, xq, 1, engine=eng, prefilter=KNN_PREFILTER, u8_mfma=KNN_U8_MFMA)
     print("Ground truth of %d queries in %d base vectors: %.3f s (exact k-NN on the device, %s rows)" % (xq.shape[1], xb.shape[1], time.perf_counter() - t0,
                                                                                                        xb.dtype))
     return ids[0]
@@ -225,8 +228,11 @@ BASE_FORMAT = None                               # --base-format f16 | bf16 (wit
 
 
 def main():
-    global BASE_FORMAT, KNN_PREFILTER
+    global BASE_FORMAT, KNN_PREFILTER, KNN_U8_MFMA
     argv = sys.argv[1:]
+    if "--knn-u8-mfma" in argv:
+        argv.remove("--knn-u8-mfma")
+        KNN_U8_MFMA = True
     if "--knn-prefilter" in argv:
         argv.remove("--knn-prefilter")
         KNN_PREFILTER = True

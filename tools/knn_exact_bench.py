@@ -17,6 +17,13 @@ PATH (default profiles/knn_prefilter.jsonl): the ratio direct / pre-filtered, th
 whether bits and ids equal the direct leg's.  Exit status 1 when they differ anywhere, or when on a Gaussian set the pre-filtered call is not faster than
 the direct one by more than the spread of the direct leg's five repeats.
 
+--u8 --mfma [n nq d] [--mfma-per-s R] [--dot4-lane-ops-per-s R] [--out PATH]: the third arm of --u8 -- the i8 matrix-core road (option "knn_u8_mfma",
+csrc/lsq_knnu.hip) against the dot4 road on ONE resident uint8 index (Index.knn), calls alternated in one process, device events, option "profile" off, one
+warm-up, medians of 5, k in {1, 100, 1000}; bits and ids compared on every case.  A separate pass with "profile" on records the phases (norms, sample +
+scan, selection) of either road.  R: what tools/ubench_mfma_i8.hip printed as "chip_mfma_per_s" (the matrix-core pass is then given as a fraction of its
+bound nq n ceil(d / 32) / 1024 / R) and tools/ubench_dot4.hip as "dot4_lane_ops_per_s".  One JSON line per k, appended to PATH (default
+profiles/knn_u8_mfma.jsonl).  Exit status 1 when bits or ids differ anywhere; the ratio is reported, not judged.
+
 VALU bound: three f32 element-ops (subtract, multiply, add) per (query, row, dimension), at 32 element-ops/clk/SIMD (packed f32), 4 SIMDs x 256 CUs,
 2.4 GHz: 7.86e13 element-ops/s."""
 import importlib, json, os, sys, time
@@ -124,6 +131,55 @@ def run_u8(n, nq, d, dot4_rate=None, reps=5):
     return ok
 
 
+def run_u8_mfma(n, nq, d, out_path, mfma_rate=None, dot4_rate=None, reps=5):
+    rng = np.random.default_rng(1)
+    dev = torch.device("cuda:0")
+    d8 = torch.from_numpy(rng.integers(0, 256, (n, d), dtype=np.uint8)).to(dev)
+    q8 = torch.from_numpy(rng.integers(0, 256, (nq, d), dtype=np.uint8)).to(dev)
+    ok, lines = True, []
+    with lsq.Engine(0) as eng, eng.index_dev(None, None, None, 0, base=d8) as ix:
+        def leg(on, k):
+            eng.set_option("knn_u8_mfma", on)
+            return ix.knn(q8, k)
+        for k in (1, 100, 1000):
+            eng.set_option("profile", 0)
+            ms, same = {0: [], 1: []}, True
+            for r in range(reps + 1):                               # repeat 0 is the warm-up
+                res = {}
+                for on in (0, 1):
+                    t, res[on] = _timed(lambda: leg(on, k))
+                    if r > 0:
+                        ms[on].append(t)
+                same = same and torch.equal(res[0][0].view(torch.int32), res[1][0].view(torch.int32)) and torch.equal(res[0][1], res[1][1])
+            eng.set_option("profile", 1)                            # the phases, apart from the timed calls
+            ph = {}
+            for on in (0, 1):
+                leg(on, k)
+                ph[on] = (ix.knn_info(), ix.knn_mfma_info())
+            med = {on: float(np.median(v)) for on, v in ms.items()}
+            spread = {on: max(v) - min(v) for on, v in ms.items()}
+            mf = ph[1][1]
+            ok = ok and same and mf["served"] == 1 and ph[1][0]["fallback_queries"] == ph[0][0]["fallback_queries"]
+            mfma_bound = nq * n * ((d + 31) // 32) / 1024.0 / mfma_rate * 1e3 if mfma_rate else None
+            dot4_bound = (nq * n * d / 4.0) / dot4_rate * 1e3 if dot4_rate else None
+            lines.append(json.dumps(dict(
+                search="knn_u8_mfma", n=n, nq=nq, d=d, k=k, reps=reps, dot4_ms=round(med[0], 3), mfma_ms=round(med[1], 3), dot4_spread_ms=round(spread[0], 3),
+                mfma_spread_ms=round(spread[1], 3), dot4_over_mfma=round(med[0] / med[1], 3), faster_beyond_spread=bool(med[0] - med[1] > max(spread.values())),
+                same_bits_and_ids=bool(same), served=mf["served"], pairs=mf["pairs"], kept=mf["kept"], fallback_queries=ph[1][0]["fallback_queries"],
+                dot4_phases_ms=dict(norms=round(ph[0][0]["norms_ms"], 3), sample_and_scan=round(ph[0][0]["scan_ms"], 3), select=round(ph[0][0]["select_ms"], 3)),
+                mfma_phases_ms=dict(norms=round(ph[1][0]["norms_ms"], 3), shifted_norms=round(mf["norms_ms"], 3), sample_and_scan=round(ph[1][0]["scan_ms"], 3),
+                                    mfma_pass=round(mf["scan_ms"], 3), select=round(ph[1][0]["select_ms"], 3)),
+                mfma_bound_ms=round(mfma_bound, 3) if mfma_bound else None,
+                mfma_pass_fraction_of_ubench_rate=round(mfma_bound / mf["scan_ms"], 3) if mfma_bound and mf["scan_ms"] > 0 else None,
+                dot4_bound_ms=round(dot4_bound, 3) if dot4_bound else None,
+                dot4_scan_fraction_of_ubench_rate=round(dot4_bound / ph[0][0]["scan_ms"], 3) if dot4_bound and ph[0][0]["scan_ms"] > 0 else None)))
+            print(lines[-1], flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write("\n".join(lines) + "\n")
+    return ok
+
+
 MFMA_FLOPS = 157e12                          # f32 matrix-core peak
 
 
@@ -186,11 +242,18 @@ if __name__ == "__main__":
         sys.exit(0 if run_prefilter(*(int(x) for x in (args[:2] + ["1000000", "10000"][len(args):])), out_path=out) else 1)
     if "--u8" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--u8"]
-        rate = None
-        if "--dot4-lane-ops-per-s" in args:
-            i = args.index("--dot4-lane-ops-per-s")
-            rate = float(args[i + 1])
-            del args[i:i + 2]
+        rate, opts = None, {}
+        for flag in ("--dot4-lane-ops-per-s", "--mfma-per-s", "--out"):
+            if flag in args:
+                i = args.index(flag)
+                opts[flag] = args[i + 1]
+                del args[i:i + 2]
+        rate = float(opts["--dot4-lane-ops-per-s"]) if "--dot4-lane-ops-per-s" in opts else None
+        if "--mfma" in args:
+            args.remove("--mfma")
+            out = opts.get("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "knn_u8_mfma.jsonl"))
+            mrate = float(opts["--mfma-per-s"]) if "--mfma-per-s" in opts else None
+            sys.exit(0 if run_u8_mfma(*(int(x) for x in (args[:3] + ["1000000", "10000", "128"][len(args):])), out_path=out, mfma_rate=mrate, dot4_rate=rate) else 1)
         sys.exit(0 if run_u8(*(int(x) for x in (args[:3] + ["1000000", "10000", "128"][len(args):])), dot4_rate=rate) else 1)
     if len(sys.argv) > 1:
         run(*(int(x) for x in (sys.argv[1:5] + ["1000000", "10000", "128", "100"][len(sys.argv) - 1:])))
