@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 2800
+#define LSQ_VERSION 2900
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -142,6 +142,8 @@ LSQ_API int lsq_set_stream(lsq_ctx *ctx, void *hip_stream);
  *        context) pre-filters the thresholded road on the matrix cores.  Same results, bit for bit.
  *   "knn_u8_mfma" (0/1, default 0; since v2800, (3r)): 1 = lsq_index_knn runs the thresholded pass of its integer road (uint8 rows x uint8 queries, d <= 258)
  *                    on the i8 matrix cores: the same results bit for bit.  As for "knn_prefilter", any non-zero value is 1.
+ *   "knn_prefilter_half" (0/1, default 0; since v2900, (3s)): 1 = where "knn_prefilter" is on and serves the call, f16 / bf16 base rows run the pre-filter's
+ *                    matrix-core pass on v_mfma_f32_32x32x16_bf16 with the queries split into two bf16 pieces.  Same results, bit for bit; any non-zero value is 1.
  *   "knn_prefilter_cap" (default 0): pending pairs per query of the pre-filter; 0 = automatic (twice the list capacity).  A test hook: same results.
  *   "range_batch" (default 0): records per fill batch of lsq_index_range_search on every lsq_index created on this context; 0 = automatic (2^28).  A
  *        test hook: small shapes cross batch boundaries, and a query larger than the budget is a batch of its own.  Same results.
@@ -1090,6 +1092,41 @@ typedef struct lsq_knn_mfma_info {
     double norms_ms, scan_ms;    /* with option "profile" = 1: the shifted norms, the matrix-core pass */
 } lsq_knn_mfma_info;
 LSQ_API int lsq_index_get_knn_mfma_info(lsq_index *ix, lsq_knn_mfma_info *out);
+
+/* ---- (3s) the pre-filter of exact k-NN on half-precision rows, on the 16-bit matrix cores (csrc/lsq_knnh.hip; since v2900) -------------------------------------
+ * THE REFERENCE HAS NO COUNTERPART.  Option "knn_prefilter_half" = 1 acts only where "knn_prefilter" = 1 serves the call (3q) AND the base rows of the index are
+ * f16 or bf16 (3o): the matrix-core pass of (3q) then runs on v_mfma_f32_32x32x16_bf16 instead of widening the rows to f32.  Each f32 query component q is
+ * split once per batch into q1 = bf16(q), q2 = bf16(q - q1) (round to nearest even); bf16 rows enter as stored, an f16 value as x_hi = bf16(x) and
+ * x_lo = x - x_hi (both exact); the dot product is the sum of the products (x, q1) (x, q2), or (x_hi, q1) (x_hi, q2) (x_lo, q1).  Norms, pending lists, the
+ * recheck by the direct chain, overflow and redo are (3q)'s.  THE RESULT DOES NOT CHANGE, NOT BY A BIT: the pair is dropped iff
+ * a > tau_q + kappa^h_d (Nx + Nq) + eta^h_d  with  kappa^h_d = ((4 d + 32) 2^-24 + rho + (3 ceil(d / 16) + 3) 2^-19) 1.01  (rounded up to f32; rho = 2^-16 for bf16 rows, 2^-15 for f16 rows) and
+ * eta^h_d = (8 d + 64) 2^-120  (lsq_knn_prefilter_half_bound; proof: DESIGN 4.31).  THE TERM 2^-19 IS A MODEL, NOT A DOCUMENTED PROPERTY: the worst error of
+ * one instruction measured against float64 on adversarial inputs (2^-22.4 of |c| + SUM |a b|; tools/ubench_mfma_bf16.hip) times 8, rounded up to a power of
+ * two.  The road's exactness rests on that model with its margin; the option is off by default.
+ *   not served  "knn_prefilter" off or itself not serving (filter, uint8 queries, exhaustive road, d > LSQ_KNN_PREFILTER_MAX_D), f32 or uint8 rows: the call
+ *               runs as without the option and says why (reason).  Redo passes of overflowed queries are always direct.
+ *   lsq_knn_prefilter_half_bound   host only, no context.  LSQ_EINVAL: d outside 1 .. LSQ_KNN_PREFILTER_MAX_D, base_format neither LSQ_BASE_F16 nor
+ *               LSQ_BASE_BF16, a null pointer.
+ *   lsq_index_get_knn_prefilter_half_info   the account of the last lsq_index_knn call of the index (written by every call).  lsq_knn_prefilter_info (3q) is
+ *               written as before (its kappa / eta / mfma_ms are then this road's).  The context forms lsq_knn_exact / _dev take f32 rows: never served. */
+enum { LSQ_KNN_PREFILTER_HALF_SERVED = 0,          /* reason: */
+       LSQ_KNN_PREFILTER_HALF_NOT_ASKED = 1,       /* option "knn_prefilter_half" is 0 */
+       LSQ_KNN_PREFILTER_HALF_PREFILTER_OFF = 2,   /* option "knn_prefilter" is 0 */
+       LSQ_KNN_PREFILTER_HALF_FILTERED = 3,        /* a row filter is in force */
+       LSQ_KNN_PREFILTER_HALF_U8_QUERIES = 4,      /* uint8 queries */
+       LSQ_KNN_PREFILTER_HALF_EXHAUSTIVE = 5,      /* the exhaustive road: n <= 65536, a large nn, or option "linscan_exhaustive" */
+       LSQ_KNN_PREFILTER_HALF_WIDE = 6,            /* d > LSQ_KNN_PREFILTER_MAX_D */
+       LSQ_KNN_PREFILTER_HALF_ROWS_NOT_HALF = 7 }; /* the base rows are f32 or uint8 */
+typedef struct lsq_knn_prefilter_half_info {
+    int64_t served, reason;      /* served 1: the matrix-core pass ran on the 16-bit tile; 0: reason = LSQ_KNN_PREFILTER_HALF_* */
+    int64_t format;              /* LSQ_BASE_F16 or LSQ_BASE_BF16 (0 when not served) */
+    int64_t pieces;              /* bf16 products per dimension in the tile's K: 2 (bf16 rows) or 3 (f16 rows) */
+    int64_t pairs, pending, kept, overflow_queries, switched_off;      /* as lsq_knn_prefilter_info */
+    double kappa, eta;           /* the window's constants at this d and format (0 when not served) */
+    double split_ms, scan_ms, recheck_ms;      /* with option "profile" = 1: the query split, the MFMA pass, the recheck */
+} lsq_knn_prefilter_half_info;
+LSQ_API int lsq_knn_prefilter_half_bound(int d, int base_format, float *kappa, float *eta);
+LSQ_API int lsq_index_get_knn_prefilter_half_info(lsq_index *ix, lsq_knn_prefilter_half_info *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

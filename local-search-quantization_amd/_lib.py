@@ -66,6 +66,17 @@ class KnnMfmaInfo(_Struct):
     _fields_ = [("served", C.c_int64), ("reason", C.c_int64), ("pairs", C.c_int64), ("kept", C.c_int64), ("norms_ms", C.c_double), ("scan_ms", C.c_double)]
 
 
+class KnnPrefilterHalfInfo(_Struct):
+    _fields_ = [("served", C.c_int64), ("reason", C.c_int64), ("format", C.c_int64), ("pieces", C.c_int64), ("pairs", C.c_int64), ("pending", C.c_int64),
+                ("kept", C.c_int64), ("overflow_queries", C.c_int64), ("switched_off", C.c_int64), ("kappa", C.c_double), ("eta", C.c_double),
+                ("split_ms", C.c_double), ("scan_ms", C.c_double), ("recheck_ms", C.c_double)]
+
+
+# lsq_knn_prefilter_half_info.reason: why a call's pre-filter pass stayed off the 16-bit tile (0: it did not)
+(KNN_PREFILTER_HALF_NOT_ASKED, KNN_PREFILTER_HALF_PREFILTER_OFF, KNN_PREFILTER_HALF_FILTERED, KNN_PREFILTER_HALF_U8_QUERIES,
+ KNN_PREFILTER_HALF_EXHAUSTIVE, KNN_PREFILTER_HALF_WIDE, KNN_PREFILTER_HALF_ROWS_NOT_HALF) = 1, 2, 3, 4, 5, 6, 7
+
+
 # lsq_knn_mfma_info.reason: why a call's thresholded pass stayed off the i8 matrix cores (0: it did not)
 KNN_MFMA_NOT_ASKED, KNN_MFMA_NOT_INTEGER_ROAD, KNN_MFMA_FILTERED, KNN_MFMA_EXHAUSTIVE = 1, 2, 3, 4
 
@@ -339,6 +350,9 @@ SIGNATURES = {
     "lsq_index_get_knn_prefilter_info": (_i, [_vp, C.POINTER(KnnPrefilterInfo)]),
     # exact k-NN of 8-bit sets on the i8 matrix cores (since v2800): what it did in the last knn call of an index
     "lsq_index_get_knn_mfma_info": (_i, [_vp, C.POINTER(KnnMfmaInfo)]),
+    # the pre-filter of exact k-NN on half-precision rows, on the 16-bit matrix cores (since v2900): its window, what it did in the last knn call of an index
+    "lsq_knn_prefilter_half_bound": (_i, [_i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "lsq_index_get_knn_prefilter_half_info": (_i, [_vp, C.POINTER(KnnPrefilterHalfInfo)]),
     # the beam-search encoder on resident codebooks (since v1600)
     "lsq_encoder_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(EncoderDesc)]),
     "lsq_encoder_destroy": (_i, [_vp]),
@@ -380,7 +394,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 2800     # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 2900     # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

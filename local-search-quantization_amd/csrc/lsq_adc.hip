@@ -479,15 +479,15 @@ struct lsq_adc_state {
     DevBuf h_db, h_q, h_tables, h_norms, h_dists, h_idx;
     PhaseClock<5> clock;                         // table, sample, scan, selection of one batch
     // the pre-filter of exact k-NN (lsq_knnm.hip): the call's norms, a batch's pending lists and their counters; its norms / MFMA / recheck clock
-    DevBuf pf_nx, pf_nq, pf_pend, pf_pcount;
-    PhaseClock<3> pf_clock;
+    DevBuf pf_nx, pf_nq, pf_pend, pf_pcount, pf_qpieces;      // (pf_qpieces: the bf16 query pieces of a batch on the 16-bit tile, lsq_knnh.hip)
+    PhaseClock<4> pf_clock;
     bool attr_set = false;
 };
 
 void lsq_adc_free(lsq_adc_state *st) {
     if (!st) return;
     DevBuf *all[] = {&st->lut, &st->keys_a, &st->keys_b, &st->tau, &st->count, &st->seg, &st->fail, &st->qsel, &st->tmp,
-                  &st->h_db, &st->h_q, &st->h_tables, &st->h_norms, &st->h_dists, &st->h_idx, &st->pf_nx, &st->pf_nq, &st->pf_pend, &st->pf_pcount};
+                  &st->h_db, &st->h_q, &st->h_tables, &st->h_norms, &st->h_dists, &st->h_idx, &st->pf_nx, &st->pf_nq, &st->pf_pend, &st->pf_pcount, &st->pf_qpieces};
     for (DevBuf *b : all) b->release();
     st->clock.release();
     st->pf_clock.release();
@@ -624,7 +624,7 @@ struct Plan { int ns, stride, r, cap; bool exhaustive; };
 
 // the pre-filter of exact k-NN in one call (lsq_knnm.hip): its window, the pending capacity, where its counts go.  run_batch takes that road for a batch
 // whose input says prefilter (never a qsel pass) and reports the queries whose pending list overflowed as fail = LSQ_KNNM_FAIL_OVERFLOW
-struct PfRun { float kappa, eta; int pcap; lsq_knn_prefilter_info *info; bool timed; };
+struct PfRun { float kappa, eta; int pcap; lsq_knn_prefilter_info *info; bool timed; bool half; double split_ms; };      // half: the 16-bit tile (lsq_knnh.hip)
 
 // Threshold rank and list capacity.  The nn-th neighbour of a query has, among the ns sampled codes, a rank that is Binomial(ns, nn / n) ~ Poisson(ks),
 // ks = nn ns / n, on exchangeable data; the list misses it iff that rank reaches r.  r = ks + 5.6 sqrt(ks) + 6 puts this below ~1e-8 per query (small
@@ -647,7 +647,7 @@ Plan make_plan(int n, int nn, int force_exhaustive) {
 
 template <int QT>
 int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const lsq_search_input &in, const int *qsel, int q0, int nqb, int nn,
-              const Plan &P, int *h_fail, lsq_linscan_stats *stats, bool timed, const PfRun *pf = nullptr) {
+              const Plan &P, int *h_fail, lsq_linscan_stats *stats, bool timed, PfRun *pf = nullptr) {
     // n: the record slots of a query on the exhaustive road.  Under a filter's compact road the walk is over the allowed rows, padded to nn slots where
     // they are fewer; a filtered call sorts on one bit more, the bit of the record of an id outside the base (what filtered rows and padding leave as)
     const int n = in.filter_rows ? std::max(in.filter_count, nn) : in.n;
@@ -691,6 +691,10 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ls
             LSQ_TRY(st->pf_pcount.ensure(sizeof(unsigned) * (size_t)nqb));
             w.nx = st->pf_nx.as<float>(); w.nq = st->pf_nq.as<float>(); w.pend = st->pf_pend.as<uint32_t>(); w.pcount = st->pf_pcount.as<unsigned>();
             w.pcap = pf->pcap; w.kappa = pf->kappa; w.eta = pf->eta; w.clock = &st->pf_clock;
+            if (pf->half) {
+                LSQ_TRY(st->pf_qpieces.ensure((size_t)lsq_knnh_scratch_bytes(nqb, in.d)));
+                w.qpieces = st->pf_qpieces.as<uint16_t>();
+            }
             LSQ_TRY(st->pf_clock.begin(pf->timed));
         }
         LSQ_TRY((launch_producer<QT, 0>(s, st->lut.as<float>(), in, qsel, q0, nqb, 1, n, st->tau.as<uint32_t>(), st->count.as<unsigned>(), P.cap,
@@ -713,9 +717,10 @@ int run_batch(lsq_adc_state *st, hipStream_t s, float *dists, int *idx, const ls
                 fi->kept += hc[(size_t)t];
                 if (hp[(size_t)t] > (unsigned)w.pcap) fi->overflow_queries += 1;
             }
-            float ms[2];
+            float ms[3];
             LSQ_TRY(st->pf_clock.read(ms));
-            fi->mfma_ms += ms[0]; fi->recheck_ms += ms[1];
+            if (pf->half) { pf->split_ms += ms[0]; fi->mfma_ms += ms[1]; fi->recheck_ms += ms[2]; }
+            else { fi->mfma_ms += ms[0]; fi->recheck_ms += ms[1]; }
         }
         if (stats) {
             std::vector<unsigned> hc((size_t)nqb);
@@ -763,7 +768,10 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
         fi->reason = !in.prefilter ? LSQ_KNN_PREFILTER_NOT_ASKED : in.filtered() ? LSQ_KNN_PREFILTER_FILTERED : in.q_u8 ? LSQ_KNN_PREFILTER_U8_QUERIES
                    : P.exhaustive ? LSQ_KNN_PREFILTER_EXHAUSTIVE : in.d > LSQ_KNN_PREFILTER_MAX_D ? LSQ_KNN_PREFILTER_WIDE : LSQ_KNN_PREFILTER_SERVED;
         if (fi->reason == LSQ_KNN_PREFILTER_SERVED && nq > 0) {
-            LSQ_TRY(lsq_knn_prefilter_bound(in.d, &pf.kappa, &pf.eta));
+            // half-precision rows may take the 16-bit tile (lsq_knnh.hip): its own window, everything else shared
+            pf.half = in.prefilter_half && lsq_base_is_half(lsq_base_format(in.base_u8));
+            if (pf.half) LSQ_TRY(lsq_knn_prefilter_half_bound(in.d, lsq_base_format(in.base_u8), &pf.kappa, &pf.eta));
+            else LSQ_TRY(lsq_knn_prefilter_bound(in.d, &pf.kappa, &pf.eta));
             // twice the list capacity: a third buffer of P.cap record-sized entries per query beside the two record buffers (the batch rule below)
             const int64_t pcap = opt.prefilter_cap > 0 ? opt.prefilter_cap : 2 * (int64_t)P.cap;
             pf.pcap = (int)std::min<int64_t>(pcap, n);
@@ -776,9 +784,22 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
             LSQ_TRY(st->pf_clock.mark(s));
             LSQ_TRY(lsq_knnm_launch_norms(s, in, nq, st->pf_nx.as<float>(), st->pf_nq.as<float>()));
             LSQ_TRY(st->pf_clock.mark(s));
-            float ms[2];
+            float ms[3];
             LSQ_TRY(st->pf_clock.read(ms));
             fi->norms_ms = ms[0];
+        }
+    }
+    if (in.kind == LSQ_SEARCH_EXACT && opt.pfh_info) {
+        lsq_knn_prefilter_half_info *hi = opt.pfh_info;
+        *hi = lsq_knn_prefilter_half_info{};
+        const int pr = opt.pf_info ? (int)opt.pf_info->reason : LSQ_KNN_PREFILTER_NOT_ASKED;
+        hi->reason = !in.prefilter_half ? LSQ_KNN_PREFILTER_HALF_NOT_ASKED : pr == LSQ_KNN_PREFILTER_NOT_ASKED ? LSQ_KNN_PREFILTER_HALF_PREFILTER_OFF
+                   : pr == LSQ_KNN_PREFILTER_FILTERED ? LSQ_KNN_PREFILTER_HALF_FILTERED : pr == LSQ_KNN_PREFILTER_U8_QUERIES ? LSQ_KNN_PREFILTER_HALF_U8_QUERIES
+                   : pr == LSQ_KNN_PREFILTER_EXHAUSTIVE ? LSQ_KNN_PREFILTER_HALF_EXHAUSTIVE : pr == LSQ_KNN_PREFILTER_WIDE ? LSQ_KNN_PREFILTER_HALF_WIDE
+                   : !lsq_base_is_half(lsq_base_format(in.base_u8)) ? LSQ_KNN_PREFILTER_HALF_ROWS_NOT_HALF : LSQ_KNN_PREFILTER_HALF_SERVED;
+        if (pf.half) {
+            hi->served = 1; hi->format = lsq_base_format(in.base_u8); hi->pieces = hi->format == LSQ_BASE_F16 ? 3 : 2;
+            hi->kappa = pf.kappa; hi->eta = pf.eta;
         }
     }
     // the i8 matrix-core road of 8-bit sets (lsq_knnu.hip): MODE 0 of the thresholded road, no filter.  The caller has said whether it was asked for
@@ -790,7 +811,9 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
     }
     const bool u8_served = opt.u8_info && opt.u8_info->served;
     if (!u8_served) cur.xnorms_s = cur.qnorms_s = nullptr;
-    int64_t qb = lsq_adc_batch_queries(per_query + (cur.prefilter ? (pf.pcap + 1) / 2 : 0));   // two key buffers of per_query entries per query; whole tiles of 16 queries
+    // (the 16-bit tile's query pieces: 4 bytes per padded dimension and query, counted in record pairs of 16 bytes like the rest)
+    const int64_t piece_units = pf.half ? ((in.d + 15) / 16 * 16 + 3) / 4 : 0;
+    int64_t qb = lsq_adc_batch_queries(per_query + (cur.prefilter ? (pf.pcap + 1) / 2 + piece_units : 0));   // two key buffers of per_query entries per query; whole tiles of 16 queries
     if (qb > 16) qb &= ~(int64_t)15;
     std::vector<int> h_fail;
     std::vector<int> failed, redo;
@@ -856,6 +879,12 @@ int lsq_adc_search(hipStream_t s, lsq_adc_state **pst, float *dists, int *idx, c
             if (stats) stats->batches += 1;
         }
         if (stats) stats->fallback_queries += (int64_t)failed.size();
+    }
+    if (pf.half && opt.pfh_info) {                  // the account of the 16-bit tile: 4.29's counters of this call, and its own split phase
+        lsq_knn_prefilter_half_info *hi = opt.pfh_info;
+        const lsq_knn_prefilter_info *fi = pf.info;
+        hi->pairs = fi->pairs; hi->pending = fi->pending; hi->kept = fi->kept; hi->overflow_queries = fi->overflow_queries; hi->switched_off = fi->switched_off;
+        hi->split_ms = pf.split_ms; hi->scan_ms = fi->mfma_ms; hi->recheck_ms = fi->recheck_ms;
     }
     if (stats) { stats->queries += nq; stats->codes = n; stats->exhaustive = P.exhaustive ? 1 : 0; stats->threshold_rank = P.r; stats->list_capacity = P.cap; }
     LSQ_HIP(hipStreamSynchronize(s));

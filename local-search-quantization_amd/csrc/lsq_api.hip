@@ -112,6 +112,7 @@ struct lsq_ctx {
     int knn_u8_int = 1;                                // option "knn_u8_int": 0 = lsq_index_knn widens 8-bit rows and queries even where the integer road applies; a test hook
     int knn_prefilter = 0, knn_prefilter_cap = 0;      // options "knn_prefilter" (exact k-NN pre-filters the thresholded road on the matrix cores: lsq_knnm.hip) and "knn_prefilter_cap" (its pending capacity; a test hook)
     int knn_u8_mfma = 0;                               // option "knn_u8_mfma": lsq_index_knn's integer road runs its thresholded pass on the i8 matrix cores (lsq_knnu.hip)
+    int knn_prefilter_half = 0;                        // option "knn_prefilter_half": with "knn_prefilter", half-precision rows take the 16-bit tile (lsq_knnh.hip)
     lsq_knn_prefilter_info knn_pf{};                   // ... where the account of the last lsq_knn_exact / lsq_knn_exact_dev call is written (no getter yet: DESIGN 4.29)
     int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
     int64_t range_batch = 0;                           // option "range_batch": records per fill batch of lsq_index_range_search (0 = automatic); a test hook
@@ -323,6 +324,7 @@ extern "C" int lsq_set_option(lsq_ctx *c, const char *key, int64_t value) {
     else if (!strcmp(key, "knn_u8_int")) c->knn_u8_int = value != 0;
     else if (!strcmp(key, "knn_prefilter")) c->knn_prefilter = value != 0;
     else if (!strcmp(key, "knn_u8_mfma")) c->knn_u8_mfma = value != 0;
+    else if (!strcmp(key, "knn_prefilter_half")) c->knn_prefilter_half = value != 0;
     else if (!strcmp(key, "knn_prefilter_cap")) {
         if (value < 0 || value > (int64_t)INT32_MAX) { lsq_set_error("knn_prefilter_cap must lie in 0..2^31-1"); return LSQ_EINVAL; }
         c->knn_prefilter_cap = (int)value;
@@ -598,6 +600,7 @@ struct lsq_index {
     lsq_index_knn_info knn{};
     lsq_knn_mfma_info knn_mf{};                        // what the i8 matrix-core road (option "knn_u8_mfma" of the context; lsq_knnu.hip) did in the last lsq_index_knn
     lsq_knn_prefilter_info knn_pf{};                   // what the pre-filter (option "knn_prefilter" of the context; lsq_knnm.hip) did in the last lsq_index_knn
+    lsq_knn_prefilter_half_info knn_pfh{};             // what its 16-bit tile (option "knn_prefilter_half"; lsq_knnh.hip) did in the last lsq_index_knn
     lsq_filter_state *filter = nullptr;                // the row filter (lsq_filter.hip): null until lsq_index_set_filter; owned copies of THIS index
     int64_t cap_rows = 0;                              // lsq_index_add: rows the flat arrays hold without another allocation (n until the first add / reserve)
     lsq_index_growth_info grow{};
@@ -1010,6 +1013,7 @@ extern "C" int lsq_index_knn(lsq_index *ix, float *dists, int *ids, const void *
     lsq_search_input in = exact_input(ix->base, ix->base_u8, (int)ix->ldb, dq, q_u8, ldq, n, d);
     in.id_base = id_base;
     in.prefilter = c->knn_prefilter;
+    in.prefilter_half = c->knn_prefilter_half;
     const bool int_road = ix->base_u8 == 1 && q_u8 && d <= 258 && c->knn_u8_int;      // d 255^2 <= 2^24: (float)D is the chain's result
     lsq_index_knn_info info{};
     if (int_road) {
@@ -1048,7 +1052,9 @@ extern "C" int lsq_index_knn(lsq_index *ix, float *dists, int *ids, const void *
     int road = 0;
     index_apply_filter(ix, &in, &road, 8);
     lsq_filter_note_road(ix->filter, road);
-    LSQ_TRY(lsq_adc_search(s, &ix->adc, call.out_d, call.out_i, in, nq, nn, exact_opts(c, &st, &ix->knn_pf, &mf)));
+    lsq_search_opts sopt = exact_opts(c, &st, &ix->knn_pf, &mf);
+    sopt.pfh_info = &ix->knn_pfh;
+    LSQ_TRY(lsq_adc_search(s, &ix->adc, call.out_d, call.out_i, in, nq, nn, sopt));
     LSQ_TRY(call.finish());
     ix->knn_mf = mf;
     info.queries = nq; info.rows = n; info.batches = st.batches; info.fallback_queries = st.fallback_queries; info.exhaustive = st.exhaustive;
@@ -1067,6 +1073,12 @@ extern "C" int lsq_index_get_knn_info(lsq_index *ix, lsq_index_knn_info *out) {
 extern "C" int lsq_index_get_knn_prefilter_info(lsq_index *ix, lsq_knn_prefilter_info *out) {
     if (!ix || !out) { lsq_set_error("lsq_index_get_knn_prefilter_info: null argument"); return LSQ_EINVAL; }
     *out = ix->knn_pf;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_knn_prefilter_half_info(lsq_index *ix, lsq_knn_prefilter_half_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_knn_prefilter_half_info: null argument"); return LSQ_EINVAL; }
+    *out = ix->knn_pfh;
     return LSQ_OK;
 }
 

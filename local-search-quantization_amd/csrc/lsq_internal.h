@@ -342,6 +342,7 @@ struct lsq_search_input {
     const int *filter_rows = nullptr;
     int filter_count = 0;
     int prefilter = 0;                       // exact: option "knn_prefilter" -- MODE 0 of the thresholded road may run on the matrix cores (lsq_knnm.hip); lsq_adc_search decides
+    int prefilter_half = 0;                  // exact: option "knn_prefilter_half" -- with prefilter and f16 / bf16 rows, that pass runs on the 16-bit tile (lsq_knnh.hip); lsq_adc_search decides
     bool filtered() const { return filter_bits != nullptr || filter_rows != nullptr; }
     int rows_walked() const { return filter_rows ? filter_count : n; }      // rows a full scan reads
     int query_width() const { return kind == LSQ_SEARCH_PQ ? m * d : d; }      // elements of a query row that are read
@@ -358,6 +359,7 @@ struct lsq_search_opts {
     int prefilter_cap = 0;                   // option "knn_prefilter_cap": the pending capacity of the pre-filter (0 = twice the list capacity); a test hook
     lsq_knn_prefilter_info *pf_info = nullptr;      // exact searches: what the pre-filter did in this call (always written when set)
     lsq_knn_mfma_info *u8_info = nullptr;    // exact searches whose input carries shifted norms: what the i8 matrix-core road did in this call
+    lsq_knn_prefilter_half_info *pfh_info = nullptr;      // exact searches: what the 16-bit tile of the pre-filter did in this call (always written when set)
 };
 // every pointer of `in` a device pointer / a host pointer (staged: upload, search, download); dists, idx [nq][nn] likewise
 int lsq_adc_search(hipStream_t s, lsq_adc_state **st, float *dists, int *idx, const lsq_search_input &in, int nq, int nn, const lsq_search_opts &opt);
@@ -370,18 +372,24 @@ int lsq_knn_launch_scan(hipStream_t s, int mode, const lsq_search_input &in, con
                         unsigned *count, int cap, uint64_t *out, int idbits, const lsq_knnm_work *pf = nullptr);
 // ---- the MFMA pre-filter of exact k-NN (lsq_knnm.hip).  nx [n] / nq [queries of the CALL]: the squared norms (lsq_knnm_launch_norms); pend
 // [nqb][pcap] row ids and pcount [nqb] (zeroed by the launch): the pending lists of the batch; clock (optional): marked before the MFMA pass, between it and
-// the recheck, and after
+// the recheck, and after.  qpieces (optional; half-precision rows only): room for lsq_knnh_scratch_bytes -- the batch takes the 16-bit tile (lsq_knnh.hip): the
+// queries are split into it first (one more mark of the clock, before the split), and kappa / eta are lsq_knn_prefilter_half_bound's
 struct lsq_knnm_work {
     const float *nx = nullptr, *nq = nullptr;
     uint32_t *pend = nullptr; unsigned *pcount = nullptr; int pcap = 0;
     float kappa = 0.0f, eta = 0.0f;
-    PhaseClock<3> *clock = nullptr;
+    PhaseClock<4> *clock = nullptr;
+    uint16_t *qpieces = nullptr;
 };
 enum { LSQ_KNNM_FAIL_OVERFLOW = 2 };      // fail[slot] of a query whose pending list overflowed (1: the selection's own verdict on its candidate list)
 int lsq_knnm_launch_norms(hipStream_t s, const lsq_search_input &in, int nq, float *nx, float *nqv);
 int lsq_knnm_launch(hipStream_t s, const lsq_search_input &in, int q0, int nqb, const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits,
                     const lsq_knnm_work &w);
 int lsq_knnm_launch_mark(hipStream_t s, const unsigned *pcount, int pcap, int *fail, int nqb);
+// ---- the pre-filter's scan on half-precision rows (lsq_knnh.hip): the bf16 pieces of a batch's queries, [2][nqb][d padded to 16], and the tile ----
+int64_t lsq_knnh_scratch_bytes(int nqb, int d);
+int lsq_knnh_launch_split(hipStream_t s, const lsq_search_input &in, int q0, int nqb, uint16_t *scratch);
+int lsq_knnh_launch_scan(hipStream_t s, const lsq_search_input &in, int q0, int nqb, const uint32_t *tau, const lsq_knnm_work &w);
 int lsq_knn_launch_norms_u8(hipStream_t s, const uint8_t *X, int64_t ld, int n, int d, uint32_t *out);
 // ---- exact k-NN of 8-bit sets on the i8 matrix cores (lsq_knnu.hip): the shifted norms, and MODE 0 of one unfiltered batch (no qsel) ----
 int lsq_knnu_launch_norms(hipStream_t s, const uint8_t *X, int64_t ld, int n, int d, int32_t *out);

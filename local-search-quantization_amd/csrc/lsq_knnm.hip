@@ -263,10 +263,17 @@ int launch_road(hipStream_t s, const lsq_search_input &in, int q0, int nqb, cons
     per_block = (per_block + KM_T - 1) / KM_T * KM_T;
     ranges = (int)(((int64_t)n + per_block - 1) / per_block);
     LSQ_HIP(hipMemsetAsync(w.pcount, 0, sizeof(unsigned) * (size_t)nqb, s));
-    if (w.clock) LSQ_TRY(w.clock->mark(s));
-    hipLaunchKernelGGL((knnm_scan_kernel<TX>), dim3((unsigned)tiles, (unsigned)ranges), dim3(KM_THREADS), 0, s, X, (int64_t)in.bstride, Q,
-                       (int64_t)in.qstride, q0, nqb, d, n, (int)per_block, w.nx, w.nq, tau, w.kappa, w.eta, w.pcount, w.pcap, w.pend);
-    LSQ_HIP(hipGetLastError());
+    if (w.qpieces) {                                  // half-precision rows on the 16-bit tile (lsq_knnh.hip): split the queries, then its scan
+        if (w.clock) LSQ_TRY(w.clock->mark(s));
+        LSQ_TRY(lsq_knnh_launch_split(s, in, q0, nqb, w.qpieces));
+        if (w.clock) LSQ_TRY(w.clock->mark(s));
+        LSQ_TRY(lsq_knnh_launch_scan(s, in, q0, nqb, tau, w));
+    } else {
+        if (w.clock) LSQ_TRY(w.clock->mark(s));
+        hipLaunchKernelGGL((knnm_scan_kernel<TX>), dim3((unsigned)tiles, (unsigned)ranges), dim3(KM_THREADS), 0, s, X, (int64_t)in.bstride, Q,
+                           (int64_t)in.qstride, q0, nqb, d, n, (int)per_block, w.nx, w.nq, tau, w.kappa, w.eta, w.pcount, w.pcap, w.pend);
+        LSQ_HIP(hipGetLastError());
+    }
     if (w.clock) LSQ_TRY(w.clock->mark(s));
     const int rtiles = (w.pcap + KM_THREADS - 1) / KM_THREADS;
     hipLaunchKernelGGL((knnm_recheck_kernel<TX>), dim3((unsigned)rtiles, (unsigned)nqb), dim3(KM_THREADS), 0, s, X, (int64_t)in.bstride, Q,

@@ -951,6 +951,12 @@ class Index(_Handle):
         switched_off, served / reason (why the direct road was taken), kappa, eta, norms_ms / mfma_ms / recheck_ms (with profile=True)"""
         return self._info("lsq_index_get_knn_prefilter_info", _lib.KnnPrefilterInfo)
 
+    def knn_prefilter_half_info(self):
+        """what the 16-bit tile of the pre-filter (Engine.set_option("knn_prefilter_half", 1), with "knn_prefilter") did in the last knn call of this index:
+        served, reason (_lib.KNN_PREFILTER_HALF_*: why not), format, pieces, pairs, pending, kept, overflow_queries, switched_off, kappa, eta,
+        split_ms / scan_ms / recheck_ms (with profile=True)"""
+        return self._info("lsq_index_get_knn_prefilter_half_info", _lib.KnnPrefilterHalfInfo)
+
     def knn_mfma_info(self):
         """what the i8 matrix-core road (Engine.set_option("knn_u8_mfma", 1)) did in the last knn call of this index: served, reason (_lib.KNN_MFMA_*: why
         not), pairs, kept, norms_ms / scan_ms (with profile=True)"""

@@ -286,7 +286,17 @@ def knn_prefilter_bound(d):
     return np.float32(kappa.value), np.float32(eta.value)
 
 
-def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0, prefilter=False, u8_mfma=False):
+def knn_prefilter_half_bound(d, base_format):
+    """-> (kappa, eta) float32: the window of the pre-filter's 16-bit tile at width d on "f16" / "bf16" base rows (lsq_knn_prefilter_half_bound)"""
+    from . import _lib
+    from .engine import base_format_code
+    kappa, eta = C.c_float(), C.c_float()
+    code = base_format_code(base_format) if isinstance(base_format, str) else base_format
+    _lib.check(_lib.load().lsq_knn_prefilter_half_bound(int(d), int(code or 0), C.byref(kappa), C.byref(eta)))
+    return np.float32(kappa.value), np.float32(eta.value)
+
+
+def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0, prefilter=False, u8_mfma=False, prefilter_half=False, base_format=None):
     """Exact k-NN, the ground truth of a recall figure (what the reference reads from sift_groundtruth.ivecs, for any base).
     X_base (d, n), X_query (d, nq) Float32 in Julia shapes, or the UInt8 matrices of bvecs_read, which are handed through un-widened (same results as
     after astype(float32), by contract).  -> dists (k, nq) float32 ascending, ids (k, nq) uint32 1-BASED, so that eval_recall(ids[0, :], idx, knn) works
@@ -295,7 +305,10 @@ def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0, prefilter=False, u
     prefilter=True (device only): the engine's option "knn_prefilter" is 1 for this call and 0 after it -- the MFMA pre-filter, same results bit for bit;
     prefilter=False leaves the option as the engine has it.
     u8_mfma=True (device only), likewise: option "knn_u8_mfma" is 1 for this call and 0 after it -- UInt8 base and queries up to d = 258 run their thresholded
-    pass on the i8 matrix cores, same results bit for bit; every other input is served as without it."""
+    pass on the i8 matrix cores, same results bit for bit; every other input is served as without it.
+    base_format="f16" / "bf16" (device only): THE BASE IS NARROWED FIRST (round to nearest even) and the result is the exact k-NN of the NARROWED rows, not of
+    X_base -- what a resident index with half-precision rows returns.  prefilter_half=True (with prefilter=True and base_format): option "knn_prefilter_half" is
+    1 for this call and 0 after it -- the pre-filter runs on the 16-bit matrix cores, same results bit for bit as without it on the same narrowed rows."""
     from . import _lib
     Xb, Xq = _base_rows(X_base), _base_rows(X_query)
     if Xb.shape[1] != Xq.shape[1]:
@@ -307,12 +320,21 @@ def knn_exact(X_base, X_query, k, *, engine=None, nthreads=0, prefilter=False, u
         raise ValueError("knn_exact: prefilter=True needs an engine (the pre-filter runs on the device)")
     if u8_mfma and engine is None:
         raise ValueError("knn_exact: u8_mfma=True needs an engine (the matrix-core road runs on the device)")
+    if (prefilter_half or base_format is not None) and engine is None:
+        raise ValueError("knn_exact: prefilter_half / base_format need an engine (half-precision rows live on the device)")
+    if prefilter_half and (not prefilter or base_format is None):
+        raise ValueError("knn_exact: prefilter_half=True needs prefilter=True and base_format=\"f16\" / \"bf16\"")
     if engine is not None:
-        asked = [name for name, on in (("knn_prefilter", prefilter), ("knn_u8_mfma", u8_mfma)) if on]
+        asked = [name for name, on in (("knn_prefilter", prefilter), ("knn_u8_mfma", u8_mfma), ("knn_prefilter_half", prefilter_half)) if on]
         for name in asked:
             engine.set_option(name, 1)
         try:
-            dists, ids = engine.knn_exact(Xb, Xq, k)
+            if base_format is not None:
+                with engine.index(None, None, None, 0, base=Xb, base_format=base_format) as ix:
+                    dists, ids = ix.knn(Xq, k)
+                ids = np.asarray(ids).astype(np.uint32)
+            else:
+                dists, ids = engine.knn_exact(Xb, Xq, k)
         finally:
             for name in asked:
                 engine.set_option(name, 0)

@@ -62,6 +62,9 @@ search.
 ids bit for bit (Index.knn_prefilter_info gives its account on a resident index).
 --knn-u8-mfma: the ground truth of a .bvecs set (uint8 base and queries) runs with option "knn_u8_mfma" = 1 -- the thresholded pass on the i8 matrix cores
 (csrc/lsq_knnu.hip), the same ids bit for bit; float data is served as without it (Index.knn_mfma_info gives the account on a resident index).
+--knn-prefilter-half: beside the ground truth, the exact k-NN of the base NARROWED to half precision (--base-format, default bf16) is computed with options
+"knn_prefilter" and "knn_prefilter_half" = 1 -- the pre-filter on the 16-bit matrix cores (csrc/lsq_knnh.hip) -- and the share of queries whose nearest
+neighbour it shares with the ground truth is printed: what narrowing costs, not the pre-filter (float data only).
 
 needs $LSQ_DATA_DIR/sift/{sift_learn,sift_base,sift_query}.fvecs and sift_groundtruth.ivecs (TEXMEX layout).  The file's ground truth
 describes the full 10^6-vector base only: for a prefix of it (nread_base < 10^6) and for the stand-in, the ground truth is exact k-NN of the base
@@ -82,6 +85,7 @@ lsq = importlib.import_module("local-search-quantization_amd")
 
 KNN_PREFILTER = False      # --knn-prefilter
 KNN_U8_MFMA = False        # --knn-u8-mfma
+KNN_PREFILTER_HALF = False # --knn-prefilter-half
 
 
 def ground_truth(xb, xq):
@@ -91,6 +95,12 @@ def ground_truth(xb, xq):
         _, ids = lsq.knn_exact(xb, xq, 1, engine=eng, prefilter=KNN_PREFILTER, u8_mfma=KNN_U8_MFMA)
     print("Ground truth of %d queries in %d base vectors: %.3f s (exact k-NN on the device, %s rows)" % (xq.shape[1], xb.shape[1], time.perf_counter() - t0,
                                                                                                        xb.dtype))
+    if KNN_PREFILTER_HALF and xb.dtype != np.uint8:
+        fmt = BASE_FORMAT or "bf16"
+        with lsq.Engine(0) as eng:
+            _, hids = lsq.knn_exact(xb, xq, 1, engine=eng, prefilter=True, prefilter_half=True, base_format=fmt)
+        print("Exact k-NN of the base narrowed to %s (16-bit pre-filter): nearest neighbour shared with the ground truth for %.2f%% of the queries"
+              % (fmt, 100.0 * float(np.mean(hids[0] == ids[0]))))
     return ids[0]
 
 
@@ -228,8 +238,11 @@ BASE_FORMAT = None                               # --base-format f16 | bf16 (wit
 
 
 def main():
-    global BASE_FORMAT, KNN_PREFILTER, KNN_U8_MFMA
+    global BASE_FORMAT, KNN_PREFILTER, KNN_U8_MFMA, KNN_PREFILTER_HALF
     argv = sys.argv[1:]
+    if "--knn-prefilter-half" in argv:
+        argv.remove("--knn-prefilter-half")
+        KNN_PREFILTER_HALF = True
     if "--knn-u8-mfma" in argv:
         argv.remove("--knn-u8-mfma")
         KNN_U8_MFMA = True
@@ -242,8 +255,8 @@ def main():
         del argv[at:at + 2]
         if BASE_FORMAT not in ("f16", "bf16"):
             raise SystemExit("--base-format takes f16 or bf16, got %r" % BASE_FORMAT)
-        if "--rerank" not in argv:
-            raise SystemExit("--base-format needs --rerank L")
+        if "--rerank" not in argv and not KNN_PREFILTER_HALF:
+            raise SystemExit("--base-format needs --rerank L or --knn-prefilter-half")
     shortlist = 0
     if "--rerank" in argv:
         at = argv.index("--rerank")

@@ -17,6 +17,12 @@ PATH (default profiles/knn_prefilter.jsonl): the ratio direct / pre-filtered, th
 whether bits and ids equal the direct leg's.  Exit status 1 when they differ anywhere, or when on a Gaussian set the pre-filtered call is not faster than
 the direct one by more than the spread of the direct leg's five repeats.
 
+--prefilter --half [n nq] [--mfma-per-s R] [--out PATH]: the pre-filter's 16-bit tile (option "knn_prefilter_half", csrc/lsq_knnh.hip) on bf16 and f16 rows:
+the direct call, the f32-tile pre-filter and the 16-bit tile alternated in one process on one resident base, medians of 5 with each leg's spread; d = 128 and
+960, k in {1, 100, 1000}.  One JSON line per case appended to PATH (default profiles/knn_prefilter_half.jsonl): call times, split / norms / MFMA pass / recheck,
+pending / kept of both tiles, the pass as a fraction of R = "chip_mfma_per_s" of tools/ubench_mfma_bf16.hip, bits and ids.  Exit status 1 when bits or ids
+differ anywhere or the 16-bit tile was not served.
+
 --u8 --mfma [n nq d] [--mfma-per-s R] [--dot4-lane-ops-per-s R] [--out PATH]: the third arm of --u8 -- the i8 matrix-core road (option "knn_u8_mfma",
 csrc/lsq_knnu.hip) against the dot4 road on ONE resident uint8 index (Index.knn), calls alternated in one process, device events, option "profile" off, one
 warm-up, medians of 5, k in {1, 100, 1000}; bits and ids compared on every case.  A separate pass with "profile" on records the phases (norms, sample +
@@ -231,7 +237,71 @@ def run_prefilter(n, nq, out_path, reps=5):
     return ok
 
 
+def run_prefilter_half(n, nq, out_path, mfma_per_s, reps=5):
+    """--prefilter --half: on f16 and bf16 rows, the direct call, the f32-tile pre-filter (4.29) and the 16-bit tile (4.31) alternated on one index"""
+    dev = torch.device("cuda:0")
+    ok, lines = True, []
+    legs = {"direct": (0, 0), "f32_tile": (1, 0), "half_tile": (1, 1)}
+    for d in (128, 960):
+        for fmt in ("bf16", "f16"):
+            g = torch.Generator(device=dev).manual_seed(2900 + d)
+            rows = torch.randn((n, d), generator=g, device=dev).to(torch.float16 if fmt == "f16" else torch.bfloat16)
+            Q = torch.randn((nq, d), generator=g, device=dev)
+            with lsq.Engine(0, profile=True) as eng, eng.index_dev(None, None, None, 0, base=rows) as ix:
+                def leg(name, k):
+                    eng.set_option("knn_prefilter", legs[name][0])
+                    eng.set_option("knn_prefilter_half", legs[name][1])
+                    return ix.knn(Q, k)
+                for k in (1, 100, 1000):
+                    ms, acct, same = {name: [] for name in legs}, {}, True
+                    for r in range(reps + 1):                       # repeat 0 is the warm-up
+                        res = {}
+                        for name in legs:
+                            t, res[name] = _timed(lambda: leg(name, k))
+                            if r > 0:
+                                ms[name].append(t)
+                            acct[name] = (ix.knn_info(), ix.knn_prefilter_info(), ix.knn_prefilter_half_info())
+                        for name in ("f32_tile", "half_tile"):
+                            same = same and torch.equal(res["direct"][0].view(torch.int32), res[name][0].view(torch.int32)) and torch.equal(res["direct"][1], res[name][1])
+                    med = {name: float(np.median(v)) for name, v in ms.items()}
+                    spread = {name: max(v) - min(v) for name, v in ms.items()}
+                    hi, pf = acct["half_tile"][2], acct["f32_tile"][1]
+                    mfmas = hi["pieces"] * nq * n * ((d + 15) // 16) / 1024.0       # 32 x 32 x 16 instructions of the pass
+                    bound_ms = mfmas / mfma_per_s * 1e3 if mfma_per_s else None
+                    ok = ok and same and hi["served"] == 1
+                    lines.append(json.dumps(dict(
+                        search="knn_prefilter_half", n=n, nq=nq, d=d, k=k, rows=fmt, reps=reps, direct_ms=round(med["direct"], 3),
+                        f32_tile_ms=round(med["f32_tile"], 3), half_tile_ms=round(med["half_tile"], 3), spread_ms={a: round(b, 3) for a, b in spread.items()},
+                        f32_tile_over_half_tile=round(med["f32_tile"] / med["half_tile"], 3),
+                        faster_beyond_spread=bool(med["f32_tile"] - med["half_tile"] > max(spread["f32_tile"], spread["half_tile"])), same_bits_and_ids=same,
+                        norms_ms=round(acct["half_tile"][1]["norms_ms"], 3), split_ms=round(hi["split_ms"], 3), scan_ms=round(hi["scan_ms"], 3),
+                        recheck_ms=round(hi["recheck_ms"], 3), f32_tile_mfma_ms=round(pf["mfma_ms"], 3), f32_tile_recheck_ms=round(pf["recheck_ms"], 3),
+                        scan_bound_ms=round(bound_ms, 3) if bound_ms else None,
+                        scan_fraction_of_measured_mfma_rate=round(bound_ms / hi["scan_ms"], 3) if bound_ms and hi["scan_ms"] > 0 else None,
+                        pieces=hi["pieces"], pairs=hi["pairs"], pending=hi["pending"], kept=hi["kept"],
+                        pending_over_kept=round(hi["pending"] / hi["kept"], 4) if hi["kept"] else None,
+                        f32_tile_pending_over_kept=round(pf["pending"] / pf["kept"], 4) if pf["kept"] else None, overflow_queries=hi["overflow_queries"],
+                        switched_off=hi["switched_off"], served=hi["served"], kappa=hi["kappa"], eta=hi["eta"])))
+                    print(lines[-1], flush=True)
+            del rows, Q
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write("\n".join(lines) + "\n")
+    return ok
+
+
 if __name__ == "__main__":
+    if "--prefilter" in sys.argv[1:] and "--half" in sys.argv[1:]:
+        # --prefilter --half [n nq] [--mfma-per-s R] [--out PATH]: R = chip_mfma_per_s of tools/ubench_mfma_bf16.hip (the pass's share of that rate is reported)
+        args = [a for a in sys.argv[1:] if a not in ("--prefilter", "--half")]
+        opts = {"--out": os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "knn_prefilter_half.jsonl"), "--mfma-per-s": "0"}
+        for flag in list(opts):
+            if flag in args:
+                i = args.index(flag)
+                opts[flag] = args[i + 1]
+                del args[i:i + 2]
+        sys.exit(0 if run_prefilter_half(*(int(x) for x in (args[:2] + ["1000000", "10000"][len(args):])), out_path=opts["--out"],
+                                         mfma_per_s=float(opts["--mfma-per-s"])) else 1)
     if "--prefilter" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--prefilter"]
         out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "knn_prefilter.jsonl")
