@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 2900
+#define LSQ_VERSION 3000
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -144,6 +144,9 @@ LSQ_API int lsq_set_stream(lsq_ctx *ctx, void *hip_stream);
  *                    on the i8 matrix cores: the same results bit for bit.  As for "knn_prefilter", any non-zero value is 1.
  *   "knn_prefilter_half" (0/1, default 0; since v2900, (3s)): 1 = where "knn_prefilter" is on and serves the call, f16 / bf16 base rows run the pre-filter's
  *                    matrix-core pass on v_mfma_f32_32x32x16_bf16 with the queries split into two bf16 pieces.  Same results, bit for bit; any non-zero value is 1.
+ *   "ivf_select" (0/1, default 0; since v3000, (3g)): 1 = lsq_index_search_ivf of every lsq_index created on this context keeps each query's nn best records
+ *                    in LDS while it scans the probed lists, instead of sorting segments afterwards, where nn (or the shortlist) <= 2048.  Same results, bit for
+ *                    bit; any non-zero value is 1.
  *   "knn_prefilter_cap" (default 0): pending pairs per query of the pre-filter; 0 = automatic (twice the list capacity).  A test hook: same results.
  *   "range_batch" (default 0): records per fill batch of lsq_index_range_search on every lsq_index created on this context; 0 = automatic (2^28).  A
  *        test hook: small shapes cross batch boundaries, and a query larger than the budget is a batch of its own.  Same results.
@@ -531,6 +534,29 @@ LSQ_API int lsq_index_set_lists(lsq_index *ix, const lsq_ivf_desc *desc);
 LSQ_API int lsq_index_search_ivf(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_coarse, const float *q_exact, int nq, int ldq,
                                  int nprobe, int shortlist, int nn, int flags, int on_device);
 LSQ_API int lsq_index_get_ivf_info(lsq_index *ix, lsq_ivf_info *out);
+/* Option "ivf_select" = 1 (since v3000; csrc/lsq_ivfsel.hip): a third road, THE SAME RESULTS BIT FOR BIT.  A block owns one query; it offers
+ * every allowed row of its probed lists, nearest list first, to a pool of P = 2 pow2ceil(max(nn, 256)) records in its LDS, admits a record only below the
+ * pool's bound (all ones until nn records are held, then the nn-th), and compacts the pool to its nn smallest whenever fewer than 256 slots are free.  With
+ * 2048 or more queries in a batch the block writes the query's dists / ids row itself; with fewer, min(nprobe, ceil(2048 / queries)) blocks share a query's
+ * lists and a merge kernel streams their sorted runs through the same pool.  No head, no tail, no overflow, no redo.  Served: nn (the shortlist, when one
+ * is given) <= LSQ_IVF_SELECT_MAX_NN, every row format, filter and flag but LSQ_IVF_EVERY_RECORD, which keeps its road.  A call that is not served runs as
+ * without the option and says why.  On this road lsq_ivf_info.records counts the records offered to pools, threshold_queries, fallback_queries and
+ * tail_capacity are 0, scan_ms is the scan with its selection and select_ms the merge. */
+enum { LSQ_IVF_SELECT_MAX_NN = 2048 };
+enum { LSQ_IVF_SELECT_SERVED = 0,            /* reason: */
+       LSQ_IVF_SELECT_NOT_ASKED = 1,         /* option "ivf_select" is 0 */
+       LSQ_IVF_SELECT_NN_TOO_LARGE = 2,      /* nn (or the shortlist) > LSQ_IVF_SELECT_MAX_NN */
+       LSQ_IVF_SELECT_EVERY_RECORD = 3 };    /* the call asked for LSQ_IVF_EVERY_RECORD */
+typedef struct lsq_ivf_select_info {     /* the last lsq_index_search_ivf call */
+    int64_t queries, served_queries;     /* queries of the call; those answered from pools (all or none) */
+    int64_t reason;                      /* LSQ_IVF_SELECT_* */
+    int64_t blocks_per_query;            /* blocks that shared a query's probed lists (the largest of the call's batches) */
+    int64_t pool_records, pool_bytes;    /* P, and the LDS bytes of the pool */
+    int64_t compactions;                 /* pool compactions of all blocks, scan and merge: a function of the data and the shapes alone */
+    int64_t merged_runs;                 /* sorted runs streamed through the merge, summed over the queries (0 where a query had one block) */
+    double scan_ms, merge_ms;            /* with option "profile" = 1 */
+} lsq_ivf_select_info;
+LSQ_API int lsq_index_get_ivf_select_info(lsq_index *ix, lsq_ivf_select_info *out);
 /* The host checker and engine-less road (no context, std::thread workers, nthreads 0 = all): the index's ingredients as plain arrays -- codes [n][m],
  * codebooks [m*h][d], dbnorms [n], centroids [nlist][d], list_of_row [n] -- and the contract's result for shortlist = 0.  Tables and distances by
  * lsq_linscan_aqd_query_extra_byte's arithmetic, coarse distances by lsq_knn_exact_cpu's.  It walks the rows in their original order and knows nothing of

@@ -103,6 +103,17 @@ class IvfInfo(_Struct):
 IVF_ADD_COARSE, IVF_EVERY_RECORD, IVF_TEST_BATCH = 1, 2, 4
 
 
+class IvfSelectInfo(_Struct):
+    _fields_ = [("queries", C.c_int64), ("served_queries", C.c_int64), ("reason", C.c_int64), ("blocks_per_query", C.c_int64),
+                ("pool_records", C.c_int64), ("pool_bytes", C.c_int64), ("compactions", C.c_int64), ("merged_runs", C.c_int64),
+                ("scan_ms", C.c_double), ("merge_ms", C.c_double)]
+
+
+# lsq_ivf_select_info.reason: why a search_ivf call was not answered from pools in LDS (0: it was)
+IVF_SELECT_NOT_ASKED, IVF_SELECT_NN_TOO_LARGE, IVF_SELECT_EVERY_RECORD = 1, 2, 3
+IVF_SELECT_MAX_NN = 2048
+
+
 class IndexPackedDesc(_Struct):
     _fields_ = [("n", C.c_int64), ("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("codes", C.c_void_p), ("norm_codes", C.c_void_p),
                 ("cbnorms", C.c_void_p), ("ncb", C.c_int), ("codebooks", C.c_void_p), ("base", C.c_void_p), ("base_u8", C.c_int), ("ldb", C.c_int),
@@ -305,6 +316,7 @@ SIGNATURES = {
     "lsq_index_set_lists": (_i, [_vp, C.POINTER(IvfDesc)]),
     "lsq_index_search_ivf": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
     "lsq_index_get_ivf_info": (_i, [_vp, C.POINTER(IvfInfo)]),
+    "lsq_index_get_ivf_select_info": (_i, [_vp, C.POINTER(IvfSelectInfo)]),      # since v3000: the road of option "ivf_select"
     "lsq_ivf_search_cpu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
     # the packed index: rows of m code bytes and one norm byte (since v1800), and the selection statistics of an index's last scan
     "lsq_index_create_packed": (_i, [C.POINTER(_vp), _vp, C.POINTER(IndexPackedDesc)]),
@@ -394,7 +406,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 2900     # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 3000    # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

@@ -112,6 +112,7 @@ struct lsq_ctx {
     int knn_u8_int = 1;                                // option "knn_u8_int": 0 = lsq_index_knn widens 8-bit rows and queries even where the integer road applies; a test hook
     int knn_prefilter = 0, knn_prefilter_cap = 0;      // options "knn_prefilter" (exact k-NN pre-filters the thresholded road on the matrix cores: lsq_knnm.hip) and "knn_prefilter_cap" (its pending capacity; a test hook)
     int knn_u8_mfma = 0;                               // option "knn_u8_mfma": lsq_index_knn's integer road runs its thresholded pass on the i8 matrix cores (lsq_knnu.hip)
+    int ivf_select = 0;                                // option "ivf_select": lsq_index_search_ivf selects inside its scan (lsq_ivfsel.hip) where that road serves the call
     int knn_prefilter_half = 0;                        // option "knn_prefilter_half": with "knn_prefilter", half-precision rows take the 16-bit tile (lsq_knnh.hip)
     lsq_knn_prefilter_info knn_pf{};                   // ... where the account of the last lsq_knn_exact / lsq_knn_exact_dev call is written (no getter yet: DESIGN 4.29)
     int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
@@ -325,6 +326,7 @@ extern "C" int lsq_set_option(lsq_ctx *c, const char *key, int64_t value) {
     else if (!strcmp(key, "knn_prefilter")) c->knn_prefilter = value != 0;
     else if (!strcmp(key, "knn_u8_mfma")) c->knn_u8_mfma = value != 0;
     else if (!strcmp(key, "knn_prefilter_half")) c->knn_prefilter_half = value != 0;
+    else if (!strcmp(key, "ivf_select")) c->ivf_select = value != 0;
     else if (!strcmp(key, "knn_prefilter_cap")) {
         if (value < 0 || value > (int64_t)INT32_MAX) { lsq_set_error("knn_prefilter_cap must lie in 0..2^31-1"); return LSQ_EINVAL; }
         c->knn_prefilter_cap = (int)value;
@@ -1138,18 +1140,25 @@ extern "C" int lsq_index_search_ivf(lsq_index *ix, float *dists, int *ids, const
         int64_t ldc = 0;
         LSQ_TRY(call.rows(ix->s_qcoarse, q_coarse ? q_coarse : q_scan, sizeof(float), ldq, ix->d, false, !on_device, &dqc, &ldc));
         if (!lsq_filter_active(ix->filter))
-            return lsq_ivf_search(c->stream, ix->ivf, &ix->adc, ix->K, scan_d, scan_i, dqs, dqc, ldc, nq, nprobe, len, flags, c->search, c->profile);
+            return lsq_ivf_search(c->stream, ix->ivf, &ix->adc, ix->K, scan_d, scan_i, dqs, dqc, ldc, nq, nprobe, len, flags, c->search, c->profile, nullptr,
+                                  c->ivf_select);
         // under a filter: the inverted layout is read as it lies, with the filter's bits in layout order (the dense road; the layout has no compact form)
         const lsq_filter_view v = lsq_filter_get(ix->filter);
         if (!v.lbits) { lsq_set_error("lsq_index_search_ivf: the filter has no bits in layout order (a failed lsq_index_set_lists / _set_filter?)"); return LSQ_EINVAL; }
         lsq_filter_note_road(ix->filter, 1);
-        return lsq_ivf_search(c->stream, ix->ivf, &ix->adc, ix->K, scan_d, scan_i, dqs, dqc, ldc, nq, nprobe, len, flags, c->search, c->profile, &v);
+        return lsq_ivf_search(c->stream, ix->ivf, &ix->adc, ix->K, scan_d, scan_i, dqs, dqc, ldc, nq, nprobe, len, flags, c->search, c->profile, &v, c->ivf_select);
     });
 }
 
 extern "C" int lsq_index_get_ivf_info(lsq_index *ix, lsq_ivf_info *out) {
     if (!ix || !out) { lsq_set_error("lsq_index_get_ivf_info: null argument"); return LSQ_EINVAL; }
     lsq_ivf_get_info(ix->ivf, out);
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_ivf_select_info(lsq_index *ix, lsq_ivf_select_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_ivf_select_info: null argument"); return LSQ_EINVAL; }
+    lsq_ivf_get_select_info(ix->ivf, out);
     return LSQ_OK;
 }
 

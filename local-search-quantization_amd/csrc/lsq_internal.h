@@ -437,7 +437,29 @@ int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **st, const uint8_t *codes, c
 // rows).  adc: the index's scan state (the coarse search and the selection run on it); coarse: how the coarse search runs (the context's hooks)
 int lsq_ivf_search(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *K, float *dists, int *ids, const float *q_scan,
                    const float *q_coarse, int64_t ldc, int nq, int nprobe, int nn, int flags, const lsq_search_opts &coarse, int timed,
-                   const struct lsq_filter_view *flt = nullptr);      // flt (lsq_filter.hip): its layout-order bits restrict the answer to the allowed rows
+                   const struct lsq_filter_view *flt = nullptr,       // flt (lsq_filter.hip): its layout-order bits restrict the answer to the allowed rows
+                   int select = 0);                                   // option "ivf_select": the selection inside the scan (lsq_ivfsel.hip) where it serves the call
+void lsq_ivf_get_select_info(const lsq_ivf_state *st, lsq_ivf_select_info *out);
+
+// ---- the inverted-list scan that selects in LDS (lsq_ivfsel.hip): one batch of queries q0 .. q0 + nqb - 1, `splits` blocks per query --------------
+// What a batch is launched with: adc_lut_kernel's tiles of the batch, the inverted layout, the probed lists of the chunk's queries ([.][nprobe], indexed by
+// q0 + slot), the caller's rows dists / out_ids [.][nn] likewise.  splits > 1: part [nqb][splits][nn] records and pcount [nqb][splits], then the merge.
+// stat [2] (zeroed by the caller): records offered to pools, compactions
+struct lsq_ivfsel_call {
+    const float *LUT; int QT;
+    const uint8_t *codes; const float *norms; const int *ids; const int *off;
+    const int *probe; const float *coarse;
+    const uint32_t *lbits;                           // a filter's bits in layout order, or null
+    int nprobe, m, nn, idbits, add, packed;
+    float *dists; int *out_ids;
+    uint64_t *part; unsigned *pcount;
+    unsigned long long *stat;
+};
+int lsq_ivfsel_pool_records(int nn);                 // P = 2 pow2ceil(max(nn, 256))
+int lsq_ivfsel_splits(int nqb, int nprobe);          // blocks per query: min(nprobe, ceil(2048 / nqb))
+size_t lsq_ivfsel_lds_bytes(int m, int packed, int nn);
+int lsq_ivfsel_launch(hipStream_t s, const lsq_ivfsel_call &c, int q0, int nqb, int splits);
+int lsq_ivfsel_launch_merge(hipStream_t s, const lsq_ivfsel_call &c, int q0, int nqb, int splits);
 
 // the coarse step of lsq_ivf_search on its own, for a scan outside lsq_ivf.hip (lsq_range.hip): the probed lists of nq queries in rank order and their
 // coarse distances ([nq][nprobe], device, in st's scratch: valid until the next call on st), and the layout they index

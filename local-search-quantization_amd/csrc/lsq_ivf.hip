@@ -296,14 +296,16 @@ struct lsq_ivf_state {
     lsq_row_groups rows;                                             // set_lists' scratch: the rows grouped by list
     DevBuf alt_codes, alt_norms, alt_ids, alt_off, add_off;          // lsq_index_add: the spare half a merge is written into (it becomes the layout at the commit), the new rows' offsets
     DevBuf cd, ci, pos, plan, lut, rec_a, rec_b, seg, count, fail, qsel, head_d, head_i;      // the search's
+    DevBuf sel_stat;                                                 // option "ivf_select": the pools' two counters of a call (lsq_ivfsel.hip)
     PhaseClock<6> clock;                                             // one batch: tables, scan, selection and, thresholded, the tail's scan and selection
     lsq_ivf_info info{};
+    lsq_ivf_select_info sel{};                                       // what the road of option "ivf_select" did in the last search
 };
 
 void lsq_ivf_free(lsq_ivf_state *st) {
     if (!st) return;
     DevBuf *all[] = {&st->cent, &st->codes, &st->norms, &st->ids, &st->off, &st->alt_codes, &st->alt_norms, &st->alt_ids, &st->alt_off, &st->add_off, &st->cd, &st->ci,
-                     &st->pos, &st->plan, &st->lut, &st->rec_a, &st->rec_b, &st->seg, &st->count, &st->fail, &st->qsel, &st->head_d, &st->head_i};
+                     &st->pos, &st->plan, &st->lut, &st->rec_a, &st->rec_b, &st->seg, &st->count, &st->fail, &st->qsel, &st->head_d, &st->head_i, &st->sel_stat};
     for (DevBuf *b : all) b->release();
     st->rows.release();
     st->clock.release();
@@ -321,6 +323,7 @@ void lsq_ivf_layout(const lsq_ivf_state *st, const int **ids, const int **off) {
 const float *lsq_ivf_centroids(const lsq_ivf_state *st) { return st && st->nlist > 0 ? st->cent.as<float>() : nullptr; }
 
 void lsq_ivf_get_info(const lsq_ivf_state *st, lsq_ivf_info *out) { *out = st ? st->info : lsq_ivf_info{}; }
+void lsq_ivf_get_select_info(const lsq_ivf_state *st, lsq_ivf_select_info *out) { *out = st ? st->sel : lsq_ivf_select_info{}; }
 
 int lsq_ivf_set_lists(hipStream_t s, lsq_ivf_state **pst, const uint8_t *codes, const float *norms, int packed, int64_t n, int m, int d,
                       const lsq_ivf_desc *desc) {
@@ -610,12 +613,87 @@ int run_chunk(Chunk &c, const float *q_coarse, int64_t ldc, const lsq_search_opt
     return LSQ_OK;
 }
 
+// ---- option "ivf_select": the road whose selection lives in the scan (lsq_ivfsel.hip).  The coarse step, the plan kernel (its totals: probed_rows) and the
+// tables are the other roads'; a batch is the scan and, where several blocks share a query, the merge of their runs.  Nothing is redone
+int run_chunk_select(Chunk &c, const float *q_coarse, int64_t ldc, const lsq_search_opts &coarse) {
+    lsq_ivf_state *st = c.st;
+    hipStream_t s = c.s;
+    const int nq = c.nq, nprobe = c.nprobe, nn = c.nn, m = c.in.m;
+    double coarse_ms = 0.0;
+    LSQ_TRY(lsq_ivf_coarse(s, st, c.adc, q_coarse, ldc, nq, nprobe, coarse, c.timed ? 1 : 0, nullptr, &coarse_ms));
+    st->info.coarse_ms += coarse_ms;
+    LSQ_TRY(st->pos.ensure(sizeof(int) * (size_t)nq * ((size_t)nprobe + 1)));
+    LSQ_TRY(st->plan.ensure(sizeof(int) * 3 * (size_t)nq));
+    hipLaunchKernelGGL(ivf_plan_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, st->ci.as<int>(), st->off.as<int>(), nq, nprobe, nn,
+                       st->pos.as<int>(), st->plan.as<int>(), c.lbits, c.lpre);
+    LSQ_HIP(hipGetLastError());
+    std::vector<int> plan(3 * (size_t)nq);
+    LSQ_HIP(hipMemcpyAsync(plan.data(), st->plan.p, sizeof(int) * plan.size(), hipMemcpyDeviceToHost, s));
+    LSQ_TRY(st->sel_stat.ensure(2 * sizeof(unsigned long long)));
+    LSQ_HIP(hipMemsetAsync(st->sel_stat.p, 0, 2 * sizeof(unsigned long long), s));
+    LSQ_HIP(hipStreamSynchronize(s));
+    for (int q = 0; q < nq; ++q) st->info.probed_rows += plan[3 * (size_t)q];
+    const int64_t qb = batch_queries(nn, c.flags);                   // a query's scratch is its runs: at most 2048 + qb of them, of nn records, in a batch
+    st->info.batch_queries = std::max<int64_t>(st->info.batch_queries, std::min<int64_t>(qb, nq));
+    const int QT = lsq_adc_lut_qt(m);
+    lsq_ivfsel_call a{};
+    a.QT = QT;
+    a.codes = st->codes.as<uint8_t>(); a.norms = st->packed ? st->table : st->norms.as<float>(); a.ids = st->ids.as<int>(); a.off = st->off.as<int>();
+    a.probe = st->ci.as<int>(); a.coarse = st->cd.as<float>(); a.lbits = c.lbits;
+    a.nprobe = nprobe; a.m = m; a.nn = nn; a.idbits = c.idbits; a.add = (c.flags & LSQ_IVF_ADD_COARSE) ? 1 : 0; a.packed = st->packed;
+    a.dists = c.dists; a.out_ids = c.ids; a.stat = st->sel_stat.as<unsigned long long>();
+    for (int q0 = 0; q0 < nq; q0 += (int)qb) {
+        const int nqb = (int)std::min<int64_t>(qb, nq - q0), tiles = (nqb + QT - 1) / QT;
+        const int splits = lsq_ivfsel_splits(nqb, nprobe);
+        LSQ_TRY(st->lut.ensure(sizeof(float) * (size_t)tiles * m * LSQ_H * QT));
+        if (splits > 1) {
+            LSQ_TRY(st->rec_a.ensure(sizeof(uint64_t) * (size_t)nqb * splits * nn));
+            LSQ_TRY(st->count.ensure(sizeof(unsigned) * (size_t)nqb * splits));
+        }
+        a.LUT = st->lut.as<float>(); a.part = st->rec_a.as<uint64_t>(); a.pcount = st->count.as<unsigned>();
+        LSQ_TRY(st->clock.begin(c.timed));
+        LSQ_TRY(st->clock.mark(s));
+        LSQ_TRY(lsq_adc_launch_lut(s, c.in, nullptr, q0, nqb, st->lut.as<float>()));
+        LSQ_TRY(st->clock.mark(s));
+        LSQ_TRY(lsq_ivfsel_launch(s, a, q0, nqb, splits));
+        LSQ_TRY(st->clock.mark(s));
+        if (splits > 1) LSQ_TRY(lsq_ivfsel_launch_merge(s, a, q0, nqb, splits));
+        LSQ_TRY(st->clock.mark(s));
+        LSQ_HIP(hipStreamSynchronize(s));                            // the next batch writes the same tables and runs
+        st->info.batches += 1;
+        st->sel.blocks_per_query = std::max<int64_t>(st->sel.blocks_per_query, splits);
+        if (splits > 1) st->sel.merged_runs += (int64_t)nqb * splits;
+        if (c.timed) {
+            float ms[5];
+            LSQ_TRY(st->clock.read(ms));
+            st->info.lut_ms += ms[0]; st->info.scan_ms += ms[1]; st->info.select_ms += ms[2];
+            st->sel.scan_ms += ms[1]; st->sel.merge_ms += ms[2];
+        }
+    }
+    unsigned long long stat[2] = {0, 0};
+    LSQ_HIP(hipMemcpyAsync(stat, st->sel_stat.p, sizeof(stat), hipMemcpyDeviceToHost, s));
+    LSQ_HIP(hipStreamSynchronize(s));
+    st->info.records += (int64_t)stat[0];
+    st->sel.compactions += (int64_t)stat[1];
+    st->sel.served_queries += nq;
+    return LSQ_OK;
+}
+
 }  // namespace
 
 int lsq_ivf_search(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *K, float *dists, int *ids, const float *q_scan,
                    const float *q_coarse, int64_t ldc, int nq, int nprobe, int nn, int flags, const lsq_search_opts &coarse, int timed,
-                   const lsq_filter_view *flt) {
+                   const lsq_filter_view *flt, int select) {
     st->info = lsq_ivf_info{};
+    st->sel = lsq_ivf_select_info{};
+    st->sel.queries = nq;
+    st->sel.reason = !select ? LSQ_IVF_SELECT_NOT_ASKED : (flags & LSQ_IVF_EVERY_RECORD) ? LSQ_IVF_SELECT_EVERY_RECORD :
+                     nn > LSQ_IVF_SELECT_MAX_NN ? LSQ_IVF_SELECT_NN_TOO_LARGE : LSQ_IVF_SELECT_SERVED;
+    const bool pools = st->sel.reason == LSQ_IVF_SELECT_SERVED;
+    if (pools) {
+        st->sel.pool_records = lsq_ivfsel_pool_records(nn);
+        st->sel.pool_bytes = (int64_t)sizeof(uint64_t) * st->sel.pool_records;
+    }
     // chunks of queries whose per-(query, probe) words stay below 2^28
     int64_t qc = (int64_t)(1u << 28) / ((int64_t)nprobe + 1);
     if (qc < 1) qc = 1;
@@ -627,7 +705,8 @@ int lsq_ivf_search(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const 
         c.in.kind = LSQ_SEARCH_LSQ; c.in.Q = q_scan + c0 * st->d; c.in.qstride = st->d; c.in.K = K; c.in.n = (int)st->n; c.in.m = st->m; c.in.d = st->d;
         c.dists = dists + c0 * nn; c.ids = ids + c0 * nn;
         c.lbits = flt ? flt->lbits : nullptr; c.lpre = flt ? flt->lpre : nullptr;
-        LSQ_TRY(run_chunk(c, q_coarse + c0 * ldc, ldc, coarse));
+        if (pools) LSQ_TRY(run_chunk_select(c, q_coarse + c0 * ldc, ldc, coarse));
+        else LSQ_TRY(run_chunk(c, q_coarse + c0 * ldc, ldc, coarse));
     }
     st->info.queries = nq;
     LSQ_HIP(hipStreamSynchronize(s));

@@ -946,6 +946,12 @@ class Index(_Handle):
         tail_capacity, coarse_ms / lut_ms / scan_ms / select_ms (with profile=True)"""
         return self._info("lsq_index_get_ivf_info", _lib.IvfInfo)
 
+    def ivf_select_info(self):
+        """what the road of Engine.set_option("ivf_select", 1) -- each query's k best records kept in LDS while its probed lists are scanned -- did in the
+        last search_ivf call: queries, served_queries, reason (_lib.IVF_SELECT_*: why not), blocks_per_query, pool_records, pool_bytes, compactions,
+        merged_runs, scan_ms / merge_ms (with profile=True)"""
+        return self._info("lsq_index_get_ivf_select_info", _lib.IvfSelectInfo)
+
     def knn_prefilter_info(self):
         """what the MFMA pre-filter (Engine.set_option("knn_prefilter", 1)) did in the last knn call of this index: pairs, pending, kept, overflow_queries,
         switched_off, served / reason (why the direct road was taken), kappa, eta, norms_ms / mfma_ms / recheck_ms (with profile=True)"""

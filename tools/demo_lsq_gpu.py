@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L [--base-format f16|bf16]] [--ivf NLIST:NPROBE [--residual] [--grow FRACTION]] [--delete FRACTION] [--radius R] [--reconstruct] [--save PATH] [--load PATH] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L [--base-format f16|bf16]] [--ivf NLIST:NPROBE [--ivf-select] [--residual] [--grow FRACTION]] [--delete FRACTION] [--radius R] [--reconstruct] [--save PATH] [--load PATH] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -22,6 +22,8 @@ re-ranked lists printed next to the ADC one.  The reference has no such stage: i
 
 --ivf NLIST:NPROBE: after the ADC scan, inverted lists over the same codes (train_coarse on the base rows, Index.set_lists) and the search that reads
 each query's NPROBE nearest lists alone (Index.search_ivf); its recall curve is printed next to the exhaustive one.  The reference has no such search.
+--ivf-select (with --ivf): the search once more under Engine.set_option("ivf_select", 1) -- the selection inside the list scan -- with its time, what
+Index.ivf_select_info reports, and whether the ids equal the default road's.
 
 --residual (with --ivf): the form of IVF that encodes what the coarse quantiser leaves, built resident on the device at the same m and NPROBE: the same
 centroids, codebooks from the three resident trainers run on the training set's residuals (Partition.assign / residuals), the base set -- f32, or un-widened
@@ -278,6 +280,11 @@ def main():
         except (ValueError, AssertionError, IndexError):
             raise SystemExit("--ivf takes NLIST:NPROBE with 1 <= NPROBE <= NLIST")
         del argv[at:at + 2]
+    ivf_select = "--ivf-select" in argv
+    if ivf_select:
+        argv.remove("--ivf-select")
+        if not ivf:
+            raise SystemExit("--ivf-select needs --ivf NLIST:NPROBE")
     fraction = None
     if "--filter" in argv:
         at = argv.index("--filter")
@@ -415,6 +422,16 @@ def main():
                 _, iidx = ix.search_ivf(Q, knn, nprobe)
                 t_ivf = time.perf_counter() - t0
                 info = ix.ivf_info()
+                if ivf_select:                                              # the same call with each query's best records kept in LDS during the scan
+                    eng.set_option("ivf_select", 1)
+                    t0 = time.perf_counter()
+                    _, sidx = ix.search_ivf(Q, knn, nprobe)
+                    t_sel = time.perf_counter() - t0
+                    sel = ix.ivf_select_info()
+                    eng.set_option("ivf_select", 0)
+                    print("IVF search with ivf_select: %.3f s; %d of %d queries answered from pools of %d records (%d blocks per query, %d compactions); "
+                          "results %s the default road's" % (t_sel, sel["served_queries"], sel["queries"], sel["pool_records"], sel["blocks_per_query"],
+                                                             sel["compactions"], "EQUAL" if np.array_equal(sidx, iidx) else "DIFFER from"))
             nb_all = x_base.shape[1]
             n0 = max(1, nb_all - max(1, int(round(grow * nb_all)))) if grow else None
             grec = gres = None

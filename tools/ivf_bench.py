@@ -8,7 +8,9 @@ Centroids: train_coarse on a prefix of 100 000 rows, every row assigned by ivf_a
 Grid: nprobe in {1, 4, 16, 64}, nn in {100, 1000}, nq in {100, 10^4}.  One process; a warm-up of every call at full size; then the thresholded road, the
 every-record road and the exhaustive scan ALTERNATED, device events around each call, option "profile" off, REPS repeats, medians.  The phase times
 (coarse / lut / scan / select) and the records written come from a pass of its own with "profile" on, which waits on events inside the call.
-recall_of_exhaustive: the share of the exhaustive scan's top-nn ids that the IVF result contains, averaged over the queries."""
+recall_of_exhaustive: the share of the exhaustive scan's top-nn ids that the IVF result contains, averaged over the queries.
+
+tools/ivf_bench.py --select [n nlist]: option "ivf_select" against the option-off call of the same index instead (select_main), to profiles/ivf_select.jsonl."""
 import importlib, json, os, statistics, sys
 import numpy as np
 import torch
@@ -102,6 +104,76 @@ def main(n, nlist):
     out.close()
 
 
+def select_main(n, nlist):
+    """--select: option "ivf_select" (csrc/lsq_ivfsel.hip) against the option-off call of the SAME index in the same process, the two ALTERNATED, REPS
+    repeats, medians; m = 8 plain rows and m = 7 packed rows; phase times and the pools' counters from a pass of its own with "profile" on.  One JSON line
+    per grid point, appended to profiles/ivf_select.jsonl"""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    centres = 3.0 * torch.randn((2 * nlist, D), device=dev, generator=g)
+    X, Qall = mixture(g, dev, centres, n), mixture(g, dev, centres, 10_000)
+    out = open(os.path.join(ROOT, "profiles", "ivf_select.jsonl"), "a")
+    med = statistics.median
+    with lsq.Engine(0) as eng:
+        Xh = X.cpu().numpy()
+        cent, _ = lsq.train_coarse(Xh[:min(n, 100_000)], nlist, niter=5, seed=2, engine=eng)
+        assign = torch.from_numpy(lsq.ivf_assign(Xh, cent, engine=eng)).to(dev)
+        dcent = torch.from_numpy(cent).to(dev)
+        del Xh
+        ntrain = min(n, 20_000)
+        for m, packed in ((8, False), (7, True)):
+            dK, _, _, _, _ = lsq.train_lsq_dev(X[:ntrain].contiguous(), m, 256, eng.randinit_dev(3, ntrain, m), 3, 2, 2, True, 4, seed=5, engine=eng,
+                                               norm_codebook=False)
+            dBs, _, _ = eng.encode_icm_dev(X, eng.randinit_dev(4, n, m), dK, m, [2], 2, 4, True, seed=6)
+            codes = dBs[-1].contiguous()
+            _, _, norms = eng.quantize_norms_dev(codes, dK, torch.zeros(1, dtype=torch.float32, device=dev), m)
+            if packed:
+                cb = torch.sort(norms)[0][torch.linspace(0, n - 1, 256, device=dev).round().long()].contiguous()
+                nc, _, _ = eng.quantize_norms_dev(codes, dK, cb, m)
+            with (eng.index_packed_dev(codes, dK, nc, cb, m) if packed else eng.index_dev(codes, dK, norms.contiguous(), m)) as ix:
+                ix.set_lists(dcent, assign)
+                for nq in (100, 10_000):
+                    Q = Qall[:nq].contiguous()
+                    for nn in (100, 1000):
+                        for nprobe in (1, 4, 16, 64):
+                            if nprobe > nlist:
+                                continue
+                            t, ids, info = {0: [], 1: []}, {}, {}
+                            for opt in (0, 1):                                  # warm-up at full size: code objects, work buffers
+                                eng.set_option("ivf_select", opt)
+                                ix.search_ivf(Q, nn, nprobe)
+                            torch.cuda.synchronize()
+                            for _ in range(REPS):
+                                for opt in (0, 1):
+                                    eng.set_option("ivf_select", opt)
+                                    ms, (_, ids[opt]) = timed(lambda: ix.search_ivf(Q, nn, nprobe))
+                                    t[opt].append(ms)
+                            assert torch.equal(ids[0], ids[1])                  # the identity, once more
+                            eng.set_option("profile", 1)
+                            for opt in (0, 1):
+                                eng.set_option("ivf_select", opt)
+                                ix.search_ivf(Q, nn, nprobe)
+                                info[opt] = ix.ivf_info()
+                            sel = ix.ivf_select_info()
+                            eng.set_option("profile", 0)
+                            eng.set_option("ivf_select", 0)
+                            phases = ("coarse_ms", "lut_ms", "scan_ms", "select_ms")
+                            line = dict(bench="ivf_select", n=n, d=D, m=m, packed=int(packed), nlist=nlist, nprobe=nprobe, nn=nn, nq=nq, reps=REPS,
+                                        off_ms=round(med(t[0]), 3), off_ms_min_max=[round(min(t[0]), 3), round(max(t[0]), 3)],
+                                        on_ms=round(med(t[1]), 3), on_ms_min_max=[round(min(t[1]), 3), round(max(t[1]), 3)],
+                                        speedup=round(med(t[0]) / med(t[1]), 3),
+                                        probed_rows_per_query=round(info[1]["probed_rows"] / nq, 1), off_fallback_queries=info[0]["fallback_queries"],
+                                        off_phases_ms={k: round(info[0][k], 3) for k in phases}, on_phases_ms={k: round(info[1][k], 3) for k in phases},
+                                        blocks_per_query=sel["blocks_per_query"], pool_records=sel["pool_records"],
+                                        compactions_per_query=round(sel["compactions"] / nq, 2), merged_runs=sel["merged_runs"])
+                            s = json.dumps(line)
+                            print(s, flush=True)
+                            out.write(s + "\n")
+                            out.flush()
+    out.close()
+
+
 if __name__ == "__main__":
-    a = [int(x) for x in sys.argv[1:3]] + [1_000_000, 1024][len(sys.argv) - 1:]
-    main(*a)
+    argv = [x for x in sys.argv[1:] if x != "--select"]
+    a = [int(x) for x in argv[:2]] + [1_000_000, 1024][len(argv):]
+    (select_main if "--select" in sys.argv else main)(*a)
