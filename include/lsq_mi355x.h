@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 3000
+#define LSQ_VERSION 3100
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -1153,6 +1153,57 @@ typedef struct lsq_knn_prefilter_half_info {
 } lsq_knn_prefilter_half_info;
 LSQ_API int lsq_knn_prefilter_half_bound(int d, int base_format, float *kappa, float *eta);
 LSQ_API int lsq_index_get_knn_prefilter_half_info(lsq_index *ix, lsq_knn_prefilter_half_info *out);
+
+/* ---- (3t) labelled search: a row predicate PER QUERY on the resident index (csrc/lsq_label.hip, csrc/lsq_pool.h; since v3100) --------------------------------
+ * THE REFERENCE HAS NO COUNTERPART.  CONTRACT (Identity L).  The index owns one 32-bit label word per row, in the original row order.  A labelled search gives
+ * query q two words (q_mask[q], q_want[q]); row r is a candidate of q iff (label[r] & q_mask[q]) == q_want[q] -- (0, 0) admits every row -- or, with flag
+ * LSQ_LABEL_ANY, iff (label[r] & q_mask[q]) != 0 (q_want is ignored; a zero mask then admits no row).  A row filter in force (3j; the tombstones of
+ * lsq_index_remove are one) still applies: a row must pass both.  FOR EVERY QUERY the result row equals, BIT FOR BIT -- distances, ids, order, ties, NaN order
+ * and the (+inf, 0) padding -- the result of lsq_index_search / lsq_index_search_ivf (same nn, nprobe, coarse add, shortlist) for that single query on the same
+ * index after lsq_index_set_filter(allowed = the query's candidates AND the filter in force): the full ranking with the other rows removed, cut to nn.  An
+ * all-rows predicate on an unfiltered index is the plain call bit for bit; with nprobe = nlist the list search equals the exhaustive one.
+ *   how         no threshold is estimated and nothing is redone: each query's nn best records live in the LDS of the blocks that scan for it (the pool of
+ *               "ivf_select", 3g), the predicate is tested per (row, query) inside the scan, and a block of the exhaustive scan serves
+ *               lsq_label_info.queries_per_block queries from ONE read of the rows.
+ *   lsq_index_set_labels   labels [n] uint32, host or device (on_device), COPIED; labels == NULL clears.  LSQ_EINVAL: n != the index's rows.  A second call
+ *               replaces the first.
+ *   lifetime    lsq_index_remove keeps the labels (the rows stay where they are); lsq_index_set_lists keeps them and rebuilds only their copy in layout
+ *               order (lazily, at the next list search); lsq_index_add and lsq_index_compact DROP them (the row set changed: set them again), and a loaded
+ *               index has none: snapshots do not carry labels, so lsq_index_save / _digest / _export are unchanged.  Carrying labels through add, compact
+ *               and snapshots as a fourth row array is the named follow-up.
+ *   refused     LSQ_EINVAL before anything is written: no labels in force; nn -- with a shortlist: the shortlist -- > LSQ_IVF_SELECT_MAX_NN (2048) or > n;
+ *               unknown flags; LSQ_IVF_EVERY_RECORD in ivf_flags (that road has no pools); a null pointer; whatever the plain call refuses.
+ *   stage two   shortlist >= nn: the labelled scan fills the shortlists, the exact re-rank of (3e) follows as behind every other search.
+ *   ivf_flags   LSQ_IVF_ADD_COARSE as in (3g); LSQ_IVF_TEST_BATCH (its test hook) is honoured: batches of at most 8 queries, lsq_label_info.batches says so.
+ *   LSQ_LABEL_TEST_ONE_SPLIT   a TEST HOOK (like option "linscan_exhaustive"): one block per query group, so that a single pool sees every row.  Same result.
+ *   lsq_label_geometry   host only, no index: how a call of this shape is laid out (the rule the device code runs on): queries per block -- the largest of 4,
+ *               2, 1 with QB (m KiB of table + 8 pool_records bytes [+ 1 KiB, packed]) <= 64 KiB --, the pool, the LDS of a block, and the row ranges of the
+ *               exhaustive scan: blocks_per_query ranges of rows_per_block rows (a multiple of 256), range y = [y rows_per_block, min(n, (y + 1) rows_per_block)).
+ *   lsq_index_get_label_info   the account of the last labelled call (labels_set / rows: the state now).  The counters are sums of integers: the same on
+ *               every call. */
+enum { LSQ_LABEL_ANY = 1, LSQ_LABEL_TEST_ONE_SPLIT = 2 };
+typedef struct lsq_label_info {
+    int64_t labels_set, rows;            /* labels in force, and over how many rows */
+    int64_t queries;                     /* of the last labelled call */
+    int64_t queries_per_block, blocks_per_query;      /* the geometry: QB, and the most blocks that shared a query */
+    int64_t pool_records;                /* P = 2 pow2ceil(max(nn, 256)) */
+    int64_t offered;                     /* records that entered pools (passed both tests and the pool's bound of the moment) */
+    int64_t compactions, merged_runs;    /* pool compactions; runs merged where several blocks shared a query */
+    int64_t allowed_pairs;               /* SUM over queries of the candidate rows that passed both tests (list search: among the probed rows) */
+    int64_t batches, layout_builds;      /* batches of queries; 1 when this call rebuilt the labels' copy in layout order */
+    double coarse_ms, lut_ms, scan_ms, merge_ms;      /* with option "profile" = 1 */
+} lsq_label_info;
+typedef struct lsq_label_geometry_info {
+    int64_t queries_per_block, pool_records, lds_bytes, query_groups, blocks_per_query, rows_per_block;
+} lsq_label_geometry_info;
+LSQ_API int lsq_index_set_labels(lsq_index *ix, const uint32_t *labels, int64_t n, int on_device);
+LSQ_API int lsq_index_search_labelled(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_exact, const uint32_t *q_mask,
+                                      const uint32_t *q_want, int nq, int ldq, int shortlist, int nn, int flags, int on_device);
+LSQ_API int lsq_index_search_ivf_labelled(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_coarse, const float *q_exact,
+                                          const uint32_t *q_mask, const uint32_t *q_want, int nq, int ldq, int nprobe, int shortlist, int nn, int ivf_flags,
+                                          int flags, int on_device);
+LSQ_API int lsq_index_get_label_info(lsq_index *ix, lsq_label_info *out);
+LSQ_API int lsq_label_geometry(int64_t n, int m, int packed, int nn, int nq, int flags, lsq_label_geometry_info *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

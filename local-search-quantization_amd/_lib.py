@@ -114,6 +114,22 @@ IVF_SELECT_NOT_ASKED, IVF_SELECT_NN_TOO_LARGE, IVF_SELECT_EVERY_RECORD = 1, 2, 3
 IVF_SELECT_MAX_NN = 2048
 
 
+class LabelInfo(_Struct):
+    _fields_ = [("labels_set", C.c_int64), ("rows", C.c_int64), ("queries", C.c_int64), ("queries_per_block", C.c_int64), ("blocks_per_query", C.c_int64),
+                ("pool_records", C.c_int64), ("offered", C.c_int64), ("compactions", C.c_int64), ("merged_runs", C.c_int64), ("allowed_pairs", C.c_int64),
+                ("batches", C.c_int64), ("layout_builds", C.c_int64), ("coarse_ms", C.c_double), ("lut_ms", C.c_double), ("scan_ms", C.c_double),
+                ("merge_ms", C.c_double)]
+
+
+class LabelGeometryInfo(_Struct):
+    _fields_ = [("queries_per_block", C.c_int64), ("pool_records", C.c_int64), ("lds_bytes", C.c_int64), ("query_groups", C.c_int64),
+                ("blocks_per_query", C.c_int64), ("rows_per_block", C.c_int64)]
+
+
+# flags of a labelled search (since v3100): the any-of rule; a test hook (one block per query group)
+LABEL_ANY, LABEL_TEST_ONE_SPLIT = 1, 2
+
+
 class IndexPackedDesc(_Struct):
     _fields_ = [("n", C.c_int64), ("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("codes", C.c_void_p), ("norm_codes", C.c_void_p),
                 ("cbnorms", C.c_void_p), ("ncb", C.c_int), ("codebooks", C.c_void_p), ("base", C.c_void_p), ("base_u8", C.c_int), ("ldb", C.c_int),
@@ -318,6 +334,12 @@ SIGNATURES = {
     "lsq_index_get_ivf_info": (_i, [_vp, C.POINTER(IvfInfo)]),
     "lsq_index_get_ivf_select_info": (_i, [_vp, C.POINTER(IvfSelectInfo)]),      # since v3000: the road of option "ivf_select"
     "lsq_ivf_search_cpu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    # labelled search (since v3100): the index's row labels, the two searches with a predicate per query, their account, the geometry rule (host only)
+    "lsq_index_set_labels": (_i, [_vp, _vp, _i64, _i]),
+    "lsq_index_search_labelled": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    "lsq_index_search_ivf_labelled": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "lsq_index_get_label_info": (_i, [_vp, C.POINTER(LabelInfo)]),
+    "lsq_label_geometry": (_i, [_i64, _i, _i, _i, _i, _i, C.POINTER(LabelGeometryInfo)]),
     # the packed index: rows of m code bytes and one norm byte (since v1800), and the selection statistics of an index's last scan
     "lsq_index_create_packed": (_i, [C.POINTER(_vp), _vp, C.POINTER(IndexPackedDesc)]),
     "lsq_index_get_packed_info": (_i, [_vp, C.POINTER(IndexPackedInfo)]),
@@ -406,7 +428,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 3000    # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 3100    # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

@@ -623,6 +623,7 @@ struct lsq_index {
     double narrow_ms = 0.0;
     PhaseClock<2> hclock;
     lsq_snapshot_io_info sinfo{};                      // the last lsq_index_save, or the lsq_index_load that made this index
+    lsq_label_state *labels = nullptr;                 // labelled search (lsq_label.hip): the row labels, owned copies, and its scratch; null until lsq_index_set_labels
 };
 
 // the filter as a scan over all rows takes it: nothing without one; else the compact road -- the ascending list of allowed rows -- where the measured rule
@@ -688,6 +689,7 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     lsq_adc_free(ix->adc);
     lsq_ivf_free(ix->ivf);
     lsq_filter_free(ix->filter);
+    lsq_label_free(ix->labels);
     ix->clock.release();
     delete ix;
     return LSQ_OK;
@@ -1112,6 +1114,7 @@ extern "C" int lsq_index_set_lists(lsq_index *ix, const lsq_ivf_desc *desc) {
     if (!desc->centroids || !desc->list_of_row) { lsq_set_error("lsq_index_set_lists: null pointer"); return LSQ_EINVAL; }
     LSQ_TRY(use_device(ix->ctx));
     ix->r_lor_valid = false;
+    lsq_label_drop_layout(ix->labels);                // the labels stay; their copy in layout order follows the new lists
     LSQ_TRY(lsq_ivf_set_lists(ix->ctx->stream, &ix->ivf, ix->codes, ix->norms, ix->packed, ix->n, ix->m, ix->d, desc));
     lsq_range_drop(ix->range);
     if (ix->cap_rows > ix->n) {                       // an index with capacity (lsq_index_reserve / _add): the layout's halves get it too
@@ -1160,6 +1163,103 @@ extern "C" int lsq_index_get_ivf_select_info(lsq_index *ix, lsq_ivf_select_info 
     if (!ix || !out) { lsq_set_error("lsq_index_get_ivf_select_info: null argument"); return LSQ_EINVAL; }
     lsq_ivf_get_select_info(ix->ivf, out);
     return LSQ_OK;
+}
+
+// ---- labelled search (lsq_label.hip): the index's labels, and the two searches with a predicate per query -------------------------------------
+extern "C" int lsq_index_set_labels(lsq_index *ix, const uint32_t *labels, int64_t n, int on_device) {
+    if (!ix) { lsq_set_error("lsq_index_set_labels: null index"); return LSQ_EINVAL; }
+    if (!labels) { lsq_label_drop(ix->labels); return LSQ_OK; }
+    if (n != ix->n) { lsq_set_error("lsq_index_set_labels: needs one label per row (got n=%lld, the index holds %lld rows)", (long long)n, (long long)ix->n); return LSQ_EINVAL; }
+    LSQ_TRY(use_device(ix->ctx));
+    return lsq_label_set(ix->ctx->stream, &ix->labels, labels, n, on_device);
+}
+
+extern "C" int lsq_index_get_label_info(lsq_index *ix, lsq_label_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_label_info: null argument"); return LSQ_EINVAL; }
+    lsq_label_get_info(ix->labels, out);
+    return LSQ_OK;
+}
+
+// the checks both labelled searches make after the plain call's own; *L: the length of stage one's lists
+static int index_label_check(const char *fn, lsq_index *ix, const uint32_t *q_mask, const uint32_t *q_want, int shortlist, int nn, int flags, int *L) {
+    if (!ix->codes) { lsq_set_error("%s: the index holds no codes", fn); return LSQ_EINVAL; }
+    if (!lsq_label_active(ix->labels)) { lsq_set_error("%s: the index has no labels (call lsq_index_set_labels first; lsq_index_add / _compact drop them)", fn); return LSQ_EINVAL; }
+    if (flags & ~(LSQ_LABEL_ANY | LSQ_LABEL_TEST_ONE_SPLIT)) { lsq_set_error("%s: unknown flags %d", fn, flags); return LSQ_EINVAL; }
+    if (!q_mask || !q_want) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    LSQ_TRY(index_shortlist(fn, shortlist, nn, L));
+    if (*L > LSQ_IVF_SELECT_MAX_NN) { lsq_set_error("%s: needs %s <= %d (got %d)", fn, shortlist > 0 ? "shortlist" : "nn", LSQ_IVF_SELECT_MAX_NN, *L); return LSQ_EINVAL; }
+    return LSQ_OK;
+}
+
+// what both roads hand the scan: the rows as the index holds them, the call's words, where the lists go
+static lsq_label_call index_label_call(lsq_index *ix, const float *dqs, const uint32_t *q_mask, const uint32_t *q_want, int nq, int len, int flags,
+                                       float *scan_d, int *scan_i) {
+    lsq_label_call lc;
+    lc.in = lsq_input(ix->codes, dqs, ix->K, ix->norms, (int)ix->n, ix->m, ix->d);
+    if (ix->packed) { lc.in.packed = 1; lc.in.cstride = ix->m + 1; }      // rows with their norm byte; norms is the table
+    lc.q_mask = q_mask; lc.q_want = q_want; lc.nq = nq; lc.nn = len; lc.flags = flags; lc.timed = ix->ctx->profile ? 1 : 0;
+    lc.dists = scan_d; lc.ids = scan_i;
+    return lc;
+}
+
+extern "C" int lsq_index_search_labelled(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_exact, const uint32_t *q_mask,
+                                         const uint32_t *q_want, int nq, int ldq, int shortlist, int nn, int flags, int on_device) {
+    const char *fn = "lsq_index_search_labelled";
+    LSQ_TRY(index_call_check(fn, ix, dists, ids, nq, ldq, nn));
+    int L = 0;
+    LSQ_TRY(index_label_check(fn, ix, q_mask, q_want, shortlist, nn, flags, &L));
+    if (L > ix->n) { lsq_set_error("%s: %s=%d exceeds the database size %lld", fn, shortlist > 0 ? "shortlist" : "nn", L, (long long)ix->n); return LSQ_EINVAL; }
+    IndexCall call{ix, nq, on_device != 0};
+    return index_two_stage(fn, call, dists, ids, q_scan, q_exact, ldq, shortlist, nn, L,
+                           [&](float *scan_d, int *scan_i, const float *dqs, int len) -> int {      // the labelled scan of every row
+        lsq_label_call lc = index_label_call(ix, dqs, q_mask, q_want, nq, len, flags, scan_d, scan_i);
+        if (lsq_filter_active(ix->filter)) {          // the filter's bits beside every row (the dense road: a predicate per query has no compact form)
+            lc.bits = lsq_filter_get(ix->filter).bits;
+            lsq_filter_note_road(ix->filter, 1);
+        } else {
+            lsq_filter_note_road(ix->filter, 0);
+        }
+        LSQ_TRY(lsq_label_search(ix->ctx->stream, ix->labels, lc));
+        lsq_label_info li;
+        lsq_label_get_info(ix->labels, &li);
+        ix->stats.scan_ms += li.lut_ms + li.scan_ms + li.merge_ms;
+        return LSQ_OK;
+    });
+}
+
+extern "C" int lsq_index_search_ivf_labelled(lsq_index *ix, float *dists, int *ids, const float *q_scan, const float *q_coarse, const float *q_exact,
+                                             const uint32_t *q_mask, const uint32_t *q_want, int nq, int ldq, int nprobe, int shortlist, int nn, int ivf_flags,
+                                             int flags, int on_device) {
+    const char *fn = "lsq_index_search_ivf_labelled";
+    LSQ_TRY(index_call_check(fn, ix, dists, ids, nq, ldq, nn));
+    int L = 0;
+    LSQ_TRY(index_label_check(fn, ix, q_mask, q_want, shortlist, nn, flags, &L));
+    const int nlist = lsq_ivf_nlist(ix->ivf);
+    if (nlist < 1) { lsq_set_error("%s: the index has no lists (call lsq_index_set_lists first)", fn); return LSQ_EINVAL; }
+    if (ivf_flags & ~(LSQ_IVF_ADD_COARSE | LSQ_IVF_EVERY_RECORD | LSQ_IVF_TEST_BATCH)) { lsq_set_error("%s: unknown ivf_flags %d", fn, ivf_flags); return LSQ_EINVAL; }
+    if (ivf_flags & LSQ_IVF_EVERY_RECORD) { lsq_set_error("%s: LSQ_IVF_EVERY_RECORD has no labelled form (that road keeps no pools)", fn); return LSQ_EINVAL; }
+    if (nprobe < 1 || nprobe > nlist) { lsq_set_error("%s: needs 1 <= nprobe <= nlist (got nprobe=%d nlist=%d)", fn, nprobe, nlist); return LSQ_EINVAL; }
+    if (L > ix->n) { lsq_set_error("%s: %s=%d exceeds the database size %lld", fn, shortlist > 0 ? "shortlist" : "nn", L, (long long)ix->n); return LSQ_EINVAL; }
+    lsq_ctx *c = ix->ctx;
+    IndexCall call{ix, nq, on_device != 0};
+    return index_two_stage(fn, call, dists, ids, q_scan, q_exact, ldq, shortlist, nn, L,
+                           [&](float *scan_d, int *scan_i, const float *dqs, int len) -> int {      // the labelled scan of each query's probed lists
+        lsq_label_call lc = index_label_call(ix, dqs, q_mask, q_want, nq, len, flags, scan_d, scan_i);
+        LSQ_TRY(call.rows(ix->s_qcoarse, q_coarse ? q_coarse : q_scan, sizeof(float), ldq, ix->d, false, !on_device, &lc.q_coarse, &lc.ldc));      // as they lie
+        lc.ivf = ix->ivf; lc.adc = &ix->adc; lc.nprobe = nprobe; lc.ivf_flags = ivf_flags; lc.coarse = c->search;
+        if (lsq_filter_active(ix->filter)) {
+            lc.bits = lsq_filter_get(ix->filter).lbits;
+            if (!lc.bits) { lsq_set_error("%s: the filter has no bits in layout order (a failed lsq_index_set_lists / _set_filter?)", fn); return LSQ_EINVAL; }
+            lsq_filter_note_road(ix->filter, 1);
+        } else {
+            lsq_filter_note_road(ix->filter, 0);
+        }
+        LSQ_TRY(lsq_label_search(c->stream, ix->labels, lc));
+        lsq_label_info li;
+        lsq_label_get_info(ix->labels, &li);
+        ix->stats.scan_ms += li.coarse_ms + li.lut_ms + li.scan_ms + li.merge_ms;
+        return LSQ_OK;
+    });
 }
 
 // ---- range search on the index (lsq_range.hip): every candidate row within a radius; the result is HELD by the index until fetched or dropped ----
@@ -1356,6 +1456,7 @@ extern "C" int lsq_index_add(lsq_index *ix, const lsq_index_add_desc *desc) {
     // 6. the commit
     if (lists) lsq_ivf_add_commit(ix->ivf, count);
     ix->r_lor_valid = false;
+    lsq_label_drop(ix->labels);                       // labels answer for the former rows: set them again
     lsq_filter_grow_commit(ix->filter, n + count);
     ix->n = n + count;
     lsq_range_drop(ix->range);                        // a held range result answers for the former rows
@@ -1486,6 +1587,7 @@ extern "C" int lsq_index_compact(lsq_index *ix, const lsq_index_compact_desc *de
         shrunk = shrink ? 1 : 0;
     }
     lsq_range_drop(ix->range);
+    lsq_label_drop(ix->labels);
     ix->r_lor_valid = false;
     ix->cinfo.n_before = n; ix->cinfo.n_after = n2;
     ix->cinfo.compactions += 1; ix->cinfo.rows_dropped += n - n2;

@@ -471,6 +471,33 @@ struct lsq_ivf_probes {
 int lsq_ivf_coarse(hipStream_t s, lsq_ivf_state *st, lsq_adc_state **adc, const float *q_coarse, int64_t ldc, int nq, int nprobe, const lsq_search_opts &coarse,
                    int timed, lsq_ivf_probes *out, double *coarse_ms);
 
+// ---- labelled search on a resident index (lsq_label.hip): the index's labels, and the scan that tests a predicate per (row, query) -----------
+struct lsq_label_state;
+void lsq_label_free(lsq_label_state *st);
+bool lsq_label_active(const lsq_label_state *st);
+void lsq_label_drop(lsq_label_state *st);            // the labels leave (lsq_index_add / _compact; st may be null)
+void lsq_label_drop_layout(lsq_label_state *st);     // the layout-order copy alone (lsq_index_set_lists): rebuilt at the next list search
+void lsq_label_get_info(const lsq_label_state *st, lsq_label_info *out);
+// labels [n], host or device: copied.  Waits for the device (the caller's array is free at the return)
+int lsq_label_set(hipStream_t s, lsq_label_state **st, const uint32_t *labels, int64_t n, int on_device);
+// one call.  in: the rows as lsq_adc_search takes them (kind LSQ, Q = q_scan rows d floats apart; packed rows as the index holds them); on the list road
+// (ivf set) only Q, K, n, m, d of it are read and the rows are ivf's layout.  bits: the filter in force -- by original row, or (list road) in layout order --
+// or null.  q_mask / q_want [nq]: host or device.  dists / ids [nq][nn]: device
+struct lsq_label_call {
+    lsq_search_input in;
+    const uint32_t *q_mask = nullptr, *q_want = nullptr, *bits = nullptr;
+    int nq = 0, nn = 0, flags = 0, timed = 0;
+    float *dists = nullptr; int *ids = nullptr;
+    lsq_ivf_state *ivf = nullptr; lsq_adc_state **adc = nullptr;      // list road: the lists, and the scan state the coarse search runs on
+    const float *q_coarse = nullptr; int64_t ldc = 0;
+    int nprobe = 0, ivf_flags = 0;                   // ivf_flags: LSQ_IVF_ADD_COARSE, LSQ_IVF_TEST_BATCH (batches of at most 8 queries)
+    lsq_search_opts coarse;                          // how the coarse search runs (the context's hooks)
+};
+int lsq_label_search(hipStream_t s, lsq_label_state *st, const lsq_label_call &c);
+int lsq_label_qb(int m, int packed, int nn);         // queries per block of the exhaustive geometry: the largest of 4, 2, 1 whose tables and pools fit 64 KiB
+size_t lsq_label_lds_bytes(int m, int packed, int nn, int qb);
+void lsq_label_split(int64_t n, int groups, int one_split, int *splits, int64_t *per);      // the row ranges: `splits` of `per` rows (a multiple of 256)
+
 // ---- range search on a resident index (lsq_range.hip): every candidate row within a radius, held by the index until fetched or dropped ------------------
 struct lsq_range_state;
 void lsq_range_free(lsq_range_state *st);

@@ -848,14 +848,51 @@ class Index(_Handle):
         _shapes(("Q_scan", Qs, (None, self.d)), *((name, a, tuple(Qs.shape)) for name, a in zip(others, Qo)))
         return (Qs, *Qo, *side.topk(Qs.shape[0], int(k), Qs))
 
-    def search(self, Q_scan, k, shortlist=0, Q_exact=None):
+    def _where(self, where, nq):
+        """where=(mask, want): two (nq,) int32 / uint32 arrays on the index's side (a device tensor is int32: torch has no uint32 arithmetic, the same bits)"""
+        side = self._side
+        mask, want = where
+        words = [side.take(a, np.int32 if _dtname(a) == "int32" else np.uint32, name) for a, name in ((mask, "where mask"), (want, "where want"))]
+        _shapes(("where mask", words[0], (nq,)), ("where want", words[1], (nq,)))
+        return words
+
+    def search(self, Q_scan, k, shortlist=0, Q_exact=None, where=None, any_of=False, flags=0):
         """Q_scan (nq,d): what the scan reads (the rotated queries of linscan_lsq); Q_exact (nq,d): the queries in the base set's own frame (default:
         Q_scan).  shortlist=0: the ADC scan alone, Engine.linscan's results; shortlist=L>=k: scan for L, re-rank to k by exact distance.
-        -> dists (nq,k) float32 ascending, ids (nq,k) int32 1-BASED   [lsq_index_search]"""
+        where=(mask, want): a predicate PER QUERY over the labels of set_labels -- row r is a candidate of query q iff (label[r] & mask[q]) == want[q], or
+        with any_of iff (label[r] & mask[q]) != 0 -- on top of a filter in force; each query's row is what set_filter(its candidates) and a one-query
+        search would return, bit for bit; k (or the shortlist) <= 2048.  where=None: exactly the plain call.  flags (with where): _lib.LABEL_TEST_ONE_SPLIT, a
+        TEST HOOK -- one block per query group, the same result.
+        -> dists (nq,k) float32 ascending, ids (nq,k) int32 1-BASED   [lsq_index_search, lsq_index_search_labelled]"""
         Qs, Qe, dists, ids = self._search_args(Q_scan, k, Q_exact=Q_exact)
         side, p = self._side, self._side.ptr
-        self._eng._call(side, "lsq_index_search", p(dists), p(ids), p(Qs), p(Qe), Qs.shape[0], self.d, int(shortlist), int(k), int(self._dev), h=self._h)
+        if where is None:
+            self._eng._call(side, "lsq_index_search", p(dists), p(ids), p(Qs), p(Qe), Qs.shape[0], self.d, int(shortlist), int(k), int(self._dev), h=self._h)
+            return dists, ids
+        mask, want = self._where(where, Qs.shape[0])
+        fl = int(flags) | (_lib.LABEL_ANY if any_of else 0)
+        self._eng._call(side, "lsq_index_search_labelled", p(dists), p(ids), p(Qs), p(Qe), p(mask), p(want), Qs.shape[0], self.d, int(shortlist), int(k), fl,
+                        int(self._dev), h=self._h)
         return dists, ids
+
+    def set_labels(self, labels):
+        """One 32-bit label word per row, in the original row order: (n,) int32 / uint32 (numpy on an Engine.index, a torch tensor on an Engine.index_dev).
+        The index keeps a copy; a second call replaces the first.  remove and set_lists keep the labels, add and compact DROP them, a loaded index has
+        none   [lsq_index_set_labels]"""
+        side = self._side
+        a = side.take(labels, np.int32 if _dtname(labels) == "int32" else np.uint32, "labels")
+        _shapes(("labels", a, (None,)))
+        self._eng._call(side, "lsq_index_set_labels", side.ptr(a) if a.shape[0] else side.ptr(side.new((1,), _I32, a)), int(a.shape[0]), int(self._dev), h=self._h)
+
+    def clear_labels(self):
+        """drop the labels: a labelled search is refused until they are set again   [lsq_index_set_labels(NULL)]"""
+        self._eng._call(self._side, "lsq_index_set_labels", None, 0, int(self._dev), h=self._h)
+
+    def label_info(self):
+        """labels_set, rows, and of the last labelled search: queries, queries_per_block, blocks_per_query, pool_records, offered, compactions, merged_runs,
+        allowed_pairs (the sum over queries of the candidate rows that passed predicate and filter), batches, layout_builds, coarse_ms / lut_ms / scan_ms /
+        merge_ms (with profile=True)"""
+        return self._info("lsq_index_get_label_info", _lib.LabelInfo)
 
     def rerank(self, Q, cand, k, id_base=1):
         """Stage two alone: cand (nq,L) int32 ids in id_base (the 0-based shortlists of linscan_pq: id_base=0).
@@ -897,16 +934,25 @@ class Index(_Handle):
         self._eng._call(side, "lsq_index_set_lists", C.byref(desc), h=self._h)
         self.nlist = int(cent.shape[0])
 
-    def search_ivf(self, Q_scan, k, nprobe, shortlist=0, Q_coarse=None, Q_exact=None, add_coarse=False, every_record=False, flags=0):
+    def search_ivf(self, Q_scan, k, nprobe, shortlist=0, Q_coarse=None, Q_exact=None, add_coarse=False, every_record=False, flags=0, where=None,
+                   any_of=False, label_flags=0):
         """search() over the rows of each query's nprobe nearest lists alone.  Q_coarse (nq,d): what is compared with the centroids (default: Q_scan);
         add_coarse: one more rounded add of the coarse distance (residual codes); every_record: the road that writes and sorts every probed row.
+        where=(mask, want), any_of: search()'s predicate per query, among the probed rows (every_record is refused with it); label_flags (with where):
+        _lib.LABEL_TEST_ONE_SPLIT, a TEST HOOK -- one block per query, the same result; flags=_lib.IVF_TEST_BATCH (a test hook too) is honoured.
         -> dists (nq,k) float32 ascending, ids (nq,k) int32 1-BASED original row ids; (+inf, 0) where the probed lists hold fewer than k rows
-        [lsq_index_search_ivf]"""
+        [lsq_index_search_ivf, lsq_index_search_ivf_labelled]"""
         Qs, Qc, Qe, dists, ids = self._search_args(Q_scan, k, Q_coarse=Q_coarse, Q_exact=Q_exact)
         side, p = self._side, self._side.ptr
         fl = int(flags) | (_lib.IVF_ADD_COARSE if add_coarse else 0) | (_lib.IVF_EVERY_RECORD if every_record else 0)
-        self._eng._call(side, "lsq_index_search_ivf", p(dists), p(ids), p(Qs), p(Qc), p(Qe), Qs.shape[0], self.d, int(nprobe), int(shortlist), int(k), fl,
-                        int(self._dev), h=self._h)
+        if where is None:
+            self._eng._call(side, "lsq_index_search_ivf", p(dists), p(ids), p(Qs), p(Qc), p(Qe), Qs.shape[0], self.d, int(nprobe), int(shortlist), int(k), fl,
+                            int(self._dev), h=self._h)
+            return dists, ids
+        mask, want = self._where(where, Qs.shape[0])
+        lf = int(label_flags) | (_lib.LABEL_ANY if any_of else 0)
+        self._eng._call(side, "lsq_index_search_ivf_labelled", p(dists), p(ids), p(Qs), p(Qc), p(Qe), p(mask), p(want), Qs.shape[0], self.d, int(nprobe),
+                        int(shortlist), int(k), fl, lf, int(self._dev), h=self._h)
         return dists, ids
 
     def range_search(self, Q_scan, radius, nprobe=0, Q_coarse=None, add_coarse=False):

@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L [--base-format f16|bf16]] [--ivf NLIST:NPROBE [--ivf-select] [--residual] [--grow FRACTION]] [--delete FRACTION] [--radius R] [--reconstruct] [--save PATH] [--load PATH] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L [--base-format f16|bf16]] [--ivf NLIST:NPROBE [--ivf-select] [--residual] [--grow FRACTION]] [--delete FRACTION] [--labels NCAT] [--radius R] [--reconstruct] [--save PATH] [--load PATH] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -53,6 +53,9 @@ back from a snapshot (Engine.load_index) and searched -- the same ids as the exh
 
 --reconstruct: the base prefix decoded from the resident codes (Index.reconstruct) with its mean squared error against the base rows, with --ivf ...
 --residual also the residual index decoded with the coarse add, and one search whose queries are stored rows (Index.search_rows).
+
+--labels NCAT: every base row gets one of NCAT random category bits (Index.set_labels) and every query asks for one category (Index.search(..., where=)): the
+recall of the labelled ADC search against the exact k-NN over the rows of the same category.  The reference has no such search.
 
 --radius R (alone or beside --ivf and --filter, whose sections run as before): range search on a resident index (Index.range_search) -- every base row
 whose ADC distance to the query is <= R, R in the scan's own units (the distances linscan_lsq prints), or `auto`: the median over the queries of the 10th
@@ -294,6 +297,15 @@ def main():
         except (ValueError, AssertionError, IndexError):
             raise SystemExit("--filter takes a FRACTION in (0, 1]")
         del argv[at:at + 2]
+    ncat = None
+    if "--labels" in argv:
+        at = argv.index("--labels")
+        try:
+            ncat = int(argv[at + 1])
+            assert 1 <= ncat <= 32
+        except (ValueError, AssertionError, IndexError):
+            raise SystemExit("--labels takes NCAT, the number of categories, in 1 .. 32")
+        del argv[at:at + 2]
     delete = None
     if "--delete" in argv:
         at = argv.index("--delete")
@@ -461,6 +473,8 @@ def main():
                       + ("         %.4f" % grec[i - 1] if grow else "") + ("      %.4f" % gres[i - 1] if gres is not None else ""))
     if fraction is not None:
         filtered_recall(fraction, name, x_base, x_query, B_base, C, db_norms, m, knn, shortlist, ivf)
+    if ncat is not None:
+        labelled_recall(ncat, name, x_base, x_query, B_base, C, db_norms, m, knn)
     if delete is not None:
         deleted_recall(delete, name, x_base, x_query, B_base, C, db_norms, m, knn, ivf)
     if radius is not None:
@@ -635,6 +649,35 @@ def filtered_recall(fraction, name, x_base, x_query, B_base, C, db_norms, m, knn
         if i <= keep:
             print("%7d   " % i + "   ".join("%-12.4f" % c[i - 1] for c in curves.values()))
     print("%s: filtered recall@1 = %.4f at fraction %g" % (name, curves["ADC"][0], fraction))
+
+
+def labelled_recall(ncat, name, x_base, x_query, B_base, C, db_norms, m, knn):
+    """--labels NCAT: every row gets one random category bit, every query asks for one category (Index.search(..., where=)); recall against the exact k-NN of
+    the same category's rows (Index.knn under set_filter, one category at a time)"""
+    n, nq = x_base.shape[1], x_query.shape[1]
+    rng = np.random.default_rng(0)
+    cat, asked = rng.integers(0, ncat, n), rng.integers(0, ncat, nq)
+    labels = (np.uint32(1) << cat.astype(np.uint32)).astype(np.uint32)
+    mask = (np.uint32(1) << asked.astype(np.uint32)).astype(np.uint32)
+    rows = np.ascontiguousarray(x_base.T)
+    Q = np.ascontiguousarray(x_query.T.astype(np.float32))
+    keep = max(1, min(knn, int(np.bincount(cat, minlength=ncat).min()), 2048))
+    with lsq.Engine(0) as eng, eng.index((B_base - 1).astype(np.uint8).T, np.ascontiguousarray(np.hstack(C).T), db_norms, m, base=rows) as ix:
+        gt = np.zeros(nq, dtype=np.uint32)
+        for c in range(ncat):                                                 # the equally restricted ground truth
+            if np.any(asked == c):
+                ix.set_filter(mask=(cat == c))
+                gt[asked == c] = ix.knn(Q[asked == c], 1, id_base=1)[1][:, 0]
+        ix.clear_filter()
+        ix.set_labels(labels)
+        _, ids = ix.search(Q, keep, where=(mask, mask))
+        info = ix.label_info()
+    rec = lsq.eval_recall(gt, np.ascontiguousarray(ids.T).astype(np.uint32), keep)
+    print("Labelled search (%d categories, one per query; %d queries per block; ground truth: exact k-NN over the category's rows)" % (ncat, info["queries_per_block"]))
+    for i in (1, 2, 5, 10, 20, 50, 100, 200, 500, 1000):
+        if i <= keep:
+            print("%7d   %-12.4f" % (i, rec[i - 1]))
+    print("%s: labelled recall@1 = %.4f over %d categories" % (name, rec[0], ncat))
 
 
 if __name__ == "__main__":
