@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 3100
+#define LSQ_VERSION 3200
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -1204,6 +1204,46 @@ LSQ_API int lsq_index_search_ivf_labelled(lsq_index *ix, float *dists, int *ids,
                                           int flags, int on_device);
 LSQ_API int lsq_index_get_label_info(lsq_index *ix, lsq_label_info *out);
 LSQ_API int lsq_label_geometry(int64_t n, int m, int packed, int nn, int nq, int flags, lsq_label_geometry_info *out);
+
+/* ---- (3u) labelled exact k-NN: the ground truth of a labelled search (csrc/lsq_labelknn.hip, csrc/lsq_pool.h; since v3200) ----------------------------------
+ * THE REFERENCE HAS NO COUNTERPART.  CONTRACT (Identity LK).  lsq_index_knn with the predicate of (3t) per query: row r is a candidate of query q iff
+ * (label[r] & q_mask[q]) == q_want[q] -- (0, 0) admits every row -- or, with LSQ_LABEL_ANY, iff (label[r] & q_mask[q]) != 0, AND the filter in force
+ * (tombstones included) allows r.  FOR EVERY QUERY the result row equals, BIT FOR BIT -- distances, ids, order, ties, NaN order and padding -- what
+ * lsq_index_knn returns for that single query on the same index after lsq_index_set_filter(the query's candidates AND the filter in force): lsq_knn_exact's
+ * full ranking (the f32 chain of (3c): e = x - q rounded, e e rounded, added in ascending dimension from +0, no FMA; ties to the smaller id, NaN last) with
+ * the other rows removed, cut to nn, (+inf, id_base - 1) behind it.  A candidate whose distance is NaN is a candidate: it precedes the padding.  An all-rows
+ * predicate on an unfiltered index is lsq_index_knn bit for bit.
+ *   how         no threshold is estimated (there is no sample to estimate from when every query has candidates of its own): a block of 256 threads walks a
+ *               range of rows, a lane per row, for queries_per_block queries at once -- the distance tile staged 16 dimensions at a time through LDS --
+ *               and offers each (row, query) record that passes to that query's pool in LDS (the pool of (3g) / (3t)).  Several blocks per query: sorted
+ *               runs, merged by the merge of (3g).  A wave none of whose rows is a candidate of any of the block's queries skips the arithmetic of the step.
+ *   served      f32, uint8, f16 and bf16 rows at any pitch (widened, exactly, where they are staged); f32 or uint8 queries (queries_u8), ldq >= d elements
+ *               apart; host-buffer and device-tensor indexes (on_device: queries, q_mask, q_want, dists, ids are device pointers); 1 <= nn <= 2048, nn <= n.
+ *   refused     LSQ_EINVAL before anything is written: no labels in force (their count is the index's n by construction: lsq_index_set_labels refuses any
+ *               other); no base rows; nn > LSQ_IVF_SELECT_MAX_NN (2048) or > n; unknown flags; a null pointer; id_base outside {0, 1}.
+ *   options     "knn_prefilter", "knn_u8_mfma", "knn_prefilter_half" and "knn_u8_int" do not apply: this call has one road, and lsq_label_knn_info says how it
+ *               ran.  uint8 x uint8 input needs no integer road: the widened chain returns the same bits (3c).
+ *   LSQ_LABEL_TEST_ONE_SPLIT   the TEST HOOK of (3t): one block per query group, so that a single pool sees every row.  Same result.
+ *   lsq_label_knn_geometry   host only, no index: the rule the launch runs on.  queries_per_block = 4096 / pool_records (8 / 4 / 2 / 1 at nn <= 256 / 512 /
+ *               1024 / 2048), lds_bytes = the pools (32 KiB) + the staged tile, and the row ranges of (3t)'s rule over the groups of queries_per_block
+ *               queries: blocks_per_query ranges of rows_per_block rows (a multiple of 256).  d is checked and otherwise unused: the tile is 16 dimensions
+ *               deep at any d.
+ *   lsq_index_get_label_knn_info   the account of the last labelled k-NN call.  The counters are sums of integers: the same on every call. */
+typedef struct lsq_label_knn_info {
+    int64_t queries, rows;               /* of the last call */
+    int64_t queries_per_block, blocks_per_query;      /* the geometry: QB, and the most blocks that shared a query */
+    int64_t pool_records, lds_bytes;     /* P = 2 pow2ceil(max(nn, 256)); LDS of a block, the kernel's static words included */
+    int64_t offered;                     /* records that entered pools (candidates below the pool's bound of the moment) */
+    int64_t compactions, merged_runs;    /* pool compactions; runs merged where several blocks shared a query */
+    int64_t allowed_pairs;               /* SUM over queries of the rows that passed predicate and filter */
+    int64_t skipped_wave_steps;          /* (wave, 64-row step) pairs whose arithmetic was skipped: no candidate of any of the block's queries among them */
+    int64_t batches;                     /* batches of queries */
+    double scan_ms, merge_ms;            /* with option "profile" = 1 */
+} lsq_label_knn_info;
+LSQ_API int lsq_index_knn_labelled(lsq_index *ix, float *dists, int *ids, const void *queries, int queries_u8, const uint32_t *q_mask,
+                                   const uint32_t *q_want, int nq, int ldq, int nn, int id_base, int flags, int on_device);
+LSQ_API int lsq_index_get_label_knn_info(lsq_index *ix, lsq_label_knn_info *out);
+LSQ_API int lsq_label_knn_geometry(int64_t n, int d, int nn, int nq, int flags, lsq_label_geometry_info *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

@@ -130,6 +130,12 @@ class LabelGeometryInfo(_Struct):
 LABEL_ANY, LABEL_TEST_ONE_SPLIT = 1, 2
 
 
+class LabelKnnInfo(_Struct):
+    _fields_ = [("queries", C.c_int64), ("rows", C.c_int64), ("queries_per_block", C.c_int64), ("blocks_per_query", C.c_int64), ("pool_records", C.c_int64),
+                ("lds_bytes", C.c_int64), ("offered", C.c_int64), ("compactions", C.c_int64), ("merged_runs", C.c_int64), ("allowed_pairs", C.c_int64),
+                ("skipped_wave_steps", C.c_int64), ("batches", C.c_int64), ("scan_ms", C.c_double), ("merge_ms", C.c_double)]
+
+
 class IndexPackedDesc(_Struct):
     _fields_ = [("n", C.c_int64), ("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("codes", C.c_void_p), ("norm_codes", C.c_void_p),
                 ("cbnorms", C.c_void_p), ("ncb", C.c_int), ("codebooks", C.c_void_p), ("base", C.c_void_p), ("base_u8", C.c_int), ("ldb", C.c_int),
@@ -340,6 +346,10 @@ SIGNATURES = {
     "lsq_index_search_ivf_labelled": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i]),
     "lsq_index_get_label_info": (_i, [_vp, C.POINTER(LabelInfo)]),
     "lsq_label_geometry": (_i, [_i64, _i, _i, _i, _i, _i, C.POINTER(LabelGeometryInfo)]),
+    # labelled exact k-NN (since v3200): lsq_index_knn with a predicate per query, its account, the geometry rule (host only)
+    "lsq_index_knn_labelled": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    "lsq_index_get_label_knn_info": (_i, [_vp, C.POINTER(LabelKnnInfo)]),
+    "lsq_label_knn_geometry": (_i, [_i64, _i, _i, _i, _i, C.POINTER(LabelGeometryInfo)]),
     # the packed index: rows of m code bytes and one norm byte (since v1800), and the selection statistics of an index's last scan
     "lsq_index_create_packed": (_i, [C.POINTER(_vp), _vp, C.POINTER(IndexPackedDesc)]),
     "lsq_index_get_packed_info": (_i, [_vp, C.POINTER(IndexPackedInfo)]),
@@ -428,7 +438,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 3100    # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 3200    # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

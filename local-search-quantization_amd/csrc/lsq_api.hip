@@ -624,6 +624,8 @@ struct lsq_index {
     PhaseClock<2> hclock;
     lsq_snapshot_io_info sinfo{};                      // the last lsq_index_save, or the lsq_index_load that made this index
     lsq_label_state *labels = nullptr;                 // labelled search (lsq_label.hip): the row labels, owned copies, and its scratch; null until lsq_index_set_labels
+    lsq_labelknn_state *label_knn = nullptr;           // labelled exact k-NN (lsq_labelknn.hip): the scratch of its calls; null until the first lsq_index_knn_labelled
+    lsq_label_knn_info lknn{};                         // ... and the account of the last one
 };
 
 // the filter as a scan over all rows takes it: nothing without one; else the compact road -- the ascending list of allowed rows -- where the measured rule
@@ -690,6 +692,7 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     lsq_ivf_free(ix->ivf);
     lsq_filter_free(ix->filter);
     lsq_label_free(ix->labels);
+    lsq_labelknn_free(ix->label_knn);
     ix->clock.release();
     delete ix;
     return LSQ_OK;
@@ -1260,6 +1263,46 @@ extern "C" int lsq_index_search_ivf_labelled(lsq_index *ix, float *dists, int *i
         ix->stats.scan_ms += li.coarse_ms + li.lut_ms + li.scan_ms + li.merge_ms;
         return LSQ_OK;
     });
+}
+
+// ---- labelled exact k-NN (lsq_labelknn.hip): lsq_index_knn with the labelled searches' predicate per query -- their ground truth ---------------
+extern "C" int lsq_index_knn_labelled(lsq_index *ix, float *dists, int *ids, const void *queries, int queries_u8, const uint32_t *q_mask,
+                                      const uint32_t *q_want, int nq, int ldq, int nn, int id_base, int flags, int on_device) {
+    const char *fn = "lsq_index_knn_labelled";
+    if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
+    if (!ix->base) { lsq_set_error("%s: the index holds no base rows", fn); return LSQ_EINVAL; }
+    if (!dists || !ids || !queries || !q_mask || !q_want) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    if (nq < 1 || ldq < ix->d) { lsq_set_error("%s: needs nq >= 1 and ldq >= d (got nq=%d ldq=%d d=%d)", fn, nq, ldq, ix->d); return LSQ_EINVAL; }
+    int64_t nlab = 0;
+    const uint32_t *labels = lsq_label_device(ix->labels, &nlab);
+    if (!labels) { lsq_set_error("%s: the index has no labels (call lsq_index_set_labels first; lsq_index_add / _compact drop them)", fn); return LSQ_EINVAL; }
+    if (nlab != ix->n) { lsq_set_error("%s: the labels answer for %lld rows, the index holds %lld", fn, (long long)nlab, (long long)ix->n); return LSQ_EINVAL; }
+    if (flags & ~(LSQ_LABEL_ANY | LSQ_LABEL_TEST_ONE_SPLIT)) { lsq_set_error("%s: unknown flags %d", fn, flags); return LSQ_EINVAL; }
+    if (nn < 1 || nn > ix->n) { lsq_set_error("%s: needs 1 <= nn <= n (got nn=%d n=%lld)", fn, nn, (long long)ix->n); return LSQ_EINVAL; }
+    if (nn > LSQ_IVF_SELECT_MAX_NN) { lsq_set_error("%s: needs nn <= %d (got %d)", fn, LSQ_IVF_SELECT_MAX_NN, nn); return LSQ_EINVAL; }
+    if (id_base != 0 && id_base != 1) { lsq_set_error("%s: id_base must be 0 or 1 (got %d)", fn, id_base); return LSQ_EINVAL; }
+    const int q_u8 = queries_u8 != 0;
+    if (!q_u8 && ((uintptr_t)queries & 3) != 0) { lsq_set_error("%s: the f32 queries are not 4-byte aligned", fn); return LSQ_EINVAL; }
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    IndexCall call{ix, nq, on_device != 0};
+    lsq_labelknn_call lc;
+    LSQ_TRY(call.rows(ix->s_qexact, queries, q_u8 ? 1 : sizeof(float), ldq, ix->d, false, !on_device, &lc.Q, &lc.ldq));      // as they lie
+    LSQ_TRY(call.outputs(dists, ids, nn));
+    lc.base = ix->base; lc.base_fmt = ix->base_u8; lc.ldb = ix->ldb; lc.q_u8 = q_u8; lc.n = ix->n; lc.d = ix->d;
+    lc.labels = labels; lc.q_mask = q_mask; lc.q_want = q_want;
+    lc.nq = nq; lc.nn = nn; lc.flags = flags; lc.id_base = id_base; lc.timed = c->profile ? 1 : 0;
+    lc.dists = call.out_d; lc.ids = call.out_i;
+    if (lsq_filter_active(ix->filter)) lc.bits = lsq_filter_get(ix->filter).bits;      // the dense road: a predicate per query has no compact form
+    lsq_filter_note_road(ix->filter, lc.bits ? 1 : 0);
+    LSQ_TRY(lsq_labelknn_search(c->stream, &ix->label_knn, lc, &ix->lknn));
+    return call.finish();
+}
+
+extern "C" int lsq_index_get_label_knn_info(lsq_index *ix, lsq_label_knn_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_label_knn_info: null argument"); return LSQ_EINVAL; }
+    *out = ix->lknn;
+    return LSQ_OK;
 }
 
 // ---- range search on the index (lsq_range.hip): every candidate row within a radius; the result is HELD by the index until fetched or dropped ----

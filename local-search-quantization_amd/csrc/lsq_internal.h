@@ -497,6 +497,22 @@ int lsq_label_search(hipStream_t s, lsq_label_state *st, const lsq_label_call &c
 int lsq_label_qb(int m, int packed, int nn);         // queries per block of the exhaustive geometry: the largest of 4, 2, 1 whose tables and pools fit 64 KiB
 size_t lsq_label_lds_bytes(int m, int packed, int nn, int qb);
 void lsq_label_split(int64_t n, int groups, int one_split, int *splits, int64_t *per);      // the row ranges: `splits` of `per` rows (a multiple of 256)
+const uint32_t *lsq_label_device(const lsq_label_state *st, int64_t *n);      // the labels in force ([*n], device, original row order), or null
+
+// ---- labelled exact k-NN (lsq_labelknn.hip): a distance tile that selects inside its walk, a predicate per (row, query) -----------------------
+struct lsq_labelknn_state;                           // the scratch of its calls, owned by the index
+void lsq_labelknn_free(lsq_labelknn_state *st);
+// one call, every pointer but q_mask / q_want (host or device) a device pointer.  base [n] rows of d elements of base_fmt (lsq_search_input's base_u8), ldb
+// elements apart; Q [nq] rows of f32 or (q_u8) bytes, ldq elements apart; labels [n]; bits: the filter in force by row, or null; dists / ids [nq][nn]
+struct lsq_labelknn_call {
+    const void *base = nullptr; int base_fmt = 0; int64_t ldb = 0;
+    const void *Q = nullptr; int q_u8 = 0; int64_t ldq = 0;
+    int64_t n = 0; int d = 0;
+    const uint32_t *labels = nullptr, *q_mask = nullptr, *q_want = nullptr, *bits = nullptr;
+    int nq = 0, nn = 0, flags = 0, id_base = 0, timed = 0;
+    float *dists = nullptr; int *ids = nullptr;
+};
+int lsq_labelknn_search(hipStream_t s, lsq_labelknn_state **st, const lsq_labelknn_call &c, lsq_label_knn_info *info);
 
 // ---- range search on a resident index (lsq_range.hip): every candidate row within a radius, held by the index until fetched or dropped ------------------
 struct lsq_range_state;

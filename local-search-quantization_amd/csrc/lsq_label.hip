@@ -280,6 +280,11 @@ void lsq_label_free(lsq_label_state *st) {
 bool lsq_label_active(const lsq_label_state *st) { return st && st->set; }
 void lsq_label_drop(lsq_label_state *st) { if (st) st->set = st->layout_valid = false; }
 void lsq_label_drop_layout(lsq_label_state *st) { if (st) st->layout_valid = false; }
+const uint32_t *lsq_label_device(const lsq_label_state *st, int64_t *n) {
+    if (!lsq_label_active(st)) return nullptr;
+    *n = st->n;
+    return st->labels.as<uint32_t>();
+}
 
 void lsq_label_get_info(const lsq_label_state *st, lsq_label_info *out) {
     *out = st ? st->info : lsq_label_info{};

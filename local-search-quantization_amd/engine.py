@@ -905,10 +905,14 @@ class Index(_Handle):
         self._eng._call(side, "lsq_index_rerank", p(dists), p(ids), p(Q), p(cand), nq, self.d, int(L), int(k), int(id_base), int(self._dev), h=self._h)
         return dists, ids
 
-    def knn(self, Q, k, id_base=0):
+    def knn(self, Q, k, id_base=0, where=None, any_of=False, flags=0):
         """Exact k-NN over the resident base rows (f32; uint8, float16 and bfloat16 rows are widened in registers, never in memory): the ground truth of a recall figure.  Q (nq,>=d) float32 or uint8 rows
         with unit column stride, any row pitch and byte offset (numpy on an Engine.index, torch on an Engine.index_dev); the first d columns are read.
-        -> dists (nq,k) float32 ascending with lsq_knn_exact's bits, ids (nq,k) int32 in id_base; ties by smaller id   [lsq_index_knn]"""
+        where=(mask, want), any_of: search()'s predicate per query over the labels of set_labels, on top of a filter in force -- the ground truth of a
+        labelled search: each query's row is what set_filter(its candidates) and a one-query knn would return, bit for bit, (+inf, id_base-1) where it has
+        fewer than k candidates; k <= 2048.  where=None: exactly the plain call.  flags (with where): _lib.LABEL_TEST_ONE_SPLIT, a TEST HOOK -- one block per
+        query group, the same result.
+        -> dists (nq,k) float32 ascending with lsq_knn_exact's bits, ids (nq,k) int32 in id_base; ties by smaller id   [lsq_index_knn, lsq_index_knn_labelled]"""
         side = self._side
         if side.dev:
             Q, u8 = side.take_x(Q, "Q", rows=True)
@@ -920,8 +924,20 @@ class Index(_Handle):
         _shapes(("Q", Q, (None, max(self.d, Q.shape[-1]))))           # at least d columns
         nq, p = Q.shape[0], side.ptr
         dists, ids = side.topk(nq, int(k), Q)
-        self._eng._call(side, "lsq_index_knn", p(dists), p(ids), p(Q), int(u8), nq, int(side.pitch(Q)), int(k), int(id_base), int(self._dev), h=self._h)
+        if where is None:
+            self._eng._call(side, "lsq_index_knn", p(dists), p(ids), p(Q), int(u8), nq, int(side.pitch(Q)), int(k), int(id_base), int(self._dev), h=self._h)
+            return dists, ids
+        mask, want = self._where(where, nq)
+        fl = int(flags) | (_lib.LABEL_ANY if any_of else 0)
+        self._eng._call(side, "lsq_index_knn_labelled", p(dists), p(ids), p(Q), int(u8), p(mask), p(want), nq, int(side.pitch(Q)), int(k), int(id_base), fl,
+                        int(self._dev), h=self._h)
         return dists, ids
+
+    def label_knn_info(self):
+        """of the last knn(where=) call: queries, rows, queries_per_block, blocks_per_query, pool_records, lds_bytes, offered, compactions, merged_runs,
+        allowed_pairs (the sum over queries of the rows that passed predicate and filter), skipped_wave_steps, batches, scan_ms / merge_ms (with
+        profile=True)   [lsq_index_get_label_knn_info]"""
+        return self._info("lsq_index_get_label_knn_info", _lib.LabelKnnInfo)
 
     def set_lists(self, centroids, assign):
         """Lay inverted lists over the index's codes: centroids (nlist,d) float32, assign (n,) int32 0-based list of every row (train_coarse and
