@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 3200
+#define LSQ_VERSION 3300
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -148,6 +148,9 @@ LSQ_API int lsq_set_stream(lsq_ctx *ctx, void *hip_stream);
  *                    in LDS while it scans the probed lists, instead of sorting segments afterwards, where nn (or the shortlist) <= 2048.  Same results, bit for
  *                    bit; any non-zero value is 1.
  *   "knn_prefilter_cap" (default 0): pending pairs per query of the pre-filter; 0 = automatic (twice the list capacity).  A test hook: same results.
+ *   "partition_mfma" (0/1, default 0; since v3300, (3i)): 1 = lsq_partition_assign of every lsq_partition created on this context finds the nearest centroid
+ *                    on the f32 matrix cores and rechecks its candidates by the direct chain.  Same list_of_row and dist, bit for bit; any non-zero value is 1.
+ *   "partition_mfma_cap" (default 0): pending candidates per row of that road; 0 = automatic.  A test hook: same results.
  *   "range_batch" (default 0): records per fill batch of lsq_index_range_search on every lsq_index created on this context; 0 = automatic (2^28).  A
  *        test hook: small shapes cross batch boundaries, and a query larger than the budget is a batch of its own.  Same results.
  *   (liblsq_mi355x_tuning.so only) "ablation": timing-only kernel variants whose results are garbage. */
@@ -659,6 +662,27 @@ LSQ_API int lsq_partition_create(lsq_partition **out, lsq_ctx *ctx, const lsq_pa
 LSQ_API int lsq_partition_destroy(lsq_partition *p);
 LSQ_API int lsq_partition_get_centroids(lsq_partition *p, float *out, int on_device);
 LSQ_API int lsq_partition_get_info(lsq_partition *p, lsq_partition_info *out);
+/* Option "partition_mfma" = 1 (since v3300; csrc/lsq_passign.hip): assign computes a = (Nc + Nx) - 2 <c, x> on v_mfma_f32_32x32x2_f32, keeps per
+ * row the centroids whose window [a - w, a + w], w = kappa_d (Nc + Nx) + eta_d (lsq_knn_prefilter_bound), reaches below the smallest upper end seen so far, and
+ * takes the minimum by (distance, list id) of the direct chain over those: THE SAME list_of_row and dist.  Rows with more candidates than the pending capacity
+ * and rows whose squared norm is not finite are redone by the direct search; if they are more than half of a call's rows, the whole call is (switched_off).
+ * served = 0 with a reason: the option is 0, or d > 16 384 (the limit of the bound).  lsq_partition_get_mfma_info: the account of the last assign. */
+enum { LSQ_PARTITION_MFMA_NOT_ASKED = 1,      /* option "partition_mfma" is 0 */
+       LSQ_PARTITION_MFMA_WIDE = 2 };         /* d > LSQ_KNN_PREFILTER_MAX_D */
+typedef struct lsq_partition_mfma_info {
+    int64_t served, reason;              /* 1 = the matrix-core road ran; else why not (LSQ_PARTITION_MFMA_*) */
+    int64_t resident;                    /* 1 = a block kept its 128 rows in LDS for the whole walk (ceil16(d) <= 256); 0 = both operands streamed */
+    int64_t rows, nlist;                 /* n, nlist */
+    int64_t splits;                      /* parts the centroids were split into (> 1 when n / 128 blocks would not fill the chip) */
+    int64_t pairs, pending;              /* n nlist; candidates appended to pending lists */
+    int64_t cap;                         /* pending capacity per row */
+    int64_t overflow_rows, nonfinite_rows;  /* rows with more candidates than cap; rows whose f32 squared norm is inf or NaN */
+    int64_t redo_rows;                   /* rows handed to the direct search (the two above) */
+    int64_t switched_off;                /* 1 = more than half of a pass needed the redo: the call was answered by the direct search */
+    double kappa, eta;                   /* the window's constants */
+    double norms_ms, scan_ms, recheck_ms, redo_ms;      /* with option "profile" = 1 */
+} lsq_partition_mfma_info;
+LSQ_API int lsq_partition_get_mfma_info(lsq_partition *p, lsq_partition_mfma_info *out);
 LSQ_API int lsq_partition_assign(lsq_partition *p, const void *X, int x_u8, int64_t n, int ldx, int32_t *list_of_row, float *dist, int on_device);
 LSQ_API int lsq_partition_update(lsq_partition *p, const void *X, int x_u8, int64_t n, int ldx, const int32_t *list_of_row, int32_t *counts,
                                  int on_device);

@@ -253,6 +253,17 @@ class PartitionInfo(_Struct):
 PARTITION_ASSIGN, PARTITION_UPDATE, PARTITION_RESIDUALS, PARTITION_CODE_NORMS = 1, 2, 3, 4
 
 
+class PartitionMfmaInfo(_Struct):
+    _fields_ = [("served", C.c_int64), ("reason", C.c_int64), ("resident", C.c_int64), ("rows", C.c_int64), ("nlist", C.c_int64), ("splits", C.c_int64),
+                ("pairs", C.c_int64), ("pending", C.c_int64), ("cap", C.c_int64), ("overflow_rows", C.c_int64), ("nonfinite_rows", C.c_int64),
+                ("redo_rows", C.c_int64), ("switched_off", C.c_int64), ("kappa", C.c_double), ("eta", C.c_double), ("norms_ms", C.c_double),
+                ("scan_ms", C.c_double), ("recheck_ms", C.c_double), ("redo_ms", C.c_double)]
+
+
+# lsq_partition_mfma_info.reason: why an assign took the direct road (0: it did not)
+PARTITION_MFMA_NOT_ASKED, PARTITION_MFMA_WIDE = 1, 2
+
+
 class Q16SnapshotNode(_Struct):
     _fields_ = [("loU", C.c_float), ("invD", C.c_float), ("D", C.c_float), ("hiq", C.c_float), ("window", C.c_int32), ("pad_", C.c_int32),
                 ("slack", C.c_double)]
@@ -407,6 +418,7 @@ SIGNATURES = {
     "lsq_partition_destroy": (_i, [_vp]),
     "lsq_partition_get_centroids": (_i, [_vp, _vp, _i]),
     "lsq_partition_get_info": (_i, [_vp, C.POINTER(PartitionInfo)]),
+    "lsq_partition_get_mfma_info": (_i, [_vp, C.POINTER(PartitionMfmaInfo)]),      # since v3300: the account of assign under option "partition_mfma"
     "lsq_partition_assign": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i]),
     "lsq_partition_update": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i]),
     "lsq_partition_residuals": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i, _i]),
@@ -438,7 +450,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 3200    # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 3300   # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

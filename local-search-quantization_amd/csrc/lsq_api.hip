@@ -114,6 +114,7 @@ struct lsq_ctx {
     int knn_u8_mfma = 0;                               // option "knn_u8_mfma": lsq_index_knn's integer road runs its thresholded pass on the i8 matrix cores (lsq_knnu.hip)
     int ivf_select = 0;                                // option "ivf_select": lsq_index_search_ivf selects inside its scan (lsq_ivfsel.hip) where that road serves the call
     int knn_prefilter_half = 0;                        // option "knn_prefilter_half": with "knn_prefilter", half-precision rows take the 16-bit tile (lsq_knnh.hip)
+    int partition_mfma = 0, partition_mfma_cap = 0;    // options "partition_mfma" (lsq_partition_assign runs on the matrix cores: lsq_passign.hip) and "partition_mfma_cap" (its pending capacity per row; a test hook)
     lsq_knn_prefilter_info knn_pf{};                   // ... where the account of the last lsq_knn_exact / lsq_knn_exact_dev call is written (no getter yet: DESIGN 4.29)
     int64_t rerank_batch = 0;                          // option "rerank_batch": queries per re-rank batch of this context's indexes (0 = automatic); a test hook
     int64_t range_batch = 0;                           // option "range_batch": records per fill batch of lsq_index_range_search (0 = automatic); a test hook
@@ -162,6 +163,11 @@ int lsq_ctx_bind(lsq_ctx *c, hipStream_t *stream, int *profile) {
     *stream = c->stream;
     *profile = c->profile;
     return LSQ_OK;
+}
+
+void lsq_ctx_partition_mfma(const lsq_ctx *c, int *on, int *cap) {
+    *on = c->partition_mfma;
+    *cap = c->partition_mfma_cap;
 }
 
 struct Timer {        // brackets a group of launches with an event pair when profiling is on
@@ -330,6 +336,11 @@ extern "C" int lsq_set_option(lsq_ctx *c, const char *key, int64_t value) {
     else if (!strcmp(key, "knn_prefilter_cap")) {
         if (value < 0 || value > (int64_t)INT32_MAX) { lsq_set_error("knn_prefilter_cap must lie in 0..2^31-1"); return LSQ_EINVAL; }
         c->knn_prefilter_cap = (int)value;
+    }
+    else if (!strcmp(key, "partition_mfma")) c->partition_mfma = value != 0;
+    else if (!strcmp(key, "partition_mfma_cap")) {
+        if (value < 0 || value > (1 << 20)) { lsq_set_error("partition_mfma_cap must lie in 0..2^20"); return LSQ_EINVAL; }
+        c->partition_mfma_cap = (int)value;
     }
     else if (!strcmp(key, "rerank_batch")) {
         if (value < 0) { lsq_set_error("rerank_batch must be >= 0"); return LSQ_EINVAL; }

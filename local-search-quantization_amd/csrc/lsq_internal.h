@@ -688,6 +688,23 @@ int lsq_snap_launch_unpack(hipStream_t s, const uint8_t *rows, int64_t n, int m,
 // ---- what a handle that lives in a file of its own (lsq_partition.hip) needs of its context (lsq_api.hip): its device made current, the stream it is bound
 // to now, option "profile".  Nothing of the context is written ------------------------------------------------------------------------------------------
 int lsq_ctx_bind(lsq_ctx *c, hipStream_t *stream, int *profile);
+// ... and its options "partition_mfma" (0 / 1) and "partition_mfma_cap" (pending capacity per row, 0 = the default)
+void lsq_ctx_partition_mfma(const lsq_ctx *c, int *on, int *cap);
+
+// ---- the partition's assign on the matrix cores (lsq_passign.hip).  Every pointer is a device pointer; ix: the handle's base-only index over
+// cent, for the rows the road hands back.  *done = 0: not served (info->reason) or switched off: the caller runs the direct search for the whole call -------
+struct lsq_passign_state;      // buffers of the road, owned by the partition handle
+void lsq_passign_free(lsq_passign_state *st);
+struct lsq_passign_call {
+    const void *X; int x_u8; int64_t n, ldx; int d;
+    const float *cent; int nlist;
+    int32_t *lor; float *dist;               // dist may be null
+    int cap_opt, profile;
+    lsq_index *ix;
+};
+int lsq_passign_run(hipStream_t s, lsq_passign_state **st, const lsq_passign_call &c, lsq_partition_mfma_info *info, int *done);
+// out[i] = the f32 fma sum of squares of row i of X (f32, or uint8 with x_u8): knnm_norms_kernel (lsq_knnm.hip)
+int lsq_knnm_launch_row_norms(hipStream_t s, const void *X, int x_u8, int64_t ld, int n, int d, float *out);
 
 // argument checks of the PQ / OPQ scan (lsq_linscan.hip), shared by the host drop-in and the device scan
 int lsq_linscan_pq_check(const char *fn, const void *dists, const void *res, const void *codes, const void *centers, const void *queries, int N,

@@ -309,6 +309,11 @@ int lsq_knnm_launch_norms(hipStream_t s, const lsq_search_input &in, int nq, flo
     return launch_norms(s, static_cast<const float *>(in.base), (int64_t)in.bstride, in.n, in.d, nx);
 }
 
+int lsq_knnm_launch_row_norms(hipStream_t s, const void *X, int x_u8, int64_t ld, int n, int d, float *out) {
+    if (x_u8) return launch_norms(s, static_cast<const uint8_t *>(X), ld, n, d, out);
+    return launch_norms(s, static_cast<const float *>(X), ld, n, d, out);
+}
+
 // MODE 0 of one batch on the pre-filtered road: pending lists, then the recheck into the candidate lists (count zeroed by the caller, as for the direct scan)
 int lsq_knnm_launch(hipStream_t s, const lsq_search_input &in, int q0, int nqb, const uint32_t *tau, unsigned *count, int cap, uint64_t *out, int idbits,
                     const lsq_knnm_work &w) {

@@ -249,6 +249,8 @@ struct lsq_partition {
     DevBuf s_codes, s_K, s_cb, s_nc, s_dbn;            // code_norms' staging
     PhaseClock<3> clock;
     lsq_partition_info info{};
+    lsq_passign_state *mfma = nullptr;                 // assign with option "partition_mfma": the matrix-core road's buffers (lsq_passign.hip), made at its first call
+    lsq_partition_mfma_info mfma_info{};               // ... and the account of the last assign
 };
 
 extern "C" int lsq_partition_destroy(lsq_partition *p) {
@@ -257,6 +259,7 @@ extern "C" int lsq_partition_destroy(lsq_partition *p) {
     int profile = 0;
     if (lsq_ctx_bind(p->ctx, &s, &profile) == LSQ_OK) (void)hipStreamSynchronize(s);
     (void)lsq_index_destroy(p->ix);
+    lsq_passign_free(p->mfma);
     DevBuf *bufs[] = {&p->cent, &p->off, &p->words, &p->s_x, &p->s_lor, &p->s_out, &p->s_cnt, &p->s_dist, &p->s_codes, &p->s_K, &p->s_cb, &p->s_nc, &p->s_dbn};
     for (DevBuf *b : bufs) b->release();
     p->rows.release();
@@ -309,6 +312,12 @@ extern "C" int lsq_partition_get_centroids(lsq_partition *p, float *out, int on_
 extern "C" int lsq_partition_get_info(lsq_partition *p, lsq_partition_info *out) {
     if (!p || !out) { lsq_set_error("lsq_partition_get_info: null argument"); return LSQ_EINVAL; }
     *out = p->info;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_partition_get_mfma_info(lsq_partition *p, lsq_partition_mfma_info *out) {
+    if (!p || !out) { lsq_set_error("lsq_partition_get_mfma_info: null argument"); return LSQ_EINVAL; }
+    *out = p->mfma_info;
     return LSQ_OK;
 }
 
@@ -373,14 +382,45 @@ extern "C" int lsq_partition_assign(lsq_partition *p, const void *X, int x_u8, i
         if (on_device) { LSQ_TRY(p->s_dist.ensure(sizeof(float) * (size_t)n)); dd = p->s_dist.as<float>(); }
         else { hd.resize((size_t)n); dd = hd.data(); }
     }
+    lsq_partition_info info{};
+    info.call = LSQ_PARTITION_ASSIGN; info.rows = n;
+    // option "partition_mfma": the matrix-core road (lsq_passign.hip) on device buffers -- a host call's rows, ids and distances through the handle's staging
+    int mfma = 0, mfma_cap = 0;
+    lsq_ctx_partition_mfma(p->ctx, &mfma, &mfma_cap);
+    lsq_partition_mfma_info mi{};
+    mi.reason = LSQ_PARTITION_MFMA_NOT_ASKED; mi.rows = n; mi.nlist = p->nlist;
+    if (mfma) {
+        lsq_passign_call call{};
+        LSQ_TRY(stage_rows(s, p, X, x_u8, n, ldx, on_device, &call.X));
+        call.x_u8 = x_u8 != 0; call.n = n; call.ldx = ldx; call.d = p->d; call.cent = p->cent.as<float>(); call.nlist = p->nlist;
+        call.lor = list_of_row; call.dist = dist;
+        if (!on_device) {
+            LSQ_TRY(p->s_out.ensure(sizeof(int32_t) * (size_t)n));
+            call.lor = p->s_out.as<int32_t>();
+            if (dist) { LSQ_TRY(p->s_dist.ensure(sizeof(float) * (size_t)n)); call.dist = p->s_dist.as<float>(); }
+        }
+        call.cap_opt = mfma_cap; call.profile = profile; call.ix = p->ix;
+        int done = 0;
+        LSQ_TRY(lsq_passign_run(s, &p->mfma, call, &mi, &done));
+        info.kernel_ms = mi.norms_ms + mi.scan_ms + mi.recheck_ms + mi.redo_ms;
+        if (done) {
+            if (!on_device) {
+                LSQ_HIP(hipMemcpyAsync(list_of_row, call.lor, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+                if (dist) LSQ_HIP(hipMemcpyAsync(dist, call.dist, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
+            }
+            LSQ_HIP(hipStreamSynchronize(s));
+            p->mfma_info = mi;
+            p->info = info;
+            return LSQ_OK;
+        }
+    }
+    p->mfma_info = mi;
     // ids [n][1] int32 0-based: the lists as they are
     LSQ_TRY(lsq_index_knn(p->ix, dd, list_of_row, X, x_u8 != 0, (int)n, ldx, 1, 0, on_device));
     if (on_device) LSQ_HIP(hipStreamSynchronize(s));
     lsq_index_knn_info ki{};
     LSQ_TRY(lsq_index_get_knn_info(p->ix, &ki));
-    lsq_partition_info info{};
-    info.call = LSQ_PARTITION_ASSIGN; info.rows = n;
-    info.kernel_ms = ki.norms_ms + ki.scan_ms + ki.select_ms;
+    info.kernel_ms += ki.norms_ms + ki.scan_ms + ki.select_ms;
     p->info = info;
     return LSQ_OK;
 }

@@ -1507,6 +1507,12 @@ class Partition(_Handle):
         (residuals: 16, 4 or 1), group_ms / kernel_ms (with profile=True)"""
         return self._info("lsq_partition_get_info", _lib.PartitionInfo)
 
+    def mfma_info(self):
+        """what the matrix-core road (Engine.set_option("partition_mfma", 1)) did in the last assign: served / reason, resident, rows, nlist, splits,
+        pairs, pending, cap, overflow_rows, nonfinite_rows, redo_rows, switched_off, kappa, eta, norms_ms / scan_ms / recheck_ms / redo_ms (with
+        profile=True)   [lsq_partition_get_mfma_info]"""
+        return self._info("lsq_partition_get_mfma_info", _lib.PartitionMfmaInfo)
+
 
 # -- host-only pieces of the path (no GPU needed) ---------------------------------------------
 

@@ -1,7 +1,7 @@
 """The reference's demos/demo_lsq_gpu.jl flow against this package (BASELINE's secondary metric, recall@1 on SIFT1M):
 OPQ init -> ChainQ init -> train_lsq -> encode the base set on the GPU -> quantise norms -> ADC linear scan -> recall.
 
-    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L [--base-format f16|bf16]] [--ivf NLIST:NPROBE [--ivf-select] [--residual] [--grow FRACTION]] [--delete FRACTION] [--labels NCAT] [--radius R] [--reconstruct] [--save PATH] [--load PATH] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
+    LSQ_DATA_DIR=/data python tools/demo_lsq_gpu.py [--resident] [--bvecs] [--rerank L [--base-format f16|bf16]] [--ivf NLIST:NPROBE [--ivf-select] [--residual [--partition-mfma]] [--grow FRACTION]] [--delete FRACTION] [--labels NCAT] [--radius R] [--reconstruct] [--save PATH] [--load PATH] [--init beam:L] [--norm-byte] [nread_train] [nread_base] [nquery]
 
 --resident: the three trainers run on ONE device tensor (train_opq_dev -> train_chainq_dev -> train_lsq_dev): the training set is uploaded once and
 the codes and codebooks stay in HBM between the stages; the rest of the flow is unchanged.
@@ -29,6 +29,9 @@ Index.ivf_select_info reports, and whether the ids equal the default road's.
 centroids, codebooks from the three resident trainers run on the training set's residuals (Partition.assign / residuals), the base set -- f32, or un-widened
 bytes with --bvecs -- through build_ivf_residual_index, searched with add_coarse; with --norm-byte the norm codebook is the scalar k-means of the training
 residuals' code_norms and the index is packed.  Its recall curve is printed as a third column.
+
+--partition-mfma (with --residual): the residual build under Engine.set_option("partition_mfma", 1) -- Partition.assign on the matrix cores -- with what
+Partition.mfma_info reports of the build's assignment; the assignment is held to ivf_assign's either way.
 
 --norm-byte: the norm byte that quantize_norms computes stays a byte up to the search: a packed index (Engine.index_packed, rows of m code bytes and one
 norm byte: the 64-bit code at m = 7) is searched through linscan_lsq_bytes, and its ids and distances are checked to equal the float-norm run's.  The
@@ -186,7 +189,7 @@ def train_resident(x_train, m, h, niter, ilsiter, icmiter, randord, npert):
     return [np.ascontiguousarray(K[i * h:(i + 1) * h].T) for i in range(m)], B, cbnorms, B_norms, obj
 
 
-def residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, npert, nprobe, knn, norm_byte, n0=None, recon=False):
+def residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, npert, nprobe, knn, norm_byte, n0=None, recon=False, mfma=False):
     """the residual index over the SAME centroids and lists, resident on the device -> (recall curve, seconds of the build, error in base, and with n0 the
     recall curve of the index built on the first n0 rows and grown by the rest -- else None)"""
     import torch
@@ -204,9 +207,15 @@ def residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         rep = {}
+        eng.set_option("partition_mfma", int(mfma))
         ix = lsq.build_ivf_residual_index(dXb, part, dK, m, engine=eng, ilsiters=[16], icmiter=icmiter, npert=npert, randord=randord, cbnorms=cb, report=rep)
         torch.cuda.synchronize()
         t_build = time.perf_counter() - t0
+        eng.set_option("partition_mfma", 0)
+        if mfma:
+            mi = part.mfma_info()
+            print("Assignment with partition_mfma: served %d (resident rows %d, %d parts), %.2f candidates per row, %d rows redone, switched off %d"
+                  % (mi["served"], mi["resident"], mi["splits"], mi["pending"] / max(mi["rows"], 1), mi["redo_rows"], mi["switched_off"]))
         assert np.array_equal(rep["assign"].cpu().numpy(), assign), "the device assignment differs from ivf_assign's"
         with ix:
             _, ridx = ix.search_ivf(torch.from_numpy(Q).cuda(), knn, nprobe, add_coarse=True)
@@ -288,6 +297,11 @@ def main():
         argv.remove("--ivf-select")
         if not ivf:
             raise SystemExit("--ivf-select needs --ivf NLIST:NPROBE")
+    part_mfma = "--partition-mfma" in argv
+    if part_mfma:
+        argv.remove("--partition-mfma")
+        if "--residual" not in argv:
+            raise SystemExit("--partition-mfma needs --ivf NLIST:NPROBE --residual")
     fraction = None
     if "--filter" in argv:
         at = argv.index("--filter")
@@ -459,7 +473,7 @@ def main():
                 grec = lsq.eval_recall(gt, np.ascontiguousarray(gidx.T).astype(np.uint32), knn)
             if residual:
                 rrec_ivf, t_res, mse, gres = residual_ivf(eng, x_train, x_base, Q, gt, cent, assign, m, h, niter, ilsiter, icmiter, randord, min(npert, m),
-                                                          nprobe, knn, norm_byte, n0, recon)
+                                                          nprobe, knn, norm_byte, n0, recon, part_mfma)
         irec = lsq.eval_recall(gt, np.ascontiguousarray(iidx.T).astype(np.uint32), knn)
         print("IVF search (nlist %d, nprobe %d): %.3f s on the resident index; %.0f of %d rows probed per query, %d of %d queries on the thresholded road"
               % (nlist, nprobe, t_ivf, info["probed_rows"] / Q.shape[0], x_base.shape[1], info["threshold_queries"], Q.shape[0]))

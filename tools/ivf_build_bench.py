@@ -140,6 +140,87 @@ def main(n, nlist):
     out.close()
 
 
+def mfma_main(n, nlist, d, followers):
+    """--mfma [n nlist d [followers]]: Partition.assign with option "partition_mfma" on and off (csrc/lsq_passign.hip), alternated on one
+    Partition in one process, one warm-up, REPS repeats, medians with the spread of each leg; kernel_ms is the call's device time (events inside the
+    call, option "profile"), wall_ms the clock around the call.  Lines are APPENDED to profiles/partition_mfma.jsonl"""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    centres = 3.0 * torch.randn((2 * nlist, d), device=dev, generator=g)
+    X = (centres[torch.randint(0, centres.shape[0], (n,), device=dev, generator=g)] + torch.randn((n, d), device=dev, generator=g)).contiguous()
+    X8 = torch.clamp(torch.round(X * 6 + 128), 0, 255).to(torch.uint8)
+    out = open(os.path.join(ROOT, "profiles", "partition_mfma.jsonl"), "a")
+
+    def emit(**line):
+        s = json.dumps(dict(bench="partition_mfma", n=n, d=d, nlist=nlist, **line))
+        print(s, flush=True)
+        out.write(s + "\n")
+        out.flush()
+
+    def legs(call):
+        """-> {on/off: (median, min, max)} of call() -> ms, the option alternated"""
+        ms = {0: [], 1: []}
+        for rep in range(REPS + 1):
+            for on in (0, 1):
+                eng.set_option("partition_mfma", on)
+                t = call()
+                if rep:
+                    ms[on].append(t)
+        eng.set_option("partition_mfma", 0)
+        return {k: (round(med(v), 3), round(min(v), 3), round(max(v), 3)) for k, v in ms.items()}
+
+    with lsq.Engine(0) as eng:
+        eng.set_option("profile", 1)
+        ncoarse = min(n, 100_000)
+        for rows, Xr in (("f32", X), ("uint8", X8)):
+            part, _ = lsq.train_coarse_dev(Xr[:ncoarse], nlist, 1, 2, engine=eng)
+            with part:
+                res, acct, phases = {}, {}, {0: [], 1: []}
+
+                def assign():
+                    on = int(len(phases[0]) > len(phases[1]))                   # legs() alternates off, on
+                    w, res[on] = wall(lambda: part.assign(Xr, want_dist=True))
+                    acct[on] = part.mfma_info()
+                    phases[on].append((part.info()["kernel_ms"], w))
+                    return part.info()["kernel_ms"]
+
+                t = legs(assign)
+                mi = acct[1]
+                flop_ms = 2.0 * n * nlist * d / 157e12 * 1e3
+                emit(item="assign", rows=rows, reps=REPS, kernel_ms_off=t[0], kernel_ms_on=t[1], speedup=round(t[0][0] / t[1][0], 2),
+                     wall_ms_off=round(med([w for _, w in phases[0][1:]]), 3), wall_ms_on=round(med([w for _, w in phases[1][1:]]), 3),
+                     ids_equal=bool(torch.equal(res[0][0], res[1][0])), dist_equal=bool(torch.equal(res[0][1].view(torch.int32), res[1][1].view(torch.int32))),
+                     phases_ms={k: round(mi[k], 3) for k in ("norms_ms", "scan_ms", "recheck_ms", "redo_ms")}, mfma_bound_ms=round(flop_ms, 3),
+                     scan_share_of_mfma_peak=round(flop_ms / mi["scan_ms"], 3) if mi["scan_ms"] else None, appends_per_row=round(mi["pending"] / n, 3),
+                     **{k: mi[k] for k in ("served", "resident", "splits", "cap", "overflow_rows", "nonfinite_rows", "redo_rows", "switched_off")})
+                if followers and rows == "f32":
+                    dassign = part.assign(Xr)
+                    scratch = eng.partition_dev(part.centroids())
+
+                    def lloyd():
+                        return wall(lambda: scratch.update(Xr, scratch.assign(Xr)))[0]
+
+                    t = legs(lloyd)
+                    emit(item="train_coarse_dev iteration", rows=rows, wall_ms_off=t[0], wall_ms_on=t[1], speedup=round(t[0][0] / t[1][0], 2))
+                    scratch.close()
+                    dK = train_codebooks(eng, part.residuals(Xr[:20_000], dassign[:20_000]), 3) if d == D else None
+                    if dK is not None:
+                        enc = dict(engine=eng, ilsiters=[2], icmiter=2, npert=4, randord=True, seed=6)
+
+                        def build():
+                            ms, ix = wall(lambda: lsq.build_ivf_residual_index(Xr, part, dK, M, **enc))
+                            ix.close()
+                            return ms
+
+                        t = legs(build)
+                        emit(item="build_ivf_residual_index", rows=rows, wall_ms_off=t[0], wall_ms_on=t[1], speedup=round(t[0][0] / t[1][0], 2))
+    out.close()
+
+
 if __name__ == "__main__":
-    a = [int(x) for x in sys.argv[1:3]] + [1_000_000, 1024][len(sys.argv) - 1:]
-    main(*a)
+    if "--mfma" in sys.argv:
+        a = [int(x) for x in sys.argv[2:6]] + [1_000_000, 1024, D, 1][len(sys.argv) - 2:]
+        mfma_main(*a)
+    else:
+        a = [int(x) for x in sys.argv[1:3]] + [1_000_000, 1024][len(sys.argv) - 1:]
+        main(*a)
