@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LSQ_VERSION 3300
+#define LSQ_VERSION 3400
 
 #if defined(__GNUC__)
 #define LSQ_API __attribute__((visibility("default")))
@@ -1268,6 +1268,43 @@ LSQ_API int lsq_index_knn_labelled(lsq_index *ix, float *dists, int *ids, const 
                                    const uint32_t *q_want, int nq, int ldq, int nn, int id_base, int flags, int on_device);
 LSQ_API int lsq_index_get_label_knn_info(lsq_index *ix, lsq_label_knn_info *out);
 LSQ_API int lsq_label_knn_geometry(int64_t n, int d, int nn, int nq, int flags, lsq_label_geometry_info *out);
+
+/* ---- (3v) labelled range search: every row within a radius, a row predicate PER QUERY (csrc/lsq_labelrange.hip; since v3400) ------------------------------
+ * THE REFERENCE HAS NO COUNTERPART.  CONTRACT (Identity LR).  lsq_index_range_search (3m) with the predicate of (3t) per query: row r is a candidate of query
+ * q iff (label[r] & q_mask[q]) == q_want[q] -- or, with LSQ_LABEL_ANY, iff (label[r] & q_mask[q]) != 0 -- AND the filter in force (tombstones included) allows
+ * r.  FOR EVERY QUERY lims, distances and ids equal, BIT FOR BIT, what lsq_index_range_search returns for that single query on the same index after
+ * lsq_index_set_filter(its candidates): the same tables, the same add order, the norm last, then the optional coarse add; dist <= r in IEEE (a NaN on either
+ * side is out); (dist, id) order; a CSR of exactly the answer's length.  Plain and packed rows, nprobe == 0 (every row) and nprobe >= 1 (the probed lists,
+ * LSQ_IVF_ADD_COARSE), host and device forms need no rule of their own.
+ *   how         two walks of the same rows, as in (3m), but the counts are kept per CELL: a cell is (query, range of rows_per_cell rows) on the every-row
+ *               road and (query, every cells_per_query-th probed list in rank order) on the list road, and one block owns a cell.  A block of 256 threads
+ *               serves queries_per_block queries (4 at m <= 8, 2 above; 1 on the list road) from one read of the rows: code words, norm, label and filter
+ *               bit once per row, the predicate per (row, query), the table gathered only where a lane of the wave passes.  COUNT stores one integer per
+ *               cell (no global atomic); a device scan over the cells in (query, cell) order gives every cell's offset and lims, of which only lims comes
+ *               back; FILL skips a block whose cells are all empty before it stages a table and writes each record at its cell's exact offset (a cursor
+ *               per (block, query) in LDS: no global cursor).  The sort and the hand-out are (3m)'s.
+ *   the result  is HELD as (3m)'s: lsq_index_range_fetch, the drop rules and lsq_index_get_range_info (queries, results, max_per_query, batches, road,
+ *               held_bytes; rows_walked = allowed_pairs) serve it unchanged.  Option "range_batch" applies.  The scratch is 12 bytes per cell.
+ *   refused     LSQ_EINVAL with nothing launched and a held result left as it was: no labels in force; everything lsq_index_range_search refuses; a
+ *               label_flags bit other than LSQ_LABEL_ANY; a null q_mask or q_want; more than 2^31 - 1 cells in one call.  nq == 0: LSQ_OK, lims[0] = 0.
+ *   lsq_index_get_label_range_info   the account of the last labelled range search.  The counters are sums of integers: the same on every call. */
+typedef struct lsq_label_range_info {
+    int64_t queries;
+    int64_t queries_per_block;           /* QB */
+    int64_t cells_per_query;             /* every row: ceil(n / rows_per_cell); lists: blocks that share a query's probed lists */
+    int64_t rows_per_cell;               /* every row: the cell length (a constant of the unit); lists: 0 (a cell is a set of lists) */
+    int64_t cells, cells_nonempty;       /* queries x cells_per_query; those that hold a result */
+    int64_t fill_blocks_launched, fill_blocks_skipped;      /* FILL: blocks launched; those that left before staging a table (every cell empty) */
+    int64_t allowed_pairs;               /* SUM over queries of the rows walked that passed predicate and filter */
+    int64_t results;                     /* = lims[nq] */
+    int64_t batches;                     /* fill batches launched */
+    double coarse_ms, lut_ms, count_ms, plan_ms, fill_ms, sort_ms;      /* with option "profile" = 1; sort_ms includes the hand-out */
+} lsq_label_range_info;
+/* the arguments of lsq_index_range_search, then q_mask / q_want [nq] uint32 (host, or device with on_device) and label_flags (LSQ_LABEL_ANY or 0) */
+LSQ_API int lsq_index_range_search_labelled(lsq_index *ix, int64_t *lims, const float *q_scan, const float *q_coarse, const float *radius,
+                                            const uint32_t *q_mask, const uint32_t *q_want, int nq, int ldq, int nprobe, int flags, int label_flags,
+                                            int on_device);
+LSQ_API int lsq_index_get_label_range_info(lsq_index *ix, lsq_label_range_info *out);
 
 /* quantize_norms(B, C, cbnorms) -> dbnormsB     src/utils.jl:6-31: per database vector the squared norm of its reconstruction
  * (f32; codebooks, then dimensions, ascending) and the 1-based index of the nearest of the `ncb` (<= 256) scalar centroids, first minimum of

@@ -136,6 +136,13 @@ class LabelKnnInfo(_Struct):
                 ("skipped_wave_steps", C.c_int64), ("batches", C.c_int64), ("scan_ms", C.c_double), ("merge_ms", C.c_double)]
 
 
+class LabelRangeInfo(_Struct):
+    _fields_ = [("queries", C.c_int64), ("queries_per_block", C.c_int64), ("cells_per_query", C.c_int64), ("rows_per_cell", C.c_int64), ("cells", C.c_int64),
+                ("cells_nonempty", C.c_int64), ("fill_blocks_launched", C.c_int64), ("fill_blocks_skipped", C.c_int64), ("allowed_pairs", C.c_int64),
+                ("results", C.c_int64), ("batches", C.c_int64), ("coarse_ms", C.c_double), ("lut_ms", C.c_double), ("count_ms", C.c_double),
+                ("plan_ms", C.c_double), ("fill_ms", C.c_double), ("sort_ms", C.c_double)]
+
+
 class IndexPackedDesc(_Struct):
     _fields_ = [("n", C.c_int64), ("d", C.c_int), ("m", C.c_int), ("h", C.c_int), ("codes", C.c_void_p), ("norm_codes", C.c_void_p),
                 ("cbnorms", C.c_void_p), ("ncb", C.c_int), ("codebooks", C.c_void_p), ("base", C.c_void_p), ("base_u8", C.c_int), ("ldb", C.c_int),
@@ -380,6 +387,9 @@ SIGNATURES = {
     "lsq_index_range_fetch": (_i, [_vp, _vp, _vp, _i64, _i]),
     "lsq_index_get_range_info": (_i, [_vp, C.POINTER(RangeInfo)]),
     "lsq_range_search_cpu": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
+    # labelled range search (since v3400): range search with a predicate per query, held like the plain call's result, and its account
+    "lsq_index_range_search_labelled": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    "lsq_index_get_label_range_info": (_i, [_vp, C.POINTER(LabelRangeInfo)]),
     # decode and search by stored row (since v2400)
     "lsq_reconstruct_cpu": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
     "lsq_index_reconstruct": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i]),
@@ -450,7 +460,7 @@ SIGNATURES = {
     "lsq_synth_codebooks_dev": (_i, [_vp, _u64, _i, _i, _i, _vp]),
 }
 
-MIN_VERSION = 3300   # the version floor: the oldest library that exports every symbol above with these structs
+MIN_VERSION = 3400  # the version floor: the oldest library that exports every symbol above with these structs
 
 _libs = {}
 

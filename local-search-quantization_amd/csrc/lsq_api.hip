@@ -637,6 +637,7 @@ struct lsq_index {
     lsq_label_state *labels = nullptr;                 // labelled search (lsq_label.hip): the row labels, owned copies, and its scratch; null until lsq_index_set_labels
     lsq_labelknn_state *label_knn = nullptr;           // labelled exact k-NN (lsq_labelknn.hip): the scratch of its calls; null until the first lsq_index_knn_labelled
     lsq_label_knn_info lknn{};                         // ... and the account of the last one
+    lsq_labelrange_state *label_range = nullptr;       // labelled range search (lsq_labelrange.hip): its scratch and account; the result is held in `range`
 };
 
 // the filter as a scan over all rows takes it: nothing without one; else the compact road -- the ascending list of allowed rows -- where the measured rule
@@ -704,6 +705,7 @@ extern "C" int lsq_index_destroy(lsq_index *ix) {
     lsq_filter_free(ix->filter);
     lsq_label_free(ix->labels);
     lsq_labelknn_free(ix->label_knn);
+    lsq_labelrange_free(ix->label_range);
     ix->clock.release();
     delete ix;
     return LSQ_OK;
@@ -1385,6 +1387,71 @@ extern "C" int lsq_index_range_fetch(lsq_index *ix, float *dists, int *ids, int6
 extern "C" int lsq_index_get_range_info(lsq_index *ix, lsq_range_info *out) {
     if (!ix || !out) { lsq_set_error("lsq_index_get_range_info: null argument"); return LSQ_EINVAL; }
     lsq_range_get_info(ix->range, out);
+    return LSQ_OK;
+}
+
+// ---- labelled range search (lsq_labelrange.hip): lsq_index_range_search with the labelled searches' predicate per query; the result is held as its ----
+extern "C" int lsq_index_range_search_labelled(lsq_index *ix, int64_t *lims, const float *q_scan, const float *q_coarse, const float *radius,
+                                               const uint32_t *q_mask, const uint32_t *q_want, int nq, int ldq, int nprobe, int flags, int label_flags,
+                                               int on_device) {
+    const char *fn = "lsq_index_range_search_labelled";
+    if (!ix) { lsq_set_error("%s: null index", fn); return LSQ_EINVAL; }
+    const int nlist = lsq_ivf_nlist(ix->ivf);
+    if (const char *why = lsq_range_refusal(lims, q_scan, radius, ix->codes != nullptr, nlist, ix->d, nq, ldq, nprobe, flags)) {
+        lsq_set_error("%s: %s (nq=%d ldq=%d d=%d nprobe=%d nlist=%d flags=%d)", fn, why, nq, ldq, ix->d, nprobe, nlist, flags);
+        return LSQ_EINVAL;
+    }
+    int64_t nlab = 0;
+    const uint32_t *labels = lsq_label_device(ix->labels, &nlab);
+    if (!labels || nlab != ix->n) { lsq_set_error("%s: the index has no labels (call lsq_index_set_labels first; lsq_index_add / _compact drop them)", fn); return LSQ_EINVAL; }
+    if (label_flags & ~LSQ_LABEL_ANY) { lsq_set_error("%s: unknown label_flags %d", fn, label_flags); return LSQ_EINVAL; }
+    if (!q_mask || !q_want) { lsq_set_error("%s: null pointer", fn); return LSQ_EINVAL; }
+    if ((int64_t)nq * lsq_labelrange_cells(ix->n, nq, nprobe) > (int64_t)INT32_MAX) {
+        lsq_set_error("%s: %d queries x %lld cells exceed 2^31 - 1 cells in one call", fn, nq, (long long)lsq_labelrange_cells(ix->n, nq, nprobe));
+        return LSQ_EINVAL;
+    }
+    lsq_ctx *c = ix->ctx;
+    LSQ_TRY(use_device(c));
+    hipStream_t s = c->stream;
+    const bool dev = on_device != 0;
+    lsq_labelrange_call call;
+    lsq_range_call &rc = call.rc;
+    rc.nq = nq; rc.nprobe = nprobe; rc.flags = flags;
+    rc.budget = lsq_range_budget(c->range_batch);
+    rc.timed = c->profile ? 1 : 0;
+    rc.in = lsq_input(ix->codes, nullptr, ix->K, ix->norms, (int)ix->n, ix->m, ix->d);
+    if (ix->packed) { rc.in.packed = 1; rc.in.cstride = ix->m + 1; }      // rows with their norm byte; norms is the table
+    call.labels = labels; call.lab = ix->labels; call.q_mask = q_mask; call.q_want = q_want; call.any = (label_flags & LSQ_LABEL_ANY) ? 1 : 0;
+    if (lsq_filter_active(ix->filter)) {              // the filter's bits beside every row (the dense road: a predicate per query has no compact form)
+        const lsq_filter_view v = lsq_filter_get(ix->filter);
+        call.bits = nprobe == 0 ? v.bits : v.lbits;
+        if (!call.bits) { lsq_set_error("%s: the filter has no bits in layout order (a failed lsq_index_set_lists / _set_filter?)", fn); return LSQ_EINVAL; }
+        rc.road = 1;
+    }
+    if (nprobe >= 1) { rc.ivf = ix->ivf; rc.adc = &ix->adc; rc.coarse = c->search; }
+    std::vector<int64_t> staged;
+    int64_t *h_lims = lims;
+    if (dev) { staged.resize((size_t)nq + 1); h_lims = staged.data(); rc.lims_dev = lims; }
+    if (nq > 0) {
+        // the scan reads query rows d floats apart, the coarse search rows as they lie; the host form stages both, and the radii
+        IndexCall rows{ix, nq, dev};
+        const float *dqs = nullptr, *dqc = nullptr, *drad = nullptr;
+        int64_t ld = 0, ldc = 0, ldr = 0;
+        LSQ_TRY(rows.rows(ix->s_qscan, q_scan, sizeof(float), ldq, ix->d, true, !dev || ldq != ix->d, &dqs, &ld));
+        if (nprobe >= 1) LSQ_TRY(rows.rows(ix->s_qcoarse, q_coarse ? q_coarse : q_scan, sizeof(float), ldq, ix->d, false, !dev, &dqc, &ldc));
+        LSQ_TRY(rows.rows(ix->s_radius, radius, sizeof(float), 1, 1, false, !dev, &drad, &ldr));
+        rc.in.Q = dqs; rc.in.qstride = ix->d;
+        rc.q_coarse = dqc; rc.ldc = ldc; rc.radius = drad;
+    }
+    lsq_filter_note_road(ix->filter, rc.road);
+    LSQ_TRY(lsq_labelrange_search(s, &ix->range, &ix->label_range, call, h_lims));
+    ix->stats.queries += nq;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_index_get_label_range_info(lsq_index *ix, lsq_label_range_info *out) {
+    if (!ix || !out) { lsq_set_error("lsq_index_get_label_range_info: null argument"); return LSQ_EINVAL; }
+    lsq_labelrange_get_info(ix->label_range, out);
     return LSQ_OK;
 }
 

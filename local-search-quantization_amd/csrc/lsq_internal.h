@@ -536,6 +536,38 @@ struct lsq_range_call {
 // h_lims [nq + 1]: HOST.  Drops the former held result first; on success the new one is held.  Waits for the device
 int lsq_range_search(hipStream_t s, lsq_range_state **st, const lsq_range_call &call, int64_t *h_lims);
 int lsq_range_fetch(hipStream_t s, lsq_range_state *st, float *dists, int *ids, int64_t capacity, int on_device);
+// what the index holds between range searches, and a call's scratch.  Said here for the other producer of a held result (lsq_labelrange.hip), which fills
+// lims (device, [nq + 1]), rec_a (a batch's records) and the held buffers' sizes itself and leaves the sort and the hand-out to lsq_range_select_batch
+struct lsq_range_state {
+    DevBuf held_d, held_i;                           // the held result: dists / ids [results]
+    bool held = false;
+    int64_t held_total = 0;
+    DevBuf lut, count, cursor, lims, rows, rec_a, rec_b, seg, tmp;      // a call's scratch
+    PhaseClock<2> clock;
+    lsq_range_info info{};
+};
+// the sort of a batch's segments (queries qa .. qb - 1 of st->lims, `records` of them in st->rec_a, the first at entry out_base of the result) and the
+// hand-out into the held buffers
+int lsq_range_select_batch(lsq_range_state *st, hipStream_t s, int qa, int qb, int64_t out_base, int64_t records, int idbits);
+
+// ---- labelled range search (lsq_labelrange.hip): counts per (query, row range) cell, exact offsets, a fill that skips empty cells --------
+struct lsq_labelrange_state;                         // the scratch of its calls and the account of the last one, owned by the index
+void lsq_labelrange_free(lsq_labelrange_state *st);
+void lsq_labelrange_get_info(const lsq_labelrange_state *st, lsq_label_range_info *out);
+// one call, every pointer but q_mask / q_want (host or device) a device pointer; the fields of lsq_range_call mean what they mean there (in.filter_rows is
+// not read: a predicate per query has no compact road; bits: the filter in force by original row, or -- list road -- in layout order, or null).  labels: by
+// original row; the list road reads lab's copy in layout order (lsq_label_layout)
+struct lsq_labelrange_call {
+    lsq_range_call rc;
+    const uint32_t *labels = nullptr, *bits = nullptr, *q_mask = nullptr, *q_want = nullptr;
+    lsq_label_state *lab = nullptr;
+    int any = 0;
+};
+int64_t lsq_labelrange_cells(int64_t n, int nq, int nprobe);      // cells per query of a call of this shape
+// h_lims [nq + 1]: HOST.  Drops the former held result of *range first; on success the new one is held there.  Waits for the device
+int lsq_labelrange_search(hipStream_t s, lsq_range_state **range, lsq_labelrange_state **st, const lsq_labelrange_call &call, int64_t *h_lims);
+// the labels in the order of the inverted layout (ids [n]: the layout's original ids), built at the first call after lsq_label_set / _drop_layout
+int lsq_label_layout(hipStream_t s, lsq_label_state *st, const int *ids, int64_t n, const uint32_t **out);
 
 // ---- row filters on a resident index (lsq_filter.hip): the set of allowed rows as the scans read it ---------------------------------------------------
 struct lsq_filter_state;

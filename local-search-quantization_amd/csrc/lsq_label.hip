@@ -303,6 +303,18 @@ int lsq_label_set(hipStream_t s, lsq_label_state **pst, const uint32_t *labels, 
     return LSQ_OK;
 }
 
+// the labels in layout order, once per (labels, lists)
+int lsq_label_layout(hipStream_t s, lsq_label_state *st, const int *ids, int64_t n, const uint32_t **out) {
+    if (!st->layout_valid) {
+        LSQ_TRY(st->layout.ensure(sizeof(uint32_t) * (size_t)n));
+        hipLaunchKernelGGL(label_layout_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, st->labels.as<uint32_t>(), ids, n, st->layout.as<uint32_t>());
+        LSQ_HIP(hipGetLastError());
+        st->layout_valid = true;
+    }
+    *out = st->layout.as<uint32_t>();
+    return LSQ_OK;
+}
+
 namespace {
 
 // one chunk of queries on either road: batches of tables, the scan, the merge where several blocks share a query
@@ -390,17 +402,11 @@ int lsq_label_search(hipStream_t s, lsq_label_state *st, const lsq_label_call &c
             double coarse_ms = 0.0;
             LSQ_TRY(lsq_ivf_coarse(s, c.ivf, c.adc, c.q_coarse + c0 * c.ldc, c.ldc, cn, c.nprobe, c.coarse, c.timed, &pr, &coarse_ms));
             st->info.coarse_ms += coarse_ms;
-            if (!st->layout_valid) {                                 // the labels in layout order, once per (labels, lists)
-                LSQ_TRY(st->layout.ensure(sizeof(uint32_t) * (size_t)pr.n));
-                hipLaunchKernelGGL(label_layout_kernel, dim3((unsigned)((pr.n + 255) / 256)), dim3(256), 0, s, st->labels.as<uint32_t>(), pr.ids, pr.n,
-                                   st->layout.as<uint32_t>());
-                LSQ_HIP(hipGetLastError());
-                st->layout_valid = true;
-                st->info.layout_builds += 1;
-            }
+            if (!st->layout_valid) st->info.layout_builds += 1;
             LabelScan b = a;
+            LSQ_TRY(lsq_label_layout(s, st, pr.ids, pr.n, &b.labels));
             b.codes = pr.codes; b.norms = pr.norms; b.ids = pr.ids; b.off = pr.off; b.probe = pr.probe; b.coarse = pr.coarse;
-            b.labels = st->layout.as<uint32_t>(); b.bits = c.bits; b.nprobe = c.nprobe; b.add = (c.ivf_flags & LSQ_IVF_ADD_COARSE) ? 1 : 0;
+            b.bits = c.bits; b.nprobe = c.nprobe; b.add = (c.ivf_flags & LSQ_IVF_ADD_COARSE) ? 1 : 0;
             b.qmask = st->qmask.as<uint32_t>() + c0; b.qwant = st->qwant.as<uint32_t>() + c0; b.dists = c.dists + c0 * nn; b.out_ids = c.ids + c0 * nn;
             lsq_search_input in = c.in;
             in.Q = static_cast<const float *>(c.in.Q) + c0 * c.in.qstride;

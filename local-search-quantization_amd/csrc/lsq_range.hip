@@ -458,15 +458,7 @@ int launch_ivf(hipStream_t s, const RangeIvf &a, int slots, bool packed) {
 
 }  // namespace
 
-struct lsq_range_state {
-    DevBuf held_d, held_i;                           // the held result: dists / ids [results]
-    bool held = false;
-    int64_t held_total = 0;
-    DevBuf lut, count, cursor, lims, rows, rec_a, rec_b, seg, tmp;      // a call's scratch
-    PhaseClock<2> clock;
-    lsq_range_info info{};
-};
-
+// (struct lsq_range_state: lsq_internal.h -- lsq_labelrange.hip holds its result in it too)
 void lsq_range_drop(lsq_range_state *st) {
     if (!st) return;
     st->held_d.release(); st->held_i.release();
@@ -499,8 +491,10 @@ struct Lap {
     }
 };
 
+}  // namespace
+
 // the sort of a batch's segments and the hand-out into the held buffers
-int select_batch(lsq_range_state *st, hipStream_t s, int qa, int qb, int64_t out_base, int64_t records, int idbits) {
+int lsq_range_select_batch(lsq_range_state *st, hipStream_t s, int qa, int qb, int64_t out_base, int64_t records, int idbits) {
     const int segs = qb - qa, end_bit = 32 + idbits;
     const uint64_t *in = st->rec_a.as<uint64_t>();
     uint64_t *out = st->rec_b.as<uint64_t>();
@@ -524,8 +518,6 @@ int select_batch(lsq_range_state *st, hipStream_t s, int qa, int qb, int64_t out
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }
-
-}  // namespace
 
 int lsq_range_search(hipStream_t s, lsq_range_state **pst, const lsq_range_call &call, int64_t *h_lims) {
     if (!*pst) *pst = new lsq_range_state();
@@ -644,7 +636,7 @@ int lsq_range_search(hipStream_t s, lsq_range_state **pst, const lsq_range_call 
                 }
                 LSQ_TRY(lap.end(&st->info.fill_ms));
                 LSQ_TRY(lap.begin());
-                LSQ_TRY(select_batch(st, s, (int)qa, (int)qb, out_base, records, idbits));
+                LSQ_TRY(lsq_range_select_batch(st, s, (int)qa, (int)qb, out_base, records, idbits));
                 LSQ_TRY(lap.end(&st->info.sort_ms));
                 st->info.batches += 1;
             }

@@ -971,13 +971,18 @@ class Index(_Handle):
                         int(shortlist), int(k), fl, lf, int(self._dev), h=self._h)
         return dists, ids
 
-    def range_search(self, Q_scan, radius, nprobe=0, Q_coarse=None, add_coarse=False):
+    def range_search(self, Q_scan, radius, nprobe=0, Q_coarse=None, add_coarse=False, where=None, any_of=False):
         """Every candidate row within `radius` of each query: radius a scalar or (nq,) float32, compared as dist <= radius (a NaN on either side returns
         nothing).  nprobe=0: every row; nprobe>=1: the rows of the query's nprobe nearest lists, chosen and (add_coarse) measured as search_ivf does.
         Under a filter: the allowed rows alone.  The distances are search()'s / search_ivf()'s own bits, so a query's result is the longest prefix
         within the radius of the ranking those return for k = all candidate rows.
+        where=(mask, want), any_of: search()'s predicate per query over the labels of set_labels, on top of a filter in force; each query's segment is what
+        set_filter(its candidates) and a one-query range_search would return, bit for bit.  where=None: exactly the plain call.
         -> lims (nq+1,) int64, dists (lims[-1],) float32, ids (lims[-1],) int32 1-BASED: query q's results are entries lims[q] .. lims[q+1]-1, ascending by
-        (dist, id); numpy on an Engine.index, torch tensors on an Engine.index_dev   [lsq_index_range_search, lsq_index_range_fetch]"""
+        (dist, id); numpy on an Engine.index, torch tensors on an Engine.index_dev
+        [lsq_index_range_search, lsq_index_range_search_labelled, lsq_index_range_fetch]"""
+        if where is None and any_of:
+            raise ValueError("any_of needs where=(mask, want)")
         side, p = self._side, self._side.ptr
         Qs = side.take(Q_scan, _F32, "Q_scan")
         Qc = Qs if Q_coarse is None else side.take(Q_coarse, _F32, "Q_coarse")
@@ -992,7 +997,14 @@ class Index(_Handle):
         spare = side.new((1,), _F32, Qs)                # nq == 0: an empty array still names one
         qs, qc, rd = (p(a) if nq else p(spare) for a in (Qs, Qc, rad))
         fl = _lib.IVF_ADD_COARSE if add_coarse else 0
-        self._eng._call(side, "lsq_index_range_search", p(lims), qs, qc if int(nprobe) else None, rd, nq, self.d, int(nprobe), fl, int(self._dev), h=self._h)
+        if where is None:
+            self._eng._call(side, "lsq_index_range_search", p(lims), qs, qc if int(nprobe) else None, rd, nq, self.d, int(nprobe), fl, int(self._dev), h=self._h)
+        else:
+            mask, want = self._where(where, nq)
+            spare_w = side.new((1,), _I32, Qs)
+            qm, qw = (p(a) if nq else p(spare_w) for a in (mask, want))
+            self._eng._call(side, "lsq_index_range_search_labelled", p(lims), qs, qc if int(nprobe) else None, rd, qm, qw, nq, self.d, int(nprobe), fl,
+                            _lib.LABEL_ANY if any_of else 0, int(self._dev), h=self._h)
         total = int(self.range_info()["results"])
         dists, ids = side.new((total,), _F32, Qs), side.new((total,), _I32, Qs)
         self._eng._call(side, "lsq_index_range_fetch", p(dists) if total else None, p(ids) if total else None, total, int(self._dev), h=self._h)
@@ -1002,6 +1014,12 @@ class Index(_Handle):
         """what the last range_search call did: queries, rows_walked, results, max_per_query, batches, road (0 unfiltered, 1 dense, 2 compact), held_bytes,
         coarse_ms / lut_ms / count_ms / fill_ms / sort_ms (with profile=True)"""
         return self._info("lsq_index_get_range_info", _lib.RangeInfo)
+
+    def label_range_info(self):
+        """what the last range_search(where=) call did: queries, queries_per_block, cells_per_query, rows_per_cell (0 with nprobe >= 1: a cell is a set of
+        lists), cells, cells_nonempty, fill_blocks_launched, fill_blocks_skipped (blocks of the second walk that left before staging a table), allowed_pairs,
+        results, batches, coarse_ms / lut_ms / count_ms / plan_ms / fill_ms / sort_ms (with profile=True)   [lsq_index_get_label_range_info]"""
+        return self._info("lsq_index_get_label_range_info", _lib.LabelRangeInfo)
 
     def ivf_info(self):
         """what the last search_ivf call did: queries, probed_rows, records, threshold_queries, fallback_queries, batches, batch_queries,
